@@ -1,6 +1,7 @@
 """bench.py -- impressions scored / sec on MI355X for LIME's candidate-scoring path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2b|cfg2a|cfg1|cfg3|cfg5|train2b|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2b|cfg2a|cfg1|cfg3|cfg5|train2b|...] [--full]
+                    [--dump-outputs DIR]
 
 With ``--gpus N`` (N > 1) from a plain shell the script launches its N ranks itself: N fresh child processes, spawned
 BEFORE this process makes any GPU call, each with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set (what the reference does
@@ -15,12 +16,20 @@ title 32 + body 128, K = 1+4, 300-d, fp32.  Impression rows are independent, so 
 collective (weak scaling); the training workloads add the one exchange step of the path, the all-reduce of the flat
 gradient bucket.
 
-Rank 0 prints ONE JSON line: metric / value / unit ... (value = exactly K timed steps between two barriers), plus
+Rank 0 prints ONE JSON line: metric / value / unit / ms_per_step ... (value = exactly K timed steps between two barriers,
+after W warm-up steps, the first of which captures the HIP graph / builds the buckets).  A plain run measures nothing else;
+its other fields are arithmetic on that time and the batches' shapes.
+``--dump-outputs DIR`` also writes what the last timed step handed its caller as float32 .npy files (see dump_outputs); the
+inputs are seeded, so two builds given the same arguments can be compared output for output.
+
+With ``--full`` the line also holds
+  "dense"           (scoring) the same K steps with the repetition shortcuts off (LIME_DENSE_TOKENS=1);
   "roofline"        the dominant kernel: ALGORITHMIC FLOPs per launch (2 m n k on the unpadded problem: in_proj counts its
                     900 useful columns, not the 960 the kernel computes) / average launch duration from HIP events recorded
                     on the launch stream, against the 157.3 TFLOP/s fp32-matrix peak of MI355X_MICROARCH.md; "frac_padded"
                     counts the padded columns as well; "traffic" is NOT measured in this run -- it is the PMC figure of the
                     rocprofv3 pass named in "traffic_source";
+  "gather"          (scoring, CROWN) the embedding gather against the HBM roofline;
   "sustained"       the same step over a >= 2 s region (>= 100 steps), batches rotating;
   "value_with_h2d"  the same K steps with the 26 input tensors copied from pinned host memory inside every step
                     (trainer.py:93-118, util.py:94);
@@ -82,6 +91,7 @@ WORKLOADS = {
 # (workload, steps, warmup) run beside the default line so that the driver's own run times them
 ALSO = (('cfg2a', 100, 10), ('cfg3', 30, 5), ('cfg5', 3, 1), ('train2b', 30, 5), ('train2b_dropout', 10, 3), ('train4', 8, 2))
 N_BATCHES = 4           # distinct resident batches a scoring run rotates through
+DUMP_MAX_PARAMS = 8 << 20   # --dump-outputs: at most this many parameter values of a training step (32 MB of float32)
 
 
 def flops_per_impression(cfg, N, per_candidate_user_side=False):
@@ -227,6 +237,23 @@ def timed(run, steps, warmup, barrier, step=None):
         out = step()
     barrier()
     return time.perf_counter() - t0, out
+
+
+def dump_outputs(run, out, directory):
+    """What the last timed step handed its caller, as float32 DIR/<name>.npy: the logits of a scoring step ([B, K]), or the
+    loss of a training step and the parameters it left in the flat bucket (every stride-th value once the bucket holds more
+    than DUMP_MAX_PARAMS: the word embedding alone is 15 M).  Called right after the timed region, before anything else
+    replays the graph or updates the parameters."""
+    import numpy as np
+    if run.train:
+        flat = run.ts.flat
+        stride = -(-flat.numel() // DUMP_MAX_PARAMS)
+        arrays = {'loss': out.reshape(1), 'params': flat[::stride]}
+    else:
+        arrays = {'logits': out}
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def kernel_profile(run, steps):
@@ -381,8 +408,10 @@ def cpu_baseline(run, logits, first_loss):
                       % (n_timed, nb, B, n_warm), 'max_rel_err_gpu_vs_cpu': err}
 
 
-def bench_workload(name, steps, warmup, rank, world, dist, D, args, full=True):
-    """Time one workload; returns the result dict on rank 0 (None elsewhere)."""
+def bench_workload(name, steps, warmup, rank, world, dist, D, args, full=True, extras=True, dump=None):
+    """Time one workload; returns the result dict on rank 0 (None elsewhere).  ``extras=False`` (a plain run): the timed steps
+    alone, without the dense pass, the instrumented per-kernel pass and everything ``full`` adds.  ``dump``: directory for
+    dump_outputs (rank 0)."""
     import torch
     run = Run(name, rank, world, overlap_streams=args.overlap_streams)
     cfg, B, N, train = run.cfg, run.B, run.N, run.train
@@ -398,6 +427,8 @@ def bench_workload(name, steps, warmup, rank, world, dist, D, args, full=True):
     dt, logits = timed(run, steps, max(0, warmup - 1), barrier)
     dt = D.max_over_ranks(dt, device='cuda')             # the slowest rank's time
     assert torch.isfinite(logits).all()
+    if dump is not None and rank == 0:
+        dump_outputs(run, logits, dump)
     sustained = h2d = None
     if full and name != 'cfg5':
         # >= 2 s and >= 100 steps, batches rotating (the K-step region above is what `value` reports)
@@ -415,7 +446,7 @@ def bench_workload(name, steps, warmup, rank, world, dist, D, args, full=True):
                'h2d_note': 'all 26 input tensors copied from pinned host memory with .cuda(non_blocking=True) inside every step'}
     dense = None
     fexec, pad_stats = executed_flops_per_impression(run)
-    if not train:
+    if extras and not train:
         # the same K steps with the repetition shortcuts OFF: every token of every slot through the encoder layer, as the
         # reference computes it (newsEncoders.py:311-321) -- what LIME_DENSE_TOKENS=1 runs
         from lime_cikm25_amd import newsEncoders
@@ -437,7 +468,7 @@ def bench_workload(name, steps, warmup, rank, world, dist, D, args, full=True):
                          'all-padding sequences once and runs in_proj over the live tokens -- same logits',
                  'max_abs_logit_difference_vs_default': float((dlogits - default_logits).abs().max()),
                  'mean_abs_logit': float(default_logits.abs().mean())}
-    by_kernel = kernel_profile(run, min(steps, 20) if full else min(steps, 5)) if rank == 0 else {}
+    by_kernel = kernel_profile(run, min(steps, 20) if full else min(steps, 5)) if (rank == 0 and extras) else {}
     if dist is not None:
         dist.barrier()
     if rank != 0:
@@ -460,13 +491,14 @@ def bench_workload(name, steps, warmup, rank, world, dist, D, args, full=True):
                    'distinct_batches': len(run.batches),
                    'streams': 'title / body / freshness / attention-weight branches forked' if args.overlap_streams else
                    'token encoders on one stream; freshness and attention-weight branches forked beside the head'},
-        'roofline': roofline(by_kernel, name, min(steps, 20) if full else min(steps, 5)),
-        'gather': gather_figures(run, by_kernel) if (rank == 0 and full and not train) else None,
         'end_to_end': {'flops_per_impression': fimp, 'achieved_tflops': round(value * fimp / 1e12, 2),
                        'frac_of_f32_mfma_peak': round(value * fimp / 1e12 / (PEAK_F32_MFMA_TFLOPS * world), 4)},
     }
-    if not train:
-        out['dense'] = dense
+    if extras:
+        out['roofline'] = roofline(by_kernel, name, min(steps, 20) if full else min(steps, 5))
+        out['gather'] = gather_figures(run, by_kernel) if (rank == 0 and full and not train) else None
+        if not train:
+            out['dense'] = dense
     if fexec is not None and not train:
         e2e = out['end_to_end']
         e2e['note'] = ('flops_per_impression is the DENSE algorithmic count of BASELINE.md section 3 (every slot, every token); the '
@@ -502,8 +534,13 @@ def main():
     ap.add_argument('--steps', type=int, default=500)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--workload', default='cfg2b', choices=sorted(WORKLOADS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-also', action='store_true', help='skip the other BASELINE configurations beside the default line')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the timed steps also measure the dense pass, the per-kernel roofline, the gather, the sustained and '
+                         'H2D regions, the CPU baseline and (default workload) the other BASELINE configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as float32 DIR/<name>.npy (rank 0)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-also', action='store_true', help='with --full: skip the other BASELINE configurations beside the default line')
     ap.add_argument('--plain', action='store_true',
                     help='only the warm-up and the K timed steps of the default path (for rocprofv3 --pmc / --kernel-trace passes: no dense '
                          'run, no sustained / H2D regions, no instrumented pass, no CPU baseline)')
@@ -536,12 +573,15 @@ def main():
     if args.plain:
         run = Run(args.workload, rank, world)
         sync = torch.cuda.synchronize
-        dt, _ = timed(run, args.steps, args.warmup, sync)
+        dt, out = timed(run, args.steps, args.warmup, sync)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(run, out, args.dump_outputs)
         print(json.dumps({'workload': args.workload, 'steps': args.steps, 'ms_per_step': round(dt / args.steps * 1e3, 4),
                           'value': round(run.B * args.steps / dt, 2)}), flush=True)
         return
-    res = bench_workload(args.workload, args.steps, args.warmup, rank, world, dist, D, args, full=True)
-    if rank == 0 and world == 1 and args.workload == 'cfg2b' and not args.no_also:
+    res = bench_workload(args.workload, args.steps, args.warmup, rank, world, dist, D, args, full=args.full, extras=args.full,
+                         dump=args.dump_outputs)
+    if args.full and rank == 0 and world == 1 and args.workload == 'cfg2b' and not args.no_also:
         also = {}
         for name, steps, warmup in ALSO:
             try:

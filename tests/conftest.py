@@ -16,7 +16,7 @@ def pytest_configure(config):
 def pytest_collection_modifyitems(config, items):
     """The multi-process GPU tests start child processes; they run FIRST, while this process has not initialised the GPU yet
     (a process that holds the device must not fork + exec on the GPU box)."""
-    items.sort(key=lambda it: 0 if 'test_multirank_gpu' in it.nodeid else 1)
+    items.sort(key=lambda it: 0 if ('test_multirank_gpu' in it.nodeid or 'test_bench_gpu' in it.nodeid) else 1)
 
 
 @pytest.fixture(scope='session')

@@ -58,7 +58,7 @@ def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2 --workload train2b` from a plain shell (no torchrun): rc 0, one JSON line, n_gpus = 2."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', 'train2b', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline'], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors='replace')[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
     assert len(lines) == 1

@@ -7,7 +7,7 @@ R=${1:-r03}
 O=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T0=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench.json 2> $O/${R}_bench.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${R}_bench.json 2> $O/${R}_bench.err
 echo "bench.py wall seconds: $(( $(date +%s) - T0 ))" | tee $O/${R}_bench_time.txt
 prof() {   # name steps extra-args...
     local name=$1 steps=$2; shift 2
