@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 7
+#define LIME_ABI_VERSION 8
 
 typedef enum {
     LIME_OK = 0,
@@ -199,6 +199,36 @@ int lime_encoder_ffn_bf16(const lime_ffn_bf16_args* args, void* stream);
 int64_t lime_ffn_pack_bf16_size(int32_t F, int32_t which);
 int lime_ffn_pack_bf16(const float* w1, int64_t ldw1, const float* b1, const float* w2, int64_t ldw2, int32_t E, int32_t F,
                        uint16_t* w1p, uint16_t* w2p, void* stream);
+
+/*
+ * lime_encoder_ffn_sp: the fp32 feed-forward half of an encoder layer in one launch, split products on the bf16 matrix cores
+ * (three bf16 terms per fp32 operand, six MFMAs per block: fp32-level products, as lime_linear_f32's split-product kernel):
+ *     y = LayerNorm(x + W2 relu(W1 x + b1) + b2)          out = y (fp32 rows [M, ldo]), or with pool32 the means of 32-row blocks
+ * x: fp32 [M, ldx], 16-byte aligned rows.  w1p / w2p: the weights as lime_ffn_pack_sp lays them out.  The hidden state stays in
+ * registers.  Only the E real columns of out are written.  Built for E <= 304, E % 4 == 0 and F a multiple of 128 up to 4096;
+ * anything else returns LIME_ERR_UNSUPPORTED (use lime_linear_f32 twice).  m_dev: optional device row count, as in lime_linear_args.
+ */
+typedef struct {
+    const float* x;       int64_t ldx;
+    const uint16_t* w1p;                    /* lime_ffn_pack_sp's two outputs (opaque: the kernel's weight-ring slots, three bf16 */
+    const uint16_t* w2p;                    /* term images each, one contiguous block per slot); 16-byte aligned                  */
+    const float* b1;                        /* fp32 [F] */
+    const float* b2;                        /* fp32 [E] */
+    const float* ln_gamma; const float* ln_beta; float ln_eps;     /* fp32 [E] */
+    int32_t pool32;                         /* 1: out is [M / 32, ldo] (M % 32 == 0); 0: out is [M, ldo] */
+    float* out;           int64_t ldo;
+    int32_t M, E, F;
+    int32_t reserved;                       /* must be 0 */
+    const int32_t* m_dev;
+} lime_ffn_sp_args;
+
+int lime_encoder_ffn_sp(const lime_ffn_sp_args* args, void* stream);
+
+/* w1 fp32 [F, E] (ld ldw1), w2 fp32 [E, F] (ld ldw2) -> w1p, w2p: bf16 buffers of lime_ffn_pack_sp_size(F, 0) and (F, 1) elements
+ * (F * 960 and F * 912). */
+int64_t lime_ffn_pack_sp_size(int32_t F, int32_t which);
+int lime_ffn_pack_sp(const float* w1, int64_t ldw1, const float* w2, int64_t ldw2, int32_t E, int32_t F, uint16_t* w1p, uint16_t* w2p,
+                     void* stream);
 
 /*
  * lime_encoder_block_bf16: everything of an encoder layer behind the attention core in one launch

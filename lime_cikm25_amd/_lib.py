@@ -10,7 +10,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_ui
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblime_hip.so')
 
-ABI_VERSION = 7          # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
+ABI_VERSION = 8          # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
 LIME_ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'relu_grad': 4}
 
 
@@ -59,6 +59,23 @@ class FfnBf16Args(ctypes.Structure):
         ('x', c_void_p), ('ldx', c_int64),
         ('w1p', c_void_p),
         ('w2p', c_void_p),
+        ('b2', c_void_p),
+        ('ln_gamma', c_void_p), ('ln_beta', c_void_p), ('ln_eps', c_float),
+        ('pool32', c_int32),
+        ('out', c_void_p), ('ldo', c_int64),
+        ('M', c_int32), ('E', c_int32), ('F', c_int32),
+        ('reserved', c_int32),
+        ('m_dev', c_void_p),
+    ]
+
+
+class FfnSpArgs(ctypes.Structure):
+    """lime_ffn_sp_args of include/lime_hip.h (same field order)."""
+    _fields_ = [
+        ('x', c_void_p), ('ldx', c_int64),
+        ('w1p', c_void_p),
+        ('w2p', c_void_p),
+        ('b1', c_void_p),
         ('b2', c_void_p),
         ('ln_gamma', c_void_p), ('ln_beta', c_void_p), ('ln_eps', c_float),
         ('pool32', c_int32),
@@ -182,6 +199,9 @@ SIGNATURES = {
     'lime_encoder_ffn_bf16': (c_int32, [ctypes.POINTER(FfnBf16Args), c_void_p]),
     'lime_ffn_pack_bf16': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     'lime_encoder_block_bf16': (c_int32, [ctypes.POINTER(EncoderBlockBf16Args), c_void_p]),
+    'lime_encoder_ffn_sp': (c_int32, [ctypes.POINTER(FfnSpArgs), c_void_p]),
+    'lime_ffn_pack_sp': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    'lime_ffn_pack_sp_size': (c_int64, [c_int32, c_int32]),
     'lime_oproj_pack_bf16_size': (c_int64, []),
     'lime_oproj_pack_bf16': (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     'lime_inproj_bf16': (c_int32, [ctypes.POINTER(InprojBf16Args), c_void_p]),

@@ -497,9 +497,23 @@ def encode_tokens(ids, table, pe, transformer, nhead, pooled_out=None):
                             ln=ln1, ln_eps=layer.norm1.eps)
         else:
             x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, res=x, ln=ln1, ln_eps=layer.norm1.eps)
-        h = ops.linear(x1, layer.linear1.weight, layer.linear1.bias, act='relu')
         last = li == len(transformer.layers) - 1
-        if last and pooled_out is not None and transformer.norm is None and S % 32 == 0 and M * S >= 4096:
+        pool = last and pooled_out is not None and transformer.norm is None and S % 32 == 0 and M * S >= 4096
+        if _ffn_sp_applicable(layer, x1):
+            # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means) in one launch: the compacted path's kernel
+            w1p, w2p = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
+            ln2 = (layer.norm2.weight, layer.norm2.bias)
+            if pool:
+                direct = S == 32 and pooled_out.data_ptr() % 16 == 0 and pooled_out.stride(0) % 4 == 0
+                blocks = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, pool32=True,
+                                            out=pooled_out if direct else None)
+                if not direct:
+                    ops.mean_pool(blocks, M, S // 32, out=pooled_out)
+                return None
+            x = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps)
+            continue
+        h = ops.linear(x1, layer.linear1.weight, layer.linear1.bias, act='relu')
+        if pool:
             blocks = ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=(layer.norm2.weight, layer.norm2.bias),
                                 ln_eps=layer.norm2.eps, pool32=True, out=pooled_out if S == 32 else None)
             if S != 32:
@@ -563,6 +577,20 @@ def compact_prepare_many(encoders, table, nhead):
     return [(cmp, w_in, pew, qkv) for (cmp, w_in, _, qkv, _, _, _), pew in zip(parts, pews)]
 
 
+SP_FUSED_FFN = os.environ.get('LIME_SP_FUSED_FFN', '1') != '0'      # 0: the fp32 linear1 / linear2 as two lime_linear_f32 launches (A/B runs)
+
+
+def _ffn_sp_applicable(layer, x1):
+    """lime_encoder_ffn_sp takes the fp32 feed-forward half where lime_linear_f32 would run both GEMMs as split products: the split
+    GEMM on, E <= 304 (E % 4 == 0), F a multiple of 128 up to 4096, biases present, 16-byte rows, and enough 128-row blocks that
+    linear1 is not left to the mid-M kernel (lime_linear_f32's fill rule)."""
+    M, E = x1.shape
+    F = layer.linear1.out_features
+    return (SP_FUSED_FFN and ops.split_gemm_on() and E <= 304 and E % 4 == 0 and F % 128 == 0 and F <= 4096 and
+            layer.linear1.bias is not None and layer.linear2.bias is not None and x1.stride(1) == 1 and x1.stride(0) % 4 == 0 and
+            x1.data_ptr() % 16 == 0 and M >= 4096 and ((M + 127) // 128) * ((F + 255) // 256) >= 160)
+
+
 _IDENT = {}
 
 
@@ -602,6 +630,16 @@ def compact_run(prep, table, pe, transformer, nhead, pooled_out):
             attn = ops.token_attention_rows(qkv_l[:, :W], qkv_l[:, W:2 * W], qkv_l[:, 2 * W:], _identity_rows(cap, x.device), cmp.n_compact,
                                             M + 1, S, nhead, hd, 1.0 / math.sqrt(hd))
             x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, res=x, ln=ln1, ln_eps=layer.norm1.eps, m_dev=cmp.n_rows)
+        if _ffn_sp_applicable(layer, x1):
+            # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means of the last layer) in one launch
+            w1p, w2p = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
+            ln2 = (layer.norm2.weight, layer.norm2.bias)
+            if li + 1 < n_layers:
+                x = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, m_dev=cmp.n_rows)
+                continue
+            blocks = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, pool32=True,
+                                        m_dev=cmp.n_rows)                                              # [cap / 32, E] block means
+            break
         h = ops.linear(x1, layer.linear1.weight, layer.linear1.bias, act='relu', m_dev=cmp.n_rows)
         if li + 1 < n_layers:
             x = ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=(layer.norm2.weight, layer.norm2.bias),

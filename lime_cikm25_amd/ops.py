@@ -765,6 +765,69 @@ def ffn_pack_bf16(w1, b1, w2):
     return w1p, w2p
 
 
+def ffn_pack_sp(w1, w2):
+    """``lime_ffn_pack_sp``: linear1 / linear2 weights (fp32 [F, E], [E, F]) -> the split (three bf16 terms) operands of ``encoder_ffn_sp``."""
+    lib = _lib.load()
+    _mat(w1, 'w1')
+    _mat(w2, 'w2')
+    F, E = w1.shape
+    if tuple(w2.shape) != (E, F):
+        raise ValueError('w2 must be [%d, %d]' % (E, F))
+    w1p = torch.empty(int(lib.lime_ffn_pack_sp_size(F, 0)), dtype=torch.bfloat16, device=w1.device)
+    w2p = torch.empty(int(lib.lime_ffn_pack_sp_size(F, 1)), dtype=torch.bfloat16, device=w1.device)
+    check(lib.lime_ffn_pack_sp(_p(w1), _ld(w1), _p(w2), _ld(w2), E, F, _p(w1p), _p(w2p), _stream()), 'lime_ffn_pack_sp')
+    return w1p, w2p
+
+
+def encoder_ffn_sp(x, w1p, w2p, b1, b2, ln, ln_eps, pool32=False, m_dev=None, out=None):
+    """``lime_encoder_ffn_sp``: LayerNorm(x + W2 relu(W1 x + b1) + b2) in one launch, fp32-level split products; x fp32 [M, E].
+    pool32: [M / 32, E] means over 32-row blocks, else [M, E] rows (``out`` may be a strided view)."""
+    lib = _lib.load()
+    _mat(x, 'x')
+    _vec(w1p, 'w1p', dtype=torch.bfloat16)
+    _vec(w2p, 'w2p', dtype=torch.bfloat16)
+    M, E = x.shape
+    F = _vec(b1, 'b1').numel()
+    if w1p.numel() != int(lib.lime_ffn_pack_sp_size(F, 0)) or w2p.numel() != int(lib.lime_ffn_pack_sp_size(F, 1)):
+        raise ValueError('w1p / w2p must be the two buffers of ffn_pack_sp for F = %d' % F)
+    if pool32 and M % 32:
+        raise ValueError('pool32 needs M %% 32 == 0 (M = %d)' % M)
+    rows_out = M // 32 if pool32 else M
+    if out is None:
+        out = torch.empty((rows_out, E), dtype=torch.float32, device=x.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (rows_out, E):
+        raise ValueError('out must be [%d, %d]' % (rows_out, E))
+    args = _lib.FfnSpArgs()
+    args.x, args.ldx = x.data_ptr(), _ld(x)
+    args.w1p, args.w2p = w1p.data_ptr(), w2p.data_ptr()
+    args.b1 = b1.data_ptr()
+    args.b2 = _vec(b2, 'b2', E).data_ptr()
+    args.ln_gamma = _vec(ln[0], 'ln gamma', E).data_ptr()
+    args.ln_beta = _vec(ln[1], 'ln beta', E).data_ptr()
+    args.ln_eps = ln_eps
+    args.pool32 = 1 if pool32 else 0
+    args.out, args.ldo = out.data_ptr(), _ld(out)
+    args.M, args.E, args.F = M, E, F
+    if m_dev is not None:
+        args.m_dev = _vec(m_dev, 'm_dev', 1, dtype=torch.int32).data_ptr()
+    if PROFILE is not None:                        # bench.py: as ONE GEMM of the two layers' FLOPs: 2 M E (2 F)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(lib.lime_encoder_ffn_sp(ctypes.byref(args), _stream()), 'lime_encoder_ffn_sp')
+        e1.record()
+        m_run = M if m_dev is None else min(M, int(m_dev.item()))
+        PROFILE.append(('ffn_sp_kernel<%s>' % ('true' if pool32 else 'false'), m_run, 2 * F, E, 2 * F, e0, e1))
+        return out
+    check(lib.lime_encoder_ffn_sp(ctypes.byref(args), _stream()), 'lime_encoder_ffn_sp')
+    return out
+
+
+def split_gemm_on():
+    """True while lime_linear_f32 routes the big-M GEMMs through the split-product kernel (``set_split_gemm``)."""
+    return bool(_lib.load().lime_set_split_gemm(-1) & 1)
+
+
 def encoder_ffn_bf16(x, w1p, w2p, b2, ln, ln_eps, E, pool32=False, m_dev=None, out=None):
     """``lime_encoder_ffn_bf16``: LayerNorm(x + W2 relu(W1 x + b1) + b2) in one launch; x bf16 [M, 304] (E real columns).
     pool32: fp32 [M / 32, 304] means over 32-row blocks, else bf16 [M, 304]."""
