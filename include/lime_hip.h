@@ -760,6 +760,27 @@ int lime_cand_attn_weights_bwd_f32(const float* qp, const float* kp, const uint8
                                    int32_t B, int32_t N, int32_t H, int32_t D, int32_t n_head, float dropout_p, uint64_t seed,
                                    uint32_t site, void* stream);
 
+/* =====================================================================================================
+ * 1-D convolution over the tokens of a sequence (layers.py:98-135 Conv1D, the CNN content encoder newsEncoders.py:535-563) as a
+ * GEMM over a gathered window (csrc/conv_sp_f32.hip; split product, or exact-fp32 MFMA under lime_set_split_gemm(0)):
+ *   out[r, o] = (accumulate ? out[r, o] : 0) + act(bias[o] + sum_{j < window} sum_{c < C} A(r, j)[c] * w[o * ldw + j * C + c])
+ *   row r = token t = r % T of sequence r / T; A(r, j) = source row r + j - pad (pad = (window - 1) / 2), ZEROS when t + j - pad is
+ *   outside [0, T); source row q = a[ids[q] * lda ...] (a gathered table row) or a[q * lda ...] (ids == NULL).
+ * w is the nn.Conv1d weight permuted to [N, window, C].  window odd; C, lda, ldw multiples of 4, a and w 16-byte aligned; M % T == 0;
+ * act NONE or RELU; bias optional; m_dev: optional device row count (rows >= min(*m_dev, M) are left untouched).  The data gradient
+ * is this call with the dense dY as A and the taps reversed in w ([C, window, N], w[c, j, o] = W[o, c, window - 1 - j]). */
+int lime_conv1d_window_f32(const float* a, int64_t lda, const int32_t* ids, const float* w, int64_t ldw, const float* bias,
+                           float* out, int64_t ldc, int32_t M, int32_t N, int32_t C, int32_t T, int32_t window, int32_t act,
+                           int32_t accumulate, const int32_t* m_dev, void* stream);
+
+/* dw[o, j * C + c] (+)= sum_r dy[r, o] * A(r, j)[c] with the windowed operand of lime_conv1d_window_f32 (dw [N, window * C]).  Rows are
+ * split over workgroups, partial tiles in `workspace` (lime_conv1d_wgrad_workspace floats) summed in split order: bitwise
+ * reproducible.  N, C, ldy, lda multiples of 4; dy, a, workspace 16-byte aligned. */
+int64_t lime_conv1d_wgrad_workspace(int32_t M, int32_t N, int32_t C, int32_t window);
+int lime_conv1d_wgrad_f32(const float* dy, int64_t ldy, const float* a, int64_t lda, const int32_t* ids, float* dw, int64_t lddw,
+                          int32_t M, int32_t N, int32_t C, int32_t T, int32_t window, int32_t accumulate, float* workspace,
+                          int64_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

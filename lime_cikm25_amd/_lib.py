@@ -269,6 +269,12 @@ SIGNATURES = {
     'lime_cand_attn_weights_bwd_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                                  c_int32, c_int32, c_float, c_uint64, c_uint32, c_void_p]),
     'lime_nll_softmax_f32': (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    # CNN content encoder: windowed conv GEMM
+    'lime_conv1d_window_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                         c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'lime_conv1d_wgrad_workspace': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    'lime_conv1d_wgrad_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                        c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -48,6 +48,9 @@ _DEFAULTS = dict(
     isab_num_heads=4,                     # config.py:81
     alpha=0.0,                            # config.py:82
     beta=0.0,                             # config.py:83
+    cnn_method='naive',                   # config.py:86
+    cnn_kernel_num=400,                   # config.py:87
+    cnn_window_size=3,                    # config.py:88
     category_embedding_dim=50,            # config.py:91
     subCategory_embedding_dim=50,         # config.py:92
     user_embedding_dim=50,                # config.py:90

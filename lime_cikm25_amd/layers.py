@@ -141,3 +141,52 @@ class Attention(nn.Module):
         x = feature.reshape(n_seq * S, D)
         hidden = ops.linear(x, self.affine1.weight, self.affine1.bias, act='tanh')
         return ops.additive_pool(hidden, self.affine2.weight.view(-1), x, n_seq, S, mask=mask)
+
+
+class Conv1D(nn.Module):
+    """layers.py:98-135: parameter holder for the CNN content encoder's convolution (``conv`` for 'naive'; ``conv1`` .. ``conv3``, windows
+    1 / 3 / 5 and cnn_kernel_num / 3 outputs each, for 'group3'), nn.Conv1d default initialisation as the reference leaves it.  The
+    arithmetic is the windowed conv GEMM (ops.conv1d_window); ``forward`` is never used on the HIP path.
+
+    Refused, as the reference refuses or fails on them: 'group4' (the assert of :100), 'group5' (its padding concatenation of :131-134
+    fails on shape), an even window (output T - 1 long: the view / masked_fill of newsEncoders.py:557-559 fail), and 'group3' with a
+    kernel count that is not a multiple of 3 (:105).  Not in the reference: the kernels need multiples of 4 for the per-conv output
+    count (the weight gradient's dY rows and the data gradient's source rows are read 16 bytes at a time)."""
+
+    def __init__(self, cnn_method, in_channels, cnn_kernel_num, cnn_window_size):
+        super().__init__()
+        if cnn_method == 'group4':
+            raise ValueError("cnn_method 'group4': the reference's Conv1D asserts against it (layers.py:100)")
+        if cnn_method == 'group5':
+            raise NotImplementedError("cnn_method 'group5': the reference's padding concatenation fails on shape (layers.py:131-134)")
+        if cnn_method not in ('naive', 'group3'):
+            raise ValueError('unknown cnn_method %r' % (cnn_method,))
+        self.cnn_method = cnn_method
+        self.in_channels = in_channels
+        if cnn_method == 'naive':
+            if cnn_window_size <= 0 or cnn_window_size % 2 == 0:
+                raise ValueError('cnn_window_size %d: an even window makes the reference output T - 1 tokens long '
+                                 '(newsEncoders.py:557-559 fail)' % cnn_window_size)
+            per_conv = cnn_kernel_num
+            self.conv = nn.Conv1d(in_channels=in_channels, out_channels=cnn_kernel_num, kernel_size=cnn_window_size,
+                                  padding=(cnn_window_size - 1) // 2)
+        else:
+            if cnn_kernel_num % 3 != 0:
+                raise ValueError("cnn_method 'group3' needs cnn_kernel_num %% 3 == 0 (layers.py:105), got %d" % cnn_kernel_num)
+            per_conv = cnn_kernel_num // 3
+            self.conv1 = nn.Conv1d(in_channels=in_channels, out_channels=per_conv, kernel_size=1, padding=0)
+            self.conv2 = nn.Conv1d(in_channels=in_channels, out_channels=per_conv, kernel_size=3, padding=1)
+            self.conv3 = nn.Conv1d(in_channels=in_channels, out_channels=per_conv, kernel_size=5, padding=2)
+        if per_conv % 4 or in_channels % 4:
+            raise NotImplementedError('the windowed conv kernels need multiples of 4 for the outputs per convolution (%d) and the '
+                                      'input width (%d)' % (per_conv, in_channels))
+
+    def convs(self):
+        """[(nn.Conv1d, first output column)] in the reference's concatenation order."""
+        if self.cnn_method == 'naive':
+            return [(self.conv, 0)]
+        n = self.conv1.out_channels
+        return [(self.conv1, 0), (self.conv2, n), (self.conv3, 2 * n)]
+
+    def forward(self, feature):
+        raise NotImplementedError('Conv1D is a parameter holder: the CNN encoder runs ops.conv1d_window')

@@ -1,5 +1,5 @@
-"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN and MHSA
-(reference newsEncoders.py:38-161, 167-373, 566-595, 806-828).
+"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN and MHSA
+(reference newsEncoders.py:38-161, 167-373, 535-563, 566-595, 806-828).
 
 The modules keep the reference's attribute and parameter names, so ``state_dict()`` has the same
 183 keys and reference checkpoints load.  Standard torch containers
@@ -20,7 +20,7 @@ import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from . import ops
-from .layers import Attention, MultiHeadAttention
+from .layers import Attention, Conv1D, MultiHeadAttention
 
 # tokens encoded per pass of the token encoder: bounds the activation workspace (9.2 KB / token)
 MAX_TOKENS_PER_PASS = 4 * 1024 * 1024
@@ -1065,4 +1065,92 @@ class MHSA(NewsEncoder):
                               out=out[m0:m1, :F])                                                       # :592
         ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
                       emb_out=out[:, F:])                                                               # :594
+        return out
+
+
+_ROW_COUNTS = {}
+
+
+def _row_count(n, device):
+    """A device int32 holding n (the m_dev of a dense pass), one per (device, n), never written after its creation."""
+    key = (device.type, device.index, n)
+    t = _ROW_COUNTS.get(key)
+    if t is None:
+        t = _ROW_COUNTS[key] = torch.full((1,), n, dtype=torch.int32, device=device)
+    return t
+
+
+class CNN(NewsEncoder):
+    """newsEncoders.py:535-563: title-only 1-D convolution (layers.py:98-135, ReLU) + additive attention.  -> [B, n, cnn_kernel_num + 100].
+
+    The convolution is the windowed conv GEMM (csrc/conv_sp_f32.hip): word rows gathered straight into its A operand, zeros beyond the
+    title's ends, bias + ReLU in the epilogue, the group3 convolutions writing their column slices of one output."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        if getattr(config, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError("compute_dtype %r: the CNN content encoder is built for fp32 (compute_dtype='fp32')" % config.compute_dtype)
+        self.max_sentence_length = config.max_title_length
+        self.cnn_kernel_num = config.cnn_kernel_num
+        self.conv = Conv1D(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size)
+        self.attention = Attention(config.cnn_kernel_num, config.attention_dim)
+        self.news_embedding_dim = config.cnn_kernel_num + config.category_embedding_dim + config.subCategory_embedding_dim
+        self.category_embedding = nn.Embedding(config.category_num, config.category_embedding_dim)     # trainable (re-created)
+        nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
+
+    def initialize(self):
+        super().initialize()
+        self.attention.initialize()
+
+    def conv_into(self, ids, table, M, T, out, m_dev=None):
+        """Conv1D + ReLU (newsEncoders.py:556) over M = sequences x T tokens whose word rows are table[ids] -> out [M, cnn_kernel_num]."""
+        for conv, col in self.conv.convs():
+            n = conv.out_channels
+            ops.conv1d_window(table, ops.conv1d_pack(conv.weight), conv.kernel_size[0], T, ids=ids, bias=conv.bias, act='relu',
+                              out=out[:, col:col + n], m_dev=m_dev)
+        return out
+
+    def _compact_applicable(self, ids):
+        return (DEDUP and ids.dtype == torch.int32 and ids.is_contiguous() and self.cnn_kernel_num % 4 == 0 and
+                self.attention.affine1.out_features % 4 == 0)
+
+    def _encode(self, ids, mask, out, compact):
+        """One pass over n titles.  Both forms run every GEMM with the SAME capacity ((n + 1) T rows) and a device row count, so the
+        dispatcher picks the same kernels and a title's representation has the same bits whether it went through the compacted or the
+        dense form (the conv kernel computes a row the same way whatever the row count)."""
+        n, T = ids.shape
+        dev = ids.device
+        K, A = self.cnn_kernel_num, self.attention.affine1.out_features
+        cap = (n + 1) * T
+        c = torch.empty((cap, K), dtype=torch.float32, device=dev)
+        hidden = torch.empty((cap, A), dtype=torch.float32, device=dev)
+        table = self.word_embedding.weight
+        a2 = self.attention.affine2.weight.view(-1)
+        if compact:
+            # the live titles + ONE representative of the padding news' title (ids all zero AND the padding news' mask); an all-zero title
+            # under another mask is live (MHSA._encode_compact)
+            cmp = ops.compact_sequences(ops.mhsa_live_ids(ids, mask))
+            mask_c = ops.mhsa_compact_mask(cmp, mask)
+            self.conv_into(cmp.ids_c, table, cap, T, c, m_dev=cmp.n_rows)                                             # :556
+            ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', m_dev=cmp.n_rows, out=hidden)
+            pooled_c = ops.additive_pool(hidden, a2, c, n + 1, T, mask=mask_c, n_seq_dev=cmp.n_compact)                  # :558
+            ops.gather_rows(cmp.seq_inv, pooled_c, out)
+            return
+        self.conv_into(ids.reshape(-1), table, n * T, T, c[:n * T])                                                     # :556
+        ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', m_dev=_row_count(n * T, dev), out=hidden)
+        ops.additive_pool(hidden[:n * T], a2, c[:n * T], n, T, mask=mask, out=out)                                      # :558
+
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out):
+        _no_train_dropout(self, self.dropout_rate)
+        M, T = title_text.shape
+        K = self.cnn_kernel_num
+        mask = title_mask if title_mask.dtype in (torch.bool, torch.uint8) else title_mask.bool()
+        mask = mask.contiguous()
+        ids = _i32(title_text).contiguous()
+        step = max(1, MAX_TOKENS_PER_PASS // T)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            self._encode(ids[m0:m1], mask[m0:m1], out[m0:m1, :K], self._compact_applicable(ids))
+        ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
+                      emb_out=out[:, K:])                                                                               # :561
         return out

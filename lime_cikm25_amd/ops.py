@@ -1477,3 +1477,92 @@ def cand_attn_weights_bwd(qp, kp, mask, dagg, B, N, H, D, n_head, p=0.0, seed=0,
     check(lib.lime_cand_attn_weights_bwd_f32(_p(qp), _p(kp), _p(m), _p(dagg), _p(dqp), _p(dkp), B, N, H, D, n_head, p, seed, site, _stream()),
           'lime_cand_attn_weights_bwd_f32')
     return dqp, dkp
+
+
+def conv1d_pack(weight):
+    """nn.Conv1d weight [O, C, window] -> the [O, window * C] operand of ``conv1d_window`` (row o = taps j, each C wide)."""
+    O, C, win = weight.shape
+    return weight.permute(0, 2, 1).reshape(O, win * C).contiguous()
+
+
+def conv1d_pack_dgrad(weight):
+    """nn.Conv1d weight [O, C, window] -> the [C, window * O] operand of the data gradient (taps reversed):
+    wd[c, j * O + o] = weight[o, c, window - 1 - j]."""
+    O, C, win = weight.shape
+    return weight.flip(2).permute(1, 2, 0).reshape(C, win * O).contiguous()
+
+
+def conv1d_window(a, w, window, T, ids=None, bias=None, act=None, out=None, accumulate=False, m_dev=None):
+    """out[r, o] (+)= act(bias[o] + sum_j A(r, j) . w[o, j C : (j + 1) C]) -- see ``lime_conv1d_window_f32``.
+
+    a: [rows, C] dense source rows (ids None, rows = M) or the [V, C] table the int32 ``ids`` [M] gather from; w: [N, window * C]
+    (``conv1d_pack``); M = sequences x T; out: [M, N] (may be a column slice of a wider output).  Out-of-sequence taps read zeros.
+    m_dev: int32 device tensor (1 element): rows >= min(m_dev, M) are neither computed nor written."""
+    lib = _lib.load()
+    _mat(a, 'a')
+    _mat(w, 'w')
+    C = a.shape[1]
+    N = w.shape[0]
+    if window <= 0 or window % 2 == 0:
+        raise ValueError('conv1d_window: window must be odd and positive (got %d)' % window)
+    if w.shape[1] != window * C:
+        raise ValueError('w must be [N, window * C] = [%d, %d], got %s' % (N, window * C, tuple(w.shape)))
+    if ids is not None:
+        _vec(ids, 'ids', dtype=torch.int32)
+        M = ids.numel()
+    else:
+        M = a.shape[0]
+    if T <= 0 or M % T:
+        raise ValueError('conv1d_window: M = %d rows is not a whole number of sequences of T = %d' % (M, T))
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate needs out')
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (M, N):
+        raise ValueError('out must be [%d, %d], got %s' % (M, N, tuple(out.shape)))
+    if C % 4 or _ld(a) % 4 or _ld(w) % 4 or a.data_ptr() % 16 or w.data_ptr() % 16:
+        raise ValueError('conv1d_window: the source width, the leading dimensions of a and w must be multiples of 4 and a, w 16-byte '
+                         'aligned (C = %d)' % C)
+    if act not in (None, 'none', 'relu'):
+        raise ValueError('conv1d_window: act must be None or relu')
+    if m_dev is not None:
+        _vec(m_dev, 'm_dev', 1, dtype=torch.int32)
+    if M == 0:
+        return out
+    check(lib.lime_conv1d_window_f32(_p(a), _ld(a), _p(ids), _p(w), _ld(w), _p(_vec(bias, 'bias', N)), _p(out), _ld(out), M, N, C, T,
+                                     window, LIME_ACT[act], 1 if accumulate else 0, _p(m_dev), _stream()), 'lime_conv1d_window_f32')
+    return out
+
+
+def conv1d_window_wgrad(dy, a, window, T, ids=None, out=None, accumulate=False):
+    """dW [N, window * C] (+)= sum_r dy[r, :]^T A(r, j) -- the weight gradient of ``conv1d_window`` in its packed layout
+    (``lime_conv1d_wgrad_f32``: fixed-order partial sums, bitwise reproducible).  dy [M, N]; a / ids as in conv1d_window."""
+    lib = _lib.load()
+    _mat(dy, 'dy')
+    _mat(a, 'a')
+    M, N = dy.shape
+    C = a.shape[1]
+    if window <= 0 or window % 2 == 0:
+        raise ValueError('conv1d_window_wgrad: window must be odd and positive (got %d)' % window)
+    if ids is not None:
+        _vec(ids, 'ids', M, dtype=torch.int32)
+    elif a.shape[0] != M:
+        raise ValueError('dy has %d rows, a has %d' % (M, a.shape[0]))
+    if T <= 0 or M % T:
+        raise ValueError('conv1d_window_wgrad: M = %d rows is not a whole number of sequences of T = %d' % (M, T))
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate needs out')
+        out = torch.empty((N, window * C), dtype=torch.float32, device=dy.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (N, window * C):
+        raise ValueError('out must be [%d, %d]' % (N, window * C))
+    if N % 4 or C % 4 or _ld(dy) % 4 or _ld(a) % 4 or dy.data_ptr() % 16 or a.data_ptr() % 16:
+        raise ValueError('conv1d_window_wgrad: N, C and the leading dimensions must be multiples of 4, dy and a 16-byte aligned')
+    if M == 0:
+        return out if accumulate else out.zero_()
+    ws = _workspace(dy.device, lib.lime_conv1d_wgrad_workspace(M, N, C, window))
+    check(lib.lime_conv1d_wgrad_f32(_p(dy), _ld(dy), _p(a), _ld(a), _p(ids), _p(out), _ld(out), M, N, C, T, window,
+                                    1 if accumulate else 0, _p(ws), ws.numel(), _stream()), 'lime_conv1d_wgrad_f32')
+    return out

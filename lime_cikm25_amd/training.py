@@ -623,6 +623,76 @@ def mhsa_content(enc, title_text, title_mask, category, subCategory):
     return torch.cat([rep, enc.dropout(cat_e.clone()), enc.dropout(sub_e.clone())], dim=1)                      # :594
 
 
+class _Conv1D(torch.autograd.Function):
+    """layers.Conv1D + ReLU (layers.py:126-130) on M = sequences x T token rows x [M, C]: the convolutions (window, weight [n, C, window],
+    bias [n]) write their column slices of one output on the windowed conv GEMM.  Backward: ReLU backward, the data gradient on the
+    same kernel with the taps reversed (summed over the convolutions in order), the weight gradient on its windowed sibling kernel, the
+    bias gradient as a column sum."""
+
+    @staticmethod
+    def forward(ctx, x, T, windows, *params):
+        x = x.contiguous()
+        M = x.shape[0]
+        ws, bs = params[0::2], params[1::2]
+        K = sum(w.shape[0] for w in ws)
+        out = torch.empty((M, K), dtype=torch.float32, device=x.device)
+        col = 0
+        for w, b, win in zip(ws, bs, windows):
+            ops.conv1d_window(x, ops.conv1d_pack(w), win, T, bias=b, act='relu', out=out[:, col:col + w.shape[0]])
+            col += w.shape[0]
+        ctx.dims = (T, windows)
+        ctx.save_for_backward(x, out, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, out, *ws = ctx.saved_tensors
+        T, windows = ctx.dims
+        M, C = x.shape
+        dy = ops.relu_bwd_(dout.contiguous().clone(), out)
+        dx = torch.empty((M, C), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        grads = []
+        col = 0
+        for i, (w, win) in enumerate(zip(ws, windows)):
+            n = w.shape[0]
+            d = dy[:, col:col + n]
+            if dx is not None:
+                ops.conv1d_window(d, ops.conv1d_pack_dgrad(w), win, T, out=dx, accumulate=i > 0)
+            dw = ops.conv1d_window_wgrad(d, x, win, T).view(n, win, C).permute(0, 2, 1).contiguous()
+            grads += [dw, ops.colsum(d)]
+            col += n
+        return (dx, None, None) + tuple(grads)
+
+
+def cnn_content(enc, title_text, title_mask, category, subCategory):
+    """newsEncoders.CNN.forward (newsEncoders.py:548-563; title only) on M flat news -> [M, cnn_kernel_num + 100].  The dropout sites
+    (counter-based masks of one seed): 0 the word embedding (:553), 1 the convolution output (dropout_, :555), 2 / 3 the category /
+    subcategory embeddings of feature_fusion (:221-226)."""
+    M, T = title_text.shape
+    att = enc.attention
+    p = float(enc.dropout.p) if enc.training else 0.0
+    seed = _draw_seed() if p > 0 else 0
+    x = embedding(enc.word_embedding.weight, title_text, hot_id=0).view(M * T, -1)                              # :553
+    if p > 0:
+        x = _Dropout.apply(x, p, seed, 0)
+    convs = enc.conv.convs()
+    params = []
+    for conv, _ in convs:
+        params += [conv.weight, conv.bias]
+    c = _Conv1D.apply(x, T, tuple(conv.kernel_size[0] for conv, _ in convs), *params)                          # :555, layers.py:126-130
+    if p > 0:
+        c = _Dropout.apply(c, p, seed, 1)
+    mask = title_mask.contiguous()
+    hidden = linear(c, att.affine1, act='tanh')                                                                 # layers.py:288
+    rep = _AdditivePool.apply(hidden, att.affine2.weight.view(-1), c, mask, M, T)                               # :557, layers.py:289-300
+    cat_e = embedding(enc.category_embedding.weight, category)
+    sub_e = embedding(enc.subCategory_embedding.weight, subCategory)
+    if p > 0:
+        cat_e = _Dropout.apply(cat_e, p, seed, 2)
+        sub_e = _Dropout.apply(sub_e, p, seed, 3)
+    return torch.cat([rep, cat_e, sub_e], dim=1)                                                                # :561, :221-226
+
+
 def lime_tail(ne, content, freshness, lifetime):
     """LIME.forward, fusion 'concat' (newsEncoders.py:140-153), from the content encoder's output -> [M, 400]."""
     fe = ne.freshness_encoder
@@ -723,8 +793,8 @@ def lifetime_weighted_logits(w, user, news, remaining_lifetime):
 
 
 def content_flat(enc, title_text, title_mask, content_text, category, subCategory):
-    """The base content encoder (CROWN: newsEncoders.py:302-373, MHSA: :582-595) on M flat news with autograd -> [M, dim]."""
-    from .newsEncoders import CROWN, MHSA
+    """The base content encoder (CROWN: newsEncoders.py:302-373, CNN: :548-563, MHSA: :582-595) on M flat news with autograd -> [M, dim]."""
+    from .newsEncoders import CNN, CROWN, MHSA
     if getattr(enc, 'compute_dtype', 'fp32') != 'fp32':
         raise NotImplementedError("compute_dtype %r is a scoring option (BASELINE config 3); the training step is fp32: build the "
                                   "model with compute_dtype='fp32' to train" % enc.compute_dtype)
@@ -733,7 +803,9 @@ def content_flat(enc, title_text, title_mask, content_text, category, subCategor
         return crown_tail(enc, title_p, body_p, category, subCategory)
     if isinstance(enc, MHSA):
         return mhsa_content(enc, title_text, title_mask, category, subCategory)
-    raise NotImplementedError('the training path covers the CROWN and MHSA content encoders')
+    if isinstance(enc, CNN):
+        return cnn_content(enc, title_text, title_mask, category, subCategory)
+    raise NotImplementedError('the training path covers the CROWN, CNN and MHSA content encoders')
 
 
 def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime):
