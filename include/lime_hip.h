@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 8
+#define LIME_ABI_VERSION 9
 
 typedef enum {
     LIME_OK = 0,
@@ -780,6 +780,21 @@ int64_t lime_conv1d_wgrad_workspace(int32_t M, int32_t N, int32_t C, int32_t win
 int lime_conv1d_wgrad_f32(const float* dy, int64_t ldy, const float* a, int64_t lda, const int32_t* ids, float* dw, int64_t lddw,
                           int32_t M, int32_t N, int32_t C, int32_t T, int32_t window, int32_t accumulate, float* workspace,
                           int64_t workspace_floats, void* stream);
+
+/* =====================================================================================================
+ * Additive attention pool in one launch (layers.py:285-300 Attention, the NAML content encoder newsEncoders.py:686-694;
+ * csrc/attn_pool_sp_f32.hip: split product, or exact-fp32 MFMA under lime_set_split_gemm(0)):
+ *   out[s * ldo + :D] = sum_t alpha[s, t] x[(s T + t) * ldx + :D],  alpha[s] = softmax_t(w2 . tanh(W1 x[s T + t] + b1))
+ *   score of a key with mask[s T + t] == 0: -1e9 (mask optional, u8 [n_seq * T]).
+ * The [rows, A] hidden state never leaves registers.  A tile of 128 rows holds floor(128 / T) whole sequences: a sequence's output
+ * has the same bits in any tile slot and for any n_seq.  w1p: W1 [A, D] as lime_attn_pool_pack_sp lays it out (opaque; repack after
+ * every change of W1).  b1 [A] (may be NULL: zeros), w2 [A].  T <= 128, D % 4 == 0, D <= 16384, A <= 512; x, out 16-byte aligned,
+ * ldx, ldo multiples of 4.  n_seq_dev: optional device sequence count (sequences >= min(*n_seq_dev, n_seq) are neither read nor
+ * written). */
+int64_t lime_attn_pool_pack_sp_size(int32_t D, int32_t A);
+int lime_attn_pool_pack_sp(const float* w1, int64_t ldw1, int32_t D, int32_t A, uint16_t* w1p, void* stream);
+int lime_attn_pool_sp_f32(const float* x, int64_t ldx, int32_t D, const uint16_t* w1p, const float* b1, const float* w2, int32_t A,
+                          const uint8_t* mask, float* out, int64_t ldo, int32_t n_seq, int32_t T, const int32_t* n_seq_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_ui
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblime_hip.so')
 
-ABI_VERSION = 8          # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
+ABI_VERSION = 9          # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
 LIME_ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'relu_grad': 4}
 
 
@@ -275,6 +275,11 @@ SIGNATURES = {
     'lime_conv1d_wgrad_workspace': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     'lime_conv1d_wgrad_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                         c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    # NAML content encoder: fused additive attention pool
+    'lime_attn_pool_pack_sp_size': (c_int64, [c_int32, c_int32]),
+    'lime_attn_pool_pack_sp': (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    'lime_attn_pool_sp_f32': (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64,
+                                        c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""Drop-in ``Model`` for the LIME-{CROWN,CNN,MHSA}-CROWN scoring path (reference model.py:11-187)."""
+"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA}-CROWN scoring path (reference model.py:11-187)."""
 import torch
 import torch.nn as nn
 
@@ -18,7 +18,7 @@ class Model(nn.Module):
     """Same constructor, attributes (``model_name``, ``config``, ``news_encoder``, ``user_encoder``,
     ``news_embedding_dim``), ``initialize()`` and 26-tensor ``forward`` as the reference's Model
     (model.py:12-187); ``state_dict()`` has the reference's key set.  ``forward`` returns logits [B, N].
-    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN' (cnn_method 'naive' or 'group3') or 'MHSA'.
+    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3') or 'MHSA'.
 
     Scoring (eval mode, or any call under ``torch.no_grad()``): the forward pass runs entirely in hand-written HIP
     kernels and records no autograd graph.  In training mode with grad enabled (``model.train(); model(...)``, what
@@ -41,6 +41,8 @@ class Model(nn.Module):
             base_encoder = newsEncoders.CROWN(config)
         elif config.content_encoder == 'CNN':
             base_encoder = newsEncoders.CNN(config)
+        elif config.content_encoder == 'NAML':
+            base_encoder = newsEncoders.NAML(config)
         elif config.content_encoder == 'MHSA':
             base_encoder = newsEncoders.MHSA(config)
         else:

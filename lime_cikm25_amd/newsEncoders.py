@@ -1,5 +1,5 @@
-"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN and MHSA
-(reference newsEncoders.py:38-161, 167-373, 535-563, 566-595, 806-828).
+"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN, NAML and MHSA
+(reference newsEncoders.py:38-161, 167-373, 535-563, 566-595, 641-695, 806-828).
 
 The modules keep the reference's attribute and parameter names, so ``state_dict()`` has the same
 183 keys and reference checkpoints load.  Standard torch containers
@@ -1153,4 +1153,114 @@ class CNN(NewsEncoder):
             self._encode(ids[m0:m1], mask[m0:m1], out[m0:m1, :K], self._compact_applicable(ids))
         ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
                       emb_out=out[:, K:])                                                                               # :561
+        return out
+
+
+class NAML(NewsEncoder):
+    """newsEncoders.py:641-695: title and body each through a 1-D convolution (layers.py:98-135, ReLU) and an additive attention, two
+    category views (Linear 50 -> cnn_kernel_num + ReLU), and an additive attention over the four views -> [B, n, cnn_kernel_num].
+
+    The convolutions are the windowed conv GEMM (csrc/conv_sp_f32.hip); the three attentions are the fused attention pool
+    (csrc/attn_pool_sp_f32.hip: tanh(affine1), the score, the softmax and the weighted sum in one launch, the hidden state in registers)
+    when ops.FUSED_ATTN_POOL asks for it, else linear(tanh) + additive_pool: on MI355X the fused launch is the slower one today.
+    Reference behaviour kept: the word attentions take NO mask (:686-687: padding positions take part in the softmax; title_mask and
+    content_mask are not read), no feature_fusion (the content dimension is cnn_kernel_num, :647), the view attention is a softmax
+    over the stack [title, body, category, subcategory] (:692-694)."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        if getattr(config, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError("compute_dtype %r: the NAML content encoder is built for fp32 (compute_dtype='fp32')" % config.compute_dtype)
+        self.max_title_length = config.max_title_length
+        self.max_content_length = config.max_abstract_length
+        self.cnn_kernel_num = config.cnn_kernel_num
+        self.news_embedding_dim = config.cnn_kernel_num                                                 # :647
+        self.title_conv = Conv1D(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size)
+        self.content_conv = Conv1D(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size)
+        self.title_attention = Attention(config.cnn_kernel_num, config.attention_dim)
+        self.content_attention = Attention(config.cnn_kernel_num, config.attention_dim)
+        self.category_affine = nn.Linear(config.category_embedding_dim, config.cnn_kernel_num, bias=True)
+        self.subCategory_affine = nn.Linear(config.subCategory_embedding_dim, config.cnn_kernel_num, bias=True)
+        self.affine1 = nn.Linear(config.cnn_kernel_num, config.attention_dim, bias=True)
+        self.affine2 = nn.Linear(config.attention_dim, 1, bias=False)
+        self.category_embedding = nn.Embedding(config.category_num, config.category_embedding_dim)     # trainable (re-created, :656)
+
+    def initialize(self):                                                                               # :658-669
+        super().initialize()
+        self.title_attention.initialize()
+        self.content_attention.initialize()
+        nn.init.xavier_uniform_(self.category_affine.weight)
+        nn.init.zeros_(self.category_affine.bias)
+        nn.init.xavier_uniform_(self.subCategory_affine.weight)
+        nn.init.zeros_(self.subCategory_affine.bias)
+        nn.init.xavier_uniform_(self.affine1.weight)
+        nn.init.zeros_(self.affine1.bias)
+        nn.init.xavier_uniform_(self.affine2.weight)
+        nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
+
+    @staticmethod
+    def conv_into(conv, ids, table, M, T, out, m_dev=None):
+        """Conv1D + ReLU (:681, :684) over M = sequences x T tokens whose word rows are table[ids] -> out [M, cnn_kernel_num]."""
+        for c, col in conv.convs():
+            n = c.out_channels
+            ops.conv1d_window(table, ops.conv1d_pack(c.weight), c.kernel_size[0], T, ids=ids, bias=c.bias, act='relu',
+                              out=out[:, col:col + n], m_dev=m_dev)
+        return out
+
+    def _compact_applicable(self, ids):
+        return DEDUP and ids.dtype == torch.int32 and ids.is_contiguous()
+
+    def _encode_text(self, ids, conv, att, w1p, out, compact):
+        """One pass over n texts (title or body): conv + the unmasked attention pool (:683-687) -> out [n, cnn_kernel_num] (a view slot).
+
+        Both forms run every launch with the SAME capacity ((n + 1) sequences of T rows) and a device count, so the dispatcher picks the
+        same kernels and a text's representation has the same bits whether it went through the compacted or the dense form (the conv
+        kernel computes a row, the attention pool a sequence, the same way whatever the counts).  Compacted: the live texts (any non-zero
+        id; NAML reads no mask) and ONE representative of the all-padding ones."""
+        n, T = ids.shape
+        dev = ids.device
+        K = self.cnn_kernel_num
+        cap = (n + 1) * T
+        c = torch.empty((cap, K), dtype=torch.float32, device=dev)
+        pooled = torch.empty((n + 1, K), dtype=torch.float32, device=dev)
+        table = self.word_embedding.weight
+        a1, a2 = att.affine1, att.affine2.weight.view(-1)
+        if compact:
+            cmp = ops.compact_sequences(ids)
+            self.conv_into(conv, cmp.ids_c, table, cap, T, c, m_dev=cmp.n_rows)                                       # :681, :684
+            ops.attn_pool(c, a1.weight, a1.bias, a2, n + 1, T, out=pooled, n_seq_dev=cmp.n_compact, w1p=w1p,
+                          m_dev=cmp.n_rows)                                                                            # :686-687
+            ops.gather_rows(cmp.seq_inv, pooled, out)
+            return
+        self.conv_into(conv, ids.reshape(-1), table, n * T, T, c[:n * T])                                              # :681, :684
+        ops.attn_pool(c, a1.weight, a1.bias, a2, n + 1, T, out=pooled, n_seq_dev=_row_count(n, dev), w1p=w1p,
+                      m_dev=_row_count(n * T, dev))                                                                    # :686-687
+        ops.gather_rows(_identity_rows(n, dev), pooled, out)
+
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out):
+        _no_train_dropout(self, self.dropout_rate)
+        M, T = title_text.shape
+        L = content_text.shape[1]
+        K = self.cnn_kernel_num
+        dev = title_text.device
+        t_ids = _i32(title_text).contiguous()
+        b_ids = _i32(content_text).contiguous()
+        fused = ops.attn_pool_fused
+        # the attention pools (ops.attn_pool: the fused launch where ops.FUSED_ATTN_POOL asks for it, else linear(tanh) + additive_pool);
+        # W1 of a fused one split into its bf16 terms HERE (inside the forward: a captured graph repacks on every replay)
+        w1p = [ops.attn_pool_pack(a.affine1.weight) if fused(K, a.affine1.out_features, t) else None
+               for a, t in ((self.title_attention, T), (self.content_attention, L), (self, 4))]
+        views = torch.empty((M, 4, K), dtype=torch.float32, device=dev)                                     # :692 stack
+        step = max(1, MAX_TOKENS_PER_PASS // max(T, L))
+        compact = self._compact_applicable(t_ids) and self._compact_applicable(b_ids)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            self._encode_text(t_ids[m0:m1], self.title_conv, self.title_attention, w1p[0], views[m0:m1, 0], compact)
+            self._encode_text(b_ids[m0:m1], self.content_conv, self.content_attention, w1p[1], views[m0:m1, 1], compact)
+        ops.linear(self.category_embedding.weight, self.category_affine.weight, self.category_affine.bias, act='relu',
+                   a_ids=_i32(category).reshape(-1).contiguous(), out=views[:, 2])                               # :689
+        ops.linear(self.subCategory_embedding.weight, self.subCategory_affine.weight, self.subCategory_affine.bias, act='relu',
+                   a_ids=_i32(subCategory).reshape(-1).contiguous(), out=views[:, 3])                            # :690
+        ops.attn_pool(views.view(M * 4, K), self.affine1.weight, self.affine1.bias, self.affine2.weight.view(-1), M, 4, out=out,
+                      w1p=w1p[2])                                                                                # :692-694
         return out

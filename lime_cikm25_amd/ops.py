@@ -7,6 +7,7 @@ dimension, so slices like ``qkv[:, 300:600]`` or ``fused[:, 900:]`` cost nothing
 """
 import ctypes
 import math
+import os
 
 import torch
 
@@ -1565,4 +1566,78 @@ def conv1d_window_wgrad(dy, a, window, T, ids=None, out=None, accumulate=False):
     ws = _workspace(dy.device, lib.lime_conv1d_wgrad_workspace(M, N, C, window))
     check(lib.lime_conv1d_wgrad_f32(_p(dy), _ld(dy), _p(a), _ld(a), _p(ids), _p(out), _ld(out), M, N, C, T, window,
                                     1 if accumulate else 0, _p(ws), ws.numel(), _stream()), 'lime_conv1d_wgrad_f32')
+    return out
+
+
+ATTN_POOL_T_MAX, ATTN_POOL_A_MAX = 128, 512       # the fused attention pool's limits (csrc/attn_pool_sp_f32.hip)
+# Measured on MI355X (tools/bench_naml.py --part pool, DESIGN.md "NAML content encoder"): at 1760 x 32, 1760 x 128 and 1760 x 4 rows
+# (D = A = 400) the fused launch takes 1.38x, 1.37x and 2.2x the time of linear(tanh) + additive_pool, so ``attn_pool`` keeps the two
+# launches unless asked for the fused one (fused=True, or LIME_FUSED_ATTN_POOL=1 for the whole process).
+FUSED_ATTN_POOL = os.environ.get('LIME_FUSED_ATTN_POOL', '0') == '1'
+
+
+def attn_pool_pack(w1):
+    """``lime_attn_pool_pack_sp``: Attention.affine1's weight (fp32 [A, D]) -> the split (three bf16 terms) operand of ``attn_pool``.
+    Runs on the stream like any launch: called inside a forward, a captured graph repacks on every replay."""
+    lib = _lib.load()
+    _mat(w1, 'w1')
+    A, D = w1.shape
+    n = int(lib.lime_attn_pool_pack_sp_size(D, A))
+    if n <= 0:
+        raise ValueError('attn_pool_pack: built for D %% 4 == 0 and A <= %d (w1 is %s)' % (ATTN_POOL_A_MAX, tuple(w1.shape)))
+    w1p = torch.empty(n, dtype=torch.bfloat16, device=w1.device)
+    check(lib.lime_attn_pool_pack_sp(_p(w1), _ld(w1), D, A, _p(w1p), _stream()), 'lime_attn_pool_pack_sp')
+    return w1p
+
+
+def attn_pool_fused(D, A, T, fused=None):
+    """True when ``attn_pool(..., fused=fused)`` runs the one-launch kernel for these dimensions (else linear(tanh) + additive_pool).
+    Depends on the dimensions and the switch only, never on the sequence count."""
+    want = FUSED_ATTN_POOL if fused is None else fused
+    return bool(want) and 0 < T <= ATTN_POOL_T_MAX and D % 4 == 0 and 0 < A <= ATTN_POOL_A_MAX
+
+
+def attn_pool(x, w1, b1, w2, n_seq, T, mask=None, out=None, n_seq_dev=None, w1p=None, fused=None, m_dev=None):
+    """layers.Attention (layers.py:285-300) over n_seq sequences of T rows of x [n_seq * T, D]:
+    out[s] = sum_t softmax_t(w2 . tanh(w1 x[s T + t] + b1)) x[s T + t] -> [n_seq, D] (``out`` may be a row-strided view, e.g. one slot
+    of a [M, 4, D] stack).  mask: optional bool / uint8 [n_seq * T] (0: the key scores -1e9).  n_seq_dev: int32 device tensor
+    (1 element): only that many sequences are read and written.
+
+    One launch (``lime_attn_pool_sp_f32``, the hidden state stays in registers) when ``attn_pool_fused(D, A, T, fused)``; w1p is the
+    packed w1 (``attn_pool_pack``; packed here when not given).  Otherwise ``linear(act='tanh')`` + ``additive_pool``; m_dev (int32
+    device tensor, 1 element, = n_seq_dev * T) then bounds the rows of the linear launch."""
+    lib = _lib.load()
+    _mat(x, 'x')
+    _mat(w1, 'w1')
+    D = x.shape[1]
+    A = w1.shape[0]
+    if w1.shape[1] != D:
+        raise ValueError('w1 must be [A, %d], got %s' % (D, tuple(w1.shape)))
+    if T <= 0 or n_seq < 0 or x.shape[0] != n_seq * T:
+        raise ValueError('x must have n_seq * T rows (n_seq = %d, T = %d, x has %d)' % (n_seq, T, x.shape[0]))
+    _vec(w2, 'w2', A)
+    _vec(b1, 'b1', A)
+    if out is None:
+        out = torch.empty((n_seq, D), dtype=torch.float32, device=x.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (n_seq, D):
+        raise ValueError('out must be [%d, %d], got %s' % (n_seq, D, tuple(out.shape)))
+    m = _mask_u8(mask, 'mask')
+    if m is not None and m.numel() != n_seq * T:
+        raise ValueError('mask must have n_seq * T elements')
+    if n_seq_dev is not None:
+        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
+    if not attn_pool_fused(D, A, T, fused):
+        hidden = linear(x, w1, b1, act='tanh', m_dev=m_dev)
+        return additive_pool(hidden, w2, x, n_seq, T, mask=m, out=out, n_seq_dev=n_seq_dev)
+    if _ld(x) % 4 or x.data_ptr() % 16 or _ld(out) % 4 or out.data_ptr() % 16:
+        raise ValueError('attn_pool: x and out must be 16-byte aligned with leading dimensions that are multiples of 4')
+    if w1p is None:
+        w1p = attn_pool_pack(w1)
+    elif w1p.dtype != torch.bfloat16 or not w1p.is_contiguous() or w1p.numel() != int(lib.lime_attn_pool_pack_sp_size(D, A)):
+        raise ValueError('w1p must be the buffer of attn_pool_pack for w1 [%d, %d]' % (A, D))
+    if n_seq == 0:
+        return out
+    check(lib.lime_attn_pool_sp_f32(_p(x), _ld(x), D, _p(w1p), _p(b1), _p(w2), A, _p(m), _p(out), _ld(out), n_seq, T, _p(n_seq_dev),
+                                    _stream()), 'lime_attn_pool_sp_f32')
     return out

@@ -693,6 +693,47 @@ def cnn_content(enc, title_text, title_mask, category, subCategory):
     return torch.cat([rep, cat_e, sub_e], dim=1)                                                                # :561, :221-226
 
 
+def _conv_c(conv, x, T):
+    """layers.Conv1D + ReLU of a parameter holder (layers.Conv1D) over M = sequences x T token rows x [M, C] -> [M, cnn_kernel_num]."""
+    convs = conv.convs()
+    params = []
+    for c, _ in convs:
+        params += [c.weight, c.bias]
+    return _Conv1D.apply(x, T, tuple(c.kernel_size[0] for c, _ in convs), *params)
+
+
+def naml_content(enc, title_text, content_text, category, subCategory):
+    """newsEncoders.NAML.forward (newsEncoders.py:671-695) on M flat news -> [M, cnn_kernel_num].  The word attentions take no mask
+    (:686-687).  The dropout sites (counter-based masks of one seed): 0 / 1 the title / body word embeddings (self.dropout, :676-677),
+    2 / 3 the title / body convolution outputs (self.dropout_, :681, :684); the category views get none (:689-690).
+
+    Unfused: the attention pools' backward needs the tanh hidden state, so each attention is linear(tanh) + _AdditivePool here while
+    the scoring path (NAML.encode_flat) runs the one-launch pool -- the two agree to rounding (summation order), not bit for bit."""
+    M, T = title_text.shape
+    L = content_text.shape[1]
+    p = float(enc.dropout.p) if enc.training else 0.0
+    seed = _draw_seed() if p > 0 else 0
+    xt = embedding(enc.word_embedding.weight, title_text, hot_id=0).view(M * T, -1)                           # :676
+    xb = embedding(enc.word_embedding.weight, content_text, hot_id=0).view(M * L, -1)                         # :677
+    if p > 0:
+        xt = _Dropout.apply(xt, p, seed, 0)
+        xb = _Dropout.apply(xb, p, seed, 1)
+    ct = _conv_c(enc.title_conv, xt, T)                                                                         # :681
+    cb = _conv_c(enc.content_conv, xb, L)                                                                       # :684
+    if p > 0:
+        ct = _Dropout.apply(ct, p, seed, 2)
+        cb = _Dropout.apply(cb, p, seed, 3)
+    views = []
+    for c, att, S in ((ct, enc.title_attention, T), (cb, enc.content_attention, L)):                           # :686-687, no mask
+        hidden = linear(c, att.affine1, act='tanh')                                                             # layers.py:288
+        views.append(_AdditivePool.apply(hidden, att.affine2.weight.view(-1), c, None, M, S))                   # layers.py:289-300
+    views.append(linear(embedding(enc.category_embedding.weight, category), enc.category_affine, act='relu'))          # :689
+    views.append(linear(embedding(enc.subCategory_embedding.weight, subCategory), enc.subCategory_affine, act='relu'))  # :690
+    feature = torch.stack(views, dim=1).view(M * 4, -1)                                                         # :692
+    hidden = linear(feature, enc.affine1, act='tanh')                                                           # :693
+    return _AdditivePool.apply(hidden, enc.affine2.weight.view(-1), feature, None, M, 4)                        # :693-694
+
+
 def lime_tail(ne, content, freshness, lifetime):
     """LIME.forward, fusion 'concat' (newsEncoders.py:140-153), from the content encoder's output -> [M, 400]."""
     fe = ne.freshness_encoder
@@ -793,8 +834,9 @@ def lifetime_weighted_logits(w, user, news, remaining_lifetime):
 
 
 def content_flat(enc, title_text, title_mask, content_text, category, subCategory):
-    """The base content encoder (CROWN: newsEncoders.py:302-373, CNN: :548-563, MHSA: :582-595) on M flat news with autograd -> [M, dim]."""
-    from .newsEncoders import CNN, CROWN, MHSA
+    """The base content encoder (CROWN: newsEncoders.py:302-373, CNN: :548-563, NAML: :671-695, MHSA: :582-595) on M flat news with
+    autograd -> [M, dim]."""
+    from .newsEncoders import CNN, CROWN, MHSA, NAML
     if getattr(enc, 'compute_dtype', 'fp32') != 'fp32':
         raise NotImplementedError("compute_dtype %r is a scoring option (BASELINE config 3); the training step is fp32: build the "
                                   "model with compute_dtype='fp32' to train" % enc.compute_dtype)
@@ -805,7 +847,9 @@ def content_flat(enc, title_text, title_mask, content_text, category, subCategor
         return mhsa_content(enc, title_text, title_mask, category, subCategory)
     if isinstance(enc, CNN):
         return cnn_content(enc, title_text, title_mask, category, subCategory)
-    raise NotImplementedError('the training path covers the CROWN, CNN and MHSA content encoders')
+    if isinstance(enc, NAML):
+        return naml_content(enc, title_text, content_text, category, subCategory)
+    raise NotImplementedError('the training path covers the CROWN, CNN, NAML and MHSA content encoders')
 
 
 def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime):
