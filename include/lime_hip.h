@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 9
+#define LIME_ABI_VERSION 10
 
 typedef enum {
     LIME_OK = 0,
@@ -795,6 +795,22 @@ int64_t lime_attn_pool_pack_sp_size(int32_t D, int32_t A);
 int lime_attn_pool_pack_sp(const float* w1, int64_t ldw1, int32_t D, int32_t A, uint16_t* w1p, void* stream);
 int lime_attn_pool_sp_f32(const float* x, int64_t ldx, int32_t D, const uint16_t* w1p, const float* b1, const float* w2, int32_t A,
                           const uint8_t* mask, float* out, int64_t ldo, int32_t n_seq, int32_t T, const int32_t* n_seq_dev, void* stream);
+
+/* =====================================================================================================
+ * Tail of the pooled user encoders in one launch (userEncoders ATT / MHSA; csrc/user_pool_match_f32.hip): additive attention pool
+ * over the history (layers.py:288-299, behind the affine1 + tanh GEMM), dot product with every candidate, remaining-lifetime weight
+ * (util.py:23-49, the rule of lime_interest_match_f32 / lime_lifetime_score_f32):
+ *   a[h] = hidden[(b H + h) * ldh + :A] . w2   (-1e9 where mask[b H + h] == 0);   alpha = softmax_h(a)
+ *   u[b, :] = sum_h alpha[h] x[(b H + h) * ldx + :D]                               -> user_rep [B, D] (may be NULL)
+ *   logits[b, n] = (u[b, :] . cand[b, n, :]) * w(remaining[b, n])                  -> logits [B, N]  (may be NULL; not both)
+ * mask: optional u8 [B, H].  cand [B, N, D] and remaining [B, N] (use_weight) are read only when logits is given.
+ * H <= 512, D <= 2048, D % 4 == 0, ldx % 4 == 0; x, cand, user_rep 16-byte aligned (LIME_ERR_BAD_ARG otherwise); hidden / w2 are read
+ * 16 bytes at a time when A % 4 == 0, ldh % 4 == 0 and both are aligned, element by element otherwise.  A workgroup per row below
+ * B = 2048, a wave per row (four rows a workgroup) from there on; a row's bits are the same in both forms, for any B and N. */
+int lime_pool_match_f32(const float* hidden, int64_t ldh, const float* w2, const float* x, int64_t ldx, const uint8_t* mask,
+                        const float* cand, const float* remaining, float alpha_s, float beta_s, int32_t use_weight,
+                        int32_t use_penalty, float* user_rep, float* logits, int32_t B, int32_t N, int32_t H, int32_t A, int32_t D,
+                        void* stream);
 
 #ifdef __cplusplus
 }

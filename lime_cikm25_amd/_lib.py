@@ -10,7 +10,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_ui
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblime_hip.so')
 
-ABI_VERSION = 9          # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
+ABI_VERSION = 10         # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
 LIME_ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'relu_grad': 4}
 
 
@@ -280,6 +280,9 @@ SIGNATURES = {
     'lime_attn_pool_pack_sp': (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'lime_attn_pool_sp_f32': (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64,
                                         c_int32, c_int32, c_void_p, c_void_p]),
+    # ATT / MHSA user encoders: attention pool over the history + candidate match + lifetime weight
+    'lime_pool_match_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                      c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None

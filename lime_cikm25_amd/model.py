@@ -1,4 +1,4 @@
-"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA}-CROWN scoring path (reference model.py:11-187)."""
+"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA}-{CROWN,ATT,MHSA} scoring path (reference model.py:11-187)."""
 import torch
 import torch.nn as nn
 
@@ -14,11 +14,23 @@ _USED = (1, 2, 3, 4, 6, 9, 10, 11, 15, 16, 17, 18, 20, 23, 24, 25)
 _PAIRS = ((17, 3), (18, 4), (20, 6), (15, 1), (16, 2), (23, 9), (24, 10))
 
 
+_USER_ENCODERS = ('CROWN', 'ATT', 'MHSA')
+# why the reference's other user encoders (model.py:67-88) stay refused
+_REFUSED_USER_ENCODERS = {
+    'LSTUR': ' (it needs user_ID embeddings and a GRU)', 'GRU': ' (it needs a GRU over the history)',
+    'PUE': ' (it needs user_ID embeddings)', 'CATT': ' (it pools the history per candidate)',
+    'MINER': ' (poly attention with per-candidate pooling)', 'SUE': ' (it is not part of this port)',
+    'FIM': ' (it needs the HDC news encoder and the FIM click predictor)',
+}
+
+
 class Model(nn.Module):
     """Same constructor, attributes (``model_name``, ``config``, ``news_encoder``, ``user_encoder``,
     ``news_embedding_dim``), ``initialize()`` and 26-tensor ``forward`` as the reference's Model
     (model.py:12-187); ``state_dict()`` has the reference's key set.  ``forward`` returns logits [B, N].
-    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3') or 'MHSA'.
+    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3') or 'MHSA';
+    ``config.user_encoder`` the user encoder: 'CROWN', 'ATT' (NAML's additive attention) or 'MHSA' (NRMS's self-attention), in any
+    pairing.
 
     Scoring (eval mode, or any call under ``torch.no_grad()``): the forward pass runs entirely in hand-written HIP
     kernels and records no autograd graph.  In training mode with grad enabled (``model.train(); model(...)``, what
@@ -48,9 +60,10 @@ class Model(nn.Module):
         else:
             raise NotImplementedError('content_encoder %r is a baseline outside the scoring path' % config.content_encoder)
         self.news_encoder = newsEncoders.LIME(config=config, base_news_encoder=base_encoder)
-        if config.user_encoder != 'CROWN':
-            raise NotImplementedError('user_encoder %r is a baseline outside the scoring path' % config.user_encoder)
-        self.user_encoder = userEncoders.CROWN(self.news_encoder, config)
+        if config.user_encoder not in _USER_ENCODERS:
+            raise NotImplementedError('user_encoder %r is outside the scoring path%s: the supported user encoders are %s' % (
+                config.user_encoder, _REFUSED_USER_ENCODERS.get(config.user_encoder, ''), ', '.join(sorted(_USER_ENCODERS))))
+        self.user_encoder = getattr(userEncoders, config.user_encoder)(self.news_encoder, config)
         self.model_name = f"{config.news_encoder}-{config.content_encoder}-{config.user_encoder}"
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)
@@ -172,7 +185,7 @@ class Model(nn.Module):
             (user_title_text, user_title_mask, user_content_text, user_category, user_subCategory, user_freshness,
              user_user_topic_lifetime)])                                              # [B, K, D], [B, H, D]
         rows = B * K
-        if n_src is None:
+        if n_src is None and hasattr(ue, 'user_node_embedding'):      # CROWN's GraphSAGE alone; the other user encoders ignore n_src
             n_src = min(rows, H + ue.user_node_embedding.shape[0])
         out = torch.empty((B, K), dtype=torch.float32, device=cand.device)
         per = max(1, rows_per_pass // K)                                              # impressions per pass ...
@@ -226,7 +239,7 @@ class Model(nn.Module):
             remaining = (b.cand_lifetime[rows] - b.cand_freshness[rows])
         else:
             raise ValueError('Invalid lifetime_type')
-        if n_src is None:
+        if n_src is None and hasattr(ue, 'user_node_embedding'):
             n_src = min(R, H + ue.user_node_embedding.shape[0])
         _, logits = ue.match(hist, c.news_category[flat_c].view(R, 1), c.news_subCategory[flat_c].view(R, 1),
                              c.news_category[flat_h].view(R, H), c.news_subCategory[flat_h].view(R, H), b.hist_mask[rows],

@@ -619,6 +619,51 @@ def lifetime_score(user, news, remaining, alpha, beta, use_weight, use_penalty):
     return logits
 
 
+# The tail of the pooled user encoders (userEncoders.ATT / MHSA): one launch (True) or lime_additive_pool_f32 + lime_lifetime_score_f32
+# on an expanded copy of the user vector (False).  The default is the faster form at the eval shape (DESIGN.md "ATT and MHSA user
+# encoders"); LIME_FUSED_POOL_MATCH=0 / 1 selects the other one.
+FUSED_POOL_MATCH = os.environ.get('LIME_FUSED_POOL_MATCH', '1') == '1'
+
+
+def pool_match(hidden, affine2, x, B, H, cand=None, remaining=None, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False, mask=None,
+               want_user=True, want_logits=True, fused=None):
+    """``lime_pool_match_f32``: additive attention pool over the H history rows of each of B users (layers.py:288-299 from the tanh
+    hidden state), and the lifetime-weighted dot product of the pooled vector with the user's N candidates (util.py:23-49).
+    hidden [B H, A], x [B H, D] (row-strided views allowed), cand [B, N, D], remaining [B, N] -> (user [B, D] or None, logits [B, N] or
+    None).  ``fused`` False: the same function on the two existing kernels (default: FUSED_POOL_MATCH)."""
+    lib = _lib.load()
+    _mat(hidden, 'hidden')
+    _mat(x, 'x')
+    A, D = hidden.shape[1], x.shape[1]
+    if hidden.shape[0] != B * H or x.shape[0] != B * H:
+        raise ValueError('hidden and x must have B * H rows')
+    if not (want_user or want_logits):
+        raise ValueError('pool_match: nothing to compute')
+    N = 1
+    if want_logits:
+        if cand is None or cand.dim() != 3 or cand.shape[0] != B or cand.shape[2] != D:
+            raise ValueError('cand must be [B, N, D]')
+        N = cand.shape[1]
+        cand = _vec(cand.contiguous(), 'cand', B * N * D)
+        if use_weight:
+            remaining = _vec(remaining.contiguous(), 'remaining', B * N)
+    if not (FUSED_POOL_MATCH if fused is None else fused):
+        user = additive_pool(hidden, affine2, x, B, H, mask=mask)
+        logits = None
+        if want_logits:
+            logits = lifetime_score(user.unsqueeze(1).expand(B, N, D), cand, remaining, alpha, beta, use_weight, use_penalty)
+        return (user if want_user else None), logits
+    m = _mask_u8(mask, 'mask')
+    if m is not None and m.numel() != B * H:
+        raise ValueError('mask must have B * H elements')
+    user = torch.empty((B, D), dtype=torch.float32, device=x.device) if want_user else None
+    logits = torch.empty((B, N), dtype=torch.float32, device=x.device) if want_logits else None
+    check(lib.lime_pool_match_f32(_p(hidden), _ld(hidden), _p(_vec(affine2, 'affine2', A)), _p(x), _ld(x), _p(m), _p(cand) if want_logits else None,
+                                  _p(remaining) if want_logits and use_weight else None, alpha, beta, int(use_weight), int(use_penalty),
+                                  _p(user), _p(logits), B, N, H, A, D, _stream()), 'lime_pool_match_f32')
+    return user, logits
+
+
 def row_scale(x, scale):
     lib = _lib.load()
     D = x.shape[-1]

@@ -183,24 +183,35 @@ class _Dropout(torch.autograd.Function):
 
 class _MaskedAttention(torch.autograd.Function):
     """The attention core of layers.MultiHeadAttention (layers.py:227-237): softmax(Q K^T / sqrt(d_k), key mask -1e9) V on the
-    packed [tokens, 3 h d_k] projections."""
+    packed [tokens, 3 h d_k] projections.
+
+    ``center_keys`` (the MHSA user encoder): the exact dK of a sequence sums to zero over its live keys in every column -- each
+    query's dS row sums to zero, and masked keys get none -- while the kernel's rows keep a common residue (delta times the rounding
+    of 1 / sum in its probabilities, some 4e-7 of the largest entry).  The residue is all that the K bias gradient, the column sum
+    of dK, consists of.  Subtracting the live keys' column mean per sequence is the projection onto what the exact gradient
+    satisfies: it takes error out and no signal."""
 
     @staticmethod
-    def forward(ctx, qkv, mask, n_seq, S, h, dk):
+    def forward(ctx, qkv, mask, n_seq, S, h, dk, center_keys=False):
         W = h * dk
         out = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], n_seq, S, h, dk, 1.0 / math.sqrt(float(dk)), key_mask=mask)
-        ctx.dims = (n_seq, S, h, dk)
+        ctx.dims = (n_seq, S, h, dk, center_keys)
         ctx.save_for_backward(qkv, mask)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, mask = ctx.saved_tensors
-        n_seq, S, h, dk = ctx.dims
+        n_seq, S, h, dk, center_keys = ctx.dims
         W = h * dk
         dqkv = ops.token_attention_bwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], dout.contiguous(), n_seq, S, h, dk,
                                        1.0 / math.sqrt(float(dk)), key_mask=mask)
-        return dqkv, None, None, None, None, None
+        if center_keys:
+            live = mask.reshape(n_seq, S, 1).to(dqkv.dtype)
+            d_k = dqkv[:, W:2 * W].view(n_seq, S, W)                       # a view: the subtraction lands in dqkv
+            mean = (d_k * live).sum(dim=1, keepdim=True) / live.sum(dim=1, keepdim=True).clamp(min=1.0)
+            d_k.sub_(mean * live)
+        return dqkv, None, None, None, None, None, None
 
 
 class _AdditivePool(torch.autograd.Function):
@@ -798,12 +809,56 @@ def _interest_inputs(ue, hist, cand, category, subCategory, user_category, user_
     return g, linear(g, ue.K), linear(cand, ue.Q)                                                                 # :161-162
 
 
+# dropout sites of the pooled user encoders (counter-based masks, csrc/dropout.h): the MHSA user encoder draws one seed per call for
+# site 0, the p = 0.5 dropout behind ``affine`` (userEncoders.py:487); the candidate-aware layer draws its own seed for its site 0 (the
+# per-head probabilities, layers.py:74), as under CROWN
+_SITE_USER_AFFINE = 0
+
+
+def pooled_user(ue, hist, category, user_category, user_history_mask):
+    """userEncoders.ATT / MHSA after the history is encoded (userEncoders.py:546-557, :470-489) -> ONE user vector per row [B, D] with
+    autograd: candidate-aware refinement on LIME's frozen category rows alone, (MHSA: masked self-attention, affine + dropout + ReLU,)
+    additive attention pooling without a mask."""
+    from .userEncoders import MHSA
+    B, H, D = hist.shape
+    ne = ue.news_encoder
+    if ue.use_candidate_aware_attn:
+        hist, _ = candidate_aware(ue.candidate_aware_attn, hist, embedding(ne.category_embedding.weight, user_category),
+                                  embedding(ne.category_embedding.weight, category), user_history_mask)
+    x = hist.reshape(B * H, D)
+    if isinstance(ue, MHSA):
+        ue.check_history_length(H)
+        mha = ue.multiheadAttention
+        if mha.d_k != mha.d_v:
+            raise NotImplementedError('d_k != d_v')
+        if H > 128:
+            raise NotImplementedError('the masked attention backward covers sequences of at most 128 rows (got a history of %d)' % H)
+        w = torch.cat([mha.W_Q.weight, mha.W_K.weight, mha.W_V.weight], dim=0)
+        b = torch.cat([mha.W_Q.bias, mha.W_K.bias, mha.W_V.bias], dim=0)
+        c = _MaskedAttention.apply(_Linear.apply(x, w, b, None), user_history_mask.contiguous(), B, H, mha.h, mha.d_k, True)   # :486
+        # relu(dropout(z)) of :487 as dropout(relu(z)): the mask scales by 0 or 1 / (1 - p) >= 0, which commutes with the ReLU exactly
+        x = _Linear.apply(c, ue.affine.weight, ue.affine.bias, 'relu')
+        if ue.training and ue.p_sequence > 0:
+            x = _Dropout.apply(x, float(ue.p_sequence), _draw_seed(), _SITE_USER_AFFINE)
+    att = ue.attention
+    hidden = linear(x, att.affine1, act='tanh')                                                                   # layers.py:288
+    return _AdditivePool.apply(hidden, att.affine2.weight.view(-1), x, None, B, H)                                # :489 / :557: no mask
+
+
+def _is_crown_user(ue):
+    from .userEncoders import CROWN
+    return isinstance(ue, CROWN)
+
+
 def user_logits(ue, weighting, hist, cand, category, subCategory, user_category, user_subCategory, user_history_mask,
                 remaining_lifetime, n_src=None):
-    """userEncoders.CROWN.forward after the history is encoded (userEncoders.py:103-105, :114-169) and the lifetime-weighted dot
-    product of model.py:181 / util.py:23-49 -> logits [B, N]."""
+    """The user encoder's forward after the history is encoded and the lifetime-weighted dot product of model.py:181 / util.py:23-49
+    -> logits [B, N].  CROWN: userEncoders.py:103-105, :114-169; ATT / MHSA: ``pooled_user`` + ``lifetime_weighted_logits``."""
     B, H, D = hist.shape
     N = cand.shape[1]
+    if not _is_crown_user(ue):
+        user = pooled_user(ue, hist, category, user_category, user_history_mask)
+        return lifetime_weighted_logits(weighting, user.unsqueeze(1), cand, remaining_lifetime)
     g, kp, qp = _interest_inputs(ue, hist, cand, category, subCategory, user_category, user_subCategory, user_history_mask, n_src)
     A = kp.shape[-1]
     w = weighting
@@ -815,7 +870,11 @@ def user_logits(ue, weighting, hist, cand, category, subCategory, user_category,
 def user_representation(ue, hist, cand, category, subCategory, user_category, user_subCategory, user_history_mask, n_src=None):
     """``user_encoder(...)`` called on its own in training mode (userEncoders.py:101-175) -> user_representation [B, N, D] with
     autograd.  The model's own forward never materialises this tensor (``user_logits`` fuses the attention with the dot product);
-    the last two steps (:163-168: softmax over the history, weighted sum) are two batched torch matmuls here."""
+    the last two steps (:163-168: softmax over the history, weighted sum) are two batched torch matmuls here.  ATT / MHSA: the pooled
+    vector over the news_num axis (:489, :557)."""
+    if not _is_crown_user(ue):
+        user = pooled_user(ue, hist, category, user_category, user_history_mask)
+        return user.unsqueeze(1).expand(-1, cand.shape[1], -1)
     g, kp, qp = _interest_inputs(ue, hist, cand, category, subCategory, user_category, user_subCategory, user_history_mask, n_src)
     a = torch.softmax(torch.bmm(qp, kp.transpose(1, 2)) / ue.attention_scalar, dim=2)                             # [B, N, H]
     return torch.bmm(a, g)
@@ -827,9 +886,11 @@ def lifetime_weighted_logits(w, user, news, remaining_lifetime):
     if not w.use_remaining_lifetime_weighting:
         return base
     r = remaining_lifetime.float()
-    weight = torch.sigmoid(w.alpha * r)
-    if w.use_expired_penalty:
+    if w.use_expired_penalty:                                                                   # util.py:39-43
+        weight = torch.sigmoid(w.alpha * r)
         weight = torch.where(r < 0, w.beta * weight, weight)
+    else:
+        weight = torch.sigmoid(w.alpha * r.abs())                                               # util.py:46
     return base * weight
 
 
@@ -910,8 +971,37 @@ class _NllSoftmax(torch.autograd.Function):
 
 
 # parameters the reference constructs and never uses on this path: autograd leaves their .grad at None, Adam and
-# clip_grad_norm_ skip them, and so does the flat bucket
+# clip_grad_norm_ skip them, and so does the flat bucket.  Substrings of the parameter names, for the CROWN user encoder:
 _DEAD = ('base_news_encoder.affine.', '.ISAB.', 'category_predictor.', 'user_encoder.affine.', 'candidate_aware_attn.value_proj.')
+
+
+def dead_parameters(model):
+    """Names (as ``model.named_parameters()`` first yields them) of the trainable parameters the reference's backward leaves at None
+    for this model -- a function of the user and the content encoder:
+      * CROWN user encoder: the ``_DEAD`` substrings (its own unused ``affine`` among them; LIME's ``category_affine`` is live, it
+        makes the topic vectors of the candidate-aware attention, userEncoders.py:103-105).
+      * ATT / MHSA: the candidate-aware attention reads ``category_embedding`` rows alone (:470,482 / :546,554), so
+        ``news_encoder.category_affine`` is dead; MHSA's ``user_encoder.affine`` is live (:487).  Dead as before: the base encoder's unused
+        ``affine``, ``candidate_aware_attn.value_proj`` and, for the CROWN content encoder, ``ISAB`` and ``category_predictor``; with
+        ``use_residual_connection`` off also the layer's ``gate_proj`` and ``layernorm`` (layers.py:84)."""
+    from .userEncoders import CROWN
+    names, seen = [], set()
+    crown = isinstance(model.user_encoder, CROWN)
+    caa = getattr(model.user_encoder, 'candidate_aware_attn', None)
+    no_residual = caa is not None and not caa.use_residual_connection          # layers.py:84: agg * x alone, gate and LayerNorm unused
+    for name, p in model.named_parameters():
+        if not p.requires_grad or id(p) in seen:
+            continue
+        seen.add(id(p))
+        if crown:
+            dead = any(d in name for d in _DEAD)
+        else:
+            dead = (name.startswith('news_encoder.category_affine.') or name.startswith('news_encoder.base_news_encoder.affine.')
+                    or '.ISAB.' in name or 'category_predictor.' in name or 'candidate_aware_attn.value_proj.' in name
+                    or (no_residual and ('candidate_aware_attn.gate_proj.' in name or 'candidate_aware_attn.layernorm.' in name)))
+        if dead:
+            names.append(name)
+    return names
 
 
 class TrainStep:
@@ -932,12 +1022,8 @@ class TrainStep:
         self.model = model
         self.lr, self.weight_decay, self.clip, self.betas, self.eps = lr, weight_decay, gradient_clip_norm, betas, eps
         self.group = process_group
-        named, seen = [], set()
-        for name, p in model.named_parameters():
-            if not p.requires_grad or id(p) in seen or any(d in name for d in _DEAD):
-                continue
-            seen.add(id(p))
-            named.append((name, p))
+        params = dict(model.named_parameters())
+        named = [(n, params[n]) for n in self.bucket_names(model)]
         self.names = [n for n, _ in named]
         self._params = named
         # every parameter starts on a 256-byte boundary of the bucket (the LDS-DMA GEMM wants 16-byte aligned operands);
@@ -962,6 +1048,21 @@ class TrainStep:
             model._graphs = {}                  # captured scoring graphs hold the parameters' old addresses
         self.step_count = 0
         self.last_norm = None
+
+    @staticmethod
+    def bucket_names(model):
+        """The parameters of the flat bucket, in bucket order: every trainable parameter (once: the user encoder's view of the news
+        encoder repeats names) that the reference's backward gives a gradient -- ``dead_parameters(model)`` are left out."""
+        dead = set(dead_parameters(model)) if hasattr(model, 'user_encoder') else None
+        names, seen = [], set()
+        for name, p in model.named_parameters():
+            if not p.requires_grad or id(p) in seen:
+                continue
+            seen.add(id(p))
+            if name in dead if dead is not None else any(d in name for d in _DEAD):
+                continue
+            names.append(name)
+        return names
 
     def backward(self, loss):
         """``loss.backward()`` with the gradients landing in the flat bucket.  The parameters' ``.grad`` views are taken away for

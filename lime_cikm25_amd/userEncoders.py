@@ -1,11 +1,11 @@
-"""Drop-in CROWN user encoder of the scoring path (reference userEncoders.py:16-175)."""
+"""Drop-in user encoders of the scoring path: CROWN (reference userEncoders.py:16-175), ATT (:529-558) and MHSA (:447-490)."""
 import math
 
 import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import CandidateAware_ClickedNewsAttention
+from .layers import Attention, CandidateAware_ClickedNewsAttention, MultiHeadAttention
 
 
 class SAGEConv(nn.Module):
@@ -218,3 +218,184 @@ class CROWN(UserEncoder):
         user, _ = self.match(history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask,
                              candidate_news_representation)
         return user
+
+
+class _PooledUser(UserEncoder):
+    """What ATT and MHSA share (userEncoders.py:447-490, :529-558): optional candidate-aware refinement of the history, an encoder-specific
+    step over the refined rows (``_sequence``), additive attention pooling WITHOUT a mask (:489, :557 -- padded slots take part in the
+    softmax) into ONE user vector per row, returned over the news_num axis.  The topic embeddings of the candidate-aware attention are
+    LIME's frozen ``category_embedding`` rows alone (:470,482 / :546,554): no ``category_affine``, no subcategory."""
+
+    p_sequence = 0.0                 # probability of the training-mode dropout inside ``_sequence``
+
+    def _init_candidate_aware(self, news_encoder, config):
+        self.use_candidate_aware_attn = config.use_candidate_ware_clicked_news_attention
+        if self.use_candidate_aware_attn:
+            self.candidate_aware_attn = CandidateAware_ClickedNewsAttention(config, news_encoder)
+
+    def _topic(self, category):
+        table = self.news_encoder.category_embedding.weight
+        idx = category.reshape(-1)
+        idx = (idx if idx.dtype == torch.int32 else idx.to(torch.int32)).contiguous()
+        out = torch.empty((idx.numel(), table.shape[1]), dtype=torch.float32, device=table.device)
+        ops.gather_rows(idx, table, out)
+        return out.view(*category.shape, -1)
+
+    def _train_dropouts(self):
+        p_caa = self.candidate_aware_attn.dropout.p if self.use_candidate_aware_attn else 0.0
+        return max(self.p_sequence, p_caa)
+
+    def attention_weights(self, category, subCategory, user_category, user_subCategory, user_history_mask, hist_div=1):
+        """The candidate-aware attention weights agg [B, H] (layers.py:66-81) from the category ids and the history mask alone (the
+        model computes them on a side stream); ``subCategory`` / ``user_subCategory`` are accepted and not read."""
+        if not self.use_candidate_aware_attn:
+            return None
+        if self.training and self.candidate_aware_attn.dropout.p > 0:
+            raise NotImplementedError('attention_weights() is the scoring kernel: in training mode the layer\'s p = 0.2 dropout '
+                                      '(layers.py:36,74) runs on the differentiable path (user_encoder(...) / Model.forward)')
+        return self.candidate_aware_attn.attention_weights(self._topic(user_category), self._topic(category), user_history_mask,
+                                                           hist_div=hist_div)
+
+    def gate_projection(self, history_embedding):
+        """W_g x of the candidate-aware attention's gate (layers.py:87) for histories [*, H, D] -> [* H, D], or None when ``match``
+        does not take the one-launch refinement."""
+        caa = self.candidate_aware_attn if self.use_candidate_aware_attn else None
+        D = history_embedding.shape[-1]
+        if caa is None or not caa.use_residual_connection or D > 512:
+            return None
+        return ops.linear(history_embedding.reshape(-1, D), caa.gate_proj.weight, None)
+
+    def _sequence(self, x, mask, rows, H, taps=None):
+        """x [rows * H, D] refined history rows -> the rows the attention pools (same shape); mask u8 / bool [rows, H]."""
+        raise NotImplementedError
+
+    def match(self, history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask,
+              candidate_news_representation, remaining_lifetime=None, weighting=None, agg=None, n_src=None, hist_div=1,
+              gate_y=None, taps=None):
+        """Everything after the history has been encoded.  Returns (user_representation [B, N, D], logits [B, N] or None), the
+        interface of ``CROWN.match``; ``n_src`` is CROWN's (GraphSAGE) and is ignored.  ``hist_div`` > 1: ``history_embedding``,
+        the history's category ids and mask hold ONE history for hist_div consecutive candidate rows; it is read through
+        row / hist_div by the refinement kernel and never repeated in memory before it.  The refined rows do differ per
+        candidate row (through ``agg``) and are materialised: with the tanh hidden state (D + A) * 4 bytes per (row, slot) under ATT, the caller bounds
+        the rows of a call (Model.score_impressions: rows_per_pass).  ``taps``: optional dict that receives the intermediate
+        tensors (tests)."""
+        if self.training and self._train_dropouts() > 0:
+            raise NotImplementedError('match() is the fused scoring kernel chain: with training-mode dropouts active (userEncoders.py:487, '
+                                      'layers.py:74) call user_encoder(...) or Model.forward, which take the differentiable path')
+        Bh, H, D = history_embedding.shape
+        B = Bh * hist_div
+        N = candidate_news_representation.shape[1]
+        cand = candidate_news_representation.contiguous()
+        caa = self.candidate_aware_attn if self.use_candidate_aware_attn else None
+        mask = user_history_mask
+        if caa is None:
+            # no refinement: the hist_div rows of a history share ONE user vector -- pool each history once, against its
+            # hist_div * N candidates
+            rows, n_cand = Bh, hist_div * N
+            x = history_embedding.reshape(Bh * H, D)
+        else:
+            rows, n_cand = B, N
+            if agg is None:
+                agg = self.attention_weights(category, subCategory, user_category, user_subCategory, user_history_mask, hist_div=hist_div)
+            if caa.use_residual_connection and D <= 512:
+                y = gate_y if gate_y is not None else ops.linear(history_embedding.reshape(Bh * H, D), caa.gate_proj.weight, None)
+                # gated residual + LayerNorm of each row's H history rows in one launch, reading a shared history through row / hist_div
+                # (the kernel's GraphSAGE column mean is CROWN's and is dropped)
+                x, _ = ops.gate_ln_sage(y, history_embedding.reshape(Bh * H, D), agg.reshape(-1), caa.gate_proj.bias, caa.layernorm.weight,
+                                        caa.layernorm.bias, caa.layernorm.eps, B, H, D, hist_div, H, None)
+            else:
+                hist = history_embedding if hist_div == 1 else history_embedding.repeat_interleave(hist_div, dim=0)
+                x = caa.refine(hist, agg).view(B * H, D)
+            if hist_div > 1:
+                mask = mask.repeat_interleave(hist_div, dim=0)
+        if taps is not None:
+            taps['hist_refined'] = x.view(rows, H, D)
+        x = self._sequence(x, mask, rows, H, taps)
+        att = self.attention
+        hidden = ops.linear(x, att.affine1.weight, att.affine1.bias, act='tanh')                           # layers.py:288
+        w = weighting
+        rl = remaining_lifetime.reshape(rows, n_cand) if (w is not None and remaining_lifetime is not None) else None
+        user, logits = ops.pool_match(
+            hidden, att.affine2.weight.view(-1), x, rows, H, cand=cand.view(rows, n_cand, D) if w is not None else None, remaining=rl,
+            alpha=w.alpha if w is not None else 0.0, beta=w.beta if w is not None else 0.0,
+            use_weight=bool(w.use_remaining_lifetime_weighting) if w is not None else False,
+            use_penalty=bool(w.use_expired_penalty) if w is not None else False,
+            mask=None, want_user=True, want_logits=w is not None)                                          # layers.py:289-299, util.py:23-49
+        if rows != B:
+            user = user.unsqueeze(1).expand(Bh, hist_div, D).reshape(B, D)
+        return user.unsqueeze(1).expand(B, N, D), (logits.view(B, N) if logits is not None else None)
+
+    def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
+                user_content_entity, category, subCategory, user_category, user_subCategory, user_history_mask,
+                user_history_graph, user_history_category_mask, user_history_category_indices, user_embedding,
+                candidate_news_representation, user_freshness, user_user_topic_lifetime):
+        history_embedding = self.news_encoder(user_title_text, user_title_mask, user_title_entity, user_content_text,
+                                              user_content_mask, user_content_entity, user_category, user_subCategory,
+                                              user_embedding, user_freshness, user_user_topic_lifetime)
+        from . import training
+        if training.wants_train_path(self, self._train_dropouts()):
+            i32 = lambda t: (t if t.dtype == torch.int32 else t.to(torch.int32)).contiguous()
+            return training.user_representation(self, history_embedding, candidate_news_representation.float(), i32(category),
+                                                i32(subCategory), i32(user_category), i32(user_subCategory),
+                                                user_history_mask.contiguous())
+        user, _ = self.match(history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask,
+                             candidate_news_representation)
+        return user
+
+
+class ATT(_PooledUser):
+    """userEncoders.py:529-558 (NAML's user encoder): additive attention over the (candidate-aware refined) history."""
+
+    def __init__(self, news_encoder, config):
+        super().__init__(news_encoder, config)
+        self.attention = Attention(self.news_embedding_dim, config.attention_dim)
+        self._init_candidate_aware(news_encoder, config)
+
+    def initialize(self):
+        self.attention.initialize()
+        if self.use_candidate_aware_attn:
+            self.candidate_aware_attn.initialize()
+
+    def _sequence(self, x, mask, rows, H, taps=None):
+        return x
+
+
+class MHSA(_PooledUser):
+    """userEncoders.py:447-490 (NRMS's user encoder): masked multi-head self-attention over the refined history, ``affine`` + dropout +
+    ReLU, then ATT's pool.  The dropout behind ``affine`` is ``F.dropout(..., training=self.training)`` with no ``p`` (:487): 0.5 in
+    training mode whatever config.dropout_rate says.  The self-attention's view (layers.py:224-226) fixes the history length to
+    config.max_history_num."""
+
+    p_sequence = 0.5
+
+    def __init__(self, news_encoder, config):
+        super().__init__(news_encoder, config)
+        self.multiheadAttention = MultiHeadAttention(config.head_num, self.news_embedding_dim, config.max_history_num,
+                                                     config.max_history_num, config.head_dim, config.head_dim)
+        self.affine = nn.Linear(config.head_num * config.head_dim, self.news_embedding_dim, bias=True)
+        self.attention = Attention(self.news_embedding_dim, config.attention_dim)
+        self._init_candidate_aware(news_encoder, config)
+
+    def initialize(self):
+        self.multiheadAttention.initialize()
+        nn.init.xavier_uniform_(self.affine.weight, gain=nn.init.calculate_gain('relu'))
+        nn.init.zeros_(self.affine.bias)
+        self.attention.initialize()
+        if self.use_candidate_aware_attn:
+            self.candidate_aware_attn.initialize()
+
+    def check_history_length(self, H):
+        mha = self.multiheadAttention
+        if H != mha.len_q:
+            raise ValueError('the MHSA user encoder attends over exactly config.max_history_num = %d history slots (layers.py:224-226), '
+                             'got a history of %d' % (mha.len_q, H))
+
+    def _sequence(self, x, mask, rows, H, taps=None):
+        self.check_history_length(H)
+        mha = self.multiheadAttention
+        c = mha.attend(mha.project(x), rows, H, mask.reshape(-1))                                           # :486, layers.py:222-238
+        h = ops.linear(c, self.affine.weight, self.affine.bias, act='relu')                                 # :487 (eval: no dropout)
+        if taps is not None:
+            taps['self_attention'] = c.view(rows, H, -1)
+            taps['post_affine'] = h.view(rows, H, -1)
+        return h

@@ -97,7 +97,8 @@ def compute_scores_cached(model, behaviors, indices, result_file, truth_file=Non
     if config.lifetime_type not in ('fixed', 'topic_wise', 'user_topic'):
         raise ValueError('Invalid lifetime_type')
     per = rows_per_forward or config.batch_size
-    slots = behaviors.hist_index.shape[1] + model.user_encoder.user_node_embedding.shape[0]
+    nodes = getattr(model.user_encoder, 'user_node_embedding', None)       # CROWN's GraphSAGE node slots; ATT / MHSA have no such bound
+    slots = behaviors.hist_index.shape[1] + nodes.shape[0] if nodes is not None else per
     if per > slots:
         raise ValueError('rows_per_forward = %d exceeds the H + config.batch_size = %d GraphSAGE node slots (SURVEY Q7): the '
                          'reference raises an index error there' % (per, slots))
