@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 10
+#define LIME_ABI_VERSION 11
 
 typedef enum {
     LIME_OK = 0,
@@ -811,6 +811,48 @@ int lime_pool_match_f32(const float* hidden, int64_t ldh, const float* w2, const
                         const float* cand, const float* remaining, float alpha_s, float beta_s, int32_t use_weight,
                         int32_t use_penalty, float* user_rep, float* logits, int32_t B, int32_t N, int32_t H, int32_t A, int32_t D,
                         void* stream);
+
+/* =====================================================================================================
+ * The dev / test pass behind the scores in one call (util.py:113-123 rank rule + evaluate.py:32-89 metrics;
+ * csrc/rank_metrics.hip): per impression the 1-based rank of every candidate row under a stable descending order
+ *     rank_i = 1 + #{j in the impression : s_j > s_i or (s_j == s_i and j < i)}       (+0.0 ties with -0.0)
+ * and, from the ranks q of its P positives among n rows (N = n - P; ahead_pos = positives ranked ahead of the row),
+ *     AUC    = (P N - sum_pos (q - 1 - ahead_pos)) / (P N)
+ *     MRR    = (sum_pos 1 / q) / P
+ *     nDCG@k = (sum_pos, q <= k  disc[q - 1]) / (sum_{p < min(k, P)} disc[p])          k = 5, 10
+ * -- what evaluate.scoring computes from the rank file, which feeds 1 / rank into every metric.
+ *   scores fp32 [R], labels u8 [R] (0 / 1), offsets int32 [n_imp + 1] (rows offsets[i] .. offsets[i + 1] - 1 belong to impression i;
+ *   non-decreasing, offsets[n_imp] == R: the caller checks that, the kernel clamps every offset into [0, R]), skip u8 [n_imp] or
+ *   NULL (non-zero: the impression's truth line has no labels; it is ranked but not counted), disc fp64 [10] = 1 / log2(p + 2).
+ *   ranks int32 [R]; per_imp fp64 [n_imp, 4] = AUC, MRR, nDCG@5, nDCG@10 (zeros unless status is 0);
+ *   status int32 [n_imp]: 0 counted, 1 skipped or no rows, 2 one class only, 3 a label outside {0, 1} or a NaN score (checked in
+ *   that order; the ranks of a status-3 impression follow the counting rule under IEEE comparisons);
+ *   sums fp64 [4] and count int64 [1]: over the status == 0 impressions (their means are the split's metrics; a sharded pass
+ *   all-reduces these five numbers).
+ * A wave per impression up to 512 rows, a workgroup above (any length).  Bitwise reproducible and independent of the grids: fixed
+ * summation orders, no atomics.  rank_blocks / reduce_blocks: workgroups of the rank launch and of the first reduction level, 0 = the
+ * default (tests and A/B runs).  workspace: lime_rank_metrics_workspace(n_imp) bytes, 8-byte aligned; per_imp 16-byte aligned. */
+typedef struct {
+    const float* scores;
+    const uint8_t* labels;
+    const int32_t* offsets;
+    const uint8_t* skip;
+    const double* disc;
+    int32_t* ranks;
+    double* per_imp;
+    int32_t* status;
+    double* sums;
+    int64_t* count;
+    void* workspace;      int64_t workspace_bytes;
+    int64_t R;
+    int32_t n_imp;
+    int32_t rank_blocks;
+    int32_t reduce_blocks;
+    int32_t reserved;     /* must be 0 */
+} lime_rank_metrics_args;
+
+int64_t lime_rank_metrics_workspace(int32_t n_imp);
+int lime_rank_metrics(const lime_rank_metrics_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_ui
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblime_hip.so')
 
-ABI_VERSION = 10         # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
+ABI_VERSION = 11         # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
 LIME_ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'relu_grad': 4}
 
 
@@ -134,6 +134,17 @@ class GatherDesc(ctypes.Structure):
 
 
 MAX_GATHERS = 16
+
+
+class RankMetricsArgs(ctypes.Structure):
+    """lime_rank_metrics_args of include/lime_hip.h (same field order)."""
+    _fields_ = [
+        ('scores', c_void_p), ('labels', c_void_p), ('offsets', c_void_p), ('skip', c_void_p), ('disc', c_void_p),
+        ('ranks', c_void_p), ('per_imp', c_void_p), ('status', c_void_p), ('sums', c_void_p), ('count', c_void_p),
+        ('workspace', c_void_p), ('workspace_bytes', c_int64),
+        ('R', c_int64),
+        ('n_imp', c_int32), ('rank_blocks', c_int32), ('reduce_blocks', c_int32), ('reserved', c_int32),
+    ]
 
 # name -> (restype, argtypes); every symbol include/lime_hip.h declares
 SIGNATURES = {
@@ -283,6 +294,9 @@ SIGNATURES = {
     # ATT / MHSA user encoders: attention pool over the history + candidate match + lifetime weight
     'lime_pool_match_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    # device-side dev / test pass: ranks and AUC / MRR / nDCG per impression, their sums
+    'lime_rank_metrics_workspace': (c_int64, [c_int32]),
+    'lime_rank_metrics': (c_int32, [ctypes.POINTER(RankMetricsArgs), c_void_p]),
 }
 
 _lib = None

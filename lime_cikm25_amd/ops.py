@@ -1686,3 +1686,100 @@ def attn_pool(x, w1, b1, w2, n_seq, T, mask=None, out=None, n_seq_dev=None, w1p=
     check(lib.lime_attn_pool_sp_f32(_p(x), _ld(x), D, _p(w1p), _p(b1), _p(w2), A, _p(m), _p(out), _ld(out), n_seq, T, _p(n_seq_dev),
                                     _stream()), 'lime_attn_pool_sp_f32')
     return out
+
+
+# ---- device-side dev / test pass: ranks + AUC / MRR / nDCG per impression (csrc/rank_metrics.hip) -----------------------------------
+class RankMetrics:
+    """Result of ``rank_metrics``: ``ranks`` int32 [R] (1-based inside the impression), ``per_impression`` fp64 [n_imp, 4] (AUC, MRR,
+    nDCG@5, nDCG@10; zeros unless status is 0), ``status`` int32 [n_imp] (0 counted, 1 skipped or no rows, 2 one class only, 3 a label
+    outside {0, 1} or a NaN score), ``sums`` fp64 [4] and ``count`` int64 [1] over the status == 0 impressions -- all device tensors."""
+    __slots__ = ('ranks', 'per_impression', 'status', 'sums', 'count')
+
+    def __init__(self, ranks, per_impression, status, sums, count):
+        self.ranks, self.per_impression, self.status, self.sums, self.count = ranks, per_impression, status, sums, count
+
+    def means(self):
+        """(AUC, MRR, nDCG@5, nDCG@10) over the counted impressions as Python floats (one device -> host copy)."""
+        s, c = self.sums.cpu().numpy(), int(self.count.cpu()[0])
+        return tuple(float(v) for v in (s / c if c else s * float('nan')))
+
+
+_DISC = {}
+
+
+def _ndcg_discounts(device):
+    """1 / log2(p + 2), p = 0..9, with numpy's bits (evaluate.dcg_score divides by np.log2)."""
+    key = str(device)
+    if key not in _DISC:
+        import numpy as np
+        _DISC[key] = torch.from_numpy(1.0 / np.log2(np.arange(10) + 2.0)).to(device)
+    return _DISC[key]
+
+
+def check_offsets(offsets, R):
+    """``offsets`` of ``rank_metrics`` as a host int32 array after the checks a launch relies on: 1-D, at least one entry, starts at
+    0, non-decreasing, ends at R.  Raises ValueError; no device work."""
+    import numpy as np
+    o = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets)
+    if o.ndim != 1 or o.size < 1 or o.dtype.kind not in 'iu':
+        raise ValueError('offsets must be a 1-D integer array of n_imp + 1 entries')
+    o = o.astype(np.int64)
+    if o[0] != 0 or o[-1] != R:
+        raise ValueError('offsets must start at 0 and end at the row count %d, got %d .. %d' % (R, o[0], o[-1]))
+    if o.size > 1 and (np.diff(o) < 0).any():
+        raise ValueError('offsets must be non-decreasing (the rows of an impression are contiguous): first decrease at entry %d'
+                         % (int(np.argmax(np.diff(o) < 0)) + 1))
+    if R > 2 ** 31 - 1:
+        raise ValueError('rank_metrics takes up to 2^31 - 1 rows')
+    return o.astype(np.int32)
+
+
+def rank_metrics(scores, labels, offsets, skip=None, rank_blocks=0, reduce_blocks=0):
+    """``lime_rank_metrics``: the dev / test pass behind the scores in one call.  scores fp32 [R], labels uint8 [R] (0 / 1) and the
+    optional skip uint8 / bool [n_imp] are CUDA tensors; ``offsets`` (n_imp + 1 entries, rows offsets[i] .. offsets[i + 1] - 1 are
+    impression i) is a host array / list / CPU tensor, checked on the host and copied, or an int32 CUDA tensor, whose check costs one
+    device -> host copy.  Returns a ``RankMetrics``.  ``rank_blocks`` / ``reduce_blocks``: workgroup counts of the rank launch and of
+    the first reduction level (0: default); the result does not depend on them."""
+    if not isinstance(scores, torch.Tensor) or not isinstance(labels, torch.Tensor):
+        raise TypeError('scores and labels must be CUDA tensors (the HIP path has no CPU fallback)')
+    R = scores.numel()
+    off_host = check_offsets(offsets, R)                    # ValueError before anything touches the device
+    n_imp = off_host.size - 1
+    if not scores.is_cuda or not labels.is_cuda or (isinstance(skip, torch.Tensor) and not skip.is_cuda):
+        raise TypeError('scores, labels and skip must be CUDA tensors (the HIP path has no CPU fallback)')
+    _vec(scores, 'scores')
+    _vec(labels, 'labels', R, dtype=torch.uint8)
+    if scores.dim() != 1:
+        raise ValueError('scores must be 1-D')
+    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+        if offsets.dtype != torch.int32 or not offsets.is_contiguous():
+            raise TypeError('a CUDA offsets tensor must be contiguous int32')
+        off = offsets
+    else:
+        off = torch.from_numpy(off_host).to(scores.device)
+    sk = None
+    if skip is not None:
+        if not isinstance(skip, torch.Tensor):
+            raise TypeError('skip must be a CUDA uint8 / bool tensor')
+        sk = _mask_u8(skip, 'skip')
+        if sk.numel() != n_imp:
+            raise ValueError('skip must have one entry per impression (%d), got %d' % (n_imp, sk.numel()))
+    if rank_blocks < 0 or reduce_blocks < 0:
+        raise ValueError('rank_blocks and reduce_blocks must be >= 0')
+    lib = _lib.load()
+    dev = scores.device
+    ranks = torch.empty(R, dtype=torch.int32, device=dev)
+    per_imp = torch.empty((n_imp, 4), dtype=torch.float64, device=dev)
+    status = torch.empty(n_imp, dtype=torch.int32, device=dev)
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ws_bytes = int(lib.lime_rank_metrics_workspace(n_imp))
+    ws = torch.empty(max(1, (ws_bytes + 7) // 8), dtype=torch.float64, device=dev)
+    disc = _ndcg_discounts(dev)
+    a = _lib.RankMetricsArgs()
+    a.scores, a.labels, a.offsets, a.skip, a.disc = scores.data_ptr(), labels.data_ptr(), off.data_ptr(), (sk.data_ptr() if sk is not None else None), disc.data_ptr()
+    a.ranks, a.per_imp, a.status, a.sums, a.count = ranks.data_ptr(), per_imp.data_ptr(), status.data_ptr(), sums.data_ptr(), count.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    a.R, a.n_imp, a.rank_blocks, a.reduce_blocks, a.reserved = R, n_imp, int(rank_blocks), int(reduce_blocks), 0
+    check(lib.lime_rank_metrics(ctypes.byref(a), _stream()), 'lime_rank_metrics')
+    return RankMetrics(ranks, per_imp, status, sums, count)

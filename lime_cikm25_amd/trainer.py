@@ -26,12 +26,13 @@ def _mkdir(path):
 
 
 class Trainer:
-    def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True):
+    def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True, device_eval=False):
         """``truth_file``: the dev truth file of config.py:262-276 ("<impression> [labels]" lines).  Without one it is written
         (as the reference's Config does at start-up) to ``<dev_res_dir>/../ref/truth-<dataset>.txt`` from ``corpus.dev_labels``
         (formats.build_corpus attaches them); a corpus without labels and no file is refused here, before any training.
         ``cached_eval``: the dev pass encodes every news once (util.compute_scores_cached) instead of once per row and slot; same
-        scores.
+        scores.  ``device_eval``: where the cached pass applies and the corpus carries ``dev_labels``, the dev pass also ranks and
+        scores on the device (util.evaluate_cached_on_device): the same rank file, metrics equal to rounding; off by default.
 
         Under torch.distributed (WORLD_SIZE in the environment) the process group is initialised and the device selected
         FIRST, so that TrainStep's broadcast of rank 0's parameters really runs (DistributedDataParallel does that at
@@ -68,6 +69,7 @@ class Trainer:
         if getattr(config, 'dropout_rate', 0.0) == 0.0 and self.rank == 0:
             print('Trainer: config.dropout_rate is 0 -- the reference trains with 0.2 (config.py:78); pass dropout_rate=0.2 for its recipe')
         self.cached_eval = cached_eval and config.lifetime_type == 'user_topic' and config.fusion_method == 'concat'
+        self.device_eval = bool(device_eval) and self.cached_eval and getattr(corpus, 'dev_labels', None) is not None
         self.dc = device_corpus if device_corpus is not None else DeviceCorpus(corpus)
         self.dev = DeviceBehaviors.from_devtest(self.dc, corpus, 'dev')
         self.step = TrainStep(model, lr=config.lr, weight_decay=config.weight_decay, gradient_clip_norm=config.gradient_clip_norm)
@@ -109,6 +111,9 @@ class Trainer:
         batch_size = 64 / max_history_num = 50)."""
         out = os.path.join(self.dev_res_dir, '%s-%d.txt' % (self.model.model_name, e))
         per = self.eval_batch_size
+        if self.cached_eval and self.device_eval:
+            return util.evaluate_cached_on_device(self.model, self.dev, self.corpus.dev_indices, self.corpus.dev_labels, result_file=out,
+                                                  rows_per_forward=per)
         if self.cached_eval:
             return util.compute_scores_cached(self.model, self.dev, self.corpus.dev_indices, out, self.truth_file, per)
         rows = list(range(self.dev.num))

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .evaluate import scoring
+from .evaluate import device_scoring, scoring
 
 
 class RemainingLifetimeWeighting(nn.Module):
@@ -117,3 +117,70 @@ def compute_scores_cached(model, behaviors, indices, result_file, truth_file=Non
         return None, None, None, None
     with open(truth_file, 'r', encoding='utf-8') as truth_f, open(result_file, 'r', encoding='utf-8') as result_f:
         return scoring(truth_f, result_f)
+
+
+def ranks_to_lists(ranks, indices):
+    """Device (or host) ranks, one per row -> the per-impression rank lists ``rank_impressions`` returns for the same rows: the
+    impressions 0 .. indices[-1], an empty list for an impression without rows."""
+    ranks = ranks.cpu().numpy() if isinstance(ranks, torch.Tensor) else np.asarray(ranks)
+    indices = np.asarray(indices, dtype=np.int64)
+    n_imp = int(indices[-1]) + 1 if indices.size else 0
+    bounds = np.searchsorted(indices, np.arange(n_imp + 1), side='left')
+    flat = ranks.tolist()
+    return [flat[bounds[i]:bounds[i + 1]] for i in range(n_imp)]
+
+
+# rows of one score_behaviors pass of evaluate_cached_on_device.  The user side of a pass materialises a few [rows, H, D] fp32
+# tensors: 0.41 MB a row measured at the default configuration (H = 50), 3.4 GB for the 8192 rows of the default; the whole pass takes
+# the same time from 4096 rows a pass up (DESIGN.md "Device-side evaluation", tools/bench_eval.py).
+DEVICE_EVAL_ROWS_PER_PASS = 8192
+
+
+def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=None, rows_per_forward=None,
+                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False):
+    """The dev / test pass of ``compute_scores_cached`` without host round trips: one ``build_news_cache``, ``score_behaviors`` in
+    passes of up to ``rows_per_pass`` rows that write into ONE device score buffer, one ``evaluate.device_scoring`` (ranks and
+    metrics in one launch, csrc/rank_metrics.hip), one device -> host copy of the result.  ``labels``: the per-impression label
+    lists (corpus.dev_labels / formats.truth_labels) in place of the truth file.  Returns (AUC, MRR, nDCG@5, nDCG@10); with
+    ``result_file`` the rank file is written from the device ranks -- the bytes ``rank_impressions`` gives for the same scores; with
+    ``return_scores`` the result is (metrics, the fp32 device score buffer).
+
+    The scores are those of ``compute_scores_cached(..., rows_per_forward)``: a row's score depends on the row count of the
+    reference's forward through the GraphSAGE source count and on nothing else of its pass, so the rows of the full
+    ``rows_per_forward`` chunks are scored many chunks at a time with n_src = rows_per_forward, and the rows of the last, short chunk
+    with n_src = its length.  (A pass of another row count may take GEMM kernels with another summation order: equal to fp32
+    rounding, bitwise equal when rows_per_pass == rows_per_forward.)  ``rows_per_pass`` bounds memory: a pass allocates 0.41 MB a row at the
+    default configuration (H = 50; measured, tools/bench_eval.py), 3.4 GB for the default of 8192 rows, and the whole pass is no
+    faster with more."""
+    config = model.config
+    if config.lifetime_type not in ('fixed', 'topic_wise', 'user_topic'):
+        raise ValueError('Invalid lifetime_type')
+    per = rows_per_forward or config.batch_size
+    nodes = getattr(model.user_encoder, 'user_node_embedding', None)       # CROWN's GraphSAGE node slots; ATT / MHSA have no such bound
+    slots = behaviors.hist_index.shape[1] + nodes.shape[0] if nodes is not None else per
+    if per > slots:
+        raise ValueError('rows_per_forward = %d exceeds the H + config.batch_size = %d GraphSAGE node slots (SURVEY Q7): the '
+                         'reference raises an index error there' % (per, slots))
+    if rows_per_pass < 1:
+        raise ValueError('rows_per_pass must be positive')
+    num = behaviors.num
+    assert num == len(indices), 'one score per (impression, candidate) row'
+    was_training = model.training
+    model.eval()
+    try:
+        cache = model.build_news_cache(behaviors.corpus)
+        dev = cache.device
+        scores = torch.empty(num, dtype=torch.float32, device=dev)
+        full = (num // per) * per                                          # the rows of the full chunks: n_src = per
+        step = max(1, rows_per_pass // per) * per
+        for r0 in range(0, full, step):
+            r1 = min(full, r0 + step)
+            scores[r0:r1] = model.score_behaviors(behaviors, torch.arange(r0, r1, device=dev), cache, n_src=per).float()
+        if full < num:                                                     # the last, short chunk: n_src = its length
+            scores[full:] = model.score_behaviors(behaviors, torch.arange(full, num, device=dev), cache, n_src=num - full).float()
+    finally:
+        model.train(was_training)
+    metrics, ranks = device_scoring(scores, indices, labels)
+    if result_file is not None:
+        write_rank_file(result_file, ranks_to_lists(ranks, indices))
+    return (metrics, scores) if return_scores else metrics
