@@ -83,13 +83,20 @@ def _side_stream(device, which=0):
 _ZERO_IDS = {}
 
 
+def _grown(cache, n, device, floor, make):
+    """The first n entries of a per-device constant (``make(size)``: all zeros, or an arange -- a prefix of either is right for every
+    n) that is allocated once and never written.  A captured HIP graph holds the ADDRESS of the tensor it was recorded with, so a
+    tensor once handed out is never released: when a caller needs more entries a new generation of at least twice the size is added
+    and the older ones stay alive in ``cache`` (at most as much memory again as the newest one), where a replay still finds them."""
+    gens = cache.setdefault((device.type, device.index), [])
+    if not gens or gens[-1].numel() < n:
+        gens.append(make(max(n, floor, 2 * gens[-1].numel() if gens else 0)))
+    return gens[-1][:n]
+
+
 def _zero_ids(n, device):
     """n zero word ids (the padding word), allocated once per device and never written: a forward does not pay a fill launch for them."""
-    key = (device.type, device.index)
-    z = _ZERO_IDS.get(key)
-    if z is None or z.numel() < n:
-        z = _ZERO_IDS[key] = torch.zeros(max(n, 512), dtype=torch.int32, device=device)
-    return z[:n]
+    return _grown(_ZERO_IDS, n, device, 512, lambda size: torch.zeros(size, dtype=torch.int32, device=device))
 
 
 def _cat_rows(ts):
@@ -596,11 +603,7 @@ _IDENT = {}
 
 def _identity_rows(n, device):
     """arange(n) int32, allocated once per device: the row map of an encoder layer behind the first (every compact row is its own)."""
-    key = (device.type, device.index)
-    z = _IDENT.get(key)
-    if z is None or z.numel() < n:
-        z = _IDENT[key] = torch.arange(max(n, 4096), dtype=torch.int32, device=device)
-    return z[:n]
+    return _grown(_IDENT, n, device, 4096, lambda size: torch.arange(size, dtype=torch.int32, device=device))
 
 
 def compact_run(prep, table, pe, transformer, nhead, pooled_out):

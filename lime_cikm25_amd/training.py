@@ -971,35 +971,39 @@ class _NllSoftmax(torch.autograd.Function):
 
 
 # parameters the reference constructs and never uses on this path: autograd leaves their .grad at None, Adam and
-# clip_grad_norm_ skip them, and so does the flat bucket.  Substrings of the parameter names, for the CROWN user encoder:
+# clip_grad_norm_ skip them, and so does the flat bucket.  Substrings of the parameter names, for the CROWN user encoder with every
+# switch of config.py:60-66 on (``dead_parameters`` is the rule for every model):
 _DEAD = ('base_news_encoder.affine.', '.ISAB.', 'category_predictor.', 'user_encoder.affine.', 'candidate_aware_attn.value_proj.')
 
 
 def dead_parameters(model):
     """Names (as ``model.named_parameters()`` first yields them) of the trainable parameters the reference's backward leaves at None
-    for this model -- a function of the user and the content encoder:
-      * CROWN user encoder: the ``_DEAD`` substrings (its own unused ``affine`` among them; LIME's ``category_affine`` is live, it
-        makes the topic vectors of the candidate-aware attention, userEncoders.py:103-105).
-      * ATT / MHSA: the candidate-aware attention reads ``category_embedding`` rows alone (:470,482 / :546,554), so
-        ``news_encoder.category_affine`` is dead; MHSA's ``user_encoder.affine`` is live (:487).  Dead as before: the base encoder's unused
-        ``affine``, ``candidate_aware_attn.value_proj`` and, for the CROWN content encoder, ``ISAB`` and ``category_predictor``; with
-        ``use_residual_connection`` off also the layer's ``gate_proj`` and ``layernorm`` (layers.py:84)."""
-    from .userEncoders import CROWN
+    for this model.  One rule for every user encoder and every setting of the switches:
+      * never used: the base encoder's ``affine``, ``candidate_aware_attn.value_proj`` and, where the content encoder has them,
+        ``ISAB`` and ``category_predictor``.
+      * ``user_encoder.affine``: only the MHSA user encoder applies it (userEncoders.py:487); CROWN constructs it and leaves it alone.
+      * ``news_encoder.category_affine`` makes the topic vectors of the CROWN user encoder's candidate-aware attention
+        (userEncoders.py:103-105) and nothing else: dead without that layer (``use_candidate_ware_clicked_news_attention`` off), and
+        under ATT / MHSA, whose layer reads ``category_embedding`` rows alone (:470,482 / :546,554).
+      * ``use_residual_connection`` off: the layer returns agg * x (layers.py:84), its ``gate_proj`` and ``layernorm`` are unused."""
+    from .userEncoders import CROWN, MHSA
+    ue = model.user_encoder
+    caa = getattr(ue, 'candidate_aware_attn', None)
+    # prefixes of the names (LIME's ``category_affine``, not the content encoder's own ``base_news_encoder.category_affine``)
+    dead = ['news_encoder.base_news_encoder.affine.', 'news_encoder.base_news_encoder.ISAB.', 'news_encoder.base_news_encoder.category_predictor.',
+            'user_encoder.candidate_aware_attn.value_proj.']
+    if not isinstance(ue, MHSA):
+        dead.append('user_encoder.affine.')
+    if not (isinstance(ue, CROWN) and caa is not None):
+        dead.append('news_encoder.category_affine.')
+    if caa is not None and not caa.use_residual_connection:
+        dead += ['user_encoder.candidate_aware_attn.gate_proj.', 'user_encoder.candidate_aware_attn.layernorm.']
     names, seen = [], set()
-    crown = isinstance(model.user_encoder, CROWN)
-    caa = getattr(model.user_encoder, 'candidate_aware_attn', None)
-    no_residual = caa is not None and not caa.use_residual_connection          # layers.py:84: agg * x alone, gate and LayerNorm unused
     for name, p in model.named_parameters():
         if not p.requires_grad or id(p) in seen:
             continue
         seen.add(id(p))
-        if crown:
-            dead = any(d in name for d in _DEAD)
-        else:
-            dead = (name.startswith('news_encoder.category_affine.') or name.startswith('news_encoder.base_news_encoder.affine.')
-                    or '.ISAB.' in name or 'category_predictor.' in name or 'candidate_aware_attn.value_proj.' in name
-                    or (no_residual and ('candidate_aware_attn.gate_proj.' in name or 'candidate_aware_attn.layernorm.' in name)))
-        if dead:
+        if name.startswith(tuple(dead)):
             names.append(name)
     return names
 

@@ -65,13 +65,30 @@ def _edit_bucket_edges(cfg, batch):
     return batch
 
 
+def _edit_lifetime_signs(cfg, batch):
+    """The last 12 remaining lifetimes (flat order): both zeros, and both signs below, around and past where sigmoid(alpha r)
+    saturates -- the values on which the weighting switches (util.py:34, :39-46) differ.  synth.make_batch alone leaves mostly
+    saturated weights."""
+    r = batch['remaining_lifetime'].reshape(-1).clone()
+    small = torch.tensor([0.0, -0.0, 0.5, -0.5, 3.0, -3.0, 40.0, -40.0, 120.0, -120.0, 400.0, -400.0])
+    assert r.numel() >= small.numel()
+    r[-small.numel():] = small
+    batch['remaining_lifetime'] = r.view(batch['remaining_lifetime'].shape)
+    return batch
+
+
 EDITS = {
     'none': _edit_none,
     'empty_history': _edit_empty_history,
     'bucket_edges': _edit_bucket_edges,
+    'lifetime_signs': _edit_lifetime_signs,
 }
 
 _SMALL = dict(vocabulary_size=5000, category_num=18, subCategory_num=270)
+_TINY = dict(max_history_num=6, max_title_length=8, max_abstract_length=16, batch_size=4, **_SMALL)
+# the shape of 'spill': rows per forward (6) > history slots (4), so the user-node term of the GraphSAGE mean is live (with _TINY and
+# B = 4 the reference's gradient of user_node_embedding is identically zero and pins nothing)
+_SPILL = dict(max_history_num=4, max_title_length=8, max_abstract_length=16, batch_size=6, **_SMALL)
 
 # name -> dict(config overrides, B, N, seed, eval_shape, edit)
 CASES = {
@@ -110,7 +127,25 @@ CASES = {
     # config.py:70 allows num_layers = 2: two post-LN encoder layers per token encoder (newsEncoders.py:244-247)
     'two_layers': dict(cfg=dict(num_layers=2, max_history_num=5, max_title_length=32, max_abstract_length=64, batch_size=3, **_SMALL),
                        B=3, N=2, seed=22, eval_shape=False, edit='none'),
+    # the four ablation switches of the scoring path (config.py:60-66), each off alone under the CROWN user encoder:
+    # no candidate-aware refinement (userEncoders.py:76,114): the encoder holds no candidate_aware_attn, 173 state-dict keys
+    'no_cand_aware': dict(cfg=dict(use_candidate_ware_clicked_news_attention=False, **_SPILL), B=6, N=3, seed=31, eval_shape=False, edit='none'),
+    # layers.py:84-91: agg * x alone, no gate, no LayerNorm (with all-padding histories in rows 0 and 3)
+    'no_residual': dict(cfg=dict(use_residual_connection=False, **_SPILL), B=6, N=3, seed=32, eval_shape=False, edit='empty_history'),
+    # util.py:34: the plain dot product
+    'no_lifetime_weight': dict(cfg=dict(use_remaining_lifetime_weighting=False, **_TINY), B=4, N=3, seed=33, eval_shape=False,
+                               edit='lifetime_signs'),
+    # util.py:46: sigmoid(alpha |r|), no beta on the expired side
+    'no_expired_penalty': dict(cfg=dict(use_expired_penalty=False, **_TINY), B=4, N=3, seed=34, eval_shape=False, edit='lifetime_signs'),
+    # all four off: the 173-key model without weighting (the residual and the penalty switch have nothing left to act on)
+    'ablation_all_off': dict(cfg=dict(use_candidate_ware_clicked_news_attention=False, use_residual_connection=False,
+                                      use_remaining_lifetime_weighting=False, use_expired_penalty=False, **_SPILL),
+                             B=6, N=3, seed=35, eval_shape=False, edit='lifetime_signs'),
+    # the row_scale branch on the reference's eval path (one candidate per row, no N axis): forward only
+    'no_residual_eval': dict(cfg=dict(use_residual_connection=False, **_TINY), B=4, N=1, seed=36, eval_shape=True, edit='none'),
 }
+# the cases above that turn a switch off and have gradient goldens (tests/golden/grad_<name>.npz)
+ABLATION_GRAD_CASES = ('no_cand_aware', 'no_residual', 'no_lifetime_weight', 'no_expired_penalty', 'ablation_all_off')
 
 WEIGHT_SEED = 7
 

@@ -292,9 +292,27 @@ def test_gate_ln_bwd(ops, rows, D):
 
 @pytest.mark.parametrize('B,N,H,A,D,penalty', [(3, 5, 50, 400, 400, True), (32, 5, 50, 400, 400, True), (2, 1, 7, 64, 48, False)])
 def test_interest_match_bwd(ops, B, N, H, A, D, penalty):
+    _interest_match_bwd_case(ops, B, N, H, A, D, True, penalty)
+
+
+@pytest.mark.parametrize('use_weight,penalty', [(True, False), (False, False)])
+def test_interest_match_bwd_switches_off_at_the_production_shape(ops, use_weight, penalty):
+    """use_expired_penalty off (util.py:46) and use_remaining_lifetime_weighting off (util.py:34) at batch 32, K = 5, history 50,
+    400 x 400 -- the shape the penalty-on branch is checked at above."""
+    _interest_match_bwd_case(ops, 32, 5, 50, 400, 400, use_weight, penalty)
+
+
+def _interest_match_bwd_case(ops, B, N, H, A, D, use_weight, penalty):
+    """One of the three weighting branches (util.py:34, :39-43, :46) forward and backward against fp64 autograd.  Among the random
+    remaining lifetimes sit both zeros (-0.0 is on the non-penalised side: r >= 0, util.py:40), +-1e5 (the sigmoid saturated both
+    ways) and +-40, as many of them as B * N holds."""
     kp, qp = rnd(B * H, A, seed=1, scale=0.3), rnd(B * N, A, seed=2, scale=0.3)
     g, cand = rnd(B * H, D, seed=3), rnd(B * N, D, seed=4)
     remaining = rnd(B, N, seed=5, scale=8.0)
+    special = torch.tensor([0.0, -0.0, 1e5, -1e5, 40.0, -40.0])[:B * N]
+    remaining.view(-1)[:special.numel()] = special
+    if B * N > 2 * special.numel():
+        remaining.view(-1)[-special.numel():] = special.flip(0)
     dlogits = rnd(B, N, seed=6)
     alpha, beta, scale = 0.3, 0.3, 1.0 / math.sqrt(A)
     kd, qd, gd, cd = (t.double().requires_grad_() for t in (kp, qp, g, cand))
@@ -302,20 +320,32 @@ def test_interest_match_bwd(ops, B, N, H, A, D, penalty):
     u = torch.softmax(a, dim=-1) @ gd.view(B, H, D)
     base = (u * cd.view(B, N, D)).sum(-1)
     r = remaining.double()
-    if penalty:
+    if not use_weight:
+        w = torch.ones_like(r)
+    elif penalty:
         w = torch.sigmoid(alpha * r)
         w = torch.where(r >= 0, w, beta * w)
     else:
         w = torch.sigmoid(alpha * r.abs())
+    if use_weight and penalty and B * N >= 2:
+        assert float(w.view(-1)[0]) == float(w.view(-1)[1]) == 0.5          # the reference statement itself: -0.0 is not penalised
     (base * w).backward(dlogits.double())
     c = lambda t: t.cuda()
     _, logits = ops.interest_match(c(kp).view(-1), c(qp).view(-1), c(g).view(-1), c(cand).view(-1), c(remaining), B, N, H, A, D, scale,
-                                   alpha, beta, True, penalty, want_user=False)
+                                   alpha, beta, use_weight, penalty, want_user=False)
     close(logits, (base * w).detach().float(), what='interest_match forward')
     got = ops.interest_match_bwd(c(kp).view(-1), c(qp).view(-1), c(g).view(-1), c(cand).view(-1), c(remaining), c(dlogits), B, N, H, A, D,
-                                 scale, alpha, beta, True, penalty)
+                                 scale, alpha, beta, use_weight, penalty)
     for name, x, ref in zip(('dkp', 'dqp', 'dg', 'dcand'), got, (kd, qd, gd, cd)):
         close(x, ref.grad.float(), tol=2e-4, what=name)
+    if not use_weight:                                                       # no `remaining` at all: the same bits
+        _, l_none = ops.interest_match(c(kp).view(-1), c(qp).view(-1), c(g).view(-1), c(cand).view(-1), None, B, N, H, A, D, scale,
+                                       alpha, beta, False, penalty, want_user=False)
+        assert torch.equal(l_none, logits)
+        none = ops.interest_match_bwd(c(kp).view(-1), c(qp).view(-1), c(g).view(-1), c(cand).view(-1), None, c(dlogits), B, N, H, A, D,
+                                      scale, alpha, beta, False, penalty)
+        for name, x, y in zip(('dkp', 'dqp', 'dg', 'dcand'), none, got):
+            assert torch.equal(x, y), name
 
 
 @pytest.mark.parametrize('B,N,H,nh,hd,p', [(4, 5, 50, 10, 40, 0.0), (4, 5, 50, 10, 40, 0.2), (3, 1, 7, 2, 8, 0.5), (2, 3, 70, 10, 40, 0.2)])

@@ -356,3 +356,48 @@ def test_two_encoder_layers(dtype, monkeypatch):
     else:
         scale = float(want.abs()[want != 0].mean())
         assert e_dense < 2e-5 and float((got - want).abs().max()) < 2e-2 * scale
+
+
+def test_captured_graph_outlives_a_regrow_of_the_identity_row_map(monkeypatch):
+    """A HIP graph captured with num_layers = 2 holds the ADDRESS of the identity row map in its token_attention_rows launches
+    (newsEncoders._identity_rows).  A later, larger batch needs a longer map: the one the graph was captured with must not go back
+    to the allocator for the next tensor of its size, or a replay of the first graph reads somebody else's data as row indices.
+    Capture + replay a small batch, score a batch that needs a longer map than any handed out so far, allocate and fill tensors of
+    the small map's size (zeros: in range as row indices whatever happens), replay the small batch: the same bits."""
+    cfg = make_config(vocabulary_size=20000, num_layers=2, batch_size=8)
+    model, sd = gpu_model(cfg, seed=73)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    rows = lambda B: (B * (5 + cfg.max_history_num) + 1) * cfg.max_abstract_length      # cap of the body encoder, the longer map
+    small = synth.make_batch(cfg, 4, 5, seed=74)
+    monkeypatch.setattr(newsEncoders, 'DEDUP', True)
+    model.use_graph = True
+    model._graphs.clear()
+    first = run(model, small, False)                             # captures
+    replay = run(model, small, False)
+    assert len(model._graphs) == 1 and torch.equal(first, replay)
+    n_small = rows(4)
+    held = newsEncoders._identity_rows(n_small, dev)             # what a call of the captured forward is handed
+    ptr = held.data_ptr()
+    avail = held.untyped_storage().nbytes() // 4                 # how long a map the cache can serve without growing
+    del held
+    B_large = 16
+    while rows(B_large) <= avail:                                # whatever ran before this test: a batch that does not fit
+        B_large *= 2
+    assert B_large <= 32, 'the cached row map is already longer than this test can outgrow (rows per forward <= H + batch_size)'
+    big = run(model, synth.make_batch(cfg, B_large, 5, seed=75), False)
+    assert len(model._graphs) == 2 and torch.isfinite(big).all()
+    assert newsEncoders._identity_rows(n_small, dev).data_ptr() != ptr, 'the larger batch was meant to outgrow the cached row map'
+    junk = [torch.zeros(n, dtype=torch.int32, device='cuda') for n in (n_small, avail) for _ in range(4)]
+    torch.cuda.synchronize()
+    again = run(model, small, False)                             # a replay of the first graph
+    assert len(model._graphs) == 2
+    assert torch.equal(again, replay)
+    del junk
+    monkeypatch.setattr(newsEncoders, 'DEDUP', False)
+    model.use_graph = False
+    want = run(model, small, False)                              # eager, dense: the same kernels per row
+    e = rel_err(again.numpy(), want.numpy())
+    print('two layers, replay after the regrow vs eager dense %.2e' % e)
+    assert e < 1e-5
+    model.use_graph = True
+    model._graphs.clear()

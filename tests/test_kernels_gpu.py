@@ -499,6 +499,16 @@ def test_interest_match(ops, B, N, H, penalty):
     check(l2, want, what='lifetime score')
     l3 = ops.lifetime_score(dev(user), dev(cand.view(B, N, D)), None, 0.3, 0.3, False, penalty)
     check(l3, (user * cand.view(B, N, D)).sum(-1), what='plain dot')
+    # use_remaining_lifetime_weighting off (util.py:34): no `remaining` at all, the logits are the plain dot product and the user
+    # representation is the same bits as with the weight on
+    u0, l0 = ops.interest_match(dev(kp), dev(qp), dev(g), dev(cand), None, B, N, H, A, D, 1 / math.sqrt(A), 0.3, 0.3, False, penalty)
+    a64 = torch.einsum('bha,bna->bnh', kp.double().view(B, H, A), qp.double().view(B, N, A)) / math.sqrt(A)
+    dot64 = ((torch.softmax(a64, dim=-1) @ g.double().view(B, H, D)) * cand.double().view(B, N, D)).sum(-1)      # fp64
+    check(l0, dot64.float(), what='logits, weight off')
+    assert torch.equal(u0, u)
+    # ... and a `remaining` passed anyway is not read
+    _, l0r = ops.interest_match(dev(kp), dev(qp), dev(g), dev(cand), dev(rem), B, N, H, A, D, 1 / math.sqrt(A), 0.3, 0.3, False, penalty)
+    assert torch.equal(l0r, l0)
 
 
 def test_row_scale_and_gather_rows(ops):

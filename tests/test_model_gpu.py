@@ -52,9 +52,11 @@ def test_golden_case(name):
     assert np.all(logits.numpy()[z] == 0) and np.array_equal(np.signbit(logits.numpy()[z]), np.signbit(g['logits'][z]))
 
 
-@pytest.mark.parametrize('name', ['cfg1_crown', 'cfg1_mhsa', 'bucket_edges', 'spill', 'empty_history'])
+@pytest.mark.parametrize('name', ['cfg1_crown', 'cfg1_mhsa', 'bucket_edges', 'spill', 'empty_history', 'no_residual', 'no_cand_aware'])
 def test_stages_against_golden(name):
-    """Sub-module forwards (the reference's own module API) against the per-stage goldens."""
+    """Sub-module forwards (the reference's own module API) against the per-stage goldens.  'no_residual': the layer called as a
+    module is its row-scale branch (layers.py:84); 'no_cand_aware': there is no such layer and no such stage, the history goes to
+    the GraphSAGE step as it is (userEncoders.py:114)."""
     cfg, batch, c = golden_cases.build_case(name)
     g = load_golden(name)
     model, sd = gpu_model(cfg)
@@ -90,10 +92,19 @@ def test_stages_against_golden(name):
               b['user_content_entity'], b['user_category'], b['user_subCategory'], None, b['user_freshness'],
               b['user_user_topic_lifetime'])
     assert rel_err(hist.cpu().numpy()[:r], g['hist_news_out']) < TOL
-    refined, agg = ue.candidate_aware_attn(hist, ue._topic(b['user_category'], b['user_subCategory']),
-                                           ue._topic(b['news_category'], b['news_subCategory']), mask=b['user_history_mask'])
-    assert rel_err(agg.cpu().numpy(), g['attn_weights_agg']) < TOL
-    assert rel_err(refined.cpu().numpy()[:r], g['hist_refined']) < TOL
+    if cfg.use_candidate_ware_clicked_news_attention:
+        assert ue.candidate_aware_attn.use_residual_connection == cfg.use_residual_connection
+        refined, agg = ue.candidate_aware_attn(hist, ue._topic(b['user_category'], b['user_subCategory']),
+                                               ue._topic(b['news_category'], b['news_subCategory']), mask=b['user_history_mask'])
+        assert rel_err(agg.cpu().numpy(), g['attn_weights_agg']) < TOL
+        assert rel_err(refined.cpu().numpy()[:r], g['hist_refined']) < TOL
+        assert (ue.gate_projection(hist) is None) == (not cfg.use_residual_connection)
+    else:
+        assert 'hist_refined' not in g and 'attn_weights_agg' not in g and not hasattr(ue, 'candidate_aware_attn')
+        assert ue.attention_weights(b['news_category'], b['news_subCategory'], b['user_category'], b['user_subCategory'],
+                                    b['user_history_mask']) is None
+        assert ue.gate_projection(hist) is None
+        refined = hist
     gcn = ue.graph_sage.forward_closed_form(refined, ue.user_node_embedding, n_src=hist.shape[0])
     assert rel_err(gcn.cpu().numpy()[:r], g['gcn_feature']) < TOL
 
@@ -217,14 +228,25 @@ def test_bf16_path_against_oracle(full_size):
     assert abs(aucs[0] - aucs[1]) <= 0.01
 
 
-def test_score_impressions_equals_eval_forward_on_expanded_rows():
+_ALL_OFF = dict(use_candidate_ware_clicked_news_attention=False, use_residual_connection=False, use_remaining_lifetime_weighting=False,
+                use_expired_penalty=False)
+SCORE_OVERRIDES = {'default': {}, 'all_off': _ALL_OFF, 'fusion_add': dict(fusion_method='add')}
+SCORE_OVERRIDES.update(zip(('no_cand_aware', 'no_residual', 'no_lifetime_weight', 'no_expired_penalty'), ({k: False} for k in _ALL_OFF)))
+
+
+@pytest.mark.parametrize('overrides', list(SCORE_OVERRIDES.values()), ids=list(SCORE_OVERRIDES))
+def test_score_impressions_equals_eval_forward_on_expanded_rows(overrides):
     """BASELINE config 5 layout: B impressions x K candidates scored with every history encoded once.  The result must be
     the reference's eval-mode function of the B * K (impression, candidate) rows (util.py:86-111): equal to this model's
-    eval forward on the expanded rows, and within tolerance of the oracle's eval forward."""
-    cfg = make_config(max_history_num=10, max_title_length=16, max_abstract_length=32, batch_size=64, vocabulary_size=5000)
+    eval forward on the expanded rows, and within tolerance of the oracle's eval forward.
+
+    Over the switches of config.py:60-66: with the candidate-aware layer or its residual off, and with fusion_method 'add' (D = 900 >
+    512, the layer present), ``CROWN.match`` takes its unfused chain, which copies a shared history per candidate (hist_div > 1); the
+    last 12 remaining lifetimes are golden_cases' 'lifetime_signs', where the two weighting switches differ."""
+    cfg = make_config(max_history_num=10, max_title_length=16, max_abstract_length=32, batch_size=64, vocabulary_size=5000, **overrides)
     model, sd = gpu_model(cfg, seed=41)
     B, K = 5, 6
-    batch = synth.make_batch(cfg, B, K, seed=42)
+    batch = golden_cases.EDITS['lifetime_signs'](cfg, synth.make_batch(cfg, B, K, seed=42))
     c = {k: v.cuda() for k, v in batch.items()}
     model.eval()
     got = model.score_impressions(c['user_category'], c['user_subCategory'], c['user_title_text'], c['user_title_mask'],
@@ -242,9 +264,12 @@ def test_score_impressions_equals_eval_forward_on_expanded_rows():
     model.use_graph = False
     ref_rows = run(model, exp, True)
     # (not bitwise: the two layouts cross the M >= 4096 threshold between the two GEMM kernels, whose k order differs)
-    assert rel_err(got.cpu().reshape(-1).numpy(), ref_rows.reshape(-1).numpy()) < 2e-5
+    e_rows = rel_err(got.cpu().reshape(-1).numpy(), ref_rows.reshape(-1).numpy())
     want = O.model_forward(sd, cfg, exp, eval_shape=True).reshape(-1)
-    assert rel_err(got.cpu().reshape(-1).numpy(), want.numpy()) < TOL
+    e_oracle = rel_err(got.cpu().reshape(-1).numpy(), want.numpy())
+    print('score_impressions %s: vs eval forward on expanded rows %.2e, vs oracle %.2e' % (overrides, e_rows, e_oracle))
+    assert e_rows < 2e-5
+    assert e_oracle < TOL
     # chunked passes give the same numbers
     again = model.score_impressions(c['user_category'], c['user_subCategory'], c['user_title_text'], c['user_title_mask'],
                                     c['user_content_text'], c['user_freshness'], c['user_user_topic_lifetime'], c['user_history_mask'],
@@ -252,6 +277,41 @@ def test_score_impressions_equals_eval_forward_on_expanded_rows():
                                     c['news_content_text'], c['news_freshness'], c['news_user_topic_lifetime'], c['remaining_lifetime'],
                                     rows_per_pass=2 * K)
     assert torch.equal(again, got)
+
+
+def test_content_cache_agrees_with_the_uncached_forward_with_every_switch_off(tmp_path):
+    """util.compute_scores_cached (Model.build_news_cache + Model.score_behaviors) against util.compute_scores on the toy corpus with the
+    CROWN content and user encoders and the four switches of config.py:60-66 off: the same rank file and metrics (the check of
+    tests/test_user_encoders_gpu.py::test_content_cache_agrees_with_the_uncached_forward)."""
+    import os
+    from helpers import GOLDEN_DIR
+    from lime_cikm25_amd import formats, util
+    from lime_cikm25_amd.device_data import DeviceBehaviors, DeviceCorpus
+    g = json.load(open(os.path.join(GOLDEN_DIR, 'formats.json')))
+    L = g['lines']
+    cfg = make_config(max_history_num=g['max_history_num'], max_title_length=g['max_title_length'],
+                      max_abstract_length=g['max_abstract_length'], vocabulary_size=len(g['word_dict']), negative_sample_num=2,
+                      category_num=len(g['category_dict']) + 1, subCategory_num=len(g['subCategory_dict']) + 1,
+                      user_num=len(g['user_ID_dict']), batch_size=16, **_ALL_OFF)
+    corpus = formats.build_corpus(cfg, [L['train_news'], L['dev_news'], L['test_news']],
+                                  [L['train_behaviors'], L['dev_behaviors'], L['test_behaviors']], g['news_ID_dict'],
+                                  g['user_ID_dict'], g['category_dict'], g['subCategory_dict'], g['word_dict'], dataset='adressa')
+    dev = DeviceBehaviors.from_devtest(DeviceCorpus(corpus), corpus, 'dev')
+    torch.manual_seed(0)
+    model = Model(cfg)
+    model.initialize()
+    torch.nn.init.normal_(model.news_encoder.base_news_encoder.word_embedding.weight, std=0.1)
+    torch.nn.init.normal_(model.user_encoder.user_node_embedding, std=0.1)          # zeros at initialisation: make the node term count
+    model = model.cuda()
+    assert not hasattr(model.user_encoder, 'candidate_aware_attn') and len(model.state_dict()) == 173
+    truth = tmp_path / 'truth.txt'
+    with open(truth, 'w') as f:
+        for i, labels in enumerate(formats.truth_labels(L['dev_behaviors'])):
+            f.write('%d %s\n' % (i + 1, json.dumps(labels).replace(' ', '')))
+    a = util.compute_scores(model, [dev.assemble(list(range(dev.num)))], corpus.dev_indices, str(tmp_path / 'rank.txt'), str(truth))
+    b = util.compute_scores_cached(model, dev, corpus.dev_indices, str(tmp_path / 'rank_cached.txt'), str(truth), rows_per_forward=dev.num)
+    assert open(tmp_path / 'rank_cached.txt').read() == open(tmp_path / 'rank.txt').read()
+    assert a == b
 
 
 def test_long_body_shape_against_oracle():

@@ -17,7 +17,8 @@ from lime_cikm25_amd.training import TrainStep, negative_log_softmax
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
 LR = 1e-5
-GRAD_CASES = ['cfg1_crown', 'cfg1_mhsa', 'spill', 'empty_history', 'full_len', 'long_body', 'fusion_gated', 'two_layers']
+GRAD_CASES = (['cfg1_crown', 'cfg1_mhsa', 'spill', 'empty_history', 'full_len', 'long_body', 'fusion_gated', 'two_layers']
+              + list(golden_cases.ABLATION_GRAD_CASES))             # the switches of config.py:60-66, each off and all off
 
 
 def train_model(name):
@@ -87,15 +88,16 @@ def test_gradients_match_the_reference(name):
     print('%s: loss %.6f (reference %.6f), worst gradient %s rel err %.2e' % (name, float(loss.detach()), float(g['loss']), *worst))
 
 
-def test_native_step_follows_torch_adam_and_clip():
+@pytest.mark.parametrize('name', ['cfg1_crown', 'no_residual', 'ablation_all_off'])
+def test_native_step_follows_torch_adam_and_clip(name):
     """TrainStep (flat buckets, HIP clip + Adam) against clip_grad_norm_ + torch.optim.Adam fed with the SAME gradients,
-    three steps; then the loss must have moved the way the torch-driven copy's did."""
-    name = 'cfg1_crown'
+    three steps; then the loss must have moved the way the torch-driven copy's did.  'no_residual' / 'ablation_all_off': the bucket
+    leaves out what the switches make dead (the layer's gate and LayerNorm; the layer and LIME's category_affine)."""
     g = golden(name)
     cfg, model, batch = train_model(name)
     _, twin, _ = train_model(name)
     step = TrainStep(model, lr=LR, gradient_clip_norm=4.0)
-    assert sorted(step.names) == sorted(json.loads(str(g['with_grad'])))
+    assert step.names == json.loads(str(g['with_grad']))
     params = [p for k, p in unique_named_parameters(twin) if k in set(step.names)]
     opt = torch.optim.Adam(params, lr=LR)
     losses = []
@@ -129,6 +131,28 @@ def test_native_step_follows_torch_adam_and_clip():
         scored = model(*batch)
     again = model(*batch)
     assert rel_err(scored.cpu().numpy(), again.detach().cpu().numpy()) < 1e-4
+
+
+def test_weight_decay_leaves_dead_parameters_alone():
+    """torch's Adam skips a parameter whose .grad is None, weight decay included: after three steps with weight_decay > 0 every
+    parameter the reference's backward gives no gradient ('no_residual': the layer's gate_proj and layernorm among them) holds the
+    bits it started with, and the bucket's parameters have moved."""
+    name = 'no_residual'
+    g = golden(name)
+    cfg, model, batch = train_model(name)
+    before = {k: p.detach().clone() for k, p in unique_named_parameters(model)}
+    step = TrainStep(model, lr=1e-3, weight_decay=0.1, gradient_clip_norm=4.0)
+    for _ in range(3):
+        step.step(*batch)
+    after = dict(unique_named_parameters(model))
+    without = json.loads(str(g['without_grad']))
+    assert {'user_encoder.candidate_aware_attn.gate_proj.weight', 'user_encoder.candidate_aware_attn.gate_proj.bias',
+            'user_encoder.candidate_aware_attn.layernorm.weight', 'user_encoder.candidate_aware_attn.layernorm.bias'} <= set(without)
+    for k in without:
+        assert k not in step.names and after[k].grad is None, k
+        assert torch.equal(after[k].detach(), before[k]), '%s changed under weight decay' % k
+    for k in step.names:
+        assert not torch.equal(after[k].detach(), before[k]), '%s did not move' % k
 
 
 def test_mixed_dropout_modes_are_refused():

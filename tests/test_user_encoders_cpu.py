@@ -65,9 +65,10 @@ def test_reference_checkpoint_loads_strictly(name):
         assert torch.equal(ue.multiheadAttention.W_K.bias, sd['user_encoder.multiheadAttention.W_K.bias'])
 
 
-@pytest.mark.parametrize('name', user_cases.GRAD_CASES)
+@pytest.mark.parametrize('name', user_cases.GRAD_CASES + golden_cases.ABLATION_GRAD_CASES)
 def test_dead_parameters_are_the_ones_the_reference_gives_no_gradient(name):
-    cfg, _, _ = user_cases.build_case(name)
+    # the ATT / MHSA cases, and the CROWN user encoder with each switch of config.py:60-66 off (tests/golden_cases.py)
+    cfg, _, _ = (user_cases if name in user_cases.CASES else golden_cases).build_case(name)
     g = load_golden('grad_' + name)
     model = Model(cfg)
     # without_grad lists every parameter whose .grad stayed None: the frozen tables (requires_grad False) and the dead ones
