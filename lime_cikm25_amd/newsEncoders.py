@@ -12,8 +12,10 @@ called.  All arithmetic runs in hand-written HIP kernels (lime_cikm25_amd.ops ->
   token attention                     one wave per 32 query rows, scores held in MFMA accumulators
   mean pool / intent tail / buckets   small fixed-order kernels
 """
+import collections
 import math
 import os
+import types
 
 import torch
 import torch.nn as nn
@@ -469,71 +471,98 @@ class CategoryPredictor(nn.Module):
         self.fc = nn.Linear(title_embedding, category_num)
 
 
-def encode_tokens(ids, table, pe, transformer, nhead, pooled_out=None):
-    """Word gather + positional table + the post-LN encoder layer(s) of newsEncoders.py:311-320.
+# How one pass over a token encoder addresses its rows: all that differs between the dense batch and the compacted one (csrc/compact.hip).
+#   n_seq, S            sequences the layer runs over (M, or M + 1 compacted: the live ones + the all-padding representative)
+#   a_ids, res_ids      word ids of the first in_proj's A gather / of the residual out_proj rebuilds
+#   w_in, pew           the first layer's in_proj weight (heads padded) and the positional table through it (+ bias), [S, 3W]
+# compacted only (None on the dense batch):
+#   qkv                 the first layer's q / k / v buffer, the S padding rows filled in behind its n_seq * S compact rows
+#   c_ids, m_tok        the first in_proj's scatter list and the device count of live tokens
+#   m_rows, n_seq_dev   device counts of compact rows / sequences
+#   row_map             the first layer's attention looks every token's q / k / v row up through it
+#   seq_inv             pooled_out[s] = pooled rows[seq_inv[s]]
+_Rows = collections.namedtuple('_Rows', 'n_seq S a_ids res_ids w_in pew qkv c_ids m_tok m_rows n_seq_dev row_map seq_inv',
+                               defaults=(None,) * 7)
 
-    ids: [M, S] int32 (every id must be in [0, V): unchecked, as on nn.Embedding's device path);
-    returns the layer output [M * S, E].  Five launches per layer, activations stay fp32.
-    With ``pooled_out`` ([M, E]) the token mean pooling of :317 / :321 is taken in the last GEMM's epilogue (pool32: means
-    over 32-token blocks; a longer sequence is finished by a mean over its S / 32 block rows) and the layer output never
-    reaches HBM; returns None then.
-    """
-    M, S = ids.shape
+
+def _encode_layers(r, table, pe, transformer, nhead, pooled_out):
+    """Word gather + positional table + the post-LN encoder layer(s) of newsEncoders.py:311-320 over the rows ``r`` describes: in_proj,
+    attention, out_proj + residual + norm1, linear1 + ReLU, linear2 + residual + norm2 -- five launches per layer (four with the fused
+    feed-forward), activations stay fp32.  With ``pooled_out`` the token mean pooling of :317 / :321 is taken in the last GEMM's
+    epilogue (pool32: means over 32-token blocks; a longer sequence is finished by a mean over its S / 32 block rows) and the layer
+    output never reaches HBM; returns None then, the layer output [n_seq * S, E] otherwise."""
+    n_seq, S = r.n_seq, r.S
     E = table.shape[1]
     hd = E // nhead
     hs = 32 if hd <= 32 else hd                    # heads padded to 32 columns in the in_proj output: the 128 x 320 GEMM
     W = nhead * hs                                 # tiles compute those columns anyway, and attention gets 16-byte loads
-    flat = ids.reshape(-1)
+    scale = 1.0 / math.sqrt(hd)
+    rows = dict(m_dev=r.m_rows)
+    pooled = pooled_out if r.seq_inv is None else None            # compacted: the pooled rows in compact order first
     x = None
     for li, layer in enumerate(transformer.layers):
         sa = layer.self_attn
-        w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, hs) if hs != hd else sa.in_proj_weight
-        b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, hs) if hs != hd else sa.in_proj_bias
+        ln1 = (layer.norm1.weight, layer.norm1.bias)
         if li == 0:
             # (E[ids] + PE) W^T + b = E[ids] W^T + (PE W^T + b)[t]: the positional term is an [S, 3W] table added as a
             # periodic residual, so the A operand is a pure row gather (which the LDS-DMA GEMM can stage directly)
-            pew = ops.linear(pe[:S], w_in, b_in)
-            qkv = ops.linear(table, w_in, None, a_ids=flat, res=pew, res_mod=S, n_alg=3 * E)
+            qkv = ops.linear(table, r.w_in, None, a_ids=r.a_ids, res=r.pew, res_mod=S, n_alg=3 * E, c_ids=r.c_ids, m_dev=r.m_tok,
+                             out=None if r.qkv is None else r.qkv[:n_seq * S])
+            qkv = qkv if r.qkv is None else r.qkv
+            res = dict(res=table, res_ids=r.res_ids, res_pe=pe, res_period=S)
         else:
-            qkv = ops.linear(x, w_in, b_in, n_alg=3 * E)
-        attn = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, 1.0 / math.sqrt(hd),
-                                   head_stride=hs)
-        ln1 = (layer.norm1.weight, layer.norm1.bias)
-        if li == 0:
-            x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, res=table, res_ids=flat, res_pe=pe, res_period=S,
-                            ln=ln1, ln_eps=layer.norm1.eps)
+            # a layer behind the first (config.py:70 allows num_layers = 2): its input rows are all distinct, so of the compaction only
+            # the sequence-level sharing is left -- device-side row counts, attention through the identity map
+            w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, hs) if hs != hd else sa.in_proj_weight
+            b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, hs) if hs != hd else sa.in_proj_bias
+            qkv = ops.linear(x, w_in, b_in, n_alg=3 * E, **rows)
+            res = dict(res=x)
+        q, k, v = qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:]
+        if r.row_map is None:
+            attn = ops.token_attention(q, k, v, n_seq, S, nhead, hd, scale, head_stride=hs)
         else:
-            x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, res=x, ln=ln1, ln_eps=layer.norm1.eps)
+            attn = ops.token_attention_rows(q, k, v, r.row_map if li == 0 else _identity_rows(n_seq * S, table.device), r.n_seq_dev,
+                                            n_seq, S, nhead, hd, scale)
+        x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, ln=ln1, ln_eps=layer.norm1.eps, **res, **rows)
         last = li == len(transformer.layers) - 1
-        pool = last and pooled_out is not None and transformer.norm is None and S % 32 == 0 and M * S >= 4096
+        pool = last and pooled_out is not None and transformer.norm is None and S % 32 == 0 and n_seq * S >= 4096
+        ln2 = (layer.norm2.weight, layer.norm2.bias)
         if _ffn_sp_applicable(layer, x1):
-            # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means) in one launch: the compacted path's kernel
+            # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means of the last layer) in one launch
             w1p, w2p = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
-            ln2 = (layer.norm2.weight, layer.norm2.bias)
-            if pool:
-                direct = S == 32 and pooled_out.data_ptr() % 16 == 0 and pooled_out.stride(0) % 4 == 0
-                blocks = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, pool32=True,
-                                            out=pooled_out if direct else None)
-                if not direct:
-                    ops.mean_pool(blocks, M, S // 32, out=pooled_out)
-                return None
-            x = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps)
+            direct = S == 32 and (pooled is None or (pooled.data_ptr() % 16 == 0 and pooled.stride(0) % 4 == 0))
+            ffn = lambda **kw: ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, **kw, **rows)
+        else:
+            h = ops.linear(x1, layer.linear1.weight, layer.linear1.bias, act='relu', **rows)
+            direct = S == 32
+            ffn = lambda **kw: ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=ln2, ln_eps=layer.norm2.eps, **kw, **rows)
+        if not pool:
+            x = ffn()
             continue
-        h = ops.linear(x1, layer.linear1.weight, layer.linear1.bias, act='relu')
-        if pool:
-            blocks = ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=(layer.norm2.weight, layer.norm2.bias),
-                                ln_eps=layer.norm2.eps, pool32=True, out=pooled_out if S == 32 else None)
-            if S != 32:
-                ops.mean_pool(blocks, M, S // 32, out=pooled_out)
-            return None
-        x = ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=(layer.norm2.weight, layer.norm2.bias),
-                       ln_eps=layer.norm2.eps)
-    if transformer.norm is not None:
-        raise NotImplementedError('a final encoder norm is not used by the reference (newsEncoders.py:245,247)')
-    if pooled_out is not None:
-        ops.mean_pool(x, M, S, out=pooled_out)
-        return None
-    return x
+        blocks = ffn(pool32=True, out=pooled if direct else None)                                      # [n_seq * S / 32, E] block means
+        pooled = blocks if direct else ops.mean_pool(blocks, n_seq, S // 32, out=pooled, n_seq_dev=r.n_seq_dev)
+        break
+    else:
+        if transformer.norm is not None:
+            raise NotImplementedError('a final encoder norm is not used by the reference (newsEncoders.py:245,247)')
+        if pooled_out is None:
+            return x
+        pooled = ops.mean_pool(x, n_seq, S, out=pooled, n_seq_dev=r.n_seq_dev)
+    if r.seq_inv is not None:
+        ops.gather_rows(r.seq_inv, pooled, pooled_out)
+    return None
+
+
+def encode_tokens(ids, table, pe, transformer, nhead, pooled_out=None):
+    """``_encode_layers`` over every token of the dense batch.  ids: [M, S] int32 (every id must be in [0, V): unchecked, as on
+    nn.Embedding's device path); returns the layer output [M * S, E], or None with ``pooled_out`` ([M, E])."""
+    M, S = ids.shape
+    hd = table.shape[1] // nhead
+    sa = transformer.layers[0].self_attn
+    w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32) if hd < 32 else sa.in_proj_weight
+    b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32) if hd < 32 else sa.in_proj_bias
+    flat = ids.reshape(-1)
+    return _encode_layers(_Rows(M, S, flat, flat, w_in, ops.linear(pe[:S], w_in, b_in)), table, pe, transformer, nhead, pooled_out)
 
 
 def encode_tokens_compact(ids, table, pe, transformer, nhead, pooled_out):
@@ -607,52 +636,11 @@ def _identity_rows(n, device):
 
 
 def compact_run(prep, table, pe, transformer, nhead, pooled_out):
+    """``encode_tokens_compact`` behind its preparation: the layer(s) over the compacted rows, ``pooled_out`` through ``seq_inv``."""
     cmp, w_in, pew, qkv = prep
-    M, S, cap = cmp.n_seq, cmp.S, cmp.cap
-    E = table.shape[1]
-    hd = E // nhead
-    W = nhead * 32
-    n_layers = len(transformer.layers)
-    x = None
-    for li, layer in enumerate(transformer.layers):
-        sa = layer.self_attn
-        ln1 = (layer.norm1.weight, layer.norm1.bias)
-        if li == 0:
-            ops.linear(table, w_in, None, a_ids=cmp.tok_ids, res=pew, res_mod=S, out=qkv[:cap], m_dev=cmp.n_live_tokens,
-                       c_ids=cmp.tok_rows, n_alg=3 * E)                                                    # live tokens only
-            attn = ops.token_attention_rows(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], cmp.row_map, cmp.n_compact, M + 1, S, nhead, hd,
-                                            1.0 / math.sqrt(hd))
-            x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, res=table, res_ids=cmp.ids_c, res_pe=pe, res_period=S,
-                            ln=ln1, ln_eps=layer.norm1.eps, m_dev=cmp.n_rows)
-        else:
-            # a layer behind the first (config.py:70 allows num_layers = 2): its input rows are all distinct, so only the sequence-level
-            # sharing is left -- the layer runs over the n_rows compact rows (device-side count), attention through the identity map
-            w_l = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)
-            b_l = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
-            qkv_l = ops.linear(x, w_l, b_l, m_dev=cmp.n_rows, n_alg=3 * E)
-            attn = ops.token_attention_rows(qkv_l[:, :W], qkv_l[:, W:2 * W], qkv_l[:, 2 * W:], _identity_rows(cap, x.device), cmp.n_compact,
-                                            M + 1, S, nhead, hd, 1.0 / math.sqrt(hd))
-            x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, res=x, ln=ln1, ln_eps=layer.norm1.eps, m_dev=cmp.n_rows)
-        if _ffn_sp_applicable(layer, x1):
-            # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means of the last layer) in one launch
-            w1p, w2p = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
-            ln2 = (layer.norm2.weight, layer.norm2.bias)
-            if li + 1 < n_layers:
-                x = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, m_dev=cmp.n_rows)
-                continue
-            blocks = ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, pool32=True,
-                                        m_dev=cmp.n_rows)                                              # [cap / 32, E] block means
-            break
-        h = ops.linear(x1, layer.linear1.weight, layer.linear1.bias, act='relu', m_dev=cmp.n_rows)
-        if li + 1 < n_layers:
-            x = ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=(layer.norm2.weight, layer.norm2.bias),
-                           ln_eps=layer.norm2.eps, m_dev=cmp.n_rows)
-            continue
-        blocks = ops.linear(h, layer.linear2.weight, layer.linear2.bias, res=x1, ln=(layer.norm2.weight, layer.norm2.bias),
-                            ln_eps=layer.norm2.eps, pool32=True, m_dev=cmp.n_rows)                     # [cap / 32, E] block means
-    pooled_c = blocks if S == 32 else ops.mean_pool(blocks, M + 1, S // 32, n_seq_dev=cmp.n_compact)
-    ops.gather_rows(cmp.seq_inv, pooled_c, pooled_out)
-    return None
+    rows = _Rows(cmp.n_seq + 1, cmp.S, cmp.tok_ids, cmp.ids_c, w_in, pew, qkv, c_ids=cmp.tok_rows, m_tok=cmp.n_live_tokens,
+                 m_rows=cmp.n_rows, n_seq_dev=cmp.n_compact, row_map=cmp.row_map, seq_inv=cmp.seq_inv)
+    return _encode_layers(rows, table, pe, transformer, nhead, pooled_out)
 
 
 def compact_applicable(ids, table, transformer, nhead):
@@ -680,167 +668,121 @@ def _ffn_fused_applicable(layer, E, EP):
             layer.linear1.bias is not None and layer.linear2.bias is not None)
 
 
-def encode_tokens_bf16(ids, table_bf16, pe, transformer, nhead, pooled_out):
-    """encode_tokens + mean pool on the bf16 matrix cores (BASELINE config 3).
+def _pack_layer_bf16(layer, first, pe, S, EP, nhead):
+    """The weights of one encoder layer in the packings its bf16 launches take -- which launches those are is decided here, from the
+    switches and the layer's shape.  E = 300 is carried as EP = 304 columns (zero weights / bias / gamma / beta in the pad, so the
+    pad stays exactly zero through the layer).  ``first``: the layer whose input is the word gather + positional table."""
+    sa = layer.self_attn
+    E = pe.shape[1]
+    hd = E // nhead
+    padv = lambda v: torch.cat([v, v.new_zeros(EP - E)])
+    p = types.SimpleNamespace(inproj=_inproj_applicable(3 * nhead * 32, EP), ffn=_ffn_fused_applicable(layer, E, EP))
+    p.block = FUSED_BLOCK and p.ffn and E % 4 == 0
+    w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)                      # fp32 [3W, E]
+    b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
+    p.w_in = ops.inproj_pack_bf16(w_in, EP) if p.inproj else ops.to_bf16(w_in, cols_out=EP)
+    # what in_proj adds to its rows: the first layer's positional term + bias (fp32 [S, 3W]), the bias alone behind it
+    p.in_rows = ops.linear(pe[:S], w_in, b_in) if first else b_in.view(1, -1) if p.inproj else b_in
+    if p.ffn:
+        p.w1p, p.w2p = ops.ffn_pack_bf16(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight)
+    else:
+        p.w1, p.w2 = ops.to_bf16(layer.linear1.weight, cols_out=EP), ops.to_bf16(layer.linear2.weight, rows_out=EP)
+        p.b2, p.ln2 = padv(layer.linear2.bias), (padv(layer.norm2.weight), padv(layer.norm2.bias))
+    if p.block:
+        p.w0p = ops.oproj_pack_bf16(sa.out_proj.weight)
+        p.add_rows = pe[:S] + sa.out_proj.bias if first else sa.out_proj.bias.view(1, E)
+    else:
+        p.w_o, p.b_o = ops.to_bf16(sa.out_proj.weight, rows_out=EP, cols_out=EP), padv(sa.out_proj.bias)
+        p.ln1 = (padv(layer.norm1.weight), padv(layer.norm1.bias))
+        p.pe_p = torch.cat([pe[:S], pe.new_zeros(S, EP - E)], dim=1) if first else None
+    return p
 
-    table_bf16: the word table converted with ``ops.to_bf16`` ([V, E rounded up to 8], zero padded).  Activations between
-    the launches are bf16; accumulation, bias, residual adds, softmax and LayerNorm are fp32.  E = 300 is carried as 304
-    columns (zero weights / bias / gamma / beta in the pad, so the pad stays exactly zero through the layer).
-    """
+
+def _encode_layers_bf16(ids, cmp, table_bf16, pe, transformer, nhead, pooled_out, shared=None):
+    """The encoder layer(s) + mean pool on the bf16 matrix cores, over every token of ``ids`` (``cmp`` None) or over its compacted batch
+    (``cmp = ops.compact_sequences(ids)``, one layer): in_proj (activation-stationary, or lime_linear_bf16) -> attention -> everything
+    behind it in one launch / out_proj + fused feed-forward / three GEMMs -> 32-token block means -> ``pooled_out``.  Activations
+    between the launches are bf16; accumulation, bias, residual adds, softmax and LayerNorm are fp32.  ``shared``: a dict that lives
+    for one forward, through which the passes over one encoder share its packed weights."""
     M, S = ids.shape
     EP = table_bf16.shape[1]
     E = pe.shape[1]
     hd = E // nhead
     if hd > 32 or S % 32 != 0:
         raise NotImplementedError('the bf16 encoder path needs head_dim <= 32 and S a multiple of 32 (got %d, %d)' % (hd, S))
-    W = nhead * 32
-    flat = ids.reshape(-1)
-    dev = ids.device
-    padv = lambda v: torch.cat([v, v.new_zeros(EP - E)])
-    x = None
-    for li, layer in enumerate(transformer.layers):
-        sa = layer.self_attn
-        w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)                  # fp32 [3W, E]
-        b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
-        if _inproj_applicable(3 * W, EP):
-            # activation-stationary q / k / v projection (csrc/inproj_bf16.hip): the tile is read once for all 3 W columns
-            w_in_p = ops.inproj_pack_bf16(w_in, EP)
-            qkv = torch.empty((M * S, 3 * W), dtype=torch.bfloat16, device=dev)
-            if li == 0:
-                ops.inproj_bf16(table_bf16, w_in_p, ops.linear(pe[:S], w_in, b_in), 3 * W, qkv, a_ids=flat)     # + positional term + bias
-            else:
-                ops.inproj_bf16(x, w_in_p, b_in.view(1, -1), 3 * W, qkv)
-        elif li == 0:
-            pew = ops.linear(pe[:S], w_in, b_in)                                     # fp32 [S, 3W]: positional term + bias
-            qkv = ops.linear_bf16(table_bf16, ops.to_bf16(w_in, cols_out=EP), None, a_ids=flat, res=pew, res_kind=1, res_mod=S, n_alg=3 * E, k_alg=E)
-        else:
-            qkv = ops.linear_bf16(x, ops.to_bf16(w_in, cols_out=EP), b_in, n_alg=3 * E, k_alg=E)
-        attn = ops.token_attention_bf16(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, 1.0 / math.sqrt(hd), out_cols=EP)
-        last = li == len(transformer.layers) - 1
-        pool = last and transformer.norm is None              # token mean pooling in the epilogue: fp32 means over 32-token blocks
-        if li == 0:
-            pe_p = torch.cat([pe[:S], pe.new_zeros(S, EP - E)], dim=1)
-        if FUSED_BLOCK and _ffn_fused_applicable(layer, E, EP) and E % 4 == 0:
-            # everything behind the attention core in ONE launch (csrc/ffn_bf16.hip): out_proj + residual + norm1 written into the
-            # stationary LDS tile the feed-forward half then reads
-            w1p, w2p = ops.ffn_pack_bf16(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight)
-            res_kw = (dict(res=table_bf16, res_kind=2, res_ids=flat, add_rows=pe[:S] + sa.out_proj.bias) if li == 0 else
-                      dict(res=x, res_kind=3, add_rows=sa.out_proj.bias.view(1, E)))
-            y = ops.encoder_block_bf16(attn, ops.oproj_pack_bf16(sa.out_proj.weight), ln1=(layer.norm1.weight, layer.norm1.bias),
-                                       ln1_eps=layer.norm1.eps, w1p=w1p, w2p=w2p, b2=layer.linear2.bias, ln2=(layer.norm2.weight, layer.norm2.bias),
-                                       ln2_eps=layer.norm2.eps, E=E, pool32=pool, **res_kw)
-            if pool:
-                return ops.mean_pool(y[:, :E], M, S // 32, out=pooled_out)
-            x = y
-            continue
-        w_o = ops.to_bf16(sa.out_proj.weight, rows_out=EP, cols_out=EP)
-        ln1 = (padv(layer.norm1.weight), padv(layer.norm1.bias))
-        if li == 0:
-            x1 = ops.linear_bf16(attn, w_o, padv(sa.out_proj.bias), res=table_bf16, res_kind=2, res_ids=flat, res_pe=pe_p,
-                                 res_period=S, ln=ln1, ln_eps=layer.norm1.eps, ln_count=E, n_alg=E, k_alg=E)
-        else:
-            x1 = ops.linear_bf16(attn, w_o, padv(sa.out_proj.bias), res=x, res_kind=3, ln=ln1, ln_eps=layer.norm1.eps, ln_count=E, n_alg=E, k_alg=E)
-        if _ffn_fused_applicable(layer, E, EP):
-            # linear1 + ReLU + linear2 + residual + norm2 in ONE launch: the hidden state stays in registers (csrc/ffn_bf16.hip)
-            w1p, w2p = ops.ffn_pack_bf16(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight)
-            y = ops.encoder_ffn_bf16(x1, w1p, w2p, layer.linear2.bias, (layer.norm2.weight, layer.norm2.bias), layer.norm2.eps, E, pool32=pool)
-            if pool:
-                return ops.mean_pool(y[:, :E], M, S // 32, out=pooled_out)
-            x = y
-            continue
-        h = ops.linear_bf16(x1, ops.to_bf16(layer.linear1.weight, cols_out=EP), layer.linear1.bias, act='relu', k_alg=E)
-        if pool:
-            blocks = ops.linear_bf16(h, ops.to_bf16(layer.linear2.weight, rows_out=EP), padv(layer.linear2.bias), res=x1, res_kind=3,
-                                     ln=(padv(layer.norm2.weight), padv(layer.norm2.bias)), ln_eps=layer.norm2.eps, ln_count=E,
-                                     pool32=True, n_alg=E)
-            return ops.mean_pool(blocks[:, :E], M, S // 32, out=pooled_out)
-        x = ops.linear_bf16(h, ops.to_bf16(layer.linear2.weight, rows_out=EP), padv(layer.linear2.bias), res=x1, res_kind=3,
-                            ln=(padv(layer.norm2.weight), padv(layer.norm2.bias)), ln_eps=layer.norm2.eps, ln_count=E, n_alg=E)
     if transformer.norm is not None:
         raise NotImplementedError('a final encoder norm is not used by the reference (newsEncoders.py:245,247)')
-    return ops.mean_pool_bf16(x, M, S, E, out=pooled_out)
+    W = nhead * 32
+    scale = 1.0 / math.sqrt(hd)
+    shared = {} if shared is None else shared
+    if cmp is None:
+        n_seq, a_ids, res_ids, c_ids, n_seq_dev, rows = M, ids.reshape(-1), ids.reshape(-1), None, None, {}
+    else:                            # live sequences + one all-padding representative, in_proj over the live tokens, the row-map attention
+        n_seq, a_ids, res_ids, c_ids, n_seq_dev, rows = M + 1, cmp.tok_ids, cmp.ids_c, cmp.tok_rows, cmp.n_compact, dict(m_dev=cmp.n_rows)
+    cap = n_seq * S
+    x = None
+    for li, layer in enumerate(transformer.layers):
+        if li not in shared:
+            shared[li] = _pack_layer_bf16(layer, li == 0, pe, S, EP, nhead)
+        p = shared[li]
+        # compacted: the S rows shared by the padding tokens, which the row map points at, stand behind the cap compact rows
+        qkv = torch.empty((cap if cmp is None else cap + S, 3 * W), dtype=torch.bfloat16, device=ids.device)
+        if li > 0 and p.inproj:
+            ops.inproj_bf16(x, p.w_in, p.in_rows, 3 * W, qkv)
+        elif li > 0:
+            ops.linear_bf16(x, p.w_in, p.in_rows, n_alg=3 * E, k_alg=E, out=qkv)
+        elif p.inproj:
+            # activation-stationary q / k / v projection (csrc/inproj_bf16.hip): the tile is read once for all 3 W columns; compacted:
+            # the S padding rows are entries of the token list behind the live tokens
+            ops.inproj_bf16(table_bf16, p.w_in, p.in_rows, 3 * W, qkv, a_ids=a_ids, c_ids=c_ids,
+                            m_dev=None if cmp is None else cmp.n_tokens_and_pad_rows)
+        else:
+            if cmp is not None:
+                ops.linear_bf16(table_bf16, p.w_in, None, a_ids=_zero_ids(S, ids.device), res=p.in_rows, res_kind=1, res_mod=S, out=qkv[cap:])
+            ops.linear_bf16(table_bf16, p.w_in, None, a_ids=a_ids, res=p.in_rows, res_kind=1, res_mod=S, out=qkv[:cap], c_ids=c_ids,
+                            m_dev=None if cmp is None else cmp.n_live_tokens, n_alg=3 * E, k_alg=E)
+        q, k, v = qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:]
+        if cmp is None:
+            attn = ops.token_attention_bf16(q, k, v, n_seq, S, nhead, hd, scale, out_cols=EP)
+        else:
+            attn = ops.token_attention_rows_bf16(q, k, v, cmp.row_map, n_seq_dev, n_seq, S, nhead, hd, scale, out_cols=EP)
+        sa = layer.self_attn
+        pool = li == len(transformer.layers) - 1                  # token mean pooling in the epilogue: fp32 means over 32-token blocks
+        res = dict(res=table_bf16, res_kind=2, res_ids=res_ids) if li == 0 else dict(res=x, res_kind=3)
+        ln2 = (layer.norm2.weight, layer.norm2.bias)
+        if p.block:
+            # everything behind the attention core in ONE launch (csrc/ffn_bf16.hip): out_proj + residual + norm1 written into the
+            # stationary LDS tile the feed-forward half then reads
+            x = ops.encoder_block_bf16(attn, p.w0p, p.add_rows, (layer.norm1.weight, layer.norm1.bias), layer.norm1.eps, w1p=p.w1p, w2p=p.w2p,
+                                       b2=layer.linear2.bias, ln2=ln2, ln2_eps=layer.norm2.eps, E=E, pool32=pool, **res, **rows)
+            continue
+        x1 = ops.linear_bf16(attn, p.w_o, p.b_o, res_pe=p.pe_p, res_period=S if li == 0 else 0, ln=p.ln1, ln_eps=layer.norm1.eps, ln_count=E,
+                             n_alg=E, k_alg=E, **res, **rows)
+        if p.ffn:
+            # linear1 + ReLU + linear2 + residual + norm2 in ONE launch: the hidden state stays in registers (csrc/ffn_bf16.hip)
+            x = ops.encoder_ffn_bf16(x1, p.w1p, p.w2p, layer.linear2.bias, ln2, layer.norm2.eps, E, pool32=pool, **rows)
+            continue
+        h = ops.linear_bf16(x1, p.w1, layer.linear1.bias, act='relu', k_alg=E, **rows)
+        x = ops.linear_bf16(h, p.w2, p.b2, res=x1, res_kind=3, ln=p.ln2, ln_eps=layer.norm2.eps, ln_count=E, pool32=pool, n_alg=E, **rows)
+    # x: the last layer's block means, fp32 [cap / 32, EP]
+    pooled = ops.mean_pool(x[:, :E], n_seq, S // 32, out=pooled_out if cmp is None else None, n_seq_dev=n_seq_dev)
+    if cmp is not None:
+        ops.gather_rows(cmp.seq_inv, pooled, pooled_out)
+    return None
+
+
+def encode_tokens_bf16(ids, table_bf16, pe, transformer, nhead, pooled_out):
+    """encode_tokens + mean pool on the bf16 matrix cores (BASELINE config 3).  table_bf16: the word table converted with
+    ``ops.to_bf16`` ([V, E rounded up to 8], zero padded)."""
+    return _encode_layers_bf16(ids, None, table_bf16, pe, transformer, nhead, pooled_out)
 
 
 def encode_tokens_bf16_compact(ids, table_bf16, pe, transformer, nhead, pooled_out, shared=None):
-    """``encode_tokens_bf16`` on the compacted batch (see ``encode_tokens_compact``): live sequences + one all-padding
-    representative through the layer, in_proj over the live tokens, the row-map bf16 attention.  The S padding rows come from
-    the same bf16 GEMM kernel as the live rows (lime_linear_bf16 takes any M)."""
-    M, S = ids.shape
-    EP = table_bf16.shape[1]
-    E = pe.shape[1]
-    hd = E // nhead
-    W = nhead * 32
-    layer = transformer.layers[0]
-    sa = layer.self_attn
-    dev = ids.device
-    cap = (M + 1) * S
-    padv = lambda v: torch.cat([v, v.new_zeros(EP - E)])
-    cmp = ops.compact_sequences(ids)
-    fused = FUSED_BLOCK and _ffn_fused_applicable(layer, E, EP) and E % 4 == 0 and _inproj_applicable(3 * W, EP)
-    if fused and shared is not None and 'w_in_p' in shared:
-        # the passes of one forward over the same encoder share the packed weights (`shared`: a dict that lives for one forward)
-        w_in_p, pew, w0p, w1p, w2p, add_rows = (shared[k] for k in ('w_in_p', 'pew', 'w0p', 'w1p', 'w2p', 'add_rows'))
-    else:
-        w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)
-        b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
-        pew = ops.linear(pe[:S], w_in, b_in)                                   # fp32 [S, 3W]
-        if fused:
-            w_in_p = ops.inproj_pack_bf16(w_in, EP)
-            w1p, w2p = ops.ffn_pack_bf16(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight)
-            w0p, add_rows = ops.oproj_pack_bf16(sa.out_proj.weight), pe[:S] + sa.out_proj.bias
-            if shared is not None:
-                shared.update(w_in_p=w_in_p, pew=pew, w0p=w0p, w1p=w1p, w2p=w2p, add_rows=add_rows)
-    qkv = torch.empty((cap + S, 3 * W), dtype=torch.bfloat16, device=dev)
-    if fused:
-        # three launches: in_proj (the live tokens and, behind them in the token list, the S padding rows the row map points at),
-        # attention, and everything behind it
-        ops.inproj_bf16(table_bf16, w_in_p, pew, 3 * W, qkv, a_ids=cmp.tok_ids, c_ids=cmp.tok_rows, m_dev=cmp.n_tokens_and_pad_rows)
-        attn = ops.token_attention_rows_bf16(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], cmp.row_map, cmp.n_compact, M + 1, S, nhead, hd,
-                                             1.0 / math.sqrt(hd), out_cols=EP)
-        blocks = ops.encoder_block_bf16(attn, w0p, add_rows, (layer.norm1.weight, layer.norm1.bias), layer.norm1.eps, res=table_bf16,
-                                        res_kind=2, res_ids=cmp.ids_c, w1p=w1p, w2p=w2p, b2=layer.linear2.bias,
-                                        ln2=(layer.norm2.weight, layer.norm2.bias), ln2_eps=layer.norm2.eps, E=E, pool32=True,
-                                        m_dev=cmp.n_rows)                       # fp32 [cap / 32, EP] block means
-        pooled_c = ops.mean_pool(blocks[:, :E], M + 1, S // 32, n_seq_dev=cmp.n_compact)
-        ops.gather_rows(cmp.seq_inv, pooled_c, pooled_out)
-        return None
-    if _inproj_applicable(3 * W, EP):
-        ops.inproj_bf16(table_bf16, ops.inproj_pack_bf16(w_in, EP), pew, 3 * W, qkv, a_ids=cmp.tok_ids, c_ids=cmp.tok_rows,
-                        m_dev=cmp.n_tokens_and_pad_rows)
-    else:
-        zeros = _zero_ids(S, dev)
-        w_in_b = ops.to_bf16(w_in, cols_out=EP)
-        ops.linear_bf16(table_bf16, w_in_b, None, a_ids=zeros, res=pew, res_kind=1, res_mod=S, out=qkv[cap:])
-        ops.linear_bf16(table_bf16, w_in_b, None, a_ids=cmp.tok_ids, res=pew, res_kind=1, res_mod=S, out=qkv[:cap], m_dev=cmp.n_live_tokens,
-                        c_ids=cmp.tok_rows, n_alg=3 * E, k_alg=E)
-    attn = ops.token_attention_rows_bf16(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], cmp.row_map, cmp.n_compact, M + 1, S, nhead, hd,
-                                         1.0 / math.sqrt(hd), out_cols=EP)
-    pe_p = torch.cat([pe[:S], pe.new_zeros(S, EP - E)], dim=1)
-    if FUSED_BLOCK and _ffn_fused_applicable(layer, E, EP) and E % 4 == 0:
-        w1p, w2p = ops.ffn_pack_bf16(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight)
-        blocks = ops.encoder_block_bf16(attn, ops.oproj_pack_bf16(sa.out_proj.weight), pe[:S] + sa.out_proj.bias, (layer.norm1.weight, layer.norm1.bias),
-                                        layer.norm1.eps, res=table_bf16, res_kind=2, res_ids=cmp.ids_c, w1p=w1p,
-                                        w2p=w2p, b2=layer.linear2.bias, ln2=(layer.norm2.weight, layer.norm2.bias), ln2_eps=layer.norm2.eps,
-                                        E=E, pool32=True, m_dev=cmp.n_rows)     # fp32 [cap / 32, EP] block means
-        pooled_c = ops.mean_pool(blocks[:, :E], M + 1, S // 32, n_seq_dev=cmp.n_compact)
-        ops.gather_rows(cmp.seq_inv, pooled_c, pooled_out)
-        return None
-    w_o = ops.to_bf16(sa.out_proj.weight, rows_out=EP, cols_out=EP)
-    x1 = ops.linear_bf16(attn, w_o, padv(sa.out_proj.bias), res=table_bf16, res_kind=2, res_ids=cmp.ids_c, res_pe=pe_p, res_period=S,
-                         ln=(padv(layer.norm1.weight), padv(layer.norm1.bias)), ln_eps=layer.norm1.eps, ln_count=E, n_alg=E, k_alg=E,
-                         m_dev=cmp.n_rows)
-    if _ffn_fused_applicable(layer, E, EP):
-        w1p, w2p = ops.ffn_pack_bf16(layer.linear1.weight, layer.linear1.bias, layer.linear2.weight)
-        blocks = ops.encoder_ffn_bf16(x1, w1p, w2p, layer.linear2.bias, (layer.norm2.weight, layer.norm2.bias), layer.norm2.eps, E,
-                                      pool32=True, m_dev=cmp.n_rows)           # fp32 [cap / 32, EP] block means
-    else:
-        h = ops.linear_bf16(x1, ops.to_bf16(layer.linear1.weight, cols_out=EP), layer.linear1.bias, act='relu', k_alg=E, m_dev=cmp.n_rows)
-        blocks = ops.linear_bf16(h, ops.to_bf16(layer.linear2.weight, rows_out=EP), padv(layer.linear2.bias), res=x1, res_kind=3,
-                                 ln=(padv(layer.norm2.weight), padv(layer.norm2.bias)), ln_eps=layer.norm2.eps, ln_count=E, pool32=True,
-                                 n_alg=E, m_dev=cmp.n_rows)
-    pooled_c = ops.mean_pool(blocks[:, :E], M + 1, S // 32, n_seq_dev=cmp.n_compact)
-    ops.gather_rows(cmp.seq_inv, pooled_c, pooled_out)
-    return None
+    """``encode_tokens_bf16`` on the compacted batch (see ``encode_tokens_compact``).  The S padding rows come from the same bf16
+    GEMM kernel as the live rows (lime_linear_bf16 takes any M)."""
+    if len(transformer.layers) != 1:
+        raise NotImplementedError('the compacted bf16 path covers one encoder layer (compact_applicable_bf16)')
+    return _encode_layers_bf16(ids, ops.compact_sequences(ids), table_bf16, pe, transformer, nhead, pooled_out, shared)
 
 
 def compact_applicable_bf16(ids, transformer, nhead, E):
@@ -1002,27 +944,30 @@ class CROWN(NewsEncoder):
 class MHSA(NewsEncoder):
     """newsEncoders.py:566-595: title-only multi-head self-attention + additive attention.  -> [B, n, 300]."""
 
-    def _encode_compact(self, ids, mask, out):
-        """The title encoder over the live sequences + ONE representative of the padding news' title (see
-        ``encode_tokens_compact``; sequence level only: this encoder masks its padding tokens, so their rows are needed).  A
-        sequence repeats the representative when its ids are all zero AND its mask is the padding news' mask (first position
-        set, corpus.py:476-477); an all-zero sequence with any other mask counts as live."""
+    def _encode(self, ids, mask, out, compact):
+        """Project -> attend -> tanh GEMM -> additive pool over the titles ``ids`` [n, T].  ``compact``: over the live sequences + ONE
+        representative of the padding news' title (see ``encode_tokens_compact``; sequence level only: this encoder masks its padding
+        tokens, so their rows are needed).  A sequence repeats the representative when its ids are all zero AND its mask is the padding
+        news' mask (first position set, corpus.py:476-477); an all-zero sequence with any other mask counts as live."""
         n, T = ids.shape
         mha = self.multiheadAttention
-        dev = ids.device
-        if mask.dtype not in (torch.bool, torch.uint8):
-            mask = mask.bool()
-        mask = mask.contiguous()
-        # all-zero ids under a mask that is not the padding news' mask: live (a sentinel in the first id); behind the compaction the
-        # sentinel goes back to the padding word and the key mask is gathered into compact order -- two launches (they were ~18 torch ops)
-        cmp = ops.compact_sequences(ops.mhsa_live_ids(ids, mask))
-        mask_c = ops.mhsa_compact_mask(cmp, mask)
-        ids_c = cmp.ids_c
-        qkv = mha.project(table=self.word_embedding.weight, ids=ids_c, m_dev=cmp.n_rows)
-        c = mha.attend(qkv, n + 1, T, mask_c, n_seq_dev=cmp.n_compact)
-        hidden = ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', m_dev=cmp.n_rows)
-        pooled_c = ops.additive_pool(hidden, self.attention.affine2.weight.view(-1), c, n + 1, T, mask=mask_c, n_seq_dev=cmp.n_compact)
-        ops.gather_rows(cmp.seq_inv, pooled_c, out)
+        n_seq, rows, seqs, ids_r = n, {}, {}, ids.reshape(-1)
+        if compact:
+            if mask.dtype not in (torch.bool, torch.uint8):
+                mask = mask.bool()
+            mask = mask.contiguous()
+            # all-zero ids under a mask that is not the padding news' mask: live (a sentinel in the first id); behind the compaction the
+            # sentinel goes back to the padding word and the key mask is gathered into compact order -- two launches (they were ~18 torch ops)
+            cmp = ops.compact_sequences(ops.mhsa_live_ids(ids, mask))
+            mask = ops.mhsa_compact_mask(cmp, mask)
+            n_seq, rows, seqs, ids_r = n + 1, dict(m_dev=cmp.n_rows), dict(n_seq_dev=cmp.n_compact), cmp.ids_c
+        qkv = mha.project(table=self.word_embedding.weight, ids=ids_r, **rows)                          # :588 + layers.py:224-226
+        c = mha.attend(qkv, n_seq, T, mask, **seqs)                                                     # layers.py:227-237
+        hidden = ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', **rows)
+        pooled = ops.additive_pool(hidden, self.attention.affine2.weight.view(-1), c, n_seq, T, mask=mask, out=None if compact else out,
+                                   **seqs)                                                              # :592
+        if compact:
+            ops.gather_rows(cmp.seq_inv, pooled, out)
 
     def _compact_applicable(self, ids, n, T):
         """The compacted title path rests on the device-count forms of the kernels, which are stricter than the dense ones:
@@ -1053,19 +998,11 @@ class MHSA(NewsEncoder):
         M, T = title_text.shape
         F = self.feature_dim
         mask = title_mask.contiguous()
-        mha = self.multiheadAttention
         step = max(1, MAX_TOKENS_PER_PASS // T)
         for m0 in range(0, M, step):
             m1 = min(M, m0 + step)
             ids = title_text[m0:m1]
-            if self._compact_applicable(ids, m1 - m0, T):
-                self._encode_compact(ids, mask[m0:m1], out[m0:m1, :F])
-                continue
-            qkv = mha.project(table=self.word_embedding.weight, ids=ids.reshape(-1))                    # :588 + layers.py:224-226
-            c = mha.attend(qkv, m1 - m0, T, mask[m0:m1])                                                # layers.py:227-237
-            hidden = ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh')
-            ops.additive_pool(hidden, self.attention.affine2.weight.view(-1), c, m1 - m0, T, mask=mask[m0:m1],
-                              out=out[m0:m1, :F])                                                       # :592
+            self._encode(ids, mask[m0:m1], out[m0:m1, :F], self._compact_applicable(ids, m1 - m0, T))
         ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
                       emb_out=out[:, F:])                                                               # :594
         return out

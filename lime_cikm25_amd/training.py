@@ -4,7 +4,8 @@
 
 Where the arithmetic runs
   * token encoders (word gather + positional table + post-LN encoder layer + mean pool, 97 % of a step's FLOPs):
-    hand-written HIP forward AND backward behind one autograd node (``_TokenEncoder``): the forward of the scoring path
+    hand-written HIP forward AND backward behind one autograd node (``_TokenEncoder``, over ``_layer_forward`` /
+    ``_layer_backward``, which the per-layer node of the two-layer path shares): the forward of the scoring path
     with the LayerNorm rstd kept, backward = LayerNorm / attention / ReLU backward kernels, the MFMA weight-gradient GEMM,
     input gradients on lime_linear_f32 with transposed weights, word-table scatter-add.
   * every nn.Linear of the tail and the user encoder: ``_Linear`` (HIP GEMMs forward and backward).
@@ -268,117 +269,136 @@ def _unpad_heads(t, groups, hd, hs):
 _SITE_EMB, _SITE_PE, _SITE_ATTN, _SITE_DROP1, _SITE_FF, _SITE_DROP2 = range(6)
 
 
-class _TokenEncoder(torch.autograd.Function):
-    """pooled [M, E] = mean_S(EncoderLayer(E[ids] + PE))  (newsEncoders.py:311-321 for one of title / body).
+def _layer_forward(ctx, x, gather, M, S, nhead, eps1, eps2, p, seed, in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w,
+                   n2_b, live=None):
+    """y [M S, E] = one post-LN TransformerEncoderLayer (newsEncoders.py:244-247): in_proj, attention, out_proj + residual + LayerNorm,
+    linear1 + ReLU, linear2 + residual + LayerNorm on the kernels of the scoring path with the LayerNorm rstd kept, or -- p > 0,
+    training-mode dropout seeded per call -- with the layer's four dropouts on the dropout kernels (masks are regenerated in the
+    backward from (seed, site)).  Leaves on ``ctx`` what ``_layer_backward`` reads.
 
-    p = 0: the fused forward of the scoring path (word gather inside the in_proj GEMM, residual + LayerNorm in the GEMM
-    epilogues).  p > 0 (training-mode dropout, seeded per call): the same layer with its six dropouts -- word embeddings and
-    positional sum (:311-312, :827), attention probabilities, dropout1 / dropout / dropout2 of the encoder layer -- on the
-    dropout kernels; masks are regenerated in the backward from (seed, site)."""
+    The input is ``x`` [M S, E], materialised, or (x None) ``gather`` = (flat ids, table, pe): E[ids] + PE.  With p = 0 that one is
+    gathered inside the in_proj GEMM and rebuilt in out_proj's epilogue; with p > 0 it is materialised through its two dropouts (word
+    embeddings and positional sum, :311-312, :827).
+    live (optional, gathered input, p = 0): (ids, rows) of the non-padding tokens (int32 device tensors, lime_compact_sequences' tok_ids /
+    tok_rows cut to their count): in_proj then runs over those only and the padding tokens' q / k / v rows -- a function of the position
+    alone -- are copied in from S rows (the reference's batch is 72 % padding tokens: newsEncoders.py:311-312 embeds them all the same)."""
+    E = in_w.shape[1]
+    hd = E // nhead
+    hs = 32 if hd <= 32 else hd
+    if hs > 32 or S > 512:
+        raise NotImplementedError('the attention kernels cover head_dim <= 32 and S <= 512 (got %d, %d)' % (hd, S))
+    W = nhead * hs
+    tok = M * S
+    dev = in_w.device
+    scale = 1.0 / math.sqrt(hd)
+    w_in = ops.pad_heads(in_w, 3 * nhead, hd, hs) if hs != hd else in_w
+    b_in = ops.pad_heads(in_b, 3 * nhead, hd, hs) if hs != hd else in_b
+    if x is None and p > 0:
+        x = ops.embed_pe_dropout(*gather, S, p, seed, _SITE_EMB, _SITE_PE)
+    if x is not None:
+        qkv = ops.linear(x, w_in, b_in, n_alg=3 * E)
+        res = dict(res=x)
+    else:
+        flat, table, pe = gather
+        pew = ops.linear(pe[:S], w_in, b_in)
+        if live is not None and live[0].numel() >= 4096:
+            tok_ids, tok_rows = live
+            qkv = torch.empty((tok, 3 * W), dtype=torch.float32, device=dev)
+            ops.linear(table, w_in, None, a_ids=tok_ids, res=pew, res_mod=S, n_alg=3 * E, c_ids=tok_rows, out=qkv)
+            pad_rows = ops.linear(table, w_in, None, a_ids=torch.zeros(S, dtype=torch.int32, device=dev), res=pew, res_mod=S)
+            ops.fill_pad_rows(flat, pad_rows, qkv, S)
+        else:
+            qkv = ops.linear(table, w_in, None, a_ids=flat, res=pew, res_mod=S, n_alg=3 * E)
+        res = dict(res=table, res_ids=flat, res_pe=pe, res_period=S)
+    lse = None
+    if p > 0:
+        ao = ops.token_attention_dropout(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, scale, p, seed, _SITE_ATTN,
+                                         head_stride=hs)
+        x1, rstd1 = ops.dropout_add_layernorm(ops.linear(ao, out_w, out_b), x, n1_w, n1_b, eps1, p, seed, _SITE_DROP1)
+        h = ops.linear(x1, l1_w, l1_b, act='relu', dropout=(p, seed, _SITE_FF))     # the dropout behind the ReLU in the GEMM's epilogue
+        y, rstd2 = ops.dropout_add_layernorm(ops.linear(h, l2_w, l2_b), x1, n2_w, n2_b, eps2, p, seed, _SITE_DROP2)
+    else:
+        # S > 128: the forward keeps its softmax statistics, the blocked backward does not recompute them
+        lse = torch.empty(tok * nhead, dtype=torch.float32, device=dev) if S > 128 else None
+        ao = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, scale, head_stride=hs, lse=lse)
+        rstd1 = torch.empty(tok, dtype=torch.float32, device=dev)
+        x1 = ops.linear(ao, out_w, out_b, ln=(n1_w, n1_b), ln_eps=eps1, ln_rstd=rstd1, **res)
+        h = ops.linear(x1, l1_w, l1_b, act='relu')
+        rstd2 = torch.empty(tok, dtype=torch.float32, device=dev)
+        y = ops.linear(h, l2_w, l2_b, res=x1, ln=(n2_w, n2_b), ln_eps=eps2, ln_rstd=rstd2)
+    ctx.dims = (M, S, E, nhead, hd, hs, p, seed)
+    ctx.lse = lse
+    ctx.save_for_backward(w_in, out_w, l1_w, l2_w, n1_w, n1_b, n2_w, n2_b, qkv, ao, x1, rstd1, h, y, rstd2, x, *(gather or ()))
+    return y
+
+
+def _layer_backward(ctx, dy, pooled=False):
+    """Backward of ``_layer_forward``: LayerNorm / attention / ReLU backward kernels, the MFMA weight-gradient GEMM, input gradients on
+    lime_linear_f32 with transposed weights.  dy: the gradient of y [M S, E], or -- ``pooled`` -- of its token means [M, E].
+    -> (the gradient of the layer input [M S, E], the gradients of the twelve weights in ``_layer_forward``'s order)."""
+    (w_in, out_w, l1_w, l2_w, n1_w, n1_b, n2_w, n2_b, qkv, ao, x1, rstd1, h, y, rstd2, x, *gather) = ctx.saved_tensors
+    M, S, E, nhead, hd, hs, p, seed = ctx.dims
+    W = nhead * hs
+    drop = p > 0
+    keep_scale = 1.0 / (1.0 - p) if drop else 1.0
+    # norm2 <- mean pool: every token of a sequence receives dpooled / S
+    dy_kw = dict(dy_div=S, dy_scale=1.0 / S) if pooled else {}
+    if drop:                                                                   # dt2: the branch through dropout2 into linear2, same pass
+        dz2, dn2_w, dn2_b, dl2_b, dt2 = ops.layernorm_bwd(dy.contiguous(), y, n2_w, n2_b, rstd2, dropout=(p, seed, _SITE_DROP2), **dy_kw)
+    else:                                                                      # dl2_b: column sums of dt2
+        dz2, dn2_w, dn2_b, dl2_b = ops.layernorm_bwd(dy.contiguous(), y, n2_w, n2_b, rstd2, **dy_kw)
+        dt2 = dz2
+    del y
+    dl2_w = ops.linear_wgrad(dt2, h)
+    # dH = dT2 W2 with the ReLU (and dropout) gradient in the GEMM's epilogue: h > 0 <=> ReLU passed and the mask kept
+    dh = ops.linear(dt2, l2_w.t().contiguous(), None, act='relu_grad', res=h, act_scale=keep_scale)
+    del h, dt2
+    dl1_w, dl1_b = ops.linear_wgrad(dh, x1, want_bias=True)
+    dx1 = ops.linear(dh, l1_w.t().contiguous(), None, res=dz2)                 # through linear1 + the residual branch
+    del dh, dz2
+    if drop:
+        dz1, dn1_w, dn1_b, dout_b, dt1 = ops.layernorm_bwd(dx1, x1, n1_w, n1_b, rstd1, dropout=(p, seed, _SITE_DROP1))
+    else:
+        dz1, dn1_w, dn1_b, dout_b = ops.layernorm_bwd(dx1, x1, n1_w, n1_b, rstd1)
+        dt1 = dz1
+    del dx1, x1
+    dout_w = ops.linear_wgrad(dt1, ao)
+    dao = ops.linear(dt1, out_w.t().contiguous(), None)
+    dqkv = ops.token_attention_bwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], dao, M, S, nhead, hd, 1.0 / math.sqrt(hd),
+                                   head_stride=hs, out=ao, dropout=(p, seed, _SITE_ATTN) if drop else None, lse=ctx.lse)
+    del dao, qkv, ao, dt1
+    if x is None:
+        x = ops.embed_pe(*gather, S)                                           # the layer input, re-gathered
+    din_w, din_b = ops.linear_wgrad(dqkv, x, want_bias=True)
+    din_w, din_b = _unpad_heads(din_w, 3 * nhead, hd, hs), _unpad_heads(din_b, 3 * nhead, hd, hs)
+    del x
+    dx = ops.linear(dqkv, w_in.t().contiguous(), None, res=dz1)                # through in_proj + the residual branch
+    return dx, (din_w, din_b, dout_w, dout_b, dl1_w, dl1_b, dl2_w, dl2_b, dn1_w, dn1_b, dn2_w, dn2_b)
+
+
+class _TokenEncoder(torch.autograd.Function):
+    """pooled [M, E] = mean_S(EncoderLayer(E[ids] + PE))  (newsEncoders.py:311-321 for one of title / body): ``_layer_forward`` over
+    the gathered input (``*live``: its live-token lists) + the token mean, the word-table scatter-add behind ``_layer_backward``."""
 
     @staticmethod
-    def forward(ctx, ids, nhead, eps1, eps2, p, seed, table, pe, in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w,
-                n2_b, *live):
-        # live (optional, p = 0): (ids, rows) of the non-padding tokens (int32 device tensors, lime_compact_sequences' tok_ids / tok_rows cut
-        # to their count): in_proj then runs over those only and the padding tokens' q / k / v rows -- a function of the position alone --
-        # are copied in from S rows (the reference's batch is 72 % padding tokens: newsEncoders.py:311-312 embeds them all the same)
-        ctx.n_extra = len(live)
-        live = live[0] if live else None
+    def forward(ctx, ids, nhead, eps1, eps2, p, seed, table, pe, *weights_live):
         M, S = ids.shape
-        E = table.shape[1]
-        hd = E // nhead
-        hs = 32 if hd <= 32 else hd
-        if hs > 32 or S > 512:
-            raise NotImplementedError('the attention kernels cover head_dim <= 32 and S <= 512 (got %d, %d)' % (hd, S))
-        W = nhead * hs
-        flat = ids.reshape(-1).contiguous()
-        tok = M * S
-        dev = table.device
-        scale = 1.0 / math.sqrt(hd)
-        w_in = ops.pad_heads(in_w, 3 * nhead, hd, hs) if hs != hd else in_w
-        b_in = ops.pad_heads(in_b, 3 * nhead, hd, hs) if hs != hd else in_b
-        x0 = None
-        if p > 0:
-            x0 = ops.embed_pe_dropout(flat, table, pe, S, p, seed, _SITE_EMB, _SITE_PE)
-            qkv = ops.linear(x0, w_in, b_in, n_alg=3 * E)
-            ao = ops.token_attention_dropout(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, scale, p, seed, _SITE_ATTN,
-                                             head_stride=hs)
-            x1, rstd1 = ops.dropout_add_layernorm(ops.linear(ao, out_w, out_b), x0, n1_w, n1_b, eps1, p, seed, _SITE_DROP1)
-            h = ops.linear(x1, l1_w, l1_b, act='relu', dropout=(p, seed, _SITE_FF))     # the dropout behind the ReLU in the GEMM's epilogue
-            y, rstd2 = ops.dropout_add_layernorm(ops.linear(h, l2_w, l2_b), x1, n2_w, n2_b, eps2, p, seed, _SITE_DROP2)
-        else:
-            pew = ops.linear(pe[:S], w_in, b_in)
-            if live is not None and live[0].numel() >= 4096:
-                tok_ids, tok_rows = live
-                qkv = torch.empty((tok, 3 * W), dtype=torch.float32, device=dev)
-                ops.linear(table, w_in, None, a_ids=tok_ids, res=pew, res_mod=S, n_alg=3 * E, c_ids=tok_rows, out=qkv)
-                pad_rows = ops.linear(table, w_in, None, a_ids=torch.zeros(S, dtype=torch.int32, device=dev), res=pew, res_mod=S)
-                ops.fill_pad_rows(flat, pad_rows, qkv, S)
-            else:
-                qkv = ops.linear(table, w_in, None, a_ids=flat, res=pew, res_mod=S, n_alg=3 * E)
-            # S > 128: the forward keeps its softmax statistics, the blocked backward does not recompute them
-            lse = torch.empty(tok * nhead, dtype=torch.float32, device=dev) if S > 128 else None
-            ao = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, scale, head_stride=hs, lse=lse)
-            rstd1 = torch.empty(tok, dtype=torch.float32, device=dev)
-            x1 = ops.linear(ao, out_w, out_b, res=table, res_ids=flat, res_pe=pe, res_period=S, ln=(n1_w, n1_b), ln_eps=eps1,
-                            ln_rstd=rstd1)
-            h = ops.linear(x1, l1_w, l1_b, act='relu')
-            rstd2 = torch.empty(tok, dtype=torch.float32, device=dev)
-            y = ops.linear(h, l2_w, l2_b, res=x1, ln=(n2_w, n2_b), ln_eps=eps2, ln_rstd=rstd2)
-        pooled = ops.mean_pool(y, M, S)
-        ctx.dims = (M, S, E, nhead, hd, hs, p, seed)
-        ctx.lse = lse if p == 0 else None
-        ctx.save_for_backward(flat, table, pe, w_in, out_w, l1_w, l2_w, n1_w, n1_b, n2_w, n2_b, qkv, ao, x1, rstd1, h, y, rstd2, x0)
-        return pooled
+        ctx.n_extra = len(weights_live) - 12
+        y = _layer_forward(ctx, None, (ids.reshape(-1).contiguous(), table, pe), M, S, nhead, eps1, eps2, p, seed, *weights_live)
+        return ops.mean_pool(y, M, S)
 
     @staticmethod
     def backward(ctx, dpooled):
-        (flat, table, pe, w_in, out_w, l1_w, l2_w, n1_w, n1_b, n2_w, n2_b, qkv, ao, x1, rstd1, h, y, rstd2, x0) = ctx.saved_tensors
-        M, S, E, nhead, hd, hs, p, seed = ctx.dims
-        W = nhead * hs
-        drop = p > 0
-        keep_scale = 1.0 / (1.0 - p) if drop else 1.0
-        dpooled = dpooled.contiguous()
-        # norm2 <- mean pool: every token of a sequence receives dpooled / S
-        if drop:                                                                   # dt2: the branch through dropout2 into linear2, same pass
-            dz2, dn2_w, dn2_b, dl2_b, dt2 = ops.layernorm_bwd(dpooled, y, n2_w, n2_b, rstd2, dy_div=S, dy_scale=1.0 / S,
-                                                             dropout=(p, seed, _SITE_DROP2))            # dl2_b: column sums of dt2
-        else:
-            dz2, dn2_w, dn2_b, dl2_b = ops.layernorm_bwd(dpooled, y, n2_w, n2_b, rstd2, dy_div=S, dy_scale=1.0 / S)
-            dt2 = dz2
-        del y
-        dl2_w = ops.linear_wgrad(dt2, h)
-        # dH = dT2 W2 with the ReLU (and dropout) gradient in the GEMM's epilogue: h > 0 <=> ReLU passed and the mask kept
-        dh = ops.linear(dt2, l2_w.t().contiguous(), None, act='relu_grad', res=h, act_scale=keep_scale)
-        del h, dt2
-        dl1_w, dl1_b = ops.linear_wgrad(dh, x1, want_bias=True)
-        dx1 = ops.linear(dh, l1_w.t().contiguous(), None, res=dz2)                 # through linear1 + the residual branch
-        del dh, dz2
-        if drop:
-            dz1, dn1_w, dn1_b, dout_b, dt1 = ops.layernorm_bwd(dx1, x1, n1_w, n1_b, rstd1, dropout=(p, seed, _SITE_DROP1))
-        else:
-            dz1, dn1_w, dn1_b, dout_b = ops.layernorm_bwd(dx1, x1, n1_w, n1_b, rstd1)
-            dt1 = dz1
-        del dx1, x1
-        dout_w = ops.linear_wgrad(dt1, ao)
-        dao = ops.linear(dt1, out_w.t().contiguous(), None)
-        dqkv = ops.token_attention_bwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], dao, M, S, nhead, hd, 1.0 / math.sqrt(hd),
-                                       head_stride=hs, out=ao, dropout=(p, seed, _SITE_ATTN) if drop else None, lse=ctx.lse)
-        del dao, qkv, ao, dt1
-        if x0 is None:
-            x0 = ops.embed_pe(flat, table, pe, S)                                  # the layer input, re-gathered
-        din_w, din_b = ops.linear_wgrad(dqkv, x0, want_bias=True)
-        din_w, din_b = _unpad_heads(din_w, 3 * nhead, hd, hs), _unpad_heads(din_b, 3 * nhead, hd, hs)
-        del x0
-        dx0 = ops.linear(dqkv, w_in.t().contiguous(), None, res=dz1)               # through in_proj + the residual branch
+        dx0, dweights = _layer_backward(ctx, dpooled, pooled=True)
+        flat, table = ctx.saved_tensors[-3:-1]
+        p, seed = ctx.dims[-2:]
         dtable = None
         if ctx.needs_input_grad[6]:
-            if drop:                                                               # back through the two input dropouts, one pass
+            if p > 0:                                                              # back through the two input dropouts, one pass
                 ops.dropout2(dx0, p, seed, _SITE_PE, _SITE_EMB, out=dx0)
             dtable = torch.zeros_like(table)
             ops.embed_bwd(flat, dx0, dtable, hot_id=0)
-        return (None, None, None, None, None, None, dtable, None, din_w, din_b, dout_w, dout_b, dl1_w, dl1_b, dl2_w, dl2_b, dn1_w,
-                dn1_b, dn2_w, dn2_b) + (None,) * ctx.n_extra
+        return (None, None, None, None, None, None, dtable, None) + dweights + (None,) * ctx.n_extra
 
 
 class _EmbedPE(torch.autograd.Function):
@@ -410,79 +430,17 @@ class _EmbedPE(torch.autograd.Function):
 
 
 class _EncoderLayer(torch.autograd.Function):
-    """y [M S, E] = one post-LN TransformerEncoderLayer over a MATERIALISED input x (newsEncoders.py:244-247): what a layer behind the
-    first needs (config.py:70 allows num_layers = 2), and the first one on that path too.  Same kernels as ``_TokenEncoder`` -- in_proj,
-    attention, out_proj + residual + LayerNorm, linear1 + ReLU, linear2 + residual + LayerNorm, with the four in-layer dropouts on the
-    counter-based masks when p > 0 -- with a dense residual instead of the gathered one, and dx as the input gradient."""
+    """y [M S, E] = ``_layer_forward`` over a MATERIALISED input x: what a layer behind the first needs (config.py:70 allows
+    num_layers = 2), and the first one on that path too; dx as the input gradient."""
 
     @staticmethod
-    def forward(ctx, x, M, S, nhead, eps1, eps2, p, seed, in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b):
-        x = x.contiguous()
-        E = x.shape[1]
-        hd = E // nhead
-        hs = 32 if hd <= 32 else hd
-        if hs > 32 or S > 512:
-            raise NotImplementedError('the attention kernels cover head_dim <= 32 and S <= 512 (got %d, %d)' % (hd, S))
-        W = nhead * hs
-        tok = M * S
-        dev = x.device
-        scale = 1.0 / math.sqrt(hd)
-        w_in = ops.pad_heads(in_w, 3 * nhead, hd, hs) if hs != hd else in_w
-        b_in = ops.pad_heads(in_b, 3 * nhead, hd, hs) if hs != hd else in_b
-        qkv = ops.linear(x, w_in, b_in, n_alg=3 * E)
-        if p > 0:
-            ao = ops.token_attention_dropout(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, scale, p, seed, _SITE_ATTN,
-                                             head_stride=hs)
-            x1, rstd1 = ops.dropout_add_layernorm(ops.linear(ao, out_w, out_b), x, n1_w, n1_b, eps1, p, seed, _SITE_DROP1)
-            h = ops.linear(x1, l1_w, l1_b, act='relu', dropout=(p, seed, _SITE_FF))     # the dropout behind the ReLU in the GEMM's epilogue
-            y, rstd2 = ops.dropout_add_layernorm(ops.linear(h, l2_w, l2_b), x1, n2_w, n2_b, eps2, p, seed, _SITE_DROP2)
-        else:
-            lse = torch.empty(tok * nhead, dtype=torch.float32, device=dev) if S > 128 else None
-            ao = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], M, S, nhead, hd, scale, head_stride=hs, lse=lse)
-            rstd1 = torch.empty(tok, dtype=torch.float32, device=dev)
-            x1 = ops.linear(ao, out_w, out_b, res=x, ln=(n1_w, n1_b), ln_eps=eps1, ln_rstd=rstd1)
-            h = ops.linear(x1, l1_w, l1_b, act='relu')
-            rstd2 = torch.empty(tok, dtype=torch.float32, device=dev)
-            y = ops.linear(h, l2_w, l2_b, res=x1, ln=(n2_w, n2_b), ln_eps=eps2, ln_rstd=rstd2)
-        ctx.dims = (M, S, E, nhead, hd, hs, p, seed)
-        ctx.lse = lse if p == 0 else None
-        ctx.save_for_backward(x, w_in, out_w, l1_w, l2_w, n1_w, n1_b, n2_w, n2_b, qkv, ao, x1, rstd1, h, y, rstd2)
-        return y
+    def forward(ctx, x, M, S, nhead, eps1, eps2, p, seed, *weights):
+        return _layer_forward(ctx, x.contiguous(), None, M, S, nhead, eps1, eps2, p, seed, *weights)
 
     @staticmethod
     def backward(ctx, dy):
-        (x, w_in, out_w, l1_w, l2_w, n1_w, n1_b, n2_w, n2_b, qkv, ao, x1, rstd1, h, y, rstd2) = ctx.saved_tensors
-        M, S, E, nhead, hd, hs, p, seed = ctx.dims
-        W = nhead * hs
-        drop = p > 0
-        keep_scale = 1.0 / (1.0 - p) if drop else 1.0
-        if drop:                                                                   # dt2: the branch through dropout2 into linear2, same pass
-            dz2, dn2_w, dn2_b, dl2_b, dt2 = ops.layernorm_bwd(dy.contiguous(), y, n2_w, n2_b, rstd2, dropout=(p, seed, _SITE_DROP2))
-        else:
-            dz2, dn2_w, dn2_b, dl2_b = ops.layernorm_bwd(dy.contiguous(), y, n2_w, n2_b, rstd2)
-            dt2 = dz2
-        dl2_w = ops.linear_wgrad(dt2, h)
-        # dH = dT2 W2 with the ReLU (and dropout) gradient in the GEMM's epilogue: h > 0 <=> ReLU passed and the mask kept
-        dh = ops.linear(dt2, l2_w.t().contiguous(), None, act='relu_grad', res=h, act_scale=keep_scale)
-        dl1_w, dl1_b = ops.linear_wgrad(dh, x1, want_bias=True)
-        dx1 = ops.linear(dh, l1_w.t().contiguous(), None, res=dz2)                 # through linear1 + the residual branch
-        del dh, dz2
-        if drop:
-            dz1, dn1_w, dn1_b, dout_b, dt1 = ops.layernorm_bwd(dx1, x1, n1_w, n1_b, rstd1, dropout=(p, seed, _SITE_DROP1))
-        else:
-            dz1, dn1_w, dn1_b, dout_b = ops.layernorm_bwd(dx1, x1, n1_w, n1_b, rstd1)
-            dt1 = dz1
-        del dx1
-        dout_w = ops.linear_wgrad(dt1, ao)
-        dao = ops.linear(dt1, out_w.t().contiguous(), None)
-        dqkv = ops.token_attention_bwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], dao, M, S, nhead, hd, 1.0 / math.sqrt(hd),
-                                       head_stride=hs, out=ao, dropout=(p, seed, _SITE_ATTN) if drop else None, lse=ctx.lse)
-        del dao, dt1
-        din_w, din_b = ops.linear_wgrad(dqkv, x, want_bias=True)
-        din_w, din_b = _unpad_heads(din_w, 3 * nhead, hd, hs), _unpad_heads(din_b, 3 * nhead, hd, hs)
-        dx = ops.linear(dqkv, w_in.t().contiguous(), None, res=dz1)                # through in_proj + the residual branch
-        return (dx, None, None, None, None, None, None, None, din_w, din_b, dout_w, dout_b, dl1_w, dl1_b, dl2_w, dl2_b, dn1_w, dn1_b,
-                dn2_w, dn2_b)
+        dx, dweights = _layer_backward(ctx, dy)
+        return (dx, None, None, None, None, None, None, None) + dweights
 
 
 class _SeqExpand(torch.autograd.Function):
@@ -547,24 +505,20 @@ def encode_tokens(ids, table, pos_encoder, transformer, nhead, p_embedding=0.0):
     p = float(ps[0])
     ids = ids.contiguous()
     dd = _dedup_sequences(ids) if p == 0 else None
+    seed = lambda: _draw_seed() if p > 0 else 0
+    weights = lambda l: (l.self_attn.in_proj_weight, l.self_attn.in_proj_bias, l.self_attn.out_proj.weight, l.self_attn.out_proj.bias,
+                         l.linear1.weight, l.linear1.bias, l.linear2.weight, l.linear2.bias, l.norm1.weight, l.norm1.bias, l.norm2.weight,
+                         l.norm2.bias)
     if len(layers) == 1:
         layer = layers[0]
-        sa = layer.self_attn
-        run = lambda rows, *live: _TokenEncoder.apply(rows, nhead, layer.norm1.eps, layer.norm2.eps, p, _draw_seed() if p > 0 else 0, table,
-                                                      pos_encoder.table(), sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight,
-                                                      sa.out_proj.bias, layer.linear1.weight, layer.linear1.bias, layer.linear2.weight,
-                                                      layer.linear2.bias, layer.norm1.weight, layer.norm1.bias, layer.norm2.weight,
-                                                      layer.norm2.bias, *live)
+        run = lambda rows, *live: _TokenEncoder.apply(rows, nhead, layer.norm1.eps, layer.norm2.eps, p, seed(), table, pos_encoder.table(),
+                                                      *weights(layer), *live)
     else:
         def run(rows):                                  # num_layers = 2 (config.py:70): materialised input, one node per layer, mean pool
             M, S = rows.shape
-            x = _EmbedPE.apply(rows, table, pos_encoder.table(), p, _draw_seed() if p > 0 else 0)
+            x = _EmbedPE.apply(rows, table, pos_encoder.table(), p, seed())
             for layer in layers:
-                sa = layer.self_attn
-                x = _EncoderLayer.apply(x, M, S, nhead, layer.norm1.eps, layer.norm2.eps, p, _draw_seed() if p > 0 else 0,
-                                        sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.linear1.weight,
-                                        layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm1.weight, layer.norm1.bias,
-                                        layer.norm2.weight, layer.norm2.bias)
+                x = _EncoderLayer.apply(x, M, S, nhead, layer.norm1.eps, layer.norm2.eps, p, seed(), *weights(layer))
             return x.view(M, S, -1).mean(dim=1)                                                                 # :317 / :321
     if dd is None:
         return run(ids)
