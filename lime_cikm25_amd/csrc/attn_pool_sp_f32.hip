@@ -20,7 +20,7 @@
 //     t = 0 .. T - 1 in order, re-reading the tile's x rows (L2 hits).
 // A device sequence count (n_seq_dev) bounds the work of a compacted batch: sequences beyond it are neither read nor written.
 #include "common.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 
 using namespace lime_dev;
@@ -50,13 +50,6 @@ struct AttnPoolP {
     int D, A, n_seq, T, spt, steps, passes;
     const int* n_seq_dev;
 };
-
-// The lane id, recomputed where it is called (ffn_sp_f32.hip: keeps hipcc from carrying the derived offsets through the tile loop)
-__device__ __forceinline__ int lane_here() {
-    int z = 0;
-    asm volatile("" : "+v"(z));
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
 
 // one 16 x 16 x 32 block: w = eight k values of hidden column fi (the three LDS term images), x = eight k values of row fi
 template <bool SPLIT>
@@ -320,17 +313,6 @@ __global__ void attn_pool_pack_kernel(const float* __restrict__ w1, long ldw1, i
     d[2 * PW * 32] = (uint16_t)(t.l & 0xFFFFu);
 }
 
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 int steps_of(int D) { return (D + 63) / 64; }
 int passes_of(int A) { return (A + PW - 1) / PW; }
 bool dims_ok(int D, int A) { return D > 0 && D % 4 == 0 && D <= 0x4000 && A > 0 && A <= A_MAX; }
@@ -373,7 +355,7 @@ extern "C" int lime_attn_pool_sp_f32(const float* x, int64_t ldx, int32_t D, con
     p.D = D; p.A = A; p.n_seq = n_seq; p.T = T; p.spt = BM / T; p.steps = steps_of(D); p.passes = passes_of(A);
     p.n_seq_dev = n_seq_dev;
     const long ntiles = ((long)n_seq + p.spt - 1) / p.spt;
-    long nwg = num_cus();
+    long nwg = lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
     hipStream_t s = (hipStream_t)stream;
     if (lime_split_mode() & 1) hipLaunchKernelGGL((attn_pool_sp_kernel<true>), dim3((unsigned)nwg), dim3(256), 0, s, p);

@@ -15,18 +15,11 @@
 #include "gemm_pp.h"
 #include "split_mfma.h"
 
+using namespace lime_dev;
+
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-// buffer addressing (as in gemm_f32.hip): wave-uniform base + 32-bit lane offset, an out-of-range offset reads as zero
-constexpr unsigned OOB = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFF0, 0x00020000);
-}
-__device__ __forceinline__ f32x4v buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
+// buffer addressing (dev_helpers.h): wave-uniform base + 32-bit lane offset, an out-of-range offset reads as zero
 __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
@@ -77,33 +70,33 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
 __global__ __launch_bounds__(256) void reduce_partials_vec4_kernel(const float* __restrict__ ws, long split_stride, int splits,
                                                                     long ldw, float* __restrict__ out, long ldo, int rows, int cols,
                                                                     int accumulate, float* __restrict__ extra) {
-    __shared__ f32x4v red4[4][64];
+    __shared__ f32x4 red4[4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c4 = (cols >> 2) + (extra != nullptr ? 1 : 0);
     const long e = (long)blockIdx.x * 64 + lane;                 // group of four columns
     const bool ok = e < (long)rows * c4;
     const int r = ok ? (int)(e / c4) : 0, c = ok ? (int)(e - (long)r * c4) * 4 : 0;
-    f32x4v s = {0.f, 0.f, 0.f, 0.f};
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
     if (ok) {
         const float* p = ws + (long)r * ldw + c;
         int i = g;
         for (; i + 12 < splits; i += 16) {
-            f32x4v v[4];
+            f32x4 v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4v*>(p + (long)(i + 4 * u) * split_stride);
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(p + (long)(i + 4 * u) * split_stride);
 #pragma unroll
             for (int u = 0; u < 4; ++u) s += v[u];
         }
-        for (; i < splits; i += 4) s += *reinterpret_cast<const f32x4v*>(p + (long)i * split_stride);
+        for (; i < splits; i += 4) s += *reinterpret_cast<const f32x4*>(p + (long)i * split_stride);
     }
     red4[g][lane] = s;
     __syncthreads();
     if (g == 0 && ok) {
-        const f32x4v t = (red4[0][lane] + red4[1][lane]) + (red4[2][lane] + red4[3][lane]);
+        const f32x4 t = (red4[0][lane] + red4[1][lane]) + (red4[2][lane] + red4[3][lane]);
         if (c == cols) {                                   // the extra column (only with `extra`)
             extra[r] = accumulate ? extra[r] + t[0] : t[0];
         } else {
-            f32x4v* o = reinterpret_cast<f32x4v*>(out + (long)r * ldo + c);
+            f32x4* o = reinterpret_cast<f32x4*>(out + (long)r * ldo + c);
             *o = accumulate ? *o + t : t;
         }
     }
@@ -115,32 +108,32 @@ __global__ __launch_bounds__(256) void reduce_partials_vec4_kernel(const float* 
 // sums meet in LDS in a fixed order.  E % 4 == 0.
 __global__ __launch_bounds__(256) void reduce_ln3_kernel(const float* __restrict__ ws, int nblk, int E, float* __restrict__ o0,
                                                           float* __restrict__ o1, float* __restrict__ o2, int accumulate) {
-    __shared__ f32x4v red[16][16];
+    __shared__ f32x4 red[16][16];
     const int cg = threadIdx.x & 15, sl = threadIdx.x >> 4;
     const int g = blockIdx.x * 16 + cg, ng = 3 * E / 4;
-    f32x4v s = {0.f, 0.f, 0.f, 0.f};
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
     if (g < ng) {
         const float* p = ws + 4L * g;
         int i = sl;
         for (; i + 48 < nblk; i += 64) {
-            f32x4v v[4];
+            f32x4 v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4v*>(p + (long)(i + 16 * u) * 3 * E);
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(p + (long)(i + 16 * u) * 3 * E);
 #pragma unroll
             for (int u = 0; u < 4; ++u) s += v[u];
         }
-        for (; i < nblk; i += 16) s += *reinterpret_cast<const f32x4v*>(p + (long)i * 3 * E);
+        for (; i < nblk; i += 16) s += *reinterpret_cast<const f32x4*>(p + (long)i * 3 * E);
     }
     red[sl][cg] = s;
     __syncthreads();
     if (sl == 0 && g < ng) {
-        f32x4v t = red[0][cg];
+        f32x4 t = red[0][cg];
 #pragma unroll
         for (int u = 1; u < 16; ++u) t += red[u][cg];
         const int c = 4 * g, k = c / E, cc = c - k * E;          // E % 4 == 0: a group never leaves its vector
         float* const o = k == 0 ? o0 : (k == 1 ? o1 : o2);
         if (o) {
-            f32x4v* q = reinterpret_cast<f32x4v*>(o + cc);
+            f32x4* q = reinterpret_cast<f32x4*>(o + cc);
             *q = accumulate ? *q + t : t;
         }
     }
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const float* __restri
 
     // Loads are branch-free buffer loads: rows beyond the slice and columns beyond N / K carry the OOB offset and read zeros.
     // Offsets are relative to the first row of the slice (the host checks that a slice spans < 2 GB).
-    f32x4v ra[A4], rb[B4];
+    f32x4 ra[A4], rb[B4];
     const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(dy + m_begin * ldy + n0);
     const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(x + m_begin * ldx + k0);
     const int rows_here = (int)(m_end - m_begin);
@@ -243,12 +236,12 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const float* __restri
 #pragma unroll
         for (int j = 0; j < A4; ++j) {
             const int f = tid + WG_THREADS * j, r = f / (WG_TN / 4), c = (f % (WG_TN / 4)) * 4;
-            *reinterpret_cast<f32x4v*>(&As[r * LDA + c]) = ra[j];
+            *reinterpret_cast<f32x4*>(&As[r * LDA + c]) = ra[j];
         }
 #pragma unroll
         for (int j = 0; j < B4; ++j) {
             const int f = tid + WG_THREADS * j, r = f / (TK / 4), c = (f % (TK / 4)) * 4;
-            if (f < WG_MC * TK / 4) *reinterpret_cast<f32x4v*>(&Bs[r * LDB + c]) = rb[j];
+            if (f < WG_MC * TK / 4) *reinterpret_cast<f32x4*>(&Bs[r * LDB + c]) = rb[j];
         }
     };
 
@@ -292,13 +285,6 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const float* __restri
 // directly (raw_ptr_buffer_load_lds, 1 KB per wave instruction, rows packed without padding), two stages, ONE barrier per
 // chunk: chunk c + 1 is in flight while chunk c is multiplied; no staging registers, no LDS stores.
 // ---------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, float* lds_base, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)          // (inside a kernel template the builtin makes the host pass drop the launch stub)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
-
 constexpr int WD_MC = 32;          // rows per chunk: two stages of 32 rows = 112 KB at TK = 320 (16-row chunks with two workgroups
                                    // per CU measured the same kernel time and double the partial tiles to sum)
 
@@ -493,7 +479,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
                                                                                           // for the column sums: occupancy)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane & 15, rg = lane >> 4;
-    const f32x4v zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (int c = threadIdx.x; c < 64 * V4; c += 256) {
         const float g = c < E ? gamma[c] : 0.f;
         Gs[c] = g;
@@ -501,7 +487,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
         IGs[c] = c < E ? 1.0f / g : 0.f;
     }
     __syncthreads();
-    f32x4v sg[V4], sb[V4], sz[V4];
+    f32x4 sg[V4], sb[V4], sz[V4];
 #pragma unroll
     for (int j = 0; j < V4; ++j) sg[j] = sb[j] = sz[j] = zero;
     const float inv_e = 1.0f / (float)E;
@@ -510,7 +496,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
         const bool rin = r < M;
         const float* pdy = dy + ((rin ? r : 0) / dy_div) * lddy;
         const float* py = y + (rin ? r : 0) * ldy;
-        f32x4v d[V4], xh[V4];
+        f32x4 d[V4], xh[V4];
         float s1 = 0.f, s2 = 0.f;
         // the three vectors are re-read from LDS for every row: hidden from the optimiser, which would otherwise hoist the
         // loop-invariant loads back into 60 registers
@@ -520,11 +506,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
         for (int j = 0; j < V4; ++j) {
             const int c = 4 * (sub + 16 * j);
             const bool ok = rin && c < E;
-            const f32x4v ga = *reinterpret_cast<const f32x4v*>(&gs[c]), be = *reinterpret_cast<const f32x4v*>(&bs[c]);
-            d[j] = ok ? *reinterpret_cast<const f32x4v*>(pdy + c) * dy_scale : zero;
-            const f32x4v yv = ok ? *reinterpret_cast<const f32x4v*>(py + c) : be;
-            xh[j] = (yv - be) * *reinterpret_cast<const f32x4v*>(&igs[c]);
-            const f32x4v g = d[j] * ga;
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(&gs[c]), be = *reinterpret_cast<const f32x4*>(&bs[c]);
+            d[j] = ok ? *reinterpret_cast<const f32x4*>(pdy + c) * dy_scale : zero;
+            const f32x4 yv = ok ? *reinterpret_cast<const f32x4*>(py + c) : be;
+            xh[j] = (yv - be) * *reinterpret_cast<const f32x4*>(&igs[c]);
+            const f32x4 g = d[j] * ga;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { s1 += g[e]; s2 += g[e] * xh[j][e]; }
         }
@@ -538,15 +524,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
         for (int j = 0; j < V4; ++j) {
             const int c = 4 * (sub + 16 * j);
             const bool ok = rin && c < E;
-            f32x4v v = (d[j] * *reinterpret_cast<const f32x4v*>(&gs[c]) - s1 - xh[j] * s2) * rs;
+            f32x4 v = (d[j] * *reinterpret_cast<const f32x4*>(&gs[c]) - s1 - xh[j] * s2) * rs;
             if (!ok) v = zero;
-            if (ok) *reinterpret_cast<f32x4v*>(dz + r * lddz + c) = v;
-            f32x4v t = v;
+            if (ok) *reinterpret_cast<f32x4*>(dz + r * lddz + c) = v;
+            f32x4 t = v;
             if (dz_drop != nullptr && ok) {            // the gradient through the dropout in front of the residual add, written alongside
                 const unsigned keep = lime_keep4(drop, ((uint64_t)r * (uint64_t)E + (uint64_t)c) >> 2);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[e] = (keep >> e) & 1u ? v[e] * drop.scale : 0.f;
-                *reinterpret_cast<f32x4v*>(dz_drop + r * lddd + c) = t;
+                *reinterpret_cast<f32x4*>(dz_drop + r * lddd + c) = t;
             }
             sg[j] += d[j] * xh[j];
             sb[j] += d[j];
@@ -630,9 +616,9 @@ __global__ __launch_bounds__(512) void token_attn_bwd_kernel(const float* __rest
     float* Os = Vs + SP * AB_LD;                // dO
     float* Ps = Os + SP * AB_LD;                // P, then dS
     const int R0 = 16 * wr;
-    const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 
-    f32x4v rq[NV4], rk[NV4], rv[NV4];
+    f32x4 rq[NV4], rk[NV4], rv[NV4];
     f32x2 ro[NV2];
     auto fetch = [&](long prob) {               // rows of problem `prob` -> registers (vec layout only)
         const bool live = prob < n_prob;
@@ -643,9 +629,9 @@ __global__ __launch_bounds__(512) void token_attn_bwd_kernel(const float* __rest
             const int e = lt + TPP * u, r = e >> 3, c = (e & 7) * 4;
             const bool ok = live && r < S && !(LIME_ATTN_BWD_ABLATE & 1);
             const long g = (row_base + (ok ? r : 0)) * ld + (long)head * head_stride + c;
-            rq[u] = ok ? *reinterpret_cast<const f32x4v*>(q + g) : z4;
-            rk[u] = ok ? *reinterpret_cast<const f32x4v*>(k + g) : z4;
-            rv[u] = ok ? *reinterpret_cast<const f32x4v*>(v + g) : z4;
+            rq[u] = ok ? *reinterpret_cast<const f32x4*>(q + g) : z4;
+            rk[u] = ok ? *reinterpret_cast<const f32x4*>(k + g) : z4;
+            rv[u] = ok ? *reinterpret_cast<const f32x4*>(v + g) : z4;
         }
 #pragma unroll
         for (int u = 0; u < NV2; ++u) {
@@ -660,9 +646,9 @@ __global__ __launch_bounds__(512) void token_attn_bwd_kernel(const float* __rest
 #pragma unroll
         for (int u = 0; u < NV4; ++u) {
             const int e = lt + TPP * u, r = e >> 3, c = (e & 7) * 4;
-            *reinterpret_cast<f32x4v*>(&Qs[r * AB_LD + c]) = rq[u];
-            *reinterpret_cast<f32x4v*>(&Ks[r * AB_LD + c]) = rk[u];
-            *reinterpret_cast<f32x4v*>(&Vs[r * AB_LD + c]) = rv[u];
+            *reinterpret_cast<f32x4*>(&Qs[r * AB_LD + c]) = rq[u];
+            *reinterpret_cast<f32x4*>(&Ks[r * AB_LD + c]) = rk[u];
+            *reinterpret_cast<f32x4*>(&Vs[r * AB_LD + c]) = rv[u];
         }
 #pragma unroll
         for (int u = 0; u < NV2; ++u) {
@@ -700,15 +686,15 @@ __global__ __launch_bounds__(512) void token_attn_bwd_kernel(const float* __rest
         {
             // the summation index d is only a label: lane group kg takes d = 8 kg .. 8 kg + 7 over the eight MFMA steps, so a
             // lane's eight operands are 32 consecutive bytes of its row -- two ds_read_b128 instead of eight ds_read_b32
-            f32x4v qa[2], oa[2];
+            f32x4 qa[2], oa[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                qa[h] = *reinterpret_cast<const f32x4v*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
-                oa[h] = *reinterpret_cast<const f32x4v*>(&Os[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
+                qa[h] = *reinterpret_cast<const f32x4*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
+                oa[h] = *reinterpret_cast<const f32x4*>(&Os[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
             }
             // two score tiles at a time (four independent accumulator chains), the next pair's K / V fragments are requested
             // before this pair's MFMAs are issued
-            f32x4v kb[2][2][2], vb[2][2][2];               // [buffer][tile of the pair][half]
+            f32x4 kb[2][2][2], vb[2][2][2];               // [buffer][tile of the pair][half]
             auto load_pair = [&](int buf, int ct) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
@@ -719,8 +705,8 @@ __global__ __launch_bounds__(512) void token_attn_bwd_kernel(const float* __rest
                             vb[buf][t][h] = oa[h] + (float)ct;
                             continue;
                         }
-                        kb[buf][t][h] = *reinterpret_cast<const f32x4v*>(&Ks[(16 * (ct + t) + fi) * AB_LD + 8 * kg + 4 * h]);
-                        vb[buf][t][h] = *reinterpret_cast<const f32x4v*>(&Vs[(16 * (ct + t) + fi) * AB_LD + 8 * kg + 4 * h]);
+                        kb[buf][t][h] = *reinterpret_cast<const f32x4*>(&Ks[(16 * (ct + t) + fi) * AB_LD + 8 * kg + 4 * h]);
+                        vb[buf][t][h] = *reinterpret_cast<const f32x4*>(&Vs[(16 * (ct + t) + fi) * AB_LD + 8 * kg + 4 * h]);
                     }
             };
             load_pair(0, 0);
@@ -869,14 +855,14 @@ __global__ __launch_bounds__(512, 2) void token_attn_fwd_dropout_kernel(const fl
     const int R0 = 16 * wr;
     const long row_base = (long)seq * S;
     // B operand of S^T = K Q^T: Q[i = R0 + fi][d = 8 kg .. 8 kg + 7] (k-permuted: 32 consecutive bytes of the lane's row)
-    f32x4v qf[2];
+    f32x4 qf[2];
     {
         const bool ok = live && R0 + fi < S;
         const float* qrow = q + (row_base + (ok ? R0 + fi : 0)) * ld + (long)head * head_stride + 8 * kg;
         if (vec) {
-            const f32x4v z = {0.f, 0.f, 0.f, 0.f};
-            qf[0] = ok ? *reinterpret_cast<const f32x4v*>(qrow) : z;
-            qf[1] = ok ? *reinterpret_cast<const f32x4v*>(qrow + 4) : z;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            qf[0] = ok ? *reinterpret_cast<const f32x4*>(qrow) : z;
+            qf[1] = ok ? *reinterpret_cast<const f32x4*>(qrow + 4) : z;
         } else {
 #pragma unroll
             for (int t = 0; t < 8; ++t) qf[t >> 2][t & 3] = (ok && 8 * kg + t < head_dim) ? qrow[t] : 0.f;
@@ -887,9 +873,9 @@ __global__ __launch_bounds__(512, 2) void token_attn_fwd_dropout_kernel(const fl
             const int r = e >> 3, c = (e & 7) * 4;
             const bool ok = live && r < S;
             const long g = (row_base + (ok ? r : 0)) * ld + (long)head * head_stride + c;
-            const f32x4v z = {0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4v*>(&Ks[r * AB_LD + c]) = ok ? *reinterpret_cast<const f32x4v*>(k + g) : z;
-            *reinterpret_cast<f32x4v*>(&Vs[r * AB_LD + c]) = ok ? *reinterpret_cast<const f32x4v*>(v + g) : z;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(&Ks[r * AB_LD + c]) = ok ? *reinterpret_cast<const f32x4*>(k + g) : z;
+            *reinterpret_cast<f32x4*>(&Vs[r * AB_LD + c]) = ok ? *reinterpret_cast<const f32x4*>(v + g) : z;
         }
     } else {
         for (int e = lt; e < SP * 32; e += TPP) {
@@ -907,9 +893,9 @@ __global__ __launch_bounds__(512, 2) void token_attn_fwd_dropout_kernel(const fl
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
             f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            f32x4v kf[2];                       // A operand: K[j = 16 ct + fi][d = 8 kg ..]
+            f32x4 kf[2];                       // A operand: K[j = 16 ct + fi][d = 8 kg ..]
 #pragma unroll
-            for (int h = 0; h < 2; ++h) kf[h] = *reinterpret_cast<const f32x4v*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
+            for (int h = 0; h < 2; ++h) kf[h] = *reinterpret_cast<const f32x4*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
 #pragma unroll
             for (int t = 0; t < 8; ++t) a = mfma16(kf[t >> 2][t & 3], qf[t >> 2][t & 3], a);
             p[ct] = a;
@@ -1025,9 +1011,9 @@ __global__ __launch_bounds__(512) void attn_stats_kernel(const float* __restrict
     stage_rows(Qs, q, ld, row_base + q0, q_valid, head * head_stride, head_dim, tid);
     __syncthreads();
     const int R0 = 16 * wave;
-    f32x4v qa[2];
+    f32x4 qa[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) qa[h] = *reinterpret_cast<const f32x4v*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
+    for (int h = 0; h < 2; ++h) qa[h] = *reinterpret_cast<const f32x4*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
     lime_dev::SplitFrag qs;
     if constexpr (SPX) {
         const float x[8] = {qa[0][0], qa[0][1], qa[0][2], qa[0][3], qa[1][0], qa[1][1], qa[1][2], qa[1][3]};
@@ -1049,9 +1035,9 @@ __global__ __launch_bounds__(512) void attn_stats_kernel(const float* __restrict
             if constexpr (SPX) {
                 a = lime_dev::split_mfma16(qs, lime_dev::split_load(Kt, LB * lime_dev::SPLIT_PITCH, 16 * ct + fi, kg), a);
             } else {
-                f32x4v kf[2];
+                f32x4 kf[2];
 #pragma unroll
-                for (int h = 0; h < 2; ++h) kf[h] = *reinterpret_cast<const f32x4v*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
+                for (int h = 0; h < 2; ++h) kf[h] = *reinterpret_cast<const f32x4*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) a = mfma16(qa[t >> 2][t & 3], kf[t >> 2][t & 3], a);
             }
@@ -1113,9 +1099,9 @@ __global__ __launch_bounds__(512) void attn_fwd_long_dropout_kernel(const float*
     const int R0 = 16 * wave;
     stage_rows(Qs, q, ld, row_base + q0, q_valid, head * head_stride, head_dim, tid);
     __syncthreads();
-    f32x4v qa[2];
+    f32x4 qa[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) qa[h] = *reinterpret_cast<const f32x4v*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
+    for (int h = 0; h < 2; ++h) qa[h] = *reinterpret_cast<const f32x4*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
     float lse[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1132,9 +1118,9 @@ __global__ __launch_bounds__(512) void attn_fwd_long_dropout_kernel(const float*
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
             f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            f32x4v kf[2];
+            f32x4 kf[2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) kf[h] = *reinterpret_cast<const f32x4v*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
+            for (int h = 0; h < 2; ++h) kf[h] = *reinterpret_cast<const f32x4*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
 #pragma unroll
             for (int t = 0; t < 8; ++t) a = mfma16(qa[t >> 2][t & 3], kf[t >> 2][t & 3], a);
 #pragma unroll
@@ -1204,20 +1190,20 @@ __global__ __launch_bounds__(512) void attn_bwd_long_kernel(const float* __restr
         __syncthreads();
         f32x4 p[NT], dp[NT];
         {
-            f32x4v qa[2], oa[2];
+            f32x4 qa[2], oa[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                qa[h] = *reinterpret_cast<const f32x4v*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
-                oa[h] = *reinterpret_cast<const f32x4v*>(&Os[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
+                qa[h] = *reinterpret_cast<const f32x4*>(&Qs[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
+                oa[h] = *reinterpret_cast<const f32x4*>(&Os[(R0 + fi) * AB_LD + 8 * kg + 4 * h]);
             }
 #pragma unroll
             for (int ct = 0; ct < NT; ++ct) {
                 f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, d0 = s0;
-                f32x4v kf[2], vf[2];
+                f32x4 kf[2], vf[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    kf[h] = *reinterpret_cast<const f32x4v*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
-                    vf[h] = *reinterpret_cast<const f32x4v*>(&Vs[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
+                    kf[h] = *reinterpret_cast<const f32x4*>(&Ks[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
+                    vf[h] = *reinterpret_cast<const f32x4*>(&Vs[(16 * ct + fi) * AB_LD + 8 * kg + 4 * h]);
                 }
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
@@ -1320,7 +1306,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_long_sp_kernel(const float* _
                                                                    float* __restrict__ dk, float* __restrict__ dv, long ldd, int S,
                                                                    int n_head, int head_dim, int head_stride, float scale, int n_blk,
                                                                    LimeDropout drop, float* __restrict__ dq_slabs, long n_tok) {
-    using namespace lime_dev;
     constexpr int KT = LB * SWZ_ROW, QT = LQ * SWZ_ROW;
     static_assert(LQ == SWZ_ROW, "the dS image has one row per key and LQ queries per row");
     extern __shared__ float smem[];
@@ -1941,17 +1926,14 @@ int launch_attn_bwd(const float* q, const float* k, const float* v, long ld, con
     constexpr int PPW = 8 / (SP / 16);
     constexpr int BYTES = PPW * (4 * SP * AB_LD + SP * (SP + 2)) * 4;
     static bool configured = false;
-    static int n_cu = 256;
     if (!configured) {
         const hipError_t e = hipFuncSetAttribute((const void*)token_attn_bwd_kernel<SP>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
         LIME_REQUIRE(e == hipSuccess, LIME_ERR_LAUNCH, "lime_token_attention_bwd_f32: cannot reserve %d bytes of LDS: %s", BYTES,
                      hipGetErrorString(e));
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            n_cu = cus;
         configured = true;
     }
     const long n_group = ((long)n_seq * n_head + PPW - 1) / PPW;
+    const int n_cu = lime_num_cus();
     const int grid = (int)(n_group < n_cu ? n_group : n_cu);             // persistent: one workgroup per CU
     // vector staging: 32-float head rows on 16-byte boundaries with zero padding columns, dO pairs on 8-byte boundaries
     const bool vec = head_stride == 32 && ld % 4 == 0 && ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0 &&

@@ -1,4 +1,4 @@
-// Error reporting and ABI version of liblime_hip.so.
+// Error reporting, the cached CU count and the ABI version of liblime_hip.so.
 #include "common.h"
 
 static thread_local char g_err[512] = "";
@@ -17,6 +17,16 @@ void lime_set_last_linear_kernel(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_kernel, sizeof(g_kernel), fmt, ap);
     va_end(ap);
+}
+
+int lime_num_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, cus = 0;
+        const bool ok = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
+        n = (ok && cus > 0) ? cus : 256;
+    }
+    return n;
 }
 
 extern "C" const char* lime_last_linear_kernel(void) { return g_kernel; }

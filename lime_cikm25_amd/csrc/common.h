@@ -22,6 +22,12 @@ void lime_set_last_linear_kernel(const char* fmt, ...);      // lime_last_linear
         }                                        \
     } while (0)
 
+// compute units of the current device: queried once, 256 when there is no device to ask (common.cpp)
+int lime_num_cus();
+
+// 16-byte vector access to rows of `ld` floats from `ptr` is possible (a NULL operand is absent, hence fine)
+static inline bool lime_al16(const void* ptr, long ld) { return ptr == nullptr || (((uintptr_t)ptr % 16) == 0 && (ld % 4) == 0); }
+
 // called right after a kernel launch; never synchronises
 static inline int lime_check_launch(const char* what) {
     hipError_t e = hipGetLastError();

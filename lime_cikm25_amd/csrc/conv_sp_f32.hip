@@ -27,7 +27,7 @@
 // (eight consecutive rows of one column) is one 32-byte read; the slices' partial tiles go to a workspace and are summed in slice
 // order by conv_wgrad_reduce_kernel -- no atomics, the same bits on every run.
 #include "common.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 
 using namespace lime_dev;
@@ -353,8 +353,6 @@ WgradPlan wgrad_plan(int M, int N, int C, int win) {
     return w;
 }
 
-inline bool al16(const void* ptr) { return ((uintptr_t)ptr % 16) == 0; }
-
 }  // namespace
 
 extern "C" int lime_conv1d_window_f32(const float* a, int64_t lda, const int32_t* ids, const float* w, int64_t ldw, const float* bias,
@@ -366,7 +364,7 @@ extern "C" int lime_conv1d_window_f32(const float* a, int64_t lda, const int32_t
     LIME_REQUIRE(M % T == 0, LIME_ERR_BAD_ARG, "lime_conv1d_window_f32: M = %d is not a whole number of sequences of T = %d", M, T);
     LIME_REQUIRE(lda >= C && ldw >= (int64_t)window * C && ldc >= N, LIME_ERR_BAD_ARG,
                  "lime_conv1d_window_f32: leading dimension smaller than the row");
-    LIME_REQUIRE(C % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && al16(a) && al16(w), LIME_ERR_UNSUPPORTED,
+    LIME_REQUIRE(C % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lime_al16(a, 0) && lime_al16(w, 0), LIME_ERR_UNSUPPORTED,
                  "lime_conv1d_window_f32: C, lda, ldw must be multiples of 4 and a, w 16-byte aligned");
     LIME_REQUIRE(act == LIME_ACT_NONE || act == LIME_ACT_RELU, LIME_ERR_UNSUPPORTED, "lime_conv1d_window_f32: act %d (none / relu only)", act);
     LIME_REQUIRE((long)M * lda < 0x7FFFFFFFL * 4L, LIME_ERR_UNSUPPORTED, "lime_conv1d_window_f32: operand too large");
@@ -374,7 +372,7 @@ extern "C" int lime_conv1d_window_f32(const float* a, int64_t lda, const int32_t
     p.a = a; p.lda = lda; p.ids = ids; p.w = w; p.ldw = ldw; p.bias = bias; p.c = out; p.ldc = ldc; p.m_dev = m_dev;
     p.M = M; p.N = N; p.C = C; p.T = T; p.win = window; p.pad = (window - 1) / 2;
     p.relu = act == LIME_ACT_RELU; p.accumulate = accumulate != 0;
-    p.vec_out = (N % 4 == 0 && ldc % 4 == 0 && al16(out)) ? 1 : 0;
+    p.vec_out = (N % 4 == 0 && ldc % 4 == 0 && lime_al16(out, 0)) ? 1 : 0;
     p.n_col_blocks = (N + BN - 1) / BN;
     const long grid = (long)((M + BM - 1) / BM) * p.n_col_blocks;
     LIME_REQUIRE(grid < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_conv1d_window_f32: grid too large");
@@ -399,7 +397,7 @@ extern "C" int lime_conv1d_wgrad_f32(const float* dy, int64_t ldy, const float* 
     LIME_REQUIRE(M % T == 0, LIME_ERR_BAD_ARG, "lime_conv1d_wgrad_f32: M = %d is not a whole number of sequences of T = %d", M, T);
     LIME_REQUIRE(ldy >= N && lda >= C && lddw >= (int64_t)window * C, LIME_ERR_BAD_ARG,
                  "lime_conv1d_wgrad_f32: leading dimension smaller than the row");
-    LIME_REQUIRE(N % 4 == 0 && C % 4 == 0 && ldy % 4 == 0 && lda % 4 == 0 && al16(dy) && al16(a) && al16(workspace), LIME_ERR_UNSUPPORTED,
+    LIME_REQUIRE(N % 4 == 0 && C % 4 == 0 && ldy % 4 == 0 && lda % 4 == 0 && lime_al16(dy, 0) && lime_al16(a, 0) && lime_al16(workspace, 0), LIME_ERR_UNSUPPORTED,
                  "lime_conv1d_wgrad_f32: N, C, ldy, lda must be multiples of 4 and dy, a, workspace 16-byte aligned");
     const WgradPlan w = wgrad_plan(M, N, C, window);
     const long slice = (long)N * window * C;

@@ -22,34 +22,32 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 // cols % 4 == 0 and 16-byte aligned rows: four elements per thread, one hash
 __global__ __launch_bounds__(256) void dropout_vec4_kernel(const float* __restrict__ src, long lds, float* __restrict__ dst, long ldd,
                                                             long rows, int cols, LimeDropout d) {
-    typedef float v4 __attribute__((ext_vector_type(4)));
     const int c4n = cols >> 2;
     const long total = rows * c4n;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long)gridDim.x * 256) {
         const long r = q / c4n;
         const int c = (int)(q - r * c4n) * 4;
         const unsigned m = lime_keep4(d, (uint64_t)q);             // elements 4 q .. 4 q + 3 = (r, c .. c + 3)
-        v4 v = *reinterpret_cast<const v4*>(src + r * lds + c);
+        f32x4 v = *reinterpret_cast<const f32x4*>(src + r * lds + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (m >> e) & 1u ? v[e] * d.scale : 0.f;
-        *reinterpret_cast<v4*>(dst + r * ldd + c) = v;
+        *reinterpret_cast<f32x4*>(dst + r * ldd + c) = v;
     }
 }
 
 // two dropout sites over the same tensor in one pass (the backward through the positional and the embedding dropout of the layer input)
 __global__ __launch_bounds__(256) void dropout2_vec4_kernel(const float* __restrict__ src, long lds, float* __restrict__ dst, long ldd,
                                                              long rows, int cols, LimeDropout d1, LimeDropout d2) {
-    typedef float v4 __attribute__((ext_vector_type(4)));
     const int c4n = cols >> 2;
     const long total = rows * c4n;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long)gridDim.x * 256) {
         const long r = q / c4n;
         const int c = (int)(q - r * c4n) * 4;
         const unsigned m = lime_keep4(d1, (uint64_t)q) & lime_keep4(d2, (uint64_t)q);
-        v4 v = *reinterpret_cast<const v4*>(src + r * lds + c);
+        f32x4 v = *reinterpret_cast<const f32x4*>(src + r * lds + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (m >> e) & 1u ? (v[e] * d1.scale) * d2.scale : 0.f;     // the same two roundings as two passes
-        *reinterpret_cast<v4*>(dst + r * ldd + c) = v;
+        *reinterpret_cast<f32x4*>(dst + r * ldd + c) = v;
     }
 }
 
@@ -117,24 +115,23 @@ __global__ __launch_bounds__(256) void dropout_add_ln_vec_kernel(const float* __
                                                                   long ldr, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                   float eps, float* __restrict__ y, long ldy, float* __restrict__ rstd,
                                                                   long M, int E, LimeDropout d) {
-    typedef float v4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane & 15, rg = lane >> 4;
-    const v4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const float inv_e = 1.0f / (float)E;
     const int e4 = E >> 2;
     for (long r4 = ((long)blockIdx.x * 4 + wave) * 4; r4 < M; r4 += (long)gridDim.x * 16) {
         const long r = r4 + rg;
         const bool rin = r < M;
-        v4 v[V4];
+        f32x4 v[V4];
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < V4; ++j) {
             const int c4 = sub + 16 * j;
-            v4 x = zero;
+            f32x4 x = zero;
             if (rin && c4 < e4) {
-                const v4 tv = *reinterpret_cast<const v4*>(t + r * ldt + 4 * c4);
-                x = *reinterpret_cast<const v4*>(res + r * ldr + 4 * c4);
+                const f32x4 tv = *reinterpret_cast<const f32x4*>(t + r * ldt + 4 * c4);
+                x = *reinterpret_cast<const f32x4*>(res + r * ldr + 4 * c4);
                 const unsigned m = lime_keep4(d, (uint64_t)(r * e4 + c4));
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x[e] += (m >> e) & 1u ? tv[e] * d.scale : 0.f;
@@ -160,8 +157,8 @@ __global__ __launch_bounds__(256) void dropout_add_ln_vec_kernel(const float* __
         for (int j = 0; j < V4; ++j) {
             const int c4 = sub + 16 * j;
             if (rin && c4 < e4) {
-                const v4 ga = *reinterpret_cast<const v4*>(gamma + 4 * c4), be = *reinterpret_cast<const v4*>(beta + 4 * c4);
-                *reinterpret_cast<v4*>(y + r * ldy + 4 * c4) = v[j] * rs * ga + be;
+                const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + 4 * c4), be = *reinterpret_cast<const f32x4*>(beta + 4 * c4);
+                *reinterpret_cast<f32x4*>(y + r * ldy + 4 * c4) = v[j] * rs * ga + be;
             }
         }
     }
@@ -171,23 +168,22 @@ __global__ __launch_bounds__(256) void embed_pe_dropout_vec4_kernel(const int* _
                                                                      long ld_table, const float* __restrict__ pe, long ld_pe, int period,
                                                                      float* __restrict__ out, long ldo, long rows, int dim,
                                                                      LimeDropout d_emb, LimeDropout d_pe) {
-    typedef float v4 __attribute__((ext_vector_type(4)));
     const int c4n = dim >> 2;
     const long total = rows * c4n;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long)gridDim.x * 256) {
         const long r = q / c4n;
         const int c = (int)(q - r * c4n) * 4;
-        v4 v = *reinterpret_cast<const v4*>(table + (long)ids[r] * ld_table + c);
+        f32x4 v = *reinterpret_cast<const f32x4*>(table + (long)ids[r] * ld_table + c);
         const unsigned m1 = lime_keep4(d_emb, (uint64_t)q), m2 = lime_keep4(d_pe, (uint64_t)q);
-        v4 p = {0.f, 0.f, 0.f, 0.f};
-        if (pe) p = *reinterpret_cast<const v4*>(pe + (r % period) * ld_pe + c);
+        f32x4 p = {0.f, 0.f, 0.f, 0.f};
+        if (pe) p = *reinterpret_cast<const f32x4*>(pe + (r % period) * ld_pe + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float x = (m1 >> e) & 1u ? v[e] * d_emb.scale : 0.f;
             x += p[e];
             v[e] = (m2 >> e) & 1u ? x * d_pe.scale : 0.f;
         }
-        *reinterpret_cast<v4*>(out + r * ldo + c) = v;
+        *reinterpret_cast<f32x4*>(out + r * ldo + c) = v;
     }
 }
 

@@ -27,7 +27,7 @@
 // the feed-forward half's input and residual, which therefore never exists in HBM.
 #include <type_traits>
 
-#include "lds_dma.h"
+#include "dev_helpers.h"
 
 using namespace lime_dev;
 
@@ -35,17 +35,6 @@ using namespace lime_dev;
 // Diagnostic build only (tools/ffn_stamps.py): per-wave s_memtime sums of the step segments; never in liblime_hip.so.
 static unsigned long long* g_ffn_stamp_buf = nullptr;
 extern "C" void lime_debug_set_ffn_stamp_buffer(unsigned long long* p) { g_ffn_stamp_buf = p; }
-#define FSTAMP(i)                                                           \
-    {                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                 \
-        tsum[i] += t_ - tlast;                                              \
-        tlast = t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-    }
-#else
-#define FSTAMP(i)
 #endif
 
 namespace {
@@ -78,14 +67,6 @@ struct FfnP {
     unsigned long long* stamps;
 #endif
 };
-
-// The lane id, recomputed where it is called (the opaque zero keeps hipcc from hoisting it -- and everything derived from it -- out
-// of the tile loop, where the values would sit in registers through all 36 steps or be spilled: scratch reloads wait vmcnt(0)).
-__device__ __forceinline__ int lane_here() {
-    int z = 0;
-    asm volatile("" : "+v"(z));
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
 
 constexpr int step_dmas(int pos) { return pos < 5 ? 4 : 5; }                       // DMA instructions per wave that fill the slot of step `pos`
 // A tile's steps by "tile position": 0..9 the out_proj chunks (OPROJ instantiations only), 10 + pos the feed-forward steps of a pass
@@ -363,9 +344,9 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
             // next tile's first steps may be either, the smaller count: waiting for one instruction more is always safe)
             wait_vm<K0 ? (TP + 2 < TP_FFN ? 5 : 4) + (TP >= 2 ? 2 : 0) : step_dmas((POS + 2) % STEPS)>();   // K0: + the previous step's residual chunk
         }
-        FSTAMP(0)                                      // 0: this wave's DMAs of the next step have landed
+        LIME_STAMP(0)                                      // 0: this wave's DMAs of the next step have landed
         ring_barrier();
-        FSTAMP(1)                                      // 1: barrier
+        LIME_STAMP(1)                                      // 1: barrier
         // the step three ahead, whose slot has just come free: inside this tile, or the next tile's first steps
         constexpr int FTP = K0 ? (TP + 3 < TP_FFN ? TP + 3 : TP_FFN + (TP + 3 - TP_FFN)) : TP_FFN + (POS + 3) % STEPS;
         constexpr int WTP = OPROJ ? (POS + 3) % STEPS : FTP;         // ... when it wraps into the next tile
@@ -410,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
             compute2(gs & 3, hb[0][POS - 5], hb[1][POS - 5], part, tail);
         }
         __builtin_amdgcn_sched_barrier(0);
-        FSTAMP(K0 ? 2 : (POS < 5 ? 3 : 4))             // 2 / 3 / 4: fragment reads + MFMAs + DMA issue: out_proj / linear1 / linear2 step
+        LIME_STAMP(K0 ? 2 : (POS < 5 ? 3 : 4))             // 2 / 3 / 4: fragment reads + MFMAs + DMA issue: out_proj / linear1 / linear2 step
         ++gs;
     };
     auto zero_acc2 = [&]() {
@@ -515,7 +496,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
                 }
             }
             zero_acc2();
-            FSTAMP(6)                                  // 6: out_proj epilogue (and ReLU / pack)
+            LIME_STAMP(6)                                  // 6: out_proj epilogue (and ReLU / pack)
         }
         for (int pass = 0; pass < NP; ++pass) {
 #pragma unroll
@@ -548,7 +529,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
             step(std::integral_constant<int, TP_FFN + 7>{}, pass);
             step(std::integral_constant<int, TP_FFN + 8>{}, pass);
         }
-        FSTAMP(6)                                      // 6: ReLU / pack (and loop overhead)
+        LIME_STAMP(6)                                      // 6: ReLU / pack (and loop overhead)
 
         // + b2 + residual (this wave's rows of the stationary tile; column E is the bias column: not part of it) -- first, so that
         // the NEXT tile can stream into the image while the rest of the epilogue runs (every CU asks HBM for its 80 KB at about
@@ -561,7 +542,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
         const unsigned char* const rbase = lds + (32 * wave + fi_) * 64 + 8 * (kg_ & 1);
         const int rswz = swz4((fi_ >> 2) & 3), rsg = kg_ >> 1;
         const float* const cs_ = cs + 4 * kg_;
-        f32x4 val[2][ND];                              // the accumulators leave the AccVGPRs here (lds_dma.h, acc_read)
+        f32x4 val[2][ND];                              // the accumulators leave the AccVGPRs here (dev_helpers.h, acc_read)
         mfma_settle();
 #pragma unroll
         for (int t = 0; t < ND; ++t) {
@@ -576,7 +557,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the image has been read ... before the DMAs overwrite those rows
         if (!last) load_x(tile + (int)gridDim.x);
-        FSTAMP(5)                                      // 5: residual added, next tile issued
+        LIME_STAMP(5)                                      // 5: residual added, next tile issued
 #if defined(LIME_FFN_ABLATE) && LIME_FFN_ABLATE == 5       // no LayerNorm / pooling / stores
         if (p.eps != 12345.f) continue;
 #endif
@@ -632,7 +613,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
                 for (int tt = 0; tt < 2; ++tt) buf_store4_bf16((val[tt][t] - mean[tt]) * rstd[tt] * ga + be, rs_c, cof[tt] + (unsigned)t * 32u, 0);
             }
         }
-        FSTAMP(7)                                      // 7: epilogue
+        LIME_STAMP(7)                                      // 7: epilogue
     }
 #ifdef LIME_STAMPS
     if (p.stamps && lane == 0) {
@@ -670,17 +651,6 @@ __global__ void oproj_pack_kernel(const float* __restrict__ w, long ldw, int E, 
     const int kk = (int)(i & 31), n = (int)((i >> 5) % DP), c = (int)(i / (32 * DP));
     const int k = 32 * c + kk;
     wp[i] = (n < E && k < E) ? (uint16_t)(pack_bf16(w[n * ldw + k], 0.f) & 0xFFFFu) : (uint16_t)0;
-}
-
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
 }
 
 }  // namespace
@@ -729,7 +699,7 @@ extern "C" int lime_encoder_ffn_bf16(const lime_ffn_bf16_args* a, void* stream) 
     p.stamps = g_ffn_stamp_buf;
 #endif
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = num_cus();
+    long nwg = lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
     hipStream_t s = (hipStream_t)stream;
     if (a->pool32) hipLaunchKernelGGL((ffn_bf16_kernel<true, false>), dim3((unsigned)nwg), dim3(256), 0, s, p);
@@ -788,7 +758,7 @@ extern "C" int lime_encoder_block_bf16(const lime_encoder_block_bf16_args* a, vo
     p.stamps = g_ffn_stamp_buf;
 #endif
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = num_cus();
+    long nwg = lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
     hipStream_t s = (hipStream_t)stream;
     if (a->pool32) hipLaunchKernelGGL((ffn_bf16_kernel<true, true>), dim3((unsigned)nwg), dim3(256), 0, s, p);

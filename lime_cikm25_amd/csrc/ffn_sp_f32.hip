@@ -20,7 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 
 using namespace lime_dev;
@@ -52,14 +52,6 @@ struct FfnSpP {
     int M, E, F;
     const int* m_dev;
 };
-
-// The lane id, recomputed where it is called (the opaque zero keeps hipcc from hoisting it -- and the offsets derived from it -- out of
-// the tile loop, where they would sit in registers through every step or be spilled; ffn_bf16.hip does the same)
-__device__ __forceinline__ int lane_here() {
-    int z = 0;
-    asm volatile("" : "+v"(z));
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
 
 template <bool POOL>
 __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
@@ -371,17 +363,6 @@ __global__ void ffn_sp_pack_kernel(const float* __restrict__ w1, long ldw1, cons
     }
 }
 
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 }  // namespace
 
 extern "C" int64_t lime_ffn_pack_sp_size(int32_t F, int32_t which) { return which == 0 ? (int64_t)F * (NCH * 32) * 3 : (int64_t)F * DP * 3; }
@@ -421,7 +402,7 @@ extern "C" int lime_encoder_ffn_sp(const lime_ffn_sp_args* a, void* stream) {
     p.b1 = a->b1; p.b2 = a->b2; p.g = a->ln_gamma; p.beta = a->ln_beta; p.eps = a->ln_eps;
     p.out = a->out; p.ldo = a->ldo; p.M = a->M; p.E = a->E; p.F = a->F; p.m_dev = a->m_dev;
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = num_cus();
+    long nwg = lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
     hipStream_t s = (hipStream_t)stream;
     if (a->pool32) hipLaunchKernelGGL((ffn_sp_kernel<true>), dim3((unsigned)nwg), dim3(256), 0, s, p);

@@ -24,8 +24,11 @@
 //   * XCD-aware bijective remap of the workgroup id: an XCD walks whole row panels, so the N-tiles that
 //     re-read one A panel hit the same 4 MiB L2.
 #include "common.h"
+#include "dev_helpers.h"
 #include "gemm_pp.h"
 #include <stdlib.h>
+
+using namespace lime_dev;
 
 #ifdef LIME_STAMPS
 // Diagnostic build only (tools/gemm_stamps.py): per-wave s_memtime sums of the main-loop segments.  The stamp values go to
@@ -33,17 +36,6 @@
 static unsigned long long* g_stamp_buf = nullptr;
 extern "C" void lime_debug_set_stamp_buffer(unsigned long long* p) { g_stamp_buf = p; }
 #define LIME_NSEG 8
-#define STAMP(i)                                                            \
-    {                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                 \
-        tsum[i] += t_ - tlast;                                              \
-        tlast = t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-    }
-#else
-#define STAMP(i)
 #endif
 
 namespace {
@@ -87,13 +79,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // Every global access goes through a buffer descriptor: a wave-uniform base (SGPRs) plus a 32-bit lane offset,
 // so a row costs one VGPR instead of a 64-bit pointer pair, and an out-of-range offset reads as zero / drops
 // the store in hardware -- rows beyond M, columns beyond N and k beyond K need no select and no branch.
-constexpr unsigned OOB = 0x80000000u;          // >= num_records of every descriptor below
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFF0, 0x00020000);
-}
+// (make_rsrc, OOB -- >= num_records of every descriptor below -- and buf_store4: dev_helpers.h)
 template <int VEC>
 __device__ __forceinline__ typename VecT<VEC>::T buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     if constexpr (VEC == 4) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -105,9 +91,6 @@ __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned vo
 }
 __device__ __forceinline__ void buf_store1(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-}
-__device__ __forceinline__ void buf_store4(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
 }
 
 // TM x TN MFMA tiles (32x32) per wave, WM x WN waves per workgroup (4 or 8 waves).
@@ -503,9 +486,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN <= 4) ? 2 : 
     for (int tile = first; tile < ntiles; tile += nwg) {
         const bool more = tile + nwg < ntiles;
         acc_init(tile);
-        STAMP(0)                                      // 0: accumulator init (residual loads issued)
+        LIME_STAMP(0)                                      // 0: accumulator init (residual loads issued)
         for (int t = 0; t + 1 < nchunk; ++t) {
-            STAMP(1)
+            LIME_STAMP(1)
             const float* Ab = &As[buf][a_off];
             const float* Wb = &Ws[buf][w_off];
 #pragma unroll
@@ -515,11 +498,11 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN <= 4) ? 2 : 
                 k8_step(Ab, Wb, s);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            STAMP(2)                                  // 2: prefetch issue + fragment reads + MFMA issue of a full chunk
+            LIME_STAMP(2)                                  // 2: prefetch issue + fragment reads + MFMA issue of a full chunk
             commit(buf ^ 1);
-            STAMP(3)                                  // 3: vmcnt wait + LDS writes
+            LIME_STAMP(3)                                  // 3: vmcnt wait + LDS writes
             lds_barrier();
-            STAMP(4)                                  // 4: barrier
+            LIME_STAMP(4)                                  // 4: barrier
             buf ^= 1;
         }
         // last chunk of the tile: the loader moves on to the next tile first
@@ -535,12 +518,12 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN <= 4) ? 2 : 
             for (int s = 0; s < tail_steps; ++s) k8_step(Ab, Wb, s);
         }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(5)                                      // 5: loader switch + tail chunk
+        LIME_STAMP(5)                                      // 5: loader switch + tail chunk
         epilogue(tile);
-        STAMP(6)                                      // 6: epilogue
+        LIME_STAMP(6)                                      // 6: epilogue
         if (more) commit(buf ^ 1);
         lds_barrier();
-        STAMP(7)                                      // 7: first commit of the next tile + barrier
+        LIME_STAMP(7)                                      // 7: first commit of the next tile + barrier
         buf ^= 1;
     }
 #ifdef LIME_STAMPS
@@ -551,17 +534,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN <= 4) ? 2 : 
 #endif
 }
 
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 template <int TM, int TN, int WM, int WN, int VEC, bool LN, bool PE, int ACT, bool GENERIC, bool VIO>
 int launch_one(const GemmP& p0, int wg_per_cu, hipStream_t stream) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -569,7 +541,7 @@ int launch_one(const GemmP& p0, int wg_per_cu, hipStream_t stream) {
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + BN - 1) / BN;
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = (long)num_cus() * wg_per_cu;
+    long nwg = (long)lime_num_cus() * wg_per_cu;
     if (nwg > ntiles) nwg = ntiles;
 #ifdef LIME_STAMPS
     p.stamps = g_stamp_buf;
@@ -712,9 +684,8 @@ extern "C" int lime_linear_f32(const lime_linear_args* a, void* stream) {
     }
     const bool simple = !has_res && (a->act == LIME_ACT_NONE || a->act == LIME_ACT_RELU);
     if (a->M >= 4096 && simple && vio) {
-        const int pad5 = (a->N + 319) / 320 * 320 - a->N, pad4 = (a->N + 255) / 256 * 256 - a->N;
         const bool relu = a->act == LIME_ACT_RELU, pe = a->a_pe != nullptr;
-        if (pad5 < pad4) {
+        if (lime_pp_wide(a->N, false)) {
             if (pe) return relu ? launch_one<1, 5, 4, 2, 4, false, true, 1, false, true>(p, 1, s) : launch_one<1, 5, 4, 2, 4, false, true, 0, false, true>(p, 1, s);
             return relu ? launch_one<1, 5, 4, 2, 4, false, false, 1, false, true>(p, 1, s) : launch_one<1, 5, 4, 2, 4, false, false, 0, false, true>(p, 1, s);
         }

@@ -14,14 +14,14 @@
 // res_ids[r] (gathered), (r / res_div) % res_mod (periodic table) or r / res_div (dense / broadcast rows).  A rows may be
 // gathered (a_ids).  No LayerNorm / pooling here (those shapes are the big-M kernel's).
 #include "common.h"
+#include "dev_helpers.h"
 #include "gemm_pp.h"
+
+using namespace lime_dev;
 
 namespace {
 
 constexpr int MB = 64, NB = 64, KB = 16, NS = 6;       // MB x NB: the largest tile (LDS is sized for it); KB-deep chunks, NS stages
-constexpr unsigned OOB = 0x80000000u;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct MidP {
     const float* a; long lda; const int* a_ids;
@@ -31,16 +31,6 @@ struct MidP {
     int shape;           // tile shape of this problem: 0 = 64 x 64, 1 = 32 x 64, 2 = 32 x 32 (mid_params)
     const int* m_dev;    // optional device-side row count (min(*m_dev, M) rows; workgroups of tiles beyond it exit)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFF0, 0x00020000);
-}
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, float* lds_base, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
-__device__ __forceinline__ int swz4(int q) { return (0x78 >> (2 * q)) & 3; }        // see gemm_pp_f32.hip
 
 __device__ __forceinline__ float act_fn(float v, int act) {
     if (act == LIME_ACT_RELU) return fmaxf(v, 0.f);
@@ -82,8 +72,8 @@ __device__ __forceinline__ void mid_tile(const MidP& p, const int tile, float* c
     const int lseg = (lane & 3) ^ swz4((lane >> 4) & 3);
     const int lda4 = (int)p.lda * 4, ldw4 = (int)p.ldw * 4;
     const bool gather = p.a_ids != nullptr;
-    const __amdgpu_buffer_rsrc_t rs_a = mk_rsrc(gather ? (const char*)p.a : (const char*)p.a + (long)row0 * p.lda * 4);
-    const __amdgpu_buffer_rsrc_t rs_w = mk_rsrc((const char*)p.w + (long)col0 * p.ldw * 4);
+    const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(gather ? (const char*)p.a : (const char*)p.a + (long)row0 * p.lda * 4);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc((const char*)p.w + (long)col0 * p.ldw * 4);
     unsigned g_voff[DPW];                           // group wave + 4 d: A group (< NA), W group (- NA) or none
     int g_lds[DPW], g_kind[DPW];                    // kind 0: A, 1: W, 2: none (its piece is zeros into a dump area behind the stages)
 #pragma unroll
@@ -210,25 +200,14 @@ __global__ __launch_bounds__(256, 3) void gemm_mid_group_kernel(const MidGroup g
     mid_tile_any(g.p[k], (int)blockIdx.x - g.first[k], lds);
 }
 
-int mid_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) n = cus;
-        else n = 256;
-    }
-    return n;
-}
-
-inline bool al16(const void* ptr, long ld) { return ptr == nullptr || (((uintptr_t)ptr % 16) == 0 && (ld % 4) == 0); }
-
 }  // namespace
 
 // fills p and the tile count; false: the problem is outside this kernel
 static bool mid_params(const lime_linear_args* a, MidP& p, long& ntiles) {
     if (a->ln_gamma || a->pool32 || a->a_pe || a->ln_rstd || a->c_ids || a->res_pe) return false;
+    if (a->dropout_p != 0.f || a->act == LIME_ACT_RELU_GRAD) return false;       // (lime_linear_f32 strips both before it comes here)
     if (a->K % 4 || a->N % 4 || a->K < 16) return false;
-    if (!al16(a->a, a->lda) || !al16(a->w, a->ldw) || !al16(a->c, a->ldc) || !al16(a->res, a->ldr)) return false;
+    if (!lime_al16(a->a, a->lda) || !lime_al16(a->w, a->ldw) || !lime_al16(a->c, a->ldc) || !lime_al16(a->res, a->ldr)) return false;
     const long lim = 0x7FFFFFF0L;
     if (64L * a->lda * 4 >= lim || 64L * a->ldw * 4 >= lim) return false;
     p.a = a->a; p.lda = a->lda; p.a_ids = a->a_ids;
@@ -237,7 +216,7 @@ static bool mid_params(const lime_linear_args* a, MidP& p, long& ntiles) {
     p.res_mod = (a->res && !a->res_ids && a->res_mod > 0) ? a->res_mod : 0;
     p.c = a->c; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.K = a->K; p.act = a->act; p.m_dev = a->m_dev;
     // the smallest tiles whose workgroups still run in ONE round (three workgroups per CU): the launch is then one tile's k loop long
-    static const long slots = 3L * mid_cus();
+    static const long slots = 3L * lime_num_cus();
     const long t64 = (long)((a->M + 63) / 64) * ((a->N + 63) / 64), t3264 = (long)((a->M + 31) / 32) * ((a->N + 63) / 64),
                t32 = (long)((a->M + 31) / 32) * ((a->N + 31) / 32);
     static const char* const force = getenv("LIME_MID_SHAPE");               // A/B switch for tools/, not a product option
@@ -270,13 +249,13 @@ extern "C" int lime_linear_group_f32(const lime_linear_args* args, int32_t n, vo
         LIME_REQUIRE(a->a && a->w && a->c, LIME_ERR_BAD_ARG, "lime_linear_group_f32: problem %d: a, w and c must be non-NULL", k);
         LIME_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0 && a->ldw >= a->K && a->ldc >= a->N && a->lda >= a->K, LIME_ERR_BAD_ARG,
                      "lime_linear_group_f32: problem %d: bad dims / leading dimensions", k);
-        LIME_REQUIRE(a->act >= LIME_ACT_NONE && a->act <= LIME_ACT_SIGMOID && a->res_mod >= 0 && (!a->res || a->res_ids || a->res_div >= 1) &&
+        LIME_REQUIRE(a->act >= LIME_ACT_NONE && a->act <= LIME_ACT_RELU_GRAD && a->res_mod >= 0 && (!a->res || a->res_ids || a->res_div >= 1) &&
                      (!a->res || a->ldr >= a->N), LIME_ERR_BAD_ARG, "lime_linear_group_f32: problem %d: bad act / residual arguments", k);
         if (a->M == 0) continue;
         long ntiles = 0;
         LIME_REQUIRE(mid_params(a, g.p[g.n], ntiles), LIME_ERR_UNSUPPORTED,
                      "lime_linear_group_f32: problem %d is outside the mid-M kernel (16-byte friendly operands, K >= 16, no LayerNorm / pooling / "
-                     "a_pe / c_ids / res_pe): launch it with lime_linear_f32", k);
+                     "a_pe / c_ids / res_pe / dropout / ReLU gradient): launch it with lime_linear_f32", k);
         g.first[g.n] = (int)total;
         total += ntiles;
         LIME_REQUIRE(total <= 0x3FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_linear_group_f32: too many tiles");

@@ -1,5 +1,5 @@
-// Internal interface between lime_linear_f32's dispatcher (gemm_f32.hip) and the two-workgroups-per-CU LDS-DMA
-// kernel (gemm_pp_f32.hip).
+// Internal interface between lime_linear_f32's dispatcher (gemm_f32.hip) and the big-M / mid-M kernels behind it (gemm_pp_f32.hip,
+// gemm_sp_f32.hip, gemm_mid_f32.hip), their shared parameter block, and the split-product entry points other units dispatch to.
 #pragma once
 #include "common.h"
 #include "dropout.h"
@@ -24,6 +24,30 @@ struct PPParams {
     unsigned long long* stamps;
 #endif
 };
+
+// The fields of PPParams that every dispatcher takes from its argument block unchanged (lime_linear_args, or lime_linear_bf16_args with
+// its bf16 operands behind float pointers).  Left to the caller: ln_rstd, ln_count where it is not N, act / res_div / act_scale / drop;
+// to launch(): the block counts.
+template <class Args>
+static inline PPParams lime_pp_params(const Args* a) {
+    PPParams p;
+    p.a = (const float*)a->a; p.lda = a->lda; p.a_ids = a->a_ids;
+    p.w = (const float*)a->w; p.ldw = a->ldw; p.bias = a->bias;
+    p.res = (const float*)a->res; p.ldr = a->ldr; p.res_mod = a->res_mod; p.res_ids = a->res_ids;
+    p.res_pe = a->res_pe; p.ldr_pe = a->ldr_pe; p.res_period = a->res_period > 0 ? a->res_period : 1;
+    p.ln_g = a->ln_gamma; p.ln_b = a->ln_beta; p.ln_eps = a->ln_eps; p.ln_rstd = nullptr;
+    p.c = (float*)a->c; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.K = a->K; p.ln_count = a->N;
+    p.n_row_blocks = p.n_col_blocks = 0;
+    p.m_dev = a->m_dev; p.c_ids = a->c_ids;
+    return p;
+}
+
+// The tile width that pads N least: true = 320 columns, false = 256.  The dispatchers differ on a tie (N = 1280 k): the split-product
+// kernel takes the wide tile (tie_wide), the fp32-MFMA kernels the narrow one.
+static inline bool lime_pp_wide(int N, bool tie_wide) {
+    const int pad5 = (N + 319) / 320 * 320 - N, pad4 = (N + 255) / 256 * 256 - N;
+    return tie_wide ? pad5 <= pad4 : pad5 < pad4;
+}
 
 int lime_linear_pp(const lime_linear_args* a, hipStream_t stream);
 int lime_linear_sp(const lime_linear_args* a, hipStream_t stream);       // gemm_sp_f32.hip (split product on the bf16 cores), same convention

@@ -18,7 +18,7 @@
 //     the CU's address path all at once); one barrier per chunk.
 //   * an LDS-DMA instruction writes 1 KB linearly (lane l -> base + 16 l), so rows cannot be padded; the image is
 //     [row][16 floats] with the 16-byte segment index XOR-swizzled by swz4((row >> 2) & 3) -- applied to the per-lane
-//     SOURCE address when staging and to the ds_read_b128 address when reading fragments (see swz4: the permutation is
+//     SOURCE address when staging and to the ds_read_b128 address when reading fragments (see swz4 in dev_helpers.h: the permutation is
 //     chosen for the hardware's non-contiguous 16-lane read groups; measured SQ_LDS_BANK_CONFLICT = 0).
 //   * the MFMA is v_mfma_f32_16x16x4_f32, not 32x32x2: same nominal rate, same LDS traffic per flop here, but half the
 //     accumulator-register traffic per flop.  (A registers-only MFMA loop on random operands is POWER limited with
@@ -30,98 +30,21 @@
 //     two shuffles).
 //   * k beyond K, rows beyond M and weight rows beyond N are out-of-range buffer offsets: the DMA writes zeros.
 #include "common.h"
+#include "dev_helpers.h"
 #include "gemm_pp.h"
+
+using namespace lime_dev;
 
 #ifdef LIME_STAMPS
 // Diagnostic build only (tools/gemm_stamps.py): per-wave s_memtime sums of the main-loop segments; never in liblime_hip.so.
 static unsigned long long* g_pp_stamp_buf = nullptr;
 extern "C" void lime_debug_set_pp_stamp_buffer(unsigned long long* p) { g_pp_stamp_buf = p; }
-#define PSTAMP(i)                                                           \
-    {                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                 \
-        tsum[i] += t_ - tlast;                                              \
-        tlast = t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-    }
-#else
-#define PSTAMP(i)
 #endif
 
 namespace {
 
 constexpr int BM = 128;   // output rows per tile (4 waves x 32)
 constexpr int BK = 16;    // k depth of one LDS stage
-constexpr unsigned OOB = 0x80000000u;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7FFFFFF0, 0x00020000);
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ int buf_load_i32(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return (int)__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0);
-}
-// 16 bytes per lane global -> LDS (lane l lands at lds_base + 16 l), out-of-range offsets write zeros.
-// (The builtin only exists in the device pass; inside a kernel TEMPLATE it makes the host pass drop the launch stub.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, float* lds_base, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds_base, 16, voff, soff, 0, 0);
-#endif
-}
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// bf16 <-> fp32 (round to nearest even; inputs are finite on this path)
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {       // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ f32x4 unpack_bf16x4(u32x2 v) {
-    f32x4 r;
-    r[0] = __builtin_bit_cast(float, v[0] << 16);
-    r[1] = __builtin_bit_cast(float, v[0] & 0xFFFF0000u);
-    r[2] = __builtin_bit_cast(float, v[1] << 16);
-    r[3] = __builtin_bit_cast(float, v[1] & 0xFFFF0000u);
-    return r;
-}
-__device__ __forceinline__ f32x4 buf_load4_bf16(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {     // 4 bf16 -> 4 floats
-    return unpack_bf16x4(__builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0)));
-}
-__device__ __forceinline__ void buf_store4_bf16(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    u32x2 o;
-    o[0] = pack_bf16(v[0], v[1]);
-    o[1] = pack_bf16(v[2], v[3]);
-    __builtin_amdgcn_raw_buffer_store_b64(o, r, voff, soff, 0);
-}
-__device__ __forceinline__ void buf_store4(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 0);
-}
-
-// Swizzle term of image row r: segment XOR swz4((r >> 2) & 3).  ds_read_b128 is serviced in four NON-contiguous 16-lane
-// groups ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, +32 for the other two; MI355X_MICROARCH.md, LDS): with the MFMA
-// 16x16 lane layout (row = lane & 15, k slot = lane >> 4) a group mixes rows 0-3 / 12-15 of one k slot with rows 4-11 of
-// another, and the plain XOR with (r >> 2) & 3 put two rows of every group on each 16-byte slot (SQ_LDS_BANK_CONFLICT =
-// 49 % of the LDS cycles).  The permutation {0, 2, 3, 1} of (r >> 2) & 3 makes all four groups conflict free.
-__device__ __forceinline__ int swz4(int q) { return (0x78 >> (2 * q)) & 3; }
-
-// Sum over the 16 lanes of a DPP row (the lanes that share a k slot, i.e. the 16 tokens of an MFMA tile): butterfly with
-// quad_perm (xor 1, xor 2) and row rotations by 4 and 8; every lane ends up with the total.
-__device__ __forceinline__ float row16_sum(float v) {
-    int x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));        // quad_perm [1,0,3,2]
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));        // quad_perm [2,3,0,1]
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, true));       // row_ror:4
-    x = __builtin_bit_cast(int, v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true));       // row_ror:8
-    return v;
-}
 
 // NTL: 32-column MFMA tiles per wave (tile width 32 * NTL).  LN: LayerNorm epilogue (one column block spans N).
 // RES: 0 none, 1 dense fp32 residual rows (r, or r % res_mod), 2 gathered rows + fp32 positional table,
@@ -508,17 +431,17 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(const PPParams p) {
         const bool more = ti + nw_x < tcount;
         const int cid_epi[2] = {cid_cur[0], cid_cur[1]};       // the loader moves on before this tile's epilogue
         acc_init(tile, par, rid_cur, cid_cur);
-        PSTAMP(0)                                     // 0: accumulator init (residual loads issued)
+        LIME_STAMP(0)                                     // 0: accumulator init (residual loads issued)
         for (int c = 0; c + 1 < nchunk; ++c) {
             issue_a(stage ^ 1, c + 1);
-            PSTAMP(1)                                 // 1: DMA issue
+            LIME_STAMP(1)                                 // 1: DMA issue
             compute(stage, stage ^ 1, c + 1);
             __builtin_amdgcn_sched_barrier(0);        // MFMAs touch no memory: hipcc otherwise sinks them below the wait + barrier
-            PSTAMP(2)                                 // 2: fragment reads + MFMA issue
+            LIME_STAMP(2)                                 // 2: fragment reads + MFMA issue
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            PSTAMP(3)                                 // 3: DMA landed
+            LIME_STAMP(3)                                 // 3: DMA landed
             lds_barrier();
-            PSTAMP(4)                                 // 4: barrier
+            LIME_STAMP(4)                                 // 4: barrier
             stage ^= 1;
         }
         // last chunk of the tile: the loader moves on to the next tile first
@@ -531,19 +454,19 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(const PPParams p) {
             prefetch_ids(tile_at(ti + 2 * nw_x));
             issue_a(stage ^ 1, 0);
         }
-        PSTAMP(5)                                     // 5: loader switch
+        LIME_STAMP(5)                                     // 5: loader switch
         compute(stage, more ? (stage ^ 1) : -1, 0);
         __builtin_amdgcn_sched_barrier(0);
-        PSTAMP(2)
+        LIME_STAMP(2)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PSTAMP(3)
+        LIME_STAMP(3)
         lds_barrier();
-        PSTAMP(4)
+        LIME_STAMP(4)
         stage ^= 1;
         // the stores retire under the next tile's first chunk; the bias image this reads is double-buffered by tile parity
         // (the next tile's acc_init rewrites the other half)
         epilogue(tile, par, cid_epi);
-        PSTAMP(6)                                     // 6: epilogue
+        LIME_STAMP(6)                                     // 6: epilogue
     }
 #ifdef LIME_STAMPS
     if (p.stamps && lane == 0) {
@@ -553,24 +476,13 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(const PPParams p) {
 #endif
 }
 
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 template <int NTL, bool LN, bool RELU, int RES, bool BF = false, bool POOL = false, bool RSTD = false, bool CID = false, int TRIM = 0>
 int launch(const PPParams& p0, hipStream_t stream) {
     PPParams p = p0;
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + NTL * 32 - 16 * TRIM - 1) / (NTL * 32 - 16 * TRIM);
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = 2L * num_cus();
+    long nwg = 2L * lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
 #ifdef LIME_STAMPS
     p.stamps = g_pp_stamp_buf;
@@ -580,8 +492,6 @@ int launch(const PPParams& p0, hipStream_t stream) {
                                 BF ? "true" : "false", POOL ? "true" : "false", RSTD ? "true" : "false", CID ? "true" : "false", TRIM);   // as rocprofv3 prints it
     return lime_check_launch("lime_linear_f32");
 }
-
-inline bool al16(const void* ptr, long ld) { return ptr == nullptr || (((uintptr_t)ptr % 16) == 0 && (ld % 4) == 0); }
 
 }  // namespace
 
@@ -595,7 +505,7 @@ int lime_linear_pp(const lime_linear_args* a, hipStream_t s) {
     if (!(a->act == LIME_ACT_NONE || (relu && !has_res))) return LIME_PP_NOT_APPLICABLE;
     if (a->K % 4 || a->N % 4 || a->K < 2 * 16) return LIME_PP_NOT_APPLICABLE;      // >= 2 chunks: a barrier between the
                                                                                      // bias image's write and its read
-    if (!al16(a->a, a->lda) || !al16(a->w, a->ldw) || !al16(a->c, a->ldc) || !al16(a->res, a->ldr) || !al16(a->res_pe, a->ldr_pe))
+    if (!lime_al16(a->a, a->lda) || !lime_al16(a->w, a->ldw) || !lime_al16(a->c, a->ldc) || !lime_al16(a->res, a->ldr) || !lime_al16(a->res_pe, a->ldr_pe))
         return LIME_PP_NOT_APPLICABLE;
     if (a->bias && (uintptr_t)a->bias % 4) return LIME_PP_NOT_APPLICABLE;
     // 32-bit byte offsets: within one 128-row block of a dense operand, within the whole of a gathered / periodic one
@@ -615,18 +525,10 @@ int lime_linear_pp(const lime_linear_args* a, hipStream_t s) {
     // column validity is tested in the last two 32-column tiles of a block only: the last block must not be narrower
     auto tail_ok = [&](int bn) { const int last = a->N - (a->N - 1) / bn * bn; return last >= bn - 64; };
 
-    PPParams p;
-    p.a = a->a; p.lda = a->lda; p.a_ids = a->a_ids;
-    p.w = a->w; p.ldw = a->ldw; p.bias = a->bias;
-    p.res = a->res; p.ldr = a->ldr; p.res_mod = a->res_mod; p.res_ids = a->res_ids;
-    p.res_pe = a->res_pe; p.ldr_pe = a->ldr_pe; p.res_period = a->res_period > 0 ? a->res_period : 1;
-    p.ln_g = a->ln_gamma; p.ln_b = a->ln_beta; p.ln_eps = a->ln_eps; p.ln_rstd = a->ln_rstd;
-    p.c = a->c; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.K = a->K; p.ln_count = a->N;
-    p.n_row_blocks = p.n_col_blocks = 0;
-    p.m_dev = a->m_dev; p.c_ids = a->c_ids;
+    PPParams p = lime_pp_params(a);
+    p.ln_rstd = a->ln_rstd;
     if (a->c_ids) {                                    // compacted in_proj: periodic residual, rows scattered by c_ids
-        const int pad5c = (a->N + 319) / 320 * 320 - a->N, pad4c = (a->N + 255) / 256 * 256 - a->N;
-        if (!(pad5c < pad4c) || !tail_ok(320)) return LIME_PP_NOT_APPLICABLE;
+        if (!lime_pp_wide(a->N, false) || !tail_ok(320)) return LIME_PP_NOT_APPLICABLE;
         return launch<10, false, false, 1, false, false, false, true>(p, s);
     }
     if (ln) {
@@ -648,10 +550,9 @@ int lime_linear_pp(const lime_linear_args* a, hipStream_t s) {
         return launch<10, true, false, 2>(p, s);
     }
     if (res == 2) return LIME_PP_NOT_APPLICABLE;
-    // the tile width (256 / 320) that pads N least
-    const int pad5 = (a->N + 319) / 320 * 320 - a->N, pad4 = (a->N + 255) / 256 * 256 - a->N;
-    if (tail_ok(pad5 < pad4 ? 320 : 256)) {
-        if (pad5 < pad4) {
+    const bool wide = lime_pp_wide(a->N, false);
+    if (tail_ok(wide ? 320 : 256)) {
+        if (wide) {
             if (res == 1) return launch<10, false, false, 1>(p, s);
             return relu ? launch<10, false, true, 0>(p, s) : launch<10, false, false, 0>(p, s);
         }
@@ -705,20 +606,13 @@ extern "C" int lime_linear_bf16(const lime_linear_bf16_args* a, void* stream) {
     const long lim = 0x7FFFFFF0L;
     LIME_REQUIRE(128L * a->lda * 2 < lim && (long)a->N * a->ldw * 2 < lim && 128L * a->ldc * 4 < lim && 128L * a->ldr * 4 < lim &&
                  (long)a->M * 4 < lim, LIME_ERR_UNSUPPORTED, "lime_linear_bf16: operand too large for 32-bit offsets");
-    const bool wide = ((a->N + 319) / 320 * 320 - a->N) < ((a->N + 255) / 256 * 256 - a->N);
+    const bool wide = lime_pp_wide(a->N, false);
     const int bn = (ln || wide) ? 320 : 256;
     LIME_REQUIRE(a->N - (a->N - 1) / bn * bn >= bn - 64, LIME_ERR_UNSUPPORTED,
                  "lime_linear_bf16: the last %d-column block of N=%d is narrower than %d columns (pad N)", bn, a->N, bn - 64);
 
-    PPParams p;
-    p.a = (const float*)a->a; p.lda = a->lda; p.a_ids = a->a_ids;
-    p.w = (const float*)a->w; p.ldw = a->ldw; p.bias = a->bias;
-    p.res = (const float*)a->res; p.ldr = a->ldr; p.res_mod = a->res_mod; p.res_ids = a->res_ids;
-    p.res_pe = a->res_pe; p.ldr_pe = a->ldr_pe; p.res_period = a->res_period > 0 ? a->res_period : 1;
-    p.ln_g = a->ln_gamma; p.ln_b = a->ln_beta; p.ln_eps = a->ln_eps; p.ln_rstd = nullptr;
-    p.c = (float*)a->c; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.K = a->K; p.ln_count = ln ? a->ln_count : a->N;
-    p.n_row_blocks = p.n_col_blocks = 0;
-    p.m_dev = a->m_dev; p.c_ids = a->c_ids;
+    PPParams p = lime_pp_params(a);
+    if (ln) p.ln_count = a->ln_count;
     if (a->c_ids) {
         LIME_REQUIRE(a->res_kind == 1 && a->res_mod > 0 && !ln && !relu && bn == 320 && (long)a->M * a->ldc * 2 < lim, LIME_ERR_UNSUPPORTED,
                      "lime_linear_bf16: c_ids needs the fp32 periodic residual (res_kind 1, res_mod > 0), no LayerNorm / activation, N in "

@@ -35,7 +35,7 @@
 // the overlapped epilogues returned (profiles/r03_notes.md).
 #include "common.h"
 #include "gemm_pp.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 
 using namespace lime_dev;
@@ -44,17 +44,6 @@ using namespace lime_dev;
 // Diagnostic build only (tools/gemm_stamps.py): per-wave s_memtime sums of the main-loop segments; never in liblime_hip.so.
 static unsigned long long* g_sp_stamp_buf = nullptr;
 extern "C" void lime_debug_set_sp_stamp_buffer(unsigned long long* p) { g_sp_stamp_buf = p; }
-#define SSTAMP(i)                                                           \
-    {                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                 \
-        tsum[i] += t_ - tlast;                                              \
-        tlast = t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-    }
-#else
-#define SSTAMP(i)
 #endif
 
 namespace {
@@ -62,18 +51,6 @@ namespace {
 constexpr int BM = 256;                    // rows per tile: 4 row waves x 64
 constexpr int ROWB = 128;                  // bytes per image row = one 32-deep fp32 chunk
 constexpr int A_BYTES = BM * ROWB;
-
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ int buf_load_i32(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return (int)__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0);
-}
-
-// the three-term split and the six-MFMA product: split_mfma.h
-using Split = SplitFrag;
-__device__ __forceinline__ Split split8(const f32x4 x0, const f32x4 x1) { return split_frag(x0, x1); }
-__device__ __forceinline__ f32x4 mfma6(const Split& w, const Split& a, f32x4 c) { return split_mfma16(w, a, c); }
 
 // CT: 16-column tiles per wave (tile width 32 CT).  LN / RELU / RES / POOL / RSTD / CID as in gemm_pp_kernel:
 // RES 0 none, 1 dense fp32 residual rows (r, or r % res_mod; with CID: c_ids[r] % res_mod), 2 rows gathered by res_ids + the fp32
@@ -189,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
 
     auto compute = [&](int stage, int nstage, int nc, int sel) {        // nstage >= 0: the DMA pieces of chunk nc go out between the tiles
         const unsigned char* const sb = lds + stage * STAGE;
-        Split a[4];
+        SplitFrag a[4];
         // the first column tile is multiplied while the activation fragments are still being split: row tile i's six MFMAs
         // go out behind split i (all four splits first would leave the matrix pipe idle for ~190 VALU instructions per chunk)
         f32x4 r0 = *reinterpret_cast<const f32x4*>(sb + w_off + h0), r1 = *reinterpret_cast<const f32x4*>(sb + w_off + h1);
@@ -203,15 +180,15 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
         // MFMAs (hipcc keeps the MFMAs together and the split behind them -- sched_group_barrier requests for a 1 : 2 interleave were
         // not honoured; the partner wave of the SIMD has the pipe meanwhile, and the loop sits at 0.89 of the bf16 pipe's sustained rate
         // either way: profiles/r03_notes.md)
-        Split w = split8(r0, r1);
+        SplitFrag w = split_frag(r0, r1);
         if (CT > 1) {
             r0 = *reinterpret_cast<const f32x4*>(sb + w_off + 16 * ROWB + h0);
             r1 = *reinterpret_cast<const f32x4*>(sb + w_off + 16 * ROWB + h1);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            a[i] = split8(x0[i], x1[i]);
-            if (0 < nct) acc[i][0] = mfma6(w, a[i], acc[i][0]);
+            a[i] = split_frag(x0[i], x1[i]);
+            if (0 < nct) acc[i][0] = split_mfma16(w, a[i], acc[i][0]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (nstage >= 0) {
@@ -219,18 +196,18 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
             if (1 < NPIECE) issue_piece(1, nstage, nc, sel);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (CT > 1) w = split8(r0, r1);
+        if (CT > 1) w = split_frag(r0, r1);
 #pragma unroll
         for (int j = 1; j < CT; ++j) {
-            Split wn = w;
+            SplitFrag wn = w;
             if (j < nct) {                             // (one basic block: the reads, this tile's MFMAs and the next tile's split)
                 if (j + 1 < CT) {                      // the next tile's fragment: read, and split under this tile's MFMAs
                     r0 = *reinterpret_cast<const f32x4*>(sb + w_off + (j + 1) * 16 * ROWB + h0);
                     r1 = *reinterpret_cast<const f32x4*>(sb + w_off + (j + 1) * 16 * ROWB + h1);
                 }
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][j] = mfma6(w, a[i], acc[i][j]);
-                if (j + 1 < CT) wn = split8(r0, r1);
+                for (int i = 0; i < 4; ++i) acc[i][j] = split_mfma16(w, a[i], acc[i][j]);
+                if (j + 1 < CT) wn = split_frag(r0, r1);
             }
             __builtin_amdgcn_sched_barrier(0);         // pins the DMA issue between the column tiles
             if (nstage >= 0) {                         // two pieces per column tile: all out in the first half of the chunk
@@ -485,16 +462,16 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
         const bool more = ti + nw_x < tcount;
         acc_init(tile, par, sel);
         load_rows(tile_at(ti + nw_x));                 // the next tile's row lists: loaded now, parked after the first chunk
-        SSTAMP(0)                                     // 0: accumulator init (residual loads issued)
+        LIME_STAMP(0)                                     // 0: accumulator init (residual loads issued)
         for (int c = 0; c + 1 < nchunk; ++c) {
             compute(stage, stage ^ 1, c + 1, sel);
             __builtin_amdgcn_sched_barrier(0);         // MFMAs touch no memory: hipcc otherwise sinks them below the wait + barrier
-            SSTAMP(c == 0 ? 1 : 2)                    // 1: first chunk of a tile (waits for the residual loads), 2: reads + split + MFMA + DMA issue
+            LIME_STAMP(c == 0 ? 1 : 2)                    // 1: first chunk of a tile (waits for the residual loads), 2: reads + split + MFMA + DMA issue
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            SSTAMP(c == 0 ? 3 : 4)                    // 3: DMA (and the previous tile's stores) landed, first chunk; 4: other chunks
+            LIME_STAMP(c == 0 ? 3 : 4)                    // 3: DMA (and the previous tile's stores) landed, first chunk; 4: other chunks
             if (c == 0) park_rows(sel ^ 1);
             lds_barrier();
-            SSTAMP(5)                                 // 5: barrier
+            LIME_STAMP(5)                                 // 5: barrier
             stage ^= 1;
         }
         // last chunk of the tile: the loader moves on to the next tile first (its row lists were parked >= one barrier ago:
@@ -502,15 +479,15 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
         if (more) loader_set_tile(tbase + ti + nw_x);
         compute(stage, more ? (stage ^ 1) : -1, 0, sel ^ 1);
         __builtin_amdgcn_sched_barrier(0);
-        SSTAMP(2)
+        LIME_STAMP(2)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SSTAMP(4)
+        LIME_STAMP(4)
         lds_barrier();
-        SSTAMP(5)
+        LIME_STAMP(5)
         stage ^= 1;
         // the stores retire under the next tile's first chunk; the bias image is double-buffered by tile parity
         epilogue(tile, par, sel);
-        SSTAMP(6)                                     // 6: epilogue (stores issued)
+        LIME_STAMP(6)                                     // 6: epilogue (stores issued)
     }
 #ifdef LIME_STAMPS
     if (p.stamps && lane == 0) {
@@ -520,24 +497,13 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
 #endif
 }
 
-int sp_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 template <int CT, bool LN, bool RELU, int RES, bool POOL = false, bool RSTD = false, bool CID = false>
 int launch(const PPParams& p0, hipStream_t stream) {
     PPParams p = p0;
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + 32 * CT - 1) / (32 * CT);
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = sp_num_cus();
+    long nwg = lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
 #ifdef LIME_STAMPS
     p.stamps = g_sp_stamp_buf;
@@ -547,8 +513,6 @@ int launch(const PPParams& p0, hipStream_t stream) {
                                 POOL ? "true" : "false", RSTD ? "true" : "false", CID ? "true" : "false");    // as rocprofv3 prints it
     return lime_check_launch("lime_linear_f32");
 }
-
-inline bool al16(const void* ptr, long ld) { return ptr == nullptr || (((uintptr_t)ptr % 16) == 0 && (ld % 4) == 0); }
 
 int g_split_mode = -1;         // -1: not read yet; 0 off; 1 on
 
@@ -584,7 +548,7 @@ int lime_linear_sp(const lime_linear_args* a, hipStream_t s) {
     if (relu_grad && (!has_res || ln || a->res_ids || a->res_mod > 0 || a->res_div > 1 || a->c_ids || a->pool32)) return LIME_PP_NOT_APPLICABLE;
     if (!(a->act == LIME_ACT_NONE || relu_grad || (relu && !has_res) || (act_rt && !ln && (!has_res || a->res_ids)))) return LIME_PP_NOT_APPLICABLE;
     if (a->K % 4 || a->N % 4 || a->K < 64) return LIME_PP_NOT_APPLICABLE;          // >= 2 chunks (row lists, bias image)
-    if (!al16(a->a, a->lda) || !al16(a->w, a->ldw) || !al16(a->c, a->ldc) || !al16(a->res, a->ldr) || !al16(a->res_pe, a->ldr_pe))
+    if (!lime_al16(a->a, a->lda) || !lime_al16(a->w, a->ldw) || !lime_al16(a->c, a->ldc) || !lime_al16(a->res, a->ldr) || !lime_al16(a->res_pe, a->ldr_pe))
         return LIME_PP_NOT_APPLICABLE;
     if (a->bias && (uintptr_t)a->bias % 4) return LIME_PP_NOT_APPLICABLE;
     const long row_blocks = ((long)a->M + BM - 1) / BM;
@@ -616,9 +580,7 @@ int lime_linear_sp(const lime_linear_args* a, hipStream_t s) {
     // the accumulators at the tile start: 186 registers, 73 TFLOP/s) -- left to the fp32 kernel; lime_set_split_gemm(3) routes it here
     if (res == 2 && ln && !(g_split_mode & 2)) return LIME_PP_NOT_APPLICABLE;      // only with lime_set_split_gemm(3)
     if (a->pool32 && !(ln && has_res && !a->res_ids && a->res_div <= 1 && a->M % 32 == 0)) return LIME_PP_NOT_APPLICABLE;
-    // the tile width (256 / 320) that pads N least
-    const int pad5 = (a->N + 319) / 320 * 320 - a->N, pad4 = (a->N + 255) / 256 * 256 - a->N;
-    const bool wide = ln || pad5 <= pad4;
+    const bool wide = ln || lime_pp_wide(a->N, true);        // (this kernel takes the wide tile on a tie)
     const long ntiles = row_blocks * ((a->N + (wide ? 319 : 255)) / (wide ? 320 : 256));
     // From the same M on as gemm_pp_f32.hip takes over from the mid-M kernel ...
     if (a->M < 4096) return LIME_PP_NOT_APPLICABLE;
@@ -629,21 +591,14 @@ int lime_linear_sp(const lime_linear_args* a, hipStream_t s) {
     // A device-side row count (m_dev) hides the real M: those launches (the compacted encoder layers) always come here.  A caller
     // that cuts its rows into EQUAL passes (Model.score_impressions) gets one kernel family -- one rounding -- for every pass.
     if (!a->m_dev && !(g_split_mode & 4)) {
-        const long ncu = sp_num_cus();
+        const long ncu = lime_num_cus();
         const long rounds = (ntiles + ncu - 1) / ncu;
         const double fill = (double)ntiles / (double)(rounds * ncu) * (double)a->N / (double)(((a->N + (wide ? 319 : 255)) / (wide ? 320 : 256)) * (wide ? 320 : 256));
         if (fill < 0.45) return LIME_PP_NOT_APPLICABLE;
     }
 
-    PPParams p;
-    p.a = a->a; p.lda = a->lda; p.a_ids = a->a_ids;
-    p.w = a->w; p.ldw = a->ldw; p.bias = a->bias;
-    p.res = a->res; p.ldr = a->ldr; p.res_mod = a->res_mod; p.res_ids = a->res_ids;
-    p.res_pe = a->res_pe; p.ldr_pe = a->ldr_pe; p.res_period = a->res_period > 0 ? a->res_period : 1;
-    p.ln_g = a->ln_gamma; p.ln_b = a->ln_beta; p.ln_eps = a->ln_eps; p.ln_rstd = a->ln_rstd;
-    p.c = a->c; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.K = a->K; p.ln_count = a->N;
-    p.n_row_blocks = p.n_col_blocks = 0;
-    p.m_dev = a->m_dev; p.c_ids = a->c_ids;
+    PPParams p = lime_pp_params(a);
+    p.ln_rstd = a->ln_rstd;
     p.act = act_rt ? a->act : 0;
     p.res_div = (res == 1 && a->res_div > 1) ? a->res_div : 1;
     p.act_scale = a->act_scale;

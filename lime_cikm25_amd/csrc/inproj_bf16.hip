@@ -19,7 +19,7 @@
 //     travel two tiles ahead as plain loads that are only consumed at a tile's first step, where everything is waited for anyway.
 #include <type_traits>
 
-#include "lds_dma.h"
+#include "dev_helpers.h"
 
 using namespace lime_dev;
 
@@ -42,12 +42,6 @@ struct InP {
     int M, N, K;
     const int* m_dev;
 };
-
-__device__ __forceinline__ int lane_here() {            // see ffn_bf16.hip
-    int z = 0;
-    asm volatile("" : "+v"(z));
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
 
 __global__ __launch_bounds__(256, 1) void inproj_bf16_kernel(const InP p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
@@ -320,17 +314,6 @@ __global__ void inproj_pack_kernel(const float* __restrict__ w, long ldw, int N,
     wp[i] = k < K ? (uint16_t)(pack_bf16(w[n * ldw + k], 0.f) & 0xFFFFu) : (uint16_t)0;
 }
 
-int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 }  // namespace
 
 extern "C" int64_t lime_inproj_pack_bf16_size(int32_t N) { return (int64_t)N * (NCH * 32); }
@@ -367,7 +350,7 @@ extern "C" int lime_inproj_bf16(const lime_inproj_bf16_args* a, void* stream) {
     p.c_ids = a->c_ids; p.out = a->out; p.ldo = a->ldo;
     p.M = a->M; p.N = a->N; p.K = a->K; p.m_dev = a->m_dev;
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = num_cus();
+    long nwg = lime_num_cus();
     if (nwg > ntiles) nwg = ntiles;
     hipLaunchKernelGGL(inproj_bf16_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, p);
     return lime_check_launch("lime_inproj_bf16");

@@ -298,12 +298,11 @@ __global__ __launch_bounds__(256) void intent_fuse_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fill_pad_rows_kernel(const int* __restrict__ ids, const float* __restrict__ src, long lds,
                                                              float* __restrict__ dst, long ldd, long rows, int S, int c4n) {
-    typedef float v4 __attribute__((ext_vector_type(4)));
     const long total = rows * c4n;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long)gridDim.x * 256) {
         const long r = q / c4n;
         const int c = (int)(q - r * c4n) * 4;
-        if (ids[r] == 0) *reinterpret_cast<v4*>(dst + r * ldd + c) = *reinterpret_cast<const v4*>(src + (r % S) * lds + c);
+        if (ids[r] == 0) *reinterpret_cast<f32x4*>(dst + r * ldd + c) = *reinterpret_cast<const f32x4*>(src + (r % S) * lds + c);
     }
 }
 

@@ -2,7 +2,7 @@
 // residuals, a product block is six MFMAs (hh, hm, mh, mm, hl, lh; small terms first, fp32 accumulation) -- the error of one fp32
 // rounding per product.  Helpers shared by the attention kernels that take their Q K^T / dO V^T products there.  gfx950 only.
 #pragma once
-#include "lds_dma.h"
+#include "dev_helpers.h"
 
 namespace lime_dev {
 

@@ -14,12 +14,11 @@
 // Unmasked, S in {32, 64, 128} (the encoder-layer shapes); longer sequences take the fp32-core variant in
 // token_attn_f32.hip.  Workgroups are persistent with the next group's K / V / Q prefetched into registers.
 #include "common.h"
+#include "dev_helpers.h"
+
+using namespace lime_dev;
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int KP = 40;    // pitch of K rows in LDS (bf16): 80 bytes, conflict-free ds_read_b128
 constexpr int LDO = 33;   // pitch of the output transpose scratch (floats)
@@ -31,12 +30,6 @@ struct AttnB {
     const int* row_map;      // MAP: q / k / v row of token (seq * S + t) is row_map[seq * S + t] (lime_compact_sequences)
     const int* n_seq_dev;    // MAP: optional device-side sequence count
 };
-
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {          // two floats -> two bf16 (round to nearest even): one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
-}
 
 template <int NT, bool MAP = false>
 __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel(const AttnB p) {
@@ -164,7 +157,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel
                 for (int m = 0; m < 2; ++m) {
                     u32x4 pb;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) pb[j] = pack2(sc[t][8 * m + 2 * j], sc[t][8 * m + 2 * j + 1]);
+                    for (int j = 0; j < 4; ++j) pb[j] = pack_bf16(sc[t][8 * m + 2 * j], sc[t][8 * m + 2 * j + 1]);
                     const unsigned short* vrow = &Vg[fi * VP + t * 32 + 16 * m + 4 * fh];
                     const u32x2 v0 = *reinterpret_cast<const u32x2*>(vrow);          // keys 16 m + 4 fh + 0..3
                     const u32x2 v1 = *reinterpret_cast<const u32x2*>(vrow + 8);      // keys 16 m + 8 + 4 fh + 0..3
@@ -185,7 +178,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel
 #pragma unroll
                     for (int it = 0; it < 8; ++it) {
                         const int row = it * 4 + rsel;
-                        const unsigned w = pack2(scr[row * LDO + 2 * cpair], scr[row * LDO + 2 * cpair + 1]);
+                        const unsigned w = pack_bf16(scr[row * LDO + 2 * cpair], scr[row * LDO + 2 * cpair + 1]);
                         unsigned short* dst = p.out + ((long)seq * S + qt * 32 + row) * p.ldo + head * hd + 2 * cpair;
                         if (2 * cpair + 1 < hd) *reinterpret_cast<unsigned*>(dst) = w;
                         else *dst = (unsigned short)(w & 0xFFFFu);
@@ -204,22 +197,11 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel
     }
 }
 
-int attn_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 template <int NT, bool MAP = false>
 int launch(AttnB p, hipStream_t s) {
     constexpr int G = 4 / NT;
     p.n_group = (p.n_pair + G - 1) / G;
-    long blocks = (long)attn_cus() * (NT <= 2 ? 4 : 3);            // 36 KB LDS, <= 128 / 170 VGPRs: 4 / 3 workgroups per CU
+    long blocks = (long)lime_num_cus() * (NT <= 2 ? 4 : 3);            // 36 KB LDS, <= 128 / 170 VGPRs: 4 / 3 workgroups per CU
     if (blocks > p.n_group) blocks = p.n_group;
     hipLaunchKernelGGL((token_attn_bf16_kernel<NT, MAP>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     return lime_check_launch("lime_token_attention_bf16");

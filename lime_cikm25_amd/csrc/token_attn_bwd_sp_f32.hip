@@ -23,7 +23,7 @@
 // The attention-probability dropout mask is regenerated from the element index as in the fp32 kernel (same seed / site / index).
 #include "common.h"
 #include "gemm_pp.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 #include "dropout.h"
 
@@ -293,19 +293,16 @@ int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, 
         return LIME_PP_NOT_APPLICABLE;
     static_assert(LDS_BYTES <= 163840, "LDS budget");
     static bool configured = false;
-    static int n_cu = 256;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         LIME_REQUIRE(e == hipSuccess, LIME_ERR_LAUNCH, "lime_token_attention_bwd_f32: cannot reserve %d bytes of LDS: %s", LDS_BYTES,
                      hipGetErrorString(e));
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            n_cu = cus;
         configured = true;
     }
     const long n_prob = (long)n_seq * n_head;
     BwdSpP p{q, k, v, ld, dout, ldo, dq, dk, dv, ldd, n_seq, S, n_head, head_dim, scale, drop};
+    const int n_cu = lime_num_cus();
     const unsigned grid = (unsigned)(n_prob < n_cu ? n_prob : n_cu);             // persistent: one workgroup per CU
     if (S == SPB) attn_bwd_sp_kernel<true><<<grid, 512, LDS_BYTES, s>>>(p);
     else attn_bwd_sp_kernel<false><<<grid, 512, LDS_BYTES, s>>>(p);

@@ -20,29 +20,20 @@
 // LDS; Q fragments come straight from global memory in MFMA operand form; short sequences pack 4 (S <= 32)
 // or 2 (S <= 64) pairs per group.  Scores live in the log2 domain so the exponential is one v_exp_f32.
 #include "common.h"
+#include "dev_helpers.h"
 #include "gemm_pp.h"
 #include <type_traits>
+
+using namespace lime_dev;
 
 #ifdef LIME_STAMPS
 // Diagnostic build only (tools/attn_stamps.py): per-wave s_memtime sums of the loop segments; never in liblime_hip.so.
 static unsigned long long* g_attn_stamp_buf = nullptr;
 extern "C" void lime_debug_set_attn_stamp_buffer(unsigned long long* p) { g_attn_stamp_buf = p; }
-#define ASTAMP(i)                                                           \
-    {                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                 \
-        tsum[i] += t_ - tlast;                                              \
-        tlast = t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-    }
-#else
-#define ASTAMP(i)
 #endif
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int LDH = 36;  // pitch of K rows in LDS (floats): conflict-free ds_read_b128
 // V is staged TRANSPOSED, Vt[head dim][key] with pitch SP + 4: accumulator registers 4g .. 4g+3 of a probability tile
 // are keys 32t + 8g + 4*half + 0..3, so the matching A operands of four consecutive PV MFMAs are one ds_read_b128
@@ -273,9 +264,9 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
     for (; group < n_group; group += gridDim.x) {
         if (!PREFETCH) fetch(group);
         stash(group);
-        ASTAMP(0)
+        LIME_STAMP(0)
         lds_barrier();
-        ASTAMP(1)
+        LIME_STAMP(1)
         const int pair = group * G + g;
         const bool live = pair < n_pair;
         const int seq = live ? pair / p.n_head : 0, head = live ? pair - seq * p.n_head : 0;
@@ -291,7 +282,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
             prefetch_q(group + gridDim.x);
         }
         __builtin_amdgcn_sched_barrier(0);
-        ASTAMP(2)
+        LIME_STAMP(2)
         if (live) {
             for (int qt = qt0; qt < NT; qt += WPP) {
                 if (qt * 32 >= S) break;
@@ -378,7 +369,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                     sum += __shfl_xor(sum, 32);
                     inv = 1.0f / sum;
                     if (p.lse && fh == 0 && qt * 32 + fi < S) p.lse[((long)seq * S + qt * 32 + fi) * p.n_head + head] = m + log2f(sum);
-                    ASTAMP(5)
+                    LIME_STAMP(5)
                 } else {
                 // ---- S^T = K Q^T: keys on rows, this lane's query on the column (rows beyond S are zeros in LDS) ------
                 f32x16 sc[NT];
@@ -394,7 +385,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                             sc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[u], qf[kk][u], sc[t], 0, 0, 0);
                     }
                 }
-                ASTAMP(3)
+                LIME_STAMP(3)
                 // ---- key padding / key mask: a select per register (its key is the same for a whole half-wave) -----
                 if constexpr (!FAST) {
 #pragma unroll
@@ -427,7 +418,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                 sum += __shfl_xor(sum, 32);
                 inv = 1.0f / sum;
                 if (p.lse && fh == 0 && qt * 32 + fi < S) p.lse[((long)seq * S + qt * 32 + fi) * p.n_head + head] = m + log2f(sum);
-                ASTAMP(4)
+                LIME_STAMP(4)
                 // ---- O^T = V^T P^T: probability registers are the B operand as they stand --------------------------
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -442,7 +433,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                             o = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[e], sc[t][4 * gq + e], o, 0, 0, 0);
                     }
                 }
-                ASTAMP(5)
+                LIME_STAMP(5)
                 }
                 // ---- transpose [head dim][query] -> [query][head dim] through the scratch, store whole head rows ----
 #pragma unroll
@@ -473,11 +464,11 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                     }
                 }
                 lds_fence();
-                ASTAMP(6)
+                LIME_STAMP(6)
             }
         }
         lds_barrier();                           // everyone is done with this group's LDS images
-        ASTAMP(7)
+        LIME_STAMP(7)
     }
 #ifdef LIME_STAMPS
     if (p.stamps && lane == 0) {
@@ -486,56 +477,42 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
 #endif
 }
 
-int attn_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
-template <int NT>
-int launch_bf16(AttnP p, hipStream_t s) {
-    constexpr int G = (NT >= 3) ? 1 : (4 / NT);
-    p.n_group = (p.n_pair + G - 1) / G;
-    const int per_cu = NT <= 2 ? 3 : (NT <= 4 ? 2 : 1);
-    long blocks = (long)attn_num_cus() * per_cu;
-    if (blocks > p.n_group) blocks = p.n_group;
-    hipLaunchKernelGGL((token_attn_kernel<NT, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return lime_check_launch("lime_token_attention_bf16");
-}
-
-template <int NT>
-int launch(AttnP p, hipStream_t s) {
+// One launch for all four entry points.  BF: bf16 operands and output; MAP: rows gathered through row_map.  Both imply the FAST
+// loaders (their entry points check the layout); the plain fp32 entries pick FAST per call.
+template <int NT, bool BF, bool MAP>
+int launch(AttnP p, hipStream_t s, const char* entry) {
     constexpr int G = (NT >= 3) ? 1 : (4 / NT);
     p.n_group = (p.n_pair + G - 1) / G;
     // LDS per workgroup decides how many are resident per CU; a few persistent workgroups per CU
     const int per_cu = NT <= 2 ? 3 : (NT <= 4 ? 2 : 1);
-    long blocks = (long)attn_num_cus() * per_cu;
+    long blocks = (long)lime_num_cus() * per_cu;
     if (blocks > p.n_group) blocks = p.n_group;
 #ifdef LIME_STAMPS
     p.stamps = g_attn_stamp_buf;
 #endif
-    // FAST: no mask, S a multiple of 32, heads padded to 32 columns, 16-byte aligned operands
-    const bool fast = p.mask == nullptr && p.S == NT * 32 && p.hs == 32 && p.ld % 4 == 0 &&
-                      (((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.v) % 16 == 0);
-    if (fast) hipLaunchKernelGGL((token_attn_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((token_attn_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return lime_check_launch("lime_token_attention_f32");
+    if constexpr (BF || MAP) {
+        hipLaunchKernelGGL((token_attn_kernel<NT, true, BF, MAP>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    } else {
+        // FAST: no mask, S a multiple of 32, heads padded to 32 columns, 16-byte aligned operands
+        const bool fast = p.mask == nullptr && p.S == NT * 32 && p.hs == 32 && p.ld % 4 == 0 &&
+                          (((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.v) % 16 == 0);
+        if (fast) hipLaunchKernelGGL((token_attn_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((token_attn_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    }
+    return lime_check_launch(entry);
 }
 
-template <int NT>
-int launch_map(AttnP p, hipStream_t s) {
-    constexpr int G = (NT >= 3) ? 1 : (4 / NT);
-    p.n_group = (p.n_pair + G - 1) / G;
-    const int per_cu = NT <= 2 ? 3 : (NT <= 4 ? 2 : 1);
-    long blocks = (long)attn_num_cus() * per_cu;
-    if (blocks > p.n_group) blocks = p.n_group;
-    hipLaunchKernelGGL((token_attn_kernel<NT, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return lime_check_launch("lime_token_attention_rows_f32");
+// nt = ceil(S / 32) key tiles -> the instantiation that holds them (1, 2, 3, 4, 8 or 16; bf16 has none for 3 and never asks for it)
+template <bool BF, bool MAP>
+int launch_nt(int nt, const AttnP& p, hipStream_t s, const char* entry) {
+    if (nt <= 1) return launch<1, BF, MAP>(p, s, entry);
+    if (nt <= 2) return launch<2, BF, MAP>(p, s, entry);
+    if constexpr (!BF) {
+        if (nt <= 3) return launch<3, BF, MAP>(p, s, entry);
+    }
+    if (nt <= 4) return launch<4, BF, MAP>(p, s, entry);
+    if (nt <= 8) return launch<8, BF, MAP>(p, s, entry);
+    return launch<16, BF, MAP>(p, s, entry);
 }
 
 }  // namespace
@@ -558,14 +535,7 @@ extern "C" int lime_token_attention_rows_f32(const float* q, const float* k, con
         if (st != LIME_PP_NOT_APPLICABLE) return st;
     }
     AttnP p{q, k, v, (long)ld_qkv, nullptr, out, (long)ldo, n_seq, S, n_head, head_dim, 32, scale, n_seq * n_head, 1, 0, 0, row_map, n_seq_dev};
-    switch (S / 32) {
-        case 1: return launch_map<1>(p, s);
-        case 2: return launch_map<2>(p, s);
-        case 3: return launch_map<3>(p, s);
-        case 4: return launch_map<4>(p, s);
-        case 8: return launch_map<8>(p, s);
-        default: return launch_map<16>(p, s);
-    }
+    return launch_nt<false, true>(S / 32, p, s, "lime_token_attention_rows_f32");
 }
 
 extern "C" int lime_token_attention_count_f32(const float* q, const float* k, const float* v, int64_t ld_qkv,
@@ -589,15 +559,8 @@ extern "C" int lime_token_attention_count_f32(const float* q, const float* k, co
         if (st != LIME_PP_NOT_APPLICABLE) return st;
     }
     AttnP p{q, k, v, (long)ld_qkv, key_mask, out, (long)ldo, n_seq, S, n_head, head_dim, head_stride, scale, n_seq * n_head, vec2, 0, 0, nullptr, n_seq_dev};
-    const int nt = (S + 31) / 32;
-    if (nt <= 1) return launch<1>(p, s);
-    if (nt <= 2) return launch<2>(p, s);
-    if (nt <= 3) return launch<3>(p, s);
-    if (nt <= 4) return launch<4>(p, s);
-    if (nt <= 8) return launch<8>(p, s);
-    return launch<16>(p, s);
+    return launch_nt<false, false>((S + 31) / 32, p, s, "lime_token_attention_f32");
 }
-
 
 extern "C" int lime_token_attention_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
                                             float* lse, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
@@ -618,13 +581,7 @@ extern "C" int lime_token_attention_lse_f32(const float* q, const float* k, cons
         if (st != LIME_PP_NOT_APPLICABLE) return st;
     }
     AttnP p{q, k, v, (long)ld_qkv, nullptr, out, (long)ldo, n_seq, S, n_head, head_dim, head_stride, scale, n_seq * n_head, vec2, 0, 0, nullptr, nullptr, lse};
-    const int nt = (S + 31) / 32;
-    if (nt <= 1) return launch<1>(p, s);
-    if (nt <= 2) return launch<2>(p, s);
-    if (nt <= 3) return launch<3>(p, s);
-    if (nt <= 4) return launch<4>(p, s);
-    if (nt <= 8) return launch<8>(p, s);
-    return launch<16>(p, s);
+    return launch_nt<false, false>((S + 31) / 32, p, s, "lime_token_attention_f32");
 }
 
 extern "C" int lime_token_attention_f32(const float* q, const float* k, const float* v, int64_t ld_qkv,
@@ -658,11 +615,5 @@ extern "C" int lime_token_attention_bf16(const uint16_t* q, const uint16_t* k, c
     }
     AttnP p{(const float*)q, (const float*)k, (const float*)v, (long)ld_qkv, nullptr, (float*)out, (long)ldo, n_seq, S, n_head,
             head_dim, 32, scale, n_seq * n_head, 1, 0, pad, nullptr, nullptr};
-    switch (S / 32) {
-        case 1: return launch_bf16<1>(p, s);
-        case 2: return launch_bf16<2>(p, s);
-        case 4: return launch_bf16<4>(p, s);
-        case 8: return launch_bf16<8>(p, s);
-        default: return launch_bf16<16>(p, s);
-    }
+    return launch_nt<true, false>(S / 32, p, s, "lime_token_attention_bf16");
 }

@@ -15,7 +15,7 @@
 // The softmax (log2 domain, v_exp_f32) and the output transpose are those of token_attn_f32.hip.
 #include "common.h"
 #include "gemm_pp.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 #include "dropout.h"
 
@@ -34,10 +34,6 @@ struct SpAttnP {
     LimeDropout drop;    // thresh != 0 (the S <= 128 kernel): attention-probability dropout, element (pair, query, key) of the mask
 };
 
-using Split = SplitFrag;                            // split_mfma.h
-__device__ __forceinline__ Split split8(const float (&x)[8]) { return split_frag(x); }
-__device__ __forceinline__ void split4(float x0, float x1, float x2, float x3, u32x2& h, u32x2& m, u32x2& l) { split_quad(x0, x1, x2, x3, h, m, l); }
-__device__ __forceinline__ f32x16 mfma6(const Split& w, const Split& a, f32x16 c) { return split_mfma32(w, a, c); }
 __device__ __forceinline__ void lds_fence() {          // (see token_attn_f32.hip: wave-level, vmcnt left alone)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
             f32x4 kv = kreg[i];
             if (dead) kv = f32x4{0.f, 0.f, 0.f, 0.f};
             u32x2 h, m, l;
-            split4(kv[0], kv[1], kv[2], kv[3], h, m, l);
+            split_quad(kv[0], kv[1], kv[2], kv[3], h, m, l);
             unsigned short* const d = &Ks[(4 * rg + i) * KP + c];
             *reinterpret_cast<u32x2*>(d) = h;
             *reinterpret_cast<u32x2*>(d + K_TERM) = m;
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
             float x0 = vreg[0][j], x1 = vreg[1][j], x2 = vreg[2][j], x3 = vreg[3][j];
             if (dead) { x0 = 0.f; x1 = 0.f; x2 = 0.f; x3 = 0.f; }
             u32x2 h, m, l;
-            split4(x0, x1, x2, x3, h, m, l);
+            split_quad(x0, x1, x2, x3, h, m, l);
             unsigned short* const d = &Vs[(sg * 32 + c + j) * VP + pos];
             *reinterpret_cast<u32x2*>(d) = h;
             *reinterpret_cast<u32x2*>(d + V_TERM) = m;
@@ -157,12 +153,12 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
         }
         __builtin_amdgcn_sched_barrier(0);
         if (live) {
-            Split qs[2];
+            SplitFrag qs[2];
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const f32x4 a = qraw[2 * s] * qscale, b = qraw[2 * s + 1] * qscale;
                 const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-                qs[s] = split8(x);
+                qs[s] = split_frag(x);
             }
             // ---- S^T = K Q^T: keys on rows, this lane's query on the column ---------------------------------------------
             f32x16 sc[NT];
@@ -173,11 +169,11 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const unsigned short* const kp = Kg + t * 32 * KP + 16 * s;
-                    Split ks;
+                    SplitFrag ks;
                     ks.h = *reinterpret_cast<const bf16x8*>(kp);
                     ks.m = *reinterpret_cast<const bf16x8*>(kp + K_TERM);
                     ks.l = *reinterpret_cast<const bf16x8*>(kp + 2 * K_TERM);
-                    sc[t] = mfma6(ks, qs[s], sc[t]);
+                    sc[t] = split_mfma32(ks, qs[s], sc[t]);
                 }
             }
             // ---- softmax over the keys of this lane's query: own registers, then the other half-wave --------------------
@@ -223,13 +219,13 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
                 for (int s = 0; s < 2; ++s) {
                     const float x[8] = {sc[t][8 * s], sc[t][8 * s + 1], sc[t][8 * s + 2], sc[t][8 * s + 3],
                                         sc[t][8 * s + 4], sc[t][8 * s + 5], sc[t][8 * s + 6], sc[t][8 * s + 7]};
-                    const Split ps = split8(x);
+                    const SplitFrag ps = split_frag(x);
                     const unsigned short* const vp = Vg + t * 32 + 16 * s;
-                    Split vs;
+                    SplitFrag vs;
                     vs.h = *reinterpret_cast<const bf16x8*>(vp);
                     vs.m = *reinterpret_cast<const bf16x8*>(vp + V_TERM);
                     vs.l = *reinterpret_cast<const bf16x8*>(vp + 2 * V_TERM);
-                    o = mfma6(vs, ps, o);
+                    o = split_mfma32(vs, ps, o);
                 }
             }
             // ---- transpose [head dim][query] -> [query][head dim] through the scratch, store whole head rows --------------
@@ -292,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             u32x2 h, m, l;
-            split4(kreg[i][0], kreg[i][1], kreg[i][2], kreg[i][3], h, m, l);
+            split_quad(kreg[i][0], kreg[i][1], kreg[i][2], kreg[i][3], h, m, l);
             unsigned short* const d = &Ks[(sr + i) * KP + c];
             *reinterpret_cast<u32x2*>(d) = h;
             *reinterpret_cast<u32x2*>(d + K_TERM) = m;
@@ -302,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             u32x2 h, m, l;
-            split4(vreg[0][j], vreg[1][j], vreg[2][j], vreg[3][j], h, m, l);
+            split_quad(vreg[0][j], vreg[1][j], vreg[2][j], vreg[3][j], h, m, l);
             unsigned short* const d = &Vs[(c + j) * VP + pos];
             *reinterpret_cast<u32x2*>(d) = h;
             *reinterpret_cast<u32x2*>(d + V_TERM) = m;
@@ -320,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
         const int pair = task / n_blk, qb = task - pair * n_blk;
         const int seq = pair / p.n_head, head = pair - seq * p.n_head;
         const int q0 = qb * 128 + wave * 32;            // this wave's 32 queries
-        Split qs[2];
+        SplitFrag qs[2];
         {
             long qrow = (long)seq * S + q0 + fi;
             if constexpr (MAP) qrow = p.row_map[qrow];
@@ -329,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
             for (int s = 0; s < 2; ++s) {
                 const f32x4 a = *reinterpret_cast<const f32x4*>(qsrc + 16 * s) * qscale, b = *reinterpret_cast<const f32x4*>(qsrc + 16 * s + 4) * qscale;
                 const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-                qs[s] = split8(x);
+                qs[s] = split_frag(x);
             }
         }
         f32x16 o;
@@ -351,11 +347,11 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const unsigned short* const kp = Kg + t * 32 * KP + 16 * s;
-                    Split ks;
+                    SplitFrag ks;
                     ks.h = *reinterpret_cast<const bf16x8*>(kp);
                     ks.m = *reinterpret_cast<const bf16x8*>(kp + K_TERM);
                     ks.l = *reinterpret_cast<const bf16x8*>(kp + 2 * K_TERM);
-                    sc[t] = mfma6(ks, qs[s], sc[t]);
+                    sc[t] = split_mfma32(ks, qs[s], sc[t]);
                 }
             }
             float mc = sc[0][0];
@@ -385,13 +381,13 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
                 for (int s = 0; s < 2; ++s) {
                     const float x[8] = {sc[t][8 * s], sc[t][8 * s + 1], sc[t][8 * s + 2], sc[t][8 * s + 3],
                                         sc[t][8 * s + 4], sc[t][8 * s + 5], sc[t][8 * s + 6], sc[t][8 * s + 7]};
-                    const Split ps = split8(x);
+                    const SplitFrag ps = split_frag(x);
                     const unsigned short* const vp = Vg + t * 32 + 16 * s;
-                    Split vs;
+                    SplitFrag vs;
                     vs.h = *reinterpret_cast<const bf16x8*>(vp);
                     vs.m = *reinterpret_cast<const bf16x8*>(vp + V_TERM);
                     vs.l = *reinterpret_cast<const bf16x8*>(vp + 2 * V_TERM);
-                    o = mfma6(vs, ps, o);
+                    o = split_mfma32(vs, ps, o);
                 }
             }
             lds_barrier();                               // everyone is done with this block's images
@@ -413,22 +409,11 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
     }
 }
 
-int sp_attn_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 template <int NT>
 int launch(SpAttnP p, hipStream_t s) {
     constexpr int G = 4 / NT;
     p.n_group = (p.n_pair + G - 1) / G;
-    long blocks = (long)sp_attn_cus() * 2;
+    long blocks = (long)lime_num_cus() * 2;
     if (blocks > p.n_group) blocks = p.n_group;
     if (p.row_map) hipLaunchKernelGGL((token_attn_sp_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((token_attn_sp_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
@@ -451,7 +436,7 @@ int lime_token_attention_sp(const float* q, const float* k, const float* v, long
     SpAttnP p{q, k, v, ld, out, ldo, n_seq, S, n_head, hd, scale, n_seq * n_head, 0, row_map, n_seq_dev, drop ? *drop : LimeDropout{0, 0, 1.f}};
     if (is_long) {
         const long n_task = (long)p.n_pair * (S / 128);
-        long blocks = (long)sp_attn_cus() * 2;
+        long blocks = (long)lime_num_cus() * 2;
         if (blocks > n_task) blocks = n_task;
         if (row_map) hipLaunchKernelGGL((token_attn_sp_long_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, p, lse);
         else hipLaunchKernelGGL((token_attn_sp_long_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, p, lse);

@@ -22,13 +22,11 @@
 
 namespace {
 
-typedef float v4 __attribute__((ext_vector_type(4)));
-
 // four consecutive elements 4 j .. 4 j + 3 of a row of n floats (zeros behind the end)
 template <bool VEC>
-__device__ __forceinline__ v4 load4(const float* __restrict__ p, int j, int n) {
-    if (VEC) return *reinterpret_cast<const v4*>(p + 4 * j);
-    v4 r;
+__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, int j, int n) {
+    if (VEC) return *reinterpret_cast<const f32x4*>(p + 4 * j);
+    f32x4 r;
     const int e = 4 * j;
     r.x = e < n ? p[e] : 0.f;
     r.y = e + 1 < n ? p[e + 1] : 0.f;
@@ -37,14 +35,14 @@ __device__ __forceinline__ v4 load4(const float* __restrict__ p, int j, int n) {
     return r;
 }
 
-__device__ __forceinline__ float dot4(v4 a, v4 b, float acc) {
+__device__ __forceinline__ float dot4(f32x4 a, f32x4 b, float acc) {
     acc = fmaf(a.x, b.x, acc);
     acc = fmaf(a.y, b.y, acc);
     acc = fmaf(a.z, b.z, acc);
     return fmaf(a.w, b.w, acc);
 }
 
-__device__ __forceinline__ v4 axpy4(float a, v4 x, v4 acc) {
+__device__ __forceinline__ f32x4 axpy4(float a, f32x4 x, f32x4 acc) {
     acc.x = fmaf(a, x.x, acc.x);
     acc.y = fmaf(a, x.y, acc.y);
     acc.z = fmaf(a, x.z, acc.z);
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict
     for (int h0 = w; h0 < H; h0 += 4 * W) {
         float part[4] = {0.f, 0.f, 0.f, 0.f};
         for (int j = lane; j < A4; j += 64) {
-            const v4 wv = load4<VEC>(w2, j, A);
+            const f32x4 wv = load4<VEC>(w2, j, A);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int h = h0 + u * W;
@@ -117,18 +115,18 @@ __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict
     const int D4 = D >> 2;
     const float* xr = x + r0 * ldx;
     for (int c = (W == 4) ? (int)threadIdx.x : lane; c < D4; c += W * 64) {
-        v4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         int h = 0;
         for (; h + 8 <= H; h += 8) {
-            v4 xv[8];
+            f32x4 xv[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) xv[k] = *reinterpret_cast<const v4*>(xr + (long)(h + k) * ldx + 4 * c);
+            for (int k = 0; k < 8; ++k) xv[k] = *reinterpret_cast<const f32x4*>(xr + (long)(h + k) * ldx + 4 * c);
 #pragma unroll
             for (int k = 0; k < 8; ++k) acc = axpy4(sc[h + k], xv[k], acc);
         }
-        for (; h < H; ++h) acc = axpy4(sc[h], *reinterpret_cast<const v4*>(xr + (long)h * ldx + 4 * c), acc);
-        *reinterpret_cast<v4*>(us + 4 * c) = acc;
-        if (user_rep != nullptr && live) *reinterpret_cast<v4*>(user_rep + row * D + 4 * c) = acc;
+        for (; h < H; ++h) acc = axpy4(sc[h], *reinterpret_cast<const f32x4*>(xr + (long)h * ldx + 4 * c), acc);
+        *reinterpret_cast<f32x4*>(us + 4 * c) = acc;
+        if (user_rep != nullptr && live) *reinterpret_cast<f32x4*>(user_rep + row * D + 4 * c) = acc;
     }
     if (logits == nullptr) return;
     __syncthreads();
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict
         const float* cp = cand + (row * N + n) * D;
         float part = 0.f;
         for (int c = lane; c < D4; c += 64)
-            part = dot4(*reinterpret_cast<const v4*>(us + 4 * c), *reinterpret_cast<const v4*>(cp + 4 * c), part);
+            part = dot4(*reinterpret_cast<const f32x4*>(us + 4 * c), *reinterpret_cast<const f32x4*>(cp + 4 * c), part);
         const float base = wave_sum(part);
         if (lane == 0 && live)
             logits[row * N + n] = use_weight ? base * lifetime_weight(remaining[row * N + n], alpha_s, beta_s, use_penalty) : base;

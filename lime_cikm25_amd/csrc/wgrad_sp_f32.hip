@@ -15,7 +15,7 @@
 // transposed by the dispatcher (the roles of dY and X swapped, the reduction writes dW^T back transposed).
 #include "common.h"
 #include "gemm_pp.h"
-#include "lds_dma.h"
+#include "dev_helpers.h"
 #include "split_mfma.h"
 
 using namespace lime_dev;
@@ -29,9 +29,6 @@ constexpr int A_FLOATS = 4 * A_GRP, B_FLOATS = 4 * B_GRP, STAGE = A_FLOATS + B_F
 constexpr int CT = TK / 32;                        // 16-column accumulator tiles per wave along k: 10
 static_assert(2 * STAGE * 4 <= 163840, "LDS budget");
 
-using Split = SplitFrag;                            // split_mfma.h
-__device__ __forceinline__ Split split8(const float (&x)[8]) { return split_frag(x); }
-__device__ __forceinline__ f32x4 mfma6(const Split& w, const Split& a, f32x4 c) { return split_mfma16(w, a, c); }
 // eight floats down a column of the [m][COLS] chunk image: rows 8 kg .. 8 kg + 7 of the lane's group
 template <int COLS>
 __device__ __forceinline__ void column8(const float* p, float (&x)[8]) {
@@ -119,25 +116,25 @@ __global__ __launch_bounds__(512, 2) void wgrad_sp_kernel(const float* __restric
             column8<TK>(bp, r);
             column8<TN>(ap, xa[0]);
             column8<TN>(ap + 16, xa[1]);
-            Split a[4];
-            Split w = split8(r);
+            SplitFrag a[4];
+            SplitFrag w = split_frag(r);
             if (CT > 1) column8<TK>(bp + 16, r);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {              // the first column tile's MFMAs go out behind each activation split
-                a[i] = split8(xa[i & 1]);
+                a[i] = split_frag(xa[i & 1]);
                 if (i + 2 < 4) column8<TN>(ap + 16 * (i + 2), xa[i & 1]);
-                if (0 < nct) acc[i][0] = mfma6(w, a[i], acc[i][0]);
+                if (0 < nct) acc[i][0] = split_mfma16(w, a[i], acc[i][0]);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (CT > 1) w = split8(r);
+            if (CT > 1) w = split_frag(r);
 #pragma unroll
             for (int t = 1; t < CT; ++t) {
-                Split wn = w;
+                SplitFrag wn = w;
                 if (t < nct) {                         // one basic block: the next fragment's reads, this tile's MFMAs, the next split
                     if (t + 1 < CT) column8<TK>(bp + 16 * (t + 1), r);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[i][t] = mfma6(w, a[i], acc[i][t]);
-                    if (t + 1 < CT) wn = split8(r);
+                    for (int i = 0; i < 4; ++i) acc[i][t] = split_mfma16(w, a[i], acc[i][t]);
+                    if (t + 1 < CT) wn = split_frag(r);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 w = wn;

@@ -1,7 +1,7 @@
 """Register / scratch budget of every kernel in liblime_hip.so, from the remarks hipcc prints while the library is built
 (`-Rpass-analysis=kernel-resource-usage`, summarised by lime_cikm25_amd.build into liblime_hip.resources.json).  CPU only.
 
-Why this is a test and not a note: the kernels that synchronise an LDS-DMA ring with COUNTED `s_waitcnt vmcnt(N)` (csrc/lds_dma.h
+Why this is a test and not a note: the kernels that synchronise an LDS-DMA ring with COUNTED `s_waitcnt vmcnt(N)` (csrc/dev_helpers.h
 wait_vm<N>, csrc/gemm_mid_f32.hip) were written -- and their counts derived -- for an instruction stream without compiler-made
 vector-memory operations.  A register spill puts scratch_store / scratch_load into that stream: they count in the same vmcnt, every
 reload is followed by a compiler `s_waitcnt vmcnt(0)` that drains the ring, and one build of the bf16 block with 11
@@ -74,6 +74,44 @@ def test_every_unit_with_counted_vmcnt_is_listed():
         if _uses_counted_vmcnt(open(path).read()):
             units.add(os.path.splitext(os.path.basename(path))[0])
     assert units <= set(COUNTED_VMCNT_UNITS), 'counted vmcnt waits in a unit this test does not guard: %s' % sorted(units - set(COUNTED_VMCNT_UNITS))
+
+
+_NOT_A_NAME = {'if', 'for', 'while', 'switch', 'return', 'sizeof', 'else', 'do', 'operator'}
+
+
+def _defined_names(text):
+    """Names a source text DEFINES: functions with a body (prototypes do not count), typedefs, `using X =` aliases, structs and
+    constexpr constants."""
+    text = re.sub(r'//[^\n]*', '', text)
+    text = re.sub(r'__attribute__\(\((?:[^()]|\((?:[^()]|\([^()]*\))*\))*\)\)', ' ', text)
+    names = set()
+    for m in re.finditer(r'^[ \t]*(?:[\w:<>,\*&]+[ \t]+)+[\*&]?(\w+)[ \t]*\([^;{}]*\)[ \t\n]*(?:const[ \t\n]*)?\{', text, re.M):
+        names.add(m.group(1))
+    for m in re.finditer(r'\btypedef\b[^;{}]*?(\w+)\s*;', text):
+        names.add(m.group(1))
+    for m in re.finditer(r'\busing\s+(\w+)\s*=|\bstruct\s+(\w+)\s*\{|\bconstexpr\s+[\w ]+?\b(\w+)\s*=', text):
+        names.add(m.group(1) or m.group(2) or m.group(3))
+    return names - _NOT_A_NAME
+
+
+def test_kernel_files_do_not_redefine_header_helpers():
+    """One definition of every shared helper: what a csrc/*.h defines (dev_helpers.h, common.h, split_mfma.h, gemm_pp.h, dropout.h)
+    no csrc/*.hip defines again -- a copy does not get the next fix to the original (the swizzle permutation, the out-of-range
+    constant, the host-pass guard around the LDS-DMA builtin all were such fixes) -- and the device's CU count is asked for in one
+    place (lime_num_cus, common.cpp)."""
+    shared = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, '*.h'))):
+        for n in _defined_names(open(path).read()):
+            shared.setdefault(n, os.path.basename(path))
+    assert {'make_rsrc', 'dma16', 'swz4', 'lane_here', 'u32x4', 'f32x4', 'lime_al16', 'split_frag', 'OOB', 'PPParams'} <= set(shared), 'the scan lost its grip'
+    copies = []
+    for path in sorted(glob.glob(os.path.join(CSRC, '*.hip'))):
+        for n in sorted(_defined_names(open(path).read()) & set(shared)):
+            copies.append('%s defines %s again (%s has it)' % (os.path.basename(path), n, shared[n]))
+    assert not copies, '\n'.join(copies)
+    askers = [os.path.basename(p) for p in sorted(glob.glob(os.path.join(CSRC, '*')))
+              if re.search(r'multiProcessorCount|hipDeviceAttributeMultiprocessorCount', open(p).read())]
+    assert askers == ['common.cpp'], 'the CU count is queried in %s: call lime_num_cus()' % askers
 
 
 def test_counted_vmcnt_kernels_are_scratch_free(resources):

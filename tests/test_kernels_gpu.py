@@ -899,6 +899,17 @@ def test_linear_group_equals_separate_launches(ops):
     lnp = dict(a=dev(rnd(200, 300, seed=15)), w=dev(rnd(300, 300, seed=16, scale=0.05)), bias=None, ln=(dev(rnd(300, seed=17) + 1.5), dev(rnd(300, seed=18))))
     outs = ops.linear_group([dict(probs[0]), lnp])
     check(outs[1], O.layer_norm(lnp['a'].cpu() @ lnp['w'].cpu().t(), lnp['ln'][0].cpu(), lnp['ln'][1].cpu()), what='fallback')
+    # so does a problem with dropout behind its activation (the grouped kernel has no mask: the entry answers UNSUPPORTED instead of
+    # ignoring dropout_p): the group equals the separate launches bit for bit, mask included
+    dp = dict(a=dev(rnd(200, 300, seed=19)), w=dev(rnd(400, 300, seed=20, scale=0.05)), bias=dev(rnd(400, seed=21)), act='relu',
+              dropout=(0.2, 1234, 7))
+    sep = [ops.linear(**dict(probs[0])).clone(), ops.linear(**dict(dp)).clone()]
+    outs = ops.linear_group([dict(probs[0]), dict(dp)])
+    assert last_kernel() != 'gemm_mid_group_kernel', last_kernel()
+    for i, (a, b) in enumerate(zip(outs, sep)):
+        assert a.shape == b.shape and torch.equal(a, b), 'dropout group, problem %d' % i
+    zeros = float((outs[1] == 0).float().mean())
+    assert zeros > 0.5, 'ReLU + p = 0.2 dropout leaves more than half of the elements zero, got %.3f' % zeros
 
 
 def test_misaligned_layernorm_epilogue_warns_once(ops):

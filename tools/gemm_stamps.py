@@ -1,8 +1,10 @@
 """Diagnostic: where a persistent GEMM workgroup spends its cycles (s_memtime stamps, LIME_STAMPS build of gemm_f32.hip).
 
-    python tools/gemm_stamps.py            # builds tools/probes/liblime_stamps.so if missing, runs the encoder GEMM shapes
+    python tools/gemm_stamps.py            # builds tools/probes/liblime_stamps.<key>.so if missing or stale, runs the encoder GEMM shapes
 """
 import ctypes
+import glob
+import hashlib
 import os
 import subprocess
 import sys
@@ -11,25 +13,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from lime_cikm25_amd import _lib, ops  # noqa: E402
+from lime_cikm25_amd import build as lime_build  # noqa: E402
 
-SO = os.path.join(ROOT, 'tools', 'probes', 'liblime_stamps.so')
 SEG = ['acc_init', 'issue', 'mfma', 'commit', 'barrier', 'switch+tail', 'epilogue', 'next commit+barrier']
 SEG_PP = ['acc_init', 'dma issue', 'reads+mfma', 'dma wait', 'barrier', 'switch', 'epilogue', '-']
 SEG_SP = ['acc_init', 'chunk 0 compute', 'chunk compute', 'chunk 0 wait (DMA + stores)', 'chunk wait (DMA)', 'barrier', 'epilogue', '-']
 
 
 def build():
-    src = os.path.join(ROOT, 'lime_cikm25_amd', 'csrc')
-    subprocess.run(['hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-shared', '-DLIME_STAMPS', '-o', SO,
-                    os.path.join(src, 'gemm_f32.hip'), os.path.join(src, 'gemm_pp_f32.hip'), os.path.join(src, 'gemm_sp_f32.hip'),
-                    os.path.join(src, 'gemm_mid_f32.hip'), os.path.join(src, 'common.cpp')], check=True)
+    """Every unit of the library with -DLIME_STAMPS (the GEMM units call into the others: dropout, the ReLU backward, ...); returns the
+    path of a binary keyed on the sources' content and the define, so a stale one is never reused."""
+    key = hashlib.sha256((lime_build.source_hash() + ' -DLIME_STAMPS').encode()).hexdigest()[:16]
+    so = os.path.join(ROOT, 'tools', 'probes', 'liblime_stamps.%s.so' % key)
+    if not os.path.exists(so):
+        for old in glob.glob(os.path.join(ROOT, 'tools', 'probes', 'liblime_stamps*.so')):
+            os.remove(old)
+        subprocess.run(['hipcc'] + lime_build.FLAGS + ['-DLIME_STAMPS', '-o', so + '.tmp'] + lime_build.sources(), check=True)
+        os.replace(so + '.tmp', so)
+    return so
 
 
 def main():
-    if not os.path.exists(SO):
-        build()
-    _lib.LIB_PATH = SO
-    lib = ctypes.CDLL(SO)
+    so = build()
+    _lib.LIB_PATH = so
+    lib = ctypes.CDLL(so)
     lib.lime_linear_f32.restype = ctypes.c_int32
     lib.lime_linear_f32.argtypes = [ctypes.POINTER(_lib.LinearArgs), ctypes.c_void_p]
     lib.lime_last_error_string.restype = ctypes.c_char_p
