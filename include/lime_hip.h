@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 11
+#define LIME_ABI_VERSION 12
 
 typedef enum {
     LIME_OK = 0,
@@ -811,6 +811,31 @@ int lime_pool_match_f32(const float* hidden, int64_t ldh, const float* w2, const
                         const float* cand, const float* remaining, float alpha_s, float beta_s, int32_t use_weight,
                         int32_t use_penalty, float* user_rep, float* logits, int32_t B, int32_t N, int32_t H, int32_t A, int32_t D,
                         void* stream);
+
+/* =====================================================================================================
+ * The occurrence side of the per-news content cache in one launch (LIME.encode_cached; csrc/cached_occurrence_f32.hip).  A news
+ * occurs in many impressions, each time with its own freshness and lifetime; FreshnessEncoder's output
+ * tanh(dense(cat(E_f[b_f], E_l[b_l]))) (newsEncoders.py:60-83) takes only nb^2 values (nb = num_buckets), so the caller keeps
+ * them -- and everything linear behind them -- as tables of nb^2 rows, row b_f * nb + b_l.  For every occurrence r < R:
+ *     pair = bucket(freshness[r]) * nb + bucket(lifetime[r])               (the rule of lime_bucketize_f32 / _cuts_f32; NaN -> 0)
+ *     LIME_OCC_CONCAT, LIME_OCC_ADD : out[r, :] = A[idx[r], :] + T[pair, :]
+ *     LIME_OCC_GATED                : g = sigmoid(P[idx[r], :] + Q[pair, :]);  out[r, :] = fma(g, A[idx[r], :], (1 - g) * T[pair, :])
+ * with, per fusion method of newsEncoders.py:111-126, :151-159 (c = content width, F = the nb^2 freshness representations):
+ *     concat + project : A = content . W_p[:, :c]^T  [n, D],  T = F . W_p[:, c:]^T + b_p     (P, Q ignored; D = lime_output_dim)
+ *     add              : A = content                 [n, D],  T = F                          (P, Q ignored; D = c)
+ *     gated            : A = content, P = content . W_g[:, :c]^T,  T = F,  Q = F . W_g[:, c:]^T + b_g            (D = c)
+ * A, P, T, Q and out are row-strided (lda .. ldo, in floats), so A and P may be column views of one cache tensor.
+ * idx int32 [R]: every id must be in [0, n) -- unchecked, as in lime_gather_rows_f32.  cuts: NULL for num_buckets = 10 (the
+ * built-in table of lime_bucketize_f32; n_cuts is ignored) or the n_cuts = nb - 1 ascending device cut points of
+ * lime_bucketize_cuts_f32.  n_pairs: the row count of T (and Q), which must equal nb^2 (LIME_ERR_BAD_ARG otherwise: a bucket pair can
+ * then never point behind the tables).  D % 4 == 0, every base pointer 16-byte aligned and every row stride a multiple of 4
+ * (LIME_ERR_BAD_ARG otherwise); 16-byte loads and stores throughout, no LDS, no atomics.  Every output element is one fixed
+ * expression of its own operands: a row's bits depend neither on R nor on its position. */
+enum { LIME_OCC_CONCAT = 0, LIME_OCC_ADD = 1, LIME_OCC_GATED = 2 };
+int lime_cached_occurrence_f32(int32_t mode, const int32_t* idx, const float* freshness, const float* lifetime, const float* cuts,
+                               int32_t n_cuts, const float* A, int64_t lda, const float* P, int64_t ldp, const float* T, int64_t ldt,
+                               const float* Q, int64_t ldq, int64_t n_pairs, float* out, int64_t ldo, int64_t R, int32_t D,
+                               void* stream);
 
 /* =====================================================================================================
  * The dev / test pass behind the scores in one call (util.py:113-123 rank rule + evaluate.py:32-89 metrics;

@@ -10,7 +10,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_ui
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'liblime_hip.so')
 
-ABI_VERSION = 11         # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
+ABI_VERSION = 12         # LIME_ABI_VERSION of include/lime_hip.h this binding was written against
 LIME_ACT = {None: 0, 'none': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'relu_grad': 4}
 
 
@@ -294,6 +294,9 @@ SIGNATURES = {
     # ATT / MHSA user encoders: attention pool over the history + candidate match + lifetime weight
     'lime_pool_match_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                       c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    # the occurrence side of the per-news content cache: bucket pair + row gathers + 'concat' / 'add' / 'gated' combine
+    'lime_cached_occurrence_f32': (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                             c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
     # device-side dev / test pass: ranks and AUC / MRR / nDCG per impression, their sums
     'lime_rank_metrics_workspace': (c_int64, [c_int32]),
     'lime_rank_metrics': (c_int32, [ctypes.POINTER(RankMetricsArgs), c_void_p]),

@@ -117,6 +117,23 @@ __device__ __forceinline__ void buf_store4_bf16(f32x4 v, __amdgpu_buffer_rsrc_t 
     o[1] = pack_bf16(v[2], v[3]);
     __builtin_amdgcn_raw_buffer_store_b64(o, r, voff, soff, 0);
 }
+// The lifetime / freshness bucket rule, stated once (lime_bucketize_f32, lime_bucketize_cuts_f32, lime_cached_occurrence_f32): the
+// number of ascending fp32 cut points that are <= v.  cuts == nullptr: the nine cut points of num_buckets = 10, the smallest floats
+// the reference's own fp32 evaluation of min(trunc(log(max(x, 1)) / log(86400) * (10 / 7)), 9) puts into buckets 1 .. 9
+// (oracle/lime_oracle.py; tests/golden/bucket_edges.npz holds both neighbours of each).  A NaN compares false: bucket 0.
+__device__ __forceinline__ int bucket_of(float v, const float* __restrict__ cuts, int n_cuts) {
+    int b = 0;
+    if (cuts == nullptr) {
+        constexpr unsigned kBucketCuts[9] = {0x45326B18u, 0x4AF8B232u, 0x50AD53E8u, 0x567199BDu, 0x5C2861F4u,
+                                     0x61EAB505u, 0x67A39429u, 0x6D6402D2u, 0x731EE960u};
+#pragma unroll
+        for (int k = 0; k < 9; ++k) b += (v >= __builtin_bit_cast(float, kBucketCuts[k])) ? 1 : 0;
+    } else {
+        for (int k = 0; k < n_cuts; ++k) b += (v >= cuts[k]) ? 1 : 0;
+    }
+    return b;
+}
+
 // Sum over the 16 lanes of a DPP row (the lanes that share a k slot, i.e. the 16 tokens of an MFMA tile): butterfly with quad_perm
 // (xor 1, xor 2) and row rotations by 4 and 8; every lane ends up with the total.
 __device__ __forceinline__ float row16_sum(float v) {

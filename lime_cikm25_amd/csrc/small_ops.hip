@@ -4,6 +4,7 @@
 // All reductions are fixed-order (wave64 shuffles, then LDS across the four waves): results are
 // bitwise reproducible run to run.
 #include "common.h"
+#include "dev_helpers.h"
 
 namespace {
 
@@ -115,19 +116,10 @@ __global__ __launch_bounds__(256) void mean_pool_flat_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------
-// lifetime / freshness buckets: comparison against the fp32 cut points (see oracle/lime_oracle.py)
+// lifetime / freshness buckets: comparison against the fp32 cut points (lime_dev::bucket_of, dev_helpers.h)
 // ---------------------------------------------------------------------------------------------------
-__constant__ unsigned c_bucket_cuts[9] = {0x45326B18u, 0x4AF8B232u, 0x50AD53E8u, 0x567199BDu, 0x5C2861F4u,
-                                          0x61EAB505u, 0x67A39429u, 0x6D6402D2u, 0x731EE960u};
-
 __global__ __launch_bounds__(256) void bucketize_kernel(const float* __restrict__ x, int* __restrict__ out, long n) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-        const float v = x[e];
-        int b = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) b += (v >= __uint_as_float(c_bucket_cuts[k])) ? 1 : 0;   // NaN compares false
-        out[e] = b;
-    }
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) out[e] = lime_dev::bucket_of(x[e], nullptr, 0);
 }
 
 // The masked title encoder (newsEncoders.py:566-595) on a compacted batch: a sequence repeats the all-padding representative when its
@@ -188,12 +180,7 @@ __global__ __launch_bounds__(256) void fuse_rows_kernel(const float* __restrict_
 // the same against a caller-supplied ascending cut-point table (num_buckets != 10)
 __global__ __launch_bounds__(256) void bucketize_cuts_kernel(const float* __restrict__ x, const float* __restrict__ cuts, int n_cuts,
                                                               int* __restrict__ out, long n) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-        const float v = x[e];
-        int b = 0;
-        for (int k = 0; k < n_cuts; ++k) b += (v >= cuts[k]) ? 1 : 0;                          // NaN compares false
-        out[e] = b;
-    }
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) out[e] = lime_dev::bucket_of(x[e], cuts, n_cuts);
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const int* __restrict__ idx, const float* __restrict__ table,

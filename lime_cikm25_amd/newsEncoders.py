@@ -179,11 +179,15 @@ class FreshnessEncoder(nn.Module):
         """int64 like the reference (newsEncoders.py:53-58); computed by threshold comparison on the device."""
         return self.buckets(x.float()).long()
 
+    def cuts_on(self, device):
+        """The cut-point table on ``device`` (None for num_buckets = 10: the table built into the kernels)."""
+        if self._cuts is not None and self._cuts.device != device:
+            self._cuts = self._cuts.to(device)
+        return self._cuts
+
     def buckets(self, x):
         """int32 buckets of a flat fp32 tensor."""
-        if self._cuts is not None and self._cuts.device != x.device:
-            self._cuts = self._cuts.to(x.device)
-        return ops.bucketize(x, self._cuts)
+        return ops.bucketize(x, self.cuts_on(x.device))
 
     def encode_flat(self, freshness, lifetime, out):
         """freshness / lifetime: [M] fp32; out: [M, hidden] (may be a view of a wider buffer)."""
@@ -284,55 +288,88 @@ class LIME(nn.Module):
         # operands instead of one on M rows), gathered into the content GEMM as a residual by the bucket pair (newsEncoders.py:60-83,
         # :151-153; same sums, associated per half).  The branch depends on the inputs' buckets and the weights only: side stream.
         fe = self.freshness_encoder
-        E, nb = fe.freshness_embedding.embedding_dim, fe.num_buckets
+        nb = fe.num_buckets
         side.wait_stream(main)
         with torch.cuda.stream(side):
             pair = torch.add(fe.buckets(lifetime), fe.buckets(freshness), alpha=nb)                        # b_f * nb + b_l, int32 [M]
-            t_f, t_l = ops.linear_group([dict(a=fe.freshness_embedding.weight, w=fe.dense.weight[:, :E], bias=None),       # [nb, cdim]
-                                         dict(a=fe.lifetime_embedding.weight, w=fe.dense.weight[:, E:], bias=fe.dense.bias)])   # [nb, cdim]
-            fresh = torch.tanh(t_f.unsqueeze(1) + t_l.unsqueeze(0)).view(nb * nb, -1)                     # row b_f * nb + b_l
-            table = ops.linear(fresh, self.project.weight[:, cdim:], self.project.bias)                   # [nb^2, final_dim]
+            table, _ = self.occurrence_tables()                                                           # [nb^2, final_dim]
         content = torch.empty((M, cdim), dtype=torch.float32, device=title_text.device)
         self.base_news_encoder.encode_flat(title_text, title_mask, content_text, category, subCategory, content)
         main.wait_stream(side)
         return ops.linear(content, self.project.weight[:, :cdim], None, res=table, res_ids=pair)         # newsEncoders.py:152-153
 
+    def occurrence_tables(self):
+        """(T, Q): what an occurrence adds to its news, for each of the num_buckets^2 (freshness bucket, lifetime bucket) pairs (row
+        b_f * nb + b_l), from the current parameters -- a handful of launches on 10- and 100-row operands, per call, on the device.
+        F = tanh(dense(cat(E_f[b_f], E_l[b_l]))) = tanh(E_f W[:, :E]^T [b_f] + (E_l W[:, E:]^T + b)[b_l])  (newsEncoders.py:60-83), then
+
+            concat + project   T = F . W_p[:, c:]^T + b_p   [nb^2, final_dim]     (the freshness half of `project`, :152-153)
+            concat, identity   T = F                        [nb^2, c]
+            add                T = F                        [nb^2, c]             (:154-155)
+            gated              T = F,  Q = F . W_g[:, c:]^T + b_g                 (the freshness half of `gate`, :156-159)
+
+        Q is None except for 'gated'."""
+        fe = self.freshness_encoder
+        E, nb = fe.freshness_embedding.embedding_dim, fe.num_buckets
+        cdim = self.base_news_encoder.news_embedding_dim
+        t_f, t_l = ops.linear_group([dict(a=fe.freshness_embedding.weight, w=fe.dense.weight[:, :E], bias=None),       # [nb, cdim]
+                                     dict(a=fe.lifetime_embedding.weight, w=fe.dense.weight[:, E:], bias=fe.dense.bias)])   # [nb, cdim]
+        fresh = torch.tanh(t_f.unsqueeze(1) + t_l.unsqueeze(0)).view(nb * nb, -1)                         # row b_f * nb + b_l
+        if self.fusion_method == 'gated':
+            return fresh, ops.linear(fresh, self.gate.weight[:, cdim:], self.gate.bias)
+        if self.fusion_method == 'concat' and not isinstance(self.project, nn.Identity):
+            return ops.linear(fresh, self.project.weight[:, cdim:], self.project.bias), None
+        return fresh, None
+
     # ---- per-news content cache (eval: a news occurs in many impressions, its token encoders need to run once) ----------
     def build_content_cache(self, title_text, title_mask, content_text, category, subCategory, rows_per_pass=8192):
-        """[n_news, output_dim]: the content half of every news pushed through its half of `project`.
+        """One row per news: everything of LIME's representation that depends on the news alone (all the token-encoder work).
 
-        LIME's representation is project(cat(content(news), freshness(freshness, lifetime))) (newsEncoders.py:146-153) and
-        project is linear, so  rep = content . W[:, :c]^T  +  freshness . W[:, c:]^T + b : the first term depends on the news
-        alone (all the token-encoder work), the second on the occurrence (two bucket lookups and two small GEMMs).  The
-        cache holds the first term per news id; ``encode_cached`` adds the second.  Rebuild it when weights change."""
-        if self.fusion_method != 'concat':
-            raise NotImplementedError("the per-news content cache splits `project` into a content and a freshness half: fusion_method "
-                                      "'concat' only (got %r); score with Model.forward / util.compute_scores" % self.fusion_method)
+        'concat' [n, output_dim]: the representation is project(cat(content(news), freshness(freshness, lifetime)))
+        (newsEncoders.py:146-153) and project is linear, so  rep = content . W[:, :c]^T  +  freshness . W[:, c:]^T + b : the cache
+        holds the first term per news id (the content itself when `project` is the identity).
+        'add' [n, c]: the content (rep = content + freshness, :154-155).
+        'gated' [n, 2 c]: columns :c the content, columns c: its half of the gate's pre-activation, content . W_g[:, :c]^T
+        (rep = g content + (1 - g) freshness, g = sigmoid(gate(cat(content, freshness))), :156-159) -- one tensor, two column views.
+        ``encode_cached`` adds the occurrence's side.  Rebuild it when weights change."""
         n = title_text.shape[0]
         cdim = self.base_news_encoder.news_embedding_dim
         dev = title_text.device
         ident = isinstance(self.project, nn.Identity)
-        cache = torch.empty((n, cdim if ident else self.project.out_features), dtype=torch.float32, device=dev)
+        gated = self.fusion_method == 'gated'
+        cache = torch.empty((n, 2 * cdim if gated else cdim if ident else self.project.out_features), dtype=torch.float32, device=dev)
+        direct = gated or ident                                               # the content is (part of) the cache row itself
         for r0 in range(0, n, rows_per_pass):
             r1 = min(n, r0 + rows_per_pass)
-            content = torch.empty((r1 - r0, cdim), dtype=torch.float32, device=dev)
+            content = cache[r0:r1, :cdim] if direct else torch.empty((r1 - r0, cdim), dtype=torch.float32, device=dev)
             self.base_news_encoder.encode_flat(_i32(title_text[r0:r1]).contiguous(), title_mask[r0:r1].contiguous(),
                                                _i32(content_text[r0:r1]).contiguous(), _i32(category[r0:r1]).contiguous(),
                                                _i32(subCategory[r0:r1]).contiguous(), content)
-            if ident:
-                cache[r0:r1] = content
-            else:
+            if gated:
+                ops.linear(content, self.gate.weight[:, :cdim], None, out=cache[r0:r1, cdim:])
+            elif not ident:
                 ops.linear(content, self.project.weight[:, :cdim], None, out=cache[r0:r1])
         return cache
 
-    def encode_cached(self, cache, news_index, freshness, lifetime):
-        """Representations of the occurrences (news_index[r], freshness[r], lifetime[r]) -> [R, output_dim]."""
+    def encode_cached(self, cache, news_index, freshness, lifetime, fused=None):
+        """Representations of the occurrences (news_index[r], freshness[r], lifetime[r]) -> [R, output_dim].
+
+        'add' and 'gated' take lime_cached_occurrence_f32: bucket pair, row gathers from the cache and from ``occurrence_tables()``,
+        combine -- one launch behind the tables.  'concat' + project takes it with ``fused=True`` (default: ops.FUSED_OCCURRENCE,
+        off) and otherwise runs FreshnessEncoder per occurrence with its half of `project` behind it, the cache gathered as a
+        residual: the same sums associated differently, so the default results stay what they were."""
         cdim = self.base_news_encoder.news_embedding_dim
         R = news_index.numel()
         idx = _i32(news_index.reshape(-1)).contiguous()
+        fr, lt = freshness.float().reshape(-1).contiguous(), lifetime.float().reshape(-1).contiguous()
+        ident = isinstance(self.project, nn.Identity)
+        if self.fusion_method != 'concat' or (not ident and (ops.FUSED_OCCURRENCE if fused is None else fused)):
+            T, Q = self.occurrence_tables()
+            A, P = (cache[:, :cdim], cache[:, cdim:]) if self.fusion_method == 'gated' else (cache, None)
+            return ops.cached_occurrence(self.fusion_method, idx, fr, lt, A, T, P, Q, cuts=self.freshness_encoder.cuts_on(cache.device))
         fresh = torch.empty((R, cdim), dtype=torch.float32, device=cache.device)
-        self.freshness_encoder.encode_flat(freshness.float().reshape(-1).contiguous(), lifetime.float().reshape(-1).contiguous(), fresh)
-        if isinstance(self.project, nn.Identity):
+        self.freshness_encoder.encode_flat(fr, lt, fresh)
+        if ident:
             return torch.cat([cache[idx.long()], fresh], dim=1)
         return ops.linear(fresh, self.project.weight[:, cdim:], self.project.bias, res=cache, res_ids=idx)
 

@@ -414,6 +414,48 @@ def gather_rows(idx, table, out):
     return out
 
 
+# LIME.encode_cached with fusion_method 'concat' + project: the freshness half as lime_cached_occurrence_f32 (True) or as today's
+# launches (False, the default: bucketize x 2, gather x 2, dense + tanh, the freshness half of `project` with the cache as a gathered
+# residual).  The two forms associate the same sums differently (equal to fp32 rounding, DESIGN.md "Cached occurrences"), so the
+# default stays until it is flipped on purpose; LIME_FUSED_OCCURRENCE=1 selects the kernel for the whole process.  'add' and 'gated'
+# have the kernel only.
+FUSED_OCCURRENCE = os.environ.get('LIME_FUSED_OCCURRENCE', '0') == '1'
+OCC_MODES = {'concat': 0, 'add': 1, 'gated': 2}             # LIME_OCC_* of include/lime_hip.h
+
+
+def cached_occurrence(mode, idx, freshness, lifetime, A, T, P=None, Q=None, cuts=None, out=None):
+    """``lime_cached_occurrence_f32``: out[r] = A[idx[r]] + T[pair[r]] ('concat', 'add') or g A[idx[r]] + (1 - g) T[pair[r]] with
+    g = sigmoid(P[idx[r]] + Q[pair[r]]) ('gated'), pair = bucket(freshness) * nb + bucket(lifetime) -- the bucket rule of ``bucketize``
+    (``cuts`` as there).  idx int32 [R] (every id in [0, A.shape[0]): not checked, like ``gather_rows``: a check would cost a host
+    synchronise), freshness / lifetime fp32 [R]; A, P [n, D] and T, Q [nb^2, D] may be row-strided views (D % 4 == 0, 16-byte rows)."""
+    lib = _lib.load()
+    if mode not in OCC_MODES:
+        raise ValueError('cached_occurrence: mode must be one of %s, got %r' % (sorted(OCC_MODES), mode))
+    gated = mode == 'gated'
+    if gated and (P is None or Q is None):
+        raise ValueError("cached_occurrence: 'gated' needs P and Q")
+    _mat(A, 'A')
+    _mat(T, 'T')
+    D = A.shape[1]
+    R = _vec(idx, 'idx', dtype=torch.int32).numel()
+    _vec(freshness, 'freshness', R)
+    _vec(lifetime, 'lifetime', R)
+    _vec(cuts, 'cuts')
+    if T.shape[1] != D:
+        raise ValueError('cached_occurrence: T has %d columns, A has %d' % (T.shape[1], D))
+    if gated and (_mat(P, 'P').shape != A.shape or _mat(Q, 'Q').shape != T.shape):
+        raise ValueError('cached_occurrence: P / Q must have the shapes of A / T')
+    if out is None:
+        out = torch.empty((R, D), dtype=torch.float32, device=A.device)
+    if tuple(_mat(out, 'out').shape) != (R, D):
+        raise ValueError('cached_occurrence: out must be [%d, %d], got %s' % (R, D, tuple(out.shape)))
+    check(lib.lime_cached_occurrence_f32(OCC_MODES[mode], _p(idx), _p(freshness), _p(lifetime), _p(cuts), cuts.numel() if cuts is not None else 0,
+                                         _p(A), _ld(A), _p(P) if gated else None, _ld(P) if gated else 0, _p(T), _ld(T),
+                                         _p(Q) if gated else None, _ld(Q) if gated else 0, T.shape[0], _p(out), _ld(out), R, D, _stream()),
+          'lime_cached_occurrence_f32')
+    return out
+
+
 def topic_rep(cat, sub, cat_table, sub_table, w=None, bias=None, out=None, emb_out=None):
     """category_affine(cat[cat_emb, sub_emb]) into ``out`` and/or the raw embedding pair into ``emb_out``."""
     lib = _lib.load()

@@ -31,7 +31,7 @@ class Trainer:
         (as the reference's Config does at start-up) to ``<dev_res_dir>/../ref/truth-<dataset>.txt`` from ``corpus.dev_labels``
         (formats.build_corpus attaches them); a corpus without labels and no file is refused here, before any training.
         ``cached_eval``: the dev pass encodes every news once (util.compute_scores_cached) instead of once per row and slot; same
-        scores.  ``device_eval``: where the cached pass applies and the corpus carries ``dev_labels``, the dev pass also ranks and
+        scores, for every fusion_method.  ``device_eval``: where the cached pass applies and the corpus carries ``dev_labels``, the dev pass also ranks and
         scores on the device (util.evaluate_cached_on_device): the same rank file, metrics equal to rounding; off by default.
 
         Under torch.distributed (WORLD_SIZE in the environment) the process group is initialised and the device selected
@@ -68,7 +68,7 @@ class Trainer:
         self.truth_file = truth_file
         if getattr(config, 'dropout_rate', 0.0) == 0.0 and self.rank == 0:
             print('Trainer: config.dropout_rate is 0 -- the reference trains with 0.2 (config.py:78); pass dropout_rate=0.2 for its recipe')
-        self.cached_eval = cached_eval and config.lifetime_type == 'user_topic' and config.fusion_method == 'concat'
+        self.cached_eval = cached_eval and config.lifetime_type == 'user_topic'
         self.device_eval = bool(device_eval) and self.cached_eval and getattr(corpus, 'dev_labels', None) is not None
         self.dc = device_corpus if device_corpus is not None else DeviceCorpus(corpus)
         self.dev = DeviceBehaviors.from_devtest(self.dc, corpus, 'dev')

@@ -1,0 +1,126 @@
+"""lime_cached_occurrence_f32 (csrc/cached_occurrence_f32.hip) and the per-news content cache of every fusion method, as far as they
+go without a GPU: the export, the ABI version, refusal of bad arguments before any launch, and the Python plumbing above them."""
+import os
+import re
+
+import pytest
+import torch
+
+from lime_cikm25_amd import _lib, make_config, Model, ops
+from lime_cikm25_amd.build import build_library
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = 'lime_cached_occurrence_f32'
+
+
+@pytest.fixture(scope='module')
+def lib():
+    build_library()
+    return _lib.load()
+
+
+def test_the_library_exports_the_kernel_and_header_binding_and_version_agree(lib):
+    header = open(os.path.join(ROOT, 'include', 'lime_hip.h')).read()
+    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+    assert re.search(r'\bint\s+%s\s*\(' % NAME, code), 'the header does not declare %s' % NAME
+    assert NAME in _lib.SIGNATURES
+    assert getattr(lib, NAME) is not None
+    # one ctypes argument per parameter of the C declaration
+    params = re.search(r'\b%s\s*\((.*?)\)\s*;' % NAME, code, flags=re.S).group(1).split(',')
+    assert len(params) == len(_lib.SIGNATURES[NAME][1]) == 20
+    assert lib.lime_abi_version() == _lib.ABI_VERSION == 12
+    assert int(re.search(r'#define\s+LIME_ABI_VERSION\s+(\d+)', header).group(1)) == 12
+    modes = dict(re.findall(r'LIME_OCC_(\w+)\s*=\s*(\d+)', code))
+    assert {k.lower(): int(v) for k, v in modes.items()} == ops.OCC_MODES
+
+
+def call(lib, mode=1, idx=0x1000, fr=0x2000, lt=0x3000, cuts=None, n_cuts=0, A=0x4000, lda=400, P=None, ldp=0, T=0x5000, ldt=400, Q=None,
+         ldq=0, n_pairs=100, out=0x6000, ldo=400, R=4, D=400):
+    """The entry point on made-up (16-byte aligned, never dereferenced) addresses: every case below must be refused before a launch."""
+    return lib.lime_cached_occurrence_f32(mode, idx, fr, lt, cuts, n_cuts, A, lda, P, ldp, T, ldt, Q, ldq, n_pairs, out, ldo, R, D, None)
+
+
+@pytest.mark.parametrize('why,kw', [
+    ('NULL idx', dict(idx=None)), ('NULL freshness', dict(fr=None)), ('NULL lifetime', dict(lt=None)), ('NULL A', dict(A=None)),
+    ('NULL T', dict(T=None)), ('NULL out', dict(out=None)), ('gated without P / Q', dict(mode=2)),
+    ('gated without Q', dict(mode=2, P=0x7000, ldp=400)),
+    ('D % 4', dict(D=398)), ('D = 0', dict(D=0)), ('negative count', dict(R=-1)), ('unknown mode', dict(mode=3)), ('negative mode', dict(mode=-1)),
+    ('row stride below D', dict(lda=396)), ('row stride % 4', dict(ldo=402)), ('misaligned base', dict(A=0x4004)),
+    ('misaligned table', dict(T=0x5008)), ('table rows != num_buckets^2', dict(n_pairs=99)),
+    ('table rows for a cut table', dict(cuts=0x8000, n_cuts=6, n_pairs=100)), ('negative cut count', dict(cuts=0x8000, n_cuts=-1, n_pairs=0)),
+])
+def test_bad_arguments_are_refused_without_a_launch(lib, why, kw):
+    assert call(lib, **kw) == -1, why
+    assert NAME.encode() in lib.lime_last_error_string()
+
+
+def test_an_empty_call_is_accepted_without_a_launch(lib):
+    assert call(lib, R=0) == 0
+    assert call(lib, mode=2, P=0x7000, ldp=400, Q=0x9000, ldq=400, R=0) == 0
+    assert call(lib, cuts=0x8000, n_cuts=6, n_pairs=49, R=0) == 0
+
+
+def test_ops_refuses_cpu_tensors_and_bad_shapes_before_any_launch():
+    idx = torch.zeros(3, dtype=torch.int32)
+    x = torch.zeros(3)
+    A, T = torch.zeros(5, 8), torch.zeros(100, 8)
+    with pytest.raises(TypeError, match='CUDA'):
+        ops.cached_occurrence('add', idx, x, x, A, T)
+    with pytest.raises(ValueError, match='mode'):
+        ops.cached_occurrence('sum', idx, x, x, A, T)
+    with pytest.raises(ValueError, match='P and Q'):
+        ops.cached_occurrence('gated', idx, x, x, A, T)
+
+
+def test_the_fused_concat_path_is_off_by_default():
+    """LIME_FUSED_OCCURRENCE is read once at import; unset, 'concat' keeps the launches it had."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != 'LIME_FUSED_OCCURRENCE'}
+    code = 'from lime_cikm25_amd import ops; print(ops.FUSED_OCCURRENCE)'
+    assert subprocess.run([sys.executable, '-c', code], env=env, cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip() == 'False'
+    env['LIME_FUSED_OCCURRENCE'] = '1'
+    assert subprocess.run([sys.executable, '-c', code], env=env, cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip() == 'True'
+
+
+@pytest.mark.parametrize('fusion,nb', [('concat', 10), ('add', 10), ('gated', 7)])
+def test_plumbing_of_the_cache_and_its_tables_without_a_device(monkeypatch, fusion, nb):
+    """LIME.occurrence_tables / encode_cached are device code; with the three ops they call replaced by shape-only stand-ins the CPU
+    can still check what they hand to the kernels: table shapes, the column views of the gated cache, the cut table, the mode."""
+    cfg = make_config(vocabulary_size=200, max_history_num=4, max_title_length=8, max_abstract_length=8, fusion_method=fusion, num_buckets=nb)
+    ne = Model(cfg).news_encoder
+    c = ne.base_news_encoder.news_embedding_dim
+    seen = {}
+
+    def linear_group(problems):
+        return [torch.zeros(p['a'].shape[0], p['w'].shape[0]) for p in problems]
+
+    def linear(a, w, bias=None, **kw):
+        seen.setdefault('linear', []).append((tuple(a.shape), tuple(w.shape), bias is not None))
+        return torch.zeros(a.shape[0], w.shape[0])
+
+    def cached_occurrence(mode, idx, fr, lt, A, T, P=None, Q=None, cuts=None, out=None):
+        seen['occ'] = dict(mode=mode, A=A, T=T, P=P, Q=Q, cuts=cuts, idx=idx, fr=fr, lt=lt)
+        return torch.zeros(idx.numel(), A.shape[1])
+
+    monkeypatch.setattr(ops, 'linear_group', linear_group)
+    monkeypatch.setattr(ops, 'linear', linear)
+    monkeypatch.setattr(ops, 'cached_occurrence', cached_occurrence)
+    T, Q = ne.occurrence_tables()
+    D = cfg.lime_output_dim if fusion == 'concat' else c
+    assert T.shape == (nb * nb, D) and ne.output_dim == D
+    assert (Q is None) == (fusion != 'gated') and (Q is None or Q.shape == (nb * nb, c))
+    # the one GEMM behind F takes the freshness half of `project` / `gate` and its bias
+    assert seen.get('linear', []) == ([] if fusion == 'add' else [((nb * nb, c), (D, c), True)])
+    cache = torch.zeros(6, 2 * c if fusion == 'gated' else D)
+    idx = torch.tensor([[0, 5], [3, 3]])
+    out = ne.encode_cached(cache, idx, torch.ones(2, 2), torch.ones(2, 2, dtype=torch.float64), fused=True)
+    o = seen['occ']
+    assert out.shape == (4, D) and o['mode'] == fusion
+    assert o['idx'].dtype == torch.int32 and o['idx'].tolist() == [0, 5, 3, 3] and o['fr'].dtype == o['lt'].dtype == torch.float32
+    assert (o['cuts'] is None) == (nb == 10) and (o['cuts'] is None or o['cuts'].numel() == nb - 1)
+    if fusion == 'gated':
+        assert o['A'].data_ptr() == cache.data_ptr() and o['P'].data_ptr() == cache[:, c:].data_ptr() and o['A'].stride(0) == 2 * c
+    else:
+        assert o['A'] is cache and o['P'] is None
+
