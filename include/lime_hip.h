@@ -879,6 +879,30 @@ typedef struct {
 int64_t lime_rank_metrics_workspace(int32_t n_imp);
 int lime_rank_metrics(const lime_rank_metrics_args* args, void* stream);
 
+/* =====================================================================================================
+ * The epoch's negative sampling on the device (Train_Dataset.negative_sampling, dataset.py:42-77; csrc/negative_sample.hip).  The
+ * non-clicked news of the N train records are resident as CSR: offsets int64 [N + 1] (record i owns entries offsets[i] ..
+ * offsets[i + 1] - 1; every offset is clamped into [0, nnz] by the kernel), neg_index int32 [nnz], neg_lifetime fp32 [nnz]; per
+ * record pos_index int32 [N], pos_lifetime fp32 [N], freshness fp32 [N].  Written in full, row i of [N, 1 + K] each:
+ *     cand_index     = [pos_index[i],    neg_index[lo + k_0],    ..., neg_index[lo + k_{K-1}]]            lo = offsets[i]
+ *     cand_freshness = [freshness[i], ... repeated]
+ *     cand_lifetime  = [pos_lifetime[i], neg_lifetime[lo + k_0], ..., neg_lifetime[lo + k_{K-1}]]
+ * with, for n = offsets[i + 1] - offsets[i] non-clicked news:
+ *     n <= K : k_j = j % n
+ *     n >  K : K distinct values, uniform over [0, m), m = n - 1 (inclusive == 0: the reference's randint excludes its upper bound, so
+ *              the last non-clicked news is never drawn) or m = n (inclusive != 0), by a partial Fisher-Yates: with
+ *              u = hi32(splitmix64(key(seed, epoch) + 16 i + j)) -- the generator and key mixing of csrc/dropout.h with site = epoch --
+ *              slot j takes the value at position r = (u * (m - j)) >> 32 of the m - j still free, and the last free value moves to r.
+ *              The multiply-shift is within (m - j) / 2^32 (relative) of uniform.
+ *     n == 0 : the row repeats its positive (the reference divides by zero; the host layers refuse such a record before any launch).
+ * Row i is a function of (seed, epoch, i) and the record alone.  1 <= K <= LIME_NEG_MAX_K, 0 <= nnz < 2^31 and non-NULL pointers, or
+ * LIME_ERR_BAD_ARG before any launch.  One thread per record; no LDS, no atomics, no allocation, no synchronise. */
+#define LIME_NEG_MAX_K 16
+int lime_negative_sample(const int64_t* offsets, const int32_t* neg_index, const float* neg_lifetime, int64_t nnz,
+                         const int32_t* pos_index, const float* pos_lifetime, const float* freshness, int32_t* cand_index,
+                         float* cand_freshness, float* cand_lifetime, int64_t N, int32_t K, uint64_t seed, uint32_t epoch,
+                         int32_t inclusive, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,7 @@ class GatherDesc(ctypes.Structure):
 
 
 MAX_GATHERS = 16
+NEG_MAX_K = 16          # LIME_NEG_MAX_K of include/lime_hip.h
 
 
 class RankMetricsArgs(ctypes.Structure):
@@ -300,6 +301,9 @@ SIGNATURES = {
     # device-side dev / test pass: ranks and AUC / MRR / nDCG per impression, their sums
     'lime_rank_metrics_workspace': (c_int64, [c_int32]),
     'lime_rank_metrics': (c_int32, [ctypes.POINTER(RankMetricsArgs), c_void_p]),
+    # the epoch's negative sampling from the resident CSR of every train record's non-clicked news
+    'lime_negative_sample': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_int32, c_uint64, c_uint32, c_int32, c_void_p]),
 }
 
 _lib = None

@@ -1825,3 +1825,45 @@ def rank_metrics(scores, labels, offsets, skip=None, rank_blocks=0, reduce_block
     a.R, a.n_imp, a.rank_blocks, a.reduce_blocks, a.reserved = R, n_imp, int(rank_blocks), int(reduce_blocks), 0
     check(lib.lime_rank_metrics(ctypes.byref(a), _stream()), 'lime_rank_metrics')
     return RankMetrics(ranks, per_imp, status, sums, count)
+
+
+# ---- the epoch's negative sampling from the resident train tables (csrc/negative_sample.hip) --------------------------------------------
+def negative_sample(offsets, neg_index, neg_lifetime, pos_index, pos_lifetime, freshness, K, seed, epoch, inclusive=False,
+                    cand_index=None, cand_freshness=None, cand_lifetime=None):
+    """``lime_negative_sample``: the candidate tables [N, 1 + K] (news index int32, freshness fp32, lifetime fp32) of one epoch from the
+    CSR of every train record's non-clicked news -- offsets int64 [N + 1], neg_index int32 [nnz], neg_lifetime fp32 [nnz] -- and the
+    per-record pos_index int32 [N], pos_lifetime fp32 [N], freshness fp32 [N]; all CUDA tensors.  Row i is a function of
+    (seed, epoch, i) and the record (device_data.counter_negative_sampling is the same rule in NumPy).  The offsets are not checked (a
+    check would cost a host synchronise; the kernel clamps them into [0, nnz]): DeviceBehaviors.train_resident checks them on the
+    host, where it also refuses a record without non-clicked news.  With the three outputs given nothing is allocated.  Returns
+    (cand_index, cand_freshness, cand_lifetime)."""
+    lib = _lib.load()
+    K, seed, epoch = int(K), int(seed), int(epoch)
+    if not 1 <= K <= _lib.NEG_MAX_K:
+        raise ValueError('negative_sample: K must be in [1, %d], got %d' % (_lib.NEG_MAX_K, K))
+    if not 0 <= epoch < 2 ** 32 - 1 or not 0 <= seed < 2 ** 64:
+        raise ValueError('negative_sample: seed must be in [0, 2^64) and epoch in [0, 2^32 - 1), got %d, %d' % (seed, epoch))
+    N = _vec(pos_index, 'pos_index', dtype=torch.int32).numel()
+    _vec(offsets, 'offsets', N + 1, dtype=torch.int64)
+    nnz = _vec(neg_index, 'neg_index', dtype=torch.int32).numel()
+    _vec(neg_lifetime, 'neg_lifetime', nnz)
+    _vec(pos_lifetime, 'pos_lifetime', N)
+    _vec(freshness, 'freshness', N)
+    if nnz >= 2 ** 31:
+        raise ValueError('negative_sample takes up to 2^31 - 1 non-clicked news in all')
+    dev = pos_index.device
+    if cand_index is None:
+        cand_index = torch.empty((N, 1 + K), dtype=torch.int32, device=dev)
+    if cand_freshness is None:
+        cand_freshness = torch.empty((N, 1 + K), dtype=torch.float32, device=dev)
+    if cand_lifetime is None:
+        cand_lifetime = torch.empty((N, 1 + K), dtype=torch.float32, device=dev)
+    for t, name, dt in ((cand_index, 'cand_index', torch.int32), (cand_freshness, 'cand_freshness', torch.float32),
+                        (cand_lifetime, 'cand_lifetime', torch.float32)):
+        _vec(t, name, N * (1 + K), dtype=dt)
+        if tuple(t.shape) != (N, 1 + K):
+            raise ValueError('negative_sample: %s must be [%d, %d], got %s' % (name, N, 1 + K, tuple(t.shape)))
+    check(lib.lime_negative_sample(_p(offsets), _p(neg_index), _p(neg_lifetime), nnz, _p(pos_index), _p(pos_lifetime), _p(freshness),
+                                   _p(cand_index), _p(cand_freshness), _p(cand_lifetime), N, K, seed, epoch, 1 if inclusive else 0,
+                                   _stream()), 'lime_negative_sample')
+    return cand_index, cand_freshness, cand_lifetime

@@ -1,5 +1,6 @@
 """The reference's training loop (trainer.py:17-244: ``Trainer.train``) on this repo's pieces: per epoch a fresh negative
-sampling, shuffled batches assembled on the device (DeviceBehaviors), the native step (TrainStep: forward, backward, one
+sampling (on the host as in the reference, or with ``device_sampling`` on the device), shuffled batches assembled on the device
+(DeviceBehaviors), the native step (TrainStep: forward, backward, one
 gradient all-reduce under torch.distributed, clip, Adam), then the dev pass (util.compute_scores) with model selection on
 ``config.dev_criterion``, a checkpoint of every improving epoch ({model_name: state_dict}, trainer.py:220) and early stopping.
 
@@ -26,13 +27,20 @@ def _mkdir(path):
 
 
 class Trainer:
-    def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True, device_eval=False):
+    def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True, device_eval=False,
+                 device_sampling=False):
         """``truth_file``: the dev truth file of config.py:262-276 ("<impression> [labels]" lines).  Without one it is written
         (as the reference's Config does at start-up) to ``<dev_res_dir>/../ref/truth-<dataset>.txt`` from ``corpus.dev_labels``
         (formats.build_corpus attaches them); a corpus without labels and no file is refused here, before any training.
         ``cached_eval``: the dev pass encodes every news once (util.compute_scores_cached) instead of once per row and slot; same
         scores, for every fusion_method.  ``device_eval``: where the cached pass applies and the corpus carries ``dev_labels``, the dev pass also ranks and
         scores on the device (util.evaluate_cached_on_device): the same rank file, metrics equal to rounding; off by default.
+        ``device_sampling``: the train split is uploaded once, here (DeviceBehaviors.train_resident), and every epoch's negatives are
+        drawn on the device, in place, by one launch (``resample(config.seed, epoch)``) instead of the host's negative_sampling and a
+        new from_train per epoch; the batch plans of the first epoch serve the whole run.  The draws follow the same rule but a
+        counter-based stream of their own, a function of (seed, epoch, record) -- not numpy.random's, so ``np.random.seed`` no longer
+        decides them (device_data.counter_negative_sampling gives the same tables on the host).  Under torch.distributed every rank
+        computes the same table from (seed, epoch): no broadcast is needed.  Off by default: nothing changes without it.
 
         Under torch.distributed (WORLD_SIZE in the environment) the process group is initialised and the device selected
         FIRST, so that TrainStep's broadcast of rank 0's parameters really runs (DistributedDataParallel does that at
@@ -72,6 +80,8 @@ class Trainer:
         self.device_eval = bool(device_eval) and self.cached_eval and getattr(corpus, 'dev_labels', None) is not None
         self.dc = device_corpus if device_corpus is not None else DeviceCorpus(corpus)
         self.dev = DeviceBehaviors.from_devtest(self.dc, corpus, 'dev')
+        self.device_sampling = bool(device_sampling)
+        self.train_split = DeviceBehaviors.train_resident(self.dc, corpus, config.negative_sample_num) if self.device_sampling else None
         self.step = TrainStep(model, lr=config.lr, weight_decay=config.weight_decay, gradient_clip_norm=config.gradient_clip_norm)
         self.results = {k: [] for k in _CRITERIA}
         self.best_dev_epoch, self.best, self.epoch_not_increase = 0, -1.0, 0
@@ -88,8 +98,11 @@ class Trainer:
 
     def train_epoch(self, e):
         cfg, model = self.config, self.model
-        samples = negative_sampling(self.corpus.train_behaviors, cfg.negative_sample_num)     # dataset.py:42-77
-        train = DeviceBehaviors.from_train(self.dc, self.corpus, *samples)
+        if self.device_sampling:
+            train = self.train_split.resample(getattr(cfg, 'seed', 0), e)                     # the same rule, on the device, in place
+        else:
+            samples = negative_sampling(self.corpus.train_behaviors, cfg.negative_sample_num)     # dataset.py:42-77
+            train = DeviceBehaviors.from_train(self.dc, self.corpus, *samples)
         # shuffle (DataLoader(shuffle=True), trainer.py:86) with a generator every rank seeds alike, as DistributedSampler
         # does with (seed, epoch): the ranks' row sets must partition ONE permutation
         order = np.random.RandomState(getattr(cfg, 'seed', 0) + e).permutation(train.num)
