@@ -38,6 +38,22 @@ static inline int lime_check_launch(const char* what) {
     return LIME_OK;
 }
 
+// Raise `kernel`'s dynamic-LDS limit to `bytes`, once: `reserved` is the caller's static (one per kernel instantiation, 0 at first)
+// and keeps the largest size granted, so a launch that fits makes no runtime call.  `entry`: the entry point the message names.
+static inline int lime_reserve_lds(const void* kernel, int bytes, int& reserved, const char* entry) {
+    if (bytes <= reserved) return LIME_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    LIME_REQUIRE(e == hipSuccess, LIME_ERR_LAUNCH, "%s: cannot reserve %d bytes of LDS: %s", entry, bytes, hipGetErrorString(e));
+    reserved = bytes;
+    return LIME_OK;
+}
+
+// workgroups of a grid-stride kernel: one per `per` of the `total` items, `cap` at the most
+static inline unsigned lime_grid_cap(long total, int per, int cap) {
+    const long g = (total + per - 1) / per;
+    return (unsigned)(g > cap ? cap : g);
+}
+
 __device__ __forceinline__ float wave_half_sum(float v) {
     // sum over the 32 lanes of this lane's half-wave (xor offsets < 32 never cross the halves)
     v += __shfl_xor(v, 16);

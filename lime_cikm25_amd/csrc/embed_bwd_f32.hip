@@ -1,4 +1,9 @@
-// lime_embed_bwd_sorted_f32: dTable[id] = sum over the rows r with ids[r] == id of dX[r], WITHOUT atomics.
+// The gradient of an embedding table, dTable[id] = sum over the rows r with ids[r] == id of dX[r], three ways (ops.embed_bwd chooses):
+//   lime_embed_bwd_small_f32   tables of at most 32 rows (the bucket embeddings): per-column LDS accumulation, no atomics
+//   lime_embed_bwd_sorted_f32  larger tables with dim <= 320 (the word table): a segmented sum over the positions sorted by id, WITHOUT
+//                              atomics and in a fixed order -- what a training step runs, bitwise reproducible
+//   lime_embed_bwd_f32         float atomics: the order of the additions varies from run to run.  Wider rows, or the deterministic
+//                              path switched off
 //
 // lime_embed_bwd_f32 adds with float atomics (a word row receives contributions from many tokens, the padding word from half
 // of them), which made the word-table gradient the one part of a training step that is not bitwise reproducible.  Here the
@@ -19,6 +24,88 @@
 
 namespace {
 
+// ---------------------------------------------------------------------------------------------------
+// word-table gradient: dTable[ids[r], :] += dX[r, :].  A workgroup walks 512 consecutive rows, one wave per row; rows
+// whose id is `hot_id` (the padding word, a large share of all tokens) are summed in registers and added once per wave.
+// ---------------------------------------------------------------------------------------------------
+template <int CPL>
+__global__ __launch_bounds__(256) void embed_bwd_kernel(const int* __restrict__ ids, const float* __restrict__ dx, long lddx,
+                                                         float* __restrict__ dtable, long ldt, long rows, int dim, int hot_id,
+                                                         int rows_per_block) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float hot[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) hot[j] = 0.f;
+    bool any_hot = false;
+    const long r0 = (long)blockIdx.x * rows_per_block;
+    const long r1 = min(rows, r0 + rows_per_block);
+    for (long r = r0 + wave; r < r1; r += 4) {
+        const int id = ids[r];
+        const float* p = dx + r * lddx;
+        if (id == hot_id) {
+            any_hot = true;
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                const int c = lane + 64 * j;
+                if (c < dim) hot[j] += p[c];
+            }
+        } else {
+            float* t = dtable + (long)id * ldt;
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                const int c = lane + 64 * j;
+                if (c < dim) unsafeAtomicAdd(t + c, p[c]);
+            }
+        }
+    }
+    if (any_hot) {
+        float* t = dtable + (long)hot_id * ldt;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int c = lane + 64 * j;
+            if (c < dim) unsafeAtomicAdd(t + c, hot[j]);
+        }
+    }
+}
+
+// Tables of at most 32 rows (the freshness / lifetime bucket embeddings, 10 rows x 500): every row receives hundreds of
+// contributions, so atomics would serialise.  A workgroup owns 64 columns; its four waves walk the rows r = wave, wave + 4,
+// ... and add into a private [32][64] LDS image each; the four images are summed in a fixed order.  No atomics.
+__global__ __launch_bounds__(512) void embed_bwd_small_kernel(const int* __restrict__ ids, const float* __restrict__ dx, long lddx,
+                                                               float* __restrict__ dtable, long ldt, long rows, int dim,
+                                                               int table_rows) {
+    // eight waves, each with its own [32][64] image of the table and sixteen rows in flight (one 64-column workgroup walks every
+    // row: with four waves and eight rows in flight the 1760 rows of a 50-column table took 55 us of dependent round trips)
+    __shared__ float acc[8][32][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    for (int t = 0; t < 32; ++t) acc[wave][t][lane] = 0.f;
+    if (c < dim) {
+        long r = wave;
+        for (; r + 120 < rows; r += 128) {
+            int id[16];
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) { id[u] = ids[r + 8 * u]; v[u] = dx[(r + 8 * u) * lddx + c]; }
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                if (id[u] >= 0 && id[u] < table_rows) acc[wave][id[u]][lane] += v[u];
+        }
+        for (; r < rows; r += 8) {
+            const int id = ids[r];
+            if (id >= 0 && id < table_rows) acc[wave][id][lane] += dx[r * lddx + c];
+        }
+    }
+    __syncthreads();
+    if (c < dim)
+        for (int t = wave; t < table_rows; t += 8)
+            dtable[(long)t * ldt + c] += ((acc[0][t][lane] + acc[1][t][lane]) + (acc[2][t][lane] + acc[3][t][lane])) +
+                                         ((acc[4][t][lane] + acc[5][t][lane]) + (acc[6][t][lane] + acc[7][t][lane]));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// lime_embed_bwd_sorted_f32: the fixed-order sum (passes H, A, B of the file-top comment)
+// ---------------------------------------------------------------------------------------------------
 constexpr int CH = 64;        // sorted positions per chunk (one wave)
 constexpr int HOT_G = 256;    // workgroups (= partial rows) of the first run's sum
 constexpr int HOT_MIN = 8192; // shorter first runs stay in passes A / B
@@ -260,4 +347,28 @@ extern "C" int lime_embed_bwd_sorted_f32(const int32_t* order, const int32_t* so
     hipLaunchKernelGGL(embed_bwd_combine_kernel, dim3(grid + 1), dim3(256), 0, s, (const float*)ws_head, (const float*)ws_tail,
                        (const ChunkFlags*)flags, (long)rows, dtable, (long)ld_table, dim, wsld, (const HotInfo*)hot, (const float*)ws_hot);
     return lime_check_launch("lime_embed_bwd_sorted_f32");
+}
+
+extern "C" int lime_embed_bwd_f32(const int32_t* ids, const float* dx, int64_t lddx, float* dtable, int64_t ld_table, int64_t rows,
+                                  int32_t dim, int32_t hot_id, void* stream) {
+    LIME_REQUIRE(ids && dx && dtable, LIME_ERR_BAD_ARG, "lime_embed_bwd_f32: null pointer");
+    LIME_REQUIRE(rows >= 0 && dim > 0 && lddx >= dim && ld_table >= dim, LIME_ERR_BAD_ARG, "lime_embed_bwd_f32: bad dimensions");
+    LIME_REQUIRE(dim <= 512, LIME_ERR_UNSUPPORTED, "lime_embed_bwd_f32: dim = %d > 512", dim);
+    if (rows == 0) return LIME_OK;
+    const int rpb = 512;
+    const int grid = (int)((rows + rpb - 1) / rpb);
+    hipStream_t s = (hipStream_t)stream;
+    if (dim <= 320) embed_bwd_kernel<5><<<grid, 256, 0, s>>>(ids, dx, lddx, dtable, ld_table, rows, dim, hot_id, rpb);
+    else embed_bwd_kernel<8><<<grid, 256, 0, s>>>(ids, dx, lddx, dtable, ld_table, rows, dim, hot_id, rpb);
+    return lime_check_launch("embed_bwd_kernel");
+}
+
+extern "C" int lime_embed_bwd_small_f32(const int32_t* ids, const float* dx, int64_t lddx, float* dtable, int64_t ld_table,
+                                        int64_t rows, int32_t dim, int32_t table_rows, void* stream) {
+    LIME_REQUIRE(ids && dx && dtable, LIME_ERR_BAD_ARG, "lime_embed_bwd_small_f32: null pointer");
+    LIME_REQUIRE(rows >= 0 && dim > 0 && lddx >= dim && ld_table >= dim, LIME_ERR_BAD_ARG, "lime_embed_bwd_small_f32: bad dimensions");
+    LIME_REQUIRE(table_rows >= 1 && table_rows <= 32, LIME_ERR_UNSUPPORTED, "lime_embed_bwd_small_f32: table_rows = %d outside [1, 32]", table_rows);
+    if (rows == 0) return LIME_OK;
+    embed_bwd_small_kernel<<<(dim + 63) / 64, 512, 0, (hipStream_t)stream>>>(ids, dx, lddx, dtable, ld_table, rows, dim, table_rows);
+    return lime_check_launch("embed_bwd_small_kernel");
 }

@@ -79,15 +79,12 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // Every global access goes through a buffer descriptor: a wave-uniform base (SGPRs) plus a 32-bit lane offset,
 // so a row costs one VGPR instead of a 64-bit pointer pair, and an out-of-range offset reads as zero / drops
 // the store in hardware -- rows beyond M, columns beyond N and k beyond K need no select and no branch.
-// (make_rsrc, OOB -- >= num_records of every descriptor below -- and buf_store4: dev_helpers.h)
+// (make_rsrc, OOB -- >= num_records of every descriptor below --, buf_load1 and buf_store4: dev_helpers.h)
 template <int VEC>
 __device__ __forceinline__ typename VecT<VEC>::T buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     if constexpr (VEC == 4) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
     else if constexpr (VEC == 2) return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
     else return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 __device__ __forceinline__ void buf_store1(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
@@ -568,7 +565,7 @@ inline bool aligned(const void* ptr, long ld, int vec) {
 }  // namespace
 
 extern "C" int lime_relu_bwd_f32(float* dh, int64_t lddh, const float* h, int64_t ldh, int64_t rows, int32_t cols, float scale,
-                                 void* stream);          // backward_f32.hip
+                                 void* stream);          // layernorm_bwd_f32.hip
 extern "C" int lime_dropout_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int32_t cols, float p, uint64_t seed,
                                 uint32_t site, void* stream);           // dropout_f32.hip
 

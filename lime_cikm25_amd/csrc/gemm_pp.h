@@ -53,12 +53,18 @@ int lime_linear_pp(const lime_linear_args* a, hipStream_t stream);
 int lime_linear_sp(const lime_linear_args* a, hipStream_t stream);       // gemm_sp_f32.hip (split product on the bf16 cores), same convention
 int lime_linear_mid(const lime_linear_args* a, hipStream_t stream);      // gemm_mid_f32.hip, same return convention
 
-// wgrad_sp_f32.hip: the weight gradient on the split product (lime_linear_wgrad_f32's big-M path, backward_f32.hip dispatches)
+// wgrad_sp_f32.hip: the weight gradient on the split product (lime_linear_wgrad_f32's big-M path, wgrad_f32.hip dispatches)
 struct LimeWgradSpPlan { bool swap; int n_tiles, k_tiles, splits, rows_per_split; long np, kp; double fill; };
 LimeWgradSpPlan lime_wgrad_sp_plan(int M, int N, int K);
 int lime_wgrad_sp_launch(const LimeWgradSpPlan& w, const float* dy, long ldy, const float* x, long ldx, float* ws, int M, int N, int K,
                          int ones_col, hipStream_t s);
 int lime_wgrad_sp_reduce_t(const LimeWgradSpPlan& w, const float* ws, float* dw, long lddw, int N, int K, int accumulate, hipStream_t s);
+// wgrad_f32.hip: out[r, c] (+)= sum over the splits of ws[split * split_stride + r * ldw + c], in a fixed order; extra (optional):
+// column `cols` of the partial grid into extra[r] in the same launch.  Hidden: between units of the library only, not in its dynamic
+// symbol table.
+__attribute__((visibility("hidden")))
+int lime_reduce_partials(const float* ws, long split_stride, int splits, long ldw, float* out, long ldo, int rows, int cols,
+                         int accumulate, hipStream_t s, float* extra = nullptr);
 int lime_split_mode();                                                   // gemm_sp_f32.hip: the lime_set_split_gemm() setting
 // token_attn_sp_f32.hip: unmasked S = 32 / 64 / 128 attention on the split product (LIME_PP_NOT_APPLICABLE: not taken)
 int lime_token_attention_sp(const float* q, const float* k, const float* v, long ld, const int* row_map, const int* n_seq_dev,

@@ -1286,8 +1286,8 @@ extern "C" int lime_cand_attn_weights_f32(const float* qp, const float* kp, cons
     }
     const size_t lds = (per_wave + 4) * sizeof(float);
     LIME_REQUIRE(lds <= 160 * 1024, LIME_ERR_UNSUPPORTED, "lime_cand_attn_weights_f32: %zu B of LDS needed", lds);
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)cand_attn_weights_serial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static int reserved = 64 * 1024;              // what a kernel may use without asking
+    if (const int st = lime_reserve_lds((const void*)cand_attn_weights_serial_kernel, (int)lds, reserved, "lime_cand_attn_weights_f32")) return st;
     hipLaunchKernelGGL(cand_attn_weights_serial_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, qp, kp, mask, agg, N, H,
                        D, n_head);
     return lime_check_launch("lime_cand_attn_weights_f32");

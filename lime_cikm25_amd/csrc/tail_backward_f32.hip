@@ -686,8 +686,8 @@ extern "C" int lime_interest_match_bwd_f32(const float* kp, const float* qp, con
     int st = lime_check_launch("interest_match_bwd_kernel");
     if (st != LIME_OK) return st;
     const long ck = (long)H * A, cg = (long)H * D;
-    sum_candidates_kernel<<<(int)((B * ck + 255) / 256 > 4096 ? 4096 : (B * ck + 255) / 256), 256, 0, s>>>(part_kp, dkp, B, N, ck);
-    sum_candidates_kernel<<<(int)((B * cg + 255) / 256 > 4096 ? 4096 : (B * cg + 255) / 256), 256, 0, s>>>(part_g, dg, B, N, cg);
+    sum_candidates_kernel<<<lime_grid_cap(B * ck, 256, 4096), 256, 0, s>>>(part_kp, dkp, B, N, ck);
+    sum_candidates_kernel<<<lime_grid_cap(B * cg, 256, 4096), 256, 0, s>>>(part_g, dg, B, N, cg);
     return lime_check_launch("sum_candidates_kernel");
 }
 
@@ -701,12 +701,8 @@ int cand_attn_train(const float* qp, const float* kp, const uint8_t* mask, const
     const size_t bytes = ((size_t)N * D + (size_t)H * D + 2 * (size_t)n_head * N * H + H + 3 * CA_MAXN + 4) * sizeof(float);
     LIME_REQUIRE(bytes <= 160 * 1024 - 512, LIME_ERR_UNSUPPORTED, "%s: %zu bytes of LDS needed", who, bytes);
     if (B == 0) return LIME_OK;
-    static size_t configured = 0;
-    if (bytes > configured) {
-        const hipError_t e = hipFuncSetAttribute((const void*)cand_attn_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        LIME_REQUIRE(e == hipSuccess, LIME_ERR_LAUNCH, "%s: cannot reserve %zu bytes of LDS: %s", who, bytes, hipGetErrorString(e));
-        configured = bytes;
-    }
+    static int reserved = 0;
+    if (const int st = lime_reserve_lds((const void*)cand_attn_train_kernel, (int)bytes, reserved, who)) return st;
     cand_attn_train_kernel<<<B, 256, bytes, (hipStream_t)stream>>>(qp, kp, mask, dagg, agg, dqp, dkp, N, H, D, n_head,
                                                                   1.0f / sqrtf((float)D), lime_make_dropout(p, seed, site), mode);
     return lime_check_launch("cand_attn_train_kernel");

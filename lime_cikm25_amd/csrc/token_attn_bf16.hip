@@ -22,7 +22,6 @@ namespace {
 
 constexpr int KP = 40;    // pitch of K rows in LDS (bf16): 80 bytes, conflict-free ds_read_b128
 constexpr int LDO = 33;   // pitch of the output transpose scratch (floats)
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct AttnB {
     const unsigned short* q; const unsigned short* k; const unsigned short* v; long ld;

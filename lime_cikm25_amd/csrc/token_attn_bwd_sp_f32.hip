@@ -1,7 +1,7 @@
 // lime_token_attention_bwd_f32 for 64 < S <= 128 with ALL FIVE products on the bf16 matrix cores as split products (split_mfma.h:
 // three bf16 terms per fp32 value, six v_mfma_f32_16x16x32_bf16 per 16 x 16 x 32 block, fp32 accumulation).  gfx950 only.
 //
-// token_attn_bwd_kernel (backward_f32.hip) keeps P / dS as an fp32 image in LDS and takes dV, dQ, dK from v_mfma_f32_16x16x4_f32
+// token_attn_bwd_kernel (token_attn_train_f32.hip) keeps P / dS as an fp32 image in LDS and takes dV, dQ, dK from v_mfma_f32_16x16x4_f32
 // (256 matrix cycles per 16 x 16 x 32 block against 96 here); three workgroup barriers per (sequence, head).  Here a 16 x 16 result
 // tile never leaves the registers before it is an operand again.  The MFMA result layout puts a tile's COLUMN on the lane (fi) and
 // its ROWS on the lane group and the registers (4 kg + r), and the k index of the next MFMA is only a summation label: registers
@@ -31,7 +31,6 @@ using namespace lime_dev;
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int SPB = 128;                              // rows per image
 constexpr int TERM = SPB * SWZ_ROW;                   // one bf16 image (unsigned shorts): 64-byte rows
 static_assert(SWZ_ROW == 32, "images hold 32 head dims per row");
@@ -292,14 +291,9 @@ int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, 
     if (((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15) != 0 || (((uintptr_t)dout) & 7) != 0)
         return LIME_PP_NOT_APPLICABLE;
     static_assert(LDS_BYTES <= 163840, "LDS budget");
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        LIME_REQUIRE(e == hipSuccess, LIME_ERR_LAUNCH, "lime_token_attention_bwd_f32: cannot reserve %d bytes of LDS: %s", LDS_BYTES,
-                     hipGetErrorString(e));
-        configured = true;
-    }
+    static int reserved[2] = {0, 0};              // per instantiation: S < SPB, S == SPB
+    const void* const kernel = S == SPB ? (const void*)attn_bwd_sp_kernel<true> : (const void*)attn_bwd_sp_kernel<false>;
+    if (const int st = lime_reserve_lds(kernel, LDS_BYTES, reserved[S == SPB], "lime_token_attention_bwd_f32")) return st;
     const long n_prob = (long)n_seq * n_head;
     BwdSpP p{q, k, v, ld, dout, ldo, dq, dk, dv, ldd, n_seq, S, n_head, head_dim, scale, drop};
     const int n_cu = lime_num_cus();

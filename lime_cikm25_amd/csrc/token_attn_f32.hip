@@ -38,7 +38,6 @@ constexpr int LDH = 36;  // pitch of K rows in LDS (floats): conflict-free ds_re
 // V is staged TRANSPOSED, Vt[head dim][key] with pitch SP + 4: accumulator registers 4g .. 4g+3 of a probability tile
 // are keys 32t + 8g + 4*half + 0..3, so the matching A operands of four consecutive PV MFMAs are one ds_read_b128
 constexpr int LDO = 33;  // pitch of the output transpose scratch
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct AttnP {
     const float* q; const float* k; const float* v; long ld; const unsigned char* mask;

@@ -25,7 +25,6 @@ namespace {
 
 constexpr int KP = 40;                    // K image pitch in bf16 (80 bytes: 16 x an odd number -> conflict-free b128 over 16 lanes)
 constexpr int LDO = 33;                   // pitch of the output transpose scratch (floats)
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct SpAttnP {
     const float* q; const float* k; const float* v; long ld;

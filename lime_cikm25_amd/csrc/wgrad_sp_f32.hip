@@ -9,7 +9,7 @@
 // 64 bytes apart modulo the bank width, so the four lane groups of a fragment read hit disjoint banks.
 //
 // One eight-wave workgroup per CU: tile 256 (n) x 320 (k) of dW over one slice of the M rows (the slices' partial tiles are summed
-// in a fixed order by reduce_partials_kernel: backward_f32.hip); wave w owns rows 64 (w & 3) of n and the k half w >> 2
+// in a fixed order by reduce_partials_kernel: wgrad_f32.hip); wave w owns rows 64 (w & 3) of n and the k half w >> 2
 // (4 x 10 accumulator tiles, 160 registers), as in gemm_sp_f32.hip.  A ones column appended to X (column K of the tile, patched
 // into the LDS image) makes column K of dW the bias gradient.  Shapes whose K pads badly (K = 512 against N = 300) are run
 // transposed by the dispatcher (the roles of dY and X swapped, the reduction writes dW^T back transposed).

@@ -1,4 +1,4 @@
-"""Diagnostic: where does token_attn_bwd_kernel spend its time?  Builds variants of backward_f32.hip with phases removed
+"""Diagnostic: where does token_attn_bwd_kernel spend its time?  Builds variants of token_attn_train_f32.hip with phases removed
 (-DLIME_ATTN_BWD_ABLATE=mask: 1 no global staging, 2 no S / dP MFMAs, 4 no softmax, 8 no dV, 16 no dQ / dK, 32 no stores) and
 times the body (S = 128) and title (S = 32) shapes.  64: the S / dP MFMAs run on register operands (no K / V fragment reads).
 
@@ -19,9 +19,9 @@ MASKS = [0, 2, 64, 4 | 8 | 16, 4 | 8 | 16 | 64, 2 | 4 | 8 | 16]
 def build(mask):
     so = os.path.join(ROOT, 'tools', 'probes', 'liblime_attn_bwd_%d.so' % mask)
     src = os.path.join(ROOT, 'lime_cikm25_amd', 'csrc')
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(src, 'backward_f32.hip')):
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(src, 'token_attn_train_f32.hip')):
         subprocess.run(['hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-shared',
-                        '-DLIME_ATTN_BWD_ABLATE=%d' % mask, '-o', so, os.path.join(src, 'backward_f32.hip'),
+                        '-DLIME_ATTN_BWD_ABLATE=%d' % mask, '-o', so, os.path.join(src, 'token_attn_train_f32.hip'),
                         os.path.join(src, 'common.cpp')], check=True)
     return so
 
