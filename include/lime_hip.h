@@ -903,6 +903,48 @@ int lime_negative_sample(const int64_t* offsets, const int32_t* neg_index, const
                          float* cand_freshness, float* cand_lifetime, int64_t N, int32_t K, uint64_t seed, uint32_t epoch,
                          int32_t inclusive, void* stream);
 
+/* =====================================================================================================
+ * One time step of a bidirectional single-layer LSTM (csrc/lstm_f32.hip): the recurrence of the CNE content encoder
+ * (newsEncoders.py:439-532: nn.LSTM(bidirectional=True) under pack_padded_sequence).  nn.LSTM's cell and parameter layout as stored:
+ * gate order i, f, g, o; whh = [weight_hh_l0; weight_hh_l0_reverse], [2, 4h, h].  R sequences of T token slots, sequence r runs over
+ * its FIRST len[r] slots (len is clamped into [0, T]).
+ *   gi [R T, >= 2 . 4h] (leading dimension ldgi): x_t W_ih^T + b_ih + b_hh of every token, forward gates in columns [0, 4h), backward
+ *   in [4h, 8h) -- one lime_linear_f32 launch over the two W_ih stacked row-wise, ahead of the time loop.
+ * Step `step` (the caller launches step = 0 .. T - 1 in order on one stream), both directions in one launch: sequence r is active iff
+ * step < len[r]; forward works on token t = step, backward on token t = len[r] - 1 - step:
+ *     pre   = gi[r T + t, direction] + W_hh h_prev         h_prev = hout[r T + t - 1, :h] (forward) / hout[r T + t + 1, h:] (backward),
+ *                                                            zero at step 0 (nothing is read then, neither hout nor c)
+ *     i, f, o = sigmoid(pre_i, pre_f, pre_o), g = tanh(pre_g);   c' = f c + i g;   hout[r T + t, direction] = o tanh(c')
+ *   c [2, R, h] is updated in place (after step T - 1 it is c_n of both directions; h_n is hout at token len - 1 / token 0).
+ *   Inactive sequences are left untouched; the caller zeroes hout once, so the rows behind a length stay zero (pad_packed_sequence).
+ *   n_rows_dev (optional DEVICE int): only the first min(*n_rows_dev, R) sequences are worked on (R stays the capacity: c's stride).
+ *   gates [R T, 2 . 4h], c_seq [R T, 2h], h_prev [R T, 2h] (all three or none): what lime_lstm_step_bwd_f32 needs -- the four gate
+ *   activations, c_t and the h_{t-1} the step read (zero for a direction's first token: NOT hout shifted by one row).
+ * h must be a multiple of 16 (a workgroup owns 64 sequences x 16 units with all four gates; v_mfma_f32_16x16x4_f32), every pointer
+ * 16-byte aligned.  A (sequence, unit) result is a fixed-order sum: its bits do not depend on R, the sequence's position, n_rows_dev.
+ *
+ * lime_lstm_step_bwd_f32: the gate gradients of step `step` (the caller runs step = T - 1 .. 0).  dh [2, R, h] is the gradient carried
+ * through W_hh (zeros at the start), dc [2, R, h] the cell carry (d c_n at the start, updated in place); dhout [R T, lddh >= 2h] (or
+ * NULL) is added at the step that produced the row.  Writes the pre-activation gradients to dgi [R T, 2 . 4h] (layout of gi, dense)
+ * and to dgs [2, R, 4h] (this step's rows, zeros for inactive sequences); the next carry is dh[d] = dgs[d] . W_hh[d], one
+ * lime_linear_group_f32 launch by the caller.  Inactive sequences keep their dc; their dh stays zero.
+ *
+ * lime_mask_lengths: len[r] = max(#non-zero bytes of mask[r, :T], min_len).
+ *
+ * lime_gate_mul_f32 (dense [rows, cols] fp32, cols a multiple of 4; min(*n_rows_dev, rows) rows when n_rows_dev is given):
+ *   mode 0: out = x * sigmoid(g) (out == g allowed) -- CNE's cross-selective gate applied to the LSTM output (newsEncoders.py:517-521)
+ *   mode 1: out[r] = x[r] * g[r / div] * scale -- the scaled-dot-product scores of :527-528 as the summands h_t (K^T q) / sqrt(A),
+ *                                                 which lime_additive_pool_f32 sums (affine2 = ones), masks, soft-maxes and pools. */
+int lime_lstm_step_f32(const float* gi, int64_t ldgi, const float* whh, const int32_t* len, float* hout, float* c, float* gates,
+                       float* c_seq, float* h_prev, int32_t R, int32_t T, int32_t h, int32_t step, const int32_t* n_rows_dev,
+                       void* stream);
+int lime_lstm_step_bwd_f32(const float* dhout, int64_t lddh, const float* gates, const float* c_seq, const int32_t* len,
+                           const float* dh, float* dc, float* dgi, float* dgs, int32_t R, int32_t T, int32_t h, int32_t step,
+                           void* stream);
+int lime_mask_lengths(const uint8_t* mask, int32_t R, int32_t T, int32_t min_len, int32_t* len, void* stream);
+int lime_gate_mul_f32(const float* x, const float* g, float* out, int64_t rows, int32_t cols, int32_t div, int32_t mode, float scale,
+                      const int32_t* n_rows_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -304,6 +304,13 @@ SIGNATURES = {
     # the epoch's negative sampling from the resident CSR of every train record's non-clicked news
     'lime_negative_sample': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int32, c_uint64, c_uint32, c_int32, c_void_p]),
+    # CNE content encoder: one step of the bidirectional LSTM, its backward step, mask -> lengths
+    'lime_lstm_step_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                     c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'lime_lstm_step_bwd_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_int32, c_int32, c_int32, c_void_p]),
+    'lime_mask_lengths': (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'lime_gate_mul_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

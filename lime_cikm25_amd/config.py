@@ -51,6 +51,7 @@ _DEFAULTS = dict(
     cnn_method='naive',                   # config.py:86
     cnn_kernel_num=400,                   # config.py:87
     cnn_window_size=3,                    # config.py:88
+    hidden_dim=400,                       # config.py:98 (CNE: the bidirectional LSTMs' hidden size per direction)
     category_embedding_dim=50,            # config.py:91
     subCategory_embedding_dim=50,         # config.py:92
     user_embedding_dim=50,                # config.py:90

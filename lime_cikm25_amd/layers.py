@@ -190,3 +190,39 @@ class Conv1D(nn.Module):
 
     def forward(self, feature):
         raise NotImplementedError('Conv1D is a parameter holder: the CNN encoder runs ops.conv1d_window')
+
+
+class LSTMHolder(nn.LSTM):
+    """nn.LSTM as a parameter holder (newsEncoders.py:449-450: one bidirectional layer, batch_first): the reference's parameter names and
+    layout (weight_ih_l0 [4h, E], weight_hh_l0 [4h, h], the two biases, and the same four with ``_reverse``; gate order i, f, g, o).  The
+    recurrence runs on the LSTM step kernel (ops.lstm); ``forward`` is never used on the HIP path."""
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError('LSTMHolder is a parameter holder: the CNE encoder runs ops.lstm (csrc/lstm_f32.hip)')
+
+
+class LinearHolder(nn.Linear):
+    """nn.Linear as a parameter holder of the CNE encoder (its GEMMs run on ops.linear with the gate arithmetic fused or behind them)."""
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError('LinearHolder is a parameter holder: the CNE encoder runs ops.linear')
+
+
+class ScaledDotProduct_CandidateAttention(nn.Module):
+    """layers.py:334-359, parameter holder: a_t = K(feature_t) . Q(query) / sqrt(attention_dim), masked with -1e9, softmax, weighted sum
+    of the features.  K has no bias, Q has one.  K(h_t) . q = h_t . (K^T q), so the CNE encoder computes one vector K^T q per sequence
+    and pools with it (newsEncoders.CNE)."""
+
+    def __init__(self, feature_dim, query_dim, attention_dim):
+        super().__init__()
+        self.K = LinearHolder(feature_dim, attention_dim, bias=False)
+        self.Q = LinearHolder(query_dim, attention_dim, bias=True)
+        self.attention_scalar = math.sqrt(float(attention_dim))
+
+    def initialize(self):
+        nn.init.xavier_uniform_(self.K.weight)
+        nn.init.xavier_uniform_(self.Q.weight)
+        nn.init.zeros_(self.Q.bias)
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError('ScaledDotProduct_CandidateAttention is a parameter holder: the CNE encoder runs its pooling kernels')

@@ -1,4 +1,4 @@
-"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA}-{CROWN,ATT,MHSA} scoring path (reference model.py:11-187)."""
+"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE}-{CROWN,ATT,MHSA} scoring path (reference model.py:11-187)."""
 import torch
 import torch.nn as nn
 
@@ -12,6 +12,9 @@ _USED = (1, 2, 3, 4, 6, 9, 10, 11, 15, 16, 17, 18, 20, 23, 24, 25)
 # (candidate tensor, history tensor) pairs the news encoder concatenates: title_text, title_mask, content_text, category,
 # subCategory, freshness, user_topic_lifetime
 _PAIRS = ((17, 3), (18, 4), (20, 6), (15, 1), (16, 2), (23, 9), (24, 10))
+# a content encoder that reads the body masks (CNE) adds user_content_mask / news_content_mask and their pair
+_USED_BODY_MASK = tuple(sorted(_USED + (7, 21)))
+_PAIRS_BODY_MASK = _PAIRS + ((21, 7),)
 
 
 _USER_ENCODERS = ('CROWN', 'ATT', 'MHSA')
@@ -28,7 +31,7 @@ class Model(nn.Module):
     """Same constructor, attributes (``model_name``, ``config``, ``news_encoder``, ``user_encoder``,
     ``news_embedding_dim``), ``initialize()`` and 26-tensor ``forward`` as the reference's Model
     (model.py:12-187); ``state_dict()`` has the reference's key set.  ``forward`` returns logits [B, N].
-    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3') or 'MHSA';
+    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3'), 'MHSA' or 'CNE';
     ``config.user_encoder`` the user encoder: 'CROWN', 'ATT' (NAML's additive attention) or 'MHSA' (NRMS's self-attention), in any
     pairing.
 
@@ -57,6 +60,8 @@ class Model(nn.Module):
             base_encoder = newsEncoders.NAML(config)
         elif config.content_encoder == 'MHSA':
             base_encoder = newsEncoders.MHSA(config)
+        elif config.content_encoder == 'CNE':
+            base_encoder = newsEncoders.CNE(config)
         else:
             raise NotImplementedError('content_encoder %r is a baseline outside the scoring path' % config.content_encoder)
         self.news_encoder = newsEncoders.LIME(config=config, base_news_encoder=base_encoder)
@@ -74,6 +79,10 @@ class Model(nn.Module):
         self.remaining_lifetime_weighting = RemainingLifetimeWeighting(config)
         self.use_graph = True
         self._graphs = {}
+        # the inputs the captured graph copies in, per model: the body masks only where the content encoder reads them
+        self.reads_content_mask = bool(getattr(base_encoder, 'reads_content_mask', False))
+        self._used = _USED_BODY_MASK if self.reads_content_mask else _USED
+        self._pairs = _PAIRS_BODY_MASK if self.reads_content_mask else _PAIRS
 
     def _apply(self, fn, *args, **kwargs):
         self._graphs = {}                      # parameter storage moves: captured pointers are stale
@@ -102,19 +111,22 @@ class Model(nn.Module):
             return training.forward_train(self, user_category, user_subCategory, user_title_text, user_title_mask,
                                           user_content_text, user_freshness, user_user_topic_lifetime, user_history_mask,
                                           news_category, news_subCategory, news_title_text, news_title_mask, news_content_text,
-                                          news_freshness, news_user_topic_lifetime, remaining_lifetime)
+                                          news_freshness, news_user_topic_lifetime, remaining_lifetime,
+                                          user_content_mask=user_content_mask if self.reads_content_mask else None,
+                                          news_content_mask=news_content_mask if self.reads_content_mask else None)
         if (self.use_graph and ops.PROFILE is None and user_category.is_cuda
                 and not torch.cuda.is_current_stream_capturing()):
             return self._forward_graphed(args)
         return self._forward_impl(*args)
 
     def _forward_graphed(self, args):
+        _USED = self._used
         used = [args[i] for i in _USED]
         key = (self.training,) + tuple((tuple(t.shape), t.dtype) for t in used)
         entry = self._graphs.get(key)
         if entry is None:
             static = list(args)
-            for i, t in zip(_USED, self._packed_like(args)):
+            for i, t in zip(_USED, self._packed_like(args, _USED, self._pairs)):
                 static[i] = t
             ops.multi_copy([(static[i], args[i]) for i in _USED])
             with torch.no_grad():
@@ -132,7 +144,7 @@ class Model(nn.Module):
         return out.clone()
 
     @staticmethod
-    def _packed_like(args):
+    def _packed_like(args, _USED=_USED, _PAIRS=_PAIRS):
         """Static input buffers for the graph: ONE allocation, with every candidate tensor directly in front of its
         history counterpart (news_title_text | user_title_text, ...) so that the encoder's `cat` of the two groups is a
         view of the buffer instead of a copy kernel (newsEncoders.LIME.encode_many)."""
@@ -161,7 +173,7 @@ class Model(nn.Module):
     def score_impressions(self, user_category, user_subCategory, user_title_text, user_title_mask, user_content_text,
                           user_freshness, user_user_topic_lifetime, user_history_mask, news_category, news_subCategory,
                           news_title_text, news_title_mask, news_content_text, news_freshness, news_user_topic_lifetime,
-                          remaining_lifetime, n_src=None, rows_per_pass=16384):
+                          remaining_lifetime, n_src=None, rows_per_pass=16384, user_content_mask=None, news_content_mask=None):
         """Scoring-only layout of BASELINE config 5: B impressions with K candidates each -> logits [B, K] with the
         reference's EVAL semantics (util.py:86-111: every (impression, candidate) pair is its own row with N = 1, Q16),
         but every history is encoded ONCE instead of once per candidate.
@@ -171,9 +183,32 @@ class Model(nn.Module):
         rows of the forward, i.e. its eval batch size (Q7); default: B * K capped at H + config.batch_size, which is what
         one reference forward over all pairs would use.  The result equals ``forward`` in eval mode on the B * K expanded
         rows (tested), the history encoder just runs B * H instead of B * K * H times.
+        ``user_content_mask`` [B, H, L] / ``news_content_mask`` [B, K, L]: the body masks, for a content encoder that reads them (CNE).
+        Under CNE a history's encoding is NOT a function of the history alone -- the reference gates every text with the memory vector
+        of the news at the same length-sorted position of the encoder call (newsEncoders.CNE) -- so nothing can be shared between the
+        K candidates of an impression: the B * K expanded rows go through the eval forward as they are, in one pass.
         """
         B, K = news_category.shape
         H = user_category.shape[1]
+        if self.reads_content_mask:
+            if user_content_mask is None or news_content_mask is None:
+                raise TypeError('the CNE content encoder reads the body masks (user_content_mask, news_content_mask): pass them -- '
+                                'a body mask is never guessed from the ids')
+            if self.training:
+                raise RuntimeError('score_impressions is the eval-mode function: call model.eval() first')
+            rows = lambda t: t.reshape((B * K,) + tuple(t.shape[2:]))                        # candidate tensors without the N axis
+            rep = lambda t: t.repeat_interleave(K, dim=0)                                    # the impression's history, once per candidate
+            if news_user_topic_lifetime.dim() == 1:
+                news_user_topic_lifetime = news_user_topic_lifetime.unsqueeze(1).expand(B, K)
+            if news_freshness.dim() == 1:
+                news_freshness = news_freshness.unsqueeze(1).expand(B, K)
+            logits = self._forward_impl(None, rep(user_category), rep(user_subCategory), rep(user_title_text), rep(user_title_mask), None,
+                                        rep(user_content_text), rep(user_content_mask), None, rep(user_freshness),
+                                        rep(user_user_topic_lifetime), rep(user_history_mask), None, None, None, rows(news_category),
+                                        rows(news_subCategory), rows(news_title_text), rows(news_title_mask), None,
+                                        rows(news_content_text), rows(news_content_mask), None, rows(news_freshness.contiguous()),
+                                        rows(news_user_topic_lifetime.contiguous()), rows(remaining_lifetime))
+            return logits.view(B, K)
         ne, ue = self.news_encoder, self.user_encoder
         if news_user_topic_lifetime.dim() == 1:
             news_user_topic_lifetime = news_user_topic_lifetime.unsqueeze(1).expand(B, K)
@@ -208,8 +243,14 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def build_news_cache(self, device_corpus, rows_per_pass=8192):
-        """Content cache for ``score_behaviors``: every news of a ``DeviceCorpus`` through the token encoders ONCE."""
+        """Content cache for ``score_behaviors``: every news of a ``DeviceCorpus`` through the token encoders ONCE.
+
+        Under CNE no part of LIME's representation that this cache could hold depends on the news alone (the gates read the memory
+        vector of the news at the same length-sorted position of the encoder call, newsEncoders.CNE): the cache is an empty
+        [n_news, 0] tensor and ``score_behaviors`` encodes the rows' news as the uncached forward does."""
         c = device_corpus
+        if self.reads_content_mask:
+            return torch.empty((c.news_title_text.shape[0], 0), dtype=torch.float32, device=c.news_title_text.device)
         return self.news_encoder.build_content_cache(c.news_title_text, c.news_title_mask, c.news_abstract_text, c.news_category,
                                                      c.news_subCategory, rows_per_pass=rows_per_pass)
 
@@ -218,15 +259,15 @@ class Model(nn.Module):
         """Scores of the (impression, candidate) rows `rows` of a dev / test ``DeviceBehaviors`` -- the function of
         util.compute_scores' forward (util.py:86-111, eval mode, N = 1 per row) -- from the news cache: no token encoder
         runs, the history and the candidate of a row are looked up by news index and only their freshness half, the user
-        encoder and the match are computed.  ``n_src`` as in score_impressions (default: the number of rows, capped)."""
+        encoder and the match are computed.  ``n_src`` as in score_impressions (default: the number of rows, capped).
+        Under CNE (an empty cache, ``build_news_cache``) the rows' batch goes through the eval forward instead: a dev / test split and
+        a model in eval mode."""
         b = behaviors
         dev = news_cache.device
         rows = torch.as_tensor(rows, device=dev).long().reshape(-1)
         R, H = rows.numel(), b.hist_index.shape[1]
         ne, ue, c = self.news_encoder, self.user_encoder, b.corpus
         hist_idx, cand_idx = b.hist_index[rows], b.cand_index[rows]                       # [R, H], [R, 1]
-        hist = ne.encode_cached(news_cache, hist_idx, b.user_freshness[rows], b.user_lifetime[rows]).view(R, H, -1)
-        cand = ne.encode_cached(news_cache, cand_idx, b.cand_freshness[rows], b.cand_lifetime[rows]).view(R, 1, -1)
         flat_h, flat_c = hist_idx.reshape(-1).long(), cand_idx.reshape(-1).long()
         # the remaining lifetime per config.lifetime_type, as util.py:98-106 derives it from the batch
         lt = getattr(self.config, 'lifetime_type', 'user_topic')
@@ -239,6 +280,11 @@ class Model(nn.Module):
             remaining = (b.cand_lifetime[rows] - b.cand_freshness[rows])
         else:
             raise ValueError('Invalid lifetime_type')
+        if self.reads_content_mask:
+            # CNE: the rows' batch through the eval forward (see build_news_cache) -- the scores of util.compute_scores over these rows
+            return self._forward_impl(*b.assemble(rows), remaining.view(R)).view(R)
+        hist = ne.encode_cached(news_cache, hist_idx, b.user_freshness[rows], b.user_lifetime[rows]).view(R, H, -1)
+        cand = ne.encode_cached(news_cache, cand_idx, b.cand_freshness[rows], b.cand_lifetime[rows]).view(R, 1, -1)
         if n_src is None and hasattr(ue, 'user_node_embedding'):
             n_src = min(R, H + ue.user_node_embedding.shape[0])
         _, logits = ue.match(hist, c.news_category[flat_c].view(R, 1), c.news_subCategory[flat_c].view(R, 1),
@@ -257,9 +303,13 @@ class Model(nn.Module):
             news_title_text = news_title_text.unsqueeze(1)
             news_title_mask = news_title_mask.unsqueeze(1)
             news_content_text = news_content_text.unsqueeze(1)
+            if self.reads_content_mask:
+                news_content_mask = news_content_mask.unsqueeze(1)
             news_freshness = news_freshness.unsqueeze(1)
             news_user_topic_lifetime = news_user_topic_lifetime.unsqueeze(1)
             remaining_lifetime = remaining_lifetime.unsqueeze(1)
+        if not self.reads_content_mask:
+            news_content_mask = user_content_mask = None
         with torch.no_grad():
             # candidate-aware attention weights depend on topic ids and the history mask only: side stream, joined below
             main = torch.cuda.current_stream()
@@ -270,9 +320,9 @@ class Model(nn.Module):
                                                           user_history_mask)
             news_representation, history_embedding = self.news_encoder.encode_many([
                 (news_title_text, news_title_mask, news_content_text, news_category, news_subCategory, news_freshness,
-                 news_user_topic_lifetime),                                      # model.py:171-173
+                 news_user_topic_lifetime, news_content_mask),                   # model.py:171-173
                 (user_title_text, user_title_mask, user_content_text, user_category, user_subCategory, user_freshness,
-                 user_user_topic_lifetime)])                                     # userEncoders.py:110-112
+                 user_user_topic_lifetime, user_content_mask)])                  # userEncoders.py:110-112
             main.wait_stream(side2)
             _, logits = self.user_encoder.match(history_embedding, news_category, news_subCategory, user_category,
                                                 user_subCategory, user_history_mask, news_representation,

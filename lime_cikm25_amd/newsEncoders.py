@@ -1,5 +1,5 @@
-"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN, NAML and MHSA
-(reference newsEncoders.py:38-161, 167-373, 535-563, 566-595, 641-695, 806-828).
+"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN, NAML, MHSA and CNE
+(reference newsEncoders.py:38-161, 167-373, 439-532, 535-563, 566-595, 641-695, 806-828).
 
 The modules keep the reference's attribute and parameter names, so ``state_dict()`` has the same
 183 keys and reference checkpoints load.  Standard torch containers
@@ -22,7 +22,7 @@ import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from . import ops
-from .layers import Attention, Conv1D, MultiHeadAttention
+from .layers import Attention, Conv1D, LinearHolder, LSTMHolder, MultiHeadAttention, ScaledDotProduct_CandidateAttention
 
 # tokens encoded per pass of the token encoder: bounds the activation workspace (9.2 KB / token)
 MAX_TOKENS_PER_PASS = 4 * 1024 * 1024
@@ -260,8 +260,18 @@ class LIME(nn.Module):
         nn.init.xavier_uniform_(self.category_affine.weight)
         nn.init.zeros_(self.category_affine.bias)
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, freshness, lifetime):
-        """Flat batch of M news -> [M, output_dim].  title_text [M, T], content_text [M, L] int32; the rest [M]."""
+    def _base_encode(self, title_text, title_mask, content_text, category, subCategory, out, content_mask, pair_groups=None):
+        """The content encoder's encode_flat; the body mask (and the reference calls' news counts) go to the encoder that reads them
+        (CNE) and to no other."""
+        enc = self.base_news_encoder
+        if getattr(enc, 'reads_content_mask', False):
+            return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out, content_mask, pair_groups)
+        return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out)
+
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None,
+                    pair_groups=None):
+        """Flat batch of M news -> [M, output_dim].  title_text [M, T], content_text [M, L] int32; the rest [M].  content_mask [M, L]:
+        the body mask, read by the CNE content encoder alone."""
         M = title_text.shape[0]
         cdim = self.base_news_encoder.news_embedding_dim
         main = torch.cuda.current_stream()
@@ -271,7 +281,7 @@ class LIME(nn.Module):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self.freshness_encoder.encode_flat(freshness, lifetime, fused[:, cdim:])
-            self.base_news_encoder.encode_flat(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim])
+            self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups)
             main.wait_stream(side)
             gate = ops.linear(fused, self.gate.weight, self.gate.bias, act='sigmoid') if self.fusion_method == 'gated' else None
             return ops.fuse_rows(fused[:, :cdim], fused[:, cdim:], gate)
@@ -280,7 +290,7 @@ class LIME(nn.Module):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self.freshness_encoder.encode_flat(freshness, lifetime, fused[:, cdim:])
-            self.base_news_encoder.encode_flat(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim])
+            self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups)
             main.wait_stream(side)
             return fused
         # project(cat(content, fresh)) = content W_c^T + (fresh W_f^T + b), and fresh = tanh(dense(cat(E_f[b1], E_l[b2]))) takes one of
@@ -294,7 +304,7 @@ class LIME(nn.Module):
             pair = torch.add(fe.buckets(lifetime), fe.buckets(freshness), alpha=nb)                        # b_f * nb + b_l, int32 [M]
             table, _ = self.occurrence_tables()                                                           # [nb^2, final_dim]
         content = torch.empty((M, cdim), dtype=torch.float32, device=title_text.device)
-        self.base_news_encoder.encode_flat(title_text, title_mask, content_text, category, subCategory, content)
+        self._base_encode(title_text, title_mask, content_text, category, subCategory, content, content_mask, pair_groups)
         main.wait_stream(side)
         return ops.linear(content, self.project.weight[:, :cdim], None, res=table, res_ids=pair)         # newsEncoders.py:152-153
 
@@ -376,11 +386,15 @@ class LIME(nn.Module):
     def encode_many(self, groups):
         """Encode several [B, n, ...] groups (candidates, history) in ONE pass over the kernels.
 
-        Each group: (title_text, title_mask, content_text, category, subCategory, freshness, lifetime).
+        Each group: (title_text, title_mask, content_text, category, subCategory, freshness, lifetime[, content_mask]) -- the optional
+        eighth member is the body mask, which the CNE content encoder reads (every group carries it then, or none does).
         Returns one [B, n, output_dim] tensor per group.
         """
-        shapes, flat = [], [[] for _ in range(7)]
-        for (tt, tm, ct, cat, sub, fr, lt) in groups:
+        shapes, flat, cmasks = [], [[] for _ in range(7)], []
+        for group in groups:
+            tt, tm, ct, cat, sub, fr, lt = group[:7]
+            if len(group) > 7 and group[7] is not None:
+                cmasks.append(group[7].reshape(tt.shape[0] * tt.shape[1], -1))
             B, n = tt.shape[0], tt.shape[1]
             shapes.append((B, n))
             if fr.dim() == 1:
@@ -393,7 +407,11 @@ class LIME(nn.Module):
                                      _i32(cat).reshape(-1), _i32(sub).reshape(-1), fr.float().reshape(-1), lt.float().reshape(-1))):
                 dst.append(t)
         cat_all = [t[0].contiguous() if len(t) == 1 else _cat_rows(t) for t in flat]
-        out = self.encode_flat(*cat_all)
+        if cmasks and len(cmasks) != len(groups):
+            raise ValueError('encode_many: the body mask must be given for every group or for none')
+        cmask = None if not cmasks else (cmasks[0].contiguous() if len(cmasks) == 1 else _cat_rows(cmasks))
+        # each group is one call of the reference's news encoder (model.py:171, userEncoders.py:110): CNE pairs its gates per call
+        out = self.encode_flat(*cat_all, content_mask=cmask, pair_groups=[B * n for B, n in shapes] if cmask is not None else None)
         res, r0 = [], 0
         for (B, n) in shapes:
             res.append(out[r0:r0 + B * n].view(B, n, -1))
@@ -412,10 +430,12 @@ class LIME(nn.Module):
             lt = lt.unsqueeze(1) if lt.dim() == 1 else lt
             lt = lt.expand_as(fr) if lt.shape != fr.shape else lt
             rep = training.news_flat(self, *_flat_inputs(title_text, title_mask, content_text, category, subCategory),
-                                     fr.float().reshape(-1).contiguous(), lt.float().reshape(-1).contiguous())
+                                     fr.float().reshape(-1).contiguous(), lt.float().reshape(-1).contiguous(),
+                                     content_mask=None if content_mask is None else content_mask.reshape(B * n, -1).contiguous(),
+                                     pair_groups=[B * n])
             return rep.view(B, n, -1)
         return self.encode_many([(title_text, title_mask, content_text, category, subCategory, news_freshness,
-                                  news_user_topic_lifetime)])[0]
+                                  news_user_topic_lifetime, content_mask)])[0]
 
 
 class NewsEncoder(nn.Module):
@@ -438,6 +458,8 @@ class NewsEncoder(nn.Module):
         self.auxiliary_loss = None
         self.affine = nn.Linear(config.word_embedding_dim, config.word_embedding_dim, bias=True)   # unused upstream too
 
+    reads_content_mask = False      # True: encode_flat needs the body mask (CNE alone)
+
     def initialize(self):
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
         nn.init.uniform_(self.subCategory_embedding.weight, -0.1, 0.1)
@@ -449,11 +471,15 @@ class NewsEncoder(nn.Module):
                 user_embedding, news_freshness=None, news_user_topic_lifetime=None):
         B, n = title_text.shape[0], title_text.shape[1]
         flat = _flat_inputs(title_text, title_mask, content_text, category, subCategory)
+        cmask = content_mask.reshape(B * n, -1).contiguous() if (self.reads_content_mask and content_mask is not None) else None
         from . import training
         if training.wants_train_path(self, self.dropout_rate):
-            return training.content_flat(self, *flat).view(B, n, -1)
+            return training.content_flat(self, *flat, content_mask=cmask, pair_groups=[B * n]).view(B, n, -1)
         out = torch.empty((B * n, self.news_embedding_dim), dtype=torch.float32, device=title_text.device)
-        self.encode_flat(*flat, out)
+        if self.reads_content_mask:
+            self.encode_flat(*flat, out, content_mask=cmask, pair_groups=[B * n])      # one call of the reference's encoder
+        else:
+            self.encode_flat(*flat, out)
         return out.view(B, n, -1)
 
 
@@ -876,7 +902,7 @@ class CROWN(NewsEncoder):
             nn.init.zeros_(intent_layer.bias)
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out):
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None):
         """M news -> out [M, 900] (out may be a column slice of a wider buffer).  The token masks are computed and never
         used by the reference (:307-308); title_mask is accepted and ignored."""
         _no_train_dropout(self, self.dropout_rate)
@@ -1030,7 +1056,7 @@ class MHSA(NewsEncoder):
         self.attention.initialize()
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out):
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None):
         _no_train_dropout(self, self.dropout_rate)
         M, T = title_text.shape
         F = self.feature_dim
@@ -1117,7 +1143,7 @@ class CNN(NewsEncoder):
         ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', m_dev=_row_count(n * T, dev), out=hidden)
         ops.additive_pool(hidden[:n * T], a2, c[:n * T], n, T, mask=mask, out=out)                                      # :558
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out):
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None):
         _no_train_dropout(self, self.dropout_rate)
         M, T = title_text.shape
         K = self.cnn_kernel_num
@@ -1214,7 +1240,7 @@ class NAML(NewsEncoder):
                       m_dev=_row_count(n * T, dev))                                                                    # :686-687
         ops.gather_rows(_identity_rows(n, dev), pooled, out)
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out):
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None):
         _no_train_dropout(self, self.dropout_rate)
         M, T = title_text.shape
         L = content_text.shape[1]
@@ -1240,4 +1266,204 @@ class NAML(NewsEncoder):
                    a_ids=_i32(subCategory).reshape(-1).contiguous(), out=views[:, 3])                            # :690
         ops.attn_pool(views.view(M * 4, K), self.affine1.weight, self.affine1.bias, self.affine2.weight.view(-1), M, 4, out=out,
                       w1p=w1p[2])                                                                                # :692-694
+        return out
+
+
+_ONES = {}
+
+
+def _ones(n, device):
+    """n ones (fp32), allocated once per device and never written."""
+    return _grown(_ONES, n, device, 1024, lambda size: torch.ones(size, dtype=torch.float32, device=device))
+
+
+class CNE(NewsEncoder):
+    """newsEncoders.py:439-532, the collaborative news encoder of CNE-SUE: title and body each through a bidirectional LSTM, cross-selective
+    gates (each text's LSTM output gated by the OTHER text's memory vector), a masked additive self attention and a scaled-dot-product
+    cross attention whose query is the other text's self-attention output.  -> [B, n, 4 hidden_dim + 100].
+
+    The recurrence is the LSTM step kernel (csrc/lstm_f32.hip, ops.lstm): the input projection of every token and both directions is
+    one GEMM with the word rows gathered into its A operand, then one launch per time step.  The gates are a GEMM with the memory term
+    as a broadcast residual and ops.gate_mul; the attentions are linear(tanh) / gate_mul + additive_pool.
+
+    Reference behaviour kept:
+      * mask slot 0 (:492-493): title_mask[:, 0] = content_mask[:, 0] = 1, so every length is >= 1 and an all-padding text runs one
+        step on word row 0.  Applied to COPIES here; the reference edits the caller's tensors in place.
+      * lengths and masks (:494-495, :503-504, :524-528): the length is the SUM of the mask, the LSTM runs over the FIRST `length` token
+        slots (pack_padded_sequence), the attentions mask by the mask's own positions.  The two agree for prefix masks.
+      * h is zero behind the length (pad_packed_sequence, :514-515); the memory vector is cat(c_n forward, c_n backward) (:512-513).
+      * each gate reads the other text's memory vector (:517-518), each cross attention the other text's self attention (:527-528).
+      * WHICH news' memory vector a gate reads (:496-499, :517-521): the reference sorts the titles by title length and the bodies by
+        body length, each for its own pack_padded_sequence, and applies the gates in SORTED order before it undoes the sorts -- the
+        title at sorted position j is gated by the body memory at sorted position j, which belongs to another news unless the two
+        orders agree.  The partner of a news therefore depends on every length in the call.  ``pair_groups`` (the news counts of the
+        reference's calls: candidates, history) reproduces it, TIED lengths in input order (the reference leaves their order to the torch build)
+        (``reference_pairs``; the goldens pin it).  ``encode_flat`` without ``pair_groups`` gives the encoder as published: every news
+        reads its OWN other text's memory vector.  A paired pass shares nothing between news, so CNE has no compacted form.
+      * category_embedding is re-created (:447) and trains; subCategory_embedding stays frozen.
+      * dropout acts on both word-embedding gathers (:501-502) and in feature_fusion (training path: training.cne_content).
+
+    The body mask is required: a missing one raises TypeError (it is never guessed from the ids).  hidden_dim must be a multiple of 16
+    (ops.LSTM_UNIT_TILE: a workgroup of the step kernel owns 16 hidden units with their four gates); fp32 only.
+
+    Memory: gi is 2 . 4 hidden_dim floats per token (12.8 KB at hidden_dim 400; MAX_TOKENS_PER_PASS would allow 51 GB), so the recurrence
+    runs in chunks of news whose gi stays within GI_BYTES_PER_PASS (``lstm_chunks``).  hout and c_n of all chunks are kept (2 hidden_dim
+    floats per token), and the gates pair over the whole call: a call has no size limit but memory."""
+
+    GI_BYTES_PER_PASS = 4 << 30
+    reads_content_mask = True
+
+    def __init__(self, config):
+        super().__init__(config)
+        if getattr(config, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError("compute_dtype %r: the CNE content encoder is built for fp32 (compute_dtype='fp32')" % config.compute_dtype)
+        h = config.hidden_dim
+        if h <= 0 or h % ops.LSTM_UNIT_TILE:
+            raise NotImplementedError('hidden_dim %d: the LSTM step kernel is built for multiples of %d' % (h, ops.LSTM_UNIT_TILE))
+        if config.word_embedding_dim % 4 or config.attention_dim % 4:
+            raise NotImplementedError('the CNE encoder needs multiples of 4 for word_embedding_dim and attention_dim')
+        self.max_title_length = config.max_title_length
+        self.max_content_length = config.max_abstract_length
+        self.hidden_dim = h
+        self.news_embedding_dim = 4 * h + config.category_embedding_dim + config.subCategory_embedding_dim          # :446
+        self.category_embedding = nn.Embedding(config.category_num, config.category_embedding_dim)                  # trainable (re-created, :447)
+        E = config.word_embedding_dim
+        self.title_lstm = LSTMHolder(E, h, batch_first=True, bidirectional=True)
+        self.content_lstm = LSTMHolder(E, h, batch_first=True, bidirectional=True)
+        self.title_H = LinearHolder(2 * h, 2 * h, bias=False)
+        self.title_M = LinearHolder(2 * h, 2 * h, bias=True)
+        self.content_H = LinearHolder(2 * h, 2 * h, bias=False)
+        self.content_M = LinearHolder(2 * h, 2 * h, bias=True)
+        self.title_self_attention = Attention(2 * h, config.attention_dim)
+        self.content_self_attention = Attention(2 * h, config.attention_dim)
+        self.title_cross_attention = ScaledDotProduct_CandidateAttention(2 * h, 2 * h, config.attention_dim)
+        self.content_cross_attention = ScaledDotProduct_CandidateAttention(2 * h, 2 * h, config.attention_dim)
+
+    def initialize(self):                                                                                           # :462-484
+        super().initialize()
+        for lstm in (self.title_lstm, self.content_lstm):
+            for p in lstm.parameters():
+                if p.dim() >= 2:
+                    nn.init.orthogonal_(p.data)
+                else:
+                    nn.init.zeros_(p.data)
+        gain = nn.init.calculate_gain('sigmoid')
+        for lin in (self.title_H, self.title_M, self.content_H, self.content_M):
+            nn.init.xavier_uniform_(lin.weight, gain=gain)
+        nn.init.zeros_(self.title_M.bias)
+        nn.init.zeros_(self.content_M.bias)
+        for att in (self.title_self_attention, self.content_self_attention, self.title_cross_attention, self.content_cross_attention):
+            att.initialize()
+        nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
+
+    @staticmethod
+    def lstm_weights(lstm):
+        """(W_ih of both directions stacked row-wise [8h, E], b_ih + b_hh stacked [8h], W_hh stacked [2, 4h, h])."""
+        wih = torch.cat([lstm.weight_ih_l0, lstm.weight_ih_l0_reverse], dim=0)
+        bias = torch.cat([lstm.bias_ih_l0 + lstm.bias_hh_l0, lstm.bias_ih_l0_reverse + lstm.bias_hh_l0_reverse], dim=0)
+        whh = torch.stack([lstm.weight_hh_l0, lstm.weight_hh_l0_reverse], dim=0)
+        return wih, bias, whh
+
+    @staticmethod
+    def reference_pairs(lens_t, lens_b, groups, cap):
+        """(int32 [cap], int32 [cap]): the news whose body memory gates the title of news i, and whose title memory gates its body, for
+        calls of ``groups`` news each (:496-499, :517-521): sorted position j of the one order meets sorted position j of the other.
+        Sorted = descending by length, TIED lengths in input order (a stable sort: the reference's default sort leaves the order of
+        ties to the torch build, so it is defined here; tools/make_cne_goldens.py runs the reference the same way).  Device-side, two
+        sorts per call; slots behind the groups pair with themselves."""
+        dev = lens_t.device
+        pt, pb = torch.arange(cap, device=dev), torch.arange(cap, device=dev)
+        o = 0
+        for n in groups:
+            st = torch.sort(lens_t[o:o + n], descending=True, stable=True).indices
+            sc = torch.sort(lens_b[o:o + n], descending=True, stable=True).indices
+            pt[o + st] = sc + o                                    # title at sorted position j <- body memory at sorted position j
+            pb[o + sc] = st + o
+            o += n
+        return pt.to(torch.int32), pb.to(torch.int32)
+
+    @staticmethod
+    def slot0_mask(mask):
+        """A uint8 COPY of the mask with slot 0 set (:492-493)."""
+        m = mask.to(torch.uint8) if mask.dtype != torch.bool else mask.view(torch.uint8).clone()
+        if m.data_ptr() == mask.data_ptr():
+            m = m.clone()
+        m[:, 0] = 1
+        return m.contiguous()
+
+    def lstm_chunks(self, n_news, S):
+        """[(first, end)] news ranges of the recurrence over n_news texts of S token slots: as few as keep a chunk's gi ([tokens,
+        2 . 4 hidden_dim] fp32) within GI_BYTES_PER_PASS, of even size.  Only gi is per chunk; hout and c_n of every chunk are kept, so
+        the gates pair over the whole call whatever its size."""
+        per = max(1, self.GI_BYTES_PER_PASS // (S * 8 * self.hidden_dim * 4))
+        n_chunks = max(1, -(-n_news // per))
+        size = -(-n_news // n_chunks)
+        return [(r0, min(n_news, r0 + size)) for r0 in range(0, n_news, size)]
+
+    def _encode(self, ids_t, mask_t, ids_b, mask_b, n_dev, pooled, pair_groups=None):
+        """`cap` news slots of which the first n_dev (a device int) are live: title ids_t [cap, T] / body ids_b [cap, L] int32, masks uint8
+        with slot 0 set -> pooled [cap, 4h] (rows behind n_dev are left alone).  Every launch has the capacity as its shape and the device
+        count as its bound."""
+        dev = ids_t.device
+        cap, h = ids_t.shape[0], self.hidden_dim
+        table = self.word_embedding.weight
+        texts = []
+        for ids, mask, lstm in ((ids_t, mask_t, self.title_lstm), (ids_b, mask_b, self.content_lstm)):
+            S = ids.shape[1]
+            n_tok = n_dev * S                                                                          # device int: live token rows
+            lens = ops.mask_lengths(mask, min_len=1)                                                   # :494-495
+            wih, bias, whh = self.lstm_weights(lstm)
+            hout = torch.zeros((cap * S, 2 * h), dtype=torch.float32, device=dev)
+            m = torch.empty((cap, 2 * h), dtype=torch.float32, device=dev)
+            for r0, r1 in self.lstm_chunks(cap, S):
+                live = n_dev if r0 == 0 else (n_dev - r0).clamp(min=0)                                 # live news of this chunk
+                gi = ops.linear(table, wih, bias, a_ids=ids[r0:r1].reshape(-1), m_dev=live * S)        # :501-502 gather + W_ih x + b
+                _, c = ops.lstm(gi, whh, lens[r0:r1], S, n_rows_dev=live, hout=hout[r0 * S:r1 * S])    # :509-510, :514-515
+                del gi
+                m[r0:r1] = c.transpose(0, 1).reshape(r1 - r0, 2 * h)                                   # :512-513
+            texts.append((S, n_tok, mask, hout, m, lens))
+        pairs = None
+        if pair_groups is not None:
+            pairs = self.reference_pairs(texts[0][5], texts[1][5], pair_groups, cap)
+        gated = []
+        for k, (H_, M_, att) in enumerate(((self.title_H, self.title_M, self.title_self_attention),
+                                           (self.content_H, self.content_M, self.content_self_attention))):
+            S, n_tok, mask, hout, _, _ = texts[k]
+            m_other = texts[1 - k][4]
+            if pairs is not None:                                                                      # the reference's partner news
+                m_other = ops.gather_rows(pairs[k], m_other, torch.empty_like(m_other))
+            tm = ops.linear(m_other, M_.weight, M_.bias, m_dev=n_dev)                                  # M(other text's memory vector)
+            pre = ops.linear(hout, H_.weight, None, res=tm, res_div=S, m_dev=n_tok)                    # :517-518 before the sigmoid
+            g = ops.gate_mul(hout, pre, out=pre, n_rows_dev=n_tok)                                     # :520-521 (in place over pre)
+            hidden = ops.linear(g, att.affine1.weight, att.affine1.bias, act='tanh', m_dev=n_tok)
+            own = ops.additive_pool(hidden, att.affine2.weight.view(-1), g, cap, S, mask=mask, n_seq_dev=n_dev)   # :524-525
+            gated.append((g, own))
+        ones = _ones(2 * h, dev)
+        for k, att in enumerate((self.title_cross_attention, self.content_cross_attention)):
+            S, n_tok, mask = texts[k][:3]
+            g, own = gated[k]
+            q = ops.linear(gated[1 - k][1], att.Q.weight, att.Q.bias, m_dev=n_dev)                     # Q(other text's self attention)
+            v = ops.linear(q, att.K.weight.t().contiguous(), None, m_dev=n_dev)                        # K^T q: K(h_t) . q = h_t . (K^T q)
+            terms = ops.gate_mul(g, v, div=S, scale=1.0 / att.attention_scalar, sigmoid=False, n_rows_dev=n_tok)
+            cross = ops.additive_pool(terms, ones, g, cap, S, mask=mask, n_seq_dev=n_dev)               # :527-528
+            ops.fuse_rows(own, cross, out=pooled[:, 2 * h * k:2 * h * (k + 1)])                         # :529
+        return pooled
+
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None, pair_groups=None):
+        """pair_groups: the news counts of the reference calls this pass stands for (they add up to M): the gates then read the
+        reference's partner news (class docstring).  None: every news reads its own other text (the encoder as published)."""
+        _no_train_dropout(self, self.dropout_rate)
+        if content_mask is None:
+            raise TypeError('the CNE content encoder reads the body mask (content_mask): pass it -- it is never guessed from the ids')
+        M, T = title_text.shape
+        L = content_text.shape[1]
+        h = self.hidden_dim
+        dev = title_text.device
+        if pair_groups is not None and sum(pair_groups) != M:
+            raise ValueError('pair_groups %s do not add up to the %d news of the pass' % (list(pair_groups), M))
+        t_mask, b_mask = self.slot0_mask(title_mask.reshape(M, T)), self.slot0_mask(content_mask.reshape(M, L))
+        self._encode(_i32(title_text).contiguous(), t_mask, _i32(content_text).contiguous(), b_mask, _row_count(M, dev), out[:, :4 * h],
+                     pair_groups)                                                                       # :529 into the first 4h columns
+        ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
+                      emb_out=out[:, 4 * h:])                                                           # :531, :221-226
         return out

@@ -1867,3 +1867,126 @@ def negative_sample(offsets, neg_index, neg_lifetime, pos_index, pos_lifetime, f
                                    _p(cand_index), _p(cand_freshness), _p(cand_lifetime), N, K, seed, epoch, 1 if inclusive else 0,
                                    _stream()), 'lime_negative_sample')
     return cand_index, cand_freshness, cand_lifetime
+
+
+# ---- CNE content encoder: bidirectional LSTM (csrc/lstm_f32.hip) ------------------------------------------------------------------
+
+LSTM_UNIT_TILE = 16          # hidden sizes the step kernel is built for: multiples of this (a workgroup owns 16 units with their four gates)
+
+
+def mask_lengths(mask, min_len=0, out=None):
+    """``lime_mask_lengths``: int32 [R] = max(number of set entries of mask[r], min_len); mask bool / uint8 [R, T]."""
+    lib = _lib.load()
+    R, T = mask.shape
+    m = _mask_u8(mask, 'mask')
+    if out is None:
+        out = torch.empty(R, dtype=torch.int32, device=mask.device)
+    _vec(out, 'out', R, dtype=torch.int32)
+    check(lib.lime_mask_lengths(_p(m), R, T, min_len, _p(out), _stream()), 'lime_mask_lengths')
+    return out
+
+
+def _lstm_dims(whh, lengths, T):
+    _vec(whh, 'whh')
+    if whh.dim() != 3 or whh.shape[0] != 2 or whh.shape[1] != 4 * whh.shape[2]:
+        raise ValueError('whh must be [2, 4h, h] (weight_hh_l0 and weight_hh_l0_reverse stacked), got %s' % (tuple(whh.shape),))
+    h = whh.shape[2]
+    if h % LSTM_UNIT_TILE:
+        raise ValueError('the LSTM step kernel needs a hidden size that is a multiple of %d, got %d' % (LSTM_UNIT_TILE, h))
+    _vec(lengths, 'lengths', dtype=torch.int32)
+    if T < 1:
+        raise ValueError('T must be >= 1')
+    return lengths.numel(), h
+
+
+def lstm_step(gi, whh, lengths, hout, c, step, T, n_rows_dev=None, saved=None):
+    """One time step of the bidirectional LSTM, both directions in one launch -- see ``lime_lstm_step_f32`` in include/lime_hip.h.
+    gi [R T, 8h]; whh [2, 4h, h]; lengths int32 [R]; hout [R T, 2h] (zeroed once by the caller) and c [2, R, h] are updated in place.
+    saved: (gates [R T, 8h], c_seq [R T, 2h], h_prev [R T, 2h]) to keep what the backward step needs."""
+    lib = _lib.load()
+    R, h = _lstm_dims(whh, lengths, T)
+    _mat(gi, 'gi')
+    _mat(hout, 'hout')
+    if gi.shape[0] != R * T or gi.shape[1] != 8 * h or tuple(hout.shape) != (R * T, 2 * h) or not hout.is_contiguous():
+        raise ValueError('gi must be [R T, 8h] and hout a contiguous [R T, 2h] (R = %d, T = %d, h = %d)' % (R, T, h))
+    _vec(c, 'c', 2 * R * h)
+    g = cs = hp = None
+    if saved is not None:
+        g, cs, hp = saved
+        _vec(g, 'gates', R * T * 8 * h)
+        _vec(cs, 'c_seq', R * T * 2 * h)
+        _vec(hp, 'h_prev', R * T * 2 * h)
+    if n_rows_dev is not None:
+        _vec(n_rows_dev, 'n_rows_dev', 1, dtype=torch.int32)
+    check(lib.lime_lstm_step_f32(_p(gi), _ld(gi), _p(whh), _p(lengths), _p(hout), _p(c), _p(g), _p(cs), _p(hp), R, T, h, step,
+                                 _p(n_rows_dev), _stream()), 'lime_lstm_step_f32')
+
+
+def lstm(gi, whh, lengths, T, n_rows_dev=None, save=False, hout=None, c=None):
+    """The whole recurrence: T ``lstm_step`` launches in order (the time loop is on the host; a captured graph records them like any other
+    launch).  Returns (hout [R T, 2h] with zeros behind every length, c [2, R, h] = c_n of both directions) and, with ``save``, the
+    (gates, c_seq, h_prev) triple of ``lstm_bwd``.  hout / c may be passed in (hout zeroed by the caller)."""
+    R, h = _lstm_dims(whh, lengths, T)
+    if hout is None:
+        hout = torch.zeros((R * T, 2 * h), dtype=torch.float32, device=gi.device)
+    if c is None:
+        c = torch.zeros((2, R, h), dtype=torch.float32, device=gi.device)
+    saved = None
+    if save:
+        saved = (torch.zeros((R * T, 8 * h), dtype=torch.float32, device=gi.device),
+                 torch.zeros((R * T, 2 * h), dtype=torch.float32, device=gi.device),
+                 torch.zeros((R * T, 2 * h), dtype=torch.float32, device=gi.device))
+    for s in range(T):
+        lstm_step(gi, whh, lengths, hout, c, s, T, n_rows_dev=n_rows_dev, saved=saved)
+    return (hout, c, saved) if save else (hout, c)
+
+
+def lstm_bwd(dhout, dc_n, whh, lengths, T, saved, whh_t=None):
+    """Backward of ``lstm``: steps T - 1 .. 0, each one gate-gradient launch (``lime_lstm_step_bwd_f32``) and -- but for step 0 -- one
+    grouped GEMM of both directions carrying dh through W_hh.  dhout [R T, 2h] or None, dc_n [2, R, h] or None.  Returns
+    dgi [R T, 8h] (zeros at padding tokens): the gradient of ``lstm``'s gi, from which the caller takes dW_ih, the bias gradients and
+    the input rows with the existing GEMM nodes, and dW_hh = dgi[:, direction]^T h_prev[:, direction].  whh_t: [2, h, 4h], W_hh transposed."""
+    lib = _lib.load()
+    R, h = _lstm_dims(whh, lengths, T)
+    gates, c_seq, _ = saved
+    dev = whh.device
+    if whh_t is None:
+        whh_t = whh.transpose(1, 2).contiguous()
+    dgi = torch.zeros((R * T, 8 * h), dtype=torch.float32, device=dev)
+    dgs = torch.empty((2, R, 4 * h), dtype=torch.float32, device=dev)
+    dh = torch.zeros((2, R, h), dtype=torch.float32, device=dev)
+    dc = torch.zeros((2, R, h), dtype=torch.float32, device=dev) if dc_n is None else dc_n.contiguous().clone()
+    lddh = 0
+    if dhout is not None:
+        _mat(dhout, 'dhout')
+        if tuple(dhout.shape) != (R * T, 2 * h):
+            raise ValueError('dhout must be [R T, 2h]')
+        lddh = _ld(dhout)
+    if R == 0:
+        return dgi
+    for s in range(T - 1, -1, -1):
+        check(lib.lime_lstm_step_bwd_f32(_p(dhout), lddh, _p(gates), _p(c_seq), _p(lengths), _p(dh), _p(dc), _p(dgi), _p(dgs), R, T, h, s,
+                                         _stream()), 'lime_lstm_step_bwd_f32')
+        if s > 0:
+            linear_group([dict(a=dgs[d], w=whh_t[d], out=dh[d]) for d in (0, 1)])
+    return dgi
+
+
+def gate_mul(x, g, div=1, scale=1.0, sigmoid=True, out=None, n_rows_dev=None):
+    """``lime_gate_mul_f32`` on contiguous [rows, cols] operands: x * sigmoid(g) (g [rows, cols]), or with ``sigmoid`` off
+    x[r] * g[r // div] * scale (g [rows / div, cols])."""
+    lib = _lib.load()
+    _mat(x, 'x')
+    _mat(g, 'g')
+    rows, cols = x.shape
+    if not x.is_contiguous() or not g.is_contiguous() or g.shape[1] != cols or g.shape[0] * (1 if sigmoid else div) < rows or (sigmoid and div != 1):
+        raise ValueError('gate_mul: x [rows, cols] and g [rows / div, cols] must be contiguous and agree')
+    if out is None:
+        out = torch.empty_like(x)
+    if tuple(out.shape) != (rows, cols) or not out.is_contiguous():
+        raise ValueError('gate_mul: out must be a contiguous [rows, cols]')
+    if n_rows_dev is not None:
+        _vec(n_rows_dev, 'n_rows_dev', 1, dtype=torch.int32)
+    check(lib.lime_gate_mul_f32(_p(x), _p(g), _p(out), rows, cols, div, 0 if sigmoid else 1, scale, _p(n_rows_dev), _stream()), 'lime_gate_mul_f32')
+    return out
+

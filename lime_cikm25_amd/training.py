@@ -699,6 +699,89 @@ def naml_content(enc, title_text, content_text, category, subCategory):
     return _AdditivePool.apply(hidden, enc.affine2.weight.view(-1), feature, None, M, 4)                        # :693-694
 
 
+class _LSTMCore(torch.autograd.Function):
+    """The recurrence of a bidirectional LSTM (nn.LSTM under pack_padded_sequence, newsEncoders.py:503-515) from the input projections
+    gi [n S, 2 . 4h] of every token: -> (hout [n S, 2h], zeros behind each length; c_n [2, n, h]).  Forward: the step kernel with the gate
+    activations, c_t and h_{t-1} kept; backward: the gate-gradient step kernel + the carry GEMM per step (ops.lstm_bwd), then dW_hh as one
+    weight-gradient GEMM per direction of the pre-activation gradients against the kept h_{t-1} (zero for a direction's first token).
+    The gradient of gi goes on to the _Linear node that made it: dW_ih, both biases and the word rows come from there."""
+
+    @staticmethod
+    def forward(ctx, gi, whh, lens, S):
+        whh = whh.contiguous()
+        hout, c, saved = ops.lstm(gi.contiguous(), whh, lens, S, save=True)
+        ctx.S = S
+        ctx.save_for_backward(whh, lens, *saved)
+        return hout, c
+
+    @staticmethod
+    def backward(ctx, dhout, dc):
+        whh, lens, gates, c_seq, h_prev = ctx.saved_tensors
+        h = whh.shape[2]
+        dgi = ops.lstm_bwd(dhout.contiguous(), dc, whh, lens, ctx.S, (gates, c_seq, h_prev))
+        dwhh = torch.stack([ops.linear_wgrad(dgi[:, d * 4 * h:(d + 1) * 4 * h], h_prev[:, d * h:(d + 1) * h]) for d in (0, 1)], dim=0)
+        return dgi, dwhh, None, None
+
+
+def cne_content(enc, title_text, title_mask, content_text, content_mask, category, subCategory, pair_groups=None):
+    """newsEncoders.CNE.forward (newsEncoders.py:486-532) on M flat news -> [M, 4 hidden_dim + 100].  One autograd node per LSTM
+    (_LSTMCore, HIP both ways) behind the _Linear node of its input projection; the gates and the cross attention's score terms are torch
+    element-wise glue, the GEMMs and the four attention pools the existing nodes.  The dropout sites (counter-based masks of one seed):
+    0 / 1 the title / body word embeddings (self.dropout, :501-502), 2 / 3 the category / subcategory embeddings of feature_fusion
+    (:221-226).  The mask-slot-0 rule (:492-493) is applied to copies of the masks.  pair_groups: the news counts of the reference calls
+    (CNE.reference_pairs: the gates read the reference's partner news); None: every news reads its own other text."""
+    from .newsEncoders import CNE
+    if content_mask is None:
+        raise TypeError('the CNE content encoder reads the body mask (content_mask): pass it -- it is never guessed from the ids')
+    M, T = title_text.shape
+    L = content_text.shape[1]
+    h = enc.hidden_dim
+    p = float(enc.dropout.p) if enc.training else 0.0
+    seed = _draw_seed() if p > 0 else 0
+    table = enc.word_embedding.weight
+    texts = []
+    for site, (ids, mask, lstm, S) in enumerate(((title_text, title_mask, enc.title_lstm, T), (content_text, content_mask, enc.content_lstm, L))):
+        mask = mask.reshape(M, S).bool().clone()
+        mask[:, 0] = True                                                                                       # :492-493, on a copy
+        x = embedding(table, ids, hot_id=0).view(M * S, -1)                                                     # :501-502
+        if p > 0:
+            x = _Dropout.apply(x, p, seed, site)
+        lens = ops.mask_lengths(mask, min_len=1)                                                                # :494-495
+        wih, bias, whh = CNE.lstm_weights(lstm)
+        hout, c = _LSTMCore.apply(_Linear.apply(x, wih, bias, None), whh, lens, S)                              # :509-515
+        texts.append((S, mask, hout, c.transpose(0, 1).reshape(M, 2 * h), lens))                                # :512-513
+    pairs = None
+    if pair_groups is not None:
+        if sum(pair_groups) != M:
+            raise ValueError('pair_groups %s do not add up to the %d news' % (list(pair_groups), M))
+        pairs = [p.long() for p in CNE.reference_pairs(texts[0][4], texts[1][4], pair_groups, M)]
+    gated = []
+    for k, (H_, M_, att) in enumerate(((enc.title_H, enc.title_M, enc.title_self_attention),
+                                       (enc.content_H, enc.content_M, enc.content_self_attention))):
+        S, mask, hout = texts[k][:3]
+        m_other = texts[1 - k][3] if pairs is None else texts[1 - k][3][pairs[k]]                               # :517-518 in sorted order
+        tm = _Linear.apply(m_other, M_.weight, M_.bias, None)                                                   # the OTHER text's memory vector
+        pre = _Linear.apply(hout, H_.weight, None, None).view(M, S, 2 * h) + tm.unsqueeze(1)
+        g = (hout.view(M, S, 2 * h) * torch.sigmoid(pre)).reshape(M * S, 2 * h)                                 # :517-521
+        hidden = linear(g, att.affine1, act='tanh')
+        gated.append((g, _AdditivePool.apply(hidden, att.affine2.weight.view(-1), g, mask, M, S)))              # :524-525
+    ones = torch.ones(2 * h, dtype=torch.float32, device=table.device)
+    reps = []
+    for k, att in enumerate((enc.title_cross_attention, enc.content_cross_attention)):
+        S, mask = texts[k][:2]
+        g, own = gated[k]
+        q = _Linear.apply(gated[1 - k][1], att.Q.weight, att.Q.bias, None)                                      # the OTHER text's self attention
+        v = _Linear.apply(q, att.K.weight.t().contiguous(), None, None)                                         # K(h_t) . q = h_t . (K^T q)
+        terms = (g.view(M, S, 2 * h) * (v * (1.0 / att.attention_scalar)).unsqueeze(1)).reshape(M * S, 2 * h)
+        reps.append(own + _AdditivePool.apply(terms, ones, g, mask, M, S))                                      # :527-529
+    cat_e = embedding(enc.category_embedding.weight, category)
+    sub_e = embedding(enc.subCategory_embedding.weight, subCategory)
+    if p > 0:
+        cat_e = _Dropout.apply(cat_e, p, seed, 2)
+        sub_e = _Dropout.apply(sub_e, p, seed, 3)
+    return torch.cat(reps + [cat_e, sub_e], dim=1)                                                              # :529-531
+
+
 def lime_tail(ne, content, freshness, lifetime):
     """LIME.forward, fusion 'concat' (newsEncoders.py:140-153), from the content encoder's output -> [M, 400]."""
     fe = ne.freshness_encoder
@@ -848,10 +931,10 @@ def lifetime_weighted_logits(w, user, news, remaining_lifetime):
     return base * weight
 
 
-def content_flat(enc, title_text, title_mask, content_text, category, subCategory):
+def content_flat(enc, title_text, title_mask, content_text, category, subCategory, content_mask=None, pair_groups=None):
     """The base content encoder (CROWN: newsEncoders.py:302-373, CNN: :548-563, NAML: :671-695, MHSA: :582-595) on M flat news with
     autograd -> [M, dim]."""
-    from .newsEncoders import CNN, CROWN, MHSA, NAML
+    from .newsEncoders import CNE, CNN, CROWN, MHSA, NAML
     if getattr(enc, 'compute_dtype', 'fp32') != 'fp32':
         raise NotImplementedError("compute_dtype %r is a scoring option (BASELINE config 3); the training step is fp32: build the "
                                   "model with compute_dtype='fp32' to train" % enc.compute_dtype)
@@ -864,18 +947,22 @@ def content_flat(enc, title_text, title_mask, content_text, category, subCategor
         return cnn_content(enc, title_text, title_mask, category, subCategory)
     if isinstance(enc, NAML):
         return naml_content(enc, title_text, content_text, category, subCategory)
-    raise NotImplementedError('the training path covers the CROWN, CNN, NAML and MHSA content encoders')
+    if isinstance(enc, CNE):
+        return cne_content(enc, title_text, title_mask, content_text, content_mask, category, subCategory, pair_groups)
+    raise NotImplementedError('the training path covers the CROWN, CNN, NAML, MHSA and CNE content encoders')
 
 
-def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime):
-    """LIME.forward (newsEncoders.py:140-161) on M flat news with autograd -> [M, 400]."""
-    content = content_flat(ne.base_news_encoder, title_text, title_mask, content_text, category, subCategory)
+def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None, pair_groups=None):
+    """LIME.forward (newsEncoders.py:140-161) on M flat news with autograd -> [M, 400].  content_mask: the body mask, read by CNE alone."""
+    content = content_flat(ne.base_news_encoder, title_text, title_mask, content_text, category, subCategory, content_mask=content_mask,
+                           pair_groups=pair_groups)
     return lime_tail(ne, content, freshness, lifetime)
 
 
 def forward_train(model, user_category, user_subCategory, user_title_text, user_title_mask, user_content_text, user_freshness,
                   user_user_topic_lifetime, user_history_mask, news_category, news_subCategory, news_title_text, news_title_mask,
-                  news_content_text, news_freshness, news_user_topic_lifetime, remaining_lifetime):
+                  news_content_text, news_freshness, news_user_topic_lifetime, remaining_lifetime, user_content_mask=None,
+                  news_content_mask=None):
     """Model.forward with [B, N] candidates (model.py:171-187), recording the autograd graph.  Candidates and history go
     through the news encoder as one flat batch of B (N + H) news.  After the token encoders come the content tail, freshness
     and project per news, then the CROWN user encoder and the lifetime-weighted dot product: 3 % of the FLOPs in some 300
@@ -895,7 +982,9 @@ def forward_train(model, user_category, user_subCategory, user_title_text, user_
     rep = news_flat(ne, i32(flat2(news_title_text, user_title_text)), flat2(news_title_mask, user_title_mask),
                     i32(flat2(news_content_text, user_content_text)), category, subCategory,
                     flat1(news_freshness.float(), user_freshness.float()).contiguous(),
-                    flat1(news_user_topic_lifetime.float(), user_user_topic_lifetime.float()).contiguous())
+                    flat1(news_user_topic_lifetime.float(), user_user_topic_lifetime.float()).contiguous(),
+                    content_mask=None if news_content_mask is None or user_content_mask is None else flat2(news_content_mask, user_content_mask),
+                    pair_groups=[B * N, B * H])                # the reference's two encoder calls (model.py:171, userEncoders.py:110)
     cand = rep[:B * N].view(B, N, -1)
     hist = rep[B * N:].view(B, H, -1)
     return user_logits(model.user_encoder, model.remaining_lifetime_weighting, hist, cand, i32(news_category).contiguous(),

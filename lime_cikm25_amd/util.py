@@ -92,7 +92,11 @@ def compute_scores_cached(model, behaviors, indices, result_file, truth_file=Non
     config.batch_size, as trainer.py:153 calls compute_scores; main.py:50,67 pass twice that, which only fits while
     2 x batch_size <= H + config.batch_size node slots) with the chunk's row count as the GraphSAGE source count, so the scores
     are those of ``compute_scores`` over the same batches; the remaining lifetime follows ``config.lifetime_type``
-    ('fixed' / 'topic_wise' / 'user_topic', util.py:98-106)."""
+    ('fixed' / 'topic_wise' / 'user_topic', util.py:98-106).
+
+    Under the CNE content encoder there is nothing to cache per news (its gates read the memory vector of another news of the same
+    encoder call): the cache is empty, every chunk of rows is encoded as ``compute_scores`` would encode that batch, and the scores
+    equal ``compute_scores``' only when the chunks are its batches (CNE's scores depend on the batch's composition)."""
     config = model.config
     if config.lifetime_type not in ('fixed', 'topic_wise', 'user_topic'):
         raise ValueError('Invalid lifetime_type')
