@@ -782,6 +782,45 @@ int lime_conv1d_wgrad_f32(const float* dy, int64_t ldy, const float* a, int64_t 
                           int64_t workspace_floats, void* stream);
 
 /* =====================================================================================================
+ * Knowledge-aware convolution + ReLU + max pool in one launch (layers.py:138-190 Conv2D_Pool, the KCNN content encoder
+ * newsEncoders.py:598-638; csrc/conv_pool_sp_f32.hip: split product, or exact-fp32 MFMA under lime_set_split_gemm(0)):
+ *   pre[s, t, o] = bias[o] + sum_{src < n_src} sum_{j < window} sum_{c < C} X_src(s T + t + j - pad)[c] * w[o * ldw + (src * window + j) * C + c]
+ *   pooled[s * ldp + o] = max(0, max_{t < P} pre[s, t, o]);  arg[s * ldarg + o] = the smallest t attaining it, -1 where pooled is 0
+ *   X_src(q) = a[src][ids[src][q] * lda[src] ...] (a gathered table row) or a[src][q * lda[src] ...] (ids[src] == NULL); ZEROS where
+ *   the position t + j - pad is outside [0, T).
+ * w is the nn.Conv2d weight [N, C, window, n_src] permuted to [N, n_src, window, C].  1 <= n_src <= 3, 1 <= window <= T, 0 <= pad <
+ * window, 1 <= P <= T <= 128 (a 128-row tile holds floor(128 / T) whole sequences).  C, N, lda[], ldw multiples of 4; a[], w, bias
+ * 16-byte aligned; anything else is refused before any launch.  bias and arg are optional.  n_seq_dev: optional device-side sequence
+ * count (sequences >= min(*n_seq_dev, n_seq) are neither computed nor written).  No atomics; the pre-activations stay in the
+ * workgroup; the bits of a (sequence, column) do not depend on the batch around the sequence. */
+typedef struct lime_conv_pool_args {
+    const float* a[3];
+    int64_t lda[3];
+    const int32_t* ids[3];
+    const float* w;
+    int64_t ldw;
+    const float* bias;
+    float* pooled;
+    int64_t ldp;
+    int32_t* arg;
+    int64_t ldarg;
+    const int32_t* n_seq_dev;
+    int32_t n_seq, T, N, C;
+    int32_t n_src, window, pad, P;
+} lime_conv_pool_args;
+int lime_conv_pool_f32(const lime_conv_pool_args* args, void* stream);
+
+/* The same pooled / arg from dense pre-activations pre[(s T + t) * ldpre + o] (+ bias): one thread per (sequence, four columns).
+ * N, ldpre, ldp multiples of 4; pre, pooled, bias 16-byte aligned. */
+int lime_relu_maxpool_f32(const float* pre, int64_t ldpre, const float* bias, float* pooled, int64_t ldp, int32_t* arg, int64_t ldarg,
+                          int32_t n_seq, int32_t T, int32_t P, int32_t N, const int32_t* n_seq_dev, void* stream);
+
+/* Backward of the pooling: dpre[(s T + t) * ldpre + o] = (arg[s, o] == t) ? dpooled[s, o] : 0 for every t < T -- all n_seq * T rows are
+ * written, each by the one thread that owns its (sequence, four columns) strip: no atomics, no pre-zeroing. */
+int lime_relu_maxpool_bwd_f32(const float* dpooled, int64_t lddp, const int32_t* arg, int64_t ldarg, float* dpre, int64_t ldpre,
+                              int32_t n_seq, int32_t T, int32_t N, void* stream);
+
+/* =====================================================================================================
  * Additive attention pool in one launch (layers.py:285-300 Attention, the NAML content encoder newsEncoders.py:686-694;
  * csrc/attn_pool_sp_f32.hip: split product, or exact-fp32 MFMA under lime_set_split_gemm(0)):
  *   out[s * ldo + :D] = sum_t alpha[s, t] x[(s T + t) * ldx + :D],  alpha[s] = softmax_t(w2 . tanh(W1 x[s T + t] + b1))

@@ -147,6 +147,20 @@ class RankMetricsArgs(ctypes.Structure):
         ('n_imp', c_int32), ('rank_blocks', c_int32), ('reduce_blocks', c_int32), ('reserved', c_int32),
     ]
 
+class ConvPoolArgs(ctypes.Structure):
+    """lime_conv_pool_args of include/lime_hip.h (same field order)."""
+    _fields_ = [
+        ('a', c_void_p * 3), ('lda', c_int64 * 3), ('ids', c_void_p * 3),
+        ('w', c_void_p), ('ldw', c_int64),
+        ('bias', c_void_p),
+        ('pooled', c_void_p), ('ldp', c_int64),
+        ('arg', c_void_p), ('ldarg', c_int64),
+        ('n_seq_dev', c_void_p),
+        ('n_seq', c_int32), ('T', c_int32), ('N', c_int32), ('C', c_int32),
+        ('n_src', c_int32), ('window', c_int32), ('pad', c_int32), ('P', c_int32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/lime_hip.h declares
 SIGNATURES = {
     'lime_abi_version': (c_int32, []),
@@ -287,6 +301,11 @@ SIGNATURES = {
     'lime_conv1d_wgrad_workspace': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     'lime_conv1d_wgrad_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                         c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
+    # KCNN content encoder: conv + ReLU + max pool in one launch, its unfused partner and the pooling's backward
+    'lime_conv_pool_f32': (c_int32, [ctypes.POINTER(ConvPoolArgs), c_void_p]),
+    'lime_relu_maxpool_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                        c_int32, c_void_p, c_void_p]),
+    'lime_relu_maxpool_bwd_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     # NAML content encoder: fused additive attention pool
     'lime_attn_pool_pack_sp_size': (c_int64, [c_int32, c_int32]),
     'lime_attn_pool_pack_sp': (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),

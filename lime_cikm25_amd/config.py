@@ -52,6 +52,8 @@ _DEFAULTS = dict(
     cnn_kernel_num=400,                   # config.py:87
     cnn_window_size=3,                    # config.py:88
     hidden_dim=400,                       # config.py:98 (CNE: the bidirectional LSTMs' hidden size per direction)
+    entity_embedding_dim=100,             # config.py:84 (KCNN: the entity table's width)
+    context_embedding_dim=100,            # config.py:85 (KCNN: the context table's width)
     category_embedding_dim=50,            # config.py:91
     subCategory_embedding_dim=50,         # config.py:92
     user_embedding_dim=50,                # config.py:90
@@ -73,6 +75,7 @@ _DEFAULTS = dict(
     category_num=18,
     subCategory_num=270,
     user_num=1000,
+    entity_size=5000,                     # KCNN: rows of the entity / context tables (corpus.py fills it from the entity dictionary)
     # not in the reference: arithmetic of the token encoders on the MI355X path.  'fp32' (exact-fp32 MFMA, the parity
     # configuration) or 'bf16' (BASELINE config 3: bf16 MFMA operands / activations, fp32 accumulate, softmax, LayerNorm)
     compute_dtype='fp32',

@@ -26,18 +26,13 @@
 // 64 o x 128 c of one tap over one slice of the rows, both operands stored into LDS transposed ([column][row]) so that a fragment
 // (eight consecutive rows of one column) is one 32-byte read; the slices' partial tiles go to a workspace and are summed in slice
 // order by conv_wgrad_reduce_kernel -- no atomics, the same bits on every run.
-#include "common.h"
-#include "dev_helpers.h"
-#include "split_mfma.h"
+#include "conv_frag.h"
 
 using namespace lime_dev;
 
 int lime_split_mode();
 
 namespace {
-
-constexpr int KC = 32;                  // chunk depth (one bf16 MFMA's k)
-constexpr int PITCH = 36;               // floats per LDS row: 32 + 4 (conflict-free 16-byte reads of 16 rows)
 
 struct ConvParams {
     const float* a;
@@ -52,45 +47,8 @@ struct ConvParams {
     int M, N, C, T, win, pad, relu, accumulate, vec_out, n_col_blocks;
 };
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
-// the 32-deep product of one chunk for one 16 x 16 accumulator tile: w = eight k values of output column fi, x = eight k values of
-// row fi (lane group kg: k = 8 kg .. 8 kg + 7)
-template <bool SPLIT>
-struct Frag;
-template <>
-struct Frag<true> {
-    SplitFrag f;
-    __device__ __forceinline__ void load(const float* p) { f = split_frag(ld4(p), ld4(p + 4)); }
-};
-template <>
-struct Frag<false> {
-    float x[8];
-    __device__ __forceinline__ void load(const float* p) {
-        const f32x4 a = ld4(p), b = ld4(p + 4);
-        x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3];
-        x[4] = b[0]; x[5] = b[1]; x[6] = b[2]; x[7] = b[3];
-    }
-};
-__device__ __forceinline__ f32x4 prod(const Frag<true>& w, const Frag<true>& x, f32x4 c) { return split_mfma16(w.f, x.f, c); }
-// v_mfma_f32_16x16x4_f32: lane (fi, kg) supplies A[fi][kg] and B[kg][fi]; product q takes k = 8 kg + q in slot kg (the same label
-// on both operands)
-__device__ __forceinline__ f32x4 prod(const Frag<false>& w, const Frag<false>& x, f32x4 c) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) c = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x[q], x.x[q], c, 0, 0, 0);
-    return c;
-}
-
-// source row of output row r under tap j (window offset j - pad), as a float offset into a / the table, or -1: zeros
-__device__ __forceinline__ long window_row(const int* ids, long lda, int r, int j, int pad, int T) {
-    const int s = r / T, t = r - s * T, tt = t + j - pad;
-    if (tt < 0 || tt >= T) return -1;
-    const int q = r + j - pad;
-    return (long)(ids ? ids[q] : q) * lda;
-}
-
 constexpr int BM = 128, BN = 128;
-constexpr int A_FL = BM * PITCH, W_FL = BN * PITCH, STAGE = A_FL + W_FL;
+constexpr int A_FL = BM * CONV_PITCH, W_FL = BN * CONV_PITCH, STAGE = A_FL + W_FL;
 static_assert(2 * STAGE * 4 <= 81920, "two workgroups per CU");
 
 template <bool SPLIT>
@@ -109,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
     const int wr = wave & 1, wc = wave >> 1;
     const int fi = lane & 15, kg = lane >> 4;
     const int seg = tid & 7, lrow = tid >> 3;          // loader: rows lrow + 32 u of the tile, floats 4 seg .. + 3 of the chunk
-    const int nq = (p.C + KC - 1) / KC, nk = p.win * nq;
+    const int nq = (p.C + CONV_KC - 1) / CONV_KC, nk = p.win * nq;
 
     long aoff[4];
     f32x4 ra[4], rw[4];
@@ -122,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
                 aoff[u] = r < M ? window_row(p.ids, p.lda, r, j, p.pad, p.T) : -1;
             }
         }
-        const int c = q * KC + 4 * seg;
+        const int c = q * CONV_KC + 4 * seg;
         const bool cin = c < p.C;
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -137,8 +95,8 @@ __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
         float* const s = lds + st * STAGE;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            *reinterpret_cast<f32x4*>(s + (lrow + 32 * u) * PITCH + 4 * seg) = ra[u];
-            *reinterpret_cast<f32x4*>(s + A_FL + (lrow + 32 * u) * PITCH + 4 * seg) = rw[u];
+            *reinterpret_cast<f32x4*>(s + (lrow + 32 * u) * CONV_PITCH + 4 * seg) = ra[u];
+            *reinterpret_cast<f32x4*>(s + A_FL + (lrow + 32 * u) * CONV_PITCH + 4 * seg) = rw[u];
         }
     };
 
@@ -148,17 +106,17 @@ __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto compute = [&](int st) {
-        const float* const sa = lds + st * STAGE + (64 * wr + fi) * PITCH + 8 * kg;
-        const float* const sw = lds + st * STAGE + A_FL + (64 * wc + fi) * PITCH + 8 * kg;
+        const float* const sa = lds + st * STAGE + (64 * wr + fi) * CONV_PITCH + 8 * kg;
+        const float* const sw = lds + st * STAGE + A_FL + (64 * wc + fi) * CONV_PITCH + 8 * kg;
         Frag<SPLIT> x[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) x[i].load(sa + i * 16 * PITCH);
+        for (int i = 0; i < 4; ++i) x[i].load_frag(sa + i * 16 * CONV_PITCH);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             Frag<SPLIT> w;
-            w.load(sw + t * 16 * PITCH);
+            w.load_frag(sw + t * 16 * CONV_PITCH);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][t] = prod(w, x[i], acc[i][t]);
+            for (int i = 0; i < 4; ++i) acc[i][t] = frag_prod(w, x[i], acc[i][t]);
         }
     };
 
@@ -205,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
 
 // ---- weight gradient -------------------------------------------------------------------------------------------------
 constexpr int BO = 64, BC = 128;
-constexpr int WY_FL = BO * PITCH, WX_FL = BC * PITCH, WSTAGE = WY_FL + WX_FL;
+constexpr int WY_FL = BO * CONV_PITCH, WX_FL = BC * CONV_PITCH, WSTAGE = WY_FL + WX_FL;
 static_assert(2 * WSTAGE * 4 <= 81920, "two workgroups per CU");
 
 struct WgradParams {
@@ -234,14 +192,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradParams
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wo = wave & 1, wk = wave >> 1;
     const int fi = lane & 15, kg = lane >> 4;
-    const int nk = (m_end - m_begin + KC - 1) / KC;
+    const int nk = (m_end - m_begin + CONV_KC - 1) / CONV_KC;
 
     // loader: dY chunk [32 rows][64 o] = 2 segments per thread (row (tid >> 4) + 16 u, o 4 (tid & 15)); X chunk [32 rows][128 c] =
     // 4 segments (row (tid >> 5) + 8 u, c 4 (tid & 31)); both stored transposed: image[column][row]
     f32x4 ry[2], rx[4];
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     auto gload = [&](int k) {
-        const int m0 = m_begin + k * KC;
+        const int m0 = m_begin + k * CONV_KC;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int r = m0 + (tid >> 4) + 16 * u, o = o0 + 4 * (tid & 15);
@@ -261,13 +219,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradParams
         for (int u = 0; u < 2; ++u) {
             const int r = (tid >> 4) + 16 * u, o = 4 * (tid & 15);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sy[(o + e) * PITCH + r] = ry[u][e];
+            for (int e = 0; e < 4; ++e) sy[(o + e) * CONV_PITCH + r] = ry[u][e];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int r = (tid >> 5) + 8 * u, c = 4 * (tid & 31);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sx[(c + e) * PITCH + r] = rx[u][e];
+            for (int e = 0; e < 4; ++e) sx[(c + e) * CONV_PITCH + r] = rx[u][e];
         }
     };
 
@@ -278,17 +236,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradParams
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto compute = [&](int st) {
-        const float* const sy = lds + st * WSTAGE + (32 * wo + fi) * PITCH + 8 * kg;
-        const float* const sx = lds + st * WSTAGE + WY_FL + (64 * wk + fi) * PITCH + 8 * kg;
+        const float* const sy = lds + st * WSTAGE + (32 * wo + fi) * CONV_PITCH + 8 * kg;
+        const float* const sx = lds + st * WSTAGE + WY_FL + (64 * wk + fi) * CONV_PITCH + 8 * kg;
         Frag<SPLIT> y[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) y[i].load(sy + i * 16 * PITCH);
+        for (int i = 0; i < 2; ++i) y[i].load_frag(sy + i * 16 * CONV_PITCH);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             Frag<SPLIT> x;
-            x.load(sx + t * 16 * PITCH);
+            x.load_frag(sx + t * 16 * CONV_PITCH);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i][t] = prod(x, y[i], acc[i][t]);
+            for (int i = 0; i < 2; ++i) acc[i][t] = frag_prod(x, y[i], acc[i][t]);
         }
     };
 
@@ -346,7 +304,7 @@ WgradPlan wgrad_plan(int M, int N, int C, int win) {
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     long rps = ((long)M + splits - 1) / splits;
-    rps = (rps + KC - 1) / KC * KC;
+    rps = (rps + CONV_KC - 1) / CONV_KC * CONV_KC;
     w.rows_per_split = (int)rps;
     w.splits = (int)(((long)M + rps - 1) / rps);
     if (w.splits < 1) w.splits = 1;

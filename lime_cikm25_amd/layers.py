@@ -192,6 +192,65 @@ class Conv1D(nn.Module):
         raise NotImplementedError('Conv1D is a parameter holder: the CNN encoder runs ops.conv1d_window')
 
 
+class Conv2D_Pool(nn.Module):
+    """layers.py:138-190: parameter holder for the KCNN content encoder's knowledge-aware convolution -- nn.Conv2d(C, O, [w, 3]) over the
+    [C, T, 3] stack of word / entity / context rows, i.e. a 1-D convolution over 3 C channels, ReLU, and the maximum over the first P
+    positions (``conv`` for 'naive'; ``conv1`` .. ``conv3`` / ``conv4``, windows 1 / 2 / 3 (/ 4), for 'group3' / 'group4'); nn.Conv2d
+    default initialisation as the reference leaves it.  The arithmetic is ops.conv_pool; ``forward`` is never used on the HIP path.
+
+    Refused: 'group5' (the reference's assert of :141), group kernel counts that do not divide (:149, :154), and -- not in the
+    reference -- a per-convolution output count or input width that is no multiple of 4 (the kernels read and write 16 bytes at a
+    time)."""
+
+    def __init__(self, cnn_method, in_channels, cnn_kernel_num, cnn_window_size, last_channel_num):
+        super().__init__()
+        if cnn_method == 'group5':
+            raise NotImplementedError("cnn_method 'group5': the reference's Conv2D_Pool asserts against it (layers.py:141)")
+        if cnn_method not in ('naive', 'group3', 'group4'):
+            raise ValueError('unknown cnn_method %r' % (cnn_method,))
+        self.cnn_method = cnn_method
+        self.in_channels = in_channels
+        self.last_channel_num = last_channel_num
+        self.cnn_window_size = cnn_window_size
+        if cnn_method == 'naive':
+            if cnn_window_size <= 0:
+                raise ValueError('cnn_window_size %d must be positive' % cnn_window_size)
+            per_conv = cnn_kernel_num
+            self.conv = nn.Conv2d(in_channels, cnn_kernel_num, kernel_size=[cnn_window_size, last_channel_num],
+                                  padding=[(cnn_window_size - 1) // 2, 0])
+        else:
+            groups = 3 if cnn_method == 'group3' else 4
+            if cnn_kernel_num % groups != 0:
+                raise ValueError('cnn_method %r needs cnn_kernel_num %% %d == 0 (layers.py:149,154), got %d' % (cnn_method, groups, cnn_kernel_num))
+            per_conv = cnn_kernel_num // groups
+            self.conv1 = nn.Conv2d(in_channels, per_conv, kernel_size=[1, last_channel_num], padding=[0, 0])
+            self.conv2 = nn.Conv2d(in_channels, per_conv, kernel_size=[2, last_channel_num], padding=[0, 0])
+            self.conv3 = nn.Conv2d(in_channels, per_conv, kernel_size=[3, last_channel_num], padding=[1, 0])
+            if groups == 4:
+                self.conv4 = nn.Conv2d(in_channels, per_conv, kernel_size=[4, last_channel_num], padding=[1, 0])
+        if per_conv % 4 or in_channels % 4:
+            raise NotImplementedError('the conv + pool kernels need multiples of 4 for the outputs per convolution (%d) and the input '
+                                      'width (%d)' % (per_conv, in_channels))
+
+    def max_window(self):
+        return max(conv.kernel_size[0] for conv, _, _, _, _ in self.convs(1 << 20))
+
+    def convs(self, T):
+        """[(nn.Conv2d, first output column, window w, left padding p, pooled positions P)] in the reference's concatenation order, for
+        sequences of T tokens: 'naive' pools T - w + 1 positions (:169), the group convolutions T, T - 1, T - 2 (, T - 3) (:174-189)."""
+        if self.cnn_method == 'naive':
+            w = self.cnn_window_size
+            return [(self.conv, 0, w, (w - 1) // 2, T - w + 1)]
+        n = self.conv1.out_channels
+        out = [(self.conv1, 0, 1, 0, T), (self.conv2, n, 2, 0, T - 1), (self.conv3, 2 * n, 3, 1, T - 2)]
+        if self.cnn_method == 'group4':
+            out.append((self.conv4, 3 * n, 4, 1, T - 3))
+        return out
+
+    def forward(self, feature):
+        raise NotImplementedError('Conv2D_Pool is a parameter holder: the KCNN encoder runs ops.conv_pool')
+
+
 class LSTMHolder(nn.LSTM):
     """nn.LSTM as a parameter holder (newsEncoders.py:449-450: one bidirectional layer, batch_first): the reference's parameter names and
     layout (weight_ih_l0 [4h, E], weight_hh_l0 [4h, h], the two biases, and the same four with ``_reverse``; gate order i, f, g, o).  The

@@ -1,4 +1,4 @@
-"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE}-{CROWN,ATT,MHSA} scoring path (reference model.py:11-187)."""
+"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE,KCNN}-{CROWN,ATT,MHSA} scoring path (reference model.py:11-187)."""
 import torch
 import torch.nn as nn
 
@@ -15,6 +15,9 @@ _PAIRS = ((17, 3), (18, 4), (20, 6), (15, 1), (16, 2), (23, 9), (24, 10))
 # a content encoder that reads the body masks (CNE) adds user_content_mask / news_content_mask and their pair
 _USED_BODY_MASK = tuple(sorted(_USED + (7, 21)))
 _PAIRS_BODY_MASK = _PAIRS + ((21, 7),)
+# a content encoder that reads the title's entity ids (KCNN) adds user_title_entity / news_title_entity and their pair
+_USED_TITLE_ENTITY = tuple(sorted(_USED + (5, 19)))
+_PAIRS_TITLE_ENTITY = _PAIRS + ((19, 5),)
 
 
 _USER_ENCODERS = ('CROWN', 'ATT', 'MHSA')
@@ -31,7 +34,8 @@ class Model(nn.Module):
     """Same constructor, attributes (``model_name``, ``config``, ``news_encoder``, ``user_encoder``,
     ``news_embedding_dim``), ``initialize()`` and 26-tensor ``forward`` as the reference's Model
     (model.py:12-187); ``state_dict()`` has the reference's key set.  ``forward`` returns logits [B, N].
-    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3'), 'MHSA' or 'CNE';
+    ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3'), 'MHSA', 'CNE' or
+    'KCNN' (cnn_method 'naive', 'group3' or 'group4'; it reads the ``*_title_entity`` inputs);
     ``config.user_encoder`` the user encoder: 'CROWN', 'ATT' (NAML's additive attention) or 'MHSA' (NRMS's self-attention), in any
     pairing.
 
@@ -62,6 +66,8 @@ class Model(nn.Module):
             base_encoder = newsEncoders.MHSA(config)
         elif config.content_encoder == 'CNE':
             base_encoder = newsEncoders.CNE(config)
+        elif config.content_encoder == 'KCNN':
+            base_encoder = newsEncoders.KCNN(config)
         else:
             raise NotImplementedError('content_encoder %r is a baseline outside the scoring path' % config.content_encoder)
         self.news_encoder = newsEncoders.LIME(config=config, base_news_encoder=base_encoder)
@@ -81,8 +87,9 @@ class Model(nn.Module):
         self._graphs = {}
         # the inputs the captured graph copies in, per model: the body masks only where the content encoder reads them
         self.reads_content_mask = bool(getattr(base_encoder, 'reads_content_mask', False))
-        self._used = _USED_BODY_MASK if self.reads_content_mask else _USED
-        self._pairs = _PAIRS_BODY_MASK if self.reads_content_mask else _PAIRS
+        self.reads_title_entity = bool(getattr(base_encoder, 'reads_title_entity', False))
+        self._used = _USED_BODY_MASK if self.reads_content_mask else _USED_TITLE_ENTITY if self.reads_title_entity else _USED
+        self._pairs = _PAIRS_BODY_MASK if self.reads_content_mask else _PAIRS_TITLE_ENTITY if self.reads_title_entity else _PAIRS
 
     def _apply(self, fn, *args, **kwargs):
         self._graphs = {}                      # parameter storage moves: captured pointers are stale
@@ -113,7 +120,9 @@ class Model(nn.Module):
                                           news_category, news_subCategory, news_title_text, news_title_mask, news_content_text,
                                           news_freshness, news_user_topic_lifetime, remaining_lifetime,
                                           user_content_mask=user_content_mask if self.reads_content_mask else None,
-                                          news_content_mask=news_content_mask if self.reads_content_mask else None)
+                                          news_content_mask=news_content_mask if self.reads_content_mask else None,
+                                          user_title_entity=user_title_entity if self.reads_title_entity else None,
+                                          news_title_entity=news_title_entity if self.reads_title_entity else None)
         if (self.use_graph and ops.PROFILE is None and user_category.is_cuda
                 and not torch.cuda.is_current_stream_capturing()):
             return self._forward_graphed(args)
@@ -173,7 +182,8 @@ class Model(nn.Module):
     def score_impressions(self, user_category, user_subCategory, user_title_text, user_title_mask, user_content_text,
                           user_freshness, user_user_topic_lifetime, user_history_mask, news_category, news_subCategory,
                           news_title_text, news_title_mask, news_content_text, news_freshness, news_user_topic_lifetime,
-                          remaining_lifetime, n_src=None, rows_per_pass=16384, user_content_mask=None, news_content_mask=None):
+                          remaining_lifetime, n_src=None, rows_per_pass=16384, user_content_mask=None, news_content_mask=None,
+                          user_title_entity=None, news_title_entity=None):
         """Scoring-only layout of BASELINE config 5: B impressions with K candidates each -> logits [B, K] with the
         reference's EVAL semantics (util.py:86-111: every (impression, candidate) pair is its own row with N = 1, Q16),
         but every history is encoded ONCE instead of once per candidate.
@@ -187,6 +197,8 @@ class Model(nn.Module):
         Under CNE a history's encoding is NOT a function of the history alone -- the reference gates every text with the memory vector
         of the news at the same length-sorted position of the encoder call (newsEncoders.CNE) -- so nothing can be shared between the
         K candidates of an impression: the B * K expanded rows go through the eval forward as they are, in one pass.
+        ``user_title_entity`` [B, H, T] / ``news_title_entity`` [B, K, T]: the titles' entity ids, for the content encoder that reads
+        them (KCNN); a KCNN representation depends on the news alone, so the histories are still encoded once.
         """
         B, K = news_category.shape
         H = user_category.shape[1]
@@ -210,15 +222,20 @@ class Model(nn.Module):
                                         rows(news_user_topic_lifetime.contiguous()), rows(remaining_lifetime))
             return logits.view(B, K)
         ne, ue = self.news_encoder, self.user_encoder
+        if self.reads_title_entity and (user_title_entity is None or news_title_entity is None):
+            raise TypeError('the KCNN content encoder reads the title entity ids (user_title_entity, news_title_entity): pass them -- '
+                            'the ids are never guessed')
+        if not self.reads_title_entity:
+            user_title_entity = news_title_entity = None
         if news_user_topic_lifetime.dim() == 1:
             news_user_topic_lifetime = news_user_topic_lifetime.unsqueeze(1).expand(B, K)
         if news_freshness.dim() == 1:
             news_freshness = news_freshness.unsqueeze(1).expand(B, K)
         cand, hist = ne.encode_many([
             (news_title_text, news_title_mask, news_content_text, news_category, news_subCategory, news_freshness.contiguous(),
-             news_user_topic_lifetime.contiguous()),
+             news_user_topic_lifetime.contiguous(), None, news_title_entity),
             (user_title_text, user_title_mask, user_content_text, user_category, user_subCategory, user_freshness,
-             user_user_topic_lifetime)])                                              # [B, K, D], [B, H, D]
+             user_user_topic_lifetime, None, user_title_entity)])                     # [B, K, D], [B, H, D]
         rows = B * K
         if n_src is None and hasattr(ue, 'user_node_embedding'):      # CROWN's GraphSAGE alone; the other user encoders ignore n_src
             n_src = min(rows, H + ue.user_node_embedding.shape[0])
@@ -252,7 +269,8 @@ class Model(nn.Module):
         if self.reads_content_mask:
             return torch.empty((c.news_title_text.shape[0], 0), dtype=torch.float32, device=c.news_title_text.device)
         return self.news_encoder.build_content_cache(c.news_title_text, c.news_title_mask, c.news_abstract_text, c.news_category,
-                                                     c.news_subCategory, rows_per_pass=rows_per_pass)
+                                                     c.news_subCategory, rows_per_pass=rows_per_pass,
+                                                     title_entity=c.news_title_entity if self.reads_title_entity else None)
 
     @torch.no_grad()
     def score_behaviors(self, behaviors, rows, news_cache, n_src=None):
@@ -305,11 +323,15 @@ class Model(nn.Module):
             news_content_text = news_content_text.unsqueeze(1)
             if self.reads_content_mask:
                 news_content_mask = news_content_mask.unsqueeze(1)
+            if self.reads_title_entity:
+                news_title_entity = news_title_entity.unsqueeze(1)
             news_freshness = news_freshness.unsqueeze(1)
             news_user_topic_lifetime = news_user_topic_lifetime.unsqueeze(1)
             remaining_lifetime = remaining_lifetime.unsqueeze(1)
         if not self.reads_content_mask:
             news_content_mask = user_content_mask = None
+        if not self.reads_title_entity:
+            news_title_entity = user_title_entity = None
         with torch.no_grad():
             # candidate-aware attention weights depend on topic ids and the history mask only: side stream, joined below
             main = torch.cuda.current_stream()
@@ -320,9 +342,9 @@ class Model(nn.Module):
                                                           user_history_mask)
             news_representation, history_embedding = self.news_encoder.encode_many([
                 (news_title_text, news_title_mask, news_content_text, news_category, news_subCategory, news_freshness,
-                 news_user_topic_lifetime, news_content_mask),                   # model.py:171-173
+                 news_user_topic_lifetime, news_content_mask, news_title_entity),     # model.py:171-173
                 (user_title_text, user_title_mask, user_content_text, user_category, user_subCategory, user_freshness,
-                 user_user_topic_lifetime, user_content_mask)])                  # userEncoders.py:110-112
+                 user_user_topic_lifetime, user_content_mask, user_title_entity)])    # userEncoders.py:110-112
             main.wait_stream(side2)
             _, logits = self.user_encoder.match(history_embedding, news_category, news_subCategory, user_category,
                                                 user_subCategory, user_history_mask, news_representation,

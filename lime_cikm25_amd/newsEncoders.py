@@ -1,5 +1,5 @@
-"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN, NAML, MHSA and CNE
-(reference newsEncoders.py:38-161, 167-373, 439-532, 535-563, 566-595, 641-695, 806-828).
+"""Drop-in news encoders of the scoring path: FreshnessEncoder, LIME, CROWN, CNN, NAML, MHSA, CNE and KCNN
+(reference newsEncoders.py:38-161, 167-373, 439-532, 535-563, 566-595, 598-638, 641-695, 806-828).
 
 The modules keep the reference's attribute and parameter names, so ``state_dict()`` has the same
 183 keys and reference checkpoints load.  Standard torch containers
@@ -22,7 +22,7 @@ import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
 from . import ops
-from .layers import Attention, Conv1D, LinearHolder, LSTMHolder, MultiHeadAttention, ScaledDotProduct_CandidateAttention
+from .layers import Attention, Conv1D, Conv2D_Pool, LinearHolder, LSTMHolder, MultiHeadAttention, ScaledDotProduct_CandidateAttention
 
 # tokens encoded per pass of the token encoder: bounds the activation workspace (9.2 KB / token)
 MAX_TOKENS_PER_PASS = 4 * 1024 * 1024
@@ -260,18 +260,21 @@ class LIME(nn.Module):
         nn.init.xavier_uniform_(self.category_affine.weight)
         nn.init.zeros_(self.category_affine.bias)
 
-    def _base_encode(self, title_text, title_mask, content_text, category, subCategory, out, content_mask, pair_groups=None):
+    def _base_encode(self, title_text, title_mask, content_text, category, subCategory, out, content_mask, pair_groups=None,
+                     title_entity=None):
         """The content encoder's encode_flat; the body mask (and the reference calls' news counts) go to the encoder that reads them
-        (CNE) and to no other."""
+        (CNE) and to no other, the title's entity ids to KCNN."""
         enc = self.base_news_encoder
+        if getattr(enc, 'reads_title_entity', False):
+            return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out, title_entity=title_entity)
         if getattr(enc, 'reads_content_mask', False):
             return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out, content_mask, pair_groups)
         return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out)
 
     def encode_flat(self, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None,
-                    pair_groups=None):
+                    pair_groups=None, title_entity=None):
         """Flat batch of M news -> [M, output_dim].  title_text [M, T], content_text [M, L] int32; the rest [M].  content_mask [M, L]:
-        the body mask, read by the CNE content encoder alone."""
+        the body mask, read by the CNE content encoder alone.  title_entity [M, T] int32: the title's entity ids, read by KCNN alone."""
         M = title_text.shape[0]
         cdim = self.base_news_encoder.news_embedding_dim
         main = torch.cuda.current_stream()
@@ -281,7 +284,8 @@ class LIME(nn.Module):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self.freshness_encoder.encode_flat(freshness, lifetime, fused[:, cdim:])
-            self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups)
+            self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups,
+                              title_entity)
             main.wait_stream(side)
             gate = ops.linear(fused, self.gate.weight, self.gate.bias, act='sigmoid') if self.fusion_method == 'gated' else None
             return ops.fuse_rows(fused[:, :cdim], fused[:, cdim:], gate)
@@ -290,7 +294,8 @@ class LIME(nn.Module):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self.freshness_encoder.encode_flat(freshness, lifetime, fused[:, cdim:])
-            self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups)
+            self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups,
+                              title_entity)
             main.wait_stream(side)
             return fused
         # project(cat(content, fresh)) = content W_c^T + (fresh W_f^T + b), and fresh = tanh(dense(cat(E_f[b1], E_l[b2]))) takes one of
@@ -304,7 +309,7 @@ class LIME(nn.Module):
             pair = torch.add(fe.buckets(lifetime), fe.buckets(freshness), alpha=nb)                        # b_f * nb + b_l, int32 [M]
             table, _ = self.occurrence_tables()                                                           # [nb^2, final_dim]
         content = torch.empty((M, cdim), dtype=torch.float32, device=title_text.device)
-        self._base_encode(title_text, title_mask, content_text, category, subCategory, content, content_mask, pair_groups)
+        self._base_encode(title_text, title_mask, content_text, category, subCategory, content, content_mask, pair_groups, title_entity)
         main.wait_stream(side)
         return ops.linear(content, self.project.weight[:, :cdim], None, res=table, res_ids=pair)         # newsEncoders.py:152-153
 
@@ -332,7 +337,7 @@ class LIME(nn.Module):
         return fresh, None
 
     # ---- per-news content cache (eval: a news occurs in many impressions, its token encoders need to run once) ----------
-    def build_content_cache(self, title_text, title_mask, content_text, category, subCategory, rows_per_pass=8192):
+    def build_content_cache(self, title_text, title_mask, content_text, category, subCategory, rows_per_pass=8192, title_entity=None):
         """One row per news: everything of LIME's representation that depends on the news alone (all the token-encoder work).
 
         'concat' [n, output_dim]: the representation is project(cat(content(news), freshness(freshness, lifetime)))
@@ -341,8 +346,12 @@ class LIME(nn.Module):
         'add' [n, c]: the content (rep = content + freshness, :154-155).
         'gated' [n, 2 c]: columns :c the content, columns c: its half of the gate's pre-activation, content . W_g[:, :c]^T
         (rep = g content + (1 - g) freshness, g = sigmoid(gate(cat(content, freshness))), :156-159) -- one tensor, two column views.
-        ``encode_cached`` adds the occurrence's side.  Rebuild it when weights change."""
+        ``encode_cached`` adds the occurrence's side.  Rebuild it when weights change.
+        ``title_entity`` [n, T]: the titles' entity ids, for the content encoder that reads them (KCNN)."""
         n = title_text.shape[0]
+        reads_entity = getattr(self.base_news_encoder, 'reads_title_entity', False)
+        if reads_entity and title_entity is None:
+            raise TypeError('the KCNN content encoder reads the title entity ids: pass title_entity -- the ids are never guessed')
         cdim = self.base_news_encoder.news_embedding_dim
         dev = title_text.device
         ident = isinstance(self.project, nn.Identity)
@@ -352,9 +361,10 @@ class LIME(nn.Module):
         for r0 in range(0, n, rows_per_pass):
             r1 = min(n, r0 + rows_per_pass)
             content = cache[r0:r1, :cdim] if direct else torch.empty((r1 - r0, cdim), dtype=torch.float32, device=dev)
+            kw = dict(title_entity=_i32(title_entity[r0:r1]).contiguous()) if reads_entity else {}
             self.base_news_encoder.encode_flat(_i32(title_text[r0:r1]).contiguous(), title_mask[r0:r1].contiguous(),
                                                _i32(content_text[r0:r1]).contiguous(), _i32(category[r0:r1]).contiguous(),
-                                               _i32(subCategory[r0:r1]).contiguous(), content)
+                                               _i32(subCategory[r0:r1]).contiguous(), content, **kw)
             if gated:
                 ops.linear(content, self.gate.weight[:, :cdim], None, out=cache[r0:r1, cdim:])
             elif not ident:
@@ -386,15 +396,18 @@ class LIME(nn.Module):
     def encode_many(self, groups):
         """Encode several [B, n, ...] groups (candidates, history) in ONE pass over the kernels.
 
-        Each group: (title_text, title_mask, content_text, category, subCategory, freshness, lifetime[, content_mask]) -- the optional
-        eighth member is the body mask, which the CNE content encoder reads (every group carries it then, or none does).
+        Each group: (title_text, title_mask, content_text, category, subCategory, freshness, lifetime[, content_mask[, title_entity]])
+        -- the optional eighth member is the body mask, which the CNE content encoder reads, the optional ninth the title's entity ids,
+        which KCNN reads (every group carries them then, or none does).
         Returns one [B, n, output_dim] tensor per group.
         """
-        shapes, flat, cmasks = [], [[] for _ in range(7)], []
+        shapes, flat, cmasks, ents = [], [[] for _ in range(7)], [], []
         for group in groups:
             tt, tm, ct, cat, sub, fr, lt = group[:7]
             if len(group) > 7 and group[7] is not None:
                 cmasks.append(group[7].reshape(tt.shape[0] * tt.shape[1], -1))
+            if len(group) > 8 and group[8] is not None:
+                ents.append(_i32(group[8]).reshape(tt.shape[0] * tt.shape[1], -1))
             B, n = tt.shape[0], tt.shape[1]
             shapes.append((B, n))
             if fr.dim() == 1:
@@ -411,7 +424,13 @@ class LIME(nn.Module):
             raise ValueError('encode_many: the body mask must be given for every group or for none')
         cmask = None if not cmasks else (cmasks[0].contiguous() if len(cmasks) == 1 else _cat_rows(cmasks))
         # each group is one call of the reference's news encoder (model.py:171, userEncoders.py:110): CNE pairs its gates per call
-        out = self.encode_flat(*cat_all, content_mask=cmask, pair_groups=[B * n for B, n in shapes] if cmask is not None else None)
+        if ents and len(ents) != len(groups):
+            raise ValueError('encode_many: the title entity ids must be given for every group or for none')
+        if getattr(self.base_news_encoder, 'reads_title_entity', False) and not ents:
+            raise TypeError('the KCNN content encoder reads the title entity ids: every group needs them -- the ids are never guessed')
+        ent = None if not ents else (ents[0].contiguous() if len(ents) == 1 else _cat_rows(ents))
+        out = self.encode_flat(*cat_all, content_mask=cmask, pair_groups=[B * n for B, n in shapes] if cmask is not None else None,
+                               title_entity=ent)
         res, r0 = [], 0
         for (B, n) in shapes:
             res.append(out[r0:r0 + B * n].view(B, n, -1))
@@ -432,10 +451,16 @@ class LIME(nn.Module):
             rep = training.news_flat(self, *_flat_inputs(title_text, title_mask, content_text, category, subCategory),
                                      fr.float().reshape(-1).contiguous(), lt.float().reshape(-1).contiguous(),
                                      content_mask=None if content_mask is None else content_mask.reshape(B * n, -1).contiguous(),
-                                     pair_groups=[B * n])
+                                     pair_groups=[B * n], title_entity=self._entity_rows(title_entity, B * n))
             return rep.view(B, n, -1)
+        reads_entity = getattr(self.base_news_encoder, 'reads_title_entity', False)
         return self.encode_many([(title_text, title_mask, content_text, category, subCategory, news_freshness,
-                                  news_user_topic_lifetime, content_mask)])[0]
+                                  news_user_topic_lifetime, content_mask, title_entity if reads_entity else None)])[0]
+
+    def _entity_rows(self, title_entity, rows):
+        if not getattr(self.base_news_encoder, 'reads_title_entity', False) or title_entity is None:
+            return None
+        return _i32(title_entity).reshape(rows, -1).contiguous()
 
 
 class NewsEncoder(nn.Module):
@@ -459,6 +484,7 @@ class NewsEncoder(nn.Module):
         self.affine = nn.Linear(config.word_embedding_dim, config.word_embedding_dim, bias=True)   # unused upstream too
 
     reads_content_mask = False      # True: encode_flat needs the body mask (CNE alone)
+    reads_title_entity = False      # True: encode_flat needs the title's entity ids (KCNN alone)
 
     def initialize(self):
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
@@ -472,11 +498,18 @@ class NewsEncoder(nn.Module):
         B, n = title_text.shape[0], title_text.shape[1]
         flat = _flat_inputs(title_text, title_mask, content_text, category, subCategory)
         cmask = content_mask.reshape(B * n, -1).contiguous() if (self.reads_content_mask and content_mask is not None) else None
+        ent = None
+        if self.reads_title_entity:
+            if title_entity is None:
+                raise TypeError('the KCNN content encoder reads the title entity ids: pass title_entity')
+            ent = _i32(title_entity).reshape(B * n, -1).contiguous()
         from . import training
         if training.wants_train_path(self, self.dropout_rate):
-            return training.content_flat(self, *flat, content_mask=cmask, pair_groups=[B * n]).view(B, n, -1)
+            return training.content_flat(self, *flat, content_mask=cmask, pair_groups=[B * n], title_entity=ent).view(B, n, -1)
         out = torch.empty((B * n, self.news_embedding_dim), dtype=torch.float32, device=title_text.device)
-        if self.reads_content_mask:
+        if self.reads_title_entity:
+            self.encode_flat(*flat, out, title_entity=ent)
+        elif self.reads_content_mask:
             self.encode_flat(*flat, out, content_mask=cmask, pair_groups=[B * n])      # one call of the reference's encoder
         else:
             self.encode_flat(*flat, out)
@@ -1156,6 +1189,89 @@ class CNN(NewsEncoder):
             self._encode(ids[m0:m1], mask[m0:m1], out[m0:m1, :K], self._compact_applicable(ids))
         ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
                       emb_out=out[:, K:])                                                                               # :561
+        return out
+
+
+class KCNN(NewsEncoder):
+    """newsEncoders.py:598-638: DKN's knowledge-aware CNN over the title -- per token the word row, tanh(M_entity(entity row)) and
+    tanh(M_context(context row)) side by side, Conv2D_Pool (layers.py:138-190: convolution over the three, ReLU, maximum over the pooled
+    positions), then feature_fusion with the encoder's own trainable category table.  -> [B, n, cnn_kernel_num + 100].  No mask, no
+    dropout in front of the convolution: padding tokens take part (:630-633).
+
+    ``entity_embedding`` / ``context_embedding`` are filled by the caller (``load_state_dict`` or ``.weight.data.copy_``) as the word
+    table is; the reference unpickles them from the cwd (:607-610).
+
+    The convolution, ReLU and pooling are ops.conv_pool (csrc/conv_pool_sp_f32.hip): the word rows are gathered straight into its A
+    operand by word id.  The two transforms take whichever has fewer rows: a [entity_size, C] table tanh(E M^T + b) per forward, gathered
+    inside the kernel by entity id, or one row per token through the GEMM's own gather (ops.linear(a_ids=...))."""
+
+    reads_title_entity = True
+
+    def __init__(self, config):
+        super().__init__(config)
+        if getattr(config, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError("compute_dtype %r: the KCNN content encoder is built for fp32 (compute_dtype='fp32')" % config.compute_dtype)
+        self.max_title_length = config.max_title_length
+        self.cnn_kernel_num = config.cnn_kernel_num
+        self.entity_embedding_dim = config.entity_embedding_dim
+        self.context_embedding_dim = config.context_embedding_dim
+        self.entity_embedding = nn.Embedding(num_embeddings=config.entity_size, embedding_dim=self.entity_embedding_dim)
+        self.context_embedding = nn.Embedding(num_embeddings=config.entity_size, embedding_dim=self.context_embedding_dim)
+        self.M_entity = LinearHolder(self.entity_embedding_dim, self.word_embedding_dim, bias=True)
+        self.M_context = LinearHolder(self.context_embedding_dim, self.word_embedding_dim, bias=True)
+        self.knowledge_cnn = Conv2D_Pool(config.cnn_method, config.word_embedding_dim, config.cnn_kernel_num, config.cnn_window_size, 3)
+        if config.max_title_length < self.knowledge_cnn.max_window():
+            raise ValueError('max_title_length %d is smaller than the largest convolution window %d: no position is left to pool '
+                             '(layers.py:169-189)' % (config.max_title_length, self.knowledge_cnn.max_window()))
+        if self.entity_embedding_dim % 4 or self.context_embedding_dim % 4:
+            raise NotImplementedError('the entity / context tables must be a multiple of 4 wide')
+        self.news_embedding_dim = config.cnn_kernel_num + config.category_embedding_dim + config.subCategory_embedding_dim
+        self.category_embedding = nn.Embedding(config.category_num, config.category_embedding_dim)     # trainable (re-created, :615)
+
+    def initialize(self):                                                                              # :617-623
+        super().initialize()
+        nn.init.xavier_uniform_(self.M_entity.weight, gain=nn.init.calculate_gain('tanh'))
+        nn.init.zeros_(self.M_entity.bias)
+        nn.init.xavier_uniform_(self.M_context.weight, gain=nn.init.calculate_gain('tanh'))
+        nn.init.zeros_(self.M_context.bias)
+        nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
+
+    def sources(self, word_ids, entity_ids):
+        """The three (a, ids) sources of ops.conv_pool for the flat int32 word / entity ids of the tokens (:630-633)."""
+        n_tok = word_ids.numel()
+        src = [(self.word_embedding.weight, word_ids)]
+        for table, lin in ((self.entity_embedding.weight, self.M_entity), (self.context_embedding.weight, self.M_context)):
+            if table.shape[0] <= n_tok:
+                src.append((ops.linear(table, lin.weight, lin.bias, act='tanh'), entity_ids))
+            else:
+                src.append((ops.linear(table, lin.weight, lin.bias, act='tanh', a_ids=entity_ids), None))
+        return src
+
+    def conv_pool_into(self, src, T, out, fused=None):
+        """Conv2D_Pool over the sources' sequences of T tokens -> out [n, cnn_kernel_num] (the group convolutions write column slices)."""
+        for conv, col, w, p, P in self.knowledge_cnn.convs(T):
+            ops.conv_pool(src, ops.conv_pool_pack(conv.weight), w, p, P, T, bias=conv.bias, out=out[:, col:col + conv.out_channels],
+                          fused=fused)
+        return out
+
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None, title_entity=None):
+        _no_train_dropout(self, self.dropout_rate)
+        if title_entity is None:
+            raise TypeError('the KCNN content encoder reads the title entity ids (title_entity): the ids are never guessed')
+        M, T = title_text.shape
+        if tuple(title_entity.shape) != (M, T):
+            raise ValueError('title_entity must be [%d, %d] like title_text, got %s' % (M, T, tuple(title_entity.shape)))
+        if T < self.knowledge_cnn.max_window():
+            raise ValueError('titles of %d tokens are shorter than the largest convolution window %d' % (T, self.knowledge_cnn.max_window()))
+        K = self.cnn_kernel_num
+        ids = _i32(title_text).contiguous()
+        ent = _i32(title_entity).contiguous()
+        step = max(1, MAX_TOKENS_PER_PASS // T)
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            self.conv_pool_into(self.sources(ids[m0:m1].reshape(-1), ent[m0:m1].reshape(-1)), T, out[m0:m1, :K])   # :630-635
+        ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
+                      emb_out=out[:, K:])                                                                           # :637
         return out
 
 

@@ -1656,6 +1656,172 @@ def conv1d_window_wgrad(dy, a, window, T, ids=None, out=None, accumulate=False):
     return out
 
 
+CONV_POOL_T_MAX = 128            # the fused conv + pool kernel's limit: a 128-row tile holds whole sequences (csrc/conv_pool_sp_f32.hip)
+# Measured on MI355X (tools/bench_kcnn.py --part kernel, DESIGN.md "KCNN content encoder"; interleaved, medians of 15 rounds): three
+# sources of 300 columns -> 400, window 3, at 1760 x 32 tokens the fused launch takes 0.971 ms against 1.053 ms for conv1d_window per
+# source + relu_maxpool, at 8192 x 32 (one pass of the content cache) 4.325 against 4.774 ms.  So ``conv_pool`` takes the fused kernel
+# wherever it applies (T <= 128) unless asked for the other form (fused=False, or LIME_FUSED_CONV_POOL=0 for the whole process).
+FUSED_CONV_POOL = os.environ.get('LIME_FUSED_CONV_POOL', '1') == '1'
+
+
+def conv_pool_pack(weight):
+    """nn.Conv2d weight [O, C, window, n_src] -> the [O, n_src * window * C] operand of ``conv_pool``: column (src * window + j) * C + c."""
+    O, C, win, n_src = weight.shape
+    return weight.permute(0, 3, 2, 1).reshape(O, n_src * win * C).contiguous()
+
+
+def _pool_outputs(n_seq, N, device, out, arg, want_arg):
+    if out is None:
+        out = torch.empty((n_seq, N), dtype=torch.float32, device=device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (n_seq, N):
+        raise ValueError('out must be [%d, %d], got %s' % (n_seq, N, tuple(out.shape)))
+    if arg is None and want_arg:
+        arg = torch.empty((n_seq, N), dtype=torch.int32, device=device)
+    if arg is not None:
+        _mat(arg, 'arg', dtype=torch.int32)
+        if tuple(arg.shape) != (n_seq, N):
+            raise ValueError('arg must be [%d, %d], got %s' % (n_seq, N, tuple(arg.shape)))
+    return out, arg
+
+
+def relu_maxpool(pre, n_seq, T, P, bias=None, out=None, arg=None, want_arg=False, n_seq_dev=None):
+    """pooled[s, o] = max(0, max_{t < P} pre[s T + t, o] + bias[o]) and (``want_arg`` / ``arg``) the smallest t attaining it, -1 where
+    the pooled value is 0 -- ``lime_relu_maxpool_f32``.  pre [n_seq * T, N] (may be a column slice).  -> out, or (out, arg)."""
+    lib = _lib.load()
+    _mat(pre, 'pre')
+    N = pre.shape[1]
+    if pre.shape[0] != n_seq * T:
+        raise ValueError('pre has %d rows, expected n_seq * T = %d' % (pre.shape[0], n_seq * T))
+    if not 1 <= P <= T:
+        raise ValueError('relu_maxpool: P = %d outside 1 .. T = %d' % (P, T))
+    out, arg = _pool_outputs(n_seq, N, pre.device, out, arg, want_arg)
+    if N % 4 or _ld(pre) % 4 or _ld(out) % 4 or pre.data_ptr() % 16 or out.data_ptr() % 16:
+        raise ValueError('relu_maxpool: N and the leading dimensions must be multiples of 4, pre and out 16-byte aligned')
+    if n_seq_dev is not None:
+        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
+    if n_seq > 0:
+        check(lib.lime_relu_maxpool_f32(_p(pre), _ld(pre), _p(_vec(bias, 'bias', N)), _p(out), _ld(out), _p(arg), 0 if arg is None else _ld(arg),
+                                        n_seq, T, P, N, _p(n_seq_dev), _stream()), 'lime_relu_maxpool_f32')
+    return out if arg is None else (out, arg)
+
+
+def relu_maxpool_bwd(dpooled, arg, T, out=None):
+    """dpre [n_seq * T, N]: dpooled[s, o] at row s T + arg[s, o] where arg >= 0, zeros everywhere else; every element is written
+    (``lime_relu_maxpool_bwd_f32``: no atomics, no pre-zeroing)."""
+    lib = _lib.load()
+    _mat(dpooled, 'dpooled')
+    _mat(arg, 'arg', dtype=torch.int32)
+    n_seq, N = dpooled.shape
+    if tuple(arg.shape) != (n_seq, N):
+        raise ValueError('arg must be [%d, %d], got %s' % (n_seq, N, tuple(arg.shape)))
+    if T <= 0:
+        raise ValueError('relu_maxpool_bwd: T must be positive')
+    if out is None:
+        out = torch.empty((n_seq * T, N), dtype=torch.float32, device=dpooled.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (n_seq * T, N):
+        raise ValueError('out must be [%d, %d], got %s' % (n_seq * T, N, tuple(out.shape)))
+    if N % 4 or _ld(dpooled) % 4 or _ld(out) % 4 or dpooled.data_ptr() % 16 or out.data_ptr() % 16:
+        raise ValueError('relu_maxpool_bwd: N and the leading dimensions must be multiples of 4, dpooled and out 16-byte aligned')
+    if n_seq > 0:
+        check(lib.lime_relu_maxpool_bwd_f32(_p(dpooled), _ld(dpooled), _p(arg), _ld(arg), _p(out), _ld(out), n_seq, T, N, _stream()),
+              'lime_relu_maxpool_bwd_f32')
+    return out
+
+
+def conv_pool_odd_window(window, pad):
+    """(window', shift): the odd window with pad' = (window' - 1) / 2 that holds the taps of (window, pad) behind ``shift`` zero taps --
+    how ``conv1d_window`` and its gradients express the even windows (2, 0) and (4, 1) of Conv2D_Pool."""
+    shift = max(0, window - 1 - 2 * pad)                  # zero taps in front: pad' - pad with window' = window + shift
+    wodd = window + shift
+    if wodd % 2 == 0 or (wodd - 1) // 2 != pad + shift:
+        raise ValueError('conv_pool: (window, pad) = (%d, %d) is not an odd centred window behind zero first taps' % (window, pad))
+    return wodd, shift
+
+
+def conv_pool_unfused_weights(w, n_src, window, pad, C):
+    """The packed [N, n_src * window * C] weight of ``conv_pool`` -> per source the [N, window' * C] operand of ``conv1d_window``
+    (``conv_pool_odd_window``: zero first taps for an even window)."""
+    wodd, shift = conv_pool_odd_window(window, pad)
+    N = w.shape[0]
+    w4 = w.view(N, n_src, window, C)
+    if shift == 0:
+        return [w4[:, s].reshape(N, window * C) for s in range(n_src)], wodd
+    out = w.new_zeros((n_src, N, wodd, C))
+    out[:, :, shift:] = w4.permute(1, 0, 2, 3)
+    return [out[s].view(N, wodd * C) for s in range(n_src)], wodd
+
+
+def conv_pool(sources, w, window, pad, P, T, bias=None, out=None, arg=None, want_arg=False, n_seq_dev=None, fused=None):
+    """pooled[s, o] = max(0, max_{t < P} (bias[o] + sum_src sum_{j < window} X_src(s T + t + j - pad) . w[o, (src window + j) C : + C])),
+    optionally with the position ``arg`` [n_seq, N] int32 of the maximum (-1 where pooled is 0): the KCNN convolution + ReLU + max pool.
+
+    sources: 1 to 3 pairs (a, ids): a [rows, C] dense rows (ids None) or the [V, C] table that the int32 ``ids`` [n_seq * T] gather from.
+    w: [N, n_src * window * C] (``conv_pool_pack``).  out may be a column slice of a wider output.  n_seq_dev: int32 device tensor (1
+    element): sequences >= min(n_seq_dev, n_seq) are neither computed nor written.
+    fused True: ``lime_conv_pool_f32``, one launch, T <= 128.  False: per source ``conv1d_window`` (accumulate) into a dense
+    [n_seq * T, N] pre-activation, then ``relu_maxpool`` -- the fallback for longer sequences and the A/B partner.  None: FUSED_CONV_POOL
+    where the fused kernel applies."""
+    lib = _lib.load()
+    if not 1 <= len(sources) <= 3:
+        raise ValueError('conv_pool takes 1 to 3 sources, got %d' % len(sources))
+    _mat(w, 'w')
+    N = w.shape[0]
+    C = sources[0][0].shape[1] if isinstance(sources[0][0], torch.Tensor) and sources[0][0].dim() == 2 else 0
+    M = None
+    for a, ids in sources:
+        _mat(a, 'a')
+        if a.shape[1] != C:
+            raise ValueError('conv_pool: every source must be %d wide, got %d' % (C, a.shape[1]))
+        if ids is not None:
+            _vec(ids, 'ids', dtype=torch.int32)
+        m = a.shape[0] if ids is None else ids.numel()
+        if M is not None and m != M:
+            raise ValueError('conv_pool: the sources have %d and %d rows' % (M, m))
+        M = m
+        if C % 4 or _ld(a) % 4 or a.data_ptr() % 16:
+            raise ValueError('conv_pool: the source width and leading dimensions must be multiples of 4 and the sources 16-byte aligned')
+    n_src = len(sources)
+    if T <= 0 or M % T:
+        raise ValueError('conv_pool: %d rows is not a whole number of sequences of T = %d' % (M, T))
+    n_seq = M // T
+    if not (1 <= window <= T and 0 <= pad < window and 1 <= P <= T):
+        raise ValueError('conv_pool: window %d, pad %d, P %d outside what T = %d allows' % (window, pad, P, T))
+    if w.shape[1] != n_src * window * C:
+        raise ValueError('w must be [N, n_src * window * C] = [%d, %d], got %s' % (N, n_src * window * C, tuple(w.shape)))
+    if N % 4 or _ld(w) % 4 or w.data_ptr() % 16:
+        raise ValueError('conv_pool: N and the leading dimension of w must be multiples of 4 and w 16-byte aligned')
+    out, arg = _pool_outputs(n_seq, N, w.device, out, arg, want_arg)
+    bias = _vec(bias, 'bias', N)
+    if n_seq_dev is not None:
+        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
+    if fused is None:
+        fused = FUSED_CONV_POOL and T <= CONV_POOL_T_MAX
+    if n_seq == 0:
+        return out if arg is None else (out, arg)
+    if fused:
+        if T > CONV_POOL_T_MAX:
+            raise ValueError('conv_pool: the fused kernel holds whole sequences in a tile, T = %d > %d (use fused=False)' % (T, CONV_POOL_T_MAX))
+        a = _lib.ConvPoolArgs()
+        for s, (src, ids) in enumerate(sources):
+            a.a[s], a.lda[s], a.ids[s] = src.data_ptr(), _ld(src), (None if ids is None else ids.data_ptr())
+        a.w, a.ldw, a.bias = w.data_ptr(), _ld(w), (None if bias is None else bias.data_ptr())
+        a.pooled, a.ldp = out.data_ptr(), _ld(out)
+        a.arg, a.ldarg = (None, 0) if arg is None else (arg.data_ptr(), _ld(arg))
+        a.n_seq_dev = None if n_seq_dev is None else n_seq_dev.data_ptr()
+        a.n_seq, a.T, a.N, a.C, a.n_src, a.window, a.pad, a.P = n_seq, T, N, C, n_src, window, pad, P
+        check(lib.lime_conv_pool_f32(ctypes.byref(a), _stream()), 'lime_conv_pool_f32')
+        return out if arg is None else (out, arg)
+    ws, wodd = conv_pool_unfused_weights(w, n_src, window, pad, C)
+    pre = torch.empty((M, N), dtype=torch.float32, device=w.device)
+    m_dev = None if n_seq_dev is None else n_seq_dev * T
+    for s, (src, ids) in enumerate(sources):
+        conv1d_window(src, ws[s], wodd, T, ids=ids, out=pre, accumulate=s > 0, m_dev=m_dev)
+    relu_maxpool(pre, n_seq, T, P, bias=bias, out=out, arg=arg, n_seq_dev=n_seq_dev)
+    return out if arg is None else (out, arg)
+
+
 ATTN_POOL_T_MAX, ATTN_POOL_A_MAX = 128, 512       # the fused attention pool's limits (csrc/attn_pool_sp_f32.hip)
 # Measured on MI355X (tools/bench_naml.py --part pool, DESIGN.md "NAML content encoder"): at 1760 x 32, 1760 x 128 and 1760 x 4 rows
 # (D = A = 400) the fused launch takes 1.38x, 1.37x and 2.2x the time of linear(tanh) + additive_pool, so ``attn_pool`` keeps the two

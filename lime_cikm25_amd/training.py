@@ -658,6 +658,85 @@ def cnn_content(enc, title_text, title_mask, category, subCategory):
     return torch.cat([rep, cat_e, sub_e], dim=1)                                                                # :561, :221-226
 
 
+class _ConvPool(torch.autograd.Function):
+    """layers.Conv2D_Pool (layers.py:165-190) on M = sequences x T token rows of three dense [M, C] sources: per convolution
+    (window w, left padding p, pooled positions P; weight [n, C, w, 3], bias [n]) ONE launch of the fused conv + ReLU + max-pool kernel
+    into its column slice of the output, the position of every maximum kept.  Backward: the pooling's backward writes the
+    pre-activation gradient (dpooled at the kept position, zeros elsewhere); from there the weight gradient per source on the windowed
+    weight-gradient kernel, the bias gradient as a column sum and the data gradients on the windowed conv with the taps reversed
+    (summed over the convolutions in order) -- an even window as the next odd one behind a zero first tap."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, x2, T, specs, *params):
+        xs = [x.contiguous() for x in (x0, x1, x2)]
+        M = xs[0].shape[0]
+        n_seq = M // T
+        ws, bs = params[0::2], params[1::2]
+        K = sum(w.shape[0] for w in ws)
+        out = torch.empty((n_seq, K), dtype=torch.float32, device=x0.device)
+        arg = torch.empty((n_seq, K), dtype=torch.int32, device=x0.device)
+        col = 0
+        for w, b, (win, pad, P) in zip(ws, bs, specs):
+            n = w.shape[0]
+            ops.conv_pool([(x, None) for x in xs], ops.conv_pool_pack(w), win, pad, P, T, bias=b, out=out[:, col:col + n],
+                          arg=arg[:, col:col + n], fused=T <= ops.CONV_POOL_T_MAX)
+            col += n
+        ctx.dims = (T, specs)
+        ctx.save_for_backward(arg, *xs, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        arg, x0, x1, x2, *ws = ctx.saved_tensors
+        xs = (x0, x1, x2)
+        T, specs = ctx.dims
+        M, C = x0.shape
+        dout = dout.contiguous()
+        dxs = [torch.empty((M, C), dtype=torch.float32, device=x0.device) if ctx.needs_input_grad[s] else None for s in range(3)]
+        grads = []
+        col = 0
+        for i, (w, (win, pad, P)) in enumerate(zip(ws, specs)):
+            n = w.shape[0]
+            wodd, shift = ops.conv_pool_odd_window(win, pad)
+            dpre = ops.relu_maxpool_bwd(dout[:, col:col + n], arg[:, col:col + n], T)                    # [M, n]
+            dws = []
+            for s in range(3):
+                if dxs[s] is not None:
+                    w_s = nn.functional.pad(w[:, :, :, s], (shift, 0))                                   # [n, C, wodd]: zero first taps
+                    ops.conv1d_window(dpre, ops.conv1d_pack_dgrad(w_s), wodd, T, out=dxs[s], accumulate=i > 0)
+                dw = ops.conv1d_window_wgrad(dpre, xs[s], wodd, T).view(n, wodd, C)[:, shift:]           # [n, win, C]
+                dws.append(dw.permute(0, 2, 1))
+            grads += [torch.stack(dws, dim=3).contiguous(), ops.colsum(dpre)]
+            col += n
+        return tuple(dxs) + (None, None) + tuple(grads)
+
+
+def kcnn_content(enc, title_text, title_entity, category, subCategory):
+    """newsEncoders.KCNN.forward (newsEncoders.py:625-638; title only, no mask) on M flat news -> [M, cnn_kernel_num + 100].  The only
+    dropout sites are the two of feature_fusion (:221-226): 0 the category embedding, 1 the subcategory embedding."""
+    if title_entity is None:
+        raise TypeError('the KCNN content encoder reads the title entity ids (title_entity): the ids are never guessed')
+    M, T = title_text.shape
+    p = float(enc.dropout.p) if enc.training else 0.0
+    seed = _draw_seed() if p > 0 else 0
+    x0 = embedding(enc.word_embedding.weight, title_text, hot_id=0).view(M * T, -1)                             # :630
+    e = embedding(enc.entity_embedding.weight, title_entity, hot_id=0).view(M * T, -1)                          # :631
+    c = embedding(enc.context_embedding.weight, title_entity, hot_id=0).view(M * T, -1)                         # :632
+    x1 = linear(e, enc.M_entity, act='tanh')                                                                    # :633
+    x2 = linear(c, enc.M_context, act='tanh')
+    convs = enc.knowledge_cnn.convs(T)
+    params = []
+    for conv, _, _, _, _ in convs:
+        params += [conv.weight, conv.bias]
+    rep = _ConvPool.apply(x0, x1, x2, T, tuple((w, pad, P) for _, _, w, pad, P in convs), *params)              # :635
+    cat_e = embedding(enc.category_embedding.weight, category)
+    sub_e = embedding(enc.subCategory_embedding.weight, subCategory)
+    if p > 0:
+        cat_e = _Dropout.apply(cat_e, p, seed, 0)
+        sub_e = _Dropout.apply(sub_e, p, seed, 1)
+    return torch.cat([rep, cat_e, sub_e], dim=1)                                                                # :637, :221-226
+
+
 def _conv_c(conv, x, T):
     """layers.Conv1D + ReLU of a parameter holder (layers.Conv1D) over M = sequences x T token rows x [M, C] -> [M, cnn_kernel_num]."""
     convs = conv.convs()
@@ -931,10 +1010,10 @@ def lifetime_weighted_logits(w, user, news, remaining_lifetime):
     return base * weight
 
 
-def content_flat(enc, title_text, title_mask, content_text, category, subCategory, content_mask=None, pair_groups=None):
-    """The base content encoder (CROWN: newsEncoders.py:302-373, CNN: :548-563, NAML: :671-695, MHSA: :582-595) on M flat news with
-    autograd -> [M, dim]."""
-    from .newsEncoders import CNE, CNN, CROWN, MHSA, NAML
+def content_flat(enc, title_text, title_mask, content_text, category, subCategory, content_mask=None, pair_groups=None, title_entity=None):
+    """The base content encoder (CROWN: newsEncoders.py:302-373, CNN: :548-563, NAML: :671-695, MHSA: :582-595, KCNN: :625-638) on M flat
+    news with autograd -> [M, dim]."""
+    from .newsEncoders import CNE, CNN, CROWN, KCNN, MHSA, NAML
     if getattr(enc, 'compute_dtype', 'fp32') != 'fp32':
         raise NotImplementedError("compute_dtype %r is a scoring option (BASELINE config 3); the training step is fp32: build the "
                                   "model with compute_dtype='fp32' to train" % enc.compute_dtype)
@@ -949,20 +1028,24 @@ def content_flat(enc, title_text, title_mask, content_text, category, subCategor
         return naml_content(enc, title_text, content_text, category, subCategory)
     if isinstance(enc, CNE):
         return cne_content(enc, title_text, title_mask, content_text, content_mask, category, subCategory, pair_groups)
-    raise NotImplementedError('the training path covers the CROWN, CNN, NAML, MHSA and CNE content encoders')
+    if isinstance(enc, KCNN):
+        return kcnn_content(enc, title_text, title_entity, category, subCategory)
+    raise NotImplementedError('the training path covers the CROWN, CNN, NAML, MHSA, CNE and KCNN content encoders')
 
 
-def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None, pair_groups=None):
-    """LIME.forward (newsEncoders.py:140-161) on M flat news with autograd -> [M, 400].  content_mask: the body mask, read by CNE alone."""
+def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None, pair_groups=None,
+              title_entity=None):
+    """LIME.forward (newsEncoders.py:140-161) on M flat news with autograd -> [M, 400].  content_mask: the body mask, read by CNE alone;
+    title_entity: the title's entity ids, read by KCNN alone."""
     content = content_flat(ne.base_news_encoder, title_text, title_mask, content_text, category, subCategory, content_mask=content_mask,
-                           pair_groups=pair_groups)
+                           pair_groups=pair_groups, title_entity=title_entity)
     return lime_tail(ne, content, freshness, lifetime)
 
 
 def forward_train(model, user_category, user_subCategory, user_title_text, user_title_mask, user_content_text, user_freshness,
                   user_user_topic_lifetime, user_history_mask, news_category, news_subCategory, news_title_text, news_title_mask,
                   news_content_text, news_freshness, news_user_topic_lifetime, remaining_lifetime, user_content_mask=None,
-                  news_content_mask=None):
+                  news_content_mask=None, user_title_entity=None, news_title_entity=None):
     """Model.forward with [B, N] candidates (model.py:171-187), recording the autograd graph.  Candidates and history go
     through the news encoder as one flat batch of B (N + H) news.  After the token encoders come the content tail, freshness
     and project per news, then the CROWN user encoder and the lifetime-weighted dot product: 3 % of the FLOPs in some 300
@@ -984,7 +1067,9 @@ def forward_train(model, user_category, user_subCategory, user_title_text, user_
                     flat1(news_freshness.float(), user_freshness.float()).contiguous(),
                     flat1(news_user_topic_lifetime.float(), user_user_topic_lifetime.float()).contiguous(),
                     content_mask=None if news_content_mask is None or user_content_mask is None else flat2(news_content_mask, user_content_mask),
-                    pair_groups=[B * N, B * H])                # the reference's two encoder calls (model.py:171, userEncoders.py:110)
+                    pair_groups=[B * N, B * H],                # the reference's two encoder calls (model.py:171, userEncoders.py:110)
+                    title_entity=None if news_title_entity is None or user_title_entity is None else
+                    i32(flat2(news_title_entity, user_title_entity)))
     cand = rep[:B * N].view(B, N, -1)
     hist = rep[B * N:].view(B, H, -1)
     return user_logits(model.user_encoder, model.remaining_lifetime_weighting, hist, cand, i32(news_category).contiguous(),
