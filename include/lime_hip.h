@@ -984,6 +984,30 @@ int lime_mask_lengths(const uint8_t* mask, int32_t R, int32_t T, int32_t min_len
 int lime_gate_mul_f32(const float* x, const float* g, float* out, int64_t rows, int32_t cols, int32_t div, int32_t mode, float scale,
                       const int32_t* n_rows_dev, void* stream);
 
+/* =====================================================================================================
+ * CNE's per-news recurrence cache (csrc/seq_cache_f32.hip; newsEncoders.CNERecurrenceCache).  The LSTM output h_t of a text and the
+ * hidden-state half of its gate pre-activation, H h_t (newsEncoders.py:517-518), depend on the news alone: the cache keeps both for the
+ * live tokens only, PACKED -- news i owns the rows offsets[i] .. offsets[i] + lens[i] - 1 of [sum(lens), C] tensors (C = 2 hidden_dim),
+ * token slots 0 .. lens[i] - 1 in order; offsets int64 [n + 1] is the exclusive prefix sum of lens int32 [n].
+ *
+ * lime_seq_pack_f32: dst[offsets[i] + t, :] = src[i S + t, :] for t < min(lens[i], S), i < n -- a dense [n S, C] chunk into the packed
+ * rows.  offsets holds DESTINATION rows (of dst as passed); no other row of dst is written.
+ *
+ * lime_cne_gate_cached_f32: the cross-selective gate of a batch from the cache, one launch.  For batch slot r < min(*n_rows_dev, cap)
+ * (n_rows_dev NULL: cap) and token slot t < S, with j = idx[r] (int32 news index into the cache; every id must be in [0, n) --
+ * unchecked, as in lime_gather_rows_f32):
+ *     out[r S + t, :] = t < lens[j] ?  h[offsets[j] + t, :] * sigmoid(hh[offsets[j] + t, :] + tm[r, :])  :  0
+ * tm [cap, C] is the partner's memory term M m_partner + b per slot.  Rows behind a length are written as zeros (the attention GEMM
+ * behind the gate reads all cap S rows); rows of slots >= *n_rows_dev are not touched.
+ *
+ * Both: C % 4 == 0, S >= 1, n / cap >= 0 (0: LIME_OK without a launch), src / dst / h / hh / tm / out 16-byte aligned
+ * (LIME_ERR_BAD_ARG otherwise); 16-byte loads and stores, 64-bit row offsets, no LDS, no atomics.  Every output element is one fixed
+ * expression of its own operands: a row's bits depend neither on its slot nor on n_rows_dev. */
+int lime_seq_pack_f32(const float* src, const int32_t* lens, const int64_t* offsets, float* dst, int32_t n, int32_t S, int32_t C,
+                      void* stream);
+int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* offsets, const int32_t* lens, const int32_t* idx,
+                             const float* tm, float* out, int32_t cap, int32_t S, int32_t C, const int32_t* n_rows_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

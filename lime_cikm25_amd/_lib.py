@@ -330,6 +330,10 @@ SIGNATURES = {
                                          c_int32, c_int32, c_int32, c_void_p]),
     'lime_mask_lengths': (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'lime_gate_mul_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    # CNE's per-news recurrence cache: dense chunk -> packed live rows, and the gate of a batch from the packed rows
+    'lime_seq_pack_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    'lime_cne_gate_cached_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                           c_void_p, c_void_p]),
 }
 
 _lib = None

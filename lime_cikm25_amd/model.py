@@ -272,14 +272,38 @@ class Model(nn.Module):
                                                      c.news_subCategory, rows_per_pass=rows_per_pass,
                                                      title_entity=c.news_title_entity if self.reads_title_entity else None)
 
+    def build_recurrence_cache(self, device_corpus, news_per_pass=None):
+        """CNE alone: the per-news recurrence cache of ``score_behaviors(..., recurrence_cache=...)`` -- every news of a ``DeviceCorpus``
+        through the input projection, the LSTM and the H GEMM once (newsEncoders.CNE.build_recurrence_cache; packed, 6.4 KB per live
+        token at the defaults).  Any other content encoder has ``build_news_cache`` for this and is refused with a ValueError."""
+        if self.config.content_encoder != 'CNE':
+            raise ValueError('content_encoder %r has no recurrence cache (it is the CNE content encoder\'s): use build_news_cache'
+                             % self.config.content_encoder)
+        c = device_corpus
+        return self.news_encoder.base_news_encoder.build_recurrence_cache(c.news_title_text, c.news_title_mask, c.news_abstract_text,
+                                                                          c.news_abstract_mask, news_per_pass=news_per_pass)
+
     @torch.no_grad()
-    def score_behaviors(self, behaviors, rows, news_cache, n_src=None):
+    def score_behaviors(self, behaviors, rows, news_cache, n_src=None, recurrence_cache=None, rows_per_forward=None):
         """Scores of the (impression, candidate) rows `rows` of a dev / test ``DeviceBehaviors`` -- the function of
         util.compute_scores' forward (util.py:86-111, eval mode, N = 1 per row) -- from the news cache: no token encoder
         runs, the history and the candidate of a row are looked up by news index and only their freshness half, the user
         encoder and the match are computed.  ``n_src`` as in score_impressions (default: the number of rows, capped).
         Under CNE (an empty cache, ``build_news_cache``) the rows' batch goes through the eval forward instead: a dev / test split and
-        a model in eval mode."""
+        a model in eval mode.
+
+        ``recurrence_cache`` (CNE alone, ``build_recurrence_cache``; ValueError under another content encoder): the candidates and the
+        histories of the rows are encoded from it in one pass -- no LSTM step and no hidden-state GEMM runs, only the gates, the
+        attentions, LIME's freshness tail and the match.  ``rows_per_forward`` = p: the pass stands for the reference forwards over the
+        consecutive chunks of p rows (the last may be short) -- the gates read the partners those forwards give (their news counts are
+        p candidates and p . H history news per chunk) and the GraphSAGE source count defaults to the chunk's rows -- however many rows
+        the pass holds; None: one forward over all rows.  A cache built from other parameter values raises RuntimeError: rebuild it
+        after the weights change."""
+        if recurrence_cache is not None:
+            if self.config.content_encoder != 'CNE':
+                raise ValueError('content_encoder %r does not read a recurrence cache (it is the CNE content encoder\'s)'
+                                 % self.config.content_encoder)
+            return self._score_from_recurrence(behaviors, rows, recurrence_cache, n_src, rows_per_forward)
         b = behaviors
         dev = news_cache.device
         rows = torch.as_tensor(rows, device=dev).long().reshape(-1)
@@ -287,17 +311,7 @@ class Model(nn.Module):
         ne, ue, c = self.news_encoder, self.user_encoder, b.corpus
         hist_idx, cand_idx = b.hist_index[rows], b.cand_index[rows]                       # [R, H], [R, 1]
         flat_h, flat_c = hist_idx.reshape(-1).long(), cand_idx.reshape(-1).long()
-        # the remaining lifetime per config.lifetime_type, as util.py:98-106 derives it from the batch
-        lt = getattr(self.config, 'lifetime_type', 'user_topic')
-        if lt == 'fixed':
-            remaining = self.config.fixed_lifetime - b.cand_freshness[rows]
-        elif lt == 'topic_wise':
-            cmap = torch.as_tensor(self.config.category_lifetime_map, dtype=torch.float32, device=dev)
-            remaining = cmap[c.news_category[cand_idx.reshape(-1).long()].long()].view_as(b.cand_freshness[rows]) - b.cand_freshness[rows]
-        elif lt == 'user_topic':
-            remaining = (b.cand_lifetime[rows] - b.cand_freshness[rows])
-        else:
-            raise ValueError('Invalid lifetime_type')
+        remaining = self._remaining_lifetime(b, rows, cand_idx)
         if self.reads_content_mask:
             # CNE: the rows' batch through the eval forward (see build_news_cache) -- the scores of util.compute_scores over these rows
             return self._forward_impl(*b.assemble(rows), remaining.view(R)).view(R)
@@ -309,6 +323,63 @@ class Model(nn.Module):
                              c.news_category[flat_h].view(R, H), c.news_subCategory[flat_h].view(R, H), b.hist_mask[rows],
                              cand, remaining_lifetime=remaining.view(R, 1), weighting=self.remaining_lifetime_weighting, n_src=n_src)
         return logits.view(R)
+
+    def _remaining_lifetime(self, behaviors, rows, cand_idx):
+        """The remaining lifetime of the rows' candidates per config.lifetime_type, as util.py:98-106 derives it from the batch."""
+        b = behaviors
+        lt = getattr(self.config, 'lifetime_type', 'user_topic')
+        if lt == 'fixed':
+            return self.config.fixed_lifetime - b.cand_freshness[rows]
+        if lt == 'topic_wise':
+            cmap = torch.as_tensor(self.config.category_lifetime_map, dtype=torch.float32, device=rows.device)
+            return cmap[b.corpus.news_category[cand_idx.reshape(-1).long()].long()].view_as(b.cand_freshness[rows]) - b.cand_freshness[rows]
+        if lt == 'user_topic':
+            return b.cand_lifetime[rows] - b.cand_freshness[rows]
+        raise ValueError('Invalid lifetime_type')
+
+    def _score_from_recurrence(self, behaviors, rows, rc, n_src, rows_per_forward):
+        """score_behaviors under CNE from the recurrence cache: one encoder pass over the R candidates and the R . H history news of the
+        rows (flat order: candidates, then histories, as ``_forward_impl`` encodes them), paired per chunk of rows_per_forward rows,
+        then the match per stretch of rows with one source count."""
+        b = behaviors
+        ne, ue, c = self.news_encoder, self.user_encoder, b.corpus
+        if self.training:
+            raise RuntimeError('score_behaviors is the eval-mode function: call model.eval() first')
+        if not ne.base_news_encoder.cache_is_current(rc):
+            raise RuntimeError('the recurrence cache was built from other parameter values (word table, LSTMs, title_H / content_H): '
+                               'rebuild it with build_recurrence_cache after the weights change')
+        dev = rc.title.lens.device
+        rows = torch.as_tensor(rows, device=dev).long().reshape(-1)
+        R, H = rows.numel(), b.hist_index.shape[1]
+        p = R if rows_per_forward is None else int(rows_per_forward)
+        if p < 1:
+            raise ValueError('rows_per_forward must be positive')
+        hist_idx, cand_idx = b.hist_index[rows], b.cand_index[rows]                       # [R, H], [R, 1]
+        idx = torch.cat([cand_idx.reshape(-1), hist_idx.reshape(-1)])                     # int32 [R + R H]
+        flat = idx.long()
+        chunk = torch.arange(R, device=dev) // p                                          # the reference forward a row belongs to
+        calls = torch.cat([2 * chunk, 2 * chunk.repeat_interleave(H) + 1])                # ... and its two encoder calls: candidates, history
+        cat_all, sub_all = c.news_category[flat], c.news_subCategory[flat]
+        rep = ne.encode_flat(None, c.news_title_mask[flat], None, newsEncoders._i32(cat_all), newsEncoders._i32(sub_all),
+                             torch.cat([b.cand_freshness[rows].reshape(-1), b.user_freshness[rows].reshape(-1)]),
+                             torch.cat([b.cand_lifetime[rows].reshape(-1), b.user_lifetime[rows].reshape(-1)]),
+                             content_mask=c.news_abstract_mask[flat], pair_groups=calls, recurrence=(rc, idx))
+        cand, hist = rep[:R].view(R, 1, -1), rep[R:].view(R, H, -1)
+        remaining = self._remaining_lifetime(b, rows, cand_idx).view(R, 1)
+        hist_mask = b.hist_mask[rows]
+        logits = torch.empty(R, dtype=torch.float32, device=dev)
+        full = (R // p) * p
+        for r0, r1, n in ((0, full, p), (full, R, R - full)):                             # the full chunks, then the short last one
+            if r1 == r0:
+                continue
+            src = n_src
+            if src is None:
+                src = min(n, H + ue.user_node_embedding.shape[0]) if hasattr(ue, 'user_node_embedding') else n
+            _, out = ue.match(hist[r0:r1], cat_all[r0:r1].view(-1, 1), sub_all[r0:r1].view(-1, 1), cat_all[R + r0 * H:R + r1 * H].view(-1, H),
+                              sub_all[R + r0 * H:R + r1 * H].view(-1, H), hist_mask[r0:r1], cand[r0:r1], remaining_lifetime=remaining[r0:r1],
+                              weighting=self.remaining_lifetime_weighting, n_src=src)
+            logits[r0:r1] = out.view(-1)
+        return logits
 
     def _forward_impl(self, user_ID, user_category, user_subCategory, user_title_text, user_title_mask, user_title_entity,
                       user_content_text, user_content_mask, user_content_entity, user_freshness, user_user_topic_lifetime,

@@ -261,10 +261,13 @@ class LIME(nn.Module):
         nn.init.zeros_(self.category_affine.bias)
 
     def _base_encode(self, title_text, title_mask, content_text, category, subCategory, out, content_mask, pair_groups=None,
-                     title_entity=None):
+                     title_entity=None, recurrence=None):
         """The content encoder's encode_flat; the body mask (and the reference calls' news counts) go to the encoder that reads them
-        (CNE) and to no other, the title's entity ids to KCNN."""
+        (CNE) and to no other, the title's entity ids to KCNN.  ``recurrence`` = (CNERecurrenceCache, news_index): CNE reads its
+        recurrence from the cache instead of the texts (encode_cached_flat)."""
         enc = self.base_news_encoder
+        if recurrence is not None:
+            return enc.encode_cached_flat(recurrence[0], recurrence[1], title_mask, content_mask, category, subCategory, out, pair_groups)
         if getattr(enc, 'reads_title_entity', False):
             return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out, title_entity=title_entity)
         if getattr(enc, 'reads_content_mask', False):
@@ -272,30 +275,33 @@ class LIME(nn.Module):
         return enc.encode_flat(title_text, title_mask, content_text, category, subCategory, out)
 
     def encode_flat(self, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None,
-                    pair_groups=None, title_entity=None):
+                    pair_groups=None, title_entity=None, recurrence=None):
         """Flat batch of M news -> [M, output_dim].  title_text [M, T], content_text [M, L] int32; the rest [M].  content_mask [M, L]:
-        the body mask, read by the CNE content encoder alone.  title_entity [M, T] int32: the title's entity ids, read by KCNN alone."""
-        M = title_text.shape[0]
+        the body mask, read by the CNE content encoder alone.  title_entity [M, T] int32: the title's entity ids, read by KCNN alone.
+        ``recurrence`` = (CNERecurrenceCache, news_index int32 [M]), CNE alone: the M news are news of the cache, their recurrence is read
+        from it and the texts are not (title_text / content_text may be None)."""
+        M = category.shape[0]
+        dev = category.device
         cdim = self.base_news_encoder.news_embedding_dim
         main = torch.cuda.current_stream()
-        side = _side_stream(title_text.device)
+        side = _side_stream(dev)
         if self.fusion_method in ('add', 'gated'):                                   # newsEncoders.py:154-159
-            fused = torch.empty((M, 2 * cdim), dtype=torch.float32, device=title_text.device)
+            fused = torch.empty((M, 2 * cdim), dtype=torch.float32, device=dev)
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self.freshness_encoder.encode_flat(freshness, lifetime, fused[:, cdim:])
             self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups,
-                              title_entity)
+                              title_entity, recurrence)
             main.wait_stream(side)
             gate = ops.linear(fused, self.gate.weight, self.gate.bias, act='sigmoid') if self.fusion_method == 'gated' else None
             return ops.fuse_rows(fused[:, :cdim], fused[:, cdim:], gate)
         if isinstance(self.project, nn.Identity):
-            fused = torch.empty((M, 2 * cdim), dtype=torch.float32, device=title_text.device)
+            fused = torch.empty((M, 2 * cdim), dtype=torch.float32, device=dev)
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self.freshness_encoder.encode_flat(freshness, lifetime, fused[:, cdim:])
             self._base_encode(title_text, title_mask, content_text, category, subCategory, fused[:, :cdim], content_mask, pair_groups,
-                              title_entity)
+                              title_entity, recurrence)
             main.wait_stream(side)
             return fused
         # project(cat(content, fresh)) = content W_c^T + (fresh W_f^T + b), and fresh = tanh(dense(cat(E_f[b1], E_l[b2]))) takes one of
@@ -308,8 +314,9 @@ class LIME(nn.Module):
         with torch.cuda.stream(side):
             pair = torch.add(fe.buckets(lifetime), fe.buckets(freshness), alpha=nb)                        # b_f * nb + b_l, int32 [M]
             table, _ = self.occurrence_tables()                                                           # [nb^2, final_dim]
-        content = torch.empty((M, cdim), dtype=torch.float32, device=title_text.device)
-        self._base_encode(title_text, title_mask, content_text, category, subCategory, content, content_mask, pair_groups, title_entity)
+        content = torch.empty((M, cdim), dtype=torch.float32, device=dev)
+        self._base_encode(title_text, title_mask, content_text, category, subCategory, content, content_mask, pair_groups, title_entity,
+                          recurrence)
         main.wait_stream(side)
         return ops.linear(content, self.project.weight[:, :cdim], None, res=table, res_ids=pair)         # newsEncoders.py:152-153
 
@@ -1393,6 +1400,40 @@ def _ones(n, device):
     return _grown(_ONES, n, device, 1024, lambda size: torch.ones(size, dtype=torch.float32, device=device))
 
 
+class CNERecurrenceCache:
+    """What CNE's recurrence leaves per news (CNE.build_recurrence_cache): a plain object, neither a buffer nor a parameter of the module
+    (``state_dict()`` does not know it).  Per text (``title``, ``body``), with n news, S token slots and C = 2 hidden_dim:
+
+        S        the token slots of the text (the width of its masks)
+        lens     int32 [n]          the sum of the mask after the slot-0 rule (>= 1)
+        offsets  int64 [n + 1]      the exclusive prefix sum of lens: news i owns the packed rows offsets[i] .. offsets[i + 1] - 1
+        h        fp32 [sum(lens), C]  the LSTM output of the live tokens (slots 0 .. len - 1 of each news, in order)
+        hh       fp32 [sum(lens), C]  h . H^T, the hidden-state half of the gate's pre-activation (no bias, no memory term)
+        m        fp32 [n, C]        the memory vector cat(c_n forward, c_n backward)
+
+    PACKED, not dense: a dense cache holds every token slot, (32 + 128) slots x 2 tensors x 800 floats = 1 MB per news at the defaults;
+    packed it is 2 tensors x 800 floats = 6.4 KB per LIVE token.  ``nbytes`` (``packed_nbytes``), per text:
+        2 . sum(lens) . C . 4  +  n . C . 4  +  n . 4  +  (n + 1) . 8.
+
+    ``versions``: the ``_version`` counters of the parameters the cache was built from (word table, both LSTMs, title_H, content_H).
+    They move with autograd-visible in-place updates (``load_state_dict``, torch optimizers) but NOT with edits through ``.data`` nor
+    with the native Adam step, which writes the flat parameter bucket directly; ``fingerprint`` (int64 device tensor: the sum of each
+    parameter's bit patterns) catches those.  ``CNE.cache_is_current`` compares both."""
+
+    Text = collections.namedtuple('Text', 'S lens offsets h hh m')
+
+    def __init__(self, title, body, versions, fingerprint):
+        self.title, self.body, self.versions, self.fingerprint = title, body, versions, fingerprint
+        self.n_news = title.lens.numel()
+        self.nbytes = sum(t.numel() * t.element_size() for text in (title, body) for t in text[1:])
+
+    @staticmethod
+    def packed_nbytes(lens_title, lens_body, hidden_dim):
+        """``nbytes`` of a cache over news with these title and body lengths (the formula of the class docstring)."""
+        C = 2 * hidden_dim
+        return sum(2 * sum(lens) * C * 4 + len(lens) * C * 4 + len(lens) * 4 + (len(lens) + 1) * 8 for lens in (lens_title, lens_body))
+
+
 class CNE(NewsEncoder):
     """newsEncoders.py:439-532, the collaborative news encoder of CNE-SUE: title and body each through a bidirectional LSTM, cross-selective
     gates (each text's LSTM output gated by the OTHER text's memory vector), a masked additive self attention and a scaled-dot-product
@@ -1424,7 +1465,11 @@ class CNE(NewsEncoder):
 
     Memory: gi is 2 . 4 hidden_dim floats per token (12.8 KB at hidden_dim 400; MAX_TOKENS_PER_PASS would allow 51 GB), so the recurrence
     runs in chunks of news whose gi stays within GI_BYTES_PER_PASS (``lstm_chunks``).  hout and c_n of all chunks are kept (2 hidden_dim
-    floats per token), and the gates pair over the whole call: a call has no size limit but memory."""
+    floats per token), and the gates pair over the whole call: a call has no size limit but memory.
+
+    Evaluation can take the recurrence from a per-news cache: lengths, LSTM outputs, H h_t and memory vectors depend on the news alone
+    (``build_recurrence_cache`` -> CNERecurrenceCache), the partners on the call (``encode_cached_flat``: pairing, M m_partner + b, one
+    gate launch from the packed rows, then the same attentions)."""
 
     GI_BYTES_PER_PASS = 4 << 30
     reads_content_mask = True
@@ -1485,17 +1530,30 @@ class CNE(NewsEncoder):
         """(int32 [cap], int32 [cap]): the news whose body memory gates the title of news i, and whose title memory gates its body, for
         calls of ``groups`` news each (:496-499, :517-521): sorted position j of the one order meets sorted position j of the other.
         Sorted = descending by length, TIED lengths in input order (a stable sort: the reference's default sort leaves the order of
-        ties to the torch build, so it is defined here; tools/make_cne_goldens.py runs the reference the same way).  Device-side, two
-        sorts per call; slots behind the groups pair with themselves."""
+        ties to the torch build, so it is defined here; tools/make_cne_goldens.py runs the reference the same way).
+
+        ``groups``: the news counts of the calls (a list: consecutive ranges), or an int64 device tensor with the call number of every
+        news (what a caller with hundreds of calls computes by arithmetic, Model.score_behaviors; the news of a call need not be
+        adjacent, their order within the call is their input order).  Device-side and TWO stable sorts whatever the number of calls: the
+        key call . 2^32 - length orders a text by call, then by descending length, and both texts have the same calls at the same sorted
+        positions, so the two orders meet position by position inside every call.  A list costs one slice fill per call behind the
+        first; slots behind the groups pair with themselves."""
         dev = lens_t.device
+        if isinstance(groups, torch.Tensor):
+            gid = groups
+        else:
+            gid = torch.zeros(sum(groups), dtype=torch.int64, device=dev)
+            o = 0
+            for g, n in enumerate(groups):
+                if g:
+                    gid[o:o + n] = g
+                o += n
+        total = gid.numel()
         pt, pb = torch.arange(cap, device=dev), torch.arange(cap, device=dev)
-        o = 0
-        for n in groups:
-            st = torch.sort(lens_t[o:o + n], descending=True, stable=True).indices
-            sc = torch.sort(lens_b[o:o + n], descending=True, stable=True).indices
-            pt[o + st] = sc + o                                    # title at sorted position j <- body memory at sorted position j
-            pb[o + sc] = st + o
-            o += n
+        st = torch.sort((gid << 32) - lens_t[:total], stable=True).indices
+        sc = torch.sort((gid << 32) - lens_b[:total], stable=True).indices
+        pt[st] = sc                                                # title at sorted position p <- body memory at sorted position p
+        pb[sc] = st
         return pt.to(torch.int32), pb.to(torch.int32)
 
     @staticmethod
@@ -1542,27 +1600,36 @@ class CNE(NewsEncoder):
         if pair_groups is not None:
             pairs = self.reference_pairs(texts[0][5], texts[1][5], pair_groups, cap)
         gated = []
-        for k, (H_, M_, att) in enumerate(((self.title_H, self.title_M, self.title_self_attention),
-                                           (self.content_H, self.content_M, self.content_self_attention))):
-            S, n_tok, mask, hout, _, _ = texts[k]
+        for k, (H_, M_) in enumerate(((self.title_H, self.title_M), (self.content_H, self.content_M))):
+            S, n_tok, _, hout, _, _ = texts[k]
             m_other = texts[1 - k][4]
             if pairs is not None:                                                                      # the reference's partner news
                 m_other = ops.gather_rows(pairs[k], m_other, torch.empty_like(m_other))
             tm = ops.linear(m_other, M_.weight, M_.bias, m_dev=n_dev)                                  # M(other text's memory vector)
             pre = ops.linear(hout, H_.weight, None, res=tm, res_div=S, m_dev=n_tok)                    # :517-518 before the sigmoid
-            g = ops.gate_mul(hout, pre, out=pre, n_rows_dev=n_tok)                                     # :520-521 (in place over pre)
+            gated.append(ops.gate_mul(hout, pre, out=pre, n_rows_dev=n_tok))                           # :520-521 (in place over pre)
+        return self._attend(gated, (mask_t, mask_b), n_dev, (texts[0][1], texts[1][1]), pooled)
+
+    def _attend(self, gated, masks, n_dev, n_toks, pooled):
+        """The encoder behind the gates (:524-529), from the gated LSTM outputs g [cap S, 2h] of the title and the body (zeros behind every
+        length), their masks [cap, S] (uint8, slot 0 set) and the live token rows n_toks = n_dev . S of each (device ints): self attention,
+        cross attention with the other text's self attention as the query, their sum -> pooled [cap, 4h].  Shared by the pass that runs the recurrence (``_encode``) and the pass that reads it
+        from the per-news cache (``encode_cached_flat``)."""
+        cap, h = masks[0].shape[0], self.hidden_dim
+        own = []
+        for g, mask, n_tok, att in zip(gated, masks, n_toks, (self.title_self_attention, self.content_self_attention)):
+            S = mask.shape[1]
             hidden = ops.linear(g, att.affine1.weight, att.affine1.bias, act='tanh', m_dev=n_tok)
-            own = ops.additive_pool(hidden, att.affine2.weight.view(-1), g, cap, S, mask=mask, n_seq_dev=n_dev)   # :524-525
-            gated.append((g, own))
-        ones = _ones(2 * h, dev)
+            own.append(ops.additive_pool(hidden, att.affine2.weight.view(-1), g, cap, S, mask=mask, n_seq_dev=n_dev))   # :524-525
+        ones = _ones(2 * h, gated[0].device)
         for k, att in enumerate((self.title_cross_attention, self.content_cross_attention)):
-            S, n_tok, mask = texts[k][:3]
-            g, own = gated[k]
-            q = ops.linear(gated[1 - k][1], att.Q.weight, att.Q.bias, m_dev=n_dev)                     # Q(other text's self attention)
+            g, mask = gated[k], masks[k]
+            S = mask.shape[1]
+            q = ops.linear(own[1 - k], att.Q.weight, att.Q.bias, m_dev=n_dev)                          # Q(other text's self attention)
             v = ops.linear(q, att.K.weight.t().contiguous(), None, m_dev=n_dev)                        # K^T q: K(h_t) . q = h_t . (K^T q)
-            terms = ops.gate_mul(g, v, div=S, scale=1.0 / att.attention_scalar, sigmoid=False, n_rows_dev=n_tok)
+            terms = ops.gate_mul(g, v, div=S, scale=1.0 / att.attention_scalar, sigmoid=False, n_rows_dev=n_toks[k])
             cross = ops.additive_pool(terms, ones, g, cap, S, mask=mask, n_seq_dev=n_dev)               # :527-528
-            ops.fuse_rows(own, cross, out=pooled[:, 2 * h * k:2 * h * (k + 1)])                         # :529
+            ops.fuse_rows(own[k], cross, out=pooled[:, 2 * h * k:2 * h * (k + 1)])                      # :529
         return pooled
 
     def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None, pair_groups=None):
@@ -1580,6 +1647,97 @@ class CNE(NewsEncoder):
         t_mask, b_mask = self.slot0_mask(title_mask.reshape(M, T)), self.slot0_mask(content_mask.reshape(M, L))
         self._encode(_i32(title_text).contiguous(), t_mask, _i32(content_text).contiguous(), b_mask, _row_count(M, dev), out[:, :4 * h],
                      pair_groups)                                                                       # :529 into the first 4h columns
+        ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
+                      emb_out=out[:, 4 * h:])                                                           # :531, :221-226
+        return out
+
+    # ---- per-news recurrence cache (eval: the recurrence and H h_t depend on the news alone; the gates' partners on the call) ----------
+    def _cache_sources(self):
+        """The parameters a recurrence cache is computed from."""
+        return [self.word_embedding.weight] + list(self.title_lstm.parameters()) + list(self.content_lstm.parameters()) + \
+               [self.title_H.weight, self.content_H.weight]
+
+    def _cache_state(self):
+        ps = self._cache_sources()
+        return tuple(p._version for p in ps), torch.stack([p.detach().view(torch.int32).sum(dtype=torch.int64) for p in ps])
+
+    def cache_is_current(self, cache):
+        """True while the parameters a CNERecurrenceCache was built from are what they were: the ``_version`` counters on the host first,
+        then the bit-pattern sums on the device (one small reduction per parameter and one read-back; see CNERecurrenceCache)."""
+        versions, fingerprint = self._cache_state()
+        return versions == cache.versions and fingerprint.device == cache.fingerprint.device and bool(torch.equal(fingerprint, cache.fingerprint))
+
+    @torch.no_grad()
+    def build_recurrence_cache(self, title_text, title_mask, content_text, content_mask, news_per_pass=None):
+        """-> CNERecurrenceCache over the n news title_text [n, T] / content_text [n, L] (int ids) with their masks: every text through the
+        input projection, the LSTM and the H GEMM ONCE, in chunks of news (``lstm_chunks``: a chunk's gi stays within
+        GI_BYTES_PER_PASS; ``news_per_pass`` caps a chunk further), each chunk's dense [chunk . S, 2h] results packed to the live
+        tokens (ops.seq_pack).  Dense this would be 1 MB per news at the defaults, packed it is 6.4 KB per live token
+        (CNERecurrenceCache).  One device -> host read per text (the packed row count).  Rebuild it when the weights change."""
+        _no_train_dropout(self, self.dropout_rate)
+        h = self.hidden_dim
+        table = self.word_embedding.weight
+        dev = table.device
+        n = title_text.shape[0]
+        if news_per_pass is not None and news_per_pass < 1:
+            raise ValueError('news_per_pass must be positive')
+        versions, fingerprint = self._cache_state()
+        texts = []
+        for ids, mask, lstm, H_ in ((title_text, title_mask, self.title_lstm, self.title_H),
+                                    (content_text, content_mask, self.content_lstm, self.content_H)):
+            S = ids.shape[1]
+            ids = _i32(ids).contiguous()
+            lens = ops.mask_lengths(self.slot0_mask(mask.reshape(n, S)), min_len=1)                    # :492-495
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(lens, 0, dtype=torch.int64)
+            rows = int(offsets[-1]) if n else 0
+            hp = torch.empty((rows, 2 * h), dtype=torch.float32, device=dev)
+            hhp = torch.empty((rows, 2 * h), dtype=torch.float32, device=dev)
+            m = torch.empty((n, 2 * h), dtype=torch.float32, device=dev)
+            wih, bias, whh = self.lstm_weights(lstm)
+            for c0, c1 in self.lstm_chunks(n, S) if n else []:
+                for r0 in range(c0, c1, news_per_pass or c1 - c0):
+                    r1 = min(c1, r0 + (news_per_pass or c1 - c0))
+                    gi = ops.linear(table, wih, bias, a_ids=ids[r0:r1].reshape(-1))                    # :501-502 gather + W_ih x + b
+                    hout, c = ops.lstm(gi, whh, lens[r0:r1], S)                                        # :509-510, :514-515
+                    del gi
+                    hh = ops.linear(hout, H_.weight, None)                                             # H h_t of :517-518
+                    ops.seq_pack(hout, lens[r0:r1], offsets[r0:r1], hp, S)
+                    ops.seq_pack(hh, lens[r0:r1], offsets[r0:r1], hhp, S)
+                    m[r0:r1] = c.transpose(0, 1).reshape(r1 - r0, 2 * h)                               # :512-513
+            texts.append(CNERecurrenceCache.Text(S, lens, offsets, hp, hhp, m))
+        return CNERecurrenceCache(texts[0], texts[1], versions, fingerprint)
+
+    def encode_cached_flat(self, cache, news_index, title_mask, content_mask, category, subCategory, out, pair_groups=None):
+        """``encode_flat`` for M news of a CNERecurrenceCache, news_index int32 [M]: ``_encode`` with the recurrence and the H GEMM read
+        from the cache.  What still runs per call: the pass's lengths (a gather), the pairing (``reference_pairs`` on them, per
+        ``pair_groups``: a list of counts or the per-news call numbers), the partner's memory term M m_partner + b (one small GEMM over
+        news, not over tokens), the gate from the packed rows in one launch (ops.cne_gate_cached) and, unchanged, the attentions behind
+        it (``_attend``).  title_mask [M, T] / content_mask [M, L] are the masks of the same news: they mask the attentions by position,
+        with the slot-0 rule on copies."""
+        _no_train_dropout(self, self.dropout_rate)
+        idx = _i32(news_index.reshape(-1)).contiguous()
+        M, h = idx.numel(), self.hidden_dim
+        dev = idx.device
+        T, L = cache.title.S, cache.body.S
+        if title_mask.numel() != M * T or content_mask.numel() != M * L:
+            raise ValueError('the masks must be [%d, %d] and [%d, %d] (the cache\'s token slots), got %s and %s'
+                             % (M, T, M, L, tuple(title_mask.shape), tuple(content_mask.shape)))
+        if pair_groups is not None and not isinstance(pair_groups, torch.Tensor) and sum(pair_groups) != M:
+            raise ValueError('pair_groups %s do not add up to the %d news of the pass' % (list(pair_groups), M))
+        masks = (self.slot0_mask(title_mask.reshape(M, T)), self.slot0_mask(content_mask.reshape(M, L)))
+        texts = (cache.title, cache.body)
+        pairs = None
+        if pair_groups is not None:
+            long_idx = idx.long()
+            pairs = self.reference_pairs(cache.title.lens[long_idx], cache.body.lens[long_idx], pair_groups, M)
+        gated = []
+        for k, M_ in enumerate((self.title_M, self.content_M)):
+            partner = idx if pairs is None else idx[pairs[k].long()]                                   # the reference's partner news
+            m_other = ops.gather_rows(partner, texts[1 - k].m, torch.empty((M, 2 * h), dtype=torch.float32, device=dev))
+            tm = ops.linear(m_other, M_.weight, M_.bias)                                               # M(partner's memory vector) + b
+            gated.append(ops.cne_gate_cached(texts[k].h, texts[k].hh, texts[k].offsets, texts[k].lens, idx, tm, texts[k].S))   # :517-521
+        self._attend(gated, masks, _row_count(M, dev), (_row_count(M * T, dev), _row_count(M * L, dev)), out[:, :4 * h])
         ops.topic_rep(category, subCategory, self.category_embedding.weight, self.subCategory_embedding.weight,
                       emb_out=out[:, 4 * h:])                                                           # :531, :221-226
         return out

@@ -2156,3 +2156,58 @@ def gate_mul(x, g, div=1, scale=1.0, sigmoid=True, out=None, n_rows_dev=None):
     check(lib.lime_gate_mul_f32(_p(x), _p(g), _p(out), rows, cols, div, 0 if sigmoid else 1, scale, _p(n_rows_dev), _stream()), 'lime_gate_mul_f32')
     return out
 
+
+
+# ---- CNE's per-news recurrence cache (csrc/seq_cache_f32.hip) -----------------------------------------------------------------------
+
+def _packed_rows(lens, offsets, n):
+    _vec(lens, 'lens', n, dtype=torch.int32)
+    _vec(offsets, 'offsets', dtype=torch.int64)
+    if offsets.numel() < (n if n is not None else lens.numel()):
+        raise ValueError('offsets must hold a destination row for every entry of lens')
+
+
+def seq_pack(src, lens, offsets, dst, S):
+    """``lime_seq_pack_f32``: dst[offsets[i] + t] = src[i S + t] for t < lens[i].  src [n S, C] contiguous, lens int32 [n], offsets
+    int64 [>= n] (destination rows), dst [rows, C] contiguous: the caller sizes it so that every offsets[i] + lens[i] fits."""
+    lib = _lib.load()
+    _mat(src, 'src')
+    _mat(dst, 'dst')
+    if S < 1:
+        raise ValueError('S must be >= 1')
+    n, C = lens.numel(), src.shape[1]
+    _packed_rows(lens, offsets, n)
+    if C % 4 or dst.shape[1] != C or src.shape[0] != n * S or not src.is_contiguous() or not dst.is_contiguous():
+        raise ValueError('seq_pack: src must be a contiguous [n S, C] (n = %d, S = %d), dst a contiguous [rows, C], C a multiple of 4; got %s, %s'
+                         % (n, S, tuple(src.shape), tuple(dst.shape)))
+    check(lib.lime_seq_pack_f32(_p(src), _p(lens), _p(offsets), _p(dst), n, S, C, _stream()), 'lime_seq_pack_f32')
+    return dst
+
+
+def cne_gate_cached(h, hh, offsets, lens, idx, tm, S, out=None, n_rows_dev=None):
+    """``lime_cne_gate_cached_f32``: out[r S + t] = h[offsets[j] + t] * sigmoid(hh[offsets[j] + t] + tm[r]) for t < lens[j], j = idx[r],
+    zeros behind the length -- CNE's gated LSTM output of a batch from the packed per-news cache, one launch.  h, hh [rows, C]
+    contiguous, offsets int64 [n + 1], lens int32 [n], idx int32 [cap] (news indices in [0, n): unchecked), tm [cap, C] contiguous
+    -> out [cap S, C].  n_rows_dev (int32 device tensor, 1 element): only the first min(n_rows_dev, cap) slots are written."""
+    lib = _lib.load()
+    _mat(h, 'h')
+    _mat(hh, 'hh')
+    _mat(tm, 'tm')
+    if S < 1:
+        raise ValueError('S must be >= 1')
+    _vec(idx, 'idx', dtype=torch.int32)
+    cap, C = idx.numel(), h.shape[1]
+    _packed_rows(lens, offsets, None)
+    if C % 4 or tuple(hh.shape) != tuple(h.shape) or tuple(tm.shape) != (cap, C) or not (h.is_contiguous() and hh.is_contiguous() and tm.is_contiguous()):
+        raise ValueError('cne_gate_cached: h and hh must be contiguous [rows, C] of one shape, tm a contiguous [cap, C] (cap = %d), C a multiple '
+                         'of 4; got %s, %s, %s' % (cap, tuple(h.shape), tuple(hh.shape), tuple(tm.shape)))
+    if out is None:
+        out = torch.empty((cap * S, C), dtype=torch.float32, device=h.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (cap * S, C) or not out.is_contiguous():
+        raise ValueError('cne_gate_cached: out must be a contiguous [cap S, C]')
+    if n_rows_dev is not None:
+        _vec(n_rows_dev, 'n_rows_dev', 1, dtype=torch.int32)
+    check(lib.lime_cne_gate_cached_f32(_p(h), _p(hh), _p(offsets), _p(lens), _p(idx), _p(tm), _p(out), cap, S, C, _p(n_rows_dev), _stream()),
+          'lime_cne_gate_cached_f32')
+    return out

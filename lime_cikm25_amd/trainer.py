@@ -28,7 +28,7 @@ def _mkdir(path):
 
 class Trainer:
     def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True, device_eval=False,
-                 device_sampling=False):
+                 device_sampling=False, cne_recurrence_cache=False):
         """``truth_file``: the dev truth file of config.py:262-276 ("<impression> [labels]" lines).  Without one it is written
         (as the reference's Config does at start-up) to ``<dev_res_dir>/../ref/truth-<dataset>.txt`` from ``corpus.dev_labels``
         (formats.build_corpus attaches them); a corpus without labels and no file is refused here, before any training.
@@ -41,6 +41,8 @@ class Trainer:
         counter-based stream of their own, a function of (seed, epoch, record) -- not numpy.random's, so ``np.random.seed`` no longer
         decides them (device_data.counter_negative_sampling gives the same tables on the host).  Under torch.distributed every rank
         computes the same table from (seed, epoch): no broadcast is needed.  Off by default: nothing changes without it.
+        ``cne_recurrence_cache``: under the CNE content encoder both cached dev passes build the per-news recurrence cache once per
+        epoch and score from it (util.compute_scores_cached / evaluate_cached_on_device, ``recurrence_cache``); off by default.
 
         Under torch.distributed (WORLD_SIZE in the environment) the process group is initialised and the device selected
         FIRST, so that TrainStep's broadcast of rank 0's parameters really runs (DistributedDataParallel does that at
@@ -80,6 +82,7 @@ class Trainer:
         self.device_eval = bool(device_eval) and self.cached_eval and getattr(corpus, 'dev_labels', None) is not None
         self.dc = device_corpus if device_corpus is not None else DeviceCorpus(corpus)
         self.dev = DeviceBehaviors.from_devtest(self.dc, corpus, 'dev')
+        self.cne_recurrence_cache = bool(cne_recurrence_cache)
         self.device_sampling = bool(device_sampling)
         self.train_split = DeviceBehaviors.train_resident(self.dc, corpus, config.negative_sample_num) if self.device_sampling else None
         self.step = TrainStep(model, lr=config.lr, weight_decay=config.weight_decay, gradient_clip_norm=config.gradient_clip_norm)
@@ -126,9 +129,10 @@ class Trainer:
         per = self.eval_batch_size
         if self.cached_eval and self.device_eval:
             return util.evaluate_cached_on_device(self.model, self.dev, self.corpus.dev_indices, self.corpus.dev_labels, result_file=out,
-                                                  rows_per_forward=per)
+                                                  rows_per_forward=per, recurrence_cache=self.cne_recurrence_cache)
         if self.cached_eval:
-            return util.compute_scores_cached(self.model, self.dev, self.corpus.dev_indices, out, self.truth_file, per)
+            return util.compute_scores_cached(self.model, self.dev, self.corpus.dev_indices, out, self.truth_file, per,
+                                              recurrence_cache=self.cne_recurrence_cache)
         rows = list(range(self.dev.num))
         batches = (self.dev.assemble(rows[i:i + per]) for i in range(0, len(rows), per))
         return util.compute_scores(self.model, batches, self.corpus.dev_indices, out, self.truth_file)

@@ -85,7 +85,7 @@ def compute_scores(model, batches, indices, result_file, truth_file=None):
         return scoring(truth_f, result_f)
 
 
-def compute_scores_cached(model, behaviors, indices, result_file, truth_file=None, rows_per_forward=None):
+def compute_scores_cached(model, behaviors, indices, result_file, truth_file=None, rows_per_forward=None, recurrence_cache=False):
     """The same dev / test pass from a per-news content cache (Model.build_news_cache + Model.score_behaviors): every news goes
     through the token encoders ONCE instead of once per (row, slot) -- the reference re-encodes all 51 news of every row
     (util.py:86-111).  ``behaviors``: a dev / test ``DeviceBehaviors``.  Rows are scored in chunks of ``rows_per_forward`` (default:
@@ -96,7 +96,9 @@ def compute_scores_cached(model, behaviors, indices, result_file, truth_file=Non
 
     Under the CNE content encoder there is nothing to cache per news (its gates read the memory vector of another news of the same
     encoder call): the cache is empty, every chunk of rows is encoded as ``compute_scores`` would encode that batch, and the scores
-    equal ``compute_scores``' only when the chunks are its batches (CNE's scores depend on the batch's composition)."""
+    equal ``compute_scores``' only when the chunks are its batches (CNE's scores depend on the batch's composition).
+    ``recurrence_cache`` = True (CNE alone): the recurrence of every news is cached once per call (Model.build_recurrence_cache) and
+    every chunk is scored from it -- the same chunks, the same partners, no LSTM step per chunk."""
     config = model.config
     if config.lifetime_type not in ('fixed', 'topic_wise', 'user_topic'):
         raise ValueError('Invalid lifetime_type')
@@ -109,10 +111,11 @@ def compute_scores_cached(model, behaviors, indices, result_file, truth_file=Non
     was_training = model.training
     model.eval()
     cache = model.build_news_cache(behaviors.corpus)
+    rc = dict(recurrence_cache=model.build_recurrence_cache(behaviors.corpus), rows_per_forward=per) if recurrence_cache else {}
     scores = []
     for r0 in range(0, behaviors.num, per):
         rows = list(range(r0, min(behaviors.num, r0 + per)))
-        scores.append(model.score_behaviors(behaviors, rows, cache, n_src=len(rows)).float().cpu())
+        scores.append(model.score_behaviors(behaviors, rows, cache, n_src=len(rows), **rc).float().cpu())
     model.train(was_training)
     scores = torch.cat(scores).tolist() if scores else []
     assert len(scores) == len(indices), 'one score per (impression, candidate) row'
@@ -138,10 +141,14 @@ def ranks_to_lists(ranks, indices):
 # tensors: 0.41 MB a row measured at the default configuration (H = 50), 3.4 GB for the 8192 rows of the default; the whole pass takes
 # the same time from 4096 rows a pass up (DESIGN.md "Device-side evaluation", tools/bench_eval.py).
 DEVICE_EVAL_ROWS_PER_PASS = 8192
+# ... and with CNE's recurrence cache.  A CNE pass holds token-level tensors for every news of every row: per row H + 1 news of
+# T + L token slots with the gated rows, the attention's hidden state and the cross terms (2h + attention_dim + 2h floats a slot),
+# 51 . 160 . 7.2 KB = 59 MB a row at the defaults (computed from the shapes, not measured), 15 GB for 256 rows.
+CNE_CACHED_ROWS_PER_PASS = 256
 
 
 def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=None, rows_per_forward=None,
-                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False):
+                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False, recurrence_cache=False):
     """The dev / test pass of ``compute_scores_cached`` without host round trips: one ``build_news_cache``, ``score_behaviors`` in
     passes of up to ``rows_per_pass`` rows that write into ONE device score buffer, one ``evaluate.device_scoring`` (ranks and
     metrics in one launch, csrc/rank_metrics.hip), one device -> host copy of the result.  ``labels``: the per-impression label
@@ -155,7 +162,14 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
     with n_src = its length.  (A pass of another row count may take GEMM kernels with another summation order: equal to fp32
     rounding, bitwise equal when rows_per_pass == rows_per_forward.)  ``rows_per_pass`` bounds memory: a pass allocates 0.41 MB a row at the
     default configuration (H = 50; measured, tools/bench_eval.py), 3.4 GB for the default of 8192 rows, and the whole pass is no
-    faster with more."""
+    faster with more.
+
+    Under the CNE content encoder a score also depends on the other rows of its encoder call (the gates' partners).  Without
+    ``recurrence_cache`` the CNE scores are those of ONE forward per pass of ``rows_per_pass`` rows, not of ``rows_per_forward``-row
+    forwards.  ``recurrence_cache`` = True (CNE alone) builds the per-news recurrence cache once per call
+    (Model.build_recurrence_cache) and passes it on with ``rows_per_forward``: a pass then scores many reference-sized chunks in one
+    launch chain and still pairs the gates per chunk, which gives the scores of ``compute_scores_cached(..., rows_per_forward)``; a
+    pass then holds at most CNE_CACHED_ROWS_PER_PASS rows (59 MB of token-level tensors a row at the defaults)."""
     config = model.config
     if config.lifetime_type not in ('fixed', 'topic_wise', 'user_topic'):
         raise ValueError('Invalid lifetime_type')
@@ -173,15 +187,16 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
     model.eval()
     try:
         cache = model.build_news_cache(behaviors.corpus)
+        rc = dict(recurrence_cache=model.build_recurrence_cache(behaviors.corpus), rows_per_forward=per) if recurrence_cache else {}
         dev = cache.device
         scores = torch.empty(num, dtype=torch.float32, device=dev)
         full = (num // per) * per                                          # the rows of the full chunks: n_src = per
-        step = max(1, rows_per_pass // per) * per
+        step = max(1, (min(rows_per_pass, CNE_CACHED_ROWS_PER_PASS) if recurrence_cache else rows_per_pass) // per) * per
         for r0 in range(0, full, step):
             r1 = min(full, r0 + step)
-            scores[r0:r1] = model.score_behaviors(behaviors, torch.arange(r0, r1, device=dev), cache, n_src=per).float()
+            scores[r0:r1] = model.score_behaviors(behaviors, torch.arange(r0, r1, device=dev), cache, n_src=per, **rc).float()
         if full < num:                                                     # the last, short chunk: n_src = its length
-            scores[full:] = model.score_behaviors(behaviors, torch.arange(full, num, device=dev), cache, n_src=num - full).float()
+            scores[full:] = model.score_behaviors(behaviors, torch.arange(full, num, device=dev), cache, n_src=num - full, **rc).float()
     finally:
         model.train(was_training)
     metrics, ranks = device_scoring(scores, indices, labels)
