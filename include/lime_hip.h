@@ -366,6 +366,41 @@ int lime_fill_pad_rows_f32(const int32_t* ids, const float* src, int64_t lds, fl
                            void* stream);
 int64_t lime_compact_sequences_workspace(int32_t n_seq);
 
+/*
+ * lime_compact_batch: lime_compact_sequences for the titles (ids_t [n, T]) and the bodies (ids_b [n, L]) of n news, and the NEWS level,
+ * in three launches (count, one-workgroup scan, emit).  The *_t / *_b outputs are lime_compact_sequences' for each text.  News level:
+ * nothing behind the token encoders mixes news (intent layers, intent attention, LIME.project: row-wise in eval mode), so the
+ * repetitions of the padding news need that arithmetic once.  News i repeats the padding news iff its title is all padding, its body
+ * is all padding and its key (cat, sub, the BITS of fresh and life) equals the key of the FIRST news with an all-padding title and
+ * body -- the representative.  A news that looks padded under another key stays live.
+ *   news_src  [n + 1]   compact news -> original news: live news in order, then the representative (-1 when the batch has no
+ *                       padding news; the count is then the number of live news); unused slots -1
+ *   news_inv  [n]       original news -> compact news
+ *   title_row / body_row [n + 1]   seq_inv_t[news_src[j]] / seq_inv_b[news_src[j]]; unused slots 0
+ *   cat_c, sub_c, fresh_c, life_c [n + 1]   the keys in compact order; unused slots 0
+ *   news_counts [4]     n_news, count_mult * n_news, live news, the representative's original index or -1  (device memory: m_dev arguments)
+ * Ordered and deterministic (no atomics).  work: lime_compact_batch_workspace(n) int32 words; the two sides' seq_src lists
+ * (compact -> original sequence) stay in it at work + n and work + 4 n + 2, n + 1 entries each.
+ */
+int lime_compact_batch(const int32_t* ids_t, int32_t T, int32_t pad_base_t, int32_t* seq_inv_t, int32_t* ids_c_t, int32_t* row_map_t,
+                       int32_t* tok_ids_t, int32_t* tok_rows_t, int32_t* counts_t, const int32_t* ids_b, int32_t L, int32_t pad_base_b,
+                       int32_t* seq_inv_b, int32_t* ids_c_b, int32_t* row_map_b, int32_t* tok_ids_b, int32_t* tok_rows_b, int32_t* counts_b,
+                       int32_t n, const int32_t* cat, const int32_t* sub, const float* fresh, const float* life, int32_t count_mult,
+                       int32_t* news_src, int32_t* news_inv, int32_t* title_row, int32_t* body_row, int32_t* cat_c, int32_t* sub_c,
+                       float* fresh_c, float* life_c, int32_t* news_counts, int32_t* work, void* stream);
+int64_t lime_compact_batch_workspace(int32_t n);
+
+/*
+ * lime_news_xin_f32: the pooled texts of the distinct news (lime_compact_batch) into the intent layers' input.  For j < min(cap, *n_news):
+ *   xin[j, 0 .. dim)        = mean of the nblk_t rows  title_blocks[title_row[j] * nblk_t + 0 .. nblk_t)
+ *   xin[cap + j, 0 .. dim)  = mean of the nblk_b rows  body_blocks[body_row[j] * nblk_b + 0 .. nblk_b)
+ * rows added in order and scaled by 1 / nblk as lime_mean_pool_count_f32 does (nblk = 1: the row itself); the other rows and the columns
+ * from dim on are left alone.  1 <= nblk <= 16, dim % 4 == 0, 16-byte aligned rows.
+ */
+int lime_news_xin_f32(const float* title_blocks, int64_t ld_t, int32_t nblk_t, const float* body_blocks, int64_t ld_b, int32_t nblk_b,
+                      const int32_t* title_row, const int32_t* body_row, const int32_t* n_news, float* xin, int64_t ldx, int32_t cap,
+                      int32_t dim, void* stream);
+
 /* lime_token_attention_rows_bf16: lime_token_attention_bf16 over compacted sequences (row_map / n_seq_dev as in
  * lime_token_attention_rows_f32); S in {32, 64, 128}, even head_dim. */
 int lime_token_attention_rows_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t ld_qkv, const int32_t* row_map,
@@ -431,6 +466,10 @@ int lime_topic_rep_f32(const int32_t* cat, const int32_t* sub, const float* cat_
  */
 int lime_intent_fuse_f32(const float* intents, const float* att_hidden, const float* affine2_t, const float* affine2_b,
                          float* content, int64_t ldc, int64_t M, int32_t k, int32_t D, int32_t A, void* stream);
+/* the same over the first min(M, *m_dev) news (device-side count; the rows behind it are neither read nor written); M stays the
+ * capacity that places the body half of intents / att_hidden */
+int lime_intent_fuse_count_f32(const float* intents, const float* att_hidden, const float* affine2_t, const float* affine2_b,
+                               float* content, int64_t ldc, int64_t M, int32_t k, int32_t D, int32_t A, const int32_t* m_dev, void* stream);
 
 /*
  * lime_additive_pool_f32: layers.Attention.forward (layers.py:285-300) after affine1:

@@ -182,6 +182,13 @@ SIGNATURES = {
     'lime_compact_sequences': (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p]),
     'lime_compact_sequences_workspace': (c_int64, [c_int32]),
+    'lime_compact_batch': (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'lime_compact_batch_workspace': (c_int64, [c_int32]),
+    'lime_news_xin_f32': (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_int32, c_int32, c_void_p]),
     'lime_pad_heads_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     'lime_mean_pool_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     'lime_mean_pool_count_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
@@ -194,6 +201,8 @@ SIGNATURES = {
                                      c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     'lime_intent_fuse_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
                                        c_int32, c_void_p]),
+    'lime_intent_fuse_count_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                             c_int32, c_void_p, c_void_p]),
     'lime_additive_pool_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p,
                                          c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     'lime_additive_pool_count_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p,

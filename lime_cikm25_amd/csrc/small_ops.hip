@@ -115,6 +115,37 @@ __global__ __launch_bounds__(256) void mean_pool_flat_kernel(const float* __rest
     po[0] = acc[0] * inv; po[1] = acc[1] * inv; po[2] = acc[2] * inv; po[3] = acc[3] * inv;
 }
 
+// The pooled title and body of the DISTINCT news of a batch (lime_compact_batch) into the intent layers' input: row j of the title
+// half is the mean of the nblk_t block rows of pooled sequence title_row[j], row cap + j of the body half the same from body_row[j];
+// one thread per (half, news, four columns), block rows added in row order and scaled as mean_pool_flat_kernel does (one block row:
+// the row itself).  News at or beyond *n_news are left alone.
+__global__ __launch_bounds__(256) void news_xin_kernel(const float* __restrict__ tb, long ld_t, int nblk_t, const float* __restrict__ bb,
+                                                        long ld_b, int nblk_b, const int* __restrict__ title_row,
+                                                        const int* __restrict__ body_row, const int* __restrict__ n_news,
+                                                        float* __restrict__ xin, long ldx, long cap, int dim) {
+    const int nc = dim >> 2;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const long n = min(cap, (long)*n_news);
+    if (e >= 2 * cap * nc) return;
+    const int half = e >= cap * nc;
+    const long q = e - half * cap * nc;
+    const long j = q / nc;
+    if (j >= n) return;
+    const int c = (int)(q - j * nc) * 4;
+    const int S = half ? nblk_b : nblk_t;
+    const long ld = half ? ld_b : ld_t;
+    const float* px = (half ? bb : tb) + (long)(half ? body_row[j] : title_row[j]) * S * ld + c;
+    float* po = xin + (half * cap + j) * ldx + c;
+    if (S == 1) {
+        *reinterpret_cast<f32x4*>(po) = *reinterpret_cast<const f32x4*>(px);
+        return;
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < S; ++t) acc += *reinterpret_cast<const f32x4*>(px + (long)t * ld);
+    const float inv = 1.0f / (float)S;
+    po[0] = acc[0] * inv; po[1] = acc[1] * inv; po[2] = acc[2] * inv; po[3] = acc[3] * inv;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // lifetime / freshness buckets: comparison against the fp32 cut points (lime_dev::bucket_of, dev_helpers.h)
 // ---------------------------------------------------------------------------------------------------
@@ -230,11 +261,13 @@ constexpr int MAX_INTENT = 8;
 
 __global__ __launch_bounds__(256) void intent_fuse_kernel(const float* __restrict__ intents, const float* __restrict__ hidden,
                                                            const float* __restrict__ aff2_t, const float* __restrict__ aff2_b,
-                                                           float* __restrict__ content, long ldc, long M, int k, int D, int A) {
+                                                           float* __restrict__ content, long ldc, long M, int k, int D, int A,
+                                                           const int* __restrict__ m_dev) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // [2][D] pooled vectors, then 4 floats of scratch
     float* pooled = sm;
     float* red = sm + 2 * D;
     const long m = blockIdx.x;
+    if (m_dev && m >= (long)*m_dev) return;                      // (uniform per workgroup) distinct news only: the rows behind the count hold nothing
     for (int tb = 0; tb < 2; ++tb) {
         const float* aff2 = tb == 0 ? aff2_t : aff2_b;
         const float* hid = hidden + ((long)tb * M + m) * k * A;
@@ -1233,17 +1266,45 @@ extern "C" int lime_topic_rep_f32(const int32_t* cat, const int32_t* sub, const 
     return lime_check_launch("lime_topic_rep_f32");
 }
 
-extern "C" int lime_intent_fuse_f32(const float* intents, const float* att_hidden, const float* affine2_t,
-                                    const float* affine2_b, float* content, int64_t ldc, int64_t M, int32_t k, int32_t D,
-                                    int32_t A, void* stream) {
+static int intent_fuse(const float* intents, const float* att_hidden, const float* affine2_t, const float* affine2_b, float* content,
+                       int64_t ldc, int64_t M, int32_t k, int32_t D, int32_t A, const int32_t* m_dev, void* stream) {
     LIME_REQUIRE(intents && att_hidden && affine2_t && affine2_b && content, LIME_ERR_BAD_ARG, "lime_intent_fuse_f32: NULL pointer");
     LIME_REQUIRE(M >= 0 && k > 0 && D > 0 && A > 0 && ldc >= 2 * (int64_t)D, LIME_ERR_BAD_ARG, "lime_intent_fuse_f32: bad dims");
     LIME_REQUIRE(k <= MAX_INTENT && D <= 4096, LIME_ERR_UNSUPPORTED, "lime_intent_fuse_f32: k <= 8 and D <= 4096 only");
     if (M == 0) return LIME_OK;
     const size_t lds = (size_t)(2 * D + 4) * sizeof(float);
     hipLaunchKernelGGL(intent_fuse_kernel, dim3((unsigned)M), dim3(256), lds, (hipStream_t)stream, intents, att_hidden, affine2_t,
-                       affine2_b, content, (long)ldc, (long)M, k, D, A);
+                       affine2_b, content, (long)ldc, (long)M, k, D, A, m_dev);
     return lime_check_launch("lime_intent_fuse_f32");
+}
+
+extern "C" int lime_intent_fuse_f32(const float* intents, const float* att_hidden, const float* affine2_t,
+                                    const float* affine2_b, float* content, int64_t ldc, int64_t M, int32_t k, int32_t D,
+                                    int32_t A, void* stream) {
+    return intent_fuse(intents, att_hidden, affine2_t, affine2_b, content, ldc, M, k, D, A, nullptr, stream);
+}
+
+extern "C" int lime_intent_fuse_count_f32(const float* intents, const float* att_hidden, const float* affine2_t, const float* affine2_b,
+                                          float* content, int64_t ldc, int64_t M, int32_t k, int32_t D, int32_t A, const int32_t* m_dev,
+                                          void* stream) {
+    LIME_REQUIRE(m_dev, LIME_ERR_BAD_ARG, "lime_intent_fuse_count_f32: NULL count");
+    return intent_fuse(intents, att_hidden, affine2_t, affine2_b, content, ldc, M, k, D, A, m_dev, stream);
+}
+
+extern "C" int lime_news_xin_f32(const float* title_blocks, int64_t ld_t, int32_t nblk_t, const float* body_blocks, int64_t ld_b,
+                                 int32_t nblk_b, const int32_t* title_row, const int32_t* body_row, const int32_t* n_news, float* xin,
+                                 int64_t ldx, int32_t cap, int32_t dim, void* stream) {
+    LIME_REQUIRE(title_blocks && body_blocks && title_row && body_row && n_news && xin, LIME_ERR_BAD_ARG, "lime_news_xin_f32: NULL pointer");
+    LIME_REQUIRE(cap >= 0 && dim > 0 && ld_t >= dim && ld_b >= dim && ldx >= dim, LIME_ERR_BAD_ARG, "lime_news_xin_f32: bad dims");
+    LIME_REQUIRE(nblk_t >= 1 && nblk_t <= 16 && nblk_b >= 1 && nblk_b <= 16 && dim % 4 == 0 && ld_t % 4 == 0 && ld_b % 4 == 0 && ldx % 4 == 0 &&
+                     (uintptr_t)title_blocks % 16 == 0 && (uintptr_t)body_blocks % 16 == 0 && (uintptr_t)xin % 16 == 0,
+                 LIME_ERR_UNSUPPORTED, "lime_news_xin_f32: 1 .. 16 block rows per sequence, dim %% 4 == 0, 16-byte aligned rows");
+    if (cap == 0) return LIME_OK;
+    const long total = 2L * cap * (dim >> 2);
+    LIME_REQUIRE((total + 255) / 256 <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_news_xin_f32: too many rows");
+    hipLaunchKernelGGL(news_xin_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, title_blocks, (long)ld_t,
+                       nblk_t, body_blocks, (long)ld_b, nblk_b, title_row, body_row, n_news, xin, (long)ldx, (long)cap, dim);
+    return lime_check_launch("lime_news_xin_f32");
 }
 
 extern "C" int lime_additive_pool_count_f32(const float* hidden, int64_t ldh, const float* affine2, int32_t A, const float* x,

@@ -31,6 +31,11 @@ MAX_TOKENS_PER_PASS = 4 * 1024 * 1024
 # tokens only.  Exact (same arithmetic per row, nothing cached between forwards); LIME_DENSE_TOKENS=1 (or DEDUP = False) runs
 # every token of every slot through the layer as the reference does -- the A/B switch behind bench.py's "dense" figures.
 DEDUP = os.environ.get('LIME_DENSE_TOKENS', '0') != '1'
+# Behind the token encoders, run the row-wise tail (intent layers, intent attention, fuse, LIME.project) once per DISTINCT news: the
+# repetitions of the padding news collapse onto one representative (csrc/compact.hip, lime_compact_batch) and the result is expanded
+# through news_inv.  Exact (same kernels, same arithmetic per row); needs DEDUP, covers the one-pass fp32 compacted path of CROWN
+# under LIME's concat + project.  LIME_NEWS_DEDUP=0 (or NEWS_DEDUP = False): every slot through the tail, as before (A/B runs).
+NEWS_DEDUP = os.environ.get('LIME_NEWS_DEDUP', '1') != '0'
 
 
 def _no_train_dropout(module, p):
@@ -310,6 +315,28 @@ class LIME(nn.Module):
         # :151-153; same sums, associated per half).  The branch depends on the inputs' buckets and the weights only: side stream.
         fe = self.freshness_encoder
         nb = fe.num_buckets
+        enc = self.base_news_encoder
+        if (NEWS_DEDUP and recurrence is None and title_text is not None and hasattr(enc, 'news_dedup_applicable') and
+                enc.news_dedup_applicable(title_text, content_text)):
+            # the tail once per distinct news: the compaction (three launches on branch 3, in front of the encoders' preparation) also
+            # lists the news; the bucket pair and the topic rows are taken from the compact keys, `project` runs over n_news rows and
+            # the result is expanded to the M slots -- the one launch this adds to the critical path
+            side3 = _side_stream(dev, 3)
+            side3.wait_stream(main)
+            with torch.cuda.stream(side3):
+                news = ops.compact_batch(title_text, content_text, category, subCategory, freshness.contiguous(), lifetime.contiguous(),
+                                         count_mult=enc.intent_num)
+            nw = news[2]
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                side.wait_event(nw.ready)                                    # the raw keys: no bucketize launch in front of the compaction
+                pair = torch.add(fe.buckets(nw.life_c), fe.buckets(nw.fresh_c), alpha=nb)                   # int32 [M + 1], unused slots valid
+                table, _ = self.occurrence_tables()
+            content = torch.empty((M + 1, cdim), dtype=torch.float32, device=dev)
+            enc.encode_flat(title_text, title_mask, content_text, category, subCategory, content, news=news)
+            main.wait_stream(side)
+            rep_c = ops.linear(content, self.project.weight[:, :cdim], None, res=table, res_ids=pair, m_dev=nw.n_news)
+            return ops.gather_rows(nw.news_inv, rep_c, torch.empty((M, rep_c.shape[1]), dtype=torch.float32, device=dev))
         side.wait_stream(main)
         with torch.cuda.stream(side):
             pair = torch.add(fe.buckets(lifetime), fe.buckets(freshness), alpha=nb)                        # b_f * nb + b_l, int32 [M]
@@ -588,12 +615,14 @@ _Rows = collections.namedtuple('_Rows', 'n_seq S a_ids res_ids w_in pew qkv c_id
                                defaults=(None,) * 7)
 
 
-def _encode_layers(r, table, pe, transformer, nhead, pooled_out):
+def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=False):
     """Word gather + positional table + the post-LN encoder layer(s) of newsEncoders.py:311-320 over the rows ``r`` describes: in_proj,
     attention, out_proj + residual + norm1, linear1 + ReLU, linear2 + residual + norm2 -- five launches per layer (four with the fused
     feed-forward), activations stay fp32.  With ``pooled_out`` the token mean pooling of :317 / :321 is taken in the last GEMM's
     epilogue (pool32: means over 32-token blocks; a longer sequence is finished by a mean over its S / 32 block rows) and the layer
-    output never reaches HBM; returns None then, the layer output [n_seq * S, E] otherwise."""
+    output never reaches HBM; returns None then, the layer output [n_seq * S, E] otherwise.  ``blocks_only`` (compacted rows, no
+    ``pooled_out``): returns the last GEMM's block means [n_seq * S / 32, E] in compact order and leaves the rest of the pooling and
+    the expansion through ``seq_inv`` to the caller (ops.news_xin)."""
     n_seq, S = r.n_seq, r.S
     E = table.shape[1]
     hd = E // nhead
@@ -628,7 +657,7 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out):
                                             n_seq, S, nhead, hd, scale)
         x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, ln=ln1, ln_eps=layer.norm1.eps, **res, **rows)
         last = li == len(transformer.layers) - 1
-        pool = last and pooled_out is not None and transformer.norm is None and S % 32 == 0 and n_seq * S >= 4096
+        pool = last and (pooled_out is not None or blocks_only) and transformer.norm is None and S % 32 == 0 and n_seq * S >= 4096
         ln2 = (layer.norm2.weight, layer.norm2.bias)
         if _ffn_sp_applicable(layer, x1):
             # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means of the last layer) in one launch
@@ -642,12 +671,16 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out):
         if not pool:
             x = ffn()
             continue
+        if blocks_only:
+            return ffn(pool32=True)
         blocks = ffn(pool32=True, out=pooled if direct else None)                                      # [n_seq * S / 32, E] block means
         pooled = blocks if direct else ops.mean_pool(blocks, n_seq, S // 32, out=pooled, n_seq_dev=r.n_seq_dev)
         break
     else:
         if transformer.norm is not None:
             raise NotImplementedError('a final encoder norm is not used by the reference (newsEncoders.py:245,247)')
+        if blocks_only:
+            raise NotImplementedError('blocks_only needs the pooled epilogue (S a multiple of 32, >= 4096 rows: compact_applicable)')
         if pooled_out is None:
             return x
         pooled = ops.mean_pool(x, n_seq, S, out=pooled, n_seq_dev=r.n_seq_dev)
@@ -694,18 +727,19 @@ def compact_prepare(ids, table, pe, transformer, nhead):
     return compact_prepare_many([(ids, pe, transformer)], table, nhead)[0]
 
 
-def compact_prepare_many(encoders, table, nhead):
+def compact_prepare_many(encoders, table, nhead, cmps=None):
     """``compact_prepare`` for several token encoders over one word table ((ids, pe, transformer) each): their positional tables go
-    through in_proj in ONE grouped launch, their padding rows in another (independent, latency-bound GEMMs)."""
+    through in_proj in ONE grouped launch, their padding rows in another (independent, latency-bound GEMMs).  ``cmps``: the encoders'
+    index lists when the caller has them already (``ops.compact_batch``)."""
     E = table.shape[1]
     hd = E // nhead
     W = nhead * 32
     parts = []
-    for ids, pe, transformer in encoders:
+    for i, (ids, pe, transformer) in enumerate(encoders):
         M, S = ids.shape
         sa = transformer.layers[0].self_attn
         cap = (M + 1) * S
-        cmp = ops.compact_sequences(ids)                                       # pad rows live at qkv[cap : cap + S]
+        cmp = ops.compact_sequences(ids) if cmps is None else cmps[i]           # pad rows live at qkv[cap : cap + S]
         w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)
         b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
         qkv = torch.empty((cap + S, 3 * W), dtype=torch.float32, device=ids.device)
@@ -738,12 +772,13 @@ def _identity_rows(n, device):
     return _grown(_IDENT, n, device, 4096, lambda size: torch.arange(size, dtype=torch.int32, device=device))
 
 
-def compact_run(prep, table, pe, transformer, nhead, pooled_out):
-    """``encode_tokens_compact`` behind its preparation: the layer(s) over the compacted rows, ``pooled_out`` through ``seq_inv``."""
+def compact_run(prep, table, pe, transformer, nhead, pooled_out, blocks_only=False):
+    """``encode_tokens_compact`` behind its preparation: the layer(s) over the compacted rows, ``pooled_out`` through ``seq_inv`` (or,
+    ``blocks_only``, the compact block means returned: see ``_encode_layers``)."""
     cmp, w_in, pew, qkv = prep
     rows = _Rows(cmp.n_seq + 1, cmp.S, cmp.tok_ids, cmp.ids_c, w_in, pew, qkv, c_ids=cmp.tok_rows, m_tok=cmp.n_live_tokens,
                  m_rows=cmp.n_rows, n_seq_dev=cmp.n_compact, row_map=cmp.row_map, seq_inv=cmp.seq_inv)
-    return _encode_layers(rows, table, pe, transformer, nhead, pooled_out)
+    return _encode_layers(rows, table, pe, transformer, nhead, pooled_out, blocks_only)
 
 
 def compact_applicable(ids, table, transformer, nhead):
@@ -942,9 +977,37 @@ class CROWN(NewsEncoder):
             nn.init.zeros_(intent_layer.bias)
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None):
+    def _step_of(self, S, M, bf16):
+        """News per pass of a token encoder over sequences of S tokens."""
+        E = self.word_embedding_dim
+        return min(max(1, MAX_TOKENS_PER_PASS // S),
+                   # the compacted in_proj scatters rows with 32-bit byte offsets from the base of qkv ([rows, 3 * 320])
+                   max(1, (0x7FFFFFF0 // (3 * self.head_num * 32 * (2 if bf16 else 4))) // S - 2) if DEDUP else M,
+                   # the fused bf16 entry points address a pass's rows with 32-bit byte offsets ([rows, 304] bf16)
+                   max(1, (0x7FFFFFF0 // (((E + 7) // 8 * 8) * 2)) // S - 2) if bf16 else M)
+
+    def _one_pass(self, title_text, content_text):
+        """Both token encoders on the compacted fp32 path, one pass each."""
+        M = title_text.shape[0]
+        table = self.word_embedding.weight
+        return (self.compute_dtype != 'bf16' and
+                all(M <= self._step_of(ids.shape[1], M, False) and compact_applicable(ids, table, tr, self.head_num)
+                    for ids, tr in ((title_text, self.title_transformer), (content_text, self.body_transformer))))
+
+    def news_dedup_applicable(self, title_text, content_text):
+        """The tail over the distinct news (``encode_flat(..., news=...)``) covers the one-pass compacted path, and the batches whose
+        tail GEMMs the mid-M kernel takes with and without the compaction (2 (M + 1) < 4096 rows of intent input, k (M + 1) < 12288
+        rows of intents): every computed row then keeps its kernel and its arithmetic."""
+        M = title_text.shape[0]
+        return (DEDUP and title_text.is_cuda and self._one_pass(title_text, content_text) and 2 * (M + 1) < 4096 and
+                self.intent_num * (M + 1) < 12288)
+
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None, news=None):
         """M news -> out [M, 900] (out may be a column slice of a wider buffer).  The token masks are computed and never
-        used by the reference (:307-308); title_mask is accepted and ignored."""
+        used by the reference (:307-308); title_mask is accepted and ignored.
+        ``news`` = ``ops.compact_batch(title_text, content_text, category, subCategory, ...)`` (``news_dedup_applicable`` batches only):
+        the layers behind the token encoders run over the distinct news, and ``out`` is [M + 1, 900] in compact order -- row
+        ``news[2].news_inv[i]`` is news i, rows at or beyond the device count ``news[2].n_news`` are not written."""
         _no_train_dropout(self, self.dropout_rate)
         M, T = title_text.shape
         L = content_text.shape[1]
@@ -956,8 +1019,17 @@ class CROWN(NewsEncoder):
         table = self.word_embedding.weight
         kin = E + Dc
         ldx = (kin + 3) // 4 * 4                                   # 352: keeps the rows 16-byte aligned
-        # rows [0, M): [title_pooled | category_rep], rows [M, 2M): [body_pooled | category_rep]   (:343-344)
-        xin = torch.empty((2 * M, ldx), dtype=torch.float32, device=dev)
+        dedup = news is not None
+        if dedup:
+            cmp_t, cmp_b, nw = news
+            if not self.news_dedup_applicable(title_text, content_text) or nw.n != M or nw.count_mult != k:
+                raise ValueError('news: the batch is outside news_dedup_applicable, or the lists are not this batch\'s (count_mult = intent_num)')
+            category, subCategory = nw.cat_c, nw.sub_c             # the topic rows of the distinct news
+        R = M + 1 if dedup else M                                  # rows per half of the tail: distinct news (capacity) or every slot
+        if out.shape[0] != R:
+            raise ValueError('out must have %d rows' % R)
+        # rows [0, R): [title_pooled | category_rep], rows [R, 2R): [body_pooled | category_rep]   (:343-344)
+        xin = torch.empty((2 * R, ldx), dtype=torch.float32, device=dev)
         # The title and body encoders are independent chains of five GEMM / attention launches each (optionally on two
         # streams, see SERIAL_STREAMS).
         bf16 = self.compute_dtype == 'bf16'
@@ -969,11 +1041,13 @@ class CROWN(NewsEncoder):
         side4 = _side_stream(dev, 4)
         side4.wait_stream(main)
         with torch.cuda.stream(side4):
+            if dedup:
+                side4.wait_event(nw.ready)                         # the compact keys (unused slots hold id 0: valid over the capacity)
             sub_table = self.subCategory_embedding.weight
             ops.topic_rep(category, subCategory, self.category_embedding.weight, sub_table, self.category_affine.weight,
-                          self.category_affine.bias, out=xin[:M, E:kin], emb_out=out[:, 2 * D:2 * D + Dc + sub_table.shape[1]])
+                          self.category_affine.bias, out=xin[:R, E:kin], emb_out=out[:, 2 * D:2 * D + Dc + sub_table.shape[1]])
             ops.topic_rep(category, subCategory, self.category_embedding.weight, sub_table, self.category_affine.weight,
-                          self.category_affine.bias, out=xin[M:, E:kin])
+                          self.category_affine.bias, out=xin[R:, E:kin])
             # the k intent weight matrices stacked row-wise, K = 350 carried as ldx = 352 zero-padded columns (16-byte rows: the
             # LDS-DMA GEMM kernels take it; the two pad columns of xin are zeroed to match)
             w_int = torch.nn.functional.pad(torch.cat([lin.weight for lin in self.intent_layers], dim=0), (0, ldx - kin))
@@ -982,13 +1056,8 @@ class CROWN(NewsEncoder):
                 xin[:, kin:] = 0.0
         encoders = ((title_text, self.title_pos_encoder, self.title_transformer, T),
                     (content_text, self.body_pos_encoder, self.body_transformer, L))
-        step_of = lambda S: min(max(1, MAX_TOKENS_PER_PASS // S),
-                                # the compacted in_proj scatters rows with 32-bit byte offsets from the base of qkv ([rows, 3 * 320])
-                                max(1, (0x7FFFFFF0 // (3 * self.head_num * 32 * (2 if bf16 else 4))) // S - 2) if DEDUP else M,
-                                # the fused bf16 entry points address a pass's rows with 32-bit byte offsets ([rows, 304] bf16)
-                                max(1, (0x7FFFFFF0 // (((E + 7) // 8 * 8) * 2)) // S - 2) if bf16 else M)
-        one_pass = (not bf16 and all(M <= step_of(S) and compact_applicable(ids, table, tr, self.head_num)
-                                     for ids, pos, tr, S in encoders))
+        step_of = lambda S: self._step_of(S, M, bf16)
+        one_pass = self._one_pass(title_text, content_text)
         if one_pass:
             # both encoders on the compacted path in one pass each: the body's preparation (index lists, padded weights, padding
             # rows: a dozen short launches) runs on branch 3 under the title encoder's GEMMs
@@ -996,14 +1065,19 @@ class CROWN(NewsEncoder):
             side3 = _side_stream(dev, 3)
             side3.wait_stream(main)
             with torch.cuda.stream(side3):              # both encoders' preparation together: their small GEMMs share launches
-                prep_t, prep_b = compact_prepare_many([(t_ids, t_pos.table(), t_tr), (b_ids, b_pos.table(), b_tr)], table, self.head_num)
+                prep_t, prep_b = compact_prepare_many([(t_ids, t_pos.table(), t_tr), (b_ids, b_pos.table(), b_tr)], table, self.head_num,
+                                                      cmps=(cmp_t, cmp_b) if dedup else None)
             side1 = _side_stream(dev, 7)                   # branch 7: the (short) title chain beside the body chain
             side1.wait_stream(side3)
             with torch.cuda.stream(side1):
-                compact_run(prep_t, table, t_pos.table(), t_tr, self.head_num, xin[:M, :E])                    # :311-317
+                tb = compact_run(prep_t, table, t_pos.table(), t_tr, self.head_num, None if dedup else xin[:M, :E], dedup)    # :311-317
             main.wait_stream(side3)
-            compact_run(prep_b, table, b_pos.table(), b_tr, self.head_num, xin[M:, :E])                        # :312-321
+            bb = compact_run(prep_b, table, b_pos.table(), b_tr, self.head_num, None if dedup else xin[M:, :E], dedup)        # :312-321
             main.wait_stream(side1)
+            if dedup:
+                # the pooled rows of the distinct news straight from the compact block means: the rest of the body's mean and both
+                # expansions through seq_inv in one launch (they were mean_pool + two gather_rows over all M slots)
+                ops.news_xin(tb, T // 32, bb, L // 32, nw, xin, E)
         else:
             side = _side_stream(dev, 7 if DEDUP else 1)   # compacted chunks: title beside body (branch 7); dense: branch 1 (off)
             side.wait_stream(main)
@@ -1030,17 +1104,25 @@ class CROWN(NewsEncoder):
         main.wait_stream(side4)
         # k intent layers (:284-295): [2M, 350] x [400, 350]^T each, ReLU fused, written side by side
         # (one GEMM against the k weight matrices stacked row-wise: the k layers share their input)
-        intents = ops.linear(xin, w_int, b_int, act='relu')
+        if dedup:
+            # one problem per half, each over its first n_news rows (device count): the tiles behind it exit at once
+            intents = torch.empty((2 * R, w_int.shape[0]), dtype=torch.float32, device=dev)
+            ops.linear_group([dict(a=xin[half * R:(half + 1) * R], w=w_int, bias=b_int, act='relu', out=intents[half * R:(half + 1) * R],
+                                   m_dev=nw.n_news) for half in range(2)])
+        else:
+            intents = ops.linear(xin, w_int, b_int, act='relu')
         # intent attention (:355-356): tanh(affine1) on the GEMM (title on the main stream, body on branch 5), the rest in the fuse kernel
         A = self.title_intent_attention.affine1.out_features
-        hidden = torch.empty((2 * M * k, A), dtype=torch.float32, device=dev)
-        iv = intents.view(2 * M * k, D)
+        hidden = torch.empty((2 * R * k, A), dtype=torch.float32, device=dev)
+        iv = intents.view(2 * R * k, D)
+        rows_k = dict(m_dev=nw.n_news_mult) if dedup else {}                       # k rows of intents per news
         # the two halves do not depend on each other: one grouped launch (they were two launches on two streams)
-        ops.linear_group([dict(a=iv[half * M * k:(half + 1) * M * k], w=att.affine1.weight, bias=att.affine1.bias, act='tanh',
-                               out=hidden[half * M * k:(half + 1) * M * k])
+        ops.linear_group([dict(a=iv[half * R * k:(half + 1) * R * k], w=att.affine1.weight, bias=att.affine1.bias, act='tanh',
+                               out=hidden[half * R * k:(half + 1) * R * k], **rows_k)
                           for half, att in enumerate((self.title_intent_attention, self.body_intent_attention))])
         ops.intent_fuse(iv, hidden, self.title_intent_attention.affine2.weight.view(-1),
-                        self.body_intent_attention.affine2.weight.view(-1), out, M, k, D, A)          # :355-371
+                        self.body_intent_attention.affine2.weight.view(-1), out, R, k, D, A,
+                        m_dev=nw.n_news if dedup else None)                                           # :355-371
         return out
 
 

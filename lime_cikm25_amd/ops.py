@@ -318,6 +318,85 @@ def compact_sequences(ids, pad_base=None):
     return c
 
 
+class NewsCompacted:
+    """News-level lists of ``compact_batch`` (device tensors, capacity n + 1; see lime_compact_batch in include/lime_hip.h)."""
+    __slots__ = ('n', 'news_src', 'news_inv', 'title_row', 'body_row', 'cat_c', 'sub_c', 'fresh_c', 'life_c', 'counts', 'count_mult',
+                 'ready')                                    # ready: event behind the three launches, for consumers on other streams
+
+    n_news = property(lambda self: self.counts[0:1])         # device counts as 1-element views (m_dev arguments)
+    n_news_mult = property(lambda self: self.counts[1:2])    # count_mult * n_news
+
+
+def _compacted_views(c, buf, n_seq, S):
+    """Carves ``Compacted``'s lists out of ``buf`` (``compact_sequences``' layout without the workspace); returns the words used."""
+    cap = (n_seq + 1) * S
+    c.n_seq, c.S, c.cap = n_seq, S, cap
+    c.seq_inv = buf[:n_seq]
+    o = n_seq
+    c.ids_c, c.row_map, c.tok_ids, c.tok_rows = (buf[o + i * cap:o + (i + 1) * cap] for i in range(4))
+    o += 4 * cap
+    c.counts = buf[o:o + 5]
+    return o + 8
+
+
+def compact_batch(title_ids, body_ids, cat, sub, fresh, life, count_mult=1):
+    """``compact_sequences`` for the titles [n, T] and the bodies [n, L] of n news and the news level on top, in three launches
+    (``lime_compact_batch``).  cat / sub int32 [n], fresh / life float32 [n]: the rest of a news' key.  Returns
+    (``Compacted`` title, ``Compacted`` body, ``NewsCompacted``)."""
+    lib = _lib.load()
+    for ids in (title_ids, body_ids):
+        if ids.dim() != 2 or ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous():
+            raise TypeError('ids must be contiguous CUDA int32 [n, S] tensors')
+    n, T = title_ids.shape
+    L = body_ids.shape[1]
+    if body_ids.shape[0] != n:
+        raise ValueError('title_ids and body_ids must have one row per news')
+    _vec(cat, 'cat', n, dtype=torch.int32)
+    _vec(sub, 'sub', n, dtype=torch.int32)
+    _vec(fresh, 'fresh', n)
+    _vec(life, 'life', n)
+    dev = title_ids.device
+    words = lambda S: n + 4 * (n + 1) * S + 8
+    buf = torch.empty(words(T) + words(L) + 8 * (n + 1) + 8 + int(lib.lime_compact_batch_workspace(n)), dtype=torch.int32, device=dev)
+    t, b, w = Compacted(), Compacted(), NewsCompacted()
+    o = _compacted_views(t, buf, n, T)
+    o += _compacted_views(b, buf[o:], n, L)
+    w.n, w.count_mult = n, count_mult
+    w.news_src, w.title_row, w.body_row, w.cat_c, w.sub_c, fc, lc = (buf[o + i * (n + 1):o + (i + 1) * (n + 1)] for i in range(7))
+    w.fresh_c, w.life_c = fc.view(torch.float32), lc.view(torch.float32)
+    o += 7 * (n + 1)
+    w.news_inv = buf[o:o + n]
+    o += n + 1
+    w.counts = buf[o:o + 4]
+    work = buf[o + 8:]
+    t.seq_src, b.seq_src = work[n:2 * n + 1], work[4 * n + 2:5 * n + 3]
+    check(lib.lime_compact_batch(_p(title_ids), T, t.cap, _p(t.seq_inv), _p(t.ids_c), _p(t.row_map), _p(t.tok_ids), _p(t.tok_rows),
+                                 _p(t.counts), _p(body_ids), L, b.cap, _p(b.seq_inv), _p(b.ids_c), _p(b.row_map), _p(b.tok_ids),
+                                 _p(b.tok_rows), _p(b.counts), n, _p(cat), _p(sub), _p(fresh), _p(life), count_mult, _p(w.news_src),
+                                 _p(w.news_inv), _p(w.title_row), _p(w.body_row), _p(w.cat_c), _p(w.sub_c), _p(w.fresh_c), _p(w.life_c),
+                                 _p(w.counts), _p(work), _stream()), 'lime_compact_batch')
+    w.ready = torch.cuda.Event()
+    w.ready.record()
+    return t, b, w
+
+
+def news_xin(title_blocks, nblk_t, body_blocks, nblk_b, news, xin, dim):
+    """``lime_news_xin_f32``: columns [0, dim) of xin [2 (n + 1), >= dim] from the pooled block rows of the distinct news: the title half
+    in rows [0, n + 1), the body half behind it; rows at or beyond the device count ``news.n_news`` are left alone."""
+    lib = _lib.load()
+    _mat(title_blocks, 'title_blocks')
+    _mat(body_blocks, 'body_blocks')
+    _mat(xin, 'xin')
+    cap = news.n + 1
+    if title_blocks.shape != (cap * nblk_t, dim) or body_blocks.shape != (cap * nblk_b, dim):
+        raise ValueError('title_blocks / body_blocks must be [(n + 1) * nblk, dim]')
+    if xin.shape[0] != 2 * cap or xin.shape[1] < dim:
+        raise ValueError('xin must be [2 (n + 1), >= dim]')
+    check(lib.lime_news_xin_f32(_p(title_blocks), _ld(title_blocks), nblk_t, _p(body_blocks), _ld(body_blocks), nblk_b, _p(news.title_row),
+                                _p(news.body_row), _p(news.n_news), _p(xin), _ld(xin), cap, dim, _stream()), 'lime_news_xin_f32')
+    return xin
+
+
 def pad_heads(src, n_blk, head_dim, head_stride):
     """[n_blk * head_dim, cols] (or a vector of n_blk * head_dim) -> rows padded with zeros to head_stride per block."""
     lib = _lib.load()
@@ -488,8 +567,9 @@ def topic_rep(cat, sub, cat_table, sub_table, w=None, bias=None, out=None, emb_o
     return out
 
 
-def intent_fuse(intents, att_hidden, affine2_t, affine2_b, content, M, k, D, A):
-    """intents [2*M*k, D], att_hidden [2*M*k, A] contiguous; writes content[:, :2D] (content may be a view)."""
+def intent_fuse(intents, att_hidden, affine2_t, affine2_b, content, M, k, D, A, m_dev=None):
+    """intents [2*M*k, D], att_hidden [2*M*k, A] contiguous; writes content[:, :2D] (content may be a view).  m_dev (int32 device
+    tensor, 1 element): only the first min(M, m_dev) news are read and written."""
     lib = _lib.load()
     _mat(intents, 'intents')
     _mat(att_hidden, 'att_hidden')
@@ -500,6 +580,11 @@ def intent_fuse(intents, att_hidden, affine2_t, affine2_b, content, M, k, D, A):
     _mat(content, 'content')
     if content.shape[0] != M or content.shape[1] < 2 * D:
         raise ValueError('content must be [M, >= 2D]')
+    if m_dev is not None:
+        check(lib.lime_intent_fuse_count_f32(_p(intents), _p(att_hidden), _p(_vec(affine2_t, 'affine2_t', A)),
+                                             _p(_vec(affine2_b, 'affine2_b', A)), _p(content), _ld(content), M, k, D, A,
+                                             _p(_vec(m_dev, 'm_dev', 1, dtype=torch.int32)), _stream()), 'lime_intent_fuse_count_f32')
+        return content
     check(lib.lime_intent_fuse_f32(_p(intents), _p(att_hidden), _p(_vec(affine2_t, 'affine2_t', A)),
                                    _p(_vec(affine2_b, 'affine2_b', A)), _p(content), _ld(content), M, k, D, A, _stream()),
           'lime_intent_fuse_f32')
