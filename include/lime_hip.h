@@ -123,6 +123,29 @@ int lime_linear_group_f32(const lime_linear_args* args, int32_t n, void* stream)
  * as rocprofv3 names it: lets a profiler harness match its own event timings to the kernel trace. */
 const char* lime_last_linear_kernel(void);
 
+/* What lime_linear_f32 would run for an argument block, without running it: the routing decision (csrc/gemm_f32.hip, linear_route)
+ * as data.  A pure function of the block, the lime_set_split_gemm() setting and the CU count: no launch, no pointer of the block is
+ * read through (only NULL-ness and alignment count), and with n_cu > 0 no call into the HIP runtime; n_cu <= 0 asks the current device.
+ * Returns what lime_linear_f32 would return for a block nothing takes (same status, same lime_last_error_string()), else LIME_OK and
+ *   family       which unit's kernel: LIME_LINEAR_SP gemm_sp_kernel (split product), _PP gemm_pp_kernel (fp32 MFMA, LDS-DMA),
+ *                _MID gemm_mid_kernel, _GENERAL gemm_f32_kernel; LIME_LINEAR_NONE for M == 0 (nothing is launched)
+ *   second_pass  bits: passes over C behind the GEMM where the epilogue is not fused -- LIME_LINEAR_PASS_RELU_BWD lime_relu_bwd_f32
+ *                (LIME_ACT_RELU_GRAD), LIME_LINEAR_PASS_DROPOUT lime_dropout_f32 (dropout_p); the GEMM then runs without them
+ *   mid_shape    _MID: the tile shape 0 = 64 x 64, 1 = 32 x 64, 2 = 32 x 32, and `tiles` their number (= workgroups); else -1 / 0
+ *   name         the instantiation as lime_last_linear_kernel() reports it after the launch (and as rocprofv3 prints it) */
+enum { LIME_LINEAR_NONE = 0, LIME_LINEAR_SP = 1, LIME_LINEAR_PP = 2, LIME_LINEAR_MID = 3, LIME_LINEAR_GENERAL = 4 };
+enum { LIME_LINEAR_PASS_RELU_BWD = 1, LIME_LINEAR_PASS_DROPOUT = 2 };
+typedef struct {
+    int32_t family;
+    int32_t second_pass;
+    int32_t mid_shape;
+    int32_t reserved;
+    int64_t tiles;
+    char name[96];
+} lime_linear_plan;
+
+int lime_linear_plan_f32(const lime_linear_args* args, int32_t n_cu, lime_linear_plan* out);
+
 /* Which kernels take the large 16-byte-aligned problems of lime_linear_f32 (M x N tiles >= 96 of 256 x 320) -- and, with the same bit 0, of
  * lime_linear_wgrad_f32 (M >= 4096), the unmasked padded-head lime_token_attention*_f32 (S = 32 ... 512) and lime_token_attention_bwd*_f32
  * (S > 64, no key mask):

@@ -35,6 +35,16 @@ class LinearArgs(Structure):
     ]
 
 
+class LinearPlan(Structure):
+    """Mirror of ``lime_linear_plan`` (include/lime_hip.h)."""
+    _fields_ = [('family', c_int32), ('second_pass', c_int32), ('mid_shape', c_int32), ('reserved', c_int32), ('tiles', c_int64),
+                ('name', ctypes.c_char * 96)]
+
+
+LINEAR_FAMILY = {0: None, 1: 'sp', 2: 'pp', 3: 'mid', 4: 'general'}       # LIME_LINEAR_* of include/lime_hip.h
+LINEAR_PASS_RELU_BWD, LINEAR_PASS_DROPOUT = 1, 2
+
+
 class LinearBf16Args(ctypes.Structure):
     """lime_linear_bf16_args of include/lime_hip.h (same field order)."""
     _fields_ = [
@@ -168,6 +178,7 @@ SIGNATURES = {
     'lime_last_linear_kernel': (c_char_p, []),
     'lime_set_split_gemm': (c_int32, [c_int32]),
     'lime_linear_f32': (c_int32, [POINTER(LinearArgs), c_void_p]),
+    'lime_linear_plan_f32': (c_int32, [POINTER(LinearArgs), c_int32, POINTER(LinearPlan)]),
     'lime_linear_group_f32': (c_int32, [POINTER(LinearArgs), c_int32, c_void_p]),
     'lime_embed_pe_f32': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int64,
                                     c_int32, c_void_p]),

@@ -531,118 +531,43 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN <= 4) ? 2 : 
 #endif
 }
 
-template <int TM, int TN, int WM, int WN, int VEC, bool LN, bool PE, int ACT, bool GENERIC, bool VIO>
-int launch_one(const GemmP& p0, int wg_per_cu, hipStream_t stream) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
+// gemm_f32_kernel<1, TN, WM, WN, VEC, LN, PE, ACT, GENERIC, VIO>: GENERIC is the four-wave 64 x 64 tile (TN 1, 2 x 2 waves, four
+// workgroups per CU), everything else the eight-wave 128 x 256 / 128 x 320 tile (TN 4 / 5, 4 x 2 waves, one workgroup per CU)
+struct GenChoice { int tn, vec, act; bool ln, pe, generic, vio; };
+
+const char* gen_name(const GenChoice& c) {
+    static thread_local char buf[96];
+    snprintf(buf, sizeof(buf), "gemm_f32_kernel<1, %d, %d, 2, %d, %s, %s, %d, %s, %s>", c.tn, c.generic ? 2 : 4, c.vec, lime_tf(c.ln), lime_tf(c.pe),
+             c.act, lime_tf(c.generic), lime_tf(c.vio));       // as rocprofv3 prints it
+    return buf;
+}
+
+template <int TN, int VEC, bool LN, bool PE, int ACT, bool GENERIC, bool VIO>
+int launch_one(const GemmP& p0, int n_cu, hipStream_t stream) {
+    constexpr int WM = GENERIC ? 2 : 4, WN = 2, BM = WM * 32, BN = WN * TN * 32;
     GemmP p = p0;
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + BN - 1) / BN;
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = (long)lime_num_cus() * wg_per_cu;
+    long nwg = (long)n_cu * (GENERIC ? 4 : 1);
     if (nwg > ntiles) nwg = ntiles;
 #ifdef LIME_STAMPS
     p.stamps = g_stamp_buf;
 #endif
-    hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, WM, WN, VEC, LN, PE, ACT, GENERIC, VIO>), dim3((unsigned)nwg), dim3(WM * WN * 64), 0,
-                       stream, p);
-    lime_set_last_linear_kernel("gemm_f32_kernel<%d, %d, %d, %d, %d, %s, %s, %d, %s, %s>", TM, TN, WM, WN, VEC, LN ? "true" : "false",
-                                PE ? "true" : "false", ACT, GENERIC ? "true" : "false", VIO ? "true" : "false");
+    hipLaunchKernelGGL((gemm_f32_kernel<1, TN, WM, WN, VEC, LN, PE, ACT, GENERIC, VIO>), dim3((unsigned)nwg), dim3(WM * WN * 64), 0, stream, p);
+    lime_set_last_linear_kernel("%s", gen_name({TN, VEC, ACT, LN, PE, GENERIC, VIO}));
     return lime_check_launch("lime_linear_f32");
 }
 
-// small tiles (four waves, 64 x 64): everything at run time
-int launch_small(const GemmP& p, int vec, hipStream_t s) {
-    const bool pe = p.a_pe != nullptr;
-    if (vec == 4) return pe ? launch_one<1, 1, 2, 2, 4, false, true, 0, true, false>(p, 4, s) : launch_one<1, 1, 2, 2, 4, false, false, 0, true, false>(p, 4, s);
-    if (vec == 2) return pe ? launch_one<1, 1, 2, 2, 2, false, true, 0, true, false>(p, 4, s) : launch_one<1, 1, 2, 2, 2, false, false, 0, true, false>(p, 4, s);
-    return pe ? launch_one<1, 1, 2, 2, 1, false, true, 0, true, false>(p, 4, s) : launch_one<1, 1, 2, 2, 1, false, false, 0, true, false>(p, 4, s);
-}
+// every instantiation of the general kernel: TN, VEC, LN, PE, ACT, GENERIC, VIO
+#define LIME_GEN_BUILT(X)                                                                                                       \
+    X(1, 4, 0, 0, 0, 1, 0) X(1, 2, 0, 0, 0, 1, 0) X(1, 1, 0, 0, 0, 1, 0)          /* 64 x 64 tiles, everything at run time */   \
+    X(1, 4, 0, 1, 0, 1, 0) X(1, 2, 0, 1, 0, 1, 0) X(1, 1, 0, 1, 0, 1, 0)          /* ... with a positional A operand */         \
+    X(4, 4, 1, 0, 0, 0, 1) X(4, 1, 1, 0, 0, 0, 0) X(5, 4, 1, 0, 0, 0, 1) X(5, 1, 1, 0, 0, 0, 0)      /* LayerNorm, N <= 256 / 320 */ \
+    X(5, 4, 0, 0, 0, 0, 1) X(5, 4, 0, 0, 1, 0, 1) X(5, 4, 0, 1, 0, 0, 1) X(5, 4, 0, 1, 1, 0, 1)      /* big M, 320 columns */   \
+    X(4, 4, 0, 0, 0, 0, 1) X(4, 4, 0, 0, 1, 0, 1) X(4, 4, 0, 1, 0, 0, 1) X(4, 4, 0, 1, 1, 0, 1)      /* big M, 256 columns */
 
-inline bool aligned(const void* ptr, long ld, int vec) {
-    return ptr == nullptr || (((uintptr_t)ptr % (vec * sizeof(float))) == 0 && (ld % vec) == 0);
-}
-
-}  // namespace
-
-extern "C" int lime_relu_bwd_f32(float* dh, int64_t lddh, const float* h, int64_t ldh, int64_t rows, int32_t cols, float scale,
-                                 void* stream);          // layernorm_bwd_f32.hip
-extern "C" int lime_dropout_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int32_t cols, float p, uint64_t seed,
-                                uint32_t site, void* stream);           // dropout_f32.hip
-
-extern "C" int lime_linear_f32(const lime_linear_args* a, void* stream) {
-    LIME_REQUIRE(a != nullptr, LIME_ERR_BAD_ARG, "lime_linear_f32: args is NULL");
-    LIME_REQUIRE(a->a && a->w && a->c, LIME_ERR_BAD_ARG, "lime_linear_f32: a, w and c must be non-NULL");
-    LIME_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, LIME_ERR_BAD_ARG, "lime_linear_f32: bad dims M=%d N=%d K=%d", a->M, a->N,
-                 a->K);
-    LIME_REQUIRE(a->ldw >= a->K && a->ldc >= a->N && a->lda >= a->K, LIME_ERR_BAD_ARG,
-                 "lime_linear_f32: leading dimension smaller than the row (lda=%ld ldw=%ld ldc=%ld)", (long)a->lda,
-                 (long)a->ldw, (long)a->ldc);
-    LIME_REQUIRE(!a->a_pe || (a->a_ids && a->a_period > 0 && a->lda_pe >= a->K), LIME_ERR_BAD_ARG,
-                 "lime_linear_f32: a_pe needs a_ids, a_period > 0 and lda_pe >= K");
-    LIME_REQUIRE(!a->res || a->res_ids || a->res_div >= 1, LIME_ERR_BAD_ARG, "lime_linear_f32: res_div must be >= 1");
-    LIME_REQUIRE(!a->res || a->ldr >= a->N, LIME_ERR_BAD_ARG, "lime_linear_f32: ldr smaller than N");
-    LIME_REQUIRE(!a->res_pe || (a->res_ids && a->res_period > 0 && a->ldr_pe >= a->N), LIME_ERR_BAD_ARG,
-                 "lime_linear_f32: res_pe needs res_ids, res_period > 0 and ldr_pe >= N");
-    LIME_REQUIRE(!a->ln_gamma || a->ln_beta, LIME_ERR_BAD_ARG, "lime_linear_f32: ln_gamma without ln_beta");
-    LIME_REQUIRE(a->act >= LIME_ACT_NONE && a->act <= LIME_ACT_RELU_GRAD, LIME_ERR_BAD_ARG, "lime_linear_f32: bad act %d", a->act);
-    LIME_REQUIRE(a->res_mod >= 0 && (a->pool32 == 0 || a->pool32 == 1), LIME_ERR_BAD_ARG, "lime_linear_f32: res_mod < 0 or pool32 not 0 / 1");
-    LIME_REQUIRE(!a->ln_rstd || (a->ln_gamma && !a->pool32), LIME_ERR_BAD_ARG, "lime_linear_f32: ln_rstd needs the LayerNorm epilogue without pool32");
-    if (a->M == 0) return LIME_OK;
-
-    if (a->act == LIME_ACT_RELU_GRAD) {               // the ReLU gradient as an epilogue: fused in the split-product kernel, else two launches
-        LIME_REQUIRE(a->res && !a->res_ids && a->res_mod == 0 && a->res_div <= 1 && !a->ln_gamma && !a->pool32 && !a->m_dev && !a->c_ids,
-                     LIME_ERR_BAD_ARG, "lime_linear_f32: LIME_ACT_RELU_GRAD takes res = the forward activation (dense rows) and no other epilogue");
-        const int sp = lime_linear_sp(a, (hipStream_t)stream);
-        if (sp != LIME_PP_NOT_APPLICABLE) return sp;
-        lime_linear_args plain = *a;
-        plain.act = LIME_ACT_NONE;
-        plain.res = nullptr;
-        const int st = lime_linear_f32(&plain, stream);
-        if (st != LIME_OK) return st;
-        return lime_relu_bwd_f32(a->c, a->ldc, a->res, a->ldr, a->M, a->N, a->act_scale, stream);
-    }
-
-    if (a->dropout_p != 0.f) {                        // dropout behind the activation: fused in the split-product ReLU kernel, else a pass of its own
-        LIME_REQUIRE(a->dropout_p > 0.f && a->dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_linear_f32: dropout_p outside [0, 1)");
-        LIME_REQUIRE((a->act == LIME_ACT_NONE || a->act == LIME_ACT_RELU) && !a->res && !a->ln_gamma && !a->pool32 && !a->c_ids && !a->m_dev,
-                     LIME_ERR_BAD_ARG, "lime_linear_f32: dropout_p goes with act none / ReLU and no other epilogue");
-        const int sp = lime_linear_sp(a, (hipStream_t)stream);
-        if (sp != LIME_PP_NOT_APPLICABLE) return sp;
-        lime_linear_args plain = *a;
-        plain.dropout_p = 0.f;
-        const int st = lime_linear_f32(&plain, stream);
-        if (st != LIME_OK) return st;
-        return lime_dropout_f32(a->c, a->ldc, a->c, a->ldc, a->M, a->N, a->dropout_p, a->dropout_seed, a->dropout_site, stream);
-    }
-
-    // 4096 <= M with few 128-row tiles (M = 6400, N = 400: 100 tiles on 512 workgroup slots took 60 us on the big-M kernel, 32 us in
-    // 64 x 64 tiles): the mid-M kernel first, for the problems it takes (no LayerNorm / pooling / scatter)
-    if (a->M >= 4096 && !a->ln_gamma && !a->pool32 && !a->c_ids && !a->a_pe && !(lime_split_mode() & 4) &&       // (bit 2: tests pin kernels)
-        (((long)a->M + 127) / 128) * (((long)a->N + 255) / 256) < 160) {
-        const int st = lime_linear_mid(a, (hipStream_t)stream);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
-    }
-
-    // big M, 16-byte friendly operands: two four-wave workgroups per CU with LDS-DMA staging (gemm_pp_f32.hip)
-    static const bool pp_off = getenv("LIME_GEMM_NO_PP") != nullptr;          // A/B switch for tools/, not a product option
-    if (!pp_off || a->pool32) {
-        // first choice: fp32-level split products on the bf16 matrix cores (gemm_sp_f32.hip; lime_set_split_gemm(0) turns it off)
-        const int sp = lime_linear_sp(a, (hipStream_t)stream);
-        if (sp != LIME_PP_NOT_APPLICABLE) return sp;
-        const int st = lime_linear_pp(a, (hipStream_t)stream);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
-    }
-    LIME_REQUIRE(!a->c_ids, LIME_ERR_UNSUPPORTED,
-                 "lime_linear_f32: c_ids needs the big-M kernel (M >= 4096, 16-byte operands, periodic residual, no LayerNorm, act none)");
-    if (a->m_dev) {                                   // a device-side row count outside the big-M kernel: the mid-M kernel honours it
-        const int st = lime_linear_mid(a, (hipStream_t)stream);
-        LIME_REQUIRE(st != LIME_PP_NOT_APPLICABLE, LIME_ERR_UNSUPPORTED,
-                     "lime_linear_f32: m_dev needs 16-byte friendly operands (K, N multiples of 4, aligned rows) and no LayerNorm / pooling / a_pe");
-        return st;
-    }
-    LIME_REQUIRE(!a->pool32, LIME_ERR_UNSUPPORTED,
-                 "lime_linear_f32: pool32 needs the big-M kernel (M >= 4096 and a multiple of 32, LayerNorm + dense residual, 16-byte operands)");
-
+int gen_launch(const GenChoice& c, const lime_linear_args* a, int n_cu, hipStream_t s) {
     GemmP p;
     p.a = a->a; p.lda = a->lda; p.a_ids = a->a_ids; p.a_pe = a->a_pe; p.lda_pe = a->lda_pe; p.a_period = a->a_period;
     p.w = a->w; p.ldw = a->ldw; p.bias = a->bias;
@@ -654,44 +579,148 @@ extern "C" int lime_linear_f32(const lime_linear_args* a, void* stream) {
     p.n_row_blocks = p.n_col_blocks = 0;
     // acc + bias + res (the documented order with no activation) == (res + acc) + bias up to fp32 rounding
     p.res_in_acc = (a->res != nullptr && a->act == LIME_ACT_NONE) ? 1 : 0;
+#define X(TN, VEC, LN, PE, ACT, GENERIC, VIO)                                                                                     \
+    if (c.tn == TN && c.vec == VEC && c.ln == LN && c.pe == PE && c.act == ACT && c.generic == GENERIC && c.vio == VIO)           \
+        return launch_one<TN, VEC, LN, PE, ACT, GENERIC, VIO>(p, n_cu, s);
+    LIME_GEN_BUILT(X)
+#undef X
+    LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "lime_linear_f32: %s is not built", gen_name(c));
+}
 
+// `vec`-float (4 / 2 / 1) vector access to rows of `ld` floats from `ptr` is possible (a NULL operand is absent, hence fine)
+inline bool al_vec(const void* ptr, long ld, int vec) {
+    return vec == 4 ? lime_al16(ptr, ld) : ptr == nullptr || (((uintptr_t)ptr % (vec * sizeof(float))) == 0 && (ld % vec) == 0);
+}
+
+// The general kernel's instantiation for a block without c_ids / m_dev / pool32.
+//   LayerNorm epilogue: one eight-wave 128 x 256 / 128 x 320 tile spans the row (N <= 320); the residual (if any) is
+//   preloaded into the accumulators, so it must be a plain add.  Fast instantiation: 16-byte operand staging and
+//   16-byte residual / result accesses; anything misaligned takes the scalar-IO instantiation.
+//   Big M, no residual, activation none / ReLU, everything 16-byte friendly: the same eight-wave tiles, the width
+//   (256 / 320) that pads N least.  Everything else: 64 x 64 tiles with run-time epilogue (the caller asks the mid-M kernel first).
+int gen_choose(const lime_linear_args* a, GenChoice* c) {
     int vec = 4;
-    while (vec > 1 && !((a->K % vec) == 0 && aligned(a->a, a->lda, vec) && aligned(a->w, a->ldw, vec) &&
-                        aligned(a->a_pe, a->lda_pe, vec)))
-        vec >>= 1;
-    hipStream_t s = (hipStream_t)stream;
-    // Tile selection.
-    //   LayerNorm epilogue: one eight-wave 128 x 256 / 128 x 320 tile spans the row (N <= 320); the residual (if any) is
-    //   preloaded into the accumulators, so it must be a plain add.  Fast instantiation: 16-byte operand staging and
-    //   16-byte residual / result accesses; anything misaligned takes the scalar-IO instantiation.
-    //   Big M, no residual, activation none / ReLU, everything 16-byte friendly: the same eight-wave tiles, the width
-    //   (256 / 320) that pads N least.  Everything else: 64 x 64 tiles with run-time epilogue.
-    const bool has_res = a->res != nullptr;
-    const bool vio = vec == 4 && (a->N % 4 == 0) && aligned(a->c, a->ldc, 4) && aligned(a->res, a->ldr, 4) &&
-                     aligned(a->res_pe, a->ldr_pe, 4);
+    while (vec > 1 && !((a->K % vec) == 0 && al_vec(a->a, a->lda, vec) && al_vec(a->w, a->ldw, vec) && al_vec(a->a_pe, a->lda_pe, vec))) vec >>= 1;
+    const bool has_res = a->res != nullptr, pe = a->a_pe != nullptr;
+    const bool vio = vec == 4 && (a->N % 4 == 0) && lime_al16(a->c, a->ldc) && lime_al16(a->res, a->ldr) && lime_al16(a->res_pe, a->ldr_pe);
+    *c = {1, vec, 0, false, pe, true, false};
     if (a->ln_gamma) {
         LIME_REQUIRE(a->N <= 320, LIME_ERR_UNSUPPORTED, "lime_linear_f32: LayerNorm epilogue needs N <= 320 (N=%d)", a->N);
         LIME_REQUIRE(a->act == LIME_ACT_NONE || (a->act == LIME_ACT_RELU && !has_res), LIME_ERR_UNSUPPORTED,
                      "lime_linear_f32: LayerNorm epilogue supports act none (+ residual) or ReLU (no residual)");
-        LIME_REQUIRE(a->a_pe == nullptr, LIME_ERR_UNSUPPORTED, "lime_linear_f32: LayerNorm epilogue with a positional A operand");
-        if (a->N <= 256) return vio ? launch_one<1, 4, 4, 2, 4, true, false, 0, false, true>(p, 1, s)
-                                    : launch_one<1, 4, 4, 2, 1, true, false, 0, false, false>(p, 1, s);
-        return vio ? launch_one<1, 5, 4, 2, 4, true, false, 0, false, true>(p, 1, s)
-                   : launch_one<1, 5, 4, 2, 1, true, false, 0, false, false>(p, 1, s);
+        LIME_REQUIRE(!pe, LIME_ERR_UNSUPPORTED, "lime_linear_f32: LayerNorm epilogue with a positional A operand");
+        *c = {a->N <= 256 ? 4 : 5, vio ? 4 : 1, 0, true, false, false, vio};
+    } else if (a->M >= 4096 && !has_res && (a->act == LIME_ACT_NONE || a->act == LIME_ACT_RELU) && vio) {
+        *c = {lime_pp_wide(a->N, false) ? 5 : 4, 4, a->act, false, pe, false, true};
     }
-    const bool simple = !has_res && (a->act == LIME_ACT_NONE || a->act == LIME_ACT_RELU);
-    if (a->M >= 4096 && simple && vio) {
-        const bool relu = a->act == LIME_ACT_RELU, pe = a->a_pe != nullptr;
-        if (lime_pp_wide(a->N, false)) {
-            if (pe) return relu ? launch_one<1, 5, 4, 2, 4, false, true, 1, false, true>(p, 1, s) : launch_one<1, 5, 4, 2, 4, false, true, 0, false, true>(p, 1, s);
-            return relu ? launch_one<1, 5, 4, 2, 4, false, false, 1, false, true>(p, 1, s) : launch_one<1, 5, 4, 2, 4, false, false, 0, false, true>(p, 1, s);
-        }
-        if (pe) return relu ? launch_one<1, 4, 4, 2, 4, false, true, 1, false, true>(p, 1, s) : launch_one<1, 4, 4, 2, 4, false, true, 0, false, true>(p, 1, s);
-        return relu ? launch_one<1, 4, 4, 2, 4, false, false, 1, false, true>(p, 1, s) : launch_one<1, 4, 4, 2, 4, false, false, 0, false, true>(p, 1, s);
+    return LIME_OK;
+}
+
+// ---- the routing of lime_linear_f32: one pure decision ----------------------------------------------------------------------------
+struct Route {
+    int family;                     // LIME_LINEAR_SP / _PP / _MID / _GENERAL
+    int second;                     // LIME_LINEAR_PASS_* behind the GEMM (the dropout pass runs first)
+    lime_linear_args gemm;          // the GEMM's own argument block: the caller's, less what the second passes do
+    LimeSpChoice sp; LimePpChoice pp; LimeMidChoice mid; GenChoice gen;
+};
+
+// Which kernel takes argument block a (already through check_args, M > 0) under split mode `mode` on n_cu compute units: no launch,
+// no HIP call, no pointer dereferenced.  LIME_OK and *r, or the error of a block nothing takes.  The order of preference lives here
+// and nowhere else ("Routing").
+int linear_route(const lime_linear_args* a, int mode, int n_cu, Route* r) {
+    static const bool pp_off = getenv("LIME_GEMM_NO_PP") != nullptr;          // A/B switches for tools/, not product options
+    static const bool mid_off = getenv("LIME_GEMM_NO_MID") != nullptr;
+    r->second = 0;
+    r->gemm = *a;
+    lime_linear_args* g = &r->gemm;
+    auto sp = [&] { r->family = LIME_LINEAR_SP; return lime_sp_choose(g, mode, n_cu, &r->sp); };
+    auto pp = [&] { r->family = LIME_LINEAR_PP; return lime_pp_choose(g, &r->pp); };
+    auto mid = [&] { r->family = LIME_LINEAR_MID; return !mid_off && lime_mid_choose(g, n_cu, &r->mid); };
+
+    if (g->act == LIME_ACT_RELU_GRAD) {              // the ReLU gradient as an epilogue: fused in the split-product kernel, else a second pass
+        LIME_REQUIRE(g->res && !g->res_ids && g->res_mod == 0 && g->res_div <= 1 && !g->ln_gamma && !g->pool32 && !g->m_dev && !g->c_ids,
+                     LIME_ERR_BAD_ARG, "lime_linear_f32: LIME_ACT_RELU_GRAD takes res = the forward activation (dense rows) and no other epilogue");
+        if (sp()) return LIME_OK;
+        g->act = LIME_ACT_NONE, g->res = nullptr;
+        r->second |= LIME_LINEAR_PASS_RELU_BWD;
     }
-    {   // small / mid M (and anything the big-tile kernels above do not take): the deep-prefetch LDS-DMA kernel (gemm_mid_f32.hip)
-        const int st = lime_linear_mid(a, s);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
+    if (g->dropout_p != 0.f) {                        // dropout behind the activation: fused in the split-product ReLU kernel, else a pass of its own
+        LIME_REQUIRE(g->dropout_p > 0.f && g->dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_linear_f32: dropout_p outside [0, 1)");
+        LIME_REQUIRE((g->act == LIME_ACT_NONE || g->act == LIME_ACT_RELU) && !g->res && !g->ln_gamma && !g->pool32 && !g->c_ids && !g->m_dev,
+                     LIME_ERR_BAD_ARG, "lime_linear_f32: dropout_p goes with act none / ReLU and no other epilogue");
+        if (sp()) return LIME_OK;
+        g->dropout_p = 0.f;
+        r->second |= LIME_LINEAR_PASS_DROPOUT;
     }
-    return launch_small(p, vec, s);
+    // 4096 <= M with few 128-row tiles (M = 6400, N = 400: 100 tiles on 512 workgroup slots took 60 us on the big-M kernel, 32 us in
+    // 64 x 64 tiles): the mid-M kernel first, for the problems it takes (no LayerNorm / pooling / scatter)
+    if (g->M >= 4096 && !g->ln_gamma && !g->pool32 && !g->c_ids && !g->a_pe && !(mode & 4) &&       // (bit 2: tests pin kernels)
+        (((long)g->M + 127) / 128) * (((long)g->N + 255) / 256) < 160 && mid())
+        return LIME_OK;
+    // big M, 16-byte friendly operands: first choice the fp32-level split products on the bf16 matrix cores (gemm_sp_f32.hip;
+    // lime_set_split_gemm(0) turns it off), then two four-wave workgroups per CU with LDS-DMA staging (gemm_pp_f32.hip)
+    if ((!pp_off || g->pool32) && (sp() || pp())) return LIME_OK;
+    LIME_REQUIRE(!g->c_ids, LIME_ERR_UNSUPPORTED,
+                 "lime_linear_f32: c_ids needs the big-M kernel (M >= 4096, 16-byte operands, periodic residual, no LayerNorm, act none)");
+    LIME_REQUIRE(!g->m_dev || mid(), LIME_ERR_UNSUPPORTED,      // a device-side row count outside the big-M kernel: the mid-M kernel honours it
+                 "lime_linear_f32: m_dev needs 16-byte friendly operands (K, N multiples of 4, aligned rows) and no LayerNorm / pooling / a_pe");
+    if (g->m_dev) return LIME_OK;
+    LIME_REQUIRE(!g->pool32, LIME_ERR_UNSUPPORTED,
+                 "lime_linear_f32: pool32 needs the big-M kernel (M >= 4096 and a multiple of 32, LayerNorm + dense residual, 16-byte operands)");
+    const int st = gen_choose(g, &r->gen);
+    // small / mid M (and anything the big-tile kernels above do not take): the deep-prefetch LDS-DMA kernel (gemm_mid_f32.hip)
+    if (st != LIME_OK || (r->gen.generic && mid())) return st;
+    r->family = LIME_LINEAR_GENERAL;
+    return LIME_OK;
+}
+
+int check_args(const lime_linear_args* a, const char* fn) {
+    LIME_REQUIRE(a != nullptr, LIME_ERR_BAD_ARG, "%s: args is NULL", fn);
+    LIME_REQUIRE(a->a && a->w && a->c, LIME_ERR_BAD_ARG, "%s: a, w and c must be non-NULL", fn);
+    LIME_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, LIME_ERR_BAD_ARG, "%s: bad dims M=%d N=%d K=%d", fn, a->M, a->N, a->K);
+    LIME_REQUIRE(a->ldw >= a->K && a->ldc >= a->N && a->lda >= a->K, LIME_ERR_BAD_ARG,
+                 "%s: leading dimension smaller than the row (lda=%ld ldw=%ld ldc=%ld)", fn, (long)a->lda, (long)a->ldw, (long)a->ldc);
+    LIME_REQUIRE(!a->a_pe || (a->a_ids && a->a_period > 0 && a->lda_pe >= a->K), LIME_ERR_BAD_ARG, "%s: a_pe needs a_ids, a_period > 0 and lda_pe >= K", fn);
+    LIME_REQUIRE(!a->res || a->res_ids || a->res_div >= 1, LIME_ERR_BAD_ARG, "%s: res_div must be >= 1", fn);
+    LIME_REQUIRE(!a->res || a->ldr >= a->N, LIME_ERR_BAD_ARG, "%s: ldr smaller than N", fn);
+    LIME_REQUIRE(!a->res_pe || (a->res_ids && a->res_period > 0 && a->ldr_pe >= a->N), LIME_ERR_BAD_ARG, "%s: res_pe needs res_ids, res_period > 0 and ldr_pe >= N", fn);
+    LIME_REQUIRE(!a->ln_gamma || a->ln_beta, LIME_ERR_BAD_ARG, "%s: ln_gamma without ln_beta", fn);
+    LIME_REQUIRE(a->act >= LIME_ACT_NONE && a->act <= LIME_ACT_RELU_GRAD, LIME_ERR_BAD_ARG, "%s: bad act %d", fn, a->act);
+    LIME_REQUIRE(a->res_mod >= 0 && (a->pool32 == 0 || a->pool32 == 1), LIME_ERR_BAD_ARG, "%s: res_mod < 0 or pool32 not 0 / 1", fn);
+    LIME_REQUIRE(!a->ln_rstd || (a->ln_gamma && !a->pool32), LIME_ERR_BAD_ARG, "%s: ln_rstd needs the LayerNorm epilogue without pool32", fn);
+    return LIME_OK;
+}
+
+}  // namespace
+
+extern "C" int lime_linear_plan_f32(const lime_linear_args* a, int32_t n_cu, lime_linear_plan* out) {
+    int st = check_args(a, "lime_linear_plan_f32");
+    if (st != LIME_OK) return st;
+    LIME_REQUIRE(out != nullptr, LIME_ERR_BAD_ARG, "lime_linear_plan_f32: out is NULL");
+    *out = lime_linear_plan{LIME_LINEAR_NONE, 0, -1, 0, 0, ""};
+    if (a->M == 0) return LIME_OK;
+    Route r;
+    st = linear_route(a, lime_split_mode(), n_cu > 0 ? n_cu : lime_num_cus(), &r);
+    if (st != LIME_OK) return st;
+    const bool mid = r.family == LIME_LINEAR_MID;
+    *out = lime_linear_plan{r.family, r.second, mid ? r.mid.shape : -1, 0, mid ? r.mid.ntiles : 0, ""};
+    snprintf(out->name, sizeof(out->name), "%s", r.family == LIME_LINEAR_SP ? lime_sp_name(r.sp) : r.family == LIME_LINEAR_PP ? lime_pp_name(r.pp, false)
+                                                 : mid ? lime_mid_name() : gen_name(r.gen));
+    return LIME_OK;
+}
+
+extern "C" int lime_linear_f32(const lime_linear_args* a, void* stream) {
+    int st = check_args(a, "lime_linear_f32");
+    if (st != LIME_OK || a->M == 0) return st;
+    const int n_cu = lime_num_cus();
+    hipStream_t s = (hipStream_t)stream;
+    Route r;
+    st = linear_route(a, lime_split_mode(), n_cu, &r);
+    if (st != LIME_OK) return st;
+    st = r.family == LIME_LINEAR_SP ? lime_sp_launch(r.sp, &r.gemm, s) : r.family == LIME_LINEAR_PP ? lime_pp_launch(r.pp, &r.gemm, s)
+       : r.family == LIME_LINEAR_MID ? lime_mid_launch(r.mid, &r.gemm, s) : gen_launch(r.gen, &r.gemm, n_cu, s);
+    if (st == LIME_OK && (r.second & LIME_LINEAR_PASS_DROPOUT))
+        st = lime_dropout_f32(a->c, a->ldc, a->c, a->ldc, a->M, a->N, a->dropout_p, a->dropout_seed, a->dropout_site, stream);
+    if (st == LIME_OK && (r.second & LIME_LINEAR_PASS_RELU_BWD)) st = lime_relu_bwd_f32(a->c, a->ldc, a->res, a->ldr, a->M, a->N, a->act_scale, stream);
+    return st;
 }

@@ -28,7 +28,7 @@ struct MidP {
     const float* w; long ldw; const float* bias;
     const float* res; long ldr; int res_div, res_mod; const int* res_ids;
     float* c; long ldc; int M, N, K, act, n_col_blocks;
-    int shape;           // tile shape of this problem: 0 = 64 x 64, 1 = 32 x 64, 2 = 32 x 32 (mid_params)
+    int shape;           // tile shape of this problem: 0 = 64 x 64, 1 = 32 x 64, 2 = 32 x 32 (lime_mid_choose)
     const int* m_dev;    // optional device-side row count (min(*m_dev, M) rows; workgroups of tiles beyond it exit)
 };
 
@@ -202,40 +202,38 @@ __global__ __launch_bounds__(256, 3) void gemm_mid_group_kernel(const MidGroup g
 
 }  // namespace
 
-// fills p and the tile count; false: the problem is outside this kernel
-static bool mid_params(const lime_linear_args* a, MidP& p, long& ntiles) {
+// false: the problem is outside this kernel
+bool lime_mid_choose(const lime_linear_args* a, int n_cu, LimeMidChoice* c) {
     if (a->ln_gamma || a->pool32 || a->a_pe || a->ln_rstd || a->c_ids || a->res_pe) return false;
     if (a->dropout_p != 0.f || a->act == LIME_ACT_RELU_GRAD) return false;       // (lime_linear_f32 strips both before it comes here)
-    if (a->K % 4 || a->N % 4 || a->K < 16) return false;
-    if (!lime_al16(a->a, a->lda) || !lime_al16(a->w, a->ldw) || !lime_al16(a->c, a->ldc) || !lime_al16(a->res, a->ldr)) return false;
-    const long lim = 0x7FFFFFF0L;
-    if (64L * a->lda * 4 >= lim || 64L * a->ldw * 4 >= lim) return false;
+    if (a->K < KB || !lime_pp_al16(a)) return false;
+    if (64L * a->lda * 4 >= 0x7FFFFFF0L || 64L * a->ldw * 4 >= 0x7FFFFFF0L) return false;      // 32-bit offsets within a 64-row block
+    // the smallest tiles whose workgroups still run in ONE round (three workgroups per CU): the launch is then one tile's k loop long
+    const long slots = 3L * n_cu;
+    const long t64 = (long)((a->M + 63) / 64) * ((a->N + 63) / 64), t3264 = (long)((a->M + 31) / 32) * ((a->N + 63) / 64),
+               t32 = (long)((a->M + 31) / 32) * ((a->N + 31) / 32);
+    static const char* const force = getenv("LIME_MID_SHAPE");               // A/B switch for tools/, not a product option
+    c->shape = force ? (atoi(force) == 2 ? 2 : (atoi(force) == 1 ? 1 : 0)) : (t32 <= slots ? 2 : (t3264 <= slots ? 1 : 0));
+    c->ntiles = c->shape == 2 ? t32 : (c->shape == 1 ? t3264 : t64);
+    return c->ntiles <= 0x3FFFFFFFL;
+}
+
+static MidP mid_params(const lime_linear_args* a, int shape) {
+    MidP p;
     p.a = a->a; p.lda = a->lda; p.a_ids = a->a_ids;
     p.w = a->w; p.ldw = a->ldw; p.bias = a->bias;
     p.res = a->res; p.ldr = a->ldr; p.res_div = a->res_div > 0 ? a->res_div : 1; p.res_ids = a->res_ids;
     p.res_mod = (a->res && !a->res_ids && a->res_mod > 0) ? a->res_mod : 0;
     p.c = a->c; p.ldc = a->ldc; p.M = a->M; p.N = a->N; p.K = a->K; p.act = a->act; p.m_dev = a->m_dev;
-    // the smallest tiles whose workgroups still run in ONE round (three workgroups per CU): the launch is then one tile's k loop long
-    static const long slots = 3L * lime_num_cus();
-    const long t64 = (long)((a->M + 63) / 64) * ((a->N + 63) / 64), t3264 = (long)((a->M + 31) / 32) * ((a->N + 63) / 64),
-               t32 = (long)((a->M + 31) / 32) * ((a->N + 31) / 32);
-    static const char* const force = getenv("LIME_MID_SHAPE");               // A/B switch for tools/, not a product option
-    p.shape = force ? (atoi(force) == 2 ? 2 : (atoi(force) == 1 ? 1 : 0)) : (t32 <= slots ? 2 : (t3264 <= slots ? 1 : 0));
-    const int tn = p.shape == 2 ? 32 : 64;
+    p.shape = shape;
+    const int tn = shape == 2 ? 32 : 64;
     p.n_col_blocks = (a->N + tn - 1) / tn;
-    ntiles = p.shape == 2 ? t32 : (p.shape == 1 ? t3264 : t64);
-    return ntiles <= 0x3FFFFFFFL;
+    return p;
 }
 
-// LIME_OK / error: launched; LIME_PP_NOT_APPLICABLE: the caller takes the general kernel.
-int lime_linear_mid(const lime_linear_args* a, hipStream_t s) {
-    static const bool off = getenv("LIME_GEMM_NO_MID") != nullptr;           // A/B switch for tools/, not a product option
-    if (off) return LIME_PP_NOT_APPLICABLE;
-    MidP p;
-    long ntiles = 0;
-    if (!mid_params(a, p, ntiles)) return LIME_PP_NOT_APPLICABLE;
-    hipLaunchKernelGGL(gemm_mid_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, p);
-    lime_set_last_linear_kernel("gemm_mid_kernel");
+int lime_mid_launch(const LimeMidChoice& c, const lime_linear_args* a, hipStream_t s) {
+    hipLaunchKernelGGL(gemm_mid_kernel, dim3((unsigned)c.ntiles), dim3(256), 0, s, mid_params(a, c.shape));
+    lime_set_last_linear_kernel("%s", lime_mid_name());
     return lime_check_launch("lime_linear_f32");
 }
 
@@ -244,6 +242,7 @@ extern "C" int lime_linear_group_f32(const lime_linear_args* args, int32_t n, vo
     MidGroup g;
     g.n = 0;
     long total = 0;
+    const int n_cu = lime_num_cus();
     for (int k = 0; k < n; ++k) {
         const lime_linear_args* a = &args[k];
         LIME_REQUIRE(a->a && a->w && a->c, LIME_ERR_BAD_ARG, "lime_linear_group_f32: problem %d: a, w and c must be non-NULL", k);
@@ -252,12 +251,13 @@ extern "C" int lime_linear_group_f32(const lime_linear_args* args, int32_t n, vo
         LIME_REQUIRE(a->act >= LIME_ACT_NONE && a->act <= LIME_ACT_RELU_GRAD && a->res_mod >= 0 && (!a->res || a->res_ids || a->res_div >= 1) &&
                      (!a->res || a->ldr >= a->N), LIME_ERR_BAD_ARG, "lime_linear_group_f32: problem %d: bad act / residual arguments", k);
         if (a->M == 0) continue;
-        long ntiles = 0;
-        LIME_REQUIRE(mid_params(a, g.p[g.n], ntiles), LIME_ERR_UNSUPPORTED,
+        LimeMidChoice c;
+        LIME_REQUIRE(lime_mid_choose(a, n_cu, &c), LIME_ERR_UNSUPPORTED,
                      "lime_linear_group_f32: problem %d is outside the mid-M kernel (16-byte friendly operands, K >= 16, no LayerNorm / pooling / "
                      "a_pe / c_ids / res_pe / dropout / ReLU gradient): launch it with lime_linear_f32", k);
+        g.p[g.n] = mid_params(a, c.shape);
         g.first[g.n] = (int)total;
-        total += ntiles;
+        total += c.ntiles;
         LIME_REQUIRE(total <= 0x3FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_linear_group_f32: too many tiles");
         ++g.n;
     }

@@ -1,10 +1,11 @@
-// Internal interface between lime_linear_f32's dispatcher (gemm_f32.hip) and the big-M / mid-M kernels behind it (gemm_pp_f32.hip,
-// gemm_sp_f32.hip, gemm_mid_f32.hip), their shared parameter block, and the split-product entry points other units dispatch to.
+// Internal interface between lime_linear_f32's routing (gemm_f32.hip) and the big-M / mid-M kernels behind it (gemm_pp_f32.hip,
+// gemm_sp_f32.hip, gemm_mid_f32.hip): each unit's pure chooser and the launch of what it chose, the predicates the choosers share,
+// the kernels' parameter block, and the split-product entry points other units dispatch to.
 #pragma once
 #include "common.h"
 #include "dropout.h"
 
-#define LIME_PP_NOT_APPLICABLE 1
+#define LIME_PP_NOT_APPLICABLE 1     // lime_token_attention_sp / _bwd_sp: not taken, the caller goes on to its other kernels
 
 struct PPParams {
     const float* a; long lda; const int* a_ids;
@@ -49,9 +50,56 @@ static inline bool lime_pp_wide(int N, bool tie_wide) {
     return tie_wide ? pad5 <= pad4 : pad5 < pad4;
 }
 
-int lime_linear_pp(const lime_linear_args* a, hipStream_t stream);
-int lime_linear_sp(const lime_linear_args* a, hipStream_t stream);       // gemm_sp_f32.hip (split product on the bf16 cores), same convention
-int lime_linear_mid(const lime_linear_args* a, hipStream_t stream);      // gemm_mid_f32.hip, same return convention
+// ---- lime_linear_f32's routing ------------------------------------------------------------------------------------------------
+// A chooser is a pure function of the argument block (pointers are looked at for NULL-ness and alignment only), the split mode and
+// the CU count: false = this family does not take the call, true = *c holds the template arguments of the instantiation that does.
+// lime_*_name prints them as rocprofv3 prints the kernel (plan and launch<> both call it; the string lives until the thread's next
+// call); lime_*_launch runs that instantiation, or returns LIME_ERR_UNSUPPORTED with a message when the unit does not build it.  The order of preference between the families:
+// linear_route() in gemm_f32.hip.
+
+// What the LDS-DMA kernels ask of their operands, written once.  All of them decline only, so their order does not matter.
+// 16-byte loads / stores of every row (the mid-M kernel: of a, w, c and res; it takes no res_pe)
+static inline bool lime_pp_al16(const lime_linear_args* a) {
+    return a->K % 4 == 0 && a->N % 4 == 0 && lime_al16(a->a, a->lda) && lime_al16(a->w, a->ldw) && lime_al16(a->c, a->ldc) &&
+           lime_al16(a->res, a->ldr) && lime_al16(a->res_pe, a->ldr_pe);
+}
+// residual class (the RES template argument): 0 none, 1 dense / periodic / broadcast fp32 rows, 2 rows gathered by res_ids,
+// 3 no residual: res is the forward ReLU output that gates the result (LIME_ACT_RELU_GRAD)
+static inline int lime_pp_res_class(const lime_linear_args* a) {
+    return a->act == LIME_ACT_RELU_GRAD ? 3 : !a->res ? 0 : a->res_ids ? 2 : 1;
+}
+// 32-bit byte offsets: within one block of `bm` rows of a dense operand, within the whole of a gathered / periodic / scattered one
+static inline bool lime_pp_offsets32(const lime_linear_args* a, long bm) {
+    const long lim = 0x7FFFFFF0L;
+    if (a->bias && (uintptr_t)a->bias % 4) return false;
+    if (bm * a->lda * 4 >= lim || (long)a->N * a->ldw * 4 >= lim || bm * a->ldc * 4 >= lim || bm * a->ldr * 4 >= lim || (long)a->M * 4 >= lim) return false;
+    if (a->c_ids && (long)a->M * a->ldc * 4 >= lim) return false;
+    return !(lime_pp_res_class(a) == 1 && a->res_mod > 0 && (long)a->res_mod * a->ldr * 4 >= lim);
+}
+// c_ids: compacted in_proj only -- a periodic residual indexed by the scattered row, no LayerNorm, act none
+static inline bool lime_pp_cids_form(const lime_linear_args* a) {
+    return !a->c_ids || (a->res && !a->res_ids && a->res_mod > 0 && !a->ln_gamma && a->act == LIME_ACT_NONE);
+}
+// pool32: LayerNorm over a dense residual, whole 32-row blocks
+static inline bool lime_pp_pool_form(const lime_linear_args* a) {
+    return !a->pool32 || (a->ln_gamma && a->res && !a->res_ids && a->res_div <= 1 && a->M % 32 == 0);
+}
+// LayerNorm: one tile spans the row, and the ReLU instantiations carry no LayerNorm
+static inline bool lime_pp_ln_form(const lime_linear_args* a) { return !a->ln_gamma || (a->N <= 320 && a->act != LIME_ACT_RELU); }
+
+struct LimeSpChoice { int ct, res; bool ln, relu, pool, rstd, cid; };                 // gemm_sp_kernel<CT, LN, RELU, RES, POOL, RSTD, CID>
+struct LimePpChoice { int ntl, res, trim; bool ln, relu, pool, rstd, cid; };          // gemm_pp_kernel<NTL, LN, RELU, RES, false, POOL, RSTD, CID, TRIM>
+struct LimeMidChoice { int shape; long ntiles; };                                     // gemm_mid_kernel: tile shape 0 = 64 x 64, 1 = 32 x 64, 2 = 32 x 32
+bool lime_sp_choose(const lime_linear_args* a, int mode, int n_cu, LimeSpChoice* c);  // gemm_sp_f32.hip (split product on the bf16 cores)
+bool lime_pp_choose(const lime_linear_args* a, LimePpChoice* c);                      // gemm_pp_f32.hip (fp32 MFMA, LDS-DMA staging)
+bool lime_mid_choose(const lime_linear_args* a, int n_cu, LimeMidChoice* c);          // gemm_mid_f32.hip (64-row tiles and smaller)
+const char* lime_sp_name(const LimeSpChoice& c);
+const char* lime_pp_name(const LimePpChoice& c, bool bf);
+static inline const char* lime_mid_name() { return "gemm_mid_kernel"; }
+static inline const char* lime_tf(bool v) { return v ? "true" : "false"; }
+int lime_sp_launch(const LimeSpChoice& c, const lime_linear_args* a, hipStream_t stream);
+int lime_pp_launch(const LimePpChoice& c, const lime_linear_args* a, hipStream_t stream);
+int lime_mid_launch(const LimeMidChoice& c, const lime_linear_args* a, hipStream_t stream);
 
 // wgrad_sp_f32.hip: the weight gradient on the split product (lime_linear_wgrad_f32's big-M path, wgrad_f32.hip dispatches)
 struct LimeWgradSpPlan { bool swap; int n_tiles, k_tiles, splits, rows_per_split; long np, kp; double fill; };

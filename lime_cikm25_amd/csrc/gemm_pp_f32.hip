@@ -488,90 +488,74 @@ int launch(const PPParams& p0, hipStream_t stream) {
     p.stamps = g_pp_stamp_buf;
 #endif
     hipLaunchKernelGGL((gemm_pp_kernel<NTL, LN, RELU, RES, BF, POOL, RSTD, CID, TRIM>), dim3((unsigned)nwg), dim3(256), 0, stream, p);
-    lime_set_last_linear_kernel("gemm_pp_kernel<%d, %s, %s, %d, %s, %s, %s, %s, %d>", NTL, LN ? "true" : "false", RELU ? "true" : "false", RES,
-                                BF ? "true" : "false", POOL ? "true" : "false", RSTD ? "true" : "false", CID ? "true" : "false", TRIM);   // as rocprofv3 prints it
+    lime_set_last_linear_kernel("%s", lime_pp_name({NTL, RES, TRIM, LN, RELU, POOL, RSTD, CID}, BF));
     return lime_check_launch("lime_linear_f32");
 }
 
 }  // namespace
 
-// LIME_OK / error: launched (or failed); LIME_PP_NOT_APPLICABLE: the caller takes the general kernel.
-int lime_linear_pp(const lime_linear_args* a, hipStream_t s) {
-    const bool has_res = a->res != nullptr, ln = a->ln_gamma != nullptr;
-    const bool relu = a->act == LIME_ACT_RELU;
-    if (a->M < 4096 || a->a_pe != nullptr) return LIME_PP_NOT_APPLICABLE;
-    if (a->c_ids && !(has_res && !a->res_ids && a->res_mod > 0 && !ln && a->act == LIME_ACT_NONE)) return LIME_PP_NOT_APPLICABLE;
-    if (a->c_ids && (long)a->M * a->ldc * 4 >= 0x7FFFFFF0L) return LIME_PP_NOT_APPLICABLE;    // scattered rows: offsets from C's base
-    if (!(a->act == LIME_ACT_NONE || (relu && !has_res))) return LIME_PP_NOT_APPLICABLE;
-    if (a->K % 4 || a->N % 4 || a->K < 2 * 16) return LIME_PP_NOT_APPLICABLE;      // >= 2 chunks: a barrier between the
-                                                                                     // bias image's write and its read
-    if (!lime_al16(a->a, a->lda) || !lime_al16(a->w, a->ldw) || !lime_al16(a->c, a->ldc) || !lime_al16(a->res, a->ldr) || !lime_al16(a->res_pe, a->ldr_pe))
-        return LIME_PP_NOT_APPLICABLE;
-    if (a->bias && (uintptr_t)a->bias % 4) return LIME_PP_NOT_APPLICABLE;
-    // 32-bit byte offsets: within one 128-row block of a dense operand, within the whole of a gathered / periodic one
-    const long lim = 0x7FFFFFF0L;
-    if (128L * a->lda * 4 >= lim || (long)a->N * a->ldw * 4 >= lim || 128L * a->ldc * 4 >= lim || 128L * a->ldr * 4 >= lim)
-        return LIME_PP_NOT_APPLICABLE;
-    if ((long)a->M * 4 >= lim) return LIME_PP_NOT_APPLICABLE;
-    int res = 0;
-    if (has_res) {
-        if (a->res_ids) res = 2;
-        else if (a->res_div <= 1) res = 1;
-        else return LIME_PP_NOT_APPLICABLE;
-        if (res == 1 && a->res_mod > 0 && (long)a->res_mod * a->ldr * 4 >= lim) return LIME_PP_NOT_APPLICABLE;
-    }
-    if (ln && (a->N > 320 || relu)) return LIME_PP_NOT_APPLICABLE;
-    if (a->pool32 && !(ln && has_res && !a->res_ids && a->res_div <= 1 && a->M % 32 == 0)) return LIME_PP_NOT_APPLICABLE;
+const char* lime_pp_name(const LimePpChoice& c, bool bf) {
+    static thread_local char buf[96];
+    snprintf(buf, sizeof(buf), "gemm_pp_kernel<%d, %s, %s, %d, %s, %s, %s, %s, %d>", c.ntl, lime_tf(c.ln), lime_tf(c.relu), c.res, lime_tf(bf),
+             lime_tf(c.pool), lime_tf(c.rstd), lime_tf(c.cid), c.trim);        // as rocprofv3 prints it
+    return buf;
+}
+
+// false: the caller goes on to the general kernel
+bool lime_pp_choose(const lime_linear_args* a, LimePpChoice* c) {
+    const bool has_res = a->res != nullptr, ln = a->ln_gamma != nullptr, relu = a->act == LIME_ACT_RELU;
+    if (a->M < 4096 || a->a_pe != nullptr) return false;
+    if (!(a->act == LIME_ACT_NONE || (relu && !has_res))) return false;
+    if (a->K < 2 * 16) return false;                   // >= 2 chunks: a barrier between the bias image's write and its read
+    if (!lime_pp_al16(a) || !lime_pp_offsets32(a, BM) || !lime_pp_cids_form(a) || !lime_pp_pool_form(a) || !lime_pp_ln_form(a)) return false;
+    const int res = lime_pp_res_class(a);
+    if (res == 1 && a->res_div > 1) return false;      // no broadcast rows here
     // column validity is tested in the last two 32-column tiles of a block only: the last block must not be narrower
     auto tail_ok = [&](int bn) { const int last = a->N - (a->N - 1) / bn * bn; return last >= bn - 64; };
-
-    PPParams p = lime_pp_params(a);
-    p.ln_rstd = a->ln_rstd;
-    if (a->c_ids) {                                    // compacted in_proj: periodic residual, rows scattered by c_ids
-        if (!lime_pp_wide(a->N, false) || !tail_ok(320)) return LIME_PP_NOT_APPLICABLE;
-        return launch<10, false, false, 1, false, false, false, true>(p, s);
-    }
-    if (ln) {
-        if (!tail_ok(320)) return LIME_PP_NOT_APPLICABLE;
-        if (a->ln_rstd) {                              // training forward: residual + LayerNorm, rstd kept
-            if (res == 0 || a->pool32) return LIME_PP_NOT_APPLICABLE;
-            if (a->N <= 304 && a->N >= 304 - 64)
-                return res == 1 ? launch<10, true, false, 1, false, false, true, false, 1>(p, s)
-                                : launch<10, true, false, 2, false, false, true, false, 1>(p, s);
-            return res == 1 ? launch<10, true, false, 1, false, false, true>(p, s) : launch<10, true, false, 2, false, false, true>(p, s);
-        }
-        if (a->N <= 304 && a->N >= 304 - 64 && res != 0) {   // 19 column tiles (304 columns) cover N = 300: 5 % less MFMA work, 8 registers less
-            if (res == 1) return a->pool32 ? launch<10, true, false, 1, false, true, false, false, 1>(p, s)
-                                           : launch<10, true, false, 1, false, false, false, false, 1>(p, s);
-            return launch<10, true, false, 2, false, false, false, false, 1>(p, s);
-        }
-        if (res == 0) return launch<10, true, false, 0>(p, s);
-        if (res == 1) return a->pool32 ? launch<10, true, false, 1, false, true>(p, s) : launch<10, true, false, 1>(p, s);
-        return launch<10, true, false, 2>(p, s);
-    }
-    if (res == 2) return LIME_PP_NOT_APPLICABLE;
     const bool wide = lime_pp_wide(a->N, false);
+    *c = {10, res, 0, ln, relu, a->pool32 != 0, a->ln_rstd != nullptr, a->c_ids != nullptr};
+    if (a->c_ids) return wide && tail_ok(320);         // compacted in_proj: periodic residual, rows scattered by c_ids
+    if (ln) {
+        if (!tail_ok(320) || (a->ln_rstd && res == 0)) return false;        // (training forward: residual + LayerNorm, rstd kept)
+        // 19 column tiles (304 columns) cover N = 300: 5 % less MFMA work, 8 registers less
+        if (a->N <= 304 && a->N >= 304 - 64 && res != 0) c->trim = 1;
+        return true;
+    }
+    if (res == 2) return false;
     if (tail_ok(wide ? 320 : 256)) {
-        if (wide) {
-            if (res == 1) return launch<10, false, false, 1>(p, s);
-            return relu ? launch<10, false, true, 0>(p, s) : launch<10, false, false, 0>(p, s);
-        }
-        if (res == 1) return launch<8, false, false, 1>(p, s);
-        return relu ? launch<8, false, true, 0>(p, s) : launch<8, false, false, 0>(p, s);
+        c->ntl = wide ? 10 : 8;
+        return true;
     }
     // N whose last 256 / 320-column block would be too narrow (N = 400, 1200, 200 of the layers around the encoders at large
     // batch): 19-tile (304) or 13-tile (208) slabs of the same loaders -- the trimmed tiles are simply not computed
     const int pad304 = (a->N + 303) / 304 * 304 - a->N, pad208 = (a->N + 207) / 208 * 208 - a->N;
     const bool ok304 = tail_ok(304), ok208 = tail_ok(208);
-    if (ok304 && (!ok208 || pad304 <= pad208)) {
-        if (res == 1) return launch<10, false, false, 1, false, false, false, false, 1>(p, s);
-        return relu ? launch<10, false, true, 0, false, false, false, false, 1>(p, s) : launch<10, false, false, 0, false, false, false, false, 1>(p, s);
-    }
-    if (ok208) {
-        if (res == 1) return launch<8, false, false, 1, false, false, false, false, 3>(p, s);
-        return relu ? launch<8, false, true, 0, false, false, false, false, 3>(p, s) : launch<8, false, false, 0, false, false, false, false, 3>(p, s);
-    }
-    return LIME_PP_NOT_APPLICABLE;
+    if (ok304 && (!ok208 || pad304 <= pad208)) c->trim = 1;
+    else if (ok208) c->ntl = 8, c->trim = 3;
+    else return false;
+    return true;
+}
+
+// every fp32 instantiation this unit builds: NTL, LN, RELU, RES, POOL, RSTD, CID, TRIM
+#define LIME_PP_BUILT(X)                                                                                                          \
+    X(10, 0, 0, 1, 0, 0, 1, 0)                                                                /* compacted in_proj (c_ids) */     \
+    X(10, 1, 0, 1, 0, 1, 0, 1) X(10, 1, 0, 2, 0, 1, 0, 1) X(10, 1, 0, 1, 0, 1, 0, 0) X(10, 1, 0, 2, 0, 1, 0, 0)  /* LayerNorm, rstd kept */ \
+    X(10, 1, 0, 1, 1, 0, 0, 1) X(10, 1, 0, 1, 0, 0, 0, 1) X(10, 1, 0, 2, 0, 0, 0, 1)          /* LayerNorm, 304 columns */        \
+    X(10, 1, 0, 0, 0, 0, 0, 0) X(10, 1, 0, 1, 1, 0, 0, 0) X(10, 1, 0, 1, 0, 0, 0, 0) X(10, 1, 0, 2, 0, 0, 0, 0)  /* LayerNorm, 320 */ \
+    X(10, 0, 0, 1, 0, 0, 0, 0) X(10, 0, 1, 0, 0, 0, 0, 0) X(10, 0, 0, 0, 0, 0, 0, 0)          /* 320-column blocks */             \
+    X(8, 0, 0, 1, 0, 0, 0, 0) X(8, 0, 1, 0, 0, 0, 0, 0) X(8, 0, 0, 0, 0, 0, 0, 0)             /* 256-column blocks */             \
+    X(10, 0, 0, 1, 0, 0, 0, 1) X(10, 0, 1, 0, 0, 0, 0, 1) X(10, 0, 0, 0, 0, 0, 0, 1)          /* 304-column slabs */              \
+    X(8, 0, 0, 1, 0, 0, 0, 3) X(8, 0, 1, 0, 0, 0, 0, 3) X(8, 0, 0, 0, 0, 0, 0, 3)             /* 208-column slabs */
+
+int lime_pp_launch(const LimePpChoice& c, const lime_linear_args* a, hipStream_t s) {
+    PPParams p = lime_pp_params(a);
+    p.ln_rstd = a->ln_rstd;
+#define X(NTL, LN, RELU, RES, POOL, RSTD, CID, TRIM)                                                                                 \
+    if (c.ntl == NTL && c.ln == LN && c.relu == RELU && c.res == RES && c.pool == POOL && c.rstd == RSTD && c.cid == CID && c.trim == TRIM) \
+        return launch<NTL, LN, RELU, RES, false, POOL, RSTD, CID, TRIM>(p, s);
+    LIME_PP_BUILT(X)
+#undef X
+    LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "lime_linear_f32: %s is not built", lime_pp_name(c, false));
 }
 
 // ---- bf16 operands (BASELINE config 3: bf16 MFMA, fp32 accumulate / LayerNorm) ------------------------------------------

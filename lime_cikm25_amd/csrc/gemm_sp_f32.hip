@@ -497,7 +497,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
 #endif
 }
 
-template <int CT, bool LN, bool RELU, int RES, bool POOL = false, bool RSTD = false, bool CID = false>
+template <int CT, bool LN, bool RELU, int RES, bool POOL, bool RSTD, bool CID>
 int launch(const PPParams& p0, hipStream_t stream) {
     PPParams p = p0;
     p.n_row_blocks = (p.M + BM - 1) / BM;
@@ -509,8 +509,7 @@ int launch(const PPParams& p0, hipStream_t stream) {
     p.stamps = g_sp_stamp_buf;
 #endif
     hipLaunchKernelGGL((gemm_sp_kernel<CT, LN, RELU, RES, POOL, RSTD, CID>), dim3((unsigned)nwg), dim3(512), 0, stream, p);
-    lime_set_last_linear_kernel("gemm_sp_kernel<%d, %s, %s, %d, %s, %s, %s>", CT, LN ? "true" : "false", RELU ? "true" : "false", RES,
-                                POOL ? "true" : "false", RSTD ? "true" : "false", CID ? "true" : "false");    // as rocprofv3 prints it
+    lime_set_last_linear_kernel("%s", lime_sp_name({CT, RES, LN, RELU, POOL, RSTD, CID}));
     return lime_check_launch("lime_linear_f32");
 }
 
@@ -535,100 +534,87 @@ int lime_split_mode() {
     return g_split_mode;
 }
 
-// LIME_OK / error: launched (or failed); LIME_PP_NOT_APPLICABLE: the caller takes the fp32-MFMA kernels.
-int lime_linear_sp(const lime_linear_args* a, hipStream_t s) {
-    if (g_split_mode < 0) lime_set_split_gemm(-1);
-    if (!(g_split_mode & 1)) return LIME_PP_NOT_APPLICABLE;
-    const bool has_res = a->res != nullptr, ln = a->ln_gamma != nullptr;
-    const bool relu = a->act == LIME_ACT_RELU;
-    if (a->a_pe != nullptr) return LIME_PP_NOT_APPLICABLE;
+const char* lime_sp_name(const LimeSpChoice& c) {
+    static thread_local char buf[96];
+    snprintf(buf, sizeof(buf), "gemm_sp_kernel<%d, %s, %s, %d, %s, %s, %s>", c.ct, lime_tf(c.ln), lime_tf(c.relu), c.res, lime_tf(c.pool),
+             lime_tf(c.rstd), lime_tf(c.cid));         // as rocprofv3 prints it
+    return buf;
+}
+
+// false: the caller goes on to the fp32-MFMA kernels
+bool lime_sp_choose(const lime_linear_args* a, int mode, int n_cu, LimeSpChoice* c) {
+    if (!(mode & 1) || a->a_pe != nullptr) return false;
+    const bool has_res = a->res != nullptr, ln = a->ln_gamma != nullptr, relu = a->act == LIME_ACT_RELU;
     const bool act_rt = a->act == LIME_ACT_TANH || a->act == LIME_ACT_SIGMOID;       // applied at run time in the epilogue
     const bool relu_grad = a->act == LIME_ACT_RELU_GRAD;
-    if (a->dropout_p > 0.f && !(relu && !has_res && !ln && !a->pool32 && !a->c_ids)) return LIME_PP_NOT_APPLICABLE;
-    if (relu_grad && (!has_res || ln || a->res_ids || a->res_mod > 0 || a->res_div > 1 || a->c_ids || a->pool32)) return LIME_PP_NOT_APPLICABLE;
-    if (!(a->act == LIME_ACT_NONE || relu_grad || (relu && !has_res) || (act_rt && !ln && (!has_res || a->res_ids)))) return LIME_PP_NOT_APPLICABLE;
-    if (a->K % 4 || a->N % 4 || a->K < 64) return LIME_PP_NOT_APPLICABLE;          // >= 2 chunks (row lists, bias image)
-    if (!lime_al16(a->a, a->lda) || !lime_al16(a->w, a->ldw) || !lime_al16(a->c, a->ldc) || !lime_al16(a->res, a->ldr) || !lime_al16(a->res_pe, a->ldr_pe))
-        return LIME_PP_NOT_APPLICABLE;
-    if (a->bias && (uintptr_t)a->bias % 4) return LIME_PP_NOT_APPLICABLE;
-    const long row_blocks = ((long)a->M + BM - 1) / BM;
-    if (a->c_ids && !(has_res && !a->res_ids && a->res_mod > 0 && !ln && a->act == LIME_ACT_NONE)) return LIME_PP_NOT_APPLICABLE;
+    if (a->dropout_p > 0.f && !(relu && !has_res && !ln && !a->pool32 && !a->c_ids)) return false;
+    if (relu_grad && (!has_res || ln || a->res_ids || a->res_mod > 0 || a->res_div > 1 || a->c_ids || a->pool32)) return false;
+    if (!(a->act == LIME_ACT_NONE || relu_grad || (relu && !has_res) || (act_rt && !ln && (!has_res || a->res_ids)))) return false;
+    if (a->K < 64) return false;                       // >= 2 chunks (row lists, bias image)
+    if (!lime_pp_al16(a) || !lime_pp_offsets32(a, BM) || !lime_pp_cids_form(a) || !lime_pp_pool_form(a) || !lime_pp_ln_form(a)) return false;
     const long lim = 0x7FFFFFF0L;
-    if (a->c_ids && (long)a->M * a->ldc * 4 >= lim) return LIME_PP_NOT_APPLICABLE;
-    if (256L * a->lda * 4 >= lim || (long)a->N * a->ldw * 4 >= lim || 256L * a->ldc * 4 >= lim || 256L * a->ldr * 4 >= lim ||
-        (long)a->M * 4 >= lim)
-        return LIME_PP_NOT_APPLICABLE;
-    int res = 0;
-    if (relu_grad) {
-        if ((long)a->M * a->ldr * 4 >= lim) return LIME_PP_NOT_APPLICABLE;
-        res = 3;
-    } else if (has_res) {
-        if (a->res_ids) res = 2;
-        else res = 1;                                  // dense, periodic (res_mod) or broadcast (res_div > 1) rows
-        if (res == 1 && a->res_mod > 0 && (long)a->res_mod * a->ldr * 4 >= lim) return LIME_PP_NOT_APPLICABLE;
-        if (res == 1 && a->res_div > 1 && (a->res_mod > 0 || ln || ((long)a->M / a->res_div + 1) * a->ldr * 4 >= lim)) return LIME_PP_NOT_APPLICABLE;
-    }
+    const int res = lime_pp_res_class(a);              // 1: dense, periodic (res_mod) or broadcast (res_div > 1) rows
+    if (res == 3 && (long)a->M * a->ldr * 4 >= lim) return false;
+    if (res == 1 && a->res_div > 1 && (a->res_mod > 0 || ln || ((long)a->M / a->res_div + 1) * a->ldr * 4 >= lim)) return false;
     // The epilogues the layers AROUND the encoders need (tanh / sigmoid: Attention.affine1, gates; a gathered residual without
     // LayerNorm: LIME.project over the freshness table; a broadcast residual: SAGEConv lin_r) exist here for the LARGE batches
     // (BASELINE configs[2] and [4]: 14k .. 150k rows, where the 64 x 64-tile mid-M kernel runs at a fifth of this kernel's rate);
     // below ~12k rows one round of 256-row tiles is slower than the mid-M kernel's launch.
     const bool extended = act_rt || (res == 2 && !ln) || (res == 1 && a->res_div > 1);
-    if (extended && a->M < 12288 && !(g_split_mode & 4)) return LIME_PP_NOT_APPLICABLE;
-    if (ln && (a->N > 320 || relu)) return LIME_PP_NOT_APPLICABLE;
+    if (extended && a->M < 12288 && !(mode & 4)) return false;
     // out_proj (gathered residual + positional rows + LayerNorm): this kernel's instantiation adds the residual in its epilogue and
     // keeps 265 registers in scratch there; it measures 67-80 TFLOP/s against 100 of gemm_pp_f32.hip (with the residual loaded into
     // the accumulators at the tile start: 186 registers, 73 TFLOP/s) -- left to the fp32 kernel; lime_set_split_gemm(3) routes it here
-    if (res == 2 && ln && !(g_split_mode & 2)) return LIME_PP_NOT_APPLICABLE;      // only with lime_set_split_gemm(3)
-    if (a->pool32 && !(ln && has_res && !a->res_ids && a->res_div <= 1 && a->M % 32 == 0)) return LIME_PP_NOT_APPLICABLE;
+    if (res == 2 && ln && !(mode & 2)) return false;
     const bool wide = ln || lime_pp_wide(a->N, true);        // (this kernel takes the wide tile on a tie)
-    const long ntiles = row_blocks * ((a->N + (wide ? 319 : 255)) / (wide ? 320 : 256));
+    const int bn = wide ? 320 : 256;
+    const long col_blocks = (a->N + bn - 1) / bn, ntiles = (((long)a->M + BM - 1) / BM) * col_blocks;
     // From the same M on as gemm_pp_f32.hip takes over from the mid-M kernel ...
-    if (a->M < 4096) return LIME_PP_NOT_APPLICABLE;
+    if (a->M < 4096) return false;
     // ... and only where 256-row tiles on one workgroup per CU fill the chip: a launch is `rounds` passes of ncu tiles, and a tile
     // block that hangs over N computes dead columns.  Below ~0.45 of (tiles / (rounds x ncu)) x (N / covered columns) the 128-row /
     // 64-row tile kernels win: one round here takes 70 us at K = 400 however few tiles it has (tools/exp/sp_fill.py: M = 14k, N = 400 -- fill
     // 0.34 -- 70 us here, 53 there; M = 21k -- 0.50 -- 71 vs 85; tanh, N = 200: M = 28k -- 0.33 -- 70 vs 68, M = 42k -- 0.50 -- 75 vs 107).
     // A device-side row count (m_dev) hides the real M: those launches (the compacted encoder layers) always come here.  A caller
     // that cuts its rows into EQUAL passes (Model.score_impressions) gets one kernel family -- one rounding -- for every pass.
-    if (!a->m_dev && !(g_split_mode & 4)) {
-        const long ncu = lime_num_cus();
-        const long rounds = (ntiles + ncu - 1) / ncu;
-        const double fill = (double)ntiles / (double)(rounds * ncu) * (double)a->N / (double)(((a->N + (wide ? 319 : 255)) / (wide ? 320 : 256)) * (wide ? 320 : 256));
-        if (fill < 0.45) return LIME_PP_NOT_APPLICABLE;
+    if (!a->m_dev && !(mode & 4)) {
+        const long ncu = n_cu, rounds = (ntiles + ncu - 1) / ncu;
+        const double fill = (double)ntiles / (double)(rounds * ncu) * (double)a->N / (double)(col_blocks * bn);
+        if (fill < 0.45) return false;
     }
-
-    PPParams p = lime_pp_params(a);
-    p.ln_rstd = a->ln_rstd;
-    p.act = act_rt ? a->act : 0;
-    p.res_div = (res == 1 && a->res_div > 1) ? a->res_div : 1;
-    p.act_scale = a->act_scale;
-    if (a->dropout_p > 0.f) p.drop = lime_make_dropout(a->dropout_p, a->dropout_seed, a->dropout_site);
     {   // diagnostic: LIME_SP_MASK disables classes of instantiations (bit 0 c_ids, 1 LayerNorm + rstd, 2 LayerNorm, 3 residual,
         // 4 ReLU, 5 plain; bit 6: the 256-column tiles)
         static const int mask = getenv("LIME_SP_MASK") ? atoi(getenv("LIME_SP_MASK")) : 0;
         const int cls = a->c_ids ? 0 : (ln && a->ln_rstd) ? 1 : ln ? 2 : res ? 3 : relu ? 4 : 5;
-        if (mask & (1 << cls)) return LIME_PP_NOT_APPLICABLE;
-        if (!wide && (mask & 64)) return LIME_PP_NOT_APPLICABLE;
+        if ((mask & (1 << cls)) || (!wide && (mask & 64))) return false;
     }
-    if (a->c_ids) return wide ? launch<10, false, false, 1, false, false, true>(p, s) : launch<8, false, false, 1, false, false, true>(p, s);
-    if (ln) {
-        if (a->ln_rstd) {                              // training forward: residual + LayerNorm, rstd kept
-            if (res == 0 || a->pool32) return LIME_PP_NOT_APPLICABLE;
-            return res == 1 ? launch<10, true, false, 1, false, true>(p, s) : launch<10, true, false, 2, false, true>(p, s);
-        }
-        if (res == 0) return LIME_PP_NOT_APPLICABLE;
-        if (res == 1) return a->pool32 ? launch<10, true, false, 1, true>(p, s) : launch<10, true, false, 1>(p, s);
-        return launch<10, true, false, 2>(p, s);
-    }
-    if (res == 3) {                                    // (the 320-column instantiation puts 33 registers in scratch: not built; linear1 is 512 wide)
-        if (wide) return LIME_PP_NOT_APPLICABLE;
-        return launch<8, false, false, 3>(p, s);
-    }
-    if (res == 2) return wide ? launch<10, false, false, 2>(p, s) : launch<8, false, false, 2>(p, s);
-    if (wide) {
-        if (res == 1) return launch<10, false, false, 1>(p, s);
-        return relu ? launch<10, false, true, 0>(p, s) : launch<10, false, false, 0>(p, s);
-    }
-    if (res == 1) return launch<8, false, false, 1>(p, s);
-    return relu ? launch<8, false, true, 0>(p, s) : launch<8, false, false, 0>(p, s);
+    // not built, and left to the fp32 kernel: LayerNorm without a residual; the 320-column ReLU-gradient tile (33 registers in
+    // scratch; linear1 is 512 wide)
+    if ((ln && res == 0) || (res == 3 && wide)) return false;
+    *c = {wide ? 10 : 8, res, ln, relu, a->pool32 != 0, a->ln_rstd != nullptr, a->c_ids != nullptr};
+    return true;
+}
+
+// every instantiation this unit builds: CT, LN, RELU, RES, POOL, RSTD, CID
+#define LIME_SP_BUILT(X)                                                                                                     \
+    X(10, 0, 0, 1, 0, 0, 1) X(8, 0, 0, 1, 0, 0, 1)                                  /* compacted in_proj (c_ids) */          \
+    X(10, 1, 0, 1, 0, 1, 0) X(10, 1, 0, 2, 0, 1, 0)                                 /* training forward: LayerNorm, rstd kept */ \
+    X(10, 1, 0, 1, 1, 0, 0) X(10, 1, 0, 1, 0, 0, 0) X(10, 1, 0, 2, 0, 0, 0)         /* residual + LayerNorm (+ pool32) */     \
+    X(8, 0, 0, 3, 0, 0, 0)                                                          /* ReLU gradient */                      \
+    X(10, 0, 0, 2, 0, 0, 0) X(8, 0, 0, 2, 0, 0, 0)                                  /* gathered residual */                  \
+    X(10, 0, 0, 1, 0, 0, 0) X(10, 0, 1, 0, 0, 0, 0) X(10, 0, 0, 0, 0, 0, 0)         /* 320-column tiles */                   \
+    X(8, 0, 0, 1, 0, 0, 0) X(8, 0, 1, 0, 0, 0, 0) X(8, 0, 0, 0, 0, 0, 0)            /* 256-column tiles */
+
+int lime_sp_launch(const LimeSpChoice& c, const lime_linear_args* a, hipStream_t s) {
+    PPParams p = lime_pp_params(a);
+    p.ln_rstd = a->ln_rstd; p.act_scale = a->act_scale;
+    p.act = (a->act == LIME_ACT_TANH || a->act == LIME_ACT_SIGMOID) ? a->act : 0;
+    p.res_div = (c.res == 1 && a->res_div > 1) ? a->res_div : 1;
+    if (a->dropout_p > 0.f) p.drop = lime_make_dropout(a->dropout_p, a->dropout_seed, a->dropout_site);
+#define X(CT, LN, RELU, RES, POOL, RSTD, CID)                                                                                      \
+    if (c.ct == CT && c.ln == LN && c.relu == RELU && c.res == RES && c.pool == POOL && c.rstd == RSTD && c.cid == CID)            \
+        return launch<CT, LN, RELU, RES, POOL, RSTD, CID>(p, s);
+    LIME_SP_BUILT(X)
+#undef X
+    LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "lime_linear_f32: %s is not built", lime_sp_name(c));
 }

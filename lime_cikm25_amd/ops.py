@@ -174,6 +174,19 @@ def linear(a, w, bias=None, act=None, out=None, a_ids=None, a_pe=None, a_period=
     return out
 
 
+def linear_plan(*args, n_cu=None, **kw):
+    """What ``linear`` would run for the same arguments, without running it (``lime_linear_plan_f32``): a dict with ``family``
+    ('sp' split product, 'pp' fp32 LDS-DMA, 'mid', 'general'; None for M = 0), ``kernel`` (the instantiation as
+    ``lime_last_linear_kernel()`` names it after the launch), ``relu_bwd`` / ``dropout`` (a second pass over the output follows the
+    GEMM), ``mid_shape`` (0 / 1 / 2, -1 off the mid-M kernel) and ``tiles``.  n_cu: the CU count to plan for (None: this device's).
+    A call ``linear`` would refuse raises the same LimeHipError."""
+    built, _ = linear(*args, _build_only=True, **kw)
+    plan = _lib.LinearPlan()
+    check(_lib.load().lime_linear_plan_f32(ctypes.byref(built), n_cu or 0, ctypes.byref(plan)), 'lime_linear_plan_f32')
+    return dict(family=_lib.LINEAR_FAMILY[plan.family], kernel=plan.name.decode(), relu_bwd=bool(plan.second_pass & _lib.LINEAR_PASS_RELU_BWD),
+                dropout=bool(plan.second_pass & _lib.LINEAR_PASS_DROPOUT), mid_shape=plan.mid_shape, tiles=plan.tiles)
+
+
 _SLOW_LN_WARNED = False
 
 
@@ -193,8 +206,13 @@ def linear_group(problems):
         return [linear(**kw) for kw in problems]
     lib = _lib.load()
     built = [linear(_build_only=True, **kw) for kw in problems]
-    # only problems lime_linear_f32 itself hands to the mid-M kernel: M < 4096, or below 12288 rows with an epilogue the big-M kernels
-    # take from there on only (tanh / sigmoid, broadcast or gathered residual without LayerNorm)
+    # A hand-written subset of what lime_linear_f32 routes to the mid-M kernel (linear_route in csrc/gemm_f32.hip; DESIGN.md section 5,
+    # "Routing"): M < 4096, or below 12288 rows with an epilogue the split-product kernel takes from there on only (tanh / sigmoid,
+    # broadcast or gathered residual without LayerNorm).  The C rule is wider and depends on the split mode: from 4096 rows on it also
+    # hands the mid-M kernel every problem with fewer than 160 tiles of 128 x 256, and whatever neither big-M kernel takes; with the
+    # fill rules off (set_split_gemm(force=True)) the split-product kernel takes tanh / sigmoid from 4096 rows on, which this
+    # predicate still groups.  linear_plan() states the C rule exactly; switching to it changes which launches merge, so it waits
+    # for a measurement.
     mid = lambda a: a.M < 4096 or (a.M < 12288 and (a.act in (2, 3) or (a.res and (a.res_ids or a.res_div > 1))))
     if any(not mid(a) or a.ln_gamma or a.pool32 or a.c_ids or a.a_pe or a.res_pe or a.K % 4 or a.N % 4 or a.K < 16 for a, _ in built):
         return [linear(**kw) for kw in problems]

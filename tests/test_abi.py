@@ -60,7 +60,7 @@ def test_linear_args_layout_matches_header(tmp_path):
     assert (_lib.LinearArgs.c.offset, _lib.LinearArgs.act.offset, _lib.LinearArgs.ln_eps.offset) == LAYOUT[1:]
 
 
-@pytest.mark.parametrize('cname,cls', [('lime_linear_args', 'LinearArgs'), ('lime_linear_bf16_args', 'LinearBf16Args'),
+@pytest.mark.parametrize('cname,cls', [('lime_linear_args', 'LinearArgs'), ('lime_linear_plan', 'LinearPlan'), ('lime_linear_bf16_args', 'LinearBf16Args'),
                                         ('lime_ffn_bf16_args', 'FfnBf16Args'), ('lime_encoder_block_bf16_args', 'EncoderBlockBf16Args'),
                                         ('lime_inproj_bf16_args', 'InprojBf16Args')])
 def test_every_args_struct_matches_the_header_field_by_field(tmp_path, cname, cls):

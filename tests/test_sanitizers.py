@@ -33,6 +33,14 @@ def _driver_source():
                                ('lime_inproj_bf16_args', 'lime_inproj_bf16', ('M', 'N', 'K'))):
         lines += ['  { %s a; memset(&a, 0, sizeof a); CHECK(%s(&a, 0) < 0);' % (cname, entry)] + \
                  ['    a.%s = 4096;' % d for d in dims] + ['    CHECK(%s(&a, 0) < 0); CHECK(strlen(lime_last_error_string()) > 0); n += 2; }' % entry]
+    # the routing plan over addresses that are not memory: a read through any of them ends the driver
+    lines += ['  { lime_linear_args a; lime_linear_plan p; memset(&a, 0, sizeof a);',
+              '    a.a = (const float*)0x10000; a.w = (const float*)0x40000; a.bias = (const float*)0x50000; a.c = (float*)0x90000;',
+              '    a.res = (const float*)0x60000; a.res_ids = (const int32_t*)0x70000; a.m_dev = (const int32_t*)0xD0000;',
+              '    a.M = 12288; a.N = 1280; a.K = 64; a.lda = a.ldw = 64; a.ldc = a.ldr = 1280;',
+              '    CHECK(lime_linear_plan_f32(&a, 256, &p) == 0); CHECK(p.family == LIME_LINEAR_SP && strlen(p.name) > 0);',
+              '    a.M = 1700; CHECK(lime_linear_plan_f32(&a, 256, &p) == 0); CHECK(p.family == LIME_LINEAR_MID && p.tiles > 0);',
+              '    a.K = 62; a.lda = a.ldw = 62; CHECK(lime_linear_plan_f32(&a, 256, &p) == LIME_ERR_UNSUPPORTED); n += 3; }']
     lines += ['  CHECK(lime_token_attention_bwd_workspace(1760, 512, 10) > lime_token_attention_stats_workspace(1760, 512, 10));',
               '  CHECK(lime_token_attention_bwd_workspace(1 << 20, 512, 16) > 0);      /* 64-bit arithmetic: no signed overflow */',
               '  CHECK(lime_token_attention_bwd_workspace(0, 32, 1) == 0);',
