@@ -342,7 +342,8 @@ int lime_embed_pe_f32(const int32_t* ids, const float* table, int64_t ld_table, 
  * ld_qkv (the three may alias one packed buffer).  head_stride == head_dim is the packed layout of the reference;
  * head_stride = 32 (heads padded with zero columns, see lime_pad_heads_f32) lets the kernel use aligned 16-byte loads.
  * key_mask: uint8 [n_seq, S], 0 = masked, or NULL.  out[(seq * S + t) * ldo + head * head_dim + d] (always packed).
- * Requires S <= 512, head_dim <= 32, head_stride >= head_dim.
+ * Requires S <= 512, head_stride >= head_dim, and head_dim <= 32 -- or 32 < head_dim <= 128 under the wide-head limits stated at
+ * lime_token_attention_bwd_workspace_wide.
  */
 int lime_token_attention_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask,
                              float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
@@ -681,7 +682,7 @@ int lime_relu_bwd_f32(float* dh, int64_t lddh, const float* h, int64_t ldh, int6
 /* Backward of lime_token_attention_f32 (the encoder layers; optionally the key mask of MHSA): given q / k / v as the forward read them
  * and dout [tokens, n_head * head_dim] (packed), writes dq / dk / dv in the layout of q / k / v (row stride ld_dqkv, head
  * h at column h * head_stride; columns head_dim .. head_stride - 1 come out as zeros).  The probabilities are recomputed.
- * S <= 512, head_dim <= head_stride <= 32.  S <= 128: one pass per (sequence, head); `out` and `workspace` may be NULL.
+ * S <= 512, head_dim <= head_stride <= 32 (wider heads: see lime_token_attention_bwd_workspace_wide below).  S <= 128: one pass per (sequence, head); `out` and `workspace` may be NULL.
  * 128 < S <= 512 (the 512-token bodies of BASELINE config 4): 128 x 128 blocks; needs the forward output `out` (packed like
  * dout) and lime_token_attention_bwd_workspace(n_seq, S, n_head) floats: the row statistics and one dq slab per key block behind the
  * first -- the key blocks' shares of dq are stored (no atomics) and summed in block order, so the result is bitwise reproducible.  dropout_p > 0: the forward was lime_token_attention_dropout_f32 with the same (dropout_p, seed, site).
@@ -690,6 +691,14 @@ int lime_relu_bwd_f32(float* dh, int64_t lddh, const float* h, int64_t ldh, int6
 int64_t lime_token_attention_bwd_workspace(int32_t n_seq, int32_t S, int32_t n_head);
 /* the row-statistics part of it (lse and delta per (token, head)): what lime_token_attention_dropout_f32 needs for S > 128 */
 int64_t lime_token_attention_stats_workspace(int32_t n_seq, int32_t S, int32_t n_head);
+/* Wide heads (32 < head_dim <= 128, head_dim % 4 == 0, head_stride % 4 == 0, S <= 512, 16-byte aligned operands, leading dimensions
+ * multiples of 4; csrc/token_attn_wide_f32.hip): lime_token_attention_f32 / _count_f32 / _lse_f32 / _dropout_f32 and
+ * lime_token_attention_bwd_f32 / _bwd_lse_f32 send them to exact-fp32 MFMA kernels that stream the keys in blocks of 64 (key mask, device
+ * count, lse output and dropout as for the narrow heads; lime_set_split_gemm has no effect on them).  Their backward recomputes the row
+ * statistics at every S (`out` and `lse` are accepted and not read), sums in a fixed order (bitwise reproducible) and needs
+ * lime_token_attention_bwd_workspace_wide(n_seq, S, n_head, head_dim) floats of workspace -- for head_dim <= 32 that is
+ * lime_token_attention_bwd_workspace(n_seq, S, n_head).  The forward with dropout needs no workspace for wide heads. */
+int64_t lime_token_attention_bwd_workspace_wide(int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim);
 int lime_token_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out, int64_t ld_out,
                                  const float* dout, int64_t ldo, float* dq, float* dk, float* dv, int64_t ld_dqkv, int32_t n_seq,
                                  int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale, float* workspace,

@@ -274,6 +274,7 @@ SIGNATURES = {
     'lime_relu_bwd_f32': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_float, c_void_p]),
     'lime_token_attention_bwd_workspace': (c_int64, [c_int32, c_int32, c_int32]),
     'lime_token_attention_stats_workspace': (c_int64, [c_int32, c_int32, c_int32]),
+    'lime_token_attention_bwd_workspace_wide': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     'lime_token_attention_bwd_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                                c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float,
                                                c_void_p, c_int64, c_float, c_uint64, c_uint32, c_void_p, c_void_p]),

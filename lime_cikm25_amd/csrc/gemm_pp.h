@@ -118,6 +118,16 @@ int lime_split_mode();                                                   // gemm
 int lime_token_attention_sp(const float* q, const float* k, const float* v, long ld, const int* row_map, const int* n_seq_dev,
                             float* out, long ldo, int n_seq, int S, int n_head, int hd, float scale, float* lse, hipStream_t s,
                             const LimeDropout* drop = nullptr);
+// token_attn_wide_f32.hip: 32 < head_dim <= 128 (head_dim % 4 == 0, 16-byte aligned operands), forward and backward on the fp32 MFMA; they
+// check their own limits and name `entry` in their messages.  The backward recomputes the row statistics (workspace:
+// lime_token_attention_bwd_workspace_wide floats).
+int lime_token_attention_wide(const char* entry, const float* q, const float* k, const float* v, long ld, const unsigned char* key_mask,
+                              const int* n_seq_dev, float* out, long ldo, float* lse, int n_seq, int S, int n_head, int hd, int hs,
+                              float scale, const LimeDropout* drop, hipStream_t s);
+int lime_token_attention_wide_bwd(const char* entry, const float* q, const float* k, const float* v, long ld, const float* dout, long ldo,
+                                  float* dq, float* dk, float* dv, long ldd, int n_seq, int S, int n_head, int hd, int hs, float scale,
+                                  float* workspace, long workspace_floats, const LimeDropout& drop, const unsigned char* key_mask,
+                                  hipStream_t s);
 // token_attn_bwd_sp_f32.hip: the one-pass attention backward (64 < S <= 128, no key mask) with all its products on the split product
 int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, long ld, const float* dout, long ldo, float* dq, float* dk,
                                 float* dv, long ldd, int n_seq, int S, int n_head, int head_dim, int head_stride, float scale,

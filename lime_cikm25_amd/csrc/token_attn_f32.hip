@@ -543,7 +543,9 @@ extern "C" int lime_token_attention_count_f32(const float* q, const float* k, co
     LIME_REQUIRE(q && k && v && out, LIME_ERR_BAD_ARG, "lime_token_attention_count_f32: NULL pointer");
     LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG,
                  "lime_token_attention_count_f32: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", n_seq, S, n_head, head_dim);
-    LIME_REQUIRE(head_dim <= 32, LIME_ERR_UNSUPPORTED, "lime_token_attention_count_f32: head_dim %d > 32", head_dim);
+    if (head_dim > 32)                                // wide heads: token_attn_wide_f32.hip (checks its own limits)
+        return lime_token_attention_wide("lime_token_attention_count_f32", q, k, v, (long)ld_qkv, key_mask, n_seq_dev, out, (long)ldo, nullptr,
+                                         n_seq, S, n_head, head_dim, head_stride, scale, nullptr, (hipStream_t)stream);
     LIME_REQUIRE(head_stride >= head_dim, LIME_ERR_BAD_ARG, "lime_token_attention_count_f32: head_stride %d < head_dim %d", head_stride, head_dim);
     LIME_REQUIRE(S <= 512, LIME_ERR_UNSUPPORTED, "lime_token_attention_count_f32: S %d > 512", S);
     LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
@@ -567,8 +569,11 @@ extern "C" int lime_token_attention_lse_f32(const float* q, const float* k, cons
     LIME_REQUIRE(q && k && v && out && lse, LIME_ERR_BAD_ARG, "lime_token_attention_lse_f32: NULL pointer");
     LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG,
                  "lime_token_attention_lse_f32: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", n_seq, S, n_head, head_dim);
-    LIME_REQUIRE(head_dim <= 32 && head_stride >= head_dim && S <= 512, LIME_ERR_UNSUPPORTED,
-                 "lime_token_attention_lse_f32: needs head_dim <= 32, head_stride >= head_dim, S <= 512");
+    if (head_dim > 32)
+        return lime_token_attention_wide("lime_token_attention_lse_f32", q, k, v, (long)ld_qkv, nullptr, nullptr, out, (long)ldo, lse, n_seq, S,
+                                         n_head, head_dim, head_stride, scale, nullptr, (hipStream_t)stream);
+    LIME_REQUIRE(head_stride >= head_dim && S <= 512, LIME_ERR_UNSUPPORTED,
+                 "lime_token_attention_lse_f32: needs head_stride >= head_dim, S <= 512");
     LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
                  "lime_token_attention_lse_f32: leading dimension smaller than n_head * head_dim");
     if (n_seq == 0) return LIME_OK;

@@ -1030,7 +1030,10 @@ static int attention_bwd(const float* q, const float* k, const float* v, int64_t
     LIME_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: dropout_p outside [0, 1)");
     const LimeDropout drop = lime_make_dropout(dropout_p, seed, site);
     LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: bad dimensions");
-    LIME_REQUIRE(S <= 512 && head_dim <= 32 && head_stride >= head_dim && head_stride <= 32, LIME_ERR_UNSUPPORTED,
+    if (head_dim > 32)                                         // wide heads: token_attn_wide_f32.hip recomputes the statistics (out / lse unused)
+        return lime_token_attention_wide_bwd("lime_token_attention_bwd_f32", q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head,
+                                             head_dim, head_stride, scale, workspace, workspace_floats, drop, key_mask, (hipStream_t)stream);
+    LIME_REQUIRE(S <= 512 && head_stride >= head_dim && head_stride <= 32, LIME_ERR_UNSUPPORTED,
                  "lime_token_attention_bwd_f32: needs S <= 512 and head_dim <= head_stride <= 32 (S=%d head_dim=%d head_stride=%d)",
                  S, head_dim, head_stride);
     LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ld_dqkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim,
@@ -1107,7 +1110,13 @@ extern "C" int lime_token_attention_dropout_f32(const float* q, const float* k, 
                                                 int64_t workspace_floats, void* stream) {
     LIME_REQUIRE(q && k && v && out, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: null pointer");
     LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: bad dimensions");
-    LIME_REQUIRE(S <= 512 && head_dim <= 32 && head_stride >= head_dim && head_stride <= 32, LIME_ERR_UNSUPPORTED,
+    if (head_dim > 32) {                                       // wide heads: token_attn_wide_f32.hip (one pass at every S, no workspace)
+        LIME_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: dropout_p outside [0, 1)");
+        const LimeDropout wide_drop = lime_make_dropout(dropout_p, seed, site);
+        return lime_token_attention_wide("lime_token_attention_dropout_f32", q, k, v, (long)ld_qkv, nullptr, nullptr, out, (long)ldo, nullptr,
+                                         n_seq, S, n_head, head_dim, head_stride, scale, &wide_drop, (hipStream_t)stream);
+    }
+    LIME_REQUIRE(S <= 512 && head_stride >= head_dim && head_stride <= 32, LIME_ERR_UNSUPPORTED,
                  "lime_token_attention_dropout_f32: needs S <= 512 and head_dim <= head_stride <= 32");
     LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
                  "lime_token_attention_dropout_f32: leading dimension smaller than the row");

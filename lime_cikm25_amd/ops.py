@@ -245,7 +245,9 @@ def embed_pe(ids, table, pe=None, period=0, out=None):
 def token_attention(q, k, v, n_seq, S, n_head, head_dim, scale, key_mask=None, out=None, head_stride=None, n_seq_dev=None, lse=None):
     """softmax(Q K^T * scale [+mask]) V per (sequence, head); q/k/v: [n_seq*S, n_head*head_stride] views of one pitch
     (head_stride defaults to head_dim, the packed layout); out: [n_seq*S, n_head*head_dim].  ``lse`` (float32 [n_seq*S * n_head], no
-    mask): also filled with the softmax statistics ``token_attention_bwd(..., lse=lse)`` reads instead of recomputing them."""
+    mask): also filled with the softmax statistics ``token_attention_bwd(..., lse=lse)`` reads instead of recomputing them.
+    S <= 512 and either head_dim <= 32 (any head_dim, any head_stride >= head_dim) or the wide heads 32 < head_dim <= 128 with
+    head_dim % 4 == 0, head_stride % 4 == 0, leading dimensions that are multiples of 4 and 16-byte aligned tensors."""
     lib = _lib.load()
     hs = head_dim if head_stride is None else head_stride
     for t, n in ((q, 'q'), (k, 'k'), (v, 'v')):
@@ -1399,7 +1401,8 @@ def token_attention_bwd(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_s
                         dropout=None, key_mask=None, lse=None):
     """Backward of the unmasked ``token_attention``: q / k / v column views of one packed qkv buffer [tokens, 3 * n_head *
     head_stride]; returns dqkv in the same layout.  ``out``: the forward's result (needed for S > 128).  ``dropout``:
-    (p, seed, site) of the ``token_attention_dropout`` forward."""
+    (p, seed, site) of the ``token_attention_dropout`` forward.  head_dim ranges as ``token_attention``; the wide heads
+    (32 < head_dim <= 128) recompute their statistics at every S: ``out`` and ``lse`` are optional and unused there."""
     lib = _lib.load()
     hs = head_dim if head_stride is None else head_stride
     W = n_head * hs
@@ -1416,15 +1419,20 @@ def token_attention_bwd(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_s
         dqkv = torch.empty((n_seq * S, 3 * W), dtype=torch.float32, device=q.device)
     _mat(dqkv, 'dqkv')
     dq, dk, dv = dqkv[:, :W], dqkv[:, W:2 * W], dqkv[:, 2 * W:]
-    ws, need = None, lib.lime_token_attention_bwd_workspace(n_seq, S, n_head)
-    if need:
+    wide = head_dim > 32
+    ws, need = None, lib.lime_token_attention_bwd_workspace_wide(n_seq, S, n_head, head_dim)
+    if wide:
+        ws = _workspace(q.device, need) if need else None
+        if out is not None:
+            _mat(out, 'out')
+    elif need:
         if out is None:
             raise ValueError('S > 128 needs the forward output `out`')
         _mat(out, 'out')
         if tuple(out.shape) != tuple(dout.shape):
             raise ValueError('out must have the shape of dout')
         ws = _workspace(q.device, need)
-    if lse is not None and need:                   # S > 128 with the forward's statistics: no Q K^T pass for them
+    if lse is not None and need and (not wide or (S > 128 and out is not None)):   # S > 128 with the forward's statistics
         if dropout or key_mask is not None:
             raise ValueError('lse goes with the plain (no dropout, no key mask) forward')
         _vec(lse, 'lse', n_seq * S * n_head)
@@ -1496,7 +1504,8 @@ def dropout_add_layernorm(t, res, gamma, beta, eps, p, seed, site, want_rstd=Tru
 
 
 def token_attention_dropout(q, k, v, n_seq, S, n_head, head_dim, scale, p, seed, site, head_stride=None):
-    """Unmasked encoder attention with dropout on the probabilities (training mode); layouts as ``token_attention``."""
+    """Unmasked encoder attention with dropout on the probabilities (training mode); layouts and head_dim ranges (<= 32, or the
+    wide heads up to 128) as ``token_attention``."""
     lib = _lib.load()
     hs = head_dim if head_stride is None else head_stride
     for t, name in ((q, 'q'), (k, 'k'), (v, 'v')):
@@ -1506,7 +1515,7 @@ def token_attention_dropout(q, k, v, n_seq, S, n_head, head_dim, scale, p, seed,
     if not (_ld(q) == _ld(k) == _ld(v)):
         raise ValueError('q, k, v must share one leading dimension')
     out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=q.device)
-    need = lib.lime_token_attention_stats_workspace(n_seq, S, n_head)
+    need = 0 if head_dim > 32 else lib.lime_token_attention_stats_workspace(n_seq, S, n_head)      # the wide heads run in one pass
     ws = _workspace(q.device, need) if need else None
     check(lib.lime_token_attention_dropout_f32(_p(q), _p(k), _p(v), _ld(q), _p(out), _ld(out), n_seq, S, n_head, head_dim, hs, scale,
                                                p, seed, site, _p(ws), ws.numel() if ws is not None else 0, _stream()),

@@ -285,8 +285,9 @@ def _layer_forward(ctx, x, gather, M, S, nhead, eps1, eps2, p, seed, in_w, in_b,
     E = in_w.shape[1]
     hd = E // nhead
     hs = 32 if hd <= 32 else hd
-    if hs > 32 or S > 512:
-        raise NotImplementedError('the attention kernels cover head_dim <= 32 and S <= 512 (got %d, %d)' % (hd, S))
+    if hd > 128 or (hd > 32 and hd % 4) or S > 512:
+        raise NotImplementedError('the attention kernels cover head_dim <= 32, or 32 < head_dim <= 128 with head_dim %% 4 == 0, '
+                                  'and S <= 512 (got %d, %d)' % (hd, S))
     W = nhead * hs
     tok = M * S
     dev = in_w.device
