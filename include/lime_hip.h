@@ -752,7 +752,8 @@ int lime_dropout_add_layernorm_f32(const float* t, int64_t ldt, const float* res
 /* Encoder attention with dropout on the probabilities (nn.MultiheadAttention(dropout=p) in training mode):
  * out = (keep * softmax(scale q k^T) / (1 - p)) v; layouts as lime_token_attention_f32 without a key mask; mask element
  * ((seq * n_head + head) * S + i) * S + j.  S <= 512; S > 128 runs in 128 x 128 blocks and needs
- * lime_token_attention_bwd_workspace(n_seq, S, n_head) floats of workspace (row statistics), else workspace may be NULL. */
+ * lime_token_attention_stats_workspace(n_seq, S, n_head) floats of workspace (the row statistics; the larger
+ * lime_token_attention_bwd_workspace does as well), else workspace may be NULL. */
 int lime_token_attention_dropout_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
                                      int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale,
                                      float dropout_p, uint64_t seed, uint32_t site, float* workspace, int64_t workspace_floats,

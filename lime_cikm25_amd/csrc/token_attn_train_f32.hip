@@ -1132,7 +1132,7 @@ extern "C" int lime_token_attention_dropout_f32(const float* q, const float* k, 
     if (S <= 64) return launch_attn_fwd_dropout<64>(q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale, drop, s);
     if (S <= 128) return launch_attn_fwd_dropout<128>(q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale, drop, s);
     LIME_REQUIRE(workspace && workspace_floats >= lime_token_attention_stats_workspace(n_seq, S, n_head), LIME_ERR_BAD_ARG,
-                 "lime_token_attention_dropout_f32: S > 128 needs lime_token_attention_bwd_workspace() floats of workspace");
+                 "lime_token_attention_dropout_f32: S > 128 needs lime_token_attention_stats_workspace() floats of workspace");
     const int n_blk = (S + LB - 1) / LB;
     const long n_prob = (long)n_seq * n_head;
     LIME_REQUIRE(n_prob * n_blk < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_token_attention_dropout_f32: too many blocks");
