@@ -107,11 +107,7 @@ __global__ __launch_bounds__(256, 1) void attn_pool_sp_kernel(const AttnPoolP p)
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int n_live = p.n_seq;
-    if (p.n_seq_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.n_seq_dev);
-        n_live = m < n_live ? (m > 0 ? m : 0) : n_live;
-    }
+    const int n_live = live_count(p.n_seq_dev, p.n_seq);
     const int T = p.T, spt = p.spt, D = p.D;
     const int ntiles = (n_live + spt - 1) / spt;
     int tile = blockIdx.x;
@@ -355,8 +351,7 @@ extern "C" int lime_attn_pool_sp_f32(const float* x, int64_t ldx, int32_t D, con
     p.D = D; p.A = A; p.n_seq = n_seq; p.T = T; p.spt = BM / T; p.steps = steps_of(D); p.passes = passes_of(A);
     p.n_seq_dev = n_seq_dev;
     const long ntiles = ((long)n_seq + p.spt - 1) / p.spt;
-    long nwg = lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles);
     hipStream_t s = (hipStream_t)stream;
     if (lime_split_mode() & 1) hipLaunchKernelGGL((attn_pool_sp_kernel<true>), dim3((unsigned)nwg), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((attn_pool_sp_kernel<false>), dim3((unsigned)nwg), dim3(256), 0, s, p);

@@ -48,6 +48,12 @@ static inline int lime_reserve_lds(const void* kernel, int bytes, int& reserved,
     return LIME_OK;
 }
 
+// workgroups of a persistent kernel that walks `ntiles` tiles: `per_cu` per compute unit, one per tile at the most
+static inline long lime_persistent_grid(long ntiles, int per_cu = 1) {
+    const long nwg = (long)lime_num_cus() * per_cu;
+    return nwg < ntiles ? nwg : ntiles;
+}
+
 // workgroups of a grid-stride kernel: one per `per` of the `total` items, `cap` at the most
 static inline unsigned lime_grid_cap(long total, int per, int cap) {
     const long g = (total + per - 1) / per;

@@ -7,8 +7,9 @@
 //   pooled[s, o] = max(0, max_{t < P} pre[s, t, o]),   arg[s, o] = the smallest t that attains it, -1 where pooled is 0
 //   X_src(q) = table_src[ids_src[q]] or a_src[q] (ids NULL), zeros where the position t + j - pad is outside [0, T)
 //
-// The GEMM is conv_sp_f32.hip's (conv_frag.h: 32-deep chunks of one tap of one source, fp32 LDS images, split product or fp32 MFMA
-// under lime_set_split_gemm(0); 256 threads, 128 x 128 tile, two stages, one barrier per chunk).  A tile holds floor(128 / T) WHOLE
+// The GEMM is conv_sp_f32.hip's, the one conv_tile_product of conv_frag.h (32-deep chunks of one tap of one source, fp32 LDS images,
+// split product or fp32 MFMA under lime_set_split_gemm(0); 256 threads, 128 x 128 tile, two stages, one barrier per chunk), given the
+// three-way source select as its tap and the end of the tile's live rows.  A tile holds floor(128 / T) WHOLE
 // sequences (T <= 128), so the maximum over a sequence never crosses workgroups: no atomics, and the pre-activations go from the
 // accumulators to the LDS the operand stages have left (132-float rows) and from there to one thread per (sequence, column), which
 // walks t = 0 .. P - 1 in order.  They never reach memory.  The chunk order of an output element is fixed, so its bits do not depend
@@ -25,11 +26,9 @@ int lime_split_mode();
 
 namespace {
 
-constexpr int BM = 128, BN = 128;
-constexpr int A_FL = BM * CONV_PITCH, W_FL = BN * CONV_PITCH, STAGE = A_FL + W_FL;
+constexpr int BM = CONV_BM, BN = CONV_BN;
 constexpr int EP_PITCH = BN + 4;        // the epilogue's [BM][BN] pre-activation image
-static_assert(2 * STAGE * 4 <= 81920, "two workgroups per CU");
-static_assert(BM * EP_PITCH <= 2 * STAGE, "the epilogue image fits the operand stages");
+static_assert(BM * EP_PITCH <= 2 * CONV_STAGE, "the epilogue image fits the operand stages");
 
 struct PoolParams {
     const float* a0; const float* a1; const float* a2;
@@ -48,12 +47,8 @@ struct PoolParams {
 
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void conv_pool_sp_kernel(const PoolParams p) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * STAGE];
-    int n_seq = p.n_seq;
-    if (p.n_seq_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.n_seq_dev);
-        n_seq = m < n_seq ? (m > 0 ? m : 0) : n_seq;
-    }
+    __shared__ __attribute__((aligned(16))) float lds[2 * CONV_STAGE];
+    const int n_seq = live_count(p.n_seq_dev, p.n_seq);
     const int rb = blockIdx.x / p.n_col_blocks, cb = blockIdx.x - rb * p.n_col_blocks;
     const int seq0 = rb * p.seq_per_tile, col0 = cb * BN;
     if (seq0 >= n_seq) return;
@@ -63,75 +58,14 @@ __global__ __launch_bounds__(256, 2) void conv_pool_sp_kernel(const PoolParams p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave & 1, wc = wave >> 1;
     const int fi = lane & 15, kg = lane >> 4;
-    const int seg = tid & 7, lrow = tid >> 3;          // loader: rows lrow + 32 u of the tile, floats 4 seg .. + 3 of the chunk
-    const int nq = (p.C + CONV_KC - 1) / CONV_KC, nk = p.n_src * p.win * nq;
-
-    long aoff[4];
-    const float* asrc = p.a0;
-    f32x4 ra[4], rw[4];
-    auto gload = [&](int k) {
-        const int sj = k / nq, q = k - sj * nq;        // sj = src win + j: the weight's tap block
-        if (q == 0) {                                  // a new (source, tap): the four source rows of this thread
-            const int src = sj / p.win, j = sj - src * p.win;
-            asrc = src == 0 ? p.a0 : src == 1 ? p.a1 : p.a2;
-            const long lda = src == 0 ? p.lda0 : src == 1 ? p.lda1 : p.lda2;
-            const int* const ids = src == 0 ? p.ids0 : src == 1 ? p.ids1 : p.ids2;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int r = lrow + 32 * u;
-                aoff[u] = r < rows ? window_row(ids, lda, row0 + r, j, p.pad, p.T) : -1;
-            }
-        }
-        const int c = q * CONV_KC + 4 * seg;
-        const bool cin = c < p.C;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ra[u] = (cin && aoff[u] >= 0) ? ld4(asrc + aoff[u] + c) : z;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int n = col0 + lrow + 32 * u;
-            rw[u] = (cin && n < p.N) ? ld4(p.w + (long)n * p.ldw + (long)sj * p.C + c) : z;
-        }
-    };
-    auto sstore = [&](int st) {
-        float* const s = lds + st * STAGE;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            *reinterpret_cast<f32x4*>(s + (lrow + 32 * u) * CONV_PITCH + 4 * seg) = ra[u];
-            *reinterpret_cast<f32x4*>(s + A_FL + (lrow + 32 * u) * CONV_PITCH + 4 * seg) = rw[u];
-        }
-    };
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](int st) {
-        const float* const sa = lds + st * STAGE + (64 * wr + fi) * CONV_PITCH + 8 * kg;
-        const float* const sw = lds + st * STAGE + A_FL + (64 * wc + fi) * CONV_PITCH + 8 * kg;
-        Frag<SPLIT> x[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[i].load_frag(sa + i * 16 * CONV_PITCH);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            Frag<SPLIT> w;
-            w.load_frag(sw + t * 16 * CONV_PITCH);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][t] = frag_prod(w, x[i], acc[i][t]);
-        }
+    auto tap = [&p](int sj) {                          // sj = src win + j: the weight's tap block
+        const int src = sj / p.win;
+        return ConvTap{src == 0 ? p.a0 : src == 1 ? p.a1 : p.a2, src == 0 ? p.lda0 : src == 1 ? p.lda1 : p.lda2,
+                       src == 0 ? p.ids0 : src == 1 ? p.ids1 : p.ids2, sj - src * p.win};
     };
-
-    gload(0);
-    sstore(0);
-    lds_barrier();
-    for (int k = 0; k < nk; ++k) {
-        const bool more = k + 1 < nk;
-        if (more) gload(k + 1);                        // in flight under this chunk's products
-        compute(k & 1);
-        if (more) sstore((k + 1) & 1);                 // the other stage: its last reader finished before the previous barrier
-        lds_barrier();
-    }
+    conv_tile_product<SPLIT>(lds, acc, tap, p.n_src * p.win, p.w, p.ldw, p.C, p.N, p.T, p.pad, row0, row0 + rows, col0);
 
     // epilogue 1: the pre-activations of the tile into LDS (every reader of the stages is past the loop's last barrier); lane (fi, kg)
     // holds row 64 wr + 16 i + fi, columns 64 wc + 16 t + 4 kg + e in acc[i][t][e]
@@ -164,10 +98,7 @@ __global__ __launch_bounds__(256, 2) void conv_pool_sp_kernel(const PoolParams p
 __global__ __launch_bounds__(256) void relu_maxpool_kernel(const float* __restrict__ pre, long ldpre, const float* __restrict__ bias,
                                                            float* __restrict__ pooled, long ldp, int* __restrict__ arg, long ldarg,
                                                            int n_seq, int T, int P, int N, const int* __restrict__ n_seq_dev) {
-    if (n_seq_dev) {
-        const int m = *n_seq_dev;
-        n_seq = m < n_seq ? (m > 0 ? m : 0) : n_seq;
-    }
+    n_seq = live_count(n_seq_dev, n_seq);
     const int n4 = N >> 2;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)n_seq * n4) return;

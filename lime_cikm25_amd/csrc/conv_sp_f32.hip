@@ -12,10 +12,12 @@
 // 16-byte segment past column C are masked to zeros (W needs no repacking beyond [O, window, C]), so a chunk never straddles taps.
 // C % 4 == 0 (a segment is valid or not as a whole).
 //
-// Structure: 256-thread workgroups (four waves), tile 128 rows x 128 columns, wave w owns rows 64 (w & 1) .. + 63 and columns
-// 64 (w >> 1) .. + 63 (4 x 4 accumulator tiles of 16 x 16, the transposed product D^T = W A^T so that a lane holds four
-// consecutive output columns of one row).  Chunks go global -> registers -> LDS (fp32, 144-byte rows), two stages, one barrier per
-// chunk: chunk k + 1's loads are in flight while chunk k is split and multiplied.  74 KB of LDS: two workgroups per CU.
+// Structure: the tile product is conv_frag.h's conv_tile_product (shared with conv_pool_sp_f32.hip): 256-thread workgroups (four
+// waves), tile 128 rows x 128 columns, wave w owns rows 64 (w & 1) .. + 63 and columns 64 (w >> 1) .. + 63 (4 x 4 accumulator tiles
+// of 16 x 16, the transposed product D^T = W A^T so that a lane holds four consecutive output columns of one row).  Chunks go
+// global -> registers -> LDS (fp32, 144-byte rows), two stages, one barrier per chunk (conv_frag.h's two_stage_loop): chunk k + 1's
+// loads are in flight while chunk k is split and multiplied.  74 KB of LDS: two workgroups per CU.  This file passes its single
+// source as the tap and M as the row end, and keeps the epilogue.
 // The epilogue honours a device-side row count (m_dev: rows >= min(*m_dev, M) are neither computed nor stored) and an output
 // leading dimension (the group3 convolutions write their column slices of one output).
 //
@@ -24,8 +26,9 @@
 //
 // The weight gradient dW[o, j C + c] = sum_r dY[r, o] A(r, j)[c] (conv_wgrad_sp_kernel) reads the same windowed operand: tiles of
 // 64 o x 128 c of one tap over one slice of the rows, both operands stored into LDS transposed ([column][row]) so that a fragment
-// (eight consecutive rows of one column) is one 32-byte read; the slices' partial tiles go to a workspace and are summed in slice
-// order by conv_wgrad_reduce_kernel -- no atomics, the same bits on every run.
+// (eight consecutive rows of one column) is one 32-byte read, its own load / store / product bodies in the same two_stage_loop; the
+// slices' partial tiles go to a workspace and are summed in slice order by conv_wgrad_reduce_kernel -- no atomics, the same bits on
+// every run.
 #include "conv_frag.h"
 
 using namespace lime_dev;
@@ -47,18 +50,12 @@ struct ConvParams {
     int M, N, C, T, win, pad, relu, accumulate, vec_out, n_col_blocks;
 };
 
-constexpr int BM = 128, BN = 128;
-constexpr int A_FL = BM * CONV_PITCH, W_FL = BN * CONV_PITCH, STAGE = A_FL + W_FL;
-static_assert(2 * STAGE * 4 <= 81920, "two workgroups per CU");
+constexpr int BM = CONV_BM, BN = CONV_BN;
 
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * STAGE];
-    int M = p.M;
-    if (p.m_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        M = m < M ? (m > 0 ? m : 0) : M;
-    }
+    __shared__ __attribute__((aligned(16))) float lds[2 * CONV_STAGE];
+    const int M = live_count(p.m_dev, p.M);
     const int rb = blockIdx.x / p.n_col_blocks, cb = blockIdx.x - rb * p.n_col_blocks;
     const int row0 = rb * BM, col0 = cb * BN;
     if (row0 >= M) return;
@@ -66,70 +63,10 @@ __global__ __launch_bounds__(256, 2) void conv_sp_kernel(const ConvParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave & 1, wc = wave >> 1;
     const int fi = lane & 15, kg = lane >> 4;
-    const int seg = tid & 7, lrow = tid >> 3;          // loader: rows lrow + 32 u of the tile, floats 4 seg .. + 3 of the chunk
-    const int nq = (p.C + CONV_KC - 1) / CONV_KC, nk = p.win * nq;
-
-    long aoff[4];
-    f32x4 ra[4], rw[4];
-    auto gload = [&](int k) {
-        const int j = k / nq, q = k - j * nq;
-        if (q == 0) {                                  // a new tap: the four source rows of this thread
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int r = row0 + lrow + 32 * u;
-                aoff[u] = r < M ? window_row(p.ids, p.lda, r, j, p.pad, p.T) : -1;
-            }
-        }
-        const int c = q * CONV_KC + 4 * seg;
-        const bool cin = c < p.C;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ra[u] = (cin && aoff[u] >= 0) ? ld4(p.a + aoff[u] + c) : z;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int n = col0 + lrow + 32 * u;
-            rw[u] = (cin && n < p.N) ? ld4(p.w + (long)n * p.ldw + (long)j * p.C + c) : z;
-        }
-    };
-    auto sstore = [&](int st) {
-        float* const s = lds + st * STAGE;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            *reinterpret_cast<f32x4*>(s + (lrow + 32 * u) * CONV_PITCH + 4 * seg) = ra[u];
-            *reinterpret_cast<f32x4*>(s + A_FL + (lrow + 32 * u) * CONV_PITCH + 4 * seg) = rw[u];
-        }
-    };
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](int st) {
-        const float* const sa = lds + st * STAGE + (64 * wr + fi) * CONV_PITCH + 8 * kg;
-        const float* const sw = lds + st * STAGE + A_FL + (64 * wc + fi) * CONV_PITCH + 8 * kg;
-        Frag<SPLIT> x[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[i].load_frag(sa + i * 16 * CONV_PITCH);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            Frag<SPLIT> w;
-            w.load_frag(sw + t * 16 * CONV_PITCH);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][t] = frag_prod(w, x[i], acc[i][t]);
-        }
-    };
-
-    gload(0);
-    sstore(0);
-    lds_barrier();
-    for (int k = 0; k < nk; ++k) {
-        const bool more = k + 1 < nk;
-        if (more) gload(k + 1);                        // in flight under this chunk's products
-        compute(k & 1);
-        if (more) sstore((k + 1) & 1);                 // the other stage: its last reader finished before the previous barrier
-        lds_barrier();
-    }
+    conv_tile_product<SPLIT>(lds, acc, [&p](int j) { return ConvTap{p.a, p.lda, p.ids, j}; }, p.win, p.w, p.ldw, p.C, p.N, p.T, p.pad,
+                             row0, M, col0);
 
     // epilogue: lane (fi, kg) holds row 64 wr + 16 i + fi, columns 64 wc + 16 t + 4 kg + e in acc[i][t][e]
 #pragma unroll
@@ -250,18 +187,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_sp_kernel(const WgradParams
         }
     };
 
-    if (nk > 0) {
-        gload(0);
-        sstore(0);
-        lds_barrier();
-        for (int k = 0; k < nk; ++k) {
-            const bool more = k + 1 < nk;
-            if (more) gload(k + 1);
-            compute(k & 1);
-            if (more) sstore((k + 1) & 1);
-            lds_barrier();
-        }
-    }
+    if (nk > 0) two_stage_loop(nk, gload, sstore, compute);
     // partial tile -> workspace slice `split` (every element of the [N][win C] slice that this tile covers is written, zeros for an
     // empty row range, so the reduction never reads stale data)
     const long ldw = (long)p.win * p.C;

@@ -53,6 +53,16 @@ __device__ __forceinline__ void ring_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// A device-side count (the compacted rows / sequences of this launch, written by an earlier kernel of the stream) against the host's
+// bound `cap`: `cap` when there is none, else the count clamped to 0 .. cap, wave-uniform.
+__device__ __forceinline__ int live_count(const int* dev, int cap) {
+    if (dev) {
+        const int m = __builtin_amdgcn_readfirstlane(*dev);
+        cap = m < cap ? (m > 0 ? m : 0) : cap;
+    }
+    return cap;
+}
+
 // The lane id, recomputed where it is called (the opaque zero keeps hipcc from hoisting it -- and everything derived from it -- out
 // of the tile loop, where the values would sit in registers through every step or be spilled: scratch reloads wait vmcnt(0)).
 __device__ __forceinline__ int lane_here() {

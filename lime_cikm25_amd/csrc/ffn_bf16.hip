@@ -80,11 +80,7 @@ __global__ __launch_bounds__(256, 1) void ffn_bf16_kernel(const FfnP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fi = lane & 15, kg = lane >> 4;
-    int M = p.M;
-    if (p.m_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        M = m < M ? (m > 0 ? m : 0) : M;
-    }
+    const int M = live_count(p.m_dev, p.M);
     const int ntiles = (M + BM - 1) / BM;
     int tile = blockIdx.x;
     if (tile >= ntiles) return;
@@ -699,8 +695,7 @@ extern "C" int lime_encoder_ffn_bf16(const lime_ffn_bf16_args* a, void* stream) 
     p.stamps = g_ffn_stamp_buf;
 #endif
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles);
     hipStream_t s = (hipStream_t)stream;
     if (a->pool32) hipLaunchKernelGGL((ffn_bf16_kernel<true, false>), dim3((unsigned)nwg), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((ffn_bf16_kernel<false, false>), dim3((unsigned)nwg), dim3(256), 0, s, p);
@@ -758,8 +753,7 @@ extern "C" int lime_encoder_block_bf16(const lime_encoder_block_bf16_args* a, vo
     p.stamps = g_ffn_stamp_buf;
 #endif
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles);
     hipStream_t s = (hipStream_t)stream;
     if (a->pool32) hipLaunchKernelGGL((ffn_bf16_kernel<true, true>), dim3((unsigned)nwg), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((ffn_bf16_kernel<false, true>), dim3((unsigned)nwg), dim3(256), 0, s, p);

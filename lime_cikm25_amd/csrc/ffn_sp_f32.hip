@@ -59,11 +59,7 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fi = lane & 15, kg = lane >> 4;
-    int M = p.M;
-    if (p.m_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        M = m < M ? (m > 0 ? m : 0) : M;
-    }
+    const int M = live_count(p.m_dev, p.M);
     const int ntiles = (M + BM - 1) / BM;
     int tile = blockIdx.x;
     if (tile >= ntiles) return;
@@ -402,8 +398,7 @@ extern "C" int lime_encoder_ffn_sp(const lime_ffn_sp_args* a, void* stream) {
     p.b1 = a->b1; p.b2 = a->b2; p.g = a->ln_gamma; p.beta = a->ln_beta; p.eps = a->ln_eps;
     p.out = a->out; p.ldo = a->ldo; p.M = a->M; p.E = a->E; p.F = a->F; p.m_dev = a->m_dev;
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles);
     hipStream_t s = (hipStream_t)stream;
     if (a->pool32) hipLaunchKernelGGL((ffn_sp_kernel<true>), dim3((unsigned)nwg), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((ffn_sp_kernel<false>), dim3((unsigned)nwg), dim3(256), 0, s, p);

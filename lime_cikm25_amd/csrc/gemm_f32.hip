@@ -543,14 +543,13 @@ const char* gen_name(const GenChoice& c) {
 }
 
 template <int TN, int VEC, bool LN, bool PE, int ACT, bool GENERIC, bool VIO>
-int launch_one(const GemmP& p0, int n_cu, hipStream_t stream) {
+int launch_one(const GemmP& p0, hipStream_t stream) {
     constexpr int WM = GENERIC ? 2 : 4, WN = 2, BM = WM * 32, BN = WN * TN * 32;
     GemmP p = p0;
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + BN - 1) / BN;
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = (long)n_cu * (GENERIC ? 4 : 1);
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles, GENERIC ? 4 : 1);
 #ifdef LIME_STAMPS
     p.stamps = g_stamp_buf;
 #endif
@@ -567,7 +566,7 @@ int launch_one(const GemmP& p0, int n_cu, hipStream_t stream) {
     X(5, 4, 0, 0, 0, 0, 1) X(5, 4, 0, 0, 1, 0, 1) X(5, 4, 0, 1, 0, 0, 1) X(5, 4, 0, 1, 1, 0, 1)      /* big M, 320 columns */   \
     X(4, 4, 0, 0, 0, 0, 1) X(4, 4, 0, 0, 1, 0, 1) X(4, 4, 0, 1, 0, 0, 1) X(4, 4, 0, 1, 1, 0, 1)      /* big M, 256 columns */
 
-int gen_launch(const GenChoice& c, const lime_linear_args* a, int n_cu, hipStream_t s) {
+int gen_launch(const GenChoice& c, const lime_linear_args* a, hipStream_t s) {
     GemmP p;
     p.a = a->a; p.lda = a->lda; p.a_ids = a->a_ids; p.a_pe = a->a_pe; p.lda_pe = a->lda_pe; p.a_period = a->a_period;
     p.w = a->w; p.ldw = a->ldw; p.bias = a->bias;
@@ -581,7 +580,7 @@ int gen_launch(const GenChoice& c, const lime_linear_args* a, int n_cu, hipStrea
     p.res_in_acc = (a->res != nullptr && a->act == LIME_ACT_NONE) ? 1 : 0;
 #define X(TN, VEC, LN, PE, ACT, GENERIC, VIO)                                                                                     \
     if (c.tn == TN && c.vec == VEC && c.ln == LN && c.pe == PE && c.act == ACT && c.generic == GENERIC && c.vio == VIO)           \
-        return launch_one<TN, VEC, LN, PE, ACT, GENERIC, VIO>(p, n_cu, s);
+        return launch_one<TN, VEC, LN, PE, ACT, GENERIC, VIO>(p, s);
     LIME_GEN_BUILT(X)
 #undef X
     LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "lime_linear_f32: %s is not built", gen_name(c));
@@ -718,7 +717,7 @@ extern "C" int lime_linear_f32(const lime_linear_args* a, void* stream) {
     st = linear_route(a, lime_split_mode(), n_cu, &r);
     if (st != LIME_OK) return st;
     st = r.family == LIME_LINEAR_SP ? lime_sp_launch(r.sp, &r.gemm, s) : r.family == LIME_LINEAR_PP ? lime_pp_launch(r.pp, &r.gemm, s)
-       : r.family == LIME_LINEAR_MID ? lime_mid_launch(r.mid, &r.gemm, s) : gen_launch(r.gen, &r.gemm, n_cu, s);
+       : r.family == LIME_LINEAR_MID ? lime_mid_launch(r.mid, &r.gemm, s) : gen_launch(r.gen, &r.gemm, s);
     if (st == LIME_OK && (r.second & LIME_LINEAR_PASS_DROPOUT))
         st = lime_dropout_f32(a->c, a->ldc, a->c, a->ldc, a->M, a->N, a->dropout_p, a->dropout_seed, a->dropout_site, stream);
     if (st == LIME_OK && (r.second & LIME_LINEAR_PASS_RELU_BWD)) st = lime_relu_bwd_f32(a->c, a->ldc, a->res, a->ldr, a->M, a->N, a->act_scale, stream);

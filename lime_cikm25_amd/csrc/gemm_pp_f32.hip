@@ -80,8 +80,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(const PPParams p) {
     const int fi = lane & 15, kg = lane >> 4;          // MFMA 16x16x4: lane (i, kg) supplies row i, k slot kg
     int M = p.M, n_row_blocks = p.n_row_blocks;
     if (p.m_dev) {                                     // device-side row count (uniform: one scalar load)
-        const int m = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        M = m < M ? (m > 0 ? m : 0) : M;
+        M = live_count(p.m_dev, M);
         n_row_blocks = (M + BM - 1) / BM;
     }
     const int ntiles = n_row_blocks * p.n_col_blocks;
@@ -482,8 +481,7 @@ int launch(const PPParams& p0, hipStream_t stream) {
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + NTL * 32 - 16 * TRIM - 1) / (NTL * 32 - 16 * TRIM);
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = 2L * lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles, 2);
 #ifdef LIME_STAMPS
     p.stamps = g_pp_stamp_buf;
 #endif

@@ -80,8 +80,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
     const int fi = lane & 15, kg = lane >> 4;
     int M = p.M, n_row_blocks = p.n_row_blocks;
     if (p.m_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        M = m < M ? (m > 0 ? m : 0) : M;
+        M = live_count(p.m_dev, M);
         n_row_blocks = (M + BM - 1) / BM;
     }
     const int ntiles = n_row_blocks * p.n_col_blocks;
@@ -503,8 +502,7 @@ int launch(const PPParams& p0, hipStream_t stream) {
     p.n_row_blocks = (p.M + BM - 1) / BM;
     p.n_col_blocks = (p.N + 32 * CT - 1) / (32 * CT);
     const long ntiles = (long)p.n_row_blocks * p.n_col_blocks;
-    long nwg = lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles);
 #ifdef LIME_STAMPS
     p.stamps = g_sp_stamp_buf;
 #endif

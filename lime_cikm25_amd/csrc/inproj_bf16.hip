@@ -48,11 +48,7 @@ __global__ __launch_bounds__(256, 1) void inproj_bf16_kernel(const InP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fi = lane & 15, kg = lane >> 4;
-    int M = p.M;
-    if (p.m_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        M = m < M ? (m > 0 ? m : 0) : M;
-    }
+    const int M = live_count(p.m_dev, p.M);
     const int ntiles = (M + BM - 1) / BM;
     int tile = blockIdx.x;
     if (tile >= ntiles) return;
@@ -350,8 +346,7 @@ extern "C" int lime_inproj_bf16(const lime_inproj_bf16_args* a, void* stream) {
     p.c_ids = a->c_ids; p.out = a->out; p.ldo = a->ldo;
     p.M = a->M; p.N = a->N; p.K = a->K; p.m_dev = a->m_dev;
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    long nwg = lime_num_cus();
-    if (nwg > ntiles) nwg = ntiles;
+    const long nwg = lime_persistent_grid(ntiles);
     hipLaunchKernelGGL(inproj_bf16_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, p);
     return lime_check_launch("lime_inproj_bf16");
 }

@@ -49,11 +49,7 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const LstmP p) {
     const int fi = lane & 15, kg = lane >> 4;
     const int dir = blockIdx.z, u0 = blockIdx.y * UT, row0 = blockIdx.x * RT;
     const int h = p.h, T = p.T, s = p.step;
-    int R = p.R;
-    if (p.n_rows_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*p.n_rows_dev);
-        R = m < R ? (m < 0 ? 0 : m) : R;
-    }
+    const int R = live_count(p.n_rows_dev, p.R);
     // every wave looks at the same 64 sequences (lane l: row0 + l), so the verdict is uniform over the workgroup
     {
         const int r = row0 + lane;

@@ -42,11 +42,7 @@ __global__ __launch_bounds__(256) void cne_gate_cached_kernel(const float* __res
                                                               const int* __restrict__ n_rows_dev) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int n = cap;
-    if (n_rows_dev) {
-        const int m = __builtin_amdgcn_readfirstlane(*n_rows_dev);
-        n = m < cap ? (m < 0 ? 0 : m) : cap;
-    }
+    const int n = lime_dev::live_count(n_rows_dev, cap);
     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int r = blockIdx.y; r < n; r += gridDim.y) {
         const long j = idx[r];

@@ -46,9 +46,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel
     int n_pair = p.n_pair, n_group = p.n_group;
     if constexpr (MAP) {
         if (p.n_seq_dev) {
-            int ns = __builtin_amdgcn_readfirstlane(*p.n_seq_dev);
-            ns = ns < p.n_seq ? (ns > 0 ? ns : 0) : p.n_seq;
-            n_pair = ns * p.n_head;
+            n_pair = live_count(p.n_seq_dev, p.n_seq) * p.n_head;
             n_group = (n_pair + 4 / NT - 1) / (4 / NT);
         }
         if (n_group == 0) return;
@@ -200,8 +198,7 @@ template <int NT, bool MAP = false>
 int launch(AttnB p, hipStream_t s) {
     constexpr int G = 4 / NT;
     p.n_group = (p.n_pair + G - 1) / G;
-    long blocks = (long)lime_num_cus() * (NT <= 2 ? 4 : 3);            // 36 KB LDS, <= 128 / 170 VGPRs: 4 / 3 workgroups per CU
-    if (blocks > p.n_group) blocks = p.n_group;
+    const long blocks = lime_persistent_grid(p.n_group, NT <= 2 ? 4 : 3);   // 36 KB LDS, <= 128 / 170 VGPRs: 4 / 3 workgroups per CU
     hipLaunchKernelGGL((token_attn_bf16_kernel<NT, MAP>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     return lime_check_launch("lime_token_attention_bf16");
 }

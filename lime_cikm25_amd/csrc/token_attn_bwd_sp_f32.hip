@@ -296,8 +296,7 @@ int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, 
     if (const int st = lime_reserve_lds(kernel, LDS_BYTES, reserved[S == SPB], "lime_token_attention_bwd_f32")) return st;
     const long n_prob = (long)n_seq * n_head;
     BwdSpP p{q, k, v, ld, dout, ldo, dq, dk, dv, ldd, n_seq, S, n_head, head_dim, scale, drop};
-    const int n_cu = lime_num_cus();
-    const unsigned grid = (unsigned)(n_prob < n_cu ? n_prob : n_cu);             // persistent: one workgroup per CU
+    const unsigned grid = (unsigned)lime_persistent_grid(n_prob);                // persistent: one workgroup per CU
     if (S == SPB) attn_bwd_sp_kernel<true><<<grid, 512, LDS_BYTES, s>>>(p);
     else attn_bwd_sp_kernel<false><<<grid, 512, LDS_BYTES, s>>>(p);
     return lime_check_launch("attn_bwd_sp_kernel");

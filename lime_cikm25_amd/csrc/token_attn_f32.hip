@@ -105,8 +105,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
     const int S = p.S, hd = p.hd, hs = p.hs;
     int n_pair = p.n_pair, n_group = p.n_group;
     if (p.n_seq_dev) {                                 // device-side sequence count (compacted batches; uniform scalar load)
-        int ns = __builtin_amdgcn_readfirstlane(*p.n_seq_dev);
-        ns = ns < p.n_seq ? (ns > 0 ? ns : 0) : p.n_seq;
+        const int ns = live_count(p.n_seq_dev, p.n_seq);
         n_pair = ns * p.n_head;
         n_group = (n_pair + (NT >= 3 ? 1 : 4 / NT) - 1) / (NT >= 3 ? 1 : 4 / NT);
         if (n_group == 0) return;
@@ -484,8 +483,7 @@ int launch(AttnP p, hipStream_t s, const char* entry) {
     p.n_group = (p.n_pair + G - 1) / G;
     // LDS per workgroup decides how many are resident per CU; a few persistent workgroups per CU
     const int per_cu = NT <= 2 ? 3 : (NT <= 4 ? 2 : 1);
-    long blocks = (long)lime_num_cus() * per_cu;
-    if (blocks > p.n_group) blocks = p.n_group;
+    const long blocks = lime_persistent_grid(p.n_group, per_cu);
 #ifdef LIME_STAMPS
     p.stamps = g_attn_stamp_buf;
 #endif

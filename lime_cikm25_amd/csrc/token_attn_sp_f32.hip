@@ -55,8 +55,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
     const int S = p.S;
     int n_pair = p.n_pair, n_group = p.n_group;
     if (p.n_seq_dev) {
-        int ns = __builtin_amdgcn_readfirstlane(*p.n_seq_dev);
-        ns = ns < p.n_seq ? (ns > 0 ? ns : 0) : p.n_seq;
+        const int ns = live_count(p.n_seq_dev, p.n_seq);
         n_pair = ns * p.n_head;
         n_group = (n_pair + G - 1) / G;
         if (n_group == 0) return;
@@ -412,8 +411,7 @@ template <int NT>
 int launch(SpAttnP p, hipStream_t s) {
     constexpr int G = 4 / NT;
     p.n_group = (p.n_pair + G - 1) / G;
-    long blocks = (long)lime_num_cus() * 2;
-    if (blocks > p.n_group) blocks = p.n_group;
+    const long blocks = lime_persistent_grid(p.n_group, 2);
     if (p.row_map) hipLaunchKernelGGL((token_attn_sp_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((token_attn_sp_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     return lime_check_launch("token_attn_sp_kernel");
@@ -435,8 +433,7 @@ int lime_token_attention_sp(const float* q, const float* k, const float* v, long
     SpAttnP p{q, k, v, ld, out, ldo, n_seq, S, n_head, hd, scale, n_seq * n_head, 0, row_map, n_seq_dev, drop ? *drop : LimeDropout{0, 0, 1.f}};
     if (is_long) {
         const long n_task = (long)p.n_pair * (S / 128);
-        long blocks = (long)lime_num_cus() * 2;
-        if (blocks > n_task) blocks = n_task;
+        const long blocks = lime_persistent_grid(n_task, 2);
         if (row_map) hipLaunchKernelGGL((token_attn_sp_long_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, p, lse);
         else hipLaunchKernelGGL((token_attn_sp_long_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, p, lse);
         return lime_check_launch("token_attn_sp_long_kernel");

@@ -971,8 +971,7 @@ int launch_attn_bwd(const float* q, const float* k, const float* v, long ld, con
     static int reserved = 0;
     if (const int st = lime_reserve_lds((const void*)token_attn_bwd_kernel<SP>, BYTES, reserved, "lime_token_attention_bwd_f32")) return st;
     const long n_group = ((long)n_seq * n_head + PPW - 1) / PPW;
-    const int n_cu = lime_num_cus();
-    const int grid = (int)(n_group < n_cu ? n_group : n_cu);             // persistent: one workgroup per CU
+    const int grid = (int)lime_persistent_grid(n_group);                 // persistent: one workgroup per CU
     // vector staging: 32-float head rows on 16-byte boundaries with zero padding columns, dO pairs on 8-byte boundaries
     const bool vec = head_stride == 32 && lime_al16(q, ld) && lime_al16(k, ld) && lime_al16(v, ld) &&
                      head_dim % 2 == 0 && ldo % 2 == 0 && (((uintptr_t)dout) & 7) == 0;

@@ -188,6 +188,14 @@ class Conv1D(nn.Module):
         n = self.conv1.out_channels
         return [(self.conv1, 0), (self.conv2, n), (self.conv3, 2 * n)]
 
+    def relu_into(self, a, T, out, ids=None, m_dev=None):
+        """Conv1D + ReLU (layers.py:126-130) over M = sequences x T tokens -> out [M, cnn_kernel_num], each convolution into its column
+        slice.  The word rows are a [M, C] (ids None) or a[ids]; m_dev: see ops.conv1d_window."""
+        for conv, col in self.convs():
+            ops.conv1d_window(a, ops.conv1d_pack(conv.weight), conv.kernel_size[0], T, ids=ids, bias=conv.bias, act='relu',
+                              out=out[:, col:col + conv.out_channels], m_dev=m_dev)
+        return out
+
     def forward(self, feature):
         raise NotImplementedError('Conv1D is a parameter holder: the CNN encoder runs ops.conv1d_window')
 

@@ -1227,14 +1227,6 @@ class CNN(NewsEncoder):
         super().initialize()
         self.attention.initialize()
 
-    def conv_into(self, ids, table, M, T, out, m_dev=None):
-        """Conv1D + ReLU (newsEncoders.py:556) over M = sequences x T tokens whose word rows are table[ids] -> out [M, cnn_kernel_num]."""
-        for conv, col in self.conv.convs():
-            n = conv.out_channels
-            ops.conv1d_window(table, ops.conv1d_pack(conv.weight), conv.kernel_size[0], T, ids=ids, bias=conv.bias, act='relu',
-                              out=out[:, col:col + n], m_dev=m_dev)
-        return out
-
     def _compact_applicable(self, ids):
         return (DEDUP and ids.dtype == torch.int32 and ids.is_contiguous() and self.cnn_kernel_num % 4 == 0 and
                 self.attention.affine1.out_features % 4 == 0)
@@ -1256,12 +1248,12 @@ class CNN(NewsEncoder):
             # under another mask is live (MHSA._encode_compact)
             cmp = ops.compact_sequences(ops.mhsa_live_ids(ids, mask))
             mask_c = ops.mhsa_compact_mask(cmp, mask)
-            self.conv_into(cmp.ids_c, table, cap, T, c, m_dev=cmp.n_rows)                                             # :556
+            self.conv.relu_into(table, T, c, ids=cmp.ids_c, m_dev=cmp.n_rows)                                         # :556
             ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', m_dev=cmp.n_rows, out=hidden)
             pooled_c = ops.additive_pool(hidden, a2, c, n + 1, T, mask=mask_c, n_seq_dev=cmp.n_compact)                  # :558
             ops.gather_rows(cmp.seq_inv, pooled_c, out)
             return
-        self.conv_into(ids.reshape(-1), table, n * T, T, c[:n * T])                                                     # :556
+        self.conv.relu_into(table, T, c[:n * T], ids=ids.reshape(-1))                                                   # :556
         ops.linear(c, self.attention.affine1.weight, self.attention.affine1.bias, act='tanh', m_dev=_row_count(n * T, dev), out=hidden)
         ops.additive_pool(hidden[:n * T], a2, c[:n * T], n, T, mask=mask, out=out)                                      # :558
 
@@ -1406,15 +1398,6 @@ class NAML(NewsEncoder):
         nn.init.xavier_uniform_(self.affine2.weight)
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
 
-    @staticmethod
-    def conv_into(conv, ids, table, M, T, out, m_dev=None):
-        """Conv1D + ReLU (:681, :684) over M = sequences x T tokens whose word rows are table[ids] -> out [M, cnn_kernel_num]."""
-        for c, col in conv.convs():
-            n = c.out_channels
-            ops.conv1d_window(table, ops.conv1d_pack(c.weight), c.kernel_size[0], T, ids=ids, bias=c.bias, act='relu',
-                              out=out[:, col:col + n], m_dev=m_dev)
-        return out
-
     def _compact_applicable(self, ids):
         return DEDUP and ids.dtype == torch.int32 and ids.is_contiguous()
 
@@ -1435,12 +1418,12 @@ class NAML(NewsEncoder):
         a1, a2 = att.affine1, att.affine2.weight.view(-1)
         if compact:
             cmp = ops.compact_sequences(ids)
-            self.conv_into(conv, cmp.ids_c, table, cap, T, c, m_dev=cmp.n_rows)                                       # :681, :684
+            conv.relu_into(table, T, c, ids=cmp.ids_c, m_dev=cmp.n_rows)                                              # :681, :684
             ops.attn_pool(c, a1.weight, a1.bias, a2, n + 1, T, out=pooled, n_seq_dev=cmp.n_compact, w1p=w1p,
                           m_dev=cmp.n_rows)                                                                            # :686-687
             ops.gather_rows(cmp.seq_inv, pooled, out)
             return
-        self.conv_into(conv, ids.reshape(-1), table, n * T, T, c[:n * T])                                              # :681, :684
+        conv.relu_into(table, T, c[:n * T], ids=ids.reshape(-1))                                                       # :681, :684
         ops.attn_pool(c, a1.weight, a1.bias, a2, n + 1, T, out=pooled, n_seq_dev=_row_count(n, dev), w1p=w1p,
                       m_dev=_row_count(n * T, dev))                                                                    # :686-687
         ops.gather_rows(_identity_rows(n, dev), pooled, out)

@@ -596,17 +596,11 @@ class _Conv1D(torch.autograd.Function):
     bias gradient as a column sum."""
 
     @staticmethod
-    def forward(ctx, x, T, windows, *params):
+    def forward(ctx, holder, x, T, *params):
         x = x.contiguous()
-        M = x.shape[0]
-        ws, bs = params[0::2], params[1::2]
-        K = sum(w.shape[0] for w in ws)
-        out = torch.empty((M, K), dtype=torch.float32, device=x.device)
-        col = 0
-        for w, b, win in zip(ws, bs, windows):
-            ops.conv1d_window(x, ops.conv1d_pack(w), win, T, bias=b, act='relu', out=out[:, col:col + w.shape[0]])
-            col += w.shape[0]
-        ctx.dims = (T, windows)
+        ws = params[0::2]                                  # the holder's own weights, as inputs of the graph
+        out = holder.relu_into(x, T, torch.empty((x.shape[0], sum(w.shape[0] for w in ws)), dtype=torch.float32, device=x.device))
+        ctx.dims = (T, tuple(w.shape[2] for w in ws))
         ctx.save_for_backward(x, out, *ws)
         return out
 
@@ -616,7 +610,7 @@ class _Conv1D(torch.autograd.Function):
         T, windows = ctx.dims
         M, C = x.shape
         dy = ops.relu_bwd_(dout.contiguous().clone(), out)
-        dx = torch.empty((M, C), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        dx = torch.empty((M, C), dtype=torch.float32, device=x.device) if ctx.needs_input_grad[1] else None
         grads = []
         col = 0
         for i, (w, win) in enumerate(zip(ws, windows)):
@@ -627,7 +621,7 @@ class _Conv1D(torch.autograd.Function):
             dw = ops.conv1d_window_wgrad(d, x, win, T).view(n, win, C).permute(0, 2, 1).contiguous()
             grads += [dw, ops.colsum(d)]
             col += n
-        return (dx, None, None) + tuple(grads)
+        return (None, dx, None) + tuple(grads)
 
 
 def cnn_content(enc, title_text, title_mask, category, subCategory):
@@ -641,11 +635,7 @@ def cnn_content(enc, title_text, title_mask, category, subCategory):
     x = embedding(enc.word_embedding.weight, title_text, hot_id=0).view(M * T, -1)                              # :553
     if p > 0:
         x = _Dropout.apply(x, p, seed, 0)
-    convs = enc.conv.convs()
-    params = []
-    for conv, _ in convs:
-        params += [conv.weight, conv.bias]
-    c = _Conv1D.apply(x, T, tuple(conv.kernel_size[0] for conv, _ in convs), *params)                          # :555, layers.py:126-130
+    c = _conv_c(enc.conv, x, T)                                                                                 # :555, layers.py:126-130
     if p > 0:
         c = _Dropout.apply(c, p, seed, 1)
     mask = title_mask.contiguous()
@@ -740,11 +730,10 @@ def kcnn_content(enc, title_text, title_entity, category, subCategory):
 
 def _conv_c(conv, x, T):
     """layers.Conv1D + ReLU of a parameter holder (layers.Conv1D) over M = sequences x T token rows x [M, C] -> [M, cnn_kernel_num]."""
-    convs = conv.convs()
     params = []
-    for c, _ in convs:
+    for c, _ in conv.convs():
         params += [c.weight, c.bias]
-    return _Conv1D.apply(x, T, tuple(c.kernel_size[0] for c, _ in convs), *params)
+    return _Conv1D.apply(conv, x, T, *params)
 
 
 def naml_content(enc, title_text, content_text, category, subCategory):

@@ -2,6 +2,7 @@
 against the reference goldens (tests/golden/cnn_*.npz, grad_cnn_*.npz: tools/make_cnn_goldens.py), the compacted path against the
 dense one and graph replay against eager (bitwise), a reproducible training step, training-mode dropout against a torch fp64 statement
 fed with the kernels' masks, and the per-news content cache against the uncached forward."""
+import functools
 import json
 import math
 import os
@@ -136,6 +137,83 @@ def test_exact_fp32_mfma_form():
     wr = w.clone().requires_grad_(True)
     (ref_conv(table[ids.long()], wr, None, T) * dy).sum().backward()
     assert rel_err(dw.view(O, win, C).permute(0, 2, 1).cpu().numpy(), wr.grad.numpy()) < KTOL
+
+
+# The edges of the shared tile product (csrc/conv_frag.h conv_tile_product, its tap and [row0, row_end) arguments) as conv_sp_kernel
+# drives it: 19 sequences of 7 tokens = 133 rows (the second 128-row tile holds 5 live rows), C = 36 (the second 32-deep chunk is
+# masked past 4 columns), N = 132 (the second column block is 4 wide), without a device row count and with one of 126 (2 live rows
+# short of the first tile, the second tile returns).
+EDGE_T, EDGE_N_SEQ, EDGE_C, EDGE_O, EDGE_LIVE = 7, 19, 36, 132, 126
+
+
+@functools.lru_cache(maxsize=None)
+def edge_problem(win):
+    """-> table, ids, x = table[ids], w, b, base (what the output holds before the launch), relu(conv) in fp64: computed once."""
+    V = 41
+    table = rnd(V, EDGE_C, seed=81)
+    table[0] = rnd(EDGE_C, seed=82) + 2.0                      # word 0 is not zero
+    w, b = rnd(EDGE_O, EDGE_C, win, seed=83, scale=0.3), rnd(EDGE_O, seed=84)
+    ids = _ids(EDGE_N_SEQ, EDGE_T, V, seed=85)
+    x = table[ids.long()]
+    base = rnd(EDGE_N_SEQ * EDGE_T, EDGE_O + 8, seed=86).float()
+    return table, ids, x, w, b, base, torch.relu(ref_conv(x, w, b, EDGE_T))
+
+
+def run_edge_window(win, gather, accumulate, split, live):
+    """The launch of test_conv_window_tile_edges -> the whole [133, 140] matrix whose columns 4 .. 135 are the output."""
+    table, ids, x, w, b, base, _ = edge_problem(win)
+    big = base.cuda()
+    m_dev = None if live is None else torch.tensor([live], dtype=torch.int32, device='cuda')
+    prev = ops.set_split_gemm(split)
+    try:
+        ops.conv1d_window((table if gather else x).float().cuda(), ops.conv1d_pack(w.float().cuda()), win, EDGE_T,
+                          ids=ids.cuda() if gather else None, bias=b.float().cuda(), act='relu', out=big[:, 4:4 + EDGE_O],
+                          accumulate=accumulate, m_dev=m_dev)
+    finally:
+        ops.set_split_gemm(prev)
+    return big.cpu()
+
+
+@pytest.mark.parametrize('split', [True, False])
+@pytest.mark.parametrize('accumulate', [False, True])
+@pytest.mark.parametrize('gather', [True, False])
+@pytest.mark.parametrize('win', [3, 5])
+def test_conv_window_tile_edges(win, gather, accumulate, split):
+    base, want = edge_problem(win)[5:]
+    cols = slice(4, 4 + EDGE_O)
+    if accumulate:
+        want = want + base[:, cols].double()
+    for live in (None, EDGE_LIVE):
+        got = run_edge_window(win, gather, accumulate, split, live)
+        n = EDGE_N_SEQ * EDGE_T if live is None else live
+        e = rel_err(got[:n, cols].numpy(), want[:n].numpy())
+        print('win %d gather %d accumulate %d split %d live %s: %.2e' % (win, gather, accumulate, split, live, e))
+        assert e < KTOL, e
+        assert torch.equal(got[n:], base[n:])                  # the rows behind the count keep what they held
+        assert torch.equal(got[:, :4], base[:, :4]) and torch.equal(got[:, 4 + EDGE_O:], base[:, 4 + EDGE_O:])
+
+
+def run_edge_wgrad(split):
+    """The launch of test_conv_wgrad_tile_edges: dW [8, 3 * 36] of 133 rows."""
+    x = edge_problem(3)[2]
+    dy = rnd(EDGE_N_SEQ * EDGE_T, 8, seed=87)
+    prev = ops.set_split_gemm(split)
+    try:
+        return ops.conv1d_window_wgrad(dy.float().cuda(), x.float().cuda(), 3, EDGE_T), dy
+    finally:
+        ops.set_split_gemm(prev)
+
+
+@pytest.mark.parametrize('split', [True, False])
+def test_conv_wgrad_tile_edges(split):
+    """133 rows are four whole 32-row chunks and one of 5; 8 outputs and 36 columns leave most of the 64 x 128 tile masked."""
+    dw, dy = run_edge_wgrad(split)
+    x = edge_problem(3)[2]
+    w = torch.zeros(8, EDGE_C, 3, dtype=torch.float64, requires_grad=True)
+    (ref_conv(x, w, None, EDGE_T) * dy).sum().backward()
+    e = rel_err(dw.view(8, 3, EDGE_C).permute(0, 2, 1).cpu().numpy(), w.grad.numpy())
+    assert e < KTOL, e
+    assert torch.equal(run_edge_wgrad(split)[0], dw)           # fixed summation order
 
 
 # ---------------------------------------------------------------------------------------------------------------------

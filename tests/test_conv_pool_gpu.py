@@ -208,6 +208,67 @@ def test_a_sequence_has_the_same_bits_wherever_it_sits():
     assert torch.equal(moved[0], full[30]) and torch.equal(moved[4], full[11])
 
 
+# The edges of the shared tile product (csrc/conv_frag.h conv_tile_product) as conv_pool_sp_kernel drives it: T = 12 puts 10 whole
+# sequences into a 128-row tile and leaves 8 tile rows dead, 11 sequences leave one for the second tile, C = 36 masks most of the second
+# chunk, N = 132 makes a second column block of 4; the tap walks one gathered source or a gathered and two dense ones, each with a
+# leading dimension of its own.
+EDGE = dict(n_seq=11, T=12, N=132, C=36, V=29)
+EDGE_LDA = (36, 40, 44)
+
+
+def edge_sources(n_src, order):
+    """-> (fp64 dense sources, device (a, ids) pairs) with the sequences in ``order``."""
+    n_seq, T, C, V = EDGE['n_seq'], EDGE['T'], EDGE['C'], EDGE['V']
+    g = torch.Generator().manual_seed(301)
+    table = rnd(V, C, seed=302)
+    ids = torch.randint(0, V, (n_seq, T), generator=g, dtype=torch.int32)
+    ids[:, ::3] = 0
+    ids = ids[order].reshape(-1).contiguous()
+    xs, src = [table[ids.long()]], [(table.float().cuda(), ids.cuda())]
+    for s in range(1, n_src):
+        x = rnd(n_seq, T, C, seed=302 + s)[order].reshape(-1, C)
+        buf = torch.full((n_seq * T, EDGE_LDA[s]), 9.0, device='cuda')
+        buf[:, :C] = x.float().cuda()
+        xs.append(x)
+        src.append((buf[:, :C], None))
+    return xs, src
+
+
+def run_edge_pool(n_src, win, pad, split, order=None, live=None):
+    """One fused launch on the edge problem -> pooled, arg (filled with 7.0 / 99 first), the fp64 pre-activations, P."""
+    n_seq, T, N, C = EDGE['n_seq'], EDGE['T'], EDGE['N'], EDGE['C']
+    P = T - win + 1
+    xs, src = edge_sources(n_src, torch.arange(n_seq) if order is None else order)
+    w = rnd(N, C, win, n_src, seed=310 + win, scale=3.0 / math.sqrt(n_src * win * C))
+    b = rnd(N, seed=311, scale=0.5)
+    out = torch.full((n_seq, N), 7.0, device='cuda')
+    arg = torch.full((n_seq, N), 99, dtype=torch.int32, device='cuda')
+    count = None if live is None else torch.tensor([live], dtype=torch.int32, device='cuda')
+    prev = ops.set_split_gemm(split)
+    try:
+        ops.conv_pool(src, ops.conv_pool_pack(w.float().cuda()), win, pad, P, T, bias=b.float().cuda(), out=out, arg=arg, n_seq_dev=count,
+                      fused=True)
+    finally:
+        ops.set_split_gemm(prev)
+    return out, arg, ref_pre(xs, w, b, T, pad), P
+
+
+@pytest.mark.parametrize('split', [True, False])
+@pytest.mark.parametrize('win,pad', [(2, 0), (2, 1), (3, 1)])
+@pytest.mark.parametrize('n_src', [1, 3])
+def test_fused_tile_edges(n_src, win, pad, split):
+    n_seq = EDGE['n_seq']
+    full, full_arg, pre, P = run_edge_pool(n_src, win, pad, split)
+    check_pool(full, full_arg, pre, P, 'edge')
+    # a device count of 10: the second tile returns, sequence 10 keeps what it held, the position included
+    part, part_arg = run_edge_pool(n_src, win, pad, split, live=10)[:2]
+    assert torch.equal(part[:10], full[:10]) and torch.equal(part_arg[:10], full_arg[:10])
+    assert torch.all(part[10] == 7.0) and torch.all(part_arg[10] == 99)
+    # the batch in reverse order: every sequence in another tile slot, the last one now first -- the same bits
+    back, back_arg = run_edge_pool(n_src, win, pad, split, order=torch.arange(n_seq - 1, -1, -1))[:2]
+    assert torch.equal(back.flip(0), full) and torch.equal(back_arg.flip(0), full_arg)
+
+
 def test_long_sequences_take_the_unfused_form():
     n_seq, T, N, C, n_src, win, pad, P = 3, 130, 36, 20, 3, 3, 1, 128
     xs, src, w, b = make_problem(n_seq, T, N, C, n_src, win, (True, False, True), seed=51)

@@ -104,7 +104,8 @@ def test_kernel_files_do_not_redefine_header_helpers():
         for n in _defined_names(open(path).read()):
             shared.setdefault(n, os.path.basename(path))
     assert {'make_rsrc', 'dma16', 'swz4', 'lane_here', 'u32x4', 'f32x4', 'lime_al16', 'split_frag', 'OOB', 'PPParams', 'LOG2E', 'mfma16',
-            'buf_load1'} <= set(shared), 'the scan lost its grip'
+            'buf_load1', 'live_count', 'lime_persistent_grid', 'conv_tile_product', 'two_stage_loop', 'ConvTap',
+            'CONV_STAGE'} <= set(shared), 'the scan lost its grip'
     copies = []
     for path in sorted(glob.glob(os.path.join(CSRC, '*.hip'))):
         for n in sorted(_defined_names(open(path).read()) & set(shared)):
