@@ -724,9 +724,15 @@ int lime_additive_pool_bwd_f32(const float* hidden, int64_t ldh, const float* af
                                float* da2_part, int32_t n_seq, int32_t S, void* stream);
 
 /* ---- dropout inside the token encoders in training mode --------------------------------------------------------------
- * Masks are a pure function of (seed, site, element index) (csrc/dropout.h): element e of site `site` is kept iff
- * hash(seed, site, e) >= p * 2^32, kept values are scaled by 1 / (1 - p); the backward regenerates the mask from the same
- * triple.  torch's Philox stream is not reproduced (it differs between torch's own CPU and GPU generators as well). */
+ * Masks are a pure function of (seed, site, element index) (csrc/dropout.h); the backward regenerates the mask from the same
+ * triple.  One splitmix64 value serves four consecutive elements, 16 bits each:
+ *     key    = seed * 0x9E3779B97F4A7C15 + (uint64)(uint32)(site + 1) * 0xD1B54A32D192ED03          (wrapping uint64)
+ *     z      = (e >> 2) + key;  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *     thresh = p <= 0 ? 0 : min(floor(p * 2^16 + 0.5), 0xFFFF)                                     (round(p * 2^16))
+ *     element e is kept iff ((z >> 16 (e & 3)) & 0xFFFF) >= thresh
+ * so p is realised in steps of 2^-16 (the keep probability is 1 - thresh / 2^16), while kept values are scaled by the exact fp32
+ * 1 / (1 - p).  tests/dropout_cases.py states the same on the host.  torch's Philox stream is not reproduced (it differs between
+ * torch's own CPU and GPU generators as well). */
 
 /* dst[r, c] = keep(r * cols + c) ? src[r, c] / (1 - p) : 0   (src == dst allowed).  Forward of nn.Dropout, and -- applied to a
  * gradient with the forward's (seed, site) -- its backward. */

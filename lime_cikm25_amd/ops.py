@@ -1475,13 +1475,16 @@ def dropout(src, p, seed, site, out=None):
 
 
 def embed_pe_dropout(ids, table, pe, period, p, seed, site_emb, site_pe):
-    """drop(drop(table[ids]) + pe[r % period]) -> [len(ids), dim]."""
+    """drop(drop(table[ids]) + pe[r % period]) -> [len(ids), dim]; ``pe`` None: drop(drop(table[ids]))."""
     lib = _lib.load()
     _vec(ids, 'ids', dtype=torch.int32)
     _mat(table, 'table')
-    _mat(pe, 'pe')
+    if pe is not None:
+        _mat(pe, 'pe')
+        if pe.shape[1] != table.shape[1] or period <= 0 or pe.shape[0] < period:
+            raise ValueError('pe must be [>= period, dim]')
     out = torch.empty((ids.numel(), table.shape[1]), dtype=torch.float32, device=table.device)
-    check(lib.lime_embed_pe_dropout_f32(_p(ids), _p(table), _ld(table), _p(pe), _ld(pe), period, _p(out), _ld(out), ids.numel(),
+    check(lib.lime_embed_pe_dropout_f32(_p(ids), _p(table), _ld(table), _p(pe), _ld(pe) if pe is not None else 0, period, _p(out), _ld(out), ids.numel(),
                                         table.shape[1], p, seed, site_emb, site_pe, _stream()), 'lime_embed_pe_dropout_f32')
     return out
 

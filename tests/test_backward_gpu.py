@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from dropout_cases import cand_attn_ref, layernorm_bwd_ref      # statements shared with tests/test_dropout_kernels_gpu.py
 from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -94,25 +95,21 @@ def test_layernorm_bwd_and_rstd(ops, M, E, div):
     res = rnd(M, E, seed=4)
     gamma, beta = rnd(E, seed=5) * 0.5 + 1.0, rnd(E, seed=6)
     dy = rnd((M + div - 1) // div, E, seed=7)
-    z = (a @ w.t() + b + res).double().requires_grad_()
-    gd, bd = gamma.double().requires_grad_(), beta.double().requires_grad_()
-    y = F.layer_norm(z, (E,), gd, bd, 1e-5)
-    dy_full = dy.double().repeat_interleave(div, dim=0)[:M] / div
-    y.backward(dy_full)
-    rstd_want = (1.0 / torch.sqrt(z.detach().var(dim=1, unbiased=False) + 1e-5)).float()
+    y, rstd_want, dz_want, dg_want, db_want, dzs_want = layernorm_bwd_ref((a @ w.t() + b + res).double(), gamma, beta, dy, div)
+    rstd_want = rstd_want.float()
 
     if E <= 320:          # the fused LayerNorm epilogue of lime_linear_f32 hands out rstd
         rstd = torch.empty(M, dtype=torch.float32, device='cuda')
         yg = ops.linear(a.cuda(), w.cuda(), b.cuda(), res=res.cuda(), ln=(gamma.cuda(), beta.cuda()), ln_rstd=rstd)
-        close(yg, y.detach().float(), what='fused LN forward')
+        close(yg, y.float(), what='fused LN forward')
         close(rstd, rstd_want, what='ln_rstd')
     else:
-        yg, rstd = y.detach().float().cuda(), rstd_want.cuda()
+        yg, rstd = y.float().cuda(), rstd_want.cuda()
     dz, dg, db, dzs = ops.layernorm_bwd(dy.cuda(), yg, gamma.cuda(), beta.cuda(), rstd, dy_div=div, dy_scale=1.0 / div)
-    close(dz, z.grad.float(), tol=2e-4, what='dz')
-    close(dg, gd.grad.float(), tol=2e-4, what='dgamma')
-    close(db, bd.grad.float(), tol=2e-4, what='dbeta')
-    close(dzs, z.grad.sum(0).float(), tol=2e-4, what='dzsum')
+    close(dz, dz_want.float(), tol=2e-4, what='dz')
+    close(dg, dg_want.float(), tol=2e-4, what='dgamma')
+    close(db, db_want.float(), tol=2e-4, what='dbeta')
+    close(dzs, dzs_want.float(), tol=2e-4, what='dzsum')
 
 
 def test_relu_bwd(ops):
@@ -360,13 +357,7 @@ def test_cand_attn_weights_train_and_bwd(ops, B, N, H, nh, hd, p):
     dagg = rnd(B, H, seed=3)
     m = ops.dropout(torch.ones(B * nh * N, H, device='cuda'), p, seed, 0).cpu().double().view(B, nh, N, H)
     qd, kd = qp.double().requires_grad_(), kp.double().requires_grad_()
-    Q = qd.view(B, N, nh, hd).transpose(1, 2)
-    K = kd.view(B, H, nh, hd).transpose(1, 2)
-    sc = (Q @ K.transpose(-2, -1)) / (D ** 0.5)
-    sc = sc.masked_fill(mask.view(B, 1, 1, H) == 0, -1e9)
-    a = torch.softmax(sc, dim=-1) * m
-    qw = torch.softmax(torch.norm(Q.transpose(1, 2).reshape(B, N, -1), dim=-1), dim=1)
-    agg = torch.softmax((a.sum(dim=1) * qw.unsqueeze(-1)).sum(dim=1), dim=-1)
+    agg = cand_attn_ref(qd, kd, mask, m, B, N, H, nh, hd)
     agg.backward(dagg.double())
     got = ops.cand_attn_weights_train(qp.cuda().view(-1), kp.cuda().view(-1), mask.cuda(), B, N, H, D, nh, p, seed, 0)
     close(got, agg.detach().float(), what='agg')

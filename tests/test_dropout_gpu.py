@@ -1,7 +1,8 @@
 """Training-mode dropout inside the token encoders on the MI355X.  torch's random stream cannot be matched (it differs between
 torch's own CPU and GPU generators), so the arithmetic is pinned differently: the masks the kernels use are read back through
 ``ops.dropout`` on all-ones tensors (same seed / site / element index) and fed to a plain torch fp64 statement of the post-LN
-encoder layer with explicit masks; forward and every gradient of the HIP layer must match that (1e-3, north star)."""
+encoder layer with explicit masks; forward and every gradient of the HIP layer must match that (1e-3, north star).
+The read-back masks themselves are pinned to a host statement of csrc/dropout.h by tests/test_dropout_kernels_gpu.py."""
 import math
 
 import pytest

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import wide_head_cases
+from dropout_cases import attn_ref          # the attention statement (shared with tests/test_dropout_kernels_gpu.py)
 from helpers import load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -44,15 +45,6 @@ def close(got, want, tol, what=''):
     print('%s: rel err %.3e (bound %.1e)' % (what, e, tol))
     assert e <= tol, '%s: rel err %.3e > %.1e' % (what, e, tol)
     return e
-
-
-def attn_ref(vals, n_seq, S, h, hd, scale, mask=None):
-    """vals [tok, 3, h, hd] -> (out [tok, h * hd], log2-domain lse [n_seq, h, S]) in vals' dtype."""
-    q, k, v = (vals[:, i].reshape(n_seq, S, h, hd).transpose(1, 2) for i in range(3))
-    a = (q * scale) @ k.transpose(-2, -1)
-    if mask is not None:
-        a = a.masked_fill(mask.view(n_seq, 1, 1, S) == 0, -1e9)
-    return (torch.softmax(a, dim=-1) @ v).transpose(1, 2).reshape(n_seq * S, h * hd), torch.logsumexp(a, dim=-1) / math.log(2.0)
 
 
 def packed(vals, hs, fill=0.0):
