@@ -35,7 +35,8 @@ typedef enum {
     LIME_OK = 0,
     LIME_ERR_BAD_ARG = -1,      /* null pointer, non-positive dimension, misaligned leading dimension */
     LIME_ERR_UNSUPPORTED = -2,  /* shape outside what the kernels are built for */
-    LIME_ERR_LAUNCH = -3        /* hipGetLastError() after the launch was not hipSuccess */
+    LIME_ERR_LAUNCH = -3,       /* hipGetLastError() after the launch was not hipSuccess */
+    LIME_NOT_APPLICABLE = 1     /* nothing was launched and nothing is wrong: the entry does not cover this call (lime_token_attention_vocab_f32) */
 } lime_status;
 
 int lime_abi_version(void);
@@ -424,6 +425,20 @@ int64_t lime_compact_batch_workspace(int32_t n);
 int lime_news_xin_f32(const float* title_blocks, int64_t ld_t, int32_t nblk_t, const float* body_blocks, int64_t ld_b, int32_t nblk_b,
                       const int32_t* title_row, const int32_t* body_row, const int32_t* n_news, float* xin, int64_t ldx, int32_t cap,
                       int32_t dim, void* stream);
+
+/*
+ * lime_token_attention_vocab_f32: the attention of the FIRST encoder layer over a per-vocabulary in_proj product.  The q / k / v
+ * row of token (seq * S + t) is qkv_vocab[ids[seq * S + t]] + pos_rows[t]: qkv_vocab is the [V, ld] table E W_in^T (q | k | v at
+ * columns 0, W, 2W with W = n_head * 32: heads padded to 32 columns), pos_rows the [S, ld] table PE W_in^T + b in the same layout,
+ * the sum one fp32 add per element -- bit for bit lime_token_attention_f32 over the materialised rows.  A padding token is id 0 at
+ * its position; ids are not range-checked.  min(*n_seq_dev, n_seq) sequences are computed when n_seq_dev is given.
+ * Split-product kernel only: returns LIME_NOT_APPLICABLE, launching nothing, under lime_set_split_gemm(0) or outside S in
+ * {32, 64, 128}, head_dim <= 32, ld % 4 == 0, ld >= 3 W, 16-byte aligned tables -- the caller then runs in_proj and
+ * lime_token_attention_rows_f32.
+ */
+int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
+                                   const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
+                                   int32_t head_dim, float scale, void* stream);
 
 /* lime_token_attention_rows_bf16: lime_token_attention_bf16 over compacted sequences (row_map / n_seq_dev as in
  * lime_token_attention_rows_f32); S in {32, 64, 128}, even head_dim. */

@@ -11,8 +11,8 @@
 //     and fed back as linear2's B operand IN REGISTER ORDER (four steps, one 32-wide hidden chunk each): the k index of an MFMA is
 //     only a summation label, so linear2's weight columns are packed in the order the hidden registers come out (the trick of
 //     ffn_bf16.hip).  No LDS round trip, no cross-lane movement for the hidden state.
-//   * weights: pre-split into three bf16 term images by lime_ffn_pack_sp (inside the forward: parameters may change between graph
-//     replays), every step's slot ONE contiguous block in the order of its LDS image (swizzled [row][64-byte] rows: conflict-free
+//   * weights: pre-split into three bf16 term images by lime_ffn_pack_sp (inside the forward, or -- CROWN's scoring path -- once per weight
+//     change, refilled in place before a graph replay: newsEncoders.WeightProducts), every step's slot ONE contiguous block in the order of its LDS image (swizzled [row][64-byte] rows: conflict-free
 //     ds_read_b128 fragments), copied by LDS-DMA into two ring slots: step s + 1 is issued during step s (one instruction per
 //     MFMA group), then one vmcnt(0) wait + barrier per step (the two-stage drain of gemm_sp_f32.hip).
 //   * epilogue: + b2 + the residual rows (fp32, re-read: L2 hits), LayerNorm (the four lanes that share a token meet through two

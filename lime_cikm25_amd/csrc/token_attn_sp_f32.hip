@@ -13,6 +13,11 @@
 //   * the MFMA's k index is a summation label: the 16 keys of a P V step sit in the accumulator layout's order (registers 8 s .. 8 s + 7
 //     of a lane = keys 16 s + {0..3, 8..11} + 4 half), and the V image stores its keys in that order (bits 2 and 3 of the key swapped).
 // The softmax (log2 domain, v_exp_f32) and the output transpose are those of token_attn_f32.hip.
+//
+// lime_token_attention_vocab_f32 (token_attn_sp_vocab_kernel): the first encoder layer over a per-vocabulary in_proj product.  The
+// operand row of token r = seq S + t is row ids[r] of a [V, ld] table (q | k | v at columns 0, W, 2W) plus row t of an [S, ld]
+// positional table: one fp32 add per element where the fragment is consumed (stash() for K / V, before the qscale multiply for Q), so
+// the result is bit for bit that of the dense kernel over the materialised rows.
 #include "common.h"
 #include "gemm_pp.h"
 #include "dev_helpers.h"
@@ -39,13 +44,18 @@ __device__ __forceinline__ void lds_fence() {          // (see token_attn_f32.hi
 }
 
 // NT: 32-token tiles per sequence (1, 2, 4); a group is 4 / NT (sequence, head) pairs = 128 key rows.  MAP: operand rows through
-// p.row_map (the compacted-sequence variant), the sequence count optionally from device memory.
-template <int NT, bool MAP>
-__global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) {
+// p.row_map (the compacted-sequence variant), the sequence count optionally from device memory.  VOC: p.row_map holds WORD IDS, the
+// rows of the [V, ld] product table p.q / p.k / p.v point into, and row t of ``pos`` ([S, ld], same column layout) is added.
+template <int NT, bool MAP, bool VOC>
+__device__ __forceinline__ void token_attn_sp_body(const SpAttnP p, const float* __restrict__ pos) {
     constexpr int G = 4 / NT, SP = NT * 32;
     constexpr int VP = SP + 8;                          // V^T image pitch in bf16 (2 S + 16 bytes: 16 x odd for S = 32, 64, 128)
     constexpr int K_TERM = 128 * KP, V_TERM = G * 32 * VP;
     constexpr bool PREFETCH = NT == 4;
+    // The prefetching instantiation holds K / V / Q of the next group (48 registers) across the MFMAs at 248 of its 256 registers:
+    // the next group's positional rows (48 more) are asked for behind the last P V product, where the 64 score registers are dead,
+    // and arrive under the output transpose and the barrier.
+    constexpr bool POS_LATE = PREFETCH;
     __shared__ __attribute__((aligned(16))) unsigned short Ks[3 * K_TERM];
     __shared__ __attribute__((aligned(16))) unsigned short Vs[3 * V_TERM];
     __shared__ __attribute__((aligned(16))) float Scr[4 * 32 * LDO];
@@ -66,6 +76,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
     const int c = (tid & 7) * 4, rg = tid >> 3;
     const int sg = (4 * rg) / SP, sr = (4 * rg) % SP;   // pair inside the group, first row inside the pair
     f32x4 kreg[4], vreg[4];
+    f32x4 kpos[VOC ? 4 : 1], vpos[VOC ? 4 : 1], qpos[VOC ? 4 : 1];     // VOC: the positional rows of kreg / vreg / the Q fragments
     auto fetch = [&](int group) {
         int pair = group * G + sg;
         pair = pair < n_pair ? pair : n_pair - 1;       // an invalid pair is clamped here and zero-filled in stash()
@@ -73,10 +84,28 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             long row = (long)seq * S + sr + i;
-            if constexpr (MAP) row = p.row_map[row];
+            if constexpr (MAP || VOC) row = p.row_map[row];
             const long off = row * p.ld + head * 32 + c;
             kreg[i] = *reinterpret_cast<const f32x4*>(p.k + off);
             vreg[i] = *reinterpret_cast<const f32x4*>(p.v + off);
+        }
+    };
+    // VOC: rows sr .. sr + 3 of the positional table, this thread's columns of the pair's head (L2 resident: S rows for all sequences).
+    // Addressed as a base that moves with the head + 32-bit byte offsets that do not (the host keeps S ld 4 below 2^31): what stays
+    // live across the loop is one register per row, not a pointer per load.
+    auto fetch_pos = [&](int group) {
+        if constexpr (VOC) {
+            int pair = group * G + sg;
+            pair = pair < n_pair ? pair : n_pair - 1;
+            const long kcol = p.k - p.q, vcol = p.v - p.q;      // column offsets of k / v in a table row (W, 2W)
+            const char* const kb = reinterpret_cast<const char*>(pos + kcol + (pair % p.n_head) * 32);
+            const char* const vb = reinterpret_cast<const char*>(pos + vcol + (pair % p.n_head) * 32);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned off = ((unsigned)(sr + i) * (unsigned)p.ld + (unsigned)c) * 4u;
+                kpos[i] = *reinterpret_cast<const f32x4*>(kb + off);
+                vpos[i] = *reinterpret_cast<const f32x4*>(vb + off);
+            }
         }
     };
     auto stash = [&](int group) {
@@ -85,6 +114,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             f32x4 kv = kreg[i];
+            if constexpr (VOC) kv = kv + kpos[i];
             if (dead) kv = f32x4{0.f, 0.f, 0.f, 0.f};
             u32x2 h, m, l;
             split_quad(kv[0], kv[1], kv[2], kv[3], h, m, l);
@@ -94,14 +124,15 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
             *reinterpret_cast<u32x2*>(d + 2 * K_TERM) = l;
         }
         // V^T: dim c + j, keys sr .. sr + 3 at position (sr with bits 2 and 3 swapped) -> 8 bytes per term
-        const int pos = (sr & ~12) | ((sr & 4) << 1) | ((sr & 8) >> 1);
+        const int vkey = (sr & ~12) | ((sr & 4) << 1) | ((sr & 8) >> 1);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float x0 = vreg[0][j], x1 = vreg[1][j], x2 = vreg[2][j], x3 = vreg[3][j];
+            if constexpr (VOC) { x0 += vpos[0][j]; x1 += vpos[1][j]; x2 += vpos[2][j]; x3 += vpos[3][j]; }
             if (dead) { x0 = 0.f; x1 = 0.f; x2 = 0.f; x3 = 0.f; }
             u32x2 h, m, l;
             split_quad(x0, x1, x2, x3, h, m, l);
-            unsigned short* const d = &Vs[(sg * 32 + c + j) * VP + pos];
+            unsigned short* const d = &Vs[(sg * 32 + c + j) * VP + vkey];
             *reinterpret_cast<u32x2*>(d) = h;
             *reinterpret_cast<u32x2*>(d + V_TERM) = m;
             *reinterpret_cast<u32x2*>(d + 2 * V_TERM) = l;
@@ -121,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
         pr = pr < n_pair ? pr : n_pair - 1;
         const int sq = pr / p.n_head, hh = pr - sq * p.n_head;
         long qrow = (long)sq * S + qt * 32 + fi;
-        if constexpr (MAP) qrow = p.row_map[qrow];
+        if constexpr (MAP || VOC) qrow = p.row_map[qrow];
         const float* const qsrc = p.q + qrow * p.ld + hh * 32 + 8 * fh;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -129,25 +160,45 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
             dst[2 * s + 1] = *reinterpret_cast<const f32x4*>(qsrc + 16 * s + 4);
         }
     };
+    auto q_pos = [&](int grp) {                         // VOC: the positional rows of q_rows' fragments
+        if constexpr (VOC) {
+            int pr = grp * G + g;
+            pr = pr < n_pair ? pr : n_pair - 1;
+            const char* const qb = reinterpret_cast<const char*>(pos + (pr % p.n_head) * 32);
+            const unsigned off = ((unsigned)(qt * 32 + fi) * (unsigned)p.ld + 8u * fh) * 4u;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                qpos[2 * s] = *reinterpret_cast<const f32x4*>(qb + off + 64 * s);
+                qpos[2 * s + 1] = *reinterpret_cast<const f32x4*>(qb + off + 64 * s + 16);
+            }
+        }
+    };
 
     int group = blockIdx.x;
-    if (PREFETCH) { fetch(group); q_rows(group, qnext); }
+    if (PREFETCH) { fetch(group); q_rows(group, qnext); fetch_pos(group); q_pos(group); }
     for (; group < n_group; group += gridDim.x) {
-        if (!PREFETCH) fetch(group);
+        if (!PREFETCH) { fetch(group); fetch_pos(group); }
         stash(group);
         lds_barrier();
         const int pair = group * G + g;
         const bool live = pair < n_pair;
         const int seq = live ? pair / p.n_head : 0, head = live ? pair - seq * p.n_head : 0;
-        if (!PREFETCH) { if (live) q_rows(group, qraw); }
+        if (!PREFETCH) { if (live) { q_rows(group, qraw); q_pos(group); } }
         else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) qraw[i] = qnext[i];
+        }
+        if constexpr (VOC) {
+            if (PREFETCH || live) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) qraw[i] = qraw[i] + qpos[i];
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (PREFETCH && group + (int)gridDim.x < n_group) {     // the next group's K / V / Q: in flight under the MFMAs
             fetch(group + gridDim.x);
             q_rows(group + gridDim.x, qnext);
+            if constexpr (VOC && !POS_LATE) { fetch_pos(group + gridDim.x); q_pos(group + gridDim.x); }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (live) {
@@ -193,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
             }
             sum += __shfl_xor(sum, 32);
             const float inv = 1.0f / sum;
-            if (p.drop.thresh != 0) {
+            if (!VOC && p.drop.thresh != 0) {                  // (the vocabulary rows are a scoring path: no dropout)
                 // nn.MultiheadAttention's dropout on the probabilities (newsEncoders.py:244-247, training mode): keep / (1 - p) goes
                 // onto the unnormalised e (the sum above is over all of them).  Registers 4 g .. 4 g + 3 of a tile are four consecutive
                 // keys: one hash each, element index (pair S + query) S + key as the backward regenerates it.
@@ -226,21 +277,47 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) 
                     o = split_mfma32(vs, ps, o);
                 }
             }
+            if constexpr (VOC && POS_LATE) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (group + (int)gridDim.x < n_group) { fetch_pos(group + gridDim.x); q_pos(group + gridDim.x); }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             // ---- transpose [head dim][query] -> [query][head dim] through the scratch, store whole head rows --------------
 #pragma unroll
             for (int r = 0; r < 16; ++r) scr[fi * LDO + (r & 3) + 8 * (r >> 2) + krow] = o[r] * inv;
             lds_fence();
             if (fi < p.hd) {
+                if constexpr (VOC) {                     // one running pointer: sixteen hoisted row offsets would not fit beside the
+                    float* op = p.out + ((long)seq * S + qt * 32 + fh) * p.ldo + head * p.hd + fi;      // positional registers
 #pragma unroll
-                for (int it = 0; it < 16; ++it) {
-                    const int row = it * 2 + fh;
-                    p.out[((long)seq * S + qt * 32 + row) * p.ldo + head * p.hd + fi] = scr[row * LDO + fi];
+                    for (int it = 0; it < 16; ++it) {
+                        *op = scr[(it * 2 + fh) * LDO + fi];
+                        op += 2 * p.ldo;
+                    }
+                } else {
+#pragma unroll
+                    for (int it = 0; it < 16; ++it) {
+                        const int row = it * 2 + fh;
+                        p.out[((long)seq * S + qt * 32 + row) * p.ldo + head * p.hd + fi] = scr[row * LDO + fi];
+                    }
                 }
             }
             lds_fence();
+        } else if constexpr (VOC && POS_LATE) {          // (G = 1: every group inside the loop is live; kept for the general case)
+            if (group + (int)gridDim.x < n_group) { fetch_pos(group + gridDim.x); q_pos(group + gridDim.x); }
         }
         lds_barrier();                                   // everyone is done with this group's LDS images
     }
+}
+
+template <int NT, bool MAP>
+__global__ __launch_bounds__(256, 2) void token_attn_sp_kernel(const SpAttnP p) {
+    token_attn_sp_body<NT, MAP, false>(p, nullptr);
+}
+
+template <int NT>
+__global__ __launch_bounds__(256, 2) void token_attn_sp_vocab_kernel(const SpAttnP p, const float* __restrict__ pos) {
+    token_attn_sp_body<NT, false, true>(p, pos);
 }
 
 // Long sequences (S = 256 or 512: the 512-token bodies of BASELINE configs[3]): a task is one (sequence, head) pair x one block of
@@ -417,6 +494,15 @@ int launch(SpAttnP p, hipStream_t s) {
     return lime_check_launch("token_attn_sp_kernel");
 }
 
+template <int NT>
+int launch_vocab(SpAttnP p, const float* pos, hipStream_t s) {
+    constexpr int G = 4 / NT;
+    p.n_group = (p.n_pair + G - 1) / G;
+    const long blocks = lime_persistent_grid(p.n_group, 2);
+    hipLaunchKernelGGL((token_attn_sp_vocab_kernel<NT>), dim3((unsigned)blocks), dim3(256), 0, s, p, pos);
+    return lime_check_launch("token_attn_sp_vocab_kernel");
+}
+
 }  // namespace
 
 // LIME_OK / error: launched; LIME_PP_NOT_APPLICABLE: the caller takes token_attn_f32.hip's kernels (masks, other lengths, unpadded
@@ -442,5 +528,31 @@ int lime_token_attention_sp(const float* q, const float* k, const float* v, long
         case 1: return launch<1>(p, s);
         case 2: return launch<2>(p, s);
         default: return launch<4>(p, s);
+    }
+}
+
+// Attention of the first encoder layer over a per-vocabulary in_proj product (see the header of this file and include/lime_hip.h).
+// LIME_PP_NOT_APPLICABLE (the caller keeps the in_proj + row-map path): the split product switched off, or a shape outside
+// S in {32, 64, 128}, head_dim <= 32, 16-byte aligned rows.
+extern "C" int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
+                                              const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
+                                              int32_t head_dim, float scale, void* stream) {
+    LIME_REQUIRE(qkv_vocab && pos_rows && ids && out, LIME_ERR_BAD_ARG, "lime_token_attention_vocab_f32: NULL pointer");
+    LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG,
+                 "lime_token_attention_vocab_f32: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", n_seq, S, n_head, head_dim);
+    LIME_REQUIRE(ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG, "lime_token_attention_vocab_f32: ldo smaller than n_head * head_dim");
+    if (!(lime_split_mode() & 1)) return LIME_PP_NOT_APPLICABLE;
+    const int64_t W = (int64_t)n_head * 32;
+    if (!(S == 32 || S == 64 || S == 128) || head_dim > 32 || ld % 4 != 0 || ld < 3 * W || ld > (1 << 21) ||     // 32-bit offsets into pos_rows
+        (((uintptr_t)qkv_vocab | (uintptr_t)pos_rows) % 16) != 0)
+        return LIME_PP_NOT_APPLICABLE;
+    if (n_seq == 0) return LIME_OK;
+    SpAttnP p{qkv_vocab, qkv_vocab + W, qkv_vocab + 2 * W, (long)ld, out, (long)ldo, n_seq, S, n_head, head_dim, scale, n_seq * n_head, 0,
+              ids, n_seq_dev, LimeDropout{0, 0, 1.f}};
+    hipStream_t s = (hipStream_t)stream;
+    switch (S / 32) {
+        case 1: return launch_vocab<1>(p, pos_rows, s);
+        case 2: return launch_vocab<2>(p, pos_rows, s);
+        default: return launch_vocab<4>(p, pos_rows, s);
     }
 }

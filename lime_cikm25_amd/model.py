@@ -93,7 +93,25 @@ class Model(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         self._graphs = {}                      # parameter storage moves: captured pointers are stale
+        self._products_key = None              # (the content encoder drops what it keeps across forwards in its own _apply)
         return super()._apply(fn, *args, **kwargs)
+
+    def weights_changed(self):
+        """Tell the model that parameter memory was written in a way torch does not record: an edit through ``p.data`` (it moves
+        neither ``p._version`` nor the address), or a kernel handed a raw pointer.  What is kept across scoring forwards
+        (``newsEncoders.WeightProducts``) is recomputed, in place, before the next one.  In-place torch ops on the parameters,
+        ``load_state_dict``, ``TrainStep`` and ``.to()`` need no such call."""
+        ops.note_param_write()
+
+    def _sync_weight_products(self):
+        """Before a scoring forward: bring the content encoder's weight products up to date (in place, on the current stream) and drop
+        the captured graphs if one of their buffers had to move or the forward changed between the two first-layer paths."""
+        enc = self.news_encoder.base_news_encoder
+        if hasattr(enc, 'products_key'):
+            key = enc.products_key()
+            if key != getattr(self, '_products_key', None):
+                self._products_key = key
+                self._graphs = {}
 
     def initialize(self):
         self.news_encoder.initialize()
@@ -125,6 +143,7 @@ class Model(nn.Module):
                                           news_title_entity=news_title_entity if self.reads_title_entity else None)
         if (self.use_graph and ops.PROFILE is None and user_category.is_cuda
                 and not torch.cuda.is_current_stream_capturing()):
+            self._sync_weight_products()       # (an eager forward brings them up to date where it uses them: CROWN.encode_flat)
             return self._forward_graphed(args)
         return self._forward_impl(*args)
 
@@ -146,6 +165,9 @@ class Model(nn.Module):
                 out = self._forward_impl(*static)
             entry = (graph, [static[i] for i in _USED], out)
             self._graphs[key] = entry
+            enc = self.news_encoder.base_news_encoder
+            if hasattr(enc, 'products_key'):
+                self._products_key = enc.products_key()      # (the warm-up may have built the weight products this graph reads)
         graph, static_used, out = entry
         keep = ops.multi_copy(list(zip(static_used, used)))          # one launch for all the inputs
         graph.replay()

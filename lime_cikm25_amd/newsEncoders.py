@@ -499,7 +499,9 @@ class LIME(nn.Module):
 
 class NewsEncoder(nn.Module):
     """newsEncoders.py:167-225: shared tables.  The word table is filled by the caller (``load_state_dict`` or
-    ``word_embedding.weight.data.copy_``); the reference unpickles it from the cwd at :173-174."""
+    ``word_embedding.weight.data.copy_``); the reference unpickles it from the cwd at :173-174.  An edit through ``.data`` moves
+    neither the tensor's version counter nor its address: after one, call ``Model.weights_changed()`` (or
+    ``ops.note_param_write()``) so that what CROWN keeps across forwards (``WeightProducts``) is recomputed."""
 
     def __init__(self, config):
         super().__init__()
@@ -611,8 +613,13 @@ class CategoryPredictor(nn.Module):
 #   m_rows, n_seq_dev   device counts of compact rows / sequences
 #   row_map             the first layer's attention looks every token's q / k / v row up through it
 #   seq_inv             pooled_out[s] = pooled rows[seq_inv[s]]
-_Rows = collections.namedtuple('_Rows', 'n_seq S a_ids res_ids w_in pew qkv c_ids m_tok m_rows n_seq_dev row_map seq_inv',
-                               defaults=(None,) * 7)
+# kept across forwards (``WeightProducts``; None: computed in this forward):
+#   ew                  the word table through the first in_proj, [V, 3W]: with it the first layer runs no in_proj, attention reads
+#                       token r's q / k / v as ew[res_ids[r]] + pew[r % S] (a padding token is id 0), and w_in / qkv / c_ids /
+#                       row_map are not needed
+#   ffn                 per layer, the (w1p, w2p) of ops.ffn_pack_sp
+_Rows = collections.namedtuple('_Rows', 'n_seq S a_ids res_ids w_in pew qkv c_ids m_tok m_rows n_seq_dev row_map seq_inv ew ffn',
+                               defaults=(None,) * 9)
 
 
 def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=False):
@@ -635,7 +642,11 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=Fal
     for li, layer in enumerate(transformer.layers):
         sa = layer.self_attn
         ln1 = (layer.norm1.weight, layer.norm1.bias)
-        if li == 0:
+        qkv = None
+        if li == 0 and r.ew is not None:
+            # (E W^T)[ids] + (PE W^T + b)[t] with both products kept across forwards: no in_proj, attention adds the two rows
+            res = dict(res=table, res_ids=r.res_ids, res_pe=pe, res_period=S)
+        elif li == 0:
             # (E[ids] + PE) W^T + b = E[ids] W^T + (PE W^T + b)[t]: the positional term is an [S, 3W] table added as a
             # periodic residual, so the A operand is a pure row gather (which the LDS-DMA GEMM can stage directly)
             qkv = ops.linear(table, r.w_in, None, a_ids=r.a_ids, res=r.pew, res_mod=S, n_alg=3 * E, c_ids=r.c_ids, m_dev=r.m_tok,
@@ -649,11 +660,15 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=Fal
             b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, hs) if hs != hd else sa.in_proj_bias
             qkv = ops.linear(x, w_in, b_in, n_alg=3 * E, **rows)
             res = dict(res=x)
-        q, k, v = qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:]
-        if r.row_map is None:
-            attn = ops.token_attention(q, k, v, n_seq, S, nhead, hd, scale, head_stride=hs)
+        if qkv is None:
+            attn = ops.token_attention_vocab(r.ew, r.pew, r.res_ids, r.n_seq_dev, n_seq, S, nhead, hd, scale)
+            if attn is None:
+                raise RuntimeError('lime_token_attention_vocab_f32 does not cover S = %d, head_dim = %d (vocab_qkv_applicable said it would)' % (S, hd))
+        elif r.row_map is None:
+            attn = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], n_seq, S, nhead, hd, scale, head_stride=hs)
         else:
-            attn = ops.token_attention_rows(q, k, v, r.row_map if li == 0 else _identity_rows(n_seq * S, table.device), r.n_seq_dev,
+            attn = ops.token_attention_rows(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:],
+                                            r.row_map if li == 0 else _identity_rows(n_seq * S, table.device), r.n_seq_dev,
                                             n_seq, S, nhead, hd, scale)
         x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, ln=ln1, ln_eps=layer.norm1.eps, **res, **rows)
         last = li == len(transformer.layers) - 1
@@ -661,7 +676,7 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=Fal
         ln2 = (layer.norm2.weight, layer.norm2.bias)
         if _ffn_sp_applicable(layer, x1):
             # linear1 + ReLU + linear2 + residual + norm2 (+ the 32-token block means of the last layer) in one launch
-            w1p, w2p = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
+            w1p, w2p = r.ffn[li] if r.ffn is not None else ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
             direct = S == 32 and (pooled is None or (pooled.data_ptr() % 16 == 0 and pooled.stride(0) % 4 == 0))
             ffn = lambda **kw: ops.encoder_ffn_sp(x1, w1p, w2p, layer.linear1.bias, layer.linear2.bias, ln2, layer.norm2.eps, **kw, **rows)
         else:
@@ -701,7 +716,7 @@ def encode_tokens(ids, table, pe, transformer, nhead, pooled_out=None):
     return _encode_layers(_Rows(M, S, flat, flat, w_in, ops.linear(pe[:S], w_in, b_in)), table, pe, transformer, nhead, pooled_out)
 
 
-def encode_tokens_compact(ids, table, pe, transformer, nhead, pooled_out):
+def encode_tokens_compact(ids, table, pe, transformer, nhead, pooled_out, products=None):
     """``encode_tokens(..., pooled_out)`` without the repetitions of a padded batch (csrc/compact.hip): the history slots of an
     impression are padded with the all-zero <PAD> news (corpus.py:476-477, dataset.py:105-141) and every text with the padding
     word behind it; the reference encodes them all (newsEncoders.py:311-321).
@@ -716,51 +731,70 @@ def encode_tokens_compact(ids, table, pe, transformer, nhead, pooled_out):
     Counts live in device memory (lime_linear_args.m_dev / n_seq_dev), buffers have their full-batch size: the forward stays one
     HIP graph.  Same kernels, same per-row arithmetic as the dense path; results differ from it only through the S padding rows
     coming from the small-M GEMM kernel (different k order, ~1e-7).  Returns None (the result is ``pooled_out``).
+
+    ``products``: this encoder's entry of ``WeightProducts.encoder`` (weight-only results kept across forwards: the word and
+    positional tables through the first in_proj, the packed feed-forward weights); the first layer then runs no in_proj at all.
     """
-    return compact_run(compact_prepare(ids, table, pe, transformer, nhead), table, pe, transformer, nhead, pooled_out)
+    return compact_run(compact_prepare(ids, table, pe, transformer, nhead, products), table, pe, transformer, nhead, pooled_out)
 
 
-def compact_prepare(ids, table, pe, transformer, nhead):
+def compact_prepare(ids, table, pe, transformer, nhead, products=None):
     """Everything of ``encode_tokens_compact`` in front of the big GEMMs -- index lists, padded in_proj weights, the positional
     table through in_proj, the S rows shared by the padding tokens: a dozen short launches that depend on the ids and the
     weights only, so the caller can run them on a side stream under another encoder's GEMMs."""
-    return compact_prepare_many([(ids, pe, transformer)], table, nhead)[0]
+    return compact_prepare_many([(ids, pe, transformer)], table, nhead, products=None if products is None else [products])[0]
 
 
-def compact_prepare_many(encoders, table, nhead, cmps=None):
+def compact_prepare_many(encoders, table, nhead, cmps=None, products=None):
     """``compact_prepare`` for several token encoders over one word table ((ids, pe, transformer) each): their positional tables go
     through in_proj in ONE grouped launch, their padding rows in another (independent, latency-bound GEMMs).  ``cmps``: the encoders'
-    index lists when the caller has them already (``ops.compact_batch``)."""
+    index lists when the caller has them already (``ops.compact_batch``).  ``products``: per encoder, its entry of
+    ``WeightProducts.encoder`` or None; an encoder whose entry holds ``ew`` needs the index lists only -- no padded weights, no
+    positional GEMM, no padding rows, no q / k / v buffer."""
     E = table.shape[1]
     hd = E // nhead
     W = nhead * 32
-    parts = []
+    products = products or [None] * len(encoders)
+    preps, parts = [None] * len(encoders), []
     for i, (ids, pe, transformer) in enumerate(encoders):
         M, S = ids.shape
         sa = transformer.layers[0].self_attn
         cap = (M + 1) * S
         cmp = ops.compact_sequences(ids) if cmps is None else cmps[i]           # pad rows live at qkv[cap : cap + S]
+        prod = products[i] or {}
+        if prod.get('ew') is not None:
+            preps[i] = (cmp, None, prod['pew'], None, prod)
+            continue
         w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)
         b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
         qkv = torch.empty((cap + S, 3 * W), dtype=torch.float32, device=ids.device)
-        parts.append((cmp, w_in, b_in, qkv, pe, S, cap))
-    pews = ops.linear_group([dict(a=pe[:S], w=w_in, bias=b_in) for (_, w_in, b_in, _, pe, S, _) in parts])   # [S, 3W]: positional term + bias
-    ops.linear_group([dict(a=table, w=w_in, bias=None, a_ids=_zero_ids(S, table.device), res=pew, res_mod=S, out=qkv[cap:])
-                      for (_, w_in, _, qkv, _, S, cap), pew in zip(parts, pews)])                             # the S padding rows
-    return [(cmp, w_in, pew, qkv) for (cmp, w_in, _, qkv, _, _, _), pew in zip(parts, pews)]
+        parts.append((cmp, w_in, b_in, qkv, pe, S, cap, i, prod))
+    if parts:
+        pews = ops.linear_group([dict(a=pe[:S], w=w_in, bias=b_in) for (_, w_in, b_in, _, pe, S, _, _, _) in parts])   # [S, 3W]: positional term + bias
+        ops.linear_group([dict(a=table, w=w_in, bias=None, a_ids=_zero_ids(S, table.device), res=pew, res_mod=S, out=qkv[cap:])
+                          for (_, w_in, _, qkv, _, S, cap, _, _), pew in zip(parts, pews)])                       # the S padding rows
+        for (cmp, w_in, _, qkv, _, _, _, i, prod), pew in zip(parts, pews):
+            preps[i] = (cmp, w_in, pew, qkv, prod)
+    return preps
 
 
 SP_FUSED_FFN = os.environ.get('LIME_SP_FUSED_FFN', '1') != '0'      # 0: the fp32 linear1 / linear2 as two lime_linear_f32 launches (A/B runs)
 
 
+def _ffn_sp_shape(layer, E):
+    """The shapes lime_encoder_ffn_sp / lime_ffn_pack_sp are built for: E <= 304 (E % 4 == 0), F a multiple of 128 up to 4096, biases."""
+    F = layer.linear1.out_features
+    return (E <= 304 and E % 4 == 0 and F % 128 == 0 and F <= 4096 and layer.linear1.bias is not None and
+            layer.linear2.bias is not None)
+
+
 def _ffn_sp_applicable(layer, x1):
     """lime_encoder_ffn_sp takes the fp32 feed-forward half where lime_linear_f32 would run both GEMMs as split products: the split
-    GEMM on, E <= 304 (E % 4 == 0), F a multiple of 128 up to 4096, biases present, 16-byte rows, and enough 128-row blocks that
-    linear1 is not left to the mid-M kernel (lime_linear_f32's fill rule)."""
+    GEMM on, a shape of ``_ffn_sp_shape``, 16-byte rows, and enough 128-row blocks that linear1 is not left to the mid-M kernel
+    (lime_linear_f32's fill rule)."""
     M, E = x1.shape
     F = layer.linear1.out_features
-    return (SP_FUSED_FFN and ops.split_gemm_on() and E <= 304 and E % 4 == 0 and F % 128 == 0 and F <= 4096 and
-            layer.linear1.bias is not None and layer.linear2.bias is not None and x1.stride(1) == 1 and x1.stride(0) % 4 == 0 and
+    return (SP_FUSED_FFN and ops.split_gemm_on() and _ffn_sp_shape(layer, E) and x1.stride(1) == 1 and x1.stride(0) % 4 == 0 and
             x1.data_ptr() % 16 == 0 and M >= 4096 and ((M + 127) // 128) * ((F + 255) // 256) >= 160)
 
 
@@ -775,9 +809,10 @@ def _identity_rows(n, device):
 def compact_run(prep, table, pe, transformer, nhead, pooled_out, blocks_only=False):
     """``encode_tokens_compact`` behind its preparation: the layer(s) over the compacted rows, ``pooled_out`` through ``seq_inv`` (or,
     ``blocks_only``, the compact block means returned: see ``_encode_layers``)."""
-    cmp, w_in, pew, qkv = prep
+    cmp, w_in, pew, qkv, prod = prep
     rows = _Rows(cmp.n_seq + 1, cmp.S, cmp.tok_ids, cmp.ids_c, w_in, pew, qkv, c_ids=cmp.tok_rows, m_tok=cmp.n_live_tokens,
-                 m_rows=cmp.n_rows, n_seq_dev=cmp.n_compact, row_map=cmp.row_map, seq_inv=cmp.seq_inv)
+                 m_rows=cmp.n_rows, n_seq_dev=cmp.n_compact, row_map=cmp.row_map, seq_inv=cmp.seq_inv, ew=prod.get('ew'),
+                 ffn=prod.get('ffn'))
     return _encode_layers(rows, table, pe, transformer, nhead, pooled_out, blocks_only)
 
 
@@ -929,6 +964,112 @@ def compact_applicable_bf16(ids, transformer, nhead, E):
             (E // nhead) % 2 == 0 and S in (32, 64, 128) and (M + 1) * S >= 4096 and ids.dtype == torch.int32 and ids.is_contiguous())
 
 
+# ---- weight-only results kept across forwards ------------------------------------------------------------------------------------
+# 0 (LIME_VOCAB_QKV=0): every forward derives what it needs from the weights itself -- in_proj over the batch's tokens, the
+# feed-forward weights packed per call -- as before ``WeightProducts`` (A/B runs)
+VOCAB_QKV = os.environ.get('LIME_VOCAB_QKV', '1') != '0'
+
+
+def weight_state(sources, writes):
+    """What a result derived from the tensors ``sources`` has to remember to know later whether it is still theirs: address, shape
+    and version counter of each (an in-place torch op, ``load_state_dict`` or ``copy_`` moves the version; ``.to()`` / a re-pointed
+    ``.data`` the address) and ``writes``, the count of writes torch does not see (``ops.PARAM_WRITES``: the native optimizer step
+    goes through raw pointers).  An edit through ``tensor.data`` moves none of the three: ``Model.weights_changed()``.  Host only."""
+    return tuple((t.data_ptr(), tuple(t.shape), t._version) for t in sources), int(writes)
+
+
+def weight_state_stale(recorded, current):
+    """The staleness rule of ``WeightProducts``: None while ``recorded`` (the ``weight_state`` a result was computed under) still
+    describes the sources, else why not -- 'never' (nothing recorded), 'moved' (a source's address or shape differs, or their number),
+    'version' (an in-place write torch counted), 'writes' (a raw-pointer write was announced).  Pure: two tuples in, a word out."""
+    if recorded is None:
+        return 'never'
+    (rec, rec_writes), (cur, cur_writes) = recorded, current
+    if len(rec) != len(cur) or any(a[:2] != b[:2] for a, b in zip(rec, cur)):
+        return 'moved'
+    if any(a[2] != b[2] for a, b in zip(rec, cur)):
+        return 'version'
+    return 'writes' if rec_writes != cur_writes else None
+
+
+def vocab_qkv_applicable(S, E, nhead):
+    """``lime_token_attention_vocab_f32`` covers the first layer of a token encoder over S-token sequences."""
+    return S in (32, 64, 128) and E % nhead == 0 and E // nhead <= 32 and E % 4 == 0
+
+
+_GENERATION = [0]
+
+
+def _next_generation():
+    """Process-wide, so that no two sets of product buffers ever carry one number: a module that lost its ``WeightProducts``
+    (``_apply``) and built another must not look unchanged to a holder of captured graphs."""
+    _GENERATION[0] += 1
+    return _GENERATION[0]
+
+
+class WeightProducts:
+    """What the fp32 token encoders of a CROWN module compute from weights alone, kept from one scoring forward to the next:
+
+      * per encoder, ``ew`` = E W_in^T over the WHOLE word table ([V, 3W], heads padded to 32 columns) and ``pew`` = PE W_in^T + b
+        ([S, 3W]): the first layer then runs no in_proj -- attention reads a token's q / k / v row as ew[id] + pew[t]
+        (ops.token_attention_vocab).  One forward of the flagship batch pushes 79k token rows through that GEMM against a
+        50k-row table, and a dev pass scores thousands of batches between two weight updates;
+      * per encoder and layer, the packed feed-forward weights of ``ops.ffn_pack_sp``.
+
+    ``refresh`` recomputes them IN PLACE when ``weight_state_stale`` says so: captured HIP graphs hold the buffers' addresses.
+    ``generation`` takes a new process-wide number whenever a buffer had to be (re)allocated or dropped instead; whoever holds graphs
+    drops them then."""
+
+    def __init__(self, budget):
+        self.state = None
+        self.budget = budget               # bytes of [V, 3W] products this set was built under
+        self.encoder = [{}, {}]            # title, body: dict(ew=, pew=, ffn=[(w1p, w2p) per layer]); 'ew' / 'pew' absent over the budget
+        self.generation = _next_generation()
+        self.refreshes = 0                 # recomputations so far (tests, logs)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for e in self.encoder for t in (e.get('ew'), e.get('pew')) if t is not None)
+
+    def _buffer(self, old, shape, dtype, device):
+        if old is not None and tuple(old.shape) == tuple(shape) and old.dtype == dtype and old.device == device:
+            return old
+        self.generation = _next_generation()
+        return torch.empty(shape, dtype=dtype, device=device)
+
+    def refresh(self, state, table, encoders, nhead, budget):
+        """Recompute everything on the current stream.  encoders: (positional table, transformer, S) for title and body."""
+        self.budget = budget
+        V, E = table.shape
+        hd, W, dev = E // nhead, nhead * 32, table.device
+        want = [vocab_qkv_applicable(S, E, nhead) for _, _, S in encoders]
+        if sum(V * 3 * W * 4 for w in want if w) > budget:
+            want = [False, False]
+        with torch.no_grad():
+            for ent, (pe, transformer, S), w in zip(self.encoder, encoders, want):
+                if w:
+                    sa = transformer.layers[0].self_attn
+                    w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)
+                    b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
+                    ent['ew'] = ops.linear(table, w_in, None, out=self._buffer(ent.get('ew'), (V, 3 * W), torch.float32, dev))
+                    ent['pew'] = ops.linear(pe[:S], w_in, b_in, out=self._buffer(ent.get('pew'), (S, 3 * W), torch.float32, dev))
+                elif 'ew' in ent:
+                    del ent['ew'], ent['pew']
+                    self.generation = _next_generation()
+                packs = ent.get('ffn') or [None] * len(transformer.layers)
+                for li, layer in enumerate(transformer.layers):
+                    if not _ffn_sp_shape(layer, E):
+                        packs[li] = None
+                        continue
+                    if packs[li] is None or packs[li][0].device != dev:
+                        self.generation = _next_generation()
+                        packs[li] = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
+                    else:
+                        ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight, out=packs[li])
+                ent['ffn'] = packs
+        self.state = state
+        self.refreshes += 1
+
+
 class CROWN(NewsEncoder):
     """newsEncoders.py:228-373: title/body transformer encoders, mean pooling, category-aware k-intent
     disentanglement, intent attention, title-body similarity, feature fusion.  -> [B, n, 900]."""
@@ -976,6 +1117,55 @@ class CROWN(NewsEncoder):
             nn.init.xavier_uniform_(intent_layer.weight)
             nn.init.zeros_(intent_layer.bias)
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
+
+    vocab_qkv_budget = 1 << 30     # bytes of [V, 3W] products a module may keep (both encoders: V <= 139k at 960 columns)
+
+    def _product_sources(self):
+        """Every tensor ``WeightProducts`` is computed from, in a fixed order."""
+        src = [self.word_embedding.weight]
+        for pos, tr in ((self.title_pos_encoder, self.title_transformer), (self.body_pos_encoder, self.body_transformer)):
+            sa = tr.layers[0].self_attn
+            src += [sa.in_proj_weight, sa.in_proj_bias, pos.pe]
+            for layer in tr.layers:
+                src += [layer.linear1.weight, layer.linear2.weight]
+        return src
+
+    def weight_products(self, create=True):
+        """The module's ``WeightProducts``, current for the weights as they are now, or None where the forward derives everything
+        itself: the switch ``VOCAB_QKV`` off, bf16, the split product off, a CPU module -- and a stream capture in progress with
+        stale products (nothing can be computed outside the graph then; the captured forward keeps its in_proj).  Stale products
+        are recomputed here, in place and on the current stream.  ``create``: build them when the module has none yet -- what
+        ``encode_flat`` asks for once it knows that a compacted call site takes them (they cost 2 V 960 floats and one GEMM over
+        the vocabulary per encoder); a holder of captured graphs passes False before a replay (``products_key``)."""
+        table = self.word_embedding.weight
+        if not VOCAB_QKV or self.compute_dtype == 'bf16' or not table.is_cuda or not ops.split_gemm_on():
+            return None
+        wp = getattr(self, '_products', None)
+        if wp is None and not create:
+            return None
+        state = weight_state(self._product_sources(), ops.PARAM_WRITES)
+        budget = self.vocab_qkv_budget
+        if wp is not None and weight_state_stale(wp.state, state) is None and wp.budget == budget:
+            return wp
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        if wp is None:
+            wp = self._products = WeightProducts(budget)
+        wp.refresh(state, table, ((self.title_pos_encoder.table(), self.title_transformer, self.max_title_length),
+                                  (self.body_pos_encoder.table(), self.body_transformer, self.max_body_length)), self.head_num, budget)
+        return wp
+
+    def products_key(self):
+        """Changes whenever a graph captured over ``encode_flat`` must not be replayed any more: a product buffer was allocated,
+        reallocated or dropped, or the forward switched between the products and the in-graph in_proj.  Brings existing products up
+        to date (in place) on the way; builds none."""
+        used = self.weight_products(create=False) is not None
+        wp = getattr(self, '_products', None)
+        return (None if wp is None else wp.generation, used)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._products = None                  # parameter storage moves (and maybe the device): nothing kept stays valid
+        return super()._apply(fn, *args, **kwargs)
 
     def _step_of(self, S, M, bf16):
         """News per pass of a token encoder over sequences of S tokens."""
@@ -1058,6 +1248,12 @@ class CROWN(NewsEncoder):
                     (content_text, self.body_pos_encoder, self.body_transformer, L))
         step_of = lambda S: self._step_of(S, M, bf16)
         one_pass = self._one_pass(title_text, content_text)
+        # what is kept across forwards (WeightProducts): built or refreshed here, in front of every branch, and only when a
+        # compacted call site below takes it
+        compacted = not bf16 and (one_pass or any(compact_applicable(ids[m0:min(M, m0 + step_of(S))], table, tr, self.head_num)
+                                                   for ids, _, tr, S in encoders for m0 in range(0, M, step_of(S))))
+        wp = self.weight_products() if compacted else None
+        prods = [None, None] if wp is None else wp.encoder
         if one_pass:
             # both encoders on the compacted path in one pass each: the body's preparation (index lists, padded weights, padding
             # rows: a dozen short launches) runs on branch 3 under the title encoder's GEMMs
@@ -1066,7 +1262,7 @@ class CROWN(NewsEncoder):
             side3.wait_stream(main)
             with torch.cuda.stream(side3):              # both encoders' preparation together: their small GEMMs share launches
                 prep_t, prep_b = compact_prepare_many([(t_ids, t_pos.table(), t_tr), (b_ids, b_pos.table(), b_tr)], table, self.head_num,
-                                                      cmps=(cmp_t, cmp_b) if dedup else None)
+                                                      cmps=(cmp_t, cmp_b) if dedup else None, products=prods)
             side1 = _side_stream(dev, 7)                   # branch 7: the (short) title chain beside the body chain
             side1.wait_stream(side3)
             with torch.cuda.stream(side1):
@@ -1096,7 +1292,7 @@ class CROWN(NewsEncoder):
                             continue
                         if compact_applicable(ids[m0:m1], table, tr, self.head_num):
                             encode_tokens_compact(ids[m0:m1], table, pos.table(), tr, self.head_num,
-                                                  pooled_out=xin[half * M + m0:half * M + m1, :E])
+                                                  pooled_out=xin[half * M + m0:half * M + m1, :E], products=prods[half])
                             continue
                         encode_tokens(ids[m0:m1], table, pos.table(), tr, self.head_num,
                                       pooled_out=xin[half * M + m0:half * M + m1, :E])                                   # :311-321

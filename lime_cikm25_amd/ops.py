@@ -20,6 +20,17 @@ from ._lib import LinearArgs, LIME_ACT, check
 PROFILE = None
 
 
+# Counts the writes to parameter memory that torch cannot see: a kernel handed a raw pointer (the native Adam step over the flat
+# bucket) moves no tensor's ``_version``.  Everything derived from weights and kept across forwards (newsEncoders.WeightProducts)
+# compares this counter as well; whoever adds such a writer calls ``note_param_write()``.
+PARAM_WRITES = 0
+
+
+def note_param_write():
+    global PARAM_WRITES
+    PARAM_WRITES += 1
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -301,6 +312,41 @@ def token_attention_rows(q, k, v, row_map, n_seq_dev, n_seq, S, n_head, head_dim
     _mat(out, 'out')
     check(lib.lime_token_attention_rows_f32(_p(q), _p(k), _p(v), _ld(q), _p(row_map), _p(n_seq_dev), _p(out), _ld(out), n_seq, S,
                                             n_head, head_dim, scale, _stream()), 'lime_token_attention_rows_f32')
+    return out
+
+
+NOT_APPLICABLE = 1            # LIME_NOT_APPLICABLE of include/lime_hip.h
+
+
+def token_attention_vocab(qkv_vocab, pos_rows, ids, n_seq_dev, n_seq, S, n_head, head_dim, scale, out=None):
+    """``lime_token_attention_vocab_f32``: the first encoder layer's attention over a per-vocabulary in_proj product.  qkv_vocab:
+    [V, 3 * n_head * 32] (q | k | v, heads 32 columns apart); pos_rows: [>= S, same columns]; ids: int32 [>= n_seq * S] word ids
+    (unchecked in [0, V)); the q / k / v row of token (seq, t) is ``qkv_vocab[ids[seq * S + t]] + pos_rows[t]``.  n_seq_dev as in
+    ``token_attention_rows``.  Returns ``out`` [n_seq * S, n_head * head_dim], or None when the entry does not cover the call (the
+    split product switched off, S outside {32, 64, 128}, head_dim > 32): nothing was launched, the caller keeps the in_proj path."""
+    lib = _lib.load()
+    _mat(qkv_vocab, 'qkv_vocab')
+    _mat(pos_rows, 'pos_rows')
+    W = n_head * 32
+    if qkv_vocab.shape[1] != 3 * W or pos_rows.shape[1] != 3 * W or _ld(qkv_vocab) != _ld(pos_rows):
+        raise ValueError('qkv_vocab and pos_rows must have 3 * n_head * 32 columns and one leading dimension')
+    if pos_rows.shape[0] < S:
+        raise ValueError('pos_rows must have at least S rows')
+    _vec(ids, 'ids', dtype=torch.int32)
+    if ids.numel() < n_seq * S:
+        raise ValueError('ids must cover n_seq * S tokens')
+    if n_seq_dev is not None:
+        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
+    if out is None:
+        out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=qkv_vocab.device)
+    _mat(out, 'out')
+    if out.shape[0] != n_seq * S or out.shape[1] != n_head * head_dim:
+        raise ValueError('out must be [n_seq * S, n_head * head_dim]')
+    st = lib.lime_token_attention_vocab_f32(_p(qkv_vocab), _ld(qkv_vocab), _p(pos_rows), _p(ids), _p(n_seq_dev), _p(out), _ld(out), n_seq, S,
+                                            n_head, head_dim, scale, _stream())
+    if st == NOT_APPLICABLE:
+        return None
+    check(st, 'lime_token_attention_vocab_f32')
     return out
 
 
@@ -958,16 +1004,21 @@ def ffn_pack_bf16(w1, b1, w2):
     return w1p, w2p
 
 
-def ffn_pack_sp(w1, w2):
-    """``lime_ffn_pack_sp``: linear1 / linear2 weights (fp32 [F, E], [E, F]) -> the split (three bf16 terms) operands of ``encoder_ffn_sp``."""
+def ffn_pack_sp(w1, w2, out=None):
+    """``lime_ffn_pack_sp``: linear1 / linear2 weights (fp32 [F, E], [E, F]) -> the split (three bf16 terms) operands of ``encoder_ffn_sp``.
+    ``out``: a (w1p, w2p) pair of an earlier call for the same shapes, refilled in place."""
     lib = _lib.load()
     _mat(w1, 'w1')
     _mat(w2, 'w2')
     F, E = w1.shape
     if tuple(w2.shape) != (E, F):
         raise ValueError('w2 must be [%d, %d]' % (E, F))
-    w1p = torch.empty(int(lib.lime_ffn_pack_sp_size(F, 0)), dtype=torch.bfloat16, device=w1.device)
-    w2p = torch.empty(int(lib.lime_ffn_pack_sp_size(F, 1)), dtype=torch.bfloat16, device=w1.device)
+    n1, n2 = int(lib.lime_ffn_pack_sp_size(F, 0)), int(lib.lime_ffn_pack_sp_size(F, 1))
+    if out is not None:
+        w1p, w2p = _vec(out[0], 'w1p', n1, dtype=torch.bfloat16), _vec(out[1], 'w2p', n2, dtype=torch.bfloat16)
+    else:
+        w1p = torch.empty(n1, dtype=torch.bfloat16, device=w1.device)
+        w2p = torch.empty(n2, dtype=torch.bfloat16, device=w1.device)
     check(lib.lime_ffn_pack_sp(_p(w1), _ld(w1), _p(w2), _ld(w2), E, F, _p(w1p), _p(w2p), _stream()), 'lime_ffn_pack_sp')
     return w1p, w2p
 
@@ -1573,6 +1624,7 @@ def grad_clip_coef(g, max_norm):
 
 def adam_step_(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=None):
     lib = _lib.load()
+    note_param_write()                             # p is written through its address: no tensor's _version moves
     n = p.numel()
     for t, name in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
         _vec(t, name, n)

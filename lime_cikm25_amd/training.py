@@ -1166,6 +1166,7 @@ class TrainStep:
                 p.grad = self.grad[off:off + n].view(p.shape)
                 off += align(n)
         distributed.broadcast_(self.flat, 0, process_group)      # replicas start from rank 0's parameters (as under DDP)
+        ops.note_param_write()                 # the parameters were written through the bucket, not through themselves
         if hasattr(model, '_graphs'):
             model._graphs = {}                  # captured scoring graphs hold the parameters' old addresses
         self.step_count = 0
