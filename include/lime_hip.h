@@ -41,6 +41,8 @@ typedef enum {
 
 int lime_abi_version(void);
 const char* lime_last_error_string(void);
+/* compute units of the current device as the library's launch geometry counts them (persistent grids: one workgroup per CU) */
+int64_t lime_device_cus(void);
 
 /* activation applied after bias (+ residual) */
 enum { LIME_ACT_NONE = 0, LIME_ACT_RELU = 1, LIME_ACT_TANH = 2, LIME_ACT_SIGMOID = 3,
@@ -253,6 +255,37 @@ int lime_encoder_ffn_sp(const lime_ffn_sp_args* args, void* stream);
 int64_t lime_ffn_pack_sp_size(int32_t F, int32_t which);
 int lime_ffn_pack_sp(const float* w1, int64_t ldw1, const float* w2, int64_t ldw2, int32_t E, int32_t F, uint16_t* w1p, uint16_t* w2p,
                      void* stream);
+
+/*
+ * lime_encoder_oproj_sp: out_proj + residual + norm1 of an fp32 encoder layer in one launch, split products on the bf16 matrix
+ * cores (the arithmetic of lime_encoder_ffn_sp's linear2 half):
+ *     x1 = LayerNorm(residual + attn Wo^T + bo)           out = x1 (fp32 rows [M, ldo]; only the E real columns are written)
+ * attn: fp32 [M, lda], 16-byte aligned rows (the attention output).  wp: Wo as lime_oproj_pack_sp lays it out.  The residual of
+ * row r is res[r] (res_ids NULL: res is [M, ldr]) or res[res_ids[r]] + res_pe[r % res_period] (res is the [V, ldr] word table,
+ * ids unchecked in [0, V); res_pe NULL: no positional term).  Rows at or beyond the row count are neither read nor written.
+ * Built for E <= 304 and E % 4 == 0; anything else returns LIME_ERR_UNSUPPORTED (use lime_linear_f32).  m_dev: optional device row
+ * count, as in lime_linear_args.
+ */
+typedef struct {
+    const float* attn;    int64_t lda;
+    const uint16_t* wp;                     /* lime_oproj_pack_sp's output (opaque: the kernel's weight-ring slots); 16-byte aligned */
+    const float* bias;                      /* fp32 [E] */
+    const float* res;     int64_t ldr;      /* 16-byte aligned rows */
+    const int32_t* res_ids;                 /* int32 [M] or NULL */
+    const float* res_pe;  int64_t ldr_pe;   /* [>= res_period, ldr_pe] or NULL (with res_ids only) */
+    int32_t res_period;
+    float ln_eps;
+    const float* ln_gamma; const float* ln_beta;                   /* fp32 [E] */
+    float* out;           int64_t ldo;
+    int32_t M, E;
+    const int32_t* m_dev;
+} lime_oproj_sp_args;
+
+int lime_encoder_oproj_sp(const lime_oproj_sp_args* args, void* stream);
+
+/* w fp32 [E, E] (ld ldw) -> wp: a bf16 buffer of lime_oproj_pack_sp_size() elements (10 * 3 * 304 * 32). */
+int64_t lime_oproj_pack_sp_size(void);
+int lime_oproj_pack_sp(const float* w, int64_t ldw, int32_t E, uint16_t* wp, void* stream);
 
 /*
  * lime_encoder_block_bf16: everything of an encoder layer behind the attention core in one launch

@@ -96,6 +96,24 @@ class FfnSpArgs(ctypes.Structure):
     ]
 
 
+class OprojSpArgs(ctypes.Structure):
+    """lime_oproj_sp_args of include/lime_hip.h (same field order)."""
+    _fields_ = [
+        ('attn', c_void_p), ('lda', c_int64),
+        ('wp', c_void_p),
+        ('bias', c_void_p),
+        ('res', c_void_p), ('ldr', c_int64),
+        ('res_ids', c_void_p),
+        ('res_pe', c_void_p), ('ldr_pe', c_int64),
+        ('res_period', c_int32),
+        ('ln_eps', c_float),
+        ('ln_gamma', c_void_p), ('ln_beta', c_void_p),
+        ('out', c_void_p), ('ldo', c_int64),
+        ('M', c_int32), ('E', c_int32),
+        ('m_dev', c_void_p),
+    ]
+
+
 class EncoderBlockBf16Args(ctypes.Structure):
     """lime_encoder_block_bf16_args of include/lime_hip.h (same field order)."""
     _fields_ = [
@@ -175,6 +193,7 @@ class ConvPoolArgs(ctypes.Structure):
 SIGNATURES = {
     'lime_abi_version': (c_int32, []),
     'lime_last_error_string': (c_char_p, []),
+    'lime_device_cus': (c_int64, []),
     'lime_last_linear_kernel': (c_char_p, []),
     'lime_set_split_gemm': (c_int32, [c_int32]),
     'lime_linear_f32': (c_int32, [POINTER(LinearArgs), c_void_p]),
@@ -250,6 +269,9 @@ SIGNATURES = {
     'lime_encoder_ffn_sp': (c_int32, [ctypes.POINTER(FfnSpArgs), c_void_p]),
     'lime_ffn_pack_sp': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     'lime_ffn_pack_sp_size': (c_int64, [c_int32, c_int32]),
+    'lime_encoder_oproj_sp': (c_int32, [ctypes.POINTER(OprojSpArgs), c_void_p]),
+    'lime_oproj_pack_sp': (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    'lime_oproj_pack_sp_size': (c_int64, []),
     'lime_oproj_pack_bf16_size': (c_int64, []),
     'lime_oproj_pack_bf16': (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     'lime_inproj_bf16': (c_int32, [ctypes.POINTER(InprojBf16Args), c_void_p]),

@@ -29,6 +29,7 @@ int lime_num_cus() {
     return n;
 }
 
+extern "C" int64_t lime_device_cus(void) { return lime_num_cus(); }
 extern "C" const char* lime_last_linear_kernel(void) { return g_kernel; }
 extern "C" int lime_abi_version(void) { return LIME_ABI_VERSION; }
 extern "C" const char* lime_last_error_string(void) { return g_err; }

@@ -618,8 +618,9 @@ class CategoryPredictor(nn.Module):
 #                       token r's q / k / v as ew[res_ids[r]] + pew[r % S] (a padding token is id 0), and w_in / qkv / c_ids /
 #                       row_map are not needed
 #   ffn                 per layer, the (w1p, w2p) of ops.ffn_pack_sp
-_Rows = collections.namedtuple('_Rows', 'n_seq S a_ids res_ids w_in pew qkv c_ids m_tok m_rows n_seq_dev row_map seq_inv ew ffn',
-                               defaults=(None,) * 9)
+#   oproj               per layer, the packed out_proj weight of ops.oproj_pack_sp
+_Rows = collections.namedtuple('_Rows', 'n_seq S a_ids res_ids w_in pew qkv c_ids m_tok m_rows n_seq_dev row_map seq_inv ew ffn oproj',
+                               defaults=(None,) * 10)
 
 
 def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=False):
@@ -670,7 +671,12 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=Fal
             attn = ops.token_attention_rows(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:],
                                             r.row_map if li == 0 else _identity_rows(n_seq * S, table.device), r.n_seq_dev,
                                             n_seq, S, nhead, hd, scale)
-        x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, ln=ln1, ln_eps=layer.norm1.eps, **res, **rows)
+        if _oproj_sp_applicable(sa, attn, res):
+            # out_proj + residual + norm1 as split products in one token-stationary launch
+            wop = r.oproj[li] if r.oproj is not None and r.oproj[li] is not None else ops.oproj_pack_sp(sa.out_proj.weight)
+            x1 = ops.encoder_oproj_sp(attn, wop, sa.out_proj.bias, ln1, layer.norm1.eps, **res, **rows)
+        else:
+            x1 = ops.linear(attn, sa.out_proj.weight, sa.out_proj.bias, ln=ln1, ln_eps=layer.norm1.eps, **res, **rows)
         last = li == len(transformer.layers) - 1
         pool = last and (pooled_out is not None or blocks_only) and transformer.norm is None and S % 32 == 0 and n_seq * S >= 4096
         ln2 = (layer.norm2.weight, layer.norm2.bias)
@@ -798,6 +804,25 @@ def _ffn_sp_applicable(layer, x1):
             x1.data_ptr() % 16 == 0 and M >= 4096 and ((M + 127) // 128) * ((F + 255) // 256) >= 160)
 
 
+SP_OPROJ = os.environ.get('LIME_SP_OPROJ', '1') != '0'      # 0: the fp32 out_proj + norm1 stays with lime_linear_f32 (A/B runs)
+
+
+def oproj_sp_rule(on, split_on, M, E, has_bias, aligned):
+    """The rule of ``_oproj_sp_applicable`` as a pure function: the switch and the split GEMM on, E within the build (E <= 304,
+    E % 4 == 0), a bias, 16-byte rows, at least 4096 rows and 160 tiles of 128 rows -- below that a persistent grid of one workgroup
+    per CU leaves too much of the chip idle and lime_linear_f32's own fill rules choose better."""
+    return bool(on and split_on and 0 < E <= 304 and E % 4 == 0 and has_bias and aligned and M >= 4096 and (M + 127) // 128 >= 160)
+
+
+def _oproj_sp_applicable(sa, attn, res):
+    """lime_encoder_oproj_sp takes out_proj + residual + norm1 of the fp32 scoring layers (compacted or dense rows, every layer)
+    under ``oproj_sp_rule``; ``res``: the residual arguments ``_encode_layers`` would hand ``ops.linear``."""
+    M, E = attn.shape
+    ok16 = lambda t: t is None or (t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+    return oproj_sp_rule(SP_OPROJ, ops.split_gemm_on(), M, E, sa.out_proj.bias is not None,
+                         ok16(attn) and ok16(res['res']) and ok16(res.get('res_pe')))
+
+
 _IDENT = {}
 
 
@@ -812,7 +837,7 @@ def compact_run(prep, table, pe, transformer, nhead, pooled_out, blocks_only=Fal
     cmp, w_in, pew, qkv, prod = prep
     rows = _Rows(cmp.n_seq + 1, cmp.S, cmp.tok_ids, cmp.ids_c, w_in, pew, qkv, c_ids=cmp.tok_rows, m_tok=cmp.n_live_tokens,
                  m_rows=cmp.n_rows, n_seq_dev=cmp.n_compact, row_map=cmp.row_map, seq_inv=cmp.seq_inv, ew=prod.get('ew'),
-                 ffn=prod.get('ffn'))
+                 ffn=prod.get('ffn'), oproj=prod.get('oproj'))
     return _encode_layers(rows, table, pe, transformer, nhead, pooled_out, blocks_only)
 
 
@@ -1014,7 +1039,8 @@ class WeightProducts:
         ([S, 3W]): the first layer then runs no in_proj -- attention reads a token's q / k / v row as ew[id] + pew[t]
         (ops.token_attention_vocab).  One forward of the flagship batch pushes 79k token rows through that GEMM against a
         50k-row table, and a dev pass scores thousands of batches between two weight updates;
-      * per encoder and layer, the packed feed-forward weights of ``ops.ffn_pack_sp``.
+      * per encoder and layer, the packed feed-forward weights of ``ops.ffn_pack_sp`` and the packed out_proj weight of
+        ``ops.oproj_pack_sp``.
 
     ``refresh`` recomputes them IN PLACE when ``weight_state_stale`` says so: captured HIP graphs hold the buffers' addresses.
     ``generation`` takes a new process-wide number whenever a buffer had to be (re)allocated or dropped instead; whoever holds graphs
@@ -1023,7 +1049,7 @@ class WeightProducts:
     def __init__(self, budget):
         self.state = None
         self.budget = budget               # bytes of [V, 3W] products this set was built under
-        self.encoder = [{}, {}]            # title, body: dict(ew=, pew=, ffn=[(w1p, w2p) per layer]); 'ew' / 'pew' absent over the budget
+        self.encoder = [{}, {}]            # title, body: dict(ew=, pew=, ffn=[(w1p, w2p) per layer], oproj=[wp per layer]); 'ew' / 'pew' absent over the budget
         self.generation = _next_generation()
         self.refreshes = 0                 # recomputations so far (tests, logs)
 
@@ -1066,6 +1092,16 @@ class WeightProducts:
                     else:
                         ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight, out=packs[li])
                 ent['ffn'] = packs
+                wops = ent.get('oproj') or [None] * len(transformer.layers)
+                for li, layer in enumerate(transformer.layers):
+                    if not (E <= 304 and E % 4 == 0):
+                        wops[li] = None
+                    elif wops[li] is None or wops[li].device != dev:
+                        self.generation = _next_generation()
+                        wops[li] = ops.oproj_pack_sp(layer.self_attn.out_proj.weight)
+                    else:
+                        ops.oproj_pack_sp(layer.self_attn.out_proj.weight, out=wops[li])
+                ent['oproj'] = wops
         self.state = state
         self.refreshes += 1
 
@@ -1127,7 +1163,7 @@ class CROWN(NewsEncoder):
             sa = tr.layers[0].self_attn
             src += [sa.in_proj_weight, sa.in_proj_bias, pos.pe]
             for layer in tr.layers:
-                src += [layer.linear1.weight, layer.linear2.weight]
+                src += [layer.linear1.weight, layer.linear2.weight, layer.self_attn.out_proj.weight]
         return src
 
     def weight_products(self, create=True):

@@ -1067,6 +1067,75 @@ def encoder_ffn_sp(x, w1p, w2p, b1, b2, ln, ln_eps, pool32=False, m_dev=None, ou
     return out
 
 
+def device_cus():
+    """``lime_device_cus``: the CU count the library sizes its persistent grids by."""
+    return int(_lib.load().lime_device_cus())
+
+
+def oproj_pack_sp(w, out=None):
+    """``lime_oproj_pack_sp``: the out_proj weight (fp32 [E, E]) -> the split (three bf16 terms) operand of ``encoder_oproj_sp``.
+    ``out``: the buffer of an earlier call, refilled in place."""
+    lib = _lib.load()
+    _mat(w, 'w')
+    E = w.shape[0]
+    if w.shape[1] != E:
+        raise ValueError('w must be square, got %s' % (tuple(w.shape),))
+    n = int(lib.lime_oproj_pack_sp_size())
+    wp = _vec(out, 'wp', n, dtype=torch.bfloat16) if out is not None else torch.empty(n, dtype=torch.bfloat16, device=w.device)
+    check(lib.lime_oproj_pack_sp(_p(w), _ld(w), E, _p(wp), _stream()), 'lime_oproj_pack_sp')
+    return wp
+
+
+def encoder_oproj_sp(attn, wp, bias, ln, ln_eps, res, res_ids=None, res_pe=None, res_period=0, m_dev=None, out=None):
+    """``lime_encoder_oproj_sp``: LayerNorm(residual + attn Wo^T + bias) in one launch, fp32-level split products; attn fp32 [M, E].
+    The residual of row r is ``res[r]`` or, with ``res_ids`` (int32 [M]), ``res[res_ids[r]] + res_pe[r % res_period]``."""
+    lib = _lib.load()
+    _mat(attn, 'attn')
+    M, E = attn.shape
+    _vec(wp, 'wp', int(lib.lime_oproj_pack_sp_size()), dtype=torch.bfloat16)
+    _mat(res, 'res')
+    if res.shape[1] != E:
+        raise ValueError('res must have E=%d columns' % E)
+    if out is None:
+        out = torch.empty((M, E), dtype=torch.float32, device=attn.device)
+    _mat(out, 'out')
+    if tuple(out.shape) != (M, E):
+        raise ValueError('out must be [%d, %d]' % (M, E))
+    args = _lib.OprojSpArgs()
+    args.attn, args.lda = attn.data_ptr(), _ld(attn)
+    args.wp = wp.data_ptr()
+    args.bias = _vec(bias, 'bias', E).data_ptr()
+    args.res, args.ldr = res.data_ptr(), _ld(res)
+    if res_ids is not None:
+        args.res_ids = _vec(res_ids, 'res_ids', M, dtype=torch.int32).data_ptr()
+        if res_pe is not None:
+            _mat(res_pe, 'res_pe')
+            if res_pe.shape[1] != E or res_pe.shape[0] < res_period or res_period <= 0:
+                raise ValueError('res_pe must be [>=res_period, E]')
+            args.res_pe, args.ldr_pe, args.res_period = res_pe.data_ptr(), _ld(res_pe), res_period
+    elif res_pe is not None:
+        raise ValueError('res_pe needs res_ids')
+    elif res.shape[0] < M:
+        raise ValueError('res has %d rows, needs >= %d' % (res.shape[0], M))
+    args.ln_gamma = _vec(ln[0], 'ln gamma', E).data_ptr()
+    args.ln_beta = _vec(ln[1], 'ln beta', E).data_ptr()
+    args.ln_eps = ln_eps
+    args.out, args.ldo = out.data_ptr(), _ld(out)
+    args.M, args.E = M, E
+    if m_dev is not None:
+        args.m_dev = _vec(m_dev, 'm_dev', 1, dtype=torch.int32).data_ptr()
+    if PROFILE is not None:                        # bench.py: as one GEMM of 2 M E E FLOPs
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(lib.lime_encoder_oproj_sp(ctypes.byref(args), _stream()), 'lime_encoder_oproj_sp')
+        e1.record()
+        m_run = M if m_dev is None else min(M, int(m_dev.item()))
+        PROFILE.append(('oproj_sp_kernel', m_run, E, E, E, e0, e1))
+        return out
+    check(lib.lime_encoder_oproj_sp(ctypes.byref(args), _stream()), 'lime_encoder_oproj_sp')
+    return out
+
+
 def split_gemm_on():
     """True while lime_linear_f32 routes the big-M GEMMs through the split-product kernel (``set_split_gemm``)."""
     return bool(_lib.load().lime_set_split_gemm(-1) & 1)
