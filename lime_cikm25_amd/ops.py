@@ -315,7 +315,7 @@ def token_attention_rows(q, k, v, row_map, n_seq_dev, n_seq, S, n_head, head_dim
     return out
 
 
-NOT_APPLICABLE = 1            # LIME_NOT_APPLICABLE of include/lime_hip.h
+NOT_APPLICABLE = _lib.CONSTANTS['LIME_NOT_APPLICABLE']
 
 
 def token_attention_vocab(qkv_vocab, pos_rows, ids, n_seq_dev, n_seq, S, n_head, head_dim, scale, out=None):
@@ -565,7 +565,7 @@ def gather_rows(idx, table, out):
 # default stays until it is flipped on purpose; LIME_FUSED_OCCURRENCE=1 selects the kernel for the whole process.  'add' and 'gated'
 # have the kernel only.
 FUSED_OCCURRENCE = os.environ.get('LIME_FUSED_OCCURRENCE', '0') == '1'
-OCC_MODES = {'concat': 0, 'add': 1, 'gated': 2}             # LIME_OCC_* of include/lime_hip.h
+OCC_MODES = {'concat': _lib.CONSTANTS['LIME_OCC_CONCAT'], 'add': _lib.CONSTANTS['LIME_OCC_ADD'], 'gated': _lib.CONSTANTS['LIME_OCC_GATED']}
 
 
 def cached_occurrence(mode, idx, freshness, lifetime, A, T, P=None, Q=None, cuts=None, out=None):

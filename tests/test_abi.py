@@ -3,13 +3,17 @@ arguments before touching the GPU.  No compute calls here (CPU only)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
 from lime_cikm25_amd import _lib
+from lime_cikm25_amd._header import Header
 from lime_cikm25_amd.build import build_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'lime_hip.h')
 
 
 @pytest.fixture(scope='module')
@@ -19,7 +23,7 @@ def lib():
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, 'include', 'lime_hip.h')).read()
+    text = open(HEADER).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     return sorted(set(re.findall(r'\b(lime_[a-z0-9_]+)\s*\(', text)))
 
@@ -33,53 +37,140 @@ def test_header_and_binding_agree(lib):
 
 
 def test_abi_version(lib):
-    header = open(os.path.join(ROOT, 'include', 'lime_hip.h')).read()
+    header = open(HEADER).read()
     declared = int(re.search(r'#define\s+LIME_ABI_VERSION\s+(\d+)', header).group(1))
     assert lib.lime_abi_version() == _lib.ABI_VERSION == declared
 
 
-def _c_layout(tmp_path):
-    """sizeof / offsetof of lime_linear_args as gcc sees the header."""
-    import shutil
-    import subprocess
+def _gcc(tmp_path, source, *flags):
     if shutil.which('gcc') is None:
         pytest.skip('no gcc')
-    src = tmp_path / 'sz.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu", '
-                   'sizeof(lime_linear_args), offsetof(lime_linear_args, c), offsetof(lime_linear_args, act), '
-                   'offsetof(lime_linear_args, ln_eps)); return 0;}' % os.path.join(ROOT, 'include', 'lime_hip.h'))
-    exe = tmp_path / 'sz'
-    subprocess.run(['gcc', '-o', str(exe), str(src)], check=True)
-    return tuple(int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
+    src = tmp_path / 'abi.c'
+    src.write_text(source)
+    return subprocess.run(['gcc', '-std=c11', '-Werror', *flags, str(src)], capture_output=True, text=True, cwd=tmp_path)
 
 
-def test_linear_args_layout_matches_header(tmp_path):
-    # the ctypes mirror must have exactly the layout the C compiler gives the struct in include/lime_hip.h
-    LAYOUT = _c_layout(tmp_path)
-    assert ctypes.sizeof(_lib.LinearArgs) == LAYOUT[0]
-    assert (_lib.LinearArgs.c.offset, _lib.LinearArgs.act.offset, _lib.LinearArgs.ln_eps.offset) == LAYOUT[1:]
+def test_every_struct_matches_the_header_field_by_field(tmp_path):
+    """sizeof, and the offset and size of EVERY field, of every struct the reader found against what gcc gives it."""
+    assert len(_lib.STRUCTS) >= 12
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void) {']
+    for cname, st in _lib.STRUCTS.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        lines += ['printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (cname, f, cname, f, cname, f) for f, _ in st._fields_]
+    r = _gcc(tmp_path, '\n'.join(lines + ['return 0; }']), '-o', 'abi')
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = subprocess.run([str(tmp_path / 'abi')], check=True, capture_output=True, text=True).stdout.splitlines()
+    want = []
+    for cname, st in _lib.STRUCTS.items():
+        want.append('%s %d' % (cname, ctypes.sizeof(st)))
+        want += ['%s.%s %d %d' % (cname, f, getattr(st, f).offset, getattr(st, f).size) for f, _ in st._fields_]
+    assert got == want
 
 
-@pytest.mark.parametrize('cname,cls', [('lime_linear_args', 'LinearArgs'), ('lime_linear_plan', 'LinearPlan'), ('lime_linear_bf16_args', 'LinearBf16Args'),
-                                        ('lime_ffn_bf16_args', 'FfnBf16Args'), ('lime_encoder_block_bf16_args', 'EncoderBlockBf16Args'),
-                                        ('lime_inproj_bf16_args', 'InprojBf16Args')])
-def test_every_args_struct_matches_the_header_field_by_field(tmp_path, cname, cls):
-    """sizeof and the offset of EVERY field of the ctypes mirror against what gcc gives the struct of include/lime_hip.h."""
-    import shutil
-    import subprocess
-    if shutil.which('gcc') is None:
-        pytest.skip('no gcc')
-    st = getattr(_lib, cls)
-    fields = [f[0] for f in st._fields_]
-    src = tmp_path / 'off.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu", sizeof(%s));\n%s\nreturn 0;}' % (
-        os.path.join(ROOT, 'include', 'lime_hip.h'), cname,
-        '\n'.join('printf(" %%zu", offsetof(%s, %s));' % (cname, f) for f in fields)))
-    exe = tmp_path / 'off'
-    subprocess.run(['gcc', '-o', str(exe), str(src)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert ctypes.sizeof(st) == got[0], cname
-    assert [getattr(st, f).offset for f in fields] == got[1:], cname
+C_SCALAR = {ctypes.c_int32: 'int32_t', ctypes.c_int64: 'int64_t', ctypes.c_uint32: 'uint32_t', ctypes.c_uint64: 'uint64_t',
+            ctypes.c_float: 'float'}
+
+
+def signature_unit(signatures):
+    """A C unit that initialises one function pointer per entry with the header's own function.  The pointer's scalar parameter and
+    return types are spelled from the DERIVED ctypes classes, its pointer types as the header's text: the unit compiles under -Werror
+    only if every entry has the count, the order and every scalar class and width the C compiler sees in the header."""
+    lines = ['#include "%s"' % HEADER]
+    for name, (res, args) in sorted(signatures.items()):
+        ret, params = _lib.C_TYPES[name]
+        spelled = [C_SCALAR.get(cls, text) for cls, text in zip(args, params)]
+        lines.append('%s (*const p_%s)(%s) = %s;' % (C_SCALAR.get(res, ret), name, ', '.join(spelled) or 'void', name))
+    return '\n'.join(lines) + '\n'
+
+
+def test_every_signature_is_what_the_c_compiler_sees(tmp_path):
+    assert len(_lib.SIGNATURES) >= 121 and sorted(_lib.SIGNATURES) == sorted(_lib.C_TYPES)
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert len(args) == len(_lib.C_TYPES[name][1]), name
+    r = _gcc(tmp_path, signature_unit(_lib.SIGNATURES), '-fsyntax-only')
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def _narrowed(args):
+    i = args.index(ctypes.c_int64)
+    return args[:i] + [ctypes.c_int32] + args[i + 1:]
+
+
+@pytest.mark.parametrize('name,wrong', [
+    ('lime_negative_sample', _narrowed),                              # an int64_t taken for an int32_t
+    ('lime_token_attention_bwd_f32', lambda args: args[:-1]),         # an argument dropped
+    ('lime_adam_f32', lambda args: args[:5] + [ctypes.c_int32] + args[6:]),   # an int32_t where the header has a float
+])
+def test_a_wrong_signature_does_not_compile(tmp_path, name, wrong):
+    """The control of the test above: its generator, fed ONE deliberately wrong entry, must be refused by the compiler."""
+    res, args = _lib.SIGNATURES[name]
+    assert wrong(list(args)) != args
+    r = _gcc(tmp_path, signature_unit(dict(_lib.SIGNATURES, **{name: (res, wrong(list(args)))})), '-fsyntax-only')
+    assert r.returncode != 0 and 'p_' + name in r.stderr, r.stderr[-3000:]
+
+
+SMALL = '''/* a comment
+   over two lines */
+#ifndef SMALL_H
+#define SMALL_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define SMALL_N 3   // a line comment
+typedef enum { SMALL_OK = 0, SMALL_ERR = -1 } small_status;
+enum { SMALL_A, SMALL_B, SMALL_C = 0x10, SMALL_D, SMALL_E = SMALL_N };
+typedef struct small_tag {
+    const float* a[SMALL_N];
+    int32_t M, N, *p;
+    char name[8];
+    uint64_t const seed;
+} small_args;
+int small_version(void);
+const char* small_name(void);
+int64_t small_run(const small_args* args, small_args const* more, const uint8_t* mask,
+                  int n, float scale,
+                  uint32_t site, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+'''
+
+
+def test_the_reader_on_every_form_the_header_uses():
+    from ctypes import POINTER, c_char, c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+    h = Header(SMALL)
+    assert h.constants == dict(SMALL_N=3, SMALL_OK=0, SMALL_ERR=-1, SMALL_A=0, SMALL_B=1, SMALL_C=16, SMALL_D=17, SMALL_E=3)
+    st = h.structs['small_args']
+    assert list(h.structs) == ['small_args'] and st.__name__ == 'small_args'
+    assert st._fields_ == [('a', c_void_p * 3), ('M', c_int32), ('N', c_int32), ('p', c_void_p), ('name', c_char * 8), ('seed', c_uint64)]
+    assert h.signatures == {'small_version': (c_int32, []), 'small_name': (c_char_p, []),
+                            'small_run': (c_int64, [POINTER(st), POINTER(st), c_void_p, c_int32, c_float, c_uint32, c_void_p])}
+    assert h.c_types['small_run'] == ('int64_t', ['const small_args*', 'small_args const*', 'const uint8_t*', 'int', 'float', 'uint32_t', 'void*'])
+
+
+@pytest.mark.parametrize('bad,line', [
+    ('int f(int a);\n\nvoid g(int a);\n', 3),                      # a return type without a ctypes class
+    ('int f(double x);\n', 1),                                     # a scalar outside the table
+    ('/* c\n */\ntypedef struct { int a; double b; } s;\n', 3),
+    ('typedef int (*callback)(int);\n', 1),
+    ('int f(int a[3]);\n', 1),
+    ('int f(int32_t);\n', 1),                                      # an unnamed parameter
+    ('enum { A = 1 << 2 };\n', 1),
+    ('\n#define N (1 + 2)\n', 2),
+    ('#if FOO\nint f(void);\n#endif\n', 1),
+    ('int f(void);\nint g(void)\n', 2),                            # no terminating semicolon
+])
+def test_the_reader_raises_on_what_it_cannot_read_and_names_the_line(bad, line):
+    with pytest.raises(ValueError, match=r'^x\.h:%d: ' % line):
+        Header(bad, 'x.h')
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, 'HEADER_PATH', str(tmp_path / 'nope.h'))
+    with pytest.raises(_lib.LimeHipError, match='nope.h is missing'):
+        _lib._read_header()
 
 
 def test_bad_arguments_are_rejected_without_a_launch(lib):

@@ -1,14 +1,10 @@
-"""Host side of lime_encoder_oproj_sp without a GPU: the applicability rule as a pure function, the ctypes mirror of its args struct
-against the header, and the staleness rule's sources.  (The pack layout is read back from the device: tests/test_oproj_sp_gpu.py.)"""
-import ctypes
+"""Host side of lime_encoder_oproj_sp without a GPU: the applicability rule as a pure function and the staleness rule's sources.
+(The pack layout is read back from the device: tests/test_oproj_sp_gpu.py; the args struct against the header: tests/test_abi.py.)"""
 import os
-import shutil
 import subprocess
 import sys
 
-import pytest
-
-from lime_cikm25_amd import _lib, make_config, newsEncoders
+from lime_cikm25_amd import make_config, newsEncoders
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,22 +32,6 @@ def test_switch_is_read_from_the_environment():
     out = subprocess.run([sys.executable, '-c', code], cwd=ROOT, env=dict(os.environ, LIME_SP_OPROJ='0'), check=True,
                          capture_output=True, text=True).stdout
     assert out.strip() == 'False'
-
-
-def test_args_struct_matches_the_header_field_by_field(tmp_path):
-    if shutil.which('gcc') is None:
-        pytest.skip('no gcc')
-    st, cname = _lib.OprojSpArgs, 'lime_oproj_sp_args'
-    fields = [f[0] for f in st._fields_]
-    src = tmp_path / 'off.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu", sizeof(%s));\n%s\nreturn 0;}' % (
-        os.path.join(ROOT, 'include', 'lime_hip.h'), cname,
-        '\n'.join('printf(" %%zu", offsetof(%s, %s));' % (cname, f) for f in fields)))
-    exe = tmp_path / 'off'
-    subprocess.run(['gcc', '-o', str(exe), str(src)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert ctypes.sizeof(st) == got[0]
-    assert [getattr(st, f).offset for f in fields] == got[1:]
 
 
 def test_out_proj_weights_are_sources_of_the_weight_products():
