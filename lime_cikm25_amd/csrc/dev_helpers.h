@@ -53,6 +53,23 @@ __device__ __forceinline__ void ring_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// Bit 31 of a buffer offset (beyond num_records: zeros come back, nothing is read or written) when one of `a`, `b` is negative.  The
+// branch-free form of `cond ? offset : OOB`: written as a select, hipcc turns a test shared by a group of loads into divergent control
+// flow -- two exec-masked loads into the same registers with a `s_waitcnt vmcnt(0)` between them, and a join that waits in front of
+// the MFMAs.
+__device__ __forceinline__ unsigned dead_bit(int a, int b) { return (unsigned)(a | b) & OOB; }
+// vmcnt(0), and the registers the wave's loads land in pass through the statement: hipcc's own bookkeeping does not see a wait in
+// inline asm and would put `s_waitcnt vmcnt(..)` of its own in front of the registers' first use, behind younger loads and DMAs.
+// (One statement for all of them: in front of a statement of its own each register gets hipcc's counted wait again.)
+__device__ __forceinline__ void wait_vm0_landed(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
+    wait_vm<0>();
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+__device__ __forceinline__ void wait_vm0_landed(f32x4& a, f32x4& b, f32x4& c, f32x4& d, f32x4& e, f32x4& f, f32x4& g, f32x4& h) {
+    wait_vm<0>();
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
+}
+
 // A device-side count (the compacted rows / sequences of this launch, written by an earlier kernel of the stream) against the host's
 // bound `cap`: `cap` when there is none, else the count clamped to 0 .. cap, wave-uniform.
 __device__ __forceinline__ int live_count(const int* dev, int cap) {

@@ -15,8 +15,11 @@
 //     change, refilled in place before a graph replay: newsEncoders.WeightProducts), every step's slot ONE contiguous block in the order of its LDS image (swizzled [row][64-byte] rows: conflict-free
 //     ds_read_b128 fragments), copied by LDS-DMA into two ring slots: step s + 1 is issued during step s (one instruction per
 //     MFMA group), then one vmcnt(0) wait + barrier per step (the two-stage drain of gemm_sp_f32.hip).
-//   * epilogue: + b2 + the residual rows (fp32, re-read: L2 hits), LayerNorm (the four lanes that share a token meet through two
-//     shuffles), then fp32 rows or, with `pool32`, the 32-token block means of the wave.
+//   * epilogue: + b2 + the residual rows (fp32, re-read: L2 hits, all 38 quads of a lane requested before the first is used),
+//     LayerNorm (the four lanes that share a token meet through two shuffles), then fp32 rows or, with `pool32`, the 32-token
+//     block means of the wave.
+//   * every load is branch-free and the next step's (behind a tile's last step: the next tile's) fragments are requested
+//     unconditionally, so the only vmcnt waits of the tile loop are the one that ends each step and the epilogue's.
 #include <type_traits>
 
 #include "common.h"
@@ -104,7 +107,8 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
         for (int i = 0; i < DMA_PER_WAVE; ++i) issue_one(s, slot, i);
     };
     // the layer input fragments of a linear1 step: chunks 2 pos, 2 pos + 1, token halves tt, k 8 kg .. 8 kg + 7 as two quads
-    // (E % 4 == 0: a quad is real or beyond E as a whole; rows beyond M and quads beyond E read zeros)
+    // (E % 4 == 0: a quad is real or beyond E as a whole; rows beyond M and quads beyond E read zeros).  Branch-free (dead_bit,
+    // dev_helpers.h): as `cond ? offset : OOB` every load became two exec-masked loads with a vmcnt(0) between them.
     f32x4 xn[2][2][2];
     auto load_x = [&](int t, int pos) {
         const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.x + (long)t * BM * p.ldx);
@@ -119,10 +123,14 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int col = 32 * (2 * pos + cc) + 8 * kg + 4 * q;
-                    const unsigned vo = (rl < rows_left && col < E) ? ro + (unsigned)col * 4u : OOB;
-                    xn[cc][tt][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, vo, 0, 0));
+                    xn[cc][tt][q] = buf_load4(rs_x, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
                 }
         }
+    };
+    // vmcnt(0) with the fragments passed through it (wait_vm0_landed, dev_helpers.h): hipcc's own wait would sit in front of their
+    // first use, at the top of the next step, behind that step's loads
+    auto wait_x = [&]() {
+        wait_vm0_landed(xn[0][0][0], xn[0][0][1], xn[0][1][0], xn[0][1][1], xn[1][0][0], xn[1][0][1], xn[1][1][0], xn[1][1][1]);
     };
 
     // MFMA lane layout (v_mfma_f32_16x16x32_bf16, a = weight rows = output columns, b = tokens): lane (fi, kg) reads k 8 kg .. 8 kg + 7
@@ -140,7 +148,7 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
     // prologue: the first step of this workgroup's first tile
     issue_w(0, 0);
     load_x(tile, 0);
-    wait_vm<0>();
+    wait_x();
     ring_barrier();
     int gs = 0;                                        // steps run by this workgroup (ring position)
     for (; tile < ntiles; tile += gridDim.x) {
@@ -168,10 +176,10 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
             const bool go = !(wrap && last);
             const int ns = wrap ? 0 : pass * STEPS + POS + 1;
             const int nslot = (gs + 1) & 1;
-            if (go) {
-                constexpr int NPOS = (POS + 1) % STEPS;
-                if constexpr (NPOS < L1_STEPS) load_x(wrap ? tile + (int)gridDim.x : tile, NPOS);
-            }
+            // (unconditional: behind this workgroup's last tile every row is beyond M and nothing is read; under `if (go)` the
+            // fragments become a phi whose copy waits for these loads ahead of the MFMAs)
+            constexpr int NPOS = (POS + 1) % STEPS;
+            if constexpr (NPOS < L1_STEPS) load_x(wrap ? tile + (int)gridDim.x : tile, NPOS);
             auto part = [&](int i) {
                 if (go && i < DMA_PER_WAVE) issue_one(ns, nslot, i);
             };
@@ -228,8 +236,9 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            wait_vm<0>();                              // this wave's part of the next slot (and its layer input fragments)
-            ring_barrier();                            // ... everyone's: the next slot is complete, this one is free
+            if constexpr (NPOS < L1_STEPS) wait_x();   // this wave's part of the next slot (and its layer input fragments)
+            else wait_vm<0>();
+            ring_barrier();                           // ... everyone's: the next slot is complete, this one is free
             ++gs;
         };
         for (int pass = 0; pass < NP; ++pass) {
@@ -253,17 +262,29 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
         const float* const cs_ = cs + 4 * kg;
         const float inv_n = 1.0f / (float)E;
         float mean[2], rstd[2];
-        // one token half at a time (its 19 residual loads, then its statistics): both halves' loads at once would not fit the VGPRs
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
+        // the residual rows: all 19 quads of a token half are requested before the first is used (the fence: left alone, hipcc
+        // sinks each load to its use and waits vmcnt(0) behind every one -- 38 round trips in a row per tile), half 1's before half
+        // 0's statistics
+        f32x4 rr[2][ND];
+        auto load_res = [&](int tt) {
             const int rl = 32 * wave + 16 * tt + fi;
             const unsigned ro = (unsigned)rl * (unsigned)p.ldx * 4u;
-            float s1 = 0.f;
 #pragma unroll
             for (int t = 0; t < ND; ++t) {
                 const int col = 16 * t + 4 * kg;
-                const unsigned vo = (rl < rows_left && col < E) ? ro + (unsigned)col * 4u : OOB;
-                const f32x4 r = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, vo, 0, 0));
+                rr[tt][t] = buf_load4(rs_r, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
+            }
+        };
+        load_res(0);
+        __builtin_amdgcn_sched_barrier(0);
+        load_res(1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            float s1 = 0.f;
+#pragma unroll
+            for (int t = 0; t < ND; ++t) {
+                const f32x4 r = rr[tt][t];
                 const f32x4 b = *reinterpret_cast<const f32x4*>(cs_ + 16 * t);
                 const f32x4 v = acc2[tt][t] + b + r;
                 acc2[tt][t] = v;

@@ -77,10 +77,8 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
             dma16(rs_w, lds + slot * SLOT + b * 1024, (unsigned)lane * 16u, s * SLOT + b * 1024);
         }
     };
-    // Every load below is branch-free: a buffer offset gets bit 31 (beyond num_records: zeros come back, nothing is read) when one of
-    // `a`, `b` is negative.  Written as `cond ? offset : OOB`, hipcc turns the row test shared by a group of loads into divergent
-    // control flow, and the join waits vmcnt(0) in front of the MFMAs -- with the residual gather in flight.
-    auto dead_bit = [](int a, int b) { return (unsigned)(a | b) & OOB; };
+    // Every load below is branch-free (dead_bit, dev_helpers.h): a join of divergent control flow would wait vmcnt(0) in front of the
+    // MFMAs -- with the residual gather in flight.
     // the attention rows of step s: token halves tt, k 32 s + 8 kg .. + 7 as two quads (E % 4 == 0: a quad is real or beyond E as a
     // whole; rows beyond M and quads beyond E read zeros)
     f32x4 xn[2][2];
@@ -152,13 +150,9 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
         return f;
     };
     f32x4 acc[2][ND];
-    // vmcnt(0), and the attention fragments pass through the statement: hipcc's own bookkeeping does not see a wait in inline asm and
-    // would put `s_waitcnt vmcnt(0 .. 3)` in front of the fragments' first use, at the top of the next step -- where the tile's word
-    // ids and the previous tile's stores are in flight
-    auto wait_all = [&]() {
-        wait_vm<0>();
-        asm volatile("" : "+v"(xn[0][0]), "+v"(xn[0][1]), "+v"(xn[1][0]), "+v"(xn[1][1]));
-    };
+    // vmcnt(0) with the attention fragments passed through it (wait_vm0_landed, dev_helpers.h): hipcc's own wait would sit in front of
+    // the fragments' first use, at the top of the next step -- where the tile's word ids and the previous tile's stores are in flight
+    auto wait_all = [&]() { wait_vm0_landed(xn[0][0], xn[0][1], xn[1][0], xn[1][1]); };
 
     // prologue: the first step of this workgroup's first tile
     for (int i = 0; i < DMA_PER_WAVE; ++i) issue_one(0, 0, i);
