@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 12
+#define LIME_ABI_VERSION 13
 
 typedef enum {
     LIME_OK = 0,
@@ -472,6 +472,61 @@ int lime_news_xin_f32(const float* title_blocks, int64_t ld_t, int32_t nblk_t, c
 int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
                                    const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
                                    int32_t head_dim, float scale, void* stream);
+
+/* The arguments of the six fp32 forward entries (lime_token_attention_f32, _count_f32, _lse_f32, _rows_f32, _vocab_f32, _dropout_f32)
+ * as one block; `form` says which entry is speaking, fields an entry does not have are 0 / NULL.  The vocab form: q = qkv_vocab,
+ * k = q + W, v = q + 2 W (W = n_head * 32), row_map = ids; rows and vocab: head_stride = 32. */
+enum { LIME_ATTN_FORM_PLAIN = 0, LIME_ATTN_FORM_COUNT = 1, LIME_ATTN_FORM_LSE = 2, LIME_ATTN_FORM_ROWS = 3, LIME_ATTN_FORM_VOCAB = 4,
+       LIME_ATTN_FORM_DROPOUT = 5 };
+typedef struct {
+    const float* q;
+    const float* k;
+    const float* v;
+    int64_t ld_qkv;
+    const float* pos_rows;
+    const int32_t* row_map;
+    const uint8_t* key_mask;
+    const int32_t* n_seq_dev;
+    float* lse;
+    float* out;
+    int64_t ldo;
+    float* workspace;
+    int64_t workspace_floats;
+    uint64_t dropout_seed;
+    float dropout_p;
+    uint32_t dropout_site;
+    int32_t n_seq, S, n_head, head_dim, head_stride;
+    float scale;
+    int32_t form;
+    int32_t reserved;
+} lime_token_attention_args;
+
+/* What the fp32 token-attention forward would run for an argument block, without running it: the routing decision
+ * (csrc/token_attn_f32.hip, lime_attn_route) as data.  A pure function of the block and the
+ * lime_set_split_gemm() setting: no launch, no call into the HIP runtime, no pointer of the block is read through (only NULL-ness
+ * and alignment count); the CU count sizes the grids and chooses no kernel.  Returns what the entry named by `form` would return
+ * where it launches nothing -- its refusal (same status, same lime_last_error_string()) or LIME_NOT_APPLICABLE (vocab form) -- else
+ * LIME_OK and
+ *   family      LIME_ATTN_SP token_attn_sp_kernel (split product, S = 32 / 64 / 128 in one pass), _SP_LONG token_attn_sp_long_kernel
+ *               (S = 256 / 512 in key blocks), _SP_VOCAB token_attn_sp_vocab_kernel, _MFMA token_attn_kernel (exact-fp32 MFMA),
+ *               _WIDE wide_fwd_kernel (head_dim > 32), _DROPOUT token_attn_fwd_dropout_kernel (one pass, S <= 128), _DROPOUT_LONG
+ *               attn_fwd_long_dropout_kernel (key blocks); LIME_ATTN_NONE for n_seq == 0 (nothing is launched)
+ *   stats_pass  the row-statistics launch in front of it: LIME_ATTN_STATS_NONE, _FP32 (attn_stats_kernel<false>) or _SPLIT
+ *               (attn_stats_kernel<true>: Q K^T as split products)
+ *   n_launches  0, 1 or 2
+ *   name        the n_launches instantiations in launch order, as rocprofv3 prints them */
+enum { LIME_ATTN_NONE = 0, LIME_ATTN_SP = 1, LIME_ATTN_SP_LONG = 2, LIME_ATTN_SP_VOCAB = 3, LIME_ATTN_MFMA = 4, LIME_ATTN_WIDE = 5,
+       LIME_ATTN_DROPOUT = 6, LIME_ATTN_DROPOUT_LONG = 7 };
+enum { LIME_ATTN_STATS_NONE = 0, LIME_ATTN_STATS_FP32 = 1, LIME_ATTN_STATS_SPLIT = 2 };
+typedef struct {
+    int32_t family;
+    int32_t stats_pass;
+    int32_t n_launches;
+    int32_t reserved;
+    char name[2][64];
+} lime_token_attention_plan;
+
+int lime_token_attention_plan_f32(const lime_token_attention_args* args, lime_token_attention_plan* out);
 
 /* lime_token_attention_rows_bf16: lime_token_attention_bf16 over compacted sequences (row_map / n_seq_dev as in
  * lime_token_attention_rows_f32); S in {32, 64, 128}, even head_dim. */

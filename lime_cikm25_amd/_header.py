@@ -10,7 +10,7 @@ from ctypes import POINTER, c_char, c_char_p, c_float, c_int32, c_int64, c_uint3
 
 SCALARS = {'int': c_int32, 'int32_t': c_int32, 'int64_t': c_int64, 'uint32_t': c_uint32, 'uint64_t': c_uint64, 'float': c_float,
            'char': c_char}
-_DECLARATOR = re.compile(r'^(.*[\s*])(\w+)\s*(?:\[\s*(\w+)\s*\])?$', re.S)
+_DECLARATOR = re.compile(r'^(.*[\s*])(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)$', re.S)
 
 
 class Header:
@@ -104,21 +104,23 @@ class Header:
             self.constants[name] = value
 
     def _split(self, text, what):
-        """'const float* a[3]' -> ('const float*', 'a', '3')"""
+        """'const float* a[3]' -> ('const float*', 'a', ['3']); 'char n[2][64]' -> ('char', 'n', ['2', '64'])"""
         m = _DECLARATOR.match(text.strip())
         if not m or not m.group(1).strip():
             self._fail('cannot read the %s %r' % (what, text))
-        return ' '.join(m.group(1).split()), m.group(2), m.group(3)
+        return ' '.join(m.group(1).split()), m.group(2), re.findall(r'\w+', m.group(3))
 
     def _fields(self, body):
         fields = []
         for member in filter(None, (s.strip() for s in body.split(';'))):
             first, *more = member.split(',')
-            ctype, name, bound = self._split(first, 'field')
+            ctype, name, bounds = self._split(first, 'field')
             base = ctype.split('*')[0]                  # `const float* a, b`: b is a float
-            for ctype, name, bound in [(ctype, name, bound)] + [self._split(base + ' ' + d, 'field') for d in more]:
+            for ctype, name, bounds in [(ctype, name, bounds)] + [self._split(base + ' ' + d, 'field') for d in more]:
                 t = self._ctype(ctype, name)
-                fields.append((name, t * self._int(bound) if bound else t))
+                for bound in reversed(bounds):          # `char n[2][64]`: two arrays of 64
+                    t = t * self._int(bound)
+                fields.append((name, t))
         return fields
 
     def _ctype(self, ctype, name):

@@ -37,6 +37,8 @@ C_TYPES = _abi.c_types               # name -> (return type, parameter types) in
 LinearArgs = STRUCTS['lime_linear_args']
 LinearPlan = STRUCTS['lime_linear_plan']
 LinearBf16Args = STRUCTS['lime_linear_bf16_args']
+TokenAttentionArgs = STRUCTS['lime_token_attention_args']
+TokenAttentionPlan = STRUCTS['lime_token_attention_plan']
 FfnBf16Args = STRUCTS['lime_ffn_bf16_args']
 FfnSpArgs = STRUCTS['lime_ffn_sp_args']
 OprojSpArgs = STRUCTS['lime_oproj_sp_args']
@@ -55,6 +57,10 @@ LIME_ACT = {None: CONSTANTS['LIME_ACT_NONE'], 'none': CONSTANTS['LIME_ACT_NONE']
             'tanh': CONSTANTS['LIME_ACT_TANH'], 'sigmoid': CONSTANTS['LIME_ACT_SIGMOID'], 'relu_grad': CONSTANTS['LIME_ACT_RELU_GRAD']}
 LINEAR_FAMILY = {CONSTANTS['LIME_LINEAR_NONE']: None, CONSTANTS['LIME_LINEAR_SP']: 'sp', CONSTANTS['LIME_LINEAR_PP']: 'pp',
                  CONSTANTS['LIME_LINEAR_MID']: 'mid', CONSTANTS['LIME_LINEAR_GENERAL']: 'general'}
+ATTN_FORM = {f: CONSTANTS['LIME_ATTN_FORM_' + f.upper()] for f in ('plain', 'count', 'lse', 'rows', 'vocab', 'dropout')}
+ATTN_FAMILY = {CONSTANTS['LIME_ATTN_' + f.upper()]: f for f in ('sp', 'sp_long', 'sp_vocab', 'mfma', 'wide', 'dropout', 'dropout_long')}
+ATTN_FAMILY[CONSTANTS['LIME_ATTN_NONE']] = None
+ATTN_STATS = {CONSTANTS['LIME_ATTN_STATS_NONE']: None, CONSTANTS['LIME_ATTN_STATS_FP32']: 'fp32', CONSTANTS['LIME_ATTN_STATS_SPLIT']: 'split'}
 LINEAR_PASS_RELU_BWD = CONSTANTS['LIME_LINEAR_PASS_RELU_BWD']
 LINEAR_PASS_DROPOUT = CONSTANTS['LIME_LINEAR_PASS_DROPOUT']
 

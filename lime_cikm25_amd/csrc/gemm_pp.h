@@ -5,8 +5,6 @@
 #include "common.h"
 #include "dropout.h"
 
-#define LIME_PP_NOT_APPLICABLE 1     // lime_token_attention_sp / _bwd_sp: not taken, the caller goes on to its other kernels
-
 struct PPParams {
     const float* a; long lda; const int* a_ids;
     const float* w; long ldw; const float* bias;
@@ -114,21 +112,15 @@ __attribute__((visibility("hidden")))
 int lime_reduce_partials(const float* ws, long split_stride, int splits, long ldw, float* out, long ldo, int rows, int cols,
                          int accumulate, hipStream_t s, float* extra = nullptr);
 int lime_split_mode();                                                   // gemm_sp_f32.hip: the lime_set_split_gemm() setting
-// token_attn_sp_f32.hip: unmasked S = 32 / 64 / 128 attention on the split product (LIME_PP_NOT_APPLICABLE: not taken)
-int lime_token_attention_sp(const float* q, const float* k, const float* v, long ld, const int* row_map, const int* n_seq_dev,
-                            float* out, long ldo, int n_seq, int S, int n_head, int hd, float scale, float* lse, hipStream_t s,
-                            const LimeDropout* drop = nullptr);
-// token_attn_wide_f32.hip: 32 < head_dim <= 128 (head_dim % 4 == 0, 16-byte aligned operands), forward and backward on the fp32 MFMA; they
-// check their own limits and name `entry` in their messages.  The backward recomputes the row statistics (workspace:
-// lime_token_attention_bwd_workspace_wide floats).
-int lime_token_attention_wide(const char* entry, const float* q, const float* k, const float* v, long ld, const unsigned char* key_mask,
-                              const int* n_seq_dev, float* out, long ldo, float* lse, int n_seq, int S, int n_head, int hd, int hs,
-                              float scale, const LimeDropout* drop, hipStream_t s);
+// token_attn_wide_f32.hip: the backward at 32 < head_dim <= 128 (head_dim % 4 == 0, 16-byte aligned operands) on the fp32 MFMA; it checks
+// its own limits and names `entry` in its messages, and recomputes the row statistics (workspace:
+// lime_token_attention_bwd_workspace_wide floats).  The forward: token_attn.h.
 int lime_token_attention_wide_bwd(const char* entry, const float* q, const float* k, const float* v, long ld, const float* dout, long ldo,
                                   float* dq, float* dk, float* dv, long ldd, int n_seq, int S, int n_head, int hd, int hs, float scale,
                                   float* workspace, long workspace_floats, const LimeDropout& drop, const unsigned char* key_mask,
                                   hipStream_t s);
-// token_attn_bwd_sp_f32.hip: the one-pass attention backward (64 < S <= 128, no key mask) with all its products on the split product
+// token_attn_bwd_sp_f32.hip: the one-pass attention backward (64 < S <= 128, no key mask) with all its products on the split product;
+// LIME_NOT_APPLICABLE: not taken, the caller goes on to its other kernels
 int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, long ld, const float* dout, long ldo, float* dq, float* dk,
                                 float* dv, long ldd, int n_seq, int S, int n_head, int head_dim, int head_stride, float scale,
                                 const LimeDropout& drop, hipStream_t s);

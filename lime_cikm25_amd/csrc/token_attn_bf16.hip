@@ -205,13 +205,13 @@ int launch(AttnB p, hipStream_t s) {
 
 }  // namespace
 
-// S = 32 / 64 / 128 with an even head_dim: the bf16-MFMA kernel; returns 1 when the shape is not its (the caller in
+// S = 32 / 64 / 128 with an even head_dim: the bf16-MFMA kernel; returns LIME_NOT_APPLICABLE when the shape is not its (the caller in
 // token_attn_f32.hip then takes the fp32-core variant).
 int lime_token_attention_bf16_mfma(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t ld_qkv, uint16_t* out, int64_t ldo,
                                    int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, float scale, int32_t out_pad,
                                    hipStream_t s) {
-    if (!(S == 32 || S == 64 || S == 128) || scale <= 0.f) return 1;
-    if ((uintptr_t)out % 4 != 0 || ldo % 2 != 0 || head_dim % 2 != 0) return 1;        // 4-byte output stores
+    if (!(S == 32 || S == 64 || S == 128) || scale <= 0.f) return LIME_NOT_APPLICABLE;
+    if ((uintptr_t)out % 4 != 0 || ldo % 2 != 0 || head_dim % 2 != 0) return LIME_NOT_APPLICABLE;        // 4-byte output stores
     AttnB p{q, k, v, (long)ld_qkv, out, (long)ldo, n_seq, S, n_head, head_dim, scale, n_seq * n_head, 0, out_pad, nullptr, nullptr};
     switch (S / 32) {
         case 1: return launch<1>(p, s);

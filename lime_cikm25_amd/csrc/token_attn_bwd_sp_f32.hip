@@ -282,14 +282,14 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_kernel(const BwdSpP p) {
 
 }  // namespace
 
-// LIME_PP_NOT_APPLICABLE: the caller takes token_attn_bwd_kernel (shapes / alignments outside this build)
+// LIME_NOT_APPLICABLE: the caller takes token_attn_bwd_kernel (shapes / alignments outside this build)
 int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, long ld, const float* dout, long ldo, float* dq, float* dk,
                                 float* dv, long ldd, int n_seq, int S, int n_head, int head_dim, int head_stride, float scale,
                                 const LimeDropout& drop, hipStream_t s) {
-    if (!(S > 64 && S <= SPB && S % 4 == 0 && head_stride == 32 && head_dim <= 32 && head_dim % 2 == 0)) return LIME_PP_NOT_APPLICABLE;
-    if (ld % 4 != 0 || ldd % 4 != 0 || ldo % 2 != 0) return LIME_PP_NOT_APPLICABLE;
+    if (!(S > 64 && S <= SPB && S % 4 == 0 && head_stride == 32 && head_dim <= 32 && head_dim % 2 == 0)) return LIME_NOT_APPLICABLE;
+    if (ld % 4 != 0 || ldd % 4 != 0 || ldo % 2 != 0) return LIME_NOT_APPLICABLE;
     if (((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15) != 0 || (((uintptr_t)dout) & 7) != 0)
-        return LIME_PP_NOT_APPLICABLE;
+        return LIME_NOT_APPLICABLE;
     static_assert(LDS_BYTES <= 163840, "LDS budget");
     static int reserved[2] = {0, 0};              // per instantiation: S < SPB, S == SPB
     const void* const kernel = S == SPB ? (const void*)attn_bwd_sp_kernel<true> : (const void*)attn_bwd_sp_kernel<false>;

@@ -21,6 +21,7 @@
 // or 2 (S <= 64) pairs per group.  Scores live in the log2 domain so the exponential is one v_exp_f32.
 #include "common.h"
 #include "dev_helpers.h"
+#include "token_attn.h"
 #include "gemm_pp.h"
 #include <type_traits>
 
@@ -475,9 +476,9 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
 #endif
 }
 
-// One launch for all four entry points.  BF: bf16 operands and output; MAP: rows gathered through row_map.  Both imply the FAST
-// loaders (their entry points check the layout); the plain fp32 entries pick FAST per call.
-template <int NT, bool BF, bool MAP>
+// One launch for every entry point; the caller has chosen the instantiation.  BF: bf16 operands and output; MAP: rows gathered through
+// row_map.  Both exist with the FAST loaders only (static_asserts above).
+template <int NT, bool FAST, bool BF, bool MAP>
 int launch(AttnP p, hipStream_t s, const char* entry) {
     constexpr int G = (NT >= 3) ? 1 : (4 / NT);
     p.n_group = (p.n_pair + G - 1) / G;
@@ -487,109 +488,249 @@ int launch(AttnP p, hipStream_t s, const char* entry) {
 #ifdef LIME_STAMPS
     p.stamps = g_attn_stamp_buf;
 #endif
-    if constexpr (BF || MAP) {
-        hipLaunchKernelGGL((token_attn_kernel<NT, true, BF, MAP>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    } else {
-        // FAST: no mask, S a multiple of 32, heads padded to 32 columns, 16-byte aligned operands
-        const bool fast = p.mask == nullptr && p.S == NT * 32 && p.hs == 32 && p.ld % 4 == 0 &&
-                          (((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.v) % 16 == 0);
-        if (fast) hipLaunchKernelGGL((token_attn_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((token_attn_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    }
+    hipLaunchKernelGGL((token_attn_kernel<NT, FAST, BF, MAP>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     return lime_check_launch(entry);
 }
 
-// nt = ceil(S / 32) key tiles -> the instantiation that holds them (1, 2, 3, 4, 8 or 16; bf16 has none for 3 and never asks for it)
-template <bool BF, bool MAP>
+// nt key tiles -> the instantiation that holds them: 1, 2, 3, 4, 8 or 16 (bf16 has none for 3)
+template <bool FAST, bool BF, bool MAP>
 int launch_nt(int nt, const AttnP& p, hipStream_t s, const char* entry) {
-    if (nt <= 1) return launch<1, BF, MAP>(p, s, entry);
-    if (nt <= 2) return launch<2, BF, MAP>(p, s, entry);
-    if constexpr (!BF) {
-        if (nt <= 3) return launch<3, BF, MAP>(p, s, entry);
+    switch (nt) {
+        case 1: return launch<1, FAST, BF, MAP>(p, s, entry);
+        case 2: return launch<2, FAST, BF, MAP>(p, s, entry);
+        case 3: if constexpr (!BF) return launch<3, FAST, BF, MAP>(p, s, entry); else break;
+        case 4: return launch<4, FAST, BF, MAP>(p, s, entry);
+        case 8: return launch<8, FAST, BF, MAP>(p, s, entry);
+        case 16: return launch<16, FAST, BF, MAP>(p, s, entry);
     }
-    if (nt <= 4) return launch<4, BF, MAP>(p, s, entry);
-    if (nt <= 8) return launch<8, BF, MAP>(p, s, entry);
-    return launch<16, BF, MAP>(p, s, entry);
+    LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "%s: token_attn_kernel<%d, ...> is not built", entry, nt);
 }
 
 }  // namespace
 
-extern "C" int lime_token_attention_rows_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const int32_t* row_map,
-                                             const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S,
-                                             int32_t n_head, int32_t head_dim, float scale, void* stream) {
-    LIME_REQUIRE(q && k && v && out && row_map, LIME_ERR_BAD_ARG, "lime_token_attention_rows_f32: NULL pointer");
-    LIME_REQUIRE(n_seq >= 0 && n_head > 0 && head_dim > 0 && head_dim <= 32, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_rows_f32: bad dims n_seq=%d n_head=%d head_dim=%d", n_seq, n_head, head_dim);
-    LIME_REQUIRE(S > 0 && S <= 512 && S % 32 == 0 && (S / 32 <= 4 || S / 32 == 8 || S / 32 == 16), LIME_ERR_UNSUPPORTED,
-                 "lime_token_attention_rows_f32: S must be 32, 64, 96, 128, 256 or 512 (got %d)", S);
-    LIME_REQUIRE(ld_qkv >= (int64_t)n_head * 32 && ld_qkv % 4 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0),
-                 LIME_ERR_BAD_ARG, "lime_token_attention_rows_f32: heads are 32 columns apart (zero padded), rows 16-byte aligned");
-    LIME_REQUIRE(ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG, "lime_token_attention_rows_f32: ldo smaller than n_head * head_dim");
-    if (n_seq == 0) return LIME_OK;
-    hipStream_t s = (hipStream_t)stream;
-    {   // S <= 128: the split-product kernel (token_attn_sp_f32.hip) unless lime_set_split_gemm(0)
-        const int st = lime_token_attention_sp(q, k, v, (long)ld_qkv, row_map, n_seq_dev, out, (long)ldo, n_seq, S, n_head, head_dim, scale, nullptr, s);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
-    }
-    AttnP p{q, k, v, (long)ld_qkv, nullptr, out, (long)ldo, n_seq, S, n_head, head_dim, 32, scale, n_seq * n_head, 1, 0, 0, row_map, n_seq_dev};
-    return launch_nt<false, true>(S / 32, p, s, "lime_token_attention_rows_f32");
+int lime_attn_mfma_launch(const LimeAttnRoute& r, const lime_token_attention_args& a, hipStream_t s) {
+    // 8-byte loads of the general path need an even head_dim, head_stride and leading dimension and 8-byte aligned bases
+    const int vec2 = (a.head_dim % 2 == 0) && (a.head_stride % 2 == 0) && (a.ld_qkv % 2 == 0) &&
+                     (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 8 == 0);
+    AttnP p{a.q, a.k, a.v, (long)a.ld_qkv, a.key_mask, a.out, (long)a.ldo, a.n_seq, a.S, a.n_head, a.head_dim, a.head_stride, a.scale,
+            a.n_seq * a.n_head, vec2, 0, 0, a.row_map, a.n_seq_dev, a.lse};
+    const char* const entry = r.map ? "lime_token_attention_rows_f32" : "lime_token_attention_f32";
+    if (r.map) return launch_nt<true, false, true>(r.n, p, s, entry);
+    return r.fast ? launch_nt<true, false, false>(r.n, p, s, entry) : launch_nt<false, false, false>(r.n, p, s, entry);
 }
 
-extern "C" int lime_token_attention_count_f32(const float* q, const float* k, const float* v, int64_t ld_qkv,
-                                              const uint8_t* key_mask, const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq,
-                                              int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale, void* stream) {
-    LIME_REQUIRE(q && k && v && out, LIME_ERR_BAD_ARG, "lime_token_attention_count_f32: NULL pointer");
-    LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_count_f32: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", n_seq, S, n_head, head_dim);
-    if (head_dim > 32)                                // wide heads: token_attn_wide_f32.hip (checks its own limits)
-        return lime_token_attention_wide("lime_token_attention_count_f32", q, k, v, (long)ld_qkv, key_mask, n_seq_dev, out, (long)ldo, nullptr,
-                                         n_seq, S, n_head, head_dim, head_stride, scale, nullptr, (hipStream_t)stream);
-    LIME_REQUIRE(head_stride >= head_dim, LIME_ERR_BAD_ARG, "lime_token_attention_count_f32: head_stride %d < head_dim %d", head_stride, head_dim);
-    LIME_REQUIRE(S <= 512, LIME_ERR_UNSUPPORTED, "lime_token_attention_count_f32: S %d > 512", S);
-    LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_count_f32: leading dimension smaller than n_head * head_dim");
-    if (n_seq == 0) return LIME_OK;
-    // 8-byte loads need an even head_dim and leading dimension and 8-byte aligned bases
-    const int vec2 = (head_dim % 2 == 0) && (head_stride % 2 == 0) && (ld_qkv % 2 == 0) &&
-                     (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 8 == 0);
-    hipStream_t s = (hipStream_t)stream;
-    if (key_mask == nullptr && head_stride == 32) {   // the encoder layers' shapes: the split-product kernel (token_attn_sp_f32.hip)
-        const int st = lime_token_attention_sp(q, k, v, (long)ld_qkv, nullptr, n_seq_dev, out, (long)ldo, n_seq, S, n_head, head_dim, scale, nullptr, s);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
+// ---- The fp32 forward: its six entries, the checks they share and the one pure route that chooses the kernel.
+// An entry fills the argument block; attention_forward() routes it and hands the route to the unit that owns the kernel
+// (token_attn.h).  lime_token_attention_plan_f32 returns the same decision as data.
+
+enum { PLAIN = LIME_ATTN_FORM_PLAIN, COUNT = LIME_ATTN_FORM_COUNT, LSE = LIME_ATTN_FORM_LSE, ROWS = LIME_ATTN_FORM_ROWS,
+       VOCAB = LIME_ATTN_FORM_VOCAB, DROPOUT = LIME_ATTN_FORM_DROPOUT };
+
+const char* lime_attn_entry(int form) {
+    static const char* const names[] = {"lime_token_attention_count_f32", "lime_token_attention_count_f32", "lime_token_attention_lse_f32",
+                                        "lime_token_attention_rows_f32", "lime_token_attention_vocab_f32", "lime_token_attention_dropout_f32"};
+    return names[form];          // lime_token_attention_f32 is the count entry without a count, and reports as it
+}
+
+int lime_attn_route(const lime_token_attention_args& a, int split_mode, LimeAttnRoute* r) {
+    *r = LimeAttnRoute{LIME_ATTN_NONE, 0, false, false, LIME_ATTN_STATS_NONE};
+    const char* const e = lime_attn_entry(a.form);
+    const int form = a.form, S = a.S, hd = a.head_dim, hs = a.head_stride;
+    const long W = (long)a.n_head * 32;
+    const bool split = (split_mode & 1) != 0, drop_p_ok = a.dropout_p >= 0.f && a.dropout_p < 1.f;
+    const bool al16 = (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) == 0;
+
+    // ---- the checks every entry makes, in the order and the words each of them has always used ----
+    LIME_REQUIRE(a.q && a.k && a.v && a.out && (form != LSE || a.lse) && ((form != ROWS && form != VOCAB) || a.row_map) &&
+                 (form != VOCAB || a.pos_rows), LIME_ERR_BAD_ARG, form == DROPOUT ? "%s: null pointer" : "%s: NULL pointer", e);
+    if (form == ROWS)
+        LIME_REQUIRE(a.n_seq >= 0 && a.n_head > 0 && hd > 0 && hd <= 32, LIME_ERR_BAD_ARG, "%s: bad dims n_seq=%d n_head=%d head_dim=%d", e,
+                     a.n_seq, a.n_head, hd);
+    else
+        LIME_REQUIRE(a.n_seq >= 0 && S > 0 && a.n_head > 0 && hd > 0, LIME_ERR_BAD_ARG,
+                     form == DROPOUT ? "%s: bad dimensions" : "%s: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", e, a.n_seq, S, a.n_head, hd);
+
+    if (form == VOCAB) {         // split product only; what it does not cover is the caller's in_proj + row-map path, not an error
+        LIME_REQUIRE(a.ldo >= (int64_t)a.n_head * hd, LIME_ERR_BAD_ARG, "%s: ldo smaller than n_head * head_dim", e);
+        if (!split || !(S == 32 || S == 64 || S == 128) || hd > 32 || a.ld_qkv % 4 != 0 || a.ld_qkv < 3 * W ||
+            a.ld_qkv > (1 << 21) ||                                      // 32-bit offsets into pos_rows
+            (((uintptr_t)a.q | (uintptr_t)a.pos_rows) % 16) != 0)
+            return LIME_NOT_APPLICABLE;
+        if (a.n_seq > 0) *r = LimeAttnRoute{LIME_ATTN_SP_VOCAB, S / 32, false, false, LIME_ATTN_STATS_NONE};
+        return LIME_OK;
     }
-    AttnP p{q, k, v, (long)ld_qkv, key_mask, out, (long)ldo, n_seq, S, n_head, head_dim, head_stride, scale, n_seq * n_head, vec2, 0, 0, nullptr, n_seq_dev};
-    return launch_nt<false, false>((S + 31) / 32, p, s, "lime_token_attention_f32");
+
+    if (hd > 32) {               // wide heads: one family at every S, on the fp32 MFMA under either split mode
+        if (form == DROPOUT) LIME_REQUIRE(drop_p_ok, LIME_ERR_BAD_ARG, "%s: dropout_p outside [0, 1)", e);
+        if (const int st = lime_attn_wide_limits(e, S, a.n_head, hd, hs, a.n_seq)) return st;
+        LIME_REQUIRE(a.ld_qkv >= (int64_t)a.n_head * hs && a.ldo >= (int64_t)a.n_head * hd, LIME_ERR_BAD_ARG,
+                     "%s: leading dimension smaller than the row", e);
+        LIME_REQUIRE(lime_al16(a.q, a.ld_qkv) && lime_al16(a.k, a.ld_qkv) && lime_al16(a.v, a.ld_qkv) && lime_al16(a.out, a.ldo),
+                     LIME_ERR_UNSUPPORTED, "%s: head_dim > 32 needs 16-byte aligned q / k / v / out and leading dimensions that are multiples of 4", e);
+        if (a.n_seq > 0) *r = LimeAttnRoute{LIME_ATTN_WIDE, (hd + 15) / 16, false, false, LIME_ATTN_STATS_NONE};
+        return LIME_OK;
+    }
+
+    if (form == ROWS) {
+        LIME_REQUIRE(S > 0 && S <= 512 && S % 32 == 0 && (S / 32 <= 4 || S / 32 == 8 || S / 32 == 16), LIME_ERR_UNSUPPORTED,
+                     "%s: S must be 32, 64, 96, 128, 256 or 512 (got %d)", e, S);
+        LIME_REQUIRE(a.ld_qkv >= W && a.ld_qkv % 4 == 0 && al16, LIME_ERR_BAD_ARG,
+                     "%s: heads are 32 columns apart (zero padded), rows 16-byte aligned", e);
+        LIME_REQUIRE(a.ldo >= (int64_t)a.n_head * hd, LIME_ERR_BAD_ARG, "%s: ldo smaller than n_head * head_dim", e);
+    } else {
+        if (form == LSE)
+            LIME_REQUIRE(hs >= hd && S <= 512, LIME_ERR_UNSUPPORTED, "%s: needs head_stride >= head_dim, S <= 512", e);
+        else if (form == DROPOUT)
+            LIME_REQUIRE(S <= 512 && hs >= hd && hs <= 32, LIME_ERR_UNSUPPORTED, "%s: needs S <= 512 and head_dim <= head_stride <= 32", e);
+        else {
+            LIME_REQUIRE(hs >= hd, LIME_ERR_BAD_ARG, "%s: head_stride %d < head_dim %d", e, hs, hd);
+            LIME_REQUIRE(S <= 512, LIME_ERR_UNSUPPORTED, "%s: S %d > 512", e, S);
+        }
+        LIME_REQUIRE(a.ld_qkv >= (int64_t)a.n_head * hs && a.ldo >= (int64_t)a.n_head * hd, LIME_ERR_BAD_ARG,
+                     form == DROPOUT ? "%s: leading dimension smaller than the row" : "%s: leading dimension smaller than n_head * head_dim", e);
+        if (form == DROPOUT) LIME_REQUIRE(drop_p_ok, LIME_ERR_BAD_ARG, "%s: dropout_p outside [0, 1)", e);
+    }
+    if (a.n_seq == 0) return LIME_OK;
+
+    // ---- the route (head_dim <= 32) ----
+    // The split-product kernels: no key mask, heads 32 columns apart, 16-byte rows; one pass at S = 32 / 64 / 128 (the only one that
+    // draws the dropout mask), key blocks at 256 / 512 (the only one that writes lse)
+    const bool one_pass = S == 32 || S == 64 || S == 128, blocked = S == 256 || S == 512;
+    const bool sp = split && a.key_mask == nullptr && hs == 32 && a.ld_qkv % 4 == 0 && a.ld_qkv >= W && al16 &&
+                    (form == LSE ? blocked : form == DROPOUT ? one_pass : one_pass || blocked);
+    if (sp) {
+        *r = LimeAttnRoute{one_pass ? LIME_ATTN_SP : LIME_ATTN_SP_LONG, one_pass ? S / 32 : 0, false, form == ROWS, LIME_ATTN_STATS_NONE};
+        return LIME_OK;
+    }
+    if (form == DROPOUT) {       // the fp32 kernels that draw the mask: one pass up to 128 keys, else the row statistics + key blocks
+        if (S <= 128) {
+            *r = LimeAttnRoute{LIME_ATTN_DROPOUT, S <= 32 ? 32 : (S <= 64 ? 64 : 128), false, false, LIME_ATTN_STATS_NONE};
+            return LIME_OK;
+        }
+        LIME_REQUIRE(a.workspace && a.workspace_floats >= lime_token_attention_stats_workspace(a.n_seq, S, a.n_head), LIME_ERR_BAD_ARG,
+                     "%s: S > 128 needs lime_token_attention_stats_workspace() floats of workspace", e);
+        LIME_REQUIRE((long)a.n_seq * a.n_head * ((S + 127) / 128) < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "%s: too many blocks", e);
+        *r = LimeAttnRoute{LIME_ATTN_DROPOUT_LONG, 0, false, false, split ? LIME_ATTN_STATS_SPLIT : LIME_ATTN_STATS_FP32};
+        return LIME_OK;
+    }
+    // token_attn_kernel.  FAST: no mask, whole 32-key tiles, heads padded to 32 columns, 16-byte aligned operands (the row map implies it)
+    const int tiles = (S + 31) / 32, nt = tiles <= 4 ? tiles : (tiles <= 8 ? 8 : 16);         // the instantiation that holds the key tiles
+    const bool fast = form == ROWS || (a.key_mask == nullptr && S == nt * 32 && hs == 32 && a.ld_qkv % 4 == 0 && al16);
+    *r = LimeAttnRoute{LIME_ATTN_MFMA, nt, fast, form == ROWS, LIME_ATTN_STATS_NONE};
+    return LIME_OK;
+}
+
+namespace {
+
+// launch `which` (0, 1) of the route as rocprofv3 prints it
+void route_name(const LimeAttnRoute& r, int which, char* buf, size_t n) {
+    const char* const map = r.map ? "true" : "false";
+    switch (r.family) {
+        case LIME_ATTN_SP: snprintf(buf, n, "token_attn_sp_kernel<%d, %s>", r.n, map); break;
+        case LIME_ATTN_SP_LONG: snprintf(buf, n, "token_attn_sp_long_kernel<%s>", map); break;
+        case LIME_ATTN_SP_VOCAB: snprintf(buf, n, "token_attn_sp_vocab_kernel<%d>", r.n); break;
+        case LIME_ATTN_MFMA: snprintf(buf, n, "token_attn_kernel<%d, %s, false, %s>", r.n, r.fast ? "true" : "false", map); break;
+        case LIME_ATTN_WIDE: snprintf(buf, n, "wide_fwd_kernel<%d>", r.n); break;
+        case LIME_ATTN_DROPOUT: snprintf(buf, n, "token_attn_fwd_dropout_kernel<%d>", r.n); break;
+        case LIME_ATTN_DROPOUT_LONG:
+            if (which == 0) snprintf(buf, n, "attn_stats_kernel<%s>", r.stats == LIME_ATTN_STATS_SPLIT ? "true" : "false");
+            else snprintf(buf, n, "attn_fwd_long_dropout_kernel");
+            break;
+        default: buf[0] = 0;
+    }
+}
+
+int attention_forward(const lime_token_attention_args& a, void* stream) {
+    LimeAttnRoute r;
+    const int st = lime_attn_route(a, lime_split_mode(), &r);
+    if (st != LIME_OK) return st;
+    switch (r.family) {
+        case LIME_ATTN_NONE: return LIME_OK;
+        case LIME_ATTN_SP: case LIME_ATTN_SP_LONG: case LIME_ATTN_SP_VOCAB: return lime_attn_sp_launch(r, a, (hipStream_t)stream);
+        case LIME_ATTN_MFMA: return lime_attn_mfma_launch(r, a, (hipStream_t)stream);
+        case LIME_ATTN_WIDE: return lime_attn_wide_launch(r, a, (hipStream_t)stream);
+        default: return lime_attn_dropout_launch(r, a, (hipStream_t)stream);
+    }
+}
+
+// the fields every form has
+lime_token_attention_args block(int form, const float* q, const float* k, const float* v, int64_t ld, float* out, int64_t ldo, int32_t n_seq,
+                                int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale) {
+    lime_token_attention_args a = {};
+    a.form = form;
+    a.q = q; a.k = k; a.v = v; a.ld_qkv = ld; a.out = out; a.ldo = ldo;
+    a.n_seq = n_seq; a.S = S; a.n_head = n_head; a.head_dim = head_dim; a.head_stride = head_stride; a.scale = scale;
+    return a;
+}
+
+}  // namespace
+
+extern "C" int lime_token_attention_plan_f32(const lime_token_attention_args* args, lime_token_attention_plan* out) {
+    LIME_REQUIRE(args != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_plan_f32: args is NULL");
+    LIME_REQUIRE(out != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_plan_f32: out is NULL");
+    LIME_REQUIRE(args->form >= PLAIN && args->form <= DROPOUT, LIME_ERR_BAD_ARG, "lime_token_attention_plan_f32: form %d", args->form);
+    *out = lime_token_attention_plan{};
+    LimeAttnRoute r;
+    const int st = lime_attn_route(*args, lime_split_mode(), &r);
+    if (st != LIME_OK || r.family == LIME_ATTN_NONE) return st;
+    out->family = r.family;
+    out->stats_pass = r.stats;
+    out->n_launches = r.stats != LIME_ATTN_STATS_NONE ? 2 : 1;
+    for (int i = 0; i < out->n_launches; ++i) route_name(r, i, out->name[i], sizeof(out->name[i]));
+    return LIME_OK;
+}
+
+extern "C" int lime_token_attention_count_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask,
+                                              const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
+                                              int32_t head_dim, int32_t head_stride, float scale, void* stream) {
+    lime_token_attention_args a = block(COUNT, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
+    a.key_mask = key_mask; a.n_seq_dev = n_seq_dev;
+    return attention_forward(a, stream);
+}
+
+extern "C" int lime_token_attention_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask, float* out,
+                                        int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
+                                        float scale, void* stream) {
+    lime_token_attention_args a = block(PLAIN, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
+    a.key_mask = key_mask;
+    return attention_forward(a, stream);
 }
 
 extern "C" int lime_token_attention_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
                                             float* lse, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
                                             float scale, void* stream) {
-    LIME_REQUIRE(q && k && v && out && lse, LIME_ERR_BAD_ARG, "lime_token_attention_lse_f32: NULL pointer");
-    LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_lse_f32: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", n_seq, S, n_head, head_dim);
-    if (head_dim > 32)
-        return lime_token_attention_wide("lime_token_attention_lse_f32", q, k, v, (long)ld_qkv, nullptr, nullptr, out, (long)ldo, lse, n_seq, S,
-                                         n_head, head_dim, head_stride, scale, nullptr, (hipStream_t)stream);
-    LIME_REQUIRE(head_stride >= head_dim && S <= 512, LIME_ERR_UNSUPPORTED,
-                 "lime_token_attention_lse_f32: needs head_stride >= head_dim, S <= 512");
-    LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_lse_f32: leading dimension smaller than n_head * head_dim");
-    if (n_seq == 0) return LIME_OK;
-    const int vec2 = (head_dim % 2 == 0) && (head_stride % 2 == 0) && (ld_qkv % 2 == 0) &&
-                     (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 8 == 0);
-    hipStream_t s = (hipStream_t)stream;
-    if (head_stride == 32) {                          // S = 256 / 512, padded heads: the split-product kernel with key blocks
-        const int st = lime_token_attention_sp(q, k, v, (long)ld_qkv, nullptr, nullptr, out, (long)ldo, n_seq, S, n_head, head_dim, scale, lse, s);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
-    }
-    AttnP p{q, k, v, (long)ld_qkv, nullptr, out, (long)ldo, n_seq, S, n_head, head_dim, head_stride, scale, n_seq * n_head, vec2, 0, 0, nullptr, nullptr, lse};
-    return launch_nt<false, false>((S + 31) / 32, p, s, "lime_token_attention_f32");
+    lime_token_attention_args a = block(LSE, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
+    a.lse = lse;
+    return attention_forward(a, stream);
 }
 
-extern "C" int lime_token_attention_f32(const float* q, const float* k, const float* v, int64_t ld_qkv,
-                                        const uint8_t* key_mask, float* out, int64_t ldo, int32_t n_seq, int32_t S,
-                                        int32_t n_head, int32_t head_dim, int32_t head_stride, float scale, void* stream) {
-    return lime_token_attention_count_f32(q, k, v, ld_qkv, key_mask, nullptr, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale, stream);
+extern "C" int lime_token_attention_rows_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const int32_t* row_map,
+                                             const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
+                                             int32_t head_dim, float scale, void* stream) {
+    lime_token_attention_args a = block(ROWS, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, 32, scale);
+    a.row_map = row_map; a.n_seq_dev = n_seq_dev;
+    return attention_forward(a, stream);
+}
+
+// The first encoder layer over a per-vocabulary in_proj product (token_attn_sp_f32.hip's header, include/lime_hip.h): q | k | v sit
+// side by side in the table's rows, the word ids take the row map's place.
+extern "C" int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
+                                              const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
+                                              int32_t head_dim, float scale, void* stream) {
+    const int64_t W = (int64_t)n_head * 32;
+    lime_token_attention_args a = block(VOCAB, qkv_vocab, qkv_vocab ? qkv_vocab + W : nullptr, qkv_vocab ? qkv_vocab + 2 * W : nullptr, ld,
+                                        out, ldo, n_seq, S, n_head, head_dim, 32, scale);
+    a.pos_rows = pos_rows; a.row_map = ids; a.n_seq_dev = n_seq_dev;
+    return attention_forward(a, stream);
+}
+
+extern "C" int lime_token_attention_dropout_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
+                                                int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
+                                                float scale, float dropout_p, uint64_t seed, uint32_t site, float* workspace,
+                                                int64_t workspace_floats, void* stream) {
+    lime_token_attention_args a = block(DROPOUT, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
+    a.dropout_p = dropout_p; a.dropout_seed = seed; a.dropout_site = site; a.workspace = workspace; a.workspace_floats = workspace_floats;
+    return attention_forward(a, stream);
 }
 
 int lime_token_attention_bf16_mfma(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t ld_qkv, uint16_t* out, int64_t ldo,
@@ -613,9 +754,9 @@ extern "C" int lime_token_attention_bf16(const uint16_t* q, const uint16_t* k, c
     hipStream_t s = (hipStream_t)stream;
     {   // S <= 128: scores and P.V on the bf16 matrix cores; longer sequences: the fp32-core variant below
         const int st = lime_token_attention_bf16_mfma(q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, scale, pad, s);
-        if (st != 1) return st;
+        if (st != LIME_NOT_APPLICABLE) return st;
     }
     AttnP p{(const float*)q, (const float*)k, (const float*)v, (long)ld_qkv, nullptr, (float*)out, (long)ldo, n_seq, S, n_head,
             head_dim, 32, scale, n_seq * n_head, 1, 0, pad, nullptr, nullptr};
-    return launch_nt<true, false>(S / 32, p, s, "lime_token_attention_bf16");
+    return launch_nt<true, true, false>(S / 32, p, s, "lime_token_attention_bf16");
 }

@@ -19,7 +19,7 @@
 // positional table: one fp32 add per element where the fragment is consumed (stash() for K / V, before the qscale multiply for Q), so
 // the result is bit for bit that of the dense kernel over the materialised rows.
 #include "common.h"
-#include "gemm_pp.h"
+#include "token_attn.h"
 #include "dev_helpers.h"
 #include "split_mfma.h"
 #include "dropout.h"
@@ -484,75 +484,38 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
     }
 }
 
+// token_attn_sp_kernel<NT, MAP>, or token_attn_sp_vocab_kernel<NT> with the positional rows
 template <int NT>
-int launch(SpAttnP p, hipStream_t s) {
+int launch(SpAttnP p, bool map, const float* pos, hipStream_t s) {
     constexpr int G = 4 / NT;
     p.n_group = (p.n_pair + G - 1) / G;
-    const long blocks = lime_persistent_grid(p.n_group, 2);
-    if (p.row_map) hipLaunchKernelGGL((token_attn_sp_kernel<NT, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((token_attn_sp_kernel<NT, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return lime_check_launch("token_attn_sp_kernel");
-}
-
-template <int NT>
-int launch_vocab(SpAttnP p, const float* pos, hipStream_t s) {
-    constexpr int G = 4 / NT;
-    p.n_group = (p.n_pair + G - 1) / G;
-    const long blocks = lime_persistent_grid(p.n_group, 2);
-    hipLaunchKernelGGL((token_attn_sp_vocab_kernel<NT>), dim3((unsigned)blocks), dim3(256), 0, s, p, pos);
-    return lime_check_launch("token_attn_sp_vocab_kernel");
+    const dim3 blocks((unsigned)lime_persistent_grid(p.n_group, 2));
+    if (pos) hipLaunchKernelGGL((token_attn_sp_vocab_kernel<NT>), blocks, dim3(256), 0, s, p, pos);
+    else if (map) hipLaunchKernelGGL((token_attn_sp_kernel<NT, true>), blocks, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((token_attn_sp_kernel<NT, false>), blocks, dim3(256), 0, s, p);
+    return lime_check_launch(pos ? "token_attn_sp_vocab_kernel" : "token_attn_sp_kernel");
 }
 
 }  // namespace
 
-// LIME_OK / error: launched; LIME_PP_NOT_APPLICABLE: the caller takes token_attn_f32.hip's kernels (masks, other lengths, unpadded
-// heads, the split product switched off).  lse (optional, S = 256 / 512 only): [tokens, n_head] log2-domain log-sum-exp.
-int lime_token_attention_sp(const float* q, const float* k, const float* v, long ld, const int* row_map, const int* n_seq_dev,
-                            float* out, long ldo, int n_seq, int S, int n_head, int hd, float scale, float* lse, hipStream_t s,
-                            const LimeDropout* drop) {
-    if (!(lime_split_mode() & 1)) return LIME_PP_NOT_APPLICABLE;
-    const bool is_long = S == 256 || S == 512;
-    if (!(S == 32 || S == 64 || S == 128 || is_long)) return LIME_PP_NOT_APPLICABLE;
-    if (lse && !is_long) return LIME_PP_NOT_APPLICABLE;
-    if (drop && drop->thresh != 0 && (is_long || row_map)) return LIME_PP_NOT_APPLICABLE;       // probability dropout: the S <= 128 kernel only
-    if (ld % 4 != 0 || ld < (long)n_head * 32 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16) != 0 || hd > 32) return LIME_PP_NOT_APPLICABLE;
-    SpAttnP p{q, k, v, ld, out, ldo, n_seq, S, n_head, hd, scale, n_seq * n_head, 0, row_map, n_seq_dev, drop ? *drop : LimeDropout{0, 0, 1.f}};
-    if (is_long) {
-        const long n_task = (long)p.n_pair * (S / 128);
+// The split-product families of the fp32 forward (token_attn_f32.hip chose r): the one-pass kernel (S = 32 / 64 / 128; the dropout form
+// draws its mask on the probability registers), the key-block kernel (S = 256 / 512; optionally writes a.lse, the [tokens, n_head]
+// log2-domain log-sum-exp) and the vocab kernel (a.row_map holds word ids, a.pos_rows the positional rows).
+int lime_attn_sp_launch(const LimeAttnRoute& r, const lime_token_attention_args& a, hipStream_t s) {
+    SpAttnP p{a.q, a.k, a.v, (long)a.ld_qkv, a.out, (long)a.ldo, a.n_seq, a.S, a.n_head, a.head_dim, a.scale, a.n_seq * a.n_head, 0,
+              a.row_map, a.n_seq_dev, lime_attn_dropout(a)};
+    if (r.family == LIME_ATTN_SP_LONG) {
+        const long n_task = (long)p.n_pair * (a.S / 128);
         const long blocks = lime_persistent_grid(n_task, 2);
-        if (row_map) hipLaunchKernelGGL((token_attn_sp_long_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, p, lse);
-        else hipLaunchKernelGGL((token_attn_sp_long_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, p, lse);
+        if (r.map) hipLaunchKernelGGL((token_attn_sp_long_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, p, a.lse);
+        else hipLaunchKernelGGL((token_attn_sp_long_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, p, a.lse);
         return lime_check_launch("token_attn_sp_long_kernel");
     }
-    switch (S / 32) {
-        case 1: return launch<1>(p, s);
-        case 2: return launch<2>(p, s);
-        default: return launch<4>(p, s);
+    const float* const pos = r.family == LIME_ATTN_SP_VOCAB ? a.pos_rows : nullptr;
+    switch (r.n) {
+        case 1: return launch<1>(p, r.map, pos, s);
+        case 2: return launch<2>(p, r.map, pos, s);
+        case 4: return launch<4>(p, r.map, pos, s);
     }
-}
-
-// Attention of the first encoder layer over a per-vocabulary in_proj product (see the header of this file and include/lime_hip.h).
-// LIME_PP_NOT_APPLICABLE (the caller keeps the in_proj + row-map path): the split product switched off, or a shape outside
-// S in {32, 64, 128}, head_dim <= 32, 16-byte aligned rows.
-extern "C" int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
-                                              const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                              int32_t head_dim, float scale, void* stream) {
-    LIME_REQUIRE(qkv_vocab && pos_rows && ids && out, LIME_ERR_BAD_ARG, "lime_token_attention_vocab_f32: NULL pointer");
-    LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_vocab_f32: bad dims n_seq=%d S=%d n_head=%d head_dim=%d", n_seq, S, n_head, head_dim);
-    LIME_REQUIRE(ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG, "lime_token_attention_vocab_f32: ldo smaller than n_head * head_dim");
-    if (!(lime_split_mode() & 1)) return LIME_PP_NOT_APPLICABLE;
-    const int64_t W = (int64_t)n_head * 32;
-    if (!(S == 32 || S == 64 || S == 128) || head_dim > 32 || ld % 4 != 0 || ld < 3 * W || ld > (1 << 21) ||     // 32-bit offsets into pos_rows
-        (((uintptr_t)qkv_vocab | (uintptr_t)pos_rows) % 16) != 0)
-        return LIME_PP_NOT_APPLICABLE;
-    if (n_seq == 0) return LIME_OK;
-    SpAttnP p{qkv_vocab, qkv_vocab + W, qkv_vocab + 2 * W, (long)ld, out, (long)ldo, n_seq, S, n_head, head_dim, scale, n_seq * n_head, 0,
-              ids, n_seq_dev, LimeDropout{0, 0, 1.f}};
-    hipStream_t s = (hipStream_t)stream;
-    switch (S / 32) {
-        case 1: return launch_vocab<1>(p, pos_rows, s);
-        case 2: return launch_vocab<2>(p, pos_rows, s);
-        default: return launch_vocab<4>(p, pos_rows, s);
-    }
+    LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "%s: token_attn_sp_kernel<%d, ...> is not built", lime_attn_entry(a.form), r.n);
 }

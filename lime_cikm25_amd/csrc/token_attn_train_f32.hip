@@ -9,6 +9,7 @@
 #include "dev_helpers.h"
 #include "dropout.h"
 #include "gemm_pp.h"
+#include "token_attn.h"
 #include "split_mfma.h"
 
 using namespace lime_dev;
@@ -1045,7 +1046,7 @@ static int attention_bwd(const float* q, const float* k, const float* v, int64_t
         if (key_mask == nullptr && (lime_split_mode() & 1)) {      // every product on the bf16 matrix cores (token_attn_bwd_sp_f32.hip)
             const int st = lime_token_attention_bwd_sp(q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride,
                                                        scale, drop, s);
-            if (st != LIME_PP_NOT_APPLICABLE) return st;
+            if (st != LIME_NOT_APPLICABLE) return st;
         }
         return launch_attn_bwd<128>(q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride, scale, drop, key_mask, s);
     }
@@ -1103,46 +1104,28 @@ extern "C" int lime_token_attention_bwd_lse_f32(const float* q, const float* k, 
                          workspace, workspace_floats, 0.f, 0, 0, nullptr, lse, stream);
 }
 
-extern "C" int lime_token_attention_dropout_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
-                                                int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
-                                                float scale, float dropout_p, uint64_t seed, uint32_t site, float* workspace,
-                                                int64_t workspace_floats, void* stream) {
-    LIME_REQUIRE(q && k && v && out, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: null pointer");
-    LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: bad dimensions");
-    if (head_dim > 32) {                                       // wide heads: token_attn_wide_f32.hip (one pass at every S, no workspace)
-        LIME_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: dropout_p outside [0, 1)");
-        const LimeDropout wide_drop = lime_make_dropout(dropout_p, seed, site);
-        return lime_token_attention_wide("lime_token_attention_dropout_f32", q, k, v, (long)ld_qkv, nullptr, nullptr, out, (long)ldo, nullptr,
-                                         n_seq, S, n_head, head_dim, head_stride, scale, &wide_drop, (hipStream_t)stream);
+// The fp32 kernels of the dropout forward (token_attn_f32.hip chose r and made the checks): the one-pass kernel's length bucket
+// r.n, or the row statistics (r.stats: on which arithmetic) + the key-block kernel.
+int lime_attn_dropout_launch(const LimeAttnRoute& r, const lime_token_attention_args& a, hipStream_t s) {
+    const LimeDropout drop = lime_attn_dropout(a);
+    if (r.family == LIME_ATTN_DROPOUT) {
+        switch (r.n) {
+            case 32: return launch_attn_fwd_dropout<32>(a.q, a.k, a.v, a.ld_qkv, a.out, a.ldo, a.n_seq, a.S, a.n_head, a.head_dim, a.head_stride, a.scale, drop, s);
+            case 64: return launch_attn_fwd_dropout<64>(a.q, a.k, a.v, a.ld_qkv, a.out, a.ldo, a.n_seq, a.S, a.n_head, a.head_dim, a.head_stride, a.scale, drop, s);
+            case 128: return launch_attn_fwd_dropout<128>(a.q, a.k, a.v, a.ld_qkv, a.out, a.ldo, a.n_seq, a.S, a.n_head, a.head_dim, a.head_stride, a.scale, drop, s);
+        }
+        LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "lime_token_attention_dropout_f32: token_attn_fwd_dropout_kernel<%d> is not built", r.n);
     }
-    LIME_REQUIRE(S <= 512 && head_stride >= head_dim && head_stride <= 32, LIME_ERR_UNSUPPORTED,
-                 "lime_token_attention_dropout_f32: needs S <= 512 and head_dim <= head_stride <= 32");
-    LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_dropout_f32: leading dimension smaller than the row");
-    LIME_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_token_attention_dropout_f32: dropout_p outside [0, 1)");
-    if (n_seq == 0) return LIME_OK;
-    const LimeDropout drop = lime_make_dropout(dropout_p, seed, site);
-    hipStream_t s = (hipStream_t)stream;
-    if (head_stride == 32 && (S == 32 || S == 64 || S == 128)) {       // the split-product forward with the mask on its probability registers
-        const int st = lime_token_attention_sp(q, k, v, (long)ld_qkv, nullptr, nullptr, out, (long)ldo, n_seq, S, n_head, head_dim, scale, nullptr, s, &drop);
-        if (st != LIME_PP_NOT_APPLICABLE) return st;
-    }
-    if (S <= 32) return launch_attn_fwd_dropout<32>(q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale, drop, s);
-    if (S <= 64) return launch_attn_fwd_dropout<64>(q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale, drop, s);
-    if (S <= 128) return launch_attn_fwd_dropout<128>(q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale, drop, s);
-    LIME_REQUIRE(workspace && workspace_floats >= lime_token_attention_stats_workspace(n_seq, S, n_head), LIME_ERR_BAD_ARG,
-                 "lime_token_attention_dropout_f32: S > 128 needs lime_token_attention_stats_workspace() floats of workspace");
-    const int n_blk = (S + LB - 1) / LB;
-    const long n_prob = (long)n_seq * n_head;
-    LIME_REQUIRE(n_prob * n_blk < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_token_attention_dropout_f32: too many blocks");
-    int st = launch_attn_stats((lime_split_mode() & 1) != 0, q, k, ld_qkv, nullptr, 0, nullptr, 0, workspace, n_prob, S, n_head, head_dim,
-                               head_stride, scale, n_blk, s);
+    const int n_blk = (a.S + LB - 1) / LB;
+    const long n_prob = (long)a.n_seq * a.n_head;
+    int st = launch_attn_stats(r.stats == LIME_ATTN_STATS_SPLIT, a.q, a.k, a.ld_qkv, nullptr, 0, nullptr, 0, a.workspace, n_prob, a.S, a.n_head,
+                               a.head_dim, a.head_stride, a.scale, n_blk, s);
     if (st != LIME_OK) return st;
     constexpr int BYTES = (3 * LB * AB_LD + LB * (LB + 2)) * 4;
     static int reserved = 0;
     st = lime_reserve_lds((const void*)attn_fwd_long_dropout_kernel, BYTES, reserved, "lime_token_attention_dropout_f32");
     if (st != LIME_OK) return st;
-    attn_fwd_long_dropout_kernel<<<(unsigned)(n_prob * n_blk), 512, BYTES, s>>>(q, k, v, ld_qkv, workspace, out, ldo, S, n_head, head_dim,
-                                                                               head_stride, scale, n_blk, drop);
+    attn_fwd_long_dropout_kernel<<<(unsigned)(n_prob * n_blk), 512, BYTES, s>>>(a.q, a.k, a.v, a.ld_qkv, a.workspace, a.out, a.ldo, a.S, a.n_head,
+                                                                               a.head_dim, a.head_stride, a.scale, n_blk, drop);
     return lime_check_launch("attn_fwd_long_dropout_kernel");
 }

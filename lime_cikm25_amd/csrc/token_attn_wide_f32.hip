@@ -20,6 +20,7 @@
 #include "dev_helpers.h"
 #include "dropout.h"
 #include "gemm_pp.h"
+#include "token_attn.h"
 
 using namespace lime_dev;
 
@@ -377,19 +378,23 @@ int launch_wide(int which, const WideP& p, unsigned grid, hipStream_t s, const c
     return lime_check_launch(entry);
 }
 
-int launch_wide_nk(int which, const WideP& p, unsigned grid, hipStream_t s, const char* entry) {
-    switch ((p.hd + 15) / 16) {
+// nk = ceil(head_dim / 16): the instantiation that holds the padded head
+int launch_wide_nk(int which, int nk, const WideP& p, unsigned grid, hipStream_t s, const char* entry) {
+    switch (nk) {
         case 3: return launch_wide<3>(which, p, grid, s, entry);
         case 4: return launch_wide<4>(which, p, grid, s, entry);
         case 5: return launch_wide<5>(which, p, grid, s, entry);
         case 6: return launch_wide<6>(which, p, grid, s, entry);
         case 7: return launch_wide<7>(which, p, grid, s, entry);
-        default: return launch_wide<8>(which, p, grid, s, entry);
+        case 8: return launch_wide<8>(which, p, grid, s, entry);
     }
+    LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "%s: the wide kernels are not built for %d 16-column steps", entry, nk);
 }
 
+}  // namespace
+
 // what every wide call checks before a launch
-int wide_limits(const char* entry, int S, int n_head, int hd, int hs, long n_seq) {
+int lime_attn_wide_limits(const char* entry, int S, int n_head, int hd, int hs, long n_seq) {
     LIME_REQUIRE(hd > 32 && hd <= 128 && hd % 4 == 0 && S <= 512 && hs >= hd && hs % 4 == 0, LIME_ERR_UNSUPPORTED,
                  "%s: head_dim > 32 needs head_dim <= 128, head_dim %% 4 == 0, head_stride %% 4 == 0, head_stride >= head_dim and S <= 512 "
                  "(got head_dim=%d head_stride=%d S=%d); head_dim <= 32 takes any head_dim", entry, hd, hs, S);
@@ -397,21 +402,13 @@ int wide_limits(const char* entry, int S, int n_head, int hd, int hs, long n_seq
     return LIME_OK;
 }
 
-}  // namespace
-
-int lime_token_attention_wide(const char* entry, const float* q, const float* k, const float* v, long ld, const unsigned char* key_mask,
-                              const int* n_seq_dev, float* out, long ldo, float* lse, int n_seq, int S, int n_head, int hd, int hs,
-                              float scale, const LimeDropout* drop, hipStream_t s) {
-    if (const int st = wide_limits(entry, S, n_head, hd, hs, n_seq)) return st;
-    LIME_REQUIRE(ld >= (long)n_head * hs && ldo >= (long)n_head * hd, LIME_ERR_BAD_ARG, "%s: leading dimension smaller than the row", entry);
-    LIME_REQUIRE(lime_al16(q, ld) && lime_al16(k, ld) && lime_al16(v, ld) && lime_al16(out, ldo), LIME_ERR_UNSUPPORTED,
-                 "%s: head_dim > 32 needs 16-byte aligned q / k / v / out and leading dimensions that are multiples of 4", entry);
-    if (n_seq == 0) return LIME_OK;
+// The forward of every fp32 form at head_dim > 32 (token_attn_f32.hip has made the checks): r.n is NK
+int lime_attn_wide_launch(const LimeAttnRoute& r, const lime_token_attention_args& a, hipStream_t s) {
     WideP p{};
-    p.q = q; p.k = k; p.v = v; p.ld = ld; p.mask = key_mask; p.n_seq_dev = n_seq_dev; p.out = out; p.ldo = ldo; p.lse = lse;
-    p.S = S; p.n_head = n_head; p.hd = hd; p.hs = hs; p.n_blk = (S + WB - 1) / WB; p.scale = scale;
-    p.drop = drop != nullptr ? *drop : lime_make_dropout(0.f, 0, 0);
-    return launch_wide_nk(0, p, (unsigned)((long)n_seq * n_head * p.n_blk), s, entry);
+    p.q = a.q; p.k = a.k; p.v = a.v; p.ld = a.ld_qkv; p.mask = a.key_mask; p.n_seq_dev = a.n_seq_dev; p.out = a.out; p.ldo = a.ldo; p.lse = a.lse;
+    p.S = a.S; p.n_head = a.n_head; p.hd = a.head_dim; p.hs = a.head_stride; p.n_blk = (a.S + WB - 1) / WB; p.scale = a.scale;
+    p.drop = lime_attn_dropout(a);
+    return launch_wide_nk(0, r.n, p, (unsigned)((long)a.n_seq * a.n_head * p.n_blk), s, lime_attn_entry(a.form));
 }
 
 extern "C" int64_t lime_token_attention_bwd_workspace_wide(int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim) {
@@ -423,7 +420,7 @@ int lime_token_attention_wide_bwd(const char* entry, const float* q, const float
                                   float* dq, float* dk, float* dv, long ldd, int n_seq, int S, int n_head, int hd, int hs, float scale,
                                   float* workspace, long workspace_floats, const LimeDropout& drop, const unsigned char* key_mask,
                                   hipStream_t s) {
-    if (const int st = wide_limits(entry, S, n_head, hd, hs, n_seq)) return st;
+    if (const int st = lime_attn_wide_limits(entry, S, n_head, hd, hs, n_seq)) return st;
     LIME_REQUIRE(ld >= (long)n_head * hs && ldd >= (long)n_head * hs && ldo >= (long)n_head * hd, LIME_ERR_BAD_ARG,
                  "%s: leading dimension smaller than the row", entry);
     LIME_REQUIRE(lime_al16(q, ld) && lime_al16(k, ld) && lime_al16(v, ld) && lime_al16(dout, ldo) && lime_al16(dq, ldd) &&
@@ -436,6 +433,6 @@ int lime_token_attention_wide_bwd(const char* entry, const float* q, const float
     p.q = q; p.k = k; p.v = v; p.ld = ld; p.mask = key_mask; p.dout = dout; p.ldg = ldo; p.dq = dq; p.dk = dk; p.dv = dv; p.ldd = ldd;
     p.stats = workspace; p.S = S; p.n_head = n_head; p.hd = hd; p.hs = hs; p.n_blk = (S + WB - 1) / WB; p.scale = scale; p.drop = drop;
     const unsigned grid = (unsigned)((long)n_seq * n_head * p.n_blk);
-    if (const int st = launch_wide_nk(1, p, grid, s, entry)) return st;      // statistics + dQ
-    return launch_wide_nk(2, p, grid, s, entry);                             // dK, dV (reads the statistics)
+    if (const int st = launch_wide_nk(1, (hd + 15) / 16, p, grid, s, entry)) return st;      // statistics + dQ
+    return launch_wide_nk(2, (hd + 15) / 16, p, grid, s, entry);                             // dK, dV (reads the statistics)
 }

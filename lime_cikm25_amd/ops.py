@@ -350,6 +350,44 @@ def token_attention_vocab(qkv_vocab, pos_rows, ids, n_seq_dev, n_seq, S, n_head,
     return out
 
 
+def token_attention_plan(form, q=None, k=None, v=None, n_seq=0, S=0, n_head=0, head_dim=0, scale=1.0, key_mask=None, out=None,
+                         head_stride=None, n_seq_dev=None, lse=None, row_map=None, qkv_vocab=None, pos_rows=None, ids=None, p=0.0, seed=0,
+                         site=0):
+    """What the fp32 forward wrapper of ``form`` ('plain' / 'count' / 'lse': ``token_attention``; 'rows': ``token_attention_rows``;
+    'vocab': ``token_attention_vocab``; 'dropout': ``token_attention_dropout``) would run for the same arguments, without running it
+    (``lime_token_attention_plan_f32``): a dict with ``family`` ('sp', 'sp_long', 'sp_vocab', 'mfma', 'wide', 'dropout',
+    'dropout_long'; None where nothing is launched), ``stats_pass`` (None / 'fp32' / 'split') and ``kernels`` (the instantiations in
+    launch order, as rocprofv3 prints them).  None where the vocab form does not cover the call; a call the entry would refuse raises the
+    same LimeHipError.  The tensors' shapes are not checked here: only their addresses and leading dimensions reach the plan."""
+    a = _lib.TokenAttentionArgs()
+    a.form = _lib.ATTN_FORM[form]
+    a.n_seq, a.S, a.n_head, a.head_dim, a.scale = n_seq, S, n_head, head_dim, scale
+    a.head_stride = 32 if form in ('rows', 'vocab') else (head_dim if head_stride is None else head_stride)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    if form == 'vocab':
+        W = n_head * 32
+        a.q, a.k, a.v = (qkv_vocab.data_ptr() + 4 * W * i for i in range(3))
+        a.ld_qkv, a.pos_rows, a.row_map = _ld(qkv_vocab), ptr(pos_rows), ptr(ids)
+    else:
+        a.q, a.k, a.v, a.ld_qkv, a.row_map = ptr(q), ptr(k), ptr(v), _ld(q), ptr(row_map)
+    if out is None:                                     # the wrappers allocate it: any aligned address stands for it
+        a.out, a.ldo = 256, n_head * head_dim
+    else:
+        a.out, a.ldo = out.data_ptr(), _ld(out)
+    a.key_mask, a.n_seq_dev, a.lse = ptr(_mask_u8(key_mask, 'key_mask')), ptr(n_seq_dev), ptr(lse)
+    if form == 'dropout':
+        a.dropout_p, a.dropout_seed, a.dropout_site = p, seed, site
+        a.workspace_floats = 0 if head_dim > 32 else _lib.load().lime_token_attention_stats_workspace(n_seq, S, n_head)
+        a.workspace = 256 if a.workspace_floats else None
+    plan = _lib.TokenAttentionPlan()
+    st = _lib.load().lime_token_attention_plan_f32(ctypes.byref(a), ctypes.byref(plan))
+    if st == NOT_APPLICABLE:
+        return None
+    check(st, 'lime_token_attention_plan_f32')
+    return dict(family=_lib.ATTN_FAMILY[plan.family], stats_pass=_lib.ATTN_STATS[plan.stats_pass],
+                kernels=[plan.name[i].value.decode() for i in range(plan.n_launches)])
+
+
 class Compacted:
     """Index lists of ``compact_sequences`` (all int32 device tensors; see lime_compact_sequences in include/lime_hip.h)."""
     __slots__ = ('n_seq', 'S', 'cap', 'seq_inv', 'seq_src', 'ids_c', 'row_map', 'tok_ids', 'tok_rows', 'counts')

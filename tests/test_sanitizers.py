@@ -41,6 +41,15 @@ def _driver_source():
               '    CHECK(lime_linear_plan_f32(&a, 256, &p) == 0); CHECK(p.family == LIME_LINEAR_SP && strlen(p.name) > 0);',
               '    a.M = 1700; CHECK(lime_linear_plan_f32(&a, 256, &p) == 0); CHECK(p.family == LIME_LINEAR_MID && p.tiles > 0);',
               '    a.K = 62; a.lda = a.ldw = 62; CHECK(lime_linear_plan_f32(&a, 256, &p) == LIME_ERR_UNSUPPORTED); n += 3; }']
+    # the attention plan likewise: one call taken (S = 96: token_attn_kernel under either split mode), one refused, one not applicable
+    lines += ['  { lime_token_attention_args a; lime_token_attention_plan p; memset(&a, 0, sizeof a);',
+              '    a.q = (const float*)0x10000; a.k = a.q + 96; a.v = a.q + 192; a.out = (float*)0x90000; a.ld_qkv = 288; a.ldo = 60;',
+              '    a.n_seq = 3; a.S = 96; a.n_head = 3; a.head_dim = 20; a.head_stride = 32; a.scale = 0.25f; a.form = LIME_ATTN_FORM_PLAIN;',
+              '    CHECK(lime_token_attention_plan_f32(&a, &p) == 0); CHECK(p.family == LIME_ATTN_MFMA && p.n_launches == 1);',
+              '    CHECK(strcmp(p.name[0], "token_attn_kernel<3, true, false, false>") == 0);',
+              '    a.S = 513; CHECK(lime_token_attention_plan_f32(&a, &p) == LIME_ERR_UNSUPPORTED); CHECK(p.n_launches == 0);',
+              '    a.S = 96; a.form = LIME_ATTN_FORM_VOCAB; a.pos_rows = (const float*)0x30000; a.row_map = (const int32_t*)0x80000;',
+              '    CHECK(lime_token_attention_plan_f32(&a, &p) == LIME_NOT_APPLICABLE); n += 3; }']
     lines += ['  CHECK(lime_token_attention_bwd_workspace(1760, 512, 10) > lime_token_attention_stats_workspace(1760, 512, 10));',
               '  CHECK(lime_token_attention_bwd_workspace(1 << 20, 512, 16) > 0);      /* 64-bit arithmetic: no signed overflow */',
               '  CHECK(lime_token_attention_bwd_workspace(0, 32, 1) == 0);',
