@@ -1189,6 +1189,34 @@ int lime_seq_pack_f32(const float* src, const int32_t* lens, const int64_t* offs
 int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* offsets, const int32_t* lens, const int32_t* idx,
                              const float* tm, float* out, int32_t cap, int32_t S, int32_t C, const int32_t* n_rows_dev, void* stream);
 
+/* =====================================================================================================
+ * Pool recommendation (Model.score_pool / Model.recommend).
+ *
+ * lime_grouped_match_f32 (csrc/grouped_match_f32.hip): the function of lime_interest_match_f32 for GROUPS of pairs that share one
+ * refined history -- a group is one (user, candidate topic), its pairs are the pool's news of that topic.  kp [G H, A] and g [G H, D]
+ * per group; qp [P, A], cand [P, D], remaining [P] (read when use_weight != 0) per pair; offsets int64 [G + 1] on the device: the pairs
+ * of group i are rows offsets[i] .. offsets[i + 1] - 1 (every offset is clamped into [0, P] by the kernel; pairs outside every group
+ * are not written).  For pair p of group i:
+ *     s[h] = kp[i H + h, :] . qp[p, :] * scale,  alpha = softmax_h(s),  logits[p] = (sum_h alpha[h] (g[i H + h, :] . cand[p, :])) * w(remaining[p])
+ * with w the weight of lime_interest_match_f32 (alpha_s, beta_s, use_weight, use_penalty).  Exact fp32 on v_mfma_f32_16x16x4_f32, a
+ * workgroup per 64-pair tile of a group; fixed-order sums, no atomics: a pair's bits depend neither on P, G, the group's position nor
+ * the pair's place in its tile.  1 <= H <= 128, A and D multiples of 4 up to 2048 (LIME_ERR_UNSUPPORTED otherwise); kp, g, qp, cand
+ * 16-byte aligned (LIME_ERR_BAD_ARG otherwise).  H = 1 is the match of one pooled user vector g[i] per group (alpha = 1).
+ *
+ * lime_topk_rows_f32 (csrc/topk_rows_f32.hip): per row u < U of scores [U, C] (leading dimension ld >= C) the k best entries:
+ * positions int32 [U, k] (column indices) and top_scores fp32 [U, k] (the input's bits at those positions), in descending order of
+ * the score; equal scores -- +0.0 and -0.0 are equal -- lower position first; a NaN ranks behind every number, NaNs in position
+ * order.  Slots behind the C-th hold position -1 and score -inf.  1 <= k <= 128, 1 <= C < 2^31, U <= 65535 (LIME_ERR_UNSUPPORTED
+ * otherwise).  A row is split over workgroups of 4096 columns, their lists merged by one workgroup per row; the result is the k
+ * largest of distinct integer keys and so independent of the split and the run.  workspace: lime_topk_rows_workspace(U, C) floats
+ * (0 for C <= 4096: workspace may be NULL), 8-byte aligned. */
+int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
+                           const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D, float scale,
+                           float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
+int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
+int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
+                       float* workspace, int64_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,19 @@ __device__ __forceinline__ void lds_barrier() {
 
 __device__ __forceinline__ float lime_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// The remaining-lifetime weight (util.py:23-49), the expression of lime_interest_match_f32 / lime_lifetime_score_f32:
+// positive_mask * w + negative_mask * beta * w with the expired penalty, sigmoid(alpha |r|) without
+__device__ __forceinline__ float lifetime_weight(float r, float alpha_s, float beta_s, int use_penalty) {
+    float w;
+    if (use_penalty) {
+        w = lime_sigmoid(alpha_s * r);
+        w = (r >= 0.f ? 1.f : 0.f) * w + (r < 0.f ? 1.f : 0.f) * beta_s * w;
+    } else {
+        w = lime_sigmoid(alpha_s * fabsf(r));
+    }
+    return w;
+}
+
 // XCD-aware bijective remap of a 1-D grid: the 8 XCDs take workgroups round-robin by blockIdx, so
 // logical ids are handed out such that each XCD walks one contiguous range (tiles that share
 // operand panels then share an L2).  Placement only changes speed, never results.

@@ -50,18 +50,6 @@ __device__ __forceinline__ f32x4 axpy4(float a, f32x4 x, f32x4 acc) {
     return acc;
 }
 
-// util.py:23-49, the expression of lime_interest_match_f32 / lime_lifetime_score_f32
-__device__ __forceinline__ float lifetime_weight(float r, float alpha_s, float beta_s, int use_penalty) {
-    float w;
-    if (use_penalty) {
-        w = lime_sigmoid(alpha_s * r);
-        w = (r >= 0.f ? 1.f : 0.f) * w + (r < 0.f ? 1.f : 0.f) * beta_s * w;
-    } else {
-        w = lime_sigmoid(alpha_s * fabsf(r));
-    }
-    return w;
-}
-
 template <int W, bool VEC>
 __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict__ hidden, long ldh, const float* __restrict__ w2,
                                                           const float* __restrict__ x, long ldx,

@@ -349,15 +349,153 @@ class Model(nn.Module):
     def _remaining_lifetime(self, behaviors, rows, cand_idx):
         """The remaining lifetime of the rows' candidates per config.lifetime_type, as util.py:98-106 derives it from the batch."""
         b = behaviors
+        return self._lifetime_rule(b.cand_freshness[rows], lambda: b.cand_lifetime[rows],
+                                   lambda: b.corpus.news_category[cand_idx.reshape(-1).long()])
+
+    def _lifetime_rule(self, freshness, lifetime, category):
+        """util.py:98-106: the remaining lifetime of candidates from their freshness and, per config.lifetime_type, the fixed lifetime,
+        the lifetime of their category or their own (user, topic) lifetime.  ``lifetime`` / ``category``: callables that give the
+        tensor (shaped like ``freshness`` / with as many elements), asked only under the type that reads it."""
         lt = getattr(self.config, 'lifetime_type', 'user_topic')
         if lt == 'fixed':
-            return self.config.fixed_lifetime - b.cand_freshness[rows]
+            return self.config.fixed_lifetime - freshness
         if lt == 'topic_wise':
-            cmap = torch.as_tensor(self.config.category_lifetime_map, dtype=torch.float32, device=rows.device)
-            return cmap[b.corpus.news_category[cand_idx.reshape(-1).long()].long()].view_as(b.cand_freshness[rows]) - b.cand_freshness[rows]
+            cmap = torch.as_tensor(self.config.category_lifetime_map, dtype=torch.float32, device=freshness.device)
+            return cmap[category().long()].view_as(freshness) - freshness
         if lt == 'user_topic':
-            return b.cand_lifetime[rows] - b.cand_freshness[rows]
+            return lifetime() - freshness
         raise ValueError('Invalid lifetime_type')
+
+    def _check_pool(self, news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
+                    pairs_per_pass, k=None):
+        """The host-side refusals of score_pool / recommend (ValueError, before any launch) -> (U, H, C)."""
+        if self.reads_content_mask:
+            raise ValueError('content_encoder \'CNE\' has no per-news content cache (its gates read the partner news of the encoder call, '
+                             'build_news_cache): score_pool / recommend cannot serve it -- score the pairs with score_behaviors')
+        if news_cache.dim() != 2 or news_cache.shape[1] == 0:
+            raise ValueError('news_cache must be the [n_news, width] tensor of build_news_cache, got %s' % (tuple(news_cache.shape),))
+        if hist_index.dim() != 2:
+            raise ValueError('hist_index must be [U, H], got %s' % (tuple(hist_index.shape),))
+        U, H = hist_index.shape
+        for t, name in ((hist_mask, 'hist_mask'), (user_freshness, 'user_freshness'), (user_lifetime, 'user_lifetime')):
+            if tuple(t.shape) != (U, H):
+                raise ValueError('%s must be [U, H] = [%d, %d] like hist_index, got %s' % (name, U, H, tuple(t.shape)))
+        if cand_index.dim() != 1 or cand_index.numel() < 1:
+            raise ValueError('cand_index must be [C] with C >= 1 -- ONE pool for all users -- got %s' % (tuple(cand_index.shape),))
+        C = cand_index.numel()
+        if hist_index.dtype not in (torch.int32, torch.int64) or cand_index.dtype not in (torch.int32, torch.int64):
+            raise ValueError('hist_index and cand_index must be int32 or int64 news indices, got %s and %s' % (hist_index.dtype, cand_index.dtype))
+        for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
+            if tuple(t.shape) not in ((C,), (U, C)):
+                raise ValueError('%s must be [C] = [%d] or [U, C] = [%d, %d], got %s' % (name, C, U, C, tuple(t.shape)))
+        if int(pairs_per_pass) < 1:
+            raise ValueError('pairs_per_pass must be positive, got %r' % (pairs_per_pass,))
+        if k is not None and not 1 <= int(k) <= 128:
+            raise ValueError('recommend keeps 1 <= k <= 128 news per user (lime_topk_rows_f32), got k = %r' % (k,))
+        return U, H, C
+
+    @torch.no_grad()
+    def score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                   cand_lifetime, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+        """Scores [U, C] of U users against ONE shared pool of C candidate news, from the news cache: ``scores[u, j]`` is the
+        eval-mode score (N = 1, util.py:86-111) of the row (history u, candidate ``cand_index[j]``) -- what ``score_behaviors``
+        returns for that row with the same ``n_src``.
+
+        ``corpus``: the DeviceCorpus the cache was built from; ``hist_index`` / ``hist_mask`` / ``user_freshness`` /
+        ``user_lifetime`` [U, H]: the fields of a DeviceBehaviors row; ``cand_index`` [C]; ``cand_freshness`` [C] or [U, C];
+        ``cand_lifetime`` [U, C] (or [C], broadcast).  The remaining lifetime follows config.lifetime_type.  ``n_src``: as in
+        score_impressions (default min(U C, H + config.batch_size) under the CROWN user encoder; ignored otherwise).
+
+        Under the eval shape the candidate enters the user side only through its topic (layers.py:66-81), so the refinement, the
+        user encoder's own step and the operands of the match are computed once per (user, candidate topic) -- (user, category) under
+        ATT / MHSA, once per user with the candidate-aware attention off -- and every pair is left with two dot products per history
+        slot and the epilogue (lime_grouped_match_f32; recommend.pool_plan for the grouping).  Users go through in passes that keep
+        the candidate rows (users x C) and the refined history rows (users x topics x H) within ``pairs_per_pass`` rows each, at
+        least one user a pass: the default keeps the scratch around 1 GB at the full-size model.
+        ``exclude_history``: a pair whose candidate sits in a masked-in slot of the user's history scores -inf.
+        CNE has no per-news cache and is refused (ValueError)."""
+        from . import recommend as rec
+        U, H, C = self._check_pool(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                   cand_lifetime, pairs_per_pass)
+        ne, ue, c = self.news_encoder, self.user_encoder, corpus
+        dev = news_cache.device
+        crown = hasattr(ue, 'user_node_embedding')
+        cidx = cand_index.to(dev).long()
+        cat_c, sub_c = c.news_category[cidx], c.news_subCategory[cidx]
+        by = None if not ue.use_candidate_aware_attn else 'topic' if crown else 'category'
+        plan = rec.pool_plan(cat_c.cpu().numpy(), sub_c.cpu().numpy(), by)
+        T = plan.category.shape[0]
+        order = torch.as_tensor(plan.order, device=dev)
+        fresh = cand_freshness.to(dev).float().expand(U, C)
+        remaining = self._lifetime_rule(fresh, lambda: cand_lifetime.to(dev).float().expand(U, C), lambda: cat_c.unsqueeze(0).expand(U, C))
+        life = cand_lifetime.to(dev).float().expand(U, C)
+        # the pool in plan (topic) order: what every pass reads
+        idx_s, fresh_s, life_s, rem_s = cidx[order], fresh[:, order], life[:, order], remaining.float()[:, order]
+        hist = ne.encode_cached(news_cache, hist_index, user_freshness, user_lifetime).view(U, H, -1)
+        D = hist.shape[2]
+        flat_h = hist_index.reshape(-1).long()
+        ucat, usub = c.news_category[flat_h].view(U, H), c.news_subCategory[flat_h].view(U, H)
+        if n_src is None and crown:
+            n_src = min(U * C, H + ue.user_node_embedding.shape[0])
+        gate_y = ue.gate_projection(hist)                                             # once for every pass's histories
+        per = rec.users_per_pass(U, C, T, H, int(pairs_per_pass))
+        cat_t = torch.as_tensor(plan.category, device=dev).to(c.news_category.dtype)
+        sub_t = torch.as_tensor(plan.subCategory, device=dev).to(c.news_subCategory.dtype)
+        w = self.remaining_lifetime_weighting
+        out = torch.empty((U, C), dtype=torch.float32, device=dev)
+        for u0 in range(0, U, per):
+            u1 = min(U, u0 + per)
+            n = u1 - u0
+            # groups are user-major: hist_div = T topics share one history (never repeated in memory before the refinement)
+            operands = ue.match_operands(hist[u0:u1], cat_t.repeat(n).view(n * T, 1), sub_t.repeat(n).view(n * T, 1), ucat[u0:u1], usub[u0:u1],
+                                         hist_mask[u0:u1], n_src=n_src, hist_div=T,
+                                         gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
+            cand = ne.encode_cached(news_cache, idx_s.unsqueeze(0).expand(n, C), fresh_s[u0:u1], life_s[u0:u1])     # [n C, D]
+            offsets = torch.as_tensor(rec.group_offsets(plan.segments, n), device=dev)
+            if crown:
+                g, kp, _ = operands
+                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                     # userEncoders.py:162
+                h_match, scale = H, 1.0 / ue.attention_scalar
+            else:
+                # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
+                g, h_match, scale = operands, 1, 1.0
+                kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=dev)
+                qp = torch.zeros((n * C, 4), dtype=torch.float32, device=dev)
+            logits = ops.grouped_match(kp, g.reshape(-1, D), qp, cand, rem_s[u0:u1].reshape(-1), offsets, h_match, scale, w.alpha, w.beta,
+                                       bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty))
+            out[u0:u1].index_copy_(1, order, logits.view(n, C))
+        if exclude_history:
+            out.masked_fill_(self._in_history(news_cache.shape[0], hist_index, hist_mask, cidx), float('-inf'))
+        return out
+
+    @staticmethod
+    def _in_history(n_news, hist_index, hist_mask, cidx):
+        """bool [U, C]: candidate j sits in a masked-in slot of user u's history."""
+        U, H = hist_index.shape
+        seen = torch.zeros((U, n_news), dtype=torch.bool, device=cidx.device)
+        live = hist_mask.to(cidx.device).bool()
+        users = torch.arange(U, device=cidx.device).unsqueeze(1).expand(U, H)
+        seen[users[live], hist_index.to(cidx.device).long()[live]] = True
+        return seen[:, cidx]
+
+    @torch.no_grad()
+    def recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                  cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+        """The k best news of the pool per user, on the device: ``score_pool`` (same arguments), then lime_topk_rows_f32 ->
+        (positions int32 [U, k] into ``cand_index``, scores fp32 [U, k]).  Rows are in descending order of the score; equal scores
+        (+0.0 and -0.0 are equal) go lower position first; a NaN ranks after every number, in position order.  With
+        ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is never returned; when fewer than k
+        candidates remain, the trailing slots hold position -1 and score -inf.  1 <= k <= 128."""
+        self._check_pool(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
+                         pairs_per_pass, k=k)
+        scores = self.score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                 cand_lifetime, n_src=n_src, pairs_per_pass=pairs_per_pass, exclude_history=exclude_history)
+        positions, top = ops.topk_rows(scores, int(k))
+        if exclude_history:
+            gone = self._in_history(news_cache.shape[0], hist_index, hist_mask, cand_index.to(scores.device).long())
+            gone = gone.gather(1, positions.clamp(min=0).long()) & (positions >= 0)
+            positions = torch.where(gone, torch.full_like(positions, -1), positions)
+        return positions, top
 
     def _score_from_recurrence(self, behaviors, rows, rc, n_src, rows_per_forward):
         """score_behaviors under CNE from the recurrence cache: one encoder pass over the R candidates and the R . H history news of the

@@ -895,6 +895,50 @@ def pool_match(hidden, affine2, x, B, H, cand=None, remaining=None, alpha=0.0, b
     return user, logits
 
 
+def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False):
+    """``lime_grouped_match_f32``: the history-vs-candidate attention, the dot-product match and the remaining-lifetime weight for
+    groups of pairs that share one refined history.  kp [G H, A], g [G H, D] per group; qp [P, A], cand [P, D], remaining [P] per
+    pair; offsets int64 [G + 1] (device): the pairs of group i are rows offsets[i] .. offsets[i + 1] - 1 -> logits [P] (pairs outside
+    every group keep what ``torch.empty`` gave them).  1 <= H <= 128; A, D multiples of 4 up to 2048."""
+    lib = _lib.load()
+    for t, name in ((kp, 'kp'), (g, 'g'), (qp, 'qp'), (cand, 'cand')):
+        _mat(t, name)
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    A, D, P = kp.shape[1], g.shape[1], qp.shape[0]
+    if H < 1 or kp.shape[0] % H or g.shape[0] != kp.shape[0]:
+        raise ValueError('kp and g must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], g.shape[0], H))
+    G = kp.shape[0] // H
+    if qp.shape[1] != A or cand.shape != (P, D):
+        raise ValueError('qp must be [P, %d] and cand [P, %d], got %s and %s' % (A, D, tuple(qp.shape), tuple(cand.shape)))
+    _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
+    if use_weight:
+        remaining = _vec(remaining.contiguous(), 'remaining', P)
+    logits = torch.empty((P,), dtype=torch.float32, device=qp.device)
+    check(lib.lime_grouped_match_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(remaining) if use_weight else None, _p(offsets), _p(logits),
+                                     G, P, H, A, D, scale, alpha, beta, int(use_weight), int(use_penalty), _stream()),
+          'lime_grouped_match_f32')
+    return logits
+
+
+def topk_rows(scores, k):
+    """``lime_topk_rows_f32``: per row of scores [U, C] (a row-strided view is fine) the k best -> (positions int32 [U, k], scores fp32
+    [U, k]) in descending order; equal scores (+0.0 == -0.0) lower position first, NaN behind every number; slots behind the C-th hold
+    -1 / -inf.  1 <= k <= 128."""
+    lib = _lib.load()
+    _mat(scores, 'scores')
+    U, C = scores.shape
+    k = int(k)
+    if k < 1 or C < 1:
+        raise ValueError('topk_rows needs k >= 1 and at least one column, got k = %d, C = %d' % (k, C))
+    positions = torch.empty((U, k), dtype=torch.int32, device=scores.device)
+    top = torch.empty((U, k), dtype=torch.float32, device=scores.device)
+    need = int(lib.lime_topk_rows_workspace(U, C))
+    ws = _workspace(scores.device, need) if need else None
+    check(lib.lime_topk_rows_f32(_p(scores), _ld(scores), U, C, k, _p(positions), _p(top), _p(ws), need, _stream()), 'lime_topk_rows_f32')
+    return positions, top
+
+
 def row_scale(x, scale):
     lib = _lib.load()
     D = x.shape[-1]

@@ -1,0 +1,85 @@
+"""The host side of pool recommendation (Model.score_pool / Model.recommend): the grouping plan.  Pure numpy, no GPU.
+
+Under the eval shape the candidate enters the user side only through its topic (layers.py:66-81 reads the candidate's topic row and
+nothing else of it), so everything up to the operands of the match is computed once per (user, candidate topic) GROUP and the pool is
+walked in topic order: ``pool_plan`` sorts the pool by topic key and gives the CSR of the topics' segments, ``group_offsets`` lays the
+segments out user-major for the users of one pass."""
+import collections
+
+import numpy as np
+
+PoolPlan = collections.namedtuple('PoolPlan', 'order segments category subCategory')
+PoolPlan.__doc__ = """order int64 [C]: pool positions in group order (stable: position order inside a group); segments int64 [T + 1]:
+group t owns order[segments[t]:segments[t + 1]]; category / subCategory int64 [T]: the topic of group t (what the user side reads)."""
+
+
+def pool_plan(category, subCategory, by='topic', topics=None):
+    """Group a pool of C news by what the user side reads of a candidate.
+
+    ``by``: 'topic' -- (category, subCategory), the CROWN user encoder; 'category' -- the category alone (ATT / MHSA: no subcategory
+    enters their candidate-aware attention; a group's ``subCategory`` is its first member's and is not read); None -- the
+    candidate-aware attention is off, the user side does not read the candidate at all: ONE group.
+    ``topics``: optional list of (category, subCategory) keys (of categories for 'category') that fixes the groups and their order,
+    e.g. every topic of the corpus, so that plans of different pools line up; a topic without a candidate stays as an EMPTY group, a
+    candidate whose topic is not listed is a ValueError.  Default: the pool's own topics, ascending."""
+    cat = np.asarray(category).reshape(-1).astype(np.int64)
+    sub = np.asarray(subCategory).reshape(-1).astype(np.int64)
+    C = cat.shape[0]
+    if C < 1 or sub.shape[0] != C:
+        raise ValueError('pool_plan needs category and subCategory of one length >= 1, got %d and %d' % (C, sub.shape[0]))
+    if by not in ('topic', 'category', None):
+        raise ValueError("by must be 'topic', 'category' or None, got %r" % (by,))
+    if by is None:
+        if topics is not None:
+            raise ValueError('by=None makes one group: topics cannot be given')
+        return PoolPlan(np.arange(C, dtype=np.int64), np.array([0, C], dtype=np.int64), cat[:1].copy(), sub[:1].copy())
+    if cat.min() < 0 or sub.min() < 0:
+        raise ValueError('negative topic ids')
+    width = int(sub.max()) + 1
+    if topics is not None:
+        tk = np.asarray(topics, dtype=np.int64).reshape(len(topics), -1)
+        if tk.shape[1] != (2 if by == 'topic' else 1) or (tk < 0).any():
+            raise ValueError('topics must be non-negative (category, subCategory) pairs for by=\'topic\', categories for by=\'category\'')
+        width = max(width, int(tk[:, -1].max()) + 1) if by == 'topic' else width
+    key = cat * width + sub if by == 'topic' else cat
+    if topics is None:
+        order = np.argsort(key, kind='stable')
+        skey = key[order]
+        first = np.flatnonzero(np.concatenate([[True], skey[1:] != skey[:-1]]))
+        segments = np.concatenate([first, [C]]).astype(np.int64)
+        return PoolPlan(order.astype(np.int64), segments, cat[order[first]], sub[order[first]])
+    gkey = tk[:, 0] * width + tk[:, 1] if by == 'topic' else tk[:, 0]
+    if len(set(gkey.tolist())) != len(gkey):
+        raise ValueError('topics holds a key twice')
+    slot = {int(k): t for t, k in enumerate(gkey)}
+    try:
+        group = np.array([slot[int(k)] for k in key], dtype=np.int64)
+    except KeyError as e:
+        raise ValueError('a candidate\'s topic (key %s) is not in topics' % e) from None
+    order = np.argsort(group, kind='stable')
+    segments = np.concatenate([[0], np.cumsum(np.bincount(group, minlength=len(gkey)))]).astype(np.int64)
+    g_sub = tk[:, 1] if by == 'topic' else np.zeros(len(gkey), dtype=np.int64)
+    return PoolPlan(order.astype(np.int64), segments, tk[:, 0].copy(), g_sub)
+
+
+def group_offsets(segments, n_users):
+    """The CSR of one pass's groups over its pairs, user-major: the pairs of a pass are [n_users, C] in plan order (pair u C + j is user
+    u with pool position order[j]), group u T + t owns pairs u C + segments[t] .. u C + segments[t + 1] - 1 -> int64 [n_users T + 1]."""
+    seg = np.asarray(segments, dtype=np.int64).reshape(-1)
+    if seg.shape[0] < 2 or seg[0] != 0 or (np.diff(seg) < 0).any():
+        raise ValueError('segments must start at 0 and not decrease')
+    if n_users < 0:
+        raise ValueError('n_users must not be negative')
+    C = int(seg[-1])
+    starts = (np.arange(n_users, dtype=np.int64)[:, None] * C + seg[None, :-1]).reshape(-1)
+    return np.concatenate([starts, [n_users * C]]).astype(np.int64)
+
+
+def users_per_pass(n_users, C, n_groups, H, pairs_per_pass):
+    """Users of one pass: as many as keep both the candidate rows (users x C) and the refined history rows (users x groups x H) within
+    ``pairs_per_pass`` rows -- one user at the least, then evened out over the passes."""
+    if pairs_per_pass < 1:
+        raise ValueError('pairs_per_pass must be positive')
+    per = max(1, min(n_users, pairs_per_pass // max(C, 1), pairs_per_pass // max(n_groups * H, 1)))
+    n_pass = (n_users + per - 1) // per if n_users else 1
+    return max(1, (n_users + n_pass - 1) // n_pass)

@@ -140,22 +140,42 @@ class CROWN(UserEncoder):
         B = Bh * hist_div
         N = candidate_news_representation.shape[1]
         cand = candidate_news_representation.contiguous()
+        g, kp, qp = self.match_operands(history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask,
+                                        agg=agg, n_src=n_src, hist_div=hist_div, gate_y=gate_y, cand=cand.view(B * N, D))
+        w = weighting
+        user, logits = ops.interest_match(
+            kp, qp, g.reshape(-1), cand.reshape(-1), remaining_lifetime, B, N, H, self.attention_dim, D,
+            1.0 / self.attention_scalar,
+            w.alpha if w is not None else 0.0, w.beta if w is not None else 0.0,
+            bool(w.use_remaining_lifetime_weighting) if w is not None else False,
+            bool(w.use_expired_penalty) if w is not None else False,
+            want_logits=w is not None, want_user=True)
+        return user, logits
+
+    def match_operands(self, history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask, agg=None,
+                       n_src=None, hist_div=1, gate_y=None, cand=None):
+        """Everything of ``match`` up to the operands of its last kernel: (g [B, H, D], the GraphSAGE step over the refined history,
+        kp [B H, A] = K g, qp = Q(cand) [rows of cand, A] or None).  The B = Bh * hist_div rows are ``match``'s rows -- or, from
+        Model.score_pool, the (user, candidate topic) GROUPS, user-major with hist_div topics per user: ``category`` / ``subCategory``
+        [B, 1] then hold a group's topic, and ``cand`` is left out (the pairs' Q runs once per pass, outside)."""
+        Bh, H, D = history_embedding.shape
+        B = Bh * hist_div
         n_src = B if n_src is None else n_src
         caa = self.candidate_aware_attn if self.use_candidate_aware_attn else None
         fused = caa is not None and caa.use_residual_connection and D <= 512
         main = torch.cuda.current_stream()
-        if fused and gate_y is None:
+        qp = side6 = None
+        if fused and gate_y is None and cand is not None:
             # Q(candidates) (:162) and gate_proj(history) (layers.py:87) do not depend on each other: one grouped launch
-            qp, gate_y = ops.linear_group([dict(a=cand.view(B * N, D), w=self.Q.weight, bias=self.Q.bias),
+            qp, gate_y = ops.linear_group([dict(a=cand, w=self.Q.weight, bias=self.Q.bias),
                                            dict(a=history_embedding.reshape(Bh * H, D), w=caa.gate_proj.weight, bias=None)])
-            side6 = None
-        else:
+        elif cand is not None:
             # the candidate side of the match (:162) needs the candidates only: branch 6, beside the history chain
             from .newsEncoders import _side_stream
             side6 = _side_stream(cand.device, 6)
             side6.wait_stream(main)
             with torch.cuda.stream(side6):
-                qp = ops.linear(cand.view(B * N, D), self.Q.weight, self.Q.bias)                             # :162
+                qp = ops.linear(cand, self.Q.weight, self.Q.bias)                                             # :162
         if caa is not None and agg is None:
             # (hist_div > 1: user_category / user_subCategory / user_history_mask are [B / hist_div, H] -- one history per hist_div rows)
             agg = self.attention_weights(category, subCategory, user_category, user_subCategory, user_history_mask, hist_div=hist_div)
@@ -166,7 +186,7 @@ class CROWN(UserEncoder):
             # shared history through row / hist_div (no per-candidate copies) and takes the user-node part of the mean -- the same
             # vector for every row -- as one precomputed sum                                                  :121,:151-157
             hist = history_embedding.reshape(Bh * H, D)
-            y = gate_y
+            y = gate_y if gate_y is not None else ops.linear(hist, caa.gate_proj.weight, None)
             node_const = self.user_node_embedding[:n_src - H].sum(dim=0) if n_src > H else None
             refined, m = ops.gate_ln_sage(y, hist, agg.reshape(-1), caa.gate_proj.bias, caa.layernorm.weight, caa.layernorm.bias,
                                           caa.layernorm.eps, B, H, D, hist_div, n_src, node_const)
@@ -181,15 +201,7 @@ class CROWN(UserEncoder):
         kp = ops.linear(g.view(B * H, D), self.K.weight, None)                                               # :161
         if side6 is not None:
             main.wait_stream(side6)
-        w = weighting
-        user, logits = ops.interest_match(
-            kp, qp, g.reshape(-1), cand.reshape(-1), remaining_lifetime, B, N, H, self.attention_dim, D,
-            1.0 / self.attention_scalar,
-            w.alpha if w is not None else 0.0, w.beta if w is not None else 0.0,
-            bool(w.use_remaining_lifetime_weighting) if w is not None else False,
-            bool(w.use_expired_penalty) if w is not None else False,
-            want_logits=w is not None, want_user=True)
-        return user, logits
+        return g, kp, qp
 
     def gate_projection(self, history_embedding):
         """W_g x of the candidate-aware attention's gate (layers.py:87) for histories [*, H, D] -> [* H, D], or None when ``match``
@@ -286,15 +298,48 @@ class _PooledUser(UserEncoder):
         B = Bh * hist_div
         N = candidate_news_representation.shape[1]
         cand = candidate_news_representation.contiguous()
+        x, hidden, rows = self._pool_inputs(history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask,
+                                            agg, hist_div, gate_y, taps)
+        n_cand = B * N // rows
+        att = self.attention
+        w = weighting
+        rl = remaining_lifetime.reshape(rows, n_cand) if (w is not None and remaining_lifetime is not None) else None
+        user, logits = ops.pool_match(
+            hidden, att.affine2.weight.view(-1), x, rows, H, cand=cand.view(rows, n_cand, D) if w is not None else None, remaining=rl,
+            alpha=w.alpha if w is not None else 0.0, beta=w.beta if w is not None else 0.0,
+            use_weight=bool(w.use_remaining_lifetime_weighting) if w is not None else False,
+            use_penalty=bool(w.use_expired_penalty) if w is not None else False,
+            mask=None, want_user=True, want_logits=w is not None)                                          # layers.py:289-299, util.py:23-49
+        if rows != B:
+            user = user.unsqueeze(1).expand(Bh, hist_div, D).reshape(B, D)
+        return user.unsqueeze(1).expand(B, N, D), (logits.view(B, N) if logits is not None else None)
+
+    def match_operands(self, history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask, agg=None,
+                       n_src=None, hist_div=1, gate_y=None):
+        """Everything of ``match`` up to the dot product: the pooled user vector of every row, [rows, D] -- rows = Bh * hist_div with the
+        candidate-aware attention (from Model.score_pool the (user, candidate category) groups, user-major; ``category`` [rows, 1] holds
+        a group's category), rows = Bh without it (one vector per history).  The match of a vector with its candidates is CROWN's last
+        kernel with a history of ONE row (lime_grouped_match_f32, H = 1).  ``n_src`` is CROWN's and is ignored."""
+        H = history_embedding.shape[1]
+        x, hidden, rows = self._pool_inputs(history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask,
+                                            agg, hist_div, gate_y, None)
+        user, _ = ops.pool_match(hidden, self.attention.affine2.weight.view(-1), x, rows, H, mask=None, want_user=True, want_logits=False)
+        return user
+
+    def _pool_inputs(self, history_embedding, category, subCategory, user_category, user_subCategory, user_history_mask, agg, hist_div,
+                     gate_y, taps):
+        """The rows the attention pools and their tanh hidden state: (x [rows H, D], hidden [rows H, A], rows)."""
+        Bh, H, D = history_embedding.shape
+        B = Bh * hist_div
         caa = self.candidate_aware_attn if self.use_candidate_aware_attn else None
         mask = user_history_mask
         if caa is None:
             # no refinement: the hist_div rows of a history share ONE user vector -- pool each history once, against its
             # hist_div * N candidates
-            rows, n_cand = Bh, hist_div * N
+            rows = Bh
             x = history_embedding.reshape(Bh * H, D)
         else:
-            rows, n_cand = B, N
+            rows = B
             if agg is None:
                 agg = self.attention_weights(category, subCategory, user_category, user_subCategory, user_history_mask, hist_div=hist_div)
             if caa.use_residual_connection and D <= 512:
@@ -313,17 +358,7 @@ class _PooledUser(UserEncoder):
         x = self._sequence(x, mask, rows, H, taps)
         att = self.attention
         hidden = ops.linear(x, att.affine1.weight, att.affine1.bias, act='tanh')                           # layers.py:288
-        w = weighting
-        rl = remaining_lifetime.reshape(rows, n_cand) if (w is not None and remaining_lifetime is not None) else None
-        user, logits = ops.pool_match(
-            hidden, att.affine2.weight.view(-1), x, rows, H, cand=cand.view(rows, n_cand, D) if w is not None else None, remaining=rl,
-            alpha=w.alpha if w is not None else 0.0, beta=w.beta if w is not None else 0.0,
-            use_weight=bool(w.use_remaining_lifetime_weighting) if w is not None else False,
-            use_penalty=bool(w.use_expired_penalty) if w is not None else False,
-            mask=None, want_user=True, want_logits=w is not None)                                          # layers.py:289-299, util.py:23-49
-        if rows != B:
-            user = user.unsqueeze(1).expand(Bh, hist_div, D).reshape(B, D)
-        return user.unsqueeze(1).expand(B, N, D), (logits.view(B, N) if logits is not None else None)
+        return x, hidden, rows
 
     def forward(self, user_title_text, user_title_mask, user_title_entity, user_content_text, user_content_mask,
                 user_content_entity, category, subCategory, user_category, user_subCategory, user_history_mask,
