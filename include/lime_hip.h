@@ -1217,6 +1217,40 @@ int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);
 
+/* =====================================================================================================
+ * Candidate lists (Model.score_lists / Model.recommend_lists): U users, each with its OWN list of candidates, as a CSR over P
+ * (user, candidate) pairs -- offsets int64 [U + 1] on the device, user u owns pairs offsets[u] .. offsets[u + 1] - 1.
+ *
+ * lime_list_plan_count / lime_list_plan (csrc/list_plan.hip): the device form of recommend.list_plan, bit for bit.  keys int32 [P] is
+ * the topic id of every pair, 0 <= key < T_all <= 8192 (LIME_ERR_UNSUPPORTED beyond: one LDS table of bins per workgroup; U, P < 2^31).
+ * The count writes n_distinct int32 [U], the number of distinct keys of each list.  The plan takes S >= max(1, max n_distinct) slots
+ * per user and writes
+ *     order int64 [P]: the pairs of user u stay in rows offsets[u] .. offsets[u + 1] - 1, sorted by key, stable in list order;
+ *     group_offsets int64 [U S + 1]: group u S + s -- user u's s-th key in ascending order -- owns rows group_offsets[u S + s] ..
+ *         group_offsets[u S + s + 1] - 1 of order; a slot behind the user's last key is an empty group;
+ *     slot_key int32 [U S]: the key of each slot; an unused slot repeats the key of the user's slot 0 (key 0 for an empty list).
+ * One workgroup per user, no global atomics: the result is a fixed function of the inputs.  Every offset is clamped into [0, P].  A
+ * pair whose key is outside [0, T_all) takes no slot: such pairs go behind the user's last key in order, so order stays a permutation,
+ * every pair with a key in range is in its right group and nothing outside the buffers is read or written; the last user's such pairs
+ * lie behind group_offsets[U S] -- in no group --, another user's lie in the rows of that user's last slot.  With an S below a user's
+ * n_distinct the keys beyond S get no slot entry (their rows run on into the next group).
+ *
+ * lime_topk_segments_f32 (csrc/topk_segments_f32.hip): lime_topk_rows_f32 over the segments of a flat scores fp32 [P]: positions
+ * int32 [U, k] -- counted WITHIN the segment -- and top_scores fp32 [U, k] (the input's bits), the same order (descending; +0.0 ==
+ * -0.0; equal scores lower position first; a NaN behind every number, NaNs in position order); slots behind the segment's length
+ * -- all k of an empty segment -- hold -1 and -inf.  1 <= k <= 128, every segment shorter than 2^31, U + P / 4096 < 2^31
+ * (LIME_ERR_UNSUPPORTED otherwise).  A segment longer than 4096 is split into chunks whose lists one workgroup merges; the grid is
+ * U + P / 4096 chunks, which covers every split without reading the device, and the result -- the k largest of distinct integer
+ * keys -- is independent of the split and the run.  Offsets are clamped into [0, P].  workspace: lime_topk_segments_workspace(U, P)
+ * floats (never 0 for U >= 1), 8-byte aligned; what it holds on entry does not matter. */
+int lime_list_plan_count(const int32_t* keys, const int64_t* offsets, int64_t U, int64_t P, int32_t T_all, int32_t* n_distinct,
+                         void* stream);
+int lime_list_plan(const int32_t* keys, const int64_t* offsets, int64_t U, int64_t P, int32_t T_all, int32_t S, int64_t* order,
+                   int64_t* group_offsets, int32_t* slot_key, void* stream);
+int64_t lime_topk_segments_workspace(int64_t U, int64_t P);
+int lime_topk_segments_f32(const float* scores, const int64_t* offsets, int64_t U, int64_t P, int32_t k, int32_t* positions,
+                           float* top_scores, float* workspace, int64_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,19 @@ def _padded_tail(lists, H, dtype):
     return out
 
 
+def topic_table_of(corpus, by):
+    """``recommend.topic_table`` over ``corpus.news_category`` / ``corpus.news_subCategory`` (tensors), as tensors on their device;
+    kept on the corpus per ``by`` (the ids are read back to the host once per corpus and ``by``, never per call)."""
+    from .recommend import topic_table
+    tables = corpus.__dict__.setdefault('_topic_tables', {})
+    if by not in tables:
+        cat, sub = corpus.news_category, corpus.news_subCategory
+        topic, tcat, tsub = topic_table(cat.cpu().numpy(), sub.cpu().numpy(), by)
+        tables[by] = (torch.from_numpy(topic).to(cat.device), torch.from_numpy(tcat).to(cat.device).to(cat.dtype),
+                      torch.from_numpy(tsub).to(sub.device).to(sub.dtype))
+    return tables[by]
+
+
 class DeviceCorpus:
     """The eight per-news arrays of the reference's Corpus (corpus.py:360-367) on the device."""
 
@@ -161,6 +174,12 @@ class DeviceCorpus:
             setattr(self, name, torch.from_numpy(arr).to(self.device))
         self.max_history_num = corpus.max_history_num
         self.category_num = corpus.config.category_num
+        self._topic_tables = {}
+
+    def topic_table(self, by):
+        """``recommend.topic_table`` of this corpus, on the device: (topic_of_news int32 [n_news], category [T_all], subCategory
+        [T_all], the topics' ids in the dtype of ``news_category``).  Computed once per ``by`` and kept."""
+        return topic_table_of(self, by)
 
     def fields(self):
         return [getattr(self, n) for n in _NEWS_FIELDS]

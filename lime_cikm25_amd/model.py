@@ -366,12 +366,14 @@ class Model(nn.Module):
             return lifetime() - freshness
         raise ValueError('Invalid lifetime_type')
 
+    _NO_CONTENT_CACHE = ('content_encoder \'CNE\' has no per-news content cache (its gates read the partner news of the encoder call, '
+                         'build_news_cache): score_pool / recommend cannot serve it -- score the pairs with score_behaviors')
+
     def _check_pool(self, news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
                     pairs_per_pass, k=None):
         """The host-side refusals of score_pool / recommend (ValueError, before any launch) -> (U, H, C)."""
         if self.reads_content_mask:
-            raise ValueError('content_encoder \'CNE\' has no per-news content cache (its gates read the partner news of the encoder call, '
-                             'build_news_cache): score_pool / recommend cannot serve it -- score the pairs with score_behaviors')
+            raise ValueError(self._NO_CONTENT_CACHE)
         if news_cache.dim() != 2 or news_cache.shape[1] == 0:
             raise ValueError('news_cache must be the [n_news, width] tensor of build_news_cache, got %s' % (tuple(news_cache.shape),))
         if hist_index.dim() != 2:
@@ -495,6 +497,167 @@ class Model(nn.Module):
             gone = self._in_history(news_cache.shape[0], hist_index, hist_mask, cand_index.to(scores.device).long())
             gone = gone.gather(1, positions.clamp(min=0).long()) & (positions >= 0)
             positions = torch.where(gone, torch.full_like(positions, -1), positions)
+        return positions, top
+
+    def _check_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                     cand_freshness, cand_lifetime, pairs_per_pass, k=None):
+        """The host-side refusals of score_lists / recommend_lists (ValueError, before any launch) -> (U, H, P, the offsets as a
+        host int64 array, ``by``, the corpus' topic table)."""
+        import numpy as np
+        from . import recommend as rec
+        from .device_data import topic_table_of
+        if self.reads_content_mask:
+            raise ValueError(self._NO_CONTENT_CACHE)
+        if news_cache.dim() != 2 or news_cache.shape[1] == 0:
+            raise ValueError('news_cache must be the [n_news, width] tensor of build_news_cache, got %s' % (tuple(news_cache.shape),))
+        if hist_index.dim() != 2:
+            raise ValueError('hist_index must be [U, H], got %s' % (tuple(hist_index.shape),))
+        U, H = hist_index.shape
+        for t, name in ((hist_mask, 'hist_mask'), (user_freshness, 'user_freshness'), (user_lifetime, 'user_lifetime')):
+            if tuple(t.shape) != (U, H):
+                raise ValueError('%s must be [U, H] = [%d, %d] like hist_index, got %s' % (name, U, H, tuple(t.shape)))
+        if cand_index.dim() != 1:
+            raise ValueError('cand_index must be [P], the lists one behind the other, got %s' % (tuple(cand_index.shape),))
+        P = cand_index.numel()
+        if hist_index.dtype not in (torch.int32, torch.int64) or cand_index.dtype not in (torch.int32, torch.int64):
+            raise ValueError('hist_index and cand_index must be int32 or int64 news indices, got %s and %s' % (hist_index.dtype, cand_index.dtype))
+        off = cand_offsets.detach().cpu().numpy() if isinstance(cand_offsets, torch.Tensor) else np.asarray(cand_offsets)
+        if off.ndim != 1 or off.shape[0] != U + 1 or off.dtype.kind not in 'iu':
+            raise ValueError('cand_offsets must be U + 1 = %d integers (the CSR of the lists), got %s %s' % (U + 1, off.dtype, off.shape))
+        off = off.astype(np.int64)
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != P:
+            raise ValueError('cand_offsets must start at 0, not decrease and end at P = %d, got %d .. %d%s'
+                             % (P, off[0], off[-1], ' (decreasing)' if (np.diff(off) < 0).any() else ''))
+        for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
+            if tuple(t.shape) != (P,):
+                raise ValueError('%s must be [P] = [%d], got %s' % (name, P, tuple(t.shape)))
+        if int(pairs_per_pass) < 1:
+            raise ValueError('pairs_per_pass must be positive, got %r' % (pairs_per_pass,))
+        if k is not None and not 1 <= int(k) <= 128:
+            raise ValueError('recommend_lists keeps 1 <= k <= 128 news per user (lime_topk_segments_f32), got k = %r' % (k,))
+        if P == 0:
+            return U, H, P, off, None, None
+        ue = self.user_encoder
+        by = None if not ue.use_candidate_aware_attn else 'topic' if hasattr(ue, 'user_node_embedding') else 'category'
+        table = topic_table_of(corpus, by)
+        if table[1].numel() > rec.MAX_TOPICS:
+            raise ValueError('the corpus has %d topics, lime_list_plan groups up to %d' % (table[1].numel(), rec.MAX_TOPICS))
+        return U, H, P, off, by, table
+
+    @torch.no_grad()
+    def score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
+                    cand_lifetime, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+        """Scores fp32 [P], in list order, of U users against a candidate list of THEIR OWN each, from the news cache: user u's list is
+        ``cand_index[cand_offsets[u]:cand_offsets[u + 1]]`` and ``scores[p]`` is the eval-mode score (N = 1, util.py:86-111) of the
+        row (history u, candidate ``cand_index[p]``) -- what ``score_behaviors`` returns for that row with the same ``n_src``.
+
+        ``corpus``, the four history arguments [U, H], ``n_src`` (default min(P, H + config.batch_size) under the CROWN user encoder,
+        ignored otherwise) and ``exclude_history`` as in ``score_pool``; ``cand_offsets`` [U + 1], host or device (it is checked on the
+        host); ``cand_index`` / ``cand_freshness`` / ``cand_lifetime`` [P].  The remaining lifetime follows config.lifetime_type.
+
+        ``score_pool``'s body with lists in place of the pool: the pairs are grouped by (user, candidate topic) on the device
+        (ops.list_plan -- its read of the lists' distinct-topic counts is the call's only synchronisation), the user side runs once
+        per group and lime_grouped_match_f32 leaves each pair its two dot products per history slot.  The groups keep the regular
+        ``hist_div`` layout: every user of a pass gets S_pass slots, the largest number of distinct topics among the pass's lists, and
+        a list with fewer topics leaves slots whose refinement nobody reads.  Passes run over consecutive users and keep their pairs
+        and their users x S_pass x H refined rows within ``pairs_per_pass`` each, one user a pass at the least.
+        CNE has no per-news cache and is refused (ValueError)."""
+        return self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                                 cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
+
+    def _score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                     cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
+        """score_lists -> (scores [P], the offsets on the device, bool [P] "excluded" or None)."""
+        from . import recommend as rec
+        U, H, P, off, by, table = self._check_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
+                                                    cand_index, cand_freshness, cand_lifetime, pairs_per_pass, k)
+        ne, ue, c = self.news_encoder, self.user_encoder, corpus
+        dev = news_cache.device
+        offsets = torch.from_numpy(off).to(dev)
+        if P == 0:
+            return torch.empty((0,), dtype=torch.float32, device=dev), offsets, None
+        crown = hasattr(ue, 'user_node_embedding')
+        topic_of_news, cat_t, sub_t = table
+        cidx = cand_index.to(dev).long()
+        fresh, life = cand_freshness.to(dev).float(), cand_lifetime.to(dev).float()
+        remaining = self._lifetime_rule(fresh, lambda: life, lambda: c.news_category[cidx]).float()
+        keys = topic_of_news[cidx]
+        plan = ops.list_plan(keys, offsets, n_keys=cat_t.numel())                      # the call's one device -> host read
+        S = (plan.slot_key.numel() // U) if U else 1
+        hist = ne.encode_cached(news_cache, hist_index, user_freshness, user_lifetime).view(U, H, -1)
+        D = hist.shape[2]
+        flat_h = hist_index.reshape(-1).long()
+        ucat, usub = c.news_category[flat_h].view(U, H), c.news_subCategory[flat_h].view(U, H)
+        if n_src is None and crown:
+            n_src = min(P, H + ue.user_node_embedding.shape[0])
+        gate_y = ue.gate_projection(hist)                                             # once for every pass's histories
+        w = self.remaining_lifetime_weighting
+        out = torch.empty((P,), dtype=torch.float32, device=dev)
+        for u0, u1, S_pass in rec.list_passes(off, plan.n_distinct, H, int(pairs_per_pass)):
+            p0, p1 = int(off[u0]), int(off[u1])
+            n, n_pair = u1 - u0, p1 - p0
+            if n_pair == 0:
+                continue
+            if S_pass == S:                                                           # the pass's plan is a slice of the call's
+                rows, goff, skey = plan.order[p0:p1], plan.group_offsets[u0 * S:u1 * S + 1] - p0, plan.slot_key[u0 * S:u1 * S]
+            else:                                                                     # fewer slots suffice: no slot count is read again
+                sub = ops.list_plan(keys[p0:p1], offsets[u0:u1 + 1] - p0, slots=S_pass, n_keys=cat_t.numel(),
+                                    n_distinct=plan.n_distinct[u0:u1])
+                rows, goff, skey = sub.order + p0, sub.group_offsets, sub.slot_key
+            skey = skey.long()
+            # groups are user-major: hist_div = S_pass slots share one history (never repeated in memory before the refinement)
+            operands = ue.match_operands(hist[u0:u1], cat_t[skey].view(n * S_pass, 1), sub_t[skey].view(n * S_pass, 1), ucat[u0:u1],
+                                         usub[u0:u1], hist_mask[u0:u1], n_src=n_src, hist_div=S_pass,
+                                         gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
+            cand = ne.encode_cached(news_cache, cidx[rows].view(1, n_pair), fresh[rows].view(1, n_pair), life[rows].view(1, n_pair))
+            if crown:
+                g, kp, _ = operands
+                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                     # userEncoders.py:162
+                h_match, scale = H, 1.0 / ue.attention_scalar
+            else:
+                # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
+                g, h_match, scale = operands, 1, 1.0
+                kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=dev)
+                qp = torch.zeros((n_pair, 4), dtype=torch.float32, device=dev)
+            logits = ops.grouped_match(kp, g.reshape(-1, D), qp, cand, remaining[rows], goff.contiguous(), h_match, scale, w.alpha, w.beta,
+                                       bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty))
+            out.index_copy_(0, rows, logits)
+        gone = None
+        if exclude_history:
+            gone = self._in_own_history(hist_index.to(dev), hist_mask.to(dev), offsets, cidx)
+            out.masked_fill_(gone, float('-inf'))
+        return out, offsets, gone
+
+    @staticmethod
+    def _in_own_history(hist_index, hist_mask, offsets, cidx, pairs_per_step=1 << 18):
+        """bool [P]: the candidate of pair p sits in a masked-in slot of ITS user's history -- per pair against the user's H slots."""
+        U, P = hist_index.shape[0], cidx.numel()
+        user = torch.repeat_interleave(torch.arange(U, device=cidx.device), offsets[1:] - offsets[:-1], output_size=P)
+        hist, live = hist_index.long(), hist_mask.bool()
+        gone = torch.empty((P,), dtype=torch.bool, device=cidx.device)
+        for p0 in range(0, P, pairs_per_step):
+            u = user[p0:p0 + pairs_per_step]
+            gone[p0:p0 + pairs_per_step] = ((hist[u] == cidx[p0:p0 + pairs_per_step].unsqueeze(1)) & live[u]).any(dim=1)
+        return gone
+
+    @torch.no_grad()
+    def recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                        cand_freshness, cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+        """The k best news of every user's OWN list, on the device: ``score_lists`` (same arguments), then lime_topk_segments_f32 ->
+        (positions int32 [U, k] into the user's list -- candidate ``cand_index[cand_offsets[u] + positions[u, j]]`` --, scores fp32
+        [U, k]) in ``recommend``'s order.  With ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is
+        never returned; the trailing slots of a list with fewer than k candidates left (all k of an empty list) hold position -1 and
+        score -inf.  1 <= k <= 128."""
+        scores, offsets, gone = self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
+                                                  cand_index, cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
+        U, k = hist_index.shape[0], int(k)
+        if scores.numel() == 0:
+            return (torch.full((U, k), -1, dtype=torch.int32, device=scores.device),
+                    torch.full((U, k), float('-inf'), dtype=torch.float32, device=scores.device))
+        positions, top = ops.topk_segments(scores, offsets, k)
+        if gone is not None:
+            at = (offsets[:-1].unsqueeze(1) + positions.clamp(min=0).long()).clamp(max=scores.numel() - 1)
+            positions = torch.where(gone[at] & (positions >= 0), torch.full_like(positions, -1), positions)
         return positions, top
 
     def _score_from_recurrence(self, behaviors, rows, rc, n_src, rows_per_forward):

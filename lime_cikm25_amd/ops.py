@@ -939,6 +939,63 @@ def topk_rows(scores, k):
     return positions, top
 
 
+def list_plan(keys, offsets, slots=None, n_keys=8192, n_distinct=None):
+    """``lime_list_plan_count`` + ``lime_list_plan``: ``recommend.list_plan`` on the device, bit for bit.  keys int32 [P] (device,
+    0 <= key < ``n_keys`` <= 8192), offsets int64 [U + 1] (device) -> recommend.ListPlan(order int64 [P], group_offsets int64
+    [U S + 1], slot_key int32 [U S] -- device tensors -- and n_distinct int32 [U], a host array).
+
+    The count runs first and ``n_distinct`` is read back ONCE, to pick S = max(1, n_distinct.max()) (or to check ``slots``: a smaller
+    one is a ValueError): that small device -> host copy is the only synchronisation of the candidate-list path.  A caller that
+    already holds the counts of these very lists passes them as ``n_distinct`` (host) and adds none."""
+    import numpy as np
+    from .recommend import ListPlan
+    lib = _lib.load()
+    _vec(keys, 'keys', dtype=torch.int32)
+    P = keys.numel()
+    _vec(offsets, 'offsets', dtype=torch.int64)
+    U = offsets.numel() - 1
+    if U < 0:
+        raise ValueError('offsets must hold U + 1 >= 1 entries')
+    dev = keys.device
+    if n_distinct is None:
+        nd_dev = torch.empty((U,), dtype=torch.int32, device=dev)
+        check(lib.lime_list_plan_count(_p(keys), _p(offsets), U, P, int(n_keys), _p(nd_dev), _stream()), 'lime_list_plan_count')
+        n_distinct = nd_dev.cpu().numpy()
+    else:
+        n_distinct = np.asarray(n_distinct, dtype=np.int32).reshape(-1)
+        if n_distinct.shape[0] != U:
+            raise ValueError('n_distinct must have U = %d entries, got %d' % (U, n_distinct.shape[0]))
+    need = max(1, int(n_distinct.max())) if U else 1
+    S = need if slots is None else int(slots)
+    if S < need:
+        raise ValueError('slots = %d, but a list holds %d distinct keys' % (S, need))
+    order = torch.empty((P,), dtype=torch.int64, device=dev)
+    group_offsets = torch.empty((U * S + 1,), dtype=torch.int64, device=dev)
+    slot_key = torch.empty((U * S,), dtype=torch.int32, device=dev)
+    check(lib.lime_list_plan(_p(keys), _p(offsets), U, P, int(n_keys), S, _p(order), _p(group_offsets), _p(slot_key), _stream()),
+          'lime_list_plan')
+    return ListPlan(order, group_offsets, slot_key, n_distinct)
+
+
+def topk_segments(scores, offsets, k):
+    """``lime_topk_segments_f32``: the k best of every segment of scores fp32 [P]; offsets int64 [U + 1] (device): segment u is
+    scores[offsets[u]:offsets[u + 1]] -> (positions int32 [U, k] WITHIN the segment, scores fp32 [U, k]) in ``topk_rows``' order;
+    slots behind a segment's length (all of an empty segment's) hold -1 / -inf.  1 <= k <= 128."""
+    lib = _lib.load()
+    _vec(scores, 'scores')
+    _vec(offsets, 'offsets', dtype=torch.int64)
+    U, P, k = offsets.numel() - 1, scores.numel(), int(k)
+    if U < 0 or not 1 <= k <= 128:
+        raise ValueError('topk_segments needs 1 <= k <= 128 and U + 1 >= 1 offsets, got k = %d, %d offsets' % (k, U + 1))
+    positions = torch.empty((U, k), dtype=torch.int32, device=scores.device)
+    top = torch.empty((U, k), dtype=torch.float32, device=scores.device)
+    need = int(lib.lime_topk_segments_workspace(U, P))
+    ws = _workspace(scores.device, need) if need else None
+    check(lib.lime_topk_segments_f32(_p(scores), _p(offsets), U, P, k, _p(positions), _p(top), _p(ws), ws.numel() if need else 0, _stream()),
+          'lime_topk_segments_f32')
+    return positions, top
+
+
 def row_scale(x, scale):
     lib = _lib.load()
     D = x.shape[-1]

@@ -83,3 +83,91 @@ def users_per_pass(n_users, C, n_groups, H, pairs_per_pass):
     per = max(1, min(n_users, pairs_per_pass // max(C, 1), pairs_per_pass // max(n_groups * H, 1)))
     n_pass = (n_users + per - 1) // per if n_users else 1
     return max(1, (n_users + n_pass - 1) // n_pass)
+
+
+# ---- candidate lists (Model.score_lists / Model.recommend_lists): every user has a list of its own -------------------------------------
+MAX_TOPICS = 8192                     # lime_list_plan's table of bins
+
+ListPlan = collections.namedtuple('ListPlan', 'order group_offsets slot_key n_distinct')
+ListPlan.__doc__ = """order int64 [P]: the pairs in group order -- user u's stay in rows offsets[u] .. offsets[u + 1] - 1, sorted by slot,
+stable in list order; group_offsets int64 [U S + 1]: group u S + s (user u, its s-th key ascending) owns order[group_offsets[u S + s]:
+group_offsets[u S + s + 1]]; slot_key int32 [U S]: the key of each slot (an unused slot: the key of the user's slot 0; an empty list:
+key 0); n_distinct int32 [U]: the distinct keys of each list."""
+
+
+def topic_table(category, subCategory, by):
+    """Dense topic ids for a corpus of n_news news -> (topic_of_news int32 [n_news], category int64 [T_all], subCategory int64 [T_all]).
+    ``by`` as in ``pool_plan``: 'topic' -- the (category, subCategory) pair; 'category' -- the category alone (a topic's subCategory is
+    its first news' and is not read); None -- one id, 0, for every news.  The ids ascend in ``pool_plan``'s key order, so two news
+    share an id exactly when ``pool_plan`` puts them into one group."""
+    cat = np.asarray(category).reshape(-1).astype(np.int64)
+    sub = np.asarray(subCategory).reshape(-1).astype(np.int64)
+    if cat.shape[0] < 1 or sub.shape[0] != cat.shape[0]:
+        raise ValueError('topic_table needs category and subCategory of one length >= 1, got %d and %d' % (cat.shape[0], sub.shape[0]))
+    if by not in ('topic', 'category', None):
+        raise ValueError("by must be 'topic', 'category' or None, got %r" % (by,))
+    if by is None:
+        return np.zeros(cat.shape[0], dtype=np.int32), cat[:1].copy(), sub[:1].copy()
+    if cat.min() < 0 or sub.min() < 0:
+        raise ValueError('negative topic ids')
+    key = cat * (int(sub.max()) + 1) + sub if by == 'topic' else cat
+    _, first, topic = np.unique(key, return_index=True, return_inverse=True)
+    return topic.reshape(-1).astype(np.int32), cat[first], sub[first]
+
+
+def list_plan(keys, offsets, slots=None):
+    """Group the pairs of U candidate lists by (user, key): the host statement of ``ops.list_plan`` (lime_list_plan).
+
+    ``keys`` int [P]: the topic id of every pair (>= 0); ``offsets`` int64 [U + 1]: the CSR of the lists.  A user's distinct keys take
+    slots 0 .. n_distinct[u] - 1 in ascending key order; ``slots`` = S slots per user (default max(1, n_distinct.max()); fewer than
+    n_distinct.max() is a ValueError); groups are user-major, the slots behind a user's last key are empty groups -> ListPlan."""
+    keys = np.asarray(keys).reshape(-1).astype(np.int64)
+    off = np.asarray(offsets).reshape(-1).astype(np.int64)
+    P = keys.shape[0]
+    if off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != P:
+        raise ValueError('offsets must start at 0, not decrease and end at P = %d' % P)
+    if P and keys.min() < 0:
+        raise ValueError('negative keys')
+    U = off.shape[0] - 1
+    lens = np.diff(off)
+    user = np.repeat(np.arange(U, dtype=np.int64), lens)
+    order = np.lexsort((np.arange(P), keys, user)).astype(np.int64)           # by user, then key, then list order
+    su, sk = user[order], keys[order]
+    new = np.ones(P, dtype=bool)
+    new[1:] = (su[1:] != su[:-1]) | (sk[1:] != sk[:-1])                       # the first row of every (user, key) group
+    n_distinct = np.bincount(su[new], minlength=U).astype(np.int32)
+    need = max(1, int(n_distinct.max())) if U else 1
+    S = need if slots is None else int(slots)
+    if S < need:
+        raise ValueError('slots = %d, but a list holds %d distinct keys' % (S, need))
+    rows = np.flatnonzero(new)
+    slot = np.arange(rows.shape[0]) - np.repeat(np.cumsum(n_distinct) - n_distinct, n_distinct)
+    group_offsets = np.empty(U * S + 1, dtype=np.int64)
+    group_offsets[:-1] = np.repeat(off[1:], S)                                # an unused slot: empty, at the end of the user's rows
+    group_offsets[-1] = P
+    group_offsets[su[rows] * S + slot] = rows
+    slot_key = np.zeros((U, S), dtype=np.int32)
+    has = n_distinct > 0
+    slot_key[has] = sk[off[:-1][has]][:, None]                                # the user's first (smallest) key
+    slot_key.reshape(-1)[su[rows] * S + slot] = sk[rows]
+    return ListPlan(order, group_offsets, slot_key.reshape(-1), n_distinct)
+
+
+def list_passes(offsets, n_distinct, H, pairs_per_pass):
+    """Consecutive users per pass of Model.score_lists -> list of (u0, u1, S_pass): a pass keeps its pairs and its users x S_pass x H
+    refined rows within ``pairs_per_pass`` each, S_pass = max(1, the largest n_distinct of its users); one user a pass at the least."""
+    if pairs_per_pass < 1:
+        raise ValueError('pairs_per_pass must be positive')
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    nd = np.asarray(n_distinct, dtype=np.int64).reshape(-1)
+    U, passes, u0 = off.shape[0] - 1, [], 0
+    while u0 < U:
+        u1, S = u0 + 1, max(1, int(nd[u0]))
+        while u1 < U:
+            S1 = max(S, int(nd[u1]))
+            if off[u1 + 1] - off[u0] > pairs_per_pass or (u1 + 1 - u0) * S1 * H > pairs_per_pass:
+                break
+            u1, S = u1 + 1, S1
+        passes.append((u0, u1, S))
+        u0 = u1
+    return passes

@@ -28,13 +28,15 @@ def _mkdir(path):
 
 class Trainer:
     def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True, device_eval=False,
-                 device_sampling=False, cne_recurrence_cache=False):
+                 device_sampling=False, cne_recurrence_cache=False, grouped_eval=False):
         """``truth_file``: the dev truth file of config.py:262-276 ("<impression> [labels]" lines).  Without one it is written
         (as the reference's Config does at start-up) to ``<dev_res_dir>/../ref/truth-<dataset>.txt`` from ``corpus.dev_labels``
         (formats.build_corpus attaches them); a corpus without labels and no file is refused here, before any training.
         ``cached_eval``: the dev pass encodes every news once (util.compute_scores_cached) instead of once per row and slot; same
         scores, for every fusion_method.  ``device_eval``: where the cached pass applies and the corpus carries ``dev_labels``, the dev pass also ranks and
         scores on the device (util.evaluate_cached_on_device): the same rank file, metrics equal to rounding; off by default.
+        ``grouped_eval``: passed on to that pass as ``grouped`` -- an impression is scored as one user with its own candidate list
+        (Model.score_lists); scores equal to fp32 rounding, a ValueError under CNE; off by default.
         ``device_sampling``: the train split is uploaded once, here (DeviceBehaviors.train_resident), and every epoch's negatives are
         drawn on the device, in place, by one launch (``resample(config.seed, epoch)``) instead of the host's negative_sampling and a
         new from_train per epoch; the batch plans of the first epoch serve the whole run.  The draws follow the same rule but a
@@ -83,6 +85,7 @@ class Trainer:
         self.dc = device_corpus if device_corpus is not None else DeviceCorpus(corpus)
         self.dev = DeviceBehaviors.from_devtest(self.dc, corpus, 'dev')
         self.cne_recurrence_cache = bool(cne_recurrence_cache)
+        self.grouped_eval = bool(grouped_eval)
         self.device_sampling = bool(device_sampling)
         self.train_split = DeviceBehaviors.train_resident(self.dc, corpus, config.negative_sample_num) if self.device_sampling else None
         self.step = TrainStep(model, lr=config.lr, weight_decay=config.weight_decay, gradient_clip_norm=config.gradient_clip_norm)
@@ -129,7 +132,7 @@ class Trainer:
         per = self.eval_batch_size
         if self.cached_eval and self.device_eval:
             return util.evaluate_cached_on_device(self.model, self.dev, self.corpus.dev_indices, self.corpus.dev_labels, result_file=out,
-                                                  rows_per_forward=per, recurrence_cache=self.cne_recurrence_cache)
+                                                  rows_per_forward=per, recurrence_cache=self.cne_recurrence_cache, grouped=self.grouped_eval)
         if self.cached_eval:
             return util.compute_scores_cached(self.model, self.dev, self.corpus.dev_indices, out, self.truth_file, per,
                                               recurrence_cache=self.cne_recurrence_cache)

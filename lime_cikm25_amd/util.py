@@ -147,8 +147,51 @@ DEVICE_EVAL_ROWS_PER_PASS = 8192
 CNE_CACHED_ROWS_PER_PASS = 256
 
 
+def impression_runs(indices, r0, r1):
+    """The runs of equal values in indices[r0:r1] -> their first rows, int64 [n_runs + 1] ending with r1 (host)."""
+    idx = np.asarray(indices, dtype=np.int64)[r0:r1]
+    starts = np.flatnonzero(np.concatenate([[True], idx[1:] != idx[:-1]])) if idx.size else np.zeros(0, dtype=np.int64)
+    return np.concatenate([starts + r0, [r1]]).astype(np.int64)
+
+
+def check_one_history_per_impression(behaviors, indices):
+    """ValueError unless all rows of every impression (run of equal values in ``indices``) carry identical hist_index / hist_mask /
+    user_freshness / user_lifetime: compared on the device, one flag read back; remembered on ``behaviors`` once it holds."""
+    b = behaviors
+    if getattr(b, '_one_history_per_impression', False) or b.num < 2:
+        return
+    dev = b.hist_index.device
+    idx = torch.as_tensor(np.asarray(indices, dtype=np.int64), device=dev)
+    differs = torch.zeros(b.num - 1, dtype=torch.bool, device=dev)
+    for t in (b.hist_index, b.hist_mask, b.user_freshness, b.user_lifetime):
+        differs |= (t[1:] != t[:-1]).any(dim=1)
+    bad = differs & (idx[1:] == idx[:-1])
+    if bool(bad.any()):
+        row = int(torch.nonzero(bad)[0]) + 1
+        raise ValueError('impression %d: row %d carries another history than the row before it -- the grouped dev pass reads an '
+                         'impression\'s history from its first row' % (int(idx[row]), row))
+    b._one_history_per_impression = True
+
+
+def _score_grouped(model, behaviors, indices, cache, scores, full, per, rows_per_pass):
+    """evaluate_cached_on_device(grouped=True): rows [0, full) with n_src = per, rows [full, num) with n_src = their count, each as
+    one ``score_lists`` call over the impressions' lists, into ``scores``."""
+    b = behaviors
+    check_one_history_per_impression(b, indices)
+    dev, H = cache.device, b.hist_index.shape[1]
+    for r0, r1, n_src in ((0, full, per), (full, b.num, b.num - full)):
+        if r1 == r0:
+            continue
+        runs = impression_runs(indices, r0, r1)
+        first = torch.from_numpy(runs[:-1]).to(dev)
+        scores[r0:r1] = model.score_lists(cache, b.corpus, b.hist_index[first], b.hist_mask[first], b.user_freshness[first],
+                                          b.user_lifetime[first], runs - r0, b.cand_index[r0:r1].reshape(-1),
+                                          b.cand_freshness[r0:r1].reshape(-1), b.cand_lifetime[r0:r1].reshape(-1), n_src=n_src,
+                                          pairs_per_pass=max(1, rows_per_pass * H))
+
+
 def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=None, rows_per_forward=None,
-                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False, recurrence_cache=False):
+                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False, recurrence_cache=False, grouped=False):
     """The dev / test pass of ``compute_scores_cached`` without host round trips: one ``build_news_cache``, ``score_behaviors`` in
     passes of up to ``rows_per_pass`` rows that write into ONE device score buffer, one ``evaluate.device_scoring`` (ranks and
     metrics in one launch, csrc/rank_metrics.hip), one device -> host copy of the result.  ``labels``: the per-impression label
@@ -169,8 +212,20 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
     forwards.  ``recurrence_cache`` = True (CNE alone) builds the per-news recurrence cache once per call
     (Model.build_recurrence_cache) and passes it on with ``rows_per_forward``: a pass then scores many reference-sized chunks in one
     launch chain and still pairs the gates per chunk, which gives the scores of ``compute_scores_cached(..., rows_per_forward)``; a
-    pass then holds at most CNE_CACHED_ROWS_PER_PASS rows (59 MB of token-level tensors a row at the defaults)."""
+    pass then holds at most CNE_CACHED_ROWS_PER_PASS rows (59 MB of token-level tensors a row at the defaults).
+
+    ``grouped`` = True: the rows go through ``Model.score_lists`` instead -- an impression (a run of equal values in ``indices``) is
+    one user with its rows as its candidate list and the history of its first row, so the user side runs once per (impression,
+    candidate topic) and not once per row.  The chunk rule is kept: the rows of the full chunks with n_src = rows_per_forward, the
+    rows of the short last chunk with n_src = its length, an impression that straddles that boundary cut into two lists -- two
+    ``score_lists`` calls at the most, each within ``rows_per_pass`` x H refined rows a pass.  Same score buffer, same
+    ``device_scoring``; the scores equal the ungrouped ones to fp32 rounding.  Once per ``DeviceBehaviors`` it is checked, on the device,
+    that all rows of an impression carry one history (a split of ``from_devtest`` does): ValueError naming the first impression that
+    does not.  CNE has no per-news cache: ``grouped`` is a ValueError there.  Off by default."""
     config = model.config
+    if grouped and model.reads_content_mask:
+        raise ValueError('content_encoder \'CNE\' has no per-news content cache: the grouped dev pass (Model.score_lists) cannot serve '
+                         'it -- use grouped=False')
     if config.lifetime_type not in ('fixed', 'topic_wise', 'user_topic'):
         raise ValueError('Invalid lifetime_type')
     per = rows_per_forward or config.batch_size
@@ -192,11 +247,14 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
         scores = torch.empty(num, dtype=torch.float32, device=dev)
         full = (num // per) * per                                          # the rows of the full chunks: n_src = per
         step = max(1, (min(rows_per_pass, CNE_CACHED_ROWS_PER_PASS) if recurrence_cache else rows_per_pass) // per) * per
-        for r0 in range(0, full, step):
-            r1 = min(full, r0 + step)
-            scores[r0:r1] = model.score_behaviors(behaviors, torch.arange(r0, r1, device=dev), cache, n_src=per, **rc).float()
-        if full < num:                                                     # the last, short chunk: n_src = its length
-            scores[full:] = model.score_behaviors(behaviors, torch.arange(full, num, device=dev), cache, n_src=num - full, **rc).float()
+        if grouped:
+            _score_grouped(model, behaviors, indices, cache, scores, full, per, rows_per_pass)
+        else:
+            for r0 in range(0, full, step):
+                r1 = min(full, r0 + step)
+                scores[r0:r1] = model.score_behaviors(behaviors, torch.arange(r0, r1, device=dev), cache, n_src=per, **rc).float()
+            if full < num:                                                 # the last, short chunk: n_src = its length
+                scores[full:] = model.score_behaviors(behaviors, torch.arange(full, num, device=dev), cache, n_src=num - full, **rc).float()
     finally:
         model.train(was_training)
     metrics, ranks = device_scoring(scores, indices, labels)

@@ -1,0 +1,194 @@
+"""Candidate lists at the sizes they are served at: Model.recommend_lists and the grouped dev pass against the forms that score such
+rows today, alternated in one process after warm-up.  Full-size model, synthetic weights, MIND's topic counts (18 categories, 270
+subcategories, each under one category), under the CROWN and the ATT user encoder.
+
+  * serving: 1024 users x 100 candidates of their own, k = 10 -- ``recommend_lists`` against ``score_behaviors`` over the same rows
+    (calls of ``--old-rows`` rows) plus a ``torch.topk`` per list;
+  * dev: 50,000 impressions with tools/bench_eval.py's list lengths -- ``evaluate_cached_on_device(grouped=True)`` against
+    ``grouped=False`` on the same split.
+
+Device-event medians.  Each line also carries the share of EMPTY group slots per pass (a pass gives every user as many slots as its
+list with the most topics needs).  Prints one JSON line per (shape, user encoder) and writes them to ``--json-out`` (default
+profiles/recommend_lists.json).
+
+    python tools/bench_lists.py --rounds 3
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from lime_cikm25_amd import DeviceBehaviors, DeviceCorpus, Model, make_config, ops, recommend, synth, util  # noqa: E402
+from bench_eval import make_dev_split  # noqa: E402
+
+
+def say(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def spread(xs):
+    return {'median': round(statistics.median(xs), 3), 'min': round(min(xs), 3), 'max': round(max(xs), 3)}
+
+
+def alternate(new_form, old_form, rounds):
+    for _ in range(2):                                                     # warm-up: kernels loaded, the allocator holds the blocks
+        new_form()
+        old_form()
+    torch.cuda.synchronize()
+    new_ms, old_ms = [], []
+    for _ in range(rounds):
+        dt, new = event_ms(new_form)
+        new_ms.append(dt)
+        dt, old = event_ms(old_form)
+        old_ms.append(dt)
+    return new_ms, old_ms, new, old
+
+
+def empty_slots(model, dc, cand_index, offsets, H, pairs_per_pass):
+    """Share of group slots that hold no pair, per pass of score_lists: (overall, smallest, largest, passes, largest slot count)."""
+    ue = model.user_encoder
+    by = None if not ue.use_candidate_aware_attn else 'topic' if hasattr(ue, 'user_node_embedding') else 'category'
+    topic_of_news, cat_t, _ = dc.topic_table(by)
+    plan = ops.list_plan(topic_of_news[cand_index.long()], torch.from_numpy(offsets).cuda(), n_keys=cat_t.numel())
+    nd = plan.n_distinct.astype(np.int64)
+    shares, used, slots, s_max = [], 0, 0, 1
+    for u0, u1, S in recommend.list_passes(offsets, nd, H, pairs_per_pass):
+        n_used, n_slot = int(nd[u0:u1].sum()), (u1 - u0) * S
+        shares.append(1.0 - n_used / n_slot)
+        used, slots, s_max = used + n_used, slots + n_slot, max(s_max, S)
+    return {'overall': round(1.0 - used / max(slots, 1), 4), 'min_pass': round(min(shares), 4), 'max_pass': round(max(shares), 4),
+            'passes': len(shares), 'largest_slot_count': s_max, 'mean_distinct_topics_per_list': round(float(nd.mean()), 2)}
+
+
+def serving(model, dc, cache, cfg, args, rng, n_news):
+    U, C, k, H = args.users, args.candidates, args.k, cfg.max_history_num
+    P = U * C
+    n_hist = rng.integers(5, H + 1, size=U)
+    mask = np.arange(H)[None, :] < n_hist[:, None]
+    hist = np.where(mask, rng.integers(1, n_news, size=(U, H)), 0).astype(np.int32)
+    ufr = np.where(mask, np.exp(rng.uniform(np.log(60.0), np.log(30 * 86400.0), size=(U, H))), 0.0).astype(np.float32)
+    ult = np.where(mask, np.exp(rng.uniform(np.log(600.0), np.log(14 * 86400.0), size=(U, H))), 0.0).astype(np.float32)
+    cands = rng.integers(1, n_news, size=P).astype(np.int32)               # every user a list of its own
+    cfr = np.exp(rng.uniform(np.log(60.0), np.log(3 * 86400.0), size=P)).astype(np.float32)
+    clt = (cfr * np.exp(rng.uniform(-1.0, 1.0, size=P))).astype(np.float32)                         # remaining lifetime of either sign
+    offsets = (np.arange(U + 1) * C).astype(np.int64)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    list_args = dict(news_cache=cache, corpus=dc, hist_index=t(hist), hist_mask=t(mask), user_freshness=t(ufr), user_lifetime=t(ult),
+                     cand_offsets=t(offsets), cand_index=t(cands), cand_freshness=t(cfr), cand_lifetime=t(clt))
+    n_src = min(P, H + cfg.batch_size)
+    user = np.repeat(np.arange(U), C)
+    beh = DeviceBehaviors(dc, user, hist[user], mask[user], ufr[user], ult[user], cands.reshape(P, 1), cfr.reshape(P, 1), clt.reshape(P, 1),
+                          eval_shape=True)
+    rows = torch.arange(P, device='cuda')
+
+    def new_form():
+        return model.recommend_lists(**list_args, k=k, n_src=n_src)
+
+    def old_form():
+        scores = torch.cat([model.score_behaviors(beh, rows[r0:r0 + args.old_rows], cache, n_src=n_src) for r0 in range(0, P, args.old_rows)])
+        top, pos = torch.topk(scores.view(U, C), k, dim=1)                 # (the lists are as long as each other here: one topk serves all)
+        return pos, top
+
+    new_ms, old_ms, (pos, top), (pos_old, top_old) = alternate(new_form, old_form, args.rounds)
+    new_med, old_med = statistics.median(new_ms), statistics.median(old_ms)
+    # a saturated lifetime weight makes a score an exact zero: among equal scores torch.topk keeps any, recommend_lists the first
+    untied = top_old != 0
+    floor = float(top_old[untied].abs().mean())
+    return {'bench': 'recommend_lists', 'shape': 'serving', 'users': U, 'candidates_per_user': C, 'pairs': P, 'H': H, 'k': k,
+            'rounds': args.rounds, 'recommend_lists_ms': spread(new_ms), 'score_behaviors_topk_ms': spread(old_ms),
+            'score_behaviors_rows_per_call': args.old_rows, 'us_per_pair_recommend_lists': round(1e3 * new_med / P, 4),
+            'us_per_pair_score_behaviors': round(1e3 * old_med / P, 4), 'per_pair_ratio_old_over_new': round(old_med / new_med, 2),
+            'same_positions_fraction': round(float((pos.long() == pos_old).float().mean()), 4),
+            'same_positions_fraction_where_the_score_is_not_zero': round(float((pos.long() == pos_old)[untied].float().mean()), 4),
+            'top_scores_that_are_exact_zeros_fraction': round(float((~untied).float().mean()), 4),
+            'max_top_score_difference_over_mean_magnitude': float(((top - top_old).abs().max() / floor).cpu()),
+            'empty_group_slots': empty_slots(model, dc, list_args['cand_index'], offsets, H, 1 << 18)}
+
+
+def dev_pass(model, dc, cfg, args, n_news):
+    beh, indices, labels, counts = make_dev_split(cfg, dc, args.impressions, n_news, args.seed)
+    per, H = cfg.batch_size, cfg.max_history_num
+    say('dev split: %d impressions, %d rows' % (len(labels), beh.num))
+
+    def new_form():
+        return util.evaluate_cached_on_device(model, beh, indices, labels, rows_per_forward=per, return_scores=True, grouped=True)
+
+    def old_form():
+        return util.evaluate_cached_on_device(model, beh, indices, labels, rows_per_forward=per, return_scores=True)
+
+    new_ms, old_ms, (m_new, s_new), (m_old, s_old) = alternate(new_form, old_form, args.rounds)
+    new_med, old_med = statistics.median(new_ms), statistics.median(old_ms)
+    floor = float(s_old[s_old != 0].abs().mean())
+    full = (beh.num // per) * per
+    runs = util.impression_runs(indices, 0, full)
+    return {'bench': 'recommend_lists', 'shape': 'dev', 'impressions': len(labels), 'rows': beh.num, 'H': H, 'rows_per_forward': per,
+            'rounds': args.rounds, 'grouped_ms': spread(new_ms), 'row_wise_ms': spread(old_ms),
+            'us_per_pair_grouped': round(1e3 * new_med / beh.num, 4), 'us_per_pair_row_wise': round(1e3 * old_med / beh.num, 4),
+            'ratio_row_wise_over_grouped': round(old_med / new_med, 2),
+            'max_score_difference_over_mean_magnitude': float(((s_new - s_old).abs().max() / floor).cpu()),
+            'metrics_grouped': [float(x) for x in m_new], 'metrics_row_wise': [float(x) for x in m_old],
+            'empty_group_slots': empty_slots(model, dc, beh.cand_index[:full].reshape(-1), runs - runs[0],
+                                             H, util.DEVICE_EVAL_ROWS_PER_PASS * H)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--users', type=int, default=1024)
+    ap.add_argument('--candidates', type=int, default=100)
+    ap.add_argument('--k', type=int, default=10)
+    ap.add_argument('--impressions', type=int, default=50000)
+    ap.add_argument('--news', type=int, default=20000)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--old-rows', type=int, default=8192, help='rows per score_behaviors call of the serving shape')
+    ap.add_argument('--user-encoders', nargs='*', default=['CROWN', 'ATT'])
+    ap.add_argument('--shapes', nargs='*', default=['serving', 'dev'])
+    ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--json-out', default=os.path.join(ROOT, 'profiles', 'recommend_lists.json'))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'bench_lists.py measures on the GPU: there is no CPU path'
+
+    lines = []
+    for user_encoder in args.user_encoders:
+        cfg = make_config(user_encoder=user_encoder, vocabulary_size=50000)
+        corpus = synth.synth_corpus(cfg, n_news=args.news, n_train=1, n_dev=1, seed=args.seed)
+        # MIND's subcategories each sit under one category: about 270 topics in all (independent draws would give 18 x 270)
+        corpus.news_category[1:] = 1 + corpus.news_subCategory[1:] % (cfg.category_num - 1)
+        dc = DeviceCorpus(corpus)
+        model = Model(cfg)
+        model.initialize()
+        synth.fill_state_dict(model, seed=args.seed)
+        model = model.cuda().eval()
+        cache = model.build_news_cache(dc)
+        rng = np.random.default_rng(args.seed)
+        for shape in args.shapes:
+            line = serving(model, dc, cache, cfg, args, rng, args.news) if shape == 'serving' else dev_pass(model, dc, cfg, args, args.news)
+            line.update(user_encoder=user_encoder, device=torch.cuda.get_device_name(0))
+            say(line)
+            lines.append(json.dumps(line))
+            torch.cuda.empty_cache()
+        del model, cache, dc
+        torch.cuda.empty_cache()
+    print('\n'.join(lines))
+    if args.json_out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json_out)), exist_ok=True)
+        with open(args.json_out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
