@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from . import newsEncoders, ops, training, userEncoders
+from . import newsEncoders, ops, recommend as rec, training, userEncoders
 from .util import RemainingLifetimeWeighting
 
 # positions (in the 26-tensor signature, model.py:151-154) of the inputs the scoring path reads; the others
@@ -369,9 +369,16 @@ class Model(nn.Module):
     _NO_CONTENT_CACHE = ('content_encoder \'CNE\' has no per-news content cache (its gates read the partner news of the encoder call, '
                          'build_news_cache): score_pool / recommend cannot serve it -- score the pairs with score_behaviors')
 
-    def _check_pool(self, news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
-                    pairs_per_pass, k=None):
-        """The host-side refusals of score_pool / recommend (ValueError, before any launch) -> (U, H, C)."""
+    def grouped_by(self):
+        """What the user side reads of a candidate, as the ``by`` of recommend.pool_plan / topic_table."""
+        crown = hasattr(self.user_encoder, 'user_node_embedding')
+        return None if not self.user_encoder.use_candidate_aware_attn else 'topic' if crown else 'category'
+
+    def _check_grouped(self, news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index, check_candidates,
+                       pairs_per_pass, k, top_k):
+        """The host-side refusals (ValueError, before any launch) that the pool and the lists share, in their order -> (U, H, what
+        ``check_candidates`` returned).  The form's own stand in between: ``bad_index``: its words when cand_index is not shaped as it
+        wants, or None; ``check_candidates(U)`` raises over its other candidate arguments; ``top_k``: (its recommend entry, its kernel)."""
         if self.reads_content_mask:
             raise ValueError(self._NO_CONTENT_CACHE)
         if news_cache.dim() != 2 or news_cache.shape[1] == 0:
@@ -382,19 +389,16 @@ class Model(nn.Module):
         for t, name in ((hist_mask, 'hist_mask'), (user_freshness, 'user_freshness'), (user_lifetime, 'user_lifetime')):
             if tuple(t.shape) != (U, H):
                 raise ValueError('%s must be [U, H] = [%d, %d] like hist_index, got %s' % (name, U, H, tuple(t.shape)))
-        if cand_index.dim() != 1 or cand_index.numel() < 1:
-            raise ValueError('cand_index must be [C] with C >= 1 -- ONE pool for all users -- got %s' % (tuple(cand_index.shape),))
-        C = cand_index.numel()
+        if bad_index:
+            raise ValueError('%s got %s' % (bad_index, tuple(cand_index.shape)))
         if hist_index.dtype not in (torch.int32, torch.int64) or cand_index.dtype not in (torch.int32, torch.int64):
             raise ValueError('hist_index and cand_index must be int32 or int64 news indices, got %s and %s' % (hist_index.dtype, cand_index.dtype))
-        for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
-            if tuple(t.shape) not in ((C,), (U, C)):
-                raise ValueError('%s must be [C] = [%d] or [U, C] = [%d, %d], got %s' % (name, C, U, C, tuple(t.shape)))
+        own = check_candidates(U)
         if int(pairs_per_pass) < 1:
             raise ValueError('pairs_per_pass must be positive, got %r' % (pairs_per_pass,))
         if k is not None and not 1 <= int(k) <= 128:
-            raise ValueError('recommend keeps 1 <= k <= 128 news per user (lime_topk_rows_f32), got k = %r' % (k,))
-        return U, H, C
+            raise ValueError('%s keeps 1 <= k <= 128 news per user (%s), got k = %r' % (top_k + (k,)))
+        return U, H, own
 
     @torch.no_grad()
     def score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
@@ -416,59 +420,83 @@ class Model(nn.Module):
         least one user a pass: the default keeps the scratch around 1 GB at the full-size model.
         ``exclude_history``: a pair whose candidate sits in a masked-in slot of the user's history scores -inf.
         CNE has no per-news cache and is refused (ValueError)."""
-        from . import recommend as rec
-        U, H, C = self._check_pool(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                   cand_lifetime, pairs_per_pass)
-        ne, ue, c = self.news_encoder, self.user_encoder, corpus
-        dev = news_cache.device
-        crown = hasattr(ue, 'user_node_embedding')
+        return self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
+
+    def _user_side(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, n_src, n_pairs):
+        """What every pass of a call reads of the users, once per call -> (hist [U, H, D], ucat [U, H], usub [U, H], hist_mask,
+        gate_y, n_src -- its default from the call's ``n_pairs``)."""
+        ue, (U, H) = self.user_encoder, hist_index.shape
+        hist = self.news_encoder.encode_cached(news_cache, hist_index, user_freshness, user_lifetime).view(U, H, -1)
+        flat_h = hist_index.reshape(-1).long()
+        ucat, usub = corpus.news_category[flat_h].view(U, H), corpus.news_subCategory[flat_h].view(U, H)
+        if n_src is None and hasattr(ue, 'user_node_embedding'):
+            n_src = min(n_pairs, H + ue.user_node_embedding.shape[0])
+        return hist, ucat, usub, hist_mask, ue.gate_projection(hist), n_src       # the gate's projection: once for every pass's histories
+
+    def _match_pass(self, news_cache, users, cands, pick, u0, u1, slots, category, subCategory, group_offsets):
+        """The logits fp32 [pairs], in group order, of one pass of a grouped match: the users u0:u1 (``users``: what ``_user_side``
+        gave), each with ``slots`` groups, user-major (hist_div = slots: a user's groups share one history, never repeated in memory
+        before the refinement); category / subCategory [n slots, 1]: what the user side reads of a group; ``cands``: the call's
+        candidates (news index, freshness, lifetime, remaining lifetime) and ``pick(t)`` the pass's of one of them, in group order;
+        group_offsets int64 [n slots + 1]: the groups' CSR over them, on the device or still on the host (the copy waits for the
+        stream, so it stands behind the launches that do not read it).  The user side runs once per group and the match per pair."""
+        hist, ucat, usub, hist_mask, gate_y, n_src = users
+        index, freshness, lifetime, remaining = cands
+        ne, ue, w = self.news_encoder, self.user_encoder, self.remaining_lifetime_weighting
+        H, D = hist.shape[1:]
+        operands = ue.match_operands(hist[u0:u1], category, subCategory, ucat[u0:u1], usub[u0:u1], hist_mask[u0:u1], n_src=n_src,
+                                     hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
+        cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))           # [pairs, D]
+        group_offsets = torch.as_tensor(group_offsets, device=cand.device)
+        if hasattr(ue, 'user_node_embedding'):
+            g, kp, _ = operands
+            qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                     # userEncoders.py:162
+            h_match, scale = H, 1.0 / ue.attention_scalar
+        else:
+            # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
+            g, h_match, scale = operands, 1, 1.0
+            kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=cand.device)
+            qp = torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=cand.device)
+        return ops.grouped_match(kp, g.reshape(-1, D), qp, cand, pick(remaining).reshape(-1), group_offsets, h_match, scale, w.alpha, w.beta,
+                                 bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty))
+
+    def _score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                    cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
+        """score_pool -> (scores [U, C], bool [U, C] "excluded" or None): the passes over recommend.pool_plan's ONE host plan."""
+        C = cand_index.numel()
+
+        def check_candidates(U):
+            for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
+                if tuple(t.shape) not in ((C,), (U, C)):
+                    raise ValueError('%s must be [C] = [%d] or [U, C] = [%d, %d], got %s' % (name, C, U, C, tuple(t.shape)))
+        bad_index = 'cand_index must be [C] with C >= 1 -- ONE pool for all users --' if cand_index.dim() != 1 or C < 1 else None
+        U, H, _ = self._check_grouped(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index,
+                                      check_candidates, pairs_per_pass, k, ('recommend', 'lime_topk_rows_f32'))
+        c, dev = corpus, news_cache.device
         cidx = cand_index.to(dev).long()
         cat_c, sub_c = c.news_category[cidx], c.news_subCategory[cidx]
-        by = None if not ue.use_candidate_aware_attn else 'topic' if crown else 'category'
-        plan = rec.pool_plan(cat_c.cpu().numpy(), sub_c.cpu().numpy(), by)
-        T = plan.category.shape[0]
-        order = torch.as_tensor(plan.order, device=dev)
-        fresh = cand_freshness.to(dev).float().expand(U, C)
-        remaining = self._lifetime_rule(fresh, lambda: cand_lifetime.to(dev).float().expand(U, C), lambda: cat_c.unsqueeze(0).expand(U, C))
-        life = cand_lifetime.to(dev).float().expand(U, C)
+        plan = rec.pool_plan(cat_c.cpu().numpy(), sub_c.cpu().numpy(), self.grouped_by())
+        T, order = plan.category.shape[0], torch.as_tensor(plan.order, device=dev)
+        fresh, life = cand_freshness.to(dev).float().expand(U, C), cand_lifetime.to(dev).float().expand(U, C)
+        remaining = self._lifetime_rule(fresh, lambda: life, lambda: cat_c.unsqueeze(0).expand(U, C))
         # the pool in plan (topic) order: what every pass reads
-        idx_s, fresh_s, life_s, rem_s = cidx[order], fresh[:, order], life[:, order], remaining.float()[:, order]
-        hist = ne.encode_cached(news_cache, hist_index, user_freshness, user_lifetime).view(U, H, -1)
-        D = hist.shape[2]
-        flat_h = hist_index.reshape(-1).long()
-        ucat, usub = c.news_category[flat_h].view(U, H), c.news_subCategory[flat_h].view(U, H)
-        if n_src is None and crown:
-            n_src = min(U * C, H + ue.user_node_embedding.shape[0])
-        gate_y = ue.gate_projection(hist)                                             # once for every pass's histories
+        cands = cidx[order].unsqueeze(0).expand(U, C), fresh[:, order], life[:, order], remaining.float()[:, order]
+        users = self._user_side(news_cache, c, hist_index, hist_mask, user_freshness, user_lifetime, n_src, U * C)
         per = rec.users_per_pass(U, C, T, H, int(pairs_per_pass))
         cat_t = torch.as_tensor(plan.category, device=dev).to(c.news_category.dtype)
         sub_t = torch.as_tensor(plan.subCategory, device=dev).to(c.news_subCategory.dtype)
-        w = self.remaining_lifetime_weighting
         out = torch.empty((U, C), dtype=torch.float32, device=dev)
         for u0 in range(0, U, per):
             u1 = min(U, u0 + per)
             n = u1 - u0
-            # groups are user-major: hist_div = T topics share one history (never repeated in memory before the refinement)
-            operands = ue.match_operands(hist[u0:u1], cat_t.repeat(n).view(n * T, 1), sub_t.repeat(n).view(n * T, 1), ucat[u0:u1], usub[u0:u1],
-                                         hist_mask[u0:u1], n_src=n_src, hist_div=T,
-                                         gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
-            cand = ne.encode_cached(news_cache, idx_s.unsqueeze(0).expand(n, C), fresh_s[u0:u1], life_s[u0:u1])     # [n C, D]
-            offsets = torch.as_tensor(rec.group_offsets(plan.segments, n), device=dev)
-            if crown:
-                g, kp, _ = operands
-                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                     # userEncoders.py:162
-                h_match, scale = H, 1.0 / ue.attention_scalar
-            else:
-                # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
-                g, h_match, scale = operands, 1, 1.0
-                kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=dev)
-                qp = torch.zeros((n * C, 4), dtype=torch.float32, device=dev)
-            logits = ops.grouped_match(kp, g.reshape(-1, D), qp, cand, rem_s[u0:u1].reshape(-1), offsets, h_match, scale, w.alpha, w.beta,
-                                       bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty))
+            logits = self._match_pass(news_cache, users, cands, lambda t: t[u0:u1], u0, u1, T, cat_t.repeat(n).view(n * T, 1),
+                                      sub_t.repeat(n).view(n * T, 1), rec.group_offsets(plan.segments, n))
             out[u0:u1].index_copy_(1, order, logits.view(n, C))
+        gone = self._in_history(news_cache.shape[0], hist_index, hist_mask, cidx) if exclude_history else None
         if exclude_history:
-            out.masked_fill_(self._in_history(news_cache.shape[0], hist_index, hist_mask, cidx), float('-inf'))
-        return out
+            out.masked_fill_(gone, float('-inf'))
+        return out, gone
 
     @staticmethod
     def _in_history(n_news, hist_index, hist_mask, cidx):
@@ -488,61 +516,13 @@ class Model(nn.Module):
         (+0.0 and -0.0 are equal) go lower position first; a NaN ranks after every number, in position order.  With
         ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is never returned; when fewer than k
         candidates remain, the trailing slots hold position -1 and score -inf.  1 <= k <= 128."""
-        self._check_pool(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
-                         pairs_per_pass, k=k)
-        scores = self.score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                 cand_lifetime, n_src=n_src, pairs_per_pass=pairs_per_pass, exclude_history=exclude_history)
+        scores, gone = self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                        cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
         positions, top = ops.topk_rows(scores, int(k))
-        if exclude_history:
-            gone = self._in_history(news_cache.shape[0], hist_index, hist_mask, cand_index.to(scores.device).long())
+        if gone is not None:
             gone = gone.gather(1, positions.clamp(min=0).long()) & (positions >= 0)
             positions = torch.where(gone, torch.full_like(positions, -1), positions)
         return positions, top
-
-    def _check_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
-                     cand_freshness, cand_lifetime, pairs_per_pass, k=None):
-        """The host-side refusals of score_lists / recommend_lists (ValueError, before any launch) -> (U, H, P, the offsets as a
-        host int64 array, ``by``, the corpus' topic table)."""
-        import numpy as np
-        from . import recommend as rec
-        from .device_data import topic_table_of
-        if self.reads_content_mask:
-            raise ValueError(self._NO_CONTENT_CACHE)
-        if news_cache.dim() != 2 or news_cache.shape[1] == 0:
-            raise ValueError('news_cache must be the [n_news, width] tensor of build_news_cache, got %s' % (tuple(news_cache.shape),))
-        if hist_index.dim() != 2:
-            raise ValueError('hist_index must be [U, H], got %s' % (tuple(hist_index.shape),))
-        U, H = hist_index.shape
-        for t, name in ((hist_mask, 'hist_mask'), (user_freshness, 'user_freshness'), (user_lifetime, 'user_lifetime')):
-            if tuple(t.shape) != (U, H):
-                raise ValueError('%s must be [U, H] = [%d, %d] like hist_index, got %s' % (name, U, H, tuple(t.shape)))
-        if cand_index.dim() != 1:
-            raise ValueError('cand_index must be [P], the lists one behind the other, got %s' % (tuple(cand_index.shape),))
-        P = cand_index.numel()
-        if hist_index.dtype not in (torch.int32, torch.int64) or cand_index.dtype not in (torch.int32, torch.int64):
-            raise ValueError('hist_index and cand_index must be int32 or int64 news indices, got %s and %s' % (hist_index.dtype, cand_index.dtype))
-        off = cand_offsets.detach().cpu().numpy() if isinstance(cand_offsets, torch.Tensor) else np.asarray(cand_offsets)
-        if off.ndim != 1 or off.shape[0] != U + 1 or off.dtype.kind not in 'iu':
-            raise ValueError('cand_offsets must be U + 1 = %d integers (the CSR of the lists), got %s %s' % (U + 1, off.dtype, off.shape))
-        off = off.astype(np.int64)
-        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != P:
-            raise ValueError('cand_offsets must start at 0, not decrease and end at P = %d, got %d .. %d%s'
-                             % (P, off[0], off[-1], ' (decreasing)' if (np.diff(off) < 0).any() else ''))
-        for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
-            if tuple(t.shape) != (P,):
-                raise ValueError('%s must be [P] = [%d], got %s' % (name, P, tuple(t.shape)))
-        if int(pairs_per_pass) < 1:
-            raise ValueError('pairs_per_pass must be positive, got %r' % (pairs_per_pass,))
-        if k is not None and not 1 <= int(k) <= 128:
-            raise ValueError('recommend_lists keeps 1 <= k <= 128 news per user (lime_topk_segments_f32), got k = %r' % (k,))
-        if P == 0:
-            return U, H, P, off, None, None
-        ue = self.user_encoder
-        by = None if not ue.use_candidate_aware_attn else 'topic' if hasattr(ue, 'user_node_embedding') else 'category'
-        table = topic_table_of(corpus, by)
-        if table[1].numel() > rec.MAX_TOPICS:
-            raise ValueError('the corpus has %d topics, lime_list_plan groups up to %d' % (table[1].numel(), rec.MAX_TOPICS))
-        return U, H, P, off, by, table
 
     @torch.no_grad()
     def score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
@@ -555,7 +535,7 @@ class Model(nn.Module):
         ignored otherwise) and ``exclude_history`` as in ``score_pool``; ``cand_offsets`` [U + 1], host or device (it is checked on the
         host); ``cand_index`` / ``cand_freshness`` / ``cand_lifetime`` [P].  The remaining lifetime follows config.lifetime_type.
 
-        ``score_pool``'s body with lists in place of the pool: the pairs are grouped by (user, candidate topic) on the device
+        ``score_pool``'s passes over a plan of the lists: the pairs are grouped by (user, candidate topic) on the device
         (ops.list_plan -- its read of the lists' distinct-topic counts is the call's only synchronisation), the user side runs once
         per group and lime_grouped_match_f32 leaves each pair its two dot products per history slot.  The groups keep the regular
         ``hist_div`` layout: every user of a pass gets S_pass slots, the largest number of distinct topics among the pass's lists, and
@@ -567,36 +547,44 @@ class Model(nn.Module):
 
     def _score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
                      cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
-        """score_lists -> (scores [P], the offsets on the device, bool [P] "excluded" or None)."""
-        from . import recommend as rec
-        U, H, P, off, by, table = self._check_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
-                                                    cand_index, cand_freshness, cand_lifetime, pairs_per_pass, k)
-        ne, ue, c = self.news_encoder, self.user_encoder, corpus
+        """score_lists -> (scores [P], the offsets on the device, bool [P] "excluded" or None): the passes over ops.list_plan's plan."""
+        import numpy as np
+        from .device_data import topic_table_of
+        P = cand_index.numel()
+
+        def check_candidates(U):
+            off = cand_offsets.detach().cpu().numpy() if isinstance(cand_offsets, torch.Tensor) else np.asarray(cand_offsets)
+            if off.ndim != 1 or off.shape[0] != U + 1 or off.dtype.kind not in 'iu':
+                raise ValueError('cand_offsets must be U + 1 = %d integers (the CSR of the lists), got %s %s' % (U + 1, off.dtype, off.shape))
+            off = off.astype(np.int64)
+            if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != P:
+                raise ValueError('cand_offsets must start at 0, not decrease and end at P = %d, got %d .. %d%s'
+                                 % (P, off[0], off[-1], ' (decreasing)' if (np.diff(off) < 0).any() else ''))
+            for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
+                if tuple(t.shape) != (P,):
+                    raise ValueError('%s must be [P] = [%d], got %s' % (name, P, tuple(t.shape)))
+            return off
+        bad_index = 'cand_index must be [P], the lists one behind the other,' if cand_index.dim() != 1 else None
+        U, H, off = self._check_grouped(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index,
+                                        check_candidates, pairs_per_pass, k, ('recommend_lists', 'lime_topk_segments_f32'))
         dev = news_cache.device
         offsets = torch.from_numpy(off).to(dev)
         if P == 0:
             return torch.empty((0,), dtype=torch.float32, device=dev), offsets, None
-        crown = hasattr(ue, 'user_node_embedding')
-        topic_of_news, cat_t, sub_t = table
+        topic_of_news, cat_t, sub_t = topic_table_of(corpus, self.grouped_by())
+        if cat_t.numel() > rec.MAX_TOPICS:
+            raise ValueError('the corpus has %d topics, lime_list_plan groups up to %d' % (cat_t.numel(), rec.MAX_TOPICS))
         cidx = cand_index.to(dev).long()
         fresh, life = cand_freshness.to(dev).float(), cand_lifetime.to(dev).float()
-        remaining = self._lifetime_rule(fresh, lambda: life, lambda: c.news_category[cidx]).float()
+        remaining = self._lifetime_rule(fresh, lambda: life, lambda: corpus.news_category[cidx]).float()
         keys = topic_of_news[cidx]
         plan = ops.list_plan(keys, offsets, n_keys=cat_t.numel())                      # the call's one device -> host read
         S = (plan.slot_key.numel() // U) if U else 1
-        hist = ne.encode_cached(news_cache, hist_index, user_freshness, user_lifetime).view(U, H, -1)
-        D = hist.shape[2]
-        flat_h = hist_index.reshape(-1).long()
-        ucat, usub = c.news_category[flat_h].view(U, H), c.news_subCategory[flat_h].view(U, H)
-        if n_src is None and crown:
-            n_src = min(P, H + ue.user_node_embedding.shape[0])
-        gate_y = ue.gate_projection(hist)                                             # once for every pass's histories
-        w = self.remaining_lifetime_weighting
+        users = self._user_side(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, n_src, P)
         out = torch.empty((P,), dtype=torch.float32, device=dev)
         for u0, u1, S_pass in rec.list_passes(off, plan.n_distinct, H, int(pairs_per_pass)):
             p0, p1 = int(off[u0]), int(off[u1])
-            n, n_pair = u1 - u0, p1 - p0
-            if n_pair == 0:
+            if p1 == p0:
                 continue
             if S_pass == S:                                                           # the pass's plan is a slice of the call's
                 rows, goff, skey = plan.order[p0:p1], plan.group_offsets[u0 * S:u1 * S + 1] - p0, plan.slot_key[u0 * S:u1 * S]
@@ -605,26 +593,10 @@ class Model(nn.Module):
                                     n_distinct=plan.n_distinct[u0:u1])
                 rows, goff, skey = sub.order + p0, sub.group_offsets, sub.slot_key
             skey = skey.long()
-            # groups are user-major: hist_div = S_pass slots share one history (never repeated in memory before the refinement)
-            operands = ue.match_operands(hist[u0:u1], cat_t[skey].view(n * S_pass, 1), sub_t[skey].view(n * S_pass, 1), ucat[u0:u1],
-                                         usub[u0:u1], hist_mask[u0:u1], n_src=n_src, hist_div=S_pass,
-                                         gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
-            cand = ne.encode_cached(news_cache, cidx[rows].view(1, n_pair), fresh[rows].view(1, n_pair), life[rows].view(1, n_pair))
-            if crown:
-                g, kp, _ = operands
-                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                     # userEncoders.py:162
-                h_match, scale = H, 1.0 / ue.attention_scalar
-            else:
-                # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
-                g, h_match, scale = operands, 1, 1.0
-                kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=dev)
-                qp = torch.zeros((n_pair, 4), dtype=torch.float32, device=dev)
-            logits = ops.grouped_match(kp, g.reshape(-1, D), qp, cand, remaining[rows], goff.contiguous(), h_match, scale, w.alpha, w.beta,
-                                       bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty))
-            out.index_copy_(0, rows, logits)
-        gone = None
+            out.index_copy_(0, rows, self._match_pass(news_cache, users, (cidx, fresh, life, remaining), lambda t: t[rows], u0, u1, S_pass,
+                                                      cat_t[skey].view(-1, 1), sub_t[skey].view(-1, 1), goff.contiguous()))
+        gone = self._in_own_history(hist_index.to(dev), hist_mask.to(dev), offsets, cidx) if exclude_history else None
         if exclude_history:
-            gone = self._in_own_history(hist_index.to(dev), hist_mask.to(dev), offsets, cidx)
             out.masked_fill_(gone, float('-inf'))
         return out, offsets, gone
 

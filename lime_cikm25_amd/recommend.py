@@ -13,6 +13,23 @@ PoolPlan.__doc__ = """order int64 [C]: pool positions in group order (stable: po
 group t owns order[segments[t]:segments[t + 1]]; category / subCategory int64 [T]: the topic of group t (what the user side reads)."""
 
 
+def _topics(who, category, subCategory, by):
+    """The topic arguments of ``who`` (pool_plan / topic_table) as int64 [n], n >= 1, refused as both refuse them."""
+    cat, sub = (np.asarray(a).reshape(-1).astype(np.int64) for a in (category, subCategory))
+    if cat.shape[0] < 1 or sub.shape[0] != cat.shape[0]:
+        raise ValueError('%s needs category and subCategory of one length >= 1, got %d and %d' % (who, cat.shape[0], sub.shape[0]))
+    if by not in ('topic', 'category', None):
+        raise ValueError("by must be 'topic', 'category' or None, got %r" % (by,))
+    if by is not None and (cat.min() < 0 or sub.min() < 0):
+        raise ValueError('negative topic ids')
+    return cat, sub
+
+
+def _topic_key(cat, sub, by, width):
+    """One integer per news that two news share exactly when they fall into one group; ``width``: above every subCategory."""
+    return cat * width + sub if by == 'topic' else cat
+
+
 def pool_plan(category, subCategory, by='topic', topics=None):
     """Group a pool of C news by what the user side reads of a candidate.
 
@@ -22,33 +39,26 @@ def pool_plan(category, subCategory, by='topic', topics=None):
     ``topics``: optional list of (category, subCategory) keys (of categories for 'category') that fixes the groups and their order,
     e.g. every topic of the corpus, so that plans of different pools line up; a topic without a candidate stays as an EMPTY group, a
     candidate whose topic is not listed is a ValueError.  Default: the pool's own topics, ascending."""
-    cat = np.asarray(category).reshape(-1).astype(np.int64)
-    sub = np.asarray(subCategory).reshape(-1).astype(np.int64)
+    cat, sub = _topics('pool_plan', category, subCategory, by)
     C = cat.shape[0]
-    if C < 1 or sub.shape[0] != C:
-        raise ValueError('pool_plan needs category and subCategory of one length >= 1, got %d and %d' % (C, sub.shape[0]))
-    if by not in ('topic', 'category', None):
-        raise ValueError("by must be 'topic', 'category' or None, got %r" % (by,))
     if by is None:
         if topics is not None:
             raise ValueError('by=None makes one group: topics cannot be given')
         return PoolPlan(np.arange(C, dtype=np.int64), np.array([0, C], dtype=np.int64), cat[:1].copy(), sub[:1].copy())
-    if cat.min() < 0 or sub.min() < 0:
-        raise ValueError('negative topic ids')
     width = int(sub.max()) + 1
     if topics is not None:
         tk = np.asarray(topics, dtype=np.int64).reshape(len(topics), -1)
         if tk.shape[1] != (2 if by == 'topic' else 1) or (tk < 0).any():
             raise ValueError('topics must be non-negative (category, subCategory) pairs for by=\'topic\', categories for by=\'category\'')
         width = max(width, int(tk[:, -1].max()) + 1) if by == 'topic' else width
-    key = cat * width + sub if by == 'topic' else cat
+    key = _topic_key(cat, sub, by, width)
     if topics is None:
         order = np.argsort(key, kind='stable')
         skey = key[order]
         first = np.flatnonzero(np.concatenate([[True], skey[1:] != skey[:-1]]))
         segments = np.concatenate([first, [C]]).astype(np.int64)
         return PoolPlan(order.astype(np.int64), segments, cat[order[first]], sub[order[first]])
-    gkey = tk[:, 0] * width + tk[:, 1] if by == 'topic' else tk[:, 0]
+    gkey = _topic_key(tk[:, 0], tk[:, -1], by, width)
     if len(set(gkey.tolist())) != len(gkey):
         raise ValueError('topics holds a key twice')
     slot = {int(k): t for t, k in enumerate(gkey)}
@@ -100,17 +110,10 @@ def topic_table(category, subCategory, by):
     ``by`` as in ``pool_plan``: 'topic' -- the (category, subCategory) pair; 'category' -- the category alone (a topic's subCategory is
     its first news' and is not read); None -- one id, 0, for every news.  The ids ascend in ``pool_plan``'s key order, so two news
     share an id exactly when ``pool_plan`` puts them into one group."""
-    cat = np.asarray(category).reshape(-1).astype(np.int64)
-    sub = np.asarray(subCategory).reshape(-1).astype(np.int64)
-    if cat.shape[0] < 1 or sub.shape[0] != cat.shape[0]:
-        raise ValueError('topic_table needs category and subCategory of one length >= 1, got %d and %d' % (cat.shape[0], sub.shape[0]))
-    if by not in ('topic', 'category', None):
-        raise ValueError("by must be 'topic', 'category' or None, got %r" % (by,))
+    cat, sub = _topics('topic_table', category, subCategory, by)
     if by is None:
         return np.zeros(cat.shape[0], dtype=np.int32), cat[:1].copy(), sub[:1].copy()
-    if cat.min() < 0 or sub.min() < 0:
-        raise ValueError('negative topic ids')
-    key = cat * (int(sub.max()) + 1) + sub if by == 'topic' else cat
+    key = _topic_key(cat, sub, by, int(sub.max()) + 1)
     _, first, topic = np.unique(key, return_index=True, return_inverse=True)
     return topic.reshape(-1).astype(np.int32), cat[first], sub[first]
 

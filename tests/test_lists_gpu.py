@@ -188,6 +188,13 @@ def test_exclude_history():
         assert (pos[u][len(live):] == -1).all() and np.isneginf(top[u][len(live):]).all()
 
 
+def test_exclude_history_does_not_depend_on_the_passes():
+    model, args, want, n_src, *_ = build('crown_user')
+    one = model.recommend_lists(**args, k=LENS[0], n_src=n_src, exclude_history=True)
+    many = model.recommend_lists(**args, k=LENS[0], n_src=n_src, exclude_history=True, pairs_per_pass=1)   # one user a pass, re-planned
+    assert torch.equal(many[0], one[0]) and torch.equal(many[1], one[1])
+
+
 def test_a_user_whose_whole_list_is_in_the_history():
     model, args, want, n_src, hist, mask, cands = build('crown_user')
     few = dict(args, cand_offsets=torch.tensor([0, 3, 3, 5, 5]), cand_index=args['cand_index'][:5], cand_freshness=args['cand_freshness'][:5],

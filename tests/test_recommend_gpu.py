@@ -156,6 +156,13 @@ def test_exclude_history():
         assert torch.equal(scores[u][torch.from_numpy(~gone).cuda()], plain[u][torch.from_numpy(~gone).cuda()])
 
 
+def test_exclude_history_does_not_depend_on_the_passes():
+    model, args, want, n_src, *_ = build('crown_user')
+    one = model.recommend(**args, k=C, n_src=n_src, exclude_history=True)
+    many = model.recommend(**args, k=C, n_src=n_src, exclude_history=True, pairs_per_pass=40)          # one user a pass
+    assert torch.equal(many[0], one[0]) and torch.equal(many[1], one[1])
+
+
 def test_a_user_whose_whole_pool_is_in_the_history():
     model, args, want, n_src, hist, mask, pool = build('crown_user')
     H = hist.shape[1]

@@ -61,9 +61,7 @@ def alternate(new_form, old_form, rounds):
 
 def empty_slots(model, dc, cand_index, offsets, H, pairs_per_pass):
     """Share of group slots that hold no pair, per pass of score_lists: (overall, smallest, largest, passes, largest slot count)."""
-    ue = model.user_encoder
-    by = None if not ue.use_candidate_aware_attn else 'topic' if hasattr(ue, 'user_node_embedding') else 'category'
-    topic_of_news, cat_t, _ = dc.topic_table(by)
+    topic_of_news, cat_t, _ = dc.topic_table(model.grouped_by())
     plan = ops.list_plan(topic_of_news[cand_index.long()], torch.from_numpy(offsets).cuda(), n_keys=cat_t.numel())
     nd = plan.n_distinct.astype(np.int64)
     shares, used, slots, s_max = [], 0, 0, 1
