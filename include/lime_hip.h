@@ -1203,6 +1203,15 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * the pair's place in its tile.  1 <= H <= 128, A and D multiples of 4 up to 2048 (LIME_ERR_UNSUPPORTED otherwise); kp, g, qp, cand
  * 16-byte aligned (LIME_ERR_BAD_ARG otherwise).  H = 1 is the match of one pooled user vector g[i] per group (alpha = 1).
  *
+ * lime_grouped_match_indexed_f32 (same file): the same function with the pairs' own operands read through an index -- qp [n, A] and
+ * cand [n, D] are TABLES of n rows and pair p reads row index[p] of both (index int32 [P] on the device); remaining, offsets and
+ * logits stay per pair.  For a model whose candidate representation depends on the news alone (no LIME: Model._match_pass) the tables
+ * are the pool's rows or the news cache itself, and no [P, D] copy of them exists.  A pair's bits equal those of
+ * lime_grouped_match_f32 on the gathered rows qp[index], cand[index].  An index outside [0, n) is CLAMPED into it by the kernel (as
+ * the offsets are): a bad plan reads in range and gives the result of the row it was clamped to.  n = 0 with P > 0 is
+ * LIME_ERR_BAD_ARG; n < 2^31 (LIME_ERR_UNSUPPORTED beyond); the other limits and statuses are those of lime_grouped_match_f32, checked
+ * in the same order before any launch.
+ *
  * lime_topk_rows_f32 (csrc/topk_rows_f32.hip): per row u < U of scores [U, C] (leading dimension ld >= C) the k best entries:
  * positions int32 [U, k] (column indices) and top_scores fp32 [U, k] (the input's bits at those positions), in descending order of
  * the score; equal scores -- +0.0 and -0.0 are equal -- lower position first; a NaN ranks behind every number, NaNs in position
@@ -1213,6 +1222,10 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
 int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
                            const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D, float scale,
                            float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
+int lime_grouped_match_indexed_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
+                                   const int64_t* offsets, const int32_t* index, int64_t n, float* logits, int64_t G, int64_t P,
+                                   int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s, int32_t use_weight,
+                                   int32_t use_penalty, void* stream);
 int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);

@@ -16,6 +16,11 @@
 // run on the results (h over the lane's 4 T registers in order, then the two butterfly steps over the lanes 16 and 32 apart).  Every sum has
 // a fixed order that depends on H, A and D alone: a pair's bits depend neither on P, G, the group's position, the pair's place in its
 // tile nor the grid.  No atomics.
+//
+// The indexed form (lime_grouped_match_indexed_f32): the pair's own operands are rows of two TABLES, qp [n, A] and cand [n, D], and
+// pair p reads row index[p] of both -- a candidate whose representation depends on the news alone is not copied once per (user,
+// candidate) pair.  Nothing else changes: only the row that tile_product reads as Y differs, so a pair's bits are those of the plain
+// form on the gathered rows.  An index outside [0, n) is clamped into it (as the offsets are clamped): a bad plan reads in range.
 #include "dev_helpers.h"
 
 namespace {
@@ -99,12 +104,14 @@ __device__ __forceinline__ void tile_product(const float* __restrict__ X, long x
     lds_barrier();
 }
 
-template <int T>
+// INDEXED: qp / cand are tables of n rows and pair p reads row index[p] (clamped into [0, n)) of both; else row p (index unread).
+template <int T, bool INDEXED>
 __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restrict__ kp, const float* __restrict__ g,
                                                              const float* __restrict__ qp, const float* __restrict__ cand,
                                                              const float* __restrict__ remaining, const long* __restrict__ offsets,
-                                                             float* __restrict__ logits, long P, int H, int A, int D, float scale,
-                                                             float alpha_s, float beta_s, int use_weight, int use_penalty) {
+                                                             const int* __restrict__ index, int n, float* __restrict__ logits, long P, int H,
+                                                             int A, int D, float scale, float alpha_s, float beta_s, int use_weight,
+                                                             int use_penalty) {
     __shared__ __attribute__((aligned(16))) float img[2 * 16 * T * CHUNK];
     const long grp = blockIdx.x;
     long lo = offsets[grp], hi = offsets[grp + 1];
@@ -115,9 +122,14 @@ __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restr
     for (long tile = blockIdx.y; tile < n_tile; tile += gridDim.y) {         // (workgroup-uniform: the barriers inside stay whole)
         const long p = lo + tile * PAIRS + 16 * wave + (lane & 15);
         const bool live = p < hi;
+        long y = p;                                          // the pair's row of qp and cand
+        if constexpr (INDEXED) {
+            const int i = live ? index[p] : 0;
+            y = i < 0 ? 0 : (i >= n ? n - 1 : i);
+        }
         f32x4 s[T], m[T];
-        tile_product<T>(kp, grp * H, H, qp, p, live, A, img, s);
-        tile_product<T>(g, grp * H, H, cand, p, live, D, img, m);
+        tile_product<T>(kp, grp * H, H, qp, y, live, A, img, s);
+        tile_product<T>(g, grp * H, H, cand, y, live, D, img, m);
         // softmax over the history (unmasked, userEncoders.py:164) and the weighted sum, on this lane's 4 T values of its pair
         const int h0 = 4 * (lane_here() >> 4);               // (recomputed: hoisted out of the tile loop, the 4 T padding tests
                                                              // would sit in SGPR pairs through both products and spill)
@@ -153,17 +165,22 @@ __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restr
 
 }  // namespace
 
-extern "C" int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
-                                      const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D,
-                                      float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream) {
-    LIME_REQUIRE(kp && g && qp && cand && offsets && logits, LIME_ERR_BAD_ARG, "lime_grouped_match_f32: NULL pointer");
-    LIME_REQUIRE(!use_weight || remaining, LIME_ERR_BAD_ARG, "lime_grouped_match_f32: remaining is NULL");
-    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && D > 0, LIME_ERR_BAD_ARG, "lime_grouped_match_f32: bad dims");
-    LIME_REQUIRE(H <= 128 && A <= 2048 && D <= 2048 && A % 4 == 0 && D % 4 == 0 && G < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
-                 "lime_grouped_match_f32: H %d, A %d, D %d outside 1 <= H <= 128, A and D multiples of 4 up to 2048 (or %lld groups >= 2^31)",
-                 H, A, D, (long long)G);
+namespace {
+
+// The checks and the launch both entries share.  index == nullptr: the plain form (qp / cand hold P rows).
+int grouped_match_launch(const char* who, const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
+                         const int64_t* offsets, const int32_t* index, int64_t n, bool indexed, float* logits, int64_t G, int64_t P,
+                         int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s, int32_t use_weight,
+                         int32_t use_penalty, void* stream) {
+    LIME_REQUIRE(kp && g && qp && cand && offsets && logits && (!indexed || index), LIME_ERR_BAD_ARG, "%s: NULL pointer", who);
+    LIME_REQUIRE(!use_weight || remaining, LIME_ERR_BAD_ARG, "%s: remaining is NULL", who);
+    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && D > 0 && n >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
+    LIME_REQUIRE(H <= 128 && A <= 2048 && D <= 2048 && A % 4 == 0 && D % 4 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
+                 "%s: H %d, A %d, D %d outside 1 <= H <= 128, A and D multiples of 4 up to 2048 (or %lld groups / %lld table rows >= 2^31)",
+                 who, H, A, D, (long long)G, (long long)n);
     LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qp, A) && lime_al16(g, D) && lime_al16(cand, D), LIME_ERR_BAD_ARG,
-                 "lime_grouped_match_f32: kp, qp, g and cand must be 16-byte aligned");
+                 "%s: kp, qp, g and cand must be 16-byte aligned", who);
+    LIME_REQUIRE(!indexed || n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
     if (G == 0 || P == 0) return LIME_OK;
     // tile slices per group: enough workgroups to fill the chip when the groups are few (one group per user with the candidate-aware
     // attention off), never more than the tiles the pairs can make.  The split changes which workgroup takes a tile, not its bits.
@@ -172,13 +189,37 @@ extern "C" int lime_grouped_match_f32(const float* kp, const float* g, const flo
     slices = slices > all_tiles ? all_tiles : slices;
     slices = slices < 1 ? 1 : (slices > 65535 ? 65535 : slices);
     const dim3 grid((unsigned)G, (unsigned)slices);
-#define LIME_GM_LAUNCH(T_)                                                                                                              \
-    hipLaunchKernelGGL((grouped_match_kernel<T_>), grid, dim3(256), 0, (hipStream_t)stream, kp, g, qp, cand, remaining, (const long*)offsets, \
-                       logits, (long)P, H, A, D, scale, alpha_s, beta_s, use_weight, use_penalty)
-    if (H <= 16) LIME_GM_LAUNCH(1);
-    else if (H <= 32) LIME_GM_LAUNCH(2);
-    else if (H <= 64) LIME_GM_LAUNCH(4);
-    else LIME_GM_LAUNCH(8);
+#define LIME_GM_LAUNCH(T_, I_)                                                                                                          \
+    hipLaunchKernelGGL((grouped_match_kernel<T_, I_>), grid, dim3(256), 0, (hipStream_t)stream, kp, g, qp, cand, remaining,             \
+                       (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, D, scale, alpha_s, beta_s, use_weight,   \
+                       use_penalty)
+#define LIME_GM_PICK(I_)                                                                                                                \
+    do {                                                                                                                                \
+        if (H <= 16) LIME_GM_LAUNCH(1, I_);                                                                                             \
+        else if (H <= 32) LIME_GM_LAUNCH(2, I_);                                                                                        \
+        else if (H <= 64) LIME_GM_LAUNCH(4, I_);                                                                                        \
+        else LIME_GM_LAUNCH(8, I_);                                                                                                     \
+    } while (0)
+    if (indexed) LIME_GM_PICK(true);
+    else LIME_GM_PICK(false);
+#undef LIME_GM_PICK
 #undef LIME_GM_LAUNCH
-    return lime_check_launch("lime_grouped_match_f32");
+    return lime_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
+                                      const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D,
+                                      float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream) {
+    return grouped_match_launch("lime_grouped_match_f32", kp, g, qp, cand, remaining, offsets, nullptr, 0, false, logits, G, P, H, A, D,
+                                scale, alpha_s, beta_s, use_weight, use_penalty, stream);
+}
+
+extern "C" int lime_grouped_match_indexed_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
+                                              const int64_t* offsets, const int32_t* index, int64_t n, float* logits, int64_t G, int64_t P,
+                                              int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s,
+                                              int32_t use_weight, int32_t use_penalty, void* stream) {
+    return grouped_match_launch("lime_grouped_match_indexed_f32", kp, g, qp, cand, remaining, offsets, index, n, true, logits, G, P, H, A,
+                                D, scale, alpha_s, beta_s, use_weight, use_penalty, stream);
 }

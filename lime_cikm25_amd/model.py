@@ -1,4 +1,7 @@
-"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE,KCNN}-{CROWN,ATT,MHSA} scoring path (reference model.py:11-187)."""
+"""Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE,KCNN}-{CROWN,ATT,MHSA} scoring path and the baselines without LIME,
+{CROWN,CNN,NAML,MHSA,KCNN}-{ATT,MHSA} and CROWN-CROWN (reference model.py:11-187)."""
+import os
+
 import torch
 import torch.nn as nn
 
@@ -21,6 +24,9 @@ _PAIRS_TITLE_ENTITY = _PAIRS + ((19, 5),)
 
 
 _USER_ENCODERS = ('CROWN', 'ATT', 'MHSA')
+_CONTENT_ENCODERS = ('CROWN', 'CNN', 'NAML', 'MHSA', 'CNE', 'KCNN')
+# config.news_encoder other than 'LIME' (model.py:41-62): the content encoder as the news encoder itself, the baselines of the paper
+_PLAIN_NEWS_ENCODERS = ('CROWN', 'CNN', 'NAML', 'MHSA', 'KCNN')
 # why the reference's other user encoders (model.py:67-88) stay refused
 _REFUSED_USER_ENCODERS = {
     'LSTUR': ' (it needs user_ID embeddings and a GRU)', 'GRU': ' (it needs a GRU over the history)',
@@ -30,10 +36,20 @@ _REFUSED_USER_ENCODERS = {
 }
 
 
+# A baseline model's candidates depend on the news alone: the grouped match reads them in place through an index
+# (lime_grouped_match_indexed_f32).  LIME_INDEXED_MATCH=0 keeps the gather form for them too -- one materialised row and one Q row per
+# (user, candidate) pair, the path LIME models take -- as the yardstick of the indexed one (tools/bench_recommend.py, tools/bench_lists.py).
+INDEXED_MATCH = os.environ.get('LIME_INDEXED_MATCH', '1') != '0'
+
+
 class Model(nn.Module):
     """Same constructor, attributes (``model_name``, ``config``, ``news_encoder``, ``user_encoder``,
     ``news_embedding_dim``), ``initialize()`` and 26-tensor ``forward`` as the reference's Model
     (model.py:12-187); ``state_dict()`` has the reference's key set.  ``forward`` returns logits [B, N].
+    ``config.news_encoder``: 'LIME' (the default), or 'CROWN', 'CNN', 'NAML', 'MHSA' or 'KCNN' -- that content encoder as the news
+    encoder itself, the baselines of the paper (model.py:41-62: ``model_name`` is "X-Y", ``news_encoder`` IS the content encoder, so the
+    keys carry no ``base_news_encoder.`` level, ``config.content_encoder`` is not read, freshness and lifetime inputs are accepted and
+    not read; the ATT and MHSA user encoders pair with all five, CROWN with 'CROWN' alone; 'CNE' without LIME stays refused).
     ``config.content_encoder`` picks LIME's base encoder: 'CROWN', 'CNN', 'NAML' (cnn_method 'naive' or 'group3'), 'MHSA', 'CNE' or
     'KCNN' (cnn_method 'naive', 'group3' or 'group4'; it reads the ``*_title_entity`` inputs);
     ``config.user_encoder`` the user encoder: 'CROWN', 'ATT' (NAML's additive attention) or 'MHSA' (NRMS's self-attention), in any
@@ -54,28 +70,35 @@ class Model(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
-        if config.news_encoder != 'LIME':
-            raise NotImplementedError('news_encoder %r: the MI355X path covers LIME (config.py:25)' % config.news_encoder)
-        if config.content_encoder == 'CROWN':
-            base_encoder = newsEncoders.CROWN(config)
-        elif config.content_encoder == 'CNN':
-            base_encoder = newsEncoders.CNN(config)
-        elif config.content_encoder == 'NAML':
-            base_encoder = newsEncoders.NAML(config)
-        elif config.content_encoder == 'MHSA':
-            base_encoder = newsEncoders.MHSA(config)
-        elif config.content_encoder == 'CNE':
-            base_encoder = newsEncoders.CNE(config)
-        elif config.content_encoder == 'KCNN':
-            base_encoder = newsEncoders.KCNN(config)
+        if config.news_encoder == 'LIME':
+            if config.content_encoder not in _CONTENT_ENCODERS:
+                raise NotImplementedError('content_encoder %r is a baseline outside the scoring path' % config.content_encoder)
+            base_encoder = getattr(newsEncoders, config.content_encoder)(config)
+            self.news_encoder = newsEncoders.LIME(config=config, base_news_encoder=base_encoder)
+        elif config.news_encoder in _PLAIN_NEWS_ENCODERS:
+            # the baseline form (model.py:41-62): the content encoder IS the news encoder -- no wrapper, so the state_dict keys are
+            # news_encoder.word_embedding.weight, ...; config.content_encoder is not read
+            base_encoder = self.news_encoder = getattr(newsEncoders, config.news_encoder)(config)
+        elif config.news_encoder == 'CNE':
+            raise NotImplementedError('news_encoder \'CNE\' without LIME stays refused: its gates pair the news of an encoder call, so it '
+                                      'has no per-news cache, and its 1,700-column representation is outside the refinement kernels -- '
+                                      'use news_encoder=\'LIME\' with content_encoder=\'CNE\'')
         else:
-            raise NotImplementedError('content_encoder %r is a baseline outside the scoring path' % config.content_encoder)
-        self.news_encoder = newsEncoders.LIME(config=config, base_news_encoder=base_encoder)
+            raise NotImplementedError('news_encoder %r: the MI355X path covers LIME (config.py:25) and the baselines %s' % (
+                config.news_encoder, ', '.join(_PLAIN_NEWS_ENCODERS)))
         if config.user_encoder not in _USER_ENCODERS:
             raise NotImplementedError('user_encoder %r is outside the scoring path%s: the supported user encoders are %s' % (
                 config.user_encoder, _REFUSED_USER_ENCODERS.get(config.user_encoder, ''), ', '.join(sorted(_USER_ENCODERS))))
+        if config.user_encoder == 'CROWN' and config.news_encoder not in ('LIME', 'CROWN'):
+            # userEncoders.py:103-105: the CROWN user encoder runs news_encoder.category_affine over the 100-wide topic pair
+            raise NotImplementedError('user_encoder \'CROWN\' needs the news encoder\'s category_affine over the (category, subCategory) '
+                                      'pair (userEncoders.py:103-105): news_encoder %r has %s -- pair it with ATT or MHSA, or put it under LIME'
+                                      % (config.news_encoder, 'a category_affine of another shape' if hasattr(self.news_encoder, 'category_affine')
+                                         else 'no category_affine'))
         self.user_encoder = getattr(userEncoders, config.user_encoder)(self.news_encoder, config)
-        self.model_name = f"{config.news_encoder}-{config.content_encoder}-{config.user_encoder}"
+        self.plain = config.news_encoder != 'LIME'          # a baseline: the news encoder is the content encoder itself
+        self.model_name = (f"{config.news_encoder}-{config.user_encoder}" if self.plain else
+                           f"{config.news_encoder}-{config.content_encoder}-{config.user_encoder}")     # model.py:92-95
         self.news_embedding_dim = self.news_encoder.news_embedding_dim
         self.dropout = nn.Dropout(p=config.dropout_rate)
         self.use_user_embedding = False
@@ -90,6 +113,11 @@ class Model(nn.Module):
         self.reads_title_entity = bool(getattr(base_encoder, 'reads_title_entity', False))
         self._used = _USED_BODY_MASK if self.reads_content_mask else _USED_TITLE_ENTITY if self.reads_title_entity else _USED
         self._pairs = _PAIRS_BODY_MASK if self.reads_content_mask else _PAIRS_TITLE_ENTITY if self.reads_title_entity else _PAIRS
+
+    @property
+    def content_encoder(self):
+        """The content encoder: LIME's base encoder, or the news encoder itself in the baseline form."""
+        return self.news_encoder if self.plain else self.news_encoder.base_news_encoder
 
     def _apply(self, fn, *args, **kwargs):
         self._graphs = {}                      # parameter storage moves: captured pointers are stale
@@ -106,7 +134,7 @@ class Model(nn.Module):
     def _sync_weight_products(self):
         """Before a scoring forward: bring the content encoder's weight products up to date (in place, on the current stream) and drop
         the captured graphs if one of their buffers had to move or the forward changed between the two first-layer paths."""
-        enc = self.news_encoder.base_news_encoder
+        enc = self.content_encoder
         if hasattr(enc, 'products_key'):
             key = enc.products_key()
             if key != getattr(self, '_products_key', None):
@@ -165,7 +193,7 @@ class Model(nn.Module):
                 out = self._forward_impl(*static)
             entry = (graph, [static[i] for i in _USED], out)
             self._graphs[key] = entry
-            enc = self.news_encoder.base_news_encoder
+            enc = self.content_encoder
             if hasattr(enc, 'products_key'):
                 self._products_key = enc.products_key()      # (the warm-up may have built the weight products this graph reads)
         graph, static_used, out = entry
@@ -419,7 +447,10 @@ class Model(nn.Module):
         the candidate rows (users x C) and the refined history rows (users x topics x H) within ``pairs_per_pass`` rows each, at
         least one user a pass: the default keeps the scratch around 1 GB at the full-size model.
         ``exclude_history``: a pair whose candidate sits in a masked-in slot of the user's history scores -inf.
-        CNE has no per-news cache and is refused (ValueError)."""
+        CNE has no per-news cache and is refused (ValueError).
+        A baseline model (no LIME): a candidate's row depends on the news alone, so the pool's C rows (and their Q) are made once per
+        call and every pair reads them in place through its pool position (lime_grouped_match_indexed_f32, ``_candidate_tables``); the
+        passes are then bounded by the refined history rows alone.  LIME_INDEXED_MATCH=0 keeps the per-pair rows."""
         return self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                                 cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
 
@@ -438,28 +469,52 @@ class Model(nn.Module):
         """The logits fp32 [pairs], in group order, of one pass of a grouped match: the users u0:u1 (``users``: what ``_user_side``
         gave), each with ``slots`` groups, user-major (hist_div = slots: a user's groups share one history, never repeated in memory
         before the refinement); category / subCategory [n slots, 1]: what the user side reads of a group; ``cands``: the call's
-        candidates (news index, freshness, lifetime, remaining lifetime) and ``pick(t)`` the pass's of one of them, in group order;
+        candidates (news index, freshness, lifetime, remaining lifetime, then what ``_candidate_tables`` gave and -- with tables -- every
+        pair's row of them) and ``pick(t)`` the pass's of one of them, in group order;
         group_offsets int64 [n slots + 1]: the groups' CSR over them, on the device or still on the host (the copy waits for the
         stream, so it stands behind the launches that do not read it).  The user side runs once per group and the match per pair."""
         hist, ucat, usub, hist_mask, gate_y, n_src = users
-        index, freshness, lifetime, remaining = cands
+        index, freshness, lifetime, remaining, tables, position = cands
         ne, ue, w = self.news_encoder, self.user_encoder, self.remaining_lifetime_weighting
         H, D = hist.shape[1:]
+        dev = news_cache.device
         operands = ue.match_operands(hist[u0:u1], category, subCategory, ucat[u0:u1], usub[u0:u1], hist_mask[u0:u1], n_src=n_src,
                                      hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
-        cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))           # [pairs, D]
-        group_offsets = torch.as_tensor(group_offsets, device=cand.device)
-        if hasattr(ue, 'user_node_embedding'):
+        crown = hasattr(ue, 'user_node_embedding')
+        if tables is None:
+            cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))       # [pairs, D]
+            at = None
+        else:
+            cand, qp = tables                                                                       # the call's tables, read in place
+            at = newsEncoders._i32(pick(position).reshape(-1)).contiguous()                         # int32 [pairs]: the pair's table row
+        group_offsets = torch.as_tensor(group_offsets, device=dev)
+        if crown:
             g, kp, _ = operands
-            qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                     # userEncoders.py:162
+            if tables is None:
+                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                 # userEncoders.py:162
             h_match, scale = H, 1.0 / ue.attention_scalar
         else:
             # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
             g, h_match, scale = operands, 1, 1.0
-            kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=cand.device)
-            qp = torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=cand.device)
+            kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=dev)
+            if tables is None:
+                qp = torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=dev)
         return ops.grouped_match(kp, g.reshape(-1, D), qp, cand, pick(remaining).reshape(-1), group_offsets, h_match, scale, w.alpha, w.beta,
-                                 bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty))
+                                 bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=at)
+
+    def _candidate_tables(self, news_cache, rows=None):
+        """The ONE place that asks whether a candidate's representation depends on the news alone (``occurrence_free``: a baseline
+        model's news encoder; LIME's rows depend on the occurrence) -> None: ``_match_pass`` materialises a row and a Q row per pair; or
+        the tables (cand [n, D], qp [n, A]) that lime_grouped_match_indexed_f32 reads in place, once per call: the news of ``rows``
+        (the pool, in plan order) or, with ``rows`` None, every news of the cache (the lists: a pair's index is its news id).  Under
+        ATT / MHSA (a history of one row) qp is never felt: n rows of four zero columns -- the kernel reads both tables at one index."""
+        ne, ue = self.news_encoder, self.user_encoder
+        if not (INDEXED_MATCH and getattr(ne, 'occurrence_free', False)):
+            return None
+        cand = news_cache.contiguous() if rows is None else ne.encode_cached(news_cache, rows)
+        if hasattr(ue, 'user_node_embedding'):
+            return cand, ops.linear(cand, ue.Q.weight, ue.Q.bias)                                             # userEncoders.py:162
+        return cand, torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=cand.device)
 
     def _score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                     cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
@@ -481,9 +536,12 @@ class Model(nn.Module):
         fresh, life = cand_freshness.to(dev).float().expand(U, C), cand_lifetime.to(dev).float().expand(U, C)
         remaining = self._lifetime_rule(fresh, lambda: life, lambda: cat_c.unsqueeze(0).expand(U, C))
         # the pool in plan (topic) order: what every pass reads
-        cands = cidx[order].unsqueeze(0).expand(U, C), fresh[:, order], life[:, order], remaining.float()[:, order]
+        tables = self._candidate_tables(news_cache, cidx[order])       # (a baseline model: the pool's C rows and their Q, once per call)
+        cands = (cidx[order].unsqueeze(0).expand(U, C), fresh[:, order], life[:, order], remaining.float()[:, order], tables,
+                 None if tables is None else torch.arange(C, dtype=torch.int32, device=dev).unsqueeze(0).expand(U, C))
         users = self._user_side(news_cache, c, hist_index, hist_mask, user_freshness, user_lifetime, n_src, U * C)
-        per = rec.users_per_pass(U, C, T, H, int(pairs_per_pass))
+        # (read in place, the candidates take no rows of a pass: the refined rows alone bound its users)
+        per = rec.users_per_pass(U, C if tables is None else 0, T, H, int(pairs_per_pass))
         cat_t = torch.as_tensor(plan.category, device=dev).to(c.news_category.dtype)
         sub_t = torch.as_tensor(plan.subCategory, device=dev).to(c.news_subCategory.dtype)
         out = torch.empty((U, C), dtype=torch.float32, device=dev)
@@ -541,7 +599,9 @@ class Model(nn.Module):
         ``hist_div`` layout: every user of a pass gets S_pass slots, the largest number of distinct topics among the pass's lists, and
         a list with fewer topics leaves slots whose refinement nobody reads.  Passes run over consecutive users and keep their pairs
         and their users x S_pass x H refined rows within ``pairs_per_pass`` each, one user a pass at the least.
-        CNE has no per-news cache and is refused (ValueError)."""
+        CNE has no per-news cache and is refused (ValueError).
+        A baseline model (no LIME): the candidates are read in place from the cache through the pair's news id
+        (lime_grouped_match_indexed_f32), with Q of every news of the cache computed once per call under the CROWN user encoder."""
         return self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
                                  cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
 
@@ -581,6 +641,7 @@ class Model(nn.Module):
         plan = ops.list_plan(keys, offsets, n_keys=cat_t.numel())                      # the call's one device -> host read
         S = (plan.slot_key.numel() // U) if U else 1
         users = self._user_side(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, n_src, P)
+        tables = self._candidate_tables(news_cache)                   # (a baseline model: the cache itself, and Q of every news once)
         out = torch.empty((P,), dtype=torch.float32, device=dev)
         for u0, u1, S_pass in rec.list_passes(off, plan.n_distinct, H, int(pairs_per_pass)):
             p0, p1 = int(off[u0]), int(off[u1])
@@ -593,7 +654,8 @@ class Model(nn.Module):
                                     n_distinct=plan.n_distinct[u0:u1])
                 rows, goff, skey = sub.order + p0, sub.group_offsets, sub.slot_key
             skey = skey.long()
-            out.index_copy_(0, rows, self._match_pass(news_cache, users, (cidx, fresh, life, remaining), lambda t: t[rows], u0, u1, S_pass,
+            out.index_copy_(0, rows, self._match_pass(news_cache, users, (cidx, fresh, life, remaining, tables, cidx), lambda t: t[rows], u0, u1,
+                                                      S_pass,
                                                       cat_t[skey].view(-1, 1), sub_t[skey].view(-1, 1), goff.contiguous()))
         gone = self._in_own_history(hist_index.to(dev), hist_mask.to(dev), offsets, cidx) if exclude_history else None
         if exclude_history:

@@ -551,6 +551,69 @@ class NewsEncoder(nn.Module):
             self.encode_flat(*flat, out)
         return out.view(B, n, -1)
 
+    # ---- the content encoder as the model's news encoder itself (config.news_encoder = 'CROWN', 'CNN', ...: reference model.py:41-62,
+    # the baselines LIME is compared with).  The surface Model calls on LIME, with the occurrence side -- freshness, the user's topic
+    # lifetime -- being the identity: a representation depends on the news alone.
+    occurrence_free = True          # Model._match_pass: candidates are read in place through an index (LIME: one row per occurrence)
+
+    def encode_rows(self, title_text, title_mask, content_text, category, subCategory, title_entity=None):
+        """M flat news -> [M, news_embedding_dim] on the scoring kernels (``encode_flat`` into a fresh buffer)."""
+        if self.reads_content_mask:
+            raise NotImplementedError('%s pairs the news of an encoder call: it has no per-news form' % type(self).__name__)
+        out = torch.empty((category.shape[0], self.news_embedding_dim), dtype=torch.float32, device=category.device)
+        if self.reads_title_entity:
+            if title_entity is None:
+                raise TypeError('the KCNN content encoder reads the title entity ids: pass title_entity -- the ids are never guessed')
+            self.encode_flat(title_text, title_mask, content_text, category, subCategory, out, title_entity=title_entity)
+        else:
+            self.encode_flat(title_text, title_mask, content_text, category, subCategory, out)
+        return out
+
+    def encode_many(self, groups):
+        """``LIME.encode_many`` without the occurrence side: several [B, n, ...] groups (candidates, history) in ONE pass over the kernels
+        -> one [B, n, news_embedding_dim] tensor per group.  A group's freshness, lifetime and body mask (members six to eight) are
+        accepted and not read; the ninth, the title's entity ids, is read by KCNN alone."""
+        shapes, flat, ents = [], [[] for _ in range(5)], []
+        for group in groups:
+            tt, tm, ct, cat, sub = group[:5]
+            B, n = tt.shape[0], tt.shape[1]
+            shapes.append((B, n))
+            if len(group) > 8 and group[8] is not None:
+                ents.append(_i32(group[8]).reshape(B * n, -1))
+            for dst, t in zip(flat, (_i32(tt).reshape(B * n, -1), tm.reshape(B * n, -1), _i32(ct).reshape(B * n, -1),
+                                     _i32(cat).reshape(-1), _i32(sub).reshape(-1))):
+                dst.append(t)
+        if ents and len(ents) != len(groups):
+            raise ValueError('encode_many: the title entity ids must be given for every group or for none')
+        cat_all = [t[0].contiguous() if len(t) == 1 else _cat_rows(t) for t in flat]
+        ent = None if not ents else (ents[0].contiguous() if len(ents) == 1 else _cat_rows(ents))
+        out = self.encode_rows(*cat_all, title_entity=ent)
+        res, r0 = [], 0
+        for (B, n) in shapes:
+            res.append(out[r0:r0 + B * n].view(B, n, -1))
+            r0 += B * n
+        return res
+
+    def build_content_cache(self, title_text, title_mask, content_text, category, subCategory, rows_per_pass=8192, title_entity=None):
+        """One row per news [n, news_embedding_dim]: the news' representation itself (nothing of it depends on the occurrence).
+        Rebuild it when weights change.  ``title_entity`` [n, T]: the titles' entity ids, for KCNN."""
+        n = title_text.shape[0]
+        if self.reads_title_entity and title_entity is None:
+            raise TypeError('the KCNN content encoder reads the title entity ids: pass title_entity -- the ids are never guessed')
+        cache = torch.empty((n, self.news_embedding_dim), dtype=torch.float32, device=title_text.device)
+        for r0 in range(0, n, rows_per_pass):
+            r1 = min(n, r0 + rows_per_pass)
+            kw = dict(title_entity=_i32(title_entity[r0:r1]).contiguous()) if self.reads_title_entity else {}
+            self.encode_flat(_i32(title_text[r0:r1]).contiguous(), title_mask[r0:r1].contiguous(), _i32(content_text[r0:r1]).contiguous(),
+                             _i32(category[r0:r1]).contiguous(), _i32(subCategory[r0:r1]).contiguous(), cache[r0:r1], **kw)
+        return cache
+
+    def encode_cached(self, cache, news_index, freshness=None, lifetime=None, fused=None):
+        """Representations of the occurrences -> [R, news_embedding_dim]: a row gather from the cache (``freshness`` / ``lifetime`` are
+        accepted and not read)."""
+        idx = _i32(news_index.reshape(-1)).contiguous()
+        return ops.gather_rows(idx, cache, torch.empty((idx.numel(), cache.shape[1]), dtype=torch.float32, device=cache.device))
+
 
 class PositionalEncoding(nn.Module):
     """newsEncoders.py:806-828: the sinusoid table, a registered buffer (part of the state_dict)."""

@@ -895,29 +895,49 @@ def pool_match(hidden, affine2, x, B, H, cand=None, remaining=None, alpha=0.0, b
     return user, logits
 
 
-def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False):
+def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False, index=None,
+                  n=None):
     """``lime_grouped_match_f32``: the history-vs-candidate attention, the dot-product match and the remaining-lifetime weight for
     groups of pairs that share one refined history.  kp [G H, A], g [G H, D] per group; qp [P, A], cand [P, D], remaining [P] per
     pair; offsets int64 [G + 1] (device): the pairs of group i are rows offsets[i] .. offsets[i + 1] - 1 -> logits [P] (pairs outside
-    every group keep what ``torch.empty`` gave them).  1 <= H <= 128; A, D multiples of 4 up to 2048."""
+    every group keep what ``torch.empty`` gave them).  1 <= H <= 128; A, D multiples of 4 up to 2048.
+
+    ``index`` int32 [P] (``lime_grouped_match_indexed_f32``): qp and cand are tables and pair p reads row index[p] of both -- the first
+    ``n`` rows of each (default: all of qp's; cand has at least as many); the kernel clamps an index outside [0, n) into it.  A pair's
+    bits are those of the plain form on ``qp[index]``, ``cand[index]``."""
     lib = _lib.load()
     for t, name in ((kp, 'kp'), (g, 'g'), (qp, 'qp'), (cand, 'cand')):
         _mat(t, name)
         if not t.is_contiguous():
             raise ValueError('%s must be contiguous' % name)
-    A, D, P = kp.shape[1], g.shape[1], qp.shape[0]
+    A, D = kp.shape[1], g.shape[1]
     if H < 1 or kp.shape[0] % H or g.shape[0] != kp.shape[0]:
         raise ValueError('kp and g must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], g.shape[0], H))
     G = kp.shape[0] // H
-    if qp.shape[1] != A or cand.shape != (P, D):
-        raise ValueError('qp must be [P, %d] and cand [P, %d], got %s and %s' % (A, D, tuple(qp.shape), tuple(cand.shape)))
+    if index is None:
+        if n is not None:
+            raise ValueError('n is the table size of the indexed form: give index too')
+        P = qp.shape[0]
+        if qp.shape[1] != A or cand.shape != (P, D):
+            raise ValueError('qp must be [P, %d] and cand [P, %d], got %s and %s' % (A, D, tuple(qp.shape), tuple(cand.shape)))
+    else:
+        P = index.numel()
+        index = _vec(index, 'index', P, dtype=torch.int32)
+        n = qp.shape[0] if n is None else int(n)
+        if qp.shape[1] != A or cand.shape[1] != D or not 0 <= n <= min(qp.shape[0], cand.shape[0]):
+            raise ValueError('qp must be [>= n, %d] and cand [>= n, %d] with n = %d, got %s and %s' % (A, D, n, tuple(qp.shape), tuple(cand.shape)))
     _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
     if use_weight:
         remaining = _vec(remaining.contiguous(), 'remaining', P)
     logits = torch.empty((P,), dtype=torch.float32, device=qp.device)
-    check(lib.lime_grouped_match_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(remaining) if use_weight else None, _p(offsets), _p(logits),
-                                     G, P, H, A, D, scale, alpha, beta, int(use_weight), int(use_penalty), _stream()),
-          'lime_grouped_match_f32')
+    if index is None:
+        check(lib.lime_grouped_match_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(remaining) if use_weight else None, _p(offsets), _p(logits),
+                                         G, P, H, A, D, scale, alpha, beta, int(use_weight), int(use_penalty), _stream()),
+              'lime_grouped_match_f32')
+    else:
+        check(lib.lime_grouped_match_indexed_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(remaining) if use_weight else None, _p(offsets),
+                                                 _p(index), n, _p(logits), G, P, H, A, D, scale, alpha, beta, int(use_weight),
+                                                 int(use_penalty), _stream()), 'lime_grouped_match_indexed_f32')
     return logits
 
 

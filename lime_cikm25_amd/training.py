@@ -1026,7 +1026,11 @@ def content_flat(enc, title_text, title_mask, content_text, category, subCategor
 def news_flat(ne, title_text, title_mask, content_text, category, subCategory, freshness, lifetime, content_mask=None, pair_groups=None,
               title_entity=None):
     """LIME.forward (newsEncoders.py:140-161) on M flat news with autograd -> [M, 400].  content_mask: the body mask, read by CNE alone;
-    title_entity: the title's entity ids, read by KCNN alone."""
+    title_entity: the title's entity ids, read by KCNN alone.  A content encoder used as the news encoder itself (the baseline form,
+    model.py:41-62) is its own representation: freshness and lifetime are not read."""
+    if not hasattr(ne, 'base_news_encoder'):
+        return content_flat(ne, title_text, title_mask, content_text, category, subCategory, content_mask=content_mask,
+                            pair_groups=pair_groups, title_entity=title_entity)
     content = content_flat(ne.base_news_encoder, title_text, title_mask, content_text, category, subCategory, content_mask=content_mask,
                            pair_groups=pair_groups, title_entity=title_entity)
     return lime_tail(ne, content, freshness, lifetime)
@@ -1103,16 +1107,20 @@ def dead_parameters(model):
       * ``news_encoder.category_affine`` makes the topic vectors of the CROWN user encoder's candidate-aware attention
         (userEncoders.py:103-105) and nothing else: dead without that layer (``use_candidate_ware_clicked_news_attention`` off), and
         under ATT / MHSA, whose layer reads ``category_embedding`` rows alone (:470,482 / :546,554).
-      * ``use_residual_connection`` off: the layer returns agg * x (layers.py:84), its ``gate_proj`` and ``layernorm`` are unused."""
+      * ``use_residual_connection`` off: the layer returns agg * x (layers.py:84), its ``gate_proj`` and ``layernorm`` are unused.
+    The baseline form (the content encoder is ``news_encoder`` itself, model.py:41-62): the same never-used parameters without the
+    ``base_news_encoder.`` level, and ``news_encoder.category_affine`` is the content encoder's own layer, which its representation
+    reads whatever the user encoder is (CROWN: newsEncoders.py:340, NAML: :689) -- never dead."""
     from .userEncoders import CROWN, MHSA
     ue = model.user_encoder
     caa = getattr(ue, 'candidate_aware_attn', None)
+    plain = not hasattr(model.news_encoder, 'base_news_encoder')
     # prefixes of the names (LIME's ``category_affine``, not the content encoder's own ``base_news_encoder.category_affine``)
-    dead = ['news_encoder.base_news_encoder.affine.', 'news_encoder.base_news_encoder.ISAB.', 'news_encoder.base_news_encoder.category_predictor.',
-            'user_encoder.candidate_aware_attn.value_proj.']
+    enc = 'news_encoder.' if plain else 'news_encoder.base_news_encoder.'
+    dead = [enc + 'affine.', enc + 'ISAB.', enc + 'category_predictor.', 'user_encoder.candidate_aware_attn.value_proj.']
     if not isinstance(ue, MHSA):
         dead.append('user_encoder.affine.')
-    if not (isinstance(ue, CROWN) and caa is not None):
+    if not plain and not (isinstance(ue, CROWN) and caa is not None):
         dead.append('news_encoder.category_affine.')
     if caa is not None and not caa.use_residual_connection:
         dead += ['user_encoder.candidate_aware_attn.gate_proj.', 'user_encoder.candidate_aware_attn.layernorm.']

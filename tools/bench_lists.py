@@ -12,6 +12,13 @@ list with the most topics needs).  Prints one JSON line per (shape, user encoder
 profiles/recommend_lists.json).
 
     python tools/bench_lists.py --rounds 3
+
+``--news-encoder X`` measures a baseline model -- X as the news encoder itself, no LIME, under each of ``--user-encoders`` -- at the
+serving shape instead: ``recommend_lists`` on lime_grouped_match_indexed_f32 (the cache read in place, Q of every news once per call)
+alternated with the same model on the gather form (tools/bench_recommend.py, ``plain_forms``); the lines are appended to
+profiles/plain_recommend.json.
+
+    python tools/bench_lists.py --news-encoder CROWN --user-encoders CROWN --rounds 3
 """
 import argparse
 import json
@@ -26,6 +33,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from lime_cikm25_amd import DeviceBehaviors, DeviceCorpus, Model, make_config, ops, recommend, synth, util  # noqa: E402
 from bench_eval import make_dev_split  # noqa: E402
+from bench_recommend import plain_forms  # noqa: E402
 
 
 def say(*a):
@@ -73,7 +81,7 @@ def empty_slots(model, dc, cand_index, offsets, H, pairs_per_pass):
             'passes': len(shares), 'largest_slot_count': s_max, 'mean_distinct_topics_per_list': round(float(nd.mean()), 2)}
 
 
-def serving(model, dc, cache, cfg, args, rng, n_news):
+def serving(model, dc, cache, cfg, args, rng, n_news, plain=False):
     U, C, k, H = args.users, args.candidates, args.k, cfg.max_history_num
     P = U * C
     n_hist = rng.integers(5, H + 1, size=U)
@@ -89,6 +97,10 @@ def serving(model, dc, cache, cfg, args, rng, n_news):
     list_args = dict(news_cache=cache, corpus=dc, hist_index=t(hist), hist_mask=t(mask), user_freshness=t(ufr), user_lifetime=t(ult),
                      cand_offsets=t(offsets), cand_index=t(cands), cand_freshness=t(cfr), cand_lifetime=t(clt))
     n_src = min(P, H + cfg.batch_size)
+    if plain:
+        return plain_forms(model, list_args, k, n_src, args.rounds, dict(
+            bench='recommend_lists', shape='serving', model=model.model_name, users=U, candidates_per_user=C, pairs=P, news=n_news, H=H, k=k),
+            entry='recommend_lists')
     user = np.repeat(np.arange(U), C)
     beh = DeviceBehaviors(dc, user, hist[user], mask[user], ufr[user], ult[user], cands.reshape(P, 1), cfr.reshape(P, 1), clt.reshape(P, 1),
                           eval_shape=True)
@@ -156,13 +168,20 @@ def main():
     ap.add_argument('--user-encoders', nargs='*', default=['CROWN', 'ATT'])
     ap.add_argument('--shapes', nargs='*', default=['serving', 'dev'])
     ap.add_argument('--seed', type=int, default=1)
-    ap.add_argument('--json-out', default=os.path.join(ROOT, 'profiles', 'recommend_lists.json'))
+    ap.add_argument('--news-encoder', default='LIME', help="'LIME' (default) or a baseline: CROWN, CNN, NAML, MHSA, KCNN (serving shape)")
+    ap.add_argument('--json-out', default=None, help='default: profiles/recommend_lists.json (LIME, rewritten), '
+                                                     'profiles/plain_recommend.json (a baseline, appended to)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_lists.py measures on the GPU: there is no CPU path'
+    plain = args.news_encoder != 'LIME'
+    if plain:
+        args.shapes = ['serving']
+    if args.json_out is None:
+        args.json_out = os.path.join(ROOT, 'profiles', 'plain_recommend.json' if plain else 'recommend_lists.json')
 
     lines = []
     for user_encoder in args.user_encoders:
-        cfg = make_config(user_encoder=user_encoder, vocabulary_size=50000)
+        cfg = make_config(news_encoder=args.news_encoder, user_encoder=user_encoder, vocabulary_size=50000)
         corpus = synth.synth_corpus(cfg, n_news=args.news, n_train=1, n_dev=1, seed=args.seed)
         # MIND's subcategories each sit under one category: about 270 topics in all (independent draws would give 18 x 270)
         corpus.news_category[1:] = 1 + corpus.news_subCategory[1:] % (cfg.category_num - 1)
@@ -174,7 +193,8 @@ def main():
         cache = model.build_news_cache(dc)
         rng = np.random.default_rng(args.seed)
         for shape in args.shapes:
-            line = serving(model, dc, cache, cfg, args, rng, args.news) if shape == 'serving' else dev_pass(model, dc, cfg, args, args.news)
+            line = (serving(model, dc, cache, cfg, args, rng, args.news, plain) if shape == 'serving' else
+                    dev_pass(model, dc, cfg, args, args.news))
             line.update(user_encoder=user_encoder, device=torch.cuda.get_device_name(0))
             say(line)
             lines.append(json.dumps(line))
@@ -184,7 +204,7 @@ def main():
     print('\n'.join(lines))
     if args.json_out:
         os.makedirs(os.path.dirname(os.path.abspath(args.json_out)), exist_ok=True)
-        with open(args.json_out, 'w') as f:
+        with open(args.json_out, 'a' if plain else 'w') as f:
             f.write('\n'.join(lines) + '\n')
 
 

@@ -7,6 +7,13 @@ Model.score_behaviors over the (user, candidate) pairs written out as rows, then
 compare.  Device-event medians.  Prints one JSON line per pool and writes them to ``--json-out`` (default profiles/recommend.json).
 
     python tools/bench_recommend.py --rounds 5
+
+``--news-encoder X`` (with ``--user-encoder Y``) measures a baseline model -- X as the news encoder itself, no LIME -- instead: its
+candidates depend on the news alone, and Model.recommend on lime_grouped_match_indexed_f32 (the pool's rows and their Q once per call,
+read in place) is alternated with the same model on the gather form (LIME_INDEXED_MATCH=0: one materialised row and one Q row per pair,
+the kernel LIME models take).  One JSON line per pool, appended to profiles/plain_recommend.json.
+
+    python tools/bench_recommend.py --news-encoder CROWN --user-encoder CROWN --rounds 5
 """
 import argparse
 import json
@@ -19,6 +26,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from lime_cikm25_amd import DeviceBehaviors, DeviceCorpus, Model, make_config, synth  # noqa: E402
+from lime_cikm25_amd import model as model_module  # noqa: E402
 
 
 def say(*a):
@@ -34,6 +42,43 @@ def event_ms(fn):
     return e0.elapsed_time(e1), out
 
 
+def plain_forms(model, call_args, k, n_src, rounds, head, entry='recommend'):
+    """A baseline model's ``entry`` on the indexed match and on the gather form, alternated after warm-up -> the result line."""
+    def form(indexed):
+        model_module.INDEXED_MATCH = indexed
+        try:
+            return getattr(model, entry)(**call_args, k=k, n_src=n_src)
+        finally:
+            model_module.INDEXED_MATCH = True
+
+    for _ in range(2):
+        form(True)
+        form(False)
+    torch.cuda.synchronize()
+    ms, pos = {True: [], False: []}, {}
+    for _ in range(rounds):
+        for indexed in (True, False):
+            dt, out = event_ms(lambda: form(indexed))
+            ms[indexed].append(dt)
+            pos[indexed] = out[0]
+    agree = float((pos[True] == pos[False]).float().mean())
+    peak = {}
+    for indexed in (True, False):                                          # the call's own peak above what is resident
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        form(indexed)
+        torch.cuda.synchronize()
+        peak[indexed] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+    stat = lambda v: {'median': round(statistics.median(v), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
+    line = dict(head, rounds=rounds, indexed_ms=stat(ms[True]), gather_ms=stat(ms[False]),
+                gather_over_indexed=round(statistics.median(ms[False]) / statistics.median(ms[True]), 3),
+                indexed_peak_mib=round(peak[True], 1), gather_peak_mib=round(peak[False], 1),
+                same_positions_fraction=round(agree, 4), device=torch.cuda.get_device_name(0))
+    say(line)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--users', type=int, default=32)
@@ -43,11 +88,17 @@ def main():
     ap.add_argument('--old-pairs', type=int, default=131072, help='pairs the score_behaviors form runs over, at the most')
     ap.add_argument('--old-rows', type=int, default=16384, help='rows per score_behaviors call')
     ap.add_argument('--seed', type=int, default=1)
-    ap.add_argument('--json-out', default=os.path.join(ROOT, 'profiles', 'recommend.json'))
+    ap.add_argument('--news-encoder', default='LIME', help="'LIME' (default) or a baseline: CROWN, CNN, NAML, MHSA, KCNN")
+    ap.add_argument('--user-encoder', default='CROWN')
+    ap.add_argument('--json-out', default=None, help='default: profiles/recommend.json (LIME, rewritten), profiles/plain_recommend.json '
+                                                     '(a baseline, appended to)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_recommend.py measures on the GPU: there is no CPU path'
+    plain = args.news_encoder != 'LIME'
+    if args.json_out is None:
+        args.json_out = os.path.join(ROOT, 'profiles', 'plain_recommend.json' if plain else 'recommend.json')
 
-    cfg = make_config()
+    cfg = make_config(news_encoder=args.news_encoder, user_encoder=args.user_encoder)
     U, H, k = args.users, cfg.max_history_num, args.k
     n_news = max(args.pools) + 1
     corpus = synth.synth_corpus(cfg, n_news=n_news, n_train=1, n_dev=1, seed=args.seed)
@@ -78,6 +129,10 @@ def main():
                          cand_index=t(pool), cand_freshness=t(cfr), cand_lifetime=t(clt))
         n_src = min(U * C, H + cfg.batch_size)
         topics = len(set(zip(corpus.news_category[pool].tolist(), corpus.news_subCategory[pool].tolist())))
+        if plain:
+            lines.append(json.dumps(plain_forms(model, pool_args, k, n_src, args.rounds, dict(
+                bench='recommend', model=model.model_name, users=U, H=H, pool=C, topics_in_pool=topics, k=k, pairs=U * C))))
+            continue
         # the second form: whole users, as many as --old-pairs allows
         u_old = max(1, min(U, args.old_pairs // C))
         R = u_old * C
@@ -123,7 +178,7 @@ def main():
     print('\n'.join(lines))
     if args.json_out:
         os.makedirs(os.path.dirname(os.path.abspath(args.json_out)), exist_ok=True)
-        with open(args.json_out, 'w') as f:
+        with open(args.json_out, 'a' if plain else 'w') as f:
             f.write('\n'.join(lines) + '\n')
 
 
