@@ -790,7 +790,8 @@ int lime_relu_bwd_f32(float* dh, int64_t lddh, const float* h, int64_t ldh, int6
  * dout) and lime_token_attention_bwd_workspace(n_seq, S, n_head) floats: the row statistics and one dq slab per key block behind the
  * first -- the key blocks' shares of dq are stored (no atomics) and summed in block order, so the result is bitwise reproducible.  dropout_p > 0: the forward was lime_token_attention_dropout_f32 with the same (dropout_p, seed, site).
  * key_mask (uint8 [n_seq, S], 0 = masked, or NULL; S <= 128): the masked attention of layers.MultiHeadAttention
- * (layers.py:227-232) -- masked scores are constants (-1e9) and receive no gradient. */
+ * (layers.py:227-232) -- masked scores are constants (-1e9) and receive no gradient.
+ * Which kernels a call runs: DESIGN.md section 5.5 has the routing table, lime_token_attention_bwd_plan_f32 below returns a call's row. */
 int64_t lime_token_attention_bwd_workspace(int32_t n_seq, int32_t S, int32_t n_head);
 /* the row-statistics part of it (lse and delta per (token, head)): what lime_token_attention_dropout_f32 needs for S > 128 */
 int64_t lime_token_attention_stats_workspace(int32_t n_seq, int32_t S, int32_t n_head);
@@ -818,6 +819,59 @@ int lime_token_attention_bwd_lse_f32(const float* q, const float* k, const float
                                      const float* lse, const float* dout, int64_t ldo, float* dq, float* dk, float* dv, int64_t ld_dqkv,
                                      int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale,
                                      float* workspace, int64_t workspace_floats, void* stream);
+
+/* The arguments of the two fp32 backward entries as one block; `entry` says which of them is speaking (the lse entry: dropout_p = 0,
+ * key_mask = NULL; the plain entry does not look at lse). */
+enum { LIME_BWD_ATTN_ENTRY_PLAIN = 0, LIME_BWD_ATTN_ENTRY_LSE = 1 };
+typedef struct {
+    const float* q;
+    const float* k;
+    const float* v;
+    int64_t ld_qkv;
+    const float* out;
+    int64_t ld_out;
+    const float* lse;
+    const float* dout;
+    int64_t ldo;
+    float* dq;
+    float* dk;
+    float* dv;
+    int64_t ld_dqkv;
+    float* workspace;
+    int64_t workspace_floats;
+    const uint8_t* key_mask;
+    uint64_t dropout_seed;
+    float dropout_p;
+    uint32_t dropout_site;
+    int32_t n_seq, S, n_head, head_dim, head_stride;
+    float scale;
+    int32_t entry;
+    int32_t reserved;
+} lime_token_attention_bwd_args;
+
+/* What lime_token_attention_bwd_f32 / _bwd_lse_f32 would run for an argument block, without running it: the backward's routing
+ * decision (csrc/token_attn_f32.hip, lime_attn_bwd_route; DESIGN.md section 5.5 has the table) as data, under the contract of
+ * lime_token_attention_plan_f32 -- a pure function of the block and the lime_set_split_gemm() setting, no launch, no pointer read
+ * through.  Returns the entry's refusal (same status, same lime_last_error_string()) where it launches nothing, else LIME_OK and
+ *   family      LIME_BWD_ATTN_ONE_PASS token_attn_bwd_kernel<32 | 64 | 128> (exact-fp32 MFMA, S <= 128), _SP attn_bwd_sp_kernel<FULL>
+ *               (split product, 64 < S <= 128), _LONG attn_bwd_long_kernel / _LONG_SP attn_bwd_long_sp_kernel (key blocks, S > 128),
+ *               _WIDE wide_bwd_q_kernel<NK> + wide_bwd_kv_kernel<NK> (head_dim > 32); LIME_BWD_ATTN_NONE for n_seq == 0
+ *   stats_pass  the launch in front of a blocked kernel: LIME_BWD_ATTN_PASS_NONE, _STATS_FP32 (attn_stats_kernel<false>), _STATS_SPLIT
+ *               (attn_stats_kernel<true>) or _DELTA (attn_delta_kernel: the lse entry)
+ *   n_launches  0 to 3 (a blocked kernel is followed by attn_dq_reduce_kernel)
+ *   name        the n_launches instantiations in launch order, as rocprofv3 prints them */
+enum { LIME_BWD_ATTN_NONE = 0, LIME_BWD_ATTN_ONE_PASS = 1, LIME_BWD_ATTN_SP = 2, LIME_BWD_ATTN_LONG = 3, LIME_BWD_ATTN_LONG_SP = 4,
+       LIME_BWD_ATTN_WIDE = 5 };
+enum { LIME_BWD_ATTN_PASS_NONE = 0, LIME_BWD_ATTN_PASS_STATS_FP32 = 1, LIME_BWD_ATTN_PASS_STATS_SPLIT = 2, LIME_BWD_ATTN_PASS_DELTA = 3 };
+typedef struct {
+    int32_t family;
+    int32_t stats_pass;
+    int32_t n_launches;
+    int32_t reserved;
+    char name[3][64];
+} lime_token_attention_bwd_plan;
+
+int lime_token_attention_bwd_plan_f32(const lime_token_attention_bwd_args* args, lime_token_attention_bwd_plan* out);
 
 /* Backward of lime_additive_pool_f32 (layers.Attention over a title's tokens, layers.py:285-300 / newsEncoders.py:591-592; the MHSA content
  * encoder in training): dhidden [n_seq * S, A], dx [n_seq * S, D] and da2_part [n_seq, A], the per-sequence partial rows of the

@@ -39,6 +39,8 @@ LinearPlan = STRUCTS['lime_linear_plan']
 LinearBf16Args = STRUCTS['lime_linear_bf16_args']
 TokenAttentionArgs = STRUCTS['lime_token_attention_args']
 TokenAttentionPlan = STRUCTS['lime_token_attention_plan']
+TokenAttentionBwdArgs = STRUCTS['lime_token_attention_bwd_args']
+TokenAttentionBwdPlan = STRUCTS['lime_token_attention_bwd_plan']
 FfnBf16Args = STRUCTS['lime_ffn_bf16_args']
 FfnSpArgs = STRUCTS['lime_ffn_sp_args']
 OprojSpArgs = STRUCTS['lime_oproj_sp_args']
@@ -61,6 +63,11 @@ ATTN_FORM = {f: CONSTANTS['LIME_ATTN_FORM_' + f.upper()] for f in ('plain', 'cou
 ATTN_FAMILY = {CONSTANTS['LIME_ATTN_' + f.upper()]: f for f in ('sp', 'sp_long', 'sp_vocab', 'mfma', 'wide', 'dropout', 'dropout_long')}
 ATTN_FAMILY[CONSTANTS['LIME_ATTN_NONE']] = None
 ATTN_STATS = {CONSTANTS['LIME_ATTN_STATS_NONE']: None, CONSTANTS['LIME_ATTN_STATS_FP32']: 'fp32', CONSTANTS['LIME_ATTN_STATS_SPLIT']: 'split'}
+BWD_ATTN_ENTRY = {e: CONSTANTS['LIME_BWD_ATTN_ENTRY_' + e.upper()] for e in ('plain', 'lse')}
+BWD_ATTN_FAMILY = {CONSTANTS['LIME_BWD_ATTN_' + f.upper()]: f for f in ('one_pass', 'sp', 'long', 'long_sp', 'wide')}
+BWD_ATTN_FAMILY[CONSTANTS['LIME_BWD_ATTN_NONE']] = None
+BWD_ATTN_PASS = {CONSTANTS['LIME_BWD_ATTN_PASS_NONE']: None, CONSTANTS['LIME_BWD_ATTN_PASS_STATS_FP32']: 'fp32',
+                 CONSTANTS['LIME_BWD_ATTN_PASS_STATS_SPLIT']: 'split', CONSTANTS['LIME_BWD_ATTN_PASS_DELTA']: 'delta'}
 LINEAR_PASS_RELU_BWD = CONSTANTS['LIME_LINEAR_PASS_RELU_BWD']
 LINEAR_PASS_DROPOUT = CONSTANTS['LIME_LINEAR_PASS_DROPOUT']
 

@@ -112,15 +112,3 @@ __attribute__((visibility("hidden")))
 int lime_reduce_partials(const float* ws, long split_stride, int splits, long ldw, float* out, long ldo, int rows, int cols,
                          int accumulate, hipStream_t s, float* extra = nullptr);
 int lime_split_mode();                                                   // gemm_sp_f32.hip: the lime_set_split_gemm() setting
-// token_attn_wide_f32.hip: the backward at 32 < head_dim <= 128 (head_dim % 4 == 0, 16-byte aligned operands) on the fp32 MFMA; it checks
-// its own limits and names `entry` in its messages, and recomputes the row statistics (workspace:
-// lime_token_attention_bwd_workspace_wide floats).  The forward: token_attn.h.
-int lime_token_attention_wide_bwd(const char* entry, const float* q, const float* k, const float* v, long ld, const float* dout, long ldo,
-                                  float* dq, float* dk, float* dv, long ldd, int n_seq, int S, int n_head, int hd, int hs, float scale,
-                                  float* workspace, long workspace_floats, const LimeDropout& drop, const unsigned char* key_mask,
-                                  hipStream_t s);
-// token_attn_bwd_sp_f32.hip: the one-pass attention backward (64 < S <= 128, no key mask) with all its products on the split product;
-// LIME_NOT_APPLICABLE: not taken, the caller goes on to its other kernels
-int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, long ld, const float* dout, long ldo, float* dq, float* dk,
-                                float* dv, long ldd, int n_seq, int S, int n_head, int head_dim, int head_stride, float scale,
-                                const LimeDropout& drop, hipStream_t s);

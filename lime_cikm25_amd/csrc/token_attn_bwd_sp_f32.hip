@@ -26,6 +26,7 @@
 #include "dev_helpers.h"
 #include "split_mfma.h"
 #include "dropout.h"
+#include "token_attn.h"
 
 using namespace lime_dev;
 
@@ -282,22 +283,19 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_kernel(const BwdSpP p) {
 
 }  // namespace
 
-// LIME_NOT_APPLICABLE: the caller takes token_attn_bwd_kernel (shapes / alignments outside this build)
-int lime_token_attention_bwd_sp(const float* q, const float* k, const float* v, long ld, const float* dout, long ldo, float* dq, float* dk,
-                                float* dv, long ldd, int n_seq, int S, int n_head, int head_dim, int head_stride, float scale,
-                                const LimeDropout& drop, hipStream_t s) {
-    if (!(S > 64 && S <= SPB && S % 4 == 0 && head_stride == 32 && head_dim <= 32 && head_dim % 2 == 0)) return LIME_NOT_APPLICABLE;
-    if (ld % 4 != 0 || ldd % 4 != 0 || ldo % 2 != 0) return LIME_NOT_APPLICABLE;
-    if (((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15) != 0 || (((uintptr_t)dout) & 7) != 0)
-        return LIME_NOT_APPLICABLE;
+// The one-pass backward with all its products on the split product (token_attn_f32.hip chose r and made the checks: 64 < S <= 128,
+// S % 4 == 0, no key mask, even heads 32 columns apart, 16-byte rows, 8-byte dout pairs): r.n is FULL
+int lime_attn_bwd_sp_launch(const LimeAttnBwdRoute& r, const lime_token_attention_bwd_args& a, hipStream_t s) {
     static_assert(LDS_BYTES <= 163840, "LDS budget");
     static int reserved[2] = {0, 0};              // per instantiation: S < SPB, S == SPB
-    const void* const kernel = S == SPB ? (const void*)attn_bwd_sp_kernel<true> : (const void*)attn_bwd_sp_kernel<false>;
-    if (const int st = lime_reserve_lds(kernel, LDS_BYTES, reserved[S == SPB], "lime_token_attention_bwd_f32")) return st;
-    const long n_prob = (long)n_seq * n_head;
-    BwdSpP p{q, k, v, ld, dout, ldo, dq, dk, dv, ldd, n_seq, S, n_head, head_dim, scale, drop};
+    const bool full = r.n != 0;
+    const void* const kernel = full ? (const void*)attn_bwd_sp_kernel<true> : (const void*)attn_bwd_sp_kernel<false>;
+    if (const int st = lime_reserve_lds(kernel, LDS_BYTES, reserved[full], "lime_token_attention_bwd_f32")) return st;
+    const long n_prob = (long)a.n_seq * a.n_head;
+    BwdSpP p{a.q, a.k, a.v, (long)a.ld_qkv, a.dout, (long)a.ldo, a.dq, a.dk, a.dv, (long)a.ld_dqkv, a.n_seq, a.S, a.n_head, a.head_dim, a.scale,
+             lime_attn_bwd_dropout(a)};
     const unsigned grid = (unsigned)lime_persistent_grid(n_prob);                // persistent: one workgroup per CU
-    if (S == SPB) attn_bwd_sp_kernel<true><<<grid, 512, LDS_BYTES, s>>>(p);
+    if (full) attn_bwd_sp_kernel<true><<<grid, 512, LDS_BYTES, s>>>(p);
     else attn_bwd_sp_kernel<false><<<grid, 512, LDS_BYTES, s>>>(p);
     return lime_check_launch("attn_bwd_sp_kernel");
 }

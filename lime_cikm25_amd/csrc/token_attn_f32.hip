@@ -733,6 +733,138 @@ extern "C" int lime_token_attention_dropout_f32(const float* q, const float* k, 
     return attention_forward(a, stream);
 }
 
+// ---- The fp32 backward: its two entries and the one pure route that makes their checks and chooses the kernels (DESIGN.md section
+// 5.5), as above.  lime_token_attention_bwd_plan_f32 returns the same decision as data.
+
+int lime_attn_bwd_route(const lime_token_attention_bwd_args& a, int split_mode, LimeAttnBwdRoute* r) {
+    *r = LimeAttnBwdRoute{LIME_BWD_ATTN_NONE, 0, LIME_BWD_ATTN_PASS_NONE, false};
+    const bool lse = a.entry == LIME_BWD_ATTN_ENTRY_LSE, split = (split_mode & 1) != 0;
+    const int S = a.S, hd = a.head_dim, hs = a.head_stride;
+    const char* const e = "lime_token_attention_bwd_f32";      // the lse entry speaks under this name too, but for its own two messages
+
+    // ---- the checks both entries make, in the order and the words they have always used ----
+    if (lse) LIME_REQUIRE(a.lse != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_lse_f32: lse is NULL");
+    LIME_REQUIRE(a.q && a.k && a.v && a.dout && a.dq && a.dk && a.dv, LIME_ERR_BAD_ARG, "%s: null pointer", e);
+    LIME_REQUIRE(a.dropout_p >= 0.f && a.dropout_p < 1.f, LIME_ERR_BAD_ARG, "%s: dropout_p outside [0, 1)", e);
+    LIME_REQUIRE(a.n_seq >= 0 && S > 0 && a.n_head > 0 && hd > 0, LIME_ERR_BAD_ARG, "%s: bad dimensions", e);
+
+    if (hd > 32) {               // wide heads: one family at every S, which recomputes the statistics (out / lse unused)
+        if (const int st = lime_attn_wide_limits(e, S, a.n_head, hd, hs, a.n_seq)) return st;
+        LIME_REQUIRE(a.ld_qkv >= (int64_t)a.n_head * hs && a.ld_dqkv >= (int64_t)a.n_head * hs && a.ldo >= (int64_t)a.n_head * hd,
+                     LIME_ERR_BAD_ARG, "%s: leading dimension smaller than the row", e);
+        LIME_REQUIRE(lime_al16(a.q, a.ld_qkv) && lime_al16(a.k, a.ld_qkv) && lime_al16(a.v, a.ld_qkv) && lime_al16(a.dout, a.ldo) &&
+                     lime_al16(a.dq, a.ld_dqkv) && lime_al16(a.dk, a.ld_dqkv) && lime_al16(a.dv, a.ld_dqkv), LIME_ERR_UNSUPPORTED,
+                     "%s: head_dim > 32 needs 16-byte aligned q / k / v / dout / dq / dk / dv and leading dimensions that are multiples of 4", e);
+        if (a.n_seq == 0) return LIME_OK;
+        LIME_REQUIRE(a.workspace != nullptr && a.workspace_floats >= lime_token_attention_bwd_workspace_wide(a.n_seq, S, a.n_head, hd),
+                     LIME_ERR_BAD_ARG, "%s: head_dim > 32 needs lime_token_attention_bwd_workspace_wide() floats of workspace", e);
+        *r = LimeAttnBwdRoute{LIME_BWD_ATTN_WIDE, (hd + 15) / 16, LIME_BWD_ATTN_PASS_NONE, false};
+        return LIME_OK;
+    }
+
+    LIME_REQUIRE(S <= 512 && hs >= hd && hs <= 32, LIME_ERR_UNSUPPORTED,
+                 "%s: needs S <= 512 and head_dim <= head_stride <= 32 (S=%d head_dim=%d head_stride=%d)", e, S, hd, hs);
+    LIME_REQUIRE(a.ld_qkv >= (int64_t)a.n_head * hs && a.ld_dqkv >= (int64_t)a.n_head * hs && a.ldo >= (int64_t)a.n_head * hd,
+                 LIME_ERR_BAD_ARG, "%s: leading dimension smaller than the row", e);
+    if (a.n_seq == 0) return LIME_OK;
+
+    // ---- the route (head_dim <= 32) ----
+    if (S <= 128) {
+        // One pass per (sequence, head).  All five products on the bf16 matrix cores as split products: 64 < S <= 128 in whole groups of four
+        // rows, no key mask, even heads 32 columns apart, 16-byte rows of q / k / v / dq / dk / dv, 8-byte pairs of dout
+        const bool sp = split && a.key_mask == nullptr && S > 64 && S % 4 == 0 && hs == 32 && hd % 2 == 0 && a.ld_qkv % 4 == 0 &&
+                        a.ld_dqkv % 4 == 0 && a.ldo % 2 == 0 && ((uintptr_t)a.dout % 8) == 0 &&
+                        (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) % 16) == 0;
+        if (sp) *r = LimeAttnBwdRoute{LIME_BWD_ATTN_SP, S == 128, LIME_BWD_ATTN_PASS_NONE, false};
+        else *r = LimeAttnBwdRoute{LIME_BWD_ATTN_ONE_PASS, S <= 32 ? 32 : (S <= 64 ? 64 : 128), LIME_BWD_ATTN_PASS_NONE, false};
+        return LIME_OK;
+    }
+    // Key blocks: the row statistics first (behind a forward that kept its log-sum-exp only delta = dO . O is left), then the blocked
+    // kernel, whose key blocks' shares of dq attn_dq_reduce_kernel sums (S > 128: there are always at least two blocks)
+    LIME_REQUIRE(a.key_mask == nullptr, LIME_ERR_UNSUPPORTED, "%s: a key mask needs S <= 128", e);
+    LIME_REQUIRE(a.out && a.ld_out >= (int64_t)a.n_head * hd, LIME_ERR_BAD_ARG, "%s: S > 128 needs the forward output `out` (delta = dO . O)", e);
+    const LimeAttnBwdCarve w = lime_attn_bwd_carve(a.n_seq, S, a.n_head);
+    LIME_REQUIRE(a.workspace && a.workspace_floats >= w.total, LIME_ERR_BAD_ARG,
+                 "%s: S > 128 needs lime_token_attention_bwd_workspace() floats of workspace", e);
+    LIME_REQUIRE((long)a.n_seq * a.n_head * w.n_blk < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "%s: too many blocks", e);
+    if (lse)
+        LIME_REQUIRE(a.n_head <= 64 && a.n_head * hd <= 1024, LIME_ERR_UNSUPPORTED,
+                     "lime_token_attention_bwd_lse_f32: n_head > 64 or n_head * head_dim > 1024");
+    *r = LimeAttnBwdRoute{split ? LIME_BWD_ATTN_LONG_SP : LIME_BWD_ATTN_LONG, 0,
+                          lse ? LIME_BWD_ATTN_PASS_DELTA : (split ? LIME_BWD_ATTN_PASS_STATS_SPLIT : LIME_BWD_ATTN_PASS_STATS_FP32), true};
+    return LIME_OK;
+}
+
+namespace {
+
+// the route's launches in order, as rocprofv3 prints them; returns how many
+int bwd_route_names(const LimeAttnBwdRoute& r, char (*name)[64]) {
+    static const char* const pass[] = {nullptr, "attn_stats_kernel<false>", "attn_stats_kernel<true>", "attn_delta_kernel"};
+    int n = 0;
+    if (r.pass != LIME_BWD_ATTN_PASS_NONE) snprintf(name[n++], 64, "%s", pass[r.pass]);
+    switch (r.family) {
+        case LIME_BWD_ATTN_ONE_PASS: snprintf(name[n++], 64, "token_attn_bwd_kernel<%d>", r.n); break;
+        case LIME_BWD_ATTN_SP: snprintf(name[n++], 64, "attn_bwd_sp_kernel<%s>", r.n ? "true" : "false"); break;
+        case LIME_BWD_ATTN_LONG: snprintf(name[n++], 64, "attn_bwd_long_kernel"); break;
+        case LIME_BWD_ATTN_LONG_SP: snprintf(name[n++], 64, "attn_bwd_long_sp_kernel"); break;
+        case LIME_BWD_ATTN_WIDE:
+            snprintf(name[n++], 64, "wide_bwd_q_kernel<%d>", r.n);
+            snprintf(name[n++], 64, "wide_bwd_kv_kernel<%d>", r.n);
+            break;
+    }
+    if (r.reduce) snprintf(name[n++], 64, "attn_dq_reduce_kernel");
+    return n;
+}
+
+int attention_backward(const lime_token_attention_bwd_args& a, void* stream) {
+    LimeAttnBwdRoute r;
+    const int st = lime_attn_bwd_route(a, lime_split_mode(), &r);
+    if (st != LIME_OK) return st;
+    switch (r.family) {
+        case LIME_BWD_ATTN_NONE: return LIME_OK;
+        case LIME_BWD_ATTN_SP: return lime_attn_bwd_sp_launch(r, a, (hipStream_t)stream);
+        case LIME_BWD_ATTN_WIDE: return lime_attn_bwd_wide_launch(r, a, (hipStream_t)stream);
+        default: return lime_attn_bwd_launch(r, a, (hipStream_t)stream);
+    }
+}
+
+}  // namespace
+
+extern "C" int lime_token_attention_bwd_plan_f32(const lime_token_attention_bwd_args* args, lime_token_attention_bwd_plan* out) {
+    LIME_REQUIRE(args != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_plan_f32: args is NULL");
+    LIME_REQUIRE(out != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_plan_f32: out is NULL");
+    LIME_REQUIRE(args->entry == LIME_BWD_ATTN_ENTRY_PLAIN || args->entry == LIME_BWD_ATTN_ENTRY_LSE, LIME_ERR_BAD_ARG,
+                 "lime_token_attention_bwd_plan_f32: entry %d", args->entry);
+    *out = lime_token_attention_bwd_plan{};
+    LimeAttnBwdRoute r;
+    const int st = lime_attn_bwd_route(*args, lime_split_mode(), &r);
+    if (st != LIME_OK) return st;
+    out->family = r.family;
+    out->stats_pass = r.pass;
+    out->n_launches = bwd_route_names(r, out->name);
+    return LIME_OK;
+}
+
+extern "C" int lime_token_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
+                                            int64_t ld_out, const float* dout, int64_t ldo, float* dq, float* dk, float* dv,
+                                            int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
+                                            int32_t head_stride, float scale, float* workspace, int64_t workspace_floats,
+                                            float dropout_p, uint64_t seed, uint32_t site, const uint8_t* key_mask, void* stream) {
+    const lime_token_attention_bwd_args a = {q, k, v, ld_qkv, out, ld_out, nullptr, dout, ldo, dq, dk, dv, ld_dqkv, workspace, workspace_floats,
+                                             key_mask, seed, dropout_p, site, n_seq, S, n_head, head_dim, head_stride, scale,
+                                             LIME_BWD_ATTN_ENTRY_PLAIN, 0};
+    return attention_backward(a, stream);
+}
+
+extern "C" int lime_token_attention_bwd_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
+                                                int64_t ld_out, const float* lse, const float* dout, int64_t ldo, float* dq, float* dk,
+                                                float* dv, int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
+                                                int32_t head_stride, float scale, float* workspace, int64_t workspace_floats, void* stream) {
+    const lime_token_attention_bwd_args a = {q, k, v, ld_qkv, out, ld_out, lse, dout, ldo, dq, dk, dv, ld_dqkv, workspace, workspace_floats,
+                                             nullptr, 0, 0.f, 0, n_seq, S, n_head, head_dim, head_stride, scale, LIME_BWD_ATTN_ENTRY_LSE, 0};
+    return attention_backward(a, stream);
+}
+
 int lime_token_attention_bf16_mfma(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t ld_qkv, uint16_t* out, int64_t ldo,
                                    int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, float scale, int32_t out_pad,
                                    hipStream_t s);          // token_attn_bf16.hip

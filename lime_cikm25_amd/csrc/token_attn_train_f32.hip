@@ -1,8 +1,9 @@
-// The token attention that only training runs: lime_token_attention_bwd_f32 / _bwd_lse_f32 (dQ / dK / dV of softmax(scale Q K^T) V per
-// (sequence, head), probabilities recomputed) and lime_token_attention_dropout_f32 (the forward with probability dropout).
+// The token attention that only training runs: the fp32 kernels of lime_token_attention_bwd_f32 / _bwd_lse_f32 (dQ / dK / dV of
+// softmax(scale Q K^T) V per (sequence, head), probabilities recomputed) and of lime_token_attention_dropout_f32 (the forward with
+// probability dropout).  The entries, their checks and the choice among these kernels: token_attn_f32.hip (one pure route per direction).
 //
 //   S <= 128   token_attn_bwd_kernel<SP>, token_attn_fwd_dropout_kernel<SP>: one pass, fp32 MFMA (64 < S <= 128 without a key mask: the
-//              split-product backward of token_attn_bwd_sp_f32.hip, and the forward of token_attn_sp_f32.hip, are tried first)
+//              split-product backward of token_attn_bwd_sp_f32.hip, and the forward of token_attn_sp_f32.hip, come first)
 //   S > 128    attn_stats_kernel<SPX> (row statistics: serves the forward with dropout AND the backward), or attn_delta_kernel behind a
 //              forward that kept its log-sum-exp; then attn_fwd_long_dropout_kernel, or attn_bwd_long_kernel (fp32 MFMA) /
 //              attn_bwd_long_sp_kernel (split product, lime_set_split_gemm) + attn_dq_reduce_kernel over the key blocks' dQ slabs
@@ -411,8 +412,9 @@ __global__ __launch_bounds__(512, 2) void token_attn_fwd_dropout_kernel(const fl
 // Sequences longer than 128 tokens (BASELINE config 4: body length 512): the same mathematics in 128 x 128 blocks.
 //   attn_stats_kernel      per query row: lse = log2 sum_j exp(scale q.k_j) over ALL keys, delta = dO . O (O: the forward output)
 //   attn_bwd_long_kernel   one workgroup per (sequence, head, key block): P = exp(scale S - lse) needs no row reduction any
-//                          more; dK / dV of the block accumulate in registers over the query blocks, the dQ contributions of
-//                          the key blocks are added with float atomics (dq is zeroed first)
+//                          more; dK / dV of the block accumulate in registers over the query blocks; key block 0 writes its dQ
+//                          share to dq, every other block to a slab of its own
+//   attn_dq_reduce_kernel  adds the slabs to dq in block order (no atomics: bitwise reproducible)
 // Eight waves, 16 rows each, as in token_attn_bwd_kernel.
 // ---------------------------------------------------------------------------------------------------
 constexpr int LB = 128;          // block edge
@@ -964,20 +966,19 @@ __global__ __launch_bounds__(256) void attn_dq_reduce_kernel(float* __restrict__
 }
 
 template <int SP>
-int launch_attn_bwd(const float* q, const float* k, const float* v, long ld, const float* dout, long ldo, float* dq, float* dk,
-                    float* dv, long ldd, int n_seq, int S, int n_head, int head_dim, int head_stride, float scale,
-                    const LimeDropout& drop, const unsigned char* key_mask, hipStream_t s) {
+int launch_attn_bwd(const lime_token_attention_bwd_args& a, hipStream_t s) {
     constexpr int PPW = 8 / (SP / 16);
     constexpr int BYTES = PPW * (4 * SP * AB_LD + SP * (SP + 2)) * 4;
     static int reserved = 0;
     if (const int st = lime_reserve_lds((const void*)token_attn_bwd_kernel<SP>, BYTES, reserved, "lime_token_attention_bwd_f32")) return st;
-    const long n_group = ((long)n_seq * n_head + PPW - 1) / PPW;
+    const long n_group = ((long)a.n_seq * a.n_head + PPW - 1) / PPW;
     const int grid = (int)lime_persistent_grid(n_group);                 // persistent: one workgroup per CU
     // vector staging: 32-float head rows on 16-byte boundaries with zero padding columns, dO pairs on 8-byte boundaries
-    const bool vec = head_stride == 32 && lime_al16(q, ld) && lime_al16(k, ld) && lime_al16(v, ld) &&
-                     head_dim % 2 == 0 && ldo % 2 == 0 && (((uintptr_t)dout) & 7) == 0;
-    token_attn_bwd_kernel<SP><<<grid, 512, BYTES, s>>>(q, k, v, ld, dout, ldo, dq, dk, dv, ldd, n_seq, S, n_head, head_dim,
-                                                      head_stride, scale, vec ? 1 : 0, drop, key_mask);
+    const bool vec = a.head_stride == 32 && lime_al16(a.q, a.ld_qkv) && lime_al16(a.k, a.ld_qkv) && lime_al16(a.v, a.ld_qkv) &&
+                     a.head_dim % 2 == 0 && a.ldo % 2 == 0 && (((uintptr_t)a.dout) & 7) == 0;
+    token_attn_bwd_kernel<SP><<<grid, 512, BYTES, s>>>(a.q, a.k, a.v, a.ld_qkv, a.dout, a.ldo, a.dq, a.dk, a.dv, a.ld_dqkv, a.n_seq, a.S,
+                                                      a.n_head, a.head_dim, a.head_stride, a.scale, vec ? 1 : 0, lime_attn_bwd_dropout(a),
+                                                      a.key_mask);
     return lime_check_launch("token_attn_bwd_kernel");
 }
 
@@ -1014,60 +1015,40 @@ extern "C" int64_t lime_token_attention_stats_workspace(int32_t n_seq, int32_t S
     return S > 128 ? (int64_t)n_seq * S * n_head * 2 : 0;            // lse and delta per (token, head) for the blocked paths
 }
 
-extern "C" int64_t lime_token_attention_bwd_workspace(int32_t n_seq, int32_t S, int32_t n_head) {
-    if (S <= 128) return 0;
-    const int64_t n_blk = (S + LB - 1) / LB;
-    // the row statistics + one [tokens][n_head * 32] slab per key block behind the first (their shares of dq, summed in block order)
-    return lime_token_attention_stats_workspace(n_seq, S, n_head) + (n_blk - 1) * (int64_t)n_seq * S * n_head * 32;
+// the blocked backward (S > 128): the row statistics, then one [tokens][n_head * 32] slab per key block behind the first (their shares
+// of dq, summed in block order)
+LimeAttnBwdCarve lime_attn_bwd_carve(int n_seq, int S, int n_head) {
+    const int n_blk = (S + LB - 1) / LB;
+    const int64_t stats = lime_token_attention_stats_workspace(n_seq, S, n_head);
+    return LimeAttnBwdCarve{n_blk, stats, stats + (n_blk - 1) * (int64_t)n_seq * S * n_head * 32};
 }
 
-static int attention_bwd(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
-                         int64_t ld_out, const float* dout, int64_t ldo, float* dq, float* dk, float* dv,
-                         int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
-                         int32_t head_stride, float scale, float* workspace, int64_t workspace_floats,
-                         float dropout_p, uint64_t seed, uint32_t site, const uint8_t* key_mask, const float* lse, void* stream) {
-    LIME_REQUIRE(q && k && v && dout && dq && dk && dv, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: null pointer");
-    LIME_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: dropout_p outside [0, 1)");
-    const LimeDropout drop = lime_make_dropout(dropout_p, seed, site);
-    LIME_REQUIRE(n_seq >= 0 && S > 0 && n_head > 0 && head_dim > 0, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: bad dimensions");
-    if (head_dim > 32)                                         // wide heads: token_attn_wide_f32.hip recomputes the statistics (out / lse unused)
-        return lime_token_attention_wide_bwd("lime_token_attention_bwd_f32", q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head,
-                                             head_dim, head_stride, scale, workspace, workspace_floats, drop, key_mask, (hipStream_t)stream);
-    LIME_REQUIRE(S <= 512 && head_stride >= head_dim && head_stride <= 32, LIME_ERR_UNSUPPORTED,
-                 "lime_token_attention_bwd_f32: needs S <= 512 and head_dim <= head_stride <= 32 (S=%d head_dim=%d head_stride=%d)",
-                 S, head_dim, head_stride);
-    LIME_REQUIRE(ld_qkv >= (int64_t)n_head * head_stride && ld_dqkv >= (int64_t)n_head * head_stride && ldo >= (int64_t)n_head * head_dim,
-                 LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: leading dimension smaller than the row");
-    if (n_seq == 0) return LIME_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (S <= 32) return launch_attn_bwd<32>(q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride, scale, drop, key_mask, s);
-    if (S <= 64) return launch_attn_bwd<64>(q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride, scale, drop, key_mask, s);
-    if (S <= 128) {
-        if (key_mask == nullptr && (lime_split_mode() & 1)) {      // every product on the bf16 matrix cores (token_attn_bwd_sp_f32.hip)
-            const int st = lime_token_attention_bwd_sp(q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride,
-                                                       scale, drop, s);
-            if (st != LIME_NOT_APPLICABLE) return st;
+extern "C" int64_t lime_token_attention_bwd_workspace(int32_t n_seq, int32_t S, int32_t n_head) {
+    return S > 128 ? lime_attn_bwd_carve(n_seq, S, n_head).total : 0;
+}
+
+// The fp32 kernels of the backward at head_dim <= 32 (token_attn_f32.hip chose r and made the checks): the one-pass kernel's length
+// bucket r.n, or the pass r.pass (row statistics, or delta alone) + the key-block kernel on the arithmetic of r.family + the sum of the
+// key blocks' dq slabs.
+int lime_attn_bwd_launch(const LimeAttnBwdRoute& r, const lime_token_attention_bwd_args& a, hipStream_t s) {
+    if (r.family == LIME_BWD_ATTN_ONE_PASS) {
+        switch (r.n) {
+            case 32: return launch_attn_bwd<32>(a, s);
+            case 64: return launch_attn_bwd<64>(a, s);
+            case 128: return launch_attn_bwd<128>(a, s);
         }
-        return launch_attn_bwd<128>(q, k, v, ld_qkv, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride, scale, drop, key_mask, s);
+        LIME_REQUIRE(false, LIME_ERR_UNSUPPORTED, "lime_token_attention_bwd_f32: token_attn_bwd_kernel<%d> is not built", r.n);
     }
-    // blocked path
-    LIME_REQUIRE(key_mask == nullptr, LIME_ERR_UNSUPPORTED, "lime_token_attention_bwd_f32: a key mask needs S <= 128");
-    LIME_REQUIRE(out && ld_out >= (int64_t)n_head * head_dim, LIME_ERR_BAD_ARG,
-                 "lime_token_attention_bwd_f32: S > 128 needs the forward output `out` (delta = dO . O)");
-    LIME_REQUIRE(workspace && workspace_floats >= lime_token_attention_bwd_workspace(n_seq, S, n_head), LIME_ERR_BAD_ARG,
-                 "lime_token_attention_bwd_f32: S > 128 needs lime_token_attention_bwd_workspace() floats of workspace");
-    const int n_blk = (S + LB - 1) / LB;
-    const long n_prob = (long)n_seq * n_head;
-    LIME_REQUIRE(n_prob * n_blk < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_token_attention_bwd_f32: too many blocks");
-    float* const dq_slabs = workspace + lime_token_attention_stats_workspace(n_seq, S, n_head);
-    const long n_tok = (long)n_seq * S;
-    const bool spx = (lime_split_mode() & 1) != 0;             // Q K^T / dO V^T as split products on the bf16 matrix cores
+    const LimeAttnBwdCarve w = lime_attn_bwd_carve(a.n_seq, a.S, a.n_head);
+    float* const stats = a.workspace;
+    float* const dq_slabs = a.workspace + w.stats;
+    const long n_prob = (long)a.n_seq * a.n_head, n_tok = (long)a.n_seq * a.S;
     int st;
-    if (lse) {                                                 // the forward kept its log-sum-exp: only delta = dO . O is left
-        LIME_REQUIRE(n_head <= 64 && n_head * head_dim <= 1024, LIME_ERR_UNSUPPORTED, "lime_token_attention_bwd_lse_f32: n_head > 64 or n_head * head_dim > 1024");
-        attn_delta_kernel<<<lime_grid_cap(n_tok, 4, 8192), 256, 0, s>>>(out, ld_out, dout, ldo, lse, workspace, n_tok, n_head, head_dim);
-        st = lime_check_launch("attn_stats_kernel");
-    } else st = launch_attn_stats(spx, q, k, ld_qkv, out, ld_out, dout, ldo, workspace, n_prob, S, n_head, head_dim, head_stride, scale, n_blk, s);
+    if (r.pass == LIME_BWD_ATTN_PASS_DELTA) {                    // the forward kept its log-sum-exp: only delta = dO . O is left
+        attn_delta_kernel<<<lime_grid_cap(n_tok, 4, 8192), 256, 0, s>>>(a.out, a.ld_out, a.dout, a.ldo, a.lse, stats, n_tok, a.n_head, a.head_dim);
+        st = lime_check_launch("attn_delta_kernel");
+    } else st = launch_attn_stats(r.pass == LIME_BWD_ATTN_PASS_STATS_SPLIT, a.q, a.k, a.ld_qkv, a.out, a.ld_out, a.dout, a.ldo, stats, n_prob,
+                                  a.S, a.n_head, a.head_dim, a.head_stride, a.scale, w.n_blk, s);
     if (st != LIME_OK) return st;
     // the two blocked kernels take the same arguments; they differ in LDS bytes and workgroup size (two four-wave workgroups per CU
     // for the split product, one eight-wave workgroup for the fp32 MFMA)
@@ -1075,33 +1056,17 @@ static int attention_bwd(const float* q, const float* k, const float* v, int64_t
     constexpr int BYTES_SP = (3 * LB * lime_dev::SWZ_ROW + 3 * LQ * lime_dev::SWZ_ROW + 2 * LQ) * 4;
     static_assert(2 * BYTES_SP <= 163840, "LDS budget: two workgroups per CU");
     static int reserved[2] = {0, 0};
+    const bool spx = r.family == LIME_BWD_ATTN_LONG_SP;          // Q K^T / dO V^T as split products on the bf16 matrix cores
     const auto kernel = spx ? attn_bwd_long_sp_kernel : attn_bwd_long_kernel;
     const int bytes = spx ? BYTES_SP : BYTES;
     st = lime_reserve_lds((const void*)kernel, bytes, reserved[spx], "lime_token_attention_bwd_f32");
     if (st != LIME_OK) return st;
-    kernel<<<(unsigned)(n_prob * n_blk), spx ? 256 : 512, bytes, s>>>(q, k, v, ld_qkv, dout, ldo, workspace, dq, dk, dv, ld_dqkv, S, n_head,
-                                                                   head_dim, head_stride, scale, n_blk, drop, dq_slabs, n_tok);
+    kernel<<<(unsigned)(n_prob * w.n_blk), spx ? 256 : 512, bytes, s>>>(a.q, a.k, a.v, a.ld_qkv, a.dout, a.ldo, stats, a.dq, a.dk, a.dv, a.ld_dqkv,
+                                                                     a.S, a.n_head, a.head_dim, a.head_stride, a.scale, w.n_blk,
+                                                                     lime_attn_bwd_dropout(a), dq_slabs, n_tok);
     st = lime_check_launch(spx ? "attn_bwd_long_sp_kernel" : "attn_bwd_long_kernel");
-    if (st != LIME_OK || n_blk == 1) return st;
-    return launch_attn_dq_reduce(dq, ld_dqkv, dq_slabs, n_tok, n_head, head_stride, n_blk - 1, s);
-}
-
-extern "C" int lime_token_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
-                                            int64_t ld_out, const float* dout, int64_t ldo, float* dq, float* dk, float* dv,
-                                            int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
-                                            int32_t head_stride, float scale, float* workspace, int64_t workspace_floats,
-                                            float dropout_p, uint64_t seed, uint32_t site, const uint8_t* key_mask, void* stream) {
-    return attention_bwd(q, k, v, ld_qkv, out, ld_out, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride, scale,
-                         workspace, workspace_floats, dropout_p, seed, site, key_mask, nullptr, stream);
-}
-
-extern "C" int lime_token_attention_bwd_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
-                                                int64_t ld_out, const float* lse, const float* dout, int64_t ldo, float* dq, float* dk,
-                                                float* dv, int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
-                                                int32_t head_stride, float scale, float* workspace, int64_t workspace_floats, void* stream) {
-    LIME_REQUIRE(lse != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_lse_f32: lse is NULL");
-    return attention_bwd(q, k, v, ld_qkv, out, ld_out, dout, ldo, dq, dk, dv, ld_dqkv, n_seq, S, n_head, head_dim, head_stride, scale,
-                         workspace, workspace_floats, 0.f, 0, 0, nullptr, lse, stream);
+    if (st != LIME_OK || !r.reduce) return st;
+    return launch_attn_dq_reduce(a.dq, a.ld_dqkv, dq_slabs, n_tok, a.n_head, a.head_stride, w.n_blk - 1, s);
 }
 
 // The fp32 kernels of the dropout forward (token_attn_f32.hip chose r and made the checks): the one-pass kernel's length bucket

@@ -416,23 +416,15 @@ extern "C" int64_t lime_token_attention_bwd_workspace_wide(int32_t n_seq, int32_
     return (int64_t)n_seq * S * n_head * 3;          // row maximum, 1 / sum and delta per (token, head), at every S
 }
 
-int lime_token_attention_wide_bwd(const char* entry, const float* q, const float* k, const float* v, long ld, const float* dout, long ldo,
-                                  float* dq, float* dk, float* dv, long ldd, int n_seq, int S, int n_head, int hd, int hs, float scale,
-                                  float* workspace, long workspace_floats, const LimeDropout& drop, const unsigned char* key_mask,
-                                  hipStream_t s) {
-    if (const int st = lime_attn_wide_limits(entry, S, n_head, hd, hs, n_seq)) return st;
-    LIME_REQUIRE(ld >= (long)n_head * hs && ldd >= (long)n_head * hs && ldo >= (long)n_head * hd, LIME_ERR_BAD_ARG,
-                 "%s: leading dimension smaller than the row", entry);
-    LIME_REQUIRE(lime_al16(q, ld) && lime_al16(k, ld) && lime_al16(v, ld) && lime_al16(dout, ldo) && lime_al16(dq, ldd) &&
-                 lime_al16(dk, ldd) && lime_al16(dv, ldd), LIME_ERR_UNSUPPORTED,
-                 "%s: head_dim > 32 needs 16-byte aligned q / k / v / dout / dq / dk / dv and leading dimensions that are multiples of 4", entry);
-    if (n_seq == 0) return LIME_OK;
-    LIME_REQUIRE(workspace != nullptr && workspace_floats >= lime_token_attention_bwd_workspace_wide(n_seq, S, n_head, hd), LIME_ERR_BAD_ARG,
-                 "%s: head_dim > 32 needs lime_token_attention_bwd_workspace_wide() floats of workspace", entry);
+// The backward at head_dim > 32 (token_attn_f32.hip has made the checks): r.n is NK; the statistics + dQ, then dK and dV, which reads
+// the statistics
+int lime_attn_bwd_wide_launch(const LimeAttnBwdRoute& r, const lime_token_attention_bwd_args& a, hipStream_t s) {
+    const char* const entry = "lime_token_attention_bwd_f32";
     WideP p{};
-    p.q = q; p.k = k; p.v = v; p.ld = ld; p.mask = key_mask; p.dout = dout; p.ldg = ldo; p.dq = dq; p.dk = dk; p.dv = dv; p.ldd = ldd;
-    p.stats = workspace; p.S = S; p.n_head = n_head; p.hd = hd; p.hs = hs; p.n_blk = (S + WB - 1) / WB; p.scale = scale; p.drop = drop;
-    const unsigned grid = (unsigned)((long)n_seq * n_head * p.n_blk);
-    if (const int st = launch_wide_nk(1, (hd + 15) / 16, p, grid, s, entry)) return st;      // statistics + dQ
-    return launch_wide_nk(2, (hd + 15) / 16, p, grid, s, entry);                             // dK, dV (reads the statistics)
+    p.q = a.q; p.k = a.k; p.v = a.v; p.ld = a.ld_qkv; p.mask = a.key_mask; p.dout = a.dout; p.ldg = a.ldo; p.dq = a.dq; p.dk = a.dk; p.dv = a.dv;
+    p.ldd = a.ld_dqkv; p.stats = a.workspace; p.S = a.S; p.n_head = a.n_head; p.hd = a.head_dim; p.hs = a.head_stride;
+    p.n_blk = (a.S + WB - 1) / WB; p.scale = a.scale; p.drop = lime_attn_bwd_dropout(a);
+    const unsigned grid = (unsigned)((long)a.n_seq * a.n_head * p.n_blk);
+    if (const int st = launch_wide_nk(1, r.n, p, grid, s, entry)) return st;
+    return launch_wide_nk(2, r.n, p, grid, s, entry);
 }

@@ -1676,12 +1676,9 @@ def relu_bwd_(dh, h, scale=1.0):
     return dh
 
 
-def token_attention_bwd(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride=None, dqkv=None, out=None,
-                        dropout=None, key_mask=None, lse=None):
-    """Backward of the unmasked ``token_attention``: q / k / v column views of one packed qkv buffer [tokens, 3 * n_head *
-    head_stride]; returns dqkv in the same layout.  ``out``: the forward's result (needed for S > 128).  ``dropout``:
-    (p, seed, site) of the ``token_attention_dropout`` forward.  head_dim ranges as ``token_attention``; the wide heads
-    (32 < head_dim <= 128) recompute their statistics at every S: ``out`` and ``lse`` are optional and unused there."""
+def _token_attention_bwd_block(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride, dqkv, out, dropout, key_mask, lse):
+    """(lime_token_attention_bwd_args, dqkv, what the block points into and nobody else holds) for ``token_attention_bwd``'s arguments: the operand checks,
+    the workspace and the choice between the two C entries, for the call and for its plan."""
     lib = _lib.load()
     hs = head_dim if head_stride is None else head_stride
     W = n_head * hs
@@ -1711,19 +1708,60 @@ def token_attention_bwd(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_s
         if tuple(out.shape) != tuple(dout.shape):
             raise ValueError('out must have the shape of dout')
         ws = _workspace(q.device, need)
-    if lse is not None and need and (not wide or (S > 128 and out is not None)):   # S > 128 with the forward's statistics
+    # The lse entry is used only where a workspace is needed (narrow heads: S > 128, where the forward's lse saves the statistics pass)
+    # and, for wide heads (which need one at every S and read neither), only with S > 128 and `out` given -- the call a narrow head
+    # would make.  Everywhere else lse is ignored and the plain entry speaks.
+    use_lse = bool(lse is not None and need and (not wide or (S > 128 and out is not None)))
+    a = _lib.TokenAttentionBwdArgs()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a.q, a.k, a.v, a.ld_qkv = ptr(q), ptr(k), ptr(v), _ld(q)
+    a.dout, a.ldo, a.dq, a.dk, a.dv, a.ld_dqkv = ptr(dout), _ld(dout), ptr(dq), ptr(dk), ptr(dv), _ld(dqkv)
+    a.n_seq, a.S, a.n_head, a.head_dim, a.head_stride, a.scale = n_seq, S, n_head, head_dim, hs, scale
+    a.workspace, a.workspace_floats = ptr(ws), ws.numel() if ws is not None else 0
+    if use_lse:
         if dropout or key_mask is not None:
             raise ValueError('lse goes with the plain (no dropout, no key mask) forward')
         _vec(lse, 'lse', n_seq * S * n_head)
-        check(lib.lime_token_attention_bwd_lse_f32(_p(q), _p(k), _p(v), _ld(q), _p(out), _ld(out), _p(lse), _p(dout), _ld(dout), _p(dq),
-                                                   _p(dk), _p(dv), _ld(dqkv), n_seq, S, n_head, head_dim, hs, scale, _p(ws), ws.numel(),
-                                                   _stream()), 'lime_token_attention_bwd_lse_f32')
+        a.entry, a.out, a.ld_out, a.lse = _lib.BWD_ATTN_ENTRY['lse'], ptr(out), _ld(out), ptr(lse)
+        return a, dqkv, ws
+    key_mask = _mask_u8(key_mask, 'key_mask')
+    a.entry, a.out, a.ld_out, a.key_mask = _lib.BWD_ATTN_ENTRY['plain'], ptr(out), _ld(out) if out is not None else 0, ptr(key_mask)
+    a.dropout_p, a.dropout_seed, a.dropout_site = dropout or (0.0, 0, 0)
+    return a, dqkv, (ws, key_mask)
+
+
+def token_attention_bwd(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride=None, dqkv=None, out=None,
+                        dropout=None, key_mask=None, lse=None):
+    """Backward of the unmasked ``token_attention``: q / k / v column views of one packed qkv buffer [tokens, 3 * n_head *
+    head_stride]; returns dqkv in the same layout.  ``out``: the forward's result (needed for S > 128).  ``dropout``:
+    (p, seed, site) of the ``token_attention_dropout`` forward.  head_dim ranges as ``token_attention``; the wide heads
+    (32 < head_dim <= 128) recompute their statistics at every S: ``out`` and ``lse`` are optional and unused there."""
+    lib = _lib.load()
+    a, dqkv, _keep = _token_attention_bwd_block(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride, dqkv, out, dropout, key_mask, lse)
+    c = ctypes.c_void_p
+    if a.entry == _lib.BWD_ATTN_ENTRY['lse']:
+        check(lib.lime_token_attention_bwd_lse_f32(c(a.q), c(a.k), c(a.v), a.ld_qkv, c(a.out), a.ld_out, c(a.lse), c(a.dout), a.ldo, c(a.dq),
+                                                   c(a.dk), c(a.dv), a.ld_dqkv, n_seq, S, n_head, head_dim, a.head_stride, scale,
+                                                   c(a.workspace), a.workspace_floats, _stream()), 'lime_token_attention_bwd_lse_f32')
         return dqkv
-    check(lib.lime_token_attention_bwd_f32(_p(q), _p(k), _p(v), _ld(q), _p(out), _ld(out) if out is not None else 0, _p(dout),
-                                           _ld(dout), _p(dq), _p(dk), _p(dv), _ld(dqkv), n_seq, S, n_head, head_dim, hs, scale,
-                                           _p(ws), ws.numel() if ws is not None else 0, *(dropout or (0.0, 0, 0)),
-                                           _p(_mask_u8(key_mask, 'key_mask')), _stream()), 'lime_token_attention_bwd_f32')
+    check(lib.lime_token_attention_bwd_f32(c(a.q), c(a.k), c(a.v), a.ld_qkv, c(a.out), a.ld_out, c(a.dout), a.ldo, c(a.dq), c(a.dk), c(a.dv),
+                                           a.ld_dqkv, n_seq, S, n_head, head_dim, a.head_stride, scale, c(a.workspace), a.workspace_floats,
+                                           a.dropout_p, a.dropout_seed, a.dropout_site, c(a.key_mask), _stream()),
+          'lime_token_attention_bwd_f32')
     return dqkv
+
+
+def token_attention_bwd_plan(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride=None, dqkv=None, out=None,
+                             dropout=None, key_mask=None, lse=None):
+    """What ``token_attention_bwd`` would run for the same arguments, without running it (``lime_token_attention_bwd_plan_f32``): a dict
+    with ``family`` ('one_pass', 'sp', 'long', 'long_sp', 'wide'; None where nothing is launched), ``stats_pass`` (None / 'fp32' /
+    'split' / 'delta') and ``kernels`` (the instantiations in launch order, as rocprofv3 prints them).  A call the wrapper or the entry
+    would refuse raises the same error."""
+    a, _dqkv, _keep = _token_attention_bwd_block(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride, dqkv, out, dropout, key_mask, lse)
+    plan = _lib.TokenAttentionBwdPlan()
+    check(_lib.load().lime_token_attention_bwd_plan_f32(ctypes.byref(a), ctypes.byref(plan)), 'lime_token_attention_bwd_plan_f32')
+    return dict(family=_lib.BWD_ATTN_FAMILY[plan.family], stats_pass=_lib.BWD_ATTN_PASS[plan.stats_pass],
+                kernels=[plan.name[i].value.decode() for i in range(plan.n_launches)])
 
 
 def dropout2(src, p, seed, site1, site2, out=None):
