@@ -29,14 +29,14 @@
 extern "C" {
 #endif
 
-#define LIME_ABI_VERSION 13
+#define LIME_ABI_VERSION 14
 
 typedef enum {
     LIME_OK = 0,
     LIME_ERR_BAD_ARG = -1,      /* null pointer, non-positive dimension, misaligned leading dimension */
     LIME_ERR_UNSUPPORTED = -2,  /* shape outside what the kernels are built for */
     LIME_ERR_LAUNCH = -3,       /* hipGetLastError() after the launch was not hipSuccess */
-    LIME_NOT_APPLICABLE = 1     /* nothing was launched and nothing is wrong: the entry does not cover this call (lime_token_attention_vocab_f32) */
+    LIME_NOT_APPLICABLE = 1     /* nothing was launched and nothing is wrong: the entry does not cover this call (lime_token_attention_f32, vocab form) */
 } lime_status;
 
 int lime_abi_version(void);
@@ -150,7 +150,7 @@ typedef struct {
 int lime_linear_plan_f32(const lime_linear_args* args, int32_t n_cu, lime_linear_plan* out);
 
 /* Which kernels take the large 16-byte-aligned problems of lime_linear_f32 (M x N tiles >= 96 of 256 x 320) -- and, with the same bit 0, of
- * lime_linear_wgrad_f32 (M >= 4096), the unmasked padded-head lime_token_attention*_f32 (S = 32 ... 512) and lime_token_attention_bwd*_f32
+ * lime_linear_wgrad_f32 (M >= 4096), the unmasked padded-head lime_token_attention_f32 (S = 32 ... 512) and lime_token_attention_bwd_f32
  * (S > 64, no key mask):
  *   1 (default): csrc/gemm_sp_f32.hip -- fp32 operands split in registers into three bf16 terms each, six bf16 MFMAs per product
  *                block with fp32 accumulation: the error of one fp32 rounding per product (the same bound as the fp32 MFMA), fp32's
@@ -369,38 +369,6 @@ int lime_embed_pe_f32(const int32_t* ids, const float* table, int64_t ld_table, 
                       int32_t period, float* out, int64_t ldo, int64_t rows, int32_t dim, void* stream);
 
 /*
- * lime_token_attention_f32: softmax(Q K^T * scale [+ key mask]) V per (sequence, head), exact-fp32 MFMA.
- * Replaces the attention core of nn.MultiheadAttention inside the TransformerEncoderLayers
- * (newsEncoders.py:316,320; unmasked) and layers.MultiHeadAttention.forward (layers.py:227-237; key mask
- * filled with -1e9).  q/k/v: row (seq * S + t), column (head * head_stride + d), d < head_dim, leading dimension
- * ld_qkv (the three may alias one packed buffer).  head_stride == head_dim is the packed layout of the reference;
- * head_stride = 32 (heads padded with zero columns, see lime_pad_heads_f32) lets the kernel use aligned 16-byte loads.
- * key_mask: uint8 [n_seq, S], 0 = masked, or NULL.  out[(seq * S + t) * ldo + head * head_dim + d] (always packed).
- * Requires S <= 512, head_stride >= head_dim, and head_dim <= 32 -- or 32 < head_dim <= 128 under the wide-head limits stated at
- * lime_token_attention_bwd_workspace_wide.
- */
-int lime_token_attention_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask,
-                             float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
-                             int32_t head_stride, float scale, void* stream);
-
-/* lime_token_attention_count_f32: lime_token_attention_f32 with an optional device-side sequence count (min(*n_seq_dev, n_seq)
- * sequences are computed; n_seq is the capacity): the masked attention of a compacted batch inside a HIP graph. */
-int lime_token_attention_count_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask,
-                                   const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                   int32_t head_dim, int32_t head_stride, float scale, void* stream);
-
-/*
- * lime_token_attention_rows_f32: lime_token_attention_f32 (unmasked, heads padded to 32 columns) over COMPACTED sequences: the
- * q / k / v row of token (seq * S + t) is row_map[seq * S + t] -- a live token's own row, or one of the S rows that all padding
- * tokens at position t share (lime_compact_sequences) -- and min(*n_seq_dev, n_seq) sequences are computed when n_seq_dev is
- * given (a device int: the launch sits in a HIP graph, the count changes per batch).  out rows stay dense: (seq * S + t).
- * S in {32, 64, 96, 128, 256, 512}; q / k / v 16-byte aligned, ld_qkv % 4 == 0.
- */
-int lime_token_attention_rows_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const int32_t* row_map,
-                                  const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                  int32_t head_dim, float scale, void* stream);
-
-/*
  * lime_compact_sequences: index lists for encoding only what differs in a batch of token sequences (ids int32 [n_seq, S], 0 = the
  * padding word).  The reference encodes every slot (newsEncoders.py:311-321), including history slots padded with the all-zero
  * <PAD> news (corpus.py:476-477) and the padding behind every text; those are exact repetitions:
@@ -460,22 +428,45 @@ int lime_news_xin_f32(const float* title_blocks, int64_t ld_t, int32_t nblk_t, c
                       int32_t dim, void* stream);
 
 /*
- * lime_token_attention_vocab_f32: the attention of the FIRST encoder layer over a per-vocabulary in_proj product.  The q / k / v
- * row of token (seq * S + t) is qkv_vocab[ids[seq * S + t]] + pos_rows[t]: qkv_vocab is the [V, ld] table E W_in^T (q | k | v at
- * columns 0, W, 2W with W = n_head * 32: heads padded to 32 columns), pos_rows the [S, ld] table PE W_in^T + b in the same layout,
- * the sum one fp32 add per element -- bit for bit lime_token_attention_f32 over the materialised rows.  A padding token is id 0 at
- * its position; ids are not range-checked.  min(*n_seq_dev, n_seq) sequences are computed when n_seq_dev is given.
- * Split-product kernel only: returns LIME_NOT_APPLICABLE, launching nothing, under lime_set_split_gemm(0) or outside S in
- * {32, 64, 128}, head_dim <= 32, ld % 4 == 0, ld >= 3 W, 16-byte aligned tables -- the caller then runs in_proj and
- * lime_token_attention_rows_f32.
+ * lime_token_attention_f32: softmax(Q K^T * scale [+ key mask]) V per (sequence, head) in fp32, from one argument block.  Replaces the
+ * attention core of nn.MultiheadAttention inside the TransformerEncoderLayers (newsEncoders.py:316,320; unmasked) and
+ * layers.MultiHeadAttention.forward (layers.py:227-237; key mask filled with -1e9).  `form` says which call it is; fields a form does not
+ * have are 0 / NULL.  Each form's refusals carry the name it had as an entry of its own (given with the form below).
+ * Which kernels a call runs: DESIGN.md section 5.2 has the routing table, lime_token_attention_plan_f32 below returns a call's row.
+ *
+ * All forms: q / k / v row (seq * S + t), column (head * head_stride + d), d < head_dim, leading dimension ld_qkv (the three may alias
+ * one packed buffer).  head_stride == head_dim is the packed layout of the reference; head_stride = 32 (heads padded with zero columns,
+ * see lime_pad_heads_f32) lets the kernels use aligned 16-byte loads.  out[(seq * S + t) * ldo + head * head_dim + d] (always packed).
+ * S <= 512, head_stride >= head_dim, and head_dim <= 32 -- or 32 < head_dim <= 128 under the wide-head limits stated at
+ * lime_token_attention_bwd_workspace_wide (not the rows and vocab forms).
+ *
+ * PLAIN, COUNT (lime_token_attention_count_f32): key_mask uint8 [n_seq, S], 0 = masked, or NULL.  n_seq_dev, optional: a device int;
+ * min(*n_seq_dev, n_seq) sequences are computed and n_seq is the capacity -- the masked attention of a compacted batch inside a HIP
+ * graph, where the count changes per batch.  COUNT is PLAIN that hands a count over.
+ *
+ * LSE (lime_token_attention_lse_f32): no key mask, no device count; also writes lse [tokens, n_head] -- per (token, head) the
+ * log2-domain log-sum-exp of the scaled scores, max + log2(sum 2^(s - max)) with s = scale * log2(e) * q . k -- for a training step
+ * whose backward (LIME_BWD_ATTN_ENTRY_LSE) reads it: S > 128 pays a Q K^T pass of its own for the statistics otherwise.
+ *
+ * ROWS (lime_token_attention_rows_f32): unmasked, head_stride = 32, over COMPACTED sequences: the q / k / v row of token (seq * S + t)
+ * is row_map[seq * S + t] -- a live token's own row, or one of the S rows that all padding tokens at position t share
+ * (lime_compact_sequences); n_seq_dev as above.  out rows stay dense: (seq * S + t).  S in {32, 64, 96, 128, 256, 512}, head_dim <= 32;
+ * q / k / v 16-byte aligned, ld_qkv % 4 == 0.
+ *
+ * VOCAB (lime_token_attention_vocab_f32): the attention of the FIRST encoder layer over a per-vocabulary in_proj product.  The q / k / v
+ * row of token (seq * S + t) is qkv_vocab[ids[seq * S + t]] + pos_rows[t]: qkv_vocab is the [V, ld_qkv] table E W_in^T (q | k | v at
+ * columns 0, W, 2W with W = n_head * 32), pos_rows the [S, ld_qkv] table PE W_in^T + b in the same layout, the sum one fp32 add per
+ * element -- bit for bit PLAIN over the materialised rows.  The block holds q = qkv_vocab, k = q + W, v = q + 2 W, row_map = ids,
+ * head_stride = 32.  A padding token is id 0 at its position; ids are not range-checked; n_seq_dev as above.  Split-product kernel
+ * only: returns LIME_NOT_APPLICABLE, launching nothing, under lime_set_split_gemm(0) or outside S in {32, 64, 128}, head_dim <= 32,
+ * ld_qkv % 4 == 0, 3 W <= ld_qkv <= 2^21, 16-byte aligned tables -- the caller then runs in_proj and the ROWS form.
+ *
+ * DROPOUT (lime_token_attention_dropout_f32): dropout on the probabilities (nn.MultiheadAttention(dropout=p) in training mode):
+ * out = (keep * softmax(scale q k^T) / (1 - p)) v, no key mask, mask element ((seq * n_head + head) * S + i) * S + j drawn from
+ * (dropout_p, dropout_seed, dropout_site) as stated at lime_dropout_f32.  head_dim <= 32 needs head_stride <= 32; there S > 128 runs
+ * in 128 x 128 blocks and needs lime_token_attention_stats_workspace(n_seq, S, n_head) floats of workspace (the row statistics; the
+ * larger lime_token_attention_bwd_workspace does as well), else workspace may be NULL.
  */
-int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
-                                   const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                   int32_t head_dim, float scale, void* stream);
-
-/* The arguments of the six fp32 forward entries (lime_token_attention_f32, _count_f32, _lse_f32, _rows_f32, _vocab_f32, _dropout_f32)
- * as one block; `form` says which entry is speaking, fields an entry does not have are 0 / NULL.  The vocab form: q = qkv_vocab,
- * k = q + W, v = q + 2 W (W = n_head * 32), row_map = ids; rows and vocab: head_stride = 32. */
 enum { LIME_ATTN_FORM_PLAIN = 0, LIME_ATTN_FORM_COUNT = 1, LIME_ATTN_FORM_LSE = 2, LIME_ATTN_FORM_ROWS = 3, LIME_ATTN_FORM_VOCAB = 4,
        LIME_ATTN_FORM_DROPOUT = 5 };
 typedef struct {
@@ -501,11 +492,13 @@ typedef struct {
     int32_t reserved;
 } lime_token_attention_args;
 
+int lime_token_attention_f32(const lime_token_attention_args* args, void* stream);
+
 /* What the fp32 token-attention forward would run for an argument block, without running it: the routing decision
  * (csrc/token_attn_f32.hip, lime_attn_route) as data.  A pure function of the block and the
  * lime_set_split_gemm() setting: no launch, no call into the HIP runtime, no pointer of the block is read through (only NULL-ness
- * and alignment count); the CU count sizes the grids and chooses no kernel.  Returns what the entry named by `form` would return
- * where it launches nothing -- its refusal (same status, same lime_last_error_string()) or LIME_NOT_APPLICABLE (vocab form) -- else
+ * and alignment count); the CU count sizes the grids and chooses no kernel.  Returns what lime_token_attention_f32 would return
+ * where it launches nothing -- the form's refusal (same status, same lime_last_error_string()) or LIME_NOT_APPLICABLE (vocab form) -- else
  * LIME_OK and
  *   family      LIME_ATTN_SP token_attn_sp_kernel (split product, S = 32 / 64 / 128 in one pass), _SP_LONG token_attn_sp_long_kernel
  *               (S = 256 / 512 in key blocks), _SP_VOCAB token_attn_sp_vocab_kernel, _MFMA token_attn_kernel (exact-fp32 MFMA),
@@ -529,7 +522,7 @@ typedef struct {
 int lime_token_attention_plan_f32(const lime_token_attention_args* args, lime_token_attention_plan* out);
 
 /* lime_token_attention_rows_bf16: lime_token_attention_bf16 over compacted sequences (row_map / n_seq_dev as in
- * lime_token_attention_rows_f32); S in {32, 64, 128}, even head_dim. */
+ * the ROWS form of lime_token_attention_f32); S in {32, 64, 128}, even head_dim. */
 int lime_token_attention_rows_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t ld_qkv, const int32_t* row_map,
                                    const int32_t* n_seq_dev, uint16_t* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
                                    int32_t head_dim, float scale, int32_t out_cols, void* stream);
@@ -782,46 +775,30 @@ int lime_layernorm_bwd_dropout_f32(const float* dy, int64_t lddy, int32_t dy_div
  * ReLU + the dropout that follows it when h is the dropped-out activation (scale = 1 / (1 - p)) */
 int lime_relu_bwd_f32(float* dh, int64_t lddh, const float* h, int64_t ldh, int64_t rows, int32_t cols, float scale, void* stream);
 
-/* Backward of lime_token_attention_f32 (the encoder layers; optionally the key mask of MHSA): given q / k / v as the forward read them
- * and dout [tokens, n_head * head_dim] (packed), writes dq / dk / dv in the layout of q / k / v (row stride ld_dqkv, head
+/* lime_token_attention_bwd_f32 (below, behind its argument block): backward of lime_token_attention_f32 (the encoder layers;
+ * optionally the key mask of MHSA).  Given q / k / v as the forward read them and dout [tokens, n_head * head_dim] (packed), writes dq / dk / dv in the layout of q / k / v (row stride ld_dqkv, head
  * h at column h * head_stride; columns head_dim .. head_stride - 1 come out as zeros).  The probabilities are recomputed.
  * S <= 512, head_dim <= head_stride <= 32 (wider heads: see lime_token_attention_bwd_workspace_wide below).  S <= 128: one pass per (sequence, head); `out` and `workspace` may be NULL.
  * 128 < S <= 512 (the 512-token bodies of BASELINE config 4): 128 x 128 blocks; needs the forward output `out` (packed like
  * dout) and lime_token_attention_bwd_workspace(n_seq, S, n_head) floats: the row statistics and one dq slab per key block behind the
- * first -- the key blocks' shares of dq are stored (no atomics) and summed in block order, so the result is bitwise reproducible.  dropout_p > 0: the forward was lime_token_attention_dropout_f32 with the same (dropout_p, seed, site).
+ * first -- the key blocks' shares of dq are stored (no atomics) and summed in block order, so the result is bitwise reproducible.  dropout_p > 0: the forward was the DROPOUT form with the same (dropout_p, seed, site).
  * key_mask (uint8 [n_seq, S], 0 = masked, or NULL; S <= 128): the masked attention of layers.MultiHeadAttention
  * (layers.py:227-232) -- masked scores are constants (-1e9) and receive no gradient.
  * Which kernels a call runs: DESIGN.md section 5.5 has the routing table, lime_token_attention_bwd_plan_f32 below returns a call's row. */
 int64_t lime_token_attention_bwd_workspace(int32_t n_seq, int32_t S, int32_t n_head);
-/* the row-statistics part of it (lse and delta per (token, head)): what lime_token_attention_dropout_f32 needs for S > 128 */
+/* the row-statistics part of it (lse and delta per (token, head)): what the forward's DROPOUT form needs for S > 128 */
 int64_t lime_token_attention_stats_workspace(int32_t n_seq, int32_t S, int32_t n_head);
 /* Wide heads (32 < head_dim <= 128, head_dim % 4 == 0, head_stride % 4 == 0, S <= 512, 16-byte aligned operands, leading dimensions
- * multiples of 4; csrc/token_attn_wide_f32.hip): lime_token_attention_f32 / _count_f32 / _lse_f32 / _dropout_f32 and
- * lime_token_attention_bwd_f32 / _bwd_lse_f32 send them to exact-fp32 MFMA kernels that stream the keys in blocks of 64 (key mask, device
+ * multiples of 4; csrc/token_attn_wide_f32.hip): lime_token_attention_f32 (forms PLAIN, COUNT, LSE, DROPOUT) and
+ * lime_token_attention_bwd_f32 send them to exact-fp32 MFMA kernels that stream the keys in blocks of 64 (key mask, device
  * count, lse output and dropout as for the narrow heads; lime_set_split_gemm has no effect on them).  Their backward recomputes the row
  * statistics at every S (`out` and `lse` are accepted and not read), sums in a fixed order (bitwise reproducible) and needs
  * lime_token_attention_bwd_workspace_wide(n_seq, S, n_head, head_dim) floats of workspace -- for head_dim <= 32 that is
  * lime_token_attention_bwd_workspace(n_seq, S, n_head).  The forward with dropout needs no workspace for wide heads. */
 int64_t lime_token_attention_bwd_workspace_wide(int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim);
-int lime_token_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out, int64_t ld_out,
-                                 const float* dout, int64_t ldo, float* dq, float* dk, float* dv, int64_t ld_dqkv, int32_t n_seq,
-                                 int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale, float* workspace,
-                                 int64_t workspace_floats, float dropout_p, uint64_t seed, uint32_t site, const uint8_t* key_mask,
-                                 void* stream);
-
-/* The pair for a training step whose forward keeps its softmax statistics (S > 128 pays a Q K^T pass of its own for them otherwise):
- * lime_token_attention_lse_f32 is lime_token_attention_f32 without a key mask that also writes lse [tokens, n_head] -- per (token, head)
- * the log2-domain log-sum-exp of the scaled scores, max + log2(sum 2^(s - max)) with s = scale * log2(e) * q . k --;
- * lime_token_attention_bwd_lse_f32 is lime_token_attention_bwd_f32 (no dropout, no key mask) reading it. */
-int lime_token_attention_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo, float* lse,
-                                 int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale, void* stream);
-int lime_token_attention_bwd_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out, int64_t ld_out,
-                                     const float* lse, const float* dout, int64_t ldo, float* dq, float* dk, float* dv, int64_t ld_dqkv,
-                                     int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale,
-                                     float* workspace, int64_t workspace_floats, void* stream);
-
-/* The arguments of the two fp32 backward entries as one block; `entry` says which of them is speaking (the lse entry: dropout_p = 0,
- * key_mask = NULL; the plain entry does not look at lse). */
+/* `entry` says which backward it is.  PLAIN does not look at lse.  LSE (its own two refusals speak as lime_token_attention_bwd_lse_f32,
+ * all others as lime_token_attention_bwd_f32): behind a forward of the LSE form, reading the lse [tokens, n_head] it wrote instead of
+ * recomputing the statistics (S > 128); dropout_p = 0, key_mask = NULL. */
 enum { LIME_BWD_ATTN_ENTRY_PLAIN = 0, LIME_BWD_ATTN_ENTRY_LSE = 1 };
 typedef struct {
     const float* q;
@@ -849,7 +826,9 @@ typedef struct {
     int32_t reserved;
 } lime_token_attention_bwd_args;
 
-/* What lime_token_attention_bwd_f32 / _bwd_lse_f32 would run for an argument block, without running it: the backward's routing
+int lime_token_attention_bwd_f32(const lime_token_attention_bwd_args* args, void* stream);
+
+/* What lime_token_attention_bwd_f32 would run for an argument block, without running it: the backward's routing
  * decision (csrc/token_attn_f32.hip, lime_attn_bwd_route; DESIGN.md section 5.5 has the table) as data, under the contract of
  * lime_token_attention_plan_f32 -- a pure function of the block and the lime_set_split_gemm() setting, no launch, no pointer read
  * through.  Returns the entry's refusal (same status, same lime_last_error_string()) where it launches nothing, else LIME_OK and
@@ -911,16 +890,6 @@ int lime_embed_pe_dropout_f32(const int32_t* ids, const float* table, int64_t ld
 int lime_dropout_add_layernorm_f32(const float* t, int64_t ldt, const float* res, int64_t ldr, const float* gamma, const float* beta,
                                    float eps, float* y, int64_t ldy, float* rstd, int64_t M, int32_t E, float p, uint64_t seed,
                                    uint32_t site, void* stream);
-
-/* Encoder attention with dropout on the probabilities (nn.MultiheadAttention(dropout=p) in training mode):
- * out = (keep * softmax(scale q k^T) / (1 - p)) v; layouts as lime_token_attention_f32 without a key mask; mask element
- * ((seq * n_head + head) * S + i) * S + j.  S <= 512; S > 128 runs in 128 x 128 blocks and needs
- * lime_token_attention_stats_workspace(n_seq, S, n_head) floats of workspace (the row statistics; the larger
- * lime_token_attention_bwd_workspace does as well), else workspace may be NULL. */
-int lime_token_attention_dropout_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
-                                     int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale,
-                                     float dropout_p, uint64_t seed, uint32_t site, float* workspace, int64_t workspace_floats,
-                                     void* stream);
 
 /* dtable[ids[r], :] += dx[r, :] (nn.Embedding backward, newsEncoders.py:311-312).  dtable must be initialised by the
  * caller (zeros, or a gradient to add to).  Rows with ids[r] == hot_id (the padding word, pass -1 for none) are summed

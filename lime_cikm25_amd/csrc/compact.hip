@@ -6,7 +6,7 @@
 //   * an all-padding sequence has the same pooled output wherever it occurs (the encoder layer has no mask and no
 //     cross-sequence term), so ONE representative is encoded and every such slot reads its result;
 //   * a padding token's in_proj row depends on its position only ((E[0] + PE[t]) W^T + b), so in_proj runs over the live
-//     tokens and attention reads the S table rows for the rest (lime_token_attention_rows_f32).
+//     tokens and attention reads the S table rows for the rest (lime_token_attention_f32, rows form).
 // Nothing is approximated and nothing is cached between forwards.  This file turns the [n_seq, S] id matrix into the index
 // lists those kernels consume -- on the device, in fixed-size buffers, with the counts in device memory, so that the
 // whole forward stays one HIP graph:

@@ -1,5 +1,5 @@
-// Between the fp32 token-attention routing (token_attn_f32.hip: the six lime_token_attention*_f32 forward entries and the two
-// lime_token_attention_bwd*_f32 backward entries, one pure route per direction) and the units that own the kernels: one launcher per
+// Between the fp32 token-attention routing (token_attn_f32.hip: lime_token_attention_f32 and lime_token_attention_bwd_f32, each taking
+// its argument block, one pure route per direction) and the units that own the kernels: one launcher per
 // family, which runs the instantiation the route chose and decides nothing itself.  A choice outside the table of built
 // instantiations is LIME_ERR_UNSUPPORTED with a message, as in gemm_pp.h.
 #pragma once
@@ -13,9 +13,9 @@
 struct LimeAttnRoute { int family, n; bool fast, map; int stats; };
 
 // Pure: a function of the block (pointers: NULL-ness and alignment only) and the split mode; no HIP call.  LIME_OK with r->family set
-// (LIME_ATTN_NONE: nothing to launch), LIME_NOT_APPLICABLE (vocab form), or the entry's refusal.
+// (LIME_ATTN_NONE: nothing to launch), LIME_NOT_APPLICABLE (vocab form), or the form's refusal.
 int lime_attn_route(const lime_token_attention_args& a, int split_mode, LimeAttnRoute* r);
-const char* lime_attn_entry(int form);                // the name the form's messages carry
+const char* lime_attn_entry(int form);                // the historical name the form's messages carry
 static inline LimeDropout lime_attn_dropout(const lime_token_attention_args& a) {
     return a.form == LIME_ATTN_FORM_DROPOUT ? lime_make_dropout(a.dropout_p, a.dropout_seed, a.dropout_site) : LimeDropout{0, 0, 1.f};
 }
@@ -31,10 +31,10 @@ int lime_attn_wide_limits(const char* entry, int S, int n_head, int hd, int hs, 
 // launch in front of a blocked kernel; reduce: attn_dq_reduce_kernel follows it.
 struct LimeAttnBwdRoute { int family, n, pass; bool reduce; };
 
-// Pure, as lime_attn_route: LIME_OK with r->family set (LIME_BWD_ATTN_NONE: nothing to launch), or the refusal of the entry a.entry names.
+// Pure, as lime_attn_route: LIME_OK with r->family set (LIME_BWD_ATTN_NONE: nothing to launch), or the refusal of the form a.entry names.
 int lime_attn_bwd_route(const lime_token_attention_bwd_args& a, int split_mode, LimeAttnBwdRoute* r);
 static inline LimeDropout lime_attn_bwd_dropout(const lime_token_attention_bwd_args& a) {
-    return lime_make_dropout(a.dropout_p, a.dropout_seed, a.dropout_site);       // the lse entry's block holds p = 0
+    return lime_make_dropout(a.dropout_p, a.dropout_seed, a.dropout_site);       // the lse form's block holds p = 0
 }
 // token_attn_train_f32.hip: the blocked backward's workspace, stated once for the size query, the route's check and the launch -- the row
 // statistics (lse and delta per (token, head)) in its first `stats` floats, behind them one [tokens][n_head * 32] dq slab per key block

@@ -519,9 +519,9 @@ int lime_attn_mfma_launch(const LimeAttnRoute& r, const lime_token_attention_arg
     return r.fast ? launch_nt<true, false, false>(r.n, p, s, entry) : launch_nt<false, false, false>(r.n, p, s, entry);
 }
 
-// ---- The fp32 forward: its six entries, the checks they share and the one pure route that chooses the kernel.
-// An entry fills the argument block; attention_forward() routes it and hands the route to the unit that owns the kernel
-// (token_attn.h).  lime_token_attention_plan_f32 returns the same decision as data.
+// ---- The fp32 forward: the one pure route that makes every form's checks and chooses the kernel.  The caller
+// fills the argument block; lime_token_attention_f32 routes it and hands the route to the unit that owns the kernel (token_attn.h),
+// lime_token_attention_plan_f32 returns the same decision as data.
 
 enum { PLAIN = LIME_ATTN_FORM_PLAIN, COUNT = LIME_ATTN_FORM_COUNT, LSE = LIME_ATTN_FORM_LSE, ROWS = LIME_ATTN_FORM_ROWS,
        VOCAB = LIME_ATTN_FORM_VOCAB, DROPOUT = LIME_ATTN_FORM_DROPOUT };
@@ -529,7 +529,7 @@ enum { PLAIN = LIME_ATTN_FORM_PLAIN, COUNT = LIME_ATTN_FORM_COUNT, LSE = LIME_AT
 const char* lime_attn_entry(int form) {
     static const char* const names[] = {"lime_token_attention_count_f32", "lime_token_attention_count_f32", "lime_token_attention_lse_f32",
                                         "lime_token_attention_rows_f32", "lime_token_attention_vocab_f32", "lime_token_attention_dropout_f32"};
-    return names[form];          // lime_token_attention_f32 is the count entry without a count, and reports as it
+    return names[form];          // the names the forms had as entries of their own; plain is count without a count, and reports as it
 }
 
 int lime_attn_route(const lime_token_attention_args& a, int split_mode, LimeAttnRoute* r) {
@@ -640,29 +640,6 @@ void route_name(const LimeAttnRoute& r, int which, char* buf, size_t n) {
     }
 }
 
-int attention_forward(const lime_token_attention_args& a, void* stream) {
-    LimeAttnRoute r;
-    const int st = lime_attn_route(a, lime_split_mode(), &r);
-    if (st != LIME_OK) return st;
-    switch (r.family) {
-        case LIME_ATTN_NONE: return LIME_OK;
-        case LIME_ATTN_SP: case LIME_ATTN_SP_LONG: case LIME_ATTN_SP_VOCAB: return lime_attn_sp_launch(r, a, (hipStream_t)stream);
-        case LIME_ATTN_MFMA: return lime_attn_mfma_launch(r, a, (hipStream_t)stream);
-        case LIME_ATTN_WIDE: return lime_attn_wide_launch(r, a, (hipStream_t)stream);
-        default: return lime_attn_dropout_launch(r, a, (hipStream_t)stream);
-    }
-}
-
-// the fields every form has
-lime_token_attention_args block(int form, const float* q, const float* k, const float* v, int64_t ld, float* out, int64_t ldo, int32_t n_seq,
-                                int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride, float scale) {
-    lime_token_attention_args a = {};
-    a.form = form;
-    a.q = q; a.k = k; a.v = v; a.ld_qkv = ld; a.out = out; a.ldo = ldo;
-    a.n_seq = n_seq; a.S = S; a.n_head = n_head; a.head_dim = head_dim; a.head_stride = head_stride; a.scale = scale;
-    return a;
-}
-
 }  // namespace
 
 extern "C" int lime_token_attention_plan_f32(const lime_token_attention_args* args, lime_token_attention_plan* out) {
@@ -680,61 +657,23 @@ extern "C" int lime_token_attention_plan_f32(const lime_token_attention_args* ar
     return LIME_OK;
 }
 
-extern "C" int lime_token_attention_count_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask,
-                                              const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                              int32_t head_dim, int32_t head_stride, float scale, void* stream) {
-    lime_token_attention_args a = block(COUNT, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
-    a.key_mask = key_mask; a.n_seq_dev = n_seq_dev;
-    return attention_forward(a, stream);
+extern "C" int lime_token_attention_f32(const lime_token_attention_args* args, void* stream) {
+    LIME_REQUIRE(args != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_f32: args is NULL");
+    LIME_REQUIRE(args->form >= PLAIN && args->form <= DROPOUT, LIME_ERR_BAD_ARG, "lime_token_attention_f32: form %d", args->form);
+    LimeAttnRoute r;
+    const int st = lime_attn_route(*args, lime_split_mode(), &r);
+    if (st != LIME_OK) return st;
+    switch (r.family) {
+        case LIME_ATTN_NONE: return LIME_OK;
+        case LIME_ATTN_SP: case LIME_ATTN_SP_LONG: case LIME_ATTN_SP_VOCAB: return lime_attn_sp_launch(r, *args, (hipStream_t)stream);
+        case LIME_ATTN_MFMA: return lime_attn_mfma_launch(r, *args, (hipStream_t)stream);
+        case LIME_ATTN_WIDE: return lime_attn_wide_launch(r, *args, (hipStream_t)stream);
+        default: return lime_attn_dropout_launch(r, *args, (hipStream_t)stream);
+    }
 }
 
-extern "C" int lime_token_attention_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const uint8_t* key_mask, float* out,
-                                        int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
-                                        float scale, void* stream) {
-    lime_token_attention_args a = block(PLAIN, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
-    a.key_mask = key_mask;
-    return attention_forward(a, stream);
-}
-
-extern "C" int lime_token_attention_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
-                                            float* lse, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
-                                            float scale, void* stream) {
-    lime_token_attention_args a = block(LSE, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
-    a.lse = lse;
-    return attention_forward(a, stream);
-}
-
-extern "C" int lime_token_attention_rows_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const int32_t* row_map,
-                                             const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                             int32_t head_dim, float scale, void* stream) {
-    lime_token_attention_args a = block(ROWS, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, 32, scale);
-    a.row_map = row_map; a.n_seq_dev = n_seq_dev;
-    return attention_forward(a, stream);
-}
-
-// The first encoder layer over a per-vocabulary in_proj product (token_attn_sp_f32.hip's header, include/lime_hip.h): q | k | v sit
-// side by side in the table's rows, the word ids take the row map's place.
-extern "C" int lime_token_attention_vocab_f32(const float* qkv_vocab, int64_t ld, const float* pos_rows, const int32_t* ids,
-                                              const int32_t* n_seq_dev, float* out, int64_t ldo, int32_t n_seq, int32_t S, int32_t n_head,
-                                              int32_t head_dim, float scale, void* stream) {
-    const int64_t W = (int64_t)n_head * 32;
-    lime_token_attention_args a = block(VOCAB, qkv_vocab, qkv_vocab ? qkv_vocab + W : nullptr, qkv_vocab ? qkv_vocab + 2 * W : nullptr, ld,
-                                        out, ldo, n_seq, S, n_head, head_dim, 32, scale);
-    a.pos_rows = pos_rows; a.row_map = ids; a.n_seq_dev = n_seq_dev;
-    return attention_forward(a, stream);
-}
-
-extern "C" int lime_token_attention_dropout_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, float* out, int64_t ldo,
-                                                int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim, int32_t head_stride,
-                                                float scale, float dropout_p, uint64_t seed, uint32_t site, float* workspace,
-                                                int64_t workspace_floats, void* stream) {
-    lime_token_attention_args a = block(DROPOUT, q, k, v, ld_qkv, out, ldo, n_seq, S, n_head, head_dim, head_stride, scale);
-    a.dropout_p = dropout_p; a.dropout_seed = seed; a.dropout_site = site; a.workspace = workspace; a.workspace_floats = workspace_floats;
-    return attention_forward(a, stream);
-}
-
-// ---- The fp32 backward: its two entries and the one pure route that makes their checks and chooses the kernels (DESIGN.md section
-// 5.5), as above.  lime_token_attention_bwd_plan_f32 returns the same decision as data.
+// ---- The fp32 backward: the one pure route that makes both forms' checks and chooses the kernels, as above.
+// lime_token_attention_bwd_plan_f32 returns the same decision as data.
 
 int lime_attn_bwd_route(const lime_token_attention_bwd_args& a, int split_mode, LimeAttnBwdRoute* r) {
     *r = LimeAttnBwdRoute{LIME_BWD_ATTN_NONE, 0, LIME_BWD_ATTN_PASS_NONE, false};
@@ -816,18 +755,6 @@ int bwd_route_names(const LimeAttnBwdRoute& r, char (*name)[64]) {
     return n;
 }
 
-int attention_backward(const lime_token_attention_bwd_args& a, void* stream) {
-    LimeAttnBwdRoute r;
-    const int st = lime_attn_bwd_route(a, lime_split_mode(), &r);
-    if (st != LIME_OK) return st;
-    switch (r.family) {
-        case LIME_BWD_ATTN_NONE: return LIME_OK;
-        case LIME_BWD_ATTN_SP: return lime_attn_bwd_sp_launch(r, a, (hipStream_t)stream);
-        case LIME_BWD_ATTN_WIDE: return lime_attn_bwd_wide_launch(r, a, (hipStream_t)stream);
-        default: return lime_attn_bwd_launch(r, a, (hipStream_t)stream);
-    }
-}
-
 }  // namespace
 
 extern "C" int lime_token_attention_bwd_plan_f32(const lime_token_attention_bwd_args* args, lime_token_attention_bwd_plan* out) {
@@ -845,24 +772,19 @@ extern "C" int lime_token_attention_bwd_plan_f32(const lime_token_attention_bwd_
     return LIME_OK;
 }
 
-extern "C" int lime_token_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
-                                            int64_t ld_out, const float* dout, int64_t ldo, float* dq, float* dk, float* dv,
-                                            int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
-                                            int32_t head_stride, float scale, float* workspace, int64_t workspace_floats,
-                                            float dropout_p, uint64_t seed, uint32_t site, const uint8_t* key_mask, void* stream) {
-    const lime_token_attention_bwd_args a = {q, k, v, ld_qkv, out, ld_out, nullptr, dout, ldo, dq, dk, dv, ld_dqkv, workspace, workspace_floats,
-                                             key_mask, seed, dropout_p, site, n_seq, S, n_head, head_dim, head_stride, scale,
-                                             LIME_BWD_ATTN_ENTRY_PLAIN, 0};
-    return attention_backward(a, stream);
-}
-
-extern "C" int lime_token_attention_bwd_lse_f32(const float* q, const float* k, const float* v, int64_t ld_qkv, const float* out,
-                                                int64_t ld_out, const float* lse, const float* dout, int64_t ldo, float* dq, float* dk,
-                                                float* dv, int64_t ld_dqkv, int32_t n_seq, int32_t S, int32_t n_head, int32_t head_dim,
-                                                int32_t head_stride, float scale, float* workspace, int64_t workspace_floats, void* stream) {
-    const lime_token_attention_bwd_args a = {q, k, v, ld_qkv, out, ld_out, lse, dout, ldo, dq, dk, dv, ld_dqkv, workspace, workspace_floats,
-                                             nullptr, 0, 0.f, 0, n_seq, S, n_head, head_dim, head_stride, scale, LIME_BWD_ATTN_ENTRY_LSE, 0};
-    return attention_backward(a, stream);
+extern "C" int lime_token_attention_bwd_f32(const lime_token_attention_bwd_args* args, void* stream) {
+    LIME_REQUIRE(args != nullptr, LIME_ERR_BAD_ARG, "lime_token_attention_bwd_f32: args is NULL");
+    LIME_REQUIRE(args->entry == LIME_BWD_ATTN_ENTRY_PLAIN || args->entry == LIME_BWD_ATTN_ENTRY_LSE, LIME_ERR_BAD_ARG,
+                 "lime_token_attention_bwd_f32: entry %d", args->entry);
+    LimeAttnBwdRoute r;
+    const int st = lime_attn_bwd_route(*args, lime_split_mode(), &r);
+    if (st != LIME_OK) return st;
+    switch (r.family) {
+        case LIME_BWD_ATTN_NONE: return LIME_OK;
+        case LIME_BWD_ATTN_SP: return lime_attn_bwd_sp_launch(r, *args, (hipStream_t)stream);
+        case LIME_BWD_ATTN_WIDE: return lime_attn_bwd_wide_launch(r, *args, (hipStream_t)stream);
+        default: return lime_attn_bwd_launch(r, *args, (hipStream_t)stream);
+    }
 }
 
 int lime_token_attention_bf16_mfma(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t ld_qkv, uint16_t* out, int64_t ldo,

@@ -1,4 +1,4 @@
-// lime_token_attention_f32 / lime_token_attention_rows_f32 on the bf16 matrix cores with fp32-level arithmetic (the "split product" of
+// lime_token_attention_f32 (the dense forms and the rows form) on the bf16 matrix cores with fp32-level arithmetic (the "split product" of
 // gemm_sp_f32.hip): the unmasked shapes of the encoder layers (S = 32, 64 or 128 tokens per sequence, heads 32 columns apart).
 //
 // Structure as token_attn_f32.hip -- persistent four-wave workgroups over groups of (sequence, head) pairs, K / V of the next group
@@ -14,7 +14,7 @@
 //     of a lane = keys 16 s + {0..3, 8..11} + 4 half), and the V image stores its keys in that order (bits 2 and 3 of the key swapped).
 // The softmax (log2 domain, v_exp_f32) and the output transpose are those of token_attn_f32.hip.
 //
-// lime_token_attention_vocab_f32 (token_attn_sp_vocab_kernel): the first encoder layer over a per-vocabulary in_proj product.  The
+// Its vocab form (token_attn_sp_vocab_kernel): the first encoder layer over a per-vocabulary in_proj product.  The
 // operand row of token r = seq S + t is row ids[r] of a [V, ld] table (q | k | v at columns 0, W, 2W) plus row t of an [S, ld]
 // positional table: one fp32 add per element where the fragment is consumed (stash() for K / V, before the qscale multiply for Q), so
 // the result is bit for bit that of the dense kernel over the materialised rows.
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_vocab_kernel(const SpAtt
 // 128 queries (a wave per 32-query tile, its Q split once); the keys go through LDS in blocks of 128 -- K / V images as above, the
 // next block's rows prefetched into registers -- with a running maximum: o and the probability sum are rescaled by 2^(m_old - m_new)
 // when a block raises the maximum.  Optionally writes the log2-domain log-sum-exp of every query (p.lse: what the blocked backward
-// needs, lime_token_attention_lse_f32).
+// needs, the lse form).
 template <bool MAP>
 __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttnP p, float* __restrict__ lse) {
     constexpr int SP = 128, VP = SP + 8;

@@ -1,6 +1,6 @@
-// The token attention that only training runs: the fp32 kernels of lime_token_attention_bwd_f32 / _bwd_lse_f32 (dQ / dK / dV of
-// softmax(scale Q K^T) V per (sequence, head), probabilities recomputed) and of lime_token_attention_dropout_f32 (the forward with
-// probability dropout).  The entries, their checks and the choice among these kernels: token_attn_f32.hip (one pure route per direction).
+// The token attention that only training runs: the fp32 kernels of lime_token_attention_bwd_f32 (dQ / dK / dV of
+// softmax(scale Q K^T) V per (sequence, head), probabilities recomputed) and of lime_token_attention_f32's dropout form (the forward with
+// probability dropout).  The two entries, the checks and the choice among these kernels: token_attn_f32.hip (one pure route per direction).
 //
 //   S <= 128   token_attn_bwd_kernel<SP>, token_attn_fwd_dropout_kernel<SP>: one pass, fp32 MFMA (64 < S <= 128 without a key mask: the
 //              split-product backward of token_attn_bwd_sp_f32.hip, and the forward of token_attn_sp_f32.hip, come first)
@@ -923,7 +923,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_long_sp_kernel(const float* _
 }
 
 // stats[(token, head)] = (lse from the forward, delta = dO . O): the statistics pass without its Q K^T products, for a forward that
-// kept its log-sum-exp (lime_token_attention_lse_f32)
+// kept its log-sum-exp (the forward's lse form)
 __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict__ out, long ldout, const float* __restrict__ dout, long ldo,
                                                           const float* __restrict__ lse, float* __restrict__ stats, long n_tok, int n_head,
                                                           int head_dim) {

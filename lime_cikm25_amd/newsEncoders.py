@@ -727,7 +727,7 @@ def _encode_layers(r, table, pe, transformer, nhead, pooled_out, blocks_only=Fal
         if qkv is None:
             attn = ops.token_attention_vocab(r.ew, r.pew, r.res_ids, r.n_seq_dev, n_seq, S, nhead, hd, scale)
             if attn is None:
-                raise RuntimeError('lime_token_attention_vocab_f32 does not cover S = %d, head_dim = %d (vocab_qkv_applicable said it would)' % (S, hd))
+                raise RuntimeError('the vocab form of lime_token_attention_f32 does not cover S = %d, head_dim = %d (vocab_qkv_applicable said it would)' % (S, hd))
         elif r.row_map is None:
             attn = ops.token_attention(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], n_seq, S, nhead, hd, scale, head_stride=hs)
         else:
@@ -1081,7 +1081,7 @@ def weight_state_stale(recorded, current):
 
 
 def vocab_qkv_applicable(S, E, nhead):
-    """``lime_token_attention_vocab_f32`` covers the first layer of a token encoder over S-token sequences."""
+    """The vocab form of ``lime_token_attention_f32`` covers the first layer of a token encoder over S-token sequences."""
     return S in (32, 64, 128) and E % nhead == 0 and E // nhead <= 32 and E % 4 == 0
 
 

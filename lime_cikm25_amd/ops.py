@@ -253,101 +253,118 @@ def embed_pe(ids, table, pe=None, period=0, out=None):
     return out
 
 
+NOT_APPLICABLE = _lib.CONSTANTS['LIME_NOT_APPLICABLE']
+
+
+def _token_attention_block(form, q=None, k=None, v=None, n_seq=0, S=0, n_head=0, head_dim=0, scale=1.0, key_mask=None, out=None,
+                           head_stride=None, n_seq_dev=None, lse=None, row_map=None, qkv_vocab=None, pos_rows=None, ids=None, p=0.0,
+                           seed=0, site=0):
+    """(lime_token_attention_args, out, what the block points into and nobody else holds) for the arguments of the fp32 forward wrapper
+    of ``form`` ('plain' / 'count' / 'lse': ``token_attention``; 'rows': ``token_attention_rows``; 'vocab': ``token_attention_vocab``;
+    'dropout': ``token_attention_dropout``): that wrapper's operand checks, the output where none was given and the dropout form's
+    workspace, for the call and for its plan."""
+    lib = _lib.load()
+    a = _lib.TokenAttentionArgs()
+    a.form = _lib.ATTN_FORM[form]
+    hs = 32 if form in ('rows', 'vocab') else (head_dim if head_stride is None else head_stride)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    mask = ws = None
+    if form == 'vocab':
+        _mat(qkv_vocab, 'qkv_vocab')
+        _mat(pos_rows, 'pos_rows')
+        W = n_head * 32
+        if qkv_vocab.shape[1] != 3 * W or pos_rows.shape[1] != 3 * W or _ld(qkv_vocab) != _ld(pos_rows):
+            raise ValueError('qkv_vocab and pos_rows must have 3 * n_head * 32 columns and one leading dimension')
+        if pos_rows.shape[0] < S:
+            raise ValueError('pos_rows must have at least S rows')
+        _vec(ids, 'ids', dtype=torch.int32)
+        if ids.numel() < n_seq * S:
+            raise ValueError('ids must cover n_seq * S tokens')
+        a.q, a.k, a.v = (qkv_vocab.data_ptr() + 4 * W * i for i in range(3))          # q | k | v side by side in the table's rows
+        a.ld_qkv, a.pos_rows, a.row_map, device = _ld(qkv_vocab), ptr(pos_rows), ptr(ids), qkv_vocab.device
+    else:
+        for t, n in ((q, 'q'), (k, 'k'), (v, 'v')):
+            _mat(t, n)
+            if form == 'rows':
+                if t.shape[1] != n_head * 32:
+                    raise ValueError('%s must have n_head * 32 columns' % n)
+            elif tuple(t.shape) != (n_seq * S, n_head * hs):
+                raise ValueError('%s must be [n_seq * S, n_head * head_stride]' % n if form == 'dropout' else
+                                 '%s must be [%d, %d]' % (n, n_seq * S, n_head * hs))
+        if not (_ld(q) == _ld(k) == _ld(v)):
+            raise ValueError('q, k, v must share one leading dimension' if form == 'dropout' else 'q, k and v must share one leading dimension')
+        a.q, a.k, a.v, a.ld_qkv, device = ptr(q), ptr(k), ptr(v), _ld(q), q.device
+    if form == 'rows':
+        _vec(row_map, 'row_map', dtype=torch.int32)
+        if row_map.numel() < n_seq * S:
+            raise ValueError('row_map must cover n_seq * S tokens')
+        a.row_map = ptr(row_map)
+    if form in ('rows', 'vocab', 'count') and n_seq_dev is not None:           # a compacted batch: the sequence count lives on the device
+        a.n_seq_dev = ptr(_vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32))
+    if out is None:
+        out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=device)
+    _mat(out, 'out')
+    if form == 'vocab' and (out.shape[0] != n_seq * S or out.shape[1] != n_head * head_dim):
+        raise ValueError('out must be [n_seq * S, n_head * head_dim]')
+    if form in ('plain', 'count', 'lse'):
+        mask = _mask_u8(key_mask, 'key_mask')
+        if mask is not None and mask.numel() != n_seq * S:
+            raise ValueError('key_mask must have n_seq * S elements')
+        if form == 'lse':
+            if mask is not None or n_seq_dev is not None:
+                raise ValueError('lse goes with the unmasked, host-counted call')
+            a.lse = ptr(_vec(lse, 'lse', n_seq * S * n_head))
+        a.key_mask = ptr(mask)
+    if form == 'dropout':
+        need = 0 if head_dim > 32 else lib.lime_token_attention_stats_workspace(n_seq, S, n_head)      # the wide heads run in one pass
+        ws = _workspace(device, need) if need else None
+        a.workspace, a.workspace_floats = ptr(ws), ws.numel() if ws is not None else 0
+        a.dropout_p, a.dropout_seed, a.dropout_site = p, seed, site
+    a.out, a.ldo = out.data_ptr(), _ld(out)
+    a.n_seq, a.S, a.n_head, a.head_dim, a.head_stride, a.scale = n_seq, S, n_head, head_dim, hs, scale
+    return a, out, (mask, ws)
+
+
+def _token_attention(form, **kw):
+    """The one forward call: ``lime_token_attention_f32`` over the block of ``form``'s wrapper arguments.  None where the vocab form
+    does not cover the call (nothing was launched)."""
+    a, out, _keep = _token_attention_block(form, **kw)
+    st = _lib.load().lime_token_attention_f32(ctypes.byref(a), _stream())
+    if st == NOT_APPLICABLE:
+        return None
+    check(st, 'lime_token_attention_f32')
+    return out
+
+
 def token_attention(q, k, v, n_seq, S, n_head, head_dim, scale, key_mask=None, out=None, head_stride=None, n_seq_dev=None, lse=None):
     """softmax(Q K^T * scale [+mask]) V per (sequence, head); q/k/v: [n_seq*S, n_head*head_stride] views of one pitch
     (head_stride defaults to head_dim, the packed layout); out: [n_seq*S, n_head*head_dim].  ``lse`` (float32 [n_seq*S * n_head], no
     mask): also filled with the softmax statistics ``token_attention_bwd(..., lse=lse)`` reads instead of recomputing them.
+    ``n_seq_dev`` (int32 device tensor, 1 element): a compacted batch, whose sequence count lives on the device.
     S <= 512 and either head_dim <= 32 (any head_dim, any head_stride >= head_dim) or the wide heads 32 < head_dim <= 128 with
     head_dim % 4 == 0, head_stride % 4 == 0, leading dimensions that are multiples of 4 and 16-byte aligned tensors."""
-    lib = _lib.load()
-    hs = head_dim if head_stride is None else head_stride
-    for t, n in ((q, 'q'), (k, 'k'), (v, 'v')):
-        _mat(t, n)
-        if tuple(t.shape) != (n_seq * S, n_head * hs):
-            raise ValueError('%s must be [%d, %d]' % (n, n_seq * S, n_head * hs))
-    if not (_ld(q) == _ld(k) == _ld(v)):
-        raise ValueError('q, k and v must share one leading dimension')
-    if out is None:
-        out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=q.device)
-    _mat(out, 'out')
-    m = _mask_u8(key_mask, 'key_mask')
-    if m is not None and m.numel() != n_seq * S:
-        raise ValueError('key_mask must have n_seq * S elements')
-    if lse is not None:
-        if m is not None or n_seq_dev is not None:
-            raise ValueError('lse goes with the unmasked, host-counted call')
-        _vec(lse, 'lse', n_seq * S * n_head)
-        check(lib.lime_token_attention_lse_f32(_p(q), _p(k), _p(v), _ld(q), _p(out), _ld(out), _p(lse), n_seq, S, n_head, head_dim, hs,
-                                               scale, _stream()), 'lime_token_attention_lse_f32')
-        return out
-    if n_seq_dev is not None:                      # a compacted batch: the sequence count lives on the device
-        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
-        check(lib.lime_token_attention_count_f32(_p(q), _p(k), _p(v), _ld(q), _p(m), _p(n_seq_dev), _p(out), _ld(out), n_seq, S, n_head,
-                                                 head_dim, hs, scale, _stream()), 'lime_token_attention_count_f32')
-        return out
-    check(lib.lime_token_attention_f32(_p(q), _p(k), _p(v), _ld(q), _p(m), _p(out), _ld(out), n_seq, S, n_head, head_dim, hs,
-                                       scale, _stream()), 'lime_token_attention_f32')
-    return out
+    form = 'lse' if lse is not None else ('count' if n_seq_dev is not None else 'plain')
+    return _token_attention(form, q=q, k=k, v=v, n_seq=n_seq, S=S, n_head=n_head, head_dim=head_dim, scale=scale, key_mask=key_mask,
+                            out=out, head_stride=head_stride, n_seq_dev=n_seq_dev, lse=lse)
 
 
 def token_attention_rows(q, k, v, row_map, n_seq_dev, n_seq, S, n_head, head_dim, scale, out=None):
-    """``lime_token_attention_rows_f32``: attention over compacted sequences.  q / k / v: column views (heads 32 columns apart) of
-    one buffer that also holds the S rows shared by the padding tokens; row_map: int32 [n_seq * S] -> row of that buffer;
+    """The rows form of ``lime_token_attention_f32``: attention over compacted sequences.  q / k / v: column views (heads 32 columns
+    apart) of one buffer that also holds the S rows shared by the padding tokens; row_map: int32 [n_seq * S] -> row of that buffer;
     n_seq_dev: int32 device tensor (1 element) or None; out: [n_seq * S, n_head * head_dim] (rows of sequences beyond the
     device count are left untouched)."""
-    lib = _lib.load()
-    for t, n in ((q, 'q'), (k, 'k'), (v, 'v')):
-        _mat(t, n)
-        if t.shape[1] != n_head * 32:
-            raise ValueError('%s must have n_head * 32 columns' % n)
-    if not (_ld(q) == _ld(k) == _ld(v)):
-        raise ValueError('q, k and v must share one leading dimension')
-    _vec(row_map, 'row_map', dtype=torch.int32)
-    if row_map.numel() < n_seq * S:
-        raise ValueError('row_map must cover n_seq * S tokens')
-    if n_seq_dev is not None:
-        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
-    if out is None:
-        out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=q.device)
-    _mat(out, 'out')
-    check(lib.lime_token_attention_rows_f32(_p(q), _p(k), _p(v), _ld(q), _p(row_map), _p(n_seq_dev), _p(out), _ld(out), n_seq, S,
-                                            n_head, head_dim, scale, _stream()), 'lime_token_attention_rows_f32')
-    return out
-
-
-NOT_APPLICABLE = _lib.CONSTANTS['LIME_NOT_APPLICABLE']
+    return _token_attention('rows', q=q, k=k, v=v, row_map=row_map, n_seq_dev=n_seq_dev, n_seq=n_seq, S=S, n_head=n_head,
+                            head_dim=head_dim, scale=scale, out=out)
 
 
 def token_attention_vocab(qkv_vocab, pos_rows, ids, n_seq_dev, n_seq, S, n_head, head_dim, scale, out=None):
-    """``lime_token_attention_vocab_f32``: the first encoder layer's attention over a per-vocabulary in_proj product.  qkv_vocab:
-    [V, 3 * n_head * 32] (q | k | v, heads 32 columns apart); pos_rows: [>= S, same columns]; ids: int32 [>= n_seq * S] word ids
-    (unchecked in [0, V)); the q / k / v row of token (seq, t) is ``qkv_vocab[ids[seq * S + t]] + pos_rows[t]``.  n_seq_dev as in
-    ``token_attention_rows``.  Returns ``out`` [n_seq * S, n_head * head_dim], or None when the entry does not cover the call (the
+    """The vocab form of ``lime_token_attention_f32``: the first encoder layer's attention over a per-vocabulary in_proj product.
+    qkv_vocab: [V, 3 * n_head * 32] (q | k | v, heads 32 columns apart); pos_rows: [>= S, same columns]; ids: int32 [>= n_seq * S] word
+    ids (unchecked in [0, V)); the q / k / v row of token (seq, t) is ``qkv_vocab[ids[seq * S + t]] + pos_rows[t]``.  n_seq_dev as in
+    ``token_attention_rows``.  Returns ``out`` [n_seq * S, n_head * head_dim], or None when the form does not cover the call (the
     split product switched off, S outside {32, 64, 128}, head_dim > 32): nothing was launched, the caller keeps the in_proj path."""
-    lib = _lib.load()
-    _mat(qkv_vocab, 'qkv_vocab')
-    _mat(pos_rows, 'pos_rows')
-    W = n_head * 32
-    if qkv_vocab.shape[1] != 3 * W or pos_rows.shape[1] != 3 * W or _ld(qkv_vocab) != _ld(pos_rows):
-        raise ValueError('qkv_vocab and pos_rows must have 3 * n_head * 32 columns and one leading dimension')
-    if pos_rows.shape[0] < S:
-        raise ValueError('pos_rows must have at least S rows')
-    _vec(ids, 'ids', dtype=torch.int32)
-    if ids.numel() < n_seq * S:
-        raise ValueError('ids must cover n_seq * S tokens')
-    if n_seq_dev is not None:
-        _vec(n_seq_dev, 'n_seq_dev', 1, dtype=torch.int32)
-    if out is None:
-        out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=qkv_vocab.device)
-    _mat(out, 'out')
-    if out.shape[0] != n_seq * S or out.shape[1] != n_head * head_dim:
-        raise ValueError('out must be [n_seq * S, n_head * head_dim]')
-    st = lib.lime_token_attention_vocab_f32(_p(qkv_vocab), _ld(qkv_vocab), _p(pos_rows), _p(ids), _p(n_seq_dev), _p(out), _ld(out), n_seq, S,
-                                            n_head, head_dim, scale, _stream())
-    if st == NOT_APPLICABLE:
-        return None
-    check(st, 'lime_token_attention_vocab_f32')
-    return out
+    return _token_attention('vocab', qkv_vocab=qkv_vocab, pos_rows=pos_rows, ids=ids, n_seq_dev=n_seq_dev, n_seq=n_seq, S=S, n_head=n_head,
+                            head_dim=head_dim, scale=scale, out=out)
 
 
 def token_attention_plan(form, q=None, k=None, v=None, n_seq=0, S=0, n_head=0, head_dim=0, scale=1.0, key_mask=None, out=None,
@@ -357,28 +374,11 @@ def token_attention_plan(form, q=None, k=None, v=None, n_seq=0, S=0, n_head=0, h
     'vocab': ``token_attention_vocab``; 'dropout': ``token_attention_dropout``) would run for the same arguments, without running it
     (``lime_token_attention_plan_f32``): a dict with ``family`` ('sp', 'sp_long', 'sp_vocab', 'mfma', 'wide', 'dropout',
     'dropout_long'; None where nothing is launched), ``stats_pass`` (None / 'fp32' / 'split') and ``kernels`` (the instantiations in
-    launch order, as rocprofv3 prints them).  None where the vocab form does not cover the call; a call the entry would refuse raises the
-    same LimeHipError.  The tensors' shapes are not checked here: only their addresses and leading dimensions reach the plan."""
-    a = _lib.TokenAttentionArgs()
-    a.form = _lib.ATTN_FORM[form]
-    a.n_seq, a.S, a.n_head, a.head_dim, a.scale = n_seq, S, n_head, head_dim, scale
-    a.head_stride = 32 if form in ('rows', 'vocab') else (head_dim if head_stride is None else head_stride)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    if form == 'vocab':
-        W = n_head * 32
-        a.q, a.k, a.v = (qkv_vocab.data_ptr() + 4 * W * i for i in range(3))
-        a.ld_qkv, a.pos_rows, a.row_map = _ld(qkv_vocab), ptr(pos_rows), ptr(ids)
-    else:
-        a.q, a.k, a.v, a.ld_qkv, a.row_map = ptr(q), ptr(k), ptr(v), _ld(q), ptr(row_map)
-    if out is None:                                     # the wrappers allocate it: any aligned address stands for it
-        a.out, a.ldo = 256, n_head * head_dim
-    else:
-        a.out, a.ldo = out.data_ptr(), _ld(out)
-    a.key_mask, a.n_seq_dev, a.lse = ptr(_mask_u8(key_mask, 'key_mask')), ptr(n_seq_dev), ptr(lse)
-    if form == 'dropout':
-        a.dropout_p, a.dropout_seed, a.dropout_site = p, seed, site
-        a.workspace_floats = 0 if head_dim > 32 else _lib.load().lime_token_attention_stats_workspace(n_seq, S, n_head)
-        a.workspace = 256 if a.workspace_floats else None
+    launch order, as rocprofv3 prints them).  None where the vocab form does not cover the call; a call the wrapper or the library would
+    refuse raises the same error."""
+    a, _out, _keep = _token_attention_block(form, q=q, k=k, v=v, n_seq=n_seq, S=S, n_head=n_head, head_dim=head_dim, scale=scale,
+                                            key_mask=key_mask, out=out, head_stride=head_stride, n_seq_dev=n_seq_dev, lse=lse,
+                                            row_map=row_map, qkv_vocab=qkv_vocab, pos_rows=pos_rows, ids=ids, p=p, seed=seed, site=site)
     plan = _lib.TokenAttentionPlan()
     st = _lib.load().lime_token_attention_plan_f32(ctypes.byref(a), ctypes.byref(plan))
     if st == NOT_APPLICABLE:
@@ -1678,7 +1678,7 @@ def relu_bwd_(dh, h, scale=1.0):
 
 def _token_attention_bwd_block(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride, dqkv, out, dropout, key_mask, lse):
     """(lime_token_attention_bwd_args, dqkv, what the block points into and nobody else holds) for ``token_attention_bwd``'s arguments: the operand checks,
-    the workspace and the choice between the two C entries, for the call and for its plan."""
+    the workspace and the choice between the entry's two forms, for the call and for its plan."""
     lib = _lib.load()
     hs = head_dim if head_stride is None else head_stride
     W = n_head * hs
@@ -1736,18 +1736,8 @@ def token_attention_bwd(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_s
     head_stride]; returns dqkv in the same layout.  ``out``: the forward's result (needed for S > 128).  ``dropout``:
     (p, seed, site) of the ``token_attention_dropout`` forward.  head_dim ranges as ``token_attention``; the wide heads
     (32 < head_dim <= 128) recompute their statistics at every S: ``out`` and ``lse`` are optional and unused there."""
-    lib = _lib.load()
     a, dqkv, _keep = _token_attention_bwd_block(q, k, v, dout, n_seq, S, n_head, head_dim, scale, head_stride, dqkv, out, dropout, key_mask, lse)
-    c = ctypes.c_void_p
-    if a.entry == _lib.BWD_ATTN_ENTRY['lse']:
-        check(lib.lime_token_attention_bwd_lse_f32(c(a.q), c(a.k), c(a.v), a.ld_qkv, c(a.out), a.ld_out, c(a.lse), c(a.dout), a.ldo, c(a.dq),
-                                                   c(a.dk), c(a.dv), a.ld_dqkv, n_seq, S, n_head, head_dim, a.head_stride, scale,
-                                                   c(a.workspace), a.workspace_floats, _stream()), 'lime_token_attention_bwd_lse_f32')
-        return dqkv
-    check(lib.lime_token_attention_bwd_f32(c(a.q), c(a.k), c(a.v), a.ld_qkv, c(a.out), a.ld_out, c(a.dout), a.ldo, c(a.dq), c(a.dk), c(a.dv),
-                                           a.ld_dqkv, n_seq, S, n_head, head_dim, a.head_stride, scale, c(a.workspace), a.workspace_floats,
-                                           a.dropout_p, a.dropout_seed, a.dropout_site, c(a.key_mask), _stream()),
-          'lime_token_attention_bwd_f32')
+    check(_lib.load().lime_token_attention_bwd_f32(ctypes.byref(a), _stream()), 'lime_token_attention_bwd_f32')
     return dqkv
 
 
@@ -1826,21 +1816,8 @@ def dropout_add_layernorm(t, res, gamma, beta, eps, p, seed, site, want_rstd=Tru
 def token_attention_dropout(q, k, v, n_seq, S, n_head, head_dim, scale, p, seed, site, head_stride=None):
     """Unmasked encoder attention with dropout on the probabilities (training mode); layouts and head_dim ranges (<= 32, or the
     wide heads up to 128) as ``token_attention``."""
-    lib = _lib.load()
-    hs = head_dim if head_stride is None else head_stride
-    for t, name in ((q, 'q'), (k, 'k'), (v, 'v')):
-        _mat(t, name)
-        if t.shape[0] != n_seq * S or t.shape[1] != n_head * hs:
-            raise ValueError('%s must be [n_seq * S, n_head * head_stride]' % name)
-    if not (_ld(q) == _ld(k) == _ld(v)):
-        raise ValueError('q, k, v must share one leading dimension')
-    out = torch.empty((n_seq * S, n_head * head_dim), dtype=torch.float32, device=q.device)
-    need = 0 if head_dim > 32 else lib.lime_token_attention_stats_workspace(n_seq, S, n_head)      # the wide heads run in one pass
-    ws = _workspace(q.device, need) if need else None
-    check(lib.lime_token_attention_dropout_f32(_p(q), _p(k), _p(v), _ld(q), _p(out), _ld(out), n_seq, S, n_head, head_dim, hs, scale,
-                                               p, seed, site, _p(ws), ws.numel() if ws is not None else 0, _stream()),
-          'lime_token_attention_dropout_f32')
-    return out
+    return _token_attention('dropout', q=q, k=k, v=v, n_seq=n_seq, S=S, n_head=n_head, head_dim=head_dim, scale=scale, p=p, seed=seed,
+                            site=site, head_stride=head_stride)
 
 
 DETERMINISTIC_EMBED_BWD = True      # word-table gradient by sort + segmented sum (no atomics); False: the float-atomic kernel

@@ -179,7 +179,16 @@ def test_bad_arguments_are_rejected_without_a_launch(lib):
     a = _lib.LinearArgs()
     assert lib.lime_linear_f32(ctypes.byref(a), None) == -1
     assert lib.lime_bucketize_f32(None, None, 4, None) == -1
-    assert lib.lime_token_attention_f32(None, None, None, 0, None, None, 0, 1, 1, 1, 1, 1, 1.0, None) == -1
+    for entry, block, field in ((lib.lime_token_attention_f32, _lib.TokenAttentionArgs, 'form'),
+                                (lib.lime_token_attention_bwd_f32, _lib.TokenAttentionBwdArgs, 'entry')):
+        assert entry(None, None) == -1
+        assert b'NULL' in lib.lime_last_error_string()
+        a = block()
+        assert entry(ctypes.byref(a), None) == -1
+        for bad in (-1, max(_lib.ATTN_FORM.values()) + 1 if field == 'form' else max(_lib.BWD_ATTN_ENTRY.values()) + 1):
+            setattr(a, field, bad)
+            assert entry(ctypes.byref(a), None) == -1
+            assert ('%s %d' % (field, bad)).encode() in lib.lime_last_error_string()
     assert lib.lime_pad_heads_f32(None, 1, None, 1, 1, 1, 1, 1, None) == -1
     assert lib.lime_multi_copy(None, 3, None) == -1
     assert lib.lime_multi_copy(None, 0, None) == 0

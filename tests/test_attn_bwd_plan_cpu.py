@@ -170,3 +170,20 @@ def test_plan_rejects_a_missing_block_and_an_unknown_entry(lib):
         a.entry = entry
         assert lib.lime_token_attention_bwd_plan_f32(ctypes.byref(a), ctypes.byref(plan)) == -1
         assert b'lime_token_attention_bwd_plan_f32: entry' in lib.lime_last_error_string()
+
+
+def test_the_run_entry_refuses_a_missing_block_before_any_launch(lib):
+    """lime_token_attention_bwd_f32 over nothing that could launch: no block, an entry outside the enum, and all-zero blocks, which the
+    first check of either entry (lse, then the operands) refuses."""
+    assert lib.lime_token_attention_bwd_f32(None, None) == -1
+    assert b'lime_token_attention_bwd_f32: args is NULL' in lib.lime_last_error_string()
+    for entry in (-1, 2):
+        a = _lib.TokenAttentionBwdArgs()
+        a.entry = entry
+        assert lib.lime_token_attention_bwd_f32(ctypes.byref(a), None) == -1
+        assert lib.lime_last_error_string().decode() == 'lime_token_attention_bwd_f32: entry %d' % entry
+    for entry, message in (('plain', 'lime_token_attention_bwd_f32: null pointer'), ('lse', 'lime_token_attention_bwd_lse_f32: lse is NULL')):
+        a = _lib.TokenAttentionBwdArgs()
+        a.entry = _lib.BWD_ATTN_ENTRY[entry]
+        assert lib.lime_token_attention_bwd_f32(ctypes.byref(a), None) == -1
+        assert lib.lime_last_error_string().decode() == message

@@ -157,3 +157,22 @@ def test_plan_rejects_a_missing_block(lib):
     assert lib.lime_token_attention_plan_f32(ctypes.byref(a), None) == -1
     a.form = 6
     assert lib.lime_token_attention_plan_f32(ctypes.byref(a), ctypes.byref(plan)) == -1
+
+
+def test_the_run_entry_refuses_a_missing_block_before_any_launch(lib):
+    """lime_token_attention_f32 over nothing that could launch: no block, a form outside the enum, and all-zero blocks, which every
+    form's first check (the operands) refuses under the form's own name."""
+    assert lib.lime_token_attention_f32(None, None) == C['LIME_ERR_BAD_ARG']
+    assert b'lime_token_attention_f32: args is NULL' in lib.lime_last_error_string()
+    for form in (-1, 6):
+        a = _lib.TokenAttentionArgs()
+        a.form = form
+        assert lib.lime_token_attention_f32(ctypes.byref(a), None) == C['LIME_ERR_BAD_ARG']
+        assert lib.lime_last_error_string().decode() == 'lime_token_attention_f32: form %d' % form
+    names = {'plain': 'count', 'count': 'count', 'lse': 'lse', 'rows': 'rows', 'vocab': 'vocab', 'dropout': 'dropout'}
+    for form in arc.FORMS:
+        a = _lib.TokenAttentionArgs()
+        a.form = _lib.ATTN_FORM[form]
+        assert lib.lime_token_attention_f32(ctypes.byref(a), None) == C['LIME_ERR_BAD_ARG'], form
+        assert lib.lime_last_error_string().decode() == 'lime_token_attention_%s_f32: %s pointer' % (
+            names[form], 'null' if form == 'dropout' else 'NULL'), form

@@ -28,8 +28,8 @@ def test_the_library_exports_the_kernel_and_header_binding_and_version_agree(lib
     # one ctypes argument per parameter of the C declaration
     params = re.search(r'\b%s\s*\((.*?)\)\s*;' % NAME, code, flags=re.S).group(1).split(',')
     assert len(params) == len(_lib.SIGNATURES[NAME][1]) == 20
-    assert lib.lime_abi_version() == _lib.ABI_VERSION == 13
-    assert int(re.search(r'#define\s+LIME_ABI_VERSION\s+(\d+)', header).group(1)) == 13
+    assert lib.lime_abi_version() == _lib.ABI_VERSION == 14
+    assert int(re.search(r'#define\s+LIME_ABI_VERSION\s+(\d+)', header).group(1)) == 14
     modes = dict(re.findall(r'LIME_OCC_(\w+)\s*=\s*(\d+)', code))
     assert {k.lower(): int(v) for k, v in modes.items()} == ops.OCC_MODES
 

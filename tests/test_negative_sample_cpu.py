@@ -149,7 +149,7 @@ def test_entry_point_refuses_bad_arguments_without_a_launch():
 
 
 def test_abi_version_is_unchanged():
-    assert _lib.ABI_VERSION == 13
+    assert _lib.ABI_VERSION == 14
     assert 'lime_negative_sample' in _lib.SIGNATURES and _lib.NEG_MAX_K == 16
 
 

@@ -147,7 +147,7 @@ def test_new_symbols_are_declared_bound_and_exported(lib):
         assert name + '(' in header
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
         assert (' T ' + name + '\n') in exported
-    assert lib.lime_abi_version() == 13 == _lib.ABI_VERSION
+    assert lib.lime_abi_version() == 14 == _lib.ABI_VERSION
 
 
 def test_new_entries_refuse_bad_arguments_without_a_launch(lib):

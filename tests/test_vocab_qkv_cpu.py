@@ -1,5 +1,7 @@
 """The staleness rule of newsEncoders.WeightProducts (weight_state / weight_state_stale: pure host functions) and the binding of the
 attention entry that reads the products.  CPU only."""
+import ctypes
+
 import torch
 import torch.nn as nn
 
@@ -55,5 +57,5 @@ def test_applicability_follows_the_native_entry():
     assert ok(32, 300, 10) and ok(64, 300, 10) and ok(128, 300, 10)
     assert not ok(96, 300, 10) and not ok(256, 300, 10) and not ok(512, 300, 10)         # the long-sequence kernel is not covered
     assert not ok(128, 400, 10)                                                           # heads wider than 32 columns
-    assert 'lime_token_attention_vocab_f32' in _lib.SIGNATURES
-    assert len(_lib.SIGNATURES['lime_token_attention_vocab_f32'][1]) == 13
+    assert 'vocab' in _lib.ATTN_FORM
+    assert _lib.SIGNATURES['lime_token_attention_f32'][1] == [ctypes.POINTER(_lib.TokenAttentionArgs), ctypes.c_void_p]

@@ -1,10 +1,10 @@
 """Diagnostic: where does token_attn_bwd_kernel spend its time?  Builds variants of token_attn_train_f32.hip with phases removed
 (-DLIME_ATTN_BWD_ABLATE=mask: 1 no global staging, 2 no S / dP MFMAs, 4 no softmax, 8 no dV, 16 no dQ / dK, 32 no stores) and
 times the body (S = 128) and title (S = 32) shapes.  64: the S / dP MFMAs run on register operands (no K / V fragment reads).
+Every variant is a whole library; the split product is switched off so that token_attn_bwd_kernel takes both shapes.
 
     python tools/attn_bwd_ablate.py
 """
-import ctypes
 import os
 import subprocess
 import sys
@@ -12,6 +12,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
+from lime_cikm25_amd import _lib, ops  # noqa: E402
+from lime_cikm25_amd import build as lime_build  # noqa: E402
 
 MASKS = [0, 2, 64, 4 | 8 | 16, 4 | 8 | 16 | 64, 2 | 4 | 8 | 16]
 
@@ -21,8 +23,7 @@ def build(mask):
     src = os.path.join(ROOT, 'lime_cikm25_amd', 'csrc')
     if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(src, 'token_attn_train_f32.hip')):
         subprocess.run(['hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-shared',
-                        '-DLIME_ATTN_BWD_ABLATE=%d' % mask, '-o', so, os.path.join(src, 'token_attn_train_f32.hip'),
-                        os.path.join(src, 'common.cpp')], check=True)
+                        '-DLIME_ATTN_BWD_ABLATE=%d' % mask, '-o', so] + lime_build.sources(), check=True)
     return so
 
 
@@ -31,24 +32,18 @@ def main():
     nh, hd, hs = 10, 30, 32
     W = nh * hs
     for mask in MASKS:
-        lib = ctypes.CDLL(build(mask))
-        f = lib.lime_token_attention_bwd_f32
-        f.restype = ctypes.c_int32
-        f.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + \
-                     [ctypes.c_void_p] * 3 + [ctypes.c_int64] + [ctypes.c_int32] * 5 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_int64,
-                                                                                      ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.LIB_PATH, _lib._lib = build(mask), None          # the wrappers below call this variant
+        _lib.load().lime_set_split_gemm(0)
         line = 'mask %2d' % mask
         for n_seq, S in ((1760, 128), (1760, 32)):
             tok = n_seq * S
             qkv = (torch.rand(tok, 3 * W, device=dev) - 0.5)
             dout = torch.rand(tok, nh * hd, device=dev) - 0.5
             dqkv = torch.empty_like(qkv)
-            P = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + 4 * off)
 
             def run():
-                st = f(P(qkv), P(qkv, W), P(qkv, 2 * W), 3 * W, None, 0, P(dout), nh * hd, P(dqkv), P(dqkv, W), P(dqkv, 2 * W), 3 * W,
-                       n_seq, S, nh, hd, hs, 1.0 / hd ** 0.5, None, 0, 0.0, 0, 0, None, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-                assert st == 0
+                ops.token_attention_bwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], dout, n_seq, S, nh, hd, 1.0 / hd ** 0.5, head_stride=hs,
+                                        dqkv=dqkv)
             for _ in range(3):
                 run()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
