@@ -1235,6 +1235,25 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * LIME_ERR_BAD_ARG; n < 2^31 (LIME_ERR_UNSUPPORTED beyond); the other limits and statuses are those of lime_grouped_match_f32, checked
  * in the same order before any launch.
  *
+ * lime_grouped_mlp_match_f32 (csrc/grouped_mlp_match_f32.hip): the grouped match under the MLP click predictor (config.click_predictor =
+ * 'mlp', reference model.py:113-115, :182-184: logits = out(relu(mlp(cat[user, news])))), with mlp.weight [Dh, 2 D] split into its
+ * user half W_u = mlp.weight[:, :D] and its news half W_n = mlp.weight[:, D:].  kp [G H, A] and gu = g W_u^T [G H, Dh] per group; qp
+ * [P, A] and nw = cand W_n^T + mlp.bias [P, Dh] per pair; w_out [Dh] = out.weight, b_out = out.bias, ONE float on the device (NULL:
+ * 0); offsets as in lime_grouped_match_f32.  For pair p of group i:
+ *     s[h] = kp[i H + h, :] . qp[p, :] * scale,  a = softmax_h(s),  u[j] = sum_h a[h] gu[i H + h, j],
+ *     logits[p] = sum_j relu(u[j] + nw[p, j]) w_out[j] + b_out
+ * There is no remaining-lifetime weight under this predictor.  The pooled hidden row u exists in registers alone: no [P, D] user row
+ * and no [P, Dh] hidden row is written.  Exact fp32 on v_mfma_f32_16x16x4_f32, a workgroup per 64-pair tile of a group; the first
+ * product and the softmax are the instructions of lime_grouped_match_f32; fixed-order sums, no atomics: a pair's bits depend on H, A
+ * and Dh alone -- not on P, G, the group's position or the pair's place in its tile.  1 <= H <= 128, A a multiple of 4 up to 2048, Dh
+ * any EVEN number up to 2048 (LIME_ERR_UNSUPPORTED otherwise); kp, qp 16-byte aligned, gu, nw 8-byte aligned (LIME_ERR_BAD_ARG
+ * otherwise).  H = 1 is the predictor on one pooled user vector per group (a = 1; kp and qp are not felt).
+ *
+ * lime_grouped_mlp_match_indexed_f32 (same file): qp [n, A] and nw [n, Dh] are TABLES of n rows and pair p reads row index[p] of both
+ * (index int32 [P] on the device).  A pair's bits equal those of lime_grouped_mlp_match_f32 on the gathered rows.  The clamping of an
+ * index outside [0, n), n = 0 with P > 0 (LIME_ERR_BAD_ARG) and n < 2^31 are the rules of lime_grouped_match_indexed_f32, checked in
+ * the same order before any launch.
+ *
  * lime_topk_rows_f32 (csrc/topk_rows_f32.hip): per row u < U of scores [U, C] (leading dimension ld >= C) the k best entries:
  * positions int32 [U, k] (column indices) and top_scores fp32 [U, k] (the input's bits at those positions), in descending order of
  * the score; equal scores -- +0.0 and -0.0 are equal -- lower position first; a NaN ranks behind every number, NaNs in position
@@ -1249,6 +1268,12 @@ int lime_grouped_match_indexed_f32(const float* kp, const float* g, const float*
                                    const int64_t* offsets, const int32_t* index, int64_t n, float* logits, int64_t G, int64_t P,
                                    int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s, int32_t use_weight,
                                    int32_t use_penalty, void* stream);
+int lime_grouped_mlp_match_f32(const float* kp, const float* gu, const float* qp, const float* nw, const float* w_out, const float* b_out,
+                               const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t Dh, float scale,
+                               void* stream);
+int lime_grouped_mlp_match_indexed_f32(const float* kp, const float* gu, const float* qp, const float* nw, const float* w_out,
+                                       const float* b_out, const int64_t* offsets, const int32_t* index, int64_t n, float* logits,
+                                       int64_t G, int64_t P, int32_t H, int32_t A, int32_t Dh, float scale, void* stream);
 int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);

@@ -11,7 +11,7 @@
 // only, chunk c + 1 on its way from global memory into registers while chunk c is multiplied, two buffers and one barrier per chunk.
 // The pair's own operand (qp, then cand) is read by its wave straight from global memory, 16 bytes per lane.  Columns behind A / D
 // are zeros in registers; no load goes past a row.
-// Exact fp32: v_mfma_f32_16x16x4_f32 (mfma16).  A lane's four loaded columns go to four accumulators; every FLUSH chunks the four are
+// Exact fp32: v_mfma_f32_16x16x4_f32 (mfma16).  A lane's four loaded columns go to four accumulators; every GM_FLUSH chunks the four are
 // added as (c0 + c1) + (c2 + c3) into a compensated running sum and start again from zero.  The softmax and the weighted sum over h
 // run on the results (h over the lane's 4 T registers in order, then the two butterfly steps over the lanes 16 and 32 apart).  Every sum has
 // a fixed order that depends on H, A and D alone: a pair's bits depend neither on P, G, the group's position, the pair's place in its
@@ -19,90 +19,13 @@
 //
 // The indexed form (lime_grouped_match_indexed_f32): the pair's own operands are rows of two TABLES, qp [n, A] and cand [n, D], and
 // pair p reads row index[p] of both -- a candidate whose representation depends on the news alone is not copied once per (user,
-// candidate) pair.  Nothing else changes: only the row that tile_product reads as Y differs, so a pair's bits are those of the plain
+// candidate) pair.  Nothing else changes: only the row that gm_tile_product reads as Y differs, so a pair's bits are those of the plain
 // form on the gathered rows.  An index outside [0, n) is clamped into it (as the offsets are clamped): a bad plan reads in range.
-#include "dev_helpers.h"
+#include "grouped_tile.h"        // the tile product and the softmax, shared with grouped_mlp_match_f32.hip
 
 namespace {
 
 using namespace lime_dev;
-
-constexpr int PAIRS = 64;            // pairs of a workgroup tile: 16 per wave
-constexpr int CHUNK = 16;            // columns of an LDS chunk: one 64-byte row of the swizzled image
-constexpr int FLUSH = 2;             // chunks between two flushes of the MFMA accumulators into the compensated sum
-
-// One [16 T x 16] tile product per wave over K columns: out[t][r] = X[16 t + 4 (lane >> 4) + r, :K] . Y[pair of lane & 15, :K].
-// X: the group's rows x0 .. x0 + H - 1 of a dense [*, K] matrix (shared by the workgroup, through `img`); Y: row `yrow` of a dense
-// [*, K] matrix, or nothing (zeros) when `ylive` is false.  Ends with a barrier: `img` is free again when it returns.
-template <int T>
-__device__ __forceinline__ void tile_product(const float* __restrict__ X, long x0, int H, const float* __restrict__ Y, long yrow, bool ylive,
-                                             int K, float* img, f32x4 (&out)[T]) {
-    constexpr int NL = T < 4 ? 1 : T / 4;                    // 16-byte pieces of a chunk per thread: 16 T rows x 4 segments / 256
-    const int lane = threadIdx.x & 63;
-    const int ar = lane & 15, as = lane >> 4;                // this lane's row of a 16-row tile and its 16-byte segment
-    const int n_chunk = (K + CHUNK - 1) / CHUNK;
-    f32x4 xs[NL], ys;
-    f32x4 acc[T][4];
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    auto fetch = [&](int c) {
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            const int piece = (int)threadIdx.x + 256 * j;
-            const int row = piece >> 2, col = c * CHUNK + 4 * (piece & 3);
-            xs[j] = (row < H && col < K) ? *reinterpret_cast<const f32x4*>(X + (x0 + row) * K + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        const int col = c * CHUNK + 4 * as;
-        ys = (ylive && col < K) ? *reinterpret_cast<const f32x4*>(Y + yrow * K + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-    };
-
-    // The accumulators are emptied every FLUSH chunks into a compensated sum (tot + comp, Knuth's two-sum): one fmaf chain over all
-    // K / 4 of a lane's column groups loses about three times what lime_interest_match_f32's shuffle trees lose at K = 400; chains
-    // of 4 FLUSH products with an exactly corrected running sum behind them lose less than those trees.
-    f32x4 tot[T], comp[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) tot[t] = comp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto flush = [&]() {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const f32x4 v = (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
-            const f32x4 s = tot[t] + v;
-            const f32x4 b = s - tot[t];
-            comp[t] += (tot[t] - (s - b)) + (v - b);
-            tot[t] = s;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-
-    fetch(0);
-    for (int c = 0; c < n_chunk; ++c) {
-        float* buf = img + (c & 1) * (16 * T * CHUNK);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            const int piece = (int)threadIdx.x + 256 * j;
-            const int row = piece >> 2, seg = piece & 3;
-            if (row < 16 * T) *reinterpret_cast<f32x4*>(buf + row * CHUNK + 4 * (seg ^ swz4((row >> 2) & 3))) = xs[j];
-        }
-        const f32x4 b = ys;
-        lds_barrier();                                       // (two buffers: the chunk written here was last read two barriers ago)
-        if (c + 1 < n_chunk) fetch(c + 1);
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int row = 16 * t + ar;
-            const f32x4 a = *reinterpret_cast<const f32x4*>(buf + row * CHUNK + 4 * (as ^ swz4((row >> 2) & 3)));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[t][i] = mfma16(a[i], b[i], acc[t][i]);
-        }
-        if ((c + 1) % FLUSH == 0 || c + 1 == n_chunk) flush();
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) out[t] = tot[t] + comp[t];
-    lds_barrier();
-}
 
 // INDEXED: qp / cand are tables of n rows and pair p reads row index[p] (clamped into [0, n)) of both; else row p (index unread).
 template <int T, bool INDEXED>
@@ -112,15 +35,15 @@ __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restr
                                                              const int* __restrict__ index, int n, float* __restrict__ logits, long P, int H,
                                                              int A, int D, float scale, float alpha_s, float beta_s, int use_weight,
                                                              int use_penalty) {
-    __shared__ __attribute__((aligned(16))) float img[2 * 16 * T * CHUNK];
+    __shared__ __attribute__((aligned(16))) float img[2 * 16 * T * GM_CHUNK];
     const long grp = blockIdx.x;
     long lo = offsets[grp], hi = offsets[grp + 1];
     lo = lo < 0 ? 0 : (lo > P ? P : lo);                     // every offset clamped into [0, P]: a bad plan reads and writes in range
     hi = hi < lo ? lo : (hi > P ? P : hi);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long n_tile = (hi - lo + PAIRS - 1) / PAIRS;
+    const long n_tile = (hi - lo + GM_PAIRS - 1) / GM_PAIRS;
     for (long tile = blockIdx.y; tile < n_tile; tile += gridDim.y) {         // (workgroup-uniform: the barriers inside stay whole)
-        const long p = lo + tile * PAIRS + 16 * wave + (lane & 15);
+        const long p = lo + tile * GM_PAIRS + 16 * wave + (lane & 15);
         const bool live = p < hi;
         long y = p;                                          // the pair's row of qp and cand
         if constexpr (INDEXED) {
@@ -128,32 +51,14 @@ __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restr
             y = i < 0 ? 0 : (i >= n ? n - 1 : i);
         }
         f32x4 s[T], m[T];
-        tile_product<T>(kp, grp * H, H, qp, y, live, A, img, s);
-        tile_product<T>(g, grp * H, H, cand, y, live, D, img, m);
-        // softmax over the history (unmasked, userEncoders.py:164) and the weighted sum, on this lane's 4 T values of its pair
-        const int h0 = 4 * (lane_here() >> 4);               // (recomputed: hoisted out of the tile loop, the 4 T padding tests
-                                                             // would sit in SGPR pairs through both products and spill)
-        float mx = -INFINITY;
+        gm_tile_product<T>(kp, grp * H, H, qp, y, live, A, img, s);
+        gm_tile_product<T>(g, grp * H, H, cand, y, live, D, img, m);
+        // softmax over the history (grouped_tile.h: s becomes exp(s - max)) and the weighted sum, on this lane's 4 T values of its pair
+        float den = gm_tile_softmax<T>(s, H, scale), num = 0.f;
 #pragma unroll
         for (int t = 0; t < T; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[t][r] = (16 * t + h0 + r < H) ? s[t][r] * scale : -INFINITY;
-                mx = fmaxf(mx, s[t][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float den = 0.f, num = 0.f;
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = expf(s[t][r] - mx);          // (a padded row holds -inf: exactly 0)
-                den += e;
-                num = fmaf(e, m[t][r], num);
-            }
-        den += __shfl_xor(den, 16);
-        den += __shfl_xor(den, 32);
+            for (int r = 0; r < 4; ++r) num = fmaf(s[t][r], m[t][r], num);
         num += __shfl_xor(num, 16);
         num += __shfl_xor(num, 32);
         if (live && lane < 16) {
@@ -184,7 +89,7 @@ int grouped_match_launch(const char* who, const float* kp, const float* g, const
     if (G == 0 || P == 0) return LIME_OK;
     // tile slices per group: enough workgroups to fill the chip when the groups are few (one group per user with the candidate-aware
     // attention off), never more than the tiles the pairs can make.  The split changes which workgroup takes a tile, not its bits.
-    const long all_tiles = (P + PAIRS - 1) / PAIRS;
+    const long all_tiles = (P + GM_PAIRS - 1) / GM_PAIRS;
     long slices = (8L * lime_num_cus() + G - 1) / G;
     slices = slices > all_tiles ? all_tiles : slices;
     slices = slices < 1 ? 1 : (slices > 65535 ? 65535 : slices);

@@ -1,0 +1,116 @@
+// What the grouped matches share (grouped_match_f32.hip, grouped_mlp_match_f32.hip): the [16 T x 16] tile product of a group's shared
+// rows with a wave's 16 pairs, and the softmax over the history on its result.  One copy: both kernels' first product and softmax are
+// the same instructions, so a pair's attention weights are the same bits in both.
+#pragma once
+#include "dev_helpers.h"
+
+namespace lime_dev {
+
+constexpr int GM_PAIRS = 64;            // pairs of a workgroup tile: 16 per wave
+constexpr int GM_CHUNK = 16;            // columns of an LDS chunk: one 64-byte row of the swizzled image
+constexpr int GM_FLUSH = 2;             // chunks between two flushes of the MFMA accumulators into the compensated sum
+
+// One [16 T x 16] tile product per wave over K columns: out[t][r] = X[16 t + 4 (lane >> 4) + r, :K] . Y[pair of lane & 15, :K].
+// X: the group's rows x0 .. x0 + H - 1 of a dense [*, K] matrix (shared by the workgroup, through `img`); Y: row `yrow` of a dense
+// [*, K] matrix, or nothing (zeros) when `ylive` is false.  Ends with a barrier: `img` is free again when it returns.
+template <int T>
+__device__ __forceinline__ void gm_tile_product(const float* __restrict__ X, long x0, int H, const float* __restrict__ Y, long yrow, bool ylive,
+                                             int K, float* img, f32x4 (&out)[T]) {
+    constexpr int NL = T < 4 ? 1 : T / 4;                    // 16-byte pieces of a chunk per thread: 16 T rows x 4 segments / 256
+    const int lane = threadIdx.x & 63;
+    const int ar = lane & 15, as = lane >> 4;                // this lane's row of a 16-row tile and its 16-byte segment
+    const int n_chunk = (K + GM_CHUNK - 1) / GM_CHUNK;
+    f32x4 xs[NL], ys;
+    f32x4 acc[T][4];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto fetch = [&](int c) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+            const int piece = (int)threadIdx.x + 256 * j;
+            const int row = piece >> 2, col = c * GM_CHUNK + 4 * (piece & 3);
+            xs[j] = (row < H && col < K) ? *reinterpret_cast<const f32x4*>(X + (x0 + row) * K + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const int col = c * GM_CHUNK + 4 * as;
+        ys = (ylive && col < K) ? *reinterpret_cast<const f32x4*>(Y + yrow * K + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+
+    // The accumulators are emptied every GM_FLUSH chunks into a compensated sum (tot + comp, Knuth's two-sum): one fmaf chain over all
+    // K / 4 of a lane's column groups loses about three times what lime_interest_match_f32's shuffle trees lose at K = 400; chains
+    // of 4 GM_FLUSH products with an exactly corrected running sum behind them lose less than those trees.
+    f32x4 tot[T], comp[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) tot[t] = comp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto flush = [&]() {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const f32x4 v = (acc[t][0] + acc[t][1]) + (acc[t][2] + acc[t][3]);
+            const f32x4 s = tot[t] + v;
+            const f32x4 b = s - tot[t];
+            comp[t] += (tot[t] - (s - b)) + (v - b);
+            tot[t] = s;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+
+    fetch(0);
+    for (int c = 0; c < n_chunk; ++c) {
+        float* buf = img + (c & 1) * (16 * T * GM_CHUNK);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+            const int piece = (int)threadIdx.x + 256 * j;
+            const int row = piece >> 2, seg = piece & 3;
+            if (row < 16 * T) *reinterpret_cast<f32x4*>(buf + row * GM_CHUNK + 4 * (seg ^ swz4((row >> 2) & 3))) = xs[j];
+        }
+        const f32x4 b = ys;
+        lds_barrier();                                       // (two buffers: the chunk written here was last read two barriers ago)
+        if (c + 1 < n_chunk) fetch(c + 1);
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int row = 16 * t + ar;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(buf + row * GM_CHUNK + 4 * (as ^ swz4((row >> 2) & 3)));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[t][i] = mfma16(a[i], b[i], acc[t][i]);
+        }
+        if ((c + 1) % GM_FLUSH == 0 || c + 1 == n_chunk) flush();
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) out[t] = tot[t] + comp[t];
+    lds_barrier();
+}
+
+// The softmax over the history (unmasked, userEncoders.py:164) on a tile product's scores, this lane's 4 T values of its pair (h =
+// 16 t + 4 (lane >> 4) + r): s becomes e = exp(s * scale - max), exactly 0 for a padded row h >= H; returns the pair's sum of e over
+// all h (h over the lane's registers in order, then the two butterfly steps over the lanes 16 and 32 apart), in every lane of the pair.
+template <int T>
+__device__ __forceinline__ float gm_tile_softmax(f32x4 (&s)[T], int H, float scale) {
+    const int h0 = 4 * (lane_here() >> 4);                   // (recomputed: hoisted out of the tile loop, the 4 T padding tests
+                                                             // would sit in SGPR pairs through both products and spill)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[t][r] = (16 * t + h0 + r < H) ? s[t][r] * scale : -INFINITY;
+            mx = fmaxf(mx, s[t][r]);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    float den = 0.f;
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[t][r] = expf(s[t][r] - mx);                    // (a padded row holds -inf: exactly 0)
+            den += s[t][r];
+        }
+    den += __shfl_xor(den, 16);
+    den += __shfl_xor(den, 32);
+    return den;
+}
+
+}  // namespace lime_dev

@@ -36,6 +36,13 @@ _REFUSED_USER_ENCODERS = {
 }
 
 
+# why the reference's other click predictors (model.py:116-128, :185-186) stay refused
+_REFUSED_CLICK_PREDICTORS = {
+    'sigmoid': ' (the reference\'s forward has no branch for it: model.py:179-186 leaves logits unset)',
+    'FIM': ' (it needs the HDC news encoder and the FIM user encoder, model.py:108-110)',
+}
+
+
 # A baseline model's candidates depend on the news alone: the grouped match reads them in place through an index
 # (lime_grouped_match_indexed_f32).  LIME_INDEXED_MATCH=0 keeps the gather form for them too -- one materialised row and one Q row per
 # (user, candidate) pair, the path LIME models take -- as the yardstick of the indexed one (tools/bench_recommend.py, tools/bench_lists.py).
@@ -54,6 +61,9 @@ class Model(nn.Module):
     'KCNN' (cnn_method 'naive', 'group3' or 'group4'; it reads the ``*_title_entity`` inputs);
     ``config.user_encoder`` the user encoder: 'CROWN', 'ATT' (NAML's additive attention) or 'MHSA' (NRMS's self-attention), in any
     pairing.
+    ``config.click_predictor``: 'dot_product' (the default: the lifetime-weighted dot product) or 'mlp' (model.py:113-115, :182-184:
+    ``logits = out(dropout(relu(mlp(cat[user, news]))))`` with ``mlp``: 2 D -> D // 2 and ``out``: D // 2 -> 1, the last four keys of the
+    state_dict; no remaining-lifetime weight, ``remaining_lifetime`` is accepted and not read), with any of the models above.
 
     Scoring (eval mode, or any call under ``torch.no_grad()``): the forward pass runs entirely in hand-written HIP
     kernels and records no autograd graph.  In training mode with grad enabled (``model.train(); model(...)``, what
@@ -103,9 +113,14 @@ class Model(nn.Module):
         self.dropout = nn.Dropout(p=config.dropout_rate)
         self.use_user_embedding = False
         self.click_predictor = config.click_predictor
-        if self.click_predictor != 'dot_product':
-            raise NotImplementedError('click_predictor %r: LIME uses dot_product (config.py:109)' % self.click_predictor)
+        if self.click_predictor == 'mlp':                    # model.py:113-115
+            self.mlp = nn.Linear(in_features=self.news_embedding_dim * 2, out_features=self.news_embedding_dim // 2, bias=True)
+            self.out = nn.Linear(in_features=self.news_embedding_dim // 2, out_features=1, bias=True)
+        elif self.click_predictor != 'dot_product':
+            raise NotImplementedError('click_predictor %r stays refused%s: the supported click predictors are dot_product (config.py:109) '
+                                      'and mlp' % (self.click_predictor, _REFUSED_CLICK_PREDICTORS.get(self.click_predictor, '')))
         self.remaining_lifetime_weighting = RemainingLifetimeWeighting(config)
+        self._regular_offsets = {}
         self.use_graph = True
         self._graphs = {}
         # the inputs the captured graph copies in, per model: the body masks only where the content encoder reads them
@@ -121,6 +136,7 @@ class Model(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         self._graphs = {}                      # parameter storage moves: captured pointers are stale
+        self._regular_offsets = {}
         self._products_key = None              # (the content encoder drops what it keeps across forwards in its own _apply)
         return super()._apply(fn, *args, **kwargs)
 
@@ -144,6 +160,9 @@ class Model(nn.Module):
     def initialize(self):
         self.news_encoder.initialize()
         self.user_encoder.initialize()
+        if self.click_predictor == 'mlp':                    # model.py:139-141 (``out`` keeps nn.Linear's default initialisation)
+            nn.init.xavier_uniform_(self.mlp.weight, gain=nn.init.calculate_gain('relu'))
+            nn.init.zeros_(self.mlp.bias)
         self.remaining_lifetime_weighting.initialize()
 
     def forward(self, user_ID, user_category, user_subCategory, user_title_text, user_title_mask, user_title_entity,
@@ -300,11 +319,10 @@ class Model(nn.Module):
             b1 = min(B, b0 + per)
             n = (b1 - b0) * K
             # the history side (embeddings, topic ids, mask) is shared by the K candidate rows of an impression: hist_div
-            _, logits = ue.match(hist[b0:b1], news_category[b0:b1].reshape(n, 1), news_subCategory[b0:b1].reshape(n, 1),
-                                 user_category[b0:b1], user_subCategory[b0:b1], user_history_mask[b0:b1],
-                                 cand[b0:b1].reshape(n, 1, -1), remaining_lifetime=rl[b0:b1].reshape(n, 1),
-                                 weighting=self.remaining_lifetime_weighting, n_src=n_src, hist_div=K,
-                                 gate_y=None if gate_y is None else gate_y[b0 * H:b1 * H])
+            logits = self._row_logits(hist[b0:b1], news_category[b0:b1].reshape(n, 1), news_subCategory[b0:b1].reshape(n, 1),
+                                      user_category[b0:b1], user_subCategory[b0:b1], user_history_mask[b0:b1],
+                                      cand[b0:b1].reshape(n, 1, -1), rl[b0:b1].reshape(n, 1), n_src=n_src, hist_div=K,
+                                      gate_y=None if gate_y is None else gate_y[b0 * H:b1 * H])
             out[b0:b1] = logits.view(b1 - b0, K)
         return out
 
@@ -369,9 +387,9 @@ class Model(nn.Module):
         cand = ne.encode_cached(news_cache, cand_idx, b.cand_freshness[rows], b.cand_lifetime[rows]).view(R, 1, -1)
         if n_src is None and hasattr(ue, 'user_node_embedding'):
             n_src = min(R, H + ue.user_node_embedding.shape[0])
-        _, logits = ue.match(hist, c.news_category[flat_c].view(R, 1), c.news_subCategory[flat_c].view(R, 1),
-                             c.news_category[flat_h].view(R, H), c.news_subCategory[flat_h].view(R, H), b.hist_mask[rows],
-                             cand, remaining_lifetime=remaining.view(R, 1), weighting=self.remaining_lifetime_weighting, n_src=n_src)
+        logits = self._row_logits(hist, c.news_category[flat_c].view(R, 1), c.news_subCategory[flat_c].view(R, 1),
+                                  c.news_category[flat_h].view(R, H), c.news_subCategory[flat_h].view(R, H), b.hist_mask[rows],
+                                  cand, remaining.view(R, 1), n_src=n_src)
         return logits.view(R)
 
     def _remaining_lifetime(self, behaviors, rows, cand_idx):
@@ -475,46 +493,138 @@ class Model(nn.Module):
         stream, so it stands behind the launches that do not read it).  The user side runs once per group and the match per pair."""
         hist, ucat, usub, hist_mask, gate_y, n_src = users
         index, freshness, lifetime, remaining, tables, position = cands
-        ne, ue, w = self.news_encoder, self.user_encoder, self.remaining_lifetime_weighting
-        H, D = hist.shape[1:]
+        ne, ue = self.news_encoder, self.user_encoder
+        H = hist.shape[1]
         dev = news_cache.device
         operands = ue.match_operands(hist[u0:u1], category, subCategory, ucat[u0:u1], usub[u0:u1], hist_mask[u0:u1], n_src=n_src,
                                      hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
-        crown = hasattr(ue, 'user_node_embedding')
         if tables is None:
             cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))       # [pairs, D]
             at = None
         else:
-            cand, qp = tables                                                                       # the call's tables, read in place
+            cand = None                                                                             # the call's tables, read in place
             at = newsEncoders._i32(pick(position).reshape(-1)).contiguous()                         # int32 [pairs]: the pair's table row
-        group_offsets = torch.as_tensor(group_offsets, device=dev)
-        if crown:
-            g, kp, _ = operands
-            if tables is None:
-                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                 # userEncoders.py:162
+        return self._click_logits(operands, cand, pick(remaining).reshape(-1), torch.as_tensor(group_offsets, device=dev), H, tables=tables,
+                                  index=at)
+
+    def _offsets_of_rows(self, groups, pairs, device):
+        """int64 [groups + 1] on the device: the CSR of the regular shape, ``pairs`` pairs per group.  Kept per shape: a captured forward
+        reads the tensor its eager warm-up built (no host-made tensor is born inside a capture)."""
+        key = (groups, pairs, str(device))
+        off = self._regular_offsets.get(key)
+        if off is None:
+            off = self._regular_offsets[key] = (torch.arange(groups + 1, dtype=torch.int64) * pairs).to(device)
+        return off
+
+    def _row_logits(self, hist, category, subCategory, user_category, user_subCategory, user_history_mask, cand, remaining, agg=None,
+                    n_src=None, hist_div=1, gate_y=None):
+        """The logits [B, N] of the regular shape -- B = hist.shape[0] * hist_div rows with N candidates each, ``ue.match``'s arguments.
+        Under the dot-product predictor this IS ``ue.match`` (the match fused into the user encoder's last kernel); under the MLP
+        predictor the user encoder stops at its operands and ``_click_logits`` takes the rows as groups of N pairs."""
+        ue = self.user_encoder
+        if self.click_predictor == 'dot_product':
+            return ue.match(hist, category, subCategory, user_category, user_subCategory, user_history_mask, cand,
+                            remaining_lifetime=remaining, weighting=self.remaining_lifetime_weighting, agg=agg, n_src=n_src,
+                            hist_div=hist_div, gate_y=gate_y)[1]
+        if self.training and (ue.training or self.dropout.training):
+            raise NotImplementedError('the scoring kernel chain has no training-mode dropouts: Model.forward takes the differentiable path')
+        B, N, D = cand.shape
+        flat = cand.contiguous().view(B * N, D)
+        kw = dict(cand=flat) if hasattr(ue, 'user_node_embedding') else {}
+        operands = ue.match_operands(hist, category, subCategory, user_category, user_subCategory, user_history_mask, agg=agg, n_src=n_src,
+                                     hist_div=hist_div, gate_y=gate_y, **kw)
+        groups = (operands[0] if isinstance(operands, tuple) else operands).shape[0]     # (ATT / MHSA without refinement: one per history)
+        per = B * N // groups
+        return self._click_logits(operands, flat, None, self._offsets_of_rows(groups, per, flat.device), hist.shape[1], regular=per).view(B, N)
+
+    def _click_logits(self, operands, cand, remaining, offsets, H, tables=None, index=None, regular=None):
+        """The ONE place that turns (user-side operands, candidates) into logits, for either click predictor -> fp32 [pairs].
+        ``operands``: what ``user_encoder.match_operands`` gave for G groups -- CROWN: (g [G, H, D], kp [G H, A], qp [pairs, A] or None:
+        made here); ATT / MHSA: the pooled vector [G, D], a history of ONE row whose softmax weight is 1 (kp and qp are not felt).
+        ``cand`` [pairs, D] in group order and ``offsets`` int64 [G + 1] their CSR; or ``tables`` (``_candidate_tables``) read in place
+        through ``index`` int32 [pairs].  ``remaining`` [pairs]: read by the dot product's lifetime weight alone.  ``regular``: the pairs
+        per group where every group has as many (the [B, N] shape).
+
+        dot_product (model.py:179-181): lime_grouped_match_f32.  mlp (:182-184): with mlp.weight split into its user half W_u and its
+        news half W_n, gu = g W_u^T once per history row and nw = cand W_n^T + mlp.bias once per candidate row (a table for a baseline
+        model), then lime_grouped_mlp_match_f32 keeps a pair's pooled hidden row in registers; ops.FUSED_MLP_MATCH off: the composed
+        form -- the pairs' user rows, ``linear(cat, mlp, act='relu')``, the product with ``out`` -- on existing launches."""
+        ue, w = self.user_encoder, self.remaining_lifetime_weighting
+        if hasattr(ue, 'user_node_embedding'):
+            g, kp, qp = operands
+            D = g.shape[-1]
+            g = g.reshape(-1, D)
             h_match, scale = H, 1.0 / ue.attention_scalar
+            if tables is not None:
+                qp = tables[1]
+            elif qp is None:
+                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                 # userEncoders.py:162
         else:
-            # one pooled vector per group: the same match with a history of one row (its softmax weight is 1, kp and qp are not felt)
             g, h_match, scale = operands, 1, 1.0
-            kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=dev)
-            if tables is None:
-                qp = torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=dev)
-        return ops.grouped_match(kp, g.reshape(-1, D), qp, cand, pick(remaining).reshape(-1), group_offsets, h_match, scale, w.alpha, w.beta,
-                                 bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=at)
+            D = g.shape[-1]
+            kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=g.device)
+            qp = tables[1] if tables is not None else torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=g.device)
+        if tables is not None:
+            cand = tables[0]
+        if self.click_predictor == 'dot_product':
+            return ops.grouped_match(kp, g, qp, cand, remaining, offsets, h_match, scale, w.alpha, w.beta,
+                                     bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=index)
+        mlp, out = self.mlp, self.out
+        if ops.FUSED_MLP_MATCH:
+            gu = ops.linear(g, mlp.weight[:, :D], None)
+            nw = tables[2] if tables is not None else ops.linear(cand, mlp.weight[:, D:], mlp.bias)
+            return ops.grouped_mlp_match(kp, gu, qp, nw, out.weight, out.bias, offsets, h_match, scale, index=index)
+        return self._composed_mlp_logits(kp, g, qp, cand, offsets, h_match, scale, index, regular)
+
+    def _composed_mlp_logits(self, kp, g, qp, cand, offsets, H, scale, index, regular):
+        """The MLP predictor on existing launches (ops.FUSED_MLP_MATCH off; the yardstick of the fused kernel): the user row of every
+        pair -- lime_interest_match_f32's, or the group's pooled vector -- then ops.mlp_predictor on the [pairs, 2 D] rows.  Irregular
+        groups go through in steps of pairs, each with its own copy of its group's H history rows."""
+        mlp, out = self.mlp, self.out
+        D, G = g.shape[1], g.shape[0] // H
+        P = index.numel() if index is not None else cand.shape[0]
+        predict = lambda user, news: ops.mlp_predictor(user, news, mlp.weight, mlp.bias, out.weight, out.bias)
+        if regular is not None and index is None and H > 1:
+            user, _ = ops.interest_match(kp.reshape(-1), qp.reshape(-1), g.reshape(-1), cand.reshape(-1), None, G, regular, H, kp.shape[1], D,
+                                         scale, 0.0, 0.0, False, False, want_logits=False, want_user=True)
+            return predict(user.view(P, D), cand)
+        group = torch.repeat_interleave(torch.arange(G, device=g.device), offsets[1:] - offsets[:-1], output_size=P)
+        logits = torch.empty((P,), dtype=torch.float32, device=g.device)
+        slots = torch.arange(H, device=g.device)
+        step = 1024 if H > 1 else 1 << 16
+        for p0 in range(0, P, step):
+            p1 = min(P, p0 + step)
+            at = slice(p0, p1) if index is None else index[p0:p1].long()
+            news = cand[at].contiguous()
+            if H > 1:
+                rows = (group[p0:p1].unsqueeze(1) * H + slots).reshape(-1)
+                user, _ = ops.interest_match(kp[rows].reshape(-1), qp[at].reshape(-1), g[rows].reshape(-1), news.reshape(-1), None, p1 - p0, 1,
+                                             H, kp.shape[1], D, scale, 0.0, 0.0, False, False, want_logits=False, want_user=True)
+                user = user.view(p1 - p0, D)
+            else:
+                user = g[group[p0:p1]]
+            logits[p0:p1] = predict(user, news)
+        return logits
 
     def _candidate_tables(self, news_cache, rows=None):
         """The ONE place that asks whether a candidate's representation depends on the news alone (``occurrence_free``: a baseline
         model's news encoder; LIME's rows depend on the occurrence) -> None: ``_match_pass`` materialises a row and a Q row per pair; or
         the tables (cand [n, D], qp [n, A]) that lime_grouped_match_indexed_f32 reads in place, once per call: the news of ``rows``
         (the pool, in plan order) or, with ``rows`` None, every news of the cache (the lists: a pair's index is its news id).  Under
-        ATT / MHSA (a history of one row) qp is never felt: n rows of four zero columns -- the kernel reads both tables at one index."""
+        ATT / MHSA (a history of one row) qp is never felt: n rows of four zero columns -- the kernel reads both tables at one index.
+        Under the MLP click predictor a third table stands beside them: nw [n, D // 2] = cand W_n^T + mlp.bias, the news half of the
+        predictor's hidden layer, once per call (lime_grouped_mlp_match_indexed_f32 reads it; None on the composed form and under
+        the dot product)."""
         ne, ue = self.news_encoder, self.user_encoder
         if not (INDEXED_MATCH and getattr(ne, 'occurrence_free', False)):
             return None
         cand = news_cache.contiguous() if rows is None else ne.encode_cached(news_cache, rows)
+        # the MLP predictor's news half of the hidden layer, nw = cand W_n^T + mlp.bias: a function of the news alone too
+        nw = (ops.linear(cand, self.mlp.weight[:, cand.shape[1]:], self.mlp.bias)
+              if self.click_predictor == 'mlp' and ops.FUSED_MLP_MATCH else None)
         if hasattr(ue, 'user_node_embedding'):
-            return cand, ops.linear(cand, ue.Q.weight, ue.Q.bias)                                             # userEncoders.py:162
-        return cand, torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=cand.device)
+            return cand, ops.linear(cand, ue.Q.weight, ue.Q.bias), nw                                         # userEncoders.py:162
+        return cand, torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=cand.device), nw
 
     def _score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                     cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
@@ -732,9 +842,9 @@ class Model(nn.Module):
             src = n_src
             if src is None:
                 src = min(n, H + ue.user_node_embedding.shape[0]) if hasattr(ue, 'user_node_embedding') else n
-            _, out = ue.match(hist[r0:r1], cat_all[r0:r1].view(-1, 1), sub_all[r0:r1].view(-1, 1), cat_all[R + r0 * H:R + r1 * H].view(-1, H),
-                              sub_all[R + r0 * H:R + r1 * H].view(-1, H), hist_mask[r0:r1], cand[r0:r1], remaining_lifetime=remaining[r0:r1],
-                              weighting=self.remaining_lifetime_weighting, n_src=src)
+            out = self._row_logits(hist[r0:r1], cat_all[r0:r1].view(-1, 1), sub_all[r0:r1].view(-1, 1),
+                                   cat_all[R + r0 * H:R + r1 * H].view(-1, H), sub_all[R + r0 * H:R + r1 * H].view(-1, H), hist_mask[r0:r1],
+                                   cand[r0:r1], remaining[r0:r1], n_src=src)
             logits[r0:r1] = out.view(-1)
         return logits
 
@@ -774,8 +884,6 @@ class Model(nn.Module):
                 (user_title_text, user_title_mask, user_content_text, user_category, user_subCategory, user_freshness,
                  user_user_topic_lifetime, user_content_mask, user_title_entity)])    # userEncoders.py:110-112
             main.wait_stream(side2)
-            _, logits = self.user_encoder.match(history_embedding, news_category, news_subCategory, user_category,
-                                                user_subCategory, user_history_mask, news_representation,
-                                                remaining_lifetime=remaining_lifetime.float(),
-                                                weighting=self.remaining_lifetime_weighting, agg=agg)   # model.py:174-181
+            logits = self._row_logits(history_embedding, news_category, news_subCategory, user_category, user_subCategory,
+                                      user_history_mask, news_representation, remaining_lifetime.float(), agg=agg)   # model.py:174-184
         return logits

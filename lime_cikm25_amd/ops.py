@@ -941,6 +941,65 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
     return logits
 
 
+# The MLP click predictor's match (config.click_predictor = 'mlp'): one launch per pass that keeps the pooled hidden row of a pair in
+# registers (True, lime_grouped_mlp_match_f32), or the composed form on existing launches -- the pairs' user rows, then
+# ``linear(cat[user, news], mlp, act='relu')``, then the product with ``out`` -- which writes a [pairs, D] user row and a [pairs, D // 2]
+# hidden row per pair (False).  The composed form is the fallback and the yardstick of the fused one's error
+# (tests/test_grouped_mlp_match_gpu.py, tools/bench_mlp_match.py).  LIME_FUSED_MLP_MATCH=0 selects it.
+FUSED_MLP_MATCH = os.environ.get('LIME_FUSED_MLP_MATCH', '1') != '0'
+
+
+def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=None, n=None):
+    """``lime_grouped_mlp_match_f32``: the history-vs-candidate attention and the MLP click predictor for groups of pairs that share one
+    refined history.  kp [G H, A] and gu = g W_u^T [G H, Dh] per group; qp [P, A] and nw = cand W_n^T + mlp.bias [P, Dh] per pair; w_out
+    [Dh] (out.weight), b_out [1] (out.bias; None: 0); offsets int64 [G + 1] (device) -> logits [P] (pairs outside every group keep what
+    ``torch.empty`` gave them).  1 <= H <= 128; A a multiple of 4, Dh even, both up to 2048.
+
+    ``index`` int32 [P] (``lime_grouped_mlp_match_indexed_f32``): qp and nw are tables and pair p reads row index[p] of both -- the
+    first ``n`` rows of each (default: all of qp's); the kernel clamps an index outside [0, n) into it.  A pair's bits are those of the
+    plain form on ``qp[index]``, ``nw[index]``."""
+    lib = _lib.load()
+    for t, name in ((kp, 'kp'), (gu, 'gu'), (qp, 'qp'), (nw, 'nw')):
+        _mat(t, name)
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    A, Dh = kp.shape[1], gu.shape[1]
+    if H < 1 or kp.shape[0] % H or gu.shape[0] != kp.shape[0]:
+        raise ValueError('kp and gu must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], gu.shape[0], H))
+    G = kp.shape[0] // H
+    if index is None:
+        if n is not None:
+            raise ValueError('n is the table size of the indexed form: give index too')
+        P = qp.shape[0]
+        if qp.shape[1] != A or nw.shape != (P, Dh):
+            raise ValueError('qp must be [P, %d] and nw [P, %d], got %s and %s' % (A, Dh, tuple(qp.shape), tuple(nw.shape)))
+    else:
+        P = index.numel()
+        index = _vec(index, 'index', P, dtype=torch.int32)
+        n = qp.shape[0] if n is None else int(n)
+        if qp.shape[1] != A or nw.shape[1] != Dh or not 0 <= n <= min(qp.shape[0], nw.shape[0]):
+            raise ValueError('qp must be [>= n, %d] and nw [>= n, %d] with n = %d, got %s and %s' % (A, Dh, n, tuple(qp.shape), tuple(nw.shape)))
+    _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
+    w_out = _vec(w_out.reshape(-1), 'w_out', Dh)
+    if b_out is not None:
+        b_out = _vec(b_out.reshape(-1), 'b_out', 1)
+    logits = torch.empty((P,), dtype=torch.float32, device=qp.device)
+    if index is None:
+        check(lib.lime_grouped_mlp_match_f32(_p(kp), _p(gu), _p(qp), _p(nw), _p(w_out), _p(b_out), _p(offsets), _p(logits), G, P, H, A, Dh,
+                                             scale, _stream()), 'lime_grouped_mlp_match_f32')
+    else:
+        check(lib.lime_grouped_mlp_match_indexed_f32(_p(kp), _p(gu), _p(qp), _p(nw), _p(w_out), _p(b_out), _p(offsets), _p(index), n,
+                                                     _p(logits), G, P, H, A, Dh, scale, _stream()), 'lime_grouped_mlp_match_indexed_f32')
+    return logits
+
+
+def mlp_predictor(user, news, mlp_w, mlp_b, out_w, out_b):
+    """The MLP click predictor on materialised rows, the composed form (reference model.py:182-184 in eval mode):
+    ``out(relu(mlp(cat[user, news])))`` for user [P, D], news [P, D] -> logits [P], on lime_linear_f32."""
+    hidden = linear(torch.cat([user, news], dim=1), mlp_w, mlp_b, act='relu')
+    return linear(hidden, out_w.reshape(1, -1), out_b).view(-1)
+
+
 def topk_rows(scores, k):
     """``lime_topk_rows_f32``: per row of scores [U, C] (a row-strided view is fine) the k best -> (positions int32 [U, k], scores fp32
     [U, k]) in descending order; equal scores (+0.0 == -0.0) lower position first, NaN behind every number; slots behind the C-th hold

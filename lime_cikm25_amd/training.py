@@ -956,10 +956,31 @@ def _is_crown_user(ue):
     return isinstance(ue, CROWN)
 
 
+# the dropout site of the MLP click predictor (model.py:183: Model.dropout behind the ReLU), a number of its own under a seed of its own
+_SITE_CLICK_PREDICTOR = 1
+
+
+def mlp_logits(model, user, cand):
+    """The MLP click predictor (model.py:182-184) with autograd: ``out(dropout(relu(mlp(cat[user, news]))))`` for user / cand
+    [B, N, D] -> logits [B, N].  ``mlp`` with its ReLU and ``out`` are ``_Linear`` nodes; the dropout is ``Model.dropout`` (p =
+    config.dropout_rate, active when that module is in training mode) on the counter-based masks."""
+    B, N, D = cand.shape
+    x = torch.cat([user.expand(B, N, D), cand], dim=2).reshape(B * N, 2 * D)
+    hidden = _Linear.apply(x, model.mlp.weight, model.mlp.bias, 'relu')
+    if model.dropout.training and model.dropout.p > 0:
+        hidden = _Dropout.apply(hidden, float(model.dropout.p), _draw_seed(), _SITE_CLICK_PREDICTOR)
+    return _Linear.apply(hidden, model.out.weight, model.out.bias, None).view(B, N)
+
+
 def user_logits(ue, weighting, hist, cand, category, subCategory, user_category, user_subCategory, user_history_mask,
-                remaining_lifetime, n_src=None):
+                remaining_lifetime, n_src=None, predictor=None):
     """The user encoder's forward after the history is encoded and the lifetime-weighted dot product of model.py:181 / util.py:23-49
-    -> logits [B, N].  CROWN: userEncoders.py:103-105, :114-169; ATT / MHSA: ``pooled_user`` + ``lifetime_weighted_logits``."""
+    -> logits [B, N].  CROWN: userEncoders.py:103-105, :114-169; ATT / MHSA: ``pooled_user`` + ``lifetime_weighted_logits``.
+    ``predictor``: the Model, when its click predictor is not the dot product -- 'mlp' (model.py:182-184): ``user_representation``,
+    then ``mlp_logits``; ``remaining_lifetime`` is not read."""
+    if predictor is not None and predictor.click_predictor == 'mlp':
+        user = user_representation(ue, hist, cand, category, subCategory, user_category, user_subCategory, user_history_mask, n_src)
+        return mlp_logits(predictor, user, cand)
     B, H, D = hist.shape
     N = cand.shape[1]
     if not _is_crown_user(ue):
@@ -1068,7 +1089,8 @@ def forward_train(model, user_category, user_subCategory, user_title_text, user_
     hist = rep[B * N:].view(B, H, -1)
     return user_logits(model.user_encoder, model.remaining_lifetime_weighting, hist, cand, i32(news_category).contiguous(),
                        i32(news_subCategory).contiguous(), i32(user_category).contiguous(), i32(user_subCategory).contiguous(),
-                       user_history_mask.contiguous(), remaining_lifetime.float().contiguous())
+                       user_history_mask.contiguous(), remaining_lifetime.float().contiguous(),
+                       predictor=model if model.click_predictor != 'dot_product' else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
