@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void dropout_add_ln_kernel(const float* __rest
             v[j] = x;
             s += x;
         }
-        const float mean = wave_sum(s) * inv_e;
+        const float mean = wave_sum(s) / (float)E;          // (a quotient: exact on a constant row, gemm_f32.hip says why)
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void dropout_add_ln_vec_kernel(const float* __
             s += (x[0] + x[1]) + (x[2] + x[3]);
         }
         s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
-        const float mean = s * inv_e;
+        const float mean = s / (float)E;
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < V4; ++j) {

@@ -389,7 +389,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN <= 4) ? 2 : 
                     float tot = 0.f;
 #pragma unroll
                     for (int w = 0; w < WN; ++w) tot += red_sum[w * BM + wrow0 + i * 32 + fi];
-                    mean[i] = tot * inv_n;
+                    // a quotient, not tot * inv_n: the exact sum of a constant row divides back to its value, and the
+                    // product would be fused into the subtraction below with the rounding of 1 / N in it
+                    mean[i] = tot / (float)p.N;
                     float q = 0.f;
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {

@@ -314,7 +314,6 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(const PPParams p) {
         tile_rc(tile, row0, col0);
         const float* const bs = Bs + (par ? BN : 0) + 4 * kg;
         const __amdgpu_buffer_rsrc_t rs_c = make_rsrc((char*)p.c + ((CID ? 0L : (long)row0 * p.ldc) + col0) * ES);
-        float sum[2] = {0.f, 0.f}, sq[2] = {0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < NT16; ++t) {
             const f32x4 b = *reinterpret_cast<const f32x4*>(bs + 16 * t);
@@ -326,23 +325,37 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(const PPParams p) {
                     for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
                 }
                 acc[tt][t] = v;
-                if constexpr (LN) {                    // columns beyond N are exact zeros (zero weights, zero bias)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { sum[tt] += v[j]; sq[tt] += v[j] * v[j]; }
-                }
             }
         }
         float mean[2] = {0.f, 0.f}, rstd[2] = {0.f, 0.f};
         if constexpr (LN) {
-            const float inv_n = 1.0f / (float)p.ln_count;        // the real columns (zero-padded ones add nothing to the sums)
+            // LayerNorm statistics as sums of v - shift, the shift being the row's own column 0 (lane (fi, kg = 0)):
+            // E[(v - shift)^2] - E[v - shift]^2 is conditioned by |mean - shift| / std (a few units), where E[v^2] - mean^2 loses
+            // mean^2 / var of the significand; a constant row gives mean = its value and variance 0 exactly.  A padded zero minus
+            // the shift is not zero: the columns beyond the real ones stay out.  One row at a time: one row's sums are live.
+            const float inv_n = 1.0f / (float)p.ln_count;        // the real columns
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
-                float s1 = sum[tt], s2 = sq[tt];
+                const float shift = __shfl(acc[tt][0][0], fi);
+                float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                for (int t = 0; t < NT16; ++t) {
+                    // fp32: ln_count = N, a multiple of 4; bf16: the caller's zero padding may begin anywhere (ln_count <= N)
+                    const int c = col0 + 16 * t + 4 * kg;
+                    const bool in = t < NT16 - 4 || c < p.N;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float d = (BF ? c + j < p.ln_count : in) ? acc[tt][t][j] - shift : 0.f;
+                        s1 += d;
+                        s2 += d * d;
+                    }
+                }
                 s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
                 s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-                mean[tt] = s1 * inv_n;
-                rstd[tt] = rsqrtf(fmaxf(s2 * inv_n - mean[tt] * mean[tt], 0.f) + p.ln_eps);
-
+                const float dm = s1 * inv_n;                     // mean - shift
+                mean[tt] = shift + dm;
+                rstd[tt] = rsqrtf(fmaxf(s2 * inv_n - dm * dm, 0.f) + p.ln_eps);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         unsigned cof[2];

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
     float* const Bs = reinterpret_cast<float*>(lds + O_BS);        // bias of the tile's columns, double-buffered by tile parity
     float* const Gs = reinterpret_cast<float*>(lds + O_GS);
     float* const Es = reinterpret_cast<float*>(lds + O_ES);
-    f32x2* const lnp = reinterpret_cast<f32x2*>(lds + O_LNP);      // [row][column half] partial (sum, sum of squares)
+    f32x2* const lnp = reinterpret_cast<f32x2*>(lds + O_LNP);      // [row][column half] the half's (mean, centred sum of squares)
     unsigned* const arow = reinterpret_cast<unsigned*>(lds + O_AROW);   // [2][256] byte offset of each tile row's A row (or OOB)
     int* const ids = reinterpret_cast<int*>(lds + O_IDS);          // [2][256] residual row ids (RES == 2) or output rows (CID)
 
@@ -280,7 +280,10 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
         int row0, col0;
         tile_rc(tile, row0, col0);
         const float* const bs = Bs + (par ? BN : 0) + cw0 + 4 * kg;
-        float sum[4] = {0.f, 0.f, 0.f, 0.f}, sq[4] = {0.f, 0.f, 0.f, 0.f};
+        // LayerNorm sums of v - shift (below): with the residual added in this epilogue (RES 2) they are taken as the values are made,
+        // else in a pass of their own
+        constexpr bool STATS_INLINE = LN && RES >= 2;
+        float sum[4] = {0.f, 0.f, 0.f, 0.f}, sq[4] = {0.f, 0.f, 0.f, 0.f}, shift[4] = {0.f, 0.f, 0.f, 0.f};
         unsigned rof[4] = {OOB, OOB, OOB, OOB}, pof[4] = {OOB, OOB, OOB, OOB};
         const __amdgpu_buffer_rsrc_t rs_res2 = make_rsrc(p.res ? (const void*)p.res : (const void*)p.w);
         const __amdgpu_buffer_rsrc_t rs_rpe2 = make_rsrc(p.res_pe ? (const void*)p.res_pe : (const void*)p.w);
@@ -356,33 +359,95 @@ __global__ __launch_bounds__(512, 2) void gemm_sp_kernel(const PPParams p) {
                     buf_store4(v, rs_c, (col0 + cw0 + 16 * t + 4 * kg < p.N) ? cof[i] + (unsigned)t * 64u : OOB, 0);
                 }
                 acc[i][t] = v;
-                if constexpr (LN) {                    // columns beyond N are exact zeros (zero weights, zero bias, no residual)
+                if constexpr (STATS_INLINE) {
+                    if (t == 0) shift[i] = __shfl(v[0], fi);
+                    if constexpr (RSTD) {
+                        if (t == 0) __builtin_amdgcn_sched_barrier(0);      // (keeps this instantiation inside its scratch allowance)
+                    }
+                    const bool in = col0 + cw0 + 16 * t + 4 * kg < p.N;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { sum[i] += v[j]; sq[i] += v[j] * v[j]; }
+                    for (int j = 0; j < 4; ++j) {
+                        const float d = in ? v[j] - shift[i] : 0.f;
+                        sum[i] += d;
+                        sq[i] += d * d;
+                    }
                 }
             }
             if constexpr (RES == 2 || RES == 3) __builtin_amdgcn_sched_barrier(0);      // one column tile's residual loads at a time
         }
         float mean[4] = {0.f, 0.f, 0.f, 0.f}, rstd[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (LN) {
-            // a row's columns are spread over the two column halves: the halves' partial sums meet in LDS
+        // LayerNorm: a row's columns are spread over the two column halves.  Each half sums v - shift over its n_h real columns, the
+        // shift being the first column this wave holds of the row (lane (fi, kg = 0)): what E[x^2] - mean^2 loses to cancellation is then
+        // set by |mean - shift| / std, not by mean / std, and a constant row gives its value and 0 exactly.  A padded zero minus the
+        // shift is not zero: the columns beyond N stay out.  The halves turn their sums into (mean, centred sum of squares), which meet in
+        // LDS and are merged pairwise (Chan et al.) -- the same operands in the same order in both halves (half 0, half 1), so the two
+        // waves of a row agree bit for bit.  The two forms below are one computation; each is the one the register allocator takes
+        // without more scratch than the instantiation had (tests/test_kernel_resources.py).
+        if constexpr (STATS_INLINE) {
+            const int left = p.N - col0 - cw0;
+            const float n_h = (float)(left <= 0 ? 0 : (left >= 16 * CT ? 16 * CT : left)), n_o = (float)p.ln_count - n_h;
+            const float inv_h = n_h > 0.f ? 1.0f / n_h : 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float s1 = sum[i], s2 = sq[i];
                 s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
                 s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-                sum[i] = s1; sq[i] = s2;
-                if (kg == 0) lnp[(64 * wr + 16 * i + fi) * 2 + wc] = f32x2{s1, s2};
+                const float dm = s1 * inv_h;                     // this half's mean - shift
+                sum[i] = shift[i] + dm;
+                sq[i] = fmaxf(s2 - s1 * dm, 0.f);
+                if (kg == 0) lnp[(64 * wr + 16 * i + fi) * 2 + wc] = f32x2{sum[i], sq[i]};
             }
             lds_barrier();
             const float inv_n = 1.0f / (float)p.ln_count;
+            const float n0 = wc ? n_o : n_h, n1 = wc ? n_h : n_o;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const f32x2 o = lnp[(64 * wr + 16 * i + fi) * 2 + (wc ^ 1)];
-                // the same association in both halves (half 0 + half 1): the two waves of a row agree bit for bit
-                const float s1 = wc ? o[0] + sum[i] : sum[i] + o[0], s2 = wc ? o[1] + sq[i] : sq[i] + o[1];
-                mean[i] = s1 * inv_n;
-                rstd[i] = rsqrtf(fmaxf(s2 * inv_n - mean[i] * mean[i], 0.f) + p.ln_eps);
+                const float m0 = wc ? o[0] : sum[i], m1 = wc ? sum[i] : o[0], q0 = wc ? o[1] : sq[i], q1 = wc ? sq[i] : o[1];
+                const float dl = n1 > 0.f ? m1 - m0 : 0.f;       // (a half without real columns has no mean)
+                mean[i] = m0 + dl * (n1 * inv_n);
+                rstd[i] = rsqrtf(((q0 + q1) + dl * dl * (n0 * n1 * inv_n)) * inv_n + p.ln_eps);
+            }
+        } else if constexpr (LN) {
+            // (the column counts and what is made of them are wave-uniform: kept in scalar registers, the vector ones are all taken)
+            auto uni = [](float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); };
+            const int left = p.N - col0 - cw0;
+            const int n_h = __builtin_amdgcn_readfirstlane(left <= 0 ? 0 : (left >= 16 * CT ? 16 * CT : left)), n_o = p.ln_count - n_h;
+            const float inv_h = uni(n_h > 0 ? 1.0f / (float)n_h : 0.f);
+            float hm[4], hq[4];                                  // the half's mean and centred sum of squares
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                        // one row at a time: one row's sums are live
+                const float sh = __shfl(acc[i][0][0], fi);
+                float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                for (int t = 0; t < CT; ++t) {
+                    const bool in = col0 + cw0 + 16 * t + 4 * kg < p.N;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float d = in ? acc[i][t][j] - sh : 0.f;
+                        s1 += d;
+                        s2 += d * d;
+                    }
+                }
+                s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
+                s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+                const float dm = s1 * inv_h;                     // this half's mean - shift
+                hm[i] = sh + dm;
+                hq[i] = fmaxf(s2 - s1 * dm, 0.f);
+                if (kg == 0) lnp[(64 * wr + 16 * i + fi) * 2 + wc] = f32x2{hm[i], hq[i]};
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            lds_barrier();
+            const float inv_n = uni(1.0f / (float)p.ln_count);
+            const int n0 = wc ? n_o : n_h, n1 = wc ? n_h : n_o;
+            const float w1 = uni((float)n1 * inv_n), w01 = uni((float)(n0 * n1) * inv_n * inv_n);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f32x2 o = lnp[(64 * wr + 16 * i + fi) * 2 + (wc ^ 1)];
+                const float m0 = wc ? o[0] : hm[i], m1 = wc ? hm[i] : o[0], q0 = wc ? o[1] : hq[i], q1 = wc ? hq[i] : o[1];
+                const float dl = n1 > 0 ? m1 - m0 : 0.f;         // (a half without real columns has no mean)
+                mean[i] = m0 + dl * w1;
+                rstd[i] = rsqrtf((q0 + q1) * inv_n + dl * dl * w01 + p.ln_eps);
             }
         }
         if constexpr (RSTD) {

@@ -937,7 +937,7 @@ __global__ __launch_bounds__(NW * 64) void gate_ln_sage_kernel(const float* __re
                 sum += v[j];
             }
         }
-        const float mean = wave_sum(sum) * inv_d;
+        const float mean = wave_sum(sum) / (float)D;        // (a quotient, as in gate_ln_kernel: exact on a constant row)
         float sq = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
