@@ -1254,6 +1254,25 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * index outside [0, n), n = 0 with P > 0 (LIME_ERR_BAD_ARG) and n < 2^31 are the rules of lime_grouped_match_indexed_f32, checked in
  * the same order before any launch.
  *
+ * lime_grouped_match_occurrence_f32 (csrc/grouped_match_f32.hip): the indexed form with each pair's own operands COMPOSED from a
+ * news table and an occurrence table -- qa [n, A] and ca [n, D] read through index int32 [P], qt [n_occ, A] and ct [n_occ, D] read
+ * through occ int32 [P] (both on the device):
+ *     qp[p, :] = qa[index[p], :] + qt[occ[p], :],   cand[p, :] = ca[index[p], :] + ct[occ[p], :]
+ * one fp32 add per element, a + t in that order, made while the operand is loaded.  A LIME candidate under 'add' or 'concat' +
+ * project is A[news] + T[b_f nb + b_l] with everything behind it linear (Model._candidate_tables): no [P, D] row and no [P, A] Q row
+ * exists.  A pair's bits equal those of lime_grouped_match_f32 on rows composed with that one fp32 add, and depend neither on P, G,
+ * the group's position, the pair's place in its tile, n nor n_occ.  index is CLAMPED into [0, n) and occ into [0, n_occ) by the
+ * kernel, as the offsets are.  LIME_ERR_BAD_ARG before any launch: a NULL index, occ or table, a table that is not 16-byte aligned,
+ * n = 0 or n_occ = 0 with P > 0; n, n_occ < 2^31 and the dims of lime_grouped_match_f32 (LIME_ERR_UNSUPPORTED beyond), checked in the
+ * order of lime_grouped_match_indexed_f32 with each occurrence check behind its indexed twin.  No LDS beyond the plain form's, no
+ * atomics.
+ *
+ * lime_grouped_mlp_match_occurrence_f32 (csrc/grouped_mlp_match_f32.hip): the same composition under the MLP click predictor --
+ *     qp[p, :] = qa[index[p], :] + qt[occ[p], :],   nw[p, :] = na[index[p], :] + nt[occ[p], :]
+ * with na [n, Dh] = ca W_n^T + mlp.bias and nt [n_occ, Dh] = ct W_n^T (no bias: it is in na).  A pair's bits equal those of
+ * lime_grouped_mlp_match_f32 on the composed rows; clamping, statuses and their order are those of
+ * lime_grouped_match_occurrence_f32, with na / nt 8-byte aligned as nw is.
+ *
  * lime_topk_rows_f32 (csrc/topk_rows_f32.hip): per row u < U of scores [U, C] (leading dimension ld >= C) the k best entries:
  * positions int32 [U, k] (column indices) and top_scores fp32 [U, k] (the input's bits at those positions), in descending order of
  * the score; equal scores -- +0.0 and -0.0 are equal -- lower position first; a NaN ranks behind every number, NaNs in position
@@ -1274,6 +1293,15 @@ int lime_grouped_mlp_match_f32(const float* kp, const float* gu, const float* qp
 int lime_grouped_mlp_match_indexed_f32(const float* kp, const float* gu, const float* qp, const float* nw, const float* w_out,
                                        const float* b_out, const int64_t* offsets, const int32_t* index, int64_t n, float* logits,
                                        int64_t G, int64_t P, int32_t H, int32_t A, int32_t Dh, float scale, void* stream);
+int lime_grouped_match_occurrence_f32(const float* kp, const float* g, const float* qa, const float* ca, const float* qt, const float* ct,
+                                      const float* remaining, const int64_t* offsets, const int32_t* index, int64_t n,
+                                      const int32_t* occ, int64_t n_occ, float* logits, int64_t G, int64_t P, int32_t H, int32_t A,
+                                      int32_t D, float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty,
+                                      void* stream);
+int lime_grouped_mlp_match_occurrence_f32(const float* kp, const float* gu, const float* qa, const float* na, const float* qt,
+                                          const float* nt, const float* w_out, const float* b_out, const int64_t* offsets,
+                                          const int32_t* index, int64_t n, const int32_t* occ, int64_t n_occ, float* logits, int64_t G,
+                                          int64_t P, int32_t H, int32_t A, int32_t Dh, float scale, void* stream);
 int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);

@@ -21,6 +21,12 @@
 // pair p reads row index[p] of both -- a candidate whose representation depends on the news alone is not copied once per (user,
 // candidate) pair.  Nothing else changes: only the row that gm_tile_product reads as Y differs, so a pair's bits are those of the plain
 // form on the gathered rows.  An index outside [0, n) is clamped into it (as the offsets are clamped): a bad plan reads in range.
+//
+// The occurrence-composed form (lime_grouped_match_occurrence_f32): a LIME candidate under 'add' or 'concat' + project is
+// A[news] + T[occurrence] with everything behind it linear, so the pair's operands are sums of a row of a news table and a row of an
+// occurrence table: qp = qa[index[p]] + qt[occ[p]], cand = ca[index[p]] + ct[occ[p]], one fp32 add per element as the operand is
+// fetched (gm_tile_product<T, true>).  A pair's bits are those of the plain form on rows composed with that add; occ is clamped into
+// [0, n_occ) as index is into [0, n).  No LDS beyond the plain form's, no atomics.
 #include "grouped_tile.h"        // the tile product and the softmax, shared with grouped_mlp_match_f32.hip
 
 namespace {
@@ -28,13 +34,16 @@ namespace {
 using namespace lime_dev;
 
 // INDEXED: qp / cand are tables of n rows and pair p reads row index[p] (clamped into [0, n)) of both; else row p (index unread).
-template <int T, bool INDEXED>
+// OCC: nothing, or one GmOccurrence behind the other arguments (the occurrence-composed form, INDEXED): the pair's operands are its
+// table rows plus row occ[p] (clamped into [0, n_occ)) of the occurrence tables.  A trailing pack, so that the plain and the indexed
+// instantiations keep their signatures and their code.
+template <int T, bool INDEXED, class... OCC>
 __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restrict__ kp, const float* __restrict__ g,
                                                              const float* __restrict__ qp, const float* __restrict__ cand,
                                                              const float* __restrict__ remaining, const long* __restrict__ offsets,
                                                              const int* __restrict__ index, int n, float* __restrict__ logits, long P, int H,
                                                              int A, int D, float scale, float alpha_s, float beta_s, int use_weight,
-                                                             int use_penalty) {
+                                                             int use_penalty, OCC... occurrence) {
     __shared__ __attribute__((aligned(16))) float img[2 * 16 * T * GM_CHUNK];
     const long grp = blockIdx.x;
     long lo = offsets[grp], hi = offsets[grp + 1];
@@ -51,8 +60,15 @@ __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restr
             y = i < 0 ? 0 : (i >= n ? n - 1 : i);
         }
         f32x4 s[T], m[T];
-        gm_tile_product<T>(kp, grp * H, H, qp, y, live, A, img, s);
-        gm_tile_product<T>(g, grp * H, H, cand, y, live, D, img, m);
+        if constexpr (sizeof...(OCC) != 0) {
+            const GmOccurrence oc = (occurrence, ...);
+            const long z = gm_occurrence_row(oc, p, live);   // the pair's row of the occurrence tables qt (oc.qt) and ct (oc.vt)
+            gm_tile_product<T, true>(kp, grp * H, H, qp, y, live, A, img, s, oc.qt, z);
+            gm_tile_product<T, true>(g, grp * H, H, cand, y, live, D, img, m, oc.vt, z);
+        } else {
+            gm_tile_product<T>(kp, grp * H, H, qp, y, live, A, img, s);
+            gm_tile_product<T>(g, grp * H, H, cand, y, live, D, img, m);
+        }
         // softmax over the history (grouped_tile.h: s becomes exp(s - max)) and the weighted sum, on this lane's 4 T values of its pair
         float den = gm_tile_softmax<T>(s, H, scale), num = 0.f;
 #pragma unroll
@@ -72,20 +88,26 @@ __global__ __launch_bounds__(256) void grouped_match_kernel(const float* __restr
 
 namespace {
 
-// The checks and the launch both entries share.  index == nullptr: the plain form (qp / cand hold P rows).
-int grouped_match_launch(const char* who, const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
-                         const int64_t* offsets, const int32_t* index, int64_t n, bool indexed, float* logits, int64_t G, int64_t P,
-                         int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s, int32_t use_weight,
-                         int32_t use_penalty, void* stream) {
-    LIME_REQUIRE(kp && g && qp && cand && offsets && logits && (!indexed || index), LIME_ERR_BAD_ARG, "%s: NULL pointer", who);
+// The checks and the launch the three entries share.  form GM_PLAIN: qp / cand hold P rows (index unread); GM_INDEXED: tables of n rows;
+// GM_OCCURRENCE: those tables plus qt / ct of n_occ rows, read through occ.
+int grouped_match_launch(const char* who, int form, const float* kp, const float* g, const float* qp, const float* cand, const float* qt,
+                         const float* ct, const float* remaining, const int64_t* offsets, const int32_t* index, int64_t n,
+                         const int32_t* occ, int64_t n_occ, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D,
+                         float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream) {
+    const bool indexed = form != GM_PLAIN, composed = form == GM_OCCURRENCE;
+    LIME_REQUIRE(kp && g && qp && cand && offsets && logits && (!indexed || index) && (!composed || (qt && ct && occ)), LIME_ERR_BAD_ARG,
+                 "%s: NULL pointer", who);
     LIME_REQUIRE(!use_weight || remaining, LIME_ERR_BAD_ARG, "%s: remaining is NULL", who);
-    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && D > 0 && n >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
-    LIME_REQUIRE(H <= 128 && A <= 2048 && D <= 2048 && A % 4 == 0 && D % 4 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
-                 "%s: H %d, A %d, D %d outside 1 <= H <= 128, A and D multiples of 4 up to 2048 (or %lld groups / %lld table rows >= 2^31)",
-                 who, H, A, D, (long long)G, (long long)n);
-    LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qp, A) && lime_al16(g, D) && lime_al16(cand, D), LIME_ERR_BAD_ARG,
-                 "%s: kp, qp, g and cand must be 16-byte aligned", who);
+    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && D > 0 && n >= 0 && n_occ >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
+    LIME_REQUIRE(H <= 128 && A <= 2048 && D <= 2048 && A % 4 == 0 && D % 4 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL &&
+                     n_occ <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
+                 "%s: H %d, A %d, D %d outside 1 <= H <= 128, A and D multiples of 4 up to 2048 (or %lld groups / %lld, %lld table rows >= 2^31)",
+                 who, H, A, D, (long long)G, (long long)n, (long long)n_occ);
+    LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qp, A) && lime_al16(g, D) && lime_al16(cand, D) &&
+                     (!composed || (lime_al16(qt, A) && lime_al16(ct, D))), LIME_ERR_BAD_ARG,
+                 "%s: kp, qp, g and cand (and the occurrence tables) must be 16-byte aligned", who);
     LIME_REQUIRE(!indexed || n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
+    LIME_REQUIRE(!composed || n_occ > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty occurrence table", who, (long long)P);
     if (G == 0 || P == 0) return LIME_OK;
     // tile slices per group: enough workgroups to fill the chip when the groups are few (one group per user with the candidate-aware
     // attention off), never more than the tiles the pairs can make.  The split changes which workgroup takes a tile, not its bits.
@@ -98,16 +120,22 @@ int grouped_match_launch(const char* who, const float* kp, const float* g, const
     hipLaunchKernelGGL((grouped_match_kernel<T_, I_>), grid, dim3(256), 0, (hipStream_t)stream, kp, g, qp, cand, remaining,             \
                        (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, D, scale, alpha_s, beta_s, use_weight,   \
                        use_penalty)
-#define LIME_GM_PICK(I_)                                                                                                                \
+#define LIME_GM_LAUNCH_OCC(T_, I_)                                                                                                      \
+    hipLaunchKernelGGL((grouped_match_kernel<T_, I_, GmOccurrence>), grid, dim3(256), 0, (hipStream_t)stream, kp, g, qp, cand,          \
+                       remaining, (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, D, scale, alpha_s, beta_s,    \
+                       use_weight, use_penalty, GmOccurrence{qt, ct, (const int*)occ, (int)n_occ})
+#define LIME_GM_PICK(L_, I_)                                                                                                            \
     do {                                                                                                                                \
-        if (H <= 16) LIME_GM_LAUNCH(1, I_);                                                                                             \
-        else if (H <= 32) LIME_GM_LAUNCH(2, I_);                                                                                        \
-        else if (H <= 64) LIME_GM_LAUNCH(4, I_);                                                                                        \
-        else LIME_GM_LAUNCH(8, I_);                                                                                                     \
+        if (H <= 16) L_(1, I_);                                                                                                         \
+        else if (H <= 32) L_(2, I_);                                                                                                    \
+        else if (H <= 64) L_(4, I_);                                                                                                    \
+        else L_(8, I_);                                                                                                                 \
     } while (0)
-    if (indexed) LIME_GM_PICK(true);
-    else LIME_GM_PICK(false);
+    if (composed) LIME_GM_PICK(LIME_GM_LAUNCH_OCC, true);
+    else if (indexed) LIME_GM_PICK(LIME_GM_LAUNCH, true);
+    else LIME_GM_PICK(LIME_GM_LAUNCH, false);
 #undef LIME_GM_PICK
+#undef LIME_GM_LAUNCH_OCC
 #undef LIME_GM_LAUNCH
     return lime_check_launch(who);
 }
@@ -117,14 +145,23 @@ int grouped_match_launch(const char* who, const float* kp, const float* g, const
 extern "C" int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
                                       const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D,
                                       float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream) {
-    return grouped_match_launch("lime_grouped_match_f32", kp, g, qp, cand, remaining, offsets, nullptr, 0, false, logits, G, P, H, A, D,
-                                scale, alpha_s, beta_s, use_weight, use_penalty, stream);
+    return grouped_match_launch("lime_grouped_match_f32", GM_PLAIN, kp, g, qp, cand, nullptr, nullptr, remaining, offsets, nullptr, 0,
+                                nullptr, 0, logits, G, P, H, A, D, scale, alpha_s, beta_s, use_weight, use_penalty, stream);
 }
 
 extern "C" int lime_grouped_match_indexed_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
                                               const int64_t* offsets, const int32_t* index, int64_t n, float* logits, int64_t G, int64_t P,
                                               int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s,
                                               int32_t use_weight, int32_t use_penalty, void* stream) {
-    return grouped_match_launch("lime_grouped_match_indexed_f32", kp, g, qp, cand, remaining, offsets, index, n, true, logits, G, P, H, A,
-                                D, scale, alpha_s, beta_s, use_weight, use_penalty, stream);
+    return grouped_match_launch("lime_grouped_match_indexed_f32", GM_INDEXED, kp, g, qp, cand, nullptr, nullptr, remaining, offsets, index,
+                                n, nullptr, 0, logits, G, P, H, A, D, scale, alpha_s, beta_s, use_weight, use_penalty, stream);
+}
+
+extern "C" int lime_grouped_match_occurrence_f32(const float* kp, const float* g, const float* qa, const float* ca, const float* qt,
+                                                 const float* ct, const float* remaining, const int64_t* offsets, const int32_t* index,
+                                                 int64_t n, const int32_t* occ, int64_t n_occ, float* logits, int64_t G, int64_t P,
+                                                 int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s,
+                                                 int32_t use_weight, int32_t use_penalty, void* stream) {
+    return grouped_match_launch("lime_grouped_match_occurrence_f32", GM_OCCURRENCE, kp, g, qa, ca, qt, ct, remaining, offsets, index, n,
+                                occ, n_occ, logits, G, P, H, A, D, scale, alpha_s, beta_s, use_weight, use_penalty, stream);
 }

@@ -23,6 +23,8 @@
 //
 // The indexed form (lime_grouped_mlp_match_indexed_f32): qp [n, A] and nw [n, Dh] are tables and pair p reads row index[p] of both,
 // clamped into [0, n) -- the rules of lime_grouped_match_indexed_f32.
+// The occurrence-composed form (lime_grouped_mlp_match_occurrence_f32): qp = qa[index[p]] + qt[occ[p]] and nw = na[index[p]] +
+// nt[occ[p]], one fp32 add per element as the operand is fetched -- the rules of lime_grouped_match_occurrence_f32.
 #include "grouped_tile.h"
 
 namespace {
@@ -32,12 +34,15 @@ using namespace lime_dev;
 constexpr int GS = 20;               // floats of an LDS row of the gu chunk (16 used): the four k slots' rows, 4 apart, land 80 floats
                                      // = 16 banks apart, so a wave's ds_read_b32 of 4 rows x 16 columns touches every bank once
 
-template <int T, bool INDEXED>
+// INDEXED, OCC: as in grouped_match_f32.hip -- the pair's row p of qp / nw, row index[p] of two tables, or (one GmOccurrence behind the
+// other arguments) that row plus row occ[p] of the occurrence tables qt (oc.qt) and nt (oc.vt).
+template <int T, bool INDEXED, class... OCC>
 __global__ __launch_bounds__(256) void grouped_mlp_match_kernel(const float* __restrict__ kp, const float* __restrict__ gu,
                                                                  const float* __restrict__ qp, const float* __restrict__ nw,
                                                                  const float* __restrict__ w_out, const float* __restrict__ b_out,
                                                                  const long* __restrict__ offsets, const int* __restrict__ index, int n,
-                                                                 float* __restrict__ logits, long P, int H, int A, int Dh, float scale) {
+                                                                 float* __restrict__ logits, long P, int H, int A, int Dh, float scale,
+                                                                 OCC... occurrence) {
     constexpr int ROWS = 16 * T;
     constexpr int NP = T < 2 ? 1 : T / 2;                    // 8-byte pieces of a gu chunk per thread: 16 T rows x 8 pieces / 256
     __shared__ __attribute__((aligned(16))) float img[2 * ROWS * GS];       // (the first product uses 2 * ROWS * GM_CHUNK of it)
@@ -60,7 +65,16 @@ __global__ __launch_bounds__(256) void grouped_mlp_match_kernel(const float* __r
             y = i < 0 ? 0 : (i >= n ? n - 1 : i);
         }
         f32x4 a[T];
-        gm_tile_product<T>(kp, x0, H, qp, y, live, A, img, a);
+        const float* nt = nullptr;                           // the occurrence table beside nw and the pair's row of it (composed form)
+        long z = 0;
+        if constexpr (sizeof...(OCC) != 0) {
+            const GmOccurrence oc = (occurrence, ...);
+            nt = oc.vt;
+            z = gm_occurrence_row(oc, p, live);
+            gm_tile_product<T, true>(kp, x0, H, qp, y, live, A, img, a, oc.qt, z);
+        } else {
+            gm_tile_product<T>(kp, x0, H, qp, y, live, A, img, a);
+        }
         const float den = gm_tile_softmax<T>(a, H, scale);
 #pragma unroll
         for (int t = 0; t < T; ++t)
@@ -81,6 +95,10 @@ __global__ __launch_bounds__(256) void grouped_mlp_match_kernel(const float* __r
                                                              // columns lies within the row or behind it)
             n0 = (live && col < Dh) ? *reinterpret_cast<const f32x2*>(nw + y * Dh + col) : f32x2{0.f, 0.f};
             n1 = (live && col + 2 < Dh) ? *reinterpret_cast<const f32x2*>(nw + y * Dh + col + 2) : f32x2{0.f, 0.f};
+            if constexpr (sizeof...(OCC) != 0) {             // nw = na[index] + nt[occ], a + t, as the columns are fetched
+                n0 += (live && col < Dh) ? *reinterpret_cast<const f32x2*>(nt + z * Dh + col) : f32x2{0.f, 0.f};
+                n1 += (live && col + 2 < Dh) ? *reinterpret_cast<const f32x2*>(nt + z * Dh + col + 2) : f32x2{0.f, 0.f};
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) wo[r] = col + r < Dh ? w_out[col + r] : 0.f;
         };
@@ -115,19 +133,25 @@ __global__ __launch_bounds__(256) void grouped_mlp_match_kernel(const float* __r
     }
 }
 
-// The checks and the launch both entries share.  index == nullptr: the plain form (qp / nw hold P rows).
-int grouped_mlp_match_launch(const char* who, const float* kp, const float* gu, const float* qp, const float* nw, const float* w_out,
-                             const float* b_out, const int64_t* offsets, const int32_t* index, int64_t n, bool indexed, float* logits,
-                             int64_t G, int64_t P, int32_t H, int32_t A, int32_t Dh, float scale, void* stream) {
-    LIME_REQUIRE(kp && gu && qp && nw && w_out && offsets && logits && (!indexed || index), LIME_ERR_BAD_ARG, "%s: NULL pointer", who);
-    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && Dh > 0 && n >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
-    LIME_REQUIRE(H <= 128 && A <= 2048 && Dh <= 2048 && A % 4 == 0 && Dh % 2 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL,
-                 LIME_ERR_UNSUPPORTED,
-                 "%s: H %d, A %d, Dh %d outside 1 <= H <= 128, A a multiple of 4 and Dh even, both up to 2048 (or %lld groups / %lld table "
-                 "rows >= 2^31)", who, H, A, Dh, (long long)G, (long long)n);
+// The checks and the launch the three entries share.  form GM_PLAIN: qp / nw hold P rows (index unread); GM_INDEXED: tables of n rows;
+// GM_OCCURRENCE: those tables plus qt / nt of n_occ rows, read through occ.
+int grouped_mlp_match_launch(const char* who, int form, const float* kp, const float* gu, const float* qp, const float* nw, const float* qt,
+                             const float* nt, const float* w_out, const float* b_out, const int64_t* offsets, const int32_t* index,
+                             int64_t n, const int32_t* occ, int64_t n_occ, float* logits, int64_t G, int64_t P, int32_t H, int32_t A,
+                             int32_t Dh, float scale, void* stream) {
+    const bool indexed = form != GM_PLAIN, composed = form == GM_OCCURRENCE;
+    LIME_REQUIRE(kp && gu && qp && nw && w_out && offsets && logits && (!indexed || index) && (!composed || (qt && nt && occ)),
+                 LIME_ERR_BAD_ARG, "%s: NULL pointer", who);
+    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && Dh > 0 && n >= 0 && n_occ >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
+    LIME_REQUIRE(H <= 128 && A <= 2048 && Dh <= 2048 && A % 4 == 0 && Dh % 2 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL &&
+                     n_occ <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
+                 "%s: H %d, A %d, Dh %d outside 1 <= H <= 128, A a multiple of 4 and Dh even, both up to 2048 (or %lld groups / %lld, %lld "
+                 "table rows >= 2^31)", who, H, A, Dh, (long long)G, (long long)n, (long long)n_occ);
     LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qp, A) && (uintptr_t)gu % 8 == 0 && (uintptr_t)nw % 8 == 0 && (uintptr_t)w_out % 4 == 0 &&
-                     (uintptr_t)b_out % 4 == 0, LIME_ERR_BAD_ARG, "%s: kp and qp must be 16-byte aligned, gu and nw 8-byte aligned", who);
+                     (uintptr_t)b_out % 4 == 0 && (!composed || (lime_al16(qt, A) && (uintptr_t)nt % 8 == 0)), LIME_ERR_BAD_ARG,
+                 "%s: kp and qp (and qt) must be 16-byte aligned, gu and nw (and nt) 8-byte aligned", who);
     LIME_REQUIRE(!indexed || n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
+    LIME_REQUIRE(!composed || n_occ > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty occurrence table", who, (long long)P);
     if (G == 0 || P == 0) return LIME_OK;
     // tile slices per group, as in lime_grouped_match_f32: the split changes which workgroup takes a tile, not its bits
     const long all_tiles = (P + GM_PAIRS - 1) / GM_PAIRS;
@@ -138,16 +162,22 @@ int grouped_mlp_match_launch(const char* who, const float* kp, const float* gu, 
 #define LIME_GMM_LAUNCH(T_, I_)                                                                                                         \
     hipLaunchKernelGGL((grouped_mlp_match_kernel<T_, I_>), grid, dim3(256), 0, (hipStream_t)stream, kp, gu, qp, nw, w_out, b_out,       \
                        (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, Dh, scale)
-#define LIME_GMM_PICK(I_)                                                                                                               \
+#define LIME_GMM_LAUNCH_OCC(T_, I_)                                                                                                     \
+    hipLaunchKernelGGL((grouped_mlp_match_kernel<T_, I_, GmOccurrence>), grid, dim3(256), 0, (hipStream_t)stream, kp, gu, qp, nw,       \
+                       w_out, b_out, (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, Dh, scale,                 \
+                       GmOccurrence{qt, nt, (const int*)occ, (int)n_occ})
+#define LIME_GMM_PICK(L_, I_)                                                                                                           \
     do {                                                                                                                                \
-        if (H <= 16) LIME_GMM_LAUNCH(1, I_);                                                                                            \
-        else if (H <= 32) LIME_GMM_LAUNCH(2, I_);                                                                                       \
-        else if (H <= 64) LIME_GMM_LAUNCH(4, I_);                                                                                       \
-        else LIME_GMM_LAUNCH(8, I_);                                                                                                    \
+        if (H <= 16) L_(1, I_);                                                                                                         \
+        else if (H <= 32) L_(2, I_);                                                                                                    \
+        else if (H <= 64) L_(4, I_);                                                                                                    \
+        else L_(8, I_);                                                                                                                 \
     } while (0)
-    if (indexed) LIME_GMM_PICK(true);
-    else LIME_GMM_PICK(false);
+    if (composed) LIME_GMM_PICK(LIME_GMM_LAUNCH_OCC, true);
+    else if (indexed) LIME_GMM_PICK(LIME_GMM_LAUNCH, true);
+    else LIME_GMM_PICK(LIME_GMM_LAUNCH, false);
 #undef LIME_GMM_PICK
+#undef LIME_GMM_LAUNCH_OCC
 #undef LIME_GMM_LAUNCH
     return lime_check_launch(who);
 }
@@ -157,14 +187,22 @@ int grouped_mlp_match_launch(const char* who, const float* kp, const float* gu, 
 extern "C" int lime_grouped_mlp_match_f32(const float* kp, const float* gu, const float* qp, const float* nw, const float* w_out,
                                           const float* b_out, const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H,
                                           int32_t A, int32_t Dh, float scale, void* stream) {
-    return grouped_mlp_match_launch("lime_grouped_mlp_match_f32", kp, gu, qp, nw, w_out, b_out, offsets, nullptr, 0, false, logits, G, P,
-                                    H, A, Dh, scale, stream);
+    return grouped_mlp_match_launch("lime_grouped_mlp_match_f32", GM_PLAIN, kp, gu, qp, nw, nullptr, nullptr, w_out, b_out, offsets, nullptr,
+                                    0, nullptr, 0, logits, G, P, H, A, Dh, scale, stream);
 }
 
 extern "C" int lime_grouped_mlp_match_indexed_f32(const float* kp, const float* gu, const float* qp, const float* nw, const float* w_out,
                                                   const float* b_out, const int64_t* offsets, const int32_t* index, int64_t n,
                                                   float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t Dh, float scale,
                                                   void* stream) {
-    return grouped_mlp_match_launch("lime_grouped_mlp_match_indexed_f32", kp, gu, qp, nw, w_out, b_out, offsets, index, n, true, logits,
-                                    G, P, H, A, Dh, scale, stream);
+    return grouped_mlp_match_launch("lime_grouped_mlp_match_indexed_f32", GM_INDEXED, kp, gu, qp, nw, nullptr, nullptr, w_out, b_out,
+                                    offsets, index, n, nullptr, 0, logits, G, P, H, A, Dh, scale, stream);
+}
+
+extern "C" int lime_grouped_mlp_match_occurrence_f32(const float* kp, const float* gu, const float* qa, const float* na, const float* qt,
+                                                     const float* nt, const float* w_out, const float* b_out, const int64_t* offsets,
+                                                     const int32_t* index, int64_t n, const int32_t* occ, int64_t n_occ, float* logits,
+                                                     int64_t G, int64_t P, int32_t H, int32_t A, int32_t Dh, float scale, void* stream) {
+    return grouped_mlp_match_launch("lime_grouped_mlp_match_occurrence_f32", GM_OCCURRENCE, kp, gu, qa, na, qt, nt, w_out, b_out, offsets,
+                                    index, n, occ, n_occ, logits, G, P, H, A, Dh, scale, stream);
 }

@@ -10,12 +10,33 @@ constexpr int GM_PAIRS = 64;            // pairs of a workgroup tile: 16 per wav
 constexpr int GM_CHUNK = 16;            // columns of an LDS chunk: one 64-byte row of the swizzled image
 constexpr int GM_FLUSH = 2;             // chunks between two flushes of the MFMA accumulators into the compensated sum
 
+// Where a pair's own operands come from: its own row p (GM_PLAIN); row index[p] of a table (GM_INDEXED); or that row plus row occ[p]
+// of an occurrence table, one fp32 add per element (GM_OCCURRENCE).
+constexpr int GM_PLAIN = 0, GM_INDEXED = 1, GM_OCCURRENCE = 2;
+
+// What the occurrence-composed form adds to the indexed form's arguments: qt [n_occ, A] beside the qp table, vt [n_occ, D or Dh]
+// beside the table of the second operand (cand / nw), and the pairs' rows of both, occ int32 [P].
+struct GmOccurrence {
+    const float* qt;
+    const float* vt;
+    const int* occ;
+    int n_occ;
+};
+
+// Pair p's row of the occurrence tables: occ[p] clamped into [0, n_occ), as an index is into [0, n) -- a bad plan reads in range.
+__device__ __forceinline__ long gm_occurrence_row(const GmOccurrence& oc, long p, bool live) {
+    const int o = live ? oc.occ[p] : 0;
+    return o < 0 ? 0 : (o >= oc.n_occ ? oc.n_occ - 1 : o);
+}
+
 // One [16 T x 16] tile product per wave over K columns: out[t][r] = X[16 t + 4 (lane >> 4) + r, :K] . Y[pair of lane & 15, :K].
 // X: the group's rows x0 .. x0 + H - 1 of a dense [*, K] matrix (shared by the workgroup, through `img`); Y: row `yrow` of a dense
 // [*, K] matrix, or nothing (zeros) when `ylive` is false.  Ends with a barrier: `img` is free again when it returns.
-template <int T>
+// ADD (the occurrence-composed forms): the pair's operand is Y[yrow, :] + Y2[y2row, :], one fp32 add per element, a + t in that order,
+// made when the chunk is fetched -- only the sum lives across the barrier, and the product is that of the plain form on the composed row.
+template <int T, bool ADD = false>
 __device__ __forceinline__ void gm_tile_product(const float* __restrict__ X, long x0, int H, const float* __restrict__ Y, long yrow, bool ylive,
-                                             int K, float* img, f32x4 (&out)[T]) {
+                                             int K, float* img, f32x4 (&out)[T], const float* __restrict__ Y2 = nullptr, long y2row = 0) {
     constexpr int NL = T < 4 ? 1 : T / 4;                    // 16-byte pieces of a chunk per thread: 16 T rows x 4 segments / 256
     const int lane = threadIdx.x & 63;
     const int ar = lane & 15, as = lane >> 4;                // this lane's row of a 16-row tile and its 16-byte segment
@@ -36,6 +57,7 @@ __device__ __forceinline__ void gm_tile_product(const float* __restrict__ X, lon
         }
         const int col = c * GM_CHUNK + 4 * as;
         ys = (ylive && col < K) ? *reinterpret_cast<const f32x4*>(Y + yrow * K + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (ADD) ys += (ylive && col < K) ? *reinterpret_cast<const f32x4*>(Y2 + y2row * K + col) : f32x4{0.f, 0.f, 0.f, 0.f};
     };
 
     // The accumulators are emptied every GM_FLUSH chunks into a compensated sum (tot + comp, Knuth's two-sum): one fmaf chain over all

@@ -47,6 +47,12 @@ _REFUSED_CLICK_PREDICTORS = {
 # (lime_grouped_match_indexed_f32).  LIME_INDEXED_MATCH=0 keeps the gather form for them too -- one materialised row and one Q row per
 # (user, candidate) pair, the path LIME models take -- as the yardstick of the indexed one (tools/bench_recommend.py, tools/bench_lists.py).
 INDEXED_MATCH = os.environ.get('LIME_INDEXED_MATCH', '1') != '0'
+# A LIME candidate under 'add' or 'concat' + project is A[news] + T[occurrence] with everything behind it linear: the grouped match
+# composes it from a news table and an occurrence table while it loads the pair's operand (lime_grouped_match_occurrence_f32,
+# Model.occurrence_match_applicable), and no row, Q row or nw row exists per (user, candidate) pair.  Off by default: every path is
+# then the materialised one, bit for bit; LIME_OCCURRENCE_MATCH=1 turns it on (tools/bench_recommend.py and tools/bench_lists.py
+# alternate the two, DESIGN.md "LIME candidates in place").
+OCCURRENCE_MATCH = os.environ.get('LIME_OCCURRENCE_MATCH', '0') != '0'
 
 
 class Model(nn.Module):
@@ -468,7 +474,10 @@ class Model(nn.Module):
         CNE has no per-news cache and is refused (ValueError).
         A baseline model (no LIME): a candidate's row depends on the news alone, so the pool's C rows (and their Q) are made once per
         call and every pair reads them in place through its pool position (lime_grouped_match_indexed_f32, ``_candidate_tables``); the
-        passes are then bounded by the refined history rows alone.  LIME_INDEXED_MATCH=0 keeps the per-pair rows."""
+        passes are then bounded by the refined history rows alone.  LIME_INDEXED_MATCH=0 keeps the per-pair rows.
+        A LIME model with LIME_OCCURRENCE_MATCH=1 where ``occurrence_match_applicable()`` holds: the pool's cache rows (with their Q /
+        MLP news half) are one set of tables and ``occurrence_tables()`` (with theirs) another, and every pair is composed from a row
+        of each in the kernel (lime_grouped_match_occurrence_f32) -- no ``encode_cached``, Q or MLP GEMM runs over the pairs."""
         return self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                                 cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
 
@@ -500,12 +509,14 @@ class Model(nn.Module):
                                      hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
         if tables is None:
             cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))       # [pairs, D]
-            at = None
+            at = occ = None
         else:
             cand = None                                                                             # the call's tables, read in place
             at = newsEncoders._i32(pick(position).reshape(-1)).contiguous()                         # int32 [pairs]: the pair's table row
+            # a LIME model's occurrence tables: the pair's row of them is its bucket pair -- two bucket launches, no row per pair
+            occ = None if tables[3] is None else ne.occurrence_ids(pick(freshness), pick(lifetime))
         return self._click_logits(operands, cand, pick(remaining).reshape(-1), torch.as_tensor(group_offsets, device=dev), H, tables=tables,
-                                  index=at)
+                                  index=at, occ=occ)
 
     def _offsets_of_rows(self, groups, pairs, device):
         """int64 [groups + 1] on the device: the CSR of the regular shape, ``pairs`` pairs per group.  Kept per shape: a captured forward
@@ -537,13 +548,15 @@ class Model(nn.Module):
         per = B * N // groups
         return self._click_logits(operands, flat, None, self._offsets_of_rows(groups, per, flat.device), hist.shape[1], regular=per).view(B, N)
 
-    def _click_logits(self, operands, cand, remaining, offsets, H, tables=None, index=None, regular=None):
+    def _click_logits(self, operands, cand, remaining, offsets, H, tables=None, index=None, occ=None, regular=None):
         """The ONE place that turns (user-side operands, candidates) into logits, for either click predictor -> fp32 [pairs].
         ``operands``: what ``user_encoder.match_operands`` gave for G groups -- CROWN: (g [G, H, D], kp [G H, A], qp [pairs, A] or None:
         made here); ATT / MHSA: the pooled vector [G, D], a history of ONE row whose softmax weight is 1 (kp and qp are not felt).
         ``cand`` [pairs, D] in group order and ``offsets`` int64 [G + 1] their CSR; or ``tables`` (``_candidate_tables``) read in place
-        through ``index`` int32 [pairs].  ``remaining`` [pairs]: read by the dot product's lifetime weight alone.  ``regular``: the pairs
-        per group where every group has as many (the [B, N] shape).
+        through ``index`` int32 [pairs] -- and, where the tables carry occurrence tables (a LIME model), composed with the row ``occ``
+        int32 [pairs] of those in the kernel (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  ``remaining``
+        [pairs]: read by the dot product's lifetime weight alone.  ``regular``: the pairs per group where every group has as many (the
+        [B, N] shape).
 
         dot_product (model.py:179-181): lime_grouped_match_f32.  mlp (:182-184): with mlp.weight split into its user half W_u and its
         news half W_n, gu = g W_u^T once per history row and nw = cand W_n^T + mlp.bias once per candidate row (a table for a baseline
@@ -566,14 +579,17 @@ class Model(nn.Module):
             qp = tables[1] if tables is not None else torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=g.device)
         if tables is not None:
             cand = tables[0]
+        ct, qt, nt = tables[3] if tables is not None and tables[3] is not None else (None, None, None)
         if self.click_predictor == 'dot_product':
+            composed = dict(occ=occ, qt=qt, ct=ct) if ct is not None else {}
             return ops.grouped_match(kp, g, qp, cand, remaining, offsets, h_match, scale, w.alpha, w.beta,
-                                     bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=index)
+                                     bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=index, **composed)
         mlp, out = self.mlp, self.out
         if ops.FUSED_MLP_MATCH:
             gu = ops.linear(g, mlp.weight[:, :D], None)
             nw = tables[2] if tables is not None else ops.linear(cand, mlp.weight[:, D:], mlp.bias)
-            return ops.grouped_mlp_match(kp, gu, qp, nw, out.weight, out.bias, offsets, h_match, scale, index=index)
+            composed = dict(occ=occ, qt=qt, nt=nt) if nt is not None else {}
+            return ops.grouped_mlp_match(kp, gu, qp, nw, out.weight, out.bias, offsets, h_match, scale, index=index, **composed)
         return self._composed_mlp_logits(kp, g, qp, cand, offsets, h_match, scale, index, regular)
 
     def _composed_mlp_logits(self, kp, g, qp, cand, offsets, H, scale, index, regular):
@@ -606,25 +622,55 @@ class Model(nn.Module):
             logits[p0:p1] = predict(user, news)
         return logits
 
+    def occurrence_match_applicable(self):
+        """Whether a candidate of this model is a row of a news table plus a row of an occurrence table with only linear maps behind it,
+        so that the grouped match can compose it in place (lime_grouped_match_occurrence_f32): a LIME model with fusion_method 'add', or
+        'concat' with a projection -- rep(news, occurrence) = A[news] + T[b_f nb + b_l] (LIME.occurrence_tables).  A pure host
+        predicate of the configuration.  The others stay on the materialised path:
+          'gated': the row is g A + (1 - g) T with g a sigmoid of both sides -- not linear in the occurrence;
+          'concat' with ``project`` the identity: the occurrence's columns are concatenated behind the news', not added to them;
+          CNE: no part of its representation depends on the news alone, so there is no cache to take a table from;
+          the composed MLP form (ops.FUSED_MLP_MATCH off): it is the yardstick on existing launches and reads materialised rows;
+          a baseline model: no occurrence at all -- it keeps its indexed path (``occurrence_free``)."""
+        ne = self.news_encoder
+        if self.plain or self.reads_content_mask:
+            return False
+        if self.click_predictor == 'mlp' and not ops.FUSED_MLP_MATCH:
+            return False
+        return ne.fusion_method == 'add' or (ne.fusion_method == 'concat' and not isinstance(ne.project, nn.Identity))
+
     def _candidate_tables(self, news_cache, rows=None):
-        """The ONE place that asks whether a candidate's representation depends on the news alone (``occurrence_free``: a baseline
-        model's news encoder; LIME's rows depend on the occurrence) -> None: ``_match_pass`` materialises a row and a Q row per pair; or
-        the tables (cand [n, D], qp [n, A]) that lime_grouped_match_indexed_f32 reads in place, once per call: the news of ``rows``
-        (the pool, in plan order) or, with ``rows`` None, every news of the cache (the lists: a pair's index is its news id).  Under
-        ATT / MHSA (a history of one row) qp is never felt: n rows of four zero columns -- the kernel reads both tables at one index.
+        """The ONE place that asks how the candidates are read -> None: ``_match_pass`` materialises a row and a Q row per pair; or
+        the tables (cand [n, D], qp [n, A], nw, occurrence tables) that the grouped match reads in place, once per call: the news of
+        ``rows`` (the pool, in plan order) or, with ``rows`` None, every news of the cache (the lists: a pair's index is its news id).
+        Under ATT / MHSA (a history of one row) qp is never felt: n rows of four zero columns -- the kernel reads both tables at one index.
         Under the MLP click predictor a third table stands beside them: nw [n, D // 2] = cand W_n^T + mlp.bias, the news half of the
-        predictor's hidden layer, once per call (lime_grouped_mlp_match_indexed_f32 reads it; None on the composed form and under
-        the dot product)."""
+        predictor's hidden layer, once per call (None on the composed form and under the dot product).
+
+        A baseline model (``occurrence_free``: the representation depends on the news alone, INDEXED_MATCH): cand is the news' rows
+        themselves and the fourth entry is None (lime_grouped_match_indexed_f32 / lime_grouped_mlp_match_indexed_f32).
+        A LIME model for which ``occurrence_match_applicable()`` holds (OCCURRENCE_MATCH): cand = A, the cache rows, qp = A Q^T + b_Q and
+        nw = A W_n^T + mlp.bias, and the fourth entry is (ct, qt, nt) = (T, T Q^T, T W_n^T) [num_buckets^2 rows, no bias: it is in
+        the news tables] from LIME.occurrence_tables(); a pair adds its bucket pair's row of them in the kernel
+        (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  Every other model: None."""
         ne, ue = self.news_encoder, self.user_encoder
-        if not (INDEXED_MATCH and getattr(ne, 'occurrence_free', False)):
+        plain = INDEXED_MATCH and getattr(ne, 'occurrence_free', False)
+        if not plain and not (OCCURRENCE_MATCH and self.occurrence_match_applicable()):
             return None
-        cand = news_cache.contiguous() if rows is None else ne.encode_cached(news_cache, rows)
-        # the MLP predictor's news half of the hidden layer, nw = cand W_n^T + mlp.bias: a function of the news alone too
-        nw = (ops.linear(cand, self.mlp.weight[:, cand.shape[1]:], self.mlp.bias)
-              if self.click_predictor == 'mlp' and ops.FUSED_MLP_MATCH else None)
-        if hasattr(ue, 'user_node_embedding'):
-            return cand, ops.linear(cand, ue.Q.weight, ue.Q.bias), nw                                         # userEncoders.py:162
-        return cand, torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=cand.device), nw
+        if plain:
+            cand, ct = (news_cache.contiguous() if rows is None else ne.encode_cached(news_cache, rows)), None
+        else:
+            cand, ct = (news_cache.contiguous() if rows is None else news_cache.index_select(0, rows)), ne.occurrence_tables()[0]
+        crown, mlp = hasattr(ue, 'user_node_embedding'), self.click_predictor == 'mlp' and ops.FUSED_MLP_MATCH
+
+        def behind(t, bias):
+            """(qp, nw) of the rows t: Q (userEncoders.py:162; four zero columns where it is never felt) and the MLP predictor's news
+            half of the hidden layer, a function of the news alone too."""
+            qp = (ops.linear(t, ue.Q.weight, ue.Q.bias if bias else None) if crown else
+                  torch.zeros((t.shape[0], 4), dtype=torch.float32, device=t.device))
+            return qp, (ops.linear(t, self.mlp.weight[:, t.shape[1]:], self.mlp.bias if bias else None) if mlp else None)
+        qp, nw = behind(cand, True)
+        return cand, qp, nw, (None if ct is None else (ct,) + behind(ct, False))
 
     def _score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                     cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
@@ -711,7 +757,9 @@ class Model(nn.Module):
         and their users x S_pass x H refined rows within ``pairs_per_pass`` each, one user a pass at the least.
         CNE has no per-news cache and is refused (ValueError).
         A baseline model (no LIME): the candidates are read in place from the cache through the pair's news id
-        (lime_grouped_match_indexed_f32), with Q of every news of the cache computed once per call under the CROWN user encoder."""
+        (lime_grouped_match_indexed_f32), with Q of every news of the cache computed once per call under the CROWN user encoder.
+        A LIME model with LIME_OCCURRENCE_MATCH=1 where ``occurrence_match_applicable()`` holds: the cache itself is the news table, a
+        pair's index its news id, and the occurrence is composed in the kernel as in ``score_pool``."""
         return self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
                                  cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
 

@@ -370,6 +370,13 @@ class LIME(nn.Module):
             return ops.linear(fresh, self.project.weight[:, cdim:], self.project.bias), None
         return fresh, None
 
+    def occurrence_ids(self, freshness, lifetime):
+        """int32 [R]: the row b_f * nb + b_l of ``occurrence_tables()`` for each occurrence (freshness[r], lifetime[r]) -- the two bucket
+        launches and their sum, nothing per column."""
+        fe = self.freshness_encoder
+        fr, lt = freshness.float().reshape(-1).contiguous(), lifetime.float().reshape(-1).contiguous()
+        return torch.add(fe.buckets(lt), fe.buckets(fr), alpha=fe.num_buckets)
+
     # ---- per-news content cache (eval: a news occurs in many impressions, its token encoders need to run once) ----------
     def build_content_cache(self, title_text, title_mask, content_text, category, subCategory, rows_per_pass=8192, title_entity=None):
         """One row per news: everything of LIME's representation that depends on the news alone (all the token-encoder work).

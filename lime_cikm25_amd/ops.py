@@ -895,8 +895,26 @@ def pool_match(hidden, affine2, x, B, H, cand=None, remaining=None, alpha=0.0, b
     return user, logits
 
 
+def _occurrence_tables(index, occ, tables, n_occ):
+    """The host checks of the occurrence-composed forms: ``tables`` = ((tensor, name, columns), ...), the occurrence tables beside
+    the news tables; occ int32 [P] like index -> (occ, n_occ: the first rows of each that occ may name, default all of the first's)."""
+    if index is None or occ is None:
+        raise ValueError('occ names rows of the occurrence tables next to index: give index, occ and the tables together')
+    for t, name, cols in tables:
+        if t is None:
+            raise ValueError('the occurrence-composed form needs %s' % name)
+        _mat(t, name)
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    n_occ = tables[0][0].shape[0] if n_occ is None else int(n_occ)
+    if any(t.shape[1] != cols for t, _, cols in tables) or not 0 <= n_occ <= min(t.shape[0] for t, _, _ in tables):
+        raise ValueError('%s with n_occ = %d, got %s' % (' and '.join('%s must be [>= n_occ, %d]' % (name, cols) for _, name, cols in tables),
+                                                         n_occ, ' and '.join(str(tuple(t.shape)) for t, _, _ in tables)))
+    return _vec(occ, 'occ', index.numel(), dtype=torch.int32), n_occ
+
+
 def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False, index=None,
-                  n=None):
+                  n=None, occ=None, qt=None, ct=None, n_occ=None):
     """``lime_grouped_match_f32``: the history-vs-candidate attention, the dot-product match and the remaining-lifetime weight for
     groups of pairs that share one refined history.  kp [G H, A], g [G H, D] per group; qp [P, A], cand [P, D], remaining [P] per
     pair; offsets int64 [G + 1] (device): the pairs of group i are rows offsets[i] .. offsets[i + 1] - 1 -> logits [P] (pairs outside
@@ -904,7 +922,11 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
 
     ``index`` int32 [P] (``lime_grouped_match_indexed_f32``): qp and cand are tables and pair p reads row index[p] of both -- the first
     ``n`` rows of each (default: all of qp's; cand has at least as many); the kernel clamps an index outside [0, n) into it.  A pair's
-    bits are those of the plain form on ``qp[index]``, ``cand[index]``."""
+    bits are those of the plain form on ``qp[index]``, ``cand[index]``.
+
+    ``occ`` int32 [P] with ``qt`` [n_occ, A] and ``ct`` [n_occ, D] next to ``index`` (``lime_grouped_match_occurrence_f32``): the
+    pair's operands are composed in the kernel, ``qp[index] + qt[occ]`` and ``cand[index] + ct[occ]`` (one fp32 add per element; occ
+    is clamped into [0, n_occ), default all of qt's rows).  A pair's bits are those of the plain form on those sums."""
     lib = _lib.load()
     for t, name in ((kp, 'kp'), (g, 'g'), (qp, 'qp'), (cand, 'cand')):
         _mat(t, name)
@@ -926,6 +948,9 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
         n = qp.shape[0] if n is None else int(n)
         if qp.shape[1] != A or cand.shape[1] != D or not 0 <= n <= min(qp.shape[0], cand.shape[0]):
             raise ValueError('qp must be [>= n, %d] and cand [>= n, %d] with n = %d, got %s and %s' % (A, D, n, tuple(qp.shape), tuple(cand.shape)))
+    composed = occ is not None or qt is not None or ct is not None or n_occ is not None
+    if composed:
+        occ, n_occ = _occurrence_tables(index, occ, ((qt, 'qt', A), (ct, 'ct', D)), n_occ)
     _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
     if use_weight:
         remaining = _vec(remaining.contiguous(), 'remaining', P)
@@ -934,6 +959,10 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
         check(lib.lime_grouped_match_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(remaining) if use_weight else None, _p(offsets), _p(logits),
                                          G, P, H, A, D, scale, alpha, beta, int(use_weight), int(use_penalty), _stream()),
               'lime_grouped_match_f32')
+    elif composed:
+        check(lib.lime_grouped_match_occurrence_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(qt), _p(ct), _p(remaining) if use_weight else None,
+                                                    _p(offsets), _p(index), n, _p(occ), n_occ, _p(logits), G, P, H, A, D, scale, alpha, beta,
+                                                    int(use_weight), int(use_penalty), _stream()), 'lime_grouped_match_occurrence_f32')
     else:
         check(lib.lime_grouped_match_indexed_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(remaining) if use_weight else None, _p(offsets),
                                                  _p(index), n, _p(logits), G, P, H, A, D, scale, alpha, beta, int(use_weight),
@@ -949,7 +978,7 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
 FUSED_MLP_MATCH = os.environ.get('LIME_FUSED_MLP_MATCH', '1') != '0'
 
 
-def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=None, n=None):
+def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=None, n=None, occ=None, qt=None, nt=None, n_occ=None):
     """``lime_grouped_mlp_match_f32``: the history-vs-candidate attention and the MLP click predictor for groups of pairs that share one
     refined history.  kp [G H, A] and gu = g W_u^T [G H, Dh] per group; qp [P, A] and nw = cand W_n^T + mlp.bias [P, Dh] per pair; w_out
     [Dh] (out.weight), b_out [1] (out.bias; None: 0); offsets int64 [G + 1] (device) -> logits [P] (pairs outside every group keep what
@@ -957,7 +986,11 @@ def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=Non
 
     ``index`` int32 [P] (``lime_grouped_mlp_match_indexed_f32``): qp and nw are tables and pair p reads row index[p] of both -- the
     first ``n`` rows of each (default: all of qp's); the kernel clamps an index outside [0, n) into it.  A pair's bits are those of the
-    plain form on ``qp[index]``, ``nw[index]``."""
+    plain form on ``qp[index]``, ``nw[index]``.
+
+    ``occ`` int32 [P] with ``qt`` [n_occ, A] and ``nt`` [n_occ, Dh] next to ``index`` (``lime_grouped_mlp_match_occurrence_f32``): the
+    pair's operands are composed in the kernel, ``qp[index] + qt[occ]`` and ``nw[index] + nt[occ]`` -- the rules of
+    ``grouped_match``'s occurrence form."""
     lib = _lib.load()
     for t, name in ((kp, 'kp'), (gu, 'gu'), (qp, 'qp'), (nw, 'nw')):
         _mat(t, name)
@@ -979,6 +1012,9 @@ def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=Non
         n = qp.shape[0] if n is None else int(n)
         if qp.shape[1] != A or nw.shape[1] != Dh or not 0 <= n <= min(qp.shape[0], nw.shape[0]):
             raise ValueError('qp must be [>= n, %d] and nw [>= n, %d] with n = %d, got %s and %s' % (A, Dh, n, tuple(qp.shape), tuple(nw.shape)))
+    composed = occ is not None or qt is not None or nt is not None or n_occ is not None
+    if composed:
+        occ, n_occ = _occurrence_tables(index, occ, ((qt, 'qt', A), (nt, 'nt', Dh)), n_occ)
     _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
     w_out = _vec(w_out.reshape(-1), 'w_out', Dh)
     if b_out is not None:
@@ -987,6 +1023,10 @@ def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=Non
     if index is None:
         check(lib.lime_grouped_mlp_match_f32(_p(kp), _p(gu), _p(qp), _p(nw), _p(w_out), _p(b_out), _p(offsets), _p(logits), G, P, H, A, Dh,
                                              scale, _stream()), 'lime_grouped_mlp_match_f32')
+    elif composed:
+        check(lib.lime_grouped_mlp_match_occurrence_f32(_p(kp), _p(gu), _p(qp), _p(nw), _p(qt), _p(nt), _p(w_out), _p(b_out), _p(offsets),
+                                                        _p(index), n, _p(occ), n_occ, _p(logits), G, P, H, A, Dh, scale, _stream()),
+              'lime_grouped_mlp_match_occurrence_f32')
     else:
         check(lib.lime_grouped_mlp_match_indexed_f32(_p(kp), _p(gu), _p(qp), _p(nw), _p(w_out), _p(b_out), _p(offsets), _p(index), n,
                                                      _p(logits), G, P, H, A, Dh, scale, _stream()), 'lime_grouped_mlp_match_indexed_f32')

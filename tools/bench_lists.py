@@ -19,6 +19,12 @@ alternated with the same model on the gather form (tools/bench_recommend.py, ``p
 profiles/plain_recommend.json.
 
     python tools/bench_lists.py --news-encoder CROWN --user-encoders CROWN --rounds 3
+
+``--occurrence-match`` (with ``--content-encoder X``) measures a LIME model at the serving shape with its candidates composed in the
+kernel (LIME_OCCURRENCE_MATCH=1: the cache read in place, Q of every news and of the occurrence tables once per call) alternated with
+the same model on the materialised path (``occurrence_forms``); the lines are appended to profiles/occurrence_match.json.
+
+    python tools/bench_lists.py --occurrence-match --content-encoder NAML --user-encoders ATT --rounds 3
 """
 import argparse
 import json
@@ -33,7 +39,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from lime_cikm25_amd import DeviceBehaviors, DeviceCorpus, Model, make_config, ops, recommend, synth, util  # noqa: E402
 from bench_eval import make_dev_split  # noqa: E402
-from bench_recommend import plain_forms  # noqa: E402
+from bench_recommend import occurrence_forms, plain_forms  # noqa: E402
 
 
 def say(*a):
@@ -81,7 +87,7 @@ def empty_slots(model, dc, cand_index, offsets, H, pairs_per_pass):
             'passes': len(shares), 'largest_slot_count': s_max, 'mean_distinct_topics_per_list': round(float(nd.mean()), 2)}
 
 
-def serving(model, dc, cache, cfg, args, rng, n_news, plain=False):
+def serving(model, dc, cache, cfg, args, rng, n_news, forms=None):
     U, C, k, H = args.users, args.candidates, args.k, cfg.max_history_num
     P = U * C
     n_hist = rng.integers(5, H + 1, size=U)
@@ -97,8 +103,8 @@ def serving(model, dc, cache, cfg, args, rng, n_news, plain=False):
     list_args = dict(news_cache=cache, corpus=dc, hist_index=t(hist), hist_mask=t(mask), user_freshness=t(ufr), user_lifetime=t(ult),
                      cand_offsets=t(offsets), cand_index=t(cands), cand_freshness=t(cfr), cand_lifetime=t(clt))
     n_src = min(P, H + cfg.batch_size)
-    if plain:
-        return plain_forms(model, list_args, k, n_src, args.rounds, dict(
+    if forms is not None:                                                  # one model, a module switch on and off
+        return forms(model, list_args, k, n_src, args.rounds, dict(
             bench='recommend_lists', shape='serving', model=model.model_name, users=U, candidates_per_user=C, pairs=P, news=n_news, H=H, k=k),
             entry='recommend_lists')
     user = np.repeat(np.arange(U), C)
@@ -169,19 +175,27 @@ def main():
     ap.add_argument('--shapes', nargs='*', default=['serving', 'dev'])
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--news-encoder', default='LIME', help="'LIME' (default) or a baseline: CROWN, CNN, NAML, MHSA, KCNN (serving shape)")
+    ap.add_argument('--content-encoder', default='CROWN', help="LIME's content encoder (read with --occurrence-match)")
+    ap.add_argument('--occurrence-match', action='store_true',
+                    help='a LIME model composed in the kernel against its materialised path (serving shape)')
     ap.add_argument('--json-out', default=None, help='default: profiles/recommend_lists.json (LIME, rewritten), '
-                                                     'profiles/plain_recommend.json (a baseline, appended to)')
+                                                     'profiles/plain_recommend.json (a baseline, appended to), '
+                                                     'profiles/occurrence_match.json (--occurrence-match, appended to)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_lists.py measures on the GPU: there is no CPU path'
     plain = args.news_encoder != 'LIME'
-    if plain:
+    assert not (plain and args.occurrence_match), 'a baseline model has no occurrence: --occurrence-match measures LIME models'
+    forms = plain_forms if plain else occurrence_forms if args.occurrence_match else None
+    if forms is not None:
         args.shapes = ['serving']
     if args.json_out is None:
-        args.json_out = os.path.join(ROOT, 'profiles', 'plain_recommend.json' if plain else 'recommend_lists.json')
+        args.json_out = os.path.join(ROOT, 'profiles', 'plain_recommend.json' if plain else
+                                     'occurrence_match.json' if args.occurrence_match else 'recommend_lists.json')
 
     lines = []
     for user_encoder in args.user_encoders:
-        cfg = make_config(news_encoder=args.news_encoder, user_encoder=user_encoder, vocabulary_size=50000)
+        cfg = make_config(news_encoder=args.news_encoder, user_encoder=user_encoder, content_encoder=args.content_encoder,
+                          vocabulary_size=50000)
         corpus = synth.synth_corpus(cfg, n_news=args.news, n_train=1, n_dev=1, seed=args.seed)
         # MIND's subcategories each sit under one category: about 270 topics in all (independent draws would give 18 x 270)
         corpus.news_category[1:] = 1 + corpus.news_subCategory[1:] % (cfg.category_num - 1)
@@ -193,7 +207,7 @@ def main():
         cache = model.build_news_cache(dc)
         rng = np.random.default_rng(args.seed)
         for shape in args.shapes:
-            line = (serving(model, dc, cache, cfg, args, rng, args.news, plain) if shape == 'serving' else
+            line = (serving(model, dc, cache, cfg, args, rng, args.news, forms) if shape == 'serving' else
                     dev_pass(model, dc, cfg, args, args.news))
             line.update(user_encoder=user_encoder, device=torch.cuda.get_device_name(0))
             say(line)
@@ -204,7 +218,7 @@ def main():
     print('\n'.join(lines))
     if args.json_out:
         os.makedirs(os.path.dirname(os.path.abspath(args.json_out)), exist_ok=True)
-        with open(args.json_out, 'a' if plain else 'w') as f:
+        with open(args.json_out, 'a' if forms is not None else 'w') as f:
             f.write('\n'.join(lines) + '\n')
 
 

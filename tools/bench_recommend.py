@@ -14,6 +14,13 @@ read in place) is alternated with the same model on the gather form (LIME_INDEXE
 the kernel LIME models take).  One JSON line per pool, appended to profiles/plain_recommend.json.
 
     python tools/bench_recommend.py --news-encoder CROWN --user-encoder CROWN --rounds 5
+
+``--occurrence-match`` (with ``--content-encoder X --user-encoder Y``) measures a LIME model with its candidates composed in the
+kernel (LIME_OCCURRENCE_MATCH=1: lime_grouped_match_occurrence_f32 on the pool's cache rows and the occurrence tables) alternated
+with the same model on the materialised path (the switch off: one encode_cached row, one Q row per pair).  One JSON line per pool,
+appended to profiles/occurrence_match.json.
+
+    python tools/bench_recommend.py --occurrence-match --content-encoder NAML --user-encoder ATT --rounds 5
 """
 import argparse
 import json
@@ -42,14 +49,15 @@ def event_ms(fn):
     return e0.elapsed_time(e1), out
 
 
-def plain_forms(model, call_args, k, n_src, rounds, head, entry='recommend'):
-    """A baseline model's ``entry`` on the indexed match and on the gather form, alternated after warm-up -> the result line."""
-    def form(indexed):
-        model_module.INDEXED_MATCH = indexed
+def switch_forms(model, call_args, k, n_src, rounds, head, entry, switch, default, names):
+    """``entry`` of one model with the module switch ``switch`` of lime_cikm25_amd.model on and off, alternated after warm-up -> the
+    result line; ``names``: what the two forms are called in it (on, off); ``default``: the value the switch is left at."""
+    def form(on):
+        setattr(model_module, switch, on)
         try:
             return getattr(model, entry)(**call_args, k=k, n_src=n_src)
         finally:
-            model_module.INDEXED_MATCH = True
+            setattr(model_module, switch, default)
 
     for _ in range(2):
         form(True)
@@ -57,26 +65,38 @@ def plain_forms(model, call_args, k, n_src, rounds, head, entry='recommend'):
     torch.cuda.synchronize()
     ms, pos = {True: [], False: []}, {}
     for _ in range(rounds):
-        for indexed in (True, False):
-            dt, out = event_ms(lambda: form(indexed))
-            ms[indexed].append(dt)
-            pos[indexed] = out[0]
+        for on in (True, False):
+            dt, out = event_ms(lambda: form(on))
+            ms[on].append(dt)
+            pos[on] = out[0]
     agree = float((pos[True] == pos[False]).float().mean())
     peak = {}
-    for indexed in (True, False):                                          # the call's own peak above what is resident
+    for on in (True, False):                                               # the call's own peak above what is resident
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
-        form(indexed)
+        form(on)
         torch.cuda.synchronize()
-        peak[indexed] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+        peak[on] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
     stat = lambda v: {'median': round(statistics.median(v), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
-    line = dict(head, rounds=rounds, indexed_ms=stat(ms[True]), gather_ms=stat(ms[False]),
-                gather_over_indexed=round(statistics.median(ms[False]) / statistics.median(ms[True]), 3),
-                indexed_peak_mib=round(peak[True], 1), gather_peak_mib=round(peak[False], 1),
+    new, old = names
+    line = dict(head, rounds=rounds, **{new + '_ms': stat(ms[True]), old + '_ms': stat(ms[False]),
+                                        '%s_over_%s' % (old, new): round(statistics.median(ms[False]) / statistics.median(ms[True]), 3),
+                                        new + '_peak_mib': round(peak[True], 1), old + '_peak_mib': round(peak[False], 1)},
                 same_positions_fraction=round(agree, 4), device=torch.cuda.get_device_name(0))
     say(line)
     return line
+
+
+def plain_forms(model, call_args, k, n_src, rounds, head, entry='recommend'):
+    """A baseline model's ``entry`` on the indexed match and on the gather form."""
+    return switch_forms(model, call_args, k, n_src, rounds, head, entry, 'INDEXED_MATCH', True, ('indexed', 'gather'))
+
+
+def occurrence_forms(model, call_args, k, n_src, rounds, head, entry='recommend'):
+    """A LIME model's ``entry`` with its candidates composed in the kernel and on the materialised path (the parent's code)."""
+    assert model.occurrence_match_applicable(), '%s keeps the materialised path: nothing to alternate' % model.model_name
+    return switch_forms(model, call_args, k, n_src, rounds, head, entry, 'OCCURRENCE_MATCH', False, ('composed', 'materialised'))
 
 
 def main():
@@ -90,15 +110,21 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--news-encoder', default='LIME', help="'LIME' (default) or a baseline: CROWN, CNN, NAML, MHSA, KCNN")
     ap.add_argument('--user-encoder', default='CROWN')
+    ap.add_argument('--content-encoder', default='CROWN', help="LIME's content encoder (read with --occurrence-match)")
+    ap.add_argument('--occurrence-match', action='store_true', help='a LIME model composed in the kernel against its materialised path')
     ap.add_argument('--json-out', default=None, help='default: profiles/recommend.json (LIME, rewritten), profiles/plain_recommend.json '
-                                                     '(a baseline, appended to)')
+                                                     '(a baseline, appended to), profiles/occurrence_match.json (--occurrence-match, '
+                                                     'appended to)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_recommend.py measures on the GPU: there is no CPU path'
     plain = args.news_encoder != 'LIME'
+    assert not (plain and args.occurrence_match), 'a baseline model has no occurrence: --occurrence-match measures LIME models'
+    forms = plain_forms if plain else occurrence_forms if args.occurrence_match else None
     if args.json_out is None:
-        args.json_out = os.path.join(ROOT, 'profiles', 'plain_recommend.json' if plain else 'recommend.json')
+        args.json_out = os.path.join(ROOT, 'profiles', 'plain_recommend.json' if plain else
+                                     'occurrence_match.json' if args.occurrence_match else 'recommend.json')
 
-    cfg = make_config(news_encoder=args.news_encoder, user_encoder=args.user_encoder)
+    cfg = make_config(news_encoder=args.news_encoder, user_encoder=args.user_encoder, content_encoder=args.content_encoder)
     U, H, k = args.users, cfg.max_history_num, args.k
     n_news = max(args.pools) + 1
     corpus = synth.synth_corpus(cfg, n_news=n_news, n_train=1, n_dev=1, seed=args.seed)
@@ -129,8 +155,8 @@ def main():
                          cand_index=t(pool), cand_freshness=t(cfr), cand_lifetime=t(clt))
         n_src = min(U * C, H + cfg.batch_size)
         topics = len(set(zip(corpus.news_category[pool].tolist(), corpus.news_subCategory[pool].tolist())))
-        if plain:
-            lines.append(json.dumps(plain_forms(model, pool_args, k, n_src, args.rounds, dict(
+        if forms is not None:
+            lines.append(json.dumps(forms(model, pool_args, k, n_src, args.rounds, dict(
                 bench='recommend', model=model.model_name, users=U, H=H, pool=C, topics_in_pool=topics, k=k, pairs=U * C))))
             continue
         # the second form: whole users, as many as --old-pairs allows
@@ -178,7 +204,7 @@ def main():
     print('\n'.join(lines))
     if args.json_out:
         os.makedirs(os.path.dirname(os.path.abspath(args.json_out)), exist_ok=True)
-        with open(args.json_out, 'a' if plain else 'w') as f:
+        with open(args.json_out, 'a' if forms is not None else 'w') as f:
             f.write('\n'.join(lines) + '\n')
 
 
