@@ -1273,6 +1273,26 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * lime_grouped_mlp_match_f32 on the composed rows; clamping, statuses and their order are those of
  * lime_grouped_match_occurrence_f32, with na / nt 8-byte aligned as nw is.
  *
+ * lime_grouped_match_schedule_f32 (csrc/grouped_match_schedule_f32.hip): lime_grouped_match_occurrence_f32 for S time slots of every
+ * pair in one launch (Model.score_schedule).  kp, g, qa, ca, qt, ct, offsets, index, n, n_occ and the weight parameters are the
+ * twin's; occ int32 [S, P], remaining fp32 [S, P] (read when use_weight != 0) and logits fp32 [S, P] have leading dimension P.  Per
+ * (slot s, pair p of group i), in the FACTORISED form
+ *     s[h] = (kp[i H + h, :] . qa[index[p], :] + kp[i H + h, :] . qt[occ[s, p], :]) * scale,   a = softmax_h(s),
+ *     logits[s, p] = (sum_h a[h] (g[i H + h, :] . ca[index[p], :] + g[i H + h, :] . ct[occ[s, p], :])) * w(remaining[s, p])
+ * The news-table products run once per pair (the pass body of lime_grouped_match_f32: exact fp32 on v_mfma_f32_16x16x4_f32, the
+ * compensated sum) and stay in registers across the slot loop.  The occurrence terms are FORMED IN THE KERNEL: every workgroup makes its
+ * group's [n_occ, H] products with qt and with ct by the same tile product and keeps them in LDS for all its tiles -- there is no
+ * workspace, and no launch and no buffer other than occ, remaining and logits grows with S P.  It rounds two partial sums where the
+ * twin rounds one composed operand: the results agree to fp32 rounding, not bit for bit.
+ * Without occurrence tables -- qt == ct == NULL and n_occ == 0 (occ is then not read and may be NULL), a baseline model -- the table
+ * terms are absent and the bits of (s, p) are those of lime_grouped_match_indexed_f32 for pair p with remaining[s, p].
+ * A workgroup per 64-pair tile of a group, fixed-order sums, no atomics: the bits of (s, p) depend on its own operands and on H, A and
+ * D alone -- not on S, the slot's position, the other slots, P, G, the group's position or the pair's place in its tile.  index, occ
+ * and offsets are clamped as in the twin.  Statuses before any launch: the twin's, in its order (the occurrence tables may be absent);
+ * then LIME_ERR_BAD_ARG for S < 1, for occurrence tables with a NULL occ, for one table without the other or n_occ > 0 without tables;
+ * then LIME_ERR_UNSUPPORTED where the tables do not fit the workgroup's LDS: 2048 T + 8 n_occ Hs bytes <= 65536, with T = 1, 2, 4, 8
+ * for H <= 16, 32, 64, 128 and Hs = H rounded up to a multiple of 4 (H = 50 with 100 occurrences: 49,792 bytes; H = 128: n_occ <= 48).
+ *
  * lime_topk_rows_f32 (csrc/topk_rows_f32.hip): per row u < U of scores [U, C] (leading dimension ld >= C) the k best entries:
  * positions int32 [U, k] (column indices) and top_scores fp32 [U, k] (the input's bits at those positions), in descending order of
  * the score; equal scores -- +0.0 and -0.0 are equal -- lower position first; a NaN ranks behind every number, NaNs in position
@@ -1302,6 +1322,10 @@ int lime_grouped_mlp_match_occurrence_f32(const float* kp, const float* gu, cons
                                           const float* nt, const float* w_out, const float* b_out, const int64_t* offsets,
                                           const int32_t* index, int64_t n, const int32_t* occ, int64_t n_occ, float* logits, int64_t G,
                                           int64_t P, int32_t H, int32_t A, int32_t Dh, float scale, void* stream);
+int lime_grouped_match_schedule_f32(const float* kp, const float* g, const float* qa, const float* ca, const float* qt, const float* ct,
+                                    const float* remaining, const int64_t* offsets, const int32_t* index, int64_t n, const int32_t* occ,
+                                    int64_t n_occ, float* logits, int64_t G, int64_t P, int32_t S, int32_t H, int32_t A, int32_t D,
+                                    float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
 int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);

@@ -53,6 +53,11 @@ INDEXED_MATCH = os.environ.get('LIME_INDEXED_MATCH', '1') != '0'
 # then the materialised one, bit for bit; LIME_OCCURRENCE_MATCH=1 turns it on (tools/bench_recommend.py and tools/bench_lists.py
 # alternate the two, DESIGN.md "LIME candidates in place").
 OCCURRENCE_MATCH = os.environ.get('LIME_OCCURRENCE_MATCH', '0') != '0'
+# A schedule of S time slots (Model.score_schedule) moves only the occurrence row and the remaining lifetime of such a candidate, so
+# the two big products of the match run once per pair and a slot is an epilogue (lime_grouped_match_schedule_f32,
+# Model.schedule_match_applicable).  On by default for that entry; LIME_SCHEDULE_MATCH=0 keeps the shared-user-side route -- the
+# existing match once per slot on one user side, bit for bit S score_pool calls -- as its yardstick (tools/bench_schedule.py).
+SCHEDULE_MATCH = os.environ.get('LIME_SCHEDULE_MATCH', '1') != '0'
 
 
 class Model(nn.Module):
@@ -500,13 +505,30 @@ class Model(nn.Module):
         pair's row of them) and ``pick(t)`` the pass's of one of them, in group order;
         group_offsets int64 [n slots + 1]: the groups' CSR over them, on the device or still on the host (the copy waits for the
         stream, so it stands behind the launches that do not read it).  The user side runs once per group and the match per pair."""
+        return self._pass_logits(news_cache, self._pass_operands(users, u0, u1, slots, category, subCategory), cands, pick, group_offsets,
+                                 users[0].shape[1])
+
+    def _pass_operands(self, users, u0, u1, slots, category, subCategory):
+        """The user side of one pass (``_match_pass``'s users u0:u1 with ``slots`` groups each) -> what ``match_operands`` gives: once
+        per pass, whatever the number of candidate sets (time slots) matched against it."""
         hist, ucat, usub, hist_mask, gate_y, n_src = users
-        index, freshness, lifetime, remaining, tables, position = cands
-        ne, ue = self.news_encoder, self.user_encoder
         H = hist.shape[1]
+        return self.user_encoder.match_operands(hist[u0:u1], category, subCategory, ucat[u0:u1], usub[u0:u1], hist_mask[u0:u1], n_src=n_src,
+                                                hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
+
+    def _pass_logits(self, news_cache, operands, cands, pick, group_offsets, H):
+        """The candidate side of one pass and its match against ``operands`` (``_match_pass``'s other arguments) -> fp32 [pairs].
+        A schedule on the factorised route: freshness and remaining carry a leading slot axis [S, ...] over the call's tables, and the
+        pass is ONE launch for all its slots (lime_grouped_match_schedule_f32) -> fp32 [S, pairs]."""
+        index, freshness, lifetime, remaining, tables, position = cands
+        ne = self.news_encoder
         dev = news_cache.device
-        operands = ue.match_operands(hist[u0:u1], category, subCategory, ucat[u0:u1], usub[u0:u1], hist_mask[u0:u1], n_src=n_src,
-                                     hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
+        if freshness.dim() == 3:
+            S = freshness.shape[0]
+            at = newsEncoders._i32(pick(position).reshape(-1)).contiguous()
+            occ = None if tables[3] is None else ne.occurrence_ids_schedule(pick(freshness).reshape(S, -1), pick(lifetime).reshape(-1))
+            return self._click_logits(operands, None, pick(remaining).reshape(S, -1), torch.as_tensor(group_offsets, device=dev), H,
+                                      tables=tables, index=at, occ=occ)
         if tables is None:
             cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))       # [pairs, D]
             at = occ = None
@@ -556,7 +578,8 @@ class Model(nn.Module):
         through ``index`` int32 [pairs] -- and, where the tables carry occurrence tables (a LIME model), composed with the row ``occ``
         int32 [pairs] of those in the kernel (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  ``remaining``
         [pairs]: read by the dot product's lifetime weight alone.  ``regular``: the pairs per group where every group has as many (the
-        [B, N] shape).
+        [B, N] shape).  A schedule on the factorised route (dot product over tables): ``remaining`` (and ``occ``) [S, pairs] -> fp32
+        [S, pairs], every slot in one lime_grouped_match_schedule_f32 launch.
 
         dot_product (model.py:179-181): lime_grouped_match_f32.  mlp (:182-184): with mlp.weight split into its user half W_u and its
         news half W_n, gu = g W_u^T once per history row and nw = cand W_n^T + mlp.bias once per candidate row (a table for a baseline
@@ -582,6 +605,10 @@ class Model(nn.Module):
         ct, qt, nt = tables[3] if tables is not None and tables[3] is not None else (None, None, None)
         if self.click_predictor == 'dot_product':
             composed = dict(occ=occ, qt=qt, ct=ct) if ct is not None else {}
+            if remaining.dim() == 2:                             # a schedule over the tables: remaining (and occ) [S, pairs], one launch
+                return ops.grouped_match_schedule(kp, g, qp, cand, remaining, offsets, index, h_match, scale, w.alpha, w.beta,
+                                                  bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty),
+                                                  slots=remaining.shape[0], **composed)
             return ops.grouped_match(kp, g, qp, cand, remaining, offsets, h_match, scale, w.alpha, w.beta,
                                      bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=index, **composed)
         mlp, out = self.mlp, self.out
@@ -639,7 +666,36 @@ class Model(nn.Module):
             return False
         return ne.fusion_method == 'add' or (ne.fusion_method == 'concat' and not isinstance(ne.project, nn.Identity))
 
-    def _candidate_tables(self, news_cache, rows=None):
+    def schedule_match_applicable(self, H=None):
+        """Whether a schedule of this model can take the factorised route (lime_grouped_match_schedule_f32): the dot-product predictor
+        on a model whose candidate is a news-table row plus an occurrence-table row (``occurrence_match_applicable()``) or the
+        news-table row alone (a baseline, ``occurrence_free``), within the kernel's limits -- the [num_buckets^2, H] occurrence terms
+        of a group fit its LDS (ops.grouped_match_schedule_fits; H: the history rows the match sees, config.max_history_num under the
+        CROWN user encoder, 1 under ATT / MHSA).  A pure host predicate of the configuration (and ``H``, default
+        config.max_history_num); the LIME_SCHEDULE_MATCH switch is not part of it."""
+        ne = self.news_encoder
+        if self.click_predictor != 'dot_product' or self.reads_content_mask:
+            return False
+        if getattr(ne, 'occurrence_free', False):
+            n_occ = 0
+        elif self.occurrence_match_applicable():
+            n_occ = ne.freshness_encoder.num_buckets ** 2
+        else:
+            return False
+        H = int(self.config.max_history_num if H is None else H)
+        return ops.grouped_match_schedule_fits(H if hasattr(self.user_encoder, 'user_node_embedding') else 1, n_occ)
+
+    def schedule_route(self, n_slots, H=None):
+        """How ``score_schedule`` serves ``n_slots`` slots -> 'single': one slot is ``score_pool`` itself; 'expand': a baseline under
+        the MLP predictor reads no time at all -- one slot, repeated; 'factorised': ``schedule_match_applicable(H)`` with the
+        LIME_SCHEDULE_MATCH switch on; 'shared': every other model -- one user side, the existing match once per slot."""
+        if int(n_slots) == 1:
+            return 'single'
+        if self.click_predictor == 'mlp' and getattr(self.news_encoder, 'occurrence_free', False):
+            return 'expand'
+        return 'factorised' if SCHEDULE_MATCH and self.schedule_match_applicable(H) else 'shared'
+
+    def _candidate_tables(self, news_cache, rows=None, always=False):
         """The ONE place that asks how the candidates are read -> None: ``_match_pass`` materialises a row and a Q row per pair; or
         the tables (cand [n, D], qp [n, A], nw, occurrence tables) that the grouped match reads in place, once per call: the news of
         ``rows`` (the pool, in plan order) or, with ``rows`` None, every news of the cache (the lists: a pair's index is its news id).
@@ -652,10 +708,11 @@ class Model(nn.Module):
         A LIME model for which ``occurrence_match_applicable()`` holds (OCCURRENCE_MATCH): cand = A, the cache rows, qp = A Q^T + b_Q and
         nw = A W_n^T + mlp.bias, and the fourth entry is (ct, qt, nt) = (T, T Q^T, T W_n^T) [num_buckets^2 rows, no bias: it is in
         the news tables] from LIME.occurrence_tables(); a pair adds its bucket pair's row of them in the kernel
-        (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  Every other model: None."""
+        (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  Every other model: None.
+        ``always``: the tables wherever the model has them, whatever the two switches say (the factorised schedule reads nothing else)."""
         ne, ue = self.news_encoder, self.user_encoder
-        plain = INDEXED_MATCH and getattr(ne, 'occurrence_free', False)
-        if not plain and not (OCCURRENCE_MATCH and self.occurrence_match_applicable()):
+        plain = (INDEXED_MATCH or always) and getattr(ne, 'occurrence_free', False)
+        if not plain and not ((OCCURRENCE_MATCH or always) and self.occurrence_match_applicable()):
             return None
         if plain:
             cand, ct = (news_cache.contiguous() if rows is None else ne.encode_cached(news_cache, rows)), None
@@ -673,44 +730,73 @@ class Model(nn.Module):
         return cand, qp, nw, (None if ct is None else (ct,) + behind(ct, False))
 
     def _score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                    cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
-        """score_pool -> (scores [U, C], bool [U, C] "excluded" or None): the passes over recommend.pool_plan's ONE host plan."""
+                    cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None, slot_offsets=None):
+        """score_pool -> (scores [U, C], bool [U, C] "excluded" or None): the passes over recommend.pool_plan's ONE host plan.
+        With ``slot_offsets`` [S] (score_schedule): scores [S, U, C], slot s at freshness ``cand_freshness + slot_offsets[s]`` (the sum
+        made in fp32), by ``schedule_route(S, H)`` -- 'single': this very path at that freshness; 'shared': the user side once per
+        call, ``match_operands`` once per pass, the candidate side and the match once per slot; 'factorised': the call's tables
+        (whatever LIME_INDEXED_MATCH / LIME_OCCURRENCE_MATCH say) and one lime_grouped_match_schedule_f32 launch per pass for all
+        slots; 'expand': one slot, repeated."""
         C = cand_index.numel()
+        entry = 'recommend' if slot_offsets is None else 'recommend_schedule'
 
         def check_candidates(U):
             for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
                 if tuple(t.shape) not in ((C,), (U, C)):
                     raise ValueError('%s must be [C] = [%d] or [U, C] = [%d, %d], got %s' % (name, C, U, C, tuple(t.shape)))
+            if slot_offsets is not None and (slot_offsets.dim() != 1 or slot_offsets.numel() < 1 or not slot_offsets.is_floating_point()):
+                raise ValueError('slot_offsets must be a float [S] with S >= 1 -- the slots\' offsets in the unit of the freshness --, got %s %s'
+                                 % (slot_offsets.dtype, tuple(slot_offsets.shape)))
         bad_index = 'cand_index must be [C] with C >= 1 -- ONE pool for all users --' if cand_index.dim() != 1 or C < 1 else None
         U, H, _ = self._check_grouped(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index,
-                                      check_candidates, pairs_per_pass, k, ('recommend', 'lime_topk_rows_f32'))
+                                      check_candidates, pairs_per_pass, k, (entry, 'lime_topk_rows_f32'))
         c, dev = corpus, news_cache.device
+        S = 1 if slot_offsets is None else slot_offsets.numel()
+        route = 'single' if slot_offsets is None else self.schedule_route(S, H)
+        offs = None if slot_offsets is None else slot_offsets.to(dev).float()
+        if offs is not None and route in ('single', 'expand'):                 # one slot is computed (no slot is felt under 'expand')
+            cand_freshness, offs = cand_freshness.to(dev).float() + offs[0], None
+        sets = 1 if offs is None else S                                         # the candidate sets that are matched
         cidx = cand_index.to(dev).long()
         cat_c, sub_c = c.news_category[cidx], c.news_subCategory[cidx]
         plan = rec.pool_plan(cat_c.cpu().numpy(), sub_c.cpu().numpy(), self.grouped_by())
         T, order = plan.category.shape[0], torch.as_tensor(plan.order, device=dev)
         fresh, life = cand_freshness.to(dev).float().expand(U, C), cand_lifetime.to(dev).float().expand(U, C)
-        remaining = self._lifetime_rule(fresh, lambda: life, lambda: cat_c.unsqueeze(0).expand(U, C))
+        fresh = fresh.unsqueeze(0) if offs is None else fresh.unsqueeze(0) + offs.view(S, 1, 1)            # [sets, U, C]
+        remaining = self._lifetime_rule(fresh, lambda: life.unsqueeze(0).expand(sets, U, C),
+                                        lambda: cat_c.view(1, 1, C).expand(sets, U, C)).float()
         # the pool in plan (topic) order: what every pass reads
-        tables = self._candidate_tables(news_cache, cidx[order])       # (a baseline model: the pool's C rows and their Q, once per call)
-        cands = (cidx[order].unsqueeze(0).expand(U, C), fresh[:, order], life[:, order], remaining.float()[:, order], tables,
-                 None if tables is None else torch.arange(C, dtype=torch.int32, device=dev).unsqueeze(0).expand(U, C))
+        # (a baseline model: the pool's C rows and their Q, once per call)
+        tables = self._candidate_tables(news_cache, cidx[order], always=route == 'factorised')
+        index, life = cidx[order].unsqueeze(0).expand(U, C), life[:, order]
+        fresh, remaining = fresh[:, :, order], remaining[:, :, order]
+        position = None if tables is None else torch.arange(C, dtype=torch.int32, device=dev).unsqueeze(0).expand(U, C)
         users = self._user_side(news_cache, c, hist_index, hist_mask, user_freshness, user_lifetime, n_src, U * C)
         # (read in place, the candidates take no rows of a pass: the refined rows alone bound its users)
         per = rec.users_per_pass(U, C if tables is None else 0, T, H, int(pairs_per_pass))
         cat_t = torch.as_tensor(plan.category, device=dev).to(c.news_category.dtype)
         sub_t = torch.as_tensor(plan.subCategory, device=dev).to(c.news_subCategory.dtype)
-        out = torch.empty((U, C), dtype=torch.float32, device=dev)
+        out = torch.empty((sets, U, C), dtype=torch.float32, device=dev)
         for u0 in range(0, U, per):
             u1 = min(U, u0 + per)
             n = u1 - u0
-            logits = self._match_pass(news_cache, users, cands, lambda t: t[u0:u1], u0, u1, T, cat_t.repeat(n).view(n * T, 1),
-                                      sub_t.repeat(n).view(n * T, 1), rec.group_offsets(plan.segments, n))
-            out[u0:u1].index_copy_(1, order, logits.view(n, C))
+            operands = self._pass_operands(users, u0, u1, T, cat_t.repeat(n).view(n * T, 1), sub_t.repeat(n).view(n * T, 1))
+            goff = rec.group_offsets(plan.segments, n)
+            if route == 'factorised':                                          # every slot of the pass in one launch
+                logits = self._pass_logits(news_cache, operands, (index, fresh, life, remaining, tables, position),
+                                           lambda t: t[..., u0:u1, :], goff, H)
+                out[:, u0:u1].index_copy_(2, order, logits.view(sets, n, C))
+                continue
+            for s in range(sets):
+                logits = self._pass_logits(news_cache, operands, (index, fresh[s], life, remaining[s], tables, position),
+                                           lambda t: t[u0:u1], goff, H)
+                out[s, u0:u1].index_copy_(1, order, logits.view(n, C))
         gone = self._in_history(news_cache.shape[0], hist_index, hist_mask, cidx) if exclude_history else None
         if exclude_history:
-            out.masked_fill_(gone, float('-inf'))
-        return out, gone
+            out.masked_fill_(gone.unsqueeze(0), float('-inf'))
+        if slot_offsets is None:
+            return out[0], gone
+        return (out.repeat(S, 1, 1) if sets != S else out), gone
 
     @staticmethod
     def _in_history(n_news, hist_index, hist_mask, cidx):
@@ -735,6 +821,49 @@ class Model(nn.Module):
         positions, top = ops.topk_rows(scores, int(k))
         if gone is not None:
             gone = gone.gather(1, positions.clamp(min=0).long()) & (positions >= 0)
+            positions = torch.where(gone, torch.full_like(positions, -1), positions)
+        return positions, top
+
+    @torch.no_grad()
+    def score_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                       cand_lifetime, slot_offsets, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+        """``score_pool`` over a schedule of S time slots -> fp32 [S, U, C]: ``scores[s]`` is what ``score_pool`` returns when called
+        with ``cand_freshness + slot_offsets[s]`` -- the pool as it will rank ``slot_offsets[s]`` from now, every candidate that much
+        older: its freshness bucket moves, its remaining lifetime shrinks, past its lifetime it takes the expired penalty.
+        ``slot_offsets``: float [S], S >= 1, in the unit of the freshness inputs, in any order, repeats allowed (the sum is made in
+        fp32).  ``cand_lifetime``, the histories and their freshness / lifetime are as given for every slot: a lifetime belongs to the
+        (user, topic), a history's freshness to the click.  Every other argument, its checks and its refusals are ``score_pool``'s.
+
+        The user side does not depend on the slot and runs once per call (``match_operands`` once per pass of users).  By
+        ``schedule_route(S, H)``:
+          'single' (S = 1): ``score_pool`` itself, same launches, same bits;
+          'factorised' -- the dot-product predictor where a candidate is A[news] + T[occurrence] with linear maps behind it
+            (``occurrence_match_applicable()``) or A[news] alone (a baseline): the news-table products of the match run once per
+            pair and every slot adds its occurrence's terms from per-group tables (lime_grouped_match_schedule_f32: one launch per
+            pass for all slots; ``scores[s]`` agrees with ``score_pool`` to fp32 rounding, bit for bit on a baseline);
+          'shared' -- 'gated', 'concat' with the identity projection, a LIME model under the MLP predictor, shapes beyond the
+            kernel's limits, or LIME_SCHEDULE_MATCH=0: the existing match once per slot on the shared operands, bit for bit S
+            ``score_pool`` calls;
+          'expand' -- a baseline under the MLP predictor reads no time at all: one slot, repeated."""
+        return self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                cand_lifetime, n_src, pairs_per_pass, exclude_history, slot_offsets=torch.as_tensor(slot_offsets))[0]
+
+    @torch.no_grad()
+    def recommend_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                           cand_lifetime, slot_offsets, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+        """The k best news of the pool per user in every slot of a schedule: ``score_schedule`` (same arguments), then
+        lime_topk_rows_f32 over the [S U, C] view of its scores (in chunks of slots that keep the kernel's 65535 rows) -> (positions
+        int32 [S, U, k] into ``cand_index``, scores fp32 [S, U, k]); slot s holds what ``recommend`` returns at
+        ``cand_freshness + slot_offsets[s]``, in its order and with its -1 / -inf for excluded or missing slots.  1 <= k <= 128."""
+        scores, gone = self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                        cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k,
+                                        slot_offsets=torch.as_tensor(slot_offsets))
+        S, U, C = scores.shape
+        step = max(1, 65535 // max(U, 1))
+        found = [ops.topk_rows(scores[s0:s0 + step].view(-1, C), int(k)) for s0 in range(0, S, step)]
+        positions, top = (torch.cat([f[i] for f in found]).view(S, U, int(k)) for i in (0, 1))
+        if gone is not None:
+            gone = gone.unsqueeze(0).expand(S, U, C).gather(2, positions.clamp(min=0).long()) & (positions >= 0)
             positions = torch.where(gone, torch.full_like(positions, -1), positions)
         return positions, top
 

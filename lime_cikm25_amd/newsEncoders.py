@@ -377,6 +377,14 @@ class LIME(nn.Module):
         fr, lt = freshness.float().reshape(-1).contiguous(), lifetime.float().reshape(-1).contiguous()
         return torch.add(fe.buckets(lt), fe.buckets(fr), alpha=fe.num_buckets)
 
+    def occurrence_ids_schedule(self, freshness, lifetime):
+        """int32 [S, R]: ``occurrence_ids`` for S time slots of R occurrences whose lifetime does not move with the slot -- freshness
+        [S, R], lifetime [R]: the lifetime's bucket launch runs once, over R."""
+        fe = self.freshness_encoder
+        S = freshness.shape[0]
+        fr, lt = freshness.float().reshape(-1).contiguous(), lifetime.float().reshape(-1).contiguous()
+        return torch.add(fe.buckets(lt).unsqueeze(0), fe.buckets(fr).view(S, -1), alpha=fe.num_buckets)
+
     # ---- per-news content cache (eval: a news occurs in many impressions, its token encoders need to run once) ----------
     def build_content_cache(self, title_text, title_mask, content_text, category, subCategory, rows_per_pass=8192, title_entity=None):
         """One row per news: everything of LIME's representation that depends on the news alone (all the token-encoder work).

@@ -970,6 +970,64 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
     return logits
 
 
+def grouped_match_schedule_fits(H, n_occ):
+    """Whether ``lime_grouped_match_schedule_f32`` takes a history of H rows with n_occ occurrence rows: 1 <= H <= 128 and its LDS
+    bound, 2048 T + 8 n_occ Hs <= 65536 bytes (T = 1, 2, 4, 8 for H <= 16, 32, 64, 128; Hs = H rounded up to 4).  Pure host arithmetic."""
+    if not 1 <= H <= 128 or n_occ < 0:
+        return False
+    T = 1 if H <= 16 else 2 if H <= 32 else 4 if H <= 64 else 8
+    return 2048 * T + 8 * n_occ * ((H + 3) // 4 * 4) <= 65536
+
+
+def grouped_match_schedule(kp, g, qa, ca, remaining, offsets, index, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False,
+                           n=None, occ=None, qt=None, ct=None, n_occ=None, slots=None):
+    """``lime_grouped_match_schedule_f32``: ``grouped_match``'s occurrence form for S time slots of every pair in one launch.  kp
+    [G H, A], g [G H, D] per group; the news tables qa [n, A] and ca [n, D] read through ``index`` int32 [P]; ``remaining`` fp32 [S, P]
+    (read under ``use_weight``); offsets int64 [G + 1] (device) -> logits fp32 [S, P].
+
+    ``occ`` int32 [S, P] with ``qt`` [n_occ, A] and ``ct`` [n_occ, D]: slot s of pair p is the match of ``qa[index] + qt[occ[s]]`` and
+    ``ca[index] + ct[occ[s]]`` in the factorised form -- the news-table products once per pair, the occurrence terms from per-group
+    tables the kernel forms in LDS (2048 T + 8 n_occ Hs bytes <= 65536: ``LimeHipError`` beyond).  Without them (a baseline model) only
+    the weight moves with the slot and a slot's bits are those of ``grouped_match``'s indexed form.  ``slots``: S, where neither
+    ``occ`` nor ``remaining`` gives it."""
+    lib = _lib.load()
+    for t, name in ((kp, 'kp'), (g, 'g'), (qa, 'qa'), (ca, 'ca')):
+        _mat(t, name)
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    A, D = kp.shape[1], g.shape[1]
+    if H < 1 or kp.shape[0] % H or g.shape[0] != kp.shape[0]:
+        raise ValueError('kp and g must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], g.shape[0], H))
+    G = kp.shape[0] // H
+    P = index.numel()
+    index = _vec(index, 'index', P, dtype=torch.int32)
+    n = qa.shape[0] if n is None else int(n)
+    if qa.shape[1] != A or ca.shape[1] != D or not 0 <= n <= min(qa.shape[0], ca.shape[0]):
+        raise ValueError('qa must be [>= n, %d] and ca [>= n, %d] with n = %d, got %s and %s' % (A, D, n, tuple(qa.shape), tuple(ca.shape)))
+    given = [t.shape[0] for t in (occ, remaining if use_weight else None) if t is not None] + ([int(slots)] if slots is not None else [])
+    if not given or min(given) != max(given) or given[0] < 1:
+        raise ValueError('the slot count S >= 1 comes from occ [S, P], remaining [S, P] or slots, and they must agree: got %s' % (given,))
+    S = given[0]
+    composed = occ is not None or qt is not None or ct is not None or n_occ is not None
+    if composed:
+        if occ is None or tuple(occ.shape) != (S, P):
+            raise ValueError('occ must be [S, P] = [%d, %d], got %s' % (S, P, None if occ is None else tuple(occ.shape)))
+        occ = occ.contiguous()
+        _, n_occ = _occurrence_tables(index, occ[0], ((qt, 'qt', A), (ct, 'ct', D)), n_occ)        # the tables' checks, on one slot
+        occ = _vec(occ.view(-1), 'occ', S * P, dtype=torch.int32)
+    _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
+    if use_weight:
+        if tuple(remaining.shape) != (S, P):
+            raise ValueError('remaining must be [S, P] = [%d, %d], got %s' % (S, P, tuple(remaining.shape)))
+        remaining = _vec(remaining.contiguous().view(-1), 'remaining', S * P)
+    logits = torch.empty((S, P), dtype=torch.float32, device=qa.device)
+    check(lib.lime_grouped_match_schedule_f32(_p(kp), _p(g), _p(qa), _p(ca), _p(qt) if composed else None, _p(ct) if composed else None,
+                                              _p(remaining) if use_weight else None, _p(offsets), _p(index), n,
+                                              _p(occ) if composed else None, n_occ if composed else 0, _p(logits), G, P, S, H, A, D, scale,
+                                              alpha, beta, int(use_weight), int(use_penalty), _stream()), 'lime_grouped_match_schedule_f32')
+    return logits
+
+
 # The MLP click predictor's match (config.click_predictor = 'mlp'): one launch per pass that keeps the pooled hidden row of a pair in
 # registers (True, lime_grouped_mlp_match_f32), or the composed form on existing launches -- the pairs' user rows, then
 # ``linear(cat[user, news], mlp, act='relu')``, then the product with ``out`` -- which writes a [pairs, D] user row and a [pairs, D // 2]
