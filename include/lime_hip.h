@@ -232,7 +232,9 @@ int lime_ffn_pack_bf16(const float* w1, int64_t ldw1, const float* b1, const flo
  *     y = LayerNorm(x + W2 relu(W1 x + b1) + b2)          out = y (fp32 rows [M, ldo]), or with pool32 the means of 32-row blocks
  * x: fp32 [M, ldx], 16-byte aligned rows.  w1p / w2p: the weights as lime_ffn_pack_sp lays them out.  The hidden state stays in
  * registers.  Only the E real columns of out are written.  Built for E <= 304, E % 4 == 0 and F a multiple of 128 up to 4096;
- * anything else returns LIME_ERR_UNSUPPORTED (use lime_linear_f32 twice).  m_dev: optional device row count, as in lime_linear_args.
+ * anything else returns LIME_ERR_UNSUPPORTED (use lime_linear_f32 twice).  m_dev: optional device row count, as in lime_linear_args
+ * (with pool32 a multiple of 32: a block is live or dead as a whole).  One 512-thread workgroup per CU (two waves per SIMD), 16 rows
+ * per wave; a row's bits, and with pool32 a block's, do not depend on where in a launch it sits.
  */
 typedef struct {
     const float* x;       int64_t ldx;
@@ -264,7 +266,8 @@ int lime_ffn_pack_sp(const float* w1, int64_t ldw1, const float* w2, int64_t ldw
  * row r is res[r] (res_ids NULL: res is [M, ldr]) or res[res_ids[r]] + res_pe[r % res_period] (res is the [V, ldr] word table,
  * ids unchecked in [0, V); res_pe NULL: no positional term).  Rows at or beyond the row count are neither read nor written.
  * Built for E <= 304 and E % 4 == 0; anything else returns LIME_ERR_UNSUPPORTED (use lime_linear_f32).  m_dev: optional device row
- * count, as in lime_linear_args.
+ * count, as in lime_linear_args.  One 512-thread workgroup per CU (two waves per SIMD), 16 rows per wave; a row's bits do not
+ * depend on where in a launch it sits.
  */
 typedef struct {
     const float* attn;    int64_t lda;

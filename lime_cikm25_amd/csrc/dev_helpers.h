@@ -61,13 +61,13 @@ __device__ __forceinline__ unsigned dead_bit(int a, int b) { return (unsigned)(a
 // vmcnt(0), and the registers the wave's loads land in pass through the statement: hipcc's own bookkeeping does not see a wait in
 // inline asm and would put `s_waitcnt vmcnt(..)` of its own in front of the registers' first use, behind younger loads and DMAs.
 // (One statement for all of them: in front of a statement of its own each register gets hipcc's counted wait again.)
+__device__ __forceinline__ void wait_vm0_landed(f32x4& a, f32x4& b) {
+    wait_vm<0>();
+    asm volatile("" : "+v"(a), "+v"(b));
+}
 __device__ __forceinline__ void wait_vm0_landed(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
     wait_vm<0>();
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-__device__ __forceinline__ void wait_vm0_landed(f32x4& a, f32x4& b, f32x4& c, f32x4& d, f32x4& e, f32x4& f, f32x4& g, f32x4& h) {
-    wait_vm<0>();
-    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
 }
 
 // A device-side count (the compacted rows / sequences of this launch, written by an earlier kernel of the stream) against the host's

@@ -3,8 +3,9 @@
 // fp32 operand, six MFMAs per 16 x 16 x 32 block).  Replaces two gemm_sp_kernel launches whose 512-wide hidden state made an HBM round
 // trip (2 KB written and read back per token) and whose LayerNorm launch filled the chip badly at the title shape.
 //
-//   * a workgroup (4 waves, one per SIMD, one per CU) owns a 128-token tile; a wave owns 32 tokens (two 16-token halves) x all
-//     304 model columns: 2 x 19 accumulator tiles for linear2 stay in registers through the whole tile.
+//   * a workgroup (8 waves, two per SIMD, one workgroup per CU) owns a 128-token tile; wave w owns tokens 16 w .. 16 w + 15 x all
+//     304 model columns: 19 accumulator tiles for linear2 stay in registers through the whole tile.  Two waves share a SIMD so that
+//     one's waits (LDS fragments, the step's vmcnt(0), the register splits, the epilogue's loads) leave the matrix pipe to the other.
 //   * the hidden state runs in passes of 128 columns.  Linear1 (five steps, two 32-deep k chunks each): the layer input's fragments
 //     are read straight from global memory (a wave's tokens are its own; the rows are L2 resident after the first pass) one step
 //     ahead, split in registers; b1 is the accumulator init.  After ReLU the hidden tiles 2 kc, 2 kc + 1 are split in registers
@@ -15,9 +16,10 @@
 //     change, refilled in place before a graph replay: newsEncoders.WeightProducts), every step's slot ONE contiguous block in the order of its LDS image (swizzled [row][64-byte] rows: conflict-free
 //     ds_read_b128 fragments), copied by LDS-DMA into two ring slots: step s + 1 is issued during step s (one instruction per
 //     MFMA group), then one vmcnt(0) wait + barrier per step (the two-stage drain of gemm_sp_f32.hip).
-//   * epilogue: + b2 + the residual rows (fp32, re-read: L2 hits, all 38 quads of a lane requested before the first is used),
+//   * epilogue: + b2 + the residual rows (fp32, re-read: L2 hits, all 19 quads of a lane requested before the first is used),
 //     LayerNorm (the four lanes that share a token meet through two shuffles), then fp32 rows or, with `pool32`, the 32-token
-//     block means of the wave.
+//     block means of the wave pair 2 b, 2 b + 1: the odd wave hands its normalised values to the even one through the ring slot the
+//     tile's last step has just left.
 //   * every load is branch-free and the next step's (behind a tile's last step: the next tile's) fragments are requested
 //     unconditionally, so the only vmcnt waits of the tile loop are the one that ends each step and the epilogue's.
 #include <type_traits>
@@ -30,7 +32,8 @@ using namespace lime_dev;
 
 namespace {
 
-constexpr int BM = 128;                    // tokens per tile (4 waves x 32)
+constexpr int NW = 8, NTHR = 64 * NW;        // waves per workgroup: two per SIMD
+constexpr int BM = 16 * NW;                // tokens per tile: 128, one 16-token MFMA tile per wave
 constexpr int ND = 19, DP = 16 * ND;       // model columns carried: 304
 constexpr int NCH = 10;                    // 32-deep k chunks of the layer input (320 >= E)
 constexpr int PW = 128;                    // hidden columns per pass
@@ -57,7 +60,7 @@ struct FfnSpP {
 };
 
 template <bool POOL>
-__global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
+__global__ __launch_bounds__(NTHR, 1) void ffn_sp_kernel(const FfnSpP p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -70,17 +73,17 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
     const int E = p.E;
 
     float* const cs = reinterpret_cast<float*>(lds + CONST_OFF);
-    for (int c = tid; c < DP; c += 256) {
+    for (int c = tid; c < DP; c += NTHR) {
         cs[c] = c < E ? p.b2[c] : 0.f;
         cs[DP + c] = c < E ? p.g[c] : 0.f;
         cs[2 * DP + c] = c < E ? p.beta[c] : 0.f;
     }
-    for (int c = tid; c < p.F; c += 256) cs[3 * DP + c] = p.b1[c];
+    for (int c = tid; c < p.F; c += NTHR) cs[3 * DP + c] = p.b1[c];
     __syncthreads();                                   // nothing in flight yet
 
     const __amdgpu_buffer_rsrc_t rs_w1 = make_rsrc(p.w1p), rs_w2 = make_rsrc(p.w2p);
     // step s of a tile: pass s / 9, position s % 9 (0..4 linear1, 5..8 linear2).  The packed slot is one contiguous block: a slot of
-    // n KB is n DMA instructions (1 KB each, lane l lands at +16 l), instruction i of wave w is block (4 i + w + rot) % n.  The
+    // n KB is n DMA instructions (1 KB each, lane l lands at +16 l), instruction i of wave w is block (8 i + w + rot) % n.  The
     // rotation by the CU's position in its XCD keeps the 32 CUs that share an L2 from asking for the same lines at the same moment.
     const int rot = (int)((blockIdx.x >> 3) * 5u);
     auto issue_one = [&](int s, int slot, int i) {
@@ -88,49 +91,46 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
         unsigned char* const dst = lds + slot * SLOT;
         if (pos < L1_STEPS) {
             constexpr int NI = SLOT1 / 1024;
-            const int idx = 4 * i + wave;
+            const int idx = NW * i + wave;
             if (idx < NI) {
                 const int b = (idx + rot) % NI;
                 dma16(rs_w1, dst + b * 1024, (unsigned)lane * 16u, (pass * L1_STEPS + pos) * SLOT1 + b * 1024);
             }
         } else {
             constexpr int NI = SLOT2 / 1024;
-            const int idx = 4 * i + wave;
+            const int idx = NW * i + wave;
             if (idx < NI) {
                 const int b = (idx + rot) % NI;
                 dma16(rs_w2, dst + b * 1024, (unsigned)lane * 16u, (pass * (PW / 32) + pos - L1_STEPS) * SLOT2 + b * 1024);
             }
         }
     };
-    constexpr int DMA_PER_WAVE = (SLOT2 / 1024 + 3) / 4;     // 15: at most this many instructions per wave and slot
+    constexpr int DMA_PER_WAVE = (SLOT2 / 1024 + NW - 1) / NW;     // 8: at most this many instructions per wave and slot
     auto issue_w = [&](int s, int slot) {
         for (int i = 0; i < DMA_PER_WAVE; ++i) issue_one(s, slot, i);
     };
-    // the layer input fragments of a linear1 step: chunks 2 pos, 2 pos + 1, token halves tt, k 8 kg .. 8 kg + 7 as two quads
+    // the layer input fragments of a linear1 step: chunks 2 pos, 2 pos + 1, k 8 kg .. 8 kg + 7 as two quads
     // (E % 4 == 0: a quad is real or beyond E as a whole; rows beyond M and quads beyond E read zeros).  Branch-free (dead_bit,
     // dev_helpers.h): as `cond ? offset : OOB` every load became two exec-masked loads with a vmcnt(0) between them.
-    f32x4 xn[2][2][2];
+    f32x4 xn[2][2];
     auto load_x = [&](int t, int pos) {
         const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.x + (long)t * BM * p.ldx);
         const int rows_left = M - t * BM;
         const int ln = lane_here(), fi = ln & 15, kg = ln >> 4;
+        const int rl = 16 * wave + fi;
+        const unsigned ro = (unsigned)rl * (unsigned)p.ldx * 4u;
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int rl = 32 * wave + 16 * tt + fi;
-            const unsigned ro = (unsigned)rl * (unsigned)p.ldx * 4u;
+        for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
-            for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int col = 32 * (2 * pos + cc) + 8 * kg + 4 * q;
-                    xn[cc][tt][q] = buf_load4(rs_x, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
-                }
-        }
+            for (int q = 0; q < 2; ++q) {
+                const int col = 32 * (2 * pos + cc) + 8 * kg + 4 * q;
+                xn[cc][q] = buf_load4(rs_x, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
+            }
     };
     // vmcnt(0) with the fragments passed through it (wait_vm0_landed, dev_helpers.h): hipcc's own wait would sit in front of their
     // first use, at the top of the next step, behind that step's loads
     auto wait_x = [&]() {
-        wait_vm0_landed(xn[0][0][0], xn[0][0][1], xn[0][1][0], xn[0][1][1], xn[1][0][0], xn[1][0][1], xn[1][1][0], xn[1][1][1]);
+        wait_vm0_landed(xn[0][0], xn[0][1], xn[1][0], xn[1][1]);
     };
 
     // MFMA lane layout (v_mfma_f32_16x16x32_bf16, a = weight rows = output columns, b = tokens): lane (fi, kg) reads k 8 kg .. 8 kg + 7
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
         f.l = *reinterpret_cast<const bf16x8*>(b + 2 * term);
         return f;
     };
-    f32x4 acc1[2][NT1], acc2[2][ND];
+    f32x4 acc1[NT1], acc2[ND];
 
     // prologue: the first step of this workgroup's first tile
     issue_w(0, 0);
@@ -154,24 +154,20 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
     for (; tile < ntiles; tile += gridDim.x) {
         const bool last = tile + (int)gridDim.x >= ntiles;
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int t = 0; t < ND; ++t) acc2[tt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < ND; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         // step `pos` of pass `pass`: the fragments of its layer input (loaded one step ahead) leave xn before the next step's loads
         // reuse it; the next step goes into the other slot (everyone has left it: the barrier behind the previous step).  One weight
         // fragment (three terms) is read ahead of the MFMAs that use the previous one; sched_barriers keep hipcc from hoisting more.
         auto step = [&](auto pos_c, int pass) {
             constexpr int POS = decltype(pos_c)::value;
             const unsigned char* const sb = lds + (gs & 1) * SLOT + w_off;
-            f32x4 xc[2][2][2];
+            f32x4 xc[2][2];
             if constexpr (POS < L1_STEPS) {
 #pragma unroll
-                for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) { xc[cc][tt][0] = xn[cc][tt][0]; xc[cc][tt][1] = xn[cc][tt][1]; }
+                for (int cc = 0; cc < 2; ++cc) { xc[cc][0] = xn[cc][0]; xc[cc][1] = xn[cc][1]; }
             }
             // the next step: its layer input fragments now, its weight slot one DMA instruction per MFMA group below (issued all at
-            // once, a wave's 12-15 instructions queue in the CU's address path and the wave waits there before its first MFMA)
+            // once, a wave's 6-8 instructions queue in the CU's address path and the wave waits there before its first MFMA)
             const bool wrap = POS == STEPS - 1 && pass == NP - 1;
             const bool go = !(wrap && last);
             const int ns = wrap ? 0 : pass * STEPS + POS + 1;
@@ -189,22 +185,19 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
 #pragma unroll
                     for (int t = 0; t < NT1; ++t) {
                         const f32x4 b = *reinterpret_cast<const f32x4*>(b1 + 16 * t);
-                        acc1[0][t] = b;
-                        acc1[1][t] = b;
+                        acc1[t] = b;
                     }
                 }
                 SplitFrag w[2];
                 w[0] = wfrag(sb, TERM1);
 #pragma unroll
                 for (int cc = 0; cc < 2; ++cc) {
-                    const SplitFrag x0 = split_frag(xc[cc][0][0], xc[cc][0][1]);
-                    const SplitFrag x1 = split_frag(xc[cc][1][0], xc[cc][1][1]);
+                    const SplitFrag x0 = split_frag(xc[cc][0], xc[cc][1]);
 #pragma unroll
                     for (int t = 0; t < NT1; ++t) {
                         const int i = cc * NT1 + t;
                         if (i + 1 < 2 * NT1) w[(i + 1) & 1] = wfrag(sb + ((i + 1) / NT1) * CHUNK1 + ((i + 1) % NT1) * 1024, TERM1);
-                        acc1[0][t] = split_mfma16(w[i & 1], x0, acc1[0][t]);
-                        acc1[1][t] = split_mfma16(w[i & 1], x1, acc1[1][t]);
+                        acc1[t] = split_mfma16(w[i & 1], x0, acc1[t]);
                         __builtin_amdgcn_sched_barrier(0);
                         part(i);
                         __builtin_amdgcn_sched_barrier(0);
@@ -212,25 +205,21 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
                 }
                 if constexpr (POS == L1_STEPS - 1) {
 #pragma unroll
-                    for (int tt = 0; tt < 2; ++tt)
+                    for (int t = 0; t < NT1; ++t)
 #pragma unroll
-                        for (int t = 0; t < NT1; ++t)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) acc1[tt][t][r] = fmaxf(acc1[tt][t][r], 0.f);
+                        for (int r = 0; r < 4; ++r) acc1[t][r] = fmaxf(acc1[t][r], 0.f);
                 }
             } else {
                 // hidden chunk KC: tiles 2 KC and 2 KC + 1 side by side are the lane's 8 k slots (k = 32 KC + 16 a + 4 kg + r at slot
                 // 4 a + r: the order lime_ffn_pack_sp gives linear2's weight columns)
                 constexpr int KC = POS - L1_STEPS;
-                const SplitFrag h0 = split_frag(acc1[0][2 * KC], acc1[0][2 * KC + 1]);
-                const SplitFrag h1 = split_frag(acc1[1][2 * KC], acc1[1][2 * KC + 1]);
+                const SplitFrag h0 = split_frag(acc1[2 * KC], acc1[2 * KC + 1]);
                 SplitFrag w[2];
                 w[0] = wfrag(sb, TERM2);
 #pragma unroll
                 for (int t = 0; t < ND; ++t) {
                     if (t + 1 < ND) w[(t + 1) & 1] = wfrag(sb + (t + 1) * 1024, TERM2);
-                    acc2[0][t] = split_mfma16(w[t & 1], h0, acc2[0][t]);
-                    acc2[1][t] = split_mfma16(w[t & 1], h1, acc2[1][t]);
+                    acc2[t] = split_mfma16(w[t & 1], h0, acc2[t]);
                     __builtin_amdgcn_sched_barrier(0);
                     part(t);
                     __builtin_amdgcn_sched_barrier(0);
@@ -261,82 +250,91 @@ __global__ __launch_bounds__(256, 1) void ffn_sp_kernel(const FfnSpP p) {
         const int le = lane_here(), fi = le & 15, kg = le >> 4;      // epilogue-only offsets are computed here, not carried through the tile
         const float* const cs_ = cs + 4 * kg;
         const float inv_n = 1.0f / (float)E;
-        float mean[2], rstd[2];
-        // the residual rows: all 19 quads of a token half are requested before the first is used (the fence: left alone, hipcc
-        // sinks each load to its use and waits vmcnt(0) behind every one -- 38 round trips in a row per tile), half 1's before half
-        // 0's statistics
-        f32x4 rr[2][ND];
-        auto load_res = [&](int tt) {
-            const int rl = 32 * wave + 16 * tt + fi;
+        // the residual rows: all 19 quads of the lane's token are requested before the first is used (the fence: left alone, hipcc
+        // sinks each load to its use and waits vmcnt(0) behind every one -- 19 round trips in a row per tile)
+        const int rl = 16 * wave + fi;
+        f32x4 rr[ND];
+        {
             const unsigned ro = (unsigned)rl * (unsigned)p.ldx * 4u;
 #pragma unroll
             for (int t = 0; t < ND; ++t) {
                 const int col = 16 * t + 4 * kg;
-                rr[tt][t] = buf_load4(rs_r, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
+                rr[t] = buf_load4(rs_r, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
             }
-        };
-        load_res(0);
-        __builtin_amdgcn_sched_barrier(0);
-        load_res(1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            float s1 = 0.f;
-#pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                const f32x4 r = rr[tt][t];
-                const f32x4 b = *reinterpret_cast<const f32x4*>(cs_ + 16 * t);
-                const f32x4 v = acc2[tt][t] + b + r;
-                acc2[tt][t] = v;
-                s1 += (v[0] + v[1]) + (v[2] + v[3]);
-            }
-            s1 += __shfl_xor(s1, 16);
-            s1 += __shfl_xor(s1, 32);
-            mean[tt] = s1 * inv_n;
-            float s2 = 0.f;
-#pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                if (16 * t + 4 * kg < E) {
-                    const f32x4 d = acc2[tt][t] - mean[tt];
-                    s2 += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-                }
-            }
-            s2 += __shfl_xor(s2, 16);
-            s2 += __shfl_xor(s2, 32);
-            rstd[tt] = rsqrtf(s2 * inv_n + p.eps);
-            __builtin_amdgcn_sched_barrier(0);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        float s1 = 0.f;
+#pragma unroll
+        for (int t = 0; t < ND; ++t) {
+            const f32x4 r = rr[t];
+            const f32x4 b = *reinterpret_cast<const f32x4*>(cs_ + 16 * t);
+            const f32x4 v = acc2[t] + b + r;
+            acc2[t] = v;
+            s1 += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+        s1 += __shfl_xor(s1, 16);
+        s1 += __shfl_xor(s1, 32);
+        const float mean = s1 * inv_n;
+        float s2 = 0.f;
+#pragma unroll
+        for (int t = 0; t < ND; ++t) {
+            if (16 * t + 4 * kg < E) {
+                const f32x4 d = acc2[t] - mean;
+                s2 += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+            }
+        }
+        s2 += __shfl_xor(s2, 16);
+        s2 += __shfl_xor(s2, 32);
+        const float rstd = rsqrtf(s2 * inv_n + p.eps);
+        __builtin_amdgcn_sched_barrier(0);
         const float* const gs_ = cs_ + DP;
         const float* const es_ = cs_ + 2 * DP;
+        auto norm = [&](int t) {
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(gs_ + 16 * t);
+            const f32x4 be = *reinterpret_cast<const f32x4*>(es_ + 16 * t);
+            return (acc2[t] - mean) * rstd * ga + be;
+        };
         if constexpr (POOL) {
-            // block row (row0 + 32 wave) / 32: the column means over this wave's 32 tokens (all valid or all beyond M)
-            const int rl0 = 32 * wave;
+            // block row (row0 + 32 b) / 32: the column means over the 32 tokens of the wave pair 2 b, 2 b + 1 (all valid or all beyond
+            // M).  The odd wave hands its normalised values to the even wave (same lane, same register: y = y_even + y_odd, then the
+            // 16-lane sum, then 1/32) through the ring slot the tile's last step has just left -- the other one holds the next tile's
+            // first step.  A slot takes 57 of the 76 KB the four pairs have: two rounds of ten and nine column tiles.  The barrier
+            // behind the second round stands in front of the next tile's first step, whose DMA goes into this slot.
+            constexpr int RT = (ND + 1) / 2;
+            const int pair = wave >> 1;
+            const bool odd = (wave & 1) != 0;
+            f32x4* const stage = reinterpret_cast<f32x4*>(lds + ((gs + 1) & 1) * SLOT) + pair * RT * 64 + le;
+            const int rl0 = 32 * pair;
             const __amdgpu_buffer_rsrc_t rs_p = make_rsrc(p.out + ((row0 + rl0) >> 5) * p.ldo);
             const bool rows_ok = rl0 < rows_left;
 #pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                const f32x4 ga = *reinterpret_cast<const f32x4*>(gs_ + 16 * t);
-                const f32x4 be = *reinterpret_cast<const f32x4*>(es_ + 16 * t);
-                f32x4 y = (acc2[0][t] - mean[0]) * rstd[0] * ga + be;
-                y += (acc2[1][t] - mean[1]) * rstd[1] * ga + be;
+            for (int r = 0; r < 2; ++r) {
+                constexpr int T1[2] = {RT, ND};
+                if (odd) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) y[j] = row16_sum(y[j]) * (1.0f / 32.0f);
-                const int col = 16 * t + 4 * kg;
-                buf_store4(y, rs_p, (rows_ok && fi == 0 && col < E) ? (unsigned)col * 4u : OOB, 0);
+                    for (int t = RT * r; t < T1[r]; ++t) stage[(t - RT * r) * 64] = norm(t);
+                }
+                ring_barrier();
+                if (!odd) {
+#pragma unroll
+                    for (int t = RT * r; t < T1[r]; ++t) {
+                        f32x4 y = norm(t);
+                        y += stage[(t - RT * r) * 64];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) y[j] = row16_sum(y[j]) * (1.0f / 32.0f);
+                        const int col = 16 * t + 4 * kg;
+                        buf_store4(y, rs_p, (rows_ok && fi == 0 && col < E) ? (unsigned)col * 4u : OOB, 0);
+                    }
+                }
+                ring_barrier();
             }
         } else {
             const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(p.out + row0 * p.ldo);
+            const unsigned ro = (unsigned)rl * (unsigned)p.ldo * 4u;
 #pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-                const int rl = 32 * wave + 16 * tt + fi;
-                const unsigned ro = (unsigned)rl * (unsigned)p.ldo * 4u;
-#pragma unroll
-                for (int t = 0; t < ND; ++t) {
-                    const f32x4 ga = *reinterpret_cast<const f32x4*>(gs_ + 16 * t);
-                    const f32x4 be = *reinterpret_cast<const f32x4*>(es_ + 16 * t);
-                    const int col = 16 * t + 4 * kg;
-                    buf_store4((acc2[tt][t] - mean[tt]) * rstd[tt] * ga + be, rs_c, (rl < rows_left && col < E) ? ro + (unsigned)col * 4u : OOB, 0);
-                }
+            for (int t = 0; t < ND; ++t) {
+                const int col = 16 * t + 4 * kg;
+                buf_store4(norm(t), rs_c, (rl < rows_left && col < E) ? ro + (unsigned)col * 4u : OOB, 0);
             }
         }
     }
@@ -421,7 +419,7 @@ extern "C" int lime_encoder_ffn_sp(const lime_ffn_sp_args* a, void* stream) {
     const long ntiles = ((long)a->M + BM - 1) / BM;
     const long nwg = lime_persistent_grid(ntiles);
     hipStream_t s = (hipStream_t)stream;
-    if (a->pool32) hipLaunchKernelGGL((ffn_sp_kernel<true>), dim3((unsigned)nwg), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((ffn_sp_kernel<false>), dim3((unsigned)nwg), dim3(256), 0, s, p);
+    if (a->pool32) hipLaunchKernelGGL((ffn_sp_kernel<true>), dim3((unsigned)nwg), dim3(NTHR), 0, s, p);
+    else hipLaunchKernelGGL((ffn_sp_kernel<false>), dim3((unsigned)nwg), dim3(NTHR), 0, s, p);
     return lime_check_launch("lime_encoder_ffn_sp");
 }

@@ -2,19 +2,20 @@
 // launch with split products on the bf16 matrix cores (split_mfma.h: three bf16 terms per fp32 operand, six MFMAs per 16 x 16 x 32
 // block).  Token-stationary, the geometry and the weight ring of ffn_sp_f32.hip's linear2 half:
 //
-//   * a workgroup (4 waves, one per SIMD, one per CU) owns a 128-token tile; a wave owns 32 tokens (two 16-token halves) x all
-//     304 model columns: 2 x 19 accumulator tiles, zero at the start of a tile.
+//   * a workgroup (8 waves, two per SIMD, one workgroup per CU) owns a 128-token tile; wave w owns tokens 16 w .. 16 w + 15 x all
+//     304 model columns: 19 accumulator tiles, zero at the start of a tile.  Two waves share a SIMD so that one's waits leave the
+//     matrix pipe to the other.
 //   * ten steps per tile, one 32-deep k chunk each.  Wo is pre-split into three bf16 term images by lime_oproj_pack_sp (inside the
 //     forward, or once per weight change: newsEncoders.WeightProducts), every chunk ONE contiguous block in the order of its LDS image
 //     (swizzled [row][64-byte] rows: conflict-free ds_read_b128 fragments), copied by LDS-DMA into two ring slots: step s + 1 is
 //     issued during step s (one instruction per MFMA group), then one vmcnt(0) wait + barrier per step.
-//   * B operand: the attention output rows of the wave's own tokens, straight from global memory one step ahead (four 16-byte
+//   * B operand: the attention output rows of the wave's own tokens, straight from global memory one step ahead (two 16-byte
 //     loads per lane and step), split in registers.
-//   * epilogue, one token half at a time: + bo, + the residual row -- res[row], or the word row table[res_ids[row]] (an HBM gather,
-//     through a 64-bit row address per lane) and then the positional row pe[row % period] (cache-hot) in a second sweep --
-//     LayerNorm over the E real columns (the four lanes that share a token meet through two shuffles), fp32 rows out.  Half 0's
-//     residual rows are requested BEFORE the tile's last step (their latency falls under its 228 MFMAs; no hidden state is live, so
-//     the 76 landing registers are free), half 1's before half 0's statistics.
+//   * epilogue: + bo, + the residual row -- res[row], or the word row table[res_ids[row]] (an HBM gather, through a 64-bit row
+//     address per lane) and then the positional row pe[row % period] (cache-hot) in a second sweep -- LayerNorm over the E real
+//     columns (the four lanes that share a token meet through two shuffles), fp32 rows out.  The word rows are requested BEFORE the
+//     tile's last step (their latency falls under its 114 MFMAs; the 76 landing registers are free), the positional rows behind it,
+//     ahead of the first sweep.
 //   * a row's arithmetic does not depend on the tile or the launch it sits in: one k order, one reduction order.
 #include <type_traits>
 
@@ -26,13 +27,14 @@ using namespace lime_dev;
 
 namespace {
 
-constexpr int BM = 128;                    // tokens per tile (4 waves x 32)
+constexpr int NW = 8, NTHR = 64 * NW;        // waves per workgroup: two per SIMD
+constexpr int BM = 16 * NW;                // tokens per tile: 128, one 16-token MFMA tile per wave
 constexpr int ND = 19, DP = 16 * ND;       // model columns carried: 304
 constexpr int NCH = 10;                    // 32-deep k chunks (320 >= E): the steps of a tile
 constexpr int TERM = DP * 64;              // bytes of one term image of a chunk: [304 rows][32 bf16]
 constexpr int SLOT = 3 * TERM;             // 58,368: a step
 constexpr int NI = SLOT / 1024;            // 57 DMA instructions (1 KB each) per slot
-constexpr int DMA_PER_WAVE = (NI + 3) / 4; // 15: at most this many per wave and slot
+constexpr int DMA_PER_WAVE = (NI + NW - 1) / NW;     // 8: at most this many per wave and slot
 constexpr int CONST_OFF = 2 * SLOT;        // bo, gamma, beta [304] fp32
 constexpr int LDS_BYTES = CONST_OFF + 3 * DP * 4;                // 120,384 of the CU's 163,840
 
@@ -46,7 +48,7 @@ struct OprojSpP {
     const int* m_dev;
 };
 
-__global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
+__global__ __launch_bounds__(NTHR, 1) void oproj_sp_kernel(const OprojSpP p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
     const int E = p.E;
 
     float* const cs = reinterpret_cast<float*>(lds + CONST_OFF);
-    for (int c = tid; c < DP; c += 256) {
+    for (int c = tid; c < DP; c += NTHR) {
         cs[c] = c < E ? p.bias[c] : 0.f;
         cs[DP + c] = c < E ? p.g[c] : 0.f;
         cs[2 * DP + c] = c < E ? p.beta[c] : 0.f;
@@ -67,11 +69,11 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
 
     const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.wp), rs_pe = make_rsrc(p.pe);
     // step s of a tile is chunk s: one contiguous block of 57 KB = 57 DMA instructions (1 KB each, lane l lands at +16 l), instruction
-    // i of wave w is block (4 i + w + rot) % 57.  The rotation by the CU's position in its XCD keeps the 32 CUs that share an L2 from
+    // i of wave w is block (8 i + w + rot) % 57.  The rotation by the CU's position in its XCD keeps the 32 CUs that share an L2 from
     // asking for the same lines at the same moment.
     const int rot = (int)((blockIdx.x >> 3) * 5u);
     auto issue_one = [&](int s, int slot, int i) {
-        const int idx = 4 * i + wave;
+        const int idx = NW * i + wave;
         if (idx < NI) {
             const int b = (idx + rot) % NI;
             dma16(rs_w, lds + slot * SLOT + b * 1024, (unsigned)lane * 16u, s * SLOT + b * 1024);
@@ -79,45 +81,38 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
     };
     // Every load below is branch-free (dead_bit, dev_helpers.h): a join of divergent control flow would wait vmcnt(0) in front of the
     // MFMAs -- with the residual gather in flight.
-    // the attention rows of step s: token halves tt, k 32 s + 8 kg .. + 7 as two quads (E % 4 == 0: a quad is real or beyond E as a
+    // the attention rows of step s: k 32 s + 8 kg .. + 7 as two quads (E % 4 == 0: a quad is real or beyond E as a
     // whole; rows beyond M and quads beyond E read zeros)
-    f32x4 xn[2][2];
+    f32x4 xn[2];
     auto load_x = [&](int t, int s) {
         const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.a + (long)t * BM * p.lda);
         const int rows_left = M - t * BM;
         const int ln = lane_here(), fi = ln & 15, kg = ln >> 4;
+        const int rl = 16 * wave + fi;
+        const unsigned ro = (unsigned)rl * (unsigned)p.lda * 4u;
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int rl = 32 * wave + 16 * tt + fi;
-            const unsigned ro = (unsigned)rl * (unsigned)p.lda * 4u;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int col = 32 * s + 8 * kg + 4 * q;
-                xn[tt][q] = buf_load4(rs_x, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
-            }
+        for (int q = 0; q < 2; ++q) {
+            const int col = 32 * s + 8 * kg + 4 * q;
+            xn[q] = buf_load4(rs_x, (ro + (unsigned)col * 4u) | dead_bit(rows_left - 1 - rl, E - 1 - col), 0);
         }
     };
-    // the word ids of the lane's two tokens (0 without ids and for rows beyond M), read at the top of the tile: a step of their own
-    // ahead of the rows they address
-    int rid[2];
+    // the word id of the lane's token (0 without ids and for rows beyond M), read at the top of the tile: a step of its own ahead of
+    // the row it addresses
+    int rid;
     auto load_ids = [&](int t) {
         const __amdgpu_buffer_rsrc_t rs_i = make_rsrc(p.ids + (long)t * BM);
         const int rows_left = p.ids ? M - t * BM : 0;
-        const int fi = lane_here() & 15;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int rl = 32 * wave + 16 * tt + fi;
-            rid[tt] = buf_load_i32(rs_i, (unsigned)rl * 4u | dead_bit(rows_left - 1 - rl, 0));
-        }
+        const int rl = 16 * wave + (lane_here() & 15);
+        rid = buf_load_i32(rs_i, (unsigned)rl * 4u | dead_bit(rows_left - 1 - rl, 0));
     };
-    // the residual rows of token half tt of tile t: the 19 quads of res[row] or table[rid[tt]], through a 64-bit row address.  A lane
-    // whose row is beyond M asks for row 0, a quad beyond E for quad 0 of its row (both are there); neither value is used -- the
-    // statistics and the stores skip them.
+    // the residual rows of tile t: the 19 quads of res[row] or table[rid], through a 64-bit row address.  A lane whose row is beyond
+    // M asks for row 0, a quad beyond E for quad 0 of its row (both are there); neither value is used -- the statistics and the
+    // stores skip them.
     f32x4 rr[ND], pq[ND];
-    auto load_res = [&](int t, int tt) {
+    auto load_res = [&](int t) {
         const int ln = lane_here(), fi = ln & 15, kg = ln >> 4;
-        const long row = (long)t * BM + 32 * wave + 16 * tt + fi;
-        int id = rid[tt];
+        const long row = (long)t * BM + 16 * wave + fi;
+        int id = rid;
         asm volatile("" : "+v"(id));                   // the id is waited for HERE (its address arithmetic would be hoisted to the load)
         const float* const rp = p.res + (row < M ? (p.ids ? (long)id : row) : 0L) * p.ldr;
 #pragma unroll
@@ -127,9 +122,9 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
         }
     };
     // ... and their positional rows pe[row % period] (a few KB shared by every tile: cache hits); zeros without a positional table
-    auto load_pe = [&](int t, int tt) {
+    auto load_pe = [&](int t) {
         const int ln = lane_here(), fi = ln & 15, kg = ln >> 4;
-        const int row = t * BM + 32 * wave + 16 * tt + fi;
+        const int row = t * BM + 16 * wave + fi;
         const unsigned ro = ((unsigned)row % (unsigned)(p.pe ? p.period : 1)) * (unsigned)p.ldpe * 4u;
         const int live = p.pe ? M - 1 - row : -1;
 #pragma unroll
@@ -149,10 +144,10 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
         f.l = *reinterpret_cast<const bf16x8*>(b + 2 * TERM);
         return f;
     };
-    f32x4 acc[2][ND];
+    f32x4 acc[ND];
     // vmcnt(0) with the attention fragments passed through it (wait_vm0_landed, dev_helpers.h): hipcc's own wait would sit in front of
     // the fragments' first use, at the top of the next step -- where the tile's word ids and the previous tile's stores are in flight
-    auto wait_all = [&]() { wait_vm0_landed(xn[0][0], xn[0][1], xn[1][0], xn[1][1]); };
+    auto wait_all = [&]() { wait_vm0_landed(xn[0], xn[1]); };
 
     // prologue: the first step of this workgroup's first tile
     for (int i = 0; i < DMA_PER_WAVE; ++i) issue_one(0, 0, i);
@@ -163,24 +158,21 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
     for (; tile < ntiles; tile += gridDim.x) {
         const bool last = tile + (int)gridDim.x >= ntiles;
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int t = 0; t < ND; ++t) acc[tt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < ND; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         load_ids(tile);                                // (lands behind step 0's wait)
         // step s: its attention fragments (loaded one step ahead) leave xn before the next step's loads reuse it; the next step's
         // weights go into the other slot (everyone has left it: the barrier behind the previous step), one DMA instruction per MFMA
         // group.  One weight fragment (three terms) is read ahead of the MFMAs that use the previous one; sched_barriers keep hipcc
-        // from hoisting more.  The tile's last step also carries half 0's residual rows and the next tile's first step.
+        // from hoisting more.  The tile's last step also carries the residual (word) rows and the next tile's first step.
         auto step = [&](auto last_c, int s) {
             constexpr bool LAST = decltype(last_c)::value;
             const unsigned char* const sb = lds + (gs & 1) * SLOT + w_off;
-            const SplitFrag x0 = split_frag(xn[0][0], xn[0][1]);
-            const SplitFrag x1 = split_frag(xn[1][0], xn[1][1]);
+            const SplitFrag x0 = split_frag(xn[0], xn[1]);
             __builtin_amdgcn_sched_barrier(0);
             const bool go = !(LAST && last);
             const int ns = LAST ? 0 : s + 1;
             const int nslot = (gs + 1) & 1;
-            if constexpr (LAST) load_res(tile, 0);
+            if constexpr (LAST) load_res(tile);
             // (unconditional: behind this workgroup's last tile every row is beyond M and nothing is read; under `if (go)` the
             // fragments become a phi whose copy waits for these loads -- and the gather in front of them -- ahead of the MFMAs)
             load_x(LAST ? tile + (int)gridDim.x : tile, ns);
@@ -189,8 +181,7 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
 #pragma unroll
             for (int t = 0; t < ND; ++t) {
                 if (t + 1 < ND) w[(t + 1) & 1] = wfrag(sb + (t + 1) * 1024);
-                acc[0][t] = split_mfma16(w[t & 1], x0, acc[0][t]);
-                acc[1][t] = split_mfma16(w[t & 1], x1, acc[1][t]);
+                acc[t] = split_mfma16(w[t & 1], x0, acc[t]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (go && t < DMA_PER_WAVE) issue_one(ns, nslot, t);
                 __builtin_amdgcn_sched_barrier(0);
@@ -209,65 +200,53 @@ __global__ __launch_bounds__(256, 1) void oproj_sp_kernel(const OprojSpP p) {
         const int le = lane_here(), fi = le & 15, kg = le >> 4;      // epilogue-only offsets are computed here, not carried through the tile
         const float* const cs_ = cs + 4 * kg;
         const float inv_n = 1.0f / (float)E;
-        float mean[2], rstd[2];
+        // the word rows are here (the wait behind the last step); the cache-hot positional rows are requested now and land under
+        // the first sweep
+        load_pe(tile);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            // half 0's word rows are here (the wait behind the last step); half 1's are requested as soon as half 0's have left rr,
-            // ahead of half 0's positional sweep and statistics -- vmcnt counts in issue order, so the cache-hot positional rows of
-            // half 0 are requested BEFORE that gather (both halves' landing registers during the last step would not fit the VGPRs)
-            if (tt == 0) load_pe(tile, 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(cs_ + 16 * t);
-                acc[tt][t] = acc[tt][t] + b + rr[t];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (tt == 0) load_res(tile, 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < ND; ++t) acc[tt][t] += pq[t];
-            __builtin_amdgcn_sched_barrier(0);
-            float s1 = 0.f;
-#pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                if (16 * t + 4 * kg < E) {
-                    const f32x4 v = acc[tt][t];
-                    s1 += (v[0] + v[1]) + (v[2] + v[3]);
-                }
-            }
-            s1 += __shfl_xor(s1, 16);
-            s1 += __shfl_xor(s1, 32);
-            mean[tt] = s1 * inv_n;
-            float s2 = 0.f;
-#pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                if (16 * t + 4 * kg < E) {
-                    const f32x4 d = acc[tt][t] - mean[tt];
-                    s2 += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-                }
-            }
-            s2 += __shfl_xor(s2, 16);
-            s2 += __shfl_xor(s2, 32);
-            rstd[tt] = rsqrtf(s2 * inv_n + p.eps);
-            __builtin_amdgcn_sched_barrier(0);
-            if (tt == 0) load_pe(tile, 1);             // (behind the statistics: with it in flight through them the VGPRs overflow)
-            __builtin_amdgcn_sched_barrier(0);
+        for (int t = 0; t < ND; ++t) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(cs_ + 16 * t);
+            acc[t] = acc[t] + b + rr[t];
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < ND; ++t) acc[t] += pq[t];
+        __builtin_amdgcn_sched_barrier(0);
+        float s1 = 0.f;
+#pragma unroll
+        for (int t = 0; t < ND; ++t) {
+            if (16 * t + 4 * kg < E) {
+                const f32x4 v = acc[t];
+                s1 += (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        }
+        s1 += __shfl_xor(s1, 16);
+        s1 += __shfl_xor(s1, 32);
+        const float mean = s1 * inv_n;
+        float s2 = 0.f;
+#pragma unroll
+        for (int t = 0; t < ND; ++t) {
+            if (16 * t + 4 * kg < E) {
+                const f32x4 d = acc[t] - mean;
+                s2 += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+            }
+        }
+        s2 += __shfl_xor(s2, 16);
+        s2 += __shfl_xor(s2, 32);
+        const float rstd = rsqrtf(s2 * inv_n + p.eps);
+        __builtin_amdgcn_sched_barrier(0);
         const float* const gs_ = cs_ + DP;
         const float* const es_ = cs_ + 2 * DP;
         const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(p.out + row0 * p.ldo);
+        const int rl = 16 * wave + fi;
+        const unsigned ro = (unsigned)rl * (unsigned)p.ldo * 4u;
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int rl = 32 * wave + 16 * tt + fi;
-            const unsigned ro = (unsigned)rl * (unsigned)p.ldo * 4u;
-#pragma unroll
-            for (int t = 0; t < ND; ++t) {
-                const f32x4 ga = *reinterpret_cast<const f32x4*>(gs_ + 16 * t);
-                const f32x4 be = *reinterpret_cast<const f32x4*>(es_ + 16 * t);
-                const int col = 16 * t + 4 * kg;
-                buf_store4((acc[tt][t] - mean[tt]) * rstd[tt] * ga + be, rs_c, (rl < rows_left && col < E) ? ro + (unsigned)col * 4u : OOB, 0);
-            }
+        for (int t = 0; t < ND; ++t) {
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(gs_ + 16 * t);
+            const f32x4 be = *reinterpret_cast<const f32x4*>(es_ + 16 * t);
+            const int col = 16 * t + 4 * kg;
+            buf_store4((acc[t] - mean) * rstd * ga + be, rs_c, (rl < rows_left && col < E) ? ro + (unsigned)col * 4u : OOB, 0);
         }
     }
 }
@@ -328,6 +307,6 @@ extern "C" int lime_encoder_oproj_sp(const lime_oproj_sp_args* a, void* stream) 
     p.res = a->res; p.ldr = a->ldr; p.ids = a->res_ids; p.pe = a->res_pe; p.ldpe = a->ldr_pe; p.period = a->res_period;
     p.out = a->out; p.ldo = a->ldo; p.M = a->M; p.E = a->E; p.m_dev = a->m_dev;
     const long ntiles = ((long)a->M + BM - 1) / BM;
-    hipLaunchKernelGGL(oproj_sp_kernel, dim3((unsigned)lime_persistent_grid(ntiles)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(oproj_sp_kernel, dim3((unsigned)lime_persistent_grid(ntiles)), dim3(NTHR), 0, (hipStream_t)stream, p);
     return lime_check_launch("lime_encoder_oproj_sp");
 }
