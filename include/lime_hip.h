@@ -928,6 +928,20 @@ int lime_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float
 int lime_nll_softmax_f32(const float* logits, int64_t ld, int32_t B, int32_t K, float* loss, float* dlogits, int64_t ldd,
                          void* stream);
 
+/* A linear classifier and its cross-entropy against an integer target in one launch (csrc/linear_xent_f32.hip): CROWN's category
+ * predictor on the title intent vector (newsEncoders.py:358-364, :375-393; F.cross_entropy on a one-hot probability target).  Per row r
+ * of x [M, D] (leading dimension ldx >= D: a column slice of a wider tensor), with w [C, D], b [C] (NULL: no bias), in fp32:
+ *     z = x[r] w^T + b;   row_loss[r] = scale (logsumexp(z) - z[target[r]])   (max-subtracted);
+ *     dlogits[r, :] = scale (softmax(z) - onehot(target[r]))   [M, C];   dx[r, :] = dlogits[r, :] w   [M, D], leading dimension lddx.
+ * dlogits and dx are optional (NULL: not computed).  A target outside [0, C) is the all-zero one-hot row: its row_loss, dlogits and dx
+ * are exact zeros and nothing is read at its index.  The scalar loss is the sum of row_loss (lime_colsum_f32 over [M, 1]: fixed order);
+ * scale = weight / M gives the weighted mean.  M, D, C >= 1, ldx >= D, lddx >= D (LIME_ERR_BAD_ARG otherwise, as for a NULL x, w,
+ * target or row_loss); C <= 1024 (LIME_ERR_UNSUPPORTED beyond), checked in that order before any launch.  A wave per row, w staged in LDS
+ * while it fits 64 KB and read through L2 beyond; 16-byte accesses when D % 4 == 0 and x, w, dx and their leading dimensions are
+ * 16-byte aligned.  Explicit fmaf, fixed-order sums, no atomics, no workspace: a row's bits depend on neither M, its place nor the run. */
+int lime_linear_xent_f32(const float* x, int64_t ldx, const float* w, const float* b, const int32_t* target, float scale,
+                         float* row_loss, float* dlogits, float* dx, int64_t lddx, int32_t M, int32_t D, int32_t C, void* stream);
+
 /* ---- backward of the fused tail kernels (csrc/tail_backward_f32.hip) -------------------------------------------------- */
 
 /* Backward of lime_intent_fuse_f32 (newsEncoders.py:355-371: intent attention over the k intents of title and body, cosine

@@ -70,10 +70,12 @@ __global__ __launch_bounds__(256) void nll_softmax_kernel(const float* __restric
         for (int j = 1; j < K; ++j) mx = fmaxf(mx, x[j]);
         float s = 0.f;
         for (int j = 0; j < K; ++j) s += expf(x[j] - mx);
-        const float lse = mx + logf(s);
-        part += lse - x[0];
+        // every difference is taken against the row's maximum: x[j] - (mx + logf(s)) rounds at the size of the logits (4e-6 at 100),
+        // which 1 - softmax[0] of a confident row does not survive (logits of 100 occur: the dot product of unnormalised vectors)
+        part += logf(s) - (x[0] - mx);
+        const float inv_s = 1.0f / s;
         if (dlogits)
-            for (int j = 0; j < K; ++j) dlogits[(long)b * ldd + j] = (expf(x[j] - lse) - (j == 0 ? 1.0f : 0.f)) * inv_b;
+            for (int j = 0; j < K; ++j) dlogits[(long)b * ldd + j] = (expf(x[j] - mx) * inv_s - (j == 0 ? 1.0f : 0.f)) * inv_b;
     }
     const float tot = block_sum_4(part, red);
     if (threadIdx.x == 0) *loss = tot * inv_b;

@@ -1,5 +1,6 @@
 """Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE,KCNN}-{CROWN,ATT,MHSA} scoring path and the baselines without LIME,
 {CROWN,CNN,NAML,MHSA,KCNN}-{ATT,MHSA} and CROWN-CROWN (reference model.py:11-187)."""
+import functools
 import os
 
 import torch
@@ -75,6 +76,18 @@ class Model(nn.Module):
     ``config.click_predictor``: 'dot_product' (the default: the lifetime-weighted dot product) or 'mlp' (model.py:113-115, :182-184:
     ``logits = out(dropout(relu(mlp(cat[user, news]))))`` with ``mlp``: 2 D -> D // 2 and ``out``: D // 2 -> 1, the last four keys of the
     state_dict; no remaining-lifetime weight, ``remaining_lifetime`` is accepted and not read), with any of the models above.
+
+    ``config.alpha`` (config.py:81, the weight of CROWN's category-prediction loss): with a bare CROWN news encoder ('CROWN' with
+    the CROWN, ATT or MHSA user encoder) and ``alpha != 0``, a forward on the differentiable path leaves on
+    ``model.news_encoder.auxiliary_loss`` a 0-dim tensor with autograd: alpha x the mean over the B H history rows (padded slots
+    count, with category 0) of the cross-entropy of ``category_predictor.fc(title intent vector)`` against the news' category
+    (newsEncoders.py:358-364), which trainer.py:137-139 adds to the loss -- ``loss = loss + model.news_encoder.auxiliary_loss.mean()``
+    works as written.  The reference runs the predictor on the candidate rows as well (model.py:171) and overwrites that value with the
+    history call's (userEncoders.py:110): the candidates' value is not computed here.  Every other forward -- scoring, the cached
+    passes, the serving entries -- sets the attribute to None (the reference computes the value in eval mode too, where nothing
+    reads it).  Under LIME the attribute stays None and ``category_predictor`` untrained whatever ``alpha`` is (the wrapper copies the
+    attribute once at construction, newsEncoders.py:100-103), and with ``alpha == 0`` nothing is computed: the reference's term is
+    then an exact zero with exact-zero gradients, on which Adam moves nothing (``training.trains_category_predictor``).
 
     Scoring (eval mode, or any call under ``torch.no_grad()``): the forward pass runs entirely in hand-written HIP
     kernels and records no autograd graph.  In training mode with grad enabled (``model.train(); model(...)``, what
@@ -186,6 +199,7 @@ class Model(nn.Module):
                 user_history_mask, user_history_graph, user_history_category_mask, user_history_category_indices, news_category,
                 news_subCategory, news_title_text, news_title_mask, news_title_entity, news_content_text, news_content_mask,
                 news_content_entity, news_freshness, news_user_topic_lifetime, remaining_lifetime)
+        self.news_encoder.auxiliary_loss = None        # only the differentiable path below leaves a term (no stale tensor survives)
         if self.training and (torch.is_grad_enabled() or self.news_encoder.training or self.user_encoder.training):
             # trainer.py:131-145: model.train(); logits = model(...); loss.backward() -- the differentiable path.  It is also the
             # path with the training-mode dropouts (model.train() under no_grad: the layer's p = 0.2 dropout of layers.py:74 is
@@ -1064,3 +1078,18 @@ class Model(nn.Module):
             logits = self._row_logits(history_embedding, news_category, news_subCategory, user_category, user_subCategory,
                                       user_history_mask, news_representation, remaining_lifetime.float(), agg=agg)   # model.py:174-184
         return logits
+
+
+def _clears_auxiliary_loss(fn):
+    """An entry that scores, caches or serves leaves no category-prediction term behind: ``news_encoder.auxiliary_loss`` is None after
+    it, whatever an earlier training forward stored there."""
+    @functools.wraps(fn)
+    def entry(self, *args, **kwargs):
+        self.news_encoder.auxiliary_loss = None
+        return fn(self, *args, **kwargs)
+    return entry
+
+
+for _name in ('score_impressions', 'build_news_cache', 'build_recurrence_cache', 'score_behaviors', 'score_pool', 'recommend',
+              'score_schedule', 'recommend_schedule', 'score_lists', 'recommend_lists'):
+    setattr(Model, _name, _clears_auxiliary_loss(getattr(Model, _name)))

@@ -2045,6 +2045,41 @@ def nll_softmax(logits, want_grad=True):
     return loss, d
 
 
+def linear_xent(x, w, b, target, scale, want_grads=True):
+    """The linear classifier z = x w^T + b and its cross-entropy against ``target`` in one launch (``lime_linear_xent_f32``): ->
+    (loss [1], row_loss [M], dlogits [M, C] or None, dx [M, D] or None) with row_loss = scale (logsumexp(z) - z[target]), loss their
+    fixed-order sum (the column-sum kernel), dlogits = scale (softmax(z) - onehot(target)) and dx = dlogits w.  x [M, D] may be a
+    column slice of a wider tensor; w [C, D] with C <= 1024; b [C] or None; target int32 [M] -- a target outside [0, C) is the all-zero
+    one-hot row (zero loss, zero gradients).  ``scale`` = weight / M gives the weighted mean over the rows."""
+    # shapes first (they read no device memory), then dtype / device / layout
+    for t, name in ((x, 'x'), (w, 'w')):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError('%s must be a 2-D tensor' % name)
+    M, D = x.shape
+    C = w.shape[0]
+    if w.shape[1] != D:
+        raise ValueError('x has %d columns, w has %d' % (D, w.shape[1]))
+    if M < 1 or D < 1 or not 1 <= C <= 1024:
+        raise ValueError('linear_xent needs M >= 1, D >= 1 and 1 <= C <= 1024, got M = %d, D = %d, C = %d' % (M, D, C))
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.int32:
+        raise TypeError('target must be an int32 tensor')
+    if target.numel() != M or (b is not None and b.numel() != C):
+        raise ValueError('target must have M = %d elements and b C = %d' % (M, C))
+    _mat(x, 'x')
+    _mat(w, 'w')
+    if not w.is_contiguous():
+        raise ValueError('w must be contiguous')
+    _vec(b, 'b', C)
+    _vec(target, 'target', M, dtype=torch.int32)
+    lib = _lib.load()
+    row_loss = torch.empty(M, dtype=torch.float32, device=x.device)
+    d = torch.empty((M, C), dtype=torch.float32, device=x.device) if want_grads else None
+    dx = torch.empty((M, D), dtype=torch.float32, device=x.device) if want_grads else None
+    check(lib.lime_linear_xent_f32(_p(x), _ld(x), _p(w), _p(b), _p(target), float(scale), _p(row_loss), _p(d), _p(dx), D, M, D, C,
+                                   _stream()), 'lime_linear_xent_f32')
+    return colsum(row_loss.view(M, 1)), row_loss, d, dx
+
+
 # ---- backward of the fused tail kernels -----------------------------------------------------------------------------------
 def intent_fuse_bwd(intents, att_hidden, affine2_t, affine2_b, dcontent, M, k, D, A):
     """-> (d_intents [2Mk, D], d_hidden [2Mk, A], d_affine2_title [A], d_affine2_body [A])."""

@@ -129,6 +129,44 @@ class _IntentFuse(torch.autograd.Function):
         return d_int, d_hid, da_t, da_b, None, None
 
 
+class _LinearXent(torch.autograd.Function):
+    """scale * sum_rows cross_entropy(x w^T + b, target) on lime_linear_xent_f32 (newsEncoders.py:375-393 behind :358-364).  The forward
+    launch already writes dlogits and dx; backward scales them by the incoming dloss, dW = dlogits^T x on the weight-gradient GEMM and
+    db as a column sum."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, target, scale):
+        loss, _, dlogits, dx = ops.linear_xent(x, w.contiguous(), b, target, scale)
+        ctx.has_bias = b is not None
+        ctx.save_for_backward(x, dlogits, dx)
+        return loss.squeeze_(0)           # 0-dim without being a view, as _NllSoftmax's
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, dlogits, dx = ctx.saved_tensors
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = dx * dloss
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            d = dlogits * dloss
+            if ctx.needs_input_grad[1]:
+                gw = ops.linear_wgrad(d, x, want_bias=want_b)
+                if want_b:
+                    gw, gb = gw
+            else:
+                gb = ops.colsum(d)
+        return gx, gw, gb, None, None
+
+
+def category_loss(enc, title_intent, category, alpha):
+    """The auxiliary loss of the CROWN content encoder ``enc`` for one encoder call (newsEncoders.py:358-364): alpha x the mean over the
+    rows of cross_entropy(category_predictor.fc(title_intent), one_hot(category)) -> a 0-dim tensor with autograd.  ``title_intent``
+    [M, intent_embedding_dim] may be a column slice; ``category`` int32 [M]."""
+    fc = enc.category_predictor.fc
+    return _LinearXent.apply(title_intent, fc.weight, fc.bias, category, float(alpha) / title_intent.shape[0])
+
+
 class _GateLN(torch.autograd.Function):
     """LayerNorm(g s x + (1 - g) x), g = sigmoid(s y + bias) (layers.py:84-89); y = W_g x comes from the caller's GEMM."""
 
@@ -1087,6 +1125,11 @@ def forward_train(model, user_category, user_subCategory, user_title_text, user_
                     i32(flat2(news_title_entity, user_title_entity)))
     cand = rep[:B * N].view(B, N, -1)
     hist = rep[B * N:].view(B, H, -1)
+    ne.auxiliary_loss = None
+    if trains_category_predictor(model):
+        # the title intent vector is the first intent_embedding_dim columns of the representation (_IntentFuse's title half, carried
+        # through crown_tail's concat untouched); the term is the history call's alone, padded slots (category 0) included
+        ne.auxiliary_loss = category_loss(ne, rep[B * N:, :ne.intent_embedding_dim], i32(user_category).reshape(-1).contiguous(), ne.alpha)
     return user_logits(model.user_encoder, model.remaining_lifetime_weighting, hist, cand, i32(news_category).contiguous(),
                        i32(news_subCategory).contiguous(), i32(user_category).contiguous(), i32(user_subCategory).contiguous(),
                        user_history_mask.contiguous(), remaining_lifetime.float().contiguous(),
@@ -1106,7 +1149,7 @@ class _NllSoftmax(torch.autograd.Function):
     def forward(ctx, logits):
         loss, d = ops.nll_softmax(logits.contiguous())
         ctx.save_for_backward(d)
-        return loss.view(())
+        return loss.squeeze_(0)           # 0-dim without being a view: the trainer's in-place ``loss += ...`` (trainer.py:139) is allowed
 
     @staticmethod
     def backward(ctx, dloss):
@@ -1120,11 +1163,24 @@ class _NllSoftmax(torch.autograd.Function):
 _DEAD = ('base_news_encoder.affine.', '.ISAB.', 'category_predictor.', 'user_encoder.affine.', 'candidate_aware_attn.value_proj.')
 
 
+def trains_category_predictor(model):
+    """True when the reference's trainer adds the category-prediction loss for this model (trainer.py:137-139): the news encoder is a
+    bare CROWN content encoder (no LIME wrapper: newsEncoders.py:100-103 copies ``auxiliary_loss`` once at construction, while it is
+    None, and never again, so under LIME the trainer reads None whatever ``alpha`` is) and ``config.alpha`` is not 0.  At ``alpha == 0``
+    the reference's term is an exact zero with exact-zero gradients -- Adam's moments of ``category_predictor.fc`` stay 0 and the
+    parameters never move (weight_decay is 0, config.py:47) -- so it is left out altogether: no launch, no attribute, the same bucket
+    and the same bits as a model without the option."""
+    from .newsEncoders import CROWN
+    ne = model.news_encoder
+    return isinstance(ne, CROWN) and not hasattr(ne, 'base_news_encoder') and float(ne.alpha) != 0.0
+
+
 def dead_parameters(model):
     """Names (as ``model.named_parameters()`` first yields them) of the trainable parameters the reference's backward leaves at None
     for this model.  One rule for every user encoder and every setting of the switches:
       * never used: the base encoder's ``affine``, ``candidate_aware_attn.value_proj`` and, where the content encoder has them,
-        ``ISAB`` and ``category_predictor``.
+        ``ISAB`` and ``category_predictor`` -- except that a bare CROWN news encoder with ``alpha != 0`` trains
+        ``category_predictor.fc`` through its category-prediction loss (``trains_category_predictor``).
       * ``user_encoder.affine``: only the MHSA user encoder applies it (userEncoders.py:487); CROWN constructs it and leaves it alone.
       * ``news_encoder.category_affine`` makes the topic vectors of the CROWN user encoder's candidate-aware attention
         (userEncoders.py:103-105) and nothing else: dead without that layer (``use_candidate_ware_clicked_news_attention`` off), and
@@ -1139,7 +1195,9 @@ def dead_parameters(model):
     plain = not hasattr(model.news_encoder, 'base_news_encoder')
     # prefixes of the names (LIME's ``category_affine``, not the content encoder's own ``base_news_encoder.category_affine``)
     enc = 'news_encoder.' if plain else 'news_encoder.base_news_encoder.'
-    dead = [enc + 'affine.', enc + 'ISAB.', enc + 'category_predictor.', 'user_encoder.candidate_aware_attn.value_proj.']
+    dead = [enc + 'affine.', enc + 'ISAB.', 'user_encoder.candidate_aware_attn.value_proj.']
+    if not trains_category_predictor(model):
+        dead.append(enc + 'category_predictor.')
     if not isinstance(ue, MHSA):
         dead.append('user_encoder.affine.')
     if not plain and not (isinstance(ue, CROWN) and caa is not None):
@@ -1160,6 +1218,11 @@ class TrainStep:
     """trainer.py:33 + :143-148 for one process (one GPU): Adam(lr, weight_decay) over the parameters that receive
     gradients, ``clip_grad_norm_(gradient_clip_norm)``, and -- under torch.distributed -- ONE all-reduce (RCCL over xGMI on
     ROCm) of the flat gradient bucket before the clip, averaging over ranks as DistributedDataParallel does.
+
+    The loss of ``step`` is the click loss plus, where the model has one, the category-prediction loss the forward left on
+    ``model.news_encoder.auxiliary_loss`` (trainer.py:137-139: a bare CROWN news encoder with ``alpha != 0``; None otherwise), and
+    ``category_predictor.fc`` is in the bucket exactly then.  Under several ranks each rank's term is the mean over its own rows, and
+    the gradient average below equals DistributedDataParallel's.
 
     Parameters are re-pointed into one flat fp32 buffer (``p.data`` becomes a view, values preserved) and their ``.grad``
     into a second one, so zeroing, the norm, the all-reduce and the Adam update are one launch each.
@@ -1295,9 +1358,13 @@ class TrainStep:
         return {n: ((named[n].data_ptr() - base) // 4, named[n].numel(), tuple(named[n].shape)) for n in self.names}
 
     def step(self, *batch):
-        """One training step on a batch in ``Model.forward``'s 26-tensor order; returns the (device) loss."""
+        """One training step on a batch in ``Model.forward``'s 26-tensor order; returns the (device) loss: the click loss plus the
+        category-prediction loss where the forward left one (the sum the reference's trainer prints)."""
         logits = self.model(*batch)
         loss = negative_log_softmax(logits)
+        aux = getattr(getattr(self.model, 'news_encoder', None), 'auxiliary_loss', None)
+        if aux is not None:
+            loss = loss + aux
         self.backward_and_update(loss)
         return loss.detach()
 

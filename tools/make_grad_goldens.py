@@ -57,6 +57,13 @@ def _reference_model(cfg):
     return model
 
 
+def training_loss(model, logits):
+    """The loss a case differentiates: the trainer's ``negative_log_softmax`` (trainer.py:71-73).  A tool whose cases train with more
+    than that swaps this function (tools/make_aux_goldens.py adds trainer.py:137-139's auxiliary loss); ``run_case`` and the guard's two
+    runs both go through it."""
+    return (-torch.log_softmax(logits, dim=1).select(dim=1, index=0)).mean()
+
+
 def reference_double_error(name):
     """How far the reference's fp32 gradients are from the reference's own fp64 gradients, by compare_grads' measure over every entry
     (|a - b| / max(|a|, rms(a), 1e-5), a the fp32 gradient): -> (parameter, worst).  What this reaches is not left for an implementation.
@@ -72,7 +79,7 @@ def reference_double_error(name):
             model = model.double()
             b = {k: (v.double() if v.is_floating_point() else v) for k, v in batch.items()}
         logits = model(*b.values())
-        (-torch.log_softmax(logits, dim=1).select(dim=1, index=0)).mean().backward()
+        training_loss(model, logits).backward()
         out, seen = {}, set()
         for k, p in model.named_parameters():
             if id(p) not in seen and p.grad is not None:
@@ -121,7 +128,7 @@ def run_case(name):
     keep = KEEP_SMALL if name in SMALL_CASES else KEEP
     model = _reference_model(cfg)
     logits = model(*batch.values())
-    loss = (-torch.log_softmax(logits, dim=1).select(dim=1, index=0)).mean()           # trainer.py:71-73
+    loss = training_loss(model, logits)
     loss.backward()
     out = {'loss': loss.detach().numpy(), 'logits': logits.detach().numpy()}
     with_grad, without = [], []
