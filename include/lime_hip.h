@@ -1316,7 +1316,21 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * order.  Slots behind the C-th hold position -1 and score -inf.  1 <= k <= 128, 1 <= C < 2^31, U <= 65535 (LIME_ERR_UNSUPPORTED
  * otherwise).  A row is split over workgroups of 4096 columns, their lists merged by one workgroup per row; the result is the k
  * largest of distinct integer keys and so independent of the split and the run.  workspace: lime_topk_rows_workspace(U, C) floats
- * (0 for C <= 4096: workspace may be NULL), 8-byte aligned. */
+ * (0 for C <= 4096: workspace may be NULL), 8-byte aligned.
+ *
+ * lime_topk_rows_quota_f32 (csrc/topk_quota_f32.hip): lime_topk_rows_f32 under a quota per group (Model.recommend(max_per_topic=)).
+ * Column j belongs to group keys[j] (int32 [C], shared by all rows).  Walk a row's entries in lime_topk_rows_f32's order; take an
+ * entry unless `quota` entries of its group were taken before it; stop at k.  positions / top_scores [U, k] hold the taken entries in
+ * that order (the input's bits), the slots behind the last taken one position -1 and score -inf.  drop: NULL, or uint8 [drop_rows, C]
+ * (contiguous): row r is masked by drop[r % drop_rows] -- the [S U, C] view of a schedule shares one [U, C] mask -- and an entry
+ * whose byte is not 0 takes no part: it uses no quota and is never returned.  An entry whose key is outside [0, n_keys) is dropped
+ * the same way; nothing outside the buffers is read.  Equivalently: the k best of the union, over the groups, of each group's `quota`
+ * best -- and a chunk of the row may be cut to the first 128 entries of its OWN walk before the merged set is walked again, so the
+ * passes are lime_topk_rows_f32's with a walk behind every sort, and the result does not depend on the split or the run.  Statuses
+ * before any launch: LIME_ERR_BAD_ARG for a NULL scores / keys / output, bad dims, quota < 1, n_keys < 1, a drop mask with
+ * drop_rows < 1, a short or misaligned workspace; LIME_ERR_UNSUPPORTED outside 1 <= k <= 128, C < 2^31, U <= 65535, n_keys <= 8192
+ * (lime_list_plan's table size).  workspace: lime_topk_rows_quota_workspace(U, C) floats (0 for C <= 4096: workspace may be NULL),
+ * 8-byte aligned; what it holds on entry does not matter. */
 int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
                            const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D, float scale,
                            float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
@@ -1346,6 +1360,10 @@ int lime_grouped_match_schedule_f32(const float* kp, const float* g, const float
 int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);
+int64_t lime_topk_rows_quota_workspace(int64_t U, int64_t C);
+int lime_topk_rows_quota_f32(const float* scores, int64_t ld, int64_t U, int64_t C, const int32_t* keys, int32_t n_keys, int32_t quota,
+                             const uint8_t* drop, int64_t drop_rows, int32_t k, int32_t* positions, float* top_scores, float* workspace,
+                             int64_t workspace_floats, void* stream);
 
 /* =====================================================================================================
  * Candidate lists (Model.score_lists / Model.recommend_lists): U users, each with its OWN list of candidates, as a CSR over P
@@ -1372,7 +1390,13 @@ int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, in
  * (LIME_ERR_UNSUPPORTED otherwise).  A segment longer than 4096 is split into chunks whose lists one workgroup merges; the grid is
  * U + P / 4096 chunks, which covers every split without reading the device, and the result -- the k largest of distinct integer
  * keys -- is independent of the split and the run.  Offsets are clamped into [0, P].  workspace: lime_topk_segments_workspace(U, P)
- * floats (never 0 for U >= 1), 8-byte aligned; what it holds on entry does not matter. */
+ * floats (never 0 for U >= 1), 8-byte aligned; what it holds on entry does not matter.
+ *
+ * lime_topk_segments_quota_f32 (csrc/topk_quota_f32.hip): lime_topk_rows_quota_f32's walk over the segments of a CSR
+ * (Model.recommend_lists(max_per_topic=)): keys int32 [P] and drop uint8 [P] (or NULL) lie beside scores, entry by entry; positions
+ * count WITHIN the segment.  Limits, grid rule and clamped offsets are lime_topk_segments_f32's, with quota >= 1 and 1 <= n_keys <=
+ * 8192 added as in the row form.  workspace: lime_topk_segments_quota_workspace(U, P) floats, 8-byte aligned; what it holds on entry
+ * does not matter. */
 int lime_list_plan_count(const int32_t* keys, const int64_t* offsets, int64_t U, int64_t P, int32_t T_all, int32_t* n_distinct,
                          void* stream);
 int lime_list_plan(const int32_t* keys, const int64_t* offsets, int64_t U, int64_t P, int32_t T_all, int32_t S, int64_t* order,
@@ -1380,6 +1404,10 @@ int lime_list_plan(const int32_t* keys, const int64_t* offsets, int64_t U, int64
 int64_t lime_topk_segments_workspace(int64_t U, int64_t P);
 int lime_topk_segments_f32(const float* scores, const int64_t* offsets, int64_t U, int64_t P, int32_t k, int32_t* positions,
                            float* top_scores, float* workspace, int64_t workspace_floats, void* stream);
+int64_t lime_topk_segments_quota_workspace(int64_t U, int64_t P);
+int lime_topk_segments_quota_f32(const float* scores, const int64_t* offsets, int64_t U, int64_t P, const int32_t* keys, int32_t n_keys,
+                                 int32_t quota, const uint8_t* drop, int32_t k, int32_t* positions, float* top_scores, float* workspace,
+                                 int64_t workspace_floats, void* stream);
 
 #ifdef __cplusplus
 }

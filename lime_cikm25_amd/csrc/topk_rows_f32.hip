@@ -36,8 +36,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     write_row(s, scores + row * ld, k, positions + row * k, top + row * k);
 }
 
-inline long chunks_of(long C) { return (C + TOPK_CHUNK - 1) / TOPK_CHUNK; }
-
 }  // namespace
 
 extern "C" int64_t lime_topk_rows_workspace(int64_t U, int64_t C) {

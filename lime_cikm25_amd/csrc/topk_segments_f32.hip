@@ -13,55 +13,9 @@
 
 namespace {
 
-constexpr int SCAN_THREADS = 256;
-
-struct seg_range {
-    long lo;
-    int n;
-};
-
-__device__ __forceinline__ seg_range segment_of(const long* __restrict__ offsets, long u, long P) {
-    long lo = offsets[u], hi = offsets[u + 1];
-    lo = lo < 0 ? 0 : (lo > P ? P : lo);
-    hi = hi < lo ? lo : (hi > P ? P : hi);
-    const long n = hi - lo;
-    return seg_range{lo, (int)(n > 0x7FFFFFFFL ? 0x7FFFFFFFL : n)};
-}
-
-__device__ __forceinline__ int chunks_in(int n) { return n <= TOPK_CHUNK ? 1 : (int)(((long)n + TOPK_CHUNK - 1) / TOPK_CHUNK); }
-
-// chunk_start[u], list_start[u] for u <= U: exclusive running sums of the segments' chunk counts and list counts
 __global__ __launch_bounds__(SCAN_THREADS) void topk_seg_scan_kernel(const long* __restrict__ offsets, long U, long P,
                                                                        int* __restrict__ chunk_start, int* __restrict__ list_start) {
-    __shared__ long part[2][SCAN_THREADS];                   // (chunks << 32 | lists) per thread: both sums stay below 2^31
-    const long per = (U + SCAN_THREADS - 1) / SCAN_THREADS;
-    const long u0 = per * threadIdx.x, u1 = u0 + per < U ? u0 + per : U;
-    long mine = 0;
-    for (long u = u0; u < u1; ++u) {
-        const int c = chunks_in(segment_of(offsets, u, P).n);
-        mine += ((long)c << 32) | (long)(c > 1 ? c : 0);
-    }
-    part[0][threadIdx.x] = mine;
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < SCAN_THREADS; d <<= 1) {             // inclusive scan over the threads' sums
-        const long v = part[cur][threadIdx.x] + (threadIdx.x >= d ? part[cur][threadIdx.x - d] : 0);
-        part[cur ^ 1][threadIdx.x] = v;
-        cur ^= 1;
-        __syncthreads();
-    }
-    long run = part[cur][threadIdx.x] - mine;
-    for (long u = u0; u < u1; ++u) {
-        chunk_start[u] = (int)(run >> 32);
-        list_start[u] = (int)(run & 0xFFFFFFFFL);
-        const int c = chunks_in(segment_of(offsets, u, P).n);
-        run += ((long)c << 32) | (long)(c > 1 ? c : 0);
-    }
-    if (threadIdx.x == SCAN_THREADS - 1) {
-        const long all = part[cur][threadIdx.x];
-        chunk_start[U] = (int)(all >> 32);
-        list_start[U] = (int)(all & 0xFFFFFFFFL);
-    }
+    seg_scan(offsets, U, P, chunk_start, list_start);
 }
 
 __global__ __launch_bounds__(256) void topk_seg_chunk_kernel(const float* __restrict__ scores, const long* __restrict__ offsets, long U,
@@ -71,13 +25,7 @@ __global__ __launch_bounds__(256) void topk_seg_chunk_kernel(const float* __rest
     __shared__ tkey s[TOPK_CHUNK];
     const int b = blockIdx.x;
     if (b >= chunk_start[U]) return;                         // (workgroup-uniform)
-    long lo = 0, hi = U;                                     // the segment u with chunk_start[u] <= b < chunk_start[u + 1]
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (chunk_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    const long u = lo;
+    const long u = segment_of_chunk(chunk_start, U, b);
     const seg_range seg = segment_of(offsets, u, P);
     const int c = b - chunk_start[u], n_chunk = chunks_in(seg.n);
     if (c < 0 || c >= n_chunk) return;                       // (offsets that decrease can break the sums: stay inside the segment)
@@ -110,14 +58,11 @@ __global__ __launch_bounds__(256) void topk_seg_merge_kernel(const float* __rest
     write_row(s, scores + segment_of(offsets, u, P).lo, k, positions + u * k, top + u * k);
 }
 
-inline int64_t head_floats(int64_t U) { return ((2 * (U + 1) + 1) / 2) * 2; }          // the two int32 [U + 1] sums, an even count
-inline int64_t list_slots(int64_t P) { return 2 * (P / TOPK_CHUNK); }
-
 }  // namespace
 
 extern "C" int64_t lime_topk_segments_workspace(int64_t U, int64_t P) {
     if (U <= 0 || P < 0) return 0;
-    return head_floats(U) + list_slots(P) * TOPK_MAX * 2;    // one 64-bit key = two floats
+    return seg_head_floats(U) + seg_list_slots(P) * TOPK_MAX * 2;    // one 64-bit key = two floats
 }
 
 extern "C" int lime_topk_segments_f32(const float* scores, const int64_t* offsets, int64_t U, int64_t P, int32_t k, int32_t* positions,
@@ -135,8 +80,8 @@ extern "C" int lime_topk_segments_f32(const float* scores, const int64_t* offset
     LIME_REQUIRE(((uintptr_t)workspace & 7) == 0, LIME_ERR_BAD_ARG, "lime_topk_segments_f32: workspace must be 8-byte aligned");
     int* chunk_start = reinterpret_cast<int*>(workspace);
     int* list_start = chunk_start + (U + 1);
-    tkey* lists = reinterpret_cast<tkey*>(workspace + head_floats(U));
-    const long list_cap = list_slots(P);
+    tkey* lists = reinterpret_cast<tkey*>(workspace + seg_head_floats(U));
+    const long list_cap = seg_list_slots(P);
     hipLaunchKernelGGL(topk_seg_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const long*)offsets, (long)U, (long)P,
                        chunk_start, list_start);
     int st = lime_check_launch("lime_topk_segments_f32");

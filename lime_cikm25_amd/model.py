@@ -1,6 +1,8 @@
 """Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE,KCNN}-{CROWN,ATT,MHSA} scoring path and the baselines without LIME,
 {CROWN,CNN,NAML,MHSA,KCNN}-{ATT,MHSA} and CROWN-CROWN (reference model.py:11-187)."""
+import collections
 import functools
+import numbers
 import os
 
 import torch
@@ -812,6 +814,24 @@ class Model(nn.Module):
             return out[0], gone
         return (out.repeat(S, 1, 1) if sets != S else out), gone
 
+    _TopicQuota = collections.namedtuple('_TopicQuota', 'q topic_of_news n_keys')
+
+    @staticmethod
+    def _topic_quota(corpus, max_per_topic, quota_by):
+        """The refusals of ``max_per_topic`` / ``quota_by`` (ValueError, before any launch) -> None without a quota, or (q, the corpus'
+        topic_of_news int32 [n_news] under ``quota_by`` -- device_data.topic_table_of --, its number of groups)."""
+        if max_per_topic is None:
+            return None
+        if isinstance(max_per_topic, bool) or not isinstance(max_per_topic, numbers.Integral) or max_per_topic < 1:
+            raise ValueError('max_per_topic must be an integer >= 1 (or None: no quota), got %r' % (max_per_topic,))
+        if quota_by not in ('category', 'topic'):
+            raise ValueError("quota_by must be 'category' or 'topic' (the (category, subCategory) pair), got %r" % (quota_by,))
+        from .device_data import topic_table_of
+        topic_of_news, cat_t, _ = topic_table_of(corpus, quota_by)
+        if cat_t.numel() > rec.MAX_TOPICS:
+            raise ValueError('the corpus has %d groups by %s, lime_topk_rows_quota_f32 counts up to %d' % (cat_t.numel(), quota_by, rec.MAX_TOPICS))
+        return Model._TopicQuota(int(max_per_topic), topic_of_news, cat_t.numel())
+
     @staticmethod
     def _in_history(n_news, hist_index, hist_mask, cidx):
         """bool [U, C]: candidate j sits in a masked-in slot of user u's history."""
@@ -824,14 +844,25 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                  cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+                  cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None, quota_by='category'):
         """The k best news of the pool per user, on the device: ``score_pool`` (same arguments), then lime_topk_rows_f32 ->
         (positions int32 [U, k] into ``cand_index``, scores fp32 [U, k]).  Rows are in descending order of the score; equal scores
         (+0.0 and -0.0 are equal) go lower position first; a NaN ranks after every number, in position order.  With
         ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is never returned; when fewer than k
-        candidates remain, the trailing slots hold position -1 and score -inf.  1 <= k <= 128."""
+        candidates remain, the trailing slots hold position -1 and score -inf.  1 <= k <= 128.
+
+        ``max_per_topic`` = q (an integer >= 1; None: no quota, today's launches and bits): at most q news of one group in a user's
+        row -- the candidates are walked in the order above and one is taken unless q of its group were taken before it, until k
+        are (lime_topk_rows_quota_f32; ``recommend.quota_topk`` states it on the host).  ``quota_by``: 'category', or 'topic' -- the
+        (category, subCategory) pair; it is independent of what the user side groups by (``grouped_by()``), so a model without
+        candidate-aware attention takes quotas too.  An excluded candidate uses no quota.  A corpus of more than 8192 groups is
+        refused (ValueError), as are a ``max_per_topic`` that is no integer >= 1 and an unknown ``quota_by``."""
+        quota = self._topic_quota(corpus, max_per_topic, quota_by)
         scores, gone = self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                                         cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
+        if quota is not None:                                  # the kernel drops the excluded: nothing to replace afterwards
+            return ops.topk_rows_quota(scores, quota.topic_of_news[cand_index.to(scores.device).long()], quota.q, int(k), drop=gone,
+                                       n_keys=quota.n_keys)
         positions, top = ops.topk_rows(scores, int(k))
         if gone is not None:
             gone = gone.gather(1, positions.clamp(min=0).long()) & (positions >= 0)
@@ -864,19 +895,28 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def recommend_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                           cand_lifetime, slot_offsets, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+                           cand_lifetime, slot_offsets, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None,
+                           quota_by='category'):
         """The k best news of the pool per user in every slot of a schedule: ``score_schedule`` (same arguments), then
         lime_topk_rows_f32 over the [S U, C] view of its scores (in chunks of slots that keep the kernel's 65535 rows) -> (positions
         int32 [S, U, k] into ``cand_index``, scores fp32 [S, U, k]); slot s holds what ``recommend`` returns at
-        ``cand_freshness + slot_offsets[s]``, in its order and with its -1 / -inf for excluded or missing slots.  1 <= k <= 128."""
+        ``cand_freshness + slot_offsets[s]``, in its order and with its -1 / -inf for excluded or missing slots.  1 <= k <= 128.
+        ``max_per_topic`` / ``quota_by``: as in ``recommend``, per (slot, user) row (lime_topk_rows_quota_f32 over the same view; the
+        [U, C] mask of ``exclude_history`` is handed over once, row s U + u reads its row u)."""
+        quota = self._topic_quota(corpus, max_per_topic, quota_by)
         scores, gone = self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                                         cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k,
                                         slot_offsets=torch.as_tensor(slot_offsets))
         S, U, C = scores.shape
         step = max(1, 65535 // max(U, 1))
-        found = [ops.topk_rows(scores[s0:s0 + step].view(-1, C), int(k)) for s0 in range(0, S, step)]
+        if quota is not None:
+            keys = quota.topic_of_news[cand_index.to(scores.device).long()]
+            found = [ops.topk_rows_quota(scores[s0:s0 + step].view(-1, C), keys, quota.q, int(k), drop=gone, n_keys=quota.n_keys)
+                     for s0 in range(0, S, step)]
+        else:
+            found = [ops.topk_rows(scores[s0:s0 + step].view(-1, C), int(k)) for s0 in range(0, S, step)]
         positions, top = (torch.cat([f[i] for f in found]).view(S, U, int(k)) for i in (0, 1))
-        if gone is not None:
+        if gone is not None and quota is None:
             gone = gone.unsqueeze(0).expand(S, U, C).gather(2, positions.clamp(min=0).long()) & (positions >= 0)
             positions = torch.where(gone, torch.full_like(positions, -1), positions)
         return positions, top
@@ -977,18 +1017,24 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
-                        cand_freshness, cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
+                        cand_freshness, cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None,
+                        quota_by='category'):
         """The k best news of every user's OWN list, on the device: ``score_lists`` (same arguments), then lime_topk_segments_f32 ->
         (positions int32 [U, k] into the user's list -- candidate ``cand_index[cand_offsets[u] + positions[u, j]]`` --, scores fp32
         [U, k]) in ``recommend``'s order.  With ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is
         never returned; the trailing slots of a list with fewer than k candidates left (all k of an empty list) hold position -1 and
-        score -inf.  1 <= k <= 128."""
+        score -inf.  1 <= k <= 128.
+        ``max_per_topic`` / ``quota_by``: as in ``recommend``, per list (lime_topk_segments_quota_f32)."""
+        quota = self._topic_quota(corpus, max_per_topic, quota_by)
         scores, offsets, gone = self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
                                                   cand_index, cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
         U, k = hist_index.shape[0], int(k)
         if scores.numel() == 0:
             return (torch.full((U, k), -1, dtype=torch.int32, device=scores.device),
                     torch.full((U, k), float('-inf'), dtype=torch.float32, device=scores.device))
+        if quota is not None:
+            return ops.topk_segments_quota(scores, offsets, quota.topic_of_news[cand_index.to(scores.device).long()], quota.q, k, drop=gone,
+                                           n_keys=quota.n_keys)
         positions, top = ops.topk_segments(scores, offsets, k)
         if gone is not None:
             at = (offsets[:-1].unsqueeze(1) + positions.clamp(min=0).long()).clamp(max=scores.numel() - 1)

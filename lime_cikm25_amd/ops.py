@@ -1173,6 +1173,56 @@ def topk_segments(scores, offsets, k):
     return positions, top
 
 
+def topk_rows_quota(scores, keys, quota, k, drop=None, n_keys=8192):
+    """``lime_topk_rows_quota_f32``: ``topk_rows`` with at most ``quota`` entries of one group per row (``recommend.quota_topk`` on
+    the device, bit for bit).  keys int32 [C] (device): column j belongs to group keys[j], 0 <= key < ``n_keys`` <= 8192 (a key
+    outside drops the column); drop: None or bool / uint8 [R, C] (device, contiguous), row u masked by drop[u % R]: a set entry takes
+    no part -> (positions int32 [U, k], scores fp32 [U, k]) in walk order, -1 / -inf behind the last taken entry.  1 <= k <= 128."""
+    lib = _lib.load()
+    _mat(scores, 'scores')
+    U, C = scores.shape
+    k, quota = int(k), int(quota)
+    if k < 1 or C < 1 or quota < 1:
+        raise ValueError('topk_rows_quota needs k >= 1, quota >= 1 and at least one column, got k = %d, quota = %d, C = %d' % (k, quota, C))
+    _vec(keys, 'keys', C, dtype=torch.int32)
+    rows = 0
+    if drop is not None:
+        if drop.dim() != 2 or drop.shape[1] != C or drop.shape[0] < 1:
+            raise ValueError('drop must be [R, C] = [R, %d] with R >= 1, got %s' % (C, tuple(drop.shape)))
+        rows = drop.shape[0]
+        drop = _mask_u8(drop.reshape(-1), 'drop')
+    positions = torch.empty((U, k), dtype=torch.int32, device=scores.device)
+    top = torch.empty((U, k), dtype=torch.float32, device=scores.device)
+    need = int(lib.lime_topk_rows_quota_workspace(U, C))
+    ws = _workspace(scores.device, need) if need else None
+    check(lib.lime_topk_rows_quota_f32(_p(scores), _ld(scores), U, C, _p(keys), int(n_keys), quota, _p(drop), rows, k, _p(positions), _p(top),
+                                       _p(ws), need, _stream()), 'lime_topk_rows_quota_f32')
+    return positions, top
+
+
+def topk_segments_quota(scores, offsets, keys, quota, k, drop=None, n_keys=8192):
+    """``lime_topk_segments_quota_f32``: ``topk_segments`` with at most ``quota`` entries of one group per segment
+    (``recommend.quota_topk_segments`` on the device, bit for bit).  keys int32 [P] and drop (None or bool / uint8 [P]) lie beside
+    scores [P] -> (positions int32 [U, k] WITHIN the segment, scores fp32 [U, k]).  1 <= k <= 128."""
+    lib = _lib.load()
+    _vec(scores, 'scores')
+    _vec(offsets, 'offsets', dtype=torch.int64)
+    U, P, k, quota = offsets.numel() - 1, scores.numel(), int(k), int(quota)
+    if U < 0 or not 1 <= k <= 128 or quota < 1:
+        raise ValueError('topk_segments_quota needs 1 <= k <= 128, quota >= 1 and U + 1 >= 1 offsets, got k = %d, quota = %d, %d offsets'
+                         % (k, quota, U + 1))
+    _vec(keys, 'keys', P, dtype=torch.int32)
+    if drop is not None:
+        drop = _vec(_mask_u8(drop, 'drop'), 'drop', P, dtype=torch.uint8)
+    positions = torch.empty((U, k), dtype=torch.int32, device=scores.device)
+    top = torch.empty((U, k), dtype=torch.float32, device=scores.device)
+    need = int(lib.lime_topk_segments_quota_workspace(U, P))
+    ws = _workspace(scores.device, need) if need else None
+    check(lib.lime_topk_segments_quota_f32(_p(scores), _p(offsets), U, P, _p(keys), int(n_keys), quota, _p(drop), k, _p(positions), _p(top),
+                                           _p(ws), ws.numel() if need else 0, _stream()), 'lime_topk_segments_quota_f32')
+    return positions, top
+
+
 def row_scale(x, scale):
     lib = _lib.load()
     D = x.shape[-1]

@@ -174,3 +174,70 @@ def list_passes(offsets, n_distinct, H, pairs_per_pass):
         passes.append((u0, u1, S))
         u0 = u1
     return passes
+
+
+# ---- topic quotas (Model.recommend* with max_per_topic): at most `quota` entries of one group among the k --------------------------------
+def walk_order(scores):
+    """The positions of a row of scores in ``recommend``'s order: descending score; +0.0 == -0.0; equal scores lower position first;
+    a NaN behind every number, NaNs in position order."""
+    row = np.asarray(scores, dtype=np.float32).reshape(-1)
+    nan = np.isnan(row)
+    value = np.where(nan, 0.0, row).astype(np.float64) + 0.0                 # -0.0 + 0.0 = +0.0: the zeros tie
+    order = np.argsort(-value, kind='stable')
+    return order[np.argsort(nan[order], kind='stable')]
+
+
+def quota_topk(scores, keys, k, quota, drop=None):
+    """The host statement of ``ops.topk_rows_quota`` (lime_topk_rows_quota_f32) -> (positions int32 [U, k], scores fp32 [U, k]).
+
+    ``scores`` [U, C]; ``keys`` int [C]: column j belongs to group keys[j]; ``drop``: None or bool / uint8 [R, C], row u masked by
+    drop[u % R].  Per row: walk the columns in ``walk_order``; take a column unless ``quota`` columns of its group were taken before
+    it; stop at k.  A dropped column -- its drop entry set, or its key negative -- takes no part.  The outputs hold the taken
+    columns in that order and their scores (the input's bits); the slots behind the last one hold -1 / -inf.
+    Stated through the first of the two facts that the kernel rests on -- the result is the k best of the union, over the groups, of
+    each group's ``quota`` best --: rank every column within its group, keep the ranks below ``quota``, cut at k."""
+    scores = np.asarray(scores, dtype=np.float32)
+    if scores.ndim != 2:
+        raise ValueError('scores must be [U, C], got %s' % (scores.shape,))
+    U, C = scores.shape
+    keys = np.asarray(keys).reshape(-1).astype(np.int64)
+    k, quota = int(k), int(quota)
+    if keys.shape[0] != C or k < 1 or quota < 1:
+        raise ValueError('quota_topk needs C = %d keys, k >= 1 and quota >= 1, got %d keys, k = %d, quota = %d' % (C, keys.shape[0], k, quota))
+    if drop is not None:
+        drop = np.asarray(drop).astype(bool).reshape(-1, C)
+    pos = np.full((U, k), -1, dtype=np.int32)
+    top = np.full((U, k), -np.inf, dtype=np.float32)
+    for u in range(U):
+        order = walk_order(scores[u])
+        live = keys[order] >= 0
+        if drop is not None:
+            live &= ~drop[u % drop.shape[0]][order]
+        order = order[live]
+        g = keys[order]
+        by_group = np.argsort(g, kind='stable')                               # groups together, each in walk order
+        gs = g[by_group]
+        head = np.flatnonzero(np.r_[True, gs[1:] != gs[:-1]]) if gs.size else np.zeros(0, dtype=np.int64)
+        rank = np.empty(gs.size, dtype=np.int64)
+        rank[by_group] = np.arange(gs.size) - np.repeat(head, np.diff(np.r_[head, gs.size]))
+        taken = order[rank < quota][:k]
+        pos[u, :taken.size] = taken
+        top[u, :taken.size] = scores[u, taken]
+    return pos, top
+
+
+def quota_topk_segments(scores, offsets, keys, k, quota, drop=None):
+    """``quota_topk`` over the segments of a CSR: the host statement of ``ops.topk_segments_quota`` (lime_topk_segments_quota_f32).
+    ``scores`` [P], ``offsets`` int64 [U + 1], ``keys`` int [P], ``drop`` None or [P]; positions count WITHIN the segment."""
+    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
+    off = np.asarray(offsets).reshape(-1).astype(np.int64)
+    keys = np.asarray(keys).reshape(-1)
+    U, k = off.shape[0] - 1, int(k)
+    pos = np.full((U, k), -1, dtype=np.int32)
+    top = np.full((U, k), -np.inf, dtype=np.float32)
+    drop = None if drop is None else np.asarray(drop).reshape(-1)
+    for u in range(U):
+        a, b = off[u], off[u + 1]
+        if b > a:
+            pos[u], top[u] = (r[0] for r in quota_topk(scores[None, a:b], keys[a:b], k, quota, None if drop is None else drop[None, a:b]))
+    return pos, top
