@@ -98,24 +98,13 @@ int grouped_match_launch(const char* who, int form, const float* kp, const float
     LIME_REQUIRE(kp && g && qp && cand && offsets && logits && (!indexed || index) && (!composed || (qt && ct && occ)), LIME_ERR_BAD_ARG,
                  "%s: NULL pointer", who);
     LIME_REQUIRE(!use_weight || remaining, LIME_ERR_BAD_ARG, "%s: remaining is NULL", who);
-    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && D > 0 && n >= 0 && n_occ >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
-    LIME_REQUIRE(H <= 128 && A <= 2048 && D <= 2048 && A % 4 == 0 && D % 4 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL &&
-                     n_occ <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
-                 "%s: H %d, A %d, D %d outside 1 <= H <= 128, A and D multiples of 4 up to 2048 (or %lld groups / %lld, %lld table rows >= 2^31)",
-                 who, H, A, D, (long long)G, (long long)n, (long long)n_occ);
-    LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qp, A) && lime_al16(g, D) && lime_al16(cand, D) &&
-                     (!composed || (lime_al16(qt, A) && lime_al16(ct, D))), LIME_ERR_BAD_ARG,
-                 "%s: kp, qp, g and cand (and the occurrence tables) must be 16-byte aligned", who);
-    LIME_REQUIRE(!indexed || n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
-    LIME_REQUIRE(!composed || n_occ > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty occurrence table", who, (long long)P);
+    const bool aligned = lime_al16(kp, A) && lime_al16(qp, A) && lime_al16(g, D) && lime_al16(cand, D) &&
+                         (!composed || (lime_al16(qt, A) && lime_al16(ct, D)));
+    if (const int bad = gm_check_shared(who, G, P, H, A, D, "D", 4, "A and D multiples of 4", aligned,
+                                        "kp, qp, g and cand (and the occurrence tables) must be 16-byte aligned", indexed, n, composed, n_occ))
+        return bad;
     if (G == 0 || P == 0) return LIME_OK;
-    // tile slices per group: enough workgroups to fill the chip when the groups are few (one group per user with the candidate-aware
-    // attention off), never more than the tiles the pairs can make.  The split changes which workgroup takes a tile, not its bits.
-    const long all_tiles = (P + GM_PAIRS - 1) / GM_PAIRS;
-    long slices = (8L * lime_num_cus() + G - 1) / G;
-    slices = slices > all_tiles ? all_tiles : slices;
-    slices = slices < 1 ? 1 : (slices > 65535 ? 65535 : slices);
-    const dim3 grid((unsigned)G, (unsigned)slices);
+    const dim3 grid((unsigned)G, (unsigned)gm_tile_slices(G, P));
 #define LIME_GM_LAUNCH(T_, I_)                                                                                                          \
     hipLaunchKernelGGL((grouped_match_kernel<T_, I_>), grid, dim3(256), 0, (hipStream_t)stream, kp, g, qp, cand, remaining,             \
                        (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, D, scale, alpha_s, beta_s, use_weight,   \
@@ -124,17 +113,9 @@ int grouped_match_launch(const char* who, int form, const float* kp, const float
     hipLaunchKernelGGL((grouped_match_kernel<T_, I_, GmOccurrence>), grid, dim3(256), 0, (hipStream_t)stream, kp, g, qp, cand,          \
                        remaining, (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, D, scale, alpha_s, beta_s,    \
                        use_weight, use_penalty, GmOccurrence{qt, ct, (const int*)occ, (int)n_occ})
-#define LIME_GM_PICK(L_, I_)                                                                                                            \
-    do {                                                                                                                                \
-        if (H <= 16) L_(1, I_);                                                                                                         \
-        else if (H <= 32) L_(2, I_);                                                                                                    \
-        else if (H <= 64) L_(4, I_);                                                                                                    \
-        else L_(8, I_);                                                                                                                 \
-    } while (0)
-    if (composed) LIME_GM_PICK(LIME_GM_LAUNCH_OCC, true);
-    else if (indexed) LIME_GM_PICK(LIME_GM_LAUNCH, true);
-    else LIME_GM_PICK(LIME_GM_LAUNCH, false);
-#undef LIME_GM_PICK
+    if (composed) LIME_GM_PICK(H, LIME_GM_LAUNCH_OCC, true);
+    else if (indexed) LIME_GM_PICK(H, LIME_GM_LAUNCH, true);
+    else LIME_GM_PICK(H, LIME_GM_LAUNCH, false);
 #undef LIME_GM_LAUNCH_OCC
 #undef LIME_GM_LAUNCH
     return lime_check_launch(who);

@@ -120,24 +120,19 @@ extern "C" int lime_grouped_match_schedule_f32(const float* kp, const float* g, 
                                                int32_t use_weight, int32_t use_penalty, void* stream) {
     const char* who = "lime_grouped_match_schedule_f32";
     const bool tables = qt || ct;
-    // the twin's checks in the twin's order (lime_grouped_match_occurrence_f32; the occurrence tables are optional here) ...
+    // the checks of the occurrence form (lime_grouped_match_occurrence_f32; the occurrence tables are optional here) ...
     LIME_REQUIRE(kp && g && qa && ca && offsets && logits && index, LIME_ERR_BAD_ARG, "%s: NULL pointer", who);
     LIME_REQUIRE(!use_weight || remaining, LIME_ERR_BAD_ARG, "%s: remaining is NULL", who);
-    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && D > 0 && n >= 0 && n_occ >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
-    LIME_REQUIRE(H <= 128 && A <= 2048 && D <= 2048 && A % 4 == 0 && D % 4 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL &&
-                     n_occ <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
-                 "%s: H %d, A %d, D %d outside 1 <= H <= 128, A and D multiples of 4 up to 2048 (or %lld groups / %lld, %lld table rows >= 2^31)",
-                 who, H, A, D, (long long)G, (long long)n, (long long)n_occ);
-    LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qa, A) && lime_al16(g, D) && lime_al16(ca, D) && lime_al16(qt, A) && lime_al16(ct, D),
-                 LIME_ERR_BAD_ARG, "%s: kp, qa, g and ca (and the occurrence tables) must be 16-byte aligned", who);
-    LIME_REQUIRE(n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
-    LIME_REQUIRE(!tables || n_occ > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty occurrence table", who, (long long)P);
+    const bool aligned = lime_al16(kp, A) && lime_al16(qa, A) && lime_al16(g, D) && lime_al16(ca, D) && lime_al16(qt, A) && lime_al16(ct, D);
+    if (const int bad = gm_check_shared(who, G, P, H, A, D, "D", 4, "A and D multiples of 4", aligned,
+                                        "kp, qa, g and ca (and the occurrence tables) must be 16-byte aligned", true, n, tables, n_occ))
+        return bad;
     // ... then the schedule's own
     LIME_REQUIRE(S >= 1, LIME_ERR_BAD_ARG, "%s: S = %d slots, at least one is needed", who, S);
     LIME_REQUIRE(!tables || occ, LIME_ERR_BAD_ARG, "%s: occurrence tables without occ", who);
     LIME_REQUIRE((qt != nullptr) == (ct != nullptr) && (tables || n_occ == 0), LIME_ERR_BAD_ARG,
                  "%s: qt and ct come together, and n_occ = %lld rows need them", who, (long long)n_occ);
-    const int T = H <= 16 ? 1 : H <= 32 ? 2 : H <= 64 ? 4 : 8;
+    const int T = gm_history_tiles(H);
     const long lds = gms_lds_bytes(T, H, tables ? n_occ : 0);
     LIME_REQUIRE(lds <= GMS_LDS_MAX, LIME_ERR_UNSUPPORTED,
                  "%s: %lld occurrences x H %d take %ld bytes of LDS (2048 T + 8 n_occ Hs, T = %d, Hs = H rounded up to 4), the limit is %ld",
@@ -146,30 +141,20 @@ extern "C" int lime_grouped_match_schedule_f32(const float* kp, const float* g, 
     // tile slices per group as in lime_grouped_match_f32 -- enough workgroups to fill the chip when the groups are few --, but every
     // workgroup forms its group's tables first (2 ceil(n_occ / 64) tile products), so a slice keeps at least as many tiles of its own
     // where the groups have them.  The split changes which workgroup takes a tile, not its bits.
-    const long all_tiles = (P + GM_PAIRS - 1) / GM_PAIRS;
-    long slices = (8L * lime_num_cus() + G - 1) / G;
-    slices = slices > all_tiles ? all_tiles : slices;
+    long slices = gm_tile_slices(G, P);
     if (tables) {
+        const long all_tiles = (P + GM_PAIRS - 1) / GM_PAIRS;
         const long per_group = (all_tiles + G - 1) / G, table_tiles = (n_occ + GM_PAIRS - 1) / GM_PAIRS;
         const long cap = per_group / table_tiles;
-        slices = slices > cap ? cap : slices;
+        if (slices > cap) slices = cap < 1 ? 1 : cap;
     }
-    slices = slices < 1 ? 1 : (slices > 65535 ? 65535 : slices);
     const dim3 grid((unsigned)G, (unsigned)slices);
 #define LIME_GMS_LAUNCH(T_, O_)                                                                                                         \
     hipLaunchKernelGGL((grouped_match_schedule_kernel<T_, O_>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, kp, g, qa, ca, qt,   \
                        ct, remaining, (const long*)offsets, (const int*)index, (int)n, (const int*)occ, (int)(tables ? n_occ : 0),      \
                        logits, (long)P, S, H, A, D, scale, alpha_s, beta_s, use_weight, use_penalty)
-#define LIME_GMS_PICK(O_)                                                                                                               \
-    do {                                                                                                                                \
-        if (T == 1) LIME_GMS_LAUNCH(1, O_);                                                                                             \
-        else if (T == 2) LIME_GMS_LAUNCH(2, O_);                                                                                        \
-        else if (T == 4) LIME_GMS_LAUNCH(4, O_);                                                                                        \
-        else LIME_GMS_LAUNCH(8, O_);                                                                                                    \
-    } while (0)
-    if (tables) LIME_GMS_PICK(true);
-    else LIME_GMS_PICK(false);
-#undef LIME_GMS_PICK
+    if (tables) LIME_GM_PICK(H, LIME_GMS_LAUNCH, true);
+    else LIME_GM_PICK(H, LIME_GMS_LAUNCH, false);
 #undef LIME_GMS_LAUNCH
     return lime_check_launch(who);
 }

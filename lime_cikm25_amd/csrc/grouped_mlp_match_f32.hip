@@ -142,23 +142,14 @@ int grouped_mlp_match_launch(const char* who, int form, const float* kp, const f
     const bool indexed = form != GM_PLAIN, composed = form == GM_OCCURRENCE;
     LIME_REQUIRE(kp && gu && qp && nw && w_out && offsets && logits && (!indexed || index) && (!composed || (qt && nt && occ)),
                  LIME_ERR_BAD_ARG, "%s: NULL pointer", who);
-    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && Dh > 0 && n >= 0 && n_occ >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
-    LIME_REQUIRE(H <= 128 && A <= 2048 && Dh <= 2048 && A % 4 == 0 && Dh % 2 == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL &&
-                     n_occ <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
-                 "%s: H %d, A %d, Dh %d outside 1 <= H <= 128, A a multiple of 4 and Dh even, both up to 2048 (or %lld groups / %lld, %lld "
-                 "table rows >= 2^31)", who, H, A, Dh, (long long)G, (long long)n, (long long)n_occ);
-    LIME_REQUIRE(lime_al16(kp, A) && lime_al16(qp, A) && (uintptr_t)gu % 8 == 0 && (uintptr_t)nw % 8 == 0 && (uintptr_t)w_out % 4 == 0 &&
-                     (uintptr_t)b_out % 4 == 0 && (!composed || (lime_al16(qt, A) && (uintptr_t)nt % 8 == 0)), LIME_ERR_BAD_ARG,
-                 "%s: kp and qp (and qt) must be 16-byte aligned, gu and nw (and nt) 8-byte aligned", who);
-    LIME_REQUIRE(!indexed || n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
-    LIME_REQUIRE(!composed || n_occ > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty occurrence table", who, (long long)P);
+    const bool aligned = lime_al16(kp, A) && lime_al16(qp, A) && (uintptr_t)gu % 8 == 0 && (uintptr_t)nw % 8 == 0 &&
+                         (uintptr_t)w_out % 4 == 0 && (uintptr_t)b_out % 4 == 0 && (!composed || (lime_al16(qt, A) && (uintptr_t)nt % 8 == 0));
+    if (const int bad = gm_check_shared(who, G, P, H, A, Dh, "Dh", 2, "A a multiple of 4 and Dh even, both", aligned,
+                                        "kp and qp (and qt) must be 16-byte aligned, gu and nw (and nt) 8-byte aligned", indexed, n, composed,
+                                        n_occ))
+        return bad;
     if (G == 0 || P == 0) return LIME_OK;
-    // tile slices per group, as in lime_grouped_match_f32: the split changes which workgroup takes a tile, not its bits
-    const long all_tiles = (P + GM_PAIRS - 1) / GM_PAIRS;
-    long slices = (8L * lime_num_cus() + G - 1) / G;
-    slices = slices > all_tiles ? all_tiles : slices;
-    slices = slices < 1 ? 1 : (slices > 65535 ? 65535 : slices);
-    const dim3 grid((unsigned)G, (unsigned)slices);
+    const dim3 grid((unsigned)G, (unsigned)gm_tile_slices(G, P));
 #define LIME_GMM_LAUNCH(T_, I_)                                                                                                         \
     hipLaunchKernelGGL((grouped_mlp_match_kernel<T_, I_>), grid, dim3(256), 0, (hipStream_t)stream, kp, gu, qp, nw, w_out, b_out,       \
                        (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, Dh, scale)
@@ -166,17 +157,9 @@ int grouped_mlp_match_launch(const char* who, int form, const float* kp, const f
     hipLaunchKernelGGL((grouped_mlp_match_kernel<T_, I_, GmOccurrence>), grid, dim3(256), 0, (hipStream_t)stream, kp, gu, qp, nw,       \
                        w_out, b_out, (const long*)offsets, (const int*)index, (int)n, logits, (long)P, H, A, Dh, scale,                 \
                        GmOccurrence{qt, nt, (const int*)occ, (int)n_occ})
-#define LIME_GMM_PICK(L_, I_)                                                                                                           \
-    do {                                                                                                                                \
-        if (H <= 16) L_(1, I_);                                                                                                         \
-        else if (H <= 32) L_(2, I_);                                                                                                    \
-        else if (H <= 64) L_(4, I_);                                                                                                    \
-        else L_(8, I_);                                                                                                                 \
-    } while (0)
-    if (composed) LIME_GMM_PICK(LIME_GMM_LAUNCH_OCC, true);
-    else if (indexed) LIME_GMM_PICK(LIME_GMM_LAUNCH, true);
-    else LIME_GMM_PICK(LIME_GMM_LAUNCH, false);
-#undef LIME_GMM_PICK
+    if (composed) LIME_GM_PICK(H, LIME_GMM_LAUNCH_OCC, true);
+    else if (indexed) LIME_GM_PICK(H, LIME_GMM_LAUNCH, true);
+    else LIME_GM_PICK(H, LIME_GMM_LAUNCH, false);
 #undef LIME_GMM_LAUNCH_OCC
 #undef LIME_GMM_LAUNCH
     return lime_check_launch(who);

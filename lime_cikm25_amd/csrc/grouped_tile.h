@@ -1,6 +1,7 @@
 // What the grouped matches share (grouped_match_f32.hip, grouped_mlp_match_f32.hip): the [16 T x 16] tile product of a group's shared
 // rows with a wave's 16 pairs, and the softmax over the history on its result.  One copy: both kernels' first product and softmax are
-// the same instructions, so a pair's attention weights are the same bits in both.
+// the same instructions, so a pair's attention weights are the same bits in both.  Below the device code, the host half: the H -> T
+// choice, the tile-slice rule and the argument checks that the launchers of those two units and of grouped_match_schedule_f32.hip share.
 #pragma once
 #include "dev_helpers.h"
 
@@ -136,3 +137,47 @@ __device__ __forceinline__ float gm_tile_softmax(f32x4 (&s)[T], int H, float sca
 }
 
 }  // namespace lime_dev
+
+// ---- host side: what the launchers of grouped_match_f32.hip, grouped_mlp_match_f32.hip and grouped_match_schedule_f32.hip share ----
+
+// The kernels' T: the 16-row tiles that hold a history of H <= 128 rows.
+static inline int gm_history_tiles(int H) { return H <= 16 ? 1 : H <= 32 ? 2 : H <= 64 ? 4 : 8; }
+
+// L_(T, ...) with the T of a history of H_ rows as a literal, for a launch macro L_ that names a kernel instantiation.
+#define LIME_GM_PICK(H_, L_, ...)                                                                                                       \
+    do {                                                                                                                                \
+        switch (gm_history_tiles(H_)) {                                                                                                 \
+            case 1: L_(1, __VA_ARGS__); break;                                                                                          \
+            case 2: L_(2, __VA_ARGS__); break;                                                                                          \
+            case 4: L_(4, __VA_ARGS__); break;                                                                                          \
+            default: L_(8, __VA_ARGS__);                                                                                                \
+        }                                                                                                                               \
+    } while (0)
+
+// Tile slices per group (gridDim.y) for G >= 1 groups over P >= 1 pairs: enough workgroups to fill the chip when the groups are few
+// (one group per user with the candidate-aware attention off), never more than the tiles the pairs can make.  The split changes which
+// workgroup takes a tile, not its bits.
+static inline long gm_tile_slices(int64_t G, int64_t P) {
+    const long all_tiles = (P + lime_dev::GM_PAIRS - 1) / lime_dev::GM_PAIRS;
+    long slices = (8L * lime_num_cus() + G - 1) / G;
+    slices = slices > all_tiles ? all_tiles : slices;
+    return slices < 1 ? 1 : (slices > 65535 ? 65535 : slices);
+}
+
+// The checks the three launchers share, in their order, behind the unit's own NULL checks: the dimensions, their bounds and the
+// 2^31 bounds of G / n / n_occ, the unit's alignment rule (``aligned``: whether it holds, ``align_rule``: its words), the empty tables.
+// The second operand is W columns wide, a multiple of ``w_mult``, and the unit calls it ``w_name``; ``widths``: its words for the
+// two widths' rule.  indexed / composed: whether the pairs read a table of n rows / an occurrence table of n_occ rows.
+static inline int gm_check_shared(const char* who, int64_t G, int64_t P, int32_t H, int32_t A, int32_t W, const char* w_name, int w_mult,
+                                  const char* widths, bool aligned, const char* align_rule, bool indexed, int64_t n, bool composed,
+                                  int64_t n_occ) {
+    LIME_REQUIRE(G >= 0 && P >= 0 && H > 0 && A > 0 && W > 0 && n >= 0 && n_occ >= 0, LIME_ERR_BAD_ARG, "%s: bad dims", who);
+    LIME_REQUIRE(H <= 128 && A <= 2048 && W <= 2048 && A % 4 == 0 && W % w_mult == 0 && G < 0x7FFFFFFFL && n <= 0x7FFFFFFFL &&
+                     n_occ <= 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED,
+                 "%s: H %d, A %d, %s %d outside 1 <= H <= 128, %s up to 2048 (or %lld groups / %lld, %lld table rows >= 2^31)", who, H, A,
+                 w_name, W, widths, (long long)G, (long long)n, (long long)n_occ);
+    LIME_REQUIRE(aligned, LIME_ERR_BAD_ARG, "%s: %s", who, align_rule);
+    LIME_REQUIRE(!indexed || n > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty table", who, (long long)P);
+    LIME_REQUIRE(!composed || n_occ > 0 || P == 0, LIME_ERR_BAD_ARG, "%s: %lld pairs index an empty occurrence table", who, (long long)P);
+    return LIME_OK;
+}

@@ -1,14 +1,12 @@
 """Drop-in ``Model`` for the LIME-{CROWN,CNN,NAML,MHSA,CNE,KCNN}-{CROWN,ATT,MHSA} scoring path and the baselines without LIME,
 {CROWN,CNN,NAML,MHSA,KCNN}-{ATT,MHSA} and CROWN-CROWN (reference model.py:11-187)."""
-import collections
 import functools
-import numbers
 import os
 
 import torch
 import torch.nn as nn
 
-from . import newsEncoders, ops, recommend as rec, training, userEncoders
+from . import newsEncoders, ops, serving, training, userEncoders
 from .util import RemainingLifetimeWeighting
 
 # positions (in the 26-tensor signature, model.py:151-154) of the inputs the scoring path reads; the others
@@ -447,32 +445,6 @@ class Model(nn.Module):
         crown = hasattr(self.user_encoder, 'user_node_embedding')
         return None if not self.user_encoder.use_candidate_aware_attn else 'topic' if crown else 'category'
 
-    def _check_grouped(self, news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index, check_candidates,
-                       pairs_per_pass, k, top_k):
-        """The host-side refusals (ValueError, before any launch) that the pool and the lists share, in their order -> (U, H, what
-        ``check_candidates`` returned).  The form's own stand in between: ``bad_index``: its words when cand_index is not shaped as it
-        wants, or None; ``check_candidates(U)`` raises over its other candidate arguments; ``top_k``: (its recommend entry, its kernel)."""
-        if self.reads_content_mask:
-            raise ValueError(self._NO_CONTENT_CACHE)
-        if news_cache.dim() != 2 or news_cache.shape[1] == 0:
-            raise ValueError('news_cache must be the [n_news, width] tensor of build_news_cache, got %s' % (tuple(news_cache.shape),))
-        if hist_index.dim() != 2:
-            raise ValueError('hist_index must be [U, H], got %s' % (tuple(hist_index.shape),))
-        U, H = hist_index.shape
-        for t, name in ((hist_mask, 'hist_mask'), (user_freshness, 'user_freshness'), (user_lifetime, 'user_lifetime')):
-            if tuple(t.shape) != (U, H):
-                raise ValueError('%s must be [U, H] = [%d, %d] like hist_index, got %s' % (name, U, H, tuple(t.shape)))
-        if bad_index:
-            raise ValueError('%s got %s' % (bad_index, tuple(cand_index.shape)))
-        if hist_index.dtype not in (torch.int32, torch.int64) or cand_index.dtype not in (torch.int32, torch.int64):
-            raise ValueError('hist_index and cand_index must be int32 or int64 news indices, got %s and %s' % (hist_index.dtype, cand_index.dtype))
-        own = check_candidates(U)
-        if int(pairs_per_pass) < 1:
-            raise ValueError('pairs_per_pass must be positive, got %r' % (pairs_per_pass,))
-        if k is not None and not 1 <= int(k) <= 128:
-            raise ValueError('%s keeps 1 <= k <= 128 news per user (%s), got k = %r' % (top_k + (k,)))
-        return U, H, own
-
     @torch.no_grad()
     def score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                    cand_lifetime, n_src=None, pairs_per_pass=1 << 18, exclude_history=False):
@@ -499,62 +471,8 @@ class Model(nn.Module):
         A LIME model with LIME_OCCURRENCE_MATCH=1 where ``occurrence_match_applicable()`` holds: the pool's cache rows (with their Q /
         MLP news half) are one set of tables and ``occurrence_tables()`` (with theirs) another, and every pair is composed from a row
         of each in the kernel (lime_grouped_match_occurrence_f32) -- no ``encode_cached``, Q or MLP GEMM runs over the pairs."""
-        return self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
-
-    def _user_side(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, n_src, n_pairs):
-        """What every pass of a call reads of the users, once per call -> (hist [U, H, D], ucat [U, H], usub [U, H], hist_mask,
-        gate_y, n_src -- its default from the call's ``n_pairs``)."""
-        ue, (U, H) = self.user_encoder, hist_index.shape
-        hist = self.news_encoder.encode_cached(news_cache, hist_index, user_freshness, user_lifetime).view(U, H, -1)
-        flat_h = hist_index.reshape(-1).long()
-        ucat, usub = corpus.news_category[flat_h].view(U, H), corpus.news_subCategory[flat_h].view(U, H)
-        if n_src is None and hasattr(ue, 'user_node_embedding'):
-            n_src = min(n_pairs, H + ue.user_node_embedding.shape[0])
-        return hist, ucat, usub, hist_mask, ue.gate_projection(hist), n_src       # the gate's projection: once for every pass's histories
-
-    def _match_pass(self, news_cache, users, cands, pick, u0, u1, slots, category, subCategory, group_offsets):
-        """The logits fp32 [pairs], in group order, of one pass of a grouped match: the users u0:u1 (``users``: what ``_user_side``
-        gave), each with ``slots`` groups, user-major (hist_div = slots: a user's groups share one history, never repeated in memory
-        before the refinement); category / subCategory [n slots, 1]: what the user side reads of a group; ``cands``: the call's
-        candidates (news index, freshness, lifetime, remaining lifetime, then what ``_candidate_tables`` gave and -- with tables -- every
-        pair's row of them) and ``pick(t)`` the pass's of one of them, in group order;
-        group_offsets int64 [n slots + 1]: the groups' CSR over them, on the device or still on the host (the copy waits for the
-        stream, so it stands behind the launches that do not read it).  The user side runs once per group and the match per pair."""
-        return self._pass_logits(news_cache, self._pass_operands(users, u0, u1, slots, category, subCategory), cands, pick, group_offsets,
-                                 users[0].shape[1])
-
-    def _pass_operands(self, users, u0, u1, slots, category, subCategory):
-        """The user side of one pass (``_match_pass``'s users u0:u1 with ``slots`` groups each) -> what ``match_operands`` gives: once
-        per pass, whatever the number of candidate sets (time slots) matched against it."""
-        hist, ucat, usub, hist_mask, gate_y, n_src = users
-        H = hist.shape[1]
-        return self.user_encoder.match_operands(hist[u0:u1], category, subCategory, ucat[u0:u1], usub[u0:u1], hist_mask[u0:u1], n_src=n_src,
-                                                hist_div=slots, gate_y=None if gate_y is None else gate_y[u0 * H:u1 * H])
-
-    def _pass_logits(self, news_cache, operands, cands, pick, group_offsets, H):
-        """The candidate side of one pass and its match against ``operands`` (``_match_pass``'s other arguments) -> fp32 [pairs].
-        A schedule on the factorised route: freshness and remaining carry a leading slot axis [S, ...] over the call's tables, and the
-        pass is ONE launch for all its slots (lime_grouped_match_schedule_f32) -> fp32 [S, pairs]."""
-        index, freshness, lifetime, remaining, tables, position = cands
-        ne = self.news_encoder
-        dev = news_cache.device
-        if freshness.dim() == 3:
-            S = freshness.shape[0]
-            at = newsEncoders._i32(pick(position).reshape(-1)).contiguous()
-            occ = None if tables[3] is None else ne.occurrence_ids_schedule(pick(freshness).reshape(S, -1), pick(lifetime).reshape(-1))
-            return self._click_logits(operands, None, pick(remaining).reshape(S, -1), torch.as_tensor(group_offsets, device=dev), H,
-                                      tables=tables, index=at, occ=occ)
-        if tables is None:
-            cand = ne.encode_cached(news_cache, pick(index), pick(freshness), pick(lifetime))       # [pairs, D]
-            at = occ = None
-        else:
-            cand = None                                                                             # the call's tables, read in place
-            at = newsEncoders._i32(pick(position).reshape(-1)).contiguous()                         # int32 [pairs]: the pair's table row
-            # a LIME model's occurrence tables: the pair's row of them is its bucket pair -- two bucket launches, no row per pair
-            occ = None if tables[3] is None else ne.occurrence_ids(pick(freshness), pick(lifetime))
-        return self._click_logits(operands, cand, pick(remaining).reshape(-1), torch.as_tensor(group_offsets, device=dev), H, tables=tables,
-                                  index=at, occ=occ)
+        return serving.score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                  cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
 
     def _offsets_of_rows(self, groups, pairs, device):
         """int64 [groups + 1] on the device: the CSR of the regular shape, ``pairs`` pairs per group.  Kept per shape: a captured forward
@@ -569,7 +487,7 @@ class Model(nn.Module):
                     n_src=None, hist_div=1, gate_y=None):
         """The logits [B, N] of the regular shape -- B = hist.shape[0] * hist_div rows with N candidates each, ``ue.match``'s arguments.
         Under the dot-product predictor this IS ``ue.match`` (the match fused into the user encoder's last kernel); under the MLP
-        predictor the user encoder stops at its operands and ``_click_logits`` takes the rows as groups of N pairs."""
+        predictor the user encoder stops at its operands and ``serving.click_logits`` takes the rows as groups of N pairs."""
         ue = self.user_encoder
         if self.click_predictor == 'dot_product':
             return ue.match(hist, category, subCategory, user_category, user_subCategory, user_history_mask, cand,
@@ -579,91 +497,11 @@ class Model(nn.Module):
             raise NotImplementedError('the scoring kernel chain has no training-mode dropouts: Model.forward takes the differentiable path')
         B, N, D = cand.shape
         flat = cand.contiguous().view(B * N, D)
-        kw = dict(cand=flat) if hasattr(ue, 'user_node_embedding') else {}
-        operands = ue.match_operands(hist, category, subCategory, user_category, user_subCategory, user_history_mask, agg=agg, n_src=n_src,
-                                     hist_div=hist_div, gate_y=gate_y, **kw)
-        groups = (operands[0] if isinstance(operands, tuple) else operands).shape[0]     # (ATT / MHSA without refinement: one per history)
+        operands = serving.match_operands(self, hist, category, subCategory, user_category, user_subCategory, user_history_mask, cand=flat,
+                                          pairs=B * N, agg=agg, n_src=n_src, hist_div=hist_div, gate_y=gate_y)
+        groups = operands.kp.shape[0] // operands.H                                      # (ATT / MHSA without refinement: one per history)
         per = B * N // groups
-        return self._click_logits(operands, flat, None, self._offsets_of_rows(groups, per, flat.device), hist.shape[1], regular=per).view(B, N)
-
-    def _click_logits(self, operands, cand, remaining, offsets, H, tables=None, index=None, occ=None, regular=None):
-        """The ONE place that turns (user-side operands, candidates) into logits, for either click predictor -> fp32 [pairs].
-        ``operands``: what ``user_encoder.match_operands`` gave for G groups -- CROWN: (g [G, H, D], kp [G H, A], qp [pairs, A] or None:
-        made here); ATT / MHSA: the pooled vector [G, D], a history of ONE row whose softmax weight is 1 (kp and qp are not felt).
-        ``cand`` [pairs, D] in group order and ``offsets`` int64 [G + 1] their CSR; or ``tables`` (``_candidate_tables``) read in place
-        through ``index`` int32 [pairs] -- and, where the tables carry occurrence tables (a LIME model), composed with the row ``occ``
-        int32 [pairs] of those in the kernel (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  ``remaining``
-        [pairs]: read by the dot product's lifetime weight alone.  ``regular``: the pairs per group where every group has as many (the
-        [B, N] shape).  A schedule on the factorised route (dot product over tables): ``remaining`` (and ``occ``) [S, pairs] -> fp32
-        [S, pairs], every slot in one lime_grouped_match_schedule_f32 launch.
-
-        dot_product (model.py:179-181): lime_grouped_match_f32.  mlp (:182-184): with mlp.weight split into its user half W_u and its
-        news half W_n, gu = g W_u^T once per history row and nw = cand W_n^T + mlp.bias once per candidate row (a table for a baseline
-        model), then lime_grouped_mlp_match_f32 keeps a pair's pooled hidden row in registers; ops.FUSED_MLP_MATCH off: the composed
-        form -- the pairs' user rows, ``linear(cat, mlp, act='relu')``, the product with ``out`` -- on existing launches."""
-        ue, w = self.user_encoder, self.remaining_lifetime_weighting
-        if hasattr(ue, 'user_node_embedding'):
-            g, kp, qp = operands
-            D = g.shape[-1]
-            g = g.reshape(-1, D)
-            h_match, scale = H, 1.0 / ue.attention_scalar
-            if tables is not None:
-                qp = tables[1]
-            elif qp is None:
-                qp = ops.linear(cand, ue.Q.weight, ue.Q.bias)                                                 # userEncoders.py:162
-        else:
-            g, h_match, scale = operands, 1, 1.0
-            D = g.shape[-1]
-            kp = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=g.device)
-            qp = tables[1] if tables is not None else torch.zeros((cand.shape[0], 4), dtype=torch.float32, device=g.device)
-        if tables is not None:
-            cand = tables[0]
-        ct, qt, nt = tables[3] if tables is not None and tables[3] is not None else (None, None, None)
-        if self.click_predictor == 'dot_product':
-            composed = dict(occ=occ, qt=qt, ct=ct) if ct is not None else {}
-            if remaining.dim() == 2:                             # a schedule over the tables: remaining (and occ) [S, pairs], one launch
-                return ops.grouped_match_schedule(kp, g, qp, cand, remaining, offsets, index, h_match, scale, w.alpha, w.beta,
-                                                  bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty),
-                                                  slots=remaining.shape[0], **composed)
-            return ops.grouped_match(kp, g, qp, cand, remaining, offsets, h_match, scale, w.alpha, w.beta,
-                                     bool(w.use_remaining_lifetime_weighting), bool(w.use_expired_penalty), index=index, **composed)
-        mlp, out = self.mlp, self.out
-        if ops.FUSED_MLP_MATCH:
-            gu = ops.linear(g, mlp.weight[:, :D], None)
-            nw = tables[2] if tables is not None else ops.linear(cand, mlp.weight[:, D:], mlp.bias)
-            composed = dict(occ=occ, qt=qt, nt=nt) if nt is not None else {}
-            return ops.grouped_mlp_match(kp, gu, qp, nw, out.weight, out.bias, offsets, h_match, scale, index=index, **composed)
-        return self._composed_mlp_logits(kp, g, qp, cand, offsets, h_match, scale, index, regular)
-
-    def _composed_mlp_logits(self, kp, g, qp, cand, offsets, H, scale, index, regular):
-        """The MLP predictor on existing launches (ops.FUSED_MLP_MATCH off; the yardstick of the fused kernel): the user row of every
-        pair -- lime_interest_match_f32's, or the group's pooled vector -- then ops.mlp_predictor on the [pairs, 2 D] rows.  Irregular
-        groups go through in steps of pairs, each with its own copy of its group's H history rows."""
-        mlp, out = self.mlp, self.out
-        D, G = g.shape[1], g.shape[0] // H
-        P = index.numel() if index is not None else cand.shape[0]
-        predict = lambda user, news: ops.mlp_predictor(user, news, mlp.weight, mlp.bias, out.weight, out.bias)
-        if regular is not None and index is None and H > 1:
-            user, _ = ops.interest_match(kp.reshape(-1), qp.reshape(-1), g.reshape(-1), cand.reshape(-1), None, G, regular, H, kp.shape[1], D,
-                                         scale, 0.0, 0.0, False, False, want_logits=False, want_user=True)
-            return predict(user.view(P, D), cand)
-        group = torch.repeat_interleave(torch.arange(G, device=g.device), offsets[1:] - offsets[:-1], output_size=P)
-        logits = torch.empty((P,), dtype=torch.float32, device=g.device)
-        slots = torch.arange(H, device=g.device)
-        step = 1024 if H > 1 else 1 << 16
-        for p0 in range(0, P, step):
-            p1 = min(P, p0 + step)
-            at = slice(p0, p1) if index is None else index[p0:p1].long()
-            news = cand[at].contiguous()
-            if H > 1:
-                rows = (group[p0:p1].unsqueeze(1) * H + slots).reshape(-1)
-                user, _ = ops.interest_match(kp[rows].reshape(-1), qp[at].reshape(-1), g[rows].reshape(-1), news.reshape(-1), None, p1 - p0, 1,
-                                             H, kp.shape[1], D, scale, 0.0, 0.0, False, False, want_logits=False, want_user=True)
-                user = user.view(p1 - p0, D)
-            else:
-                user = g[group[p0:p1]]
-            logits[p0:p1] = predict(user, news)
-        return logits
+        return serving.click_logits(self, operands, flat, None, self._offsets_of_rows(groups, per, flat.device), regular=per).view(B, N)
 
     def occurrence_match_applicable(self):
         """Whether a candidate of this model is a row of a news table plus a row of an occurrence table with only linear maps behind it,
@@ -712,17 +550,17 @@ class Model(nn.Module):
         return 'factorised' if SCHEDULE_MATCH and self.schedule_match_applicable(H) else 'shared'
 
     def _candidate_tables(self, news_cache, rows=None, always=False):
-        """The ONE place that asks how the candidates are read -> None: ``_match_pass`` materialises a row and a Q row per pair; or
-        the tables (cand [n, D], qp [n, A], nw, occurrence tables) that the grouped match reads in place, once per call: the news of
+        """The ONE place that asks how the candidates are read -> None: ``serving.pass_logits`` materialises a row and a Q row per pair; or
+        the ``serving.Tables`` (cand [n, D], qp [n, A], nw, occurrence) that the grouped match reads in place, once per call: the news of
         ``rows`` (the pool, in plan order) or, with ``rows`` None, every news of the cache (the lists: a pair's index is its news id).
         Under ATT / MHSA (a history of one row) qp is never felt: n rows of four zero columns -- the kernel reads both tables at one index.
         Under the MLP click predictor a third table stands beside them: nw [n, D // 2] = cand W_n^T + mlp.bias, the news half of the
         predictor's hidden layer, once per call (None on the composed form and under the dot product).
 
         A baseline model (``occurrence_free``: the representation depends on the news alone, INDEXED_MATCH): cand is the news' rows
-        themselves and the fourth entry is None (lime_grouped_match_indexed_f32 / lime_grouped_mlp_match_indexed_f32).
+        themselves and ``occurrence`` is None (lime_grouped_match_indexed_f32 / lime_grouped_mlp_match_indexed_f32).
         A LIME model for which ``occurrence_match_applicable()`` holds (OCCURRENCE_MATCH): cand = A, the cache rows, qp = A Q^T + b_Q and
-        nw = A W_n^T + mlp.bias, and the fourth entry is (ct, qt, nt) = (T, T Q^T, T W_n^T) [num_buckets^2 rows, no bias: it is in
+        nw = A W_n^T + mlp.bias, and ``occurrence`` is (ct, qt, nt) = (T, T Q^T, T W_n^T) [num_buckets^2 rows, no bias: it is in
         the news tables] from LIME.occurrence_tables(); a pair adds its bucket pair's row of them in the kernel
         (lime_grouped_match_occurrence_f32 / lime_grouped_mlp_match_occurrence_f32).  Every other model: None.
         ``always``: the tables wherever the model has them, whatever the two switches say (the factorised schedule reads nothing else)."""
@@ -742,105 +580,7 @@ class Model(nn.Module):
             qp = (ops.linear(t, ue.Q.weight, ue.Q.bias if bias else None) if crown else
                   torch.zeros((t.shape[0], 4), dtype=torch.float32, device=t.device))
             return qp, (ops.linear(t, self.mlp.weight[:, t.shape[1]:], self.mlp.bias if bias else None) if mlp else None)
-        qp, nw = behind(cand, True)
-        return cand, qp, nw, (None if ct is None else (ct,) + behind(ct, False))
-
-    def _score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                    cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None, slot_offsets=None):
-        """score_pool -> (scores [U, C], bool [U, C] "excluded" or None): the passes over recommend.pool_plan's ONE host plan.
-        With ``slot_offsets`` [S] (score_schedule): scores [S, U, C], slot s at freshness ``cand_freshness + slot_offsets[s]`` (the sum
-        made in fp32), by ``schedule_route(S, H)`` -- 'single': this very path at that freshness; 'shared': the user side once per
-        call, ``match_operands`` once per pass, the candidate side and the match once per slot; 'factorised': the call's tables
-        (whatever LIME_INDEXED_MATCH / LIME_OCCURRENCE_MATCH say) and one lime_grouped_match_schedule_f32 launch per pass for all
-        slots; 'expand': one slot, repeated."""
-        C = cand_index.numel()
-        entry = 'recommend' if slot_offsets is None else 'recommend_schedule'
-
-        def check_candidates(U):
-            for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
-                if tuple(t.shape) not in ((C,), (U, C)):
-                    raise ValueError('%s must be [C] = [%d] or [U, C] = [%d, %d], got %s' % (name, C, U, C, tuple(t.shape)))
-            if slot_offsets is not None and (slot_offsets.dim() != 1 or slot_offsets.numel() < 1 or not slot_offsets.is_floating_point()):
-                raise ValueError('slot_offsets must be a float [S] with S >= 1 -- the slots\' offsets in the unit of the freshness --, got %s %s'
-                                 % (slot_offsets.dtype, tuple(slot_offsets.shape)))
-        bad_index = 'cand_index must be [C] with C >= 1 -- ONE pool for all users --' if cand_index.dim() != 1 or C < 1 else None
-        U, H, _ = self._check_grouped(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index,
-                                      check_candidates, pairs_per_pass, k, (entry, 'lime_topk_rows_f32'))
-        c, dev = corpus, news_cache.device
-        S = 1 if slot_offsets is None else slot_offsets.numel()
-        route = 'single' if slot_offsets is None else self.schedule_route(S, H)
-        offs = None if slot_offsets is None else slot_offsets.to(dev).float()
-        if offs is not None and route in ('single', 'expand'):                 # one slot is computed (no slot is felt under 'expand')
-            cand_freshness, offs = cand_freshness.to(dev).float() + offs[0], None
-        sets = 1 if offs is None else S                                         # the candidate sets that are matched
-        cidx = cand_index.to(dev).long()
-        cat_c, sub_c = c.news_category[cidx], c.news_subCategory[cidx]
-        plan = rec.pool_plan(cat_c.cpu().numpy(), sub_c.cpu().numpy(), self.grouped_by())
-        T, order = plan.category.shape[0], torch.as_tensor(plan.order, device=dev)
-        fresh, life = cand_freshness.to(dev).float().expand(U, C), cand_lifetime.to(dev).float().expand(U, C)
-        fresh = fresh.unsqueeze(0) if offs is None else fresh.unsqueeze(0) + offs.view(S, 1, 1)            # [sets, U, C]
-        remaining = self._lifetime_rule(fresh, lambda: life.unsqueeze(0).expand(sets, U, C),
-                                        lambda: cat_c.view(1, 1, C).expand(sets, U, C)).float()
-        # the pool in plan (topic) order: what every pass reads
-        # (a baseline model: the pool's C rows and their Q, once per call)
-        tables = self._candidate_tables(news_cache, cidx[order], always=route == 'factorised')
-        index, life = cidx[order].unsqueeze(0).expand(U, C), life[:, order]
-        fresh, remaining = fresh[:, :, order], remaining[:, :, order]
-        position = None if tables is None else torch.arange(C, dtype=torch.int32, device=dev).unsqueeze(0).expand(U, C)
-        users = self._user_side(news_cache, c, hist_index, hist_mask, user_freshness, user_lifetime, n_src, U * C)
-        # (read in place, the candidates take no rows of a pass: the refined rows alone bound its users)
-        per = rec.users_per_pass(U, C if tables is None else 0, T, H, int(pairs_per_pass))
-        cat_t = torch.as_tensor(plan.category, device=dev).to(c.news_category.dtype)
-        sub_t = torch.as_tensor(plan.subCategory, device=dev).to(c.news_subCategory.dtype)
-        out = torch.empty((sets, U, C), dtype=torch.float32, device=dev)
-        for u0 in range(0, U, per):
-            u1 = min(U, u0 + per)
-            n = u1 - u0
-            operands = self._pass_operands(users, u0, u1, T, cat_t.repeat(n).view(n * T, 1), sub_t.repeat(n).view(n * T, 1))
-            goff = rec.group_offsets(plan.segments, n)
-            if route == 'factorised':                                          # every slot of the pass in one launch
-                logits = self._pass_logits(news_cache, operands, (index, fresh, life, remaining, tables, position),
-                                           lambda t: t[..., u0:u1, :], goff, H)
-                out[:, u0:u1].index_copy_(2, order, logits.view(sets, n, C))
-                continue
-            for s in range(sets):
-                logits = self._pass_logits(news_cache, operands, (index, fresh[s], life, remaining[s], tables, position),
-                                           lambda t: t[u0:u1], goff, H)
-                out[s, u0:u1].index_copy_(1, order, logits.view(n, C))
-        gone = self._in_history(news_cache.shape[0], hist_index, hist_mask, cidx) if exclude_history else None
-        if exclude_history:
-            out.masked_fill_(gone.unsqueeze(0), float('-inf'))
-        if slot_offsets is None:
-            return out[0], gone
-        return (out.repeat(S, 1, 1) if sets != S else out), gone
-
-    _TopicQuota = collections.namedtuple('_TopicQuota', 'q topic_of_news n_keys')
-
-    @staticmethod
-    def _topic_quota(corpus, max_per_topic, quota_by):
-        """The refusals of ``max_per_topic`` / ``quota_by`` (ValueError, before any launch) -> None without a quota, or (q, the corpus'
-        topic_of_news int32 [n_news] under ``quota_by`` -- device_data.topic_table_of --, its number of groups)."""
-        if max_per_topic is None:
-            return None
-        if isinstance(max_per_topic, bool) or not isinstance(max_per_topic, numbers.Integral) or max_per_topic < 1:
-            raise ValueError('max_per_topic must be an integer >= 1 (or None: no quota), got %r' % (max_per_topic,))
-        if quota_by not in ('category', 'topic'):
-            raise ValueError("quota_by must be 'category' or 'topic' (the (category, subCategory) pair), got %r" % (quota_by,))
-        from .device_data import topic_table_of
-        topic_of_news, cat_t, _ = topic_table_of(corpus, quota_by)
-        if cat_t.numel() > rec.MAX_TOPICS:
-            raise ValueError('the corpus has %d groups by %s, lime_topk_rows_quota_f32 counts up to %d' % (cat_t.numel(), quota_by, rec.MAX_TOPICS))
-        return Model._TopicQuota(int(max_per_topic), topic_of_news, cat_t.numel())
-
-    @staticmethod
-    def _in_history(n_news, hist_index, hist_mask, cidx):
-        """bool [U, C]: candidate j sits in a masked-in slot of user u's history."""
-        U, H = hist_index.shape
-        seen = torch.zeros((U, n_news), dtype=torch.bool, device=cidx.device)
-        live = hist_mask.to(cidx.device).bool()
-        users = torch.arange(U, device=cidx.device).unsqueeze(1).expand(U, H)
-        seen[users[live], hist_index.to(cidx.device).long()[live]] = True
-        return seen[:, cidx]
+        return serving.Tables(cand, *behind(cand, True), None if ct is None else serving.Occurrence(ct, *behind(ct, False)))
 
     @torch.no_grad()
     def recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
@@ -857,17 +597,8 @@ class Model(nn.Module):
         (category, subCategory) pair; it is independent of what the user side groups by (``grouped_by()``), so a model without
         candidate-aware attention takes quotas too.  An excluded candidate uses no quota.  A corpus of more than 8192 groups is
         refused (ValueError), as are a ``max_per_topic`` that is no integer >= 1 and an unknown ``quota_by``."""
-        quota = self._topic_quota(corpus, max_per_topic, quota_by)
-        scores, gone = self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                        cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
-        if quota is not None:                                  # the kernel drops the excluded: nothing to replace afterwards
-            return ops.topk_rows_quota(scores, quota.topic_of_news[cand_index.to(scores.device).long()], quota.q, int(k), drop=gone,
-                                       n_keys=quota.n_keys)
-        positions, top = ops.topk_rows(scores, int(k))
-        if gone is not None:
-            gone = gone.gather(1, positions.clamp(min=0).long()) & (positions >= 0)
-            positions = torch.where(gone, torch.full_like(positions, -1), positions)
-        return positions, top
+        return serving.recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                 cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by)
 
     @torch.no_grad()
     def score_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
@@ -890,8 +621,8 @@ class Model(nn.Module):
             kernel's limits, or LIME_SCHEDULE_MATCH=0: the existing match once per slot on the shared operands, bit for bit S
             ``score_pool`` calls;
           'expand' -- a baseline under the MLP predictor reads no time at all: one slot, repeated."""
-        return self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                cand_lifetime, n_src, pairs_per_pass, exclude_history, slot_offsets=torch.as_tensor(slot_offsets))[0]
+        return serving.score_pool(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                  cand_lifetime, n_src, pairs_per_pass, exclude_history, slot_offsets=torch.as_tensor(slot_offsets))[0]
 
     @torch.no_grad()
     def recommend_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
@@ -903,23 +634,8 @@ class Model(nn.Module):
         ``cand_freshness + slot_offsets[s]``, in its order and with its -1 / -inf for excluded or missing slots.  1 <= k <= 128.
         ``max_per_topic`` / ``quota_by``: as in ``recommend``, per (slot, user) row (lime_topk_rows_quota_f32 over the same view; the
         [U, C] mask of ``exclude_history`` is handed over once, row s U + u reads its row u)."""
-        quota = self._topic_quota(corpus, max_per_topic, quota_by)
-        scores, gone = self._score_pool(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                        cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k,
-                                        slot_offsets=torch.as_tensor(slot_offsets))
-        S, U, C = scores.shape
-        step = max(1, 65535 // max(U, 1))
-        if quota is not None:
-            keys = quota.topic_of_news[cand_index.to(scores.device).long()]
-            found = [ops.topk_rows_quota(scores[s0:s0 + step].view(-1, C), keys, quota.q, int(k), drop=gone, n_keys=quota.n_keys)
-                     for s0 in range(0, S, step)]
-        else:
-            found = [ops.topk_rows(scores[s0:s0 + step].view(-1, C), int(k)) for s0 in range(0, S, step)]
-        positions, top = (torch.cat([f[i] for f in found]).view(S, U, int(k)) for i in (0, 1))
-        if gone is not None and quota is None:
-            gone = gone.unsqueeze(0).expand(S, U, C).gather(2, positions.clamp(min=0).long()) & (positions >= 0)
-            positions = torch.where(gone, torch.full_like(positions, -1), positions)
-        return positions, top
+        return serving.recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                                 cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=slot_offsets)
 
     @torch.no_grad()
     def score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
@@ -943,77 +659,8 @@ class Model(nn.Module):
         (lime_grouped_match_indexed_f32), with Q of every news of the cache computed once per call under the CROWN user encoder.
         A LIME model with LIME_OCCURRENCE_MATCH=1 where ``occurrence_match_applicable()`` holds: the cache itself is the news table, a
         pair's index its news id, and the occurrence is composed in the kernel as in ``score_pool``."""
-        return self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
-                                 cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
-
-    def _score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
-                     cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
-        """score_lists -> (scores [P], the offsets on the device, bool [P] "excluded" or None): the passes over ops.list_plan's plan."""
-        import numpy as np
-        from .device_data import topic_table_of
-        P = cand_index.numel()
-
-        def check_candidates(U):
-            off = cand_offsets.detach().cpu().numpy() if isinstance(cand_offsets, torch.Tensor) else np.asarray(cand_offsets)
-            if off.ndim != 1 or off.shape[0] != U + 1 or off.dtype.kind not in 'iu':
-                raise ValueError('cand_offsets must be U + 1 = %d integers (the CSR of the lists), got %s %s' % (U + 1, off.dtype, off.shape))
-            off = off.astype(np.int64)
-            if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != P:
-                raise ValueError('cand_offsets must start at 0, not decrease and end at P = %d, got %d .. %d%s'
-                                 % (P, off[0], off[-1], ' (decreasing)' if (np.diff(off) < 0).any() else ''))
-            for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
-                if tuple(t.shape) != (P,):
-                    raise ValueError('%s must be [P] = [%d], got %s' % (name, P, tuple(t.shape)))
-            return off
-        bad_index = 'cand_index must be [P], the lists one behind the other,' if cand_index.dim() != 1 else None
-        U, H, off = self._check_grouped(news_cache, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, bad_index,
-                                        check_candidates, pairs_per_pass, k, ('recommend_lists', 'lime_topk_segments_f32'))
-        dev = news_cache.device
-        offsets = torch.from_numpy(off).to(dev)
-        if P == 0:
-            return torch.empty((0,), dtype=torch.float32, device=dev), offsets, None
-        topic_of_news, cat_t, sub_t = topic_table_of(corpus, self.grouped_by())
-        if cat_t.numel() > rec.MAX_TOPICS:
-            raise ValueError('the corpus has %d topics, lime_list_plan groups up to %d' % (cat_t.numel(), rec.MAX_TOPICS))
-        cidx = cand_index.to(dev).long()
-        fresh, life = cand_freshness.to(dev).float(), cand_lifetime.to(dev).float()
-        remaining = self._lifetime_rule(fresh, lambda: life, lambda: corpus.news_category[cidx]).float()
-        keys = topic_of_news[cidx]
-        plan = ops.list_plan(keys, offsets, n_keys=cat_t.numel())                      # the call's one device -> host read
-        S = (plan.slot_key.numel() // U) if U else 1
-        users = self._user_side(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, n_src, P)
-        tables = self._candidate_tables(news_cache)                   # (a baseline model: the cache itself, and Q of every news once)
-        out = torch.empty((P,), dtype=torch.float32, device=dev)
-        for u0, u1, S_pass in rec.list_passes(off, plan.n_distinct, H, int(pairs_per_pass)):
-            p0, p1 = int(off[u0]), int(off[u1])
-            if p1 == p0:
-                continue
-            if S_pass == S:                                                           # the pass's plan is a slice of the call's
-                rows, goff, skey = plan.order[p0:p1], plan.group_offsets[u0 * S:u1 * S + 1] - p0, plan.slot_key[u0 * S:u1 * S]
-            else:                                                                     # fewer slots suffice: no slot count is read again
-                sub = ops.list_plan(keys[p0:p1], offsets[u0:u1 + 1] - p0, slots=S_pass, n_keys=cat_t.numel(),
-                                    n_distinct=plan.n_distinct[u0:u1])
-                rows, goff, skey = sub.order + p0, sub.group_offsets, sub.slot_key
-            skey = skey.long()
-            out.index_copy_(0, rows, self._match_pass(news_cache, users, (cidx, fresh, life, remaining, tables, cidx), lambda t: t[rows], u0, u1,
-                                                      S_pass,
-                                                      cat_t[skey].view(-1, 1), sub_t[skey].view(-1, 1), goff.contiguous()))
-        gone = self._in_own_history(hist_index.to(dev), hist_mask.to(dev), offsets, cidx) if exclude_history else None
-        if exclude_history:
-            out.masked_fill_(gone, float('-inf'))
-        return out, offsets, gone
-
-    @staticmethod
-    def _in_own_history(hist_index, hist_mask, offsets, cidx, pairs_per_step=1 << 18):
-        """bool [P]: the candidate of pair p sits in a masked-in slot of ITS user's history -- per pair against the user's H slots."""
-        U, P = hist_index.shape[0], cidx.numel()
-        user = torch.repeat_interleave(torch.arange(U, device=cidx.device), offsets[1:] - offsets[:-1], output_size=P)
-        hist, live = hist_index.long(), hist_mask.bool()
-        gone = torch.empty((P,), dtype=torch.bool, device=cidx.device)
-        for p0 in range(0, P, pairs_per_step):
-            u = user[p0:p0 + pairs_per_step]
-            gone[p0:p0 + pairs_per_step] = ((hist[u] == cidx[p0:p0 + pairs_per_step].unsqueeze(1)) & live[u]).any(dim=1)
-        return gone
+        return serving.score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                                   cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history)[0]
 
     @torch.no_grad()
     def recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
@@ -1025,21 +672,8 @@ class Model(nn.Module):
         never returned; the trailing slots of a list with fewer than k candidates left (all k of an empty list) hold position -1 and
         score -inf.  1 <= k <= 128.
         ``max_per_topic`` / ``quota_by``: as in ``recommend``, per list (lime_topk_segments_quota_f32)."""
-        quota = self._topic_quota(corpus, max_per_topic, quota_by)
-        scores, offsets, gone = self._score_lists(news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
-                                                  cand_index, cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
-        U, k = hist_index.shape[0], int(k)
-        if scores.numel() == 0:
-            return (torch.full((U, k), -1, dtype=torch.int32, device=scores.device),
-                    torch.full((U, k), float('-inf'), dtype=torch.float32, device=scores.device))
-        if quota is not None:
-            return ops.topk_segments_quota(scores, offsets, quota.topic_of_news[cand_index.to(scores.device).long()], quota.q, k, drop=gone,
-                                           n_keys=quota.n_keys)
-        positions, top = ops.topk_segments(scores, offsets, k)
-        if gone is not None:
-            at = (offsets[:-1].unsqueeze(1) + positions.clamp(min=0).long()).clamp(max=scores.numel() - 1)
-            positions = torch.where(gone[at] & (positions >= 0), torch.full_like(positions, -1), positions)
-        return positions, top
+        return serving.recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                                       cand_freshness, cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by)
 
     def _score_from_recurrence(self, behaviors, rows, rc, n_src, rows_per_forward):
         """score_behaviors under CNE from the recurrence cache: one encoder pass over the R candidates and the R . H history news of the

@@ -569,7 +569,7 @@ class NewsEncoder(nn.Module):
     # ---- the content encoder as the model's news encoder itself (config.news_encoder = 'CROWN', 'CNN', ...: reference model.py:41-62,
     # the baselines LIME is compared with).  The surface Model calls on LIME, with the occurrence side -- freshness, the user's topic
     # lifetime -- being the identity: a representation depends on the news alone.
-    occurrence_free = True          # Model._match_pass: candidates are read in place through an index (LIME: one row per occurrence)
+    occurrence_free = True          # serving.pass_logits: candidates are read in place through an index (LIME: one row per occurrence)
 
     def encode_rows(self, title_text, title_mask, content_text, category, subCategory, title_entity=None):
         """M flat news -> [M, news_embedding_dim] on the scoring kernels (``encode_flat`` into a fresh buffer)."""

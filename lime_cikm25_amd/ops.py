@@ -913,6 +913,34 @@ def _occurrence_tables(index, occ, tables, n_occ):
     return _vec(occ, 'occ', index.numel(), dtype=torch.int32), n_occ
 
 
+def _grouped_operands(kp, g, qp, v, names, H, index, n, occurrence, plain=True):
+    """The host checks the grouped matches open with, under the caller's operand ``names``: kp [G H, A] and g [G H, W] per group; qp
+    and v per pair -- [P, A] and [P, W] (the plain form, where the entry has one: ``plain``), or tables of at least ``n`` rows read
+    through index int32 [P] (default: all of qp's) -> (G, P, A, W, index, n, composed: whether one of the ``occurrence`` arguments
+    (occ, the two tables, n_occ) is given -- ``_occurrence_tables`` then checks them, behind the caller's own)."""
+    for t, name in zip((kp, g, qp, v), names):
+        _mat(t, name)
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    (A, W), (k_, g_, q_, v_) = (kp.shape[1], g.shape[1]), names
+    if H < 1 or kp.shape[0] % H or g.shape[0] != kp.shape[0]:
+        raise ValueError('%s and %s must have G * H rows each, got %d and %d with H = %d' % (k_, g_, kp.shape[0], g.shape[0], H))
+    if plain and index is None:
+        if n is not None:
+            raise ValueError('n is the table size of the indexed form: give index too')
+        P = qp.shape[0]
+        if qp.shape[1] != A or v.shape != (P, W):
+            raise ValueError('%s must be [P, %d] and %s [P, %d], got %s and %s' % (q_, A, v_, W, tuple(qp.shape), tuple(v.shape)))
+    else:
+        P = index.numel()
+        index = _vec(index, 'index', P, dtype=torch.int32)
+        n = qp.shape[0] if n is None else int(n)
+        if qp.shape[1] != A or v.shape[1] != W or not 0 <= n <= min(qp.shape[0], v.shape[0]):
+            raise ValueError('%s must be [>= n, %d] and %s [>= n, %d] with n = %d, got %s and %s'
+                             % (q_, A, v_, W, n, tuple(qp.shape), tuple(v.shape)))
+    return kp.shape[0] // H, P, A, W, index, n, any(t is not None for t in occurrence)
+
+
 def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False, index=None,
                   n=None, occ=None, qt=None, ct=None, n_occ=None):
     """``lime_grouped_match_f32``: the history-vs-candidate attention, the dot-product match and the remaining-lifetime weight for
@@ -928,27 +956,7 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
     pair's operands are composed in the kernel, ``qp[index] + qt[occ]`` and ``cand[index] + ct[occ]`` (one fp32 add per element; occ
     is clamped into [0, n_occ), default all of qt's rows).  A pair's bits are those of the plain form on those sums."""
     lib = _lib.load()
-    for t, name in ((kp, 'kp'), (g, 'g'), (qp, 'qp'), (cand, 'cand')):
-        _mat(t, name)
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous' % name)
-    A, D = kp.shape[1], g.shape[1]
-    if H < 1 or kp.shape[0] % H or g.shape[0] != kp.shape[0]:
-        raise ValueError('kp and g must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], g.shape[0], H))
-    G = kp.shape[0] // H
-    if index is None:
-        if n is not None:
-            raise ValueError('n is the table size of the indexed form: give index too')
-        P = qp.shape[0]
-        if qp.shape[1] != A or cand.shape != (P, D):
-            raise ValueError('qp must be [P, %d] and cand [P, %d], got %s and %s' % (A, D, tuple(qp.shape), tuple(cand.shape)))
-    else:
-        P = index.numel()
-        index = _vec(index, 'index', P, dtype=torch.int32)
-        n = qp.shape[0] if n is None else int(n)
-        if qp.shape[1] != A or cand.shape[1] != D or not 0 <= n <= min(qp.shape[0], cand.shape[0]):
-            raise ValueError('qp must be [>= n, %d] and cand [>= n, %d] with n = %d, got %s and %s' % (A, D, n, tuple(qp.shape), tuple(cand.shape)))
-    composed = occ is not None or qt is not None or ct is not None or n_occ is not None
+    G, P, A, D, index, n, composed = _grouped_operands(kp, g, qp, cand, ('kp', 'g', 'qp', 'cand'), H, index, n, (occ, qt, ct, n_occ))
     if composed:
         occ, n_occ = _occurrence_tables(index, occ, ((qt, 'qt', A), (ct, 'ct', D)), n_occ)
     _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
@@ -991,24 +999,12 @@ def grouped_match_schedule(kp, g, qa, ca, remaining, offsets, index, H, scale, a
     the weight moves with the slot and a slot's bits are those of ``grouped_match``'s indexed form.  ``slots``: S, where neither
     ``occ`` nor ``remaining`` gives it."""
     lib = _lib.load()
-    for t, name in ((kp, 'kp'), (g, 'g'), (qa, 'qa'), (ca, 'ca')):
-        _mat(t, name)
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous' % name)
-    A, D = kp.shape[1], g.shape[1]
-    if H < 1 or kp.shape[0] % H or g.shape[0] != kp.shape[0]:
-        raise ValueError('kp and g must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], g.shape[0], H))
-    G = kp.shape[0] // H
-    P = index.numel()
-    index = _vec(index, 'index', P, dtype=torch.int32)
-    n = qa.shape[0] if n is None else int(n)
-    if qa.shape[1] != A or ca.shape[1] != D or not 0 <= n <= min(qa.shape[0], ca.shape[0]):
-        raise ValueError('qa must be [>= n, %d] and ca [>= n, %d] with n = %d, got %s and %s' % (A, D, n, tuple(qa.shape), tuple(ca.shape)))
+    G, P, A, D, index, n, composed = _grouped_operands(kp, g, qa, ca, ('kp', 'g', 'qa', 'ca'), H, index, n, (occ, qt, ct, n_occ),
+                                                       plain=False)
     given = [t.shape[0] for t in (occ, remaining if use_weight else None) if t is not None] + ([int(slots)] if slots is not None else [])
     if not given or min(given) != max(given) or given[0] < 1:
         raise ValueError('the slot count S >= 1 comes from occ [S, P], remaining [S, P] or slots, and they must agree: got %s' % (given,))
     S = given[0]
-    composed = occ is not None or qt is not None or ct is not None or n_occ is not None
     if composed:
         if occ is None or tuple(occ.shape) != (S, P):
             raise ValueError('occ must be [S, P] = [%d, %d], got %s' % (S, P, None if occ is None else tuple(occ.shape)))
@@ -1050,27 +1046,7 @@ def grouped_mlp_match(kp, gu, qp, nw, w_out, b_out, offsets, H, scale, index=Non
     pair's operands are composed in the kernel, ``qp[index] + qt[occ]`` and ``nw[index] + nt[occ]`` -- the rules of
     ``grouped_match``'s occurrence form."""
     lib = _lib.load()
-    for t, name in ((kp, 'kp'), (gu, 'gu'), (qp, 'qp'), (nw, 'nw')):
-        _mat(t, name)
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous' % name)
-    A, Dh = kp.shape[1], gu.shape[1]
-    if H < 1 or kp.shape[0] % H or gu.shape[0] != kp.shape[0]:
-        raise ValueError('kp and gu must have G * H rows each, got %d and %d with H = %d' % (kp.shape[0], gu.shape[0], H))
-    G = kp.shape[0] // H
-    if index is None:
-        if n is not None:
-            raise ValueError('n is the table size of the indexed form: give index too')
-        P = qp.shape[0]
-        if qp.shape[1] != A or nw.shape != (P, Dh):
-            raise ValueError('qp must be [P, %d] and nw [P, %d], got %s and %s' % (A, Dh, tuple(qp.shape), tuple(nw.shape)))
-    else:
-        P = index.numel()
-        index = _vec(index, 'index', P, dtype=torch.int32)
-        n = qp.shape[0] if n is None else int(n)
-        if qp.shape[1] != A or nw.shape[1] != Dh or not 0 <= n <= min(qp.shape[0], nw.shape[0]):
-            raise ValueError('qp must be [>= n, %d] and nw [>= n, %d] with n = %d, got %s and %s' % (A, Dh, n, tuple(qp.shape), tuple(nw.shape)))
-    composed = occ is not None or qt is not None or nt is not None or n_occ is not None
+    G, P, A, Dh, index, n, composed = _grouped_operands(kp, gu, qp, nw, ('kp', 'gu', 'qp', 'nw'), H, index, n, (occ, qt, nt, n_occ))
     if composed:
         occ, n_occ = _occurrence_tables(index, occ, ((qt, 'qt', A), (nt, 'nt', Dh)), n_occ)
     _vec(offsets, 'offsets', G + 1, dtype=torch.int64)

@@ -13,7 +13,7 @@ import test_recommend_gpu as R
 from helpers import rel_err
 from test_occurrence_match_model_gpu import _same_choice
 from test_recommend_gpu import C, K, TOL, U
-from lime_cikm25_amd import model as model_module, newsEncoders, ops
+from lime_cikm25_amd import model as model_module, newsEncoders, ops, serving
 
 pytestmark = pytest.mark.gpu
 
@@ -151,7 +151,7 @@ class _Calls:
     def __init__(self, monkeypatch, model):
         self.encode, self.linear, self.user_side, self.operands = [], [], 0, 0
         ne, ue = model.news_encoder, model.user_encoder
-        real_encode, real_linear, real_operands, real_user_side = ne.encode_cached, ops.linear, ue.match_operands, model._user_side
+        real_encode, real_linear, real_operands, real_user_side = ne.encode_cached, ops.linear, ue.match_operands, serving.user_side
 
         def encode_cached(cache, news_index, *a, **kw):
             self.encode.append(int(news_index.numel()))
@@ -171,7 +171,7 @@ class _Calls:
         monkeypatch.setattr(ne, 'encode_cached', encode_cached)
         monkeypatch.setattr(ops, 'linear', linear)
         monkeypatch.setattr(ue, 'match_operands', match_operands)
-        monkeypatch.setattr(model, '_user_side', user_side)
+        monkeypatch.setattr(serving, 'user_side', user_side)
 
 
 @pytest.mark.parametrize('name', ['crown_user', 'add', 'att_user', 'baseline_naml_att'])
