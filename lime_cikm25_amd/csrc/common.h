@@ -96,8 +96,83 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
+// The same for ONE wave.  LDS ops of a wave execute in order; drain lgkmcnt so that a tile written by some lanes is read back by
+// others, and keep the compiler from moving memory ops across the point.  Deliberately NOT a workgroup-scope fence: that also
+// waits vmcnt(0), i.e. for the prefetches and the output stores still in flight.
+__device__ __forceinline__ void wave_lds_fence() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Sum / maximum over the 256 threads (four waves) of a workgroup, in a fixed order; `red` is >= 4 floats of LDS; every thread gets
+// the result.  The barrier in front of the write protects `red` against the readers of its previous use: safe back to back.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+__device__ __forceinline__ float block_max(float v, float* red) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+// The first two thirds of a softmax over the LDS array a[0 .. n), by the 256 threads of a workgroup: a[i] <- exp(a[i] - max a),
+// returns 1 / sum of them (the caller scales where it uses the terms).  Thread t touches the elements t, t + 256, ... only: values it
+// wrote itself need no barrier in front, and the caller puts one behind before other threads read `a`.
+__device__ __forceinline__ float block_softmax_terms(float* a, int n, float* red) {
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < n; i += 256) mx = fmaxf(mx, a[i]);
+    mx = block_max(mx, red);
+    float part = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float e = expf(a[i] - mx);
+        a[i] = e;
+        part += e;
+    }
+    return 1.0f / block_sum(part, red);
+}
 
 __device__ __forceinline__ float lime_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// the run-time activation of the lime_linear_f32 epilogues (LIME_ACT_RELU_GRAD is a backward pass of its own, not an activation)
+__device__ __forceinline__ float apply_act(float v, int act) {
+    if (act == LIME_ACT_RELU) return fmaxf(v, 0.f);
+    if (act == LIME_ACT_TANH) return tanhf(v);
+    if (act == LIME_ACT_SIGMOID) return lime_sigmoid(v);
+    return v;
+}
+
+// Four consecutive elements 4 j .. 4 j + 3 of a row of n floats (zeros behind the end; VEC: one 16-byte load), and the dot product /
+// axpy over such a quad with explicit fmaf in element order: the kernels whose bits must not depend on their form use these.
+// (J: the caller's index width, int or long.)
+template <bool VEC, typename J>
+__device__ __forceinline__ f32x4 row_quad(const float* __restrict__ p, J j, int n) {
+    const J e = 4 * j;
+    if (VEC) return *reinterpret_cast<const f32x4*>(p + e);
+    f32x4 r;
+    r.x = e < n ? p[e] : 0.f;
+    r.y = e + 1 < n ? p[e + 1] : 0.f;
+    r.z = e + 2 < n ? p[e + 2] : 0.f;
+    r.w = e + 3 < n ? p[e + 3] : 0.f;
+    return r;
+}
+__device__ __forceinline__ float fma_dot4(f32x4 a, f32x4 b, float acc) {
+    acc = fmaf(a.x, b.x, acc);
+    acc = fmaf(a.y, b.y, acc);
+    acc = fmaf(a.z, b.z, acc);
+    return fmaf(a.w, b.w, acc);
+}
+__device__ __forceinline__ f32x4 fma_axpy4(float a, f32x4 x, f32x4 acc) {
+    acc.x = fmaf(a, x.x, acc.x);
+    acc.y = fmaf(a, x.y, acc.y);
+    acc.z = fmaf(a, x.z, acc.z);
+    acc.w = fmaf(a, x.w, acc.w);
+    return acc;
+}
 
 // The remaining-lifetime weight (util.py:23-49), the expression of lime_interest_match_f32 / lime_lifetime_score_f32:
 // positive_mask * w + negative_mask * beta * w with the expired penalty, sigmoid(alpha |r|) without

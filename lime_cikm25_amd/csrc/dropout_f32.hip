@@ -187,11 +187,6 @@ __global__ __launch_bounds__(256) void embed_pe_dropout_vec4_kernel(const int* _
     }
 }
 
-int grid_for(long total) {
-    const long g = (total + 255) / 256;
-    return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 extern "C" int lime_dropout_f32(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int32_t cols, float p,
@@ -202,9 +197,9 @@ extern "C" int lime_dropout_f32(const float* src, int64_t lds, float* dst, int64
     if (rows == 0) return LIME_OK;
     const LimeDropout d = lime_make_dropout(p, seed, site);
     if (cols % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0)
-        dropout_vec4_kernel<<<grid_for(rows * (cols / 4)), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols, d);
+        dropout_vec4_kernel<<<lime_grid_cap(rows * (cols / 4), 256, 16384), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols, d);
     else
-        dropout_kernel<<<grid_for(rows * cols), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols, d);
+        dropout_kernel<<<lime_grid_cap(rows * cols, 256, 16384), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols, d);
     return lime_check_launch("dropout_kernel");
 }
 
@@ -215,7 +210,7 @@ extern "C" int lime_dropout2_f32(const float* src, int64_t lds, float* dst, int6
     LIME_REQUIRE(p >= 0.f && p < 1.f, LIME_ERR_BAD_ARG, "lime_dropout2_f32: p = %g outside [0, 1)", (double)p);
     if (rows == 0) return LIME_OK;
     if (cols % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0) {
-        dropout2_vec4_kernel<<<grid_for(rows * (cols / 4)), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols,
+        dropout2_vec4_kernel<<<lime_grid_cap(rows * (cols / 4), 256, 16384), 256, 0, (hipStream_t)stream>>>(src, lds, dst, ldd, rows, cols,
                                                                                           lime_make_dropout(p, seed, site1),
                                                                                           lime_make_dropout(p, seed, site2));
         return lime_check_launch("dropout2_vec4_kernel");
@@ -236,10 +231,10 @@ extern "C" int lime_embed_pe_dropout_f32(const int32_t* ids, const float* table,
     const bool vec = dim % 4 == 0 && ld_table % 4 == 0 && ldo % 4 == 0 && (!pe || ld_pe % 4 == 0) &&
                      ((((uintptr_t)table) | ((uintptr_t)out) | ((uintptr_t)pe)) & 15) == 0;
     if (vec)
-        embed_pe_dropout_vec4_kernel<<<grid_for(rows * (dim / 4)), 256, 0, (hipStream_t)stream>>>(ids, table, ld_table, pe, ld_pe,
+        embed_pe_dropout_vec4_kernel<<<lime_grid_cap(rows * (dim / 4), 256, 16384), 256, 0, (hipStream_t)stream>>>(ids, table, ld_table, pe, ld_pe,
                                                                                                 period > 0 ? period : 1, out, ldo, rows, dim, d1, d2);
     else
-        embed_pe_dropout_kernel<<<grid_for(rows * dim), 256, 0, (hipStream_t)stream>>>(ids, table, ld_table, pe, ld_pe, period > 0 ? period : 1,
+        embed_pe_dropout_kernel<<<lime_grid_cap(rows * dim, 256, 16384), 256, 0, (hipStream_t)stream>>>(ids, table, ld_table, pe, ld_pe, period > 0 ? period : 1,
                                                                                      out, ldo, rows, dim, d1, d2);
     return lime_check_launch("embed_pe_dropout_kernel");
 }

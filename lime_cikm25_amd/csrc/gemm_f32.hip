@@ -68,13 +68,6 @@ __device__ __forceinline__ typename VecT<VEC>::T vzero() {
     return z;
 }
 
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == LIME_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == LIME_ACT_TANH) return tanhf(v);
-    if (act == LIME_ACT_SIGMOID) return lime_sigmoid(v);
-    return v;
-}
-
 // ---- buffer addressing ----------------------------------------------------------------------------------
 // Every global access goes through a buffer descriptor: a wave-uniform base (SGPRs) plus a 32-bit lane offset,
 // so a row costs one VGPR instead of a 64-bit pointer pair, and an out-of-range offset reads as zero / drops

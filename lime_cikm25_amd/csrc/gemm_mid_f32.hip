@@ -32,13 +32,6 @@ struct MidP {
     const int* m_dev;    // optional device-side row count (min(*m_dev, M) rows; workgroups of tiles beyond it exit)
 };
 
-__device__ __forceinline__ float act_fn(float v, int act) {
-    if (act == LIME_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == LIME_ACT_TANH) return tanhf(v);
-    if (act == LIME_ACT_SIGMOID) return lime_sigmoid(v);
-    return v;
-}
-
 constexpr int STAGE_MAX = (MB + NB) * KB;                            // floats
 
 // One TM x TN tile of problem p (tile index inside the problem); lds: the workgroup's NS * STAGE_MAX floats.  The tile shape is chosen
@@ -166,7 +159,7 @@ __device__ __forceinline__ void mid_tile(const MidP& p, const int tile, float* c
             for (int j = 0; j < 4; ++j) v[j] += p.bias[col + j];
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = act_fn(v[j], p.act);
+        for (int j = 0; j < 4; ++j) v[j] = apply_act(v[j], p.act);
         if (rrow >= 0) v += *reinterpret_cast<const f32x4*>(p.res + rrow * p.ldr + col);
         *reinterpret_cast<f32x4*>(crow + col) = v;
     }

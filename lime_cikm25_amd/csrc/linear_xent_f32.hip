@@ -21,19 +21,7 @@
 
 namespace {
 
-// four consecutive elements 4 j .. 4 j + 3 of a row of n floats (zeros behind the end)
-template <bool VEC>
-__device__ __forceinline__ f32x4 row_quad(const float* __restrict__ p, int j, int n) {
-    if (VEC) return *reinterpret_cast<const f32x4*>(p + 4 * (long)j);
-    f32x4 r;
-    const long e = 4 * (long)j;
-    r.x = e < n ? p[e] : 0.f;
-    r.y = e + 1 < n ? p[e + 1] : 0.f;
-    r.z = e + 2 < n ? p[e + 2] : 0.f;
-    r.w = e + 3 < n ? p[e + 3] : 0.f;
-    return r;
-}
-
+// the store that goes with row_quad (common.h): elements behind the end of the row are dropped
 template <bool VEC>
 __device__ __forceinline__ void store_quad(float* __restrict__ p, int j, int n, f32x4 v) {
     if (VEC) {
@@ -47,26 +35,11 @@ __device__ __forceinline__ void store_quad(float* __restrict__ p, int j, int n, 
     if (e + 3 < n) p[e + 3] = v.w;
 }
 
-__device__ __forceinline__ float fma_dot4(f32x4 a, f32x4 b, float acc) {
-    acc = fmaf(a.x, b.x, acc);
-    acc = fmaf(a.y, b.y, acc);
-    acc = fmaf(a.z, b.z, acc);
-    return fmaf(a.w, b.w, acc);
-}
-
-__device__ __forceinline__ f32x4 fma_axpy4(float a, f32x4 x, f32x4 acc) {
-    acc.x = fmaf(a, x.x, acc.x);
-    acc.y = fmaf(a, x.y, acc.y);
-    acc.z = fmaf(a, x.z, acc.z);
-    acc.w = fmaf(a, x.w, acc.w);
-    return acc;
-}
-
 // float4 group j of class c of w: from the LDS copy (rows of D4 whole groups) or from memory
 template <bool VEC, bool WLDS>
 __device__ __forceinline__ f32x4 w_quad(const float* __restrict__ w, const float* sm, int c, int j, int D, int D4) {
     if (WLDS) return *reinterpret_cast<const f32x4*>(sm + 4 * (c * D4 + j));
-    return row_quad<VEC>(w + (long)c * D, j, D);
+    return row_quad<VEC>(w + (long)c * D, (long)j, D);
 }
 
 // NQ: float4 groups of x a lane keeps (D <= 256 NQ), 0: the row is streamed.  CK: registers of logits a lane keeps (C <= 64 CK).
@@ -82,7 +55,7 @@ __global__ __launch_bounds__(256) void linear_xent_kernel(const float* __restric
     if (WLDS) {
         for (int e = threadIdx.x; e < C * D4; e += 256) {
             const int c = e / D4;
-            *reinterpret_cast<f32x4*>(sm + 4 * e) = row_quad<VEC>(w + (long)c * D, e - c * D4, D);
+            *reinterpret_cast<f32x4*>(sm + 4 * e) = row_quad<VEC>(w + (long)c * D, (long)(e - c * D4), D);
         }
         __syncthreads();
     }
@@ -95,7 +68,7 @@ __global__ __launch_bounds__(256) void linear_xent_kernel(const float* __restric
 #pragma unroll
             for (int q = 0; q < NX; ++q) {
                 const int j = lane + 64 * q;
-                xv[q] = j < D4 ? row_quad<VEC>(xr, j, D) : f32x4{0.f, 0.f, 0.f, 0.f};
+                xv[q] = j < D4 ? row_quad<VEC>(xr, (long)j, D) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
         // the logits, four classes in flight: class 64 k + cc lands on lane cc of zr[k]
@@ -119,7 +92,7 @@ __global__ __launch_bounds__(256) void linear_xent_kernel(const float* __restric
                     }
                 } else {
                     for (int j = lane; j < D4; j += 64) {
-                        const f32x4 xq = row_quad<VEC>(xr, j, D);
+                        const f32x4 xq = row_quad<VEC>(xr, (long)j, D);
 #pragma unroll
                         for (int u = 0; u < 4; ++u)
                             if (cc + u < cend) part[u] = fma_dot4(xq, w_quad<VEC, WLDS>(w, sm, c0 + u, j, D, D4), part[u]);

@@ -4,13 +4,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum_4(float v, float* red) {        // 256 threads, fixed order
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // ---------------------------------------------------------------------------------------------------
 // optimizer: sum of squares -> clip coefficient -> Adam   (trainer.py:33, 146-148)
 // ---------------------------------------------------------------------------------------------------
@@ -18,10 +11,8 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     __shared__ float red[4];
     float s = 0.f;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) s += g[e] * g[e];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // out[0] = total norm, out[1] = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); max_norm <= 0: 1
@@ -30,11 +21,9 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
     __shared__ float red[4];
     float s = 0.f;
     for (int e = threadIdx.x; e < n; e += 256) s += partial[e];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    s = block_sum(s, red);
     if (threadIdx.x == 0) {
-        const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
+        const float norm = sqrtf(s);
         out[0] = norm;
         out[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
     }
@@ -77,7 +66,7 @@ __global__ __launch_bounds__(256) void nll_softmax_kernel(const float* __restric
         if (dlogits)
             for (int j = 0; j < K; ++j) dlogits[(long)b * ldd + j] = (expf(x[j] - mx) * inv_s - (j == 0 ? 1.0f : 0.f)) * inv_b;
     }
-    const float tot = block_sum_4(part, red);
+    const float tot = block_sum(part, red);
     if (threadIdx.x == 0) *loss = tot * inv_b;
 }
 

@@ -1,6 +1,6 @@
-// Backward of the fused tail kernels of small_ops.hip (training step): each kernel recomputes
-// the few forward intermediates it needs (they are cheaper to redo than to keep) and writes every gradient of its stage in
-// one launch.  Reductions over the rows (bias / LayerNorm / affine2 gradients) go through per-workgroup partials in a caller
+// Backward of the fused tail kernels of news_tail_f32.hip and user_side_f32.hip (training step):
+// each kernel recomputes the few forward intermediates it needs (they are cheaper to redo than to keep) and writes every
+// gradient of its stage in one launch.  Reductions over the rows (bias / LayerNorm / affine2 gradients) go through per-workgroup partials in a caller
 // workspace and are summed in a fixed order by reduce_rows_kernel -- no atomics.
 //
 //   intent_fuse_bwd_kernel      layers.Attention over the k intents + cosine similarity + concat   (newsEncoders.py:355-371)
@@ -14,15 +14,6 @@
 namespace {
 
 constexpr int MAX_INTENT = 8;
-
-// sum over the 256 threads; `red` >= 4 floats of LDS; every thread gets the total
-__device__ __forceinline__ float bsum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // out[c] (+)= sum_s part[s * stride + c].  A workgroup owns 64 columns; its sixteen waves take the splits s = wave, wave + 16, ...
 // (coalesced 256-byte reads; with four waves a 768-split sum was 192 loads per lane: 18 us, five of them per training step) and the
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(256) void intent_fuse_bwd_kernel(const float* __res
             for (int kk = 0; kk < k; ++kk) {
                 float part = 0.f;
                 for (int j = threadIdx.x; j < A; j += 256) part += hid[kk * A + j] * aff2[j];
-                alpha[tb][kk] = bsum(part, red);
+                alpha[tb][kk] = block_sum(part, red);
                 mx = fmaxf(mx, alpha[tb][kk]);
             }
             float den = 0.f;
@@ -109,10 +100,10 @@ __global__ __launch_bounds__(256) void intent_fuse_bwd_kernel(const float* __res
             n2 += b * b;
             dsim += dcontent[m * ldc + D + d] * b;
         }
-        dot = bsum(dot, red);
-        n1 = bsum(n1, red);
-        n2 = bsum(n2, red);
-        dsim = bsum(dsim, red);
+        dot = block_sum(dot, red);
+        n1 = block_sum(n1, red);
+        n2 = block_sum(n2, red);
+        dsim = block_sum(dsim, red);
         const float nt_raw = sqrtf(n1), nb_raw = sqrtf(n2);
         const float nt = fmaxf(nt_raw, 1e-8f), nb = fmaxf(nb_raw, 1e-8f);
         const float cosv = dot / (nt * nb);
@@ -142,7 +133,7 @@ __global__ __launch_bounds__(256) void intent_fuse_bwd_kernel(const float* __res
                     part += dp * itn[kk * D + d];
                     dit[kk * D + d] = alpha[tb][kk] * dp;
                 }
-                dal[kk] = bsum(part, red);
+                dal[kk] = block_sum(part, red);
                 mix += alpha[tb][kk] * dal[kk];
             }
             for (int kk = 0; kk < k; ++kk) {
@@ -198,7 +189,7 @@ __global__ __launch_bounds__(256) void gate_ln_bwd_kernel(const float* __restric
             go[u] = in ? dout[r * D + d] : 0.f;
             part += v[u];
         }
-        const float mean = bsum(part, red) * inv_d;
+        const float mean = block_sum(part, red) * inv_d;
         part = 0.f;
 #pragma unroll
         for (int u = 0; u < DPT; ++u) {
@@ -206,7 +197,7 @@ __global__ __launch_bounds__(256) void gate_ln_bwd_kernel(const float* __restric
             v[u] = d < D ? v[u] - mean : 0.f;
             part += v[u] * v[u];
         }
-        const float rstd = 1.0f / sqrtf(bsum(part, red) * inv_d + eps);
+        const float rstd = 1.0f / sqrtf(block_sum(part, red) * inv_d + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int u = 0; u < DPT; ++u) {
@@ -220,8 +211,8 @@ __global__ __launch_bounds__(256) void gate_ln_bwd_kernel(const float* __restric
             v[u] = xh;                                            // keep xhat
             go[u] = gy;                                           // keep dout * gamma
         }
-        s1 = bsum(s1, red) * inv_d;
-        s2 = bsum(s2, red) * inv_d;
+        s1 = block_sum(s1, red) * inv_d;
+        s2 = block_sum(s2, red) * inv_d;
         float ds = 0.f;
 #pragma unroll
         for (int u = 0; u < DPT; ++u) {
@@ -236,7 +227,7 @@ __global__ __launch_bounds__(256) void gate_ln_bwd_kernel(const float* __restric
                 cb[u] += dpre;
             }
         }
-        ds = bsum(ds, red);
+        ds = block_sum(ds, red);
         if (threadIdx.x == 0) dscale[r] = ds;
     }
 #pragma unroll
@@ -281,30 +272,9 @@ __global__ __launch_bounds__(256) void interest_match_bwd_kernel(const float* __
         if (lane == 0) al[h] = part * scale;
     }
     __syncthreads();
-    float mx = -INFINITY;
-    for (int h = threadIdx.x; h < H; h += 256) mx = fmaxf(mx, al[h]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float den = 0.f;
-    for (int h = threadIdx.x; h < H; h += 256) {
-        const float e = expf(al[h] - mx);
-        al[h] = e;
-        den += e;
-    }
-    const float inv = 1.0f / bsum(den, red);
+    const float inv = block_softmax_terms(al, H, red);
     for (int h = threadIdx.x; h < H; h += 256) al[h] *= inv;
-    float w = 1.0f;
-    if (use_weight) {
-        const float r = remaining[bn];
-        if (use_penalty) {
-            w = lime_sigmoid(alpha_s * r);
-            w = (r >= 0.f ? 1.f : 0.f) * w + (r < 0.f ? 1.f : 0.f) * beta_s * w;
-        } else {
-            w = lime_sigmoid(alpha_s * fabsf(r));
-        }
-    }
+    const float w = use_weight ? lifetime_weight(remaining[bn], alpha_s, beta_s, use_penalty) : 1.0f;
     const float dbase = dlogits[bn] * w;
     __syncthreads();
     // u, d cand = dbase * u, d u = dbase * cand
@@ -331,7 +301,7 @@ __global__ __launch_bounds__(256) void interest_match_bwd_kernel(const float* __
     __syncthreads();
     float mix = 0.f;
     for (int h = threadIdx.x; h < H; h += 256) mix += al[h] * dal[h];
-    mix = bsum(mix, red);
+    mix = block_sum(mix, red);
     for (int h = threadIdx.x; h < H; h += 256) dal[h] = al[h] * (dal[h] - mix) * scale;        // d (kp . q), scale folded in
     __syncthreads();
     // d kp share and d qp
@@ -443,14 +413,10 @@ __global__ __launch_bounds__(256) void cand_attn_train_kernel(const float* __res
     {   // agg = softmax_j(pre)
         float mx = -INFINITY;
         for (int j = tid; j < H; j += 256) mx = fmaxf(mx, pre[j]);
-        mx = wave_max(mx);
-        __syncthreads();
-        if (lane == 0) red[wave] = mx;
-        __syncthreads();
-        mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        mx = block_max(mx, red);
         float den = 0.f;
         for (int j = tid; j < H; j += 256) den += expf(pre[j] - mx);
-        den = bsum(den, red);
+        den = block_sum(den, red);
         for (int j = tid; j < H; j += 256) pre[j] = expf(pre[j] - mx) / den;
     }
     __syncthreads();
@@ -461,7 +427,7 @@ __global__ __launch_bounds__(256) void cand_attn_train_kernel(const float* __res
     // ---- backward ------------------------------------------------------------------------------------------------
     float mix = 0.f;
     for (int j = tid; j < H; j += 256) mix += pre[j] * dagg[b * H + j];
-    mix = bsum(mix, red);
+    mix = block_sum(mix, red);
     for (int j = tid; j < H; j += 256) pre[j] = pre[j] * (dagg[b * H + j] - mix);             // d pre
     __syncthreads();
     // d qw[n] = sum_j dpre[j] sum_h ad[h, n, j]
@@ -541,7 +507,7 @@ __global__ __launch_bounds__(256) void sum_candidates_kernel(const float* __rest
 // reduce_rows_kernel over as many rows -- cost more than it saves)
 int persistent_grid(long rows) { return (int)(rows < 768 ? (rows < 1 ? 1 : rows) : 768); }
 
-// Backward of additive_pool_kernel (small_ops.hip; layers.Attention over the tokens of a title, layers.py:285-300 as called at
+// Backward of additive_pool_kernel (news_tail_f32.hip; layers.Attention over the tokens of a title, layers.py:285-300 as called at
 // newsEncoders.py:591-592): one workgroup per sequence recomputes alpha = softmax_t(mask(hidden_t . a2)), then
 //   dalpha_t = dout . x_t,   ds_t = alpha_t (dalpha_t - sum_u alpha_u dalpha_u)   (0 on masked tokens: their score is a constant),
 //   dx_t = alpha_t dout,     dhidden_t = ds_t a2,     da2[seq] = sum_t ds_t hidden_t   (per-sequence partial rows; the caller sums them).
@@ -571,25 +537,13 @@ __global__ __launch_bounds__(256) void additive_pool_bwd_kernel(const float* __r
         }
     }
     __syncthreads();
-    float mx = -INFINITY;
-    for (int t = threadIdx.x; t < S; t += 256) mx = fmaxf(mx, alpha[t]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float part = 0.f;
-    for (int t = threadIdx.x; t < S; t += 256) {
-        const float e = expf(alpha[t] - mx);
-        alpha[t] = e;
-        part += e;
-    }
-    const float inv = 1.0f / bsum(part, red);
+    const float inv = block_softmax_terms(alpha, S, red);
     float dotp = 0.f;
     for (int t = threadIdx.x; t < S; t += 256) {
         alpha[t] *= inv;
         dotp += alpha[t] * ds[t];
     }
-    const float dot = bsum(dotp, red);
+    const float dot = block_sum(dotp, red);
     for (int t = threadIdx.x; t < S; t += 256) ds[t] = (mask && mask[s * S + t] == 0) ? 0.f : alpha[t] * (ds[t] - dot);
     __syncthreads();
     for (int t = wave; t < S; t += 4) {

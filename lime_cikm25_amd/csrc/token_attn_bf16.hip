@@ -165,8 +165,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel
             // ---- transpose [head dim][query] -> [query][head dim] through the scratch, bf16 stores --------------------
 #pragma unroll
             for (int r = 0; r < 16; ++r) scr[fi * LDO + (r & 3) + 8 * (r >> 2) + 4 * fh] = o[r] * inv;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_fence();
             // lane -> (query row pair, two head-dim columns): 4-byte stores of two bf16
             {
                 const int cpair = fi & 15;                                // columns 2 cpair, 2 cpair + 1
@@ -187,8 +186,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 4 : 3) void token_attn_bf16_kernel
                         p.out[((long)seq * S + qt * 32 + it * 2 + fh) * p.ldo + p.n_head * hd + fi] = (unsigned short)0;
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_fence();
         }
         lds_barrier();                           // everyone is done with this group's LDS images
     }

@@ -53,14 +53,6 @@ struct AttnP {
 #endif
 };
 
-__device__ __forceinline__ void lds_fence() {
-    // LDS ops of one wave execute in order; drain lgkmcnt so that a tile written by some lanes is read back by
-    // others, and keep the compiler from moving memory ops across the point.  Deliberately NOT a workgroup-scope
-    // fence: that also waits vmcnt(0), i.e. for the K / V prefetch and the output stores still in flight.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // Two floats of row `r`, columns c, c+1 of a (sequence, head) operand; zero outside [0, rows) x [0, hd) (general path).
 __device__ __forceinline__ f32x2 load2(const float* src, long ld, int r, int c, int rows, int hd, bool vec2) {
     f32x2 v = {0.f, 0.f};
@@ -437,7 +429,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                 // ---- transpose [head dim][query] -> [query][head dim] through the scratch, store whole head rows ----
 #pragma unroll
                 for (int r = 0; r < 16; ++r) scr[fi * LDO + (r & 3) + 8 * (r >> 2) + krow] = o[r] * inv;
-                lds_fence();
+                wave_lds_fence();
                 if constexpr (BF) {
                     unsigned short* ob = reinterpret_cast<unsigned short*>(p.out);
                     if (fi < hd) {
@@ -462,7 +454,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 3 : (NT <= 4 ? 2 : 1)) void token_
                         if (qi < S) p.out[((long)seq * S + qi) * p.ldo + head * hd + fi] = scr[row * LDO + fi];
                     }
                 }
-                lds_fence();
+                wave_lds_fence();
                 LIME_STAMP(6)
             }
         }

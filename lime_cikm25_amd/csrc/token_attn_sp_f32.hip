@@ -38,11 +38,6 @@ struct SpAttnP {
     LimeDropout drop;    // thresh != 0 (the S <= 128 kernel): attention-probability dropout, element (pair, query, key) of the mask
 };
 
-__device__ __forceinline__ void lds_fence() {          // (see token_attn_f32.hip: wave-level, vmcnt left alone)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // NT: 32-token tiles per sequence (1, 2, 4); a group is 4 / NT (sequence, head) pairs = 128 key rows.  MAP: operand rows through
 // p.row_map (the compacted-sequence variant), the sequence count optionally from device memory.  VOC: p.row_map holds WORD IDS, the
 // rows of the [V, ld] product table p.q / p.k / p.v point into, and row t of ``pos`` ([S, ld], same column layout) is added.
@@ -285,7 +280,7 @@ __device__ __forceinline__ void token_attn_sp_body(const SpAttnP p, const float*
             // ---- transpose [head dim][query] -> [query][head dim] through the scratch, store whole head rows --------------
 #pragma unroll
             for (int r = 0; r < 16; ++r) scr[fi * LDO + (r & 3) + 8 * (r >> 2) + krow] = o[r] * inv;
-            lds_fence();
+            wave_lds_fence();
             if (fi < p.hd) {
                 if constexpr (VOC) {                     // one running pointer: sixteen hoisted row offsets would not fit beside the
                     float* op = p.out + ((long)seq * S + qt * 32 + fh) * p.ldo + head * p.hd + fi;      // positional registers
@@ -302,7 +297,7 @@ __device__ __forceinline__ void token_attn_sp_body(const SpAttnP p, const float*
                     }
                 }
             }
-            lds_fence();
+            wave_lds_fence();
         } else if constexpr (VOC && POS_LATE) {          // (G = 1: every group inside the loop is live; kept for the general case)
             if (group + (int)gridDim.x < n_group) { fetch_pos(group + gridDim.x); q_pos(group + gridDim.x); }
         }
@@ -472,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
         if (lse && fh == 0) lse[((long)seq * S + q0 + fi) * p.n_head + head] = m + log2f(sum);
 #pragma unroll
         for (int r = 0; r < 16; ++r) scr[fi * LDO + (r & 3) + 8 * (r >> 2) + krow] = o[r] * inv;
-        lds_fence();
+        wave_lds_fence();
         if (fi < p.hd) {
 #pragma unroll
             for (int it = 0; it < 16; ++it) {
@@ -480,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void token_attn_sp_long_kernel(const SpAttn
                 p.out[((long)seq * S + q0 + row) * p.ldo + head * p.hd + fi] = scr[row * LDO + fi];
             }
         }
-        lds_fence();
+        wave_lds_fence();
     }
 }
 

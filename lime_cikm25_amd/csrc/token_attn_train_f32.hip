@@ -936,8 +936,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
         const float* po = out + row * ldout;
         const float* pd = dout + row * ldo;
         for (int c = lane; c < width; c += 64) prod[wave][c] = po[c] * pd[c];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_fence();
         if (lane < n_head) {
             float d = 0.f;
             for (int c = 0; c < head_dim; ++c) d += prod[wave][lane * head_dim + c];
@@ -945,8 +944,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
             stats[e * 2] = lse[e];
             stats[e * 2 + 1] = d;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_fence();
     }
 }
 

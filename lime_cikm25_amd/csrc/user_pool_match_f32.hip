@@ -22,34 +22,6 @@
 
 namespace {
 
-// four consecutive elements 4 j .. 4 j + 3 of a row of n floats (zeros behind the end)
-template <bool VEC>
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, int j, int n) {
-    if (VEC) return *reinterpret_cast<const f32x4*>(p + 4 * j);
-    f32x4 r;
-    const int e = 4 * j;
-    r.x = e < n ? p[e] : 0.f;
-    r.y = e + 1 < n ? p[e + 1] : 0.f;
-    r.z = e + 2 < n ? p[e + 2] : 0.f;
-    r.w = e + 3 < n ? p[e + 3] : 0.f;
-    return r;
-}
-
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b, float acc) {
-    acc = fmaf(a.x, b.x, acc);
-    acc = fmaf(a.y, b.y, acc);
-    acc = fmaf(a.z, b.z, acc);
-    return fmaf(a.w, b.w, acc);
-}
-
-__device__ __forceinline__ f32x4 axpy4(float a, f32x4 x, f32x4 acc) {
-    acc.x = fmaf(a, x.x, acc.x);
-    acc.y = fmaf(a, x.y, acc.y);
-    acc.z = fmaf(a, x.z, acc.z);
-    acc.w = fmaf(a, x.w, acc.w);
-    return acc;
-}
-
 template <int W, bool VEC>
 __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict__ hidden, long ldh, const float* __restrict__ w2,
                                                           const float* __restrict__ x, long ldx,
@@ -73,11 +45,11 @@ __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict
     for (int h0 = w; h0 < H; h0 += 4 * W) {
         float part[4] = {0.f, 0.f, 0.f, 0.f};
         for (int j = lane; j < A4; j += 64) {
-            const f32x4 wv = load4<VEC>(w2, j, A);
+            const f32x4 wv = row_quad<VEC>(w2, j, A);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int h = h0 + u * W;
-                if (h < H) part[u] = dot4(load4<VEC>(hidden + (r0 + h) * ldh, j, A), wv, part[u]);
+                if (h < H) part[u] = fma_dot4(row_quad<VEC>(hidden + (r0 + h) * ldh, j, A), wv, part[u]);
             }
         }
 #pragma unroll
@@ -110,9 +82,9 @@ __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict
 #pragma unroll
             for (int k = 0; k < 8; ++k) xv[k] = *reinterpret_cast<const f32x4*>(xr + (long)(h + k) * ldx + 4 * c);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) acc = axpy4(sc[h + k], xv[k], acc);
+            for (int k = 0; k < 8; ++k) acc = fma_axpy4(sc[h + k], xv[k], acc);
         }
-        for (; h < H; ++h) acc = axpy4(sc[h], *reinterpret_cast<const f32x4*>(xr + (long)h * ldx + 4 * c), acc);
+        for (; h < H; ++h) acc = fma_axpy4(sc[h], *reinterpret_cast<const f32x4*>(xr + (long)h * ldx + 4 * c), acc);
         *reinterpret_cast<f32x4*>(us + 4 * c) = acc;
         if (user_rep != nullptr && live) *reinterpret_cast<f32x4*>(user_rep + row * D + 4 * c) = acc;
     }
@@ -123,7 +95,7 @@ __global__ __launch_bounds__(256) void pool_match_kernel(const float* __restrict
         const float* cp = cand + (row * N + n) * D;
         float part = 0.f;
         for (int c = lane; c < D4; c += 64)
-            part = dot4(*reinterpret_cast<const f32x4*>(us + 4 * c), *reinterpret_cast<const f32x4*>(cp + 4 * c), part);
+            part = fma_dot4(*reinterpret_cast<const f32x4*>(us + 4 * c), *reinterpret_cast<const f32x4*>(cp + 4 * c), part);
         const float base = wave_sum(part);
         if (lane == 0 && live)
             logits[row * N + n] = use_weight ? base * lifetime_weight(remaining[row * N + n], alpha_s, beta_s, use_penalty) : base;

@@ -105,7 +105,8 @@ def test_kernel_files_do_not_redefine_header_helpers():
             shared.setdefault(n, os.path.basename(path))
     assert {'make_rsrc', 'dma16', 'swz4', 'lane_here', 'u32x4', 'f32x4', 'lime_al16', 'split_frag', 'OOB', 'PPParams', 'LOG2E', 'mfma16',
             'buf_load1', 'live_count', 'lime_persistent_grid', 'conv_tile_product', 'two_stage_loop', 'ConvTap',
-            'CONV_STAGE'} <= set(shared), 'the scan lost its grip'
+            'CONV_STAGE', 'block_sum', 'block_max', 'block_softmax_terms', 'wave_lds_fence', 'lifetime_weight', 'lime_grid_cap',
+            'apply_act', 'row_quad', 'fma_dot4', 'fma_axpy4'} <= set(shared), 'the scan lost its grip'
     copies = []
     for path in sorted(glob.glob(os.path.join(CSRC, '*.hip'))):
         for n in sorted(_defined_names(open(path).read()) & set(shared)):
