@@ -1330,7 +1330,22 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * before any launch: LIME_ERR_BAD_ARG for a NULL scores / keys / output, bad dims, quota < 1, n_keys < 1, a drop mask with
  * drop_rows < 1, a short or misaligned workspace; LIME_ERR_UNSUPPORTED outside 1 <= k <= 128, C < 2^31, U <= 65535, n_keys <= 8192
  * (lime_list_plan's table size).  workspace: lime_topk_rows_quota_workspace(U, C) floats (0 for C <= 4096: workspace may be NULL),
- * 8-byte aligned; what it holds on entry does not matter. */
+ * 8-byte aligned; what it holds on entry does not matter.
+ *
+ * lime_mmr_rows_f32 (csrc/mmr_rows_f32.hip): maximal marginal relevance over a shortlist per row (Model.recommend(mmr_lambda=);
+ * recommend.mmr_select states it on the host).  scores fp32 [R, M] and ids int32 [R, M] (both contiguous): a row's shortlist, best
+ * first, as the top-k kernels return it, and the row of table fp32 [n, E] (leading dimension ld >= E) behind each entry.  An entry
+ * is DEAD when its id is outside [0, n) or its score is not finite: it is never taken and its table row is never read.  With
+ * first / last the first and last live entries of the row, rel[j] = (s[j] - s[last]) / (s[first] - s[last]) (0 for every j when
+ * the two are equal) and cos(j, i) the cosine of table rows ids[j] and ids[i] (0 when either norm is 0), a round takes the live,
+ * untaken j that maximises lam rel[j] - (1 - lam) max(0, max over the taken i of cos(j, i)), the lower j on equal values, until k
+ * are taken or no live entry is left.  picks int32 [R, k]: the taken j in the order taken, -1 behind the last.  lam = 1 is the plain
+ * order of the live entries (no table row is read), lam = 0 takes `first` first.  One workgroup per row: the inverse norms once,
+ * then per round the picked row, normalised, staged in LDS and its M dot products with the shortlist rows; fp32 throughout,
+ * fixed-order sums, no atomics, no workspace: a row's picks depend on its own operands alone, not on R, the row's position or the
+ * run.  Statuses before any launch, in this order: LIME_ERR_BAD_ARG for a NULL pointer; LIME_ERR_BAD_ARG for R < 0, M < 1, k < 1,
+ * k > M, n < 1, E < 1, ld < E, or lam outside [0, 1] or NaN; LIME_ERR_UNSUPPORTED for M > 128 (the top-k kernels' k limit),
+ * E % 4 != 0, R > 65535.  R == 0 is a success without a launch. */
 int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
                            const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D, float scale,
                            float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
@@ -1364,6 +1379,8 @@ int64_t lime_topk_rows_quota_workspace(int64_t U, int64_t C);
 int lime_topk_rows_quota_f32(const float* scores, int64_t ld, int64_t U, int64_t C, const int32_t* keys, int32_t n_keys, int32_t quota,
                              const uint8_t* drop, int64_t drop_rows, int32_t k, int32_t* positions, float* top_scores, float* workspace,
                              int64_t workspace_floats, void* stream);
+int lime_mmr_rows_f32(const float* scores, const int32_t* ids, int64_t R, int32_t M, const float* table, int64_t ld, int64_t n, int32_t E,
+                      float lam, int32_t k, int32_t* picks, void* stream);
 
 /* =====================================================================================================
  * Candidate lists (Model.score_lists / Model.recommend_lists): U users, each with its OWN list of candidates, as a CSR over P

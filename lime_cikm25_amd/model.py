@@ -584,7 +584,8 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                  cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None, quota_by='category'):
+                  cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None, quota_by='category',
+                  mmr_lambda=None, shortlist=None, similarity=None):
         """The k best news of the pool per user, on the device: ``score_pool`` (same arguments), then lime_topk_rows_f32 ->
         (positions int32 [U, k] into ``cand_index``, scores fp32 [U, k]).  Rows are in descending order of the score; equal scores
         (+0.0 and -0.0 are equal) go lower position first; a NaN ranks after every number, in position order.  With
@@ -596,9 +597,21 @@ class Model(nn.Module):
         are (lime_topk_rows_quota_f32; ``recommend.quota_topk`` states it on the host).  ``quota_by``: 'category', or 'topic' -- the
         (category, subCategory) pair; it is independent of what the user side groups by (``grouped_by()``), so a model without
         candidate-aware attention takes quotas too.  An excluded candidate uses no quota.  A corpus of more than 8192 groups is
-        refused (ValueError), as are a ``max_per_topic`` that is no integer >= 1 and an unknown ``quota_by``."""
+        refused (ValueError), as are a ``max_per_topic`` that is no integer >= 1 and an unknown ``quota_by``.
+
+        ``mmr_lambda`` = lam (a real in [0, 1]; None: no MMR, today's launches and bits): the slate is chosen by maximal marginal
+        relevance among the ``shortlist`` best (an integer in [k, 128], default min(128, max(k, 64)); under ``max_per_topic`` the
+        shortlist is the quota walk's, so the quota bounds it and MMR chooses within it).  Each round takes the shortlist entry of
+        the largest lam rel - (1 - lam) pen, rel the score scaled to [0, 1] over the shortlist and pen the largest cosine, 0 at the
+        least, to a news already taken (lime_mmr_rows_f32; ``recommend.mmr_select`` states it on the host); lam = 1 is the plain
+        slate.  The cosines are those of the rows of ``similarity`` (fp32 [n_news, E], E a multiple of 4, on the cache's device;
+        default: the content columns of ``news_cache`` -- the whole row, under 'gated' its first half).  The positions and scores
+        returned are the taken entries' in the order taken -- no longer descending --, -1 / -inf behind the last.  Refused
+        (ValueError): an ``mmr_lambda`` outside [0, 1], a ``shortlist`` outside [k, 128], a ``similarity`` of another type or shape,
+        and ``shortlist`` or ``similarity`` without ``mmr_lambda``."""
         return serving.recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                 cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by)
+                                 cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, mmr_lambda=mmr_lambda,
+                                 shortlist=shortlist, similarity=similarity)
 
     @torch.no_grad()
     def score_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
@@ -627,15 +640,17 @@ class Model(nn.Module):
     @torch.no_grad()
     def recommend_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                            cand_lifetime, slot_offsets, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None,
-                           quota_by='category'):
+                           quota_by='category', mmr_lambda=None, shortlist=None, similarity=None):
         """The k best news of the pool per user in every slot of a schedule: ``score_schedule`` (same arguments), then
         lime_topk_rows_f32 over the [S U, C] view of its scores (in chunks of slots that keep the kernel's 65535 rows) -> (positions
         int32 [S, U, k] into ``cand_index``, scores fp32 [S, U, k]); slot s holds what ``recommend`` returns at
         ``cand_freshness + slot_offsets[s]``, in its order and with its -1 / -inf for excluded or missing slots.  1 <= k <= 128.
         ``max_per_topic`` / ``quota_by``: as in ``recommend``, per (slot, user) row (lime_topk_rows_quota_f32 over the same view; the
-        [U, C] mask of ``exclude_history`` is handed over once, row s U + u reads its row u)."""
+        [U, C] mask of ``exclude_history`` is handed over once, row s U + u reads its row u).
+        ``mmr_lambda`` / ``shortlist`` / ``similarity``: as in ``recommend``, per (slot, user) row."""
         return serving.recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
-                                 cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=slot_offsets)
+                                 cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=slot_offsets,
+                                 mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity)
 
     @torch.no_grad()
     def score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
@@ -665,15 +680,17 @@ class Model(nn.Module):
     @torch.no_grad()
     def recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
                         cand_freshness, cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None,
-                        quota_by='category'):
+                        quota_by='category', mmr_lambda=None, shortlist=None, similarity=None):
         """The k best news of every user's OWN list, on the device: ``score_lists`` (same arguments), then lime_topk_segments_f32 ->
         (positions int32 [U, k] into the user's list -- candidate ``cand_index[cand_offsets[u] + positions[u, j]]`` --, scores fp32
         [U, k]) in ``recommend``'s order.  With ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is
         never returned; the trailing slots of a list with fewer than k candidates left (all k of an empty list) hold position -1 and
         score -inf.  1 <= k <= 128.
-        ``max_per_topic`` / ``quota_by``: as in ``recommend``, per list (lime_topk_segments_quota_f32)."""
+        ``max_per_topic`` / ``quota_by``: as in ``recommend``, per list (lime_topk_segments_quota_f32).
+        ``mmr_lambda`` / ``shortlist`` / ``similarity``: as in ``recommend``, per list."""
         return serving.recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
-                                       cand_freshness, cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by)
+                                       cand_freshness, cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by,
+                                       mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity)
 
     def _score_from_recurrence(self, behaviors, rows, rc, n_src, rows_per_forward):
         """score_behaviors under CNE from the recurrence cache: one encoder pass over the R candidates and the R . H history news of the

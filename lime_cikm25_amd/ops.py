@@ -1199,6 +1199,30 @@ def topk_segments_quota(scores, offsets, keys, quota, k, drop=None, n_keys=8192)
     return positions, top
 
 
+def mmr_rows(scores, ids, table, lam, k):
+    """``lime_mmr_rows_f32``: maximal marginal relevance over a shortlist per row (``recommend.mmr_select`` on the device).  scores
+    fp32 [R, M] and ids int32 [R, M] (device, contiguous): a row's shortlist, best first, and the row of ``table`` fp32 [n, E] (a
+    row-strided view is fine) behind each entry; an entry whose id is outside [0, n) or whose score is not finite is dead -> picks
+    int32 [R, k], the shortlist ranks in the order taken, -1 behind the last.  1 <= k <= M <= 128, E a multiple of 4, 0 <= lam <= 1."""
+    lib = _lib.load()
+    _mat(scores, 'scores')
+    _mat(table, 'table')
+    R, M = scores.shape
+    n, E = table.shape
+    k, lam = int(k), float(lam)
+    if not 1 <= k <= M or n < 1 or E < 1 or not 0.0 <= lam <= 1.0:
+        raise ValueError('mmr_rows needs 1 <= k <= M, a table of at least one row and column and 0 <= lam <= 1, got k = %d, M = %d, '
+                         'table %s, lam = %r' % (k, M, (n, E), lam))
+    if not scores.is_contiguous():
+        raise ValueError('scores must be contiguous, got strides %s' % (scores.stride(),))
+    _vec(ids, 'ids', R * M, dtype=torch.int32)
+    picks = torch.empty((R, k), dtype=torch.int32, device=scores.device)
+    if R == 0:                                                    # (an empty tensor has no address to hand over)
+        return picks
+    check(lib.lime_mmr_rows_f32(_p(scores), _p(ids), R, M, _p(table), _ld(table), n, E, lam, k, _p(picks), _stream()), 'lime_mmr_rows_f32')
+    return picks
+
+
 def row_scale(x, scale):
     lib = _lib.load()
     D = x.shape[-1]

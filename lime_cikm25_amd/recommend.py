@@ -241,3 +241,54 @@ def quota_topk_segments(scores, offsets, keys, k, quota, drop=None):
         if b > a:
             pos[u], top[u] = (r[0] for r in quota_topk(scores[None, a:b], keys[a:b], k, quota, None if drop is None else drop[None, a:b]))
     return pos, top
+
+
+# ---- diverse slates (Model.recommend* with mmr_lambda): maximal marginal relevance over a shortlist -------------------------------------
+def mmr_select(scores, ids, table, lam, k, return_gap=False):
+    """The host statement of ``ops.mmr_rows`` (lime_mmr_rows_f32), in fp64 -> picks int32 [R, k]: the shortlist ranks in the order
+    taken, -1 behind the last one.
+
+    ``scores`` [R, M]: a row's shortlist, best first, as the top-k kernels return it; ``ids`` int [R, M]: the row of ``table``
+    [n, E] behind each entry, -1 for an empty slot.  An entry is DEAD if its id is < 0 or >= n, or its score is not finite (an
+    excluded candidate carries -inf): it is never taken and never read from ``table``.  With ``first`` / ``last`` the first and last
+    live entries of the row: rel[j] = (s[j] - s[last]) / (s[first] - s[last]), 0 for every j when the two scores are equal;
+    cos(j, i): the cosine of rows ids[j] and ids[i], 0 when either norm is 0.  Each round takes the live, untaken j that maximises
+    v[j] = lam rel[j] - (1 - lam) pen[j], pen[j] = max(0, max over the taken i of cos(j, i)) -- 0 while nothing is taken, and a
+    negative cosine earns nothing --, the lower rank on equal v; until k are taken or no live entry is left.
+
+    Hence: lam = 1 takes the live entries in rank order (of a sorted shortlist: the plain top-k); lam = 0 takes ``first`` first
+    (every v is 0, the lowest rank wins); k >= the number of live entries returns all of them.
+    ``return_gap``: -> (picks, gap fp64 [R]): per row the smallest difference between a round's best and second-best v (inf where no
+    round had two candidates) -- a row whose gap is well above the rounding of another arithmetic has ONE right answer in it."""
+    scores = np.asarray(scores, dtype=np.float64)
+    ids = np.asarray(ids).astype(np.int64)
+    table = np.asarray(table, dtype=np.float64)
+    lam, k = float(lam), int(k)
+    if scores.ndim != 2 or ids.shape != scores.shape or table.ndim != 2:
+        raise ValueError('mmr_select needs scores and ids [R, M] and table [n, E], got %s, %s and %s' % (scores.shape, ids.shape, table.shape))
+    if k < 1 or not 0.0 <= lam <= 1.0:
+        raise ValueError('mmr_select needs k >= 1 and 0 <= lam <= 1, got k = %d, lam = %r' % (k, lam))
+    R, M = scores.shape
+    picks = np.full((R, k), -1, dtype=np.int32)
+    gaps = np.full(R, np.inf)
+    for r in range(R):
+        live = np.flatnonzero((ids[r] >= 0) & (ids[r] < table.shape[0]) & np.isfinite(scores[r]))
+        if live.size == 0:
+            continue
+        s = scores[r, live]
+        span = s[0] - s[-1]
+        rel = (s - s[-1]) / span if span != 0 else np.zeros(live.size)
+        x = table[ids[r, live]]
+        norm = np.sqrt((x * x).sum(axis=1))
+        unit = np.divide(x, norm[:, None], out=np.zeros_like(x), where=norm[:, None] > 0)
+        pen = np.zeros(live.size)
+        open_ = np.ones(live.size, dtype=bool)
+        for t in range(min(k, live.size)):
+            v = np.where(open_, lam * rel - (1.0 - lam) * pen, -np.inf)
+            best = int(np.argmax(v))                                          # the first of equal maxima: the lower rank
+            if open_.sum() > 1:
+                gaps[r] = min(gaps[r], v[best] - np.delete(v, best).max())
+            picks[r, t] = live[best]
+            open_[best] = False
+            pen = np.maximum(pen, unit @ unit[best])
+    return (picks, gaps) if return_gap else picks

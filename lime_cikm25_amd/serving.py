@@ -278,19 +278,78 @@ def _without(positions, gone):
     return torch.where(gone & (positions >= 0), torch.full_like(positions, -1), positions)
 
 
+Diversity = collections.namedtuple('Diversity', 'lam shortlist table')
+MMR_ROWS_MAX = 65535                  # lime_mmr_rows_f32's rows per launch
+
+
+def diversity(model, news_cache, k, mmr_lambda, shortlist, similarity):
+    """The refusals of ``mmr_lambda`` / ``shortlist`` / ``similarity`` (ValueError, before any launch) -> None without MMR, or
+    Diversity(lam, the shortlist's length -- default min(128, max(k, 64)) --, the similarity table fp32 [n_news, E] -- default the
+    content columns of ``news_cache``: the whole row, under 'gated' its first c columns as a column view)."""
+    if mmr_lambda is None:
+        if shortlist is not None or similarity is not None:
+            raise ValueError('shortlist and similarity are read with mmr_lambda alone: give mmr_lambda, or neither of them')
+        return None
+    if isinstance(mmr_lambda, bool) or not isinstance(mmr_lambda, numbers.Real) or not 0.0 <= mmr_lambda <= 1.0:
+        raise ValueError('mmr_lambda must be a real number in [0, 1] (or None: no MMR), got %r' % (mmr_lambda,))
+    k = int(k) if isinstance(k, numbers.Integral) and 1 <= k <= 128 else None     # (a bad k is check_grouped's to refuse)
+    if shortlist is None:
+        shortlist = min(128, max(k or 1, 64))
+    elif isinstance(shortlist, bool) or not isinstance(shortlist, numbers.Integral) or not (k or 1) <= shortlist <= 128:
+        raise ValueError('shortlist must be an integer in [k, 128] = [%s, 128], got %r' % (k if k else 'k', shortlist))
+    table = similarity
+    if table is None and news_cache.dim() == 2 and news_cache.shape[1] > 0 and not model.reads_content_mask:
+        gated = not model.plain and model.news_encoder.fusion_method == 'gated'
+        table = news_cache[:, :model.news_encoder.base_news_encoder.news_embedding_dim] if gated else news_cache
+    if table is not None:                                                         # (a bad cache is check_grouped's to refuse)
+        if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] != news_cache.shape[0]
+                or table.shape[1] < 1 or table.shape[1] % 4 or table.device != news_cache.device
+                or (table.shape[1] > 1 and table.stride(1) != 1)):
+            raise ValueError('similarity must be fp32 [n_news, E] = [%d, E] on the cache\'s device with E a multiple of 4 and unit column '
+                             'stride, got %s' % (news_cache.shape[0], '%s %s on %s' % (table.dtype, tuple(table.shape), table.device)
+                                                 if isinstance(table, torch.Tensor) else repr(table)))
+    return Diversity(float(mmr_lambda), int(shortlist), table)
+
+
+def _diverse(div, positions, top, ids, k):
+    """The tail of every recommend entry under MMR: ``positions`` / ``top`` [R, shortlist] the shortlist's (an entry that takes no
+    part holds position -1), ``ids`` int32 [R, shortlist] the similarity row of each entry (-1: none) -> (positions int32 [R, k],
+    scores fp32 [R, k]): ops.mmr_rows in launches of 65535 rows, then its picks turned into positions and score bits."""
+    top = top.contiguous()
+    picks = torch.cat([ops.mmr_rows(top[r0:r0 + MMR_ROWS_MAX], ids[r0:r0 + MMR_ROWS_MAX].contiguous(), div.table, div.lam, k)
+                       for r0 in range(0, top.shape[0], MMR_ROWS_MAX)]) if top.shape[0] else top.new_empty((0, k), dtype=torch.int32)
+    at, none = picks.clamp(min=0).long(), picks < 0
+    return (torch.gather(positions, 1, at).masked_fill(none, -1), torch.gather(top, 1, at).masked_fill(none, float('-inf')))
+
+
 _NO_SLOTS = object()         # (not None: recommend_schedule hands ``slot_offsets`` to torch.as_tensor whatever it is)
 
 
 def recommend(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime, k,
-              n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=_NO_SLOTS):
+              n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=_NO_SLOTS, mmr_lambda=None, shortlist=None,
+              similarity=None):
     """recommend -> (positions int32 [U, k], scores fp32 [U, k]); with ``slot_offsets`` recommend_schedule -> [S, U, k] each:
     ``score_pool``, then the top k of every row of its scores -- for a schedule the rows of the [S U, C] view, in chunks of slots that
-    keep the kernel's 65535 rows."""
+    keep the kernel's 65535 rows.  With ``mmr_lambda``: the top ``shortlist`` of every row the same way, then ``_diverse`` picks k of
+    them (the similarity row of a shortlist entry is its news id; -1 for an empty or excluded one)."""
     quota = topic_quota(corpus, max_per_topic, quota_by)
+    div = diversity(model, news_cache, k, mmr_lambda, shortlist, similarity)
     scores, gone = score_pool(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                               cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k,
                               slot_offsets=None if slot_offsets is _NO_SLOTS else torch.as_tensor(slot_offsets))
-    k, (U, C), whole = int(k), scores.shape[-2:], scores.dim() == 2    # whole: the unscheduled pool, its rows as they are, no copy
+    if div is not None:
+        positions, top = _top_rows(scores, gone, quota, cand_index, div.shortlist)
+        cidx = newsEncoders._i32(cand_index.to(scores.device))
+        ids = torch.where(positions >= 0, cidx[positions.clamp(min=0).long()], torch.full_like(positions, -1))
+        positions, top = _diverse(div, positions.view(-1, div.shortlist), top.view(-1, div.shortlist), ids.view(-1, div.shortlist), int(k))
+        return positions.view(scores.shape[:-1] + (int(k),)), top.view(scores.shape[:-1] + (int(k),))
+    return _top_rows(scores, gone, quota, cand_index, int(k))
+
+
+def _top_rows(scores, gone, quota, cand_index, k):
+    """The k best of every row of ``score_pool``'s scores [U, C] or [S, U, C], under ``quota`` where one is given -> (positions,
+    scores) [.., k]; an excluded candidate (``gone``) is never returned: its slot holds position -1."""
+    (U, C), whole = scores.shape[-2:], scores.dim() == 2               # whole: the unscheduled pool, its rows as they are, no copy
     step = max(1, 65535 // max(U, 1))
     rows = [scores] if whole else [scores[s0:s0 + step].view(-1, C) for s0 in range(0, scores.shape[0], step)]
     if quota is not None:                                      # the kernel drops the excluded: nothing to replace afterwards
@@ -376,16 +435,30 @@ def _in_own_history(hist_index, hist_mask, offsets, cidx, pairs_per_step=1 << 18
 
 
 def recommend_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
-                    cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by):
+                    cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, mmr_lambda=None, shortlist=None,
+                    similarity=None):
     """recommend_lists -> (positions int32 [U, k] into the user's list, scores fp32 [U, k]): ``score_lists``, then the top k of every
-    segment of its scores."""
+    segment of its scores.  With ``mmr_lambda``: the top ``shortlist`` of every segment the same way, then ``_diverse`` picks k of
+    them (the similarity row of a shortlist entry is the news id at its place in the user's list)."""
     quota = topic_quota(corpus, max_per_topic, quota_by)
+    div = diversity(model, news_cache, k, mmr_lambda, shortlist, similarity)
     scores, offsets, gone = score_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
                                         cand_index, cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
     U, k = hist_index.shape[0], int(k)
     if scores.numel() == 0:
         return (torch.full((U, k), -1, dtype=torch.int32, device=scores.device),
                 torch.full((U, k), float('-inf'), dtype=torch.float32, device=scores.device))
+    if div is None:
+        return _top_segments(scores, offsets, gone, quota, cand_index, k)
+    positions, top = _top_segments(scores, offsets, gone, quota, cand_index, div.shortlist)
+    pair = (offsets[:-1].unsqueeze(1) + positions.clamp(min=0).long()).clamp(max=scores.numel() - 1)
+    ids = torch.where(positions >= 0, newsEncoders._i32(cand_index.to(scores.device))[pair], torch.full_like(positions, -1))
+    return _diverse(div, positions, top, ids, k)
+
+
+def _top_segments(scores, offsets, gone, quota, cand_index, k):
+    """The k best of every segment of ``score_lists``' scores, under ``quota`` where one is given -> (positions, scores) [U, k]; an
+    excluded candidate (``gone``) is never returned: its slot holds position -1."""
     if quota is not None:
         return ops.topk_segments_quota(scores, offsets, quota.topic_of_news[cand_index.to(scores.device).long()], quota.q, k, drop=gone,
                                        n_keys=quota.n_keys)
