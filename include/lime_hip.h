@@ -1140,6 +1140,67 @@ int64_t lime_rank_metrics_workspace(int32_t n_imp);
 int lime_rank_metrics(const lime_rank_metrics_args* args, void* stream);
 
 /* =====================================================================================================
+ * What recommended slates are worth (util.evaluate_slates_on_device; recommend.slate_metrics states the rule on the host;
+ * csrc/slate_metrics.hip).  R slates of k slots: slot j < k of slate r is positions[r ldp + j] (int32 [R, ldp], k <= ldp: a prefix of
+ * a wider slate is evaluated in place).  With offsets int64 [R + 1] a position counts inside the slate's OWN list -- rows offsets[r] ..
+ * offsets[r + 1] - 1 of the [P] arrays, the impression's rows (every offset is clamped into [0, P]) --, without it inside ONE pool of P
+ * rows that all slates share.  news int32 [P]: the news id of a row, the row of table fp32 [n, E] (leading dimension ld) and of keys
+ * int32 [n] (0 <= key < n_keys; a key outside is no key).  labels u8 [P] (needs offsets), skip u8 [R], value fp32 [P], table and keys
+ * may each be NULL.  disc fp64 [k] = 1 / log2(p + 2).
+ *   A slot is FILLED when its position lies inside the list (the pool) and the news id behind it inside [0, n); every other slot
+ *   (-1 is the usual one) is empty: it earns nothing, nothing is read for it, and it still occupies its slot.
+ *   status int32 [R], lime_rank_metrics' rule in its order: 1 skipped, no labels or no rows; 3 a label outside {0, 1} among the
+ *   impression's rows; 2 one class only among them; 0 counted.  Ppos: the positives among the impression's rows.
+ *   per_slate fp64 [R, 8]:
+ *     0  nDCG@k   = (sum over the filled slots j with label 1 of disc[j]) / (sum_{p < min(k, Ppos)} disc[p])     } zeros unless
+ *     1  RR@k     = 1 / (1 + the first slot that holds a positive), 0 without one                                 } status is 0
+ *     2  hit@k    = 1 with a positive in a filled slot, else 0                                                    }
+ *     3  recall@k = the positives in filled slots / Ppos                                                          }
+ *     4  ILD      = 1 - mean over the pairs a < b of filled slots of cos(table[news_a], table[news_b]); cos is 0 when either norm
+ *                   is 0 (lime_mmr_rows_f32's rule); inverse norms and dot products fp32 in a fixed order, the pair sum fp64 in a
+ *                   fixed order; 0 with fewer than two filled slots or without a table
+ *     5  the distinct keys among the filled slots (0 without keys)
+ *     6  the filled slots
+ *     7  the mean of value over the filled slots, summed in fp64 in slot order (0 without value or without a filled slot)
+ *   sums fp64 [8], counts int64 [3]: counts[0] the slates with status 0 -- columns 0-3 are summed over them --, counts[1] the slates
+ *   with skip unset and >= 2 filled slots -- column 4 --, counts[2] those with skip unset and >= 1 filled slot -- columns 5-7.
+ * A wave per slate up to k = 16, a workgroup above (any R); the sums are a second launch over per_slate / status, one workgroup per output adding all slates in
+ * a fixed order and carrying the additions' rounding errors along (a sum is its terms' exact sum rounded once, whatever R): no
+ * atomics, no workspace, and reduce_blocks (workgroups of that launch, 0 = one per output) never changes a bit.
+ * Bitwise reproducible; a slate's row depends on its own operands alone, not on R, its place in the batch or the grid.
+ * Statuses before any launch, in this order: LIME_ERR_BAD_ARG for a NULL args / positions / news / disc / per_slate / status / sums /
+ * counts; for labels without offsets; for R < 0, P < 0, k < 1, k > ldp, E < 0, ld < E, n < 1; for a table with E < 1 or keys with
+ * n_keys < 1; for reserved != 0 or reduce_blocks < 0; LIME_ERR_UNSUPPORTED for k > 128 or E % 4 != 0.  R == 0 is a success without a
+ * launch that leaves zero sums and counts. */
+typedef struct {
+    const int32_t* positions;
+    const int64_t* offsets;
+    const int32_t* news;
+    const uint8_t* labels;
+    const uint8_t* skip;
+    const float* value;
+    const float* table;
+    const int32_t* keys;
+    const double* disc;
+    double* per_slate;
+    int32_t* status;
+    double* sums;
+    int64_t* counts;
+    int64_t R;
+    int64_t P;
+    int64_t ldp;
+    int64_t ld;
+    int64_t n;
+    int32_t k;
+    int32_t E;
+    int32_t n_keys;
+    int32_t reduce_blocks;
+    int32_t reserved;     /* must be 0 */
+} lime_slate_metrics_args;
+
+int lime_slate_metrics_f32(const lime_slate_metrics_args* args, void* stream);
+
+/* =====================================================================================================
  * The epoch's negative sampling on the device (Train_Dataset.negative_sampling, dataset.py:42-77; csrc/negative_sample.hip).  The
  * non-clicked news of the N train records are resident as CSR: offsets int64 [N + 1] (record i owns entries offsets[i] ..
  * offsets[i + 1] - 1; every offset is clamped into [0, nnz] by the kernel), neg_index int32 [nnz], neg_lifetime fp32 [nnz]; per

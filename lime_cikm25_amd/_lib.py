@@ -49,6 +49,7 @@ InprojBf16Args = STRUCTS['lime_inproj_bf16_args']
 CopyDesc = STRUCTS['lime_copy_desc']
 GatherDesc = STRUCTS['lime_gather_desc']
 RankMetricsArgs = STRUCTS['lime_rank_metrics_args']
+SlateMetricsArgs = STRUCTS['lime_slate_metrics_args']
 ConvPoolArgs = STRUCTS['lime_conv_pool_args']
 
 ABI_VERSION = CONSTANTS['LIME_ABI_VERSION']

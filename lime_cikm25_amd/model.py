@@ -692,6 +692,14 @@ class Model(nn.Module):
                                        cand_freshness, cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by,
                                        mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity)
 
+    @torch.no_grad()
+    def evaluate_slates(self, behaviors, indices, labels, settings, k=10, **kw):
+        """``util.evaluate_slates_on_device`` of this model: the dev split scored once, then every selection setting of ``settings``
+        (``recommend_lists``' ``max_per_topic`` / ``mmr_lambda`` ..) evaluated on those scores -- nDCG@k, RR, hit, recall against
+        intra-list distance, distinct topics, fill and a value of the caller's -> (the pass's four metrics, one dict per setting)."""
+        from . import util
+        return util.evaluate_slates_on_device(self, behaviors, indices, labels, settings, k=k, **kw)
+
     def _score_from_recurrence(self, behaviors, rows, rc, n_src, rows_per_forward):
         """score_behaviors under CNE from the recurrence cache: one encoder pass over the R candidates and the R . H history news of the
         rows (flat order: candidates, then histories, as ``_forward_impl`` encodes them), paired per chunk of rows_per_forward rows,

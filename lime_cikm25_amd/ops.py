@@ -2645,6 +2645,98 @@ def rank_metrics(scores, labels, offsets, skip=None, rank_blocks=0, reduce_block
     return RankMetrics(ranks, per_imp, status, sums, count)
 
 
+class SlateMetrics:
+    """Result of ``slate_metrics``: ``per_slate`` fp64 [R, 8] (nDCG@k, RR@k, hit@k, recall@k, ILD, distinct keys, filled slots, mean
+    value), ``status`` int32 [R] (0 counted, 1 skipped / no labels / no rows, 2 one class only, 3 a label outside {0, 1}), ``sums``
+    fp64 [8] and ``counts`` int64 [3] (the slates behind the sums of columns 0-3, of column 4, of columns 5-7) -- all device tensors."""
+    __slots__ = ('per_slate', 'status', 'sums', 'counts')
+
+    def __init__(self, per_slate, status, sums, counts):
+        self.per_slate, self.status, self.sums, self.counts = per_slate, status, sums, counts
+
+
+_SLATE_DISC = {}
+
+
+def _slate_discounts(device, k):
+    """1 / log2(p + 2), p = 0 .. k - 1, with numpy's bits: the first k of one table of 128 per device."""
+    key = str(device)
+    if key not in _SLATE_DISC:
+        import numpy as np
+        _SLATE_DISC[key] = torch.from_numpy(1.0 / np.log2(np.arange(128) + 2.0)).to(device)
+    return _SLATE_DISC[key][:k]
+
+
+def slate_metrics(positions, k, offsets, news, labels=None, skip=None, value=None, table=None, keys=None, n=None, n_keys=None,
+                  reduce_blocks=0):
+    """``lime_slate_metrics_f32``: what the slates ``positions`` int32 [R, ldp] (device; unit column stride, a row-strided view is
+    fine; the first k <= ldp slots count) are worth (``recommend.slate_metrics`` on the device).  ``offsets`` int64 [R + 1] (device):
+    a position counts inside the slate's own list, rows offsets[r] .. offsets[r + 1] - 1 of news int32 [P] / labels uint8 [P] /
+    value fp32 [P]; None: inside one pool of P rows.  skip uint8 / bool [R]; table fp32 [n, E] (a row-strided view is fine, E a
+    multiple of 4); keys int32 [n] with 0 <= key < n_keys.  ``n`` defaults to the rows of table / keys.  Every check is made on the
+    host before the launch (the offsets' VALUES are not read: the kernel clamps them into [0, P]).  Returns a ``SlateMetrics``.
+    ``reduce_blocks``: workgroups of the sums' launch (0: default); no bit of the result depends on it."""
+    if isinstance(positions, torch.Tensor) and positions.dim() == 2 and positions.shape[0] == 0:
+        positions = positions.new_empty(positions.shape)           # (no slates: whatever strides the empty tensor carries)
+    _mat(positions, 'positions', dtype=torch.int32)
+    R, ldp = positions.shape
+    k = int(k)
+    if not 1 <= k <= min(ldp, 128):
+        raise ValueError('slate_metrics needs 1 <= k <= min(ldp, 128) = %d, got k = %d' % (min(ldp, 128), k))
+    P = _vec(news, 'news', dtype=torch.int32).numel()
+    if offsets is None:
+        if labels is not None:
+            raise ValueError('labels need offsets: a pool has no impression to count the positives of')
+    else:
+        _vec(offsets, 'offsets', R + 1, dtype=torch.int64)
+    _vec(labels, 'labels', P, dtype=torch.uint8)
+    _vec(value, 'value', P)
+    sk = None
+    if skip is not None:
+        sk = _vec(_mask_u8(skip, 'skip'), 'skip', R, dtype=torch.uint8)
+    E = ld = 0
+    if table is not None:
+        _mat(table, 'table')
+        E, ld = table.shape[1], _ld(table)
+        if table.shape[0] < 1 or E < 1 or E % 4:
+            raise ValueError('table must be [n, E] with n >= 1 and E a positive multiple of 4, got %s' % (tuple(table.shape),))
+    if keys is not None:
+        _vec(keys, 'keys', dtype=torch.int32)
+        n_keys = 8192 if n_keys is None else int(n_keys)
+        if n_keys < 1:
+            raise ValueError('n_keys must be >= 1, got %d' % n_keys)
+    rows = {t.shape[0] for t in (table, keys) if t is not None}
+    if len(rows) > 1:
+        raise ValueError('table and keys must have one row per news alike, got %d and %d' % (table.shape[0], keys.numel()))
+    n = int(n) if n is not None else (rows.pop() if rows else 2 ** 31 - 1)
+    if n < 1 or (rows and n > min(rows)):
+        raise ValueError('n = %d must be in [1, the rows of table / keys]' % n)
+    if reduce_blocks < 0:
+        raise ValueError('reduce_blocks must be >= 0')
+    for t, name in ((news, 'news'), (offsets, 'offsets'), (labels, 'labels'), (sk, 'skip'), (value, 'value'), (table, 'table'),
+                    (keys, 'keys')):
+        if t is not None and t.device != positions.device:
+            raise ValueError('%s is on %s, positions on %s' % (name, t.device, positions.device))
+    lib = _lib.load()
+    dev = positions.device
+    per_slate = torch.empty((R, 8), dtype=torch.float64, device=dev)
+    status = torch.empty(R, dtype=torch.int32, device=dev)
+    if R == 0:                                                    # (an empty tensor has no address to hand over)
+        return SlateMetrics(per_slate, status, torch.zeros(8, dtype=torch.float64, device=dev), torch.zeros(3, dtype=torch.int64, device=dev))
+    sums = torch.empty(8, dtype=torch.float64, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    disc = _slate_discounts(dev, k)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = _lib.SlateMetricsArgs()
+    a.positions, a.offsets, a.news, a.labels, a.skip = ptr(positions), ptr(offsets), ptr(news), ptr(labels), ptr(sk)
+    a.value, a.table, a.keys, a.disc = ptr(value), ptr(table), ptr(keys), ptr(disc)
+    a.per_slate, a.status, a.sums, a.counts = ptr(per_slate), ptr(status), ptr(sums), ptr(counts)
+    a.R, a.P, a.ldp, a.ld, a.n = R, P, _ld(positions), ld, n
+    a.k, a.E, a.n_keys, a.reduce_blocks, a.reserved = k, E, (n_keys if keys is not None else 0), int(reduce_blocks), 0
+    check(lib.lime_slate_metrics_f32(ctypes.byref(a), _stream()), 'lime_slate_metrics_f32')
+    return SlateMetrics(per_slate, status, sums, counts)
+
+
 # ---- the epoch's negative sampling from the resident train tables (csrc/negative_sample.hip) --------------------------------------------
 def negative_sample(offsets, neg_index, neg_lifetime, pos_index, pos_lifetime, freshness, K, seed, epoch, inclusive=False,
                     cand_index=None, cand_freshness=None, cand_lifetime=None):

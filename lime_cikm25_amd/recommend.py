@@ -292,3 +292,111 @@ def mmr_select(scores, ids, table, lam, k, return_gap=False):
             open_[best] = False
             pen = np.maximum(pen, unit @ unit[best])
     return (picks, gaps) if return_gap else picks
+
+
+# ---- what a slate is worth (util.evaluate_slates_on_device): accuracy against the labels, diversity of the slots ------------------------
+SLATE_COLUMNS = ('ndcg', 'rr', 'hit', 'recall', 'ild', 'topics', 'filled', 'value')
+
+
+def slate_metrics(positions, k, offsets, news, labels=None, skip=None, value=None, table=None, keys=None, n=None, n_keys=None):
+    """The host statement of ``ops.slate_metrics`` (lime_slate_metrics_f32), in fp64 -> (per_slate fp64 [R, 8], status int32 [R],
+    sums fp64 [8], counts int64 [3]).
+
+    ``positions`` int [R, >= k]: slot j < k of slate r.  With ``offsets`` [R + 1] a position counts inside the slate's own list, rows
+    offsets[r] .. offsets[r + 1] - 1 of the [P] arrays ``news`` / ``labels`` / ``value`` (the impression's rows); with ``offsets``
+    None inside one pool of P rows that all slates share.  ``news`` [P]: the news id of a row -- the row of ``table`` [n, E] and of
+    ``keys`` [n] (a key outside [0, n_keys) is no key).  A slot is FILLED when its position lies inside the list (the pool) and the
+    news id behind it inside [0, n); every other slot (-1) is empty: it earns nothing and still occupies its slot.
+
+    status: 1 skipped (``skip`` [R]), no ``labels`` or no rows; else 3 a label outside {0, 1} among the impression's rows; else 2 one
+    class only among them; else 0.  With Ppos the positives among the impression's rows and disc[p] = 1 / log2(p + 2), the columns:
+    0 nDCG@k = (sum over the filled slots j with label 1 of disc[j]) / (sum_{p < min(k, Ppos)} disc[p]); 1 RR@k = 1 / (1 + the first
+    slot that holds a positive) or 0; 2 hit@k; 3 recall@k = hits / Ppos -- zeros unless status is 0; 4 ILD = 1 - the mean over the
+    pairs a < b of filled slots of cos(table[news_a], table[news_b]), cos 0 when either norm is 0, defined with >= 2 filled slots;
+    5 the distinct keys among the filled slots; 6 the filled slots; 7 the mean of ``value`` over them.  A column whose input is None
+    or that is not defined for the slate is 0.  Sums in slot order, one addition after the other (the kernel's order for columns
+    0-3 and 7).  counts: the slates with status 0 (they feed the sums of columns 0-3), the slates not skipped with >= 2 filled slots
+    (column 4), with >= 1 (columns 5-7)."""
+    pos = np.asarray(positions).astype(np.int64)
+    k = int(k)
+    if pos.ndim != 2 or not 1 <= k <= pos.shape[1]:
+        raise ValueError('slate_metrics needs positions [R, ldp] and 1 <= k <= ldp, got %s and k = %d' % (pos.shape, k))
+    if labels is not None and offsets is None:
+        raise ValueError('labels need offsets: a pool has no impression to count the positives of')
+    R = pos.shape[0]
+    pos = pos[:, :k]
+    news = np.asarray(news).reshape(-1).astype(np.int64)
+    P = news.shape[0]
+    table = None if table is None else np.asarray(table, dtype=np.float64)
+    keys = None if keys is None else np.asarray(keys).reshape(-1).astype(np.int64)
+    if n is None:
+        n = table.shape[0] if table is not None else keys.shape[0] if keys is not None else (int(news.max()) + 1 if P else 1)
+    if offsets is None:
+        beg, length = np.zeros(R, dtype=np.int64), np.full(R, P, dtype=np.int64)
+    else:
+        off = np.clip(np.asarray(offsets).reshape(-1).astype(np.int64), 0, P)
+        if off.shape[0] != R + 1:
+            raise ValueError('offsets must have R + 1 = %d entries, got %d' % (R + 1, off.shape[0]))
+        beg = off[:-1]
+        length = np.maximum(off[1:], beg) - beg
+    inside = (pos >= 0) & (pos < length[:, None])
+    row = np.where(inside, beg[:, None] + pos, 0)
+    nid = news[row] if P else np.zeros_like(row)
+    filled = inside & (nid >= 0) & (nid < n)
+    nid = np.where(filled, nid, 0)
+    m = filled.sum(axis=1)
+    skipped = np.zeros(R, dtype=bool) if skip is None else np.asarray(skip).reshape(-1).astype(bool)
+    per = np.zeros((R, 8), dtype=np.float64)
+    status = np.ones(R, dtype=np.int32)
+    disc = 1.0 / np.log2(np.arange(k) + 2.0)
+    if labels is not None:
+        lab = np.asarray(labels).reshape(-1).astype(np.int64)
+        seg = np.repeat(np.arange(R), length)
+        rows = np.concatenate([np.arange(b, b + c) for b, c in zip(beg, length)]) if R else np.zeros(0, dtype=np.int64)
+        n_pos = np.bincount(seg, weights=lab[rows] != 0, minlength=R).astype(np.int64)
+        bad = np.bincount(seg, weights=(lab[rows] < 0) | (lab[rows] > 1), minlength=R) > 0
+        status = np.where(skipped | (length == 0), 1, np.where(bad, 3, np.where((n_pos == 0) | (n_pos == length), 2, 0))).astype(np.int32)
+        ok = status == 0
+        gain = filled & (lab[row] != 0) if P else np.zeros_like(filled)
+        dcg, ideal, hits = np.zeros(R), np.zeros(R), np.zeros(R, dtype=np.int64)
+        first = np.full(R, -1, dtype=np.int64)
+        for j in range(k):                                                    # slot order, one addition after the other
+            dcg = np.where(gain[:, j], dcg + disc[j], dcg)
+            ideal = np.where(j < n_pos, ideal + disc[j], ideal)
+            hits += gain[:, j]
+            first = np.where((first < 0) & gain[:, j], j, first)
+        per[ok, 0] = dcg[ok] / ideal[ok]
+        per[ok, 1] = np.where(first[ok] >= 0, 1.0 / (1.0 + np.maximum(first[ok], 0)), 0.0)
+        per[ok, 2] = hits[ok] > 0
+        per[ok, 3] = hits[ok] / n_pos[ok].astype(np.float64)
+    if table is not None:
+        step = max(1, (1 << 22) // max(1, k * table.shape[1]))
+        upper = np.triu(np.ones((k, k), dtype=bool), 1)
+        for r0 in range(0, R, step):
+            f = filled[r0:r0 + step]
+            x = table[nid[r0:r0 + step]] * f[:, :, None]                      # [rows, k, E]; an empty slot: zeros
+            norm = np.sqrt((x * x).sum(axis=2))
+            unit = np.divide(x, norm[:, :, None], out=np.zeros_like(x), where=norm[:, :, None] > 0)
+            cos = unit @ unit.transpose(0, 2, 1)
+            pairs = m[r0:r0 + step] * (m[r0:r0 + step] - 1) // 2
+            total = (cos * upper).sum(axis=(1, 2))
+            per[r0:r0 + step, 4] = np.where(pairs > 0, 1.0 - total / np.maximum(pairs, 1), 0.0)
+    if keys is not None:
+        key = np.where(filled, keys[nid], -1)
+        if n_keys is not None:
+            key = np.where(key < int(n_keys), key, -1)
+        for j in range(k):
+            seen = (key[:, :j] == key[:, j:j + 1]).any(axis=1) if j else np.zeros(R, dtype=bool)
+            per[:, 5] += (key[:, j] >= 0) & ~seen
+    per[:, 6] = m
+    if value is not None:
+        val = np.asarray(value, dtype=np.float32).reshape(-1).astype(np.float64)
+        picked = np.where(filled, val[row], 0.0) if P else np.zeros(filled.shape)
+        total = np.zeros(R)
+        for j in range(k):
+            total = np.where(filled[:, j], total + picked[:, j], total)
+        per[:, 7] = np.where(m > 0, total / np.maximum(m, 1), 0.0)
+    sets = (status == 0, ~skipped & (m >= 2), ~skipped & (m >= 1))
+    counts = np.array([s.sum() for s in sets], dtype=np.int64)
+    sums = np.array([per[sets[0 if c < 4 else 1 if c == 4 else 2], c].sum() for c in range(8)], dtype=np.float64)
+    return per, status, sums, counts

@@ -282,6 +282,15 @@ Diversity = collections.namedtuple('Diversity', 'lam shortlist table')
 MMR_ROWS_MAX = 65535                  # lime_mmr_rows_f32's rows per launch
 
 
+def content_columns(model, news_cache):
+    """The default similarity table: the content columns of ``news_cache`` -- the whole row, under 'gated' its first c columns as a
+    column view -- or None where the cache has none to offer (CNE, a malformed cache)."""
+    if news_cache.dim() != 2 or news_cache.shape[1] == 0 or model.reads_content_mask:
+        return None
+    gated = not model.plain and model.news_encoder.fusion_method == 'gated'
+    return news_cache[:, :model.news_encoder.base_news_encoder.news_embedding_dim] if gated else news_cache
+
+
 def diversity(model, news_cache, k, mmr_lambda, shortlist, similarity):
     """The refusals of ``mmr_lambda`` / ``shortlist`` / ``similarity`` (ValueError, before any launch) -> None without MMR, or
     Diversity(lam, the shortlist's length -- default min(128, max(k, 64)) --, the similarity table fp32 [n_news, E] -- default the
@@ -297,10 +306,7 @@ def diversity(model, news_cache, k, mmr_lambda, shortlist, similarity):
         shortlist = min(128, max(k or 1, 64))
     elif isinstance(shortlist, bool) or not isinstance(shortlist, numbers.Integral) or not (k or 1) <= shortlist <= 128:
         raise ValueError('shortlist must be an integer in [k, 128] = [%s, 128], got %r' % (k if k else 'k', shortlist))
-    table = similarity
-    if table is None and news_cache.dim() == 2 and news_cache.shape[1] > 0 and not model.reads_content_mask:
-        gated = not model.plain and model.news_encoder.fusion_method == 'gated'
-        table = news_cache[:, :model.news_encoder.base_news_encoder.news_embedding_dim] if gated else news_cache
+    table = similarity if similarity is not None else content_columns(model, news_cache)
     if table is not None:                                                         # (a bad cache is check_grouped's to refuse)
         if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[0] != news_cache.shape[0]
                 or table.shape[1] < 1 or table.shape[1] % 4 or table.device != news_cache.device
@@ -444,7 +450,17 @@ def recommend_lists(model, news_cache, corpus, hist_index, hist_mask, user_fresh
     div = diversity(model, news_cache, k, mmr_lambda, shortlist, similarity)
     scores, offsets, gone = score_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
                                         cand_index, cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
-    U, k = hist_index.shape[0], int(k)
+    return select_segments(scores, offsets, gone, quota, div, cand_index, k)
+
+
+def select_segments(scores, offsets, gone, quota, div, cand_index, k):
+    """The slates of a score buffer, the tail of ``recommend_lists`` and the selection ``util.evaluate_slates_on_device`` sweeps:
+    ``scores`` fp32 [P] and ``offsets`` int64 [U + 1] (device) the lists' CSR, ``gone`` bool [P] or None the excluded pairs, ``quota``
+    a TopicQuota or None, ``div`` a Diversity or None, ``cand_index`` [P] the news of every pair -> (positions int32 [U, k] into the
+    user's list, scores fp32 [U, k]): the top k of every segment, under the quota where one is given; with ``div`` the top
+    ``div.shortlist`` the same way, of which ``_diverse`` picks k (the similarity row of a shortlist entry is the news id at its
+    place in the user's list).  Without a pair every slot holds -1 / -inf."""
+    U, k = offsets.numel() - 1, int(k)
     if scores.numel() == 0:
         return (torch.full((U, k), -1, dtype=torch.int32, device=scores.device),
                 torch.full((U, k), float('-inf'), dtype=torch.float32, device=scores.device))

@@ -28,7 +28,7 @@ def _mkdir(path):
 
 class Trainer:
     def __init__(self, model, config, corpus, run_index=0, truth_file=None, device_corpus=None, cached_eval=True, device_eval=False,
-                 device_sampling=False, cne_recurrence_cache=False, grouped_eval=False):
+                 device_sampling=False, cne_recurrence_cache=False, grouped_eval=False, slate_eval=None):
         """``truth_file``: the dev truth file of config.py:262-276 ("<impression> [labels]" lines).  Without one it is written
         (as the reference's Config does at start-up) to ``<dev_res_dir>/../ref/truth-<dataset>.txt`` from ``corpus.dev_labels``
         (formats.build_corpus attaches them); a corpus without labels and no file is refused here, before any training.
@@ -45,10 +45,22 @@ class Trainer:
         computes the same table from (seed, epoch): no broadcast is needed.  Off by default: nothing changes without it.
         ``cne_recurrence_cache``: under the CNE content encoder both cached dev passes build the per-news recurrence cache once per
         epoch and score from it (util.compute_scores_cached / evaluate_cached_on_device, ``recurrence_cache``); off by default.
+        ``slate_eval``: dict(settings=[...], k=10, value=None) -- the dev pass of an epoch goes through
+        util.evaluate_slates_on_device: the same rank file and metrics, and the sweep's per-setting dicts are kept on
+        ``last_slate_metrics`` and printed, one line per setting.  It needs ``device_eval`` (ValueError without, and where the device
+        pass does not apply); its settings are refused here, before any training.  None (default): the Trainer as it was.
 
         Under torch.distributed (WORLD_SIZE in the environment) the process group is initialised and the device selected
         FIRST, so that TrainStep's broadcast of rank 0's parameters really runs (DistributedDataParallel does that at
         construction, trainer.py:256), and each rank steps on ``config.batch_size // world`` rows (trainer.py:254-255)."""
+        self.slate_eval = None
+        if slate_eval is not None:                                             # refused first: nothing has touched the device yet
+            if not device_eval:
+                raise ValueError('slate_eval evaluates the slates on the scores of the device dev pass: it needs device_eval=True')
+            unknown = sorted(set(slate_eval) - {'settings', 'k', 'value'}) if isinstance(slate_eval, dict) else None
+            if unknown is None or unknown or 'settings' not in slate_eval:
+                raise ValueError('slate_eval must be dict(settings=[...], k=10, value=None), got %r' % (slate_eval,))
+            self.slate_eval = dict(settings=list(slate_eval['settings']), k=slate_eval.get('k', 10), value=slate_eval.get('value'))
         self.model, self.config, self.corpus, self.run_index = model, config, corpus, run_index
         self.rank, self.world = 0, 1
         if 'WORLD_SIZE' in os.environ and int(os.environ['WORLD_SIZE']) > 1:
@@ -86,6 +98,11 @@ class Trainer:
         self.dev = DeviceBehaviors.from_devtest(self.dc, corpus, 'dev')
         self.cne_recurrence_cache = bool(cne_recurrence_cache)
         self.grouped_eval = bool(grouped_eval)
+        self.last_slate_metrics = None
+        if self.slate_eval is not None:
+            if not self.device_eval:
+                raise ValueError('slate_eval needs the device dev pass, which serves a corpus with dev_labels under lifetime_type user_topic')
+            util.check_slate_settings(model, self.dc, self.slate_eval['settings'], self.slate_eval['k'], self.slate_eval['value'])
         self.device_sampling = bool(device_sampling)
         self.train_split = DeviceBehaviors.train_resident(self.dc, corpus, config.negative_sample_num) if self.device_sampling else None
         self.step = TrainStep(model, lr=config.lr, weight_decay=config.weight_decay, gradient_clip_norm=config.gradient_clip_norm)
@@ -130,6 +147,15 @@ class Trainer:
         batch_size = 64 / max_history_num = 50)."""
         out = os.path.join(self.dev_res_dir, '%s-%d.txt' % (self.model.model_name, e))
         per = self.eval_batch_size
+        if self.slate_eval is not None:
+            metrics, self.last_slate_metrics = util.evaluate_slates_on_device(
+                self.model, self.dev, self.corpus.dev_indices, self.corpus.dev_labels, result_file=out, rows_per_forward=per,
+                recurrence_cache=self.cne_recurrence_cache, grouped=self.grouped_eval, **self.slate_eval)
+            for s, m in zip(self.slate_eval['settings'], self.last_slate_metrics):
+                print('Epoch %d : slates %s: nDCG@%d = %.4f  RR = %.4f  hit = %.4f  recall = %.4f  ILD = %.4f  topics = %.2f  filled = %.2f'
+                      % (e, {k: v for k, v in s.items() if k != 'similarity'}, self.slate_eval['k'], m['ndcg'], m['rr'], m['hit'],
+                         m['recall'], m['ild'], m['topics'], m['filled']))
+            return metrics
         if self.cached_eval and self.device_eval:
             return util.evaluate_cached_on_device(self.model, self.dev, self.corpus.dev_indices, self.corpus.dev_labels, result_file=out,
                                                   rows_per_forward=per, recurrence_cache=self.cne_recurrence_cache, grouped=self.grouped_eval)

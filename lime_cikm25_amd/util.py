@@ -191,7 +191,8 @@ def _score_grouped(model, behaviors, indices, cache, scores, full, per, rows_per
 
 
 def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=None, rows_per_forward=None,
-                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False, recurrence_cache=False, grouped=False):
+                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, return_scores=False, recurrence_cache=False, grouped=False,
+                              news_cache=None):
     """The dev / test pass of ``compute_scores_cached`` without host round trips: one ``build_news_cache``, ``score_behaviors`` in
     passes of up to ``rows_per_pass`` rows that write into ONE device score buffer, one ``evaluate.device_scoring`` (ranks and
     metrics in one launch, csrc/rank_metrics.hip), one device -> host copy of the result.  ``labels``: the per-impression label
@@ -221,7 +222,10 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
     ``score_lists`` calls at the most, each within ``rows_per_pass`` x H refined rows a pass.  Same score buffer, same
     ``device_scoring``; the scores equal the ungrouped ones to fp32 rounding.  Once per ``DeviceBehaviors`` it is checked, on the device,
     that all rows of an impression carry one history (a split of ``from_devtest`` does): ValueError naming the first impression that
-    does not.  CNE has no per-news cache: ``grouped`` is a ValueError there.  Off by default."""
+    does not.  CNE has no per-news cache: ``grouped`` is a ValueError there.  Off by default.
+
+    ``news_cache``: the ``build_news_cache`` of this corpus under the model's present weights, where the caller holds one already
+    (evaluate_slates_on_device reads its similarity table from it); None: it is built here."""
     config = model.config
     if grouped and model.reads_content_mask:
         raise ValueError('content_encoder \'CNE\' has no per-news content cache: the grouped dev pass (Model.score_lists) cannot serve '
@@ -241,7 +245,7 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
     was_training = model.training
     model.eval()
     try:
-        cache = model.build_news_cache(behaviors.corpus)
+        cache = model.build_news_cache(behaviors.corpus) if news_cache is None else news_cache
         rc = dict(recurrence_cache=model.build_recurrence_cache(behaviors.corpus), rows_per_forward=per) if recurrence_cache else {}
         dev = cache.device
         scores = torch.empty(num, dtype=torch.float32, device=dev)
@@ -261,3 +265,133 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
     if result_file is not None:
         write_rank_file(result_file, ranks_to_lists(ranks, indices))
     return (metrics, scores) if return_scores else metrics
+
+
+# ---- the slates a selection setting makes of the dev split, and what they are worth (csrc/slate_metrics.hip) ----------------------------
+SLATE_SETTING_KEYS = ('max_per_topic', 'quota_by', 'mmr_lambda', 'shortlist', 'similarity', 'topic_by')
+SLATE_RESULT_KEYS = ('ndcg', 'rr', 'hit', 'recall', 'ild', 'topics', 'filled', 'value')        # per_slate's columns, in order
+
+
+def check_slate_settings(model, corpus, settings, k, value=None, num=None):
+    """The refusals of ``evaluate_slates_on_device`` over ``settings`` / ``k`` / ``value`` (ValueError; nothing is launched): a list of
+    dicts over SLATE_SETTING_KEYS, each refused as ``serving.topic_quota`` / ``serving.diversity`` refuse its arguments; ``topic_by``
+    'category' (default) or 'topic'; MMR without a ``similarity`` needs a model with a per-news content cache.  -> per setting
+    (TopicQuota or None, (lam, shortlist) or None, similarity or None, topic_by)."""
+    import numbers
+
+    from . import serving
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= 128:
+        raise ValueError('evaluate_slates_on_device keeps 1 <= k <= 128 news per slate (lime_slate_metrics_f32), got k = %r' % (k,))
+    if not isinstance(settings, (list, tuple)) or not all(isinstance(s, dict) for s in settings):
+        raise ValueError('settings must be a list of dicts over %s, got %r' % (SLATE_SETTING_KEYS, settings))
+    if isinstance(value, str):
+        if value not in ('freshness', 'remaining'):
+            raise ValueError("value must be 'freshness', 'remaining', a [num] tensor or None, got %r" % (value,))
+    elif value is not None and (not isinstance(value, torch.Tensor) or value.dim() != 1 or (num is not None and value.numel() != num)):
+        raise ValueError("value must be 'freshness', 'remaining', a tensor with one entry per row%s or None, got %s"
+                         % ('' if num is None else ' ([%d])' % num, tuple(value.shape) if isinstance(value, torch.Tensor) else repr(value)))
+    n_news = corpus.news_category.shape[0]
+    stub = torch.empty((n_news, 0), dtype=torch.float32, device=corpus.news_category.device)    # (no cache yet: the table comes later)
+    checked = []
+    for i, s in enumerate(settings):
+        unknown = sorted(set(s) - set(SLATE_SETTING_KEYS))
+        if unknown:
+            raise ValueError('settings[%d]: unknown key%s %s (the keys are %s)' % (i, 's' if len(unknown) > 1 else '', unknown,
+                                                                                  SLATE_SETTING_KEYS))
+        topic_by = s.get('topic_by', 'category')
+        if topic_by not in ('category', 'topic'):
+            raise ValueError("settings[%d]: topic_by must be 'category' or 'topic' (the (category, subCategory) pair), got %r" % (i, topic_by))
+        quota = serving.topic_quota(corpus, s.get('max_per_topic'), s.get('quota_by', 'category'))
+        div = serving.diversity(model, stub, k, s.get('mmr_lambda'), s.get('shortlist'), s.get('similarity'))
+        if div is not None and div.table is None and model.reads_content_mask:
+            raise ValueError('settings[%d]: %s -- give a similarity table' % (i, model._NO_CONTENT_CACHE))
+        checked.append((quota, None if div is None else (div.lam, div.shortlist), s.get('similarity'), topic_by))
+    return checked
+
+
+def sweep_slate_settings(model, behaviors, news_cache, scores, indices, labels, settings, k=10, value=None, per_impression=False):
+    """What ``evaluate_slates_on_device`` does behind its scoring pass: ``scores`` fp32 [num] (device), one per row of ``behaviors``;
+    an impression (``evaluate.impression_layout`` of ``indices`` / ``labels``) is a list of candidates.  Per setting: the slates
+    (``serving.select_segments``), then one ``ops.slate_metrics`` call; at the end ONE device -> host copy of every setting's sums
+    and counts.  -> one dict per setting (see ``evaluate_slates_on_device``)."""
+    from . import serving
+    from .device_data import topic_table_of
+    from .evaluate import impression_layout
+    b, dev = behaviors, scores.device
+    checked = check_slate_settings(model, b.corpus, settings, k, value, b.num)
+    offsets, row_labels, skip = impression_layout(indices, labels)
+    if scores.numel() != row_labels.size or b.num != row_labels.size:
+        raise ValueError('one score per (impression, candidate) row: %d scores, %d rows, %d labelled rows' % (scores.numel(), b.num, row_labels.size))
+    offsets = torch.from_numpy(offsets.astype(np.int64)).to(dev)
+    row_labels, skip = torch.from_numpy(row_labels).to(dev), torch.from_numpy(skip).to(dev)
+    cand_index = b.cand_index.reshape(-1)
+    news = cand_index.to(torch.int32).contiguous()
+    if isinstance(value, str):
+        fresh = b.cand_freshness.reshape(-1).float()
+        value = fresh if value == 'freshness' else model._lifetime_rule(fresh, lambda: b.cand_lifetime.reshape(-1).float(),
+                                                                        lambda: b.corpus.news_category[cand_index.long()]).float()
+    if value is not None:
+        value = value.to(dev).float().contiguous()
+    default_table = serving.content_columns(model, news_cache)
+    if default_table is not None and default_table.shape[1] % 4:
+        default_table = None                                                 # (lime_slate_metrics_f32 reads rows in quads)
+    found = []
+    for quota, mmr, similarity, topic_by in checked:
+        table = similarity if similarity is not None else default_table
+        div = None if mmr is None else serving.diversity(model, news_cache, k, mmr[0], mmr[1], similarity)
+        positions, _ = serving.select_segments(scores, offsets, None, quota, div, cand_index, k)
+        topic_of_news, cat_t, _ = topic_table_of(b.corpus, topic_by)
+        found.append((ops.slate_metrics(positions, k, offsets, news, row_labels, skip, value, table, topic_of_news, n_keys=cat_t.numel()),
+                      table is not None))
+    if not found:
+        return []
+    host = torch.stack([torch.cat([f.sums, f.counts.double()]) for f, _ in found]).cpu().numpy()      # (counts < 2^53: exact)
+    results = []
+    for (f, has_table), row in zip(found, host):
+        sums, counts = row[:8], row[8:].astype(np.int64)
+        mean = lambda c, n: float(sums[c] / n) if n else float('nan')
+        res = {name: mean(c, counts[0 if c < 4 else 1 if c == 4 else 2]) for c, name in enumerate(SLATE_RESULT_KEYS)}
+        if not has_table:
+            res['ild'] = float('nan')
+        if value is None:
+            res['value'] = float('nan')
+        res.update(n_relevance=int(counts[0]), n_diversity=int(counts[1]), n_slates=int(counts[2]))
+        if per_impression:
+            res.update(per_impression=f.per_slate, status=f.status)
+        results.append(res)
+    return results
+
+
+def evaluate_slates_on_device(model, behaviors, indices, labels, settings, k=10, value=None, rows_per_forward=None,
+                              rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, grouped=False, per_impression=False, result_file=None,
+                              recurrence_cache=False):
+    """The dev split scored ONCE, and a sweep of selection settings evaluated on those scores without a host round trip: how much
+    nDCG@k does a quota or an MMR trade-off cost on the labelled impressions, and how much diversity does it buy?
+
+    ``settings``: a list of dicts, one per setting, over ``max_per_topic`` / ``quota_by`` (Model.recommend's quota), ``mmr_lambda`` /
+    ``shortlist`` / ``similarity`` (its MMR) and ``topic_by`` ('category', the default, or 'topic': the keys behind 'topics'); ``{}``
+    is the plain top k.  They are refused as ``serving.topic_quota`` / ``serving.diversity`` refuse them, before any scoring.
+    ``value``: 'freshness', 'remaining' (the remaining lifetime under config.lifetime_type) or a [num] tensor, one number per row;
+    None: none.  The other arguments are ``evaluate_cached_on_device``'s, and so are the refusals (``grouped``, the chunk rule, CNE).
+
+    One ``build_news_cache``, one ``evaluate_cached_on_device(..., return_scores=True)``; every impression is then a user's list:
+    per setting ``serving.select_segments`` picks its slate of k from the score buffer (the kernels of ``recommend_lists``) and
+    lime_slate_metrics_f32 turns the slates into metrics; one device -> host copy of all settings' sums and counts at the end.
+
+    Returns ((AUC, MRR, nDCG@5, nDCG@10) -- exactly ``evaluate_cached_on_device``'s --, a list with one dict per setting): 'ndcg',
+    'rr', 'hit', 'recall' -- means over the 'n_relevance' impressions ``scoring`` counts (labelled, both classes) --, 'ild' (1 - mean
+    pairwise cosine of the slate's similarity rows: the setting's ``similarity``, else the content columns of the news cache) over
+    the 'n_diversity' labelled impressions with >= 2 filled slots, 'topics' (distinct keys), 'filled' and 'value' over the
+    'n_slates' with >= 1; nan where nothing was counted or the input is missing.  With ``per_impression`` a dict also holds
+    'per_impression' fp64 [n_imp, 8] (the columns in SLATE_RESULT_KEYS' order) and 'status' int32 [n_imp], device tensors."""
+    check_slate_settings(model, behaviors.corpus, settings, k, value, behaviors.num)
+    was_training = model.training
+    model.eval()
+    try:
+        cache = model.build_news_cache(behaviors.corpus)
+    finally:
+        model.train(was_training)
+    metrics, scores = evaluate_cached_on_device(model, behaviors, indices, labels, result_file=result_file, rows_per_forward=rows_per_forward,
+                                                rows_per_pass=rows_per_pass, return_scores=True, recurrence_cache=recurrence_cache,
+                                                grouped=grouped, news_cache=cache)
+    return metrics, sweep_slate_settings(model, behaviors, cache, scores, indices, labels, settings, k, value, per_impression)
