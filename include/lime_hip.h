@@ -1406,7 +1406,42 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * fixed-order sums, no atomics, no workspace: a row's picks depend on its own operands alone, not on R, the row's position or the
  * run.  Statuses before any launch, in this order: LIME_ERR_BAD_ARG for a NULL pointer; LIME_ERR_BAD_ARG for R < 0, M < 1, k < 1,
  * k > M, n < 1, E < 1, ld < E, or lam outside [0, 1] or NaN; LIME_ERR_UNSUPPORTED for M > 128 (the top-k kernels' k limit),
- * E % 4 != 0, R > 65535.  R == 0 is a success without a launch. */
+ * E % 4 != 0, R > 65535.  R == 0 is a success without a launch.
+ *
+ * lime_calibrate_rows_f32 / lime_slate_miscalibration (csrc/calibrate_rows.hip): calibrated slates -- a slate whose topic mix follows
+ * the reader's own (Steck, RecSys 2018; Model.recommend(calibrate_lambda=); recommend.calibrated_select and
+ * recommend.slate_miscalibration state them on the host).
+ *   The TARGET of a row: hist_keys int32 [hist_rows, H] holds the group of every history slot (a key outside [0, n_keys) is no click;
+ *   -1 is the usual one), hist_weight fp32 [hist_rows, H] its weight (NULL: 1 each; a weight that is not finite or not > 0 removes
+ *   the slot).  Row r reads history row r % hist_rows (the [S U] rows of a schedule share U histories).  W is the weight sum over the
+ *   live slots and p[g] the weight sum of the live slots of group g divided by W, both summed in slot order; a row with W == 0 (or
+ *   not finite) has NO TARGET.  The support is the groups with a live slot.  keys int32 [n]: the group of every news (a key outside
+ *   [0, n_keys) is no group).
+ *   lime_calibrate_rows_f32: scores fp32 [R, M] and ids int32 [R, M] (both contiguous) are a row's shortlist, best first, ids the
+ *   news id.  DEAD entries and rel[j] are lime_mmr_rows_f32's: an id outside [0, n) or a non-finite score; rel[j] = (s[j] - s[last])
+ *   / (s[first] - s[last]) over the live entries, 0 everywhere when the span is 0.  Round t has t entries taken, c[g] of them in
+ *   group g; with T = t + 1 and q(c) = (1 - alpha) c / T + alpha p[g], entry j of group g has
+ *       gain[j] = p[g] (ln q(c[g] + 1) - ln q(c[g])) / ln(1 / alpha)
+ *   -- 0 when the row has no target, j has no group or p[g] is 0 --, and the round takes the live, untaken j of the largest
+ *   v[j] = lam rel[j] + (1 - lam) gain[j], the lower j on equal v, until k are taken or none is left.  picks int32 [R, k]: the taken
+ *   j in the order taken, -1 behind the last.  The largest gain is the smallest KL(p || q) of the slate with j added; gain lies in
+ *   [0, 1] like rel; lam = 1 is the plain order of the live entries and reads neither keys nor the history.  The gain is formed once
+ *   per support group and rel from the score alone: two entries of one group with equal score bits carry the same v bits, and the
+ *   lower j wins.  A wave per row, four rows a workgroup, any R (the grid strides); fp32 throughout (logf, not the fast intrinsic),
+ *   fixed-order sums, no atomics, no workspace: a row's picks depend on its own operands alone, not on R, its position or the run.
+ *   Statuses before any launch, in this order: LIME_ERR_BAD_ARG for a NULL pointer (hist_weight may be NULL); for R < 0, M < 1,
+ *   k < 1, k > M, n < 1, n_keys < 1, H < 0, hist_rows < 0 or hist_rows < 1 with H > 0; for lam outside [0, 1] or NaN; for alpha
+ *   outside (0, 1) or NaN; LIME_ERR_UNSUPPORTED for M > 128, H > 128 or n_keys > 8192.  R == 0 is a success without a launch.
+ *   lime_slate_miscalibration: positions int32 [R, ldp], k, offsets int64 [R + 1] or NULL and news int32 [P] with the meanings they
+ *   have in lime_slate_metrics_f32 (a slot is FILLED when its position lies inside the list / the pool and the news id behind it
+ *   inside [0, n)).  With c[g] the filled slots of group g and F their number,
+ *       value[r] = sum over the support of p[g] ln(p[g] / ((1 - alpha) c[g] / F + alpha p[g]))      (fp64 [R])
+ *   status int32 [R]: 1 no target; else 2 no filled slot; else 0 -- and value is 0 where status is not.  alpha is the fp32 number the
+ *   selection reads, widened: the metric measures the objective that was optimised.  fp64 sums and fp64 log, p
+ *   in slot order and the terms in the order of the groups' first slots; a wave per slate.  Statuses before any launch, in this
+ *   order: LIME_ERR_BAD_ARG for a NULL pointer (offsets and hist_weight may be NULL); for R < 0, P < 0, k < 1, k > ldp, n < 1,
+ *   n_keys < 1, H < 0, hist_rows < 0 or hist_rows < 1 with H > 0; for alpha outside (0, 1) or NaN; LIME_ERR_UNSUPPORTED for k > 128,
+ *   H > 128 or n_keys > 8192.  R == 0 is a success without a launch. */
 int lime_grouped_match_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* remaining,
                            const int64_t* offsets, float* logits, int64_t G, int64_t P, int32_t H, int32_t A, int32_t D, float scale,
                            float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
@@ -1442,6 +1477,12 @@ int lime_topk_rows_quota_f32(const float* scores, int64_t ld, int64_t U, int64_t
                              int64_t workspace_floats, void* stream);
 int lime_mmr_rows_f32(const float* scores, const int32_t* ids, int64_t R, int32_t M, const float* table, int64_t ld, int64_t n, int32_t E,
                       float lam, int32_t k, int32_t* picks, void* stream);
+int lime_calibrate_rows_f32(const float* scores, const int32_t* ids, int64_t R, int32_t M, const int32_t* keys, int64_t n, int32_t n_keys,
+                            const int32_t* hist_keys, const float* hist_weight, int64_t hist_rows, int32_t H, float lam, float alpha,
+                            int32_t k, int32_t* picks, void* stream);
+int lime_slate_miscalibration(const int32_t* positions, int64_t R, int64_t ldp, int32_t k, const int64_t* offsets, const int32_t* news,
+                              int64_t P, const int32_t* keys, int64_t n, int32_t n_keys, const int32_t* hist_keys, const float* hist_weight,
+                              int64_t hist_rows, int32_t H, float alpha, double* value, int32_t* status, void* stream);
 
 /* =====================================================================================================
  * Candidate lists (Model.score_lists / Model.recommend_lists): U users, each with its OWN list of candidates, as a CSR over P

@@ -88,6 +88,19 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// A round's pick of the greedy selections over a shortlist (mmr_rows_f32.hip, calibrate_rows.hip): the better of two (v, rank) is the
+// larger v, the lower rank on equal v ("no entry": v = -inf, rank = INT_MAX); wave_best_pick leaves the wave's best in every lane.
+struct best_pick {
+    float v;
+    int j;
+};
+__device__ __forceinline__ best_pick better_pick(best_pick a, best_pick b) { return (b.v > a.v || (b.v == a.v && b.j < a.j)) ? b : a; }
+__device__ __forceinline__ best_pick wave_best_pick(best_pick a) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) a = better_pick(a, best_pick{__shfl_xor(a.v, m), __shfl_xor(a.j, m)});
+    return a;
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope fence + s_barrier, and the fence
 // also waits vmcnt(0): every global load still in flight (a prefetch) and every store (an epilogue) would be drained
 // at each barrier.  The kernels here exchange data between waves through LDS only.

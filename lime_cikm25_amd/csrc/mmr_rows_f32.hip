@@ -30,18 +30,6 @@ constexpr int MMR_MAX = 128;         // entries of a shortlist: the top-k kernel
 constexpr int MMR_CHUNK = 2048;      // floats of the picked row in LDS at a time (a multiple of 64: a lane's quads stay its own)
 constexpr int MMR_ROWS = MMR_MAX / 16;
 
-struct best_t {
-    float v;
-    int j;
-};
-// the better of two (v, rank): the larger v, the lower rank on equal v ("no entry": v = -inf, rank = INT_MAX)
-__device__ __forceinline__ best_t better(best_t a, best_t b) { return (b.v > a.v || (b.v == a.v && b.j < a.j)) ? b : a; }
-__device__ __forceinline__ best_t wave_best(best_t a) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) a = better(a, best_t{__shfl_xor(a.v, m), __shfl_xor(a.j, m)});
-    return a;
-}
-
 // The group's part of one chunk: acc[i] += sum over the chunk's quads q = t, t + 16, .. of row[i] . (SELF ? row[i] : x), rows with a
 // null pointer skipped.  q0: the chunk's first quad, nq: its quads.
 template <bool VEC, bool SELF>
@@ -132,9 +120,9 @@ __global__ __launch_bounds__(256) void mmr_rows_kernel(const float* __restrict__
         float v0 = a0 - oml * pen[j0], v1 = a1 - oml * pen[j1];
         v0 = v0 == v0 ? v0 : -3.402823466e38f;
         v1 = v1 == v1 ? v1 : -3.402823466e38f;
-        const best_t b0 = open0 ? best_t{v0, j0} : best_t{-INFINITY, 0x7FFFFFFF};
-        const best_t b1 = open1 ? best_t{v1, j1} : best_t{-INFINITY, 0x7FFFFFFF};
-        const best_t best = wave_best(better(b0, b1));
+        const best_pick b0 = open0 ? best_pick{v0, j0} : best_pick{-INFINITY, 0x7FFFFFFF};
+        const best_pick b1 = open1 ? best_pick{v1, j1} : best_pick{-INFINITY, 0x7FFFFFFF};
+        const best_pick best = wave_best_pick(better_pick(b0, b1));
         if (best.j == 0x7FFFFFFF) break;                      // no live entry left (the same in every wave)
         if (tid == 0) out[r] = best.j;
         open0 = open0 && j0 != best.j;

@@ -585,7 +585,8 @@ class Model(nn.Module):
     @torch.no_grad()
     def recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                   cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None, quota_by='category',
-                  mmr_lambda=None, shortlist=None, similarity=None):
+                  mmr_lambda=None, shortlist=None, similarity=None, calibrate_lambda=None, calibrate_by='category',
+                  calibrate_alpha=0.01, calibrate_weights=None):
         """The k best news of the pool per user, on the device: ``score_pool`` (same arguments), then lime_topk_rows_f32 ->
         (positions int32 [U, k] into ``cand_index``, scores fp32 [U, k]).  Rows are in descending order of the score; equal scores
         (+0.0 and -0.0 are equal) go lower position first; a NaN ranks after every number, in position order.  With
@@ -608,10 +609,24 @@ class Model(nn.Module):
         default: the content columns of ``news_cache`` -- the whole row, under 'gated' its first half).  The positions and scores
         returned are the taken entries' in the order taken -- no longer descending --, -1 / -inf behind the last.  Refused
         (ValueError): an ``mmr_lambda`` outside [0, 1], a ``shortlist`` outside [k, 128], a ``similarity`` of another type or shape,
-        and ``shortlist`` or ``similarity`` without ``mmr_lambda``."""
+        and ``shortlist`` or ``similarity`` without ``mmr_lambda``.
+
+        ``calibrate_lambda`` = lam (a real in [0, 1]; None: no calibration, today's launches and bits): the slate's topic mix follows
+        the reader's own (calibrated re-ranking, Steck 2018).  The target p is the distribution of the groups -- ``calibrate_by``:
+        'category' or 'topic' -- over the masked-in slots of the user's history, each slot weighing ``calibrate_weights[u, h]`` (fp32
+        [U, H] on the cache's device; None: 1 each; a weight that is not finite or not > 0 removes the slot).  Among the ``shortlist``
+        best (as under ``mmr_lambda``; under ``max_per_topic`` the quota walk's, so the two compose) each round takes the entry of
+        the largest lam rel + (1 - lam) gain, gain the drop of KL(p || (1 - alpha) slate + alpha p) that the entry brings, scaled
+        to [0, 1] by ln(1 / alpha), alpha = ``calibrate_alpha`` (lime_calibrate_rows_f32; ``recommend.calibrated_select`` states it
+        on the host); lam = 1 is the plain slate, and so is a user without a masked-in history slot.  Returned as under
+        ``mmr_lambda``.  Refused (ValueError): a ``calibrate_lambda`` that is no real in [0, 1], an unknown ``calibrate_by``, a
+        ``calibrate_alpha`` that is no real in (0, 1), ``calibrate_weights`` of another type, shape, dtype or device, any of the three
+        away from its default without ``calibrate_lambda``, ``calibrate_lambda`` together with ``mmr_lambda`` (one selection trades
+        relevance against one of the two), a corpus of more than 8192 groups, and H > 128."""
         return serving.recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                                  cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, mmr_lambda=mmr_lambda,
-                                 shortlist=shortlist, similarity=similarity)
+                                 shortlist=shortlist, similarity=similarity, calibrate_lambda=calibrate_lambda, calibrate_by=calibrate_by,
+                                 calibrate_alpha=calibrate_alpha, calibrate_weights=calibrate_weights)
 
     @torch.no_grad()
     def score_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
@@ -640,17 +655,21 @@ class Model(nn.Module):
     @torch.no_grad()
     def recommend_schedule(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                            cand_lifetime, slot_offsets, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None,
-                           quota_by='category', mmr_lambda=None, shortlist=None, similarity=None):
+                           quota_by='category', mmr_lambda=None, shortlist=None, similarity=None, calibrate_lambda=None,
+                           calibrate_by='category', calibrate_alpha=0.01, calibrate_weights=None):
         """The k best news of the pool per user in every slot of a schedule: ``score_schedule`` (same arguments), then
         lime_topk_rows_f32 over the [S U, C] view of its scores (in chunks of slots that keep the kernel's 65535 rows) -> (positions
         int32 [S, U, k] into ``cand_index``, scores fp32 [S, U, k]); slot s holds what ``recommend`` returns at
         ``cand_freshness + slot_offsets[s]``, in its order and with its -1 / -inf for excluded or missing slots.  1 <= k <= 128.
         ``max_per_topic`` / ``quota_by``: as in ``recommend``, per (slot, user) row (lime_topk_rows_quota_f32 over the same view; the
         [U, C] mask of ``exclude_history`` is handed over once, row s U + u reads its row u).
-        ``mmr_lambda`` / ``shortlist`` / ``similarity``: as in ``recommend``, per (slot, user) row."""
+        ``mmr_lambda`` / ``shortlist`` / ``similarity``: as in ``recommend``, per (slot, user) row.
+        ``calibrate_lambda`` / ``calibrate_by`` / ``calibrate_alpha`` / ``calibrate_weights``: as in ``recommend``, per (slot, user) row;
+        the [U, H] histories are handed over once, row s U + u reads user u's."""
         return serving.recommend(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                                  cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=slot_offsets,
-                                 mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity)
+                                 mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity, calibrate_lambda=calibrate_lambda,
+                                 calibrate_by=calibrate_by, calibrate_alpha=calibrate_alpha, calibrate_weights=calibrate_weights)
 
     @torch.no_grad()
     def score_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
@@ -680,23 +699,27 @@ class Model(nn.Module):
     @torch.no_grad()
     def recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
                         cand_freshness, cand_lifetime, k, n_src=None, pairs_per_pass=1 << 18, exclude_history=False, max_per_topic=None,
-                        quota_by='category', mmr_lambda=None, shortlist=None, similarity=None):
+                        quota_by='category', mmr_lambda=None, shortlist=None, similarity=None, calibrate_lambda=None,
+                        calibrate_by='category', calibrate_alpha=0.01, calibrate_weights=None):
         """The k best news of every user's OWN list, on the device: ``score_lists`` (same arguments), then lime_topk_segments_f32 ->
         (positions int32 [U, k] into the user's list -- candidate ``cand_index[cand_offsets[u] + positions[u, j]]`` --, scores fp32
         [U, k]) in ``recommend``'s order.  With ``exclude_history`` a candidate that sits in a masked-in slot of the user's history is
         never returned; the trailing slots of a list with fewer than k candidates left (all k of an empty list) hold position -1 and
         score -inf.  1 <= k <= 128.
         ``max_per_topic`` / ``quota_by``: as in ``recommend``, per list (lime_topk_segments_quota_f32).
-        ``mmr_lambda`` / ``shortlist`` / ``similarity``: as in ``recommend``, per list."""
+        ``mmr_lambda`` / ``shortlist`` / ``similarity``: as in ``recommend``, per list.
+        ``calibrate_lambda`` / ``calibrate_by`` / ``calibrate_alpha`` / ``calibrate_weights``: as in ``recommend``, per list."""
         return serving.recommend_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
                                        cand_freshness, cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by,
-                                       mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity)
+                                       mmr_lambda=mmr_lambda, shortlist=shortlist, similarity=similarity, calibrate_lambda=calibrate_lambda,
+                                       calibrate_by=calibrate_by, calibrate_alpha=calibrate_alpha, calibrate_weights=calibrate_weights)
 
     @torch.no_grad()
     def evaluate_slates(self, behaviors, indices, labels, settings, k=10, **kw):
         """``util.evaluate_slates_on_device`` of this model: the dev split scored once, then every selection setting of ``settings``
         (``recommend_lists``' ``max_per_topic`` / ``mmr_lambda`` ..) evaluated on those scores -- nDCG@k, RR, hit, recall against
-        intra-list distance, distinct topics, fill and a value of the caller's -> (the pass's four metrics, one dict per setting)."""
+        intra-list distance, distinct topics, fill and a value of the caller's -> (the pass's four metrics, one dict per setting).
+        ``calibration='category'`` / ``'topic'`` adds every setting's mean miscalibration against the impression's history."""
         from . import util
         return util.evaluate_slates_on_device(self, behaviors, indices, labels, settings, k=k, **kw)
 

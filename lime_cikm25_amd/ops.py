@@ -1223,6 +1223,57 @@ def mmr_rows(scores, ids, table, lam, k):
     return picks
 
 
+def _history(hist_keys, hist_weight, device, who):
+    """The checks of a calibration target's operands -> (hist_rows, H): hist_keys int32 [hist_rows, H] and hist_weight fp32 like it or
+    None, contiguous, on ``device``; H <= 128; at least one row where H > 0."""
+    _mat(hist_keys, 'hist_keys', dtype=torch.int32)
+    rows, H = hist_keys.shape
+    if not hist_keys.is_contiguous() or (H > 0 and rows < 1) or H > 128:
+        raise ValueError('%s needs contiguous hist_keys [hist_rows, H] with H <= 128 and hist_rows >= 1 where H > 0, got %s strides %s'
+                         % (who, tuple(hist_keys.shape), hist_keys.stride()))
+    if hist_weight is not None:
+        _mat(hist_weight, 'hist_weight')
+        if hist_weight.shape != hist_keys.shape or not hist_weight.is_contiguous():
+            raise ValueError('hist_weight must be contiguous and shaped like hist_keys %s, got %s' % (tuple(hist_keys.shape),
+                                                                                                      tuple(hist_weight.shape)))
+    for t, name in ((hist_keys, 'hist_keys'), (hist_weight, 'hist_weight')):
+        if t is not None and t.device != device:
+            raise ValueError('%s is on %s, the rows on %s' % (name, t.device, device))
+    return rows, H
+
+
+def calibrate_rows(scores, ids, keys, n_keys, hist_keys, hist_weight, lam, alpha, k):
+    """``lime_calibrate_rows_f32``: calibrated greedy selection over a shortlist per row (``recommend.calibrated_select`` on the
+    device).  scores fp32 [R, M] and ids int32 [R, M] (device, contiguous): a row's shortlist, best first, and the news id behind each
+    entry (outside [0, n), or a score that is not finite: dead); keys int32 [n]: the group of every news, 0 <= key < ``n_keys`` <=
+    8192; hist_keys int32 [hist_rows, H] (contiguous, H <= 128) and hist_weight fp32 like it or None: row r's target is history row
+    r % hist_rows -> picks int32 [R, k], the shortlist ranks in the order taken, -1 behind the last.  1 <= k <= M <= 128,
+    0 <= lam <= 1, 0 < alpha < 1."""
+    _mat(scores, 'scores')
+    R, M = scores.shape
+    k, lam, alpha, n_keys = int(k), float(lam), float(alpha), int(n_keys)
+    if not 1 <= k <= M or M > 128 or not 0.0 <= lam <= 1.0 or not 0.0 < alpha < 1.0 or not 1 <= n_keys <= 8192:
+        raise ValueError('calibrate_rows needs 1 <= k <= M <= 128, 0 <= lam <= 1, 0 < alpha < 1 and 1 <= n_keys <= 8192, got k = %d, M = %d, '
+                         'lam = %r, alpha = %r, n_keys = %d' % (k, M, lam, alpha, n_keys))
+    if not scores.is_contiguous():
+        raise ValueError('scores must be contiguous, got strides %s' % (scores.stride(),))
+    _vec(ids, 'ids', R * M, dtype=torch.int32)
+    n = _vec(keys, 'keys', dtype=torch.int32).numel()
+    if n < 1:
+        raise ValueError('keys must hold the group of at least one news')
+    rows, H = _history(hist_keys, hist_weight, scores.device, 'calibrate_rows')
+    for t, name in ((ids, 'ids'), (keys, 'keys')):
+        if t.device != scores.device:
+            raise ValueError('%s is on %s, scores on %s' % (name, t.device, scores.device))
+    picks = torch.empty((R, k), dtype=torch.int32, device=scores.device)
+    if R == 0:                                                    # (an empty tensor has no address to hand over)
+        return picks
+    lib = _lib.load()                                             # (H = 0: an empty tensor has no address; nothing is read through it)
+    check(lib.lime_calibrate_rows_f32(_p(scores), _p(ids), R, M, _p(keys), n, n_keys, ctypes.c_void_p(hist_keys.data_ptr() or 16),
+                                      _p(hist_weight) if H else None, rows, H, lam, alpha, k, _p(picks), _stream()), 'lime_calibrate_rows_f32')
+    return picks
+
+
 def row_scale(x, scale):
     lib = _lib.load()
     D = x.shape[-1]
@@ -2735,6 +2786,40 @@ def slate_metrics(positions, k, offsets, news, labels=None, skip=None, value=Non
     a.k, a.E, a.n_keys, a.reduce_blocks, a.reserved = k, E, (n_keys if keys is not None else 0), int(reduce_blocks), 0
     check(lib.lime_slate_metrics_f32(ctypes.byref(a), _stream()), 'lime_slate_metrics_f32')
     return SlateMetrics(per_slate, status, sums, counts)
+
+
+def slate_miscalibration(positions, k, offsets, news, keys, n_keys, hist_keys, hist_weight=None, alpha=0.01):
+    """``lime_slate_miscalibration``: how far the topic mix of the slates ``positions`` int32 [R, ldp] (the first k <= ldp slots) is
+    from their readers' (``recommend.slate_miscalibration`` on the device) -> (value fp64 [R], status int32 [R]: 0 defined, 1 no
+    target, 2 no filled slot).  ``positions`` / ``offsets`` / ``news`` as in ``slate_metrics``; keys int32 [n] (n bounds the news ids
+    too) with 0 <= key < ``n_keys`` <= 8192; hist_keys / hist_weight as in ``calibrate_rows``, slate r reading history row
+    r % hist_rows.  ``alpha`` is read as the fp32 number ``calibrate_rows`` reads.  k <= 128, H <= 128."""
+    if isinstance(positions, torch.Tensor) and positions.dim() == 2 and positions.shape[0] == 0:
+        positions = positions.new_empty(positions.shape)           # (no slates: whatever strides the empty tensor carries)
+    _mat(positions, 'positions', dtype=torch.int32)
+    R, ldp = positions.shape
+    k, alpha, n_keys = int(k), float(alpha), int(n_keys)
+    if not 1 <= k <= min(ldp, 128) or not 0.0 < alpha < 1.0 or not 1 <= n_keys <= 8192:
+        raise ValueError('slate_miscalibration needs 1 <= k <= min(ldp, 128) = %d, 0 < alpha < 1 and 1 <= n_keys <= 8192, got k = %d, '
+                         'alpha = %r, n_keys = %d' % (min(ldp, 128), k, alpha, n_keys))
+    P = _vec(news, 'news', dtype=torch.int32).numel()
+    _vec(offsets, 'offsets', R + 1, dtype=torch.int64)
+    n = _vec(keys, 'keys', dtype=torch.int32).numel()
+    if n < 1:
+        raise ValueError('keys must hold the group of at least one news')
+    rows, H = _history(hist_keys, hist_weight, positions.device, 'slate_miscalibration')
+    for t, name in ((news, 'news'), (offsets, 'offsets'), (keys, 'keys')):
+        if t is not None and t.device != positions.device:
+            raise ValueError('%s is on %s, positions on %s' % (name, t.device, positions.device))
+    value = torch.empty(R, dtype=torch.float64, device=positions.device)
+    status = torch.empty(R, dtype=torch.int32, device=positions.device)
+    if R == 0:                                                    # (an empty tensor has no address to hand over)
+        return value, status
+    lib = _lib.load()                                             # (P = 0 or H = 0: an empty tensor has no address; nothing is read through it)
+    check(lib.lime_slate_miscalibration(_p(positions), R, _ld(positions), k, _p(offsets), ctypes.c_void_p(news.data_ptr() or 16), P, _p(keys),
+                                        n, n_keys, ctypes.c_void_p(hist_keys.data_ptr() or 16), _p(hist_weight) if H else None, rows, H,
+                                        alpha, _p(value), _p(status), _stream()), 'lime_slate_miscalibration')
+    return value, status
 
 
 # ---- the epoch's negative sampling from the resident train tables (csrc/negative_sample.hip) --------------------------------------------

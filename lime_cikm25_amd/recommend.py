@@ -294,6 +294,167 @@ def mmr_select(scores, ids, table, lam, k, return_gap=False):
     return (picks, gaps) if return_gap else picks
 
 
+# ---- calibrated slates (Model.recommend* with calibrate_lambda): the slate's topic mix follows the reader's own -------------------------
+CALIBRATE_ALPHA = 0.01                # the share of the target mixed into the slate's distribution (Steck's smoothing)
+
+
+def calibration_target(hist_keys, n_keys, weights=None):
+    """The target of one history row -> (groups int64 [S] ascending, p fp64 [S]); S = 0: no target.  ``hist_keys`` [H]: the group of
+    every history slot, an entry outside [0, n_keys) is no click; ``weights`` [H] or None (1 each): a weight that is not finite or
+    not > 0 removes the slot.  W is the weight sum over the live slots (not finite, or 0: no target) and p[g] the weight sum of the
+    live slots of group g, taken in slot order, divided by W."""
+    hk = np.asarray(hist_keys).reshape(-1).astype(np.int64)
+    w = np.ones(hk.shape[0]) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != hk.shape[0]:
+        raise ValueError('a weight per history slot: %d weights, %d slots' % (w.shape[0], hk.shape[0]))
+    live = (hk >= 0) & (hk < int(n_keys)) & np.isfinite(w) & (w > 0)
+    none = (np.zeros(0, dtype=np.int64), np.zeros(0))
+    if not live.any():
+        return none
+    wl = w[live]
+    W = float(np.cumsum(wl)[-1])                                              # slot order, one addition after the other
+    if not (np.isfinite(W) and W > 0):
+        return none
+    groups, inverse = np.unique(hk[live], return_inverse=True)
+    return groups, np.bincount(inverse.reshape(-1), weights=wl) / W           # (bincount adds in slot order)
+
+
+def _history_rows(who, hist_keys, weights):
+    hk = np.asarray(hist_keys).astype(np.int64)
+    if hk.ndim != 2:
+        raise ValueError('%s needs hist_keys [hist_rows, H], got %s' % (who, hk.shape))
+    w = None if weights is None else np.asarray(weights, dtype=np.float64)
+    if w is not None and w.shape != hk.shape:
+        raise ValueError('%s needs weights shaped like hist_keys %s, got %s' % (who, hk.shape, w.shape))
+    if hk.shape[1] > 0 and hk.shape[0] < 1:
+        raise ValueError('%s needs at least one history row' % who)
+    return hk, w
+
+
+def calibrated_select(scores, ids, keys, n_keys, hist_keys, weights=None, lam=0.5, alpha=CALIBRATE_ALPHA, k=10, return_gap=False):
+    """The host statement of ``ops.calibrate_rows`` (lime_calibrate_rows_f32), in fp64 -> picks int32 [R, k]: the shortlist ranks in
+    the order taken, -1 behind the last one.  Calibrated re-ranking (Steck, RecSys 2018) by the greedy rule.
+
+    ``scores`` [R, M] and ``ids`` int [R, M]: a row's shortlist, best first, and the news id of each entry; ``keys`` int [n]: the
+    group of every news (a key outside [0, n_keys) is no group); ``hist_keys`` int [hist_rows, H] and ``weights`` [hist_rows, H] or
+    None: row r's TARGET p is ``calibration_target`` of history row r % hist_rows.  An entry is DEAD exactly as in ``mmr_select``:
+    its id is < 0 or >= n, or its score is not finite; rel[j] is ``mmr_select``'s too: (s[j] - s[last]) / (s[first] - s[last]) over
+    the live entries, 0 everywhere when the span is 0.  Round t has t entries taken, c[g] of them in group g.  With T = t + 1 and
+    q(c) = (1 - alpha) c / T + alpha p[g], entry j of group g has
+        gain[j] = p[g] (ln q(c[g] + 1) - ln q(c[g])) / ln(1 / alpha)        if p[g] > 0, else 0
+    (0 too when the row has no target or j has no group), and the round takes the live, untaken j of the largest
+    v[j] = lam rel[j] + (1 - lam) gain[j], the lower rank on equal v; until k are taken or none is left.
+
+    Adding j changes only its own group's term of KL(p || q~), q~[g] = (1 - alpha) c[g] / T + alpha p[g] the slate of size T with j
+    in it, so the largest gain is the smallest KL: Steck's greedy in O(M) a round.  ln(1 / alpha) is the largest value the bracket
+    times p can take (p = 1, T = 1, c = 0), so gain lies in [0, 1] like rel and lam means what it means for MMR.
+    Hence: lam = 1 takes the live entries in rank order (of a sorted shortlist); a row without a target does the same; k >= the
+    number of live entries returns all of them; a round does not read k, so a PREFIX of the picks at k is the picks at a smaller k;
+    and two entries of one group with equal scores have the same v by construction, so they come out in rank order.
+    ``return_gap``: -> (picks, gap fp64 [R]): per row the smallest difference, over the rounds, between the best v and the best v
+    among the open entries whose (group, score) differ from the winner's (a group outside the target's support counts as no group:
+    its gain is 0 by construction too); inf where no round had such an entry."""
+    scores = np.asarray(scores, dtype=np.float64)
+    ids = np.asarray(ids).astype(np.int64)
+    keys = np.asarray(keys).reshape(-1).astype(np.int64)
+    lam, alpha, k, n_keys = float(lam), float(alpha), int(k), int(n_keys)
+    if scores.ndim != 2 or ids.shape != scores.shape or keys.shape[0] < 1 or n_keys < 1:
+        raise ValueError('calibrated_select needs scores and ids [R, M], keys [n] with n >= 1 and n_keys >= 1, got %s, %s, %s and %d'
+                         % (scores.shape, ids.shape, keys.shape, n_keys))
+    if k < 1 or not 0.0 <= lam <= 1.0 or not 0.0 < alpha < 1.0:
+        raise ValueError('calibrated_select needs k >= 1, 0 <= lam <= 1 and 0 < alpha < 1, got k = %d, lam = %r, alpha = %r' % (k, lam, alpha))
+    hk, w = _history_rows('calibrated_select', hist_keys, weights)
+    R, M = scores.shape
+    picks = np.full((R, k), -1, dtype=np.int32)
+    gaps = np.full(R, np.inf)
+    scale = np.log(1.0 / alpha)
+    targets = {}
+    for r in range(R):
+        live = np.flatnonzero((ids[r] >= 0) & (ids[r] < keys.shape[0]) & np.isfinite(scores[r]))
+        if live.size == 0:
+            continue
+        s = scores[r, live]
+        span = s[0] - s[-1]
+        rel = (s - s[-1]) / span if span != 0 else np.zeros(live.size)
+        hr = r % hk.shape[0] if hk.shape[1] else -1
+        if hr not in targets:
+            targets[hr] = calibration_target(hk[hr], n_keys, None if w is None else w[hr]) if hr >= 0 else calibration_target([], n_keys)
+        groups, p = targets[hr]
+        key = keys[ids[r, live]]
+        at, pe = np.full(live.size, -1, dtype=np.int64), np.zeros(live.size)  # the entry's support group (-1: none) and its p
+        if groups.size:
+            at = np.minimum(np.searchsorted(groups, key), groups.size - 1)
+            at = np.where(groups[at] == key, at, -1)
+            pe = np.where(at >= 0, p[np.maximum(at, 0)], 0.0)
+        counts = np.zeros(max(groups.size, 1))
+        open_ = np.ones(live.size, dtype=bool)
+        for t in range(min(k, live.size)):
+            T = t + 1.0
+            ce = np.where(at >= 0, counts[np.maximum(at, 0)], 0.0)
+            has = pe > 0
+            q1 = np.where(has, (1.0 - alpha) * (ce + 1.0) / T + alpha * pe, 1.0)
+            q0 = np.where(has, (1.0 - alpha) * ce / T + alpha * pe, 1.0)
+            gain = pe * (np.log(q1) - np.log(q0)) / scale
+            v = np.where(open_, lam * rel + (1.0 - lam) * gain, -np.inf)
+            best = int(np.argmax(v))                                          # the first of equal maxima: the lower rank
+            other = open_ & ~((at == at[best]) & (s == s[best]))
+            if other.any():
+                gaps[r] = min(gaps[r], v[best] - v[other].max())
+            picks[r, t] = live[best]
+            open_[best] = False
+            if at[best] >= 0:
+                counts[at[best]] += 1.0
+    return (picks, gaps) if return_gap else picks
+
+
+def slate_miscalibration(positions, k, offsets, news, keys, n_keys, hist_keys, weights=None, alpha=CALIBRATE_ALPHA):
+    """The host statement of ``ops.slate_miscalibration`` (lime_slate_miscalibration), in fp64 -> (value fp64 [R], status int32 [R]):
+    how far the topic mix of a finished slate is from its reader's, KL(p || q~).
+
+    ``positions`` / ``k`` / ``offsets`` / ``news`` as in ``slate_metrics``, and "filled" is its rule: the position lies inside the
+    list (the pool) and the news id behind it inside [0, n), n = len(keys).  ``keys`` int [n], ``hist_keys`` / ``weights``: as in
+    ``calibrated_select`` -- slate r reads history row r % hist_rows.  With c[g] the FILLED slots of group g and F their number,
+        value = sum over the target's support of p[g] ln(p[g] / ((1 - alpha) c[g] / F + alpha p[g]))
+    status: 1 no target; else 2 no filled slot; else 0.  The value is 0 where the status is not 0."""
+    pos = np.asarray(positions).astype(np.int64)
+    k, n_keys, alpha = int(k), int(n_keys), float(alpha)
+    if pos.ndim != 2 or not 1 <= k <= pos.shape[1]:
+        raise ValueError('slate_miscalibration needs positions [R, ldp] and 1 <= k <= ldp, got %s and k = %d' % (pos.shape, k))
+    if not 0.0 < alpha < 1.0 or n_keys < 1:
+        raise ValueError('slate_miscalibration needs 0 < alpha < 1 and n_keys >= 1, got alpha = %r, n_keys = %d' % (alpha, n_keys))
+    R = pos.shape[0]
+    pos = pos[:, :k]
+    news = np.asarray(news).reshape(-1).astype(np.int64)
+    keys = np.asarray(keys).reshape(-1).astype(np.int64)
+    P, n = news.shape[0], keys.shape[0]
+    hk, w = _history_rows('slate_miscalibration', hist_keys, weights)
+    if offsets is None:
+        beg, length = np.zeros(R, dtype=np.int64), np.full(R, P, dtype=np.int64)
+    else:
+        off = np.clip(np.asarray(offsets).reshape(-1).astype(np.int64), 0, P)
+        if off.shape[0] != R + 1:
+            raise ValueError('offsets must have R + 1 = %d entries, got %d' % (R + 1, off.shape[0]))
+        beg = off[:-1]
+        length = np.maximum(off[1:], beg) - beg
+    inside = (pos >= 0) & (pos < length[:, None])
+    nid = news[np.where(inside, beg[:, None] + pos, 0)] if P else np.zeros_like(pos)
+    filled = inside & (nid >= 0) & (nid < n)
+    key = np.where(filled, keys[np.where(filled, nid, 0)], -1) if n else np.full(pos.shape, -1)
+    value, status = np.zeros(R), np.zeros(R, dtype=np.int32)
+    for r in range(R):
+        groups, p = calibration_target(hk[r % hk.shape[0]], n_keys, None if w is None else w[r % hk.shape[0]]) if hk.shape[1] else ((), ())
+        F = int(filled[r].sum())
+        if len(groups) == 0:
+            status[r] = 1
+        elif F == 0:
+            status[r] = 2
+        else:
+            c = (key[r][None, :] == groups[:, None]).sum(axis=1)
+            on = p > 0
+            value[r] = float((p[on] * np.log(p[on] / ((1.0 - alpha) * c[on] / F + alpha * p[on]))).sum())
+    return value, status
+
+
 # ---- what a slate is worth (util.evaluate_slates_on_device): accuracy against the labels, diversity of the slots ------------------------
 SLATE_COLUMNS = ('ndcg', 'rr', 'hit', 'recall', 'ild', 'topics', 'filled', 'value')
 

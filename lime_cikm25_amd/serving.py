@@ -317,15 +317,94 @@ def diversity(model, news_cache, k, mmr_lambda, shortlist, similarity):
     return Diversity(float(mmr_lambda), int(shortlist), table)
 
 
+def _reranked(select, positions, top, ids, k, rows_per_launch):
+    """The tail that the re-ranked slates share: ``select(top rows, ids rows)`` -> picks int32 [rows, k] in launches of
+    ``rows_per_launch`` rows (None: one launch), then the two gathers that turn the picks into positions and score bits."""
+    top = top.contiguous()
+    step = rows_per_launch or max(top.shape[0], 1)
+    picks = torch.cat([select(top[r0:r0 + step], ids[r0:r0 + step].contiguous())
+                       for r0 in range(0, top.shape[0], step)]) if top.shape[0] else top.new_empty((0, k), dtype=torch.int32)
+    at, none = picks.clamp(min=0).long(), picks < 0
+    return (torch.gather(positions, 1, at).masked_fill(none, -1), torch.gather(top, 1, at).masked_fill(none, float('-inf')))
+
+
 def _diverse(div, positions, top, ids, k):
     """The tail of every recommend entry under MMR: ``positions`` / ``top`` [R, shortlist] the shortlist's (an entry that takes no
     part holds position -1), ``ids`` int32 [R, shortlist] the similarity row of each entry (-1: none) -> (positions int32 [R, k],
     scores fp32 [R, k]): ops.mmr_rows in launches of 65535 rows, then its picks turned into positions and score bits."""
-    top = top.contiguous()
-    picks = torch.cat([ops.mmr_rows(top[r0:r0 + MMR_ROWS_MAX], ids[r0:r0 + MMR_ROWS_MAX].contiguous(), div.table, div.lam, k)
-                       for r0 in range(0, top.shape[0], MMR_ROWS_MAX)]) if top.shape[0] else top.new_empty((0, k), dtype=torch.int32)
-    at, none = picks.clamp(min=0).long(), picks < 0
-    return (torch.gather(positions, 1, at).masked_fill(none, -1), torch.gather(top, 1, at).masked_fill(none, float('-inf')))
+    return _reranked(lambda s, i: ops.mmr_rows(s, i, div.table, div.lam, k), positions, top, ids, k, MMR_ROWS_MAX)
+
+
+Calibration = collections.namedtuple('Calibration', 'lam shortlist by alpha weights topic_of_news n_keys')
+CALIBRATE_MAX_H = 128                 # lime_calibrate_rows_f32's history slots
+
+
+def calibration(k, calibrate_lambda, calibrate_by, calibrate_alpha, calibrate_weights, mmr_lambda, shortlist):
+    """The refusals of ``calibrate_lambda`` / ``calibrate_by`` / ``calibrate_alpha`` / ``calibrate_weights`` that read nothing but
+    their arguments (ValueError, before any launch and before the corpus is touched) -> None without calibration, or a Calibration
+    whose corpus-bound fields ``bind_calibration`` fills (shortlist: the default is ``diversity``'s, min(128, max(k, 64)))."""
+    if calibrate_lambda is None:
+        if calibrate_by != 'category' or calibrate_alpha != rec.CALIBRATE_ALPHA or calibrate_weights is not None \
+                or isinstance(calibrate_alpha, bool):
+            raise ValueError('calibrate_by, calibrate_alpha and calibrate_weights are read with calibrate_lambda alone: give '
+                             'calibrate_lambda, or leave them at their defaults')
+        return None
+    if isinstance(calibrate_lambda, bool) or not isinstance(calibrate_lambda, numbers.Real) or not 0.0 <= calibrate_lambda <= 1.0:
+        raise ValueError('calibrate_lambda must be a real number in [0, 1] (or None: no calibration), got %r' % (calibrate_lambda,))
+    if calibrate_by not in ('category', 'topic'):
+        raise ValueError("calibrate_by must be 'category' or 'topic' (the (category, subCategory) pair), got %r" % (calibrate_by,))
+    if isinstance(calibrate_alpha, bool) or not isinstance(calibrate_alpha, numbers.Real) or not 0.0 < calibrate_alpha < 1.0:
+        raise ValueError('calibrate_alpha must be a real number in (0, 1), got %r' % (calibrate_alpha,))
+    if calibrate_weights is not None and (not isinstance(calibrate_weights, torch.Tensor) or calibrate_weights.dtype != torch.float32
+                                          or calibrate_weights.dim() != 2):
+        raise ValueError('calibrate_weights must be an fp32 tensor [U, H] like hist_index, got %s'
+                         % ('%s %s' % (calibrate_weights.dtype, tuple(calibrate_weights.shape))
+                            if isinstance(calibrate_weights, torch.Tensor) else repr(calibrate_weights)))
+    if mmr_lambda is not None:
+        raise ValueError('calibrate_lambda together with mmr_lambda is out of scope: one selection trades relevance against either the '
+                         'content similarity (mmr_lambda) or the topic mix (calibrate_lambda), not both')
+    k = int(k) if isinstance(k, numbers.Integral) and 1 <= k <= 128 else None     # (a bad k is check_grouped's to refuse)
+    if shortlist is None:
+        shortlist = min(128, max(k or 1, 64))
+    elif isinstance(shortlist, bool) or not isinstance(shortlist, numbers.Integral) or not (k or 1) <= shortlist <= 128:
+        raise ValueError('shortlist must be an integer in [k, 128] = [%s, 128], got %r' % (k if k else 'k', shortlist))
+    return Calibration(float(calibrate_lambda), int(shortlist), calibrate_by, float(calibrate_alpha), calibrate_weights, None, 0)
+
+
+def bind_calibration(cal, corpus, hist_index, device):
+    """The refusals of a calibrated call that read the corpus and the histories' shape (ValueError, before any launch) -> ``cal`` with
+    the corpus' topic_of_news int32 [n_news] under ``cal.by`` and its number of groups; None stays None."""
+    if cal is None:
+        return None
+    from .device_data import topic_table_of
+    topic_of_news, cat_t, _ = topic_table_of(corpus, cal.by)
+    if cat_t.numel() > rec.MAX_TOPICS:
+        raise ValueError('the corpus has %d groups by %s, lime_calibrate_rows_f32 counts up to %d' % (cat_t.numel(), cal.by, rec.MAX_TOPICS))
+    if isinstance(hist_index, torch.Tensor) and hist_index.dim() == 2:            # (another shape is check_grouped's to refuse)
+        if hist_index.shape[1] > CALIBRATE_MAX_H:
+            raise ValueError('a calibrated slate reads up to %d history slots (lime_calibrate_rows_f32), got H = %d'
+                             % (CALIBRATE_MAX_H, hist_index.shape[1]))
+        w = cal.weights
+        if w is not None and (tuple(w.shape) != tuple(hist_index.shape) or w.device != torch.device(device)):
+            raise ValueError('calibrate_weights must be fp32 [U, H] = %s on %s like the histories, got %s on %s'
+                             % (list(hist_index.shape), device, list(w.shape), w.device))
+    return cal._replace(topic_of_news=topic_of_news, n_keys=cat_t.numel())
+
+
+def history_keys(topic_of_news, hist_index, hist_mask):
+    """hist_keys int32 [U, H] of a calibrated call: the group (``topic_of_news`` int32 [n_news], Calibration's) of every history
+    news, -1 where ``hist_mask`` is off."""
+    dev = topic_of_news.device
+    keys = topic_of_news[hist_index.to(dev).long()]
+    return torch.where(hist_mask.to(dev).bool(), keys, torch.full_like(keys, -1)).to(torch.int32).contiguous()
+
+
+def _calibrated(cal, hist_keys, positions, top, ids, k):
+    """The tail of every recommend entry under calibration: as ``_diverse``, with ops.calibrate_rows in ONE launch (its grid strides
+    over any number of rows, and row r reads history row r % U whatever the launch's first row would be)."""
+    weights = None if cal.weights is None else cal.weights.contiguous()
+    return _reranked(lambda s, i: ops.calibrate_rows(s, i, cal.topic_of_news, cal.n_keys, hist_keys, weights, cal.lam, cal.alpha, k),
+                     positions, top, ids, k, None)
 
 
 _NO_SLOTS = object()         # (not None: recommend_schedule hands ``slot_offsets`` to torch.as_tensor whatever it is)
@@ -333,21 +412,27 @@ _NO_SLOTS = object()         # (not None: recommend_schedule hands ``slot_offset
 
 def recommend(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime, k,
               n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, slot_offsets=_NO_SLOTS, mmr_lambda=None, shortlist=None,
-              similarity=None):
+              similarity=None, calibrate_lambda=None, calibrate_by='category', calibrate_alpha=rec.CALIBRATE_ALPHA, calibrate_weights=None):
     """recommend -> (positions int32 [U, k], scores fp32 [U, k]); with ``slot_offsets`` recommend_schedule -> [S, U, k] each:
     ``score_pool``, then the top k of every row of its scores -- for a schedule the rows of the [S U, C] view, in chunks of slots that
     keep the kernel's 65535 rows.  With ``mmr_lambda``: the top ``shortlist`` of every row the same way, then ``_diverse`` picks k of
-    them (the similarity row of a shortlist entry is its news id; -1 for an empty or excluded one)."""
+    them (the similarity row of a shortlist entry is its news id; -1 for an empty or excluded one).  With ``calibrate_lambda``: the
+    same shortlist and ids, of which ``_calibrated`` picks k against the topic mix of the row's history (row s U + u reads user u's)."""
     quota = topic_quota(corpus, max_per_topic, quota_by)
-    div = diversity(model, news_cache, k, mmr_lambda, shortlist, similarity)
+    cal = calibration(k, calibrate_lambda, calibrate_by, calibrate_alpha, calibrate_weights, mmr_lambda, shortlist)
+    div = diversity(model, news_cache, k, mmr_lambda, shortlist if cal is None else None, similarity)
+    cal = bind_calibration(cal, corpus, hist_index, news_cache.device)
     scores, gone = score_pool(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
                               cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k,
                               slot_offsets=None if slot_offsets is _NO_SLOTS else torch.as_tensor(slot_offsets))
-    if div is not None:
-        positions, top = _top_rows(scores, gone, quota, cand_index, div.shortlist)
+    if div is not None or cal is not None:
+        M = div.shortlist if div is not None else cal.shortlist
+        positions, top = _top_rows(scores, gone, quota, cand_index, M)
         cidx = newsEncoders._i32(cand_index.to(scores.device))
         ids = torch.where(positions >= 0, cidx[positions.clamp(min=0).long()], torch.full_like(positions, -1))
-        positions, top = _diverse(div, positions.view(-1, div.shortlist), top.view(-1, div.shortlist), ids.view(-1, div.shortlist), int(k))
+        positions, top, ids = positions.view(-1, M), top.view(-1, M), ids.view(-1, M)
+        positions, top = (_diverse(div, positions, top, ids, int(k)) if div is not None else
+                          _calibrated(cal, history_keys(cal.topic_of_news, hist_index, hist_mask), positions, top, ids, int(k)))
         return positions.view(scores.shape[:-1] + (int(k),)), top.view(scores.shape[:-1] + (int(k),))
     return _top_rows(scores, gone, quota, cand_index, int(k))
 
@@ -442,34 +527,43 @@ def _in_own_history(hist_index, hist_mask, offsets, cidx, pairs_per_step=1 << 18
 
 def recommend_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
                     cand_lifetime, k, n_src, pairs_per_pass, exclude_history, max_per_topic, quota_by, mmr_lambda=None, shortlist=None,
-                    similarity=None):
+                    similarity=None, calibrate_lambda=None, calibrate_by='category', calibrate_alpha=rec.CALIBRATE_ALPHA,
+                    calibrate_weights=None):
     """recommend_lists -> (positions int32 [U, k] into the user's list, scores fp32 [U, k]): ``score_lists``, then the top k of every
     segment of its scores.  With ``mmr_lambda``: the top ``shortlist`` of every segment the same way, then ``_diverse`` picks k of
-    them (the similarity row of a shortlist entry is the news id at its place in the user's list)."""
+    them (the similarity row of a shortlist entry is the news id at its place in the user's list).  With ``calibrate_lambda``: the
+    same shortlist and ids, of which ``_calibrated`` picks k against the topic mix of the user's history."""
     quota = topic_quota(corpus, max_per_topic, quota_by)
-    div = diversity(model, news_cache, k, mmr_lambda, shortlist, similarity)
+    cal = calibration(k, calibrate_lambda, calibrate_by, calibrate_alpha, calibrate_weights, mmr_lambda, shortlist)
+    div = diversity(model, news_cache, k, mmr_lambda, shortlist if cal is None else None, similarity)
+    cal = bind_calibration(cal, corpus, hist_index, news_cache.device)
     scores, offsets, gone = score_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets,
                                         cand_index, cand_freshness, cand_lifetime, n_src, pairs_per_pass, exclude_history, k=k)
-    return select_segments(scores, offsets, gone, quota, div, cand_index, k)
+    return select_segments(scores, offsets, gone, quota, div, cand_index, k, cal=cal,
+                           hist_keys=None if cal is None else history_keys(cal.topic_of_news, hist_index, hist_mask))
 
 
-def select_segments(scores, offsets, gone, quota, div, cand_index, k):
+def select_segments(scores, offsets, gone, quota, div, cand_index, k, cal=None, hist_keys=None):
     """The slates of a score buffer, the tail of ``recommend_lists`` and the selection ``util.evaluate_slates_on_device`` sweeps:
     ``scores`` fp32 [P] and ``offsets`` int64 [U + 1] (device) the lists' CSR, ``gone`` bool [P] or None the excluded pairs, ``quota``
     a TopicQuota or None, ``div`` a Diversity or None, ``cand_index`` [P] the news of every pair -> (positions int32 [U, k] into the
     user's list, scores fp32 [U, k]): the top k of every segment, under the quota where one is given; with ``div`` the top
     ``div.shortlist`` the same way, of which ``_diverse`` picks k (the similarity row of a shortlist entry is the news id at its
-    place in the user's list).  Without a pair every slot holds -1 / -inf."""
+    place in the user's list); with ``cal`` (a Calibration whose target fields are filled; not together with ``div``) and
+    ``hist_keys`` int32 [U, H] (``history_keys``) the top ``cal.shortlist``, of which ``_calibrated`` picks k.  Without a pair every
+    slot holds -1 / -inf."""
     U, k = offsets.numel() - 1, int(k)
+    if div is not None and cal is not None:
+        raise ValueError('select_segments takes a Diversity or a Calibration, not both')
     if scores.numel() == 0:
         return (torch.full((U, k), -1, dtype=torch.int32, device=scores.device),
                 torch.full((U, k), float('-inf'), dtype=torch.float32, device=scores.device))
-    if div is None:
+    if div is None and cal is None:
         return _top_segments(scores, offsets, gone, quota, cand_index, k)
-    positions, top = _top_segments(scores, offsets, gone, quota, cand_index, div.shortlist)
+    positions, top = _top_segments(scores, offsets, gone, quota, cand_index, div.shortlist if div is not None else cal.shortlist)
     pair = (offsets[:-1].unsqueeze(1) + positions.clamp(min=0).long()).clamp(max=scores.numel() - 1)
     ids = torch.where(positions >= 0, newsEncoders._i32(cand_index.to(scores.device))[pair], torch.full_like(positions, -1))
-    return _diverse(div, positions, top, ids, k)
+    return _diverse(div, positions, top, ids, k) if div is not None else _calibrated(cal, hist_keys, positions, top, ids, k)
 
 
 def _top_segments(scores, offsets, gone, quota, cand_index, k):

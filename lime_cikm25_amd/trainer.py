@@ -45,7 +45,7 @@ class Trainer:
         computes the same table from (seed, epoch): no broadcast is needed.  Off by default: nothing changes without it.
         ``cne_recurrence_cache``: under the CNE content encoder both cached dev passes build the per-news recurrence cache once per
         epoch and score from it (util.compute_scores_cached / evaluate_cached_on_device, ``recurrence_cache``); off by default.
-        ``slate_eval``: dict(settings=[...], k=10, value=None) -- the dev pass of an epoch goes through
+        ``slate_eval``: dict(settings=[...], k=10, value=None, calibration=None) -- the dev pass of an epoch goes through
         util.evaluate_slates_on_device: the same rank file and metrics, and the sweep's per-setting dicts are kept on
         ``last_slate_metrics`` and printed, one line per setting.  It needs ``device_eval`` (ValueError without, and where the device
         pass does not apply); its settings are refused here, before any training.  None (default): the Trainer as it was.
@@ -57,10 +57,11 @@ class Trainer:
         if slate_eval is not None:                                             # refused first: nothing has touched the device yet
             if not device_eval:
                 raise ValueError('slate_eval evaluates the slates on the scores of the device dev pass: it needs device_eval=True')
-            unknown = sorted(set(slate_eval) - {'settings', 'k', 'value'}) if isinstance(slate_eval, dict) else None
+            unknown = sorted(set(slate_eval) - {'settings', 'k', 'value', 'calibration'}) if isinstance(slate_eval, dict) else None
             if unknown is None or unknown or 'settings' not in slate_eval:
-                raise ValueError('slate_eval must be dict(settings=[...], k=10, value=None), got %r' % (slate_eval,))
-            self.slate_eval = dict(settings=list(slate_eval['settings']), k=slate_eval.get('k', 10), value=slate_eval.get('value'))
+                raise ValueError('slate_eval must be dict(settings=[...], k=10, value=None, calibration=None), got %r' % (slate_eval,))
+            self.slate_eval = dict(settings=list(slate_eval['settings']), k=slate_eval.get('k', 10), value=slate_eval.get('value'),
+                                   calibration=slate_eval.get('calibration'))
         self.model, self.config, self.corpus, self.run_index = model, config, corpus, run_index
         self.rank, self.world = 0, 1
         if 'WORLD_SIZE' in os.environ and int(os.environ['WORLD_SIZE']) > 1:
@@ -102,7 +103,8 @@ class Trainer:
         if self.slate_eval is not None:
             if not self.device_eval:
                 raise ValueError('slate_eval needs the device dev pass, which serves a corpus with dev_labels under lifetime_type user_topic')
-            util.check_slate_settings(model, self.dc, self.slate_eval['settings'], self.slate_eval['k'], self.slate_eval['value'])
+            util.check_slate_settings(model, self.dc, self.slate_eval['settings'], self.slate_eval['k'], self.slate_eval['value'],
+                                      calibration=self.slate_eval['calibration'])
         self.device_sampling = bool(device_sampling)
         self.train_split = DeviceBehaviors.train_resident(self.dc, corpus, config.negative_sample_num) if self.device_sampling else None
         self.step = TrainStep(model, lr=config.lr, weight_decay=config.weight_decay, gradient_clip_norm=config.gradient_clip_norm)
@@ -154,7 +156,8 @@ class Trainer:
             for s, m in zip(self.slate_eval['settings'], self.last_slate_metrics):
                 print('Epoch %d : slates %s: nDCG@%d = %.4f  RR = %.4f  hit = %.4f  recall = %.4f  ILD = %.4f  topics = %.2f  filled = %.2f'
                       % (e, {k: v for k, v in s.items() if k != 'similarity'}, self.slate_eval['k'], m['ndcg'], m['rr'], m['hit'],
-                         m['recall'], m['ild'], m['topics'], m['filled']))
+                         m['recall'], m['ild'], m['topics'], m['filled'])
+                      + ('  miscalibration = %.4f' % m['miscalibration'] if 'miscalibration' in m else ''))
             return metrics
         if self.cached_eval and self.device_eval:
             return util.evaluate_cached_on_device(self.model, self.dev, self.corpus.dev_indices, self.corpus.dev_labels, result_file=out,

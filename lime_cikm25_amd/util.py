@@ -268,18 +268,21 @@ def evaluate_cached_on_device(model, behaviors, indices, labels, result_file=Non
 
 
 # ---- the slates a selection setting makes of the dev split, and what they are worth (csrc/slate_metrics.hip) ----------------------------
-SLATE_SETTING_KEYS = ('max_per_topic', 'quota_by', 'mmr_lambda', 'shortlist', 'similarity', 'topic_by')
+SLATE_SETTING_KEYS = ('max_per_topic', 'quota_by', 'mmr_lambda', 'shortlist', 'similarity', 'topic_by', 'calibrate_lambda', 'calibrate_by',
+                      'calibrate_alpha')
 SLATE_RESULT_KEYS = ('ndcg', 'rr', 'hit', 'recall', 'ild', 'topics', 'filled', 'value')        # per_slate's columns, in order
 
 
-def check_slate_settings(model, corpus, settings, k, value=None, num=None):
-    """The refusals of ``evaluate_slates_on_device`` over ``settings`` / ``k`` / ``value`` (ValueError; nothing is launched): a list of
-    dicts over SLATE_SETTING_KEYS, each refused as ``serving.topic_quota`` / ``serving.diversity`` refuse its arguments; ``topic_by``
-    'category' (default) or 'topic'; MMR without a ``similarity`` needs a model with a per-news content cache.  -> per setting
-    (TopicQuota or None, (lam, shortlist) or None, similarity or None, topic_by)."""
+def check_slate_settings(model, corpus, settings, k, value=None, num=None, calibration=None, H=None):
+    """The refusals of ``evaluate_slates_on_device`` over ``settings`` / ``k`` / ``value`` / ``calibration`` (ValueError; nothing is
+    launched): a list of dicts over SLATE_SETTING_KEYS, each refused as ``serving.topic_quota`` / ``serving.diversity`` /
+    ``serving.calibration`` refuse its arguments (``H``: the history slots of the split, where known); ``topic_by`` 'category'
+    (default) or 'topic'; MMR without a ``similarity`` needs a model with a per-news content cache; ``calibration`` None, 'category'
+    or 'topic'.  -> per setting (TopicQuota or None, (lam, shortlist) or None, similarity or None, topic_by, Calibration or None)."""
     import numbers
 
     from . import serving
+    from .recommend import CALIBRATE_ALPHA
     if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= 128:
         raise ValueError('evaluate_slates_on_device keeps 1 <= k <= 128 news per slate (lime_slate_metrics_f32), got k = %r' % (k,))
     if not isinstance(settings, (list, tuple)) or not all(isinstance(s, dict) for s in settings):
@@ -290,8 +293,11 @@ def check_slate_settings(model, corpus, settings, k, value=None, num=None):
     elif value is not None and (not isinstance(value, torch.Tensor) or value.dim() != 1 or (num is not None and value.numel() != num)):
         raise ValueError("value must be 'freshness', 'remaining', a tensor with one entry per row%s or None, got %s"
                          % ('' if num is None else ' ([%d])' % num, tuple(value.shape) if isinstance(value, torch.Tensor) else repr(value)))
+    if calibration not in (None, 'category', 'topic'):
+        raise ValueError("calibration must be None, 'category' or 'topic' (the groups of the miscalibration), got %r" % (calibration,))
     n_news = corpus.news_category.shape[0]
     stub = torch.empty((n_news, 0), dtype=torch.float32, device=corpus.news_category.device)    # (no cache yet: the table comes later)
+    histories = None if H is None else stub.new_empty((0, H))                # (the shape is all that is read of them)
     checked = []
     for i, s in enumerate(settings):
         unknown = sorted(set(s) - set(SLATE_SETTING_KEYS))
@@ -302,23 +308,32 @@ def check_slate_settings(model, corpus, settings, k, value=None, num=None):
         if topic_by not in ('category', 'topic'):
             raise ValueError("settings[%d]: topic_by must be 'category' or 'topic' (the (category, subCategory) pair), got %r" % (i, topic_by))
         quota = serving.topic_quota(corpus, s.get('max_per_topic'), s.get('quota_by', 'category'))
-        div = serving.diversity(model, stub, k, s.get('mmr_lambda'), s.get('shortlist'), s.get('similarity'))
+        cal = serving.calibration(k, s.get('calibrate_lambda'), s.get('calibrate_by', 'category'),
+                                  s.get('calibrate_alpha', CALIBRATE_ALPHA), None, s.get('mmr_lambda'), s.get('shortlist'))
+        div = serving.diversity(model, stub, k, s.get('mmr_lambda'), s.get('shortlist') if cal is None else None, s.get('similarity'))
+        cal = serving.bind_calibration(cal, corpus, histories, stub.device)
         if div is not None and div.table is None and model.reads_content_mask:
             raise ValueError('settings[%d]: %s -- give a similarity table' % (i, model._NO_CONTENT_CACHE))
-        checked.append((quota, None if div is None else (div.lam, div.shortlist), s.get('similarity'), topic_by))
+        checked.append((quota, None if div is None else (div.lam, div.shortlist), s.get('similarity'), topic_by, cal))
+    if calibration is not None:                                              # the metric's own limits: the groups and the history slots
+        serving.bind_calibration(serving.Calibration(1.0, k, calibration, CALIBRATE_ALPHA, None, None, 0), corpus, histories, stub.device)
     return checked
 
 
-def sweep_slate_settings(model, behaviors, news_cache, scores, indices, labels, settings, k=10, value=None, per_impression=False):
+def sweep_slate_settings(model, behaviors, news_cache, scores, indices, labels, settings, k=10, value=None, per_impression=False,
+                         calibration=None):
     """What ``evaluate_slates_on_device`` does behind its scoring pass: ``scores`` fp32 [num] (device), one per row of ``behaviors``;
     an impression (``evaluate.impression_layout`` of ``indices`` / ``labels``) is a list of candidates.  Per setting: the slates
     (``serving.select_segments``), then one ``ops.slate_metrics`` call; at the end ONE device -> host copy of every setting's sums
-    and counts.  -> one dict per setting (see ``evaluate_slates_on_device``)."""
+    and counts.  A calibrated setting selects against the impression's history -- the history of its first row, as the grouped dev
+    pass takes it --, and with ``calibration`` one ``ops.slate_miscalibration`` call per setting measures every slate against it.
+    -> one dict per setting (see ``evaluate_slates_on_device``)."""
     from . import serving
     from .device_data import topic_table_of
     from .evaluate import impression_layout
+    from .recommend import CALIBRATE_ALPHA
     b, dev = behaviors, scores.device
-    checked = check_slate_settings(model, b.corpus, settings, k, value, b.num)
+    checked = check_slate_settings(model, b.corpus, settings, k, value, b.num, calibration, _history_slots(b))
     offsets, row_labels, skip = impression_layout(indices, labels)
     if scores.numel() != row_labels.size or b.num != row_labels.size:
         raise ValueError('one score per (impression, candidate) row: %d scores, %d rows, %d labelled rows' % (scores.numel(), b.num, row_labels.size))
@@ -335,20 +350,37 @@ def sweep_slate_settings(model, behaviors, news_cache, scores, indices, labels, 
     default_table = serving.content_columns(model, news_cache)
     if default_table is not None and default_table.shape[1] % 4:
         default_table = None                                                 # (lime_slate_metrics_f32 reads rows in quads)
+    hist_keys = {}
+
+    def history_of(by):
+        """hist_keys int32 [n_imp, H] under ``by``: the history of every impression's first row (an impression without a row: no click)."""
+        if by not in hist_keys:
+            first = offsets[:-1].clamp(max=max(b.num - 1, 0))
+            rowless = (offsets[1:] <= offsets[:-1]).unsqueeze(1)
+            hist_keys[by] = serving.history_keys(topic_table_of(b.corpus, by)[0], b.hist_index[first], b.hist_mask[first].bool() & ~rowless)
+        return hist_keys[by]
     found = []
-    for quota, mmr, similarity, topic_by in checked:
+    for quota, mmr, similarity, topic_by, cal in checked:
         table = similarity if similarity is not None else default_table
         div = None if mmr is None else serving.diversity(model, news_cache, k, mmr[0], mmr[1], similarity)
-        positions, _ = serving.select_segments(scores, offsets, None, quota, div, cand_index, k)
+        positions, _ = serving.select_segments(scores, offsets, None, quota, div, cand_index, k, cal=cal,
+                                               hist_keys=None if cal is None else history_of(cal.by))
         topic_of_news, cat_t, _ = topic_table_of(b.corpus, topic_by)
+        miscal = None
+        if calibration is not None:
+            groups, cat_g, _ = topic_table_of(b.corpus, calibration)
+            value_m, status_m = ops.slate_miscalibration(positions, k, offsets, news, groups, cat_g.numel(), history_of(calibration),
+                                                         None, CALIBRATE_ALPHA)
+            counted = (status_m == 0) & (skip == 0)
+            miscal = (value_m, status_m, torch.stack([torch.where(counted, value_m, torch.zeros_like(value_m)).sum(), counted.sum().double()]))
         found.append((ops.slate_metrics(positions, k, offsets, news, row_labels, skip, value, table, topic_of_news, n_keys=cat_t.numel()),
-                      table is not None))
+                      table is not None, miscal))
     if not found:
         return []
-    host = torch.stack([torch.cat([f.sums, f.counts.double()]) for f, _ in found]).cpu().numpy()      # (counts < 2^53: exact)
-    results = []
-    for (f, has_table), row in zip(found, host):
-        sums, counts = row[:8], row[8:].astype(np.int64)
+    host = torch.stack([torch.cat([f.sums, f.counts.double()] + ([] if m is None else [m[2]])) for f, _, m in found]).cpu().numpy()
+    results = []                                                             # (counts < 2^53: exact)
+    for (f, has_table, miscal), row in zip(found, host):
+        sums, counts = row[:8], row[8:11].astype(np.int64)
         mean = lambda c, n: float(sums[c] / n) if n else float('nan')
         res = {name: mean(c, counts[0 if c < 4 else 1 if c == 4 else 2]) for c, name in enumerate(SLATE_RESULT_KEYS)}
         if not has_table:
@@ -356,21 +388,37 @@ def sweep_slate_settings(model, behaviors, news_cache, scores, indices, labels, 
         if value is None:
             res['value'] = float('nan')
         res.update(n_relevance=int(counts[0]), n_diversity=int(counts[1]), n_slates=int(counts[2]))
+        if miscal is not None:
+            res.update(miscalibration=float(row[11] / row[12]) if row[12] else float('nan'), n_calibration=int(row[12]))
         if per_impression:
             res.update(per_impression=f.per_slate, status=f.status)
+            if miscal is not None:
+                res.update(miscalibration_per_impression=miscal[0], miscalibration_status=miscal[1])
         results.append(res)
     return results
 
 
+def _history_slots(behaviors):
+    """The history slots of a split's rows, or None where it carries no [num, H] history (the refusals' stand-ins)."""
+    hist = getattr(behaviors, 'hist_index', None)
+    return hist.shape[1] if isinstance(hist, torch.Tensor) and hist.dim() == 2 else None
+
+
 def evaluate_slates_on_device(model, behaviors, indices, labels, settings, k=10, value=None, rows_per_forward=None,
                               rows_per_pass=DEVICE_EVAL_ROWS_PER_PASS, grouped=False, per_impression=False, result_file=None,
-                              recurrence_cache=False):
+                              recurrence_cache=False, calibration=None):
     """The dev split scored ONCE, and a sweep of selection settings evaluated on those scores without a host round trip: how much
     nDCG@k does a quota or an MMR trade-off cost on the labelled impressions, and how much diversity does it buy?
 
     ``settings``: a list of dicts, one per setting, over ``max_per_topic`` / ``quota_by`` (Model.recommend's quota), ``mmr_lambda`` /
-    ``shortlist`` / ``similarity`` (its MMR) and ``topic_by`` ('category', the default, or 'topic': the keys behind 'topics'); ``{}``
-    is the plain top k.  They are refused as ``serving.topic_quota`` / ``serving.diversity`` refuse them, before any scoring.
+    ``shortlist`` / ``similarity`` (its MMR), ``calibrate_lambda`` / ``calibrate_by`` / ``calibrate_alpha`` (its calibration, against
+    the impression's history: the history of its first row; ``shortlist`` is read with either lambda) and ``topic_by`` ('category',
+    the default, or 'topic': the keys behind 'topics'); ``{}`` is the plain top k.  They are refused as ``serving.topic_quota`` /
+    ``serving.diversity`` / ``serving.calibration`` refuse them, before any scoring.
+    ``calibration``: None, or 'category' / 'topic' -- every setting's dict also holds 'miscalibration', the mean of
+    ``ops.slate_miscalibration`` (KL of the impression's history mix against the slate's, at recommend.CALIBRATE_ALPHA) over the
+    'n_calibration' slates where it is defined (status 0) and ``skip`` is unset, nan if there are none; with ``per_impression`` also
+    'miscalibration_per_impression' fp64 [n_imp] and 'miscalibration_status' int32 [n_imp].
     ``value``: 'freshness', 'remaining' (the remaining lifetime under config.lifetime_type) or a [num] tensor, one number per row;
     None: none.  The other arguments are ``evaluate_cached_on_device``'s, and so are the refusals (``grouped``, the chunk rule, CNE).
 
@@ -384,7 +432,7 @@ def evaluate_slates_on_device(model, behaviors, indices, labels, settings, k=10,
     the 'n_diversity' labelled impressions with >= 2 filled slots, 'topics' (distinct keys), 'filled' and 'value' over the
     'n_slates' with >= 1; nan where nothing was counted or the input is missing.  With ``per_impression`` a dict also holds
     'per_impression' fp64 [n_imp, 8] (the columns in SLATE_RESULT_KEYS' order) and 'status' int32 [n_imp], device tensors."""
-    check_slate_settings(model, behaviors.corpus, settings, k, value, behaviors.num)
+    check_slate_settings(model, behaviors.corpus, settings, k, value, behaviors.num, calibration, _history_slots(behaviors))
     was_training = model.training
     model.eval()
     try:
@@ -394,4 +442,4 @@ def evaluate_slates_on_device(model, behaviors, indices, labels, settings, k=10,
     metrics, scores = evaluate_cached_on_device(model, behaviors, indices, labels, result_file=result_file, rows_per_forward=rows_per_forward,
                                                 rows_per_pass=rows_per_pass, return_scores=True, recurrence_cache=recurrence_cache,
                                                 grouped=grouped, news_cache=cache)
-    return metrics, sweep_slate_settings(model, behaviors, cache, scores, indices, labels, settings, k, value, per_impression)
+    return metrics, sweep_slate_settings(model, behaviors, cache, scores, indices, labels, settings, k, value, per_impression, calibration)
