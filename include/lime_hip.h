@@ -579,6 +579,22 @@ int lime_topic_rep_f32(const int32_t* cat, const int32_t* sub, const float* cat_
                        float* emb_out, int64_t ld_emb, int64_t rows, void* stream);
 
 /*
+ * lime_news_keys_f32: what the tail over the distinct news of a batch (lime_compact_batch) takes from the compact keys, in one launch
+ * over `rows` = the capacity n + 1 (unused slots hold key 0: a valid id and bucket).  For compact news j:
+ *   pair[j]                           = bucket(fresh[j]) * nb + bucket(life[j])   (the rule of lime_bucketize_f32 when cuts == NULL
+ *                                       and nb == 10, else of lime_bucketize_cuts_f32 with n_cuts == nb - 1 ascending device cut points)
+ *   xin[j, col0 .. col0 + dout)       = lime_topic_rep_f32's row (same lanes, same order of the sums: the same bits)
+ *   xin[rows + j, col0 .. col0 + dout) = the same row again (the title half and the body half of the intent layers' input)
+ *   xin[j | rows + j, col0 + dout .. ldx) = 0                                     (the pad columns that keep the rows 16-byte aligned)
+ *   emb_out[j, 0 .. dc + ds)          = the two raw embedding rows
+ * xin is [2 rows, ldx]; its columns [0, col0) are not touched (lime_news_xin_f32 writes them).  w [dout, dc + ds]; bias may be NULL.
+ */
+int lime_news_keys_f32(const int32_t* cat, const int32_t* sub, const float* fresh, const float* life, const float* cuts, int32_t n_cuts,
+                       int32_t nb, const float* cat_table, const float* sub_table, int32_t dc, int32_t ds, const float* w,
+                       const float* bias, int32_t dout, float* xin, int64_t ldx, int32_t col0, float* emb_out, int64_t ld_emb,
+                       int32_t* pair, int64_t rows, void* stream);
+
+/*
  * lime_intent_fuse_f32: the tail of newsEncoders.CROWN.forward (:355-371).
  *   intents   [2, M, k, D]  title rows then body rows (the relu'd intent embeddings, :288)
  *   att_hidden[2, M, k, A]  tanh(affine1(intents)) (layers.py:288)

@@ -169,21 +169,21 @@ __global__ __launch_bounds__(256) void batch_count_kernel(const SeqSide t, const
     else count_seq(b.ids, w - n, b.S, b.live_cnt);
 }
 
-// what seq_scan_kernel writes for one side, from the scanned partials of this thread's range [lo, hi)
-__device__ __forceinline__ void scan_side_write(const SeqSide& d, int n, int lo, int hi, int ps, int pt, int n_live, int n_tok) {
-    const int tid = threadIdx.x;
-    for (int s = lo; s < hi; ++s) {
-        const int c = d.live_cnt[s];
-        if (c > 0) {
-            d.seq_src[ps] = s;
-            d.seq_inv[s] = ps;
-            d.tok_off[ps] = pt;
-            ++ps;
-            pt += c;
-        } else {
-            d.seq_inv[s] = n_live;
-        }
+// what seq_scan_kernel writes for sequence s of one side (c live tokens) at this thread's running prefixes ps / pt ...
+__device__ __forceinline__ void scan_side_put(const SeqSide& d, int s, int c, int& ps, int& pt, int n_live) {
+    if (c > 0) {
+        d.seq_src[ps] = s;
+        d.seq_inv[s] = ps;
+        d.tok_off[ps] = pt;
+        ++ps;
+        pt += c;
+    } else {
+        d.seq_inv[s] = n_live;
     }
+}
+// ... and behind the live sequences: the unused slots, the end of the token list, the counts
+__device__ __forceinline__ void scan_side_tail(const SeqSide& d, int n, int n_live, int n_tok) {
+    const int tid = threadIdx.x;
     for (int i = n_live + 1 + tid; i <= n; i += 1024) d.seq_src[i] = -1;
     if (tid == 0) {
         d.seq_src[n_live] = -1;
@@ -196,64 +196,110 @@ __device__ __forceinline__ void scan_side_write(const SeqSide& d, int n, int lo,
     }
 }
 
-// pass 2: ONE workgroup: the ordered scans of seq_scan_kernel for the titles and for the bodies, and the news level
+// everything the scan reads of one news: the live tokens of its title and body, and its key
+struct NewsRow { int ct, cb, cat, sub, fresh, life; };
+__device__ __forceinline__ NewsRow load_row(const SeqSide& t, const SeqSide& b, const NewsSide& w, int s) {
+    return {t.live_cnt[s], b.live_cnt[s], w.cat[s], w.sub[s], w.fresh[s], w.life[s]};
+}
+
+// pass 2: ONE workgroup: the ordered scans of seq_scan_kernel for the titles and for the bodies, and the news level.  A thread owns
+// per = ceil(n / 1024) consecutive news.  One workgroup hides no latency, so the kernel's time is its chain of dependent round trips
+// to memory, and there are two: PER > 0 (per <= PER, picked by the host) loads the rows of the thread's range into registers at the
+// start -- 6 PER independent loads, no branch between them -- and the key of the representative once it is known; every other step
+// reads registers.  PER == 0 (any n) reads a row's six words afresh in each of its three passes, still without a branch between the
+// loads.  The five scans (title sequences / tokens, body sequences / tokens, live news) go together through ONE wave-level scan
+// (shuffles, no LDS) and one pass over the 16 wave totals, the representative through a wave-level minimum: two workgroup barriers.
+template <int PER>
 __global__ __launch_bounds__(1024) void batch_scan_kernel(const SeqSide t, const SeqSide b, const NewsSide w, int n) {
-    __shared__ int part[5][1024];                 // title sequences / tokens, body sequences / tokens, live news
-    const int tid = threadIdx.x;
+    __shared__ int wave_first[16];
+    __shared__ int wave_tot[5][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int per = (n + 1023) / 1024;
     const int lo = min(n, tid * per), hi = min(n, lo + per);
-    // the representative: the first news whose title and body are both all padding (ordered minimum over the threads' ranges)
-    int first = 0x7FFFFFFF;
-    for (int s = hi - 1; s >= lo; --s)
-        if (t.live_cnt[s] == 0 && b.live_cnt[s] == 0) first = s;
-    part[0][tid] = first;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (tid < o) part[0][tid] = min(part[0][tid], part[0][tid + o]);
-        __syncthreads();
-    }
-    first = part[0][0];
-    __syncthreads();
-    const bool has_pad = first != 0x7FFFFFFF;
-    int kc = 0, ks = 0, kf = 0, kl = 0;
-    if (has_pad) { kc = w.cat[first]; ks = w.sub[first]; kf = w.fresh[first]; kl = w.life[first]; }
-    auto repeats = [&](int s) {
-        return has_pad && t.live_cnt[s] == 0 && b.live_cnt[s] == 0 && w.cat[s] == kc && w.sub[s] == ks && w.fresh[s] == kf && w.life[s] == kl;
-    };
-    int v[5] = {0, 0, 0, 0, 0};
-    for (int s = lo; s < hi; ++s) {
-        const int ct = t.live_cnt[s], cb = b.live_cnt[s];
-        v[0] += ct > 0; v[1] += ct;
-        v[2] += cb > 0; v[3] += cb;
-        v[4] += !repeats(s);
-    }
+    NewsRow reg[PER > 0 ? PER : 1];
+    if (PER > 0) {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) part[i][tid] = v[i];
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {          // Hillis-Steele inclusive scan over the 1024 partials (five arrays)
-        int a[5] = {0, 0, 0, 0, 0};
-        if (tid >= o) {
+        for (int i = 0; i < PER; ++i) reg[i] = load_row(t, b, w, min(lo + i, n - 1));       // (clamped: a valid address whatever the range)
+    }
+    // f(s, row of s) for the news of the thread's range, in order: PER > 0 unrolls over the registers, PER == 0 loops and loads
+    auto each_own = [&](auto&& f) {
+        if constexpr (PER > 0) {
 #pragma unroll
-            for (int i = 0; i < 5; ++i) a[i] = part[i][tid - o];
+            for (int i = 0; i < PER; ++i) {
+                if (lo + i < hi) f(lo + i, reg[i]);
+            }
+        } else {
+            for (int s = lo; s < hi; ++s) f(s, load_row(t, b, w, s));
         }
-        __syncthreads();
+    };
+    // the representative: the first news whose title and body are both all padding (ordered minimum over the threads' ranges);
+    // the four scans that do not depend on it are summed on the way
+    int first = 0x7FFFFFFF;
+    int v[5] = {0, 0, 0, 0, 0};
+    each_own([&](int s, const NewsRow& r) {
+        v[0] += r.ct > 0; v[1] += r.ct;
+        v[2] += r.cb > 0; v[3] += r.cb;
+        if (r.ct == 0 && r.cb == 0) first = min(first, s);
+    });
 #pragma unroll
-        for (int i = 0; i < 5; ++i) part[i][tid] += a[i];
-        __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
+    if (lane == 0) wave_first[wave] = first;
+    __syncthreads();
+    first = wave_first[lane & 15];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
+    const bool has_pad = first != 0x7FFFFFFF;
+    NewsRow key = {0, 0, 0, 0, 0, 0};
+    if (has_pad) key = load_row(t, b, w, first);
+    auto repeats = [&](const NewsRow& r) {        // (bitwise: one test, no branch per member)
+        return has_pad & (r.ct == 0) & (r.cb == 0) & (r.cat == key.cat) & (r.sub == key.sub) & (r.fresh == key.fresh) & (r.life == key.life);
+    };
+    each_own([&](int, const NewsRow& r) { v[4] += !repeats(r); });
+    // inclusive scan of the five partials over the wave's lanes, ...
+    int inc[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) inc[i] = v[i];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int up = __shfl_up(inc[i], o);
+            if (lane >= o) inc[i] += up;
+        }
     }
-    scan_side_write(t, n, lo, hi, part[0][tid] - v[0], part[1][tid] - v[1], part[0][1023], part[1][1023]);
-    scan_side_write(b, n, lo, hi, part[2][tid] - v[2], part[3][tid] - v[3], part[2][1023], part[3][1023]);
-    const int n_live = part[4][1023];
-    int pn = part[4][tid] - v[4];
-    for (int s = lo; s < hi; ++s) {
-        if (repeats(s)) {
+    if (lane == 63) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) wave_tot[i][wave] = inc[i];
+    }
+    __syncthreads();
+    // ... then every wave scans the 16 wave totals itself (lanes 0 .. 15) and takes its own offset and the grand total from them
+    int ex[5], tot[5];                            // exclusive prefix of this thread's range, total over the workgroup
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        int x = lane < 16 ? wave_tot[i][lane] : 0;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            const int up = __shfl_up(x, o);
+            if (lane >= o) x += up;
+        }
+        const int before = __shfl(x, wave > 0 ? wave - 1 : 0);
+        tot[i] = __shfl(x, 15);
+        ex[i] = (wave > 0 ? before : 0) + inc[i] - v[i];
+    }
+    const int n_live = tot[4];
+    each_own([&](int s, const NewsRow& r) {
+        scan_side_put(t, s, r.ct, ex[0], ex[1], tot[0]);
+        scan_side_put(b, s, r.cb, ex[2], ex[3], tot[2]);
+        if (repeats(r)) {
             w.news_inv[s] = n_live;
         } else {
-            w.news_src[pn] = s;
-            w.news_inv[s] = pn;
-            ++pn;
+            w.news_src[ex[4]] = s;
+            w.news_inv[s] = ex[4];
+            ++ex[4];
         }
-    }
+    });
+    scan_side_tail(t, n, tot[0], tot[1]);
+    scan_side_tail(b, n, tot[2], tot[3]);
     for (int i = n_live + 1 + tid; i <= n; i += 1024) w.news_src[i] = -1;
     if (tid == 0) {
         const int n_news = n_live + (has_pad ? 1 : 0);
@@ -335,7 +381,8 @@ extern "C" int lime_compact_batch(const int32_t* ids_t, int32_t T, int32_t pad_b
                         (int*)fresh_c, (int*)life_c, news_counts, count_mult};
     const int seq_blocks = (n + 1 + 3) / 4;
     hipLaunchKernelGGL(batch_count_kernel, dim3((unsigned)((2L * n + 3) / 4)), dim3(256), 0, s, t, b, n);
-    hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(1024), 0, s, t, b, w, n);
+    if ((n + 1023) / 1024 <= 2) hipLaunchKernelGGL(batch_scan_kernel<2>, dim3(1), dim3(1024), 0, s, t, b, w, n);     // (the thread's rows in registers)
+    else hipLaunchKernelGGL(batch_scan_kernel<0>, dim3(1), dim3(1024), 0, s, t, b, w, n);
     hipLaunchKernelGGL(batch_emit_kernel, dim3((unsigned)(2 * seq_blocks + (n + 1 + 255) / 256)), dim3(256), 0, s, t, b, w, n, seq_blocks);
     return lime_check_launch("lime_compact_batch");
 }

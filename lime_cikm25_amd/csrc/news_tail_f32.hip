@@ -4,19 +4,21 @@
 // All reductions are fixed-order (wave64 shuffles, then LDS across the four waves): results are bitwise reproducible run to run.
 // Their backward: tail_backward_f32.hip.
 #include "common.h"
+#include "dev_helpers.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // topic representation: one 64-thread workgroup per news
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void topic_rep_kernel(const int* __restrict__ cat, const int* __restrict__ sub,
-                                                        const float* __restrict__ cat_table, const float* __restrict__ sub_table,
-                                                        int dc, int ds, const float* __restrict__ w, const float* __restrict__ bias,
-                                                        int dout, float* __restrict__ out, long ldo, float* __restrict__ emb_out,
-                                                        long ld_emb) {
-    __shared__ float e[256];
-    const long r = blockIdx.x;
+// Row r of the topic representation, by the 64 threads of a workgroup: the raw embedding pair into emb_out (when given), the dense
+// layer over it into out and -- when given -- the same values into out2 (a second copy of the row: each lane stores what it summed).
+// Stated once for topic_rep_kernel and news_keys_kernel: same lanes, same order of the sums.
+__device__ __forceinline__ void topic_rep_row(long r, const int* __restrict__ cat, const int* __restrict__ sub,
+                                              const float* __restrict__ cat_table, const float* __restrict__ sub_table, int dc, int ds,
+                                              const float* __restrict__ w, const float* __restrict__ bias, int dout,
+                                              float* __restrict__ out, float* __restrict__ out2, long ldo, float* __restrict__ emb_out,
+                                              long ld_emb, float* e) {
     const int din = dc + ds;
     const float* crow = cat_table + (long)cat[r] * dc;
     const float* srow = sub_table + (long)sub[r] * ds;
@@ -31,9 +33,43 @@ __global__ __launch_bounds__(64) void topic_rep_kernel(const int* __restrict__ c
             const float* wr = w + (long)o * din;
             float acc = 0.f;
             for (int i = 0; i < din; ++i) acc += wr[i] * e[i];
-            out[r * ldo + o] = acc + (bias ? bias[o] : 0.f);
+            const float y = acc + (bias ? bias[o] : 0.f);
+            out[r * ldo + o] = y;
+            if (out2) out2[r * ldo + o] = y;
         }
     }
+}
+
+__global__ __launch_bounds__(64) void topic_rep_kernel(const int* __restrict__ cat, const int* __restrict__ sub,
+                                                        const float* __restrict__ cat_table, const float* __restrict__ sub_table,
+                                                        int dc, int ds, const float* __restrict__ w, const float* __restrict__ bias,
+                                                        int dout, float* __restrict__ out, long ldo, float* __restrict__ emb_out,
+                                                        long ld_emb) {
+    __shared__ float e[256];
+    topic_rep_row(blockIdx.x, cat, sub, cat_table, sub_table, dc, ds, w, bias, dout, out, nullptr, ldo, emb_out, ld_emb, e);
+}
+
+// What the distinct news of a batch need from their keys, one 64-thread workgroup per compact news j of `rows` (the capacity: unused
+// slots hold key 0, a valid id and bucket): the bucket pair, the topic row into BOTH halves of the intent layers' input xin
+// [2 rows, ldx] (rows j and rows + j, columns [col0, col0 + dout)), zeros into the pad columns [col0 + dout, ldx) of both, and the raw
+// embedding pair into emb_out.  Columns [0, col0) belong to lime_news_xin_f32.
+__global__ __launch_bounds__(64) void news_keys_kernel(const int* __restrict__ cat, const int* __restrict__ sub,
+                                                        const float* __restrict__ fresh, const float* __restrict__ life,
+                                                        const float* __restrict__ cuts, int n_cuts, int nb,
+                                                        const float* __restrict__ cat_table, const float* __restrict__ sub_table,
+                                                        int dc, int ds, const float* __restrict__ w, const float* __restrict__ bias,
+                                                        int dout, float* __restrict__ xin, long ldx, int col0, long rows,
+                                                        float* __restrict__ emb_out, long ld_emb, int* __restrict__ pair) {
+    __shared__ float e[256];
+    const long j = blockIdx.x;
+    if (threadIdx.x == 0) pair[j] = lime_dev::bucket_of(fresh[j], cuts, n_cuts) * nb + lime_dev::bucket_of(life[j], cuts, n_cuts);
+    float* top = xin + col0;
+    float* bot = xin + rows * ldx + col0;
+    for (int c = dout + threadIdx.x; c < (int)ldx - col0; c += 64) {
+        top[j * ldx + c] = 0.f;
+        bot[j * ldx + c] = 0.f;
+    }
+    topic_rep_row(j, cat, sub, cat_table, sub_table, dc, ds, w, bias, dout, top, bot, ldx, emb_out, ld_emb, e);
 }
 
 }  // namespace
@@ -50,6 +86,24 @@ extern "C" int lime_topic_rep_f32(const int32_t* cat, const int32_t* sub, const 
     hipLaunchKernelGGL(topic_rep_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, cat, sub, cat_table, sub_table, dc,
                        ds, w, bias, dout, out, (long)ldo, emb_out, (long)ld_emb);
     return lime_check_launch("lime_topic_rep_f32");
+}
+
+extern "C" int lime_news_keys_f32(const int32_t* cat, const int32_t* sub, const float* fresh, const float* life, const float* cuts,
+                                  int32_t n_cuts, int32_t nb, const float* cat_table, const float* sub_table, int32_t dc, int32_t ds,
+                                  const float* w, const float* bias, int32_t dout, float* xin, int64_t ldx, int32_t col0, float* emb_out,
+                                  int64_t ld_emb, int32_t* pair, int64_t rows, void* stream) {
+    LIME_REQUIRE(cat && sub && fresh && life && cat_table && sub_table && w && xin && emb_out && pair, LIME_ERR_BAD_ARG,
+                 "lime_news_keys_f32: NULL pointer");
+    LIME_REQUIRE(cuts ? (n_cuts >= 0 && n_cuts <= 4096 && nb == n_cuts + 1) : nb == 10, LIME_ERR_BAD_ARG,
+                 "lime_news_keys_f32: nb %d does not match the cut points (%d given; 10 buckets built in)", nb, cuts ? n_cuts : 9);
+    LIME_REQUIRE(dc > 0 && ds > 0 && dc + ds <= 256, LIME_ERR_UNSUPPORTED, "lime_news_keys_f32: dc + ds must be in (0, 256]");
+    LIME_REQUIRE(dout > 0 && col0 >= 0 && ldx >= (int64_t)col0 + dout && ldx < 0x7FFFFFFFL && ld_emb >= dc + ds, LIME_ERR_BAD_ARG,
+                 "lime_news_keys_f32: bad dims dout=%d col0=%d ldx=%ld ld_emb=%ld", dout, col0, (long)ldx, (long)ld_emb);
+    if (rows <= 0) return rows == 0 ? LIME_OK : LIME_ERR_BAD_ARG;
+    LIME_REQUIRE(rows < 0x7FFFFFFFL, LIME_ERR_UNSUPPORTED, "lime_news_keys_f32: too many rows");
+    hipLaunchKernelGGL(news_keys_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, cat, sub, fresh, life, cuts, n_cuts, nb,
+                       cat_table, sub_table, dc, ds, w, bias, dout, xin, (long)ldx, col0, (long)rows, emb_out, (long)ld_emb, pair);
+    return lime_check_launch("lime_news_keys_f32");
 }
 
 namespace {

@@ -171,15 +171,29 @@ class Model(nn.Module):
         ``load_state_dict``, ``TrainStep`` and ``.to()`` need no such call."""
         ops.note_param_write()
 
+    def _kept_key(self):
+        """What the captured graphs depend on beyond their inputs: the content encoder's weight products and LIME's occurrence tables
+        (``products_key`` / ``tables_key``: buffer generations and whether the forward takes them).  Brings both up to date, in place
+        and on the current stream, on the way.  None: the encoders keep nothing."""
+        # which of the two functions the encoders have is found once per news encoder object: the look-ups (a failing ``hasattr``
+        # through nn.Module.__getattr__ above all) cost as much as the keys themselves, in front of every graph replay
+        ne = self._modules['news_encoder']
+        found = self.__dict__.get('_kept_key_fns')
+        enc = ne if self.plain else ne._modules['base_news_encoder']              # (``content_encoder`` without the attribute walk)
+        if found is None or found[0] is not ne or found[1] is not enc:
+            found = self.__dict__['_kept_key_fns'] = (ne, enc, tuple(getattr(m, name) for m, name in ((enc, 'products_key'), (ne, 'tables_key'))
+                                                                      if hasattr(m, name)))
+        keys = tuple(fn() for fn in found[2])
+        return keys or None
+
     def _sync_weight_products(self):
-        """Before a scoring forward: bring the content encoder's weight products up to date (in place, on the current stream) and drop
-        the captured graphs if one of their buffers had to move or the forward changed between the two first-layer paths."""
-        enc = self.content_encoder
-        if hasattr(enc, 'products_key'):
-            key = enc.products_key()
-            if key != getattr(self, '_products_key', None):
-                self._products_key = key
-                self._graphs = {}
+        """Before a scoring forward: bring what the encoders keep across forwards up to date (in place, on the current stream) and drop
+        the captured graphs if one of those buffers had to move or the forward changed between taking them and computing its own.  An
+        in-place refresh keeps the graphs."""
+        key = self._kept_key()
+        if key != getattr(self, '_products_key', None):
+            self._products_key = key
+            self._graphs = {}
 
     def initialize(self):
         self.news_encoder.initialize()
@@ -237,9 +251,7 @@ class Model(nn.Module):
                 out = self._forward_impl(*static)
             entry = (graph, [static[i] for i in _USED], out)
             self._graphs[key] = entry
-            enc = self.content_encoder
-            if hasattr(enc, 'products_key'):
-                self._products_key = enc.products_key()      # (the warm-up may have built the weight products this graph reads)
+            self._products_key = self._kept_key()            # (the warm-up may have built the weight products / tables this graph reads)
         graph, static_used, out = entry
         keep = ops.multi_copy(list(zip(static_used, used)))          # one launch for all the inputs
         graph.replay()

@@ -319,23 +319,28 @@ class LIME(nn.Module):
         if (NEWS_DEDUP and recurrence is None and title_text is not None and hasattr(enc, 'news_dedup_applicable') and
                 enc.news_dedup_applicable(title_text, content_text)):
             # the tail once per distinct news: the compaction (three launches on branch 3, in front of the encoders' preparation) also
-            # lists the news; the bucket pair and the topic rows are taken from the compact keys, `project` runs over n_news rows and
-            # the result is expanded to the M slots -- the one launch this adds to the critical path
+            # lists the news; the bucket pair and the topic rows are taken from the compact keys (one launch on the content encoder's
+            # branch 4, which leaves the pair in nw.pair: int32 [M + 1], unused slots valid), `project` runs over n_news rows and the
+            # result is expanded to the M slots -- the one launch this adds to the critical path.  The table is the kept one, or
+            # computed here on the side stream (occurrence_tables)
             side3 = _side_stream(dev, 3)
             side3.wait_stream(main)
             with torch.cuda.stream(side3):
                 news = ops.compact_batch(title_text, content_text, category, subCategory, freshness.contiguous(), lifetime.contiguous(),
                                          count_mult=enc.intent_num)
             nw = news[2]
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                side.wait_event(nw.ready)                                    # the raw keys: no bucketize launch in front of the compaction
-                pair = torch.add(fe.buckets(nw.life_c), fe.buckets(nw.fresh_c), alpha=nb)                   # int32 [M + 1], unused slots valid
-                table, _ = self.occurrence_tables()
+            table = self._kept_tables()
+            forked = table is None
+            if forked:
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    table = self._compute_occurrence_tables()
             content = torch.empty((M + 1, cdim), dtype=torch.float32, device=dev)
-            enc.encode_flat(title_text, title_mask, content_text, category, subCategory, content, news=news)
-            main.wait_stream(side)
-            rep_c = ops.linear(content, self.project.weight[:, :cdim], None, res=table, res_ids=pair, m_dev=nw.n_news)
+            enc.encode_flat(title_text, title_mask, content_text, category, subCategory, content, news=news,
+                            buckets=(nb, fe.cuts_on(dev)))
+            if forked:
+                main.wait_stream(side)
+            rep_c = ops.linear(content, self.project.weight[:, :cdim], None, res=table[0], res_ids=nw.pair, m_dev=nw.n_news)
             return ops.gather_rows(nw.news_inv, rep_c, torch.empty((M, rep_c.shape[1]), dtype=torch.float32, device=dev))
         side.wait_stream(main)
         with torch.cuda.stream(side):
@@ -357,7 +362,62 @@ class LIME(nn.Module):
             add                T = F                        [nb^2, c]             (:154-155)
             gated              T = F,  Q = F . W_g[:, c:]^T + b_g                 (the freshness half of `gate`, :156-159)
 
-        Q is None except for 'gated'."""
+        Q is None except for 'gated'.
+
+        The tables depend on weights alone, so a scoring call takes them from ``OccurrenceTables`` (kept across calls, refreshed in
+        place under the staleness rule of ``WeightProducts``) where ``_kept_tables`` allows it, and computes them otherwise."""
+        kept = self._kept_tables()
+        return kept if kept is not None else self._compute_occurrence_tables()
+
+    def _table_sources(self):
+        """Every tensor ``occurrence_tables()`` is computed from, in a fixed order."""
+        fe = self.freshness_encoder
+        src = [fe.freshness_embedding.weight, fe.lifetime_embedding.weight, fe.dense.weight, fe.dense.bias]
+        if self.fusion_method == 'gated':
+            src += [self.gate.weight, self.gate.bias]
+        elif self.fusion_method == 'concat' and not isinstance(self.project, nn.Identity):
+            src += [self.project.weight, self.project.bias]
+        return src
+
+    def _kept_tables(self):
+        """(T, Q) from the module's ``OccurrenceTables``, current for the weights as they are now (stale ones are recomputed here, in
+        place and on the current stream), or None where the caller has to compute them: the switch ``WEIGHT_PREP_CACHE`` off, a CPU
+        module, autograd recording with a source that requires grad (a caller inside a training step: its weights move every step,
+        and whatever it builds on the tables must not alias a buffer that a later refresh overwrites), and a stream capture in
+        progress with stale tables (nothing can be computed outside the graph then)."""
+        src = kept_sources(self, '_table_paths', self._table_sources, self.fusion_method)
+        if not WEIGHT_PREP_CACHE or not src[0].is_cuda or (torch.is_grad_enabled() and any(t.requires_grad for t in src)):
+            return None
+        kept = getattr(self, '_tables', None)
+        state = weight_state(src, ops.PARAM_WRITES)
+        if kept is not None and weight_state_stale(kept.state, state) is None:
+            return kept.T, kept.Q
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        if kept is None:
+            kept = self._tables = OccurrenceTables()
+        with torch.no_grad():
+            kept.refresh(state, *self._compute_occurrence_tables())
+        return kept.T, kept.Q
+
+    def tables_key(self):
+        """Changes whenever a graph captured over ``encode_flat`` must not be replayed any more: a table buffer was allocated or
+        reallocated, or the forward switched between the kept tables and its own (``CROWN.products_key``'s counterpart).  Brings
+        existing tables up to date (in place) on the way; builds none.  None for the fusions whose ``encode_flat`` never reads the
+        tables ('add', 'gated', concat without a projection: their serving entries do, outside any captured graph)."""
+        if self.fusion_method != 'concat' or isinstance(self.project, nn.Identity):
+            return None
+        kept = getattr(self, '_tables', None)
+        used = kept is not None and self._kept_tables() is not None
+        return (None if kept is None else kept.generation, used)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.__dict__['_table_paths'] = None
+        self._tables = None                    # parameter storage moves (and maybe the device): nothing kept stays valid
+        return super()._apply(fn, *args, **kwargs)
+
+    def _compute_occurrence_tables(self):
+        """``occurrence_tables()`` from the current parameters, on the device and the current stream."""
         fe = self.freshness_encoder
         E, nb = fe.freshness_embedding.embedding_dim, fe.num_buckets
         cdim = self.base_news_encoder.news_embedding_dim
@@ -1071,6 +1131,9 @@ def compact_applicable_bf16(ids, transformer, nhead, E):
 # 0 (LIME_VOCAB_QKV=0): every forward derives what it needs from the weights itself -- in_proj over the batch's tokens, the
 # feed-forward weights packed per call -- as before ``WeightProducts`` (A/B runs)
 VOCAB_QKV = os.environ.get('LIME_VOCAB_QKV', '1') != '0'
+# 0 (LIME_WEIGHT_PREP_CACHE=0): the small weight-only preparation of a scoring forward -- CROWN's stacked intent weights, LIME's
+# occurrence tables -- is computed in every forward (and by every serving call) as before it was kept (A/B runs)
+WEIGHT_PREP_CACHE = os.environ.get('LIME_WEIGHT_PREP_CACHE', '1') != '0'
 
 
 def weight_state(sources, writes):
@@ -1087,12 +1150,69 @@ def weight_state_stale(recorded, current):
     'version' (an in-place write torch counted), 'writes' (a raw-pointer write was announced).  Pure: two tuples in, a word out."""
     if recorded is None:
         return 'never'
+    if recorded == current:                       # (one tuple comparison: the answer of nearly every forward)
+        return None
     (rec, rec_writes), (cur, cur_writes) = recorded, current
     if len(rec) != len(cur) or any(a[:2] != b[:2] for a, b in zip(rec, cur)):
         return 'moved'
     if any(a[2] != b[2] for a, b in zip(rec, cur)):
         return 'version'
     return 'writes' if rec_writes != cur_writes else None
+
+
+class SourcePaths:
+    """Where the source tensors of a kept result live below ``root``, so that every forward can fetch them without walking the module
+    tree through ``nn.Module.__getattr__`` (the walk cost more than the comparison it feeds: 8 us for LIME's six tensors, 26 us for
+    CROWN's, in front of every graph replay).  ``leaves``: (the owning module's parameter or buffer dictionary, name) per source, in the
+    order of the slow list they were found from; ``links``: (a module's child dictionary, name, child) for every hop on the way.
+    ``tensors()`` returns the sources as they are now -- a re-assigned parameter is read from its dictionary like any other -- or None
+    once a hop leads to another module than it did; the caller then asks the slow list again."""
+
+    def __init__(self, links, leaves, tag):
+        self.links, self.leaves, self.tag = links, leaves, tag
+
+    @classmethod
+    def find(cls, root, tensors, tag=None):
+        """The paths of ``tensors`` (found by identity among root's parameters and buffers), or None when one of them is not there."""
+        where = {}
+        for prefix, mod in root.named_modules(remove_duplicate=False):
+            for d in (mod._parameters, mod._buffers):
+                for name, t in d.items():
+                    if t is not None:
+                        where.setdefault(id(t), (prefix, d, name))
+        links, leaves, seen = [], [], set()
+        for t in tensors:
+            if id(t) not in where:
+                return None
+            prefix, d, name = where[id(t)]
+            leaves.append((d, name))
+            mod, path = root, ''
+            for hop in (prefix.split('.') if prefix else []):
+                child = mod._modules[hop]
+                path += '.' + hop
+                if path not in seen:
+                    seen.add(path)
+                    links.append((mod._modules, hop, child))
+                mod = child
+        return cls(links, leaves, tag)
+
+    def tensors(self, tag=None):
+        if tag != self.tag or any(d.get(name) is not child for d, name, child in self.links):
+            return None
+        return [d[name] for d, name in self.leaves]
+
+
+def kept_sources(module, slot, slow, tag=None):
+    """``slow()`` -- a module's list of source tensors -- through the ``SourcePaths`` kept in ``module.__dict__[slot]``: found at the
+    first call, asked from then on, found again when a hop or ``tag`` changed.  The module drops the slot in ``_apply``."""
+    paths = module.__dict__.get(slot)
+    if paths is not None:
+        ts = paths.tensors(tag)
+        if ts is not None:
+            return ts
+    ts = slow()
+    module.__dict__[slot] = SourcePaths.find(module, ts, tag)
+    return ts
 
 
 def vocab_qkv_applicable(S, E, nhead):
@@ -1118,7 +1238,10 @@ class WeightProducts:
         (ops.token_attention_vocab).  One forward of the flagship batch pushes 79k token rows through that GEMM against a
         50k-row table, and a dev pass scores thousands of batches between two weight updates;
       * per encoder and layer, the packed feed-forward weights of ``ops.ffn_pack_sp`` and the packed out_proj weight of
-        ``ops.oproj_pack_sp``.
+        ``ops.oproj_pack_sp``;
+      * ``intent``: the k intent layers' weights stacked row-wise with zero pad columns (``w`` [k D, ldx]) and their biases (``b``
+        [k D]), what the tail's one GEMM over the k layers reads (``WEIGHT_PREP_CACHE``; they were two cats, a pad and a copy per
+        forward).
 
     ``refresh`` recomputes them IN PLACE when ``weight_state_stale`` says so: captured HIP graphs hold the buffers' addresses.
     ``generation`` takes a new process-wide number whenever a buffer had to be (re)allocated or dropped instead; whoever holds graphs
@@ -1128,6 +1251,7 @@ class WeightProducts:
         self.state = None
         self.budget = budget               # bytes of [V, 3W] products this set was built under
         self.encoder = [{}, {}]            # title, body: dict(ew=, pew=, ffn=[(w1p, w2p) per layer], oproj=[wp per layer]); 'ew' / 'pew' absent over the budget
+        self.intent = {}                   # dict(w=, b=), or empty with WEIGHT_PREP_CACHE off
         self.generation = _next_generation()
         self.refreshes = 0                 # recomputations so far (tests, logs)
 
@@ -1140,8 +1264,9 @@ class WeightProducts:
         self.generation = _next_generation()
         return torch.empty(shape, dtype=dtype, device=device)
 
-    def refresh(self, state, table, encoders, nhead, budget):
-        """Recompute everything on the current stream.  encoders: (positional table, transformer, S) for title and body."""
+    def refresh(self, state, table, encoders, nhead, budget, intent_layers=None, ldx=0):
+        """Recompute everything on the current stream.  encoders: (positional table, transformer, S) for title and body;
+        intent_layers: the k intent layers, stacked into rows of ldx columns (None: not kept)."""
         self.budget = budget
         V, E = table.shape
         hd, W, dev = E // nhead, nhead * 32, table.device
@@ -1149,6 +1274,20 @@ class WeightProducts:
         if sum(V * 3 * W * 4 for w in want if w) > budget:
             want = [False, False]
         with torch.no_grad():
+            if intent_layers is not None:
+                D, kin = intent_layers[0].weight.shape
+                k = len(intent_layers)
+                fresh_w = self.intent.get('w') is None or tuple(self.intent['w'].shape) != (k * D, ldx) or self.intent['w'].device != dev
+                w = self.intent['w'] = self._buffer(self.intent.get('w'), (k * D, ldx), torch.float32, dev)
+                b = self.intent['b'] = self._buffer(self.intent.get('b'), (k * D,), torch.float32, dev)
+                if fresh_w and ldx > kin:
+                    w[:, kin:].zero_()                                     # the pad columns: written once, the copies below stay left of them
+                for i, lin in enumerate(intent_layers):
+                    w[i * D:(i + 1) * D, :kin].copy_(lin.weight)
+                    b[i * D:(i + 1) * D].copy_(lin.bias)
+            elif self.intent:
+                self.intent = {}
+                self.generation = _next_generation()
             for ent, (pe, transformer, S), w in zip(self.encoder, encoders, want):
                 if w:
                     sa = transformer.layers[0].self_attn
@@ -1180,6 +1319,34 @@ class WeightProducts:
                     else:
                         ops.oproj_pack_sp(layer.self_attn.out_proj.weight, out=wops[li])
                 ent['oproj'] = wops
+        self.state = state
+        self.refreshes += 1
+
+
+class OccurrenceTables:
+    """``LIME.occurrence_tables()`` kept from one scoring call to the next: the tables are a handful of launches on 10- and 100-row
+    operands that read weights only, and a scoring forward, every ``recommend*`` / ``score_*`` call and every candidate-table build
+    asked for them anew.  The rule is ``WeightProducts``': ``state`` is the ``weight_state`` the tables were computed under,
+    ``refresh`` writes new values into the SAME buffers (captured HIP graphs hold their addresses), and ``generation`` takes a new
+    process-wide number whenever a buffer had to be (re)allocated instead."""
+
+    def __init__(self):
+        self.state = None
+        self.T = self.Q = None
+        self.generation = _next_generation()
+        self.refreshes = 0
+
+    def _into(self, old, new):
+        if new is None:
+            return None
+        if old is None or old.shape != new.shape or old.dtype != new.dtype or old.device != new.device:
+            self.generation = _next_generation()
+            old = torch.empty_like(new, memory_format=torch.contiguous_format)
+        return old.copy_(new)
+
+    def refresh(self, state, T, Q):
+        """Take freshly computed tables over, on the current stream."""
+        self.T, self.Q = self._into(self.T, T), self._into(self.Q, Q)
         self.state = state
         self.refreshes += 1
 
@@ -1242,6 +1409,8 @@ class CROWN(NewsEncoder):
             src += [sa.in_proj_weight, sa.in_proj_bias, pos.pe]
             for layer in tr.layers:
                 src += [layer.linear1.weight, layer.linear2.weight, layer.self_attn.out_proj.weight]
+        for lin in self.intent_layers:
+            src += [lin.weight, lin.bias]
         return src
 
     def weight_products(self, create=True):
@@ -1257,16 +1426,18 @@ class CROWN(NewsEncoder):
         wp = getattr(self, '_products', None)
         if wp is None and not create:
             return None
-        state = weight_state(self._product_sources(), ops.PARAM_WRITES)
+        state = weight_state(kept_sources(self, '_product_paths', self._product_sources), ops.PARAM_WRITES)
         budget = self.vocab_qkv_budget
-        if wp is not None and weight_state_stale(wp.state, state) is None and wp.budget == budget:
+        if wp is not None and weight_state_stale(wp.state, state) is None and wp.budget == budget and bool(wp.intent) == WEIGHT_PREP_CACHE:
             return wp
         if torch.cuda.is_current_stream_capturing():
             return None
         if wp is None:
             wp = self._products = WeightProducts(budget)
+        kin = self.word_embedding_dim + self.category_embedding_dim
         wp.refresh(state, table, ((self.title_pos_encoder.table(), self.title_transformer, self.max_title_length),
-                                  (self.body_pos_encoder.table(), self.body_transformer, self.max_body_length)), self.head_num, budget)
+                                  (self.body_pos_encoder.table(), self.body_transformer, self.max_body_length)), self.head_num, budget,
+                   intent_layers=list(self.intent_layers) if WEIGHT_PREP_CACHE else None, ldx=(kin + 3) // 4 * 4)
         return wp
 
     def products_key(self):
@@ -1278,6 +1449,7 @@ class CROWN(NewsEncoder):
         return (None if wp is None else wp.generation, used)
 
     def _apply(self, fn, *args, **kwargs):
+        self.__dict__['_product_paths'] = None
         self._products = None                  # parameter storage moves (and maybe the device): nothing kept stays valid
         return super()._apply(fn, *args, **kwargs)
 
@@ -1306,12 +1478,15 @@ class CROWN(NewsEncoder):
         return (DEDUP and title_text.is_cuda and self._one_pass(title_text, content_text) and 2 * (M + 1) < 4096 and
                 self.intent_num * (M + 1) < 12288)
 
-    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None, news=None):
+    def encode_flat(self, title_text, title_mask, content_text, category, subCategory, out, content_mask=None, news=None,
+                    buckets=None):
         """M news -> out [M, 900] (out may be a column slice of a wider buffer).  The token masks are computed and never
         used by the reference (:307-308); title_mask is accepted and ignored.
         ``news`` = ``ops.compact_batch(title_text, content_text, category, subCategory, ...)`` (``news_dedup_applicable`` batches only):
         the layers behind the token encoders run over the distinct news, and ``out`` is [M + 1, 900] in compact order -- row
-        ``news[2].news_inv[i]`` is news i, rows at or beyond the device count ``news[2].n_news`` are not written."""
+        ``news[2].news_inv[i]`` is news i, rows at or beyond the device count ``news[2].n_news`` are not written.
+        ``buckets`` = (num_buckets, cut points or None) with ``news``: the caller (LIME) wants the bucket pair of the compact keys; the
+        launch that writes the topic rows leaves it in ``news[2].pair`` (``ops.news_keys``), valid on the caller's stream on return."""
         _no_train_dropout(self, self.dropout_rate)
         M, T = title_text.shape
         L = content_text.shape[1]
@@ -1340,24 +1515,6 @@ class CROWN(NewsEncoder):
         if bf16:                                                   # the word table in bf16, rows padded to 8 columns
             table_b = ops.to_bf16(table, cols_out=(E + 7) // 8 * 8)
         main = torch.cuda.current_stream()
-        # branch 4: the category representation (:340-342), the raw category / subCategory rows of feature_fusion (:221-225) and
-        # the stacked intent weights -- they depend on ids and weights only, and run beside the token encoders
-        side4 = _side_stream(dev, 4)
-        side4.wait_stream(main)
-        with torch.cuda.stream(side4):
-            if dedup:
-                side4.wait_event(nw.ready)                         # the compact keys (unused slots hold id 0: valid over the capacity)
-            sub_table = self.subCategory_embedding.weight
-            ops.topic_rep(category, subCategory, self.category_embedding.weight, sub_table, self.category_affine.weight,
-                          self.category_affine.bias, out=xin[:R, E:kin], emb_out=out[:, 2 * D:2 * D + Dc + sub_table.shape[1]])
-            ops.topic_rep(category, subCategory, self.category_embedding.weight, sub_table, self.category_affine.weight,
-                          self.category_affine.bias, out=xin[R:, E:kin])
-            # the k intent weight matrices stacked row-wise, K = 350 carried as ldx = 352 zero-padded columns (16-byte rows: the
-            # LDS-DMA GEMM kernels take it; the two pad columns of xin are zeroed to match)
-            w_int = torch.nn.functional.pad(torch.cat([lin.weight for lin in self.intent_layers], dim=0), (0, ldx - kin))
-            b_int = torch.cat([lin.bias for lin in self.intent_layers], dim=0)
-            if ldx > kin:
-                xin[:, kin:] = 0.0
         encoders = ((title_text, self.title_pos_encoder, self.title_transformer, T),
                     (content_text, self.body_pos_encoder, self.body_transformer, L))
         step_of = lambda S: self._step_of(S, M, bf16)
@@ -1368,6 +1525,35 @@ class CROWN(NewsEncoder):
                                                    for ids, _, tr, S in encoders for m0 in range(0, M, step_of(S))))
         wp = self.weight_products() if compacted else None
         prods = [None, None] if wp is None else wp.encoder
+        # branch 4: the category representation (:340-342) and the raw category / subCategory rows of feature_fusion (:221-225) -- they
+        # depend on ids and weights only, and run beside the token encoders.  Over the distinct news for LIME (``buckets``) it is ONE
+        # launch, ops.news_keys: the topic row into both halves of xin, the zeros of xin's pad columns and the bucket pair of the
+        # compact keys.  Otherwise: topic_rep once per half and a fill.  The stacked intent weights come from the weight products; a
+        # forward without them (bf16, a dense pass, a capture over stale products, the switches off) stacks them here.
+        side4 = _side_stream(dev, 4)
+        side4.wait_stream(main)
+        with torch.cuda.stream(side4):
+            if dedup:
+                side4.wait_event(nw.ready)                         # the compact keys (unused slots hold id 0: valid over the capacity)
+            sub_table = self.subCategory_embedding.weight
+            emb_out = out[:, 2 * D:2 * D + Dc + sub_table.shape[1]]
+            if dedup and buckets is not None:
+                nw.pair = ops.news_keys(nw, buckets[0], buckets[1], self.category_embedding.weight, sub_table, self.category_affine.weight,
+                                        self.category_affine.bias, xin, E, emb_out)
+            else:
+                ops.topic_rep(category, subCategory, self.category_embedding.weight, sub_table, self.category_affine.weight,
+                              self.category_affine.bias, out=xin[:R, E:kin], emb_out=emb_out)
+                ops.topic_rep(category, subCategory, self.category_embedding.weight, sub_table, self.category_affine.weight,
+                              self.category_affine.bias, out=xin[R:, E:kin])
+                if ldx > kin:
+                    xin[:, kin:] = 0.0
+            # the k intent weight matrices stacked row-wise, K = 350 carried as ldx = 352 zero-padded columns (16-byte rows: the
+            # LDS-DMA GEMM kernels take it; the two pad columns of xin are zeroed to match)
+            if wp is not None and wp.intent:
+                w_int, b_int = wp.intent['w'], wp.intent['b']
+            else:
+                w_int = torch.nn.functional.pad(torch.cat([lin.weight for lin in self.intent_layers], dim=0), (0, ldx - kin))
+                b_int = torch.cat([lin.bias for lin in self.intent_layers], dim=0)
         if one_pass:
             # both encoders on the compacted path in one pass each: the body's preparation (index lists, padded weights, padding
             # rows: a dozen short launches) runs on branch 3 under the title encoder's GEMMs

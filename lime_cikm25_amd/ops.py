@@ -425,7 +425,8 @@ def compact_sequences(ids, pad_base=None):
 class NewsCompacted:
     """News-level lists of ``compact_batch`` (device tensors, capacity n + 1; see lime_compact_batch in include/lime_hip.h)."""
     __slots__ = ('n', 'news_src', 'news_inv', 'title_row', 'body_row', 'cat_c', 'sub_c', 'fresh_c', 'life_c', 'counts', 'count_mult',
-                 'ready')                                    # ready: event behind the three launches, for consumers on other streams
+                 'ready',                                    # ready: event behind the three launches, for consumers on other streams
+                 'pair')                                     # the bucket pairs of the compact keys, once ``news_keys`` has run (else unset)
 
     n_news = property(lambda self: self.counts[0:1])         # device counts as 1-element views (m_dev arguments)
     n_news_mult = property(lambda self: self.counts[1:2])    # count_mult * n_news
@@ -669,6 +670,39 @@ def topic_rep(cat, sub, cat_table, sub_table, w=None, bias=None, out=None, emb_o
                                  _p(out) if w is not None else None, _ld(out) if w is not None else 0, _p(emb_out),
                                  _ld(emb_out) if emb_out is not None else 0, rows, _stream()), 'lime_topic_rep_f32')
     return out
+
+
+def news_keys(news, nb, cuts, cat_table, sub_table, w, bias, xin, col0, emb_out):
+    """``lime_news_keys_f32``: one launch over the capacity of ``news`` (``NewsCompacted``) for what the tail takes from the compact
+    keys -- returns pair int32 [n + 1] = bucket(fresh_c) * nb + bucket(life_c) (``bucketize``'s rule, ``cuts`` as there), and writes the
+    ``topic_rep`` row of every compact news into columns [col0, col0 + dout) of both halves of xin [2 (n + 1), ldx], zeros into the
+    columns behind them, and the raw embedding pair into emb_out [n + 1, dc + ds].  Columns [0, col0) of xin are left alone."""
+    lib = _lib.load()
+    rows = news.n + 1
+    _mat(cat_table, 'cat_table')
+    _mat(sub_table, 'sub_table')
+    _mat(w, 'w')
+    if not (cat_table.is_contiguous() and sub_table.is_contiguous()):
+        raise ValueError('embedding tables must be contiguous')
+    dc, ds = cat_table.shape[1], sub_table.shape[1]
+    if not w.is_contiguous() or w.shape[1] != dc + ds:
+        raise ValueError('w must be contiguous [dout, dc + ds]')
+    dout = w.shape[0]
+    _vec(bias, 'bias', dout)
+    _vec(cuts, 'cuts')
+    if cuts.numel() + 1 != nb if cuts is not None else nb != 10:
+        raise ValueError('news_keys: %d buckets need %d cut points (None: the 10 buckets built in)' % (nb, nb - 1))
+    _mat(xin, 'xin')
+    if xin.shape[0] != 2 * rows or col0 < 0 or xin.shape[1] < col0 + dout or not xin.is_contiguous():
+        raise ValueError('xin must be contiguous [2 (n + 1), >= col0 + dout]')
+    _mat(emb_out, 'emb_out')
+    if tuple(emb_out.shape) != (rows, dc + ds):
+        raise ValueError('emb_out must be [n + 1, dc + ds]')
+    pair = torch.empty((rows,), dtype=torch.int32, device=xin.device)
+    check(lib.lime_news_keys_f32(_p(news.cat_c), _p(news.sub_c), _p(news.fresh_c), _p(news.life_c), _p(cuts),
+                                 cuts.numel() if cuts is not None else 0, nb, _p(cat_table), _p(sub_table), dc, ds, _p(w), _p(bias), dout,
+                                 _p(xin), xin.shape[1], col0, _p(emb_out), _ld(emb_out), _p(pair), rows, _stream()), 'lime_news_keys_f32')
+    return pair
 
 
 def intent_fuse(intents, att_hidden, affine2_t, affine2_b, content, M, k, D, A, m_dev=None):

@@ -1,0 +1,97 @@
+"""The staleness rule over the sources of what newsEncoders.WEIGHT_PREP_CACHE keeps: the intent layers among CROWN's product sources,
+LIME's table sources for each fusion, and ``weight_state_stale`` saying 'never' / 'moved' / 'version' / 'writes' for them.  Host only."""
+import pytest
+import torch
+
+from lime_cikm25_amd import Model, make_config, newsEncoders
+
+
+def _model(**kw):
+    cfg = make_config(max_history_num=4, max_title_length=8, max_abstract_length=16, batch_size=2, vocabulary_size=50, **kw)
+    return Model(cfg)
+
+
+def _ptrs(ts):
+    return [t.data_ptr() for t in ts]
+
+
+def test_the_intent_layers_are_sources_of_the_weight_products():
+    enc = _model().news_encoder.base_news_encoder
+    src = _ptrs(enc._product_sources())
+    for lin in enc.intent_layers:
+        assert lin.weight.data_ptr() in src and lin.bias.data_ptr() in src
+    assert src == _ptrs(enc._product_sources())                      # a fixed order
+
+
+@pytest.mark.parametrize('fusion', ['concat', 'add', 'gated'])
+def test_the_table_sources_follow_the_fusion(fusion):
+    ne = _model(fusion_method=fusion).news_encoder
+    fe = ne.freshness_encoder
+    src = _ptrs(ne._table_sources())
+    assert src[:4] == _ptrs([fe.freshness_embedding.weight, fe.lifetime_embedding.weight, fe.dense.weight, fe.dense.bias])
+    rest = [ne.project.weight, ne.project.bias] if fusion == 'concat' else [ne.gate.weight, ne.gate.bias] if fusion == 'gated' else []
+    assert src[4:] == _ptrs(rest)
+    assert ne._kept_tables() is None                                 # a CPU module keeps nothing: the caller computes
+
+
+@pytest.mark.parametrize('which', ['products', 'tables'])
+def test_staleness_over_the_new_sources(which):
+    model = _model()
+    ne = model.news_encoder
+    enc = ne.base_news_encoder
+    sources = enc._product_sources if which == 'products' else ne._table_sources
+    target = enc.intent_layers[1].bias if which == 'products' else ne.freshness_encoder.dense.weight
+    state = lambda writes=0: newsEncoders.weight_state(sources(), writes)
+    assert newsEncoders.weight_state_stale(None, state()) == 'never'
+    rec = state()
+    assert newsEncoders.weight_state_stale(rec, state()) is None
+    with torch.no_grad():
+        target.add_(1.0)                                             # an in-place op: the version counter moves
+    assert newsEncoders.weight_state_stale(rec, state()) == 'version'
+    rec = state()
+    target.data.add_(1.0)                                            # an edit through .data: nothing moves ...
+    assert newsEncoders.weight_state_stale(rec, state()) is None
+    assert newsEncoders.weight_state_stale(rec, state(writes=1)) == 'writes'      # ... the writer counter does
+    target.data = target.data.clone()                                # re-pointed storage: another address
+    assert newsEncoders.weight_state_stale(rec, state()) == 'moved'
+    rec = state()
+    model.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
+    assert newsEncoders.weight_state_stale(rec, state()) == 'version'
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(x is y for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize('which', ['products', 'tables'])
+def test_the_kept_source_paths_give_the_slow_list(which):
+    """newsEncoders.kept_sources: the per-forward fetch of the sources through the modules' dictionaries is the slow list, tensor for
+    tensor -- at once, after a parameter was re-assigned, after a submodule was replaced, and after ``_apply``."""
+    model = _model()
+    ne = model.news_encoder
+    mod, slot, slow = ((ne.base_news_encoder, '_product_paths', ne.base_news_encoder._product_sources) if which == 'products' else
+                       (ne, '_table_paths', ne._table_sources))
+    fetch = lambda: newsEncoders.kept_sources(mod, slot, slow)
+    assert mod.__dict__.get(slot) is None
+    assert _same(fetch(), slow()) and isinstance(mod.__dict__[slot], newsEncoders.SourcePaths)
+    paths = mod.__dict__[slot]
+    assert _same(fetch(), slow()) and mod.__dict__[slot] is paths    # asked, not found again
+    owner = ne.base_news_encoder.intent_layers[1] if which == 'products' else ne.freshness_encoder.dense
+    owner.bias = torch.nn.Parameter(torch.zeros_like(owner.bias))    # a re-assigned parameter: read from its dictionary
+    assert _same(fetch(), slow()) and mod.__dict__[slot] is paths and any(t is owner.bias for t in fetch())
+    new = torch.nn.Linear(owner.in_features, owner.out_features)     # a replaced submodule: a hop leads elsewhere, the paths are found again
+    if which == 'products':
+        ne.base_news_encoder.intent_layers[1] = new
+    else:
+        ne.freshness_encoder.dense = new
+    assert _same(fetch(), slow()) and mod.__dict__[slot] is not paths and any(t is new.weight for t in fetch())
+    model.double()                                                   # _apply drops them
+    assert mod.__dict__.get(slot) is None and _same(fetch(), slow())
+
+
+def test_the_table_paths_follow_the_fusion_tag():
+    ne = _model().news_encoder
+    a = newsEncoders.kept_sources(ne, '_table_paths', ne._table_sources, 'concat')
+    paths = ne.__dict__['_table_paths']
+    assert newsEncoders.kept_sources(ne, '_table_paths', ne._table_sources, 'other') is not None and ne.__dict__['_table_paths'] is not paths
+    assert _same(a, ne._table_sources())
