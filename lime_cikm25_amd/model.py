@@ -161,7 +161,7 @@ class Model(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         self._graphs = {}                      # parameter storage moves: captured pointers are stale
         self._regular_offsets = {}
-        self._products_key = None              # (the content encoder drops what it keeps across forwards in its own _apply)
+        self._graphs_kept_key = None         # (the content encoder drops what it keeps across forwards in its own _apply)
         return super()._apply(fn, *args, **kwargs)
 
     def weights_changed(self):
@@ -172,27 +172,19 @@ class Model(nn.Module):
         ops.note_param_write()
 
     def _kept_key(self):
-        """What the captured graphs depend on beyond their inputs: the content encoder's weight products and LIME's occurrence tables
-        (``products_key`` / ``tables_key``: buffer generations and whether the forward takes them).  Brings both up to date, in place
-        and on the current stream, on the way.  None: the encoders keep nothing."""
-        # which of the two functions the encoders have is found once per news encoder object: the look-ups (a failing ``hasattr``
-        # through nn.Module.__getattr__ above all) cost as much as the keys themselves, in front of every graph replay
-        ne = self._modules['news_encoder']
-        found = self.__dict__.get('_kept_key_fns')
-        enc = ne if self.plain else ne._modules['base_news_encoder']              # (``content_encoder`` without the attribute walk)
-        if found is None or found[0] is not ne or found[1] is not enc:
-            found = self.__dict__['_kept_key_fns'] = (ne, enc, tuple(getattr(m, name) for m, name in ((enc, 'products_key'), (ne, 'tables_key'))
-                                                                      if hasattr(m, name)))
-        keys = tuple(fn() for fn in found[2])
-        return keys or None
+        """What the captured graphs depend on beyond their inputs: the ``kept_key()`` of the news encoder and, below LIME, of the content
+        encoder (``kept.key``: buffer generations and whether the forward takes them).  Brings what they keep up to date, in place and
+        on the current stream, on the way."""
+        ne = self._modules['news_encoder']                  # (no attribute walk through nn.Module.__getattr__ in front of every replay)
+        return ne.kept_key() if self.plain else (ne._modules['base_news_encoder'].kept_key(), ne.kept_key())
 
-    def _sync_weight_products(self):
+    def _sync_kept(self):
         """Before a scoring forward: bring what the encoders keep across forwards up to date (in place, on the current stream) and drop
         the captured graphs if one of those buffers had to move or the forward changed between taking them and computing its own.  An
         in-place refresh keeps the graphs."""
         key = self._kept_key()
-        if key != getattr(self, '_products_key', None):
-            self._products_key = key
+        if key != self.__dict__.get('_graphs_kept_key'):
+            self._graphs_kept_key = key
             self._graphs = {}
 
     def initialize(self):
@@ -229,7 +221,7 @@ class Model(nn.Module):
                                           news_title_entity=news_title_entity if self.reads_title_entity else None)
         if (self.use_graph and ops.PROFILE is None and user_category.is_cuda
                 and not torch.cuda.is_current_stream_capturing()):
-            self._sync_weight_products()       # (an eager forward brings them up to date where it uses them: CROWN.encode_flat)
+            self._sync_kept()                  # (an eager forward brings them up to date where it uses them: CROWN.encode_flat)
             return self._forward_graphed(args)
         return self._forward_impl(*args)
 
@@ -251,7 +243,7 @@ class Model(nn.Module):
                 out = self._forward_impl(*static)
             entry = (graph, [static[i] for i in _USED], out)
             self._graphs[key] = entry
-            self._products_key = self._kept_key()            # (the warm-up may have built the weight products / tables this graph reads)
+            self._graphs_kept_key = self._kept_key()            # (the warm-up may have built the weight products / tables this graph reads)
         graph, static_used, out = entry
         keep = ops.multi_copy(list(zip(static_used, used)))          # one launch for all the inputs
         graph.replay()

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 from torch.nn import TransformerEncoder, TransformerEncoderLayer
 
-from . import ops
+from . import kept, ops
 from .layers import Attention, Conv1D, Conv2D_Pool, LinearHolder, LSTMHolder, MultiHeadAttention, ScaledDotProduct_CandidateAttention
 
 # tokens encoded per pass of the token encoder: bounds the activation workspace (9.2 KB / token)
@@ -365,9 +365,9 @@ class LIME(nn.Module):
         Q is None except for 'gated'.
 
         The tables depend on weights alone, so a scoring call takes them from ``OccurrenceTables`` (kept across calls, refreshed in
-        place under the staleness rule of ``WeightProducts``) where ``_kept_tables`` allows it, and computes them otherwise."""
-        kept = self._kept_tables()
-        return kept if kept is not None else self._compute_occurrence_tables()
+        place: ``kept.Kept``) where ``_kept_tables`` allows it, and computes them otherwise."""
+        tables = self._kept_tables()
+        return tables if tables is not None else self._compute_occurrence_tables()
 
     def _table_sources(self):
         """Every tensor ``occurrence_tables()`` is computed from, in a fixed order."""
@@ -379,41 +379,26 @@ class LIME(nn.Module):
             src += [self.project.weight, self.project.bias]
         return src
 
-    def _kept_tables(self):
-        """(T, Q) from the module's ``OccurrenceTables``, current for the weights as they are now (stale ones are recomputed here, in
-        place and on the current stream), or None where the caller has to compute them: the switch ``WEIGHT_PREP_CACHE`` off, a CPU
-        module, autograd recording with a source that requires grad (a caller inside a training step: its weights move every step,
-        and whatever it builds on the tables must not alias a buffer that a later refresh overwrites), and a stream capture in
-        progress with stale tables (nothing can be computed outside the graph then)."""
-        src = kept_sources(self, '_table_paths', self._table_sources, self.fusion_method)
+    def _kept_tables(self, create=True):
+        """(T, Q) from the module's ``OccurrenceTables`` (``kept.current``), or None where the caller has to compute them: the switch
+        ``WEIGHT_PREP_CACHE`` off, a CPU module, autograd recording with a source that requires grad (a caller inside a training
+        step: its weights move every step, and whatever it builds on the tables must not alias a buffer that a later refresh
+        overwrites), and a stream capture in progress with stale tables."""
+        src = kept.kept_sources(self, '_table_paths', self._table_sources, self.fusion_method)
         if not WEIGHT_PREP_CACHE or not src[0].is_cuda or (torch.is_grad_enabled() and any(t.requires_grad for t in src)):
             return None
-        kept = getattr(self, '_tables', None)
-        state = weight_state(src, ops.PARAM_WRITES)
-        if kept is not None and weight_state_stale(kept.state, state) is None:
-            return kept.T, kept.Q
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        if kept is None:
-            kept = self._tables = OccurrenceTables()
-        with torch.no_grad():
-            kept.refresh(state, *self._compute_occurrence_tables())
-        return kept.T, kept.Q
+        tables = kept.current(self, '_tables', OccurrenceTables, src, create=create)
+        return None if tables is None else (tables.T, tables.Q)
 
-    def tables_key(self):
-        """Changes whenever a graph captured over ``encode_flat`` must not be replayed any more: a table buffer was allocated or
-        reallocated, or the forward switched between the kept tables and its own (``CROWN.products_key``'s counterpart).  Brings
-        existing tables up to date (in place) on the way; builds none.  None for the fusions whose ``encode_flat`` never reads the
-        tables ('add', 'gated', concat without a projection: their serving entries do, outside any captured graph)."""
+    def kept_key(self):
+        """``kept.key`` of the tables, or None for the fusions whose ``encode_flat`` never reads them ('add', 'gated', concat without
+        a projection: their serving entries do, outside any captured graph)."""
         if self.fusion_method != 'concat' or isinstance(self.project, nn.Identity):
             return None
-        kept = getattr(self, '_tables', None)
-        used = kept is not None and self._kept_tables() is not None
-        return (None if kept is None else kept.generation, used)
+        return kept.key(self, '_tables', self._kept_tables)
 
     def _apply(self, fn, *args, **kwargs):
-        self.__dict__['_table_paths'] = None
-        self._tables = None                    # parameter storage moves (and maybe the device): nothing kept stays valid
+        kept.forget(self, '_tables', '_table_paths')
         return super()._apply(fn, *args, **kwargs)
 
     def _compute_occurrence_tables(self):
@@ -596,6 +581,10 @@ class NewsEncoder(nn.Module):
 
     reads_content_mask = False      # True: encode_flat needs the body mask (CNE alone)
     reads_title_entity = False      # True: encode_flat needs the title's entity ids (KCNN alone)
+
+    def kept_key(self):
+        """``kept.key`` of what the encoder keeps across forwards and a captured ``encode_flat`` reads; None: nothing."""
+        return None
 
     def initialize(self):
         nn.init.uniform_(self.category_embedding.weight, -0.1, 0.1)
@@ -1136,101 +1125,12 @@ VOCAB_QKV = os.environ.get('LIME_VOCAB_QKV', '1') != '0'
 WEIGHT_PREP_CACHE = os.environ.get('LIME_WEIGHT_PREP_CACHE', '1') != '0'
 
 
-def weight_state(sources, writes):
-    """What a result derived from the tensors ``sources`` has to remember to know later whether it is still theirs: address, shape
-    and version counter of each (an in-place torch op, ``load_state_dict`` or ``copy_`` moves the version; ``.to()`` / a re-pointed
-    ``.data`` the address) and ``writes``, the count of writes torch does not see (``ops.PARAM_WRITES``: the native optimizer step
-    goes through raw pointers).  An edit through ``tensor.data`` moves none of the three: ``Model.weights_changed()``.  Host only."""
-    return tuple((t.data_ptr(), tuple(t.shape), t._version) for t in sources), int(writes)
-
-
-def weight_state_stale(recorded, current):
-    """The staleness rule of ``WeightProducts``: None while ``recorded`` (the ``weight_state`` a result was computed under) still
-    describes the sources, else why not -- 'never' (nothing recorded), 'moved' (a source's address or shape differs, or their number),
-    'version' (an in-place write torch counted), 'writes' (a raw-pointer write was announced).  Pure: two tuples in, a word out."""
-    if recorded is None:
-        return 'never'
-    if recorded == current:                       # (one tuple comparison: the answer of nearly every forward)
-        return None
-    (rec, rec_writes), (cur, cur_writes) = recorded, current
-    if len(rec) != len(cur) or any(a[:2] != b[:2] for a, b in zip(rec, cur)):
-        return 'moved'
-    if any(a[2] != b[2] for a, b in zip(rec, cur)):
-        return 'version'
-    return 'writes' if rec_writes != cur_writes else None
-
-
-class SourcePaths:
-    """Where the source tensors of a kept result live below ``root``, so that every forward can fetch them without walking the module
-    tree through ``nn.Module.__getattr__`` (the walk cost more than the comparison it feeds: 8 us for LIME's six tensors, 26 us for
-    CROWN's, in front of every graph replay).  ``leaves``: (the owning module's parameter or buffer dictionary, name) per source, in the
-    order of the slow list they were found from; ``links``: (a module's child dictionary, name, child) for every hop on the way.
-    ``tensors()`` returns the sources as they are now -- a re-assigned parameter is read from its dictionary like any other -- or None
-    once a hop leads to another module than it did; the caller then asks the slow list again."""
-
-    def __init__(self, links, leaves, tag):
-        self.links, self.leaves, self.tag = links, leaves, tag
-
-    @classmethod
-    def find(cls, root, tensors, tag=None):
-        """The paths of ``tensors`` (found by identity among root's parameters and buffers), or None when one of them is not there."""
-        where = {}
-        for prefix, mod in root.named_modules(remove_duplicate=False):
-            for d in (mod._parameters, mod._buffers):
-                for name, t in d.items():
-                    if t is not None:
-                        where.setdefault(id(t), (prefix, d, name))
-        links, leaves, seen = [], [], set()
-        for t in tensors:
-            if id(t) not in where:
-                return None
-            prefix, d, name = where[id(t)]
-            leaves.append((d, name))
-            mod, path = root, ''
-            for hop in (prefix.split('.') if prefix else []):
-                child = mod._modules[hop]
-                path += '.' + hop
-                if path not in seen:
-                    seen.add(path)
-                    links.append((mod._modules, hop, child))
-                mod = child
-        return cls(links, leaves, tag)
-
-    def tensors(self, tag=None):
-        if tag != self.tag or any(d.get(name) is not child for d, name, child in self.links):
-            return None
-        return [d[name] for d, name in self.leaves]
-
-
-def kept_sources(module, slot, slow, tag=None):
-    """``slow()`` -- a module's list of source tensors -- through the ``SourcePaths`` kept in ``module.__dict__[slot]``: found at the
-    first call, asked from then on, found again when a hop or ``tag`` changed.  The module drops the slot in ``_apply``."""
-    paths = module.__dict__.get(slot)
-    if paths is not None:
-        ts = paths.tensors(tag)
-        if ts is not None:
-            return ts
-    ts = slow()
-    module.__dict__[slot] = SourcePaths.find(module, ts, tag)
-    return ts
-
-
 def vocab_qkv_applicable(S, E, nhead):
     """The vocab form of ``lime_token_attention_f32`` covers the first layer of a token encoder over S-token sequences."""
     return S in (32, 64, 128) and E % nhead == 0 and E // nhead <= 32 and E % 4 == 0
 
 
-_GENERATION = [0]
-
-
-def _next_generation():
-    """Process-wide, so that no two sets of product buffers ever carry one number: a module that lost its ``WeightProducts``
-    (``_apply``) and built another must not look unchanged to a holder of captured graphs."""
-    _GENERATION[0] += 1
-    return _GENERATION[0]
-
-
-class WeightProducts:
+class WeightProducts(kept.Kept):
     """What the fp32 token encoders of a CROWN module compute from weights alone, kept from one scoring forward to the next:
 
       * per encoder, ``ew`` = E W_in^T over the WHOLE word table ([V, 3W], heads padded to 32 columns) and ``pew`` = PE W_in^T + b
@@ -1243,112 +1143,88 @@ class WeightProducts:
         [k D]), what the tail's one GEMM over the k layers reads (``WEIGHT_PREP_CACHE``; they were two cats, a pad and a copy per
         forward).
 
-    ``refresh`` recomputes them IN PLACE when ``weight_state_stale`` says so: captured HIP graphs hold the buffers' addresses.
-    ``generation`` takes a new process-wide number whenever a buffer had to be (re)allocated or dropped instead; whoever holds graphs
-    drops them then."""
-
-    def __init__(self, budget):
-        self.state = None
-        self.budget = budget               # bytes of [V, 3W] products this set was built under
-        self.encoder = [{}, {}]            # title, body: dict(ew=, pew=, ffn=[(w1p, w2p) per layer], oproj=[wp per layer]); 'ew' / 'pew' absent over the budget
-        self.intent = {}                   # dict(w=, b=), or empty with WEIGHT_PREP_CACHE off
-        self.generation = _next_generation()
-        self.refreshes = 0                 # recomputations so far (tests, logs)
-
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for e in self.encoder for t in (e.get('ew'), e.get('pew')) if t is not None)
-
-    def _buffer(self, old, shape, dtype, device):
-        if old is not None and tuple(old.shape) == tuple(shape) and old.dtype == dtype and old.device == device:
-            return old
-        self.generation = _next_generation()
-        return torch.empty(shape, dtype=dtype, device=device)
-
-    def refresh(self, state, table, encoders, nhead, budget, intent_layers=None, ldx=0):
-        """Recompute everything on the current stream.  encoders: (positional table, transformer, S) for title and body;
-        intent_layers: the k intent layers, stacked into rows of ldx columns (None: not kept)."""
-        self.budget = budget
-        V, E = table.shape
-        hd, W, dev = E // nhead, nhead * 32, table.device
-        want = [vocab_qkv_applicable(S, E, nhead) for _, _, S in encoders]
-        if sum(V * 3 * W * 4 for w in want if w) > budget:
-            want = [False, False]
-        with torch.no_grad():
-            if intent_layers is not None:
-                D, kin = intent_layers[0].weight.shape
-                k = len(intent_layers)
-                fresh_w = self.intent.get('w') is None or tuple(self.intent['w'].shape) != (k * D, ldx) or self.intent['w'].device != dev
-                w = self.intent['w'] = self._buffer(self.intent.get('w'), (k * D, ldx), torch.float32, dev)
-                b = self.intent['b'] = self._buffer(self.intent.get('b'), (k * D,), torch.float32, dev)
-                if fresh_w and ldx > kin:
-                    w[:, kin:].zero_()                                     # the pad columns: written once, the copies below stay left of them
-                for i, lin in enumerate(intent_layers):
-                    w[i * D:(i + 1) * D, :kin].copy_(lin.weight)
-                    b[i * D:(i + 1) * D].copy_(lin.bias)
-            elif self.intent:
-                self.intent = {}
-                self.generation = _next_generation()
-            for ent, (pe, transformer, S), w in zip(self.encoder, encoders, want):
-                if w:
-                    sa = transformer.layers[0].self_attn
-                    w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, hd, 32)
-                    b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, hd, 32)
-                    ent['ew'] = ops.linear(table, w_in, None, out=self._buffer(ent.get('ew'), (V, 3 * W), torch.float32, dev))
-                    ent['pew'] = ops.linear(pe[:S], w_in, b_in, out=self._buffer(ent.get('pew'), (S, 3 * W), torch.float32, dev))
-                elif 'ew' in ent:
-                    del ent['ew'], ent['pew']
-                    self.generation = _next_generation()
-                packs = ent.get('ffn') or [None] * len(transformer.layers)
-                for li, layer in enumerate(transformer.layers):
-                    if not _ffn_sp_shape(layer, E):
-                        packs[li] = None
-                        continue
-                    if packs[li] is None or packs[li][0].device != dev:
-                        self.generation = _next_generation()
-                        packs[li] = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight)
-                    else:
-                        ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight, out=packs[li])
-                ent['ffn'] = packs
-                wops = ent.get('oproj') or [None] * len(transformer.layers)
-                for li, layer in enumerate(transformer.layers):
-                    if not (E <= 304 and E % 4 == 0):
-                        wops[li] = None
-                    elif wops[li] is None or wops[li].device != dev:
-                        self.generation = _next_generation()
-                        wops[li] = ops.oproj_pack_sp(layer.self_attn.out_proj.weight)
-                    else:
-                        ops.oproj_pack_sp(layer.self_attn.out_proj.weight, out=wops[li])
-                ent['oproj'] = wops
-        self.state = state
-        self.refreshes += 1
-
-
-class OccurrenceTables:
-    """``LIME.occurrence_tables()`` kept from one scoring call to the next: the tables are a handful of launches on 10- and 100-row
-    operands that read weights only, and a scoring forward, every ``recommend*`` / ``score_*`` call and every candidate-table build
-    asked for them anew.  The rule is ``WeightProducts``': ``state`` is the ``weight_state`` the tables were computed under,
-    ``refresh`` writes new values into the SAME buffers (captured HIP graphs hold their addresses), and ``generation`` takes a new
-    process-wide number whenever a buffer had to be (re)allocated instead."""
+    ``config`` = (``budget``: the bytes of [V, 3W] products the module may keep, whether ``intent`` is kept).  Staleness, the in-place
+    refresh and ``generation``: ``kept.Kept``."""
 
     def __init__(self):
-        self.state = None
-        self.T = self.Q = None
-        self.generation = _next_generation()
-        self.refreshes = 0
+        super().__init__()
+        self.encoder = [{}, {}]            # title, body: dict(ew=, pew=, ffn=[(w1p, w2p) per layer], oproj=[wp per layer]); 'ew' / 'pew' absent over the budget
+        self.intent = {}                   # dict(w=, b=), or empty with WEIGHT_PREP_CACHE off
 
-    def _into(self, old, new):
-        if new is None:
-            return None
-        if old is None or old.shape != new.shape or old.dtype != new.dtype or old.device != new.device:
-            self.generation = _next_generation()
-            old = torch.empty_like(new, memory_format=torch.contiguous_format)
-        return old.copy_(new)
+    def refresh(self, crown, config):
+        """Recompute everything from ``crown``'s weights, on the current stream."""
+        self.budget, keep_intent = config                          # (budget: the one this set was built under)
+        table, nhead = crown.word_embedding.weight, crown.head_num
+        encoders = ((crown.title_pos_encoder.table(), crown.title_transformer, crown.max_title_length),
+                    (crown.body_pos_encoder.table(), crown.body_transformer, crown.max_body_length))
+        V, E = table.shape
+        want = [vocab_qkv_applicable(S, E, nhead) for _, _, S in encoders]
+        if sum(V * 3 * nhead * 32 * 4 for w in want if w) > self.budget:
+            want = [False, False]
+        if keep_intent:
+            self._stack_intent(list(crown.intent_layers), table.device)
+        elif self.intent:
+            self.intent = {}
+            self.let_go()
+        for ent, (pe, transformer, S), w in zip(self.encoder, encoders, want):
+            self._vocab_products(ent, table, pe[:S], transformer.layers[0].self_attn, nhead, w)
+            self._packs(ent, transformer.layers, E, table.device)
 
-    def refresh(self, state, T, Q):
-        """Take freshly computed tables over, on the current stream."""
-        self.T, self.Q = self._into(self.T, T), self._into(self.Q, Q)
-        self.state = state
-        self.refreshes += 1
+    def _stack_intent(self, layers, dev):
+        """``intent``: the k intent layers' weights and biases stacked, the rows padded with zeros to a multiple of 4 columns."""
+        (D, kin), k = layers[0].weight.shape, len(layers)
+        ldx, old = (kin + 3) // 4 * 4, self.intent.get('w')
+        w = self.intent['w'] = self.buffer(old, (k * D, ldx), torch.float32, dev)
+        b = self.intent['b'] = self.buffer(self.intent.get('b'), (k * D,), torch.float32, dev)
+        if w is not old and ldx > kin:
+            w[:, kin:].zero_()                                     # the pad columns: written once, the copies below stay left of them
+        for i, lin in enumerate(layers):
+            w[i * D:(i + 1) * D, :kin].copy_(lin.weight)
+            b[i * D:(i + 1) * D].copy_(lin.bias)
+
+    def _vocab_products(self, ent, table, pe, sa, nhead, want):
+        """``ent['ew']`` / ``ent['pew']`` of one token encoder: the word table and the positions ``pe`` through the in_proj of ``sa``."""
+        if want:
+            (V, E), S, W = table.shape, pe.shape[0], nhead * 32
+            w_in = ops.pad_heads(sa.in_proj_weight, 3 * nhead, E // nhead, 32)
+            b_in = ops.pad_heads(sa.in_proj_bias, 3 * nhead, E // nhead, 32)
+            ent['ew'] = ops.linear(table, w_in, None, out=self.buffer(ent.get('ew'), (V, 3 * W), torch.float32, table.device))
+            ent['pew'] = ops.linear(pe, w_in, b_in, out=self.buffer(ent.get('pew'), (S, 3 * W), torch.float32, table.device))
+        elif 'ew' in ent:
+            del ent['ew'], ent['pew']
+            self.let_go()
+
+    def _packs(self, ent, layers, E, dev):
+        """``ent['ffn']`` / ``ent['oproj']`` of one token encoder, per layer (None: a shape the split kernels do not cover)."""
+        ffn, oproj = (ent.get(name) or [None] * len(layers) for name in ('ffn', 'oproj'))
+        for li, layer in enumerate(layers):
+            if _ffn_sp_shape(layer, E):
+                sizes = ops.ffn_pack_sp_sizes(layer.linear1.weight.shape[0])
+                out = tuple(self.buffer(old, (n,), torch.bfloat16, dev) for old, n in zip(ffn[li] or (None, None), sizes))
+                ffn[li] = ops.ffn_pack_sp(layer.linear1.weight, layer.linear2.weight, out=out)
+            else:
+                ffn[li] = None
+        for li, layer in enumerate(layers):
+            if E <= 304 and E % 4 == 0:
+                out = self.buffer(oproj[li], (ops.oproj_pack_sp_size(),), torch.bfloat16, dev)
+                oproj[li] = ops.oproj_pack_sp(layer.self_attn.out_proj.weight, out=out)
+            else:
+                oproj[li] = None
+        ent['ffn'], ent['oproj'] = ffn, oproj
+
+
+class OccurrenceTables(kept.Kept):
+    """``LIME.occurrence_tables()`` kept from one scoring call to the next: the tables are a handful of launches on 10- and 100-row
+    operands that read weights only, and a scoring forward, every ``recommend*`` / ``score_*`` call and every candidate-table build
+    asked for them anew.  Staleness, the in-place refresh and ``generation``: ``kept.Kept``."""
+
+    T = Q = None
+
+    def refresh(self, lime, config):
+        """Compute the tables from ``lime``'s weights and copy them into the kept buffers, on the current stream."""
+        T, Q = lime._compute_occurrence_tables()
+        self.T = self.buffer(self.T, T.shape, T.dtype, T.device).copy_(T)
+        self.Q = None if Q is None else self.buffer(self.Q, Q.shape, Q.dtype, Q.device).copy_(Q)
 
 
 class CROWN(NewsEncoder):
@@ -1414,43 +1290,20 @@ class CROWN(NewsEncoder):
         return src
 
     def weight_products(self, create=True):
-        """The module's ``WeightProducts``, current for the weights as they are now, or None where the forward derives everything
-        itself: the switch ``VOCAB_QKV`` off, bf16, the split product off, a CPU module -- and a stream capture in progress with
-        stale products (nothing can be computed outside the graph then; the captured forward keeps its in_proj).  Stale products
-        are recomputed here, in place and on the current stream.  ``create``: build them when the module has none yet -- what
-        ``encode_flat`` asks for once it knows that a compacted call site takes them (they cost 2 V 960 floats and one GEMM over
-        the vocabulary per encoder); a holder of captured graphs passes False before a replay (``products_key``)."""
-        table = self.word_embedding.weight
-        if not VOCAB_QKV or self.compute_dtype == 'bf16' or not table.is_cuda or not ops.split_gemm_on():
+        """The module's ``WeightProducts`` (``kept.current``), or None where the forward derives everything itself, in_proj included:
+        the switch ``VOCAB_QKV`` off, bf16, the split product off, a CPU module, a capture over stale products.  ``create``: build
+        them when the module has none yet -- what ``encode_flat`` asks for once it knows that a compacted call site takes them (they
+        cost 2 V 960 floats and one GEMM over the vocabulary per encoder); ``kept_key`` passes False."""
+        src = kept.kept_sources(self, '_product_paths', self._product_sources)           # (src[0]: the word table, without an attribute walk)
+        if not VOCAB_QKV or self.compute_dtype == 'bf16' or not src[0].is_cuda or not ops.split_gemm_on():
             return None
-        wp = getattr(self, '_products', None)
-        if wp is None and not create:
-            return None
-        state = weight_state(kept_sources(self, '_product_paths', self._product_sources), ops.PARAM_WRITES)
-        budget = self.vocab_qkv_budget
-        if wp is not None and weight_state_stale(wp.state, state) is None and wp.budget == budget and bool(wp.intent) == WEIGHT_PREP_CACHE:
-            return wp
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        if wp is None:
-            wp = self._products = WeightProducts(budget)
-        kin = self.word_embedding_dim + self.category_embedding_dim
-        wp.refresh(state, table, ((self.title_pos_encoder.table(), self.title_transformer, self.max_title_length),
-                                  (self.body_pos_encoder.table(), self.body_transformer, self.max_body_length)), self.head_num, budget,
-                   intent_layers=list(self.intent_layers) if WEIGHT_PREP_CACHE else None, ldx=(kin + 3) // 4 * 4)
-        return wp
+        return kept.current(self, '_products', WeightProducts, src, (self.vocab_qkv_budget, WEIGHT_PREP_CACHE), create)
 
-    def products_key(self):
-        """Changes whenever a graph captured over ``encode_flat`` must not be replayed any more: a product buffer was allocated,
-        reallocated or dropped, or the forward switched between the products and the in-graph in_proj.  Brings existing products up
-        to date (in place) on the way; builds none."""
-        used = self.weight_products(create=False) is not None
-        wp = getattr(self, '_products', None)
-        return (None if wp is None else wp.generation, used)
+    def kept_key(self):
+        return kept.key(self, '_products', self.weight_products)
 
     def _apply(self, fn, *args, **kwargs):
-        self.__dict__['_product_paths'] = None
-        self._products = None                  # parameter storage moves (and maybe the device): nothing kept stays valid
+        kept.forget(self, '_products', '_product_paths')
         return super()._apply(fn, *args, **kwargs)
 
     def _step_of(self, S, M, bf16):
@@ -1979,7 +1832,8 @@ class CNERecurrenceCache:
     ``versions``: the ``_version`` counters of the parameters the cache was built from (word table, both LSTMs, title_H, content_H).
     They move with autograd-visible in-place updates (``load_state_dict``, torch optimizers) but NOT with edits through ``.data`` nor
     with the native Adam step, which writes the flat parameter bucket directly; ``fingerprint`` (int64 device tensor: the sum of each
-    parameter's bit patterns) catches those.  ``CNE.cache_is_current`` compares both."""
+    parameter's bit patterns) catches those.  ``CNE.cache_is_current`` compares both (another rule than ``kept.weight_state``, which
+    needs such a write announced: this cache is the caller's, not the module's)."""
 
     Text = collections.namedtuple('Text', 'S lens offsets h hh m')
 

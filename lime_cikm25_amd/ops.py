@@ -21,7 +21,7 @@ PROFILE = None
 
 
 # Counts the writes to parameter memory that torch cannot see: a kernel handed a raw pointer (the native Adam step over the flat
-# bucket) moves no tensor's ``_version``.  Everything derived from weights and kept across forwards (newsEncoders.WeightProducts)
+# bucket) moves no tensor's ``_version``.  Everything derived from weights and kept across forwards (kept.weight_state)
 # compares this counter as well; whoever adds such a writer calls ``note_param_write()``.
 PARAM_WRITES = 0
 
@@ -1455,6 +1455,12 @@ def ffn_pack_bf16(w1, b1, w2):
     return w1p, w2p
 
 
+def ffn_pack_sp_sizes(F):
+    """Elements of the bf16 buffers (w1p, w2p) that ``ffn_pack_sp`` fills for a feed-forward width F."""
+    lib = _lib.load()
+    return int(lib.lime_ffn_pack_sp_size(F, 0)), int(lib.lime_ffn_pack_sp_size(F, 1))
+
+
 def ffn_pack_sp(w1, w2, out=None):
     """``lime_ffn_pack_sp``: linear1 / linear2 weights (fp32 [F, E], [E, F]) -> the split (three bf16 terms) operands of ``encoder_ffn_sp``.
     ``out``: a (w1p, w2p) pair of an earlier call for the same shapes, refilled in place."""
@@ -1464,7 +1470,7 @@ def ffn_pack_sp(w1, w2, out=None):
     F, E = w1.shape
     if tuple(w2.shape) != (E, F):
         raise ValueError('w2 must be [%d, %d]' % (E, F))
-    n1, n2 = int(lib.lime_ffn_pack_sp_size(F, 0)), int(lib.lime_ffn_pack_sp_size(F, 1))
+    n1, n2 = ffn_pack_sp_sizes(F)
     if out is not None:
         w1p, w2p = _vec(out[0], 'w1p', n1, dtype=torch.bfloat16), _vec(out[1], 'w2p', n2, dtype=torch.bfloat16)
     else:
@@ -1523,6 +1529,11 @@ def device_cus():
     return int(_lib.load().lime_device_cus())
 
 
+def oproj_pack_sp_size():
+    """Elements of the bf16 buffer that ``oproj_pack_sp`` fills."""
+    return int(_lib.load().lime_oproj_pack_sp_size())
+
+
 def oproj_pack_sp(w, out=None):
     """``lime_oproj_pack_sp``: the out_proj weight (fp32 [E, E]) -> the split (three bf16 terms) operand of ``encoder_oproj_sp``.
     ``out``: the buffer of an earlier call, refilled in place."""
@@ -1531,7 +1542,7 @@ def oproj_pack_sp(w, out=None):
     E = w.shape[0]
     if w.shape[1] != E:
         raise ValueError('w must be square, got %s' % (tuple(w.shape),))
-    n = int(lib.lime_oproj_pack_sp_size())
+    n = oproj_pack_sp_size()
     wp = _vec(out, 'wp', n, dtype=torch.bfloat16) if out is not None else torch.empty(n, dtype=torch.bfloat16, device=w.device)
     check(lib.lime_oproj_pack_sp(_p(w), _ld(w), E, _p(wp), _stream()), 'lime_oproj_pack_sp')
     return wp

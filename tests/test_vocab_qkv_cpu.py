@@ -1,48 +1,48 @@
-"""The staleness rule of newsEncoders.WeightProducts (weight_state / weight_state_stale: pure host functions) and the binding of the
+"""The staleness rule of newsEncoders.WeightProducts (kept.weight_state / weight_state_stale: pure host functions) and the binding of the
 attention entry that reads the products.  CPU only."""
 import ctypes
 
 import torch
 import torch.nn as nn
 
-from lime_cikm25_amd import _lib, newsEncoders, ops
+from lime_cikm25_amd import _lib, kept, newsEncoders, ops
 
 
 def _state(sources, writes=0):
-    return newsEncoders.weight_state(sources, writes)
+    return kept.weight_state(sources, writes)
 
 
 def test_staleness_rule():
     lin = nn.Linear(6, 4)
     table = torch.zeros(5, 6)
     src = [table, lin.weight, lin.bias]
-    assert newsEncoders.weight_state_stale(None, _state(src)) == 'never'
+    assert kept.weight_state_stale(None, _state(src)) == 'never'
     rec = _state(src)
-    assert newsEncoders.weight_state_stale(rec, _state(src)) is None
+    assert kept.weight_state_stale(rec, _state(src)) is None
     with torch.no_grad():
         lin.weight.mul_(2.0)                                       # an in-place op under no_grad
-    assert newsEncoders.weight_state_stale(rec, _state(src)) == 'version'
+    assert kept.weight_state_stale(rec, _state(src)) == 'version'
     rec = _state(src)
     lin.load_state_dict({'weight': torch.ones(4, 6), 'bias': torch.ones(4)})
-    assert newsEncoders.weight_state_stale(rec, _state(src)) == 'version'
+    assert kept.weight_state_stale(rec, _state(src)) == 'version'
     rec = _state(src)
     table.copy_(torch.ones(5, 6))
-    assert newsEncoders.weight_state_stale(rec, _state(src)) == 'version'
+    assert kept.weight_state_stale(rec, _state(src)) == 'version'
     rec = _state(src)
     lin.weight.data.add_(1.0)                                      # the blind spot: neither version nor address moves ...
-    assert newsEncoders.weight_state_stale(rec, _state(src)) is None
-    assert newsEncoders.weight_state_stale(rec, _state(src, writes=1)) == 'writes'      # ... the writer counter does
+    assert kept.weight_state_stale(rec, _state(src)) is None
+    assert kept.weight_state_stale(rec, _state(src, writes=1)) == 'writes'      # ... the writer counter does
     lin.weight.data = torch.zeros(4, 6)                            # re-pointed storage (TrainStep's flat bucket, .to())
-    assert newsEncoders.weight_state_stale(rec, _state(src)) == 'moved'
+    assert kept.weight_state_stale(rec, _state(src)) == 'moved'
     rec = _state(src)
-    assert newsEncoders.weight_state_stale(rec, _state([torch.zeros(7, 6), lin.weight, lin.bias])) == 'moved'      # another shape
-    assert newsEncoders.weight_state_stale(rec, _state(src[:2])) == 'moved'                                         # another source list
-    assert newsEncoders.weight_state_stale(rec, _state(src)) is None
+    assert kept.weight_state_stale(rec, _state([torch.zeros(7, 6), lin.weight, lin.bias])) == 'moved'      # another shape
+    assert kept.weight_state_stale(rec, _state(src[:2])) == 'moved'                                         # another source list
+    assert kept.weight_state_stale(rec, _state(src)) is None
 
 
 def test_state_is_host_data_only():
     t = torch.zeros(3, 4)
-    (entries, writes) = newsEncoders.weight_state([t], 7)
+    (entries, writes) = kept.weight_state([t], 7)
     assert entries == ((t.data_ptr(), (3, 4), t._version),) and writes == 7
 
 

@@ -3,7 +3,7 @@ LIME's table sources for each fusion, and ``weight_state_stale`` saying 'never' 
 import pytest
 import torch
 
-from lime_cikm25_amd import Model, make_config, newsEncoders
+from lime_cikm25_amd import Model, kept, make_config
 
 
 def _model(**kw):
@@ -41,22 +41,22 @@ def test_staleness_over_the_new_sources(which):
     enc = ne.base_news_encoder
     sources = enc._product_sources if which == 'products' else ne._table_sources
     target = enc.intent_layers[1].bias if which == 'products' else ne.freshness_encoder.dense.weight
-    state = lambda writes=0: newsEncoders.weight_state(sources(), writes)
-    assert newsEncoders.weight_state_stale(None, state()) == 'never'
+    state = lambda writes=0: kept.weight_state(sources(), writes)
+    assert kept.weight_state_stale(None, state()) == 'never'
     rec = state()
-    assert newsEncoders.weight_state_stale(rec, state()) is None
+    assert kept.weight_state_stale(rec, state()) is None
     with torch.no_grad():
         target.add_(1.0)                                             # an in-place op: the version counter moves
-    assert newsEncoders.weight_state_stale(rec, state()) == 'version'
+    assert kept.weight_state_stale(rec, state()) == 'version'
     rec = state()
     target.data.add_(1.0)                                            # an edit through .data: nothing moves ...
-    assert newsEncoders.weight_state_stale(rec, state()) is None
-    assert newsEncoders.weight_state_stale(rec, state(writes=1)) == 'writes'      # ... the writer counter does
+    assert kept.weight_state_stale(rec, state()) is None
+    assert kept.weight_state_stale(rec, state(writes=1)) == 'writes'      # ... the writer counter does
     target.data = target.data.clone()                                # re-pointed storage: another address
-    assert newsEncoders.weight_state_stale(rec, state()) == 'moved'
+    assert kept.weight_state_stale(rec, state()) == 'moved'
     rec = state()
     model.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
-    assert newsEncoders.weight_state_stale(rec, state()) == 'version'
+    assert kept.weight_state_stale(rec, state()) == 'version'
 
 
 def _same(a, b):
@@ -65,15 +65,15 @@ def _same(a, b):
 
 @pytest.mark.parametrize('which', ['products', 'tables'])
 def test_the_kept_source_paths_give_the_slow_list(which):
-    """newsEncoders.kept_sources: the per-forward fetch of the sources through the modules' dictionaries is the slow list, tensor for
+    """kept.kept_sources: the per-forward fetch of the sources through the modules' dictionaries is the slow list, tensor for
     tensor -- at once, after a parameter was re-assigned, after a submodule was replaced, and after ``_apply``."""
     model = _model()
     ne = model.news_encoder
     mod, slot, slow = ((ne.base_news_encoder, '_product_paths', ne.base_news_encoder._product_sources) if which == 'products' else
                        (ne, '_table_paths', ne._table_sources))
-    fetch = lambda: newsEncoders.kept_sources(mod, slot, slow)
+    fetch = lambda: kept.kept_sources(mod, slot, slow)
     assert mod.__dict__.get(slot) is None
-    assert _same(fetch(), slow()) and isinstance(mod.__dict__[slot], newsEncoders.SourcePaths)
+    assert _same(fetch(), slow()) and isinstance(mod.__dict__[slot], kept.SourcePaths)
     paths = mod.__dict__[slot]
     assert _same(fetch(), slow()) and mod.__dict__[slot] is paths    # asked, not found again
     owner = ne.base_news_encoder.intent_layers[1] if which == 'products' else ne.freshness_encoder.dense
@@ -91,7 +91,7 @@ def test_the_kept_source_paths_give_the_slow_list(which):
 
 def test_the_table_paths_follow_the_fusion_tag():
     ne = _model().news_encoder
-    a = newsEncoders.kept_sources(ne, '_table_paths', ne._table_sources, 'concat')
+    a = kept.kept_sources(ne, '_table_paths', ne._table_sources, 'concat')
     paths = ne.__dict__['_table_paths']
-    assert newsEncoders.kept_sources(ne, '_table_paths', ne._table_sources, 'other') is not None and ne.__dict__['_table_paths'] is not paths
+    assert kept.kept_sources(ne, '_table_paths', ne._table_sources, 'other') is not None and ne.__dict__['_table_paths'] is not paths
     assert _same(a, ne._table_sources())
