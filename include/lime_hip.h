@@ -1387,6 +1387,29 @@ int lime_cne_gate_cached_f32(const float* h, const float* hh, const int64_t* off
  * then LIME_ERR_UNSUPPORTED where the tables do not fit the workgroup's LDS: 2048 T + 8 n_occ Hs bytes <= 65536, with T = 1, 2, 4, 8
  * for H <= 16, 32, 64, 128 and Hs = H rounded up to a multiple of 4 (H = 50 with 100 occurrences: 49,792 bytes; H = 128: n_occ <= 48).
  *
+ * lime_grouped_match_explain_f32 (csrc/grouped_match_explain_f32.hip): the grouped match with its terms kept (Model.explain_lists /
+ * Model.explain; recommend.explain_pairs states it on the host).  The score of a pair is a sum over the history slots,
+ *     base[p] = sum_h attn[p, h] m[h],   attn[p, :] = softmax_h(s),   m[h] = g[i H + h, :] . cand[p, :],   logits[p] = base[p] weight[p]
+ * with weight[p] = w(remaining[p]) (1 with use_weight == 0), and the entry writes, beside logits / base / weight fp32 [P]:
+ *     attn fp32 [P, H] = e[h] / den   and   contrib fp32 [P, H] = (attn[p, h] m[h]) weight[p]          (each may be NULL: not written)
+ *     top_slot int32 [P, m], top_value fp32 [P, m]: the m slots of largest contrib (by = LIME_EXPLAIN_BY_CONTRIBUTION) or largest attn
+ *     (LIME_EXPLAIN_BY_ATTENTION) among the slots whose byte of mask is set, and the written value's bits at each.
+ * mask uint8 [ceil(G / hist_div), H]: group i reads row i / hist_div -- hist_div consecutive groups share one history, as in the
+ * refinement -- (NULL: every slot is eligible).  The softmax is NOT masked (reference userEncoders.py:164): the mask gates which slots
+ * may be named, not what they weigh.  Order: lime_topk_rows_f32's -- larger value first, equal values (+0.0 and -0.0 are equal) lower
+ * slot first, a NaN behind every number; with fewer than m eligible slots the tail holds slot -1 and value 0.0.
+ * The operands take the three forms of the twins by their pointers: index == NULL: qp [P, A], cand [P, D] (lime_grouped_match_f32; occ,
+ * qt, ct NULL, n and n_occ unread); index alone: tables of n rows (lime_grouped_match_indexed_f32); index, occ, qt and ct together: the
+ * occurrence-composed form (lime_grouped_match_occurrence_f32).  The two products, the softmax and the expressions behind them are the
+ * twins': logits[p] has the BITS of the twin on the same operands.  The selection runs in the pair's four lanes on the registers the
+ * products left there (m rounds of a register argmax and two butterfly steps); no LDS beyond the twins', no workspace, no atomics,
+ * fixed-order sums: a pair's bits depend neither on P, G, the group's position, the pair's place in its tile nor the grid.  index, occ
+ * and offsets are clamped as in the twins; pairs outside every group are not written.  Statuses before any launch, in this order:
+ * LIME_ERR_BAD_ARG for a `by` that is neither constant, a NULL kp / g / qp / cand / offsets / logits / base / weight / top_slot /
+ * top_value, occ / qt / ct given in part or without index, use_weight without remaining; the twins' dimension, alignment and table
+ * checks with their statuses; LIME_ERR_BAD_ARG for m < 1, m > H or hist_div < 1; LIME_ERR_UNSUPPORTED for m > 16.  G == 0 or P == 0 is
+ * a success without a launch.
+ *
  * lime_topk_rows_f32 (csrc/topk_rows_f32.hip): per row u < U of scores [U, C] (leading dimension ld >= C) the k best entries:
  * positions int32 [U, k] (column indices) and top_scores fp32 [U, k] (the input's bits at those positions), in descending order of
  * the score; equal scores -- +0.0 and -0.0 are equal -- lower position first; a NaN ranks behind every number, NaNs in position
@@ -1484,6 +1507,14 @@ int lime_grouped_match_schedule_f32(const float* kp, const float* g, const float
                                     const float* remaining, const int64_t* offsets, const int32_t* index, int64_t n, const int32_t* occ,
                                     int64_t n_occ, float* logits, int64_t G, int64_t P, int32_t S, int32_t H, int32_t A, int32_t D,
                                     float scale, float alpha_s, float beta_s, int32_t use_weight, int32_t use_penalty, void* stream);
+/* what lime_grouped_match_explain_f32 ranks the history slots of a pair by */
+enum { LIME_EXPLAIN_BY_CONTRIBUTION = 0, LIME_EXPLAIN_BY_ATTENTION = 1 };
+int lime_grouped_match_explain_f32(const float* kp, const float* g, const float* qp, const float* cand, const float* qt, const float* ct,
+                                   const float* remaining, const int64_t* offsets, const int32_t* index, int64_t n, const int32_t* occ,
+                                   int64_t n_occ, const uint8_t* mask, int32_t hist_div, int32_t m, int32_t by, float* logits, float* base,
+                                   float* weight, float* attn, float* contrib, int32_t* top_slot, float* top_value, int64_t G, int64_t P,
+                                   int32_t H, int32_t A, int32_t D, float scale, float alpha_s, float beta_s, int32_t use_weight,
+                                   int32_t use_penalty, void* stream);
 int64_t lime_topk_rows_workspace(int64_t U, int64_t C);
 int lime_topk_rows_f32(const float* scores, int64_t ld, int64_t U, int64_t C, int32_t k, int32_t* positions, float* top_scores,
                        float* workspace, int64_t workspace_floats, void* stream);

@@ -719,6 +719,38 @@ class Model(nn.Module):
                                        calibrate_by=calibrate_by, calibrate_alpha=calibrate_alpha, calibrate_weights=calibrate_weights)
 
     @torch.no_grad()
+    def explain_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                      cand_freshness, cand_lifetime, top=3, by='contribution', dense=False, n_src=None, pairs_per_pass=1 << 18):
+        """Why each pair of ``score_lists`` (same arguments) scores what it scores -> ``serving.Explanation``(score [P], base [P],
+        weight [P], slots int32 [P, top], values [P, top], attention [P, H] or None, contribution [P, H] or None), in the caller's
+        pair order.  The model's score is a sum over the reader's history slots times the remaining-lifetime weight,
+            score = (sum_h attention[h] (g[h] . candidate)) weight = sum_h contribution[h],
+        so the explanation is exact, not a surrogate: ``score_lists``' plan, passes, user side and candidate tables, and a last launch
+        that keeps the terms it sums (lime_grouped_match_explain_f32; ``recommend.explain_pairs`` states it on the host).  ``score`` has
+        ``score_lists``' bits under the CROWN user encoder; under ATT / MHSA the pooled user vector sum_h beta[h] x[h] is taken apart
+        the same way (attention = beta, the pool's weights; the sum runs in another order, so the score agrees to fp32 rounding).
+        Under MHSA x[h] is the self-attended row of slot h: a contribution belongs to the click in the context of the others.
+
+        ``slots``: the ``top`` history slots of largest contribution (``by`` 'contribution') or attention ('attention'), best first,
+        ties lower slot first, among the slots ``hist_mask`` marks -- ``hist_index[u, slot]`` is the clicked news --, -1 (value 0)
+        behind the last one; the attention itself is not masked, as in the reference.  ``dense``: the [P, H] terms as well.
+        Refused (ValueError, before any launch): ``top`` outside 1 .. min(16, H), an unknown ``by``, ``by`` 'contribution' under the
+        MLP click predictor (behind its ReLU the logit is no sum over the slots; 'attention' is served, with contribution None, weight
+        1 and score = base from the existing MLP match), CNE, and everything ``score_lists`` refuses."""
+        return serving.explain_lists(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                                     cand_freshness, cand_lifetime, top, by, dense, n_src, pairs_per_pass)
+
+    @torch.no_grad()
+    def explain(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
+                positions, top=3, by='contribution', dense=False, n_src=None, pairs_per_pass=1 << 18):
+        """``explain_lists`` for a slate: ``positions`` int [U, k] are the positions into ``cand_index`` that ``recommend`` returned
+        for the same pool arguments (or one slot of ``recommend_schedule``'s, with that slot's offset added to ``cand_freshness``)
+        -> the same record shaped [U, k, ...].  ``score`` has the bits of ``recommend``'s scores (``n_src`` defaults as there); an
+        unfilled entry (-1) comes back as score -inf, slots -1."""
+        return serving.explain(self, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness,
+                               cand_lifetime, positions, top, by, dense, n_src, pairs_per_pass)
+
+    @torch.no_grad()
     def evaluate_slates(self, behaviors, indices, labels, settings, k=10, **kw):
         """``util.evaluate_slates_on_device`` of this model: the dev split scored once, then every selection setting of ``settings``
         (``recommend_lists``' ``max_per_topic`` / ``mmr_lambda`` ..) evaluated on those scores -- nDCG@k, RR, hit, recall against

@@ -5,6 +5,7 @@ and streams only -- every wrapper launches hand-written HIP kernels and nothing 
 2-D operands may be row-strided views (``stride(1) == 1``); the row stride is passed as the leading
 dimension, so slices like ``qkv[:, 300:600]`` or ``fused[:, 900:]`` cost nothing.
 """
+import collections
 import ctypes
 import math
 import os
@@ -1010,6 +1011,48 @@ def grouped_match(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta
                                                  _p(index), n, _p(logits), G, P, H, A, D, scale, alpha, beta, int(use_weight),
                                                  int(use_penalty), _stream()), 'lime_grouped_match_indexed_f32')
     return logits
+
+
+PairTerms = collections.namedtuple('PairTerms', 'logits base weight attn contrib top_slot top_value')
+EXPLAIN_BY = {'contribution': _lib.CONSTANTS['LIME_EXPLAIN_BY_CONTRIBUTION'], 'attention': _lib.CONSTANTS['LIME_EXPLAIN_BY_ATTENTION']}
+
+
+def grouped_match_explain(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False,
+                          mask=None, hist_div=1, m=3, by='contribution', dense=True, index=None, n=None, occ=None, qt=None, ct=None,
+                          n_occ=None):
+    """``lime_grouped_match_explain_f32``: ``grouped_match`` with its terms kept -> PairTerms(logits [P] -- the bits of
+    ``grouped_match`` on the same operands, in each of its three forms --, base [P], weight [P], attn [P, H], contrib [P, H],
+    top_slot int32 [P, m], top_value [P, m]).  attn = softmax_h(s), contrib[p, h] = attn[p, h] (g[i, h] . cand[p]) weight[p], so a
+    row of contrib sums to its logit; ``dense`` off: attn and contrib are not written (None).  top_slot / top_value: the m slots of
+    largest contrib (``by`` 'contribution') or attn ('attention') among those whose byte of ``mask`` (bool / uint8
+    [ceil(G / hist_div), H]; group i reads row i // hist_div; None: every slot) is set, larger first, equal values lower slot first,
+    -1 / 0.0 behind the last eligible one (``recommend.explain_pairs`` states all of it on the host).  1 <= m <= min(16, H).
+    Pairs outside every group keep what ``torch.empty`` gave them."""
+    lib = _lib.load()
+    if by not in EXPLAIN_BY:
+        raise ValueError("by must be 'contribution' or 'attention', got %r" % (by,))
+    G, P, A, D, index, n, composed = _grouped_operands(kp, g, qp, cand, ('kp', 'g', 'qp', 'cand'), H, index, n, (occ, qt, ct, n_occ))
+    if composed:
+        occ, n_occ = _occurrence_tables(index, occ, ((qt, 'qt', A), (ct, 'ct', D)), n_occ)
+    _vec(offsets, 'offsets', G + 1, dtype=torch.int64)
+    if use_weight:
+        remaining = _vec(remaining.contiguous(), 'remaining', P)
+    hist_div, m = int(hist_div), int(m)
+    if hist_div < 1:
+        raise ValueError('hist_div must be >= 1, got %d' % hist_div)
+    mk = _mask_u8(mask, 'mask')
+    if mk is not None and mk.numel() != (G + hist_div - 1) // hist_div * H:
+        raise ValueError('mask must be [ceil(G / hist_div), H] = [%d, %d], got %s' % ((G + hist_div - 1) // hist_div, H, tuple(mask.shape)))
+    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=kp.device)
+    out = PairTerms(new((P,)), new((P,)), new((P,)), new((P, H)) if dense else None, new((P, H)) if dense else None,
+                    new((P, max(m, 0)), torch.int32), new((P, max(m, 0))))
+    check(lib.lime_grouped_match_explain_f32(_p(kp), _p(g), _p(qp), _p(cand), _p(qt) if composed else None, _p(ct) if composed else None,
+                                             _p(remaining) if use_weight else None, _p(offsets), _p(index), n if index is not None else 0,
+                                             _p(occ) if composed else None, n_occ if composed else 0, _p(mk), hist_div, m, EXPLAIN_BY[by],
+                                             _p(out.logits), _p(out.base), _p(out.weight), _p(out.attn), _p(out.contrib), _p(out.top_slot),
+                                             _p(out.top_value), G, P, H, A, D, scale, alpha, beta, int(use_weight), int(use_penalty),
+                                             _stream()), 'lime_grouped_match_explain_f32')
+    return out
 
 
 def grouped_match_schedule_fits(H, n_occ):

@@ -561,3 +561,92 @@ def slate_metrics(positions, k, offsets, news, labels=None, skip=None, value=Non
     counts = np.array([s.sum() for s in sets], dtype=np.int64)
     sums = np.array([per[sets[0 if c < 4 else 1 if c == 4 else 2], c].sum() for c in range(8)], dtype=np.float64)
     return per, status, sums, counts
+
+
+# ---- explanations (Model.explain_lists / Model.explain): the score of a pair as a sum over the reader's history slots -------------------
+EXPLAIN_BY = ('contribution', 'attention')
+EXPLAIN_MAX_TOP = 16                  # lime_grouped_match_explain_f32's slots per pair
+PairExplanation = collections.namedtuple('PairExplanation', 'logits base weight attn contrib top_slot top_value')
+
+
+def lifetime_weight(remaining, alpha, beta, use_weight, use_penalty):
+    """The remaining-lifetime weight (util.py:23-49) in fp64: 1 with ``use_weight`` off; sigmoid(alpha r), times beta where r < 0,
+    with the expired penalty; sigmoid(alpha |r|) without."""
+    r = np.asarray(remaining, dtype=np.float64)
+    if not use_weight:
+        return np.ones_like(r)
+    with np.errstate(over='ignore'):
+        if use_penalty:
+            w = 1.0 / (1.0 + np.exp(-float(alpha) * r))
+            return np.where(r >= 0, w, float(beta) * w)
+        return 1.0 / (1.0 + np.exp(-float(alpha) * np.abs(r)))
+
+
+def top_slots(values, eligible, m):
+    """The selection rule of an explanation -> (top_slot int32 [P, m], top_value [P, m] in ``values``' dtype): per row of ``values``
+    [P, H] the m slots of largest value among those ``eligible`` (bool [P, H]) -- larger value first; equal values (+0.0 == -0.0)
+    lower slot first; a NaN behind every number (``walk_order``'s rule, in the values' own precision) --, and the value at each.
+    Fewer than m eligible slots: the tail holds -1 / 0."""
+    values = np.asarray(values)
+    eligible = np.asarray(eligible).astype(bool)
+    P, H = values.shape
+    m = int(m)
+    slot = np.full((P, m), -1, dtype=np.int32)
+    top = np.zeros((P, m), dtype=values.dtype)
+    for p in range(P):
+        nan = np.isnan(values[p])
+        order = np.argsort(-(np.where(nan, 0, values[p]) + 0.0), kind='stable')             # -0.0 + 0.0 = +0.0: the zeros tie
+        order = order[np.argsort(nan[order], kind='stable')]
+        order = order[eligible[p][order]][:m]
+        slot[p, :order.size] = order
+        top[p, :order.size] = values[p, order]
+    return slot, top
+
+
+def explain_pairs(kp, g, qp, cand, remaining, offsets, H, scale, alpha=0.0, beta=0.0, use_weight=False, use_penalty=False, mask=None,
+                  hist_div=1, m=3, by='contribution', index=None, occ=None, qt=None, ct=None):
+    """The host statement of ``ops.grouped_match_explain`` (lime_grouped_match_explain_f32), in fp64 -> PairExplanation.
+
+    kp [G H, A], g [G H, D] per group; offsets [G + 1]: the pairs of group i are rows offsets[i] .. offsets[i + 1] - 1 (every offset
+    clamped into [0, P]).  The pair's own operands: rows qp[p], cand[p]; with ``index`` [P] rows index[p] of the tables qp, cand
+    (clamped into the tables); with ``occ`` [P], ``qt`` and ``ct`` besides, those rows plus rows occ[p] of qt, ct (clamped).  Per pair:
+        s[h] = kp[i, h] . qp * scale     attn = softmax_h(s) -- UNMASKED --     m[h] = g[i, h] . cand
+        base = sum_h attn[h] m[h]     weight = w(remaining[p]) (``lifetime_weight``)     logits = base weight
+        contrib[h] = attn[h] m[h] weight                    so that       sum_h contrib[h] = logits
+    and top_slot / top_value [P, m]: ``top_slots`` of contrib (``by`` 'contribution') or attn ('attention') among the slots h with
+    mask[i // hist_div, h] set (mask [ceil(G / hist_div), H]; None: all).  A pair outside every group holds zeros and slots -1."""
+    if by not in EXPLAIN_BY:
+        raise ValueError("by must be 'contribution' or 'attention', got %r" % (by,))
+    H, m, hist_div = int(H), int(m), int(hist_div)
+    if not 1 <= m <= min(EXPLAIN_MAX_TOP, H) or hist_div < 1:
+        raise ValueError('explain_pairs names 1 <= m <= min(%d, H = %d) slots with hist_div >= 1, got m = %d, hist_div = %d'
+                         % (EXPLAIN_MAX_TOP, H, m, hist_div))
+    f64 = lambda t: np.asarray(t, dtype=np.float64)
+    kp, g, qp, cand = f64(kp), f64(g), f64(qp), f64(cand)
+    if (occ is None) != (qt is None) or (occ is None) != (ct is None) or (occ is not None and index is None):
+        raise ValueError('the occurrence-composed form takes index, occ, qt and ct together')
+    if index is not None:
+        at = np.clip(np.asarray(index).reshape(-1).astype(np.int64), 0, qp.shape[0] - 1)
+        qp, cand = qp[at], cand[at]
+        if occ is not None:
+            z = np.clip(np.asarray(occ).reshape(-1).astype(np.int64), 0, f64(qt).shape[0] - 1)
+            qp, cand = qp + f64(qt)[z], cand + f64(ct)[z]
+    P, G = qp.shape[0], kp.shape[0] // H
+    off = np.clip(np.asarray(offsets).reshape(-1).astype(np.int64), 0, P)
+    weight = lifetime_weight(np.zeros(P) if remaining is None else f64(remaining).reshape(-1), alpha, beta, use_weight, use_penalty)
+    attn, contrib, base = np.zeros((P, H)), np.zeros((P, H)), np.zeros(P)
+    eligible = np.zeros((P, H), dtype=bool)
+    mask = None if mask is None else np.asarray(mask).reshape(-1, H) != 0
+    for i in range(G):
+        lo, hi = off[i], max(off[i], off[i + 1])
+        if hi == lo:
+            continue
+        s = qp[lo:hi] @ kp[i * H:(i + 1) * H].T * float(scale)                                  # [n, H]
+        e = np.exp(s - s.max(axis=1, keepdims=True))
+        attn[lo:hi] = e / e.sum(axis=1, keepdims=True)
+        terms = attn[lo:hi] * (cand[lo:hi] @ g[i * H:(i + 1) * H].T)
+        base[lo:hi] = terms.sum(axis=1)
+        contrib[lo:hi] = terms * weight[lo:hi, None]
+        eligible[lo:hi] = True if mask is None else mask[i // hist_div]
+    slot, top = top_slots(contrib if by == 'contribution' else attn, eligible, m)
+    return PairExplanation(base * weight, base, weight, attn, contrib, slot, top)

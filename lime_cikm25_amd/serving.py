@@ -165,6 +165,14 @@ def pass_logits(model, news_cache, operands, cands, pick, group_offsets):
     one of ``cands``' per-pair tensors; group_offsets int64 [groups + 1]: the groups' CSR over the pass's pairs, on the device or still
     on the host (the copy waits for the stream, so it stands behind the launches that do not read it).  Without tables a row is
     materialised per pair; with them the pair's table row is read in place and, for a LIME model, composed with its bucket pair's."""
+    cand, at, occ, remaining = pass_candidates(model, news_cache, cands, pick)
+    return click_logits(model, operands, cand, remaining, torch.as_tensor(group_offsets, device=news_cache.device),
+                        tables=cands.tables, index=at, occ=occ)
+
+
+def pass_candidates(model, news_cache, cands, pick):
+    """The candidate side of one pass -> (cand [pairs, D] or None, index int32 [pairs] or None, occ or None, remaining): without
+    tables a row is materialised per pair; with them the pair's table row is named and, for a LIME model, its bucket pair's."""
     ne, tables = model.news_encoder, cands.tables
     per_slot = (-1,) if cands.slots is None else (cands.slots, -1)
     cand = at = occ = None
@@ -174,8 +182,7 @@ def pass_logits(model, news_cache, operands, cands, pick, group_offsets):
         at = newsEncoders._i32(pick(cands.position).reshape(-1)).contiguous()                 # int32 [pairs]: the pair's table row
         if tables.occurrence is not None:
             occ = ne.occurrence_ids_schedule(pick(cands.freshness).reshape(cands.slots or 1, -1), pick(cands.lifetime)).reshape(per_slot)
-    return click_logits(model, operands, cand, pick(cands.remaining).reshape(per_slot), torch.as_tensor(group_offsets, device=news_cache.device),
-                        tables=tables, index=at, occ=occ)
+    return cand, at, occ, pick(cands.remaining).reshape(per_slot)
 
 
 def score_pool(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
@@ -457,6 +464,34 @@ def _top_rows(scores, gone, quota, cand_index, k):
 def score_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
                 cand_lifetime, n_src, pairs_per_pass, exclude_history, k=None):
     """score_lists -> (scores [P], the offsets on the device, bool [P] "excluded" or None): the passes over ops.list_plan's plan."""
+    dev = news_cache.device
+    call = list_call(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                     cand_freshness, cand_lifetime, n_src, pairs_per_pass, k)
+    if call.passes is None:
+        return torch.empty((0,), dtype=torch.float32, device=dev), call.offsets, None
+    out = torch.empty((cand_index.numel(),), dtype=torch.float32, device=dev)
+    for t in call.passes:
+        operands = pass_operands(model, call.users, t.u0, t.u1, t.slots, t.category, t.subCategory,
+                                 pairs=t.rows.numel() if call.cands.tables is None else None)
+        out.index_copy_(0, t.rows, pass_logits(model, news_cache, operands, call.cands, lambda x: x[t.rows], t.group_offsets))
+    gone = _in_own_history(hist_index.to(dev), hist_mask.to(dev), call.offsets, call.cands.index) if exclude_history else None
+    if exclude_history:
+        out.masked_fill_(gone, float('-inf'))
+    return out, call.offsets, gone
+
+
+# A call over per-user lists, behind its host checks: the lists' offsets on the device, what every pass reads of the users and of the
+# candidates, and the passes (None: no pair at all) -- each ListPass the users u0:u1 with ``slots`` groups each, the pass's pairs in
+# group order (``rows`` into the call's [P] arrays), their groups' CSR and the topic (category, subCategory [groups, 1]) of every group.
+ListCall = collections.namedtuple('ListCall', 'offsets users cands passes')
+ListPass = collections.namedtuple('ListPass', 'u0 u1 slots rows group_offsets category subCategory')
+
+
+def list_call(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
+              cand_lifetime, n_src, pairs_per_pass, k=None):
+    """What ``score_lists`` and ``explain_lists`` share: the host refusals, the plan of the lists (ops.list_plan), the once-per-call
+    user side and candidate tables, and the passes over the plan -> ListCall (``passes`` a generator: a pass with fewer slots than
+    the call plans itself when it is reached)."""
     import numpy as np
     from .device_data import topic_table_of
     P = cand_index.numel()
@@ -479,7 +514,7 @@ def score_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness
     dev = news_cache.device
     offsets = torch.from_numpy(off).to(dev)
     if P == 0:
-        return torch.empty((0,), dtype=torch.float32, device=dev), offsets, None
+        return ListCall(offsets, None, None, None)
     topic_of_news, cat_t, sub_t = topic_table_of(corpus, model.grouped_by())
     if cat_t.numel() > rec.MAX_TOPICS:
         raise ValueError('the corpus has %d topics, lime_list_plan groups up to %d' % (cat_t.numel(), rec.MAX_TOPICS))
@@ -492,25 +527,21 @@ def score_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness
     users = user_side(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, n_src, P)
     tables = model._candidate_tables(news_cache)                  # (a baseline model: the cache itself, and Q of every news once)
     cands = Candidates(cidx, fresh, life, remaining, tables, cidx, None)           # (a pair's table row is its news id)
-    out = torch.empty((P,), dtype=torch.float32, device=dev)
-    for u0, u1, S_pass in rec.list_passes(off, plan.n_distinct, H, int(pairs_per_pass)):
-        p0, p1 = int(off[u0]), int(off[u1])
-        if p1 == p0:
-            continue
-        if S_pass == S:                                                           # the pass's plan is a slice of the call's
-            rows, goff, skey = plan.order[p0:p1], plan.group_offsets[u0 * S:u1 * S + 1] - p0, plan.slot_key[u0 * S:u1 * S]
-        else:                                                                     # fewer slots suffice: no slot count is read again
-            sub = ops.list_plan(keys[p0:p1], offsets[u0:u1 + 1] - p0, slots=S_pass, n_keys=cat_t.numel(),
-                                n_distinct=plan.n_distinct[u0:u1])
-            rows, goff, skey = sub.order + p0, sub.group_offsets, sub.slot_key
-        skey = skey.long()
-        operands = pass_operands(model, users, u0, u1, S_pass, cat_t[skey].view(-1, 1), sub_t[skey].view(-1, 1),
-                                 pairs=p1 - p0 if tables is None else None)
-        out.index_copy_(0, rows, pass_logits(model, news_cache, operands, cands, lambda t: t[rows], goff.contiguous()))
-    gone = _in_own_history(hist_index.to(dev), hist_mask.to(dev), offsets, cidx) if exclude_history else None
-    if exclude_history:
-        out.masked_fill_(gone, float('-inf'))
-    return out, offsets, gone
+
+    def passes():
+        for u0, u1, S_pass in rec.list_passes(off, plan.n_distinct, H, int(pairs_per_pass)):
+            p0, p1 = int(off[u0]), int(off[u1])
+            if p1 == p0:
+                continue
+            if S_pass == S:                                                       # the pass's plan is a slice of the call's
+                rows, goff, skey = plan.order[p0:p1], plan.group_offsets[u0 * S:u1 * S + 1] - p0, plan.slot_key[u0 * S:u1 * S]
+            else:                                                                 # fewer slots suffice: no slot count is read again
+                sub = ops.list_plan(keys[p0:p1], offsets[u0:u1 + 1] - p0, slots=S_pass, n_keys=cat_t.numel(),
+                                    n_distinct=plan.n_distinct[u0:u1])
+                rows, goff, skey = sub.order + p0, sub.group_offsets, sub.slot_key
+            skey = skey.long()
+            yield ListPass(u0, u1, S_pass, rows, goff.contiguous(), cat_t[skey].view(-1, 1), sub_t[skey].view(-1, 1))
+    return ListCall(offsets, users, cands, passes())
 
 
 def _in_own_history(hist_index, hist_mask, offsets, cidx, pairs_per_step=1 << 18):
@@ -576,3 +607,138 @@ def _top_segments(scores, offsets, gone, quota, cand_index, k):
     if gone is not None:
         positions = _without(positions, gone[(offsets[:-1].unsqueeze(1) + positions.clamp(min=0).long()).clamp(max=scores.numel() - 1)])
     return positions, top
+
+
+# ---- explanations: why a news is in the slate (Model.explain_lists / Model.explain) ----------------------------------------------------
+# Per pair, in the caller's order: score [P] (what ``score_lists`` gives the pair), base and weight [P] (score = base weight: the
+# match before the remaining-lifetime weight, and that weight), slots int32 / values fp32 [P, top] (positions into the user's history
+# row, best first, -1 / 0 behind the last masked-in one), attention / contribution fp32 [P, H] or None.
+Explanation = collections.namedtuple('Explanation', 'score base weight slots values attention contribution')
+
+
+def check_explain(model, hist_index, top, by):
+    """The refusals of ``top`` / ``by`` (ValueError, before any launch and before the shared checks), behind CNE's."""
+    if model.reads_content_mask:
+        raise ValueError(model._NO_CONTENT_CACHE)
+    if by not in rec.EXPLAIN_BY:
+        raise ValueError("by must be 'contribution' or 'attention', got %r" % (by,))
+    if by == 'contribution' and model.click_predictor == 'mlp':
+        raise ValueError("by='contribution' needs the dot-product click predictor: behind the MLP predictor's ReLU the logit is no sum "
+                         "over the history slots -- by='attention' is served")
+    H = hist_index.shape[1] if isinstance(hist_index, torch.Tensor) and hist_index.dim() == 2 else None     # (else check_grouped's to refuse)
+    most = rec.EXPLAIN_MAX_TOP if H is None else min(rec.EXPLAIN_MAX_TOP, H)
+    if isinstance(top, bool) or not isinstance(top, numbers.Integral) or not 1 <= top <= most:
+        raise ValueError('top must be an integer in 1 .. min(%d, H)%s, got %r' % (rec.EXPLAIN_MAX_TOP, '' if H is None else ' = %d' % most, top))
+
+
+def _first_one(rows, device):
+    """[rows, 4] rows (1, 0, 0, 0): the pair's side of a score that sits in column 0 of kp."""
+    q = torch.zeros((rows, 4), dtype=torch.float32, device=device)
+    q[:, 0] = 1.0
+    return q
+
+
+def explain_operands(model, users, u0, u1, slots, category, subCategory, pairs=None):
+    """``pass_operands`` with the history slots kept apart -> Operands over H rows per group, whichever the user encoder.  CROWN: the
+    operands of the match as they are.  ATT / MHSA: the user vector is the additive pool sum_h beta[h] x[h], so g = x, the rows
+    ``_pool_inputs`` pools; kp [G H, 4] holds the pool's logit affine2 . hidden[h] in column 0 and zeros behind it, and a pair's qp is
+    (1, 0, 0, 0) with scale 1: the match's softmax IS beta, and its per-slot term beta[h] (x[h] . cand).  Under MHSA x[h] is the
+    self-attended row of slot h -- a term belongs to the click in the context of the others."""
+    ue = model.user_encoder
+    if hasattr(ue, 'user_node_embedding'):
+        return pass_operands(model, users, u0, u1, slots, category, subCategory, pairs=pairs)
+    H = users.hist.shape[1]
+    x, hidden, rows = ue._pool_inputs(users.hist[u0:u1], category, subCategory, users.ucat[u0:u1], users.usub[u0:u1], users.hist_mask[u0:u1],
+                                      None, slots, None if users.gate_y is None else users.gate_y[u0 * H:u1 * H], None)
+    if rows != (u1 - u0) * slots:
+        raise ValueError('the user side gave %d histories for %d groups' % (rows, (u1 - u0) * slots))
+    w = ue.attention.affine2.weight
+    w4 = torch.zeros((4, w.shape[1]), dtype=torch.float32, device=w.device)
+    w4[0] = w[0]
+    return Operands(x, ops.linear(hidden, w4, None), None if pairs is None else _first_one(pairs, x.device), H, 1.0)
+
+
+def explain_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index, cand_freshness,
+                  cand_lifetime, top, by, dense, n_src, pairs_per_pass):
+    """explain_lists -> Explanation: ``score_lists``' plan, passes, user side and candidate tables, with the terms of every pair kept
+    by the last launch (lime_grouped_match_explain_f32).  Under the MLP predictor (``by`` 'attention' alone) the score is the existing
+    MLP match's, weight is 1 and base the score."""
+    check_explain(model, hist_index, top, by)
+    call = list_call(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_offsets, cand_index,
+                     cand_freshness, cand_lifetime, n_src, pairs_per_pass)
+    ue, w, dev = model.user_encoder, model.remaining_lifetime_weighting, news_cache.device
+    (U, H), P, top = hist_index.shape, cand_index.numel(), int(top)
+    crown, mlp = hasattr(ue, 'user_node_embedding'), model.click_predictor == 'mlp'
+    new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+    out = Explanation(new(P), new(P), new(P), new(P, top, dtype=torch.int32), new(P, top), new(P, H) if dense else None,
+                      new(P, H) if dense and not mlp else None)
+    if call.passes is None:
+        return out
+    cands = call.cands
+    tables = cands.tables
+    if tables is not None and not crown:                      # the pooled encoders' score column: (1, 0, 0, 0) + the occurrence's zeros
+        tables = tables._replace(qp=_first_one(tables.cand.shape[0], dev))
+    occurrence = None if tables is None else tables.occurrence
+    mask = hist_mask.to(dev).bool()
+    for t in call.passes:
+        pairs = t.rows.numel() if tables is None else None
+        operands = explain_operands(model, call.users, t.u0, t.u1, t.slots, t.category, t.subCategory, pairs=pairs)
+        cand, at, occ, remaining = pass_candidates(model, news_cache, cands, lambda x: x[t.rows])
+        goff = torch.as_tensor(t.group_offsets, device=dev)
+        if tables is not None:
+            rows_c, qp = tables.cand, tables.qp
+        else:
+            rows_c, qp = cand, operands.qp if operands.qp is not None else ops.linear(cand, ue.Q.weight, ue.Q.bias)
+        composed = dict(occ=occ, qt=occurrence.qt, ct=occurrence.ct) if occurrence is not None else {}
+        terms = ops.grouped_match_explain(operands.kp, operands.g, qp, rows_c, remaining, goff, operands.H, operands.scale, w.alpha, w.beta,
+                                          bool(w.use_remaining_lifetime_weighting) and not mlp, bool(w.use_expired_penalty),
+                                          mask=mask[t.u0:t.u1].contiguous(), hist_div=t.slots, m=top, by=by, dense=dense, index=at, **composed)
+        if mlp:                                               # the score is the existing MLP match's, on ITS operands
+            scored = operands if crown else pass_operands(model, call.users, t.u0, t.u1, t.slots, t.category, t.subCategory, pairs=pairs)
+            score = click_logits(model, scored, cand, remaining, goff, tables=cands.tables, index=at, occ=occ)
+            terms = terms._replace(logits=score, base=score, weight=torch.ones_like(score), contrib=None)
+        for dst, src in zip(out, (terms.logits, terms.base, terms.weight, terms.top_slot, terms.top_value, terms.attn, terms.contrib)):
+            if dst is not None:
+                dst.index_copy_(0, t.rows, src)
+    return out
+
+
+def explain(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, cand_index, cand_freshness, cand_lifetime,
+            positions, top, by, dense, n_src, pairs_per_pass):
+    """explain -> Explanation shaped [U, k, ...]: ``explain_lists`` over the lists that ``positions`` int [U, k] (``recommend``'s, or a
+    slot of ``recommend_schedule``'s at that slot's freshness) name in the pool, unfilled entries (-1) left out of them and returned as
+    score -inf, base -inf, weight 1, slots -1, zeros elsewhere.  ``n_src`` defaults as in ``score_pool``, so a score has its bits."""
+    check_explain(model, hist_index, top, by)
+    if not isinstance(hist_index, torch.Tensor) or hist_index.dim() != 2:
+        raise ValueError('hist_index must be [U, H], got %s' % (tuple(getattr(hist_index, 'shape', ())),))
+    (U, H), C, dev, ue = hist_index.shape, cand_index.numel(), news_cache.device, model.user_encoder
+    if cand_index.dim() != 1 or C < 1:
+        raise ValueError('cand_index must be [C] with C >= 1 -- ONE pool for all users -- got %s' % (tuple(cand_index.shape),))
+    if (not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[0] != U
+            or positions.dtype not in (torch.int32, torch.int64)):
+        raise ValueError('positions must be the int [U, k] = [%d, k] positions into the pool that recommend returned, got %s'
+                         % (U, '%s %s' % (positions.dtype, tuple(positions.shape)) if isinstance(positions, torch.Tensor) else repr(positions)))
+    for t, name in ((cand_freshness, 'cand_freshness'), (cand_lifetime, 'cand_lifetime')):
+        if tuple(t.shape) not in ((C,), (U, C)):
+            raise ValueError('%s must be [C] = [%d] or [U, C] = [%d, %d], got %s' % (name, C, U, C, tuple(t.shape)))
+    pos = positions.to(dev).long()
+    k = pos.shape[1]
+    filled = (pos >= 0) & (pos < C)
+    u_of, j_of = filled.nonzero(as_tuple=True)                # user-major, slot order: the lists one behind the other
+    at = pos[u_of, j_of]
+    off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), filled.sum(dim=1).cumsum(0)])
+    fresh, life = (t.to(dev).float().expand(U, C)[u_of, at] for t in (cand_freshness, cand_lifetime))
+    if n_src is None and hasattr(ue, 'user_node_embedding'):
+        n_src = min(U * C, H + ue.user_node_embedding.shape[0])
+    ex = explain_lists(model, news_cache, corpus, hist_index, hist_mask, user_freshness, user_lifetime, off, cand_index.to(dev)[at], fresh,
+                       life, top, by, dense, n_src, pairs_per_pass)
+    fills = (float('-inf'), float('-inf'), 1.0, -1, 0.0, 0.0, 0.0)
+    whole = []
+    for part, fill in zip(ex, fills):
+        if part is None:
+            whole.append(None)
+            continue
+        full = torch.full((U, k) + tuple(part.shape[1:]), fill, dtype=part.dtype, device=dev)
+        full[u_of, j_of] = part
+        whole.append(full)
+    return Explanation(*whole)
